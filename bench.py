@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- physics steps/s of the particle step on MI355X (BASELINE.json metric).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
   N > 1 either under a launcher (python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N:
   RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* come from the environment) or bare: `python bench.py --gpus N` then
   starts its own N ranks -- child processes, spawned BEFORE this process makes any GPU call -- one cuda:<local_rank>
@@ -14,9 +14,14 @@ that is already resident in HBM when the timed region starts.  Default workload 
 configs[1]: 1M particles, gravity off, the reference's 3048 x 1048 world.  The 100M-particle
 configuration (configs[2]) is measured in the same run and reported under "extra_workloads".
 
-`value` is what a long-lived host sees: the K-step windows follow each other from step W of the run until 2000
-steps have been timed (re-sorts and radix sorts inside), value = all timed steps / all timed seconds.  The figure
-of a fresh cloud (the same K steps restarted from a snapshot, as rounds 1-3 reported) is `value_fresh_cloud`.
+`value` times exactly K steps of the run, from step W on, as one window (the re-sort every 240 steps of the run and
+any radix sort a step needs fall inside it): value = K / timed seconds, `ms_per_step` = timed milliseconds / K.  The
+figure of a fresh cloud (the same K steps restarted from a snapshot, as rounds 1-3 reported) is `value_fresh_cloud`.
+
+--dump-outputs DIR (N = 1): after the timed steps, what the last of them left for a caller of the step -- positions,
+previous positions and radii in the library's order -- goes to DIR/<name>.npy (float32).  The scene is seeded, so the
+same arguments give the same inputs on every run and two builds can be compared output for output.  Above 64 MB in
+all, every array keeps the same seeded sample of rows, whose indices are DIR/sample_rows.npy (float64).
 
 One JSON line on stdout (rank 0).  `roofline` prices the dominant kernel: algorithmic bytes per launch
 ("Kernels and rooflines") / its mean launch time from hipEvent pairs recorded on the
@@ -39,10 +44,10 @@ ALGO_BYTES_PER_PARTICLE = 148    # hash 12 + sort 68 + grid 8 + 
 RESORT_EVERY = 240               # 4 s at 60 Hz (particle_system.rs:13-14)
 PROFILE_EVERY = 10               # kernels of every 10th timed step are bracketed by HIP events (an event pair
                                  # per kernel on every step costs ~35% at 1M particles)
-HEADLINE_STEPS = 2000            # the K-step windows FOLLOW each other until this many steps of the run have been timed
-MAX_HEADLINE_SECONDS = 20.0      # ... or this much time (big particle counts); `value` = all timed steps / all timed seconds
+MAX_HEADLINE_SECONDS = 20.0      # restored (fresh-cloud) windows stop after this much time at most (big particle counts)
 FRESH_SECONDS = 0.25             # N = 1: afterwards, windows restarted from the state after the warm-up (`value_fresh_cloud`)
 MAX_WINDOWS = 400
+DUMP_MAX_BYTES = 64 << 20        # --dump-outputs: at most this much in all (a seeded sample of rows above it)
 
 
 class Schedule:
@@ -64,13 +69,12 @@ class Schedule:
             self.done += c; k -= c
 
 
-def timed_windows(sched, dt, steps, sync, dist, torch, min_seconds=0.0, restore=None, min_steps=0,
-                  max_seconds=MAX_HEADLINE_SECONDS):
+def timed_windows(sched, dt, steps, sync, dist, torch, min_seconds=0.0, restore=None, max_seconds=MAX_HEADLINE_SECONDS):
     """EXACTLY `steps` steps per window, each window bracketed by barrier + synchronize on both sides and reduced
     with MAX over the ranks.  Returns the list of window times (seconds).  Every rank runs the same number of windows
     (the count follows from all-reduced times).
-    restore is None: the windows FOLLOW each other -- the run a long-lived host sees, re-sorts every 240 steps of the
-    run included -- until min_steps steps have been timed (or max_seconds).
+    restore is None: ONE window -- `steps` steps of the run as a long-lived host sees it, the re-sort every 240 steps
+    of the run included.
     restore: called before every window -- puts the system back to the state the first window starts from, so that
     every window times the SAME steps of the run (a cloud without damping relaxes: at 1M the step is 20 % slower after
     4000 steps); repeated until min_seconds have been measured."""
@@ -93,12 +97,9 @@ def timed_windows(sched, dt, steps, sync, dist, torch, min_seconds=0.0, restore=
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             el = float(t.item())
         times.append(el)
-        if len(times) >= MAX_WINDOWS or sum(times) >= max_seconds:
+        if restore is None or len(times) >= MAX_WINDOWS or sum(times) >= max_seconds:
             return times
-        if restore is not None:
-            if sum(times) >= min_seconds:
-                return times
-        elif len(times) * steps >= min_steps:
+        if sum(times) >= min_seconds:
             return times
 
 
@@ -110,6 +111,32 @@ def window_stats(times, steps):
             "median_window_ms": round(med * 1e3, 4),
             "first_window_ms": round(times[0] * 1e3, 4), "min_window_ms": round(min(times) * 1e3, 4),
             "max_window_ms": round(max(times) * 1e3, 4)}
+
+
+def dump_outputs(out_dir, arrays, max_bytes=DUMP_MAX_BYTES, seed=0):
+    """arrays: {name: array with one row per particle, the same number of rows in all}.  Writes out_dir/<name>.npy
+    as float32 (float64 stays float64).  Above max_bytes in all, every array keeps the same rows, a sample drawn
+    with `seed` (sorted), and out_dir/sample_rows.npy (float64) holds their indices.  Returns the names written."""
+    import numpy as np
+    arrays = {k: np.asarray(v) for k, v in arrays.items()}
+    arrays = {k: v if v.dtype == np.float64 else v.astype(np.float32) for k, v in arrays.items()}
+    rows = {len(v) for v in arrays.values()}
+    assert len(rows) == 1, "arrays of different lengths: %s" % {k: v.shape for k, v in arrays.items()}
+    n = rows.pop()
+    total = sum(v.nbytes for v in arrays.values())
+    if total > max_bytes:
+        per_row = total // max(1, n) + 8                        # + its float64 index
+        room = max_bytes - 256 * (len(arrays) + 1)               # the .npy headers
+        keep = np.sort(np.random.default_rng(seed).choice(n, room // per_row, replace=False))
+        arrays = {k: v[keep] for k, v in arrays.items()}
+        arrays["sample_rows"] = keep.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    stale = os.path.join(out_dir, "sample_rows.npy")            # left by an earlier, sampled dump
+    if "sample_rows" not in arrays and os.path.exists(stale):
+        os.remove(stale)
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), np.ascontiguousarray(v))
+    return sorted(arrays)
 
 
 def log(*a):
@@ -130,7 +157,7 @@ def parse():
     ap.add_argument("--no-extra", action="store_true", help="skip the 100M-particle extra workload")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--single-window", action="store_true",
-                    help="time ONE window of --steps steps (profiler runs: scripts/gpu_profile_r03.sh)")
+                    help="no fresh-cloud windows after the timed steps (profiler runs: scripts/gpu_profile_r03.sh)")
     ap.add_argument("--extra-particles", type=int, default=100_000_000)
     ap.add_argument("--extra-steps", type=int, default=250,
                     help="timed steps of the 100M legs (the re-sort at step 240 falls inside the window)")
@@ -139,6 +166,9 @@ def parse():
     ap.add_argument("--rehearse", action="store_true",
                     help="launcher rehearsal on CPU (gloo): ranks join, run the timing protocol around an empty loop, "
                          "print a line marked rehearsal -- no GPU, no physics, never a result")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="N = 1: write what the last timed step left (positions, previous positions, radii) to "
+                         "DIR/<name>.npy, float32, at most 64 MB in all")
     return ap.parse_args()
 
 
@@ -170,11 +200,12 @@ def kernel_rooflines(timings, n_particles, mode):
     return out
 
 
-def run_workload(gpe, torch, dist, rank, world_size, n, steps, warmup, mode, gravity, device, headline_steps=HEADLINE_STEPS,
-                 fresh_seconds=0.0, tail=()):
-    """Returns (mean seconds per `steps` steps over the timed windows, max over ranks; timings dict of rank 0; world;
-    window statistics; pipeline info; fresh-cloud statistics or None; tail marks).
-    The windows follow each other from step `warmup` of the run on (headline_steps in all; 0: one window).
+def run_workload(gpe, torch, dist, rank, world_size, n, steps, warmup, mode, gravity, device,
+                 fresh_seconds=0.0, tail=(), outputs=False):
+    """Returns (seconds of the timed window of `steps` steps, max over ranks; timings dict of rank 0; world;
+    window statistics; pipeline info; fresh-cloud statistics or None; tail marks; outputs or None).
+    The window starts at step `warmup` of the run.
+    outputs: the arrays a caller of the step receives after the last timed step, {name: host array}.
     fresh_seconds > 0: afterwards the state after `warmup` steps is put back again and again and the same `steps` steps
     are timed for that long -- the figure of rounds 1-3 (no radix sort inside a window, freshly written rosters).
     tail: after the windows, the run goes on to each of these step marks; ms/step of every stretch is reported."""
@@ -202,10 +233,13 @@ def run_workload(gpe, torch, dist, rank, world_size, n, steps, warmup, mode, gra
     st.ctx.sync()
     st.ctx.set_profiling(PROFILE_EVERY)     # HIP-event pairs around the kernels of every k-th step
     st.ctx.reset_timings()
-    times = timed_windows(sched, dt, steps, st.ctx.sync, dist, torch, min_steps=headline_steps)
+    times = timed_windows(sched, dt, steps, st.ctx.sync, dist, torch)
     elapsed = sum(times) / len(times)
     timings = st.ctx.timings()
     pipe = st.ctx.pipeline_info()
+    out = None
+    if outputs:
+        out = {"positions": st.positions(), "previous_positions": st.previous_positions(), "radii": st.radii()}
     marks = []
     for m in tail:                          # the same run, further on (the 100M gravity scene falls and piles up)
         k = m - sched.done
@@ -237,10 +271,10 @@ def run_workload(gpe, torch, dist, rank, world_size, n, steps, warmup, mode, gra
     p = st.positions()
     assert np.isfinite(p).all(), "non-finite positions after the run"
     st.close()
-    return elapsed, timings, world, window_stats(times, steps), pipe, fresh, marks
+    return elapsed, timings, world, window_stats(times, steps), pipe, fresh, marks, out
 
 
-def run_sharded(gpe, torch, dist, rank, world_size, n_per_gpu, steps, warmup, gravity, device, headline_steps=HEADLINE_STEPS):
+def run_sharded(gpe, torch, dist, rank, world_size, n_per_gpu, steps, warmup, gravity, device):
     """N > 1: one shard per GPU (gpu-physics-engine_amd/sharded.py): block ownership, one-block ghost band and
     migration over RCCL point-to-point every step.  Weak scaling: every rank fills its own rectangle of the
     world with n_per_gpu particles at the reference density."""
@@ -272,7 +306,7 @@ def run_sharded(gpe, torch, dist, rank, world_size, n_per_gpu, steps, warmup, gr
     eng.ctx.set_profiling(PROFILE_EVERY)
     eng.ctx.reset_timings()
     st.stats = {"migrants": 0, "ghosts": 0, "steps": 0}
-    times = timed_windows(sched, dt, steps, eng.sync, dist, torch, min_steps=headline_steps)
+    times = timed_windows(sched, dt, steps, eng.sync, dist, torch)
     elapsed = sum(times) / len(times)
     timings = eng.ctx.timings()
     _, p, _ = st.owned()
@@ -574,6 +608,10 @@ def run_soak(gpe, torch, n, mode, device, total=3000, window=100, marks=(250, 50
 
 def main():
     args = parse()
+    if args.steps < 1:
+        raise SystemExit("bench.py: --steps must be at least 1")
+    if args.dump_outputs is not None and args.gpus != 1:
+        raise SystemExit("bench.py: --dump-outputs needs --gpus 1")
     have_launcher_env = "RANK" in os.environ and "WORLD_SIZE" in os.environ
     if args.gpus > 1 and not have_launcher_env:
         raise SystemExit(launch_ranks(args))          # this parent never touches the GPU
@@ -618,14 +656,16 @@ def main():
     shard_info, pipe, fresh = None, None, None
     if world_size > 1:
         elapsed, timings, world, shard_info = run_sharded(gpe, torch, dist, rank, world_size, n, args.steps,
-                                                          args.warmup, args.gravity, local_rank,
-                                                          headline_steps=0 if args.single_window else HEADLINE_STEPS)
+                                                          args.warmup, args.gravity, local_rank)
         wstats = shard_info.pop("windows")
     else:
-        elapsed, timings, world, wstats, pipe, fresh, _ = run_workload(
+        elapsed, timings, world, wstats, pipe, fresh, _, outputs = run_workload(
             gpe, torch, dist, rank, world_size, n, args.steps, args.warmup, args.mode, args.gravity, local_rank,
-            headline_steps=0 if args.single_window else HEADLINE_STEPS,
-            fresh_seconds=0.0 if args.single_window else FRESH_SECONDS)
+            fresh_seconds=0.0 if args.single_window else FRESH_SECONDS, outputs=args.dump_outputs is not None)
+        if outputs is not None:
+            dump_outputs(args.dump_outputs, outputs)
+            log("outputs of the last timed step -> %s" % args.dump_outputs)
+            del outputs
     # The 100M legs, shaped like BASELINE.json configs[2..4]: gravity on, warm-up 10 steps (the first re-sorts),
     # then timed windows with the re-sort every 240 steps of the run INSIDE them.
     extras = []
@@ -636,19 +676,19 @@ def main():
         if world_size > 1:
             per = max(1, ne // world_size)
             log("extra workload: %d particles in all over %d GPUs (%d per GPU), gravity on ..." % (per * world_size, world_size, per))
-            r = run_sharded(gpe, torch, dist, rank, world_size, per, xs, 10, "on", local_rank, headline_steps=0)
+            r = run_sharded(gpe, torch, dist, rank, world_size, per, xs, 10, "on", local_rank)
             extras.append(("%d particles over %d GPUs (%d per GPU), gravity on (0,-9.81)%s" %
                            (per * world_size, world_size, per, " = BASELINE.json configs[3]" if world_size == 4 else ""),
                            (r[0], r[1], r[2], r[3].pop("windows"), r[3]), per, sched, xs))
             log("extra workload: %d particles per GPU (%d in all), gravity on ..." % (ne, ne * world_size))
-            r = run_sharded(gpe, torch, dist, rank, world_size, ne, xs, 10, "on", local_rank, headline_steps=0)
+            r = run_sharded(gpe, torch, dist, rank, world_size, ne, xs, 10, "on", local_rank)
             extras.append(("%d particles per GPU, %d in all, gravity on (0,-9.81)%s" %
                            (ne, ne * world_size, " = BASELINE.json configs[4]" if world_size == 8 else ""),
                            (r[0], r[1], r[2], r[3].pop("windows"), r[3]), ne, sched, xs))
         else:
             log("extra workload: %d particles, gravity on ..." % ne)
             extras.append(("%d particles, gravity on (0,-9.81) = BASELINE.json configs[2]" % ne,
-                           run_workload(gpe, torch, None, 0, 1, ne, xs, 10, args.mode, "on", local_rank, headline_steps=0,
+                           run_workload(gpe, torch, None, 0, 1, ne, xs, 10, args.mode, "on", local_rank,
                                         tail=tuple(m for m in args.extra_tail if m > 10 + xs)),
                            ne, sched, xs))
     soak = None
@@ -679,10 +719,10 @@ def main():
         "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32+u32",
         "data": "synthetic",
         "timed_steps_total": wstats["timed_steps_total"],
-        "timing": dict(wstats, value_is="ALL timed steps / ALL timed seconds: windows of `steps` steps (each bracketed by "
-                                        "barrier + synchronize, max over ranks) FOLLOW each other from step `warmup` of the run "
-                                        "until %d steps have been timed -- the Morton re-sort every %d steps of the run and "
-                                        "every radix sort a step needs fall inside the windows" % (HEADLINE_STEPS, RESORT_EVERY)),
+        "timing": dict(wstats, value_is="`steps` timed steps / their seconds: ONE window of `steps` steps (bracketed by "
+                                        "barrier + synchronize, max over ranks) from step `warmup` of the run on -- the Morton "
+                                        "re-sort every %d steps of the run and every radix sort a step needs fall inside "
+                                        "it" % RESORT_EVERY),
         "config": {"workload": "%d particles per GPU, gravity %s, world %.1f x %.1f, radius 0.5, uniform random "
                                "(BASELINE.json configs[1] at 1M per GPU)" % (n, args.gravity, world[0], world[1]),
                    "particles_per_gpu": n, "particles_total": n * ngpu, "mode": mode, "resort_every": RESORT_EVERY,
