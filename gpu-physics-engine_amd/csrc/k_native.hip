@@ -31,6 +31,7 @@
 #include <type_traits>
 
 #include "gpe_internal.h"
+#include "k_pair.h"
 
 #ifndef GPE_NAT_THREADS
 #define GPE_NAT_THREADS 512
@@ -927,110 +928,6 @@ __device__ __forceinline__ void sort_members(L &S, const uint32_t b, const uint3
     }
 }
 
-// One pair of the reference's response (collision_solver.wgsl:91-111), shared by the one-lane-per-cell and the
-// lane-group resolution.  One wave-uniform early-out (no lane of the wave can collide), then straight-line code
-// whose result a lane keeps or not by select.  Bit-exact shortcuts:
-//  * r1 == r2 (and 1/r finite, non-zero): inv1 == inv2 and inv1 + inv1 == 2 inv1 exactly, so both weights
-//    (:107-108) are exactly 0.5 -- the three divisions are skipped, not approximated.
-//  * q = vx*vx + vy*vy > 1.000001 rs^2 implies rs^2 <= distance^2 (distance = sqrt(q) correctly rounded, so
-//    distance^2 >= q (1 - 2^-22)): no collision (:95); q < 9.9e-9 implies distance < 0.0001 (:95; 0.0001f squared
-//    is 9.99999995e-9): no collision either.  Neither needs the square root.
-//  * the correctly rounded square root and quotients without the steps hipcc's sequences spend on operands that
-//    cannot occur here (below).
-// Instruction budget (round 4; the tiles are bound by VALU issue at 100 M particles):
-//  * x and y travel as one 64-bit register pair (f32x2): the subtraction, the squares, the two quotients' refinement
-//    chains, the scalings and the final additions are the same operation on both components, and gfx950 issues
-//    v_pk_add_f32 / v_pk_mul_f32 / v_pk_fma_f32 -- IEEE binary32 per component, the same rounding as the scalar
-//    forms -- in the slot of one scalar instruction.  Left to itself hipcc packed a quarter of them.
-//  * the predicates are LANE MASKS (ballot64 / lanes_of, gpe_internal.h): every comparison is voted on its own and the masks are combined
-//    by scalar ANDs.  A vote on `a && b` costs two VALU instructions (hipcc materialises the combined predicate as
-//    0 / 1 and compares it again); the response votes three times per pair.
-// `active`: the lanes that have a pair; `plain`: the lanes whose r1 is an ordinary number (1e-30 .. 1e30).  Returns the
-// lanes that collided; (p1, p2) are updated in place for them.
-#ifdef GPE_COUNT_PAIRS
-// diagnostic builds only (scripts/soak_pairs.py): pairs the colour passes walk / resolve, over all tiles (the halo cells a
-// tile recomputes for its neighbours included) -- what "ms per 10^9 pairs" in BASELINE.md is measured with
-// (4096 counters each, by workgroup, 64 bytes apart: two counters for the whole device took 300 ms per step at 100 M; and
-// only while g_pairs_on is set, so that a run reaches the step of interest at nearly the product's speed)
-constexpr int kPairCounters = 4096;
-__device__ unsigned long long g_pairs_walked[kPairCounters * 8], g_pairs_hit[kPairCounters * 8];
-__device__ uint32_t g_pairs_on;
-__device__ __forceinline__ void count_pairs(unsigned long long *ctr, const uint64_t m)
-{
-    if (m != 0 && g_pairs_on != 0u && lane_id() == (int)__builtin_ctzll(m))
-        atomicAdd(&ctr[(blockIdx.x & (kPairCounters - 1)) * 8], (unsigned long long)__popcll(m));
-}
-#endif
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ f32x2 splat2(const float v) { return (f32x2){v, v}; }
-__device__ __forceinline__ f32x2 fma2(const f32x2 a, const f32x2 b, const f32x2 c) { return __builtin_elementwise_fma(a, b, c); }
-__device__ __forceinline__ f32x2 select2(const bool c, const f32x2 a, const f32x2 b) { return (f32x2){c ? a.x : b.x, c ? a.y : b.y}; }
-__device__ __forceinline__ uint64_t plain_radius_lanes(const float r) { return ballot64(r >= 1e-30f) & ballot64(r <= 1e30f); }
-
-// BOTH = false: only p1 is updated (the lane groups, where each lane of a pair computes its own half).
-template <bool BOTH = true>
-__device__ __forceinline__ uint64_t pair_response(const uint64_t active, f32x2 &p1, std::conditional_t<BOTH, f32x2 &, const f32x2 &> p2,
-                                                  const float r1, const float r2, const uint64_t plain,
-                                                  const float stiffness, const uint64_t counted = ~0ull)
-{
-    (void)counted;                                                    // (diagnostic builds: the lanes whose pair counts)
-#ifdef GPE_COUNT_PAIRS
-    count_pairs(g_pairs_walked, active & counted);
-#endif
-    const f32x2 v = p1 - p2;                                          // :91 (live positions, :86)
-    const f32x2 vv = v * v;
-    const float q = vv.x + vv.y;
-    const float radius_sum = r1 + r2;                                 // :61
-    const float rs2 = radius_sum * radius_sum;
-    const uint64_t cand = active & ballot64(q <= rs2 * 1.000001f) & ballot64(q >= 9.9e-9f);
-    if (cand == 0) return 0;                                          // wave-uniform
-    // The correctly rounded square root and quotients WITHOUT the steps hipcc's sequences spend on operands that
-    // cannot occur here: a candidate has q in [9.9e-9, 1.000001 rs^2] and the quotients' numerators are differences
-    // of positions (0 or >= one ulp of a position), so nothing is denormal, zero-divided, infinite or NaN; the lanes
-    // that are not candidates compute garbage that the selects below discard.
-    //   sqrt: v_sqrt_f32 is within 1 ulp; try the neighbours with an exact residual (one fma each).
-    //   x / d: r = 1/d refined once (shared by the two quotients); q0 = x r; q1 = q0 + (x - d q0) r; result =
-    //   q1 + (x - d q1) r -- the core of v_div_scale / v_div_fmas / v_div_fixup, which only add scaling and specials.
-    float distance;
-    {
-        const float s0 = __builtin_amdgcn_sqrtf(q);
-        const float s_dn = __int_as_float(__float_as_int(s0) - 1), s_up = __int_as_float(__float_as_int(s0) + 1);
-        const float r_dn = __builtin_fmaf(-s_dn, s0, q);
-        float sres = r_dn <= 0.0f ? s_dn : s0;
-        const float r_up = __builtin_fmaf(-s_up, s0, q);
-        sres = r_up > 0.0f ? s_up : sres;
-        distance = sres;                                              // :93
-    }
-    const uint64_t hit = cand & ballot64(rs2 > distance * distance) & ballot64(distance > 0.0001f);   // :95
-    const float depth = radius_sum - distance;                        // :97
-    f32x2 u;
-    {
-        const float r0 = __builtin_amdgcn_rcpf(distance);
-        const float e0 = __builtin_fmaf(-distance, r0, 1.0f);
-        const f32x2 rq = splat2(__builtin_fmaf(e0, r0, r0)), nd = splat2(-distance);
-        const f32x2 q0 = v * rq;
-        const f32x2 q1 = fma2(fma2(nd, q0, v), rq, q0);
-        u = fma2(fma2(nd, q1, v), rq, q1);
-    }
-    const f32x2 c = (u * splat2(depth)) * splat2(stiffness);          // :98,101
-    float w1 = 0.5f, w2 = 0.5f;                                       // == inv1 / (inv1 + inv1), exactly
-    const uint64_t general = hit & ~(ballot64(r1 == r2) & plain);     // unequal (or odd) radii somewhere
-    if (general != 0) {                                               // wave-uniform
-        if (lanes_of(general)) {
-            const float inv1 = 1.0f / r1, inv2 = 1.0f / r2;           // :103,104
-            w1 = inv1 / (inv1 + inv2);                                // :107
-            w2 = inv2 / (inv1 + inv2);                                // :108
-        }
-    }
-    const bool mine = lanes_of(hit);
-    p1 = select2(mine, p1 + c * splat2(w1), p1);                      // :110
-    if constexpr (BOTH) p2 = select2(mine, p2 - c * splat2(w2), p2);  // :111
-#ifdef GPE_COUNT_PAIRS
-    count_pairs(g_pairs_hit, hit & counted);
-#endif
-    return hit;
-}
-
 // The reference's pair resolution (collision_solver.wgsl:66-118), on LDS-resident positions: one lane walks the
 // pairs (a, b), a < b, of its cell.  Bit-exact restatements that shorten the dependent chain:
 //  * the next partner's position is fetched while the current pair is computed: within one `a` loop every pair
@@ -1195,6 +1092,7 @@ __device__ __forceinline__ void resolve_group(L &S, const uint32_t b, const uint
     if (has) { o = (f32x2){S.px[a_slot], S.py[a_slot]}; r1 = S.rad[a_slot]; }
     f32x2 p1 = o;
     const uint64_t plain = plain_radius_lanes(r1);
+    const uint64_t careful = neg_zero_lanes(p1);                      // (see pair_response<false>)
     const float r_mirrored = dpp_mov<kDppHalfMirror>(r1);
     const uint32_t n_plus_a = n + (uint32_t)a;                        // partner s - a exists while s - a < n
     // how long the longest schedule of the wave is (the cells of a wave differ): steps beyond 2 * 4 - 3 are skipped
@@ -1214,7 +1112,7 @@ __device__ __forceinline__ void resolve_group(L &S, const uint32_t b, const uint
         constexpr uint64_t kStepLanes = group_step_lanes<s>();
         const uint64_t pairing = has_m & kStepLanes & ballot64((uint32_t)s < n_plus_a);
         constexpr uint64_t kLower = group_step_lanes<s, true>();      // (the lane with the smaller index of each pair)
-        (void)pair_response<false>(pairing, p1, ip, r1, ir, plain, stiffness, kLower);
+        (void)pair_response<false>(pairing, p1, ip, r1, ir, plain, stiffness, kLower, careful);
     });
     if (has && (__float_as_uint(p1.x) != __float_as_uint(o.x) || __float_as_uint(p1.y) != __float_as_uint(o.y))) {
         S.px[a_slot] = p1.x;
@@ -1274,6 +1172,7 @@ __device__ __forceinline__ void resolve_row(L &S, const uint32_t b, const uint32
     if (has) { o = (f32x2){S.px[a_slot], S.py[a_slot]}; r1 = S.rad[a_slot]; }
     f32x2 p1 = o;
     const uint64_t plain = plain_radius_lanes(r1);
+    const uint64_t careful = neg_zero_lanes(p1);                      // (see pair_response<false>)
     const float r_mirrored = dpp_mov<kDppRowMirror>(r1);
     const uint32_t n_plus_a = n + (uint32_t)a;                        // partner s - a exists while s - a < n
     for_each_group_step<1, 2 * (int)kRowLanes - 3>([&](auto sc) {
@@ -1288,7 +1187,7 @@ __device__ __forceinline__ void resolve_row(L &S, const uint32_t b, const uint32
         constexpr uint64_t kStepLanes = row_step_lanes<s>();
         const uint64_t pairing = has_m & kStepLanes & ballot64((uint32_t)s < n_plus_a);
         constexpr uint64_t kLower = row_step_lanes<s, true>();
-        (void)pair_response<false>(pairing, p1, ip, r1, ir, plain, stiffness, kLower);
+        (void)pair_response<false>(pairing, p1, ip, r1, ir, plain, stiffness, kLower, careful);
     });
     if (has && (__float_as_uint(p1.x) != __float_as_uint(o.x) || __float_as_uint(p1.y) != __float_as_uint(o.y))) {
         S.px[a_slot] = p1.x;
