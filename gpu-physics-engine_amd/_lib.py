@@ -127,6 +127,8 @@ SYMBOLS = [
     ("gpe_last_error", C.c_char_p, [_VP]),
     ("gpe_set_particles", _I32, [_VP, _VP, _VP, _VP, _U64]),
     ("gpe_add_particles", _I32, [_VP, _VP, _VP, _U64]),
+    ("gpe_remove_particles", _I32, [_VP, _VP, _U64, C.POINTER(_U64)]),
+    ("gpe_remove_particles_in_circle", _I32, [_VP, _F, _F, _F, C.POINTER(_U64)]),
     ("gpe_len", _I32, [_VP, C.POINTER(_U64)]),
     ("gpe_max_radius", _I32, [_VP, C.POINTER(_F)]),
     ("gpe_morton_resort", _I32, [_VP]),

@@ -116,6 +116,9 @@ static void free_particle_buffers(gpe_ctx *c)
     dev_free(c->cell_ids); dev_free(c->object_ids);
     dev_free(c->chunk_obj_count); dev_free(c->collision_cells); dev_free(c->indirect_args);
     dev_free(c->order_keys);
+    dev_free(c->remove_ws.tile_count); dev_free(c->remove_ws.tile_key); dev_free(c->remove_ws.max_key);
+    dev_free(c->remove_ws.mask);
+    c->remove_ws.tiles_cap = c->remove_ws.mask_cap = 0;
     c->cap = 0;
 }
 
@@ -315,6 +318,89 @@ static gpe_status need_particles(gpe_ctx *c)
     if (!c) return GPE_ERR_INVALID_ARG;
     if (c->n == 0 || !c->pos) return fail(c, GPE_ERR_STATE, "no particles: call gpe_set_particles first");
     return GPE_OK;
+}
+
+// ---- removal (k_remove.hip) ---------------------------------------------------------------------------
+static gpe_status check_removable(gpe_ctx *c, const char *who)
+{
+    GPE_TRY(need_particles(c));
+    if (c->shard.on || c->use_order_keys || c->has_active_box)
+        return fail(c, GPE_ERR_UNSUPPORTED, std::string(who) + ": not supported on a sharded context (gpe_shard_*, "
+                                                                "order keys or an active cell box)");
+    return GPE_OK;
+}
+
+static gpe_status remove_reserve(gpe_ctx *c, uint64_t mask_bytes)
+{
+    RemoveWorkspace &ws = c->remove_ws;
+    const uint64_t tiles = remove_tiles(c->n);
+    if (ws.tiles_cap < tiles) {
+        dev_free(ws.tile_count);
+        dev_free(ws.tile_key);
+        ws.tiles_cap = 0;
+        GPE_TRY(dev_alloc(c, &ws.tile_count, tiles));
+        GPE_TRY(dev_alloc(c, &ws.tile_key, tiles));
+        ws.tiles_cap = tiles;
+    }
+    if (!ws.max_key) GPE_TRY(dev_alloc(c, &ws.max_key, 1));
+    if (ws.mask_cap < mask_bytes) {
+        const uint64_t want = std::max(c->cap, mask_bytes);             // (a later call on fewer particles fits)
+        dev_free(ws.mask);
+        ws.mask_cap = 0;
+        GPE_TRY(dev_alloc(c, &ws.mask, want));
+        ws.mask_cap = want;
+    }
+    return scan_reserve(c, tiles);
+}
+
+// Stable compaction of the particles that survive `mask` (device bytes, != 0: removed) or, mask == NULL, the disc
+// around (x, y) with rr = radius^2.  Counts first: removing nothing or everything leaves the context untouched.
+// Afterwards the context is what gpe_set_particles(survivors) leaves on it.
+static gpe_status do_remove(gpe_ctx *c, const uint8_t *mask, float x, float y, float rr, uint64_t *n_removed)
+{
+    RemoveWorkspace &ws = c->remove_ws;
+    const uint64_t n = c->n, tiles = remove_tiles(n);
+    uint32_t survivors = 0;
+    unsigned long long key = 0;
+    Scope s(c, "Remove particles");
+    {
+        Scope k(c, "remove/count");
+        GPE_TRY(launch_remove_count(c, mask, x, y, rr, ws.tile_count, ws.tile_key, ws.max_key));
+    }
+    {
+        Scope k(c, "remove/scan");
+        GPE_TRY(inclusive_scan(c, ws.tile_count, tiles));
+    }
+    GPE_HIP(c, hipMemcpyAsync(&survivors, ws.tile_count + (tiles - 1), sizeof(survivors), hipMemcpyDeviceToHost,
+                              c->stream));
+    GPE_HIP(c, hipMemcpyAsync(&key, ws.max_key, sizeof(key), hipMemcpyDeviceToHost, c->stream));
+    GPE_HIP(c, hipStreamSynchronize(c->stream));
+    if (survivors == n) return GPE_OK;                                   // nothing removed: the context is untouched
+    if (survivors == 0)
+        return fail(c, GPE_ERR_INVALID_ARG, "gpe_remove_particles: the call would remove every particle");
+    const uint32_t winner = (uint32_t)(key & 0xFFFFFFFFull);           // old index of the survivors' max |radius|
+    if (winner >= n) return fail(c, GPE_ERR_STATE, "gpe_remove_particles: bad max-radius index");
+    float max_r = 0.f;
+    GPE_HIP(c, hipMemcpyAsync(&max_r, c->radius + winner, sizeof(max_r), hipMemcpyDeviceToHost, c->stream));
+    {
+        Scope k(c, "remove/scatter");
+        GPE_TRY(launch_remove_scatter(c, mask, x, y, rr, ws.tile_count));
+    }
+    std::swap(c->pos, c->pos_copy);                                     // as do_resort
+    std::swap(c->prev, c->prev_copy);
+    std::swap(c->radius, c->radius_copy);
+    c->n = survivors;
+    c->n_owned = survivors;
+    {
+        Scope k(c, "remove/index reset");
+        GPE_TRY(init_index_buffers(c, 0, survivors));
+    }
+    GPE_HIP(c, hipStreamSynchronize(c->stream));
+    c->max_radius = max_r;                    // max_abs_radius over the survivors: largest |r|, last on ties, sign kept
+    c->grid_max_radius = c->max_radius;
+    refresh_cell_size(c);
+    if (n_removed) *n_removed = n - survivors;
+    return reconfigure_native(c);
 }
 
 // ---- step pieces ------------------------------------------------------------------------------------
@@ -653,6 +739,32 @@ gpe_status gpe_add_particles(gpe_ctx *c, const float *pos_xy, const float *radiu
     refresh_cell_size(c);
     GPE_HIP(c, hipStreamSynchronize(c->stream));
     return reconfigure(c);
+}
+
+gpe_status gpe_remove_particles(gpe_ctx *c, const uint8_t *remove, uint64_t n, uint64_t *n_removed)
+{
+    if (n_removed) *n_removed = 0;
+    GPE_TRY(check_removable(c, "gpe_remove_particles"));
+    if (!remove) return fail(c, GPE_ERR_INVALID_ARG, "gpe_remove_particles: NULL mask");
+    if (n != c->n) return fail(c, GPE_ERR_INVALID_ARG, "gpe_remove_particles: n must equal gpe_len");
+    GPE_HIP(c, hipSetDevice(c->device));
+    GPE_HIP(c, hipStreamSynchronize(c->stream));
+    GPE_TRY(remove_reserve(c, n));
+    GPE_HIP(c, hipMemcpyAsync(c->remove_ws.mask, remove, n, hipMemcpyHostToDevice, c->stream));
+    return do_remove(c, c->remove_ws.mask, 0.f, 0.f, 0.f, n_removed);
+}
+
+gpe_status gpe_remove_particles_in_circle(gpe_ctx *c, float x, float y, float radius, uint64_t *n_removed)
+{
+    if (n_removed) *n_removed = 0;
+    GPE_TRY(check_removable(c, "gpe_remove_particles_in_circle"));
+    if (!(radius >= 0.0f) || !isfinite(radius))
+        return fail(c, GPE_ERR_INVALID_ARG, "gpe_remove_particles_in_circle: radius must be finite and >= 0");
+    GPE_HIP(c, hipSetDevice(c->device));
+    GPE_HIP(c, hipStreamSynchronize(c->stream));
+    GPE_TRY(remove_reserve(c, 0));
+    const float rr = radius * radius;        // binary32, as the device's side of the test
+    return do_remove(c, nullptr, x, y, rr, n_removed);
 }
 
 gpe_status gpe_len(const gpe_ctx *c, uint64_t *n)

@@ -248,6 +248,15 @@ struct ScanWorkspace {           // reduce-then-scan tile sums, one array per re
     std::vector<uint64_t> cap;
 };
 
+struct RemoveWorkspace {         // gpe_remove_particles* (k_remove.hip); allocated at first use, freed with the particles
+    uint32_t *tile_count = nullptr;              // per-tile survivor counts, scanned in place
+    unsigned long long *tile_key = nullptr;      // per-tile max of the survivors' bits(|radius|) << 32 | index
+    uint64_t tiles_cap = 0;
+    unsigned long long *max_key = nullptr;       // survivors' max of bits(|radius|) << 32 | index
+    uint8_t *mask = nullptr;                     // the uploaded removal mask
+    uint64_t mask_cap = 0;
+};
+
 struct SortWorkspace {
     uint32_t *keys_b = nullptr, *vals_b = nullptr;   // ping-pong partners, cap entries each
     uint64_t cap = 0;
@@ -574,6 +583,7 @@ struct gpe_ctx {
     int32_t active_box[4] = {0, 0, 0, 0};   // cx0, cy0, cx1, cy1 (inclusive) holding this rank's particles
 
     gpe::SortWorkspace sort_ws;
+    gpe::RemoveWorkspace remove_ws;
     gpe::ScanWorkspace scan_ws;
     gpe::OnesweepWorkspace os_ws;
     gpe::NativeState native;
@@ -675,6 +685,12 @@ gpe_status onesweep_sort(gpe_ctx *c, uint32_t *keys, uint32_t *vals, uint32_t *k
                          uint32_t table_entries = 0,    // table: the last pass also fills the native block table
                          const uint32_t *hist_src = nullptr,   // bases_ready: histogram copies the passes scan themselves
                          const OnesweepGate *gate = nullptr);
+// removal (k_remove.hip): mask != NULL selects the mask form, else the disc around (x, y) with rr = radius^2
+uint64_t remove_tiles(uint64_t n);
+gpe_status launch_remove_count(gpe_ctx *c, const uint8_t *mask, float x, float y, float rr, uint32_t *tile_count,
+                               unsigned long long *tile_key, unsigned long long *max_key);
+gpe_status launch_remove_scatter(gpe_ctx *c, const uint8_t *mask, float x, float y, float rr,
+                                 const uint32_t *tile_scanned);
 // native pipeline (k_native.hip)
 gpe_status native_configure(gpe_ctx *c);
 bool native_should_run(gpe_ctx *c);

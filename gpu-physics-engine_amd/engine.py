@@ -250,6 +250,26 @@ class ParticleSystem:
         rad = np.ascontiguousarray(radii, np.float32).reshape(-1)
         self.ctx.call("gpe_add_particles", _ptr(pos), _ptr(rad), pos.shape[0])
 
+    def remove_particles(self, mask):
+        """gpe_remove_particles (not in the reference): remove every particle i (storage order, as
+        download_particle_buffers returns them) with mask[i] true / non-zero; len(mask) must equal len().  The
+        survivors keep their order.  Returns the number removed."""
+        m = np.asarray(mask)
+        if m.dtype == np.bool_:
+            m = m.astype(np.uint8)
+        m = np.ascontiguousarray(m, np.uint8).reshape(-1)
+        removed = C.c_uint64()
+        self.ctx.call("gpe_remove_particles", _ptr(m), m.shape[0], C.byref(removed))
+        return removed.value
+
+    def remove_particles_in_circle(self, center, radius):
+        """gpe_remove_particles_in_circle (not in the reference): remove every particle whose centre p has
+        |p - center|^2 <= radius^2 in float32 (an eraser brush).  Returns the number removed."""
+        removed = C.c_uint64()
+        self.ctx.call("gpe_remove_particles_in_circle", float(center[0]), float(center[1]), float(radius),
+                      C.byref(removed))
+        return removed.value
+
     def len(self):
         n = C.c_uint64()
         self.ctx.call("gpe_len", C.byref(n))
@@ -432,6 +452,14 @@ class State:
     def add_particles(self, positions, radii):
         """state.rs:187-200."""
         self.particles.add_particles(positions, radii)
+
+    def remove_particles(self, mask):
+        """ParticleSystem.remove_particles: the particles with mask[i] set leave; returns how many."""
+        return self.particles.remove_particles(mask)
+
+    def remove_particles_in_circle(self, center, radius):
+        """ParticleSystem.remove_particles_in_circle: the particles inside the disc leave; returns how many."""
+        return self.particles.remove_particles_in_circle(center, radius)
 
     def positions(self):
         return self.ctx.download(L.POS, np.float32, (-1, 2))

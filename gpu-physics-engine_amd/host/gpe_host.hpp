@@ -164,6 +164,20 @@ class ParticleSystem {
     {
         ctx_->call(gpe_add_particles(ctx_->raw(), &positions[0].x, radii.data(), positions.size()));
     }
+    // not in the reference: remove every particle i with remove[i] != 0 (storage order, len() entries) / every particle
+    // whose centre lies in the disc around `center`; the survivors keep their order.  Returns the number removed.
+    uint64_t remove_particles(const std::vector<uint8_t> &remove)
+    {
+        uint64_t removed = 0;
+        ctx_->call(gpe_remove_particles(ctx_->raw(), remove.data(), remove.size(), &removed));
+        return removed;
+    }
+    uint64_t remove_particles_in_circle(Vec2 center, float radius)
+    {
+        uint64_t removed = 0;
+        ctx_->call(gpe_remove_particles_in_circle(ctx_->raw(), center.x, center.y, radius, &removed));
+        return removed;
+    }
     size_t len() const { uint64_t n = 0; ctx_->call(gpe_len(ctx_->raw(), &n)); return n; }               // :275
     float get_max_radius() const { float r = 0; ctx_->call(gpe_max_radius(ctx_->raw(), &r)); return r; } // :291
     void sort_by_cell_id(float /*cell_size: the Grid's, state.rs:123*/) { ctx_->call(gpe_morton_resort(ctx_->raw())); }

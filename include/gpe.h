@@ -113,6 +113,21 @@ gpe_status gpe_set_particles(gpe_ctx *ctx, const float *pos_xy, const float *pre
  * CollisionSystem::refresh (collision_system.rs:24-28): append n particles (prev = pos),
  * grow every dependent buffer (amortised x2 like gpu_buffer.rs:54-56), recompute cell size. */
 gpe_status gpe_add_particles(gpe_ctx *ctx, const float *pos_xy, const float *radius, uint64_t n);
+/* Remove every particle i (storage order, as gpe_download(GPE_POS) returns it) with remove[i] != 0.
+ * n must equal gpe_len.  n_removed may be NULL.  Synchronises, like gpe_add_particles.
+ * The survivors keep their order and their pos / prev / radius bits; afterwards the context is what
+ * gpe_set_particles(survivors' pos, prev, radius) would leave on it (capacity and the native step /
+ * sort counters aside): gpe_len, gpe_max_radius (largest magnitude, last on ties, sign kept), cell
+ * size, HOME_CELL_IDS = unused, PARTICLE_IDS = iota, grid arrays, native eligibility.  Compacted on
+ * the device (csrc/k_remove.hip): the mask (n bytes) is the only upload.
+ * Nothing removed: GPE_OK, *n_removed = 0, the context untouched.  Every particle removed:
+ * GPE_ERR_INVALID_ARG, the context untouched.  NULL mask or n != gpe_len: GPE_ERR_INVALID_ARG; no
+ * particles: GPE_ERR_STATE; a sharded context (gpe_shard_*, order keys, active box): GPE_ERR_UNSUPPORTED. */
+gpe_status gpe_remove_particles(gpe_ctx *ctx, const uint8_t *remove, uint64_t n, uint64_t *n_removed);
+/* Remove every particle whose centre p has (p.x-x)*(p.x-x) + (p.y-y)*(p.y-y) <= radius*radius, in
+ * IEEE binary32 with one rounding per operation, left to right, no FMA (numpy float32 gives the same
+ * set).  radius must be finite and >= 0 (else GPE_ERR_INVALID_ARG); otherwise as gpe_remove_particles. */
+gpe_status gpe_remove_particles_in_circle(gpe_ctx *ctx, float x, float y, float radius, uint64_t *n_removed);
 /* ParticleSystem::len (:275) / get_max_radius (:291) */
 gpe_status gpe_len(const gpe_ctx *ctx, uint64_t *n);
 gpe_status gpe_max_radius(const gpe_ctx *ctx, float *r);
