@@ -36,7 +36,8 @@ COUNTING_CHUNK_SIZE = 4
 
 # gpe_array
 POS, PREV, RADIUS, HOME_CELL_IDS, PARTICLE_IDS, CELL_IDS, OBJECT_IDS, COLLISION_CELLS, \
-    NUM_COLLISION_CELLS, CHUNK_OBJ_COUNT, INDIRECT_ARGS, ORDER_KEYS = range(12)
+    NUM_COLLISION_CELLS, CHUNK_OBJ_COUNT, INDIRECT_ARGS, ORDER_KEYS, UIDS = range(13)
+UID_ABSENT = 0xFFFFFFFF
 
 
 class GpeConfig(C.Structure):
@@ -129,6 +130,12 @@ SYMBOLS = [
     ("gpe_add_particles", _I32, [_VP, _VP, _VP, _U64]),
     ("gpe_remove_particles", _I32, [_VP, _VP, _U64, C.POINTER(_U64)]),
     ("gpe_remove_particles_in_circle", _I32, [_VP, _F, _F, _F, C.POINTER(_U64)]),
+    ("gpe_enable_uids", _I32, [_VP, _I32]),
+    ("gpe_set_uids", _I32, [_VP, _VP, _U64]),
+    ("gpe_next_uid", _I32, [_VP, C.POINTER(_U64)]),
+    ("gpe_set_next_uid", _I32, [_VP, _U64]),
+    ("gpe_find_uids", _I32, [_VP, _VP, _U64, _VP, _VP, _VP, _VP]),
+    ("gpe_remove_particles_by_uid", _I32, [_VP, _VP, _U64, C.POINTER(_U64)]),
     ("gpe_len", _I32, [_VP, C.POINTER(_U64)]),
     ("gpe_max_radius", _I32, [_VP, C.POINTER(_F)]),
     ("gpe_morton_resort", _I32, [_VP]),

@@ -8,6 +8,7 @@
 #include <mutex>
 
 #include "gpe_internal.h"
+#include "k_uids.h"
 
 namespace gpe {
 
@@ -108,6 +109,16 @@ static void dev_free(T *&p)
     p = nullptr;
 }
 
+// The uid buffers, the uid -> index map and the lookup staging (the uid switch itself stays as it is).
+static void free_uid_buffers(gpe_ctx *c)
+{
+    UidState &u = c->uid;
+    dev_free(u.uids); dev_free(u.uids_copy);
+    dev_free(u.map_keys); dev_free(u.map_vals); dev_free(u.dup); dev_free(u.query);
+    u.map_cap = u.query_cap = 0;
+    u.map_valid = false;
+}
+
 static void free_particle_buffers(gpe_ctx *c)
 {
     dev_free(c->pos); dev_free(c->prev); dev_free(c->radius);
@@ -119,6 +130,7 @@ static void free_particle_buffers(gpe_ctx *c)
     dev_free(c->remove_ws.tile_count); dev_free(c->remove_ws.tile_key); dev_free(c->remove_ws.max_key);
     dev_free(c->remove_ws.mask);
     c->remove_ws.tiles_cap = c->remove_ws.mask_cap = 0;
+    free_uid_buffers(c);
     c->cap = 0;
 }
 
@@ -181,6 +193,10 @@ static gpe_status alloc_particle_buffers(gpe_ctx *c, uint64_t cap, bool with_gri
     GPE_TRY(dev_alloc(c, &c->home_cell_ids, cap));
     GPE_TRY(dev_alloc(c, &c->particle_ids, cap));
     GPE_TRY(dev_alloc(c, &c->order_keys, cap));
+    if (c->uid.on) {
+        GPE_TRY(dev_alloc(c, &c->uid.uids, cap));
+        GPE_TRY(dev_alloc(c, &c->uid.uids_copy, cap));
+    }
     c->cap = cap;
     if (with_grid) GPE_TRY(alloc_grid_buffers(c, cap));
     else GPE_TRY(sort_reserve(c, cap));                                // the Morton re-sort's N pairs
@@ -228,6 +244,7 @@ struct ParticleBufferSet {
     float *radius = nullptr, *radius_copy = nullptr;
     uint32_t *home_cell_ids = nullptr, *particle_ids = nullptr, *cell_ids = nullptr, *object_ids = nullptr,
              *chunk_obj_count = nullptr, *collision_cells = nullptr, *indirect_args = nullptr, *order_keys = nullptr;
+    uint32_t *uids = nullptr, *uids_copy = nullptr;
     uint64_t cap = 0;
 };
 static ParticleBufferSet take_buffers(gpe_ctx *c)
@@ -238,11 +255,13 @@ static ParticleBufferSet take_buffers(gpe_ctx *c)
     b.home_cell_ids = c->home_cell_ids; b.particle_ids = c->particle_ids; b.cell_ids = c->cell_ids;
     b.object_ids = c->object_ids; b.chunk_obj_count = c->chunk_obj_count; b.collision_cells = c->collision_cells;
     b.indirect_args = c->indirect_args; b.order_keys = c->order_keys;
+    b.uids = c->uid.uids; b.uids_copy = c->uid.uids_copy;
     b.cap = c->cap;
     c->pos = c->prev = c->pos_copy = c->prev_copy = nullptr;
     c->radius = c->radius_copy = nullptr;
     c->home_cell_ids = c->particle_ids = c->cell_ids = c->object_ids = nullptr;
     c->chunk_obj_count = c->collision_cells = c->indirect_args = c->order_keys = nullptr;
+    c->uid.uids = c->uid.uids_copy = nullptr;
     c->cap = 0;
     return b;
 }
@@ -253,6 +272,7 @@ static void put_buffers(gpe_ctx *c, const ParticleBufferSet &b)
     c->home_cell_ids = b.home_cell_ids; c->particle_ids = b.particle_ids; c->cell_ids = b.cell_ids;
     c->object_ids = b.object_ids; c->chunk_obj_count = b.chunk_obj_count; c->collision_cells = b.collision_cells;
     c->indirect_args = b.indirect_args; c->order_keys = b.order_keys;
+    c->uid.uids = b.uids; c->uid.uids_copy = b.uids_copy;
     c->cap = b.cap;
 }
 
@@ -270,6 +290,8 @@ static gpe_status copy_into_new_buffers(gpe_ctx *c, const ParticleBufferSet &old
     }
     if (old.order_keys) GPE_COPY_OLD(order_keys, old_n);
 #undef GPE_COPY_OLD
+    if (old.uids && c->uid.uids)
+        GPE_HIP(c, hipMemcpyAsync(c->uid.uids, old.uids, old_n * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
     GPE_HIP(c, hipStreamSynchronize(c->stream));
     return GPE_OK;
 }
@@ -293,7 +315,7 @@ static gpe_status grow_particle_buffers(gpe_ctx *c, uint64_t cap)
     float *f1[] = {old.radius, old.radius_copy};
     for (float *p : f1) if (p) (void)hipFree(p);
     uint32_t *u[] = {old.home_cell_ids, old.particle_ids, old.cell_ids, old.object_ids, old.chunk_obj_count,
-                     old.collision_cells, old.indirect_args, old.order_keys};
+                     old.collision_cells, old.indirect_args, old.order_keys, old.uids, old.uids_copy};
     for (uint32_t *p : u) if (p) (void)hipFree(p);
     return GPE_OK;
 }
@@ -384,11 +406,15 @@ static gpe_status do_remove(gpe_ctx *c, const uint8_t *mask, float x, float y, f
     GPE_HIP(c, hipMemcpyAsync(&max_r, c->radius + winner, sizeof(max_r), hipMemcpyDeviceToHost, c->stream));
     {
         Scope k(c, "remove/scatter");
-        GPE_TRY(launch_remove_scatter(c, mask, x, y, rr, ws.tile_count));
+        GPE_TRY(launch_remove_scatter(c, mask, x, y, rr, ws.tile_count, c->uid.uids, c->uid.uids_copy));
     }
     std::swap(c->pos, c->pos_copy);                                     // as do_resort
     std::swap(c->prev, c->prev_copy);
     std::swap(c->radius, c->radius_copy);
+    if (c->uid.on) {
+        std::swap(c->uid.uids, c->uid.uids_copy);
+        c->uid.map_valid = false;
+    }
     c->n = survivors;
     c->n_owned = survivors;
     {
@@ -403,6 +429,84 @@ static gpe_status do_remove(gpe_ctx *c, const uint8_t *mask, float x, float y, f
     return reconfigure_native(c);
 }
 
+// ---- uids (k_uids.hip) ----------------------------------------------------------------------------------
+constexpr uint64_t kUidLimit = 1ull << 32;                     // next_uid may reach 2^32: then no particle can be added
+
+static bool is_sharded(const gpe_ctx *c) { return c->shard.on || c->use_order_keys || c->has_active_box; }
+
+// Off -> on: the uid buffers for the current capacity (none yet without particles).
+static gpe_status uids_switch_on(gpe_ctx *c)
+{
+    UidState &u = c->uid;
+    if (c->cap > 0) {
+        gpe_status st = dev_alloc(c, &u.uids, c->cap);
+        if (st == GPE_OK) st = dev_alloc(c, &u.uids_copy, c->cap);
+        if (st != GPE_OK) {
+            free_uid_buffers(c);
+            return st;
+        }
+    }
+    u.on = true;
+    u.map_valid = false;
+    return GPE_OK;
+}
+
+// The map of the c->n >= 1 uids at src (the live ones, or those gpe_set_uids staged): (uid, index) pairs sorted by
+// uid, *dup = some uid occurs twice, map_max = the last key.  Synchronises.  Leaves map_valid to the caller.
+static gpe_status uid_map_build(gpe_ctx *c, const uint32_t *src, bool *dup)
+{
+    UidState &u = c->uid;
+    const uint64_t n = c->n;
+    u.map_valid = false;
+    if (u.map_cap < n) {
+        dev_free(u.map_keys);
+        dev_free(u.map_vals);
+        u.map_cap = 0;
+        const uint64_t want = std::max(c->cap, n);
+        GPE_TRY(dev_alloc(c, &u.map_keys, want));
+        GPE_TRY(dev_alloc(c, &u.map_vals, want));
+        u.map_cap = want;
+    }
+    if (!u.dup) GPE_TRY(dev_alloc(c, &u.dup, 1));
+    GPE_TRY(sort_reserve(c, n));
+    {
+        Scope s(c, "uids/map");
+        GPE_TRY(launch_uid_map_init(c, src, n, u.map_keys, u.map_vals));
+        GPE_TRY(sort_pairs(c, u.map_keys, u.map_vals, n));
+        GPE_HIP(c, hipMemsetAsync(u.dup, 0, sizeof(uint32_t), c->stream));
+        GPE_TRY(launch_uid_adjacent(c, u.map_keys, n, u.dup));
+    }
+    uint32_t words[2] = {0, 0};
+    GPE_HIP(c, hipMemcpyAsync(&words[0], u.dup, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    GPE_HIP(c, hipMemcpyAsync(&words[1], u.map_keys + (n - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    GPE_HIP(c, hipStreamSynchronize(c->stream));
+    *dup = words[0] != 0;
+    u.map_max = words[1];
+    return GPE_OK;
+}
+
+// The live uids' map, rebuilt only when something has made it stale.  Needs c->n >= 1.
+static gpe_status uid_map_ready(gpe_ctx *c)
+{
+    if (c->uid.map_valid) return GPE_OK;
+    bool dup = false;
+    GPE_TRY(uid_map_build(c, c->uid.uids, &dup));
+    if (dup) return fail(c, GPE_ERR_STATE, "uids: two particles share a uid");
+    c->uid.map_valid = true;
+    return GPE_OK;
+}
+
+static gpe_status uid_query_reserve(gpe_ctx *c, uint64_t bytes)
+{
+    UidState &u = c->uid;
+    if (u.query_cap >= bytes) return GPE_OK;
+    dev_free(u.query);
+    u.query_cap = 0;
+    GPE_TRY(dev_alloc(c, &u.query, bytes));
+    u.query_cap = bytes;
+    return GPE_OK;
+}
+
 // ---- step pieces ------------------------------------------------------------------------------------
 static gpe_status do_resort(gpe_ctx *c)
 {
@@ -412,8 +516,15 @@ static gpe_status do_resort(gpe_ctx *c)
         Scope s(c, "Particle sort");   // particle_sort.rs:64
         GPE_TRY(sort_pairs(c, c->home_cell_ids, c->particle_ids, c->n));
     }
-    GPE_TRY(launch_rearrange(c, c->pos, c->prev, c->radius, c->particle_ids, c->n, c->pos_copy,
-                             c->prev_copy, c->radius_copy));
+    if (c->uid.on) {                   // the uids follow the same permutation (k_uids.hip)
+        GPE_TRY(launch_rearrange_uids(c, c->pos, c->prev, c->radius, c->uid.uids, c->particle_ids, c->n, c->pos_copy,
+                                      c->prev_copy, c->radius_copy, c->uid.uids_copy));
+        std::swap(c->uid.uids, c->uid.uids_copy);
+        c->uid.map_valid = false;
+    } else {
+        GPE_TRY(launch_rearrange(c, c->pos, c->prev, c->radius, c->particle_ids, c->n, c->pos_copy,
+                                 c->prev_copy, c->radius_copy));
+    }
     // particle_rearrange.rs:205-238 copies the copy set back; swapping the two sets is equivalent
     std::swap(c->pos, c->pos_copy);
     std::swap(c->prev, c->prev_copy);
@@ -710,6 +821,11 @@ gpe_status gpe_set_particles(gpe_ctx *c, const float *pos_xy, const float *prev_
                               c->stream));
     GPE_HIP(c, hipMemcpyAsync(c->radius, radius, n * sizeof(float), hipMemcpyHostToDevice, c->stream));
     GPE_TRY(init_index_buffers(c, 0, n));
+    if (c->uid.on) {                                   // as gpe_enable_uids: uid = storage index
+        GPE_TRY(launch_uid_iota(c, c->uid.uids, 0, n, 0u));
+        c->uid.next = n;
+        c->uid.map_valid = false;
+    }
     c->max_radius = max_abs_radius(radius, n, radius[0]);
     c->grid_max_radius = c->max_radius;       // Grid::new (grid.rs:66-71)
     refresh_cell_size(c);
@@ -724,6 +840,8 @@ gpe_status gpe_add_particles(gpe_ctx *c, const float *pos_xy, const float *radiu
     if (n_add == 0) return GPE_OK;
     const uint64_t old_n = c->n, new_n = c->n + n_add;
     if (new_n > (1ull << 30) - 1) return fail(c, GPE_ERR_INVALID_ARG, "gpe_add_particles: 4n must fit in u32");
+    if (c->uid.on && c->uid.next + n_add > kUidLimit)
+        return fail(c, GPE_ERR_STATE, "gpe_add_particles: the new particles' uids would pass 2^32 - 1");
     GPE_HIP(c, hipSetDevice(c->device));
     GPE_HIP(c, hipStreamSynchronize(c->stream));
     if (new_n > c->cap) GPE_TRY(grow_particle_buffers(c, std::max<uint64_t>(new_n, c->cap * 2)));
@@ -733,6 +851,11 @@ gpe_status gpe_add_particles(gpe_ctx *c, const float *pos_xy, const float *radiu
     c->n = new_n;
     c->n_owned = new_n;
     GPE_TRY(init_index_buffers(c, old_n, new_n));
+    if (c->uid.on) {                                   // next .. next + n_add - 1, in input order
+        GPE_TRY(launch_uid_iota(c, c->uid.uids, old_n, new_n, (uint32_t)c->uid.next));
+        c->uid.next += n_add;
+        c->uid.map_valid = false;
+    }
     // particle_system.rs:198: max_radius = max(max_radius, r)
     for (uint64_t i = 0; i < n_add; ++i) c->max_radius = fmaxf(c->max_radius, radius[i]);
     c->grid_max_radius = c->max_radius;   // Grid::refresh_grid (grid.rs:266)
@@ -765,6 +888,168 @@ gpe_status gpe_remove_particles_in_circle(gpe_ctx *c, float x, float y, float ra
     GPE_TRY(remove_reserve(c, 0));
     const float rr = radius * radius;        // binary32, as the device's side of the test
     return do_remove(c, nullptr, x, y, rr, n_removed);
+}
+
+// ---- uids ------------------------------------------------------------------------------------------------
+gpe_status gpe_enable_uids(gpe_ctx *c, int32_t enable)
+{
+    if (!c) return GPE_ERR_INVALID_ARG;
+    UidState &u = c->uid;
+    if (!enable) {
+        if (!u.on) return GPE_OK;
+        GPE_HIP(c, hipSetDevice(c->device));
+        GPE_HIP(c, hipStreamSynchronize(c->stream));           // (a re-sort in flight may still read them)
+        free_uid_buffers(c);
+        u.on = false;
+        u.next = 0;
+        return GPE_OK;
+    }
+    if (u.on) return GPE_OK;                                   // keeps the current uids
+    if (is_sharded(c))
+        return fail(c, GPE_ERR_UNSUPPORTED, "gpe_enable_uids: not supported on a sharded context (gpe_shard_*, order "
+                                            "keys or an active cell box)");
+    GPE_HIP(c, hipSetDevice(c->device));
+    GPE_HIP(c, hipStreamSynchronize(c->stream));
+    GPE_TRY(uids_switch_on(c));
+    const gpe_status st = launch_uid_iota(c, u.uids, 0, c->n, 0u);
+    if (st != GPE_OK) {
+        free_uid_buffers(c);
+        u.on = false;
+        return st;
+    }
+    u.next = c->n;
+    return GPE_OK;
+}
+
+gpe_status gpe_set_uids(gpe_ctx *c, const uint32_t *uids, uint64_t n)
+{
+    if (!c) return GPE_ERR_INVALID_ARG;
+    if (is_sharded(c))
+        return fail(c, GPE_ERR_UNSUPPORTED, "gpe_set_uids: not supported on a sharded context (gpe_shard_*, order "
+                                            "keys or an active cell box)");
+    if (!uids) return fail(c, GPE_ERR_INVALID_ARG, "gpe_set_uids: NULL uids");
+    if (n != c->n) return fail(c, GPE_ERR_INVALID_ARG, "gpe_set_uids: n must equal gpe_len");
+    GPE_TRY(need_particles(c));
+    GPE_HIP(c, hipSetDevice(c->device));
+    GPE_HIP(c, hipStreamSynchronize(c->stream));
+    UidState &u = c->uid;
+    const bool was_on = u.on;
+    if (!was_on) GPE_TRY(uids_switch_on(c));
+    // staged in the copy partner and checked there: the live uids change only when the new ones pass
+    bool dup = false;
+    gpe_status st = GPE_OK;
+    const hipError_t e = hipMemcpyAsync(u.uids_copy, uids, n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        st = fail(c, GPE_ERR_HIP, std::string("gpe_set_uids: upload: ") + hipGetErrorName(e));
+    }
+    if (st == GPE_OK) st = uid_map_build(c, u.uids_copy, &dup);
+    if (st == GPE_OK && dup) st = fail(c, GPE_ERR_INVALID_ARG, "gpe_set_uids: two particles would share a uid");
+    if (st != GPE_OK) {
+        if (!was_on) {                                         // off as before
+            free_uid_buffers(c);
+            u.on = false;
+        }
+        return st;
+    }
+    std::swap(u.uids, u.uids_copy);
+    u.next = (uint64_t)u.map_max + 1;
+    u.map_valid = true;                                        // the map just built is the new uids'
+    return GPE_OK;
+}
+
+gpe_status gpe_next_uid(const gpe_ctx *c, uint64_t *next)
+{
+    if (!c || !next) return GPE_ERR_INVALID_ARG;
+    if (!c->uid.on) return fail(const_cast<gpe_ctx *>(c), GPE_ERR_STATE, "gpe_next_uid: uids are off");
+    *next = c->uid.next;
+    return GPE_OK;
+}
+
+gpe_status gpe_set_next_uid(gpe_ctx *c, uint64_t next)
+{
+    if (!c) return GPE_ERR_INVALID_ARG;
+    if (!c->uid.on) return fail(c, GPE_ERR_STATE, "gpe_set_next_uid: uids are off");
+    if (next > kUidLimit) return fail(c, GPE_ERR_INVALID_ARG, "gpe_set_next_uid: next must be at most 2^32");
+    if (c->n > 0) {
+        GPE_HIP(c, hipSetDevice(c->device));
+        GPE_HIP(c, hipStreamSynchronize(c->stream));
+        GPE_TRY(uid_map_ready(c));
+        if (next <= c->uid.map_max)
+            return fail(c, GPE_ERR_INVALID_ARG, "gpe_set_next_uid: next must be above every current uid");
+    }
+    c->uid.next = next;
+    return GPE_OK;
+}
+
+gpe_status gpe_find_uids(gpe_ctx *c, const uint32_t *uids, uint64_t k, uint32_t *index_out, float *pos_xy_out,
+                         float *prev_xy_out, float *radius_out)
+{
+    if (!c) return GPE_ERR_INVALID_ARG;
+    if (!c->uid.on) return fail(c, GPE_ERR_STATE, "gpe_find_uids: uids are off");
+    if (!uids) return fail(c, GPE_ERR_INVALID_ARG, "gpe_find_uids: NULL uids");
+    if (k > (1ull << 40)) return fail(c, GPE_ERR_INVALID_ARG, "gpe_find_uids: k too large");
+    if (k == 0) return GPE_OK;
+    if (c->n == 0) {                                           // no particles: every uid is absent
+        const float nan = nanf("");
+        for (uint64_t i = 0; i < k; ++i) {
+            if (index_out) index_out[i] = GPE_UID_ABSENT;
+            if (pos_xy_out) pos_xy_out[2 * i] = pos_xy_out[2 * i + 1] = nan;
+            if (prev_xy_out) prev_xy_out[2 * i] = prev_xy_out[2 * i + 1] = nan;
+            if (radius_out) radius_out[i] = nan;
+        }
+        return GPE_OK;
+    }
+    GPE_HIP(c, hipSetDevice(c->device));
+    GPE_HIP(c, hipStreamSynchronize(c->stream));
+    GPE_TRY(uid_map_ready(c));
+    // staging: pos f32[2k] | prev f32[2k] | radius f32[k] | index u32[k] | query u32[k]
+    GPE_TRY(uid_query_reserve(c, 28 * k));
+    float2 *d_pos = reinterpret_cast<float2 *>(c->uid.query);
+    float2 *d_prev = d_pos + k;
+    float *d_radius = reinterpret_cast<float *>(d_prev + k);
+    uint32_t *d_index = reinterpret_cast<uint32_t *>(d_radius + k);
+    uint32_t *d_query = d_index + k;
+    GPE_HIP(c, hipMemcpyAsync(d_query, uids, k * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    {
+        Scope s(c, "uids/find");
+        GPE_TRY(launch_uid_find(c, c->uid.map_keys, c->uid.map_vals, c->n, d_query, k, d_index,
+                                pos_xy_out ? d_pos : nullptr, prev_xy_out ? d_prev : nullptr,
+                                radius_out ? d_radius : nullptr));
+    }
+    if (index_out)
+        GPE_HIP(c, hipMemcpyAsync(index_out, d_index, k * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    if (pos_xy_out)
+        GPE_HIP(c, hipMemcpyAsync(pos_xy_out, d_pos, k * sizeof(float2), hipMemcpyDeviceToHost, c->stream));
+    if (prev_xy_out)
+        GPE_HIP(c, hipMemcpyAsync(prev_xy_out, d_prev, k * sizeof(float2), hipMemcpyDeviceToHost, c->stream));
+    if (radius_out)
+        GPE_HIP(c, hipMemcpyAsync(radius_out, d_radius, k * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    GPE_HIP(c, hipStreamSynchronize(c->stream));
+    return check_device_errors(c);
+}
+
+gpe_status gpe_remove_particles_by_uid(gpe_ctx *c, const uint32_t *uids, uint64_t k, uint64_t *n_removed)
+{
+    if (n_removed) *n_removed = 0;
+    GPE_TRY(check_removable(c, "gpe_remove_particles_by_uid"));
+    if (!c->uid.on) return fail(c, GPE_ERR_STATE, "gpe_remove_particles_by_uid: uids are off");
+    if (!uids) return fail(c, GPE_ERR_INVALID_ARG, "gpe_remove_particles_by_uid: NULL uids");
+    if (k > (1ull << 40)) return fail(c, GPE_ERR_INVALID_ARG, "gpe_remove_particles_by_uid: k too large");
+    if (k == 0) return GPE_OK;
+    GPE_HIP(c, hipSetDevice(c->device));
+    GPE_HIP(c, hipStreamSynchronize(c->stream));
+    GPE_TRY(uid_map_ready(c));
+    GPE_TRY(remove_reserve(c, c->n));
+    GPE_TRY(uid_query_reserve(c, 4 * k));
+    uint32_t *d_query = reinterpret_cast<uint32_t *>(c->uid.query);
+    GPE_HIP(c, hipMemcpyAsync(d_query, uids, k * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    {
+        Scope s(c, "uids/mark");
+        GPE_HIP(c, hipMemsetAsync(c->remove_ws.mask, 0, c->n, c->stream));
+        GPE_TRY(launch_uid_mark(c, c->uid.map_keys, c->uid.map_vals, c->n, d_query, k, c->remove_ws.mask));
+    }
+    return do_remove(c, c->remove_ws.mask, 0.f, 0.f, 0.f, n_removed);
 }
 
 gpe_status gpe_len(const gpe_ctx *c, uint64_t *n)
@@ -929,6 +1214,11 @@ static gpe_status locate(gpe_ctx *c, gpe_array what, const void **ptr, uint64_t 
         case GPE_CHUNK_OBJ_COUNT: *ptr = c->chunk_obj_count; *bytes = num_chunks(c) * 4; break;
         case GPE_INDIRECT_ARGS: *ptr = c->indirect_args; *bytes = 12; break;
         case GPE_ORDER_KEYS: *ptr = c->order_keys; *bytes = n * 4; break;
+        case GPE_UIDS:
+            if (!c->uid.on) return fail(c, GPE_ERR_STATE, "GPE_UIDS: uids are off (gpe_enable_uids)");
+            *ptr = c->uid.uids;
+            *bytes = n * 4;
+            break;
         default: return fail(c, GPE_ERR_INVALID_ARG, "unknown gpe_array");
     }
     return GPE_OK;
@@ -1072,6 +1362,7 @@ gpe_status gpe_set_counts(gpe_ctx *c, uint64_t n_total, uint64_t n_owned)
     GPE_TRY(need_particles(c));
     if (n_total == 0 || n_total > c->cap || n_owned > n_total)
         return fail(c, GPE_ERR_INVALID_ARG, "gpe_set_counts: need 0 < n_owned <= n_total <= capacity");
+    if (c->uid.on) return fail(c, GPE_ERR_UNSUPPORTED, "gpe_set_counts: not supported while uids are on");
     c->n = n_total;
     c->n_owned = n_owned;
     return GPE_OK;
@@ -1080,6 +1371,8 @@ gpe_status gpe_set_counts(gpe_ctx *c, uint64_t n_total, uint64_t n_owned)
 gpe_status gpe_use_order_keys(gpe_ctx *c, int32_t enable)
 {
     if (!c) return GPE_ERR_INVALID_ARG;
+    if (enable && c->uid.on)
+        return fail(c, GPE_ERR_UNSUPPORTED, "gpe_use_order_keys: sharded runs carry order keys, not uids (uids are on)");
     c->use_order_keys = enable != 0;
     return GPE_OK;
 }

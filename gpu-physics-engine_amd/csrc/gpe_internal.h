@@ -257,6 +257,21 @@ struct RemoveWorkspace {         // gpe_remove_particles* (k_remove.hip); alloca
     uint64_t mask_cap = 0;
 };
 
+struct UidState {               // opt-in particle uids (gpe_enable_uids; k_uids.hip)
+    bool on = false;
+    uint64_t next = 0;                           // the uid the next added particle gets (at most 2^32)
+    uint32_t *uids = nullptr;                    // cap entries; follows pos / prev / radius through every permutation
+    uint32_t *uids_copy = nullptr;               // its partner in the copy set (swapped with it)
+    // uid -> index map, allocated at first use: uids sorted ascending (keys) with their storage index (vals)
+    uint32_t *map_keys = nullptr, *map_vals = nullptr;
+    uint64_t map_cap = 0;
+    bool map_valid = false;                      // cleared by everything that changes n, the order or the uids
+    uint32_t map_max = 0;                        // the largest uid, with the map
+    uint32_t *dup = nullptr;                     // duplicate flag of the last map build
+    uint8_t *query = nullptr;                    // gpe_find_uids / _by_uid staging: queries and results
+    uint64_t query_cap = 0;                      // bytes
+};
+
 struct SortWorkspace {
     uint32_t *keys_b = nullptr, *vals_b = nullptr;   // ping-pong partners, cap entries each
     uint64_t cap = 0;
@@ -584,6 +599,7 @@ struct gpe_ctx {
 
     gpe::SortWorkspace sort_ws;
     gpe::RemoveWorkspace remove_ws;
+    gpe::UidState uid;
     gpe::ScanWorkspace scan_ws;
     gpe::OnesweepWorkspace os_ws;
     gpe::NativeState native;
@@ -689,8 +705,10 @@ gpe_status onesweep_sort(gpe_ctx *c, uint32_t *keys, uint32_t *vals, uint32_t *k
 uint64_t remove_tiles(uint64_t n);
 gpe_status launch_remove_count(gpe_ctx *c, const uint8_t *mask, float x, float y, float rr, uint32_t *tile_count,
                                unsigned long long *tile_key, unsigned long long *max_key);
+// uids != NULL (uids on): each survivor's uid moves to uids_out as well
 gpe_status launch_remove_scatter(gpe_ctx *c, const uint8_t *mask, float x, float y, float rr,
-                                 const uint32_t *tile_scanned);
+                                 const uint32_t *tile_scanned, const uint32_t *uids = nullptr,
+                                 uint32_t *uids_out = nullptr);
 // native pipeline (k_native.hip)
 gpe_status native_configure(gpe_ctx *c);
 bool native_should_run(gpe_ctx *c);

@@ -10,7 +10,9 @@
 //   (2) inclusive_scan (k_scan.hip) over the per-tile counts; the host reads the total and the key back.
 //   (3) k_remove_scatter: the same tiles in the same order; a survivor's slot is the tile's scanned base + the
 //       survivors of the earlier rounds + those of the earlier waves of its round (LDS) + those below its lane
-//       (ballot + mbcnt).
+//       (ballot + mbcnt).  The UIDS instantiations also move each survivor's uid (gpe_enable_uids) to that slot:
+//       R 4 B + W 4 B more per survivor.  The uid pointers come last, so the uid-off instantiations read their
+//       arguments where they always did and never touch the two extra ones.
 // Bytes (circle form): count R 8 B per particle (pos) + 4 B per survivor (radius); scatter R 8 B per particle (pos, the
 // predicate) and R 12 B + W 20 B per survivor.  Mask form: the predicate reads 1 B per particle instead of pos, and the
 // scatter R 20 B + W 20 B per survivor.  100 M particles: count 0.22 ms, scatter 0.79 ms (profiles/remove/).
@@ -142,14 +144,16 @@ __global__ __launch_bounds__(kRemoveBlock) void k_remove_max_key(const unsigned 
 }
 
 // (3) stable scatter of the survivors into the copy set; tile_scanned = inclusive scan of (1)'s counts
-template <bool MASK>
+template <bool MASK, bool UIDS>
 __global__ __launch_bounds__(kRemoveBlock) void k_remove_scatter(RemovePredicate P, const float2 *__restrict__ pos,
                                                                  const float2 *__restrict__ prev,
                                                                  const float *__restrict__ radius, uint64_t n,
                                                                  const uint32_t *__restrict__ tile_scanned,
                                                                  float2 *__restrict__ pos_out,
                                                                  float2 *__restrict__ prev_out,
-                                                                 float *__restrict__ radius_out)
+                                                                 float *__restrict__ radius_out,
+                                                                 const uint32_t *__restrict__ uids,
+                                                                 uint32_t *__restrict__ uids_out)
 {
     __shared__ uint32_t s_cnt[kRemoveRounds][kRemoveWaves];
     const uint64_t first = (uint64_t)blockIdx.x * kRemoveTile + threadIdx.x;
@@ -179,6 +183,7 @@ __global__ __launch_bounds__(kRemoveBlock) void k_remove_scatter(RemovePredicate
             pos_out[dst] = pos[i];
             prev_out[dst] = prev[i];
             radius_out[dst] = radius[i];
+            if constexpr (UIDS) uids_out[dst] = uids[i];
         }
         base += round;
     }
@@ -207,16 +212,15 @@ gpe_status launch_remove_count(gpe_ctx *c, const uint8_t *mask, float x, float y
 }
 
 gpe_status launch_remove_scatter(gpe_ctx *c, const uint8_t *mask, float x, float y, float rr,
-                                 const uint32_t *tile_scanned)
+                                 const uint32_t *tile_scanned, const uint32_t *uids, uint32_t *uids_out)
 {
     const uint64_t tiles = remove_tiles(c->n);
     const RemovePredicate P{mask, x, y, rr};
-    if (mask)
-        hipLaunchKernelGGL(k_remove_scatter<true>, dim3((uint32_t)tiles), dim3(kRemoveBlock), 0, c->stream, P, c->pos,
-                           c->prev, c->radius, c->n, tile_scanned, c->pos_copy, c->prev_copy, c->radius_copy);
-    else
-        hipLaunchKernelGGL(k_remove_scatter<false>, dim3((uint32_t)tiles), dim3(kRemoveBlock), 0, c->stream, P, c->pos,
-                           c->prev, c->radius, c->n, tile_scanned, c->pos_copy, c->prev_copy, c->radius_copy);
+    const bool carry = uids != nullptr;
+    const auto kern = mask ? (carry ? k_remove_scatter<true, true> : k_remove_scatter<true, false>)
+                           : (carry ? k_remove_scatter<false, true> : k_remove_scatter<false, false>);
+    hipLaunchKernelGGL(kern, dim3((uint32_t)tiles), dim3(kRemoveBlock), 0, c->stream, P, c->pos, c->prev, c->radius,
+                       c->n, tile_scanned, c->pos_copy, c->prev_copy, c->radius_copy, uids, uids_out);
     GPE_HIP(c, hipGetLastError());
     return GPE_OK;
 }

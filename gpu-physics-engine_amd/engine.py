@@ -270,6 +270,52 @@ class ParticleSystem:
                       C.byref(removed))
         return removed.value
 
+    # Particle uids (not in the reference; include/gpe.h): an opt-in u32 per particle that the library carries through
+    # every re-sort, removal and growth, so that a host can key its own per-particle data (colours, tracers) by uid.
+    def enable_uids(self, on=True):
+        """gpe_enable_uids: off -> on gives uid = storage index and next_uid = len(); on -> on keeps them; off drops them."""
+        self.ctx.call("gpe_enable_uids", 1 if on else 0)
+
+    def uids(self):
+        """The uids in storage order (u32[len()], as download_particle_buffers orders the particles)."""
+        return self.ctx.download(L.UIDS, np.uint32)
+
+    def set_uids(self, uids):
+        """gpe_set_uids: uids[i] for storage index i, pairwise distinct; next_uid becomes max + 1."""
+        u = np.ascontiguousarray(uids, np.uint32).reshape(-1)
+        self.ctx.call("gpe_set_uids", _ptr(u), u.shape[0])
+
+    def next_uid(self):
+        """The uid the next added particle gets (GpeError GPE_ERR_STATE while uids are off)."""
+        n = C.c_uint64()
+        self.ctx.call("gpe_next_uid", C.byref(n))
+        return n.value
+
+    def set_next_uid(self, next_uid):
+        self.ctx.call("gpe_set_next_uid", int(next_uid))
+
+    def find_uids(self, uids):
+        """gpe_find_uids -> (index u32[k], pos f32[k,2], prev f32[k,2], radius f32[k]): the particles' current storage
+        indices (L.UID_ABSENT for an unknown uid) and their bits (NaN when absent)."""
+        q = np.ascontiguousarray(uids, np.uint32).reshape(-1)
+        k = q.shape[0]
+        index = np.empty(max(k, 1), np.uint32)
+        pos = np.empty((max(k, 1), 2), np.float32)
+        prev = np.empty((max(k, 1), 2), np.float32)
+        rad = np.empty(max(k, 1), np.float32)
+        qq = q if k else np.zeros(1, np.uint32)
+        self.ctx.call("gpe_find_uids", _ptr(qq), k, _ptr(index), _ptr(pos), _ptr(prev), _ptr(rad))
+        return index[:k], pos[:k], prev[:k], rad[:k]
+
+    def remove_particles_by_uid(self, uids):
+        """gpe_remove_particles_by_uid: the particles with these uids leave (unknown uids are ignored, duplicates count
+        once); otherwise as remove_particles.  Returns the number removed."""
+        q = np.ascontiguousarray(uids, np.uint32).reshape(-1)
+        qq = q if q.shape[0] else np.zeros(1, np.uint32)
+        removed = C.c_uint64()
+        self.ctx.call("gpe_remove_particles_by_uid", _ptr(qq), q.shape[0], C.byref(removed))
+        return removed.value
+
     def len(self):
         n = C.c_uint64()
         self.ctx.call("gpe_len", C.byref(n))
@@ -461,6 +507,39 @@ class State:
         """ParticleSystem.remove_particles_in_circle: the particles inside the disc leave; returns how many."""
         return self.particles.remove_particles_in_circle(center, radius)
 
+    def enable_uids(self, on=True):
+        """ParticleSystem.enable_uids."""
+        self.particles.enable_uids(on)
+
+    def uids(self):
+        return self.particles.uids()
+
+    def set_uids(self, uids):
+        self.particles.set_uids(uids)
+
+    def next_uid(self):
+        return self.particles.next_uid()
+
+    def set_next_uid(self, next_uid):
+        self.particles.set_next_uid(next_uid)
+
+    def find_uids(self, uids):
+        """ParticleSystem.find_uids -> (index, pos, prev, radius)."""
+        return self.particles.find_uids(uids)
+
+    def remove_particles_by_uid(self, uids):
+        """ParticleSystem.remove_particles_by_uid: returns how many left."""
+        return self.particles.remove_particles_by_uid(uids)
+
+    def _uids_on(self):
+        try:
+            self.particles.next_uid()
+        except L.GpeError as e:
+            if e.status == L.GPE_ERR_STATE:
+                return False
+            raise
+        return True
+
     def positions(self):
         return self.ctx.download(L.POS, np.float32, (-1, 2))
 
@@ -473,9 +552,14 @@ class State:
     # Checkpoint / restore (the reference's only state dump is download_particle_buffers,
     # particle_system.rs:258-265): the three arrays the step evolves plus the constants a step depends on.
     def save(self, path):
-        """Binary snapshot (numpy .npz, no pickle): positions, previous positions, radii, world, gravity."""
+        """Binary snapshot (numpy .npz, no pickle): positions, previous positions, radii, world, gravity; with uids on
+        also the uids and next_uid."""
+        extra = {}
+        if self._uids_on():
+            extra = dict(uids=self.uids(), next_uid=np.array([self.next_uid()], np.uint64))
         np.savez(path, format=np.array([1], np.int32), pos=self.positions(), prev=self.previous_positions(),
-                 radius=self.radii(), world=np.array(self.world, np.float32), gravity=np.array(self.gravity, np.float32))
+                 radius=self.radii(), world=np.array(self.world, np.float32), gravity=np.array(self.gravity, np.float32),
+                 **extra)
 
     @classmethod
     def load(cls, path, mode=None, device=-1):
@@ -484,8 +568,12 @@ class State:
         with np.load(path, allow_pickle=False) as d:
             if int(d["format"][0]) != 1:
                 raise ValueError("unknown snapshot format")
-            return cls(d["pos"], d["radius"], world=tuple(d["world"]), gravity=tuple(d["gravity"]), mode=mode,
-                       prev=d["prev"], device=device)
+            st = cls(d["pos"], d["radius"], world=tuple(d["world"]), gravity=tuple(d["gravity"]), mode=mode,
+                     prev=d["prev"], device=device)
+            if "uids" in d.files:
+                st.set_uids(d["uids"])
+                st.set_next_uid(int(d["next_uid"][0]))
+            return st
 
     def close(self):
         self.ctx.close()

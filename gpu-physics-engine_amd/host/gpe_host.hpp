@@ -178,6 +178,41 @@ class ParticleSystem {
         ctx_->call(gpe_remove_particles_in_circle(ctx_->raw(), center.x, center.y, radius, &removed));
         return removed;
     }
+    // not in the reference: opt-in particle uids that survive re-sorts, removal and growth (include/gpe.h)
+    void enable_uids(bool on = true) { ctx_->call(gpe_enable_uids(ctx_->raw(), on ? 1 : 0)); }
+    std::vector<uint32_t> uids() const { return ctx_->download<uint32_t>(GPE_UIDS); }        // storage order
+    void set_uids(const std::vector<uint32_t> &uids)
+    {
+        ctx_->call(gpe_set_uids(ctx_->raw(), uids.data(), uids.size()));
+    }
+    uint64_t next_uid() const { uint64_t n = 0; ctx_->call(gpe_next_uid(ctx_->raw(), &n)); return n; }
+    void set_next_uid(uint64_t next) { ctx_->call(gpe_set_next_uid(ctx_->raw(), next)); }
+    // index[i] = storage index of uids[i] or GPE_UID_ABSENT; pos / prev / radius its bits (NaN when absent)
+    struct UidLookup {
+        std::vector<uint32_t> index;
+        std::vector<Vec2> pos, prev;
+        std::vector<float> radius;
+    };
+    UidLookup find_uids(const std::vector<uint32_t> &uids) const
+    {
+        UidLookup r;
+        r.index.resize(uids.size());
+        r.pos.resize(uids.size());
+        r.prev.resize(uids.size());
+        r.radius.resize(uids.size());
+        const uint32_t none = 0;
+        ctx_->call(gpe_find_uids(ctx_->raw(), uids.empty() ? &none : uids.data(), uids.size(), r.index.data(),
+                                 reinterpret_cast<float *>(r.pos.data()), reinterpret_cast<float *>(r.prev.data()),
+                                 r.radius.data()));
+        return r;
+    }
+    uint64_t remove_particles_by_uid(const std::vector<uint32_t> &uids)
+    {
+        uint64_t removed = 0;
+        const uint32_t none = 0;
+        ctx_->call(gpe_remove_particles_by_uid(ctx_->raw(), uids.empty() ? &none : uids.data(), uids.size(), &removed));
+        return removed;
+    }
     size_t len() const { uint64_t n = 0; ctx_->call(gpe_len(ctx_->raw(), &n)); return n; }               // :275
     float get_max_radius() const { float r = 0; ctx_->call(gpe_max_radius(ctx_->raw(), &r)); return r; } // :291
     void sort_by_cell_id(float /*cell_size: the Grid's, state.rs:123*/) { ctx_->call(gpe_morton_resort(ctx_->raw())); }

@@ -144,6 +144,47 @@ gpe_status gpe_set_mouse(gpe_ctx *ctx, int32_t pressed, float x, float y);
 gpe_status gpe_set_world(gpe_ctx *ctx, float width, float height);
 gpe_status gpe_set_gravity(gpe_ctx *ctx, float gx, float gy);
 
+/* ---- particle uids (not in the reference) ----------------------------------------------------------- */
+/* The library moves particles around in storage: a re-sort permutes them, a removal compacts them, set / add rebuild
+ * or append.  A uid is an opt-in u32 per particle that the library carries through every one of those moves, so that
+ * a host can keep its own per-particle data (colours, tracers, "the particle I spawned") keyed by uid.  (Not to be
+ * confused with GPE_PARTICLE_IDS, the re-sort's permutation scratch, particle_system.rs:254.)
+ *  - Off by default.  While off, every other entry point behaves and launches exactly as without uids.
+ *  - While on:  gpe_set_particles gives uid = storage index (0..n-1) and next = n;  gpe_add_particles gives the k new
+ *    particles next .. next+k-1 in input order and next += k -- GPE_ERR_STATE, nothing added, when next + k > 2^32;
+ *    re-sorts (gpe_morton_resort, GPE_STEP_RESORT in gpe_step / gpe_run) permute the uids with pos / prev / radius;
+ *    gpe_remove_particles* compact them with the survivors; gpe_reserve and growth keep them.  Uids are never reused.
+ *  - gpe_download / gpe_array_bytes / gpe_device_ptr(GPE_UIDS): u32[n], in storage order like GPE_POS.
+ *  - Sharded runs carry GPE_ORDER_KEYS instead: gpe_enable_uids / gpe_set_uids on a context with shard state, order
+ *    keys or an active cell box, and gpe_shard_set_particles / gpe_use_order_keys(ctx, 1) / gpe_set_counts on a
+ *    context whose uids are on, return GPE_ERR_UNSUPPORTED.
+ *  - A NULL context or array: GPE_ERR_INVALID_ARG.
+ * Lookups go through a uid -> index map (the uids sorted on the device, csrc/k_uids.hip), rebuilt by the first lookup
+ * after anything has changed the uids or their order. */
+#define GPE_UID_ABSENT 0xffffffffu
+/* enable != 0, off -> on: uid = storage index (0..n-1), next = n (also with no particles yet).  On -> on: nothing
+ * changes.  enable == 0: the uids are dropped (their buffers freed). */
+gpe_status gpe_enable_uids(gpe_ctx *ctx, int32_t enable);
+/* Replace every particle's uid: uids[i] for storage index i; n must equal gpe_len (>= 1, else GPE_ERR_STATE).  The
+ * uids must be pairwise distinct (checked on the device).  Afterwards uids are on and next = max(uids) + 1 (2^32 for a
+ * uid 0xffffffff).  A duplicate, NULL uids or a wrong n: GPE_ERR_INVALID_ARG and the previous uid state -- on / off,
+ * values, next -- untouched.  Synchronises. */
+gpe_status gpe_set_uids(gpe_ctx *ctx, const uint32_t *uids, uint64_t n);
+/* The uid the next added particle gets (at most 2^32).  GPE_ERR_STATE while uids are off: how a host asks whether
+ * they are on. */
+gpe_status gpe_next_uid(const gpe_ctx *ctx, uint64_t *next);
+/* next <= the largest current uid or next > 2^32: GPE_ERR_INVALID_ARG.  GPE_ERR_STATE while uids are off. */
+gpe_status gpe_set_next_uid(gpe_ctx *ctx, uint64_t next);
+/* For each of the k uids: index_out[i] = the particle's current storage index, or GPE_UID_ABSENT; pos_xy_out[2i..2i+1],
+ * prev_xy_out[2i..2i+1], radius_out[i] = that particle's bits, or quiet NaN for an absent uid.  Every output may be
+ * NULL.  Duplicate queries are allowed, k == 0 is OK.  Blocks like gpe_download.  GPE_ERR_STATE while uids are off. */
+gpe_status gpe_find_uids(gpe_ctx *ctx, const uint32_t *uids, uint64_t k, uint32_t *index_out, float *pos_xy_out,
+                         float *prev_xy_out, float *radius_out);
+/* Remove the particles whose uid is among the k uids (absent ones are ignored, a duplicate counts once).  Otherwise
+ * exactly gpe_remove_particles with that mask: survivors keep their order, nothing removed leaves the context
+ * untouched, removing every particle is GPE_ERR_INVALID_ARG.  GPE_ERR_STATE while uids are off. */
+gpe_status gpe_remove_particles_by_uid(gpe_ctx *ctx, const uint32_t *uids, uint64_t k, uint64_t *n_removed);
+
 /* ---- grid (src/grid/grid.rs) ---------------------------------------------------------------- */
 /* Grid::compute_cell_size (:159-161) */
 float gpe_compute_cell_size(float max_obj_radius);
@@ -219,13 +260,14 @@ typedef enum gpe_array {
     GPE_NUM_COLLISION_CELLS = 8, /* u32[1] last element of the scanned chunk counts               */
     GPE_CHUNK_OBJ_COUNT = 9,   /* u32[n]   CollisionCellBuilder::chunk_obj_count (scanned)        */
     GPE_INDIRECT_ARGS = 10,    /* u32[3]   collision_cell_builder.wgsl:96-109                     */
-    GPE_ORDER_KEYS = 11        /* u32[n]   sharded runs: global object index of each local particle */
+    GPE_ORDER_KEYS = 11,       /* u32[n]   sharded runs: global object index of each local particle */
+    GPE_UIDS = 12              /* u32[n]   particle uids (gpe_enable_uids); GPE_ERR_STATE while off  */
 } gpe_array;
 /* Blocks until the stream is idle, then copies exactly `bytes` (must equal the array's size). */
 gpe_status gpe_download(gpe_ctx *ctx, gpe_array what, void *dst, uint64_t bytes);
 gpe_status gpe_array_bytes(const gpe_ctx *ctx, gpe_array what, uint64_t *bytes);
 /* Render hand-off (particle_drawer.wgsl:11-13 reads these three as storage buffers): the device
- * pointer stays valid until the next set/add_particles or morton_resort. */
+ * pointer stays valid until the next set/add_particles or morton_resort (GPE_UIDS: the same). */
 gpe_status gpe_device_ptr(gpe_ctx *ctx, gpe_array what, void **device_ptr, uint64_t *bytes);
 
 /* ---- GPU primitives (src/utils/radix_sort, src/utils/prefix_sum) ----------------------------- */
