@@ -143,9 +143,13 @@ SYMBOLS = [
     ("gpe_set_mouse", _I32, [_VP, _I32, _F, _F]),
     ("gpe_set_world", _I32, [_VP, _F, _F]),
     ("gpe_set_gravity", _I32, [_VP, _F, _F]),
+    ("gpe_world", _I32, [_VP, C.POINTER(_F), C.POINTER(_F)]),
+    ("gpe_gravity", _I32, [_VP, C.POINTER(_F), C.POINTER(_F)]),
+    ("gpe_mouse", _I32, [_VP, C.POINTER(_I32), C.POINTER(_F), C.POINTER(_F)]),
     ("gpe_compute_cell_size", _F, [_F]),
     ("gpe_grid_set_max_radius", _I32, [_VP, _F]),
     ("gpe_cell_size", _I32, [_VP, C.POINTER(_F)]),
+    ("gpe_grid_max_radius", _I32, [_VP, C.POINTER(_F)]),
     ("gpe_grid_build", _I32, [_VP]),
     ("gpe_grid_sort", _I32, [_VP]),
     ("gpe_grid_update", _I32, [_VP]),

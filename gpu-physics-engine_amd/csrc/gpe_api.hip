@@ -1091,6 +1091,31 @@ gpe_status gpe_set_gravity(gpe_ctx *c, float gx, float gy)
     return GPE_OK;
 }
 
+gpe_status gpe_world(const gpe_ctx *c, float *w, float *h)
+{
+    if (!c || !w || !h) return GPE_ERR_INVALID_ARG;
+    *w = c->cfg.world_width;
+    *h = c->cfg.world_height;
+    return GPE_OK;
+}
+
+gpe_status gpe_gravity(const gpe_ctx *c, float *gx, float *gy)
+{
+    if (!c || !gx || !gy) return GPE_ERR_INVALID_ARG;
+    *gx = c->cfg.gravity_x;
+    *gy = c->cfg.gravity_y;
+    return GPE_OK;
+}
+
+gpe_status gpe_mouse(const gpe_ctx *c, int32_t *pressed, float *x, float *y)
+{
+    if (!c || !pressed || !x || !y) return GPE_ERR_INVALID_ARG;
+    *pressed = (int32_t)c->mouse_pressed;
+    *x = c->mouse_x;
+    *y = c->mouse_y;
+    return GPE_OK;
+}
+
 gpe_status gpe_morton_resort(gpe_ctx *c)
 {
     GPE_TRY(need_particles(c));
@@ -1120,6 +1145,13 @@ gpe_status gpe_cell_size(const gpe_ctx *c, float *cs)
 {
     if (!c || !cs) return GPE_ERR_INVALID_ARG;
     *cs = c->cell_size;
+    return GPE_OK;
+}
+
+gpe_status gpe_grid_max_radius(const gpe_ctx *c, float *r)
+{
+    if (!c || !r) return GPE_ERR_INVALID_ARG;
+    *r = c->grid_max_radius;
     return GPE_OK;
 }
 

@@ -49,6 +49,24 @@ class Context:
         if stream is not None:          # a hipStream_t the caller owns and keeps alive (gpe_set_stream)
             self.call("gpe_set_stream", C.c_void_p(int(stream)))
 
+    def world(self):
+        """gpe_world: the world size the context's wall clamp uses, however it was set."""
+        w, h = C.c_float(), C.c_float()
+        self.call("gpe_world", C.byref(w), C.byref(h))
+        return (w.value, h.value)
+
+    def gravity(self):
+        """gpe_gravity: the context's gravity, however it was set."""
+        gx, gy = C.c_float(), C.c_float()
+        self.call("gpe_gravity", C.byref(gx), C.byref(gy))
+        return (gx.value, gy.value)
+
+    def mouse(self):
+        """gpe_mouse -> (pressed, (x, y)): the mouse state the next integration uses."""
+        pressed, x, y = C.c_int32(), C.c_float(), C.c_float()
+        self.call("gpe_mouse", C.byref(pressed), C.byref(x), C.byref(y))
+        return (bool(pressed.value), (x.value, y.value))
+
     def close(self):
         if getattr(self, "h", None):
             self.lib.gpe_destroy(self.h)
@@ -381,6 +399,13 @@ class Grid:
         self.ctx.call("gpe_cell_size", C.byref(cs))
         return cs.value
 
+    def max_radius(self):
+        """gpe_grid_max_radius: the radius the cell size is derived from (new_without_camera's, or the particle
+        system's max radius since the last set / add / remove)."""
+        r = C.c_float()
+        self.ctx.call("gpe_grid_max_radius", C.byref(r))
+        return r.value
+
     def build_cell_ids(self):
         self.ctx.call("gpe_grid_build")        # grid.rs:296-306
 
@@ -550,21 +575,34 @@ class State:
         return self.ctx.download(L.RADIUS, np.float32)
 
     # Checkpoint / restore (the reference's only state dump is download_particle_buffers,
-    # particle_system.rs:258-265): the three arrays the step evolves plus the constants a step depends on.
+    # particle_system.rs:258-265): the three arrays the step evolves plus the constants a step depends on, as the
+    # context holds them (they may have been set through ctx.call as well as through this class).
     def save(self, path):
         """Binary snapshot (numpy .npz, no pickle): positions, previous positions, radii, world, gravity; with uids on
-        also the uids and next_uid."""
+        also the uids and next_uid; with the mouse pressed its position (`mouse`); with a grid radius other than the
+        one gpe_set_particles derives from the saved radii (Grid.new_without_camera) that radius (`grid_max_radius`)."""
         extra = {}
         if self._uids_on():
-            extra = dict(uids=self.uids(), next_uid=np.array([self.next_uid()], np.uint64))
+            extra.update(uids=self.uids(), next_uid=np.array([self.next_uid()], np.uint64))
+        pressed, at = self.ctx.mouse()
+        if pressed:
+            extra.update(mouse=np.array(at, np.float32))
+        radius = self.radii()
+        # load() sets the particles, whose grid radius is then the radius of largest magnitude (last on ties, sign kept:
+        # gpe_set_particles); anything else -- an override, or an add's fmaxf rule with negative radii -- is written
+        a = np.abs(radius)
+        set_r = radius[len(a) - 1 - int(np.argmax(a[::-1]))] if len(a) else np.float32(0)
+        grid_r = np.array([self.grid.max_radius()], np.float32)
+        if grid_r.view(np.uint32)[0] != np.array([set_r], np.float32).view(np.uint32)[0]:
+            extra.update(grid_max_radius=grid_r)
         np.savez(path, format=np.array([1], np.int32), pos=self.positions(), prev=self.previous_positions(),
-                 radius=self.radii(), world=np.array(self.world, np.float32), gravity=np.array(self.gravity, np.float32),
-                 **extra)
+                 radius=radius, world=np.array(self.ctx.world(), np.float32),
+                 gravity=np.array(self.ctx.gravity(), np.float32), **extra)
 
     @classmethod
     def load(cls, path, mode=None, device=-1):
         """A State that continues from a snapshot written by save(): the next update() yields the same bits as
-        the saved run's next update() would have (the step has no hidden state beyond these arrays)."""
+        the saved run's next update() would have (the step has no hidden state beyond these arrays and constants)."""
         with np.load(path, allow_pickle=False) as d:
             if int(d["format"][0]) != 1:
                 raise ValueError("unknown snapshot format")
@@ -573,6 +611,10 @@ class State:
             if "uids" in d.files:
                 st.set_uids(d["uids"])
                 st.set_next_uid(int(d["next_uid"][0]))
+            if "mouse" in d.files:
+                st.particles.mouse_click_callback(True, tuple(d["mouse"]))
+            if "grid_max_radius" in d.files:
+                st.ctx.call("gpe_grid_set_max_radius", float(d["grid_max_radius"][0]))
             return st
 
     def close(self):

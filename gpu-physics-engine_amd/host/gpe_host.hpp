@@ -58,6 +58,17 @@ class Context {
     Context &operator=(const Context &) = delete;
     gpe_ctx *raw() const { return ctx_; }
     void call(gpe_status s) const { check(s, ctx_); }
+    // the step constants the context holds, however they were set
+    Vec2 world() const { Vec2 w{}; call(gpe_world(ctx_, &w.x, &w.y)); return w; }
+    Vec2 gravity() const { Vec2 g{}; call(gpe_gravity(ctx_, &g.x, &g.y)); return g; }
+    bool mouse(Vec2 *at) const
+    {
+        int32_t pressed = 0;
+        Vec2 p{};
+        call(gpe_mouse(ctx_, &pressed, &p.x, &p.y));
+        if (at) *at = p;
+        return pressed != 0;
+    }
     static void check(gpe_status s, const gpe_ctx *c)
     {
         if (s != GPE_OK) throw Error(s, gpe_last_error(c));
@@ -261,6 +272,7 @@ class Grid {
     Grid(const Context &ctx, const ParticleSystem &) : ctx_(&ctx) {}
     static float compute_cell_size(float max_obj_radius) { return gpe_compute_cell_size(max_obj_radius); }   // :159
     float cell_size() const { float cs = 0; ctx_->call(gpe_cell_size(ctx_->raw(), &cs)); return cs; }
+    float max_radius() const { float r = 0; ctx_->call(gpe_grid_max_radius(ctx_->raw(), &r)); return r; }   // cell size / 2.2
     void build_cell_ids() { ctx_->call(gpe_grid_build(ctx_->raw())); }        // :296-306
     void sort_map() { ctx_->call(gpe_grid_sort(ctx_->raw())); }               // :310-312
     void update() { ctx_->call(gpe_grid_update(ctx_->raw())); }               // :322-332

@@ -143,6 +143,11 @@ gpe_status gpe_set_mouse(gpe_ctx *ctx, int32_t pressed, float x, float y);
  * new_from_buffers hard-codes 1920x1080, particle_system.rs:86) */
 gpe_status gpe_set_world(gpe_ctx *ctx, float width, float height);
 gpe_status gpe_set_gravity(gpe_ctx *ctx, float gx, float gy);
+/* Read back the step constants the context holds, however they were set (gpe_create's config or the
+ * setters above): world size, gravity, and the mouse button state and position (pressed 0 / 1). */
+gpe_status gpe_world(const gpe_ctx *ctx, float *width, float *height);
+gpe_status gpe_gravity(const gpe_ctx *ctx, float *gx, float *gy);
+gpe_status gpe_mouse(const gpe_ctx *ctx, int32_t *pressed, float *x, float *y);
 
 /* ---- particle uids (not in the reference) ----------------------------------------------------------- */
 /* The library moves particles around in storage: a re-sort permutes them, a removal compacts them, set / add rebuild
@@ -189,9 +194,16 @@ gpe_status gpe_remove_particles_by_uid(gpe_ctx *ctx, const uint32_t *uids, uint6
 /* Grid::compute_cell_size (:159-161) */
 float gpe_compute_cell_size(float max_obj_radius);
 /* Grid::new_without_camera(ctx, max_obj_radius, &particles) (:74): override the radius the cell
- * size is derived from (default: the particle system's max radius, Grid::new :66-71). */
+ * size is derived from (default: the particle system's max radius, Grid::new :66-71).
+ * Below max_radius / 1.1 the cell is narrower than the largest particle: such a particle can lie in two
+ * cells of one colour, and the colour passes then move it from two lanes at once (so does the reference's
+ * collision_solver.wgsl).  The step still runs, but its bits are not reproducible; at or above that
+ * radius every step is. */
 gpe_status gpe_grid_set_max_radius(gpe_ctx *ctx, float max_obj_radius);
 gpe_status gpe_cell_size(const gpe_ctx *ctx, float *cell_size);     /* Grid::cell_size (:163) */
+/* The radius the cell size is derived from: the last gpe_grid_set_max_radius value, or gpe_max_radius
+ * after set / add / remove (cell size = this * 2.2 in binary32, which is not exactly invertible). */
+gpe_status gpe_grid_max_radius(const gpe_ctx *ctx, float *max_obj_radius);
 gpe_status gpe_grid_build(gpe_ctx *ctx);     /* Grid::build_cell_ids (:296-306), K5          */
 gpe_status gpe_grid_sort(gpe_ctx *ctx);      /* Grid::sort_map (:310-312), 4N-pair sort      */
 gpe_status gpe_grid_update(gpe_ctx *ctx);    /* Grid::update (:322-332) = build + sort       */

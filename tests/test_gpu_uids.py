@@ -365,6 +365,16 @@ def test_save_load(mode):
         off.save(path)
         with np.load(path) as z:
             assert sorted(z.files) == ["format", "gravity", "pos", "prev", "radius", "world"]
+        # the mouse pressed and an overridden grid radius add exactly their own fields, still format 1
+        off.particles.mouse_click_callback(True, (10.0, 20.0))
+        off.ctx.call("gpe_grid_set_max_radius", 2.0 * float(off.particles.get_max_radius()))
+        extra = os.path.join(d, "extra.npz")
+        off.save(extra)
+        with np.load(extra) as z:
+            assert sorted(z.files) == ["format", "gravity", "grid_max_radius", "mouse", "pos", "prev", "radius", "world"]
+            assert int(z["format"][0]) == 1
+        off.particles.mouse_click_callback(False, (10.0, 20.0))
+        off.ctx.call("gpe_grid_set_max_radius", float(off.particles.get_max_radius()))
         back = gpe.State.load(path, mode=MODES[mode])
         assert _status_of(lambda: back.next_uid()) == L.GPE_ERR_STATE
         assert np.array_equal(back.positions(), off.positions())
