@@ -740,7 +740,7 @@ static gpe_status check_device_errors(gpe_ctx *c)
 static gpe_status reconfigure(gpe_ctx *c)
 {
     if (c->cfg.mode == GPE_MODE_NATIVE && c->n > 0) return native_configure(c);
-    c->native.eligible = false;
+    c->native.policy.eligible = false;
     return GPE_OK;
 }
 
@@ -769,15 +769,16 @@ gpe_status gpe_get_pipeline_info(gpe_ctx *c, gpe_pipeline_info *info)
     const NativeState &N = c->native;
     if (c->cfg.mode != GPE_MODE_NATIVE) { out.pipeline = GPE_PIPELINE_COMPAT; out.reason = GPE_REASON_MODE_COMPAT; }
     else if (c->n == 0) { out.pipeline = GPE_PIPELINE_COMPAT; out.reason = GPE_REASON_NO_PARTICLES; }
-    else if (N.eligible || ((N.force || c->use_order_keys) && N.in_box)) { out.pipeline = GPE_PIPELINE_NATIVE; out.reason = GPE_REASON_NONE; }
+    else if (N.policy.eligible || ((N.force || c->use_order_keys) && N.in_box)) { out.pipeline = GPE_PIPELINE_NATIVE; out.reason = GPE_REASON_NONE; }
     else { out.pipeline = GPE_PIPELINE_COMPAT; out.reason = N.reason; }
     out.sort_passes = (uint32_t)N.passes;
     out.native_steps = N.native_steps;
     out.compat_steps = N.compat_steps;
     if (N.host_stat) {
-        out.window_max = N.host_stat[kStatWindowMax];
-        out.arena_slots = N.host_stat[kStatArena]; out.overflow_tiles = N.host_stat[kStatOverflow];
-        out.overflow_subtiles = N.host_stat[kStatSubTiles]; out.overflow_spills = N.host_stat[kStatSpills];
+        const NativeStats s = native_read_stats(N);
+        out.window_max = s.window_max;
+        out.arena_slots = s.arena; out.overflow_tiles = s.overflow;
+        out.overflow_subtiles = s.sub_tiles; out.overflow_spills = s.spills;
     }
     if (N.tile_ctl) {
         uint32_t sorts = 0, seen = 0;

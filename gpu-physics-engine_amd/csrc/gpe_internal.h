@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../include/gpe.h"
+#include "native_policy.h"
 
 namespace gpe {
 
@@ -313,7 +314,7 @@ constexpr int kNativeCtlSorts = 14;         // tile_ctl word: running count of s
 constexpr int kNativeCtlSortsSeen = 38;     // its copy in the line the tiles only read (k_native.hip kCtlSortsSeen)
 // Native (N-key sort + LDS cell windows) pipeline state
 struct NativeState {
-    bool eligible = false;           // every particle inside the world box, grid small enough, windows not over-dense
+    NativePolicy policy;             // the launch heuristics and their counters (native_policy.h)
     bool in_box = false;             // the configuration-time box check passed (density is the only possible obstacle)
     int32_t gx = 0, gy = 0;          // home cell columns / rows: cx in [0,gx), cy in [0,gy)
     int passes = 4;                  // radix passes needed for morton(gx-1, gy-1)
@@ -347,19 +348,8 @@ struct NativeState {
                                      // first pass); the sorted ids and the block table describe that grouping
     bool sort_state_valid = false;   // sorted_key / sorted ids / block table belong to the current particle set and box
     uint64_t sorted_n = 0;           // ... of this many particles
-    uint32_t sort_hold = 0;          // steps left that sort unconditionally (the scene sorted on most steps anyway)
-    uint32_t watch_steps = 0, watch_sorts = 0;   // the passes' counter over the current 64-step window
-    bool watch_valid = false;
-    uint32_t calm_steps = 0;         // steps without an over-capacity tile or a crowded window while `crowded`
-    bool crowded = false;            // many tiles run over the direct-slot form: the dense launch uses the counting-sort form
-    bool hist_fused = false;         // the hash kernel counts the radix digits (most recent steps sorted), not the gated launch
-    uint32_t hist_watch_steps = 0, hist_watch_sorts = 0;
-    uint32_t quiet_steps = 0;        // native steps since the tiles last reported an over-capacity 32x32 tile (lagged)
     uint32_t step_seq = 0;           // native_prepare_step calls: its parity selects the per-step control words
     uint32_t collide_seq = 0;        // native_collide calls: numbers the dense launches for the tile hints (k_native.hip kCtlHints)
-    uint32_t hint_quiet = 0xFFFFFFFFu; // native steps since a tile last ran over, hinted ones included (lagged): the dense launch's front workgroups
-    uint32_t new_streak = 0;         // consecutive native steps whose (lagged) list 1 was not empty
-    uint32_t dense_quiet = 0;        // native steps since list 1 or list 2 last had an entry (lagged): the over-capacity launch's grid
     const uint32_t *fresh_word = nullptr;   // tile_ctl word the tiles of the current step read (did the passes run?)
     uint32_t reason = GPE_REASON_NO_PARTICLES;   // why the native kernels do not run (GPE_REASON_*), NONE when they do
     uint64_t native_steps = 0, compat_steps = 0;
@@ -376,8 +366,6 @@ struct NativeState {
     uint32_t stat_calls = 0;
     uint32_t *host_stat = nullptr;   // pinned, 16 words (k_native.hip kStat*): window maximum, arena use, probe answer, overflow tiles
     uint32_t window_max = 0;         // the same, measured synchronously at configuration time
-    bool dense_hold = false;         // left the native path because windows were filling up
-    uint32_t steps_since_check = 0;
 };
 
 // Device-resident halo exchange of a sharded run (k_shard.hip): particle counts live on the device, the host
@@ -712,6 +700,7 @@ gpe_status launch_remove_scatter(gpe_ctx *c, const uint8_t *mask, float x, float
 // native pipeline (k_native.hip)
 gpe_status native_configure(gpe_ctx *c);
 bool native_should_run(gpe_ctx *c);
+NativeStats native_read_stats(const NativeState &N);   // one reading of N.host_stat (allocated: native_configure)
 gpe_status launch_shard_classify(gpe_ctx *c, const uint8_t *owner_of_block, const uint32_t *dest_mask_of_block,
                                  int32_t blocks_x, int32_t blocks_y, uint32_t my_rank, uint32_t *out_index,
                                  uint32_t *out_info, uint32_t *out_count, uint64_t out_capacity);

@@ -23,6 +23,7 @@
 // inputs, same operation order => same bits), so no inter-tile communication and no global colour
 // barrier is needed.  Positions are double-buffered (read pos_in, write pos_out) because neighbours
 // read a tile's step-start positions while it writes its results.
+#include <assert.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -105,7 +106,7 @@ constexpr int kCtlPerStepWords = 8;            // words [0, 8) are cleared every
 // itself, which is past the test), and a front workgroup takes a listed tile iff the header carries one of the two.
 constexpr int kCtlHints = 11;                  // [launch parity] tiles registered for the launch of that parity
 constexpr int kCtlHintsSeen = 13;              // hinted tiles of the last launch (statistics)
-constexpr uint32_t kHintMax = 64;
+// (kHintMax, the tiles a launch may register: native_policy.h, whose hint policy sizes the front workgroups by it)
 constexpr uint32_t kHintAge = 240;             // a hint entry: age << 22 | ty << 11 | tx (at most 2048 tiles per axis: 16-bit cells)
 constexpr int kCtlError = 8;                   // sticky
 // Two words each, indexed by the parity of the step (native_prepare_step counts them): a step's hash kernel clears
@@ -153,7 +154,7 @@ __device__ __forceinline__ int code_window_x(uint32_t code, int o) { return (int
 __device__ __forceinline__ int code_window_y(uint32_t code, int o) { return (int)(((code >> kCodeYShift) - (uint32_t)o) & kCodeCellMask); }
 // (the pinned host words the kernels report to -- kStat* -- are declared in gpe_internal.h: gpe_get_pipeline_info reads them too)
 constexpr uint64_t kArenaBytesPerSlot = 37;     // px, py, rad, id, hm (4 B each), 4 member entries (16 B), block (1 B)
-constexpr uint64_t kArenaMaxSlots = 1ull << 30; // the arena's slot numbers are 32 bit; 40 GB of the 288 GB
+                                                // (at most kArenaMaxSlots: native_policy.h)
 // tile sizes (cells) and LDS capacities (particles staged per region)
 #ifndef GPE_CAP_MAIN
 #define GPE_CAP_MAIN 1192
@@ -185,16 +186,7 @@ constexpr int kTileSmall = 8, kCapSmall = GPE_CAP_SMALL;
 constexpr int kCapOrd = GPE_CAP_ORD;
 // population of a 3x3-block (24x24-cell) window = what an 8x8 sub-tile looks up (it keeps ~56 % of it):
 constexpr uint32_t kWindowReport = 512;     // tiles report windows above this population
-// Windows beyond the 8x8 sub-tile's 1536 slots take their arrays from the spill arena; with the cells of up to
-// 64 members resolved by whole waves that is faster than the compat kernels for the piles gravity builds (4 M
-// particles, windows up to ~2900, cells up to ~53 members: 2.2 ms/step against 3.75).  Far denser blobs (mouse
-// attraction: thousands per cell) are one-lane O(n^2) work that the overlapping windows would repeat: those leave
-// the native path.
-#ifndef GPE_WINDOW_HANDOVER
-#define GPE_WINDOW_HANDOVER 16384
-#endif
-constexpr uint32_t kWindowHandover = GPE_WINDOW_HANDOVER;              // above it the context leaves the native path
-constexpr uint32_t kWindowEligible = GPE_WINDOW_HANDOVER * 3 / 2;      // a scene whose windows exceed this never enters it
+// (the handover and eligibility populations, kWindowHandover / kWindowEligible, are the step policy's: native_policy.h)
 
 // ---------------------------------------------------------------------------------------------------
 // hash: R pos 8 B, W key 4 B per particle; fused 4-digit histogram for the onesweep passes.
@@ -3113,6 +3105,70 @@ void native_release(gpe_ctx *c)
 
 static gpe_status arena_reserve(gpe_ctx *c, uint64_t want);
 
+// The words the tiles publish (k_native_hash, k_native_publish_probe) while the host reads them: each word on its own.
+NativeStats native_read_stats(const NativeState &N)
+{
+    assert(N.host_stat != nullptr);
+    const auto word = [&](int k) { return __atomic_load_n(&N.host_stat[k], __ATOMIC_RELAXED); };
+    NativeStats s;
+    s.window_max = word(kStatWindowMax);
+    s.arena = word(kStatArena);
+    s.probe = word(kStatProbe);
+    s.overflow = word(kStatOverflow);
+    s.sub_tiles = word(kStatSubTiles);
+    s.spills = word(kStatSpills);
+    s.sorts = word(kStatSorts);
+    s.overflow_new = word(kStatOverflowNew);
+    s.halves_over = word(kStatHalvesOver);
+    return s;
+}
+
+// Diagnostics.  GPE_FLAG_NATIVE_STATS: the step statistics every 128 native_should_run calls.
+static void native_print_stats(gpe_ctx *c, const NativeStats &s)
+{
+    NativeState &N = c->native;
+    if (N.print_stats && (++N.stat_calls & 127u) == 0)
+        fprintf(stderr, "[gpe native] call %u: window max %u, arena slots used %u of %llu, 32x32 tiles over capacity %u, "
+                        "quarters redone as 8x8 tiles %u, 8x8 tiles through the arena %u\n", N.stat_calls,
+                s.window_max, s.arena, (unsigned long long)N.arena_cap, s.overflow, s.sub_tiles, s.spills);
+}
+
+#ifdef GPE_TILE_STAMPS
+// -DGPE_TILE_STAMPS builds: the collide launches' phase stamps (CollideArgs::stamps), printed every 20 native_collide
+// calls.  Returns the stamps of this call's launches.
+static unsigned long long *native_tile_stamps(gpe_ctx *c)
+{
+    static unsigned long long *g_stamps = nullptr;
+    // ([0, 64): the dense launch's tiles; [64, 128): the windows of the over-capacity launch)
+    if (!g_stamps) { (void)hipMalloc((void **)&g_stamps, 128 * 8); (void)hipMemset(g_stamps, 0, 128 * 8); }
+    static int g_calls = 0;
+    if (++g_calls % 20 == 0) for (int part = 0; part < 2; ++part) {
+        unsigned long long h[64];
+        (void)hipStreamSynchronize(c->stream);
+        (void)hipMemcpy(h, g_stamps + 64 * part, sizeof(h), hipMemcpyDeviceToHost);
+        fprintf(stderr, part == 0 ? "[dense launch]\n" : "[over-capacity launch]\n");
+        for (int cls = 0; cls < 3; ++cls)
+            fprintf(stderr, "[P5 waves] %s: busy %.0f  barrier wait %.0f cycles per colour pass (%llu wave-passes)\n",
+                    cls == 0 ? "group waves" : cls == 1 ? "single waves" : "idle waves", h[40 + cls] ? (double)h[32 + cls] / h[40 + cls] : 0.0,
+                    h[40 + cls] ? (double)h[36 + cls] / h[40 + cls] : 0.0, h[40 + cls]);
+        fprintf(stderr, "[tile stamps] n=%llu", (unsigned long long)c->n);
+        if (h[47])
+            fprintf(stderr, "[P5 cells] per colour pass: %.1f one-lane cells, %.1f lane-group cells, %.2f whole-wave cells of %.1f members (largest %.1f);"
+                    " a wave spends %.0f cycles in them and the rows; %.2f row cells; whole-wave cells by members <=16 / <=32 / <=64 / more: %.2f %.2f %.2f %.2f\n",
+                    (double)h[44] / h[47], (double)h[45] / h[47], (double)h[46] / h[47],
+                    h[46] ? (double)h[49] / h[46] : 0.0, (double)h[50] / h[47], (double)h[48] / (double)(h[40] + h[41] + h[42]),
+                    (double)h[51] / h[47], (double)h[52] / h[47], (double)h[53] / h[47], (double)h[54] / h[47], (double)h[55] / h[47]);
+        double all = 0;
+        for (int i = 0; i < 14; ++i) all += (double)h[i];
+        for (int i = 0; i < 14; ++i)
+            fprintf(stderr, "  P%d %.0f (%.1f%%)", i, h[16 + i] ? (double)h[i] / (double)h[16 + i] : 0.0, all > 0 ? 100.0 * (double)h[i] / all : 0.0);
+        fprintf(stderr, "  (tiles %llu of %llu started)\n", h[16 + 6], h[16 + 0]);
+        if (part == 1) (void)hipMemset(g_stamps, 0, 128 * 8);
+    }
+    return g_stamps;
+}
+#endif
+
 // hash -> [sort -> block table].  *sorted_ids receives the particle ids grouped by 8x8-cell block.
 // The radix passes are enqueued every step but run only when the hash kernel finds a particle that has left the
 // reach of the grouping they last produced (kDrift* cells beyond its block): the sorted ids and the block table are
@@ -3142,36 +3198,21 @@ static gpe_status native_prepare_step(gpe_ctx *c, uint32_t **sorted_ids, bool al
     // of their own, every step, into a second block table.  Other sharded set-ups (host-side counts) always sort.
     // A scene in which nearly every step sorts anyway (a crushed pile: a third of the particles move further than the
     // kept table reaches, every step) gains nothing from the kept table and pays for it in the hash kernel (the old
-    // keys, the drift test: 1.2 instead of 0.6 ms at 100 M).  The passes' own counter says so (lagged): when three
-    // quarters of the last 64 steps sorted, the next 256 steps sort unconditionally; then the table gets another try.
-    // (While the hold lasts every step sorts by decree, which says nothing about the scene: when it ends the count starts
-    // afresh -- one window for the lagged counter to settle, one to judge -- so a scene that has calmed down keeps its table.)
-    if (N.host_stat && !always_sort) {
-        if (N.sort_hold > 0) {
-            if (--N.sort_hold == 0) { N.watch_steps = 0; N.watch_valid = false; }
-        } else if (++N.watch_steps >= 64) {
-            const uint32_t sorts = N.host_stat[kStatSorts];
-            if (N.watch_valid && sorts - N.watch_sorts >= 48) N.sort_hold = 256;
-            N.watch_sorts = sorts; N.watch_steps = 0; N.watch_valid = true;
-        }
-    }
+    // keys, the drift test: 1.2 instead of 0.6 ms at 100 M).  The passes' own counter says so (lagged): the policy's
+    // sort hold then sorts unconditionally for a while, and the table gets another try after it.
+    // Who counts the radix digits of a step that keeps its table (k_native_hash, fuse_hist): the hash kernel, fused, while
+    // many recent steps sorted (a falling or crushed cloud before the sort hold takes over -- the separate launch reads all
+    // keys again, 0.2-0.4 ms at 100 M when it runs, against the 0.075 ms per step the fused count costs the hash);
+    // otherwise the gated launch, which returns at once on the steps that do not sort.
+    const PreparePlan plan = N.policy.prepare(native_read_stats(N), always_sort, N.always_sort,
+                                              (c->cfg.flags & GPE_FLAG_FUSED_HISTOGRAMS) != 0);
     const bool sharded = c->shard.on || c->use_order_keys || c->has_active_box;
     const bool kept_sharded = c->shard.on && c->shard.active && c->use_order_keys && N.gkeys != nullptr && !N.always_sort;
     const bool gated = N.passes >= 2 && (!sharded || kept_sharded);
-    const bool reuse = gated && !always_sort && N.sort_state_valid && (kept_sharded || N.sorted_n == n) && !N.always_sort &&
-                       N.sort_hold == 0 && N.exc_count != nullptr;     // (no room for the straggler lists: sort every step)
+    const bool reuse = gated && plan.keep_table && N.sort_state_valid && (kept_sharded || N.sorted_n == n) &&
+                       N.exc_count != nullptr;                         // (no room for the straggler lists: sort every step)
     const uint64_t pairs = ((uint64_t)N.table_entries + 1) / 2;        // the table is allocated in 16-byte units
-    // Who counts the radix digits of a step that keeps its table (k_native_hash, fuse_hist): the hash kernel, fused, while
-    // at least a quarter of the last 16 steps sorted (the passes' own counter, lagged: a falling or crushed cloud before
-    // sort_hold takes over -- the separate launch reads all keys again, 0.2-0.4 ms at 100 M when it runs, against the
-    // 0.075 ms per step the fused count costs the hash);
-    // otherwise the gated launch, which returns at once on the steps that do not sort.
-    if (N.host_stat && ++N.hist_watch_steps >= 16) {
-        const uint32_t sorts = N.host_stat[kStatSorts];
-        N.hist_fused = (sorts - N.hist_watch_sorts) * 4u >= N.hist_watch_steps;
-        N.hist_watch_sorts = sorts; N.hist_watch_steps = 0;
-    }
-    const bool fuse_hist = N.hist_fused || (c->cfg.flags & GPE_FLAG_FUSED_HISTOGRAMS) != 0;
+    const bool fuse_hist = plan.fuse_hist;
     HashGhosts hg;
     hg.sorted_count = N.tile_ctl + kCtlSortedCount;
     uint64_t g_bound = 0;
@@ -3280,15 +3321,9 @@ static gpe_status native_prepare_step(gpe_ctx *c, uint32_t **sorted_ids, bool al
 gpe_status native_configure(gpe_ctx *c)
 {
     NativeState &N = c->native;
-    N.eligible = false;
+    N.policy.configure(N.host_stat ? native_read_stats(N).sorts : 0u);   // (host_stat: from an earlier configuration)
     N.in_box = false;
-    N.dense_hold = false;
-    N.steps_since_check = 0;
     N.sort_state_valid = false;          // particles, box or keys changed: the kept grouping is of something else
-    N.quiet_steps = 0;
-    N.crowded = false;
-    N.hist_fused = false; N.hist_watch_steps = 0; N.hist_watch_sorts = N.host_stat ? N.host_stat[kStatSorts] : 0u;
-    N.sort_hold = 0; N.watch_steps = 0; N.watch_valid = false;
     N.always_sort = (c->cfg.flags & GPE_FLAG_SORT_EVERY_STEP) != 0;
     N.reason = GPE_REASON_NO_PARTICLES;
     if (c->n == 0 || !(c->cell_size > 0.0f)) return GPE_OK;
@@ -3477,13 +3512,11 @@ gpe_status native_configure(gpe_ctx *c)
     GPE_HIP(c, hipStreamSynchronize(c->stream));
     GPE_HIP(c, hipMemsetAsync(N.tile_ctl, 0, kCtlSorts * sizeof(uint32_t), c->stream));
     N.window_max = wmax;
-    N.eligible = wmax <= kWindowEligible;
-    N.reason = N.eligible ? GPE_REASON_NONE : GPE_REASON_DENSE_WINDOWS;
     // gpe_config.flags: keep over-dense scenes on the native kernels (their windows then go through the spill arena);
     // print the step statistics every 128 steps; sort every step
     N.force = (c->cfg.flags & GPE_FLAG_NATIVE_FORCE) != 0;
     N.print_stats = (c->cfg.flags & GPE_FLAG_NATIVE_STATS) != 0;
-    if (N.force) { N.eligible = true; N.reason = GPE_REASON_NONE; }
+    N.reason = N.policy.admit(wmax, N.force) ? GPE_REASON_NONE : GPE_REASON_DENSE_WINDOWS;
     return GPE_OK;
 }
 
@@ -3537,47 +3570,22 @@ static gpe_status native_probe_async(gpe_ctx *c)
 bool native_should_run(gpe_ctx *c)
 {
     NativeState &N = c->native;
-    if (c->cfg.mode != GPE_MODE_NATIVE) return false;
+    if (c->cfg.mode != GPE_MODE_NATIVE || !N.host_stat) return false;   // (no host_stat: never configured this far)
     const bool must_stay = N.force || c->use_order_keys;
-    if (N.print_stats && N.host_stat && (++N.stat_calls & 127u) == 0)
-        fprintf(stderr, "[gpe native] call %u: window max %u, arena slots used %u of %llu, 32x32 tiles over capacity %u, "
-                        "quarters redone as 8x8 tiles %u, 8x8 tiles through the arena %u\n", N.stat_calls,
-                N.host_stat[kStatWindowMax], N.host_stat[kStatArena], (unsigned long long)N.arena_cap,
-                N.host_stat[kStatOverflow], N.host_stat[kStatSubTiles], N.host_stat[kStatSpills]);
-    if (!N.eligible && must_stay && N.in_box) { N.eligible = true; N.dense_hold = false; N.reason = GPE_REASON_NONE; }   // density alone never stops such a run
-    if (N.eligible) {
-        if (N.host_stat && (uint64_t)N.host_stat[kStatArena] * 2 > N.arena_cap && N.arena_cap < kArenaMaxSlots) {
-            // (on failure the old arena stays and the step goes on with it: a window it cannot hold raises
-            // kErrTileOverflow, which gpe_sync reports -- never a silent hand-over of a run that must stay native)
-            if (arena_reserve(c, std::min<uint64_t>(N.arena_cap * 2, kArenaMaxSlots)) != GPE_OK && !must_stay) return false;
-            N.host_stat[kStatArena] = 0;
-        }
-        if (!must_stay && N.host_stat && N.host_stat[kStatWindowMax] > kWindowHandover) {
-            N.eligible = false;
-            N.dense_hold = true;
-            N.reason = GPE_REASON_DENSE_WINDOWS;
-            N.steps_since_check = 0;
-            N.host_stat[kStatProbe] = 0;
-        }
-        return N.eligible;
-    }
-    if (N.dense_hold) {
-        const uint32_t probe = N.host_stat ? N.host_stat[kStatProbe] : 0u;
-        if (probe != 0 && probe - 1u <= kWindowHandover * 3 / 4) {    // the last probe found the windows thin again
-            N.dense_hold = false;
-            N.eligible = true;
-            N.reason = GPE_REASON_NONE;
-            N.host_stat[kStatWindowMax] = probe - 1u;
-            N.host_stat[kStatProbe] = 0;
-            return true;
-        }
-        if (++N.steps_since_check >= 256) {
-            N.steps_since_check = 0;
-            N.host_stat[kStatProbe] = 0;
-            (void)native_probe_async(c);
-        }
-    }
-    return false;
+    const NativeStats s = native_read_stats(N);
+    native_print_stats(c, s);
+    // (a failed growth leaves the old arena in place and the step goes on with it when it must stay: a window it cannot
+    // hold raises kErrTileOverflow, which gpe_sync reports -- never a silent hand-over of a run that must stay native)
+    const RunPlan p = N.policy.run(s, must_stay, N.in_box, N.arena_cap,
+                                   [&](uint64_t slots) { return arena_reserve(c, slots) == GPE_OK; });
+    // (the host's side of the handshake: it resets the words the plan has consumed)
+    if (p.arena_reset) __atomic_store_n(&N.host_stat[kStatArena], 0u, __ATOMIC_RELAXED);
+    if (p.readmitted || p.resume) N.reason = GPE_REASON_NONE;
+    if (p.hand_over) N.reason = GPE_REASON_DENSE_WINDOWS;
+    if (p.resume) __atomic_store_n(&N.host_stat[kStatWindowMax], s.probe - 1u, __ATOMIC_RELAXED);
+    if (p.hand_over || p.resume || p.probe) __atomic_store_n(&N.host_stat[kStatProbe], 0u, __ATOMIC_RELAXED);
+    if (p.probe) (void)native_probe_async(c);
+    return p.run;
 }
 
 // Hinted tiles (kCtlHints): the dense launch's first workgroups redo them as halves.  With rosters only (the hint travels
@@ -3586,14 +3594,11 @@ bool native_should_run(gpe_ctx *c)
 // registered tile simply tries itself again.  (Up to 8 M particles, and while the front workgroups can take at least half
 // of the tiles that run over: the 3 % are 1.5 us of the 1 M launch, against ~20 us of half-tile launch behind it, but
 // 0.1 ms at 100 M.)
-static void native_hint_policy(gpe_ctx *c, CollideArgs *A)
+static void native_hint_policy(gpe_ctx *c, const NativeStats &s, CollideArgs *A)
 {
-    NativeState &N = c->native;
-    if (A->roster_hdr == nullptr || (c->cfg.flags & GPE_FLAG_NO_HALF_TILES) != 0 || c->n > (8ull << 20) || !N.host_stat) return;
-    A->hints_on = 1u;
-    const uint32_t over = N.host_stat[kStatOverflow];
-    if (over != 0 && over <= 2u * kHintMax) N.hint_quiet = 0; else if (N.hint_quiet < 0xFFFFFFFFu) ++N.hint_quiet;
-    if (N.hint_quiet < 32u && over <= 2u * kHintMax) A->front_wgs = 2u * kHintMax;
+    const HintPlan h = c->native.policy.hints(s, A->roster_hdr != nullptr, (c->cfg.flags & GPE_FLAG_NO_HALF_TILES) != 0, c->n);
+    A->hints_on = h.hints_on ? 1u : 0u;
+    A->front_wgs = h.front_wgs;
 }
 
 // pos_in (step-start positions) -> pos_out (after the four colour passes), every particle written.
@@ -3664,34 +3669,7 @@ gpe_status native_collide(gpe_ctx *c, const float2 *pos_in, float2 *pos_out, con
     A.pack = PackArgs();
     if (c->shard.on && c->shard.active && c->shard.have_rect && verlet && A.order_keys) shard_pack_args(c, &A.pack);
 #ifdef GPE_TILE_STAMPS
-    static unsigned long long *g_stamps = nullptr;
-    // ([0, 64): the dense launch's tiles; [64, 128): the windows of the over-capacity launch)
-    if (!g_stamps) { (void)hipMalloc((void **)&g_stamps, 128 * 8); (void)hipMemset(g_stamps, 0, 128 * 8); }
-    A.stamps = g_stamps;
-    static int g_calls = 0;
-    if (++g_calls % 20 == 0) for (int part = 0; part < 2; ++part) {
-        unsigned long long h[64];
-        (void)hipStreamSynchronize(c->stream);
-        (void)hipMemcpy(h, g_stamps + 64 * part, sizeof(h), hipMemcpyDeviceToHost);
-        fprintf(stderr, part == 0 ? "[dense launch]\n" : "[over-capacity launch]\n");
-        for (int cls = 0; cls < 3; ++cls)
-            fprintf(stderr, "[P5 waves] %s: busy %.0f  barrier wait %.0f cycles per colour pass (%llu wave-passes)\n",
-                    cls == 0 ? "group waves" : cls == 1 ? "single waves" : "idle waves", h[40 + cls] ? (double)h[32 + cls] / h[40 + cls] : 0.0,
-                    h[40 + cls] ? (double)h[36 + cls] / h[40 + cls] : 0.0, h[40 + cls]);
-        fprintf(stderr, "[tile stamps] n=%llu", (unsigned long long)c->n);
-        if (h[47])
-            fprintf(stderr, "[P5 cells] per colour pass: %.1f one-lane cells, %.1f lane-group cells, %.2f whole-wave cells of %.1f members (largest %.1f);"
-                    " a wave spends %.0f cycles in them and the rows; %.2f row cells; whole-wave cells by members <=16 / <=32 / <=64 / more: %.2f %.2f %.2f %.2f\n",
-                    (double)h[44] / h[47], (double)h[45] / h[47], (double)h[46] / h[47],
-                    h[46] ? (double)h[49] / h[46] : 0.0, (double)h[50] / h[47], (double)h[48] / (double)(h[40] + h[41] + h[42]),
-                    (double)h[51] / h[47], (double)h[52] / h[47], (double)h[53] / h[47], (double)h[54] / h[47], (double)h[55] / h[47]);
-        double all = 0;
-        for (int i = 0; i < 14; ++i) all += (double)h[i];
-        for (int i = 0; i < 14; ++i)
-            fprintf(stderr, "  P%d %.0f (%.1f%%)", i, h[16 + i] ? (double)h[i] / (double)h[16 + i] : 0.0, all > 0 ? 100.0 * (double)h[i] / all : 0.0);
-        fprintf(stderr, "  (tiles %llu of %llu started)\n", h[16 + 6], h[16 + 0]);
-        if (part == 1) (void)hipMemset(g_stamps, 0, 128 * 8);
-    }
+    A.stamps = native_tile_stamps(c);
 #endif
     int32_t cx0 = 0, cy0 = 0, cx1 = N.gx - 1, cy1 = N.gy - 1;
     if (c->has_active_box) {                                           // sharded: only this rank's cells
@@ -3704,6 +3682,7 @@ gpe_status native_collide(gpe_ctx *c, const float2 *pos_in, float2 *pos_out, con
     A.tiles_x = cx1 / kTileMain - A.tile_x0 + 1;
     A.tiles_y = cy1 / kTileMain - A.tile_y0 + 1;
     const uint32_t total = (uint32_t)A.tiles_x * (uint32_t)A.tiles_y;
+    const NativeStats stats = native_read_stats(N);                   // (this call's decisions all read this one)
     bool direct_form = false;                                          // the dense launch runs direct-slot tiles
     {
         Scope s(c, verlet ? "native/collide+verlet" : "native/collide");
@@ -3719,19 +3698,10 @@ gpe_status native_collide(gpe_ctx *c, const float2 *pos_in, float2 *pos_out, con
         // direct-slot window overflows around 350) and no tile has run over for 64 steps.
         // (order-key windows carry four more bytes per particle: in the direct form that leaves 728 slots, 1.27 x the
         // mean tile's particles, and too many tiles run over; the counting-sort form holds 1024)
-        if (N.host_stat) {
-            const uint32_t over = N.host_stat[kStatOverflow];
-            if (!N.crowded) {
-                if (over > total / 50u + 4u) { N.crowded = true; N.calm_steps = 0; }
-            } else {
-                N.calm_steps = (over == 0 && N.host_stat[kStatWindowMax] == 0) ? N.calm_steps + 1 : 0;
-                if (N.calm_steps >= 64) N.crowded = false;
-            }
-        }
         // (order-key windows: the direct form needs the ghost lists of a kept sharded run; every other sharded set-up
         // looks its ghosts up in the block tables, which only the counting-sort form does)
-        const bool legacy = (c->cfg.flags & GPE_FLAG_COUNTING_SORT_TILES) != 0 || N.crowded ||
-                            (A.order_keys != nullptr && A.gho_count == nullptr);
+        const bool legacy = N.policy.counting_sort(stats, total, (c->cfg.flags & GPE_FLAG_COUNTING_SORT_TILES) != 0,
+                                                   A.order_keys != nullptr && A.gho_count == nullptr);
         direct_form = !legacy;
         if (legacy) {
             if (A.order_keys)
@@ -3779,14 +3749,14 @@ gpe_status native_collide(gpe_ctx *c, const float2 *pos_in, float2 *pos_out, con
                 }
             }
             if (!split) {
-                native_hint_policy(c, &A);
+                native_hint_policy(c, stats, &A);
                 if (A.front_wgs)
                     hipLaunchKernelGGL((k_collide_direct<32, GPE_CAP_DIRECT_ORD, true, 512, true>), dim3(grid + A.front_wgs), dim3(512), 0, c->stream, A);
                 else
                     hipLaunchKernelGGL((k_collide_direct<32, GPE_CAP_DIRECT_ORD, true, 512>), dim3(grid), dim3(512), 0, c->stream, A);
             }
         } else {
-            native_hint_policy(c, &A);
+            native_hint_policy(c, stats, &A);
             if (A.front_wgs)
                 hipLaunchKernelGGL((k_collide_direct<32, GPE_CAP_DIRECT, false, 512, true>), dim3(grid + A.front_wgs), dim3(512), 0, c->stream, A);
             else
@@ -3805,10 +3775,6 @@ gpe_status native_collide(gpe_ctx *c, const float2 *pos_in, float2 *pos_out, con
         Scope s(c, "native/collide-dense-regions");
         // (quiet_steps: since the dense launch last handed a tile on ITSELF -- hinted tiles do not count, they never reach
         // list 1; dense_quiet: since anything reached list 1 or list 2)
-        if (N.host_stat && N.host_stat[A.front_wgs ? kStatOverflowNew : kStatOverflow] != 0) N.quiet_steps = 0;
-        else if (N.quiet_steps < 0xFFFFFFFFu) ++N.quiet_steps;
-        if (N.host_stat && (N.host_stat[kStatOverflowNew] != 0 || N.host_stat[kStatHalvesOver] != 0 || (!A.front_wgs && N.host_stat[kStatOverflow] != 0))) N.dense_quiet = 0;
-        else if (N.dense_quiet < 0xFFFFFFFFu) ++N.dense_quiet;
         // The half-tile launch: while the direct-slot launch has handed tiles on lately (lagged; either way is exact --
         // without it the over-capacity launch takes the tiles of list 1).  Not behind counting-sort tiles: what does not
         // fit their 1192 particles is dense enough for the windows.
@@ -3818,23 +3784,19 @@ gpe_status native_collide(gpe_ctx *c, const float2 *pos_in, float2 *pos_out, con
         // (With front workgroups in the dense launch list 1 only holds tiles that ran over for the FIRST time -- one every
         // ~60 steps in the clumped 1 M cloud, which no lagged statistic foresees: the over-capacity launch takes those as
         // quarters, and the half-tile launch comes back when list 1 stays occupied, i.e. the hints are full.)
-        if (N.host_stat[kStatOverflowNew] != 0) { if (N.new_streak < 0xFFFFFFFFu) ++N.new_streak; } else N.new_streak = 0;
-        const bool halves_wanted = A.front_wgs ? N.new_streak >= 4u : N.quiet_steps < 32u;
-        if (direct_form && halves_wanted && (c->cfg.flags & GPE_FLAG_NO_HALF_TILES) == 0) {
+        // (The small over-capacity grid only where the empty launch matters: from a few million particles on its 6 us are
+        // noise, and a surprise -- the statistic lags by up to 64 steps -- would cost those steps milliseconds each; with
+        // front workgroups also while the lists have held few work items lately, a first-time tile being four.)
+        const OverflowPlan op = N.policy.overflow(stats, A.front_wgs, direct_form, (c->cfg.flags & GPE_FLAG_NO_HALF_TILES) != 0, c->n);
+        if (op.halves_grid) {
             A.quarters_of_halves = 1u;
-            const uint32_t hgrid = (uint32_t)std::min<uint64_t>(1024, std::max<uint64_t>(64, 2ull * N.host_stat[A.front_wgs ? kStatOverflowNew : kStatOverflow] + 32));
             if (A.order_keys)
-                hipLaunchKernelGGL(k_collide_halves<true>, dim3(hgrid), dim3(512), 0, c->stream, A);
+                hipLaunchKernelGGL(k_collide_halves<true>, dim3(op.halves_grid), dim3(512), 0, c->stream, A);
             else
-                hipLaunchKernelGGL(k_collide_halves<false>, dim3(hgrid), dim3(512), 0, c->stream, A);
+                hipLaunchKernelGGL(k_collide_halves<false>, dim3(op.halves_grid), dim3(512), 0, c->stream, A);
             GPE_HIP(c, hipGetLastError());
         }
-        // (Only where the empty launch matters: from a few million particles on its 6 us are noise, and a surprise -- the
-        // statistic lags by up to 64 steps -- would cost those steps milliseconds each.)
-        // ... or, with front workgroups, while the lists have held few work items lately (a first-time tile is four)
-        const uint64_t items = 4ull * N.host_stat[kStatOverflowNew] + 2ull * N.host_stat[kStatHalvesOver];
-        const bool small_grid = c->n <= (4ull << 20) && (N.dense_quiet > 96 || (A.front_wgs != 0u && items <= 128u));
-        const uint32_t ogrid = small_grid ? 128u : 1024u;
+        const uint32_t ogrid = op.overflow_grid;
 #ifdef GPE_TILE_STAMPS
         A.stamps += 64;
 #endif
