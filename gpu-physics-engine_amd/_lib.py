@@ -112,6 +112,13 @@ class GpeShardStats(C.Structure):
                 ("n_owned", C.c_uint64), ("n_ghost", C.c_uint64), ("n_neighbours", C.c_uint32), ("transport", C.c_uint32)]
 
 
+class GpeQueryResult(C.Structure):
+    """gpe_query_result: in struct_size / capacity, out count; every array pointer may be NULL."""
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("capacity", C.c_uint64), ("count", C.c_uint64),
+                ("index", C.POINTER(C.c_uint32)), ("uid", C.POINTER(C.c_uint32)), ("pos_xy", C.POINTER(C.c_float)),
+                ("prev_xy", C.POINTER(C.c_float)), ("radius", C.POINTER(C.c_float))]
+
+
 class GpeError(RuntimeError):
     def __init__(self, status, message):
         super().__init__("gpe status %d: %s" % (status, message))
@@ -136,6 +143,9 @@ SYMBOLS = [
     ("gpe_set_next_uid", _I32, [_VP, _U64]),
     ("gpe_find_uids", _I32, [_VP, _VP, _U64, _VP, _VP, _VP, _VP]),
     ("gpe_remove_particles_by_uid", _I32, [_VP, _VP, _U64, C.POINTER(_U64)]),
+    ("gpe_query_circle", _I32, [_VP, _F, _F, _F, C.POINTER(GpeQueryResult)]),
+    ("gpe_query_box", _I32, [_VP, _F, _F, _F, _F, C.POINTER(GpeQueryResult)]),
+    ("gpe_pick", _I32, [_VP, _F, _F, C.POINTER(GpeQueryResult)]),
     ("gpe_len", _I32, [_VP, C.POINTER(_U64)]),
     ("gpe_max_radius", _I32, [_VP, C.POINTER(_F)]),
     ("gpe_morton_resort", _I32, [_VP]),

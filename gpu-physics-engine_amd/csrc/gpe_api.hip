@@ -130,6 +130,9 @@ static void free_particle_buffers(gpe_ctx *c)
     dev_free(c->remove_ws.tile_count); dev_free(c->remove_ws.tile_key); dev_free(c->remove_ws.max_key);
     dev_free(c->remove_ws.mask);
     c->remove_ws.tiles_cap = c->remove_ws.mask_cap = 0;
+    dev_free(c->query_ws.tile_count); dev_free(c->query_ws.tile_key); dev_free(c->query_ws.pick);
+    dev_free(c->query_ws.stage);
+    c->query_ws.tiles_cap = c->query_ws.stage_cap = 0;
     free_uid_buffers(c);
     c->cap = 0;
 }
@@ -1051,6 +1054,157 @@ gpe_status gpe_remove_particles_by_uid(gpe_ctx *c, const uint32_t *uids, uint64_
         GPE_TRY(launch_uid_mark(c, c->uid.map_keys, c->uid.map_vals, c->n, d_query, k, c->remove_ws.mask));
     }
     return do_remove(c, c->remove_ws.mask, 0.f, 0.f, 0.f, n_removed);
+}
+
+// ---- region queries and picking (k_query.hip) -------------------------------------------------------------
+static gpe_status query_reserve(gpe_ctx *c, uint64_t stage_bytes)
+{
+    QueryWorkspace &ws = c->query_ws;
+    const uint64_t tiles = query_tiles(c->n);
+    if (ws.tiles_cap < tiles) {
+        dev_free(ws.tile_count);
+        dev_free(ws.tile_key);
+        ws.tiles_cap = 0;
+        GPE_TRY(dev_alloc(c, &ws.tile_count, tiles));
+        GPE_TRY(dev_alloc(c, &ws.tile_key, tiles));
+        ws.tiles_cap = tiles;
+    }
+    if (!ws.pick) GPE_TRY(dev_alloc(c, &ws.pick, 1));
+    if (ws.stage_cap < stage_bytes) {
+        dev_free(ws.stage);
+        ws.stage_cap = 0;
+        GPE_TRY(dev_alloc(c, &ws.stage, stage_bytes));
+        ws.stage_cap = stage_bytes;
+    }
+    return scan_reserve(c, tiles);
+}
+
+static bool query_wants_rows(const gpe_query_result *out)
+{
+    return out->index || out->uid || out->pos_xy || out->prev_xy || out->radius;
+}
+
+// The checks every query shares, in this order: the result struct (nothing written when it is unusable), then
+// out->count = 0, the sharded refusal and uids for a uid output.  *go = false: GPE_OK with count 0 (no particles).
+static gpe_status query_begin(gpe_ctx *c, gpe_query_result *out, const char *who, bool *go)
+{
+    *go = false;
+    if (!c) return GPE_ERR_INVALID_ARG;
+    if (!out) return fail(c, GPE_ERR_INVALID_ARG, std::string(who) + ": NULL result");
+    if (out->struct_size < sizeof(gpe_query_result))
+        return fail(c, GPE_ERR_INVALID_ARG, std::string(who) + ": struct_size is smaller than gpe_query_result");
+    out->count = 0;
+    if (is_sharded(c))
+        return fail(c, GPE_ERR_UNSUPPORTED, std::string(who) + ": not supported on a sharded context (gpe_shard_*, "
+                                                                "order keys or an active cell box)");
+    if (out->uid && !c->uid.on) return fail(c, GPE_ERR_STATE, std::string(who) + ": uid requested while uids are off");
+    if (c->n > 0xFFFFFFFFull) return fail(c, GPE_ERR_UNSUPPORTED, std::string(who) + ": more than 2^32 - 1 particles");
+    *go = c->n > 0 && c->pos;
+    return GPE_OK;
+}
+
+// Count (and, for requested rows, gather) the particles in the region; region as launch_query_count takes it.
+static gpe_status do_query(gpe_ctx *c, bool box, const float *region, gpe_query_result *out)
+{
+    GPE_HIP(c, hipSetDevice(c->device));
+    GPE_HIP(c, hipStreamSynchronize(c->stream));
+    GPE_TRY(query_reserve(c, 0));
+    QueryWorkspace &ws = c->query_ws;
+    const uint64_t tiles = query_tiles(c->n);
+    uint32_t total = 0;
+    Scope s(c, "Query particles");
+    {
+        Scope k(c, "query/count");
+        GPE_TRY(launch_query_count(c, box, region, ws.tile_count));
+    }
+    {
+        Scope k(c, "query/scan");
+        GPE_TRY(inclusive_scan(c, ws.tile_count, tiles));
+    }
+    GPE_HIP(c, hipMemcpyAsync(&total, ws.tile_count + (tiles - 1), sizeof(total), hipMemcpyDeviceToHost, c->stream));
+    GPE_HIP(c, hipStreamSynchronize(c->stream));
+    const uint64_t m = std::min<uint64_t>(total, out->capacity);
+    if (m > 0 && query_wants_rows(out)) {
+        // staging, 256-byte aligned parts, only the requested fields: pos | prev | radius | index | uid
+        auto part = [m](bool on, uint64_t width) { return on ? (m * width + 255) / 256 * 256 : 0; };
+        const uint64_t o_prev = part(out->pos_xy, 8), o_radius = o_prev + part(out->prev_xy, 8),
+                       o_index = o_radius + part(out->radius, 4), o_uid = o_index + part(out->index, 4),
+                       bytes = o_uid + part(out->uid, 4);
+        GPE_TRY(query_reserve(c, bytes));
+        uint8_t *st = ws.stage;
+        float2 *d_pos = out->pos_xy ? reinterpret_cast<float2 *>(st) : nullptr;
+        float2 *d_prev = out->prev_xy ? reinterpret_cast<float2 *>(st + o_prev) : nullptr;
+        float *d_radius = out->radius ? reinterpret_cast<float *>(st + o_radius) : nullptr;
+        uint32_t *d_index = out->index ? reinterpret_cast<uint32_t *>(st + o_index) : nullptr;
+        uint32_t *d_uid = out->uid ? reinterpret_cast<uint32_t *>(st + o_uid) : nullptr;
+        {
+            Scope k(c, "query/gather");
+            GPE_TRY(launch_query_gather(c, box, region, ws.tile_count, (uint32_t)m, d_index, d_uid, d_pos, d_prev,
+                                        d_radius));
+        }
+        if (d_index) GPE_HIP(c, hipMemcpyAsync(out->index, d_index, m * 4, hipMemcpyDeviceToHost, c->stream));
+        if (d_uid) GPE_HIP(c, hipMemcpyAsync(out->uid, d_uid, m * 4, hipMemcpyDeviceToHost, c->stream));
+        if (d_pos) GPE_HIP(c, hipMemcpyAsync(out->pos_xy, d_pos, m * 8, hipMemcpyDeviceToHost, c->stream));
+        if (d_prev) GPE_HIP(c, hipMemcpyAsync(out->prev_xy, d_prev, m * 8, hipMemcpyDeviceToHost, c->stream));
+        if (d_radius) GPE_HIP(c, hipMemcpyAsync(out->radius, d_radius, m * 4, hipMemcpyDeviceToHost, c->stream));
+        GPE_HIP(c, hipStreamSynchronize(c->stream));
+    }
+    out->count = total;
+    return GPE_OK;
+}
+
+gpe_status gpe_query_circle(gpe_ctx *c, float x, float y, float radius, gpe_query_result *out)
+{
+    bool go = false;
+    GPE_TRY(query_begin(c, out, "gpe_query_circle", &go));
+    if (!(radius >= 0.0f) || !isfinite(radius))
+        return fail(c, GPE_ERR_INVALID_ARG, "gpe_query_circle: radius must be finite and >= 0");
+    if (!go) return GPE_OK;
+    const float region[5] = {x, y, 0.f, 0.f, radius * radius};   // binary32, as gpe_remove_particles_in_circle
+    return do_query(c, false, region, out);
+}
+
+gpe_status gpe_query_box(gpe_ctx *c, float x0, float y0, float x1, float y1, gpe_query_result *out)
+{
+    bool go = false;
+    GPE_TRY(query_begin(c, out, "gpe_query_box", &go));
+    if (isnan(x0) || isnan(y0) || isnan(x1) || isnan(y1))
+        return fail(c, GPE_ERR_INVALID_ARG, "gpe_query_box: NaN bound");
+    if (!go || x0 > x1 || y0 > y1) return GPE_OK;                 // an empty box holds nothing
+    const float region[5] = {x0, y0, x1, y1, 0.f};
+    return do_query(c, true, region, out);
+}
+
+gpe_status gpe_pick(gpe_ctx *c, float x, float y, gpe_query_result *out)
+{
+    bool go = false;
+    GPE_TRY(query_begin(c, out, "gpe_pick", &go));
+    if (!go) return GPE_OK;
+    GPE_HIP(c, hipSetDevice(c->device));
+    GPE_HIP(c, hipStreamSynchronize(c->stream));
+    GPE_TRY(query_reserve(c, 0));
+    QueryWorkspace &ws = c->query_ws;
+    unsigned long long key = 0;
+    {
+        Scope s(c, "Query particles");
+        Scope k(c, "query/pick");
+        GPE_TRY(launch_pick(c, x, y, ws.tile_key, ws.pick));
+    }
+    GPE_HIP(c, hipMemcpyAsync(&key, ws.pick, sizeof(key), hipMemcpyDeviceToHost, c->stream));
+    GPE_HIP(c, hipStreamSynchronize(c->stream));
+    if (key == ~0ull) return GPE_OK;                               // no disc contains the point
+    const uint32_t i = (uint32_t)(key & 0xFFFFFFFFull);
+    if (i >= c->n) return fail(c, GPE_ERR_STATE, "gpe_pick: bad index");
+    if (out->capacity >= 1) {                                     // one row: straight from the particle buffers
+        if (out->uid) GPE_HIP(c, hipMemcpyAsync(out->uid, c->uid.uids + i, 4, hipMemcpyDeviceToHost, c->stream));
+        if (out->pos_xy) GPE_HIP(c, hipMemcpyAsync(out->pos_xy, c->pos + i, 8, hipMemcpyDeviceToHost, c->stream));
+        if (out->prev_xy) GPE_HIP(c, hipMemcpyAsync(out->prev_xy, c->prev + i, 8, hipMemcpyDeviceToHost, c->stream));
+        if (out->radius) GPE_HIP(c, hipMemcpyAsync(out->radius, c->radius + i, 4, hipMemcpyDeviceToHost, c->stream));
+        GPE_HIP(c, hipStreamSynchronize(c->stream));
+        if (out->index) out->index[0] = i;
+    }
+    out->count = 1;
+    return GPE_OK;
 }
 
 gpe_status gpe_len(const gpe_ctx *c, uint64_t *n)

@@ -258,6 +258,15 @@ struct RemoveWorkspace {         // gpe_remove_particles* (k_remove.hip); alloca
     uint64_t mask_cap = 0;
 };
 
+struct QueryWorkspace {          // gpe_query_* / gpe_pick (k_query.hip); allocated at first use, freed with the particles
+    uint32_t *tile_count = nullptr;              // per-tile match counts, scanned in place
+    unsigned long long *tile_key = nullptr;      // gpe_pick: per-tile min of bits(d2) << 32 | index
+    uint64_t tiles_cap = 0;
+    unsigned long long *pick = nullptr;          // gpe_pick: the min over the tiles
+    uint8_t *stage = nullptr;                    // the gathered rows of the requested fields
+    uint64_t stage_cap = 0;                      // bytes
+};
+
 struct UidState {               // opt-in particle uids (gpe_enable_uids; k_uids.hip)
     bool on = false;
     uint64_t next = 0;                           // the uid the next added particle gets (at most 2^32)
@@ -588,6 +597,7 @@ struct gpe_ctx {
     gpe::SortWorkspace sort_ws;
     gpe::RemoveWorkspace remove_ws;
     gpe::UidState uid;
+    gpe::QueryWorkspace query_ws;
     gpe::ScanWorkspace scan_ws;
     gpe::OnesweepWorkspace os_ws;
     gpe::NativeState native;
@@ -697,6 +707,15 @@ gpe_status launch_remove_count(gpe_ctx *c, const uint8_t *mask, float x, float y
 gpe_status launch_remove_scatter(gpe_ctx *c, const uint8_t *mask, float x, float y, float rr,
                                  const uint32_t *tile_scanned, const uint32_t *uids = nullptr,
                                  uint32_t *uids_out = nullptr);
+// region queries and picking (k_query.hip): region = {x, y, -, -, radius^2} (circle) or {x0, y0, x1, y1, -} (box)
+uint64_t query_tiles(uint64_t n);
+gpe_status launch_query_count(gpe_ctx *c, bool box, const float *region, uint32_t *tile_count);
+// the matches ranked below capacity into the non-NULL outputs (uid_out: from c->uid.uids)
+gpe_status launch_query_gather(gpe_ctx *c, bool box, const float *region, const uint32_t *tile_scanned,
+                               uint32_t capacity, uint32_t *index_out, uint32_t *uid_out, float2 *pos_out,
+                               float2 *prev_out, float *radius_out);
+// *pick = min over the particles whose disc contains (x, y) of bits(d2) << 32 | index (~0 for none)
+gpe_status launch_pick(gpe_ctx *c, float x, float y, unsigned long long *tile_key, unsigned long long *pick);
 // native pipeline (k_native.hip)
 gpe_status native_configure(gpe_ctx *c);
 bool native_should_run(gpe_ctx *c);

@@ -17,6 +17,7 @@ State composes them (state.rs:34-70).  Errors surface as GpeError (the reference
 numpy is used only to hold host arrays; every call goes through ctypes to libgpe.so.
 """
 import ctypes as C
+import collections
 import sys
 
 import numpy as np
@@ -26,6 +27,10 @@ from . import _lib as L
 
 def _ptr(a):
     return a.ctypes.data_as(C.c_void_p)
+
+
+# gpe_query_circle / gpe_query_box / gpe_pick: every match, ascending storage index (uid None while uids are off)
+QueryResult = collections.namedtuple("QueryResult", "index uid pos prev radius")
 
 
 class Context:
@@ -334,6 +339,63 @@ class ParticleSystem:
         self.ctx.call("gpe_remove_particles_by_uid", _ptr(qq), q.shape[0], C.byref(removed))
         return removed.value
 
+    # Region queries and picking (not in the reference; include/gpe.h): which particles lie in a circle or a box, or
+    # under a point, counted and gathered on the device.  The context is left exactly as it was.
+    def _uids_on(self):
+        n = C.c_uint64()
+        return self.ctx.lib.gpe_next_uid(self.ctx.h, C.byref(n)) == L.GPE_OK
+
+    def _query(self, name, args, capacity=1024):
+        """Call `name` with a modest capacity, and once more with capacity = count only if it ran over."""
+        with_uids = self._uids_on()
+        while True:
+            cap = max(int(capacity), 1)
+            index = np.empty(cap, np.uint32)
+            uid = np.empty(cap, np.uint32) if with_uids else None
+            pos = np.empty((cap, 2), np.float32)
+            prev = np.empty((cap, 2), np.float32)
+            rad = np.empty(cap, np.float32)
+            res = L.GpeQueryResult(struct_size=C.sizeof(L.GpeQueryResult), capacity=cap)
+            res.index = index.ctypes.data_as(C.POINTER(C.c_uint32))
+            if with_uids:
+                res.uid = uid.ctypes.data_as(C.POINTER(C.c_uint32))
+            res.pos_xy = pos.ctypes.data_as(C.POINTER(C.c_float))
+            res.prev_xy = prev.ctypes.data_as(C.POINTER(C.c_float))
+            res.radius = rad.ctypes.data_as(C.POINTER(C.c_float))
+            self.ctx.call(name, *args, C.byref(res))
+            k = res.count
+            if k <= cap:
+                return QueryResult(index[:k], uid[:k] if with_uids else None, pos[:k], prev[:k], rad[:k])
+            capacity = k
+
+    def _count(self, name, args):
+        res = L.GpeQueryResult(struct_size=C.sizeof(L.GpeQueryResult), capacity=0)
+        self.ctx.call(name, *args, C.byref(res))
+        return res.count
+
+    def query_circle(self, center, radius):
+        """gpe_query_circle -> QueryResult(index, uid, pos, prev, radius) of every particle whose centre p has
+        |p - center|^2 <= radius^2 in float32: exactly what remove_particles_in_circle(center, radius) would remove."""
+        return self._query("gpe_query_circle", (float(center[0]), float(center[1]), float(radius)))
+
+    def query_box(self, lo, hi):
+        """gpe_query_box -> QueryResult of every particle with lo <= p <= hi per axis (closed; +-inf bounds allowed)."""
+        return self._query("gpe_query_box", (float(lo[0]), float(lo[1]), float(hi[0]), float(hi[1])))
+
+    def pick(self, point):
+        """gpe_pick -> QueryResult of the one particle whose own disc contains `point` nearest its centre (lowest index
+        on a tie), or None when no disc contains it."""
+        r = self._query("gpe_pick", (float(point[0]), float(point[1])), capacity=1)
+        return r if r.index.shape[0] else None
+
+    def count_circle(self, center, radius):
+        """gpe_query_circle with no outputs: the number of particles query_circle would return."""
+        return self._count("gpe_query_circle", (float(center[0]), float(center[1]), float(radius)))
+
+    def count_box(self, lo, hi):
+        """gpe_query_box with no outputs: the number of particles query_box would return."""
+        return self._count("gpe_query_box", (float(lo[0]), float(lo[1]), float(hi[0]), float(hi[1])))
+
     def len(self):
         n = C.c_uint64()
         self.ctx.call("gpe_len", C.byref(n))
@@ -555,6 +617,24 @@ class State:
     def remove_particles_by_uid(self, uids):
         """ParticleSystem.remove_particles_by_uid: returns how many left."""
         return self.particles.remove_particles_by_uid(uids)
+
+    def query_circle(self, center, radius):
+        """ParticleSystem.query_circle -> QueryResult(index, uid, pos, prev, radius)."""
+        return self.particles.query_circle(center, radius)
+
+    def query_box(self, lo, hi):
+        """ParticleSystem.query_box -> QueryResult."""
+        return self.particles.query_box(lo, hi)
+
+    def pick(self, point):
+        """ParticleSystem.pick -> QueryResult of one particle, or None."""
+        return self.particles.pick(point)
+
+    def count_circle(self, center, radius):
+        return self.particles.count_circle(center, radius)
+
+    def count_box(self, lo, hi):
+        return self.particles.count_box(lo, hi)
 
     def _uids_on(self):
         try:

@@ -224,6 +224,37 @@ class ParticleSystem {
         ctx_->call(gpe_remove_particles_by_uid(ctx_->raw(), uids.empty() ? &none : uids.data(), uids.size(), &removed));
         return removed;
     }
+    // not in the reference: every particle in a circle / box, or the one under a point (include/gpe.h), ascending
+    // storage index; uid stays empty while uids are off.  pick() returns no rows when no disc contains the point.
+    struct QueryResult {
+        std::vector<uint32_t> index, uid;
+        std::vector<Vec2> pos, prev;
+        std::vector<float> radius;
+    };
+    QueryResult query_circle(Vec2 center, float radius) const
+    {
+        return query([&](gpe_query_result *r) { return gpe_query_circle(ctx_->raw(), center.x, center.y, radius, r); });
+    }
+    QueryResult query_box(Vec2 lo, Vec2 hi) const
+    {
+        return query([&](gpe_query_result *r) { return gpe_query_box(ctx_->raw(), lo.x, lo.y, hi.x, hi.y, r); });
+    }
+    QueryResult pick(Vec2 point) const
+    {
+        return query([&](gpe_query_result *r) { return gpe_pick(ctx_->raw(), point.x, point.y, r); }, 1);
+    }
+    uint64_t count_circle(Vec2 center, float radius) const
+    {
+        gpe_query_result r = empty_query();
+        ctx_->call(gpe_query_circle(ctx_->raw(), center.x, center.y, radius, &r));
+        return r.count;
+    }
+    uint64_t count_box(Vec2 lo, Vec2 hi) const
+    {
+        gpe_query_result r = empty_query();
+        ctx_->call(gpe_query_box(ctx_->raw(), lo.x, lo.y, hi.x, hi.y, &r));
+        return r.count;
+    }
     size_t len() const { uint64_t n = 0; ctx_->call(gpe_len(ctx_->raw(), &n)); return n; }               // :275
     float get_max_radius() const { float r = 0; ctx_->call(gpe_max_radius(ctx_->raw(), &r)); return r; } // :291
     void sort_by_cell_id(float /*cell_size: the Grid's, state.rs:123*/) { ctx_->call(gpe_morton_resort(ctx_->raw())); }
@@ -254,6 +285,45 @@ class ParticleSystem {
 
    private:
     explicit ParticleSystem(const Context &ctx) : ctx_(&ctx) {}
+    static gpe_query_result empty_query()
+    {
+        gpe_query_result r{};
+        r.struct_size = sizeof(gpe_query_result);
+        return r;
+    }
+    // one call with `capacity` rows, a second with capacity = count only if the first ran over
+    template <typename Call>
+    QueryResult query(Call call, uint64_t capacity = 1024) const
+    {
+        uint64_t next = 0;
+        const bool with_uids = gpe_next_uid(ctx_->raw(), &next) == GPE_OK;
+        QueryResult q;
+        for (;;) {
+            const uint64_t cap = std::max<uint64_t>(capacity, 1);
+            q.index.resize(cap);
+            q.uid.resize(with_uids ? cap : 0);
+            q.pos.resize(cap);
+            q.prev.resize(cap);
+            q.radius.resize(cap);
+            gpe_query_result r = empty_query();
+            r.capacity = cap;
+            r.index = q.index.data();
+            r.uid = with_uids ? q.uid.data() : nullptr;
+            r.pos_xy = &q.pos[0].x;
+            r.prev_xy = &q.prev[0].x;
+            r.radius = q.radius.data();
+            ctx_->call(call(&r));
+            if (r.count <= cap) {
+                q.index.resize(r.count);
+                q.uid.resize(with_uids ? r.count : 0);
+                q.pos.resize(r.count);
+                q.prev.resize(r.count);
+                q.radius.resize(r.count);
+                return q;
+            }
+            capacity = r.count;
+        }
+    }
     const Context *ctx_;
     bool mouse_pressed_ = false;
     bool sorted_once_ = false;

@@ -190,6 +190,42 @@ gpe_status gpe_find_uids(gpe_ctx *ctx, const uint32_t *uids, uint64_t k, uint32_
  * untouched, removing every particle is GPE_ERR_INVALID_ARG.  GPE_ERR_STATE while uids are off. */
 gpe_status gpe_remove_particles_by_uid(gpe_ctx *ctx, const uint32_t *uids, uint64_t k, uint64_t *n_removed);
 
+/* ---- region queries and picking (not in the reference) ------------------------------------------------------
+ * Which particles lie in a region, or under a point, without downloading every position: full passes over the
+ * particles on the device (csrc/k_query.hip) that change nothing on the context.  Positions, prev, radii, uids, the
+ * uid map, the native step / sort counters, the kept block table and the rosters are left alone; the steps after a
+ * query are bit-identical to those of a context that was never queried.  Each call blocks like gpe_download.
+ *  - Circle: p matches when (p.x-x)*(p.x-x) + (p.y-y)*(p.y-y) <= radius*radius in IEEE binary32, one rounding per
+ *    operation, left to right, no FMA: the predicate and argument check of gpe_remove_particles_in_circle, so the set a
+ *    circle query returns is exactly the set that removal with the same arguments removes.  radius must be finite and
+ *    >= 0, else GPE_ERR_INVALID_ARG.
+ *  - Box: p matches when x0 <= p.x && p.x <= x1 && y0 <= p.y && p.y <= y1 (closed; infinite bounds give half-planes).
+ *    A NaN bound: GPE_ERR_INVALID_ARG.  x0 > x1 or y0 > y1: an empty box, GPE_OK with count 0.
+ *  - Pick: among the particles whose own disc contains (x, y) -- dx*dx + dy*dy <= r*r in binary32 as above, r the
+ *    particle's radius (a negative radius acts as its magnitude) -- the one with the smallest dx*dx + dy*dy, the lowest
+ *    storage index on a tie.  count is 0 or 1.
+ *  - Output: the first min(count, capacity) matches in ascending storage index go into every non-NULL array, all
+ *    arrays filled from the same particles; host memory past those entries is left untouched.  With every array NULL
+ *    the call only counts.
+ *  - Errors: a NULL context, a NULL out or a struct_size below sizeof(gpe_query_result): GPE_ERR_INVALID_ARG; uid
+ *    requested while uids are off: GPE_ERR_STATE; a sharded context (gpe_shard_*, order keys or an active cell box):
+ *    GPE_ERR_UNSUPPORTED.  On any error count is 0 (when out is usable) and no output array is written.
+ *  - No particles: GPE_OK, count 0. */
+typedef struct gpe_query_result {
+    uint32_t struct_size;   /* in: sizeof(gpe_query_result)                                            */
+    uint32_t reserved;      /* in: 0                                                                   */
+    uint64_t capacity;      /* in: entries each non-NULL array below has room for                      */
+    uint64_t count;         /* out: number of matches (may exceed capacity)                            */
+    uint32_t *index;        /* out, may be NULL: storage indices (as gpe_download(GPE_POS)), ascending  */
+    uint32_t *uid;          /* out, may be NULL: their uids; non-NULL while uids are off: GPE_ERR_STATE */
+    float    *pos_xy;       /* out, may be NULL: f32[2 * capacity]                                     */
+    float    *prev_xy;      /* out, may be NULL: f32[2 * capacity]                                     */
+    float    *radius;       /* out, may be NULL: f32[capacity]                                         */
+} gpe_query_result;
+gpe_status gpe_query_circle(gpe_ctx *ctx, float x, float y, float radius, gpe_query_result *out);
+gpe_status gpe_query_box(gpe_ctx *ctx, float x0, float y0, float x1, float y1, gpe_query_result *out);
+gpe_status gpe_pick(gpe_ctx *ctx, float x, float y, gpe_query_result *out);
+
 /* ---- grid (src/grid/grid.rs) ---------------------------------------------------------------- */
 /* Grid::compute_cell_size (:159-161) */
 float gpe_compute_cell_size(float max_obj_radius);
