@@ -32,7 +32,7 @@ inline int stream_grid(uint64_t items, int per_block = kStreamBlock)
 // /root/reference/src)
 // ------------------------------------------------------------------------------------------------
 // grid.wgsl:101-108 / home_cell_ids.wgsl:38-45
-__device__ __forceinline__ uint32_t split_by_bits(uint32_t n)
+__host__ __device__ __forceinline__ uint32_t split_by_bits(uint32_t n)
 {
     uint32_t x = n & 0x0000FFFFu;
     x = (x | (x << 8)) & 0x00FF00FFu;

@@ -34,16 +34,9 @@
 #include "gpe_internal.h"
 #include "k_pair.h"
 
-#ifndef GPE_NAT_THREADS
-#define GPE_NAT_THREADS 512
-#endif
-#ifndef GPE_P5_PRIO
-#define GPE_P5_PRIO 0
-#endif
-
 namespace gpe {
 
-constexpr int kNatThreads = GPE_NAT_THREADS;
+constexpr int kNatThreads = 512;
 constexpr int kNatWaves = kNatThreads / 64;
 
 // exclusive scan of one value per thread over the whole workgroup (kNatWaves waves)
@@ -1378,6 +1371,21 @@ __device__ __forceinline__ int neighbour_offset(const int k)
     return (int)(int8_t)(uint8_t)(packed >> (8 * k));
 }
 
+// Consecutive slots for the particles a wave keeps (`mask`: the lanes that keep theirs): one atomic on the counter word
+// per wave, by lane 0 -- the order of the slots is free.  A slot at or beyond `cap` is not kept; the counter then tells
+// the tile that it ran over.  (The straggler and ghost intake of the direct-slot form.  Its gather, which takes the
+// slots of two rounds with one atomic, and process_tile's three intake paths keep their own copies: with a shared helper
+// k_collide_border<true> and the order-key counting-sort kernels compile to different code, which nobody has timed.)
+__device__ __forceinline__ uint32_t take_slots(uint32_t *counter, const int lane, const uint32_t cap, const uint64_t mask, bool &keep)
+{
+    uint32_t base = 0;
+    if (lane == 0 && mask) base = atomicAdd(counter, (uint32_t)__popcll(mask));
+    base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
+    const uint32_t slot = base + popc_below_lane(mask);
+    keep = keep && slot < cap;
+    return slot;
+}
+
 // One tile: returns false when the region exceeds the window's capacity (nothing written).
 // ORD: a sharded run -- the members of a cell are ordered by A.order_keys[local index] (the particle's index in the
 // unsharded system) instead of by the local index.  A template parameter, not a run-time test: the instantiation
@@ -1908,11 +1916,6 @@ __device__ __forceinline__ bool process_tile(L &S, const CollideArgs &A, const i
     }
 
     // ---- P5: the four colour passes (collision_solver.rs:224), one lane per collision cell ----------
-    // The colour passes are one long dependent chain per cell (sqrt, divisions, LDS round trips): give these
-    // waves issue priority over the other tiles' throughput phases that share the SIMD.
-#if GPE_P5_PRIO
-    __builtin_amdgcn_s_setprio(GPE_P5_PRIO);
-#endif
 #ifdef GPE_DBG_SKIP
     if (!(GPE_DBG_SKIP & 1))                                           // diagnostic builds: phase cost by omission
 #endif
@@ -2023,9 +2026,6 @@ __device__ __forceinline__ bool process_tile(L &S, const CollideArgs &A, const i
         __syncthreads();
 #endif
     }
-#if GPE_P5_PRIO
-    __builtin_amdgcn_s_setprio(0);
-#endif
     GPE_STAMP(5);
 
     // ---- P6: write the tile's own particles back ------------------------------------------------------
@@ -2228,9 +2228,6 @@ constexpr PhantomTable make_phantom_table()
     return t;
 }
 __device__ const PhantomTable kPhantomTable = make_phantom_table();
-#ifndef GPE_VAR_PHANTOM_TABLE
-#define GPE_VAR_PHANTOM_TABLE 1
-#endif
 constexpr int kDirectSlots = 6;                // member slots a zone cell owns
 constexpr int kBigCap = 96;                    // memberships beyond that, per tile
 template <int TX_, int TY_, int CAP, bool LID, int NT_>
@@ -2463,34 +2460,16 @@ __device__ __forceinline__ bool process_tile_direct(L &S, const CollideArgs &A, 
         file(zx, zy, s);
         // phantom cells: the first three set bits of the overlap mask (grid.wgsl:68-90 keeps at most three); neighbour
         // k of the scan (y outer, x inner, centre skipped): dx = {-1,0,1,-1,1,-1,0,1}[k], dy = {-1,-1,-1,0,0,1,1,1}[k]
-#if GPE_VAR_PHANTOM_TABLE
-        // (`over` is the particle's entry of kPhantomTable here: the gather looked it up)
+        // (`over` is the particle's entry of kPhantomTable: the gather looked it up)
         const int cnt = (int)(over & 3u);
 #pragma unroll
         for (int j = 0; j < 3; ++j) {
             if (j >= cnt) break;
             file(zx - 1 + (int)((over >> (2 + 4 * j)) & 3u), zy - 1 + (int)((over >> (4 + 4 * j)) & 3u), s);
         }
-#else
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            if (over == 0) break;
-            const int k = __ffs((int)over) - 1;
-            over &= over - 1u;
-            const int kk = k + (k >= 4 ? 1 : 0);                       // position in the 3 x 3 scan with the centre
-            file(zx + kk % 3 - 1, zy + kk / 3 - 1, s);
-        }
-#endif
     };
-    // what insert() takes as `over`: the mask itself, or its table entry
-    auto phantoms_of = [&](const uint32_t code) -> uint32_t {
-        const uint32_t mask = (code >> kCodeOverlapShift) & 0xFFu;
-#if GPE_VAR_PHANTOM_TABLE
-        return kPhantomTable.v[mask];
-#else
-        return mask;
-#endif
-    };
+    // what insert() takes as `over`: the table entry of the particle's overlap mask
+    auto phantoms_of = [&](const uint32_t code) -> uint32_t { return kPhantomTable.v[(code >> kCodeOverlapShift) & 0xFFu]; };
 #ifdef GPE_DBG_SKIP
     if (!(GPE_DBG_SKIP & 64))                                          // diagnostic builds: phase cost by omission (results wrong)
 #endif
@@ -2581,11 +2560,7 @@ __device__ __forceinline__ bool process_tile_direct(L &S, const CollideArgs &A, 
         const int lx = (int)(en.y & 0xFFFFu) - ox, ly = (int)(en.y >> 16) - oy;
         const uint64_t mk = ballot64(have) & ballot64((uint32_t)lx < (uint32_t)RWX) & ballot64((uint32_t)ly < (uint32_t)RWY);
         bool keep = lanes_of(mk);
-        uint32_t base = 0;
-        if (lane == 0 && mk) base = atomicAdd(&S.misc[3], (uint32_t)__popcll(mk));
-        base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
-        const uint32_t sl = base + popc_below_lane(mk);
-        keep = keep && sl < (uint32_t)L::kSlots;
+        const uint32_t sl = take_slots(&S.misc[3], lane, (uint32_t)L::kSlots, mk, keep);
         if (keep) insert(sl, pp, pr, pid, lidq, lx, ly, phantoms_of(cc));
     }
     if constexpr (ORD) {
@@ -2601,11 +2576,7 @@ __device__ __forceinline__ bool process_tile_direct(L &S, const CollideArgs &A, 
             const int lx = code_window_x(cc, ox), ly = code_window_y(cc, oy);
             const uint64_t mk = ballot64(have) & ballot64(lx < RWX) & ballot64(ly < RWY);
             bool keep = lanes_of(mk);
-            uint32_t base = 0;
-            if (lane == 0 && mk) base = atomicAdd(&S.misc[3], (uint32_t)__popcll(mk));
-            base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
-            const uint32_t sl = base + popc_below_lane(mk);
-            keep = keep && sl < (uint32_t)L::kSlots;
+            const uint32_t sl = take_slots(&S.misc[3], lane, (uint32_t)L::kSlots, mk, keep);
             if (keep) insert(sl, pp, pr, pid, lidq, lx, ly, phantoms_of(cc));
         }
     }
@@ -3066,39 +3037,33 @@ __global__ __launch_bounds__(kNatThreads, GPE_OVF_WAVES) void k_collide_overflow
 // ---------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------
-static uint32_t host_split(uint32_t n)
+// The device buffers of NativeState.  release: free and forget; reserve: a fresh buffer of `bytes` in place of the old one
+// (whose contents are not kept).  After a failed reserve the pointer is NULL and the error is the caller's: GPE_HIP for a
+// buffer the path needs.  An optional buffer is released through GPE_HIP first (a failing hipFree stays an error) and
+// then reserved: only the failed allocation means "run without".
+template <class T>
+static hipError_t release(T *&p)
 {
-    uint32_t x = n & 0x0000FFFFu;
-    x = (x | (x << 8)) & 0x00FF00FFu;
-    x = (x | (x << 4)) & 0x0F0F0F0Fu;
-    x = (x | (x << 2)) & 0x33333333u;
-    x = (x | (x << 1)) & 0x55555555u;
-    return x;
+    const hipError_t e = p ? hipFree(p) : hipSuccess;
+    p = nullptr;
+    return e;
+}
+template <class T>
+static hipError_t reserve(T *&p, size_t bytes)
+{
+    hipError_t e = release(p);
+    if (e == hipSuccess) e = hipMalloc((void **)&p, bytes);
+    if (e != hipSuccess) { (void)hipGetLastError(); p = nullptr; }
+    return e;
 }
 
 void native_release(gpe_ctx *c)
 {
     NativeState &N = c->native;
-    if (N.block_table) (void)hipFree(N.block_table);
-    if (N.keys) (void)hipFree(N.keys);
-    if (N.codes) (void)hipFree(N.codes);
-    if (N.sorted_key) (void)hipFree(N.sorted_key);
-    if (N.exc_count) (void)hipFree(N.exc_count);
-    if (N.gho_count) (void)hipFree(N.gho_count);
-    if (N.roster_hdr) (void)hipFree(N.roster_hdr);
-    if (N.roster_ids) (void)hipFree(N.roster_ids);
-    if (N.gkeys) (void)hipFree(N.gkeys);
-    if (N.gids) (void)hipFree(N.gids);
-    if (N.gkeys_b) (void)hipFree(N.gkeys_b);
-    if (N.gids_b) (void)hipFree(N.gids_b);
-    if (N.gtable) (void)hipFree(N.gtable);
-    if (N.ghist) (void)hipFree(N.ghist);
-    if (N.ids) (void)hipFree(N.ids);
-    if (N.keys_b) (void)hipFree(N.keys_b);
-    if (N.ids_b) (void)hipFree(N.ids_b);
-    if (N.tile_ctl) (void)hipFree(N.tile_ctl);
-    if (N.overflow1) (void)hipFree(N.overflow1);
-    if (N.arena) (void)hipFree(N.arena);
+    void *bufs[] = {N.block_table, N.keys, N.ids, N.keys_b, N.ids_b, N.codes, N.sorted_key, N.gkeys, N.gids, N.gkeys_b,
+                    N.gids_b, N.gtable, N.ghist, N.exc_count, N.gho_count, N.roster_hdr, N.roster_ids, N.tile_ctl,
+                    N.overflow1, N.arena};
+    for (void *b : bufs) (void)release(b);
     if (N.host_stat) (void)hipHostFree(N.host_stat);
     N = NativeState();
 }
@@ -3241,6 +3206,8 @@ static gpe_status native_prepare_step(gpe_ctx *c, uint32_t **sorted_ids, bool al
             hg.gl_entry = N.gho_count + 2 * N.exc_tiles + (size_t)parity * N.exc_tiles * kGhostSlots;
         }
     }
+    // (block key / blocks_x = key * magic >> 40: OnesweepGate::key_div_magic)
+    const uint64_t div_magic = ((1ull << 40) + (uint64_t)N.blocks_x - 1) / (uint64_t)N.blocks_x;
     {
         Scope s(c, "native/hash");
         // at least 4 keys per lane (measured: profiles/r01/tune_hash.txt)
@@ -3248,7 +3215,6 @@ static gpe_status native_prepare_step(gpe_ctx *c, uint32_t **sorted_ids, bool al
         // the kernel is launch and latency there; from 4 M particles on the grid is kHashGridMax either way)
         const int grid = (int)std::min<uint64_t>(kHashGridMax, std::max<uint64_t>(1, n / (2ull * kHashBlock)));
         const uint32_t *n_valid = (c->shard.on && c->shard.active) ? c->shard.counts_now() + kShardTotal : nullptr;
-        const uint64_t div_magic = ((1ull << 40) + (uint64_t)N.blocks_x - 1) / (uint64_t)N.blocks_x;
         const auto hash_kernel = kept_sharded ? k_native_hash<true> : k_native_hash<false>;
         hipLaunchKernelGGL(hash_kernel, dim3(grid), dim3(kHashBlock), 0, c->stream, c->pos, c->radius, n, n_valid,
                            c->cell_size, N.gx, N.gy, N.bx0, N.by0, N.blocks_x, N.blocks_y, N.table_entries, N.keys,
@@ -3281,7 +3247,7 @@ static gpe_status native_prepare_step(gpe_ctx *c, uint32_t **sorted_ids, bool al
         if (gated) {
             g.key_copy = N.sorted_key; g.table_reset = (uint4 *)N.block_table; g.table_pairs = pairs;
             g.key_blocks_x = (uint32_t)N.blocks_x;
-            g.key_div_magic = ((1ull << 40) + (uint64_t)N.blocks_x - 1) / (uint64_t)N.blocks_x;
+            g.key_div_magic = div_magic;
             g.count_now = hg.owned; g.sorted_count = N.tile_ctl + kCtlSortedCount;
         }
         GPE_TRY(onesweep_sort(c, N.keys, N.ids, N.keys_b, N.ids_b, n, N.passes, true, true, &sk, &sv, true,
@@ -3360,43 +3326,30 @@ gpe_status native_configure(gpe_ctx *c)
     if (N.passes < 1) N.passes = 1;
     N.reason = GPE_REASON_TABLE_TOO_LARGE;
     if (N.table_entries > (1u << 27)) return GPE_OK;                   // > 1 GiB of table: stay on compat
+    const size_t table_bytes = ((size_t)N.table_entries + 2) * sizeof(uint2);
+    const size_t particle_words_bytes = (c->cap + 16) * sizeof(uint32_t);   // one word per particle
     if (N.table_cap < N.table_entries) {
-        if (N.block_table) GPE_HIP(c, hipFree(N.block_table));
-        N.block_table = nullptr; N.table_cap = 0;
-        GPE_HIP(c, hipMalloc((void **)&N.block_table, ((size_t)N.table_entries + 2) * sizeof(uint2)));
+        N.table_cap = 0;
+        GPE_HIP(c, reserve(N.block_table, table_bytes));
         N.table_cap = N.table_entries;
     }
     if (N.cap < c->cap) {
-        uint32_t **bufs[4] = {&N.keys, &N.ids, &N.keys_b, &N.ids_b};
-        for (uint32_t **b : bufs) {
-            if (*b) GPE_HIP(c, hipFree(*b));
-            *b = nullptr;
-            GPE_HIP(c, hipMalloc((void **)b, (c->cap + 16) * sizeof(uint32_t)));
-        }
-        if (N.codes) GPE_HIP(c, hipFree(N.codes));
-        N.codes = nullptr;
-        GPE_HIP(c, hipMalloc((void **)&N.codes, (c->cap + 16) * sizeof(uint32_t)));
-        if (N.sorted_key) GPE_HIP(c, hipFree(N.sorted_key));
-        N.sorted_key = nullptr;
-        GPE_HIP(c, hipMalloc((void **)&N.sorted_key, (c->cap + 16) * sizeof(uint32_t)));
-        N.cap = c->cap;
+        N.cap = 0;
         N.gcap = 0;                                                    // (the ghost buffers follow below)
+        for (uint32_t **b : {&N.keys, &N.ids, &N.keys_b, &N.ids_b, &N.codes, &N.sorted_key})
+            GPE_HIP(c, reserve(*b, particle_words_bytes));
+        N.cap = c->cap;
     }
     if (c->shard.on && (N.gcap < c->cap || N.gtable_cap < N.table_entries)) {
         // sharded runs: the ghosts' sort buffers and block table
-        uint32_t **gb[4] = {&N.gkeys, &N.gids, &N.gkeys_b, &N.gids_b};
-        for (uint32_t **b : gb) {
-            if (*b) GPE_HIP(c, hipFree(*b));
-            *b = nullptr;
-            GPE_HIP(c, hipMalloc((void **)b, (c->cap + 16) * sizeof(uint32_t)));
-        }
+        N.gcap = 0; N.gtable_cap = 0;
+        for (uint32_t **b : {&N.gkeys, &N.gids, &N.gkeys_b, &N.gids_b})
+            GPE_HIP(c, reserve(*b, particle_words_bytes));
         N.gcap = c->cap;
-        if (N.gtable) GPE_HIP(c, hipFree(N.gtable));
-        N.gtable = nullptr;
-        GPE_HIP(c, hipMalloc((void **)&N.gtable, ((size_t)N.table_entries + 2) * sizeof(uint2)));
+        GPE_HIP(c, reserve(N.gtable, table_bytes));
         N.gtable_cap = N.table_entries;
         if (!N.ghist) {
-            GPE_HIP(c, hipMalloc((void **)&N.ghist, 2 * (size_t)kHistCopies * 4 * 256 * sizeof(uint32_t)));
+            GPE_HIP(c, reserve(N.ghist, 2 * (size_t)kHistCopies * 4 * 256 * sizeof(uint32_t)));
             GPE_HIP(c, hipMemsetAsync(N.ghist, 0, 2 * (size_t)kHistCopies * 4 * 256 * sizeof(uint32_t), c->stream));
         }
     }
@@ -3415,13 +3368,12 @@ gpe_status native_configure(gpe_ctx *c)
         }
         N.exc_tiles = (uint64_t)N.tb.nx * (uint64_t)N.tb.ny;
         if (N.exc_cap < N.exc_tiles) {
-            if (N.exc_count) GPE_HIP(c, hipFree(N.exc_count));
-            N.exc_count = nullptr; N.exc_entry = nullptr; N.exc_cap = 0;
+            N.exc_entry = nullptr; N.exc_cap = 0;
+            GPE_HIP(c, release(N.exc_count));
             // (264 B per tile and set: a sparse scene in a huge world -- up to 8 M tiles -- may not get them; the run
             // then sorts every step, native_prepare_step, instead of failing to configure)
             const size_t bytes = 2 * N.exc_tiles * sizeof(uint32_t) + 16 + 2 * N.exc_tiles * kExcSlots * sizeof(uint2);
-            if (hipMalloc((void **)&N.exc_count, bytes) == hipSuccess) N.exc_cap = N.exc_tiles;
-            else { (void)hipGetLastError(); N.exc_count = nullptr; }
+            if (reserve(N.exc_count, bytes) == hipSuccess) N.exc_cap = N.exc_tiles;
         }
         if (N.exc_count) {
             // (entries behind the counts of both sets, 8-byte aligned)
@@ -3434,17 +3386,17 @@ gpe_status native_configure(gpe_ctx *c)
     // slots per particle (4 x the benchmark's ratio) the run does without them.
     const bool rosters_pay = N.exc_tiles * (uint64_t)kRosterCap <= 16ull * std::max<uint64_t>(c->n, 1u << 16);
     if (!rosters_pay && N.roster_hdr) {
-        GPE_HIP(c, hipFree(N.roster_hdr)); GPE_HIP(c, hipFree(N.roster_ids));
-        N.roster_hdr = nullptr; N.roster_ids = nullptr; N.roster_cap = 0;
+        N.roster_cap = 0;
+        GPE_HIP(c, release(N.roster_hdr));
+        GPE_HIP(c, release(N.roster_ids));
     }
     if (c->shard.on && c->has_active_box && N.gho_cap < N.exc_tiles) {
         // ghost lists (sharded runs): a count and kGhostSlots ids per tile, two sets.  Optional: without them the ghosts
         // are sorted into their block table every step
-        if (N.gho_count) GPE_HIP(c, hipFree(N.gho_count));
-        N.gho_count = nullptr; N.gho_cap = 0;
-        if (hipMalloc((void **)&N.gho_count, 2 * N.exc_tiles * (1 + (size_t)kGhostSlots) * sizeof(uint32_t) + 64) == hipSuccess)
+        N.gho_cap = 0;
+        GPE_HIP(c, release(N.gho_count));
+        if (reserve(N.gho_count, 2 * N.exc_tiles * (1 + (size_t)kGhostSlots) * sizeof(uint32_t) + 64) == hipSuccess)
             N.gho_cap = N.exc_tiles;
-        else { (void)hipGetLastError(); N.gho_count = nullptr; }
     }
     if (N.gho_count) GPE_HIP(c, hipMemsetAsync(N.gho_count, 0, 2 * N.exc_tiles * sizeof(uint32_t), c->stream));
     if (rosters_pay && N.exc_count &&
@@ -3452,24 +3404,20 @@ gpe_status native_configure(gpe_ctx *c)
         // tile rosters (CollideArgs): 16 + 4 kRosterCap bytes per 32x32 tile.  Optional: a device that has no room for
         // them runs without (every step then looks its blocks up)
         if (N.roster_cap < N.exc_tiles) {
-            if (N.roster_hdr) GPE_HIP(c, hipFree(N.roster_hdr));
-            if (N.roster_ids) GPE_HIP(c, hipFree(N.roster_ids));
-            N.roster_hdr = nullptr; N.roster_ids = nullptr; N.roster_cap = 0;
-            hipError_t e1 = hipMalloc((void **)&N.roster_hdr, N.exc_tiles * sizeof(uint4));
-            hipError_t e2 = e1 == hipSuccess ? hipMalloc((void **)&N.roster_ids, N.exc_tiles * (size_t)kRosterCap * sizeof(uint32_t)) : e1;
-            if (e1 != hipSuccess || e2 != hipSuccess) {
-                (void)hipGetLastError();
-                if (N.roster_hdr) (void)hipFree(N.roster_hdr);
-                N.roster_hdr = nullptr; N.roster_ids = nullptr;
-            } else N.roster_cap = N.exc_tiles;
+            N.roster_cap = 0;
+            GPE_HIP(c, release(N.roster_hdr));
+            GPE_HIP(c, release(N.roster_ids));
+            if (reserve(N.roster_hdr, N.exc_tiles * sizeof(uint4)) == hipSuccess &&
+                reserve(N.roster_ids, N.exc_tiles * (size_t)kRosterCap * sizeof(uint32_t)) == hipSuccess)
+                N.roster_cap = N.exc_tiles;
+            else { (void)release(N.roster_hdr); (void)release(N.roster_ids); }
         }
         // (stamp 0 is never current: the tiles compare with sorts + 1)
         if (N.roster_hdr) GPE_HIP(c, hipMemsetAsync(N.roster_hdr, 0, N.exc_tiles * sizeof(uint4), c->stream));
     }
     if (N.overflow_cap < tiles) {
-        if (N.overflow1) GPE_HIP(c, hipFree(N.overflow1));
-        N.overflow1 = nullptr; N.overflow_cap = 0;
-        GPE_HIP(c, hipMalloc((void **)&N.overflow1, (3 * tiles + 32 + 2 * kHintMax) * sizeof(uint32_t)));   // (the tiles, then their halves: CollideArgs::overflow2, then the hints)
+        N.overflow_cap = 0;
+        GPE_HIP(c, reserve(N.overflow1, (3 * tiles + 32 + 2 * kHintMax) * sizeof(uint32_t)));   // (the tiles, then their halves: CollideArgs::overflow2, then the hints)
         N.overflow_cap = tiles;
     }
     {
@@ -3479,7 +3427,7 @@ gpe_status native_configure(gpe_ctx *c)
         GPE_TRY(arena_reserve(c, std::max<uint64_t>(want, N.arena_cap)));
     }
     if (!N.tile_ctl) {
-        GPE_HIP(c, hipMalloc((void **)&N.tile_ctl, kCtlWords * sizeof(uint32_t)));
+        GPE_HIP(c, reserve(N.tile_ctl, kCtlWords * sizeof(uint32_t)));
         GPE_HIP(c, hipMemsetAsync(N.tile_ctl, 0, kCtlWords * sizeof(uint32_t), c->stream));
     }
     if (!N.host_stat) GPE_HIP(c, hipHostMalloc((void **)&N.host_stat, 64, hipHostMallocDefault));
@@ -3529,14 +3477,14 @@ static gpe_status arena_reserve(gpe_ctx *c, uint64_t want)
     // the new arena first: on failure the old one stays in place (a run that must stay on the native kernels keeps
     // working with it) and the error is the caller's to report
     void *fresh = nullptr;
-    hipError_t e = hipMalloc(&fresh, want * kArenaBytesPerSlot + 256);
-    if (e != hipSuccess) (void)hipGetLastError();
+    const hipError_t e = reserve(fresh, want * kArenaBytesPerSlot + 256);
     if (e == hipErrorOutOfMemory) return fail(c, GPE_ERR_OOM, "native collide: out of device memory for the spill arena");
     if (e != hipSuccess) return fail(c, GPE_ERR_HIP, std::string("hipMalloc (spill arena): ") + hipGetErrorName(e));
     GPE_HIP(c, hipStreamSynchronize(c->stream));                       // (kernels in flight may still use the old one)
-    if (N.arena) GPE_HIP(c, hipFree(N.arena));
+    const hipError_t freed = release(N.arena);                         // (reported below: the new arena is in place either way)
     N.arena = fresh;
     N.arena_cap = want;
+    GPE_HIP(c, freed);
     return GPE_OK;
 }
 
