@@ -25,6 +25,7 @@ FLAG_XCD_EIGHTHS = 64
 FLAG_NO_HALF_TILES = 128
 FLAG_SHARD_OVERLAP = 256
 FLAG_FUSED_HISTOGRAMS = 512
+FLAG_GUARD_ALLOCS = 1024
 PIPELINE_COMPAT, PIPELINE_NATIVE = 0, 1
 (REASON_NONE, REASON_MODE_COMPAT, REASON_NO_PARTICLES, REASON_OUT_OF_BOX, REASON_GRID_TOO_WIDE,
  REASON_TABLE_TOO_LARGE, REASON_DENSE_WINDOWS) = range(7)
@@ -47,7 +48,8 @@ class GpeConfig(C.Structure):
         ("gravity_x", C.c_float), ("gravity_y", C.c_float),
         ("cell_size_multiplier", C.c_float), ("stiffness", C.c_float),
         ("mouse_strength", C.c_float), ("mode", C.c_uint32), ("profiling", C.c_uint32),
-        ("flags", C.c_uint32), ("reserved", C.c_uint32 * 4),
+        ("flags", C.c_uint32), ("guard_canary", C.c_uint32), ("guard_poison", C.c_uint32),
+        ("reserved", C.c_uint32 * 2),
     ]
 
 
@@ -117,6 +119,21 @@ class GpeQueryResult(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("capacity", C.c_uint64), ("count", C.c_uint64),
                 ("index", C.POINTER(C.c_uint32)), ("uid", C.POINTER(C.c_uint32)), ("pos_xy", C.POINTER(C.c_float)),
                 ("prev_xy", C.POINTER(C.c_float)), ("radius", C.POINTER(C.c_float))]
+
+
+GUARD_MAX_ZONES = 8
+GUARD_FRONT, GUARD_REAR = 0, 1
+
+
+class GpeGuardZone(C.Structure):
+    """gpe_guard_zone: one damaged red zone (offsets: front relative to the payload's first byte, rear to its end)."""
+    _fields_ = [("tag", C.c_char * 32), ("side", C.c_uint32), ("first_word", C.c_uint32),
+                ("first_offset", C.c_int64), ("last_offset", C.c_int64), ("payload_bytes", C.c_uint64)]
+
+
+class GpeGuardReport(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("damaged", C.c_uint32), ("listed", C.c_uint32),
+                ("allocations", C.c_uint32), ("zones", GpeGuardZone * GUARD_MAX_ZONES)]
 
 
 class GpeError(RuntimeError):
@@ -224,6 +241,8 @@ SYMBOLS = [
     ("gpe_reset_timings", _I32, [_VP]),
     ("gpe_get_timings", _I32, [_VP, C.POINTER(GpeTiming), C.POINTER(_U32)]),
     ("gpe_get_trace", _I32, [_VP, C.POINTER(GpeTraceEvent), C.POINTER(_U32)]),
+    ("gpe_guard_check", _I32, [_VP, C.POINTER(GpeGuardReport)]),
+    ("gpe_guard_registry", _I32, [_VP, C.c_char_p, _U64, C.POINTER(_U64)]),
 ]
 
 _lib = None

@@ -90,48 +90,203 @@ static void resolve_pending(gpe_ctx *c)
     c->pending.clear();
 }
 
-// ---- buffers --------------------------------------------------------------------------------------
-template <typename T>
-static gpe_status dev_alloc(gpe_ctx *c, T **p, uint64_t count)
+// ---- device memory: payload, slack, red zones ------------------------------------------
+// The only place that calls the runtime's allocator.  Every allocation of a context is in c->guard.live.
+constexpr uint32_t kGuardCanary = 0x3C3u, kGuardPoison = 0x2A5u;       // the defaults of gpe_config.guard_canary / guard_poison
+
+struct GuardZoneDesc { uint64_t start, bytes; };                       // a red zone: device address, length
+struct GuardZoneHit { unsigned long long first, last; };               // damaged bytes, relative to start (first = ~0: none)
+
+// base[0, words): the canary, except the bytes [pay_lo, pay_hi) which get the poison (bytewise at the edges)
+__global__ void k_guard_fill(uint32_t *base, uint64_t words, uint64_t pay_lo, uint64_t pay_hi, uint32_t canary,
+                             uint32_t poison)
 {
-    *p = nullptr;
-    hipError_t e = hipMalloc((void **)p, std::max<uint64_t>(count, 4) * sizeof(T) + 64);
-    if (e != hipSuccess) (void)hipGetLastError();   // the failure is reported here: do not leave it for the next launch check
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t w = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; w < words; w += stride) {
+        uint32_t v = 0;
+        for (uint32_t k = 0; k < 4; ++k) {
+            const uint64_t b = 4 * w + k;
+            v |= ((b >= pay_lo && b < pay_hi) ? poison : canary) & (0xFFu << (8 * k));
+        }
+        base[w] = v;
+    }
+}
+
+// One workgroup per zone.  Reads the aligned words that cover the zone (all inside the allocation: its base is
+// 256-byte aligned and its size a multiple of 16) and compares the zone's own bytes only.
+__global__ void k_guard_check(const GuardZoneDesc *zones, GuardZoneHit *hits, uint32_t canary)
+{
+    const GuardZoneDesc z = zones[blockIdx.x];
+    const uint64_t lo = z.start, hi = z.start + z.bytes;
+    for (uint64_t a = (lo & ~3ull) + 4ull * threadIdx.x; a < hi; a += 4ull * blockDim.x) {
+        uint32_t v = *(const uint32_t *)a ^ canary;
+        for (uint32_t k = 0; k < 4; ++k)
+            if (a + k < lo || a + k >= hi) v &= ~(0xFFu << (8 * k));   // the unaligned head / tail of a zone
+        if (v == 0) continue;
+        const uint64_t fb = (uint64_t)(__builtin_ctz(v) >> 3), lb = (uint64_t)((31 - __builtin_clz(v)) >> 3);
+        atomicMin(&hits[blockIdx.x].first, (unsigned long long)(a + fb - lo));
+        atomicMax(&hits[blockIdx.x].last, (unsigned long long)(a + lb - lo));
+    }
+}
+
+static void guard_sync(gpe_ctx *c)
+{
+    if (c->stream) (void)hipStreamSynchronize(c->stream);
+    if (c->shard.xstream) (void)hipStreamSynchronize(c->shard.xstream);
+}
+
+// Compare the zones of list[0, count) with the canary; damaged ones are appended to out (up to GPE_GUARD_MAX_ZONES
+// entries in all) and counted in *damaged.  Synchronises.
+static hipError_t guard_scan(gpe_ctx *c, const DevAlloc *list, size_t count, std::vector<gpe_guard_zone> &out,
+                             uint32_t *damaged)
+{
+    if (count == 0) return hipSuccess;
+    std::vector<GuardZoneDesc> desc(2 * count);
+    std::vector<GuardZoneHit> hit(2 * count);
+    for (size_t i = 0; i < count; ++i) {
+        const DevAlloc &a = list[i];
+        const uint64_t base = (uint64_t)a.base, ptr = (uint64_t)a.ptr;
+        desc[2 * i] = {base, ptr - base};
+        desc[2 * i + 1] = {ptr + a.payload, base + a.total - (ptr + a.payload)};
+        hit[2 * i] = hit[2 * i + 1] = {~0ull, 0ull};
+    }
+    const size_t desc_bytes = desc.size() * sizeof(GuardZoneDesc), hit_bytes = hit.size() * sizeof(GuardZoneHit);
+    uint8_t *d = nullptr;
+    hipError_t e = hipMalloc((void **)&d, desc_bytes + hit_bytes);
+    if (e != hipSuccess) { (void)hipGetLastError(); return e; }
+    guard_sync(c);
+    e = hipMemcpy(d, desc.data(), desc_bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d + desc_bytes, hit.data(), hit_bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(k_guard_check, dim3((uint32_t)desc.size()), dim3(kStreamBlock), 0, c->stream,
+                           (const GuardZoneDesc *)d, (GuardZoneHit *)(d + desc_bytes), c->guard.canary);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess) e = hipMemcpy(hit.data(), d + desc_bytes, hit_bytes, hipMemcpyDeviceToHost);
+    (void)hipFree(d);
+    if (e != hipSuccess) { (void)hipGetLastError(); return e; }
+    for (size_t z = 0; z < hit.size(); ++z) {
+        if (hit[z].first == ~0ull) continue;
+        *damaged += 1;
+        if (out.size() >= GPE_GUARD_MAX_ZONES) continue;
+        const DevAlloc &a = list[z / 2];
+        gpe_guard_zone g;
+        memset(&g, 0, sizeof(g));
+        strncpy(g.tag, a.tag, sizeof(g.tag) - 1);
+        g.side = (z & 1) ? GPE_GUARD_REAR : GPE_GUARD_FRONT;
+        const int64_t origin = (z & 1) ? 0 : -(int64_t)desc[z].bytes;  // front zone: relative to the payload's first byte
+        g.first_offset = origin + (int64_t)hit[z].first;
+        g.last_offset = origin + (int64_t)hit[z].last;
+        g.payload_bytes = a.payload;
+        (void)hipMemcpy(&g.first_word, (const void *)((desc[z].start + hit[z].first) & ~3ull), 4, hipMemcpyDeviceToHost);
+        out.push_back(g);
+    }
+    return hipSuccess;
+}
+
+static std::string guard_zone_text(const gpe_guard_zone &g)
+{
+    char buf[256];
+    snprintf(buf, sizeof(buf), "guard: %s zone of \"%s\" (payload %llu B) damaged at bytes %lld..%lld, first word 0x%08x",
+             g.side == GPE_GUARD_REAR ? "rear" : "front", g.tag, (unsigned long long)g.payload_bytes,
+             (long long)g.first_offset, (long long)g.last_offset, g.first_word);
+    return buf;
+}
+
+hipError_t gpe_dev_reserve(gpe_ctx *c, void **ptr, uint64_t payload_bytes, uint64_t slack_bytes, const char *tag)
+{
+    *ptr = nullptr;
+    GuardState &G = c->guard;
+    DevAlloc a;
+    a.payload = payload_bytes; a.slack = slack_bytes; a.tag = tag;
+    uint64_t front = 0;
+    a.total = payload_bytes + slack_bytes;
+    if (G.on) {
+        front = kGuardZone;                                            // (a multiple of 256: the payload stays aligned)
+        a.total = (front + payload_bytes + slack_bytes + kGuardZone + 15) & ~15ull;
+    }
+    hipError_t e = hipMalloc(&a.base, a.total);
+    if (e != hipSuccess) { (void)hipGetLastError(); return e; }        // reported by the caller: not left for the next launch check
+    a.ptr = (uint8_t *)a.base + front;
+    if (G.on) {
+        hipLaunchKernelGGL(k_guard_fill, dim3(stream_grid(a.total / 4)), dim3(kStreamBlock), 0, c->stream,
+                           (uint32_t *)a.base, a.total / 4, front, front + payload_bytes, G.canary, G.poison);
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);      // (the buffer may be used on another stream next)
+        if (e != hipSuccess) { (void)hipGetLastError(); (void)hipFree(a.base); return e; }
+    }
+    G.live.push_back(a);
+    *ptr = a.ptr;
+    return hipSuccess;
+}
+
+hipError_t gpe_dev_release(gpe_ctx *c, void **ptr)
+{
+    void *p = *ptr;
+    *ptr = nullptr;
+    if (!p) return hipSuccess;
+    GuardState &G = c->guard;
+    size_t i = G.live.size();
+    while (i > 0 && G.live[i - 1].ptr != p) --i;                       // (the newest first: buffers are mostly replaced)
+    if (i == 0) return G.on ? hipErrorInvalidValue : hipFree(p);       // not this context's: the caller's to free
+    const DevAlloc a = G.live[i - 1];
+    G.live.erase(G.live.begin() + (i - 1));
+    if (G.on) {
+        size_t k = 0;
+        while (k < G.released.size() && strcmp(G.released[k].tag, a.tag) != 0) ++k;
+        if (k == G.released.size()) G.released.push_back(a);
+        G.released[k] = a;
+        G.released[k].ptr = G.released[k].base = nullptr;
+        // the zones go with the buffer: look at them now, and keep what they show for the next gpe_guard_check -- or
+        // that they could not be looked at
+        const hipError_t e = guard_scan(c, &a, 1, G.kept, &G.kept_count);
+        if (e != hipSuccess && G.scan_failed == hipSuccess) G.scan_failed = e;
+    }
+    return hipFree(a.base);
+}
+
+template <typename T>
+static gpe_status dev_alloc(gpe_ctx *c, T **p, uint64_t count, const char *tag)
+{
+    // payload: count elements.  slack: the round-up to 4 elements and 64 bytes -- no kernel is known to read them; they
+    // keep the unguarded allocation at the size it always had (max(count, 4) * sizeof(T) + 64)
+    const uint64_t payload = count * sizeof(T);
+    hipError_t e = dev_reserve(c, p, payload, std::max<uint64_t>(count, 4) * sizeof(T) + 64 - payload, tag);
     if (e == hipErrorOutOfMemory) return fail(c, GPE_ERR_OOM, "hipMalloc: out of device memory");
     if (e != hipSuccess) return fail(c, GPE_ERR_HIP, std::string("hipMalloc: ") + hipGetErrorName(e));
     return GPE_OK;
 }
 
 template <typename T>
-static void dev_free(T *&p)
+static void dev_free(gpe_ctx *c, T *&p)
 {
-    if (p) (void)hipFree(p);
-    p = nullptr;
+    (void)dev_release(c, p);
 }
 
 // The uid buffers, the uid -> index map and the lookup staging (the uid switch itself stays as it is).
 static void free_uid_buffers(gpe_ctx *c)
 {
     UidState &u = c->uid;
-    dev_free(u.uids); dev_free(u.uids_copy);
-    dev_free(u.map_keys); dev_free(u.map_vals); dev_free(u.dup); dev_free(u.query);
+    dev_free(c, u.uids); dev_free(c, u.uids_copy);
+    dev_free(c, u.map_keys); dev_free(c, u.map_vals); dev_free(c, u.dup); dev_free(c, u.query);
     u.map_cap = u.query_cap = 0;
     u.map_valid = false;
 }
 
 static void free_particle_buffers(gpe_ctx *c)
 {
-    dev_free(c->pos); dev_free(c->prev); dev_free(c->radius);
-    dev_free(c->pos_copy); dev_free(c->prev_copy); dev_free(c->radius_copy);
-    dev_free(c->home_cell_ids); dev_free(c->particle_ids);
-    dev_free(c->cell_ids); dev_free(c->object_ids);
-    dev_free(c->chunk_obj_count); dev_free(c->collision_cells); dev_free(c->indirect_args);
-    dev_free(c->order_keys);
-    dev_free(c->remove_ws.tile_count); dev_free(c->remove_ws.tile_key); dev_free(c->remove_ws.max_key);
-    dev_free(c->remove_ws.mask);
+    dev_free(c, c->pos); dev_free(c, c->prev); dev_free(c, c->radius);
+    dev_free(c, c->pos_copy); dev_free(c, c->prev_copy); dev_free(c, c->radius_copy);
+    dev_free(c, c->home_cell_ids); dev_free(c, c->particle_ids);
+    dev_free(c, c->cell_ids); dev_free(c, c->object_ids);
+    dev_free(c, c->chunk_obj_count); dev_free(c, c->collision_cells); dev_free(c, c->indirect_args);
+    dev_free(c, c->order_keys);
+    dev_free(c, c->remove_ws.tile_count); dev_free(c, c->remove_ws.tile_key); dev_free(c, c->remove_ws.max_key);
+    dev_free(c, c->remove_ws.mask);
     c->remove_ws.tiles_cap = c->remove_ws.mask_cap = 0;
-    dev_free(c->query_ws.tile_count); dev_free(c->query_ws.tile_key); dev_free(c->query_ws.pick);
-    dev_free(c->query_ws.stage);
+    dev_free(c, c->query_ws.tile_count); dev_free(c, c->query_ws.tile_key); dev_free(c, c->query_ws.pick);
+    dev_free(c, c->query_ws.stage);
     c->query_ws.tiles_cap = c->query_ws.stage_cap = 0;
     free_uid_buffers(c);
     c->cap = 0;
@@ -171,15 +326,15 @@ static uint64_t num_chunks(const gpe_ctx *c)
 // an allocation on the step path, once.  At 100 M particles that is 8.4 GB of 15 that stay unallocated.
 static gpe_status alloc_grid_buffers(gpe_ctx *c, uint64_t cap)
 {
-    gpe_status st = dev_alloc(c, &c->cell_ids, cap * 4);
-    if (st == GPE_OK) st = dev_alloc(c, &c->object_ids, cap * 4);
-    if (st == GPE_OK) st = dev_alloc(c, &c->chunk_obj_count, cap);
-    if (st == GPE_OK) st = dev_alloc(c, &c->collision_cells, cap * 4);
-    if (st == GPE_OK) st = dev_alloc(c, &c->indirect_args, 4);
+    gpe_status st = dev_alloc(c, &c->cell_ids, cap * 4, "grid.cell_ids");
+    if (st == GPE_OK) st = dev_alloc(c, &c->object_ids, cap * 4, "grid.object_ids");
+    if (st == GPE_OK) st = dev_alloc(c, &c->chunk_obj_count, cap, "grid.chunk_obj_count");
+    if (st == GPE_OK) st = dev_alloc(c, &c->collision_cells, cap * 4, "grid.collision_cells");
+    if (st == GPE_OK) st = dev_alloc(c, &c->indirect_args, 4, "grid.indirect_args");
     if (st == GPE_OK) st = sort_reserve(c, cap * 4);
     if (st != GPE_OK) {
-        dev_free(c->cell_ids); dev_free(c->object_ids); dev_free(c->chunk_obj_count);
-        dev_free(c->collision_cells); dev_free(c->indirect_args);
+        dev_free(c, c->cell_ids); dev_free(c, c->object_ids); dev_free(c, c->chunk_obj_count);
+        dev_free(c, c->collision_cells); dev_free(c, c->indirect_args);
     }
     return st;
 }
@@ -187,18 +342,18 @@ static gpe_status alloc_grid_buffers(gpe_ctx *c, uint64_t cap)
 // Allocate every particle-count-dependent buffer for `cap` particles (State::new, state.rs:34-70).
 static gpe_status alloc_particle_buffers(gpe_ctx *c, uint64_t cap, bool with_grid)
 {
-    GPE_TRY(dev_alloc(c, &c->pos, cap));
-    GPE_TRY(dev_alloc(c, &c->prev, cap));
-    GPE_TRY(dev_alloc(c, &c->radius, cap));
-    GPE_TRY(dev_alloc(c, &c->pos_copy, cap));
-    GPE_TRY(dev_alloc(c, &c->prev_copy, cap));
-    GPE_TRY(dev_alloc(c, &c->radius_copy, cap));
-    GPE_TRY(dev_alloc(c, &c->home_cell_ids, cap));
-    GPE_TRY(dev_alloc(c, &c->particle_ids, cap));
-    GPE_TRY(dev_alloc(c, &c->order_keys, cap));
+    GPE_TRY(dev_alloc(c, &c->pos, cap, "particles.pos"));
+    GPE_TRY(dev_alloc(c, &c->prev, cap, "particles.prev"));
+    GPE_TRY(dev_alloc(c, &c->radius, cap, "particles.radius"));
+    GPE_TRY(dev_alloc(c, &c->pos_copy, cap, "particles.pos_copy"));
+    GPE_TRY(dev_alloc(c, &c->prev_copy, cap, "particles.prev_copy"));
+    GPE_TRY(dev_alloc(c, &c->radius_copy, cap, "particles.radius_copy"));
+    GPE_TRY(dev_alloc(c, &c->home_cell_ids, cap, "particles.home_cell_ids"));
+    GPE_TRY(dev_alloc(c, &c->particle_ids, cap, "particles.particle_ids"));
+    GPE_TRY(dev_alloc(c, &c->order_keys, cap, "particles.order_keys"));
     if (c->uid.on) {
-        GPE_TRY(dev_alloc(c, &c->uid.uids, cap));
-        GPE_TRY(dev_alloc(c, &c->uid.uids_copy, cap));
+        GPE_TRY(dev_alloc(c, &c->uid.uids, cap, "uid.uids"));
+        GPE_TRY(dev_alloc(c, &c->uid.uids_copy, cap, "uid.uids_copy"));
     }
     c->cap = cap;
     if (with_grid) GPE_TRY(alloc_grid_buffers(c, cap));
@@ -314,12 +469,12 @@ static gpe_status grow_particle_buffers(gpe_ctx *c, uint64_t cap)
         return st;
     }
     float2 *f2[] = {old.pos, old.prev, old.pos_copy, old.prev_copy};
-    for (float2 *p : f2) if (p) (void)hipFree(p);
+    for (float2 *p : f2) dev_free(c, p);
     float *f1[] = {old.radius, old.radius_copy};
-    for (float *p : f1) if (p) (void)hipFree(p);
+    for (float *p : f1) dev_free(c, p);
     uint32_t *u[] = {old.home_cell_ids, old.particle_ids, old.cell_ids, old.object_ids, old.chunk_obj_count,
                      old.collision_cells, old.indirect_args, old.order_keys, old.uids, old.uids_copy};
-    for (uint32_t *p : u) if (p) (void)hipFree(p);
+    for (uint32_t *p : u) dev_free(c, p);
     return GPE_OK;
 }
 
@@ -360,19 +515,19 @@ static gpe_status remove_reserve(gpe_ctx *c, uint64_t mask_bytes)
     RemoveWorkspace &ws = c->remove_ws;
     const uint64_t tiles = remove_tiles(c->n);
     if (ws.tiles_cap < tiles) {
-        dev_free(ws.tile_count);
-        dev_free(ws.tile_key);
+        dev_free(c, ws.tile_count);
+        dev_free(c, ws.tile_key);
         ws.tiles_cap = 0;
-        GPE_TRY(dev_alloc(c, &ws.tile_count, tiles));
-        GPE_TRY(dev_alloc(c, &ws.tile_key, tiles));
+        GPE_TRY(dev_alloc(c, &ws.tile_count, tiles, "remove.tile_count"));
+        GPE_TRY(dev_alloc(c, &ws.tile_key, tiles, "remove.tile_key"));
         ws.tiles_cap = tiles;
     }
-    if (!ws.max_key) GPE_TRY(dev_alloc(c, &ws.max_key, 1));
+    if (!ws.max_key) GPE_TRY(dev_alloc(c, &ws.max_key, 1, "remove.max_key"));
     if (ws.mask_cap < mask_bytes) {
         const uint64_t want = std::max(c->cap, mask_bytes);             // (a later call on fewer particles fits)
-        dev_free(ws.mask);
+        dev_free(c, ws.mask);
         ws.mask_cap = 0;
-        GPE_TRY(dev_alloc(c, &ws.mask, want));
+        GPE_TRY(dev_alloc(c, &ws.mask, want, "remove.mask"));
         ws.mask_cap = want;
     }
     return scan_reserve(c, tiles);
@@ -442,8 +597,8 @@ static gpe_status uids_switch_on(gpe_ctx *c)
 {
     UidState &u = c->uid;
     if (c->cap > 0) {
-        gpe_status st = dev_alloc(c, &u.uids, c->cap);
-        if (st == GPE_OK) st = dev_alloc(c, &u.uids_copy, c->cap);
+        gpe_status st = dev_alloc(c, &u.uids, c->cap, "uid.uids");
+        if (st == GPE_OK) st = dev_alloc(c, &u.uids_copy, c->cap, "uid.uids_copy");
         if (st != GPE_OK) {
             free_uid_buffers(c);
             return st;
@@ -462,15 +617,15 @@ static gpe_status uid_map_build(gpe_ctx *c, const uint32_t *src, bool *dup)
     const uint64_t n = c->n;
     u.map_valid = false;
     if (u.map_cap < n) {
-        dev_free(u.map_keys);
-        dev_free(u.map_vals);
+        dev_free(c, u.map_keys);
+        dev_free(c, u.map_vals);
         u.map_cap = 0;
         const uint64_t want = std::max(c->cap, n);
-        GPE_TRY(dev_alloc(c, &u.map_keys, want));
-        GPE_TRY(dev_alloc(c, &u.map_vals, want));
+        GPE_TRY(dev_alloc(c, &u.map_keys, want, "uid.map_keys"));
+        GPE_TRY(dev_alloc(c, &u.map_vals, want, "uid.map_vals"));
         u.map_cap = want;
     }
-    if (!u.dup) GPE_TRY(dev_alloc(c, &u.dup, 1));
+    if (!u.dup) GPE_TRY(dev_alloc(c, &u.dup, 1, "uid.dup"));
     GPE_TRY(sort_reserve(c, n));
     {
         Scope s(c, "uids/map");
@@ -503,9 +658,9 @@ static gpe_status uid_query_reserve(gpe_ctx *c, uint64_t bytes)
 {
     UidState &u = c->uid;
     if (u.query_cap >= bytes) return GPE_OK;
-    dev_free(u.query);
+    dev_free(c, u.query);
     u.query_cap = 0;
-    GPE_TRY(dev_alloc(c, &u.query, bytes));
+    GPE_TRY(dev_alloc(c, &u.query, bytes, "uid.query"));
     u.query_cap = bytes;
     return GPE_OK;
 }
@@ -662,6 +817,14 @@ gpe_status gpe_create(const gpe_config *cfg, gpe_ctx **out)
     }
     if (local.mode != GPE_MODE_COMPAT && local.mode != GPE_MODE_NATIVE)
         return fail(nullptr, GPE_ERR_INVALID_ARG, "gpe_create: unknown mode");
+    if (local.flags & GPE_FLAG_GUARD_ALLOCS) {
+        // (without the flag the two words are not looked at, as when they were reserved)
+        // nonzero, a nonzero finite f32 (a denormal), and as an index of 16-byte elements inside a 16 KiB zone
+        const uint32_t ca = local.guard_canary ? local.guard_canary : kGuardCanary;
+        const uint32_t po = local.guard_poison ? local.guard_poison : kGuardPoison;
+        if (ca >= kGuardZone / 16 || po >= kGuardZone / 16 || ca == po)
+            return fail(nullptr, GPE_ERR_INVALID_ARG, "gpe_create: guard_canary / guard_poison must be in [1, 1023] and differ");
+    }
     int count = 0;
     hipError_t e = hipGetDeviceCount(&count);
     if (e != hipSuccess || count <= 0)
@@ -679,6 +842,9 @@ gpe_status gpe_create(const gpe_config *cfg, gpe_ctx **out)
     c->profiling = local.profiling != 0;
     c->profile_every = local.profiling;
     c->use_onesweep = (local.flags & GPE_FLAG_SAFE_SORT) == 0;
+    c->guard.on = (local.flags & GPE_FLAG_GUARD_ALLOCS) != 0;
+    c->guard.canary = local.guard_canary ? local.guard_canary : kGuardCanary;
+    c->guard.poison = local.guard_poison ? local.guard_poison : kGuardPoison;
     if ((e = hipSetDevice(dev)) != hipSuccess ||
         (e = hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking)) != hipSuccess) {
         std::string m = std::string("gpe_create: ") + hipGetErrorName(e);
@@ -1062,18 +1228,18 @@ static gpe_status query_reserve(gpe_ctx *c, uint64_t stage_bytes)
     QueryWorkspace &ws = c->query_ws;
     const uint64_t tiles = query_tiles(c->n);
     if (ws.tiles_cap < tiles) {
-        dev_free(ws.tile_count);
-        dev_free(ws.tile_key);
+        dev_free(c, ws.tile_count);
+        dev_free(c, ws.tile_key);
         ws.tiles_cap = 0;
-        GPE_TRY(dev_alloc(c, &ws.tile_count, tiles));
-        GPE_TRY(dev_alloc(c, &ws.tile_key, tiles));
+        GPE_TRY(dev_alloc(c, &ws.tile_count, tiles, "query.tile_count"));
+        GPE_TRY(dev_alloc(c, &ws.tile_key, tiles, "query.tile_key"));
         ws.tiles_cap = tiles;
     }
-    if (!ws.pick) GPE_TRY(dev_alloc(c, &ws.pick, 1));
+    if (!ws.pick) GPE_TRY(dev_alloc(c, &ws.pick, 1, "query.pick"));
     if (ws.stage_cap < stage_bytes) {
-        dev_free(ws.stage);
+        dev_free(c, ws.stage);
         ws.stage_cap = 0;
-        GPE_TRY(dev_alloc(c, &ws.stage, stage_bytes));
+        GPE_TRY(dev_alloc(c, &ws.stage, stage_bytes, "query.stage"));
         ws.stage_cap = stage_bytes;
     }
     return scan_reserve(c, tiles);
@@ -1444,13 +1610,55 @@ gpe_status gpe_download(gpe_ctx *c, gpe_array what, void *dst, uint64_t bytes)
     return check_device_errors(c);
 }
 
+// ---- guarded allocations ---------------------------------------------------------------------------------------
+gpe_status gpe_guard_check(gpe_ctx *c, gpe_guard_report *out)
+{
+    if (!c || !out || out->struct_size != sizeof(gpe_guard_report)) return GPE_ERR_INVALID_ARG;
+    memset(out, 0, sizeof(*out));
+    out->struct_size = (uint32_t)sizeof(*out);
+    GuardState &G = c->guard;
+    if (!G.on) return GPE_OK;
+    GPE_HIP(c, hipSetDevice(c->device));
+    std::vector<gpe_guard_zone> found = G.kept;
+    uint32_t damaged = G.kept_count;
+    GPE_HIP(c, guard_scan(c, G.live.data(), G.live.size(), found, &damaged));
+    if (G.scan_failed != hipSuccess)
+        return fail(c, GPE_ERR_HIP, std::string("gpe_guard_check: the zones of a released buffer could not be checked: ") +
+                                        hipGetErrorName(G.scan_failed));
+    out->damaged = damaged;
+    out->listed = (uint32_t)found.size();
+    out->allocations = (uint32_t)G.live.size();
+    for (size_t i = 0; i < found.size(); ++i) out->zones[i] = found[i];
+    if (damaged) return fail(c, GPE_OK, guard_zone_text(found[0]));    // a finding, not an error: the text all the same
+    return GPE_OK;
+}
+
+gpe_status gpe_guard_registry(gpe_ctx *c, char *text, uint64_t capacity, uint64_t *needed)
+{
+    if (!c || (!text && capacity)) return GPE_ERR_INVALID_ARG;
+    std::string all;
+    for (const std::vector<DevAlloc> *list : {&c->guard.live, &c->guard.released})
+        for (const DevAlloc &a : *list)
+            all += std::string(a.tag) + " " + std::to_string(a.payload) + " " + std::to_string(a.slack) +
+                   (list == &c->guard.live ? " live\n" : " released\n");
+    if (needed) *needed = all.size() + 1;
+    if (capacity) {
+        const size_t k = std::min<size_t>(all.size(), capacity - 1);
+        memcpy(text, all.data(), k);
+        text[k] = 0;
+    }
+    return GPE_OK;
+}
+
 // ---- primitives ---------------------------------------------------------------------------------------------
 gpe_status gpe_buffer_alloc(gpe_ctx *c, uint64_t bytes, void **device_ptr)
 {
     if (!c || !device_ptr) return GPE_ERR_INVALID_ARG;
     GPE_HIP(c, hipSetDevice(c->device));
     *device_ptr = nullptr;
-    hipError_t e = hipMalloc(device_ptr, std::max<uint64_t>(bytes, 16) + 64);
+    // payload: the bytes asked for.  slack: the round-up to 16 bytes and 64 more, which the primitives may read past a
+    // caller's n elements (the 4-keys-per-lane loads of the sort and scan tiles) but never write
+    hipError_t e = gpe_dev_reserve(c, device_ptr, bytes, std::max<uint64_t>(bytes, 16) + 64 - bytes, "user.buffer");
     if (e == hipErrorOutOfMemory) return fail(c, GPE_ERR_OOM, "gpe_buffer_alloc: out of device memory");
     if (e != hipSuccess) return fail(c, GPE_ERR_HIP, std::string("gpe_buffer_alloc: ") + hipGetErrorName(e));
     return GPE_OK;
@@ -1461,7 +1669,7 @@ gpe_status gpe_buffer_free(gpe_ctx *c, void *device_ptr)
     if (!c) return GPE_ERR_INVALID_ARG;
     if (!device_ptr) return GPE_OK;
     GPE_HIP(c, hipStreamSynchronize(c->stream));
-    GPE_HIP(c, hipFree(device_ptr));
+    GPE_HIP(c, gpe_dev_release(c, &device_ptr));
     return GPE_OK;
 }
 

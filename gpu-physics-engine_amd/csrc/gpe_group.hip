@@ -82,22 +82,24 @@ gpe_status group_all_reduce_u32(gpe_ctx *c, uint32_t *d_buf, uint64_t count, uin
     // every rank reduces all ranks' buffers into a scratch of its own, then -- when nobody reads the originals any
     // more -- copies the result over its buffer
     uint32_t *tmp = nullptr;
-    hipError_t e = hipMalloc((void **)&tmp, std::max<uint64_t>(count, 16) * sizeof(uint32_t));
-    if (e != hipSuccess) { (void)hipGetLastError(); (void)gpe_local_group_abort(g); return fail(c, GPE_ERR_OOM, "local group: hipMalloc (all-reduce scratch)"); }
+    // payload: the count reduced words.  slack: the round-up to 16 words, read by nobody (the size it always had)
+    hipError_t e = dev_reserve(c, &tmp, count * sizeof(uint32_t), (std::max<uint64_t>(count, 16) - count) * sizeof(uint32_t),
+                               "group.reduce_scratch");
+    if (e != hipSuccess) { (void)gpe_local_group_abort(g); return fail(c, GPE_ERR_OOM, "local group: hipMalloc (all-reduce scratch)"); }
     (void)hipStreamSynchronize(c->stream);                             // my contribution is complete
     g->post[me].buf = d_buf;
-    if (!rendezvous(g)) { (void)hipFree(tmp); return group_fail(c, "all_reduce"); }
+    if (!rendezvous(g)) { (void)dev_release(c, tmp); return group_fail(c, "all_reduce"); }
     ReduceSources S;
     S.n = g->ws;
     for (uint32_t r = 0; r < g->ws; ++r) S.src[r] = g->post[r].buf;
     hipLaunchKernelGGL(k_group_reduce, dim3(stream_grid(count)), dim3(kStreamBlock), 0, c->stream, S, tmp, count, op);
     e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) { (void)gpe_local_group_abort(g); (void)hipFree(tmp); return fail(c, GPE_ERR_HIP, std::string("local group: all-reduce: ") + hipGetErrorName(e)); }
-    if (!rendezvous(g)) { (void)hipFree(tmp); return group_fail(c, "all_reduce"); }
+    if (e != hipSuccess) { (void)gpe_local_group_abort(g); (void)dev_release(c, tmp); return fail(c, GPE_ERR_HIP, std::string("local group: all-reduce: ") + hipGetErrorName(e)); }
+    if (!rendezvous(g)) { (void)dev_release(c, tmp); return group_fail(c, "all_reduce"); }
     e = hipMemcpyAsync(d_buf, tmp, count * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipFree(tmp);
+    (void)dev_release(c, tmp);
     if (e != hipSuccess) { (void)gpe_local_group_abort(g); return fail(c, GPE_ERR_HIP, std::string("local group: all-reduce: ") + hipGetErrorName(e)); }
     return GPE_OK;
 }

@@ -375,6 +375,9 @@ struct NativeState {
     uint32_t stat_calls = 0;
     uint32_t *host_stat = nullptr;   // pinned, 16 words (k_native.hip kStat*): window maximum, arena use, probe answer, overflow tiles
     uint32_t window_max = 0;         // the same, measured synchronously at configuration time
+    unsigned long long *dbg_stamps = nullptr;    // diagnostic builds (-DGPE_TILE_STAMPS / -DGPE_TILE_CYCLES): their device buffers
+    uint4 *dbg_cycles = nullptr;
+    uint64_t dbg_cycles_cap = 0;
 };
 
 // Device-resident halo exchange of a sharded run (k_shard.hip): particle counts live on the device, the host
@@ -558,6 +561,25 @@ struct ShardCtl {
 };
 constexpr uint64_t kCtlSmallWords = 4096;
 
+// Device memory (gpe_api.hip, "device memory"): every allocation of a context is in its registry.
+struct DevAlloc {
+    void *ptr = nullptr;             // what the owner holds: the payload's first byte
+    void *base = nullptr;            // what the runtime returned (== ptr unless guarded)
+    uint64_t payload = 0, slack = 0; // bytes kernels may write / bytes behind them that may only be read
+    uint64_t total = 0;              // bytes allocated at base
+    const char *tag = "";            // a string literal
+};
+constexpr uint64_t kGuardZone = 16384;   // bytes of a red zone at least: kHashBlock = 1024 lanes x a 16-byte store
+struct GuardState {
+    bool on = false;                 // GPE_FLAG_GUARD_ALLOCS
+    uint32_t canary = 0, poison = 0; // gpe_config.guard_canary / guard_poison
+    std::vector<DevAlloc> live;
+    std::vector<DevAlloc> released;  // guarded: one entry per tag that has been released, the last such allocation (ptr = base = NULL)
+    hipError_t scan_failed = hipSuccess;   // a check at release could not run: that buffer's evidence is lost (sticky)
+    std::vector<gpe_guard_zone> kept;   // damage found when a buffer was released (the first GPE_GUARD_MAX_ZONES)
+    uint32_t kept_count = 0;
+};
+
 }  // namespace gpe
 
 struct gpe_ctx {
@@ -603,6 +625,7 @@ struct gpe_ctx {
     gpe::NativeState native;
     gpe::ShardState shard;
     gpe::ShardCtl ctl;
+    gpe::GuardState guard;
     bool use_onesweep = true;        // GPE_SORT=safe selects the reduce-then-scan sort
 
     // profiling
@@ -635,6 +658,25 @@ gpe_status fail(gpe_ctx *ctx, gpe_status code, const std::string &msg);
         gpe_status _s = (expr);                                                                 \
         if (_s != GPE_OK) return _s;                                                            \
     } while (0)
+
+// device memory -----------------------------------------------------------------------------
+// The one allocator of device memory (gpe_api.hip).  payload_bytes: what kernels may write; slack_bytes: room behind it
+// that may only be read (stated at the call site with its reader).  Unguarded the allocation is payload + slack bytes;
+// guarded (GPE_FLAG_GUARD_ALLOCS) it is front zone | payload | rear zone, the slack inside the rear zone.  *ptr must not
+// hold a live allocation (it is overwritten; NULL after a failure).  A failure leaves no sticky HIP error behind.
+hipError_t gpe_dev_reserve(gpe_ctx *c, void **ptr, uint64_t payload_bytes, uint64_t slack_bytes, const char *tag);
+// Frees *ptr (NULL: nothing) and forgets it.  Guarded: synchronises the context's streams and checks the zones first.
+hipError_t gpe_dev_release(gpe_ctx *c, void **ptr);
+template <class T>
+inline hipError_t dev_reserve(gpe_ctx *c, T **p, uint64_t payload_bytes, uint64_t slack_bytes, const char *tag)
+{
+    return gpe_dev_reserve(c, (void **)p, payload_bytes, slack_bytes, tag);
+}
+template <class T>
+inline hipError_t dev_release(gpe_ctx *c, T *&p)
+{
+    return gpe_dev_release(c, (void **)&p);
+}
 
 // profiling scope: a hipEvent pair on ctx->stream when ctx->profiling, else nothing.
 class Scope {

@@ -176,7 +176,7 @@ static gpe_status host_all_reduce(gpe_ctx *c, uint32_t *vals, uint64_t count, ui
     if (world_size <= 1) return GPE_OK;
     if (count > kCtlSmallWords) return fail(c, GPE_ERR_INVALID_ARG, "sharded run: small all-reduce too long");
     ShardCtl &T = c->ctl;
-    if (!T.d_small) GPE_HIP(c, hipMalloc((void **)&T.d_small, kCtlSmallWords * sizeof(uint32_t)));
+    if (!T.d_small) GPE_HIP(c, dev_reserve(c, &T.d_small, kCtlSmallWords * sizeof(uint32_t), 0, "ctl.small"));
     GPE_HIP(c, hipMemcpyAsync(T.d_small, vals, count * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
     GPE_TRY(coll_all_reduce_u32(c, T.d_small, count, op));
     GPE_HIP(c, hipMemcpyAsync(vals, T.d_small, count * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
@@ -336,20 +336,22 @@ void ctl_release(gpe_ctx *c)
 {
     ShardCtl &T = c->ctl;
     void *bufs[] = {T.d_owner, T.d_mask, T.d_send, T.d_recv, T.d_small, T.d_hist, T.d_first, T.d_rows_send, T.d_rows_recv};
-    for (void *b : bufs) if (b) (void)hipFree(b);
+    for (void *b : bufs) (void)gpe_dev_release(c, &b);
     T = ShardCtl();
 }
 
 template <typename T>
-static gpe_status ensure_words(gpe_ctx *c, T **buf, uint64_t *cap, uint64_t want, uint64_t unit = 1)
+static gpe_status ensure_words(gpe_ctx *c, T **buf, uint64_t *cap, uint64_t want, const char *tag)
 {
     if (*cap >= want && *buf) return GPE_OK;
     GPE_HIP(c, hipStreamSynchronize(c->stream));
-    if (*buf) GPE_HIP(c, hipFree(*buf));
-    *buf = nullptr; *cap = 0;
-    hipError_t e = hipMalloc((void **)buf, std::max<uint64_t>(want, 16) * unit * sizeof(T) + 64);
+    GPE_HIP(c, dev_release(c, *buf));
+    *cap = 0;
+    // payload: `want` elements.  slack: the round-up to 16 elements and 64 bytes, read by nobody known (the size these
+    // buffers always had)
+    const uint64_t payload = want * sizeof(T);
+    hipError_t e = dev_reserve(c, buf, payload, std::max<uint64_t>(want, 16) * sizeof(T) + 64 - payload, tag);
     if (e != hipSuccess) {
-        (void)hipGetLastError();
         return fail(c, e == hipErrorOutOfMemory ? GPE_ERR_OOM : GPE_ERR_HIP, std::string("sharded run: hipMalloc: ") + hipGetErrorName(e));
     }
     *cap = want;
@@ -433,14 +435,14 @@ static gpe_status plan_exchange(gpe_ctx *c, bool new_layout)
             plan.slot_rank[s] = rank; plan.send_off[s] = (uint32_t)so; plan.send_cap_mig[s] = 0; plan.send_cap_gho[s] = (uint32_t)self_gho;
             plan.recv_off[s] = (uint32_t)ro; plan.recv_cap_mig[s] = 0; plan.recv_cap_gho[s] = 0;
             T.n_neighbours = (uint32_t)nb.size();
-            st = ensure_words(c, &T.d_send, &T.send_cap, so + segment_words(0, (uint32_t)self_gho) + 16);
-            if (st == GPE_OK) st = ensure_words(c, &T.d_recv, &T.recv_cap, ro + 16);
-            if (st == GPE_OK) st = ensure_words(c, &T.d_owner, &T.tables_cap, blocks);
+            st = ensure_words(c, &T.d_send, &T.send_cap, so + segment_words(0, (uint32_t)self_gho) + 16, "ctl.send");
+            if (st == GPE_OK) st = ensure_words(c, &T.d_recv, &T.recv_cap, ro + 16, "ctl.recv");
+            if (st == GPE_OK) st = ensure_words(c, &T.d_owner, &T.tables_cap, blocks, "ctl.owner");
             if (st == GPE_OK && (!T.d_mask || new_layout)) {
-                if (T.d_mask) (void)hipFree(T.d_mask);
-                T.d_mask = nullptr;
-                if (hipMalloc((void **)&T.d_mask, std::max<uint64_t>(blocks, 16) * sizeof(uint32_t) + 64) != hipSuccess) {
-                    (void)hipGetLastError();
+                (void)dev_release(c, T.d_mask);
+                // payload: a mask per block.  slack: the round-up to 16 masks and 64 bytes, read by nobody known
+                if (dev_reserve(c, &T.d_mask, blocks * sizeof(uint32_t),
+                                (std::max<uint64_t>(blocks, 16) - blocks) * sizeof(uint32_t) + 64, "ctl.mask") != hipSuccess) {
                     st = fail(c, GPE_ERR_OOM, "sharded run: hipMalloc (destination masks)");
                 }
             }
@@ -520,8 +522,8 @@ static gpe_status resort_local(gpe_ctx *c)
     const uint64_t entries = morton_entries(T.layout);
     if (T.hist_cap < entries) {
         uint64_t cap1 = T.hist_cap, cap2 = T.hist_cap;
-        GPE_TRY(ensure_words(c, &T.d_hist, &cap1, entries + 1));
-        GPE_TRY(ensure_words(c, &T.d_first, &cap2, entries + 1));
+        GPE_TRY(ensure_words(c, &T.d_hist, &cap1, entries + 1, "ctl.hist"));
+        GPE_TRY(ensure_words(c, &T.d_first, &cap2, entries + 1, "ctl.first"));
         T.hist_cap = entries;
     }
     GPE_HIP(c, hipMemsetAsync(T.d_hist, 0, entries * sizeof(uint32_t), c->stream));
@@ -556,7 +558,7 @@ static gpe_status recut_home(gpe_ctx *c, float above, int32_t *recut)
     const int bins = L.blocks_x + L.blocks_y;
     if (bins > kCutBins) return GPE_OK;
     uint64_t cap = T.rows_send_cap;
-    GPE_TRY(ensure_words(c, &T.d_rows_send, &cap, std::max<uint64_t>((uint64_t)bins, n * 6)));
+    GPE_TRY(ensure_words(c, &T.d_rows_send, &cap, std::max<uint64_t>((uint64_t)bins, n * 6), "ctl.rows_send"));
     T.rows_send_cap = cap;
     GPE_HIP(c, hipMemsetAsync(T.d_rows_send, 0, (size_t)bins * sizeof(uint32_t), c->stream));
     hipLaunchKernelGGL(k_ctl_axis_hist, dim3(std::min(256, stream_grid(n, 1024))), dim3(1024), 0, c->stream, c->pos, n,
@@ -579,9 +581,9 @@ static gpe_status recut_home(gpe_ctx *c, float above, int32_t *recut)
     std::vector<uint32_t> mask;
     build_tables(NL, owner, mask);
     const uint64_t blocks = (uint64_t)NL.blocks_x * NL.blocks_y;
-    GPE_TRY(ensure_words(c, &T.d_owner, &T.tables_cap, blocks));
+    GPE_TRY(ensure_words(c, &T.d_owner, &T.tables_cap, blocks, "ctl.owner"));
     GPE_HIP(c, hipMemcpyAsync(T.d_owner, owner.data(), blocks, hipMemcpyHostToDevice, c->stream));
-    if (!T.d_small) GPE_HIP(c, hipMalloc((void **)&T.d_small, kCtlSmallWords * sizeof(uint32_t)));
+    if (!T.d_small) GPE_HIP(c, dev_reserve(c, &T.d_small, kCtlSmallWords * sizeof(uint32_t), 0, "ctl.small"));
     GPE_HIP(c, hipMemsetAsync(T.d_small, 0, 32 * sizeof(uint32_t), c->stream));
     hipLaunchKernelGGL(k_ctl_dest, dim3(stream_grid(n)), dim3(kStreamBlock), 0, c->stream, c->pos, n, c->cell_size, T.d_owner,
                        NL.blocks_x, NL.blocks_y, c->home_cell_ids, c->particle_ids, T.d_small);
@@ -605,7 +607,7 @@ static gpe_status recut_home(gpe_ctx *c, float above, int32_t *recut)
     gpe_status st = GPE_OK;
     if (n_new == 0) st = fail(c, GPE_ERR_UNSUPPORTED, "sharded run: this rank owns no particle after the re-cut");
     cap = T.rows_recv_cap;
-    if (st == GPE_OK) st = ensure_words(c, &T.d_rows_recv, &cap, n_new * 6);
+    if (st == GPE_OK) st = ensure_words(c, &T.d_rows_recv, &cap, n_new * 6, "ctl.rows_recv");
     T.rows_recv_cap = cap;
     if (st == GPE_OK && n_new + 2 > c->cap) {
         const uint64_t need = (uint64_t)((double)n_new * 1.3) + 4096;

@@ -3041,19 +3041,17 @@ __global__ __launch_bounds__(kNatThreads, GPE_OVF_WAVES) void k_collide_overflow
 // (whose contents are not kept).  After a failed reserve the pointer is NULL and the error is the caller's: GPE_HIP for a
 // buffer the path needs.  An optional buffer is released through GPE_HIP first (a failing hipFree stays an error) and
 // then reserved: only the failed allocation means "run without".
+// payload / slack: bytes the kernels may write / bytes behind them that are only read (gpe_dev_reserve).
 template <class T>
-static hipError_t release(T *&p)
+static hipError_t release(gpe_ctx *c, T *&p)
 {
-    const hipError_t e = p ? hipFree(p) : hipSuccess;
-    p = nullptr;
-    return e;
+    return dev_release(c, p);
 }
 template <class T>
-static hipError_t reserve(T *&p, size_t bytes)
+static hipError_t reserve(gpe_ctx *c, T *&p, size_t payload, size_t slack, const char *tag)
 {
-    hipError_t e = release(p);
-    if (e == hipSuccess) e = hipMalloc((void **)&p, bytes);
-    if (e != hipSuccess) { (void)hipGetLastError(); p = nullptr; }
+    hipError_t e = release(c, p);
+    if (e == hipSuccess) e = dev_reserve(c, &p, payload, slack, tag);
     return e;
 }
 
@@ -3063,7 +3061,9 @@ void native_release(gpe_ctx *c)
     void *bufs[] = {N.block_table, N.keys, N.ids, N.keys_b, N.ids_b, N.codes, N.sorted_key, N.gkeys, N.gids, N.gkeys_b,
                     N.gids_b, N.gtable, N.ghist, N.exc_count, N.gho_count, N.roster_hdr, N.roster_ids, N.tile_ctl,
                     N.overflow1, N.arena};
-    for (void *b : bufs) (void)release(b);
+    for (void *b : bufs) (void)release(c, b);
+    (void)release(c, N.dbg_stamps);
+    (void)release(c, N.dbg_cycles);
     if (N.host_stat) (void)hipHostFree(N.host_stat);
     N = NativeState();
 }
@@ -3103,9 +3103,9 @@ static void native_print_stats(gpe_ctx *c, const NativeStats &s)
 // calls.  Returns the stamps of this call's launches.
 static unsigned long long *native_tile_stamps(gpe_ctx *c)
 {
-    static unsigned long long *g_stamps = nullptr;
+    unsigned long long *&g_stamps = c->native.dbg_stamps;
     // ([0, 64): the dense launch's tiles; [64, 128): the windows of the over-capacity launch)
-    if (!g_stamps) { (void)hipMalloc((void **)&g_stamps, 128 * 8); (void)hipMemset(g_stamps, 0, 128 * 8); }
+    if (!g_stamps && reserve(c, g_stamps, 128 * 8, 0, "native.dbg_stamps") == hipSuccess) (void)hipMemset(g_stamps, 0, 128 * 8);
     static int g_calls = 0;
     if (++g_calls % 20 == 0) for (int part = 0; part < 2; ++part) {
         unsigned long long h[64];
@@ -3326,30 +3326,39 @@ gpe_status native_configure(gpe_ctx *c)
     if (N.passes < 1) N.passes = 1;
     N.reason = GPE_REASON_TABLE_TOO_LARGE;
     if (N.table_entries > (1u << 27)) return GPE_OK;                   // > 1 GiB of table: stay on compat
-    const size_t table_bytes = ((size_t)N.table_entries + 2) * sizeof(uint2);
-    const size_t particle_words_bytes = (c->cap + 16) * sizeof(uint32_t);   // one word per particle
+    // The block table.  payload: the whole 16-byte pairs that cover its entries (the reset writes pairs: `pairs` in
+    // native_prepare_step).  slack: what is left of the two spare entries -- read by nobody known, the size it always had.
+    const size_t table_payload = (((size_t)N.table_entries + 1) / 2) * sizeof(uint4);
+    const size_t table_slack = ((size_t)N.table_entries + 2) * sizeof(uint2) - table_payload;
+    // One word per particle.  payload: cap words.  slack: 16 words the radix passes' tile loads may read behind them.
+    const size_t particle_words_bytes = c->cap * sizeof(uint32_t), particle_words_slack = 16 * sizeof(uint32_t);
     if (N.table_cap < N.table_entries) {
         N.table_cap = 0;
-        GPE_HIP(c, reserve(N.block_table, table_bytes));
+        GPE_HIP(c, reserve(c, N.block_table, table_payload, table_slack, "native.block_table"));
         N.table_cap = N.table_entries;
     }
     if (N.cap < c->cap) {
         N.cap = 0;
         N.gcap = 0;                                                    // (the ghost buffers follow below)
-        for (uint32_t **b : {&N.keys, &N.ids, &N.keys_b, &N.ids_b, &N.codes, &N.sorted_key})
-            GPE_HIP(c, reserve(*b, particle_words_bytes));
+        const std::pair<uint32_t **, const char *> words[] = {
+            {&N.keys, "native.keys"}, {&N.ids, "native.ids"}, {&N.keys_b, "native.keys_b"}, {&N.ids_b, "native.ids_b"},
+            {&N.codes, "native.codes"}, {&N.sorted_key, "native.sorted_key"}};
+        for (const auto &b : words)
+            GPE_HIP(c, reserve(c, *b.first, particle_words_bytes, particle_words_slack, b.second));
         N.cap = c->cap;
     }
     if (c->shard.on && (N.gcap < c->cap || N.gtable_cap < N.table_entries)) {
         // sharded runs: the ghosts' sort buffers and block table
         N.gcap = 0; N.gtable_cap = 0;
-        for (uint32_t **b : {&N.gkeys, &N.gids, &N.gkeys_b, &N.gids_b})
-            GPE_HIP(c, reserve(*b, particle_words_bytes));
+        const std::pair<uint32_t **, const char *> words[] = {
+            {&N.gkeys, "native.gkeys"}, {&N.gids, "native.gids"}, {&N.gkeys_b, "native.gkeys_b"}, {&N.gids_b, "native.gids_b"}};
+        for (const auto &b : words)
+            GPE_HIP(c, reserve(c, *b.first, particle_words_bytes, particle_words_slack, b.second));
         N.gcap = c->cap;
-        GPE_HIP(c, reserve(N.gtable, table_bytes));
+        GPE_HIP(c, reserve(c, N.gtable, table_payload, table_slack, "native.gtable"));
         N.gtable_cap = N.table_entries;
         if (!N.ghist) {
-            GPE_HIP(c, reserve(N.ghist, 2 * (size_t)kHistCopies * 4 * 256 * sizeof(uint32_t)));
+            GPE_HIP(c, reserve(c, N.ghist, 2 * (size_t)kHistCopies * 4 * 256 * sizeof(uint32_t), 0, "native.ghist"));
             GPE_HIP(c, hipMemsetAsync(N.ghist, 0, 2 * (size_t)kHistCopies * 4 * 256 * sizeof(uint32_t), c->stream));
         }
     }
@@ -3369,11 +3378,14 @@ gpe_status native_configure(gpe_ctx *c)
         N.exc_tiles = (uint64_t)N.tb.nx * (uint64_t)N.tb.ny;
         if (N.exc_cap < N.exc_tiles) {
             N.exc_entry = nullptr; N.exc_cap = 0;
-            GPE_HIP(c, release(N.exc_count));
+            GPE_HIP(c, release(c, N.exc_count));
             // (264 B per tile and set: a sparse scene in a huge world -- up to 8 M tiles -- may not get them; the run
             // then sorts every step, native_prepare_step, instead of failing to configure)
             const size_t bytes = 2 * N.exc_tiles * sizeof(uint32_t) + 16 + 2 * N.exc_tiles * kExcSlots * sizeof(uint2);
-            if (reserve(N.exc_count, bytes) == hipSuccess) N.exc_cap = N.exc_tiles;
+            // payload: the counts of both sets, rounded up to the entries' 8-byte alignment, and the entries.  slack: what
+            // the 16 bytes of alignment allowance leave over (8 or 12 bytes), read by nobody
+            const size_t payload = ((2 * N.exc_tiles + 1) & ~1ull) * sizeof(uint32_t) + 2 * N.exc_tiles * kExcSlots * sizeof(uint2);
+            if (reserve(c, N.exc_count, payload, bytes - payload, "native.exc") == hipSuccess) N.exc_cap = N.exc_tiles;
         }
         if (N.exc_count) {
             // (entries behind the counts of both sets, 8-byte aligned)
@@ -3387,15 +3399,16 @@ gpe_status native_configure(gpe_ctx *c)
     const bool rosters_pay = N.exc_tiles * (uint64_t)kRosterCap <= 16ull * std::max<uint64_t>(c->n, 1u << 16);
     if (!rosters_pay && N.roster_hdr) {
         N.roster_cap = 0;
-        GPE_HIP(c, release(N.roster_hdr));
-        GPE_HIP(c, release(N.roster_ids));
+        GPE_HIP(c, release(c, N.roster_hdr));
+        GPE_HIP(c, release(c, N.roster_ids));
     }
     if (c->shard.on && c->has_active_box && N.gho_cap < N.exc_tiles) {
         // ghost lists (sharded runs): a count and kGhostSlots ids per tile, two sets.  Optional: without them the ghosts
         // are sorted into their block table every step
         N.gho_cap = 0;
-        GPE_HIP(c, release(N.gho_count));
-        if (reserve(N.gho_count, 2 * N.exc_tiles * (1 + (size_t)kGhostSlots) * sizeof(uint32_t) + 64) == hipSuccess)
+        GPE_HIP(c, release(c, N.gho_count));
+        // payload: counts and ids of both sets.  slack: 64 bytes read by nobody known (the size it always had)
+        if (reserve(c, N.gho_count, 2 * N.exc_tiles * (1 + (size_t)kGhostSlots) * sizeof(uint32_t), 64, "native.gho") == hipSuccess)
             N.gho_cap = N.exc_tiles;
     }
     if (N.gho_count) GPE_HIP(c, hipMemsetAsync(N.gho_count, 0, 2 * N.exc_tiles * sizeof(uint32_t), c->stream));
@@ -3405,19 +3418,20 @@ gpe_status native_configure(gpe_ctx *c)
         // them runs without (every step then looks its blocks up)
         if (N.roster_cap < N.exc_tiles) {
             N.roster_cap = 0;
-            GPE_HIP(c, release(N.roster_hdr));
-            GPE_HIP(c, release(N.roster_ids));
-            if (reserve(N.roster_hdr, N.exc_tiles * sizeof(uint4)) == hipSuccess &&
-                reserve(N.roster_ids, N.exc_tiles * (size_t)kRosterCap * sizeof(uint32_t)) == hipSuccess)
+            GPE_HIP(c, release(c, N.roster_hdr));
+            GPE_HIP(c, release(c, N.roster_ids));
+            if (reserve(c, N.roster_hdr, N.exc_tiles * sizeof(uint4), 0, "native.roster_hdr") == hipSuccess &&
+                reserve(c, N.roster_ids, N.exc_tiles * (size_t)kRosterCap * sizeof(uint32_t), 0, "native.roster_ids") == hipSuccess)
                 N.roster_cap = N.exc_tiles;
-            else { (void)release(N.roster_hdr); (void)release(N.roster_ids); }
+            else { (void)release(c, N.roster_hdr); (void)release(c, N.roster_ids); }
         }
         // (stamp 0 is never current: the tiles compare with sorts + 1)
         if (N.roster_hdr) GPE_HIP(c, hipMemsetAsync(N.roster_hdr, 0, N.exc_tiles * sizeof(uint4), c->stream));
     }
     if (N.overflow_cap < tiles) {
         N.overflow_cap = 0;
-        GPE_HIP(c, reserve(N.overflow1, (3 * tiles + 32 + 2 * kHintMax) * sizeof(uint32_t)));   // (the tiles, then their halves: CollideArgs::overflow2, then the hints)
+        // payload: all of it -- the lists are laid out over the whole allocation; no slack
+        GPE_HIP(c, reserve(c, N.overflow1, (3 * tiles + 32 + 2 * kHintMax) * sizeof(uint32_t), 0, "native.overflow"));   // (the tiles, then their halves: CollideArgs::overflow2, then the hints)
         N.overflow_cap = tiles;
     }
     {
@@ -3427,7 +3441,7 @@ gpe_status native_configure(gpe_ctx *c)
         GPE_TRY(arena_reserve(c, std::max<uint64_t>(want, N.arena_cap)));
     }
     if (!N.tile_ctl) {
-        GPE_HIP(c, reserve(N.tile_ctl, kCtlWords * sizeof(uint32_t)));
+        GPE_HIP(c, reserve(c, N.tile_ctl, kCtlWords * sizeof(uint32_t), 0, "native.tile_ctl"));
         GPE_HIP(c, hipMemsetAsync(N.tile_ctl, 0, kCtlWords * sizeof(uint32_t), c->stream));
     }
     if (!N.host_stat) GPE_HIP(c, hipHostMalloc((void **)&N.host_stat, 64, hipHostMallocDefault));
@@ -3477,11 +3491,12 @@ static gpe_status arena_reserve(gpe_ctx *c, uint64_t want)
     // the new arena first: on failure the old one stays in place (a run that must stay on the native kernels keeps
     // working with it) and the error is the caller's to report
     void *fresh = nullptr;
-    const hipError_t e = reserve(fresh, want * kArenaBytesPerSlot + 256);
+    // payload: the slots.  slack: 256 bytes the 16-byte loads of the last slots' arrays may read behind them
+    const hipError_t e = reserve(c, fresh, want * kArenaBytesPerSlot, 256, "native.arena");
     if (e == hipErrorOutOfMemory) return fail(c, GPE_ERR_OOM, "native collide: out of device memory for the spill arena");
     if (e != hipSuccess) return fail(c, GPE_ERR_HIP, std::string("hipMalloc (spill arena): ") + hipGetErrorName(e));
     GPE_HIP(c, hipStreamSynchronize(c->stream));                       // (kernels in flight may still use the old one)
-    const hipError_t freed = release(N.arena);                         // (reported below: the new arena is in place either way)
+    const hipError_t freed = release(c, N.arena);                         // (reported below: the new arena is in place either way)
     N.arena = fresh;
     N.arena_cap = want;
     GPE_HIP(c, freed);
@@ -3828,14 +3843,14 @@ extern "C" gpe_status gpe_debug_tile_cycles(gpe_ctx *c, uint32_t *out, uint64_t 
 {
     if (!c) return GPE_ERR_INVALID_ARG;
     gpe::NativeState &N = c->native;
-    static uint4 *buf = nullptr;
-    static uint64_t cap = 0;
+    uint4 *&buf = N.dbg_cycles;
+    uint64_t &cap = N.dbg_cycles_cap;
     (void)hipStreamSynchronize(c->stream);
     const uint64_t tiles = N.exc_tiles;
     if (tiles_x) *tiles_x = (uint32_t)N.tb.nx;
     if (tiles_y) *tiles_y = (uint32_t)N.tb.ny;
     if (!out) {
-        if (cap < tiles) { if (buf) (void)hipFree(buf); if (hipMalloc((void **)&buf, tiles * sizeof(uint4)) != hipSuccess) return GPE_ERR_HIP; cap = tiles; }
+        if (cap < tiles) { cap = 0; if (gpe::dev_release(c, buf) != hipSuccess || gpe::dev_reserve(c, &buf, tiles * sizeof(uint4), 0, "native.dbg_cycles") != hipSuccess) return GPE_ERR_HIP; cap = tiles; }
         (void)hipMemset(buf, 0, tiles * sizeof(uint4));
         (void)hipMemcpyToSymbol(HIP_SYMBOL(gpe::g_tile_cycles), &buf, sizeof(buf));
         return GPE_OK;

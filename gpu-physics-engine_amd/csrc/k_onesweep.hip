@@ -422,9 +422,10 @@ gpe_status onesweep_reserve(gpe_ctx *c, uint64_t n)
     const uint64_t small_n = n < kOsSmallSort ? n : kOsSmallSort;
     const uint64_t need = std::max(os_tiles(n), os_tiles(small_n)) * 256 + 256;
     if (ws.status_cap < need) {
-        if (ws.status) GPE_HIP(c, hipFree(ws.status));
-        ws.status = nullptr; ws.status_cap = 0;
-        GPE_HIP(c, hipMalloc((void **)&ws.status, need * sizeof(uint64_t)));
+        GPE_HIP(c, dev_release(c, ws.status));
+        ws.status_cap = 0;
+        // payload: all of it, the spare 256 entries included (the memset below clears them with the rest); no slack
+        GPE_HIP(c, dev_reserve(c, &ws.status, need * sizeof(uint64_t), 0, "onesweep.status"));
         GPE_HIP(c, hipMemsetAsync(ws.status, 0, need * sizeof(uint64_t), c->stream));   // epoch 0 = never
         ws.status_cap = need;
     }
@@ -433,7 +434,7 @@ gpe_status onesweep_reserve(gpe_ctx *c, uint64_t n)
         // path uses copy 0), the digit bases, the control words
         // (two sets of copies: the native step alternates between them)
         const size_t words = 2 * (size_t)kHistCopies * 4 * 256 + 4 * 256 + 64 + 4 * 256;
-        GPE_HIP(c, hipMalloc((void **)&ws.hist4, words * sizeof(uint32_t)));
+        GPE_HIP(c, dev_reserve(c, &ws.hist4, words * sizeof(uint32_t), 0, "onesweep.hist4"));
         ws.bases4 = ws.hist4 + 2 * (size_t)kHistCopies * 4 * 256;
         ws.ctl = ws.bases4 + 4 * 256;
         ws.hist_plain = ws.ctl + 64;     // the histograms of sorts that bring none (the native step's sets stay untouched)
@@ -445,8 +446,8 @@ gpe_status onesweep_reserve(gpe_ctx *c, uint64_t n)
 void onesweep_release(gpe_ctx *c)
 {
     OnesweepWorkspace &ws = c->os_ws;
-    if (ws.status) (void)hipFree(ws.status);
-    if (ws.hist4) (void)hipFree(ws.hist4);
+    (void)dev_release(c, ws.status);
+    (void)dev_release(c, ws.hist4);
     ws = OnesweepWorkspace();
 }
 

@@ -174,21 +174,23 @@ gpe_status sort_reserve(gpe_ctx *c, uint64_t n)
 {
     SortWorkspace &ws = c->sort_ws;
     if (ws.cap < n) {
-        if (ws.keys_b) GPE_HIP(c, hipFree(ws.keys_b));
-        if (ws.vals_b) GPE_HIP(c, hipFree(ws.vals_b));
-        ws.keys_b = ws.vals_b = nullptr; ws.cap = 0;
-        GPE_HIP(c, hipMalloc((void **)&ws.keys_b, (n + 16) * sizeof(uint32_t)));
-        GPE_HIP(c, hipMalloc((void **)&ws.vals_b, (n + 16) * sizeof(uint32_t)));
+        GPE_HIP(c, dev_release(c, ws.keys_b));
+        GPE_HIP(c, dev_release(c, ws.vals_b));
+        ws.cap = 0;
+        // payload: the n pairs a pass scatters.  slack: 16 words the next pass's tile loads may read behind them
+        GPE_HIP(c, dev_reserve(c, &ws.keys_b, n * sizeof(uint32_t), 16 * sizeof(uint32_t), "sort.keys_b"));
+        GPE_HIP(c, dev_reserve(c, &ws.vals_b, n * sizeof(uint32_t), 16 * sizeof(uint32_t), "sort.vals_b"));
         ws.cap = n;
     }
     const uint64_t need = 256ull * sort_tiles(n) + 16;
     if (ws.counts_cap < need) {
-        if (ws.counts) GPE_HIP(c, hipFree(ws.counts));
-        ws.counts = nullptr; ws.counts_cap = 0;
-        GPE_HIP(c, hipMalloc((void **)&ws.counts, need * sizeof(uint32_t)));
+        GPE_HIP(c, dev_release(c, ws.counts));
+        ws.counts_cap = 0;
+        // payload: [256][tiles] counts, scanned in place.  slack: the 16 words behind them (the scan's tile loads)
+        GPE_HIP(c, dev_reserve(c, &ws.counts, (need - 16) * sizeof(uint32_t), 16 * sizeof(uint32_t), "sort.counts"));
         ws.counts_cap = need;
     }
-    if (!ws.hist4) GPE_HIP(c, hipMalloc((void **)&ws.hist4, 4 * 256 * sizeof(uint32_t)));
+    if (!ws.hist4) GPE_HIP(c, dev_reserve(c, &ws.hist4, 4 * 256 * sizeof(uint32_t), 0, "sort.hist4"));
     GPE_TRY(scan_reserve(c, need));
     GPE_TRY(onesweep_reserve(c, n));
     return GPE_OK;
@@ -197,10 +199,10 @@ gpe_status sort_reserve(gpe_ctx *c, uint64_t n)
 void sort_release(gpe_ctx *c)
 {
     SortWorkspace &ws = c->sort_ws;
-    if (ws.keys_b) (void)hipFree(ws.keys_b);
-    if (ws.vals_b) (void)hipFree(ws.vals_b);
-    if (ws.counts) (void)hipFree(ws.counts);
-    if (ws.hist4) (void)hipFree(ws.hist4);
+    (void)dev_release(c, ws.keys_b);
+    (void)dev_release(c, ws.vals_b);
+    (void)dev_release(c, ws.counts);
+    (void)dev_release(c, ws.hist4);
     ws = SortWorkspace();
 }
 

@@ -79,10 +79,11 @@ gpe_status scan_reserve(gpe_ctx *c, uint64_t n)
     for (uint64_t m = tiles_of(n); n > (uint64_t)kScanTile; ++lvl) {
         if (ws.level.size() <= lvl) { ws.level.push_back(nullptr); ws.cap.push_back(0); }
         if (ws.cap[lvl] < m) {
-            if (ws.level[lvl]) GPE_HIP(c, hipFree(ws.level[lvl]));
-            ws.level[lvl] = nullptr; ws.cap[lvl] = 0;
+            GPE_HIP(c, dev_release(c, ws.level[lvl]));
+            ws.cap[lvl] = 0;
             uint64_t want = m + m / 2 + 16;
-            GPE_HIP(c, hipMalloc((void **)&ws.level[lvl], want * sizeof(uint32_t)));
+            // payload: all `want` tile sums -- that is the capacity a later, larger scan is admitted by (ws.cap); no slack
+            GPE_HIP(c, dev_reserve(c, &ws.level[lvl], want * sizeof(uint32_t), 0, "scan.level"));
             ws.cap[lvl] = want;
         }
         n = m;
@@ -93,7 +94,7 @@ gpe_status scan_reserve(gpe_ctx *c, uint64_t n)
 
 void scan_release(gpe_ctx *c)
 {
-    for (uint32_t *p : c->scan_ws.level) if (p) (void)hipFree(p);
+    for (uint32_t *&p : c->scan_ws.level) (void)dev_release(c, p);
     c->scan_ws.level.clear();
     c->scan_ws.cap.clear();
 }

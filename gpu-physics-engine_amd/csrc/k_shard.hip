@@ -230,11 +230,11 @@ std::string shard_error_text(uint32_t flags)
 void shard_release(gpe_ctx *c)
 {
     ShardState &S = c->shard;
-    if (S.counts) (void)hipFree(S.counts);
-    if (S.holes) (void)hipFree(S.holes);
-    if (S.fill_src) (void)hipFree(S.fill_src);
-    if (S.fill_dst) (void)hipFree(S.fill_dst);
-    if (S.hole_flag) (void)hipFree(S.hole_flag);
+    (void)dev_release(c, S.counts);
+    (void)dev_release(c, S.holes);
+    (void)dev_release(c, S.fill_src);
+    (void)dev_release(c, S.fill_dst);
+    (void)dev_release(c, S.hole_flag);
     if (S.host_counts) (void)hipHostFree(S.host_counts);
     for (hipEvent_t e : S.fence) if (e) (void)hipEventDestroy(e);
     if (S.ev_packed) (void)hipEventDestroy(S.ev_packed);
@@ -264,9 +264,9 @@ static gpe_status ensure_flag_capacity(gpe_ctx *c)
 {
     ShardState &S = c->shard;
     if (S.flag_cap >= c->cap) return GPE_OK;
-    if (S.hole_flag) GPE_HIP(c, hipFree(S.hole_flag));
-    S.hole_flag = nullptr;
-    GPE_HIP(c, hipMalloc((void **)&S.hole_flag, c->cap + 64));
+    GPE_HIP(c, dev_release(c, S.hole_flag));
+    // payload: a byte per particle slot and the 64 behind them, which the memset below clears with the rest; no slack
+    GPE_HIP(c, dev_reserve(c, &S.hole_flag, c->cap + 64, 0, "shard.hole_flag"));
     GPE_HIP(c, hipMemsetAsync(S.hole_flag, 0, c->cap + 64, c->stream));
     S.flag_cap = c->cap;
     return GPE_OK;
@@ -412,7 +412,7 @@ gpe_status gpe_shard_configure(gpe_ctx *c, const gpe_shard_plan *p)
         S.slots.recv_off[s] = p->recv_off[s]; S.slots.recv_cap_mig[s] = p->recv_cap_mig[s]; S.slots.recv_cap_gho[s] = p->recv_cap_gho[s];
     }
     if (!S.counts) {
-        GPE_HIP(c, hipMalloc((void **)&S.counts, 2 * kShardSetWords * sizeof(uint32_t)));
+        GPE_HIP(c, dev_reserve(c, &S.counts, 2 * kShardSetWords * sizeof(uint32_t), 0, "shard.counts"));
         GPE_HIP(c, hipMemset(S.counts, 0, 2 * kShardSetWords * sizeof(uint32_t)));
         GPE_HIP(c, hipHostMalloc((void **)&S.host_counts, 64, hipHostMallocDefault));
         memset(S.host_counts, 0, 64);
@@ -423,9 +423,10 @@ gpe_status gpe_shard_configure(gpe_ctx *c, const gpe_shard_plan *p)
     if (S.holes_cap < want) {
         uint32_t **bufs[3] = {&S.holes, &S.fill_src, &S.fill_dst};
         for (uint32_t **b : bufs) {
-            if (*b) GPE_HIP(c, hipFree(*b));
-            *b = nullptr;
-            GPE_HIP(c, hipMalloc((void **)b, (want + 16) * sizeof(uint32_t)));
+            GPE_HIP(c, dev_release(c, *b));
+            // payload: `want` list entries.  slack: 16 words no kernel is known to read (the size the lists always had)
+            GPE_HIP(c, dev_reserve(c, b, want * sizeof(uint32_t), 16 * sizeof(uint32_t),
+                                   b == &S.holes ? "shard.holes" : b == &S.fill_src ? "shard.fill_src" : "shard.fill_dst"));
         }
         S.holes_cap = want;
     }

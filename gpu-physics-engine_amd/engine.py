@@ -37,7 +37,7 @@ class Context:
     """WgpuContext::new_for_test() stand-in (wgpu_context.rs:73-101): device + queue == HIP stream."""
 
     def __init__(self, world=(3048.0, 1048.0), gravity=(0.0, 0.0), mode=None, device=-1,
-                 profiling=False, stream=None, flags=0):
+                 profiling=False, stream=None, flags=0, guard_words=None):
         self.lib = L.load()
         cfg = L.GpeConfig()
         L.check(self.lib.gpe_config_default(C.byref(cfg)))
@@ -48,6 +48,8 @@ class Context:
             cfg.mode = mode
         cfg.profiling = int(profiling)
         cfg.flags = int(flags)          # L.FLAG_*
+        if guard_words is not None:     # (canary, poison) of L.FLAG_GUARD_ALLOCS; default: the library's
+            cfg.guard_canary, cfg.guard_poison = guard_words
         h = C.c_void_p()
         L.check(self.lib.gpe_create(C.byref(cfg), C.byref(h)))
         self.h = h
@@ -105,6 +107,28 @@ class Context:
         info.struct_size = C.sizeof(L.GpePipelineInfo)
         self.call("gpe_get_pipeline_info", C.byref(info))
         return {k: getattr(info, k) for k, _ in L.GpePipelineInfo._fields_ if k not in ("struct_size", "reserved")}
+
+    def guard_check(self):
+        """gpe_guard_check: the damaged red zones of the context's device allocations, as dicts (tag, side "front" /
+        "rear", first_offset, last_offset, first_word, payload_bytes), those of buffers released since included.  Empty
+        without L.FLAG_GUARD_ALLOCS.  Raises nothing by itself; `damaged` zones beyond L.GUARD_MAX_ZONES are only
+        counted (self.guard_damaged holds the count of the last call)."""
+        rep = L.GpeGuardReport()
+        rep.struct_size = C.sizeof(L.GpeGuardReport)
+        self.call("gpe_guard_check", C.byref(rep))
+        self.guard_damaged, self.guard_allocations = rep.damaged, rep.allocations
+        return [{"tag": z.tag.decode(), "side": "rear" if z.side == L.GUARD_REAR else "front",
+                 "first_offset": z.first_offset, "last_offset": z.last_offset, "first_word": z.first_word,
+                 "payload_bytes": z.payload_bytes} for z in rep.zones[:rep.listed]]
+
+    def guard_registry(self):
+        """gpe_guard_registry: [(tag, payload bytes, slack bytes, "live" / "released")] -- the context's live device
+        allocations, then the last released one of every tag that has seen a release."""
+        need = C.c_uint64()
+        self.call("gpe_guard_registry", None, 0, C.byref(need))
+        buf = C.create_string_buffer(need.value)
+        self.call("gpe_guard_registry", buf, need.value, None)
+        return [(t, int(p), int(s), state) for t, p, s, state in (line.split() for line in buf.value.decode().splitlines())]
 
     def device_ptr(self, what):
         """gpe_device_ptr: (address, bytes) of a particle / grid array on the device (render hand-off, state.rs:150-176)."""

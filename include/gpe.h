@@ -66,7 +66,9 @@ typedef struct gpe_config {
     uint32_t mode;                 /* GPE_MODE_*                                              */
     uint32_t profiling;            /* as gpe_set_profiling: 0 off, 1 every scope, k every k-th step */
     uint32_t flags;                /* GPE_FLAG_* (0 = the defaults); was reserved[0]          */
-    uint32_t reserved[4];
+    uint32_t guard_canary;         /* GPE_FLAG_GUARD_ALLOCS: the canary and poison words of this context, 0 = the   */
+    uint32_t guard_poison;         /* defaults 0x3C3 / 0x2A5; were reserved[0..1] (gpe_guard_check)                  */
+    uint32_t reserved[2];
 } gpe_config;
 
 /* gpe_config.flags -- switches for tests and measurements; the reference has no counterpart (state.rs:34-70 builds one
@@ -88,8 +90,10 @@ enum {
     GPE_FLAG_SHARD_OVERLAP = 256u,   /* sharded runs: the neighbour exchange on a stream of its own beside the       */
                                      /* interior tiles, the tiles along the rank's border first (off by default: on  */
                                      /* one GPU the two cross-stream waits cost more than the exchange they hide)    */
-    GPE_FLAG_FUSED_HISTOGRAMS = 512u /* NATIVE: the hash kernel counts the radix digits every step (rounds 1-3)      */
+    GPE_FLAG_FUSED_HISTOGRAMS = 512u,/* NATIVE: the hash kernel counts the radix digits every step (rounds 1-3)      */
                                      /* instead of a gated launch counting them when a sort is due; for A/B timing   */
+    GPE_FLAG_GUARD_ALLOCS = 1024u    /* tests: every device allocation of the context sits between two red zones     */
+                                     /* filled with a canary, its fresh payload is poisoned (gpe_guard_check)        */
 };
 
 /* Fills *cfg with the reference's compile-time constants. */
@@ -566,6 +570,43 @@ typedef struct gpe_trace_event {
     double duration_ms;
 } gpe_trace_event;
 gpe_status gpe_get_trace(gpe_ctx *ctx, gpe_trace_event *out, uint32_t *count);
+
+/* ---- guarded device allocations (tests; DESIGN.md "device memory: payload, slack, red zones") ---------- */
+/* With GPE_FLAG_GUARD_ALLOCS every device allocation of the context is front zone | payload | rear zone: the
+ * payload is what kernels may write, the zones (>= 16 KiB each, the read-only slack of the allocation lies at
+ * the head of the rear one) are filled with a canary word and the fresh payload with a poison word.
+ * gpe_guard_check, stream-ordered behind the context's work, compares every zone of every live allocation with
+ * the canary (one kernel), synchronises and fills *out; zones found damaged when their buffer was released or
+ * regrown are kept and reported by every later call.  Damage is a finding, not an error: the status is GPE_OK,
+ * the text of the first damaged zone goes to gpe_last_error.  Without the flag: GPE_OK, damaged = 0.  GPE_ERR_HIP when
+ * the check itself failed, now or when a buffer was released (its evidence is gone: the report would not be complete).
+ * gpe_config.guard_canary / guard_poison choose the words: each nonzero and below 1024, and different from the other --
+ * such a word is a nonzero finite f32, and used as an index of 16-byte elements it stays inside a red zone; anything
+ * else fails gpe_create with GPE_ERR_INVALID_ARG.  Without the flag the two words are ignored. */
+#define GPE_GUARD_MAX_ZONES 8
+enum { GPE_GUARD_FRONT = 0, GPE_GUARD_REAR = 1 };
+typedef struct gpe_guard_zone {
+    char     tag[32];        /* the allocation's tag, e.g. "native.codes"                                  */
+    uint32_t side;           /* GPE_GUARD_FRONT / GPE_GUARD_REAR                                           */
+    uint32_t first_word;     /* the aligned 32-bit word that holds the first damaged byte                 */
+    int64_t  first_offset;   /* first / last damaged byte: front zone relative to the payload's first     */
+    int64_t  last_offset;    /* byte (negative), rear zone relative to the first byte behind the payload  */
+    uint64_t payload_bytes;
+} gpe_guard_zone;
+typedef struct gpe_guard_report {
+    uint32_t struct_size;    /* in: sizeof(gpe_guard_report)                                               */
+    uint32_t damaged;        /* damaged zones, those kept from released buffers included                   */
+    uint32_t listed;         /* min(damaged, GPE_GUARD_MAX_ZONES): entries of zones[] filled               */
+    uint32_t allocations;    /* live allocations checked                                                   */
+    gpe_guard_zone zones[GPE_GUARD_MAX_ZONES];
+} gpe_guard_report;
+gpe_status gpe_guard_check(gpe_ctx *ctx, gpe_guard_report *out);
+/* The registry of the context's device allocations (kept with and without the flag): one line
+ * "tag payload_bytes slack_bytes live\n" per live allocation, then, with the flag, one
+ * "tag payload_bytes slack_bytes released\n" per tag of which an allocation has been released (its last one; those
+ * were checked when they went).  What the tests prove a growth with, and the coverage list of profiles/guard/ is from.
+ * NUL-terminated, truncated to capacity; *needed (may be NULL) receives the bytes the whole text takes. */
+gpe_status gpe_guard_registry(gpe_ctx *ctx, char *text, uint64_t capacity, uint64_t *needed);
 
 #ifdef __cplusplus
 }

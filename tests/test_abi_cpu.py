@@ -49,6 +49,47 @@ def test_config_defaults_are_the_reference_constants(gpe):
     assert ctypes.sizeof(gpe._lib.GpeConfig) == 64 and ctypes.sizeof(gpe._lib.GpePipelineInfo) == 64
 
 
+def test_guard_abi_flag_function_and_report(gpe):
+    """GPE_FLAG_GUARD_ALLOCS, gpe_guard_check / gpe_guard_registry, gpe_guard_report and the two words of gpe_config as
+    include/gpe.h declares them; the words of a context must be harmless when a kernel consumes one."""
+    L = gpe._lib
+    text = open(os.path.join(ROOT, "include", "gpe.h")).read()
+    assert re.search(r"GPE_FLAG_GUARD_ALLOCS\s*=\s*1024u", text) and L.FLAG_GUARD_ALLOCS == 1024
+    flags = [getattr(L, k) for k in dir(L) if k.startswith("FLAG_")]
+    assert len(flags) == len(set(flags)) and all(f & (f - 1) == 0 for f in flags)      # one bit each, none shared
+    for name in ("gpe_guard_check", "gpe_guard_registry"):
+        assert name in _declared_symbols()
+    assert int(re.search(r"#define GPE_GUARD_MAX_ZONES (\d+)", text).group(1)) == L.GUARD_MAX_ZONES == 8
+    assert ctypes.sizeof(L.GpeGuardZone) == 64 and ctypes.sizeof(L.GpeGuardReport) == 16 + 8 * 64
+    assert [n for n, _ in L.GpeGuardZone._fields_] == ["tag", "side", "first_word", "first_offset", "last_offset", "payload_bytes"]
+    assert [n for n, _ in L.GpeGuardReport._fields_] == ["struct_size", "damaged", "listed", "allocations", "zones"]
+    lib = L.load()
+    rep = L.GpeGuardReport()
+    assert lib.gpe_guard_check(None, ctypes.byref(rep)) == L.GPE_ERR_INVALID_ARG
+    assert lib.gpe_guard_registry(None, None, 0, None) == L.GPE_ERR_INVALID_ARG
+    # nonzero, a nonzero finite f32, inside a 16 KiB zone as an index of 16-byte elements, canary != poison
+    # (checked before a device is looked for; 0 selects the default of that word: 0x3C3 / 0x2A5)
+    assert [n for n, _ in L.GpeConfig._fields_][-3:] == ["guard_canary", "guard_poison", "reserved"]
+    for words, ok in (((0, 0), True), ((7, 9), True), ((7, 0), True), ((0x2A5, 0), False), ((7, 7), False), ((0x3C3, 0x3C3), False),
+                      ((0, 0x3C3), False), ((0xFFFFFFFF, 0x2A5), False), ((0x2A5, 0x7FC00000), False), ((0x2A5, 1024), False)):
+        cfg = L.GpeConfig()
+        assert lib.gpe_config_default(ctypes.byref(cfg)) == 0
+        cfg.flags, (cfg.guard_canary, cfg.guard_poison) = L.FLAG_GUARD_ALLOCS, words
+        h = ctypes.c_void_p()
+        status = lib.gpe_create(ctypes.byref(cfg), ctypes.byref(h))
+        if ok:
+            assert status in (L.GPE_OK, L.GPE_ERR_NO_DEVICE), words
+            if status == L.GPE_OK:
+                lib.gpe_destroy(h)
+        else:
+            assert status == L.GPE_ERR_INVALID_ARG, words
+            cfg.flags = 0                                  # without the flag the words are not looked at
+            status = lib.gpe_create(ctypes.byref(cfg), ctypes.byref(h))
+            assert status in (L.GPE_OK, L.GPE_ERR_NO_DEVICE), words
+            if status == L.GPE_OK:
+                lib.gpe_destroy(h)
+
+
 def test_no_gpu_means_loud_failure_not_fallback(gpe):
     import torch
     if torch.cuda.is_available():

@@ -1,0 +1,79 @@
+"""CPU checks of the device-memory contract ("device memory: payload, slack, red zones"): the runtime's
+allocator is called from one place, so that the registry and the red zones of GPE_FLAG_GUARD_ALLOCS see every buffer."""
+import glob
+import os
+import re
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "gpu-physics-engine_amd", "csrc")
+
+
+def _code(path):
+    """The file without its comments (string literals here hold no comment markers that matter to the scan)."""
+    src = open(path).read()
+    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    return re.sub(r"//[^\n]*", "", src)
+
+
+def _sources():
+    return sorted(glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(CSRC, "*.hip")))
+
+
+def test_device_allocation_has_one_home():
+    """hipMalloc( and hipFree( occur in gpe_api.hip only (gpe_dev_reserve / gpe_dev_release and the checker's own
+    scratch); every other file goes through them.  No other device allocator is used anywhere."""
+    hits = {}
+    for path in _sources():
+        code = _code(path)
+        for call in ("hipMalloc", "hipFree", "hipMallocAsync", "hipFreeAsync", "hipMallocManaged", "hipExtMallocWithFlags",
+                     "hipMallocPitch", "hipMalloc3D", "hipMallocFromPoolAsync"):
+            if re.search(r"\b%s\(" % call, code):
+                hits.setdefault(call, []).append(os.path.basename(path))
+    assert hits == {"hipMalloc": ["gpe_api.hip"], "hipFree": ["gpe_api.hip"]}, hits
+
+
+def test_pinned_host_memory_stays_where_it_was():
+    """hipHostMalloc: the two pinned mirrors (the native step's statistics, the sharded exchange's counts), nothing else."""
+    hits = sorted(os.path.basename(p) for p in _sources() if re.search(r"\bhipHostMalloc\(", _code(p)))
+    assert hits == ["k_native.hip", "k_shard.hip"], hits
+
+
+TAG = r'"(?:particles|grid|uid|remove|query|user|sort|scan|onesweep|native|shard|ctl|group)\.[a-z0-9_]+"'
+
+
+def _calls(code, name):
+    """The argument text of every call of `name(` in code (balanced parentheses), definitions and declarations aside."""
+    out = []
+    for m in re.finditer(r"(?<![\w:])%s\(" % name, code):
+        line_start = code.rfind("\n", 0, m.start()) + 1
+        head = code[line_start:m.start()]
+        if re.search(r"\b(static|inline|hipError_t|gpe_status)\s+$", head):      # a definition / declaration
+            continue
+        depth, i = 1, m.end()
+        while depth:
+            depth += {"(": 1, ")": -1}.get(code[i], 0)
+            i += 1
+        out.append(" ".join(code[m.end():i - 1].split()))
+    return out
+
+
+def test_every_allocation_site_names_a_tag():
+    """Every call of an allocating helper (gpe_dev_reserve, dev_reserve, dev_alloc, k_native.hip's reserve,
+    ensure_words) ends in a tag: a literal of the registry's naming scheme, or an expression made of such literals
+    (a choice between tags), or the tag parameter a wrapper hands on.  No tag is longer than gpe_guard_zone.tag holds."""
+    sites, tags = 0, set()
+    for path in _sources():
+        code = _code(path)
+        names = ["gpe_dev_reserve", "dev_reserve", "dev_alloc", "ensure_words"]
+        if os.path.basename(path) == "k_native.hip":
+            names.append("reserve")
+        for name in names:
+            for args in _calls(code, name):
+                last = args.rsplit(",", 1)[1].strip() if "," in args else args
+                # (a ?: choice between tags holds no comma; its literals are what counts)
+                found = re.findall(TAG, args.split(",", 3)[-1] if name != "ensure_words" else last)
+                assert found or last in ("tag", "b.second"), (os.path.basename(path), name, args)
+                sites += 1
+                tags.update(t.strip('"') for t in found)
+    assert sites >= 60, sites
+    assert all(len(t) < 32 for t in tags), sorted(tags)          # gpe_guard_zone.tag is char[32]
