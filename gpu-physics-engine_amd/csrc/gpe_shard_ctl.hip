@@ -47,10 +47,15 @@ static uint64_t morton_entries(const gpe_shard_layout &L)
 
 static bool layout_valid(const gpe_shard_layout *L)
 {
-    return L && L->struct_size == sizeof(gpe_shard_layout) && L->world_size >= 1 && L->world_size <= GPE_SHARD_MAX_RANKS &&
-           L->px >= 1 && L->py >= 1 && L->px * L->py == L->world_size && L->blocks_x >= (int32_t)L->px &&
-           L->blocks_y >= (int32_t)L->py && L->xcuts[0] == 0 && L->ycuts[0] == 0 && L->xcuts[L->px] == L->blocks_x &&
-           L->ycuts[L->py] == L->blocks_y;
+    if (!(L && L->struct_size == sizeof(gpe_shard_layout) && L->world_size >= 1 && L->world_size <= GPE_SHARD_MAX_RANKS &&
+          L->px >= 1 && L->py >= 1 && L->px * L->py == L->world_size && L->blocks_x >= (int32_t)L->px &&
+          L->blocks_y >= (int32_t)L->py && L->xcuts[0] == 0 && L->ycuts[0] == 0 && L->xcuts[L->px] == L->blocks_x &&
+          L->ycuts[L->py] == L->blocks_y))
+        return false;
+    // a layout filled in by hand: the cuts rise, as gpe_shard_layout_build makes them (the tables are indexed by them)
+    for (uint32_t i = 0; i < L->px; ++i) if (L->xcuts[i + 1] <= L->xcuts[i]) return false;
+    for (uint32_t j = 0; j < L->py; ++j) if (L->ycuts[j + 1] <= L->ycuts[j]) return false;
+    return true;
 }
 
 static void rect_blocks(const gpe_shard_layout &L, uint32_t rank, int &x0, int &y0, int &x1, int &y1)

@@ -37,17 +37,19 @@ def owner_of(layout, pos):
 class LocalShardedRun:
     """`world_size` contexts on `devices` (default: all on device 0), each owning the particles of its rectangle.
 
+    xcuts / ycuts: explicit cuts in blocks for gpe_shard_layout_build (default: equal widths); mouse: (x, y) pressed on
+    every rank, as gpe_set_mouse on the single context.
     run(dt, steps, resort_every, resort_first) is State::update x steps on every rank (gpe_shard_run_scheduled);
     owned() returns per rank (order keys, positions, previous positions): the order keys are the particles' indices in
     the single-context system after its own re-sorts, so `want_pos[keys] == pos` bit for bit."""
 
     def __init__(self, pos, rad, world, world_size, gravity=(0.0, 0.0), devices=None, prev=None, grid=None, flags=0,
-                 capacity_scale=1.0, capacity=None):
+                 capacity_scale=1.0, capacity=None, xcuts=None, ycuts=None, mouse=None):
         self.ws = int(world_size)
         pos = np.ascontiguousarray(pos, np.float32).reshape(-1, 2)
         rad = np.ascontiguousarray(rad, np.float32)
         cs = np.float32(np.abs(rad).max()) * np.float32(2.2)
-        self.layout = build_layout(world, cs, self.ws, grid=grid)
+        self.layout = build_layout(world, cs, self.ws, grid=grid, xcuts=xcuts, ycuts=ycuts)
         own = owner_of(self.layout, pos)
         self.group = C.c_void_p()
         L.check(L.load().gpe_local_group_create(self.ws, C.byref(self.group)))
@@ -60,6 +62,8 @@ class LocalShardedRun:
                 raise ValueError("rank %d owns no particle at start" % r)
             c = Context(world=world, gravity=gravity, mode=L.MODE_NATIVE, device=devices[r], flags=flags)
             self.ctx[r] = c
+            if mouse is not None:                                       # pressed at `mouse` on every rank, as on the one context
+                c.call("gpe_set_mouse", 1, float(mouse[0]), float(mouse[1]))
             p, q = np.ascontiguousarray(pos[mine]), (np.ascontiguousarray(prev[mine], np.float32) if prev is not None else None)
             c.call("gpe_shard_set_particles", _ptr(p), _ptr(q) if q is not None else None, _ptr(np.ascontiguousarray(rad[mine])),
                    _ptr(mine.astype(np.uint32)), len(mine), int(capacity or 0))

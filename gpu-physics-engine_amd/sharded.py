@@ -122,8 +122,11 @@ class Decomposition:
     def owner_of(self, pos):
         """Owner rank of host positions (numpy, same float32 arithmetic as the kernels)."""
         pos = np.asarray(pos, np.float32).reshape(-1, 2)
-        cx = np.floor(pos[:, 0] / self.cell_size).astype(np.int64) >> 3
-        cy = np.floor(pos[:, 1] / self.cell_size).astype(np.int64) >> 3
+        # (the kernels' float -> int conversion saturates at the int32 range; numpy's is undefined beyond int64, where a
+        # huge finite coordinate would land on block 0 instead of the last one.  NaN stays undefined here.)
+        with np.errstate(over="ignore"):
+            cx = np.clip(np.floor(pos[:, 0] / self.cell_size), -2147483648.0, 2147483520.0).astype(np.int64) >> 3
+            cy = np.clip(np.floor(pos[:, 1] / self.cell_size), -2147483648.0, 2147483520.0).astype(np.int64) >> 3
         cx = np.clip(cx, 0, self.bx - 1)
         cy = np.clip(cy, 0, self.by - 1)
         return self.owner[cy, cx].astype(np.int64)

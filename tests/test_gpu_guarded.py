@@ -321,7 +321,12 @@ SHARDED = _cases(
     + [("dense-patch-astride-the-cut%s" % ("-overlap" if o else ""), "test_gpu_sharded",
         "test_dense_patch_on_the_border_between_two_ranks", dict(overlap=o)) for o in (False, True)]
     + [("edge-scene-%s" % s, "test_gpu_pair_math", "test_edge_scenes_local_group_equals_single_context", dict(scene=s))
-       for s in ("isolated", "blobs_negative")])
+       for s in ("isolated", "blobs_negative")]
+    # the refusals of tests/test_gpu_sharded_fuzz.py: the rows that had no place were dropped inside their buffers
+    + [("refusal-%s" % c, "test_gpu_sharded_fuzz", "test_refusal_is_loud_on_every_rank", dict(case=c))
+       for c in ("no-slot", "holes", "capacity", "recv-overflow", "empty-after-re-cut")]
+    + [("fuzz-%d" % s, "test_gpu_sharded_fuzz", "test_sharded_fuzz_scenes_equal_single_context_and_oracle", dict(seed=s))
+       for s in (5, 8, 21)])
 
 
 @pytest.mark.parametrize("module,test,params", COMPAT)
