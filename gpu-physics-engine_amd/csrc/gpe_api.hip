@@ -732,7 +732,7 @@ static gpe_status do_step_scoped(gpe_ctx *c, float dt, uint32_t flags)
                     "box, bounded density");
     (native ? c->native.native_steps : c->native.compat_steps) += 1;
     if (native) {
-        // grid update + collision solve as N-key sort + LDS cell windows (k_native.hip); the resolved
+        // grid update + collision solve as N-key sort + LDS cell windows (gpe_native.hip, k_native.hip); the resolved
         // positions land in the scratch set, which then becomes the live one.  The integration (:130) is
         // applied as the tiles write their particles back -- same arithmetic, one pass over memory less.
         const VerletParams vp = verlet_params(c, dt);

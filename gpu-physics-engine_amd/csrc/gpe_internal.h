@@ -319,8 +319,8 @@ constexpr int kStatSubTiles = 4, kStatSpills = 5;   // quarters redone as 8x8 ti
 constexpr int kStatSorts = 6;                  // running count of steps whose radix passes ran (tile_ctl[kCtlSorts]), lagged
 constexpr int kStatOverflowNew = 7;            // ... of kStatOverflow, the tiles the dense launch handed on itself (the others were known: hinted)
 constexpr int kStatHalvesOver = 8;             // halves handed on to the over-capacity launch in the last native step
-constexpr int kNativeCtlSorts = 14;         // tile_ctl word: running count of steps whose radix passes ran (k_native.hip kCtlSorts)
-constexpr int kNativeCtlSortsSeen = 38;     // its copy in the line the tiles only read (k_native.hip kCtlSortsSeen)
+constexpr int kNativeCtlSorts = 14;         // tile_ctl word: running count of steps whose radix passes ran (native_launch.h kCtlSorts)
+constexpr int kNativeCtlSortsSeen = 38;     // its copy in the line the tiles only read (native_launch.h kCtlSortsSeen)
 // Native (N-key sort + LDS cell windows) pipeline state
 struct NativeState {
     NativePolicy policy;             // the launch heuristics and their counters (native_policy.h)
@@ -344,7 +344,7 @@ struct NativeState {
     uint32_t *exc_count = nullptr;   // straggler lists: [2][exc_tiles] counts, then [2][exc_tiles][16] entries (one allocation)
     uint2 *exc_entry = nullptr;
     uint64_t exc_tiles = 0, exc_cap = 0;
-    uint4 *roster_hdr = nullptr;           // tile rosters (k_native.hip, CollideArgs)
+    uint4 *roster_hdr = nullptr;           // tile rosters (native_launch.h, CollideArgs)
     uint32_t *roster_ids = nullptr;
     uint64_t roster_cap = 0;
     TileBox tb;                      // the tiles the straggler lists, ghost lists and rosters are kept for
@@ -358,14 +358,14 @@ struct NativeState {
     bool sort_state_valid = false;   // sorted_key / sorted ids / block table belong to the current particle set and box
     uint64_t sorted_n = 0;           // ... of this many particles
     uint32_t step_seq = 0;           // native_prepare_step calls: its parity selects the per-step control words
-    uint32_t collide_seq = 0;        // native_collide calls: numbers the dense launches for the tile hints (k_native.hip kCtlHints)
+    uint32_t collide_seq = 0;        // native_collide calls: numbers the dense launches for the tile hints (native_launch.h kCtlHints)
     const uint32_t *fresh_word = nullptr;   // tile_ctl word the tiles of the current step read (did the passes run?)
     uint32_t reason = GPE_REASON_NO_PARTICLES;   // why the native kernels do not run (GPE_REASON_*), NONE when they do
     uint64_t native_steps = 0, compat_steps = 0;
     bool always_sort = false;        // GPE_FLAG_SORT_EVERY_STEP (A/B measurements, tests): sort every step as rounds 1-2 did
     int32_t blocks_x = 0, blocks_y = 0;   // 8x8-cell blocks of the block box: table index = (by - by0) * blocks_x + (bx - bx0)
     int32_t bx0 = 0, by0 = 0;        // first block of the box (sharded runs: the rank's active box; else 0, 0)
-    uint32_t *tile_ctl = nullptr;    // device control words (k_native.hip kCtl*)
+    uint32_t *tile_ctl = nullptr;    // device control words (native_launch.h kCtl*)
     uint32_t *overflow1 = nullptr;   // packed (ty << 16 | tx) of 32x32 tiles over capacity
     uint64_t overflow_cap = 0;
     void *arena = nullptr;           // global spill arena for those tiles' particle arrays (37 B per slot)
@@ -373,7 +373,7 @@ struct NativeState {
     bool force = false;              // GPE_FLAG_NATIVE_FORCE (tests): no hand-over to the compat kernels
     bool print_stats = false;        // GPE_FLAG_NATIVE_STATS: print the step statistics every 128 steps
     uint32_t stat_calls = 0;
-    uint32_t *host_stat = nullptr;   // pinned, 16 words (k_native.hip kStat*): window maximum, arena use, probe answer, overflow tiles
+    uint32_t *host_stat = nullptr;   // pinned, 16 words (kStat* above): window maximum, arena use, probe answer, overflow tiles
     uint32_t window_max = 0;         // the same, measured synchronously at configuration time
     unsigned long long *dbg_stamps = nullptr;    // diagnostic builds (-DGPE_TILE_STAMPS / -DGPE_TILE_CYCLES): their device buffers
     uint4 *dbg_cycles = nullptr;
@@ -718,7 +718,7 @@ VerletParams verlet_params(const gpe_ctx *c, float dt);
 gpe_status onesweep_reserve(gpe_ctx *c, uint64_t n);
 void onesweep_release(gpe_ctx *c);
 gpe_status onesweep_zero_hist(gpe_ctx *c);
-// A sort that the device may skip (the native step, k_native.hip): every pass returns at once when *need == 0.
+// A sort that the device may skip (the native step, native_prepare_step): every pass returns at once when *need == 0.
 // The first pass copies the keys in input order to key_copy and resets the block table (table_pairs uint4 entries),
 // the last one sets *fresh and counts the sort.  Passed by value to the pass kernel.
 struct OnesweepGate {
@@ -758,14 +758,15 @@ gpe_status launch_query_gather(gpe_ctx *c, bool box, const float *region, const 
                                float2 *prev_out, float *radius_out);
 // *pick = min over the particles whose disc contains (x, y) of bits(d2) << 32 | index (~0 for none)
 gpe_status launch_pick(gpe_ctx *c, float x, float y, unsigned long long *tile_key, unsigned long long *pick);
-// native pipeline (k_native.hip)
+// native pipeline: its host side (gpe_native.hip; the kernels and their launchers: k_native.hip, native_launch.h)
 gpe_status native_configure(gpe_ctx *c);
 bool native_should_run(gpe_ctx *c);
 NativeStats native_read_stats(const NativeState &N);   // one reading of N.host_stat (allocated: native_configure)
+void native_release(gpe_ctx *c);
+// sharded runs (k_shard.hip)
 gpe_status launch_shard_classify(gpe_ctx *c, const uint8_t *owner_of_block, const uint32_t *dest_mask_of_block,
                                  int32_t blocks_x, int32_t blocks_y, uint32_t my_rank, uint32_t *out_index,
                                  uint32_t *out_info, uint32_t *out_count, uint64_t out_capacity);
-void native_release(gpe_ctx *c);
 void shard_release(gpe_ctx *c);
 void comm_release(gpe_ctx *c);
 void ctl_release(gpe_ctx *c);

@@ -213,6 +213,63 @@ __global__ __launch_bounds__(kUnpackBlock) void k_shard_unpack(ShardArrays A, Sh
     }
 }
 
+// ---------------------------------------------------------------------------------------------------
+// sharded runs: which owned particles must travel (gpe_shard_classify)
+// ---------------------------------------------------------------------------------------------------
+// One streaming pass over the owned particles: R pos 8 B + one table byte/word per particle.  The few
+// that sit in a block owned by another rank (migrants) or bordering other ranks (ghost candidates) are
+// appended with one global atomic per wave.
+__global__ __launch_bounds__(kStreamBlock) void k_shard_classify(const float2 *__restrict__ pos, uint64_t n_owned,
+                                                                  float cell_size,
+                                                                  const uint8_t *__restrict__ owner_of_block,
+                                                                  const uint32_t *__restrict__ dest_mask_of_block,
+                                                                  int32_t blocks_x, int32_t blocks_y, uint32_t my_rank,
+                                                                  uint32_t *__restrict__ out_index,
+                                                                  uint32_t *__restrict__ out_info,
+                                                                  uint32_t *__restrict__ out_count, uint64_t out_capacity)
+{
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    const uint64_t rounds = (n_owned + stride - 1) / stride;
+    for (uint64_t r = 0; r < rounds; ++r) {
+        const uint64_t i = r * stride + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+        uint32_t info = 0;
+        if (i < n_owned) {
+            const float2 p = pos[i];
+            int bx = cell_coord(p.x, cell_size) >> 3, by = cell_coord(p.y, cell_size) >> 3;
+            bx = min(max(bx, 0), blocks_x - 1);
+            by = min(max(by, 0), blocks_y - 1);
+            const uint32_t b = (uint32_t)by * (uint32_t)blocks_x + (uint32_t)bx;
+            const uint32_t owner = owner_of_block[b];
+            // bits 0-25: ranks bordering the block the particle sits in NOW (they need it as a ghost);
+            // bits 26-30: 1 + owner of that block when it is not this rank (the particle migrates)
+            info = (dest_mask_of_block[b] & 0x03FFFFFFu) | ((owner != my_rank) ? ((owner + 1u) << 26) : 0u);
+        }
+        const uint64_t m = ballot64(info != 0);
+        if (m == 0) continue;
+        const int leader = (int)__builtin_ctzll(m);
+        uint32_t base = 0;
+        if (lane_id() == leader) base = atomicAdd(out_count, (uint32_t)__popcll(m));
+        base = __shfl(base, leader, 64);
+        if (info != 0) {
+            const uint64_t slot = (uint64_t)base + popc_below_lane(m);
+            if (slot < out_capacity) { out_index[slot] = (uint32_t)i; out_info[slot] = info; }
+        }
+    }
+}
+
+gpe_status launch_shard_classify(gpe_ctx *c, const uint8_t *owner_of_block, const uint32_t *dest_mask_of_block,
+                                 int32_t blocks_x, int32_t blocks_y, uint32_t my_rank, uint32_t *out_index,
+                                 uint32_t *out_info, uint32_t *out_count, uint64_t out_capacity)
+{
+    if (c->n_owned == 0) return GPE_OK;
+    Scope s(c, "shard/classify");
+    hipLaunchKernelGGL(k_shard_classify, dim3(stream_grid(c->n_owned)), dim3(kStreamBlock), 0, c->stream, c->pos,
+                       c->n_owned, c->cell_size, owner_of_block, dest_mask_of_block, blocks_x, blocks_y, my_rank,
+                       out_index, out_info, out_count, out_capacity);
+    GPE_HIP(c, hipGetLastError());
+    return GPE_OK;
+}
+
 // ---------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------

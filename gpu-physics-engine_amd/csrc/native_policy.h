@@ -1,4 +1,4 @@
-// native_policy.h -- the native step's launch heuristics (k_native.hip), apart from the launches they steer.
+// native_policy.h -- the native step's launch heuristics (gpe_native.hip), apart from the launches they steer.
 // Plain C++17, no HIP header: tests/cpp/native_policy_tests.cpp drives it step by step on the CPU.
 //
 // The tiles report statistics to pinned host words (gpe_internal.h kStat*), asynchronously: what the host reads lags
@@ -26,7 +26,7 @@ constexpr uint64_t kArenaMaxSlots = 1ull << 30; // the arena's slot numbers are 
 constexpr uint32_t kWindowHandover = GPE_WINDOW_HANDOVER;              // above it the context leaves the native path
 constexpr uint32_t kWindowEligible = GPE_WINDOW_HANDOVER * 3 / 2;      // a scene whose windows exceed this never enters it
 
-// One reading of the pinned words (k_native.hip native_read_stats).
+// One reading of the pinned words (native_read_stats).
 struct NativeStats {
     uint32_t window_max = 0;     // kStatWindowMax: largest 24x24-cell window population of the last native step
     uint32_t arena = 0;          // kStatArena: spill-arena slots it handed out

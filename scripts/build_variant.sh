@@ -1,10 +1,11 @@
 #!/bin/bash
-# Build a variant of libgpe.so (extra -D flags on k_native.hip only) into gpurun_tmp/variants/<name>.so; the other
+# Build a variant of libgpe.so, <name>.so in the variants directory ($V below): extra -D flags on the native step's two files only --
+# the kernels, k_native.hip, and their host side, gpe_native.hip, which shares native_launch.h with them; the other
 # objects come from the regular in-tree build.  Runs here (hipcc cross-compiles); the .so travels with gpurun.
-# usage: bash scripts/build_variant.sh <name> "<flags>" [file.hip ...]   (default file: k_native.hip)
+# usage: bash scripts/build_variant.sh <name> "<flags>" [file.hip ...]   (default files: those two)
 set -eu
 name="$1"; flags="${2:-}"; shift; shift || true
-files=("$@"); [ ${#files[@]} -eq 0 ] && files=(k_native.hip)
+files=("$@"); [ ${#files[@]} -eq 0 ] && files=(k_native.hip gpe_native.hip)
 cd "$(dirname "$0")/.."
 python gpu-physics-engine_amd/build.py > /dev/null
 B=gpu-physics-engine_amd/csrc/build; V=gpurun_tmp/variants; mkdir -p $V/obj_$name

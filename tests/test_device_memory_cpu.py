@@ -35,7 +35,7 @@ def test_device_allocation_has_one_home():
 def test_pinned_host_memory_stays_where_it_was():
     """hipHostMalloc: the two pinned mirrors (the native step's statistics, the sharded exchange's counts), nothing else."""
     hits = sorted(os.path.basename(p) for p in _sources() if re.search(r"\bhipHostMalloc\(", _code(p)))
-    assert hits == ["k_native.hip", "k_shard.hip"], hits
+    assert hits == ["gpe_native.hip", "k_shard.hip"], hits
 
 
 TAG = r'"(?:particles|grid|uid|remove|query|user|sort|scan|onesweep|native|shard|ctl|group)\.[a-z0-9_]+"'
@@ -58,14 +58,14 @@ def _calls(code, name):
 
 
 def test_every_allocation_site_names_a_tag():
-    """Every call of an allocating helper (gpe_dev_reserve, dev_reserve, dev_alloc, k_native.hip's reserve,
+    """Every call of an allocating helper (gpe_dev_reserve, dev_reserve, dev_alloc, gpe_native.hip's reserve,
     ensure_words) ends in a tag: a literal of the registry's naming scheme, or an expression made of such literals
     (a choice between tags), or the tag parameter a wrapper hands on.  No tag is longer than gpe_guard_zone.tag holds."""
     sites, tags = 0, set()
     for path in _sources():
         code = _code(path)
         names = ["gpe_dev_reserve", "dev_reserve", "dev_alloc", "ensure_words"]
-        if os.path.basename(path) == "k_native.hip":
+        if os.path.basename(path) == "gpe_native.hip":
             names.append("reserve")
         for name in names:
             for args in _calls(code, name):
