@@ -39,6 +39,8 @@ COUNTING_CHUNK_SIZE = 4
 POS, PREV, RADIUS, HOME_CELL_IDS, PARTICLE_IDS, CELL_IDS, OBJECT_IDS, COLLISION_CELLS, \
     NUM_COLLISION_CELLS, CHUNK_OBJ_COUNT, INDIRECT_ARGS, ORDER_KEYS, UIDS = range(13)
 UID_ABSENT = 0xFFFFFFFF
+EDIT_BY_INDEX, EDIT_BY_UID = 0, 1
+VEL_ADD, VEL_SET, VEL_SCALE = 0, 1, 2
 
 
 class GpeConfig(C.Structure):
@@ -121,6 +123,13 @@ class GpeQueryResult(C.Structure):
                 ("prev_xy", C.POINTER(C.c_float)), ("radius", C.POINTER(C.c_float))]
 
 
+class GpeParticleEdit(C.Structure):
+    """gpe_particle_edit: in struct_size / key_kind / k / keys and the field arrays (each may be NULL), out edited."""
+    _fields_ = [("struct_size", C.c_uint32), ("key_kind", C.c_uint32), ("k", C.c_uint64),
+                ("keys", C.POINTER(C.c_uint32)), ("pos_xy", C.POINTER(C.c_float)), ("prev_xy", C.POINTER(C.c_float)),
+                ("radius", C.POINTER(C.c_float)), ("edited", C.c_uint64)]
+
+
 GUARD_MAX_ZONES = 8
 GUARD_FRONT, GUARD_REAR = 0, 1
 
@@ -163,6 +172,9 @@ SYMBOLS = [
     ("gpe_query_circle", _I32, [_VP, _F, _F, _F, C.POINTER(GpeQueryResult)]),
     ("gpe_query_box", _I32, [_VP, _F, _F, _F, _F, C.POINTER(GpeQueryResult)]),
     ("gpe_pick", _I32, [_VP, _F, _F, C.POINTER(GpeQueryResult)]),
+    ("gpe_edit_particles", _I32, [_VP, C.POINTER(GpeParticleEdit)]),
+    ("gpe_kick_circle", _I32, [_VP, _F, _F, _F, _U32, _F, _F, C.POINTER(_U64)]),
+    ("gpe_kick_box", _I32, [_VP, _F, _F, _F, _F, _U32, _F, _F, C.POINTER(_U64)]),
     ("gpe_len", _I32, [_VP, C.POINTER(_U64)]),
     ("gpe_max_radius", _I32, [_VP, C.POINTER(_F)]),
     ("gpe_morton_resort", _I32, [_VP]),

@@ -288,6 +288,10 @@ static void free_particle_buffers(gpe_ctx *c)
     dev_free(c, c->query_ws.tile_count); dev_free(c, c->query_ws.tile_key); dev_free(c, c->query_ws.pick);
     dev_free(c, c->query_ws.stage);
     c->query_ws.tiles_cap = c->query_ws.stage_cap = 0;
+    EditWorkspace &e = c->edit_ws;
+    dev_free(c, e.keys); dev_free(c, e.slots); dev_free(c, e.fields); dev_free(c, e.flag);
+    dev_free(c, e.tile_key); dev_free(c, e.max_key); dev_free(c, e.count);
+    e.keys_cap = e.fields_cap = e.tiles_cap = 0;
     free_uid_buffers(c);
     c->cap = 0;
 }
@@ -662,6 +666,23 @@ static gpe_status uid_query_reserve(gpe_ctx *c, uint64_t bytes)
     u.query_cap = 0;
     GPE_TRY(dev_alloc(c, &u.query, bytes, "uid.query"));
     u.query_cap = bytes;
+    return GPE_OK;
+}
+
+// ---- in-place edits (k_edit.hip) ---------------------------------------------------------------------------
+// One buffer of the edit workspace (tags "edit.*"): allocated at first use and, with a capacity word, regrown when
+// `count` passes it (cap == NULL: a buffer of fixed size).  payload: count elements; slack_bytes: stated at the call
+// with its reader.
+template <typename T>
+static gpe_status edit_buffer(gpe_ctx *c, T **p, uint64_t *cap, uint64_t count, uint64_t slack_bytes, const char *tag)
+{
+    if (*p && (!cap || *cap >= count)) return GPE_OK;
+    dev_free(c, *p);
+    if (cap) *cap = 0;
+    const hipError_t e = dev_reserve(c, p, count * sizeof(T), slack_bytes, tag);
+    if (e == hipErrorOutOfMemory) return fail(c, GPE_ERR_OOM, "hipMalloc: out of device memory");
+    if (e != hipSuccess) return fail(c, GPE_ERR_HIP, std::string("hipMalloc: ") + hipGetErrorName(e));
+    if (cap) *cap = count;
     return GPE_OK;
 }
 
@@ -1319,25 +1340,46 @@ static gpe_status do_query(gpe_ctx *c, bool box, const float *region, gpe_query_
     return GPE_OK;
 }
 
+// The argument checks and the region words (as launch_query_count takes them) of the circle and box calls: the
+// queries and the kicks (gpe_kick_*) share them, so that both select the same particles.
+static gpe_status circle_region(gpe_ctx *c, const char *who, float x, float y, float radius, float (&region)[5])
+{
+    if (!(radius >= 0.0f) || !isfinite(radius))
+        return fail(c, GPE_ERR_INVALID_ARG, std::string(who) + ": radius must be finite and >= 0");
+    const float words[5] = {x, y, 0.f, 0.f, radius * radius};     // binary32, as gpe_remove_particles_in_circle
+    std::copy(words, words + 5, region);
+    return GPE_OK;
+}
+
+// *empty: x0 > x1 or y0 > y1, a box that holds nothing
+static gpe_status box_region(gpe_ctx *c, const char *who, float x0, float y0, float x1, float y1, float (&region)[5],
+                             bool *empty)
+{
+    if (isnan(x0) || isnan(y0) || isnan(x1) || isnan(y1)) return fail(c, GPE_ERR_INVALID_ARG, std::string(who) + ": NaN bound");
+    const float words[5] = {x0, y0, x1, y1, 0.f};
+    std::copy(words, words + 5, region);
+    *empty = x0 > x1 || y0 > y1;
+    return GPE_OK;
+}
+
 gpe_status gpe_query_circle(gpe_ctx *c, float x, float y, float radius, gpe_query_result *out)
 {
     bool go = false;
+    float region[5];
     GPE_TRY(query_begin(c, out, "gpe_query_circle", &go));
-    if (!(radius >= 0.0f) || !isfinite(radius))
-        return fail(c, GPE_ERR_INVALID_ARG, "gpe_query_circle: radius must be finite and >= 0");
+    GPE_TRY(circle_region(c, "gpe_query_circle", x, y, radius, region));
     if (!go) return GPE_OK;
-    const float region[5] = {x, y, 0.f, 0.f, radius * radius};   // binary32, as gpe_remove_particles_in_circle
     return do_query(c, false, region, out);
 }
 
 gpe_status gpe_query_box(gpe_ctx *c, float x0, float y0, float x1, float y1, gpe_query_result *out)
 {
     bool go = false;
+    float region[5];
+    bool empty = false;
     GPE_TRY(query_begin(c, out, "gpe_query_box", &go));
-    if (isnan(x0) || isnan(y0) || isnan(x1) || isnan(y1))
-        return fail(c, GPE_ERR_INVALID_ARG, "gpe_query_box: NaN bound");
-    if (!go || x0 > x1 || y0 > y1) return GPE_OK;                 // an empty box holds nothing
-    const float region[5] = {x0, y0, x1, y1, 0.f};
+    GPE_TRY(box_region(c, "gpe_query_box", x0, y0, x1, y1, region, &empty));
+    if (!go || empty) return GPE_OK;                              // an empty box holds nothing
     return do_query(c, true, region, out);
 }
 
@@ -1371,6 +1413,174 @@ gpe_status gpe_pick(gpe_ctx *c, float x, float y, gpe_query_result *out)
     }
     out->count = 1;
     return GPE_OK;
+}
+
+// ---- editing particles in place (k_edit.hip) ---------------------------------------------------------------
+// staging rows, 256-byte aligned parts, only the requested fields: pos | prev | radius
+struct EditRows {
+    uint64_t o_prev = 0, o_radius = 0, bytes = 0;
+};
+static EditRows edit_rows(const gpe_particle_edit *e)
+{
+    const uint64_t k = e->k;
+    auto part = [k](bool on, uint64_t width) { return on ? (k * width + 255) / 256 * 256 : 0; };
+    EditRows r;
+    r.o_prev = part(e->pos_xy, 8);
+    r.o_radius = r.o_prev + part(e->prev_xy, 8);
+    r.bytes = r.o_radius + part(e->radius, 4);
+    return r;
+}
+
+static gpe_status do_edit(gpe_ctx *c, gpe_particle_edit *e)
+{
+    EditWorkspace &ws = c->edit_ws;
+    const uint64_t k = e->k, n = c->n;
+    const bool by_uid = e->key_kind == GPE_EDIT_BY_UID;
+    const EditRows rows = edit_rows(e);
+    if (by_uid) GPE_TRY(uid_map_ready(c));
+    // keys / slots (one capacity): sorted by sort_pairs, whose tile loads may read 16 words behind the k pairs
+    uint64_t cap_keys = ws.keys ? ws.keys_cap : 0, cap_slots = ws.slots ? ws.keys_cap : 0;
+    ws.keys_cap = 0;
+    GPE_TRY(edit_buffer(c, &ws.keys, &cap_keys, k, 16 * sizeof(uint32_t), "edit.keys"));
+    GPE_TRY(edit_buffer(c, &ws.slots, &cap_slots, k, 16 * sizeof(uint32_t), "edit.slots"));
+    ws.keys_cap = std::min(cap_keys, cap_slots);
+    GPE_TRY(edit_buffer(c, &ws.fields, &ws.fields_cap, rows.bytes, 0, "edit.fields"));
+    GPE_TRY(edit_buffer(c, &ws.flag, nullptr, 2, 0, "edit.flag"));
+    if (k > 1) GPE_TRY(sort_reserve(c, k));
+    Scope s(c, "Edit particles");
+    uint32_t flag[2] = {0, 0};
+    {
+        Scope sk(c, "edit/check");
+        GPE_HIP(c, hipMemcpyAsync(ws.keys, e->keys, k * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+        GPE_HIP(c, hipMemsetAsync(ws.flag, 0, sizeof(flag), c->stream));
+        GPE_TRY(launch_edit_check(c, by_uid, ws.keys, ws.slots, k, ws.flag));
+        if (k > 1) {                                             // two keys naming one particle become neighbours
+            GPE_TRY(sort_pairs(c, ws.keys, ws.slots, k));
+            GPE_TRY(launch_edit_adjacent(c, ws.keys, k, ws.flag));
+        }
+    }
+    GPE_HIP(c, hipMemcpyAsync(flag, ws.flag, sizeof(flag), hipMemcpyDeviceToHost, c->stream));
+    GPE_HIP(c, hipStreamSynchronize(c->stream));
+    if (flag[0] & kEditBadIndex) return fail(c, GPE_ERR_INVALID_ARG, "gpe_edit_particles: an index is not below gpe_len");
+    if (flag[0] & kEditDuplicate) return fail(c, GPE_ERR_INVALID_ARG, "gpe_edit_particles: two keys name the same particle");
+    if (flag[1] == 0) return GPE_OK;                             // every uid absent: nothing to write
+    // from here on the particles change
+    uint8_t *st = ws.fields;
+    const float2 *d_pos = e->pos_xy ? reinterpret_cast<const float2 *>(st) : nullptr;
+    const float2 *d_prev = e->prev_xy ? reinterpret_cast<const float2 *>(st + rows.o_prev) : nullptr;
+    const float *d_radius = e->radius ? reinterpret_cast<const float *>(st + rows.o_radius) : nullptr;
+    {
+        Scope sk(c, "edit/apply");
+        if (d_pos) GPE_HIP(c, hipMemcpyAsync(st, e->pos_xy, k * 8, hipMemcpyHostToDevice, c->stream));
+        if (d_prev) GPE_HIP(c, hipMemcpyAsync(st + rows.o_prev, e->prev_xy, k * 8, hipMemcpyHostToDevice, c->stream));
+        if (d_radius) GPE_HIP(c, hipMemcpyAsync(st + rows.o_radius, e->radius, k * 4, hipMemcpyHostToDevice, c->stream));
+        GPE_TRY(launch_edit_apply(c, ws.keys, ws.slots, k, d_pos, d_prev, d_radius));
+    }
+    if (d_radius) {
+        const uint64_t tiles = query_tiles(n);
+        GPE_TRY(edit_buffer(c, &ws.tile_key, &ws.tiles_cap, tiles, 0, "edit.tile_key"));
+        GPE_TRY(edit_buffer(c, &ws.max_key, nullptr, 1, 0, "edit.max_key"));
+        unsigned long long key = 0;
+        {
+            Scope sk(c, "edit/max radius");
+            GPE_TRY(launch_edit_max_radius(c, ws.tile_key, ws.max_key));
+        }
+        GPE_HIP(c, hipMemcpyAsync(&key, ws.max_key, sizeof(key), hipMemcpyDeviceToHost, c->stream));
+        GPE_HIP(c, hipStreamSynchronize(c->stream));
+        const uint32_t winner = (uint32_t)(key & 0xFFFFFFFFull);   // index of the max |radius|, the last on ties
+        if (winner >= n) return fail(c, GPE_ERR_STATE, "gpe_edit_particles: bad max-radius index");
+        float max_r = 0.f;
+        GPE_HIP(c, hipMemcpyAsync(&max_r, c->radius + winner, sizeof(max_r), hipMemcpyDeviceToHost, c->stream));
+        GPE_HIP(c, hipStreamSynchronize(c->stream));
+        c->max_radius = max_r;                                   // sign kept
+        c->grid_max_radius = c->max_radius;
+        refresh_cell_size(c);
+    }
+    GPE_HIP(c, hipStreamSynchronize(c->stream));                 // the host arrays may be released on return
+    if (d_pos || d_radius) GPE_TRY(reconfigure_native(c));       // (prev alone is part of no kept structure)
+    e->edited = flag[1];
+    return GPE_OK;
+}
+
+gpe_status gpe_edit_particles(gpe_ctx *c, gpe_particle_edit *e)
+{
+    if (!c) return GPE_ERR_INVALID_ARG;
+    if (!e) return fail(c, GPE_ERR_INVALID_ARG, "gpe_edit_particles: NULL edit");
+    if (e->struct_size < sizeof(gpe_particle_edit))
+        return fail(c, GPE_ERR_INVALID_ARG, "gpe_edit_particles: struct_size is smaller than gpe_particle_edit");
+    e->edited = 0;
+    if (!e->keys) return fail(c, GPE_ERR_INVALID_ARG, "gpe_edit_particles: NULL keys");
+    if (e->key_kind != GPE_EDIT_BY_INDEX && e->key_kind != GPE_EDIT_BY_UID)
+        return fail(c, GPE_ERR_INVALID_ARG, "gpe_edit_particles: unknown key_kind");
+    if (!e->pos_xy && !e->prev_xy && !e->radius)
+        return fail(c, GPE_ERR_INVALID_ARG, "gpe_edit_particles: every field array is NULL");
+    if (is_sharded(c))
+        return fail(c, GPE_ERR_UNSUPPORTED, "gpe_edit_particles: not supported on a sharded context (gpe_shard_*, order "
+                                            "keys or an active cell box)");
+    if (e->key_kind == GPE_EDIT_BY_UID && !c->uid.on) return fail(c, GPE_ERR_STATE, "gpe_edit_particles: uids are off");
+    if (e->k == 0) return GPE_OK;
+    GPE_TRY(need_particles(c));
+    // (more indices than particles repeat one; a list of uids may be padded with absent ones)
+    if (e->key_kind == GPE_EDIT_BY_INDEX && e->k > c->n)
+        return fail(c, GPE_ERR_INVALID_ARG, "gpe_edit_particles: two keys name the same particle");
+    if (e->k > (1ull << 30) - 1) return fail(c, GPE_ERR_INVALID_ARG, "gpe_edit_particles: k too large");
+    GPE_HIP(c, hipSetDevice(c->device));
+    GPE_HIP(c, hipStreamSynchronize(c->stream));
+    return do_edit(c, e);
+}
+
+// The checks the two kicks share, in this order: *n_kicked = 0, the sharded refusal, op and a.
+static gpe_status kick_begin(gpe_ctx *c, const char *who, uint32_t op, float ax, float ay, uint64_t *n_kicked)
+{
+    if (!c) return GPE_ERR_INVALID_ARG;
+    if (n_kicked) *n_kicked = 0;
+    if (is_sharded(c))
+        return fail(c, GPE_ERR_UNSUPPORTED, std::string(who) + ": not supported on a sharded context (gpe_shard_*, "
+                                                                "order keys or an active cell box)");
+    if (op != GPE_VEL_ADD && op != GPE_VEL_SET && op != GPE_VEL_SCALE)
+        return fail(c, GPE_ERR_INVALID_ARG, std::string(who) + ": unknown operation");
+    if (!isfinite(ax) || !isfinite(ay)) return fail(c, GPE_ERR_INVALID_ARG, std::string(who) + ": ax and ay must be finite");
+    return GPE_OK;
+}
+
+static gpe_status do_kick(gpe_ctx *c, bool box, const float *region, uint32_t op, float ax, float ay, uint64_t *n_kicked)
+{
+    if (c->n == 0 || !c->pos) return GPE_OK;                      // nothing to kick
+    GPE_HIP(c, hipSetDevice(c->device));
+    unsigned long long *d_count = nullptr;
+    if (n_kicked) {
+        GPE_TRY(edit_buffer(c, &c->edit_ws.count, nullptr, 1, 0, "edit.count"));
+        d_count = c->edit_ws.count;
+    }
+    {
+        Scope s(c, "Kick particles");
+        GPE_TRY(launch_kick(c, box, region, op, ax, ay, d_count));
+    }
+    if (!n_kicked) return GPE_OK;                                 // stream-ordered, like gpe_step
+    unsigned long long kicked = 0;
+    GPE_HIP(c, hipMemcpyAsync(&kicked, d_count, sizeof(kicked), hipMemcpyDeviceToHost, c->stream));
+    GPE_HIP(c, hipStreamSynchronize(c->stream));
+    *n_kicked = kicked;
+    return GPE_OK;
+}
+
+gpe_status gpe_kick_circle(gpe_ctx *c, float x, float y, float radius, uint32_t op, float ax, float ay, uint64_t *n_kicked)
+{
+    float region[5];
+    GPE_TRY(kick_begin(c, "gpe_kick_circle", op, ax, ay, n_kicked));
+    GPE_TRY(circle_region(c, "gpe_kick_circle", x, y, radius, region));
+    return do_kick(c, false, region, op, ax, ay, n_kicked);
+}
+
+gpe_status gpe_kick_box(gpe_ctx *c, float x0, float y0, float x1, float y1, uint32_t op, float ax, float ay,
+                        uint64_t *n_kicked)
+{
+    float region[5];
+    bool empty = false;
+    GPE_TRY(kick_begin(c, "gpe_kick_box", op, ax, ay, n_kicked));
+    GPE_TRY(box_region(c, "gpe_kick_box", x0, y0, x1, y1, region, &empty));
+    if (empty) return GPE_OK;                                     // an empty box holds nothing
+    return do_kick(c, true, region, op, ax, ay, n_kicked);
 }
 
 gpe_status gpe_len(const gpe_ctx *c, uint64_t *n)

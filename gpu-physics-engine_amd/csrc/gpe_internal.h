@@ -145,6 +145,17 @@ __device__ __forceinline__ uint32_t wave_sum(uint32_t v)
     return (uint32_t)__builtin_amdgcn_readlane((int)wave_inclusive_scan(v), 63);
 }
 
+// max over the 64 lanes, the same in every lane (the max-radius keys of k_remove.hip and k_edit.hip)
+__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v)
+{
+#pragma unroll
+    for (int d = 1; d < kWave; d <<= 1) {
+        const unsigned long long o = __shfl_xor(v, d, kWave);
+        v = o > v ? o : v;
+    }
+    return v;
+}
+
 // exclusive scan of one value per thread over a 256-thread block; `total` receives the block sum.
 // s_w: >= 4 words of LDS scratch.  Contains __syncthreads (all 256 threads must call it).
 __device__ __forceinline__ uint32_t block256_exclusive_scan(uint32_t v, uint32_t *s_w, uint32_t *total)
@@ -266,6 +277,21 @@ struct QueryWorkspace {          // gpe_query_* / gpe_pick (k_query.hip); alloca
     uint8_t *stage = nullptr;                    // the gathered rows of the requested fields
     uint64_t stage_cap = 0;                      // bytes
 };
+
+struct EditWorkspace {           // gpe_edit_particles / gpe_kick_* (k_edit.hip); allocated at first use, freed with the particles
+    uint32_t *keys = nullptr;                    // the caller's keys, resolved to storage indices in place, then sorted
+    uint32_t *slots = nullptr;                   // each key's position in the caller's arrays, sorted with it
+    uint64_t keys_cap = 0;
+    uint8_t *fields = nullptr;                   // the staged rows of the requested fields: pos | prev | radius
+    uint64_t fields_cap = 0;                     // bytes
+    uint32_t *flag = nullptr;                    // [0] refusal bits (kEditBadIndex / kEditDuplicate), [1] keys that name a particle
+    unsigned long long *tile_key = nullptr;      // radius edits: per-tile max of bits(|radius|) << 32 | index
+    uint64_t tiles_cap = 0;
+    unsigned long long *max_key = nullptr;       // ... and the max over the tiles
+    unsigned long long *count = nullptr;         // gpe_kick_*: particles kicked (zeroed by the call)
+};
+constexpr uint32_t kEditBadIndex = 1u, kEditDuplicate = 2u;
+constexpr uint32_t kEditPos = 1u, kEditPrev = 2u, kEditRadius = 4u;   // field mask of k_edit_apply
 
 struct UidState {               // opt-in particle uids (gpe_enable_uids; k_uids.hip)
     bool on = false;
@@ -620,6 +646,7 @@ struct gpe_ctx {
     gpe::RemoveWorkspace remove_ws;
     gpe::UidState uid;
     gpe::QueryWorkspace query_ws;
+    gpe::EditWorkspace edit_ws;
     gpe::ScanWorkspace scan_ws;
     gpe::OnesweepWorkspace os_ws;
     gpe::NativeState native;
@@ -745,6 +772,8 @@ gpe_status onesweep_sort(gpe_ctx *c, uint32_t *keys, uint32_t *vals, uint32_t *k
 uint64_t remove_tiles(uint64_t n);
 gpe_status launch_remove_count(gpe_ctx *c, const uint8_t *mask, float x, float y, float rr, uint32_t *tile_count,
                                unsigned long long *tile_key, unsigned long long *max_key);
+// *max_key = max over tile_key[0 .. tiles) (k_remove_max_key; also the fold of a radius edit's keys)
+gpe_status launch_max_key_fold(gpe_ctx *c, const unsigned long long *tile_key, uint64_t tiles, unsigned long long *max_key);
 // uids != NULL (uids on): each survivor's uid moves to uids_out as well
 gpe_status launch_remove_scatter(gpe_ctx *c, const uint8_t *mask, float x, float y, float rr,
                                  const uint32_t *tile_scanned, const uint32_t *uids = nullptr,
@@ -758,6 +787,20 @@ gpe_status launch_query_gather(gpe_ctx *c, bool box, const float *region, const 
                                float2 *prev_out, float *radius_out);
 // *pick = min over the particles whose disc contains (x, y) of bits(d2) << 32 | index (~0 for none)
 gpe_status launch_pick(gpe_ctx *c, float x, float y, unsigned long long *tile_key, unsigned long long *pick);
+// in-place edits (k_edit.hip).  Keyed edits: keys[i] becomes the storage index key i names (by_uid: looked up in the
+// sorted uid map of n entries; GPE_UID_ABSENT for an absent uid or an index >= n, the latter also sets kEditBadIndex in
+// flag[0]), slots[i] = i, flag[1] += the keys that name a particle.  flag zeroed by the caller.
+gpe_status launch_edit_check(gpe_ctx *c, bool by_uid, uint32_t *keys, uint32_t *slots, uint64_t k, uint32_t *flag);
+// keys sorted ascending: two equal neighbours other than GPE_UID_ABSENT set kEditDuplicate in flag[0]
+gpe_status launch_edit_adjacent(gpe_ctx *c, const uint32_t *keys, uint64_t k, uint32_t *flag);
+// particle keys[j] takes row slots[j] of every non-NULL field array (pos without prev: prev = the new pos too)
+gpe_status launch_edit_apply(gpe_ctx *c, const uint32_t *keys, const uint32_t *slots, uint64_t k, const float2 *pos_rows,
+                             const float2 *prev_rows, const float *radius_rows);
+// *max_key = max over all particles of bits(|radius|) << 32 | index (the key of k_remove_count; tile_key: query_tiles(n))
+gpe_status launch_edit_max_radius(gpe_ctx *c, unsigned long long *tile_key, unsigned long long *max_key);
+// region as launch_query_count; op GPE_VEL_*; count != NULL: *count (zeroed here) receives the particles kicked
+gpe_status launch_kick(gpe_ctx *c, bool box, const float *region, uint32_t op, float ax, float ay,
+                       unsigned long long *count);
 // native pipeline: its host side (gpe_native.hip; the kernels and their launchers: k_native.hip, native_launch.h)
 gpe_status native_configure(gpe_ctx *c);
 bool native_should_run(gpe_ctx *c);

@@ -72,16 +72,6 @@ __device__ __forceinline__ void survivors_of_tile(const RemovePredicate &P, cons
     }
 }
 
-__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v)
-{
-#pragma unroll
-    for (int d = 1; d < kWave; d <<= 1) {
-        const unsigned long long o = __shfl_xor(v, d, kWave);
-        v = o > v ? o : v;
-    }
-    return v;
-}
-
 // (1) survivors per tile, and max over the tile's survivors of bits(|radius|) << 32 | index (ties: the larger index,
 // i.e. the last element of largest magnitude, as max_abs_radius picks it; 0 for a tile without survivors)
 template <bool MASK>
@@ -191,6 +181,15 @@ __global__ __launch_bounds__(kRemoveBlock) void k_remove_scatter(RemovePredicate
 
 uint64_t remove_tiles(uint64_t n) { return (n + kRemoveTile - 1) / kRemoveTile; }
 
+gpe_status launch_max_key_fold(gpe_ctx *c, const unsigned long long *tile_key, uint64_t tiles, unsigned long long *max_key)
+{
+    GPE_HIP(c, hipMemsetAsync(max_key, 0, sizeof(*max_key), c->stream));
+    const uint64_t g = std::min<uint64_t>((tiles + 4 * kRemoveBlock - 1) / (4 * kRemoveBlock), kMaxKeyBlocks);
+    hipLaunchKernelGGL(k_remove_max_key, dim3((uint32_t)g), dim3(kRemoveBlock), 0, c->stream, tile_key, tiles, max_key);
+    GPE_HIP(c, hipGetLastError());
+    return GPE_OK;
+}
+
 gpe_status launch_remove_count(gpe_ctx *c, const uint8_t *mask, float x, float y, float rr, uint32_t *tile_count,
                                unsigned long long *tile_key, unsigned long long *max_key)
 {
@@ -204,11 +203,7 @@ gpe_status launch_remove_count(gpe_ctx *c, const uint8_t *mask, float x, float y
         hipLaunchKernelGGL(k_remove_count<false>, dim3((uint32_t)tiles), dim3(kRemoveBlock), 0, c->stream, P, c->pos,
                            c->radius, c->n, tile_count, tile_key);
     GPE_HIP(c, hipGetLastError());
-    GPE_HIP(c, hipMemsetAsync(max_key, 0, sizeof(*max_key), c->stream));
-    const uint64_t g = std::min<uint64_t>((tiles + 4 * kRemoveBlock - 1) / (4 * kRemoveBlock), kMaxKeyBlocks);
-    hipLaunchKernelGGL(k_remove_max_key, dim3((uint32_t)g), dim3(kRemoveBlock), 0, c->stream, tile_key, tiles, max_key);
-    GPE_HIP(c, hipGetLastError());
-    return GPE_OK;
+    return launch_max_key_fold(c, tile_key, tiles, max_key);
 }
 
 gpe_status launch_remove_scatter(gpe_ctx *c, const uint8_t *mask, float x, float y, float rr,

@@ -23,4 +23,20 @@ gpe_status launch_uid_find(gpe_ctx *c, const uint32_t *keys, const uint32_t *val
 gpe_status launch_uid_mark(gpe_ctx *c, const uint32_t *keys, const uint32_t *vals, uint64_t n, const uint32_t *query,
                            uint64_t k, uint8_t *mask);
 
+// The storage index of uid q in the sorted map (keys, vals) of n >= 1 entries, or GPE_UID_ABSENT.  lower_bound by
+// halving: ceil(log2 n) steps, a select each.  (k_uid_find, k_uid_mark; k_edit_check of k_edit.hip)
+__device__ __forceinline__ uint32_t uid_lookup(const uint32_t *__restrict__ keys, const uint32_t *__restrict__ vals,
+                                               uint32_t n, uint32_t q)
+{
+    uint32_t base = 0, len = n;
+    while (len > 1) {                          // uniform: the same len sequence on every lane
+        const uint32_t half = len >> 1;
+        base = keys[base + half] < q ? base + half : base;
+        len -= half;
+    }
+    const uint32_t at = base + (keys[base] < q ? 1u : 0u);
+    const uint32_t hit = at < n ? keys[at] : ~q;
+    return hit == q ? vals[at] : GPE_UID_ABSENT;
+}
+
 }  // namespace gpe

@@ -66,21 +66,6 @@ __global__ __launch_bounds__(kStreamBlock) void k_uid_adjacent(const uint32_t *_
     if (ballot64(same) != 0 && lane_id() == 0) *dup = 1u;
 }
 
-// The storage index of uid q, or GPE_UID_ABSENT.  lower_bound by halving: ceil(log2 n) steps, a select each.
-__device__ __forceinline__ uint32_t uid_lookup(const uint32_t *__restrict__ keys, const uint32_t *__restrict__ vals,
-                                               uint32_t n, uint32_t q)
-{
-    uint32_t base = 0, len = n;
-    while (len > 1) {                          // uniform: the same len sequence on every lane
-        const uint32_t half = len >> 1;
-        base = keys[base + half] < q ? base + half : base;
-        len -= half;
-    }
-    const uint32_t at = base + (keys[base] < q ? 1u : 0u);
-    const uint32_t hit = at < n ? keys[at] : ~q;
-    return hit == q ? vals[at] : GPE_UID_ABSENT;
-}
-
 __global__ __launch_bounds__(kStreamBlock) void k_uid_find(const uint32_t *__restrict__ keys,
                                                             const uint32_t *__restrict__ vals, uint32_t n,
                                                             const uint32_t *__restrict__ query, uint64_t k,

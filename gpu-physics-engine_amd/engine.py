@@ -420,6 +420,48 @@ class ParticleSystem:
         """gpe_query_box with no outputs: the number of particles query_box would return."""
         return self._count("gpe_query_box", (float(lo[0]), float(lo[1]), float(hi[0]), float(hi[1])))
 
+    # Editing particles in place (not in the reference; include/gpe.h): new pos / prev / radius for particles named by
+    # storage index or by uid, and velocity kicks of every particle in a circle or a box -- all on the device, the
+    # uids, the order and the native counters kept.
+    def edit_particles(self, indices=None, uids=None, positions=None, previous=None, radii=None):
+        """gpe_edit_particles: the particles named by `indices` (storage order) or by `uids` -- exactly one of the two --
+        take row i of every array given (positions f32[k,2], previous f32[k,2], radii f32[k]); an array left None leaves
+        that field alone, positions without previous puts the particle at rest (prev = pos).  Unknown uids are skipped.
+        Returns the number of particles written."""
+        if (indices is None) == (uids is None):
+            raise ValueError("exactly one of indices / uids must be given")
+        keys = np.ascontiguousarray(indices if uids is None else uids, np.uint32).reshape(-1)
+        k = keys.shape[0]
+        e = L.GpeParticleEdit(struct_size=C.sizeof(L.GpeParticleEdit), k=k,
+                              key_kind=L.EDIT_BY_INDEX if uids is None else L.EDIT_BY_UID)
+        keep = [keys if k else np.zeros(1, np.uint32)]                 # (alive until the call returns)
+        e.keys = keep[0].ctypes.data_as(C.POINTER(C.c_uint32))
+        for field, rows, width in (("pos_xy", positions, 2), ("prev_xy", previous, 2), ("radius", radii, 1)):
+            if rows is None:
+                continue
+            a = np.ascontiguousarray(rows, np.float32).reshape(-1)
+            if a.shape[0] != width * k:
+                raise ValueError("%s: expected %d values for %d keys" % (field, width * k, k))
+            keep.append(a if k else np.zeros(width, np.float32))
+            setattr(e, field, keep[-1].ctypes.data_as(C.POINTER(C.c_float)))
+        self.ctx.call("gpe_edit_particles", C.byref(e))
+        return e.edited
+
+    def _kick(self, name, args, op, a, count):
+        kicked = C.c_uint64()
+        self.ctx.call(name, *args, int(op), float(a[0]), float(a[1]), C.byref(kicked) if count else None)
+        return kicked.value if count else None
+
+    def kick_circle(self, center, radius, op, a, count=True):
+        """gpe_kick_circle: for every particle query_circle(center, radius) returns, per component in float32,
+        L.VEL_ADD prev -= a, L.VEL_SET prev = pos - a, L.VEL_SCALE prev = pos - (pos - prev) * a.  Returns the number
+        kicked; count=False returns None without waiting for the device (stream-ordered, like update)."""
+        return self._kick("gpe_kick_circle", (float(center[0]), float(center[1]), float(radius)), op, a, count)
+
+    def kick_box(self, lo, hi, op, a, count=True):
+        """gpe_kick_box: kick_circle for the particles query_box(lo, hi) returns."""
+        return self._kick("gpe_kick_box", (float(lo[0]), float(lo[1]), float(hi[0]), float(hi[1])), op, a, count)
+
     def len(self):
         n = C.c_uint64()
         self.ctx.call("gpe_len", C.byref(n))
@@ -659,6 +701,19 @@ class State:
 
     def count_box(self, lo, hi):
         return self.particles.count_box(lo, hi)
+
+    def edit_particles(self, indices=None, uids=None, positions=None, previous=None, radii=None):
+        """ParticleSystem.edit_particles: returns how many particles were written."""
+        return self.particles.edit_particles(indices=indices, uids=uids, positions=positions, previous=previous,
+                                             radii=radii)
+
+    def kick_circle(self, center, radius, op, a, count=True):
+        """ParticleSystem.kick_circle: returns how many were kicked (None with count=False)."""
+        return self.particles.kick_circle(center, radius, op, a, count=count)
+
+    def kick_box(self, lo, hi, op, a, count=True):
+        """ParticleSystem.kick_box."""
+        return self.particles.kick_box(lo, hi, op, a, count=count)
 
     def _uids_on(self):
         try:

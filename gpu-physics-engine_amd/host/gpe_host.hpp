@@ -255,6 +255,44 @@ class ParticleSystem {
         ctx_->call(gpe_query_box(ctx_->raw(), lo.x, lo.y, hi.x, hi.y, &r));
         return r.count;
     }
+    // not in the reference: edit particles in place on the device (include/gpe.h).  The particles named by `keys` --
+    // storage indices, or uids with by_uid -- take row i of every array given (NULL: that field stays; positions without
+    // previous: at rest, prev = pos).  Unknown uids are skipped.  Returns the number of particles written.
+    uint64_t edit_particles(const std::vector<uint32_t> &keys, bool by_uid, const std::vector<Vec2> *positions,
+                            const std::vector<Vec2> *previous = nullptr, const std::vector<float> *radii = nullptr)
+    {
+        if ((positions && positions->size() != keys.size()) || (previous && previous->size() != keys.size()) ||
+            (radii && radii->size() != keys.size()))
+            throw std::invalid_argument("edit_particles: an array differs from the keys in length");
+        const uint32_t none = 0;
+        const Vec2 none2{};
+        const bool empty = keys.empty();                                     // (k == 0: the arrays are not read)
+        gpe_particle_edit e{};
+        e.struct_size = sizeof(gpe_particle_edit);
+        e.key_kind = by_uid ? GPE_EDIT_BY_UID : GPE_EDIT_BY_INDEX;
+        e.k = keys.size();
+        e.keys = empty ? &none : keys.data();
+        e.pos_xy = positions ? (empty ? &none2.x : &(*positions)[0].x) : nullptr;
+        e.prev_xy = previous ? (empty ? &none2.x : &(*previous)[0].x) : nullptr;
+        e.radius = radii ? (empty ? &none2.x : radii->data()) : nullptr;
+        ctx_->call(gpe_edit_particles(ctx_->raw(), &e));
+        return e.edited;
+    }
+    // ... and kick the velocity pos - prev of every particle query_circle / query_box would return: op GPE_VEL_ADD
+    // (prev -= a), GPE_VEL_SET (prev = pos - a) or GPE_VEL_SCALE (prev = pos - (pos - prev) * a), per component.  Returns
+    // the number kicked; count = false returns 0 without waiting for the device (stream-ordered, like State::update).
+    uint64_t kick_circle(Vec2 center, float radius, uint32_t op, Vec2 a, bool count = true)
+    {
+        uint64_t kicked = 0;
+        ctx_->call(gpe_kick_circle(ctx_->raw(), center.x, center.y, radius, op, a.x, a.y, count ? &kicked : nullptr));
+        return kicked;
+    }
+    uint64_t kick_box(Vec2 lo, Vec2 hi, uint32_t op, Vec2 a, bool count = true)
+    {
+        uint64_t kicked = 0;
+        ctx_->call(gpe_kick_box(ctx_->raw(), lo.x, lo.y, hi.x, hi.y, op, a.x, a.y, count ? &kicked : nullptr));
+        return kicked;
+    }
     size_t len() const { uint64_t n = 0; ctx_->call(gpe_len(ctx_->raw(), &n)); return n; }               // :275
     float get_max_radius() const { float r = 0; ctx_->call(gpe_max_radius(ctx_->raw(), &r)); return r; } // :291
     void sort_by_cell_id(float /*cell_size: the Grid's, state.rs:123*/) { ctx_->call(gpe_morton_resort(ctx_->raw())); }

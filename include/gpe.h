@@ -230,6 +230,67 @@ gpe_status gpe_query_circle(gpe_ctx *ctx, float x, float y, float radius, gpe_qu
 gpe_status gpe_query_box(gpe_ctx *ctx, float x0, float y0, float x1, float y1, gpe_query_result *out);
 gpe_status gpe_pick(gpe_ctx *ctx, float x, float y, gpe_query_result *out);
 
+/* ---- editing particles in place (not in the reference) --------------------------------------------------------
+ * Change particles that exist, on the device (csrc/k_edit.hip), without the download / gpe_set_particles detour that
+ * would drop the uids, the kept block table and the native counters.  Two kinds of call:
+ *
+ * Keyed edits (gpe_edit_particles): new pos, prev or radius for the k particles named by storage index or by uid --
+ * drag, throw, resize the particle gpe_pick found.
+ *  - Fields: a non-NULL array supplies element i for the particle key i names; a NULL array leaves that field of every
+ *    named particle alone.  pos_xy without prev_xy: prev = the new pos (at rest, as gpe_add_particles leaves a new
+ *    particle).  Bits are copied, no arithmetic: any float is accepted, as gpe_set_particles accepts it.
+ *  - Leaves behind, when pos or radius was edited: what gpe_set_particles(edited pos, edited prev, edited radius) would
+ *    leave, as far as a step can see -- every later step, with or without re-sorts, in either mode, is bit-identical to
+ *    that of such a fresh context.  Capacity, the native step / sort counters, the uids and the uid map are kept (the
+ *    order does not change); the scratch index arrays (GPE_HOME_CELL_IDS and friends) keep what the last call left in
+ *    them.  The native pipeline is re-derived as after a removal: the kept block table, rosters and hints are dropped,
+ *    the box check runs again -- a particle moved outside [0, world] shows up as GPE_REASON_OUT_OF_BOX, and moving it
+ *    back returns the context to the NATIVE kernels.
+ *  - radius non-NULL: gpe_max_radius is recomputed on the device over all particles (largest magnitude, last on ties,
+ *    sign kept, as after a removal), gpe_grid_max_radius is set to it and the cell size follows.  radius NULL: max
+ *    radius, the grid max radius (a gpe_grid_set_max_radius override included) and the cell size are untouched.
+ *  - Only prev_xy: nothing is re-derived; the kept block table stays in use.
+ *  - Absent uids are skipped, as in gpe_remove_particles_by_uid; edited = k minus those.  Uids are resolved through
+ *    the uid -> index map, rebuilt first if stale.
+ *  - GPE_ERR_INVALID_ARG, the context untouched: two keys naming one particle (found on the device), an index >=
+ *    gpe_len, every field array NULL, a NULL ctx / edit / keys, struct_size below sizeof(gpe_particle_edit), an unknown
+ *    key_kind.  GPE_ERR_STATE: GPE_EDIT_BY_UID while uids are off; no particles.  GPE_ERR_UNSUPPORTED: a sharded
+ *    context (gpe_shard_*, order keys or an active cell box).  k == 0: GPE_OK, nothing changes.  On any error edited = 0.
+ *  - Synchronises, like gpe_add_particles.
+ *
+ * Region velocity edits (gpe_kick_circle / gpe_kick_box): add to, set or scale the Verlet velocity pos - prev of every
+ * particle in a circle or a box -- the push, stop and damp brush.  One pass over the particles that writes prev only.
+ *  - Region: the predicate and the argument check of gpe_query_circle / gpe_query_box; a kick touches exactly the
+ *    particles the query with the same arguments returns.
+ *  - Per matching particle and component, in IEEE binary32 with one rounding per operation and no FMA (numpy float32
+ *    gives the same bits):  GPE_VEL_ADD  prev = prev - a  (a = 0 changes no bit, except that a prev of -0 becomes +0 for
+ *    a = -0);  GPE_VEL_SET  prev = pos - a  (a = 0 freezes: prev = pos exactly);  GPE_VEL_SCALE  v = pos - prev,
+ *    v = v * a, prev = pos - v.  ax acts on x, ay on y; both must be finite and op known, else GPE_ERR_INVALID_ARG.
+ *  - Leaves alone: positions, radii, uids, the uid map, the kept block table, the rosters and the counters
+ *    (gpe_get_pipeline_info's native_sorts and roster_stamp are the same before and after); nothing is re-derived.
+ *  - n_kicked == NULL: stream-ordered, no synchronisation, like gpe_step -- a host may issue one per frame between
+ *    steps.  n_kicked != NULL: the matches are counted and the call blocks to read the count.
+ *  - An empty region (radius 0 off any particle, x0 > x1) and a context without particles: GPE_OK, count 0.  Invalid
+ *    region arguments: GPE_ERR_INVALID_ARG; a sharded context: GPE_ERR_UNSUPPORTED.  On any error *n_kicked = 0. */
+enum { GPE_EDIT_BY_INDEX = 0, GPE_EDIT_BY_UID = 1 };
+typedef struct gpe_particle_edit {
+    uint32_t struct_size;      /* in: sizeof(gpe_particle_edit)                                     */
+    uint32_t key_kind;         /* in: GPE_EDIT_BY_*                                                 */
+    uint64_t k;                /* in: number of keys                                                */
+    const uint32_t *keys;      /* in: storage indices (as gpe_download(GPE_POS)) or uids            */
+    const float *pos_xy;       /* in, may be NULL: f32[2k] new positions                            */
+    const float *prev_xy;      /* in, may be NULL: f32[2k] new previous positions                   */
+    const float *radius;       /* in, may be NULL: f32[k]  new radii                                */
+    uint64_t edited;           /* out: particles written (k minus absent uids)                      */
+} gpe_particle_edit;
+gpe_status gpe_edit_particles(gpe_ctx *ctx, gpe_particle_edit *edit);
+
+enum { GPE_VEL_ADD = 0, GPE_VEL_SET = 1, GPE_VEL_SCALE = 2 };
+gpe_status gpe_kick_circle(gpe_ctx *ctx, float x, float y, float radius,
+                           uint32_t op, float ax, float ay, uint64_t *n_kicked);
+gpe_status gpe_kick_box(gpe_ctx *ctx, float x0, float y0, float x1, float y1,
+                        uint32_t op, float ax, float ay, uint64_t *n_kicked);
+
 /* ---- grid (src/grid/grid.rs) ---------------------------------------------------------------- */
 /* Grid::compute_cell_size (:159-161) */
 float gpe_compute_cell_size(float max_obj_radius);

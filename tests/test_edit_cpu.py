@@ -1,0 +1,143 @@
+"""CPU: the in-place edit entry points (gpe_edit_particles, gpe_kick_circle, gpe_kick_box) are declared by
+include/gpe.h with the documented argument lists, gpe_particle_edit agrees between the header, _lib.GpeParticleEdit and
+the Rust struct in INTEGRATION.md, libgpe.so exports them, _lib.SYMBOLS binds them, a NULL context is refused, and
+engine.py, gpe_host.hpp and INTEGRATION.md mirror them.  What they compute is checked on the device by
+tests/test_gpu_edit.py."""
+import ctypes
+import os
+import re
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HEADER = open(os.path.join(ROOT, "include", "gpe.h")).read()
+DOC = open(os.path.join(ROOT, "INTEGRATION.md")).read()
+
+VP, F, U32 = ctypes.c_void_p, ctypes.c_float, ctypes.c_uint32
+
+DECLARATIONS = {
+    "gpe_edit_particles": ["gpe_ctx *ctx", "gpe_particle_edit *edit"],
+    "gpe_kick_circle": ["gpe_ctx *ctx", "float x", "float y", "float radius", "uint32_t op", "float ax", "float ay",
+                        "uint64_t *n_kicked"],
+    "gpe_kick_box": ["gpe_ctx *ctx", "float x0", "float y0", "float x1", "float y1", "uint32_t op", "float ax", "float ay",
+                     "uint64_t *n_kicked"],
+}
+# (name, C type, pointer) in the header's order
+FIELDS = [("struct_size", "uint32_t", False), ("key_kind", "uint32_t", False), ("k", "uint64_t", False),
+          ("keys", "uint32_t", True), ("pos_xy", "float", True), ("prev_xy", "float", True), ("radius", "float", True),
+          ("edited", "uint64_t", False)]
+RUST = {"uint32_t": "u32", "uint64_t": "u64", "float": "f32"}
+CONSTANTS = {"GPE_EDIT_BY_INDEX": 0, "GPE_EDIT_BY_UID": 1, "GPE_VEL_ADD": 0, "GPE_VEL_SET": 1, "GPE_VEL_SCALE": 2}
+PY_METHODS = ("edit_particles(self, indices=None, uids=None, positions=None, previous=None, radii=None)",
+              "kick_circle(self, center, radius, op, a, count=True)", "kick_box(self, lo, hi, op, a, count=True)")
+
+
+def _strip(text):
+    return re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+
+
+def _declaration(name):
+    m = re.search(r"gpe_status\s+%s\s*\(([^;]*?)\)\s*;" % name, _strip(HEADER), flags=re.S)
+    assert m, "%s is not declared in include/gpe.h" % name
+    return [" ".join(a.split()) for a in m.group(1).split(",")]
+
+
+def _header_fields():
+    body = re.search(r"typedef struct gpe_particle_edit \{(.*?)\} gpe_particle_edit;", _strip(HEADER), flags=re.S)
+    assert body, "gpe_particle_edit is not defined in include/gpe.h"
+    out = []
+    for decl in body.group(1).split(";"):
+        decl = " ".join(decl.split())
+        if decl:
+            m = re.match(r"(const )?([a-z0-9_]+)\s*(\*?)\s*([a-z0-9_]+)$", decl)
+            assert m, decl
+            assert bool(m.group(1)) == bool(m.group(3)), decl          # the arrays are inputs: const pointers
+            out.append((m.group(4), m.group(2), bool(m.group(3))))
+    return out
+
+
+def test_header_declares_the_edit_api_argument_for_argument():
+    for name, args in DECLARATIONS.items():
+        assert _declaration(name) == args, name
+    assert re.search(r"#define\s+GPE_ABI_VERSION\s+1u", _strip(HEADER))
+    for const, value in CONSTANTS.items():
+        assert re.search(r"\b%s\s*=\s*%d\b" % (const, value), _strip(HEADER)), const
+
+
+def test_edit_struct_agrees_in_header_ctypes_and_rust(gpe):
+    assert _header_fields() == FIELDS
+    E = gpe._lib.GpeParticleEdit
+    assert [f[0] for f in E._fields_] == [f[0] for f in FIELDS]
+    assert ctypes.sizeof(E) == 56
+    offset = 0
+    for name, ctype, ptr in FIELDS:
+        width = 8 if ptr else {"uint32_t": 4, "uint64_t": 8, "float": 4}[ctype]
+        offset = (offset + width - 1) // width * width
+        assert getattr(E, name).offset == offset, name
+        assert getattr(E, name).size == width, name
+        offset += width
+    assert re.search(r"#\[repr\(C\)\]\s*pub struct gpe_particle_edit", DOC), "INTEGRATION.md lacks gpe_particle_edit"
+    body = re.search(r"pub struct gpe_particle_edit \{(.*?)\}", DOC, flags=re.S)
+    decls = [" ".join(d.split()) for d in re.sub(r"//[^\n]*", " ", body.group(1)).split(",") if d.strip()]
+    want = ["pub %s: %s%s" % (name, "*const " if ptr else "", RUST[ctype]) for name, ctype, ptr in FIELDS]
+    assert decls == want
+    for const, value in CONSTANTS.items():
+        assert re.search(r"pub const %s: u32 = %d;" % (const, value), DOC), const
+    L = gpe._lib
+    assert (L.EDIT_BY_INDEX, L.EDIT_BY_UID, L.VEL_ADD, L.VEL_SET, L.VEL_SCALE) == (0, 1, 0, 1, 2)
+
+
+def test_library_exports_and_binds_the_edit_api(gpe):
+    gpe.build()
+    lib = ctypes.CDLL(gpe._lib.LIB_PATH)
+    E = ctypes.POINTER(gpe._lib.GpeParticleEdit)
+    N = ctypes.POINTER(ctypes.c_uint64)
+    bindings = {"gpe_edit_particles": [VP, E], "gpe_kick_circle": [VP, F, F, F, U32, F, F, N],
+                "gpe_kick_box": [VP, F, F, F, F, U32, F, F, N]}
+    bound = {name: (res, args) for name, res, args in gpe._lib.SYMBOLS}
+    for name, args in bindings.items():
+        assert hasattr(lib, name), name
+        assert bound[name] == (ctypes.c_int32, args), name
+
+
+def test_null_context_is_refused(gpe):
+    gpe.build()
+    L = gpe._lib
+    lib = L.load()
+    keys = (ctypes.c_uint32 * 1)(0)
+    rows = (ctypes.c_float * 2)(1.0, 2.0)
+    e = L.GpeParticleEdit(struct_size=ctypes.sizeof(L.GpeParticleEdit), k=1, keys=keys, pos_xy=rows, edited=7)
+    assert lib.gpe_edit_particles(None, ctypes.byref(e)) == L.GPE_ERR_INVALID_ARG
+    assert lib.gpe_edit_particles(None, None) == L.GPE_ERR_INVALID_ARG
+    kicked = ctypes.c_uint64(7)
+    assert lib.gpe_kick_circle(None, 0.0, 0.0, 1.0, L.VEL_ADD, 1.0, 0.0, ctypes.byref(kicked)) == L.GPE_ERR_INVALID_ARG
+    assert lib.gpe_kick_box(None, 0.0, 0.0, 1.0, 1.0, L.VEL_SET, 0.0, 0.0, ctypes.byref(kicked)) == L.GPE_ERR_INVALID_ARG
+    assert lib.gpe_kick_circle(None, 0.0, 0.0, 1.0, L.VEL_ADD, 1.0, 0.0, None) == L.GPE_ERR_INVALID_ARG
+    assert lib.gpe_kick_box(None, 0.0, 0.0, 1.0, 1.0, L.VEL_SCALE, 0.5, 0.5, None) == L.GPE_ERR_INVALID_ARG
+
+
+def test_host_layers_mirror_the_edit_api(gpe):
+    py = open(os.path.join(ROOT, "gpu-physics-engine_amd", "engine.py")).read()
+    hpp = open(os.path.join(ROOT, "gpu-physics-engine_amd", "host", "gpe_host.hpp")).read()
+    for cls in ("ParticleSystem", "State"):
+        body = re.search(r"\nclass %s\b.*?(?=\nclass |\Z)" % cls, py, flags=re.S).group(0)
+        for m in PY_METHODS:
+            assert "def " + m in body, (cls, m)
+    for m in ("edit_particles", "kick_circle", "kick_box"):
+        assert re.search(r"\b%s\s*\(" % m, hpp), "gpe_host.hpp lacks %s" % m
+        assert re.search(r"pub fn %s\b" % m, DOC), "INTEGRATION.md shim lacks %s" % m
+        assert callable(getattr(gpe.ParticleSystem, m)) and callable(getattr(gpe.State, m))
+    block = re.search(r'extern "C" \{(.*?)\n\}', DOC, flags=re.S).group(1)
+    for name in DECLARATIONS:
+        assert "pub fn %s(" % name in block, name
+    for name in DECLARATIONS:
+        assert re.search(r"\b%s\s*\(" % name, hpp), "gpe_host.hpp never calls %s" % name
+
+
+def test_edit_workspaces_are_tagged_and_freed_with_the_particles():
+    """The edit.* buffers go through the one allocator with a tag each, and free_particle_buffers releases them."""
+    api = open(os.path.join(ROOT, "gpu-physics-engine_amd", "csrc", "gpe_api.hip")).read()
+    tags = set(re.findall(r'"(edit\.[a-z_]+)"', api))
+    assert tags == {"edit.keys", "edit.slots", "edit.fields", "edit.flag", "edit.tile_key", "edit.max_key", "edit.count"}
+    assert all(len(t) < 32 for t in tags)
+    free = re.search(r"static void free_particle_buffers\(gpe_ctx \*c\)\s*\{(.*?)\n\}", api, flags=re.S).group(1)
+    for field in ("keys", "slots", "fields", "flag", "tile_key", "max_key", "count"):
+        assert re.search(r"dev_free\(c, e\.%s\)" % field, free), field
