@@ -123,6 +123,13 @@ class GpeQueryResult(C.Structure):
                 ("prev_xy", C.POINTER(C.c_float)), ("radius", C.POINTER(C.c_float))]
 
 
+class GpeContactResult(C.Structure):
+    """gpe_contact_result: in struct_size / capacity, out count; every array pointer may be NULL (degree: u32[gpe_len])."""
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("capacity", C.c_uint64), ("count", C.c_uint64),
+                ("index_a", C.POINTER(C.c_uint32)), ("index_b", C.POINTER(C.c_uint32)), ("uid_a", C.POINTER(C.c_uint32)),
+                ("uid_b", C.POINTER(C.c_uint32)), ("overlap", C.POINTER(C.c_float)), ("degree", C.POINTER(C.c_uint32))]
+
+
 class GpeParticleEdit(C.Structure):
     """gpe_particle_edit: in struct_size / key_kind / k / keys and the field arrays (each may be NULL), out edited."""
     _fields_ = [("struct_size", C.c_uint32), ("key_kind", C.c_uint32), ("k", C.c_uint64),
@@ -172,6 +179,7 @@ SYMBOLS = [
     ("gpe_query_circle", _I32, [_VP, _F, _F, _F, C.POINTER(GpeQueryResult)]),
     ("gpe_query_box", _I32, [_VP, _F, _F, _F, _F, C.POINTER(GpeQueryResult)]),
     ("gpe_pick", _I32, [_VP, _F, _F, C.POINTER(GpeQueryResult)]),
+    ("gpe_query_contacts", _I32, [_VP, C.POINTER(GpeContactResult)]),
     ("gpe_edit_particles", _I32, [_VP, C.POINTER(GpeParticleEdit)]),
     ("gpe_kick_circle", _I32, [_VP, _F, _F, _F, _U32, _F, _F, C.POINTER(_U64)]),
     ("gpe_kick_box", _I32, [_VP, _F, _F, _F, _F, _U32, _F, _F, C.POINTER(_U64)]),

@@ -1,6 +1,7 @@
 // gpe_api.hip -- the extern "C" boundary of include/gpe.h: context, buffers, step ordering,
 // downloads, profiling.  All device work goes to one in-order hipStream per context.
 #include <math.h>
+#include <stddef.h>
 #include <stdlib.h>
 #include <string.h>
 
@@ -288,6 +289,10 @@ static void free_particle_buffers(gpe_ctx *c)
     dev_free(c, c->query_ws.tile_count); dev_free(c, c->query_ws.tile_key); dev_free(c, c->query_ws.pick);
     dev_free(c, c->query_ws.stage);
     c->query_ws.tiles_cap = c->query_ws.stage_cap = 0;
+    ContactsWorkspace &k = c->contacts_ws;
+    dev_free(c, k.keys); dev_free(c, k.vals); dev_free(c, k.rec); dev_free(c, k.degree); dev_free(c, k.upper);
+    dev_free(c, k.tile_sum); dev_free(c, k.total); dev_free(c, k.stage);
+    k.cap = k.tiles_cap = k.stage_cap = 0;
     EditWorkspace &e = c->edit_ws;
     dev_free(c, e.keys); dev_free(c, e.slots); dev_free(c, e.fields); dev_free(c, e.flag);
     dev_free(c, e.tile_key); dev_free(c, e.max_key); dev_free(c, e.count);
@@ -1412,6 +1417,138 @@ gpe_status gpe_pick(gpe_ctx *c, float x, float y, gpe_query_result *out)
         if (out->index) out->index[0] = i;
     }
     out->count = 1;
+    return GPE_OK;
+}
+
+// ---- contact queries (k_contacts.hip) ----------------------------------------------------------------------
+static gpe_status contacts_alloc(gpe_ctx *c, void **p, uint64_t payload, uint64_t slack, const char *tag)
+{
+    const hipError_t e = gpe_dev_reserve(c, p, payload, slack, tag);
+    if (e == hipErrorOutOfMemory) return fail(c, GPE_ERR_OOM, "gpe_query_contacts: out of device memory");
+    if (e != hipSuccess) return fail(c, GPE_ERR_HIP, std::string("gpe_query_contacts: ") + hipGetErrorName(e));
+    return GPE_OK;
+}
+
+static gpe_status contacts_reserve(gpe_ctx *c, uint64_t stage_bytes)
+{
+    ContactsWorkspace &ws = c->contacts_ws;
+    const uint64_t n = c->n, tiles = contacts_tiles(n);
+    if (ws.cap < n) {
+        dev_free(c, ws.keys); dev_free(c, ws.vals); dev_free(c, ws.rec); dev_free(c, ws.degree); dev_free(c, ws.upper);
+        ws.cap = 0;
+        // keys / vals: n words each.  slack: the 16 words sort_pairs' tile loads may read behind the n pairs
+        GPE_TRY(contacts_alloc(c, (void **)&ws.keys, n * sizeof(uint32_t), 16 * sizeof(uint32_t), "contacts.keys"));
+        GPE_TRY(contacts_alloc(c, (void **)&ws.vals, n * sizeof(uint32_t), 16 * sizeof(uint32_t), "contacts.vals"));
+        // rec: n 16-byte records, read one at a time below n.  no slack
+        GPE_TRY(contacts_alloc(c, (void **)&ws.rec, n * sizeof(uint4), 0, "contacts.rec"));
+        // degree: n words, written and read by index below n.  no slack
+        GPE_TRY(contacts_alloc(c, (void **)&ws.degree, n * sizeof(uint32_t), 0, "contacts.degree"));
+        // upper: n words, scanned in place.  slack: the 16 words the scan's tile loads may read behind them
+        GPE_TRY(contacts_alloc(c, (void **)&ws.upper, n * sizeof(uint32_t), 16 * sizeof(uint32_t), "contacts.upper"));
+        ws.cap = n;
+    }
+    if (ws.tiles_cap < tiles) {
+        dev_free(c, ws.tile_sum);
+        ws.tiles_cap = 0;
+        // tile_sum: one 64-bit word per workgroup of the count.  no slack
+        GPE_TRY(contacts_alloc(c, (void **)&ws.tile_sum, tiles * sizeof(unsigned long long), 0, "contacts.tile_sum"));
+        ws.tiles_cap = tiles;
+    }
+    // total: one 64-bit word.  no slack
+    if (!ws.total) GPE_TRY(contacts_alloc(c, (void **)&ws.total, sizeof(unsigned long long), 0, "contacts.total"));
+    if (ws.stage_cap < stage_bytes) {
+        dev_free(c, ws.stage);
+        ws.stage_cap = 0;
+        // stage: the 256-byte aligned parts of the requested per-pair arrays, written below capacity.  no slack
+        GPE_TRY(contacts_alloc(c, (void **)&ws.stage, stage_bytes, 0, "contacts.stage"));
+        ws.stage_cap = stage_bytes;
+    }
+    GPE_TRY(sort_reserve(c, n));
+    return scan_reserve(c, n);
+}
+
+gpe_status gpe_query_contacts(gpe_ctx *c, gpe_contact_result *out)
+{
+    const char *who = "gpe_query_contacts";
+    if (!c) return GPE_ERR_INVALID_ARG;
+    if (!out) return fail(c, GPE_ERR_INVALID_ARG, std::string(who) + ": NULL result");
+    if (out->struct_size < sizeof(gpe_contact_result)) {
+        if (out->struct_size >= offsetof(gpe_contact_result, count) + sizeof(out->count)) out->count = 0;   // it has one
+        return fail(c, GPE_ERR_INVALID_ARG, std::string(who) + ": struct_size is smaller than gpe_contact_result");
+    }
+    out->count = 0;
+    if (is_sharded(c))
+        return fail(c, GPE_ERR_UNSUPPORTED, std::string(who) + ": not supported on a sharded context (gpe_shard_*, "
+                                                                "order keys or an active cell box)");
+    if ((out->uid_a || out->uid_b) && !c->uid.on)
+        return fail(c, GPE_ERR_STATE, std::string(who) + ": uid requested while uids are off");
+    if (c->n > 0xFFFFFFFFull) return fail(c, GPE_ERR_UNSUPPORTED, std::string(who) + ": more than 2^32 - 1 particles");
+    const uint64_t n = c->n;
+    if (n == 0 || !c->pos) return GPE_OK;
+    // the query's own cell size: a contact implies a centre distance below 2 max|r|, less than one cell of 2.2 max|r|
+    const float cell_size = gpe_compute_cell_size(fabsf(c->max_radius));
+    if (n > 1 && !isfinite(cell_size))
+        return fail(c, GPE_ERR_UNSUPPORTED, std::string(who) + ": the largest radius is not finite");
+    if (n == 1 || cell_size == 0.0f) {                             // one particle, or every radius 0: nothing touches
+        if (out->degree) std::fill(out->degree, out->degree + n, 0u);
+        return GPE_OK;
+    }
+    const bool want_pairs = out->index_a || out->index_b || out->uid_a || out->uid_b || out->overlap;
+    GPE_HIP(c, hipSetDevice(c->device));
+    GPE_HIP(c, hipStreamSynchronize(c->stream));
+    GPE_TRY(contacts_reserve(c, 0));
+    ContactsWorkspace &ws = c->contacts_ws;
+    unsigned long long total = 0;
+    Scope s(c, "Query contacts");
+    {
+        Scope k(c, "contacts/keys");
+        GPE_TRY(launch_contacts_keys(c, cell_size, ws.keys, ws.vals));
+    }
+    {
+        Scope k(c, "contacts/sort");
+        GPE_TRY(sort_pairs(c, ws.keys, ws.vals, n));
+        GPE_TRY(launch_contacts_records(c, ws.vals, ws.rec));
+    }
+    {
+        Scope k(c, "contacts/count");
+        GPE_TRY(launch_contacts_count(c, ws.keys, ws.rec, ws.degree, ws.upper, ws.tile_sum, ws.total));
+    }
+    GPE_HIP(c, hipMemcpyAsync(&total, ws.total, sizeof(total), hipMemcpyDeviceToHost, c->stream));
+    if (out->degree) GPE_HIP(c, hipMemcpyAsync(out->degree, ws.degree, n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    GPE_HIP(c, hipStreamSynchronize(c->stream));
+    if (want_pairs && total > 0xFFFFFFFFull) {                    // the one error that leaves count (and degree) set
+        out->count = total;
+        return fail(c, GPE_ERR_UNSUPPORTED, std::string(who) + ": more than 2^32 - 1 contacts cannot be listed");
+    }
+    const uint64_t m = std::min<uint64_t>(total, out->capacity);
+    if (m > 0 && want_pairs) {
+        // staging, 256-byte aligned parts, only the requested arrays: index_a | index_b | uid_a | uid_b | overlap
+        auto part = [m](bool on) { return on ? (m * 4 + 255) / 256 * 256 : 0; };
+        const uint64_t o_b = part(out->index_a), o_ua = o_b + part(out->index_b), o_ub = o_ua + part(out->uid_a),
+                       o_ov = o_ub + part(out->uid_b), bytes = o_ov + part(out->overlap);
+        GPE_TRY(contacts_reserve(c, bytes));
+        uint8_t *st = ws.stage;
+        uint32_t *d_a = out->index_a ? reinterpret_cast<uint32_t *>(st) : nullptr;
+        uint32_t *d_b = out->index_b ? reinterpret_cast<uint32_t *>(st + o_b) : nullptr;
+        uint32_t *d_ua = out->uid_a ? reinterpret_cast<uint32_t *>(st + o_ua) : nullptr;
+        uint32_t *d_ub = out->uid_b ? reinterpret_cast<uint32_t *>(st + o_ub) : nullptr;
+        float *d_ov = out->overlap ? reinterpret_cast<float *>(st + o_ov) : nullptr;
+        {
+            Scope k(c, "contacts/scan");
+            GPE_TRY(inclusive_scan(c, ws.upper, n));
+        }
+        {
+            Scope k(c, "contacts/gather");
+            GPE_TRY(launch_contacts_gather(c, ws.keys, ws.rec, ws.upper, (uint32_t)m, d_a, d_b, d_ua, d_ub, d_ov));
+        }
+        if (d_a) GPE_HIP(c, hipMemcpyAsync(out->index_a, d_a, m * 4, hipMemcpyDeviceToHost, c->stream));
+        if (d_b) GPE_HIP(c, hipMemcpyAsync(out->index_b, d_b, m * 4, hipMemcpyDeviceToHost, c->stream));
+        if (d_ua) GPE_HIP(c, hipMemcpyAsync(out->uid_a, d_ua, m * 4, hipMemcpyDeviceToHost, c->stream));
+        if (d_ub) GPE_HIP(c, hipMemcpyAsync(out->uid_b, d_ub, m * 4, hipMemcpyDeviceToHost, c->stream));
+        if (d_ov) GPE_HIP(c, hipMemcpyAsync(out->overlap, d_ov, m * 4, hipMemcpyDeviceToHost, c->stream));
+        GPE_HIP(c, hipStreamSynchronize(c->stream));
+    }
+    out->count = total;
     return GPE_OK;
 }
 

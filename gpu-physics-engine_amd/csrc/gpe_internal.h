@@ -278,6 +278,19 @@ struct QueryWorkspace {          // gpe_query_* / gpe_pick (k_query.hip); alloca
     uint64_t stage_cap = 0;                      // bytes
 };
 
+struct ContactsWorkspace {       // gpe_query_contacts (k_contacts.hip); allocated at first use, freed with the particles
+    uint32_t *keys = nullptr, *vals = nullptr;   // clamped cell key and storage index per particle, sorted by the key
+    uint4 *rec = nullptr;                        // per sorted slot: bits of x, y, radius and the storage index
+    uint32_t *degree = nullptr;                  // per particle: its contacts
+    uint32_t *upper = nullptr;                   // per particle: its contacts of higher index, scanned in place
+    uint64_t cap = 0;                            // particles the five arrays above hold
+    unsigned long long *tile_sum = nullptr;      // per workgroup of the count: the sum of its `upper`
+    uint64_t tiles_cap = 0;
+    unsigned long long *total = nullptr;         // the number of contacts
+    uint8_t *stage = nullptr;                    // the gathered rows of the requested per-pair arrays
+    uint64_t stage_cap = 0;                      // bytes
+};
+
 struct EditWorkspace {           // gpe_edit_particles / gpe_kick_* (k_edit.hip); allocated at first use, freed with the particles
     uint32_t *keys = nullptr;                    // the caller's keys, resolved to storage indices in place, then sorted
     uint32_t *slots = nullptr;                   // each key's position in the caller's arrays, sorted with it
@@ -646,6 +659,7 @@ struct gpe_ctx {
     gpe::RemoveWorkspace remove_ws;
     gpe::UidState uid;
     gpe::QueryWorkspace query_ws;
+    gpe::ContactsWorkspace contacts_ws;
     gpe::EditWorkspace edit_ws;
     gpe::ScanWorkspace scan_ws;
     gpe::OnesweepWorkspace os_ws;
@@ -787,6 +801,18 @@ gpe_status launch_query_gather(gpe_ctx *c, bool box, const float *region, const 
                                float2 *prev_out, float *radius_out);
 // *pick = min over the particles whose disc contains (x, y) of bits(d2) << 32 | index (~0 for none)
 gpe_status launch_pick(gpe_ctx *c, float x, float y, unsigned long long *tile_key, unsigned long long *pick);
+// contact queries (k_contacts.hip): keys[i] = the clamped cell of particle i under cell_size, vals[i] = i
+uint64_t contacts_tiles(uint64_t n);
+gpe_status launch_contacts_keys(gpe_ctx *c, float cell_size, uint32_t *keys, uint32_t *vals);
+// rec[t] = the particle vals[t] (vals: sorted by key)
+gpe_status launch_contacts_records(gpe_ctx *c, const uint32_t *vals, uint4 *rec);
+// degree[i], upper[i] = contacts of particle i / those of higher index; *total = the sum of upper (tile_sum: contacts_tiles(n))
+gpe_status launch_contacts_count(gpe_ctx *c, const uint32_t *keys, const uint4 *rec, uint32_t *degree, uint32_t *upper,
+                                 unsigned long long *tile_sum, unsigned long long *total);
+// the pairs ranked below capacity into the non-NULL outputs (scanned: inclusive scan of upper; uid_*: from c->uid.uids)
+gpe_status launch_contacts_gather(gpe_ctx *c, const uint32_t *keys, const uint4 *rec, const uint32_t *scanned,
+                                  uint32_t capacity, uint32_t *index_a, uint32_t *index_b, uint32_t *uid_a, uint32_t *uid_b,
+                                  float *overlap);
 // in-place edits (k_edit.hip).  Keyed edits: keys[i] becomes the storage index key i names (by_uid: looked up in the
 // sorted uid map of n entries; GPE_UID_ABSENT for an absent uid or an index >= n, the latter also sets kEditBadIndex in
 // flag[0]), slots[i] = i, flag[1] += the keys that name a particle.  flag zeroed by the caller.

@@ -31,6 +31,9 @@ def _ptr(a):
 
 # gpe_query_circle / gpe_query_box / gpe_pick: every match, ascending storage index (uid None while uids are off)
 QueryResult = collections.namedtuple("QueryResult", "index uid pos prev radius")
+# gpe_query_contacts: the touching pairs (a < b), ascending by a then b (uid_a / uid_b None while uids are off, overlap
+# None unless asked for)
+ContactResult = collections.namedtuple("ContactResult", "a b uid_a uid_b overlap")
 
 
 class Context:
@@ -420,6 +423,46 @@ class ParticleSystem:
         """gpe_query_box with no outputs: the number of particles query_box would return."""
         return self._count("gpe_query_box", (float(lo[0]), float(lo[1]), float(hi[0]), float(hi[1])))
 
+    # Contact queries (not in the reference; include/gpe.h): which particles touch -- dx*dx + dy*dy < (ri + rj)^2 in
+    # float32 -- and how many neighbours each one has, searched on the device.  The context is left exactly as it was.
+    def contacts(self, capacity=None, overlap=False):
+        """gpe_query_contacts -> ContactResult(a, b, uid_a, uid_b, overlap): the touching pairs, a < b, ascending by a
+        then b; at most `capacity` of them, all of them with capacity=None (one counting call first).  overlap=True
+        adds the penetration depths (ri + rj) - sqrt(dx*dx + dy*dy) in float32."""
+        with_uids = self._uids_on()
+        cap = self.count_contacts() if capacity is None else int(capacity)
+        room = max(cap, 1)
+        u32 = C.POINTER(C.c_uint32)
+        a, b = np.empty(room, np.uint32), np.empty(room, np.uint32)
+        ua = np.empty(room, np.uint32) if with_uids else None
+        ub = np.empty(room, np.uint32) if with_uids else None
+        ov = np.empty(room, np.float32) if overlap else None
+        res = L.GpeContactResult(struct_size=C.sizeof(L.GpeContactResult), capacity=cap)
+        res.index_a, res.index_b = a.ctypes.data_as(u32), b.ctypes.data_as(u32)
+        if with_uids:
+            res.uid_a, res.uid_b = ua.ctypes.data_as(u32), ub.ctypes.data_as(u32)
+        if overlap:
+            res.overlap = ov.ctypes.data_as(C.POINTER(C.c_float))
+        self.ctx.call("gpe_query_contacts", C.byref(res))
+        k = min(res.count, cap)
+        return ContactResult(a[:k], b[:k], ua[:k] if with_uids else None, ub[:k] if with_uids else None,
+                             ov[:k] if overlap else None)
+
+    def count_contacts(self):
+        """gpe_query_contacts with no outputs: the number of touching pairs (exact; may exceed 2^32)."""
+        res = L.GpeContactResult(struct_size=C.sizeof(L.GpeContactResult), capacity=0)
+        self.ctx.call("gpe_query_contacts", C.byref(res))
+        return res.count
+
+    def contact_degrees(self):
+        """gpe_query_contacts with the degree array only: u32[len], the number of particles touching each one."""
+        n = self.len()
+        deg = np.zeros(max(n, 1), np.uint32)
+        res = L.GpeContactResult(struct_size=C.sizeof(L.GpeContactResult), capacity=0)
+        res.degree = deg.ctypes.data_as(C.POINTER(C.c_uint32))
+        self.ctx.call("gpe_query_contacts", C.byref(res))
+        return deg[:n]
+
     # Editing particles in place (not in the reference; include/gpe.h): new pos / prev / radius for particles named by
     # storage index or by uid, and velocity kicks of every particle in a circle or a box -- all on the device, the
     # uids, the order and the native counters kept.
@@ -695,6 +738,18 @@ class State:
     def pick(self, point):
         """ParticleSystem.pick -> QueryResult of one particle, or None."""
         return self.particles.pick(point)
+
+    def contacts(self, capacity=None, overlap=False):
+        """ParticleSystem.contacts -> ContactResult(a, b, uid_a, uid_b, overlap) of the touching pairs."""
+        return self.particles.contacts(capacity, overlap)
+
+    def count_contacts(self):
+        """ParticleSystem.count_contacts -> the number of touching pairs."""
+        return self.particles.count_contacts()
+
+    def contact_degrees(self):
+        """ParticleSystem.contact_degrees -> u32[len], the contacts of every particle."""
+        return self.particles.contact_degrees()
 
     def count_circle(self, center, radius):
         return self.particles.count_circle(center, radius)

@@ -255,6 +255,56 @@ class ParticleSystem {
         ctx_->call(gpe_query_box(ctx_->raw(), lo.x, lo.y, hi.x, hi.y, &r));
         return r.count;
     }
+    // not in the reference: which particles touch -- dx*dx + dy*dy < (ri + rj)^2 in binary32 -- and how many neighbours
+    // each one has (include/gpe.h), searched on the device.  contacts(): the pairs (a < b), ascending by a then b, at most
+    // `capacity` of them (0: all, after one counting call); uid_a / uid_b stay empty while uids are off.
+    struct ContactResult {
+        std::vector<uint32_t> a, b, uid_a, uid_b;
+        std::vector<float> overlap;
+    };
+    ContactResult contacts(uint64_t capacity = 0) const
+    {
+        uint64_t next = 0;
+        const bool with_uids = gpe_next_uid(ctx_->raw(), &next) == GPE_OK;
+        const uint64_t cap = capacity ? capacity : count_contacts();
+        const uint64_t room = std::max<uint64_t>(cap, 1);
+        ContactResult q;
+        q.a.resize(room);
+        q.b.resize(room);
+        q.uid_a.resize(with_uids ? room : 0);
+        q.uid_b.resize(with_uids ? room : 0);
+        q.overlap.resize(room);
+        gpe_contact_result r = empty_contacts();
+        r.capacity = cap;
+        r.index_a = q.a.data();
+        r.index_b = q.b.data();
+        r.uid_a = with_uids ? q.uid_a.data() : nullptr;
+        r.uid_b = with_uids ? q.uid_b.data() : nullptr;
+        r.overlap = q.overlap.data();
+        ctx_->call(gpe_query_contacts(ctx_->raw(), &r));
+        const uint64_t k = std::min<uint64_t>(r.count, cap);
+        q.a.resize(k);
+        q.b.resize(k);
+        q.uid_a.resize(with_uids ? k : 0);
+        q.uid_b.resize(with_uids ? k : 0);
+        q.overlap.resize(k);
+        return q;
+    }
+    uint64_t count_contacts() const
+    {
+        gpe_contact_result r = empty_contacts();
+        ctx_->call(gpe_query_contacts(ctx_->raw(), &r));
+        return r.count;
+    }
+    std::vector<uint32_t> contact_degrees() const
+    {
+        std::vector<uint32_t> degree(len());
+        uint32_t none = 0;
+        gpe_contact_result r = empty_contacts();
+        r.degree = degree.empty() ? &none : degree.data();
+        ctx_->call(gpe_query_contacts(ctx_->raw(), &r));
+        return degree;
+    }
     // not in the reference: edit particles in place on the device (include/gpe.h).  The particles named by `keys` --
     // storage indices, or uids with by_uid -- take row i of every array given (NULL: that field stays; positions without
     // previous: at rest, prev = pos).  Unknown uids are skipped.  Returns the number of particles written.
@@ -327,6 +377,12 @@ class ParticleSystem {
     {
         gpe_query_result r{};
         r.struct_size = sizeof(gpe_query_result);
+        return r;
+    }
+    static gpe_contact_result empty_contacts()
+    {
+        gpe_contact_result r{};
+        r.struct_size = sizeof(gpe_contact_result);
         return r;
     }
     // one call with `capacity` rows, a second with capacity = count only if the first ran over

@@ -230,6 +230,58 @@ gpe_status gpe_query_circle(gpe_ctx *ctx, float x, float y, float radius, gpe_qu
 gpe_status gpe_query_box(gpe_ctx *ctx, float x0, float y0, float x1, float y1, gpe_query_result *out);
 gpe_status gpe_pick(gpe_ctx *ctx, float x, float y, gpe_query_result *out);
 
+/* ---- contact queries (not in the reference) ------------------------------------------------------------------
+ * Which particles are touching right now, and how many neighbours each one has, without downloading positions and
+ * radii for a neighbour search on the host: a cell-binned search on the device (csrc/k_contacts.hip) in scratch of
+ * its own.
+ *  - Contact predicate: particles i != j are in contact when dx*dx + dy*dy < (ri + rj)*(ri + rj), dx = xi - xj,
+ *    dy = yi - yj, in IEEE binary32, one rounding per operation, left to right, no FMA (numpy float32 gives the same
+ *    answer).  Radii are taken as stored (a negative radius enters the sum with its sign).  This is are_colliding of
+ *    collision_solver.wgsl:60-64 on the squared distance itself.  It is symmetric in i and j, because the squares of
+ *    negated differences are equal.  Coincident centres are a contact when the radius sum is non-zero.  A NaN anywhere
+ *    makes the comparison false.  This is the geometric predicate, not the step's: the step squares a rounded square
+ *    root and skips distance <= 1e-4, so the two may differ at those two edges.
+ *  - overlap = (ri + rj) - sqrtf(dx*dx + dy*dy), the square root correctly rounded: the penetration depth, the bits
+ *    numpy float32 gives.
+ *  - degree[i] = the number of j in contact with i.  The array always has gpe_len entries, whatever capacity is.
+ *  - count = the number of unordered pairs = sum(degree) / 2, summed in 64 bits.
+ *  - Pairs are ordered ascending by index_a, then ascending by index_b (index_a < index_b).  The first
+ *    min(count, capacity) pairs go into every non-NULL per-pair array, all arrays filled from the same pairs; host
+ *    memory past those entries is left untouched.  With every array NULL the call only counts.
+ *  - More than 2^32 - 1 contacts cannot be listed (the 32-bit scan cannot rank them): when a per-pair array is requested
+ *    and count > 0xFFFFFFFF the call returns GPE_ERR_UNSUPPORTED and writes no per-pair array.  This is the one error
+ *    that leaves count set; degree is delivered too.
+ *  - The search uses a cell size of its own, gpe_compute_cell_size(|gpe_max_radius|): a gpe_grid_set_max_radius
+ *    override changes nothing about the result.  A contact implies a centre distance below 2 max|r|, so the 3 x 3 cell
+ *    neighbourhood is complete.  (gpe_max_radius bounds every |radius| after set / remove / edit; gpe_add_particles
+ *    keeps max(max_radius, r) as the reference does, so it does too unless a negative radius of larger magnitude was
+ *    added.)  That cell size not finite (an infinite radius): GPE_ERR_UNSUPPORTED.  0 (every radius 0): GPE_OK, count
+ *    0, every degree 0.
+ *  - Positions may be anything gpe_set_particles accepts -- outside the world, negative, 1e30, +-inf, NaN: the result
+ *    is exactly the predicate's, and the search never reads or writes out of bounds for them.
+ *  - The query changes nothing on the context: positions, prev, radii, uids, the uid map, GPE_HOME_CELL_IDS and the
+ *    other scratch index arrays, the native step / sort counters, the kept block table and the rosters are left alone;
+ *    the steps after a query are bit-identical to those of a context that was never queried.  It works in both modes
+ *    and at any point between steps, and blocks like gpe_download.
+ *  - Errors: a NULL context, a NULL out or a struct_size below sizeof(gpe_contact_result): GPE_ERR_INVALID_ARG; a uid
+ *    array while uids are off: GPE_ERR_STATE; a sharded context (gpe_shard_*, order keys or an active cell box) and
+ *    more than 2^32 - 1 particles: GPE_ERR_UNSUPPORTED.  On these errors count is 0 (when out is usable) and nothing is
+ *    written.
+ *  - No particles, or one particle: GPE_OK, count 0. */
+typedef struct gpe_contact_result {
+    uint32_t struct_size;   /* in: sizeof(gpe_contact_result)                                   */
+    uint32_t reserved;      /* in: 0                                                            */
+    uint64_t capacity;      /* in: pairs each non-NULL per-pair array has room for              */
+    uint64_t count;         /* out: number of contacts (exact, may exceed capacity and 2^32)    */
+    uint32_t *index_a;      /* out, may be NULL: storage index of the lower particle            */
+    uint32_t *index_b;      /* out, may be NULL: storage index of the higher particle (a < b)   */
+    uint32_t *uid_a;        /* out, may be NULL: their uids; non-NULL while uids are off:       */
+    uint32_t *uid_b;        /*                   GPE_ERR_STATE                                  */
+    float    *overlap;      /* out, may be NULL: f32[capacity] penetration depth                */
+    uint32_t *degree;       /* out, may be NULL: u32[gpe_len] contacts of every particle        */
+} gpe_contact_result;       /* 72 bytes */
+gpe_status gpe_query_contacts(gpe_ctx *ctx, gpe_contact_result *out);
+
 /* ---- editing particles in place (not in the reference) --------------------------------------------------------
  * Change particles that exist, on the device (csrc/k_edit.hip), without the download / gpe_set_particles detour that
  * would drop the uids, the kept block table and the native counters.  Two kinds of call:
