@@ -40,6 +40,7 @@ POS, PREV, RADIUS, HOME_CELL_IDS, PARTICLE_IDS, CELL_IDS, OBJECT_IDS, COLLISION_
     NUM_COLLISION_CELLS, CHUNK_OBJ_COUNT, INDIRECT_ARGS, ORDER_KEYS, UIDS = range(13)
 UID_ABSENT = 0xFFFFFFFF
 EDIT_BY_INDEX, EDIT_BY_UID = 0, 1
+CLUSTER_BY_INDEX, CLUSTER_BY_UID = 0, 1
 VEL_ADD, VEL_SET, VEL_SCALE = 0, 1, 2
 
 
@@ -130,6 +131,14 @@ class GpeContactResult(C.Structure):
                 ("uid_b", C.POINTER(C.c_uint32)), ("overlap", C.POINTER(C.c_float)), ("degree", C.POINTER(C.c_uint32))]
 
 
+class GpeClusterResult(C.Structure):
+    """gpe_cluster_result: in struct_size, out count / largest_size / largest_label; every array pointer may be NULL
+    (each u32[gpe_len])."""
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("count", C.c_uint64),
+                ("largest_size", C.c_uint32), ("largest_label", C.c_uint32), ("label", C.POINTER(C.c_uint32)),
+                ("size", C.POINTER(C.c_uint32)), ("label_uid", C.POINTER(C.c_uint32))]
+
+
 class GpeParticleEdit(C.Structure):
     """gpe_particle_edit: in struct_size / key_kind / k / keys and the field arrays (each may be NULL), out edited."""
     _fields_ = [("struct_size", C.c_uint32), ("key_kind", C.c_uint32), ("k", C.c_uint64),
@@ -180,6 +189,8 @@ SYMBOLS = [
     ("gpe_query_box", _I32, [_VP, _F, _F, _F, _F, C.POINTER(GpeQueryResult)]),
     ("gpe_pick", _I32, [_VP, _F, _F, C.POINTER(GpeQueryResult)]),
     ("gpe_query_contacts", _I32, [_VP, C.POINTER(GpeContactResult)]),
+    ("gpe_query_clusters", _I32, [_VP, C.POINTER(GpeClusterResult)]),
+    ("gpe_query_cluster_of", _I32, [_VP, _U32, _U32, C.POINTER(GpeQueryResult)]),
     ("gpe_edit_particles", _I32, [_VP, C.POINTER(GpeParticleEdit)]),
     ("gpe_kick_circle", _I32, [_VP, _F, _F, _F, _U32, _F, _F, C.POINTER(_U64)]),
     ("gpe_kick_box", _I32, [_VP, _F, _F, _F, _F, _U32, _F, _F, C.POINTER(_U64)]),

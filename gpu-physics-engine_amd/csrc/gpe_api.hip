@@ -6,6 +6,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <functional>
 #include <mutex>
 
 #include "gpe_internal.h"
@@ -293,6 +294,10 @@ static void free_particle_buffers(gpe_ctx *c)
     dev_free(c, k.keys); dev_free(c, k.vals); dev_free(c, k.rec); dev_free(c, k.degree); dev_free(c, k.upper);
     dev_free(c, k.tile_sum); dev_free(c, k.total); dev_free(c, k.stage);
     k.cap = k.tiles_cap = k.stage_cap = 0;
+    ClustersWorkspace &u = c->clusters_ws;
+    dev_free(c, u.parent); dev_free(c, u.label); dev_free(c, u.root_size); dev_free(c, u.size);
+    dev_free(c, u.tile_word); dev_free(c, u.words);
+    u.cap = u.tiles_cap = 0;
     EditWorkspace &e = c->edit_ws;
     dev_free(c, e.keys); dev_free(c, e.slots); dev_free(c, e.fields); dev_free(c, e.flag);
     dev_free(c, e.tile_key); dev_free(c, e.max_key); dev_free(c, e.count);
@@ -1295,6 +1300,42 @@ static gpe_status query_begin(gpe_ctx *c, gpe_query_result *out, const char *who
     return GPE_OK;
 }
 
+// The first min(total, capacity) rows of a selection into the requested arrays of `out`, and out->count = total.
+// gather(m, index, uid, pos, prev, radius) launches the kernel that fills the staging parts (NULL: not requested).
+using QueryGather = std::function<gpe_status(uint32_t, uint32_t *, uint32_t *, float2 *, float2 *, float *)>;
+static gpe_status query_deliver(gpe_ctx *c, gpe_query_result *out, uint32_t total, const char *scope,
+                                const QueryGather &gather)
+{
+    QueryWorkspace &ws = c->query_ws;
+    const uint64_t m = std::min<uint64_t>(total, out->capacity);
+    if (m > 0 && query_wants_rows(out)) {
+        // staging, 256-byte aligned parts, only the requested fields: pos | prev | radius | index | uid
+        auto part = [m](bool on, uint64_t width) { return on ? (m * width + 255) / 256 * 256 : 0; };
+        const uint64_t o_prev = part(out->pos_xy, 8), o_radius = o_prev + part(out->prev_xy, 8),
+                       o_index = o_radius + part(out->radius, 4), o_uid = o_index + part(out->index, 4),
+                       bytes = o_uid + part(out->uid, 4);
+        GPE_TRY(query_reserve(c, bytes));
+        uint8_t *st = ws.stage;
+        float2 *d_pos = out->pos_xy ? reinterpret_cast<float2 *>(st) : nullptr;
+        float2 *d_prev = out->prev_xy ? reinterpret_cast<float2 *>(st + o_prev) : nullptr;
+        float *d_radius = out->radius ? reinterpret_cast<float *>(st + o_radius) : nullptr;
+        uint32_t *d_index = out->index ? reinterpret_cast<uint32_t *>(st + o_index) : nullptr;
+        uint32_t *d_uid = out->uid ? reinterpret_cast<uint32_t *>(st + o_uid) : nullptr;
+        {
+            Scope k(c, scope);
+            GPE_TRY(gather((uint32_t)m, d_index, d_uid, d_pos, d_prev, d_radius));
+        }
+        if (d_index) GPE_HIP(c, hipMemcpyAsync(out->index, d_index, m * 4, hipMemcpyDeviceToHost, c->stream));
+        if (d_uid) GPE_HIP(c, hipMemcpyAsync(out->uid, d_uid, m * 4, hipMemcpyDeviceToHost, c->stream));
+        if (d_pos) GPE_HIP(c, hipMemcpyAsync(out->pos_xy, d_pos, m * 8, hipMemcpyDeviceToHost, c->stream));
+        if (d_prev) GPE_HIP(c, hipMemcpyAsync(out->prev_xy, d_prev, m * 8, hipMemcpyDeviceToHost, c->stream));
+        if (d_radius) GPE_HIP(c, hipMemcpyAsync(out->radius, d_radius, m * 4, hipMemcpyDeviceToHost, c->stream));
+        GPE_HIP(c, hipStreamSynchronize(c->stream));
+    }
+    out->count = total;
+    return GPE_OK;
+}
+
 // Count (and, for requested rows, gather) the particles in the region; region as launch_query_count takes it.
 static gpe_status do_query(gpe_ctx *c, bool box, const float *region, gpe_query_result *out)
 {
@@ -1315,34 +1356,11 @@ static gpe_status do_query(gpe_ctx *c, bool box, const float *region, gpe_query_
     }
     GPE_HIP(c, hipMemcpyAsync(&total, ws.tile_count + (tiles - 1), sizeof(total), hipMemcpyDeviceToHost, c->stream));
     GPE_HIP(c, hipStreamSynchronize(c->stream));
-    const uint64_t m = std::min<uint64_t>(total, out->capacity);
-    if (m > 0 && query_wants_rows(out)) {
-        // staging, 256-byte aligned parts, only the requested fields: pos | prev | radius | index | uid
-        auto part = [m](bool on, uint64_t width) { return on ? (m * width + 255) / 256 * 256 : 0; };
-        const uint64_t o_prev = part(out->pos_xy, 8), o_radius = o_prev + part(out->prev_xy, 8),
-                       o_index = o_radius + part(out->radius, 4), o_uid = o_index + part(out->index, 4),
-                       bytes = o_uid + part(out->uid, 4);
-        GPE_TRY(query_reserve(c, bytes));
-        uint8_t *st = ws.stage;
-        float2 *d_pos = out->pos_xy ? reinterpret_cast<float2 *>(st) : nullptr;
-        float2 *d_prev = out->prev_xy ? reinterpret_cast<float2 *>(st + o_prev) : nullptr;
-        float *d_radius = out->radius ? reinterpret_cast<float *>(st + o_radius) : nullptr;
-        uint32_t *d_index = out->index ? reinterpret_cast<uint32_t *>(st + o_index) : nullptr;
-        uint32_t *d_uid = out->uid ? reinterpret_cast<uint32_t *>(st + o_uid) : nullptr;
-        {
-            Scope k(c, "query/gather");
-            GPE_TRY(launch_query_gather(c, box, region, ws.tile_count, (uint32_t)m, d_index, d_uid, d_pos, d_prev,
-                                        d_radius));
-        }
-        if (d_index) GPE_HIP(c, hipMemcpyAsync(out->index, d_index, m * 4, hipMemcpyDeviceToHost, c->stream));
-        if (d_uid) GPE_HIP(c, hipMemcpyAsync(out->uid, d_uid, m * 4, hipMemcpyDeviceToHost, c->stream));
-        if (d_pos) GPE_HIP(c, hipMemcpyAsync(out->pos_xy, d_pos, m * 8, hipMemcpyDeviceToHost, c->stream));
-        if (d_prev) GPE_HIP(c, hipMemcpyAsync(out->prev_xy, d_prev, m * 8, hipMemcpyDeviceToHost, c->stream));
-        if (d_radius) GPE_HIP(c, hipMemcpyAsync(out->radius, d_radius, m * 4, hipMemcpyDeviceToHost, c->stream));
-        GPE_HIP(c, hipStreamSynchronize(c->stream));
-    }
-    out->count = total;
-    return GPE_OK;
+    return query_deliver(c, out, total, "query/gather",
+                         [&](uint32_t m, uint32_t *d_index, uint32_t *d_uid, float2 *d_pos, float2 *d_prev, float *d_radius) {
+                             return launch_query_gather(c, box, region, c->query_ws.tile_count, m, d_index, d_uid, d_pos,
+                                                        d_prev, d_radius);
+                         });
 }
 
 // The argument checks and the region words (as launch_query_count takes them) of the circle and box calls: the
@@ -1467,6 +1485,25 @@ static gpe_status contacts_reserve(gpe_ctx *c, uint64_t stage_bytes)
     return scan_reserve(c, n);
 }
 
+// Stages (1) and (2) of the contact query, shared with the cluster query: the workspace, the cell keys under
+// `cell_size`, the sort and the 16-byte records.  Leaves contacts_ws.keys / .rec sorted by cell.  Call inside the
+// query's own scope, after the stream is idle.
+static gpe_status contacts_bin(gpe_ctx *c, float cell_size)
+{
+    GPE_TRY(contacts_reserve(c, 0));
+    ContactsWorkspace &ws = c->contacts_ws;
+    {
+        Scope k(c, "contacts/keys");
+        GPE_TRY(launch_contacts_keys(c, cell_size, ws.keys, ws.vals));
+    }
+    {
+        Scope k(c, "contacts/sort");
+        GPE_TRY(sort_pairs(c, ws.keys, ws.vals, c->n));
+        GPE_TRY(launch_contacts_records(c, ws.vals, ws.rec));
+    }
+    return GPE_OK;
+}
+
 gpe_status gpe_query_contacts(gpe_ctx *c, gpe_contact_result *out)
 {
     const char *who = "gpe_query_contacts";
@@ -1496,19 +1533,10 @@ gpe_status gpe_query_contacts(gpe_ctx *c, gpe_contact_result *out)
     const bool want_pairs = out->index_a || out->index_b || out->uid_a || out->uid_b || out->overlap;
     GPE_HIP(c, hipSetDevice(c->device));
     GPE_HIP(c, hipStreamSynchronize(c->stream));
-    GPE_TRY(contacts_reserve(c, 0));
     ContactsWorkspace &ws = c->contacts_ws;
     unsigned long long total = 0;
     Scope s(c, "Query contacts");
-    {
-        Scope k(c, "contacts/keys");
-        GPE_TRY(launch_contacts_keys(c, cell_size, ws.keys, ws.vals));
-    }
-    {
-        Scope k(c, "contacts/sort");
-        GPE_TRY(sort_pairs(c, ws.keys, ws.vals, n));
-        GPE_TRY(launch_contacts_records(c, ws.vals, ws.rec));
-    }
+    GPE_TRY(contacts_bin(c, cell_size));
     {
         Scope k(c, "contacts/count");
         GPE_TRY(launch_contacts_count(c, ws.keys, ws.rec, ws.degree, ws.upper, ws.tile_sum, ws.total));
@@ -1550,6 +1578,200 @@ gpe_status gpe_query_contacts(gpe_ctx *c, gpe_contact_result *out)
     }
     out->count = total;
     return GPE_OK;
+}
+
+// ---- contact clusters (k_clusters.hip) ---------------------------------------------------------------------
+static gpe_status clusters_alloc(gpe_ctx *c, void **p, uint64_t payload, const char *tag)
+{
+    const hipError_t e = gpe_dev_reserve(c, p, payload, 0, tag);
+    if (e == hipErrorOutOfMemory) return fail(c, GPE_ERR_OOM, "gpe_query_clusters: out of device memory");
+    if (e != hipSuccess) return fail(c, GPE_ERR_HIP, std::string("gpe_query_clusters: ") + hipGetErrorName(e));
+    return GPE_OK;
+}
+
+static gpe_status clusters_reserve(gpe_ctx *c)
+{
+    ClustersWorkspace &ws = c->clusters_ws;
+    const uint64_t n = c->n, tiles = contacts_tiles(n);
+    if (ws.cap < n) {
+        dev_free(c, ws.parent); dev_free(c, ws.label); dev_free(c, ws.root_size); dev_free(c, ws.size);
+        ws.cap = 0;
+        // parent: n words, read and written by index below n (the indices of the sorted records).  no slack
+        GPE_TRY(clusters_alloc(c, (void **)&ws.parent, n * sizeof(uint32_t), "clusters.parent"));
+        // label: n words, written by index below n; the member kernels read it by index below n (guarded tile loads).  no slack
+        GPE_TRY(clusters_alloc(c, (void **)&ws.label, n * sizeof(uint32_t), "clusters.label"));
+        // root_size: n words, indexed by a label, which is an index below n.  no slack
+        GPE_TRY(clusters_alloc(c, (void **)&ws.root_size, n * sizeof(uint32_t), "clusters.root_size"));
+        // size: n words, written by index below n.  no slack (nothing here is scanned; the members' scan runs on
+        // query.tile_count)
+        GPE_TRY(clusters_alloc(c, (void **)&ws.size, n * sizeof(uint32_t), "clusters.size"));
+        ws.cap = n;
+    }
+    if (ws.tiles_cap < tiles) {
+        dev_free(c, ws.tile_word);
+        ws.tiles_cap = 0;
+        // tile_word: one 64-bit word per workgroup of the flatten / sizes kernels.  no slack
+        GPE_TRY(clusters_alloc(c, (void **)&ws.tile_word, tiles * sizeof(unsigned long long), "clusters.tile_word"));
+        ws.tiles_cap = tiles;
+    }
+    // words: two 64-bit words.  no slack
+    if (!ws.words) GPE_TRY(clusters_alloc(c, (void **)&ws.words, 2 * sizeof(unsigned long long), "clusters.words"));
+    return GPE_OK;
+}
+
+// The checks the two cluster queries share once the result struct is usable and its count is 0: the refusals of
+// gpe_query_contacts.  *cell_size = the contact query's own cell size.
+static gpe_status clusters_begin(gpe_ctx *c, const char *who, float *cell_size)
+{
+    if (is_sharded(c))
+        return fail(c, GPE_ERR_UNSUPPORTED, std::string(who) + ": not supported on a sharded context (gpe_shard_*, "
+                                                                "order keys or an active cell box)");
+    if (c->n > 0xFFFFFFFFull) return fail(c, GPE_ERR_UNSUPPORTED, std::string(who) + ": more than 2^32 - 1 particles");
+    *cell_size = gpe_compute_cell_size(fabsf(c->max_radius));
+    if (c->n > 1 && !isfinite(*cell_size))
+        return fail(c, GPE_ERR_UNSUPPORTED, std::string(who) + ": the largest radius is not finite");
+    return GPE_OK;
+}
+
+// The labels of all particles into clusters_ws.label and the number of clusters into *count (read back; the stream is
+// idle afterwards).  n > 1 and a finite non-zero cell size.  Call inside the "Query clusters" scope.
+static gpe_status clusters_label(gpe_ctx *c, float cell_size, unsigned long long *count)
+{
+    GPE_TRY(clusters_reserve(c));
+    GPE_TRY(contacts_bin(c, cell_size));
+    ClustersWorkspace &ws = c->clusters_ws;
+    {
+        Scope k(c, "clusters/hook");
+        GPE_TRY(launch_clusters_hook(c, c->contacts_ws.keys, c->contacts_ws.rec, ws.parent));
+    }
+    {
+        Scope k(c, "clusters/flatten");
+        GPE_TRY(launch_clusters_flatten(c, ws.parent, ws.label, ws.tile_word, ws.words));
+    }
+    GPE_HIP(c, hipMemcpyAsync(count, ws.words, sizeof(*count), hipMemcpyDeviceToHost, c->stream));
+    GPE_HIP(c, hipStreamSynchronize(c->stream));
+    return GPE_OK;
+}
+
+gpe_status gpe_query_clusters(gpe_ctx *c, gpe_cluster_result *out)
+{
+    const char *who = "gpe_query_clusters";
+    if (!c) return GPE_ERR_INVALID_ARG;
+    if (!out) return fail(c, GPE_ERR_INVALID_ARG, std::string(who) + ": NULL result");
+    if (out->struct_size < sizeof(gpe_cluster_result)) {
+        if (out->struct_size >= offsetof(gpe_cluster_result, count) + sizeof(out->count)) out->count = 0;   // it has one
+        return fail(c, GPE_ERR_INVALID_ARG, std::string(who) + ": struct_size is smaller than gpe_cluster_result");
+    }
+    out->count = 0;
+    out->largest_size = out->largest_label = 0;
+    float cell_size = 0.0f;
+    GPE_TRY(clusters_begin(c, who, &cell_size));
+    if (out->label_uid && !c->uid.on)
+        return fail(c, GPE_ERR_STATE, std::string(who) + ": label_uid requested while uids are off");
+    const uint64_t n = c->n;
+    if (n == 0 || !c->pos) return GPE_OK;
+    GPE_HIP(c, hipSetDevice(c->device));
+    GPE_HIP(c, hipStreamSynchronize(c->stream));
+    if (n == 1 || cell_size == 0.0f) {                             // one particle, or every radius 0: nothing touches
+        if (out->label_uid) {                                      // label[i] = i: the particles' own uids
+            GPE_HIP(c, hipMemcpyAsync(out->label_uid, c->uid.uids, n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+            GPE_HIP(c, hipStreamSynchronize(c->stream));
+        }
+        if (out->label) for (uint64_t i = 0; i < n; ++i) out->label[i] = (uint32_t)i;
+        if (out->size) std::fill(out->size, out->size + n, 1u);
+        out->count = n;
+        out->largest_size = 1;
+        out->largest_label = 0;
+        return GPE_OK;
+    }
+    ClustersWorkspace &ws = c->clusters_ws;
+    unsigned long long count = 0, largest = 0;
+    Scope s(c, "Query clusters");
+    GPE_TRY(clusters_label(c, cell_size, &count));
+    {
+        Scope k(c, "clusters/sizes");
+        // parent is free after the flatten: it takes the uid of every particle's label
+        GPE_TRY(launch_clusters_sizes(c, ws.label, ws.root_size, ws.size, out->label_uid ? ws.parent : nullptr, ws.tile_word,
+                                      ws.words + 1));
+    }
+    GPE_HIP(c, hipMemcpyAsync(&largest, ws.words + 1, sizeof(largest), hipMemcpyDeviceToHost, c->stream));
+    if (out->label) GPE_HIP(c, hipMemcpyAsync(out->label, ws.label, n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    if (out->size) GPE_HIP(c, hipMemcpyAsync(out->size, ws.size, n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    if (out->label_uid)
+        GPE_HIP(c, hipMemcpyAsync(out->label_uid, ws.parent, n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    GPE_HIP(c, hipStreamSynchronize(c->stream));
+    out->count = count;
+    out->largest_size = (uint32_t)(largest >> 32);
+    out->largest_label = 0xFFFFFFFFu - (uint32_t)(largest & 0xFFFFFFFFull);
+    return GPE_OK;
+}
+
+gpe_status gpe_query_cluster_of(gpe_ctx *c, uint32_t key_kind, uint32_t key, gpe_query_result *out)
+{
+    const char *who = "gpe_query_cluster_of";
+    bool go = false;
+    GPE_TRY(query_begin(c, out, who, &go));
+    if (key_kind != GPE_CLUSTER_BY_INDEX && key_kind != GPE_CLUSTER_BY_UID)
+        return fail(c, GPE_ERR_INVALID_ARG, std::string(who) + ": unknown key_kind");
+    if (key_kind == GPE_CLUSTER_BY_UID && !c->uid.on)
+        return fail(c, GPE_ERR_STATE, std::string(who) + ": GPE_CLUSTER_BY_UID while uids are off");
+    if (key_kind == GPE_CLUSTER_BY_INDEX && key >= c->n)
+        return fail(c, GPE_ERR_INVALID_ARG, std::string(who) + ": index >= gpe_len");
+    float cell_size = 0.0f;
+    GPE_TRY(clusters_begin(c, who, &cell_size));
+    if (!go) return GPE_OK;                                        // no particles: every uid is absent
+    const uint64_t n = c->n;
+    GPE_HIP(c, hipSetDevice(c->device));
+    GPE_HIP(c, hipStreamSynchronize(c->stream));
+    uint32_t seed = key;
+    if (key_kind == GPE_CLUSTER_BY_UID) {                          // through the uid -> index map, as gpe_find_uids
+        GPE_TRY(uid_map_ready(c));
+        GPE_TRY(uid_query_reserve(c, 2 * sizeof(uint32_t)));
+        uint32_t *d_index = reinterpret_cast<uint32_t *>(c->uid.query), *d_query = d_index + 1;
+        GPE_HIP(c, hipMemcpyAsync(d_query, &key, sizeof(key), hipMemcpyHostToDevice, c->stream));
+        {
+            Scope k(c, "uids/find");
+            GPE_TRY(launch_uid_find(c, c->uid.map_keys, c->uid.map_vals, n, d_query, 1, d_index, nullptr, nullptr, nullptr));
+        }
+        GPE_HIP(c, hipMemcpyAsync(&seed, d_index, sizeof(seed), hipMemcpyDeviceToHost, c->stream));
+        GPE_HIP(c, hipStreamSynchronize(c->stream));
+        if (seed == GPE_UID_ABSENT) return GPE_OK;                 // an absent uid: count 0
+        if (seed >= n) return fail(c, GPE_ERR_STATE, std::string(who) + ": bad index");
+    }
+    if (n == 1 || cell_size == 0.0f) {                             // nothing touches: the seed alone, from the particle buffers
+        const uint32_t i = seed;
+        if (out->capacity >= 1) {
+            if (out->uid) GPE_HIP(c, hipMemcpyAsync(out->uid, c->uid.uids + i, 4, hipMemcpyDeviceToHost, c->stream));
+            if (out->pos_xy) GPE_HIP(c, hipMemcpyAsync(out->pos_xy, c->pos + i, 8, hipMemcpyDeviceToHost, c->stream));
+            if (out->prev_xy) GPE_HIP(c, hipMemcpyAsync(out->prev_xy, c->prev + i, 8, hipMemcpyDeviceToHost, c->stream));
+            if (out->radius) GPE_HIP(c, hipMemcpyAsync(out->radius, c->radius + i, 4, hipMemcpyDeviceToHost, c->stream));
+            GPE_HIP(c, hipStreamSynchronize(c->stream));
+            if (out->index) out->index[0] = i;
+        }
+        out->count = 1;
+        return GPE_OK;
+    }
+    GPE_TRY(query_reserve(c, 0));
+    ClustersWorkspace &ws = c->clusters_ws;
+    const uint64_t tiles = query_tiles(n);
+    unsigned long long count = 0;
+    uint32_t want = 0, total = 0;
+    Scope s(c, "Query clusters");
+    GPE_TRY(clusters_label(c, cell_size, &count));
+    GPE_HIP(c, hipMemcpyAsync(&want, ws.label + seed, sizeof(want), hipMemcpyDeviceToHost, c->stream));
+    GPE_HIP(c, hipStreamSynchronize(c->stream));
+    {
+        Scope k(c, "clusters/gather");
+        GPE_TRY(launch_clusters_member_count(c, ws.label, want, c->query_ws.tile_count));
+        GPE_TRY(inclusive_scan(c, c->query_ws.tile_count, tiles));
+    }
+    GPE_HIP(c, hipMemcpyAsync(&total, c->query_ws.tile_count + (tiles - 1), sizeof(total), hipMemcpyDeviceToHost, c->stream));
+    GPE_HIP(c, hipStreamSynchronize(c->stream));
+    return query_deliver(c, out, total, "clusters/gather",
+                         [&](uint32_t m, uint32_t *d_index, uint32_t *d_uid, float2 *d_pos, float2 *d_prev, float *d_radius) {
+                             return launch_clusters_member_gather(c, ws.label, want, c->query_ws.tile_count, m, d_index,
+                                                                  d_uid, d_pos, d_prev, d_radius);
+                         });
 }
 
 // ---- editing particles in place (k_edit.hip) ---------------------------------------------------------------

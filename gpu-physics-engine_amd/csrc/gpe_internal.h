@@ -291,6 +291,17 @@ struct ContactsWorkspace {       // gpe_query_contacts (k_contacts.hip); allocat
     uint64_t stage_cap = 0;                      // bytes
 };
 
+struct ClustersWorkspace {       // gpe_query_clusters / gpe_query_cluster_of (k_clusters.hip); allocated at first use, freed with the particles
+    uint32_t *parent = nullptr;                  // the union-find forest: parent[i] <= i; after the flatten free for label_uid
+    uint32_t *label = nullptr;                   // per particle: the lowest index of its cluster
+    uint32_t *root_size = nullptr;               // per root: the particles of its cluster (0 elsewhere)
+    uint32_t *size = nullptr;                    // per particle: the particles of its cluster
+    uint64_t cap = 0;                            // particles the four arrays above hold
+    unsigned long long *tile_word = nullptr;     // per workgroup: its number of roots, later its largest size key
+    uint64_t tiles_cap = 0;
+    unsigned long long *words = nullptr;         // [0] the number of clusters, [1] the largest size << 32 | ~label
+};
+
 struct EditWorkspace {           // gpe_edit_particles / gpe_kick_* (k_edit.hip); allocated at first use, freed with the particles
     uint32_t *keys = nullptr;                    // the caller's keys, resolved to storage indices in place, then sorted
     uint32_t *slots = nullptr;                   // each key's position in the caller's arrays, sorted with it
@@ -660,6 +671,7 @@ struct gpe_ctx {
     gpe::UidState uid;
     gpe::QueryWorkspace query_ws;
     gpe::ContactsWorkspace contacts_ws;
+    gpe::ClustersWorkspace clusters_ws;
     gpe::EditWorkspace edit_ws;
     gpe::ScanWorkspace scan_ws;
     gpe::OnesweepWorkspace os_ws;
@@ -813,6 +825,21 @@ gpe_status launch_contacts_count(gpe_ctx *c, const uint32_t *keys, const uint4 *
 gpe_status launch_contacts_gather(gpe_ctx *c, const uint32_t *keys, const uint4 *rec, const uint32_t *scanned,
                                   uint32_t capacity, uint32_t *index_a, uint32_t *index_b, uint32_t *uid_a, uint32_t *uid_b,
                                   float *overlap);
+// contact clusters (k_clusters.hip); keys / rec: the contact query's sorted cell keys and records
+// parent[i] = i, then every contact (i, j < i) unites the trees of i and j: parent[x] <= x, a component's root is its lowest index
+gpe_status launch_clusters_hook(gpe_ctx *c, const uint32_t *keys, const uint4 *rec, uint32_t *parent);
+// label[i] = root(i) (parent is compressed on the way); *count = the number of roots (tile_word: contacts_tiles(n))
+gpe_status launch_clusters_flatten(gpe_ctx *c, uint32_t *parent, uint32_t *label, unsigned long long *tile_word,
+                                   unsigned long long *count);
+// root_size[r] = particles labelled r, size[i] = root_size[label[i]], label_uid[i] = uids[label[i]] (NULL: not wanted);
+// *largest = max over the roots of size << 32 | (0xFFFFFFFF - label)
+gpe_status launch_clusters_sizes(gpe_ctx *c, const uint32_t *label, uint32_t *root_size, uint32_t *size,
+                                 uint32_t *label_uid, unsigned long long *tile_word, unsigned long long *largest);
+// the particles labelled `want`, counted and gathered as launch_query_count / launch_query_gather do for a region
+gpe_status launch_clusters_member_count(gpe_ctx *c, const uint32_t *label, uint32_t want, uint32_t *tile_count);
+gpe_status launch_clusters_member_gather(gpe_ctx *c, const uint32_t *label, uint32_t want, const uint32_t *tile_scanned,
+                                         uint32_t capacity, uint32_t *index_out, uint32_t *uid_out, float2 *pos_out,
+                                         float2 *prev_out, float *radius_out);
 // in-place edits (k_edit.hip).  Keyed edits: keys[i] becomes the storage index key i names (by_uid: looked up in the
 // sorted uid map of n entries; GPE_UID_ABSENT for an absent uid or an index >= n, the latter also sets kEditBadIndex in
 // flag[0]), slots[i] = i, flag[1] += the keys that name a particle.  flag zeroed by the caller.

@@ -34,6 +34,9 @@ QueryResult = collections.namedtuple("QueryResult", "index uid pos prev radius")
 # gpe_query_contacts: the touching pairs (a < b), ascending by a then b (uid_a / uid_b None while uids are off, overlap
 # None unless asked for)
 ContactResult = collections.namedtuple("ContactResult", "a b uid_a uid_b overlap")
+# gpe_query_clusters: per particle the lowest index of its contact cluster, that cluster's size and the uid of particle
+# label[i] (None while uids are off); the number of clusters, and the size and label of the largest one
+ClusterResult = collections.namedtuple("ClusterResult", "label size label_uid count largest_size largest_label")
 
 
 class Context:
@@ -463,6 +466,58 @@ class ParticleSystem:
         self.ctx.call("gpe_query_contacts", C.byref(res))
         return deg[:n]
 
+    # Contact clusters (not in the reference; include/gpe.h): the connected components of the contact graph, labelled on
+    # the device by the lowest storage index of each.  The context is left exactly as it was.
+    def clusters(self):
+        """gpe_query_clusters -> ClusterResult(label, size, label_uid, count, largest_size, largest_label): label[i] =
+        the lowest index among the particles a chain of contacts joins to i, size[i] = how many they are, label_uid[i]
+        = the uid of particle label[i] (None while uids are off)."""
+        with_uids = self._uids_on()
+        n = self.len()
+        u32 = C.POINTER(C.c_uint32)
+        label, size = np.zeros(max(n, 1), np.uint32), np.zeros(max(n, 1), np.uint32)
+        label_uid = np.zeros(max(n, 1), np.uint32) if with_uids else None
+        res = L.GpeClusterResult(struct_size=C.sizeof(L.GpeClusterResult))
+        res.label, res.size = label.ctypes.data_as(u32), size.ctypes.data_as(u32)
+        if with_uids:
+            res.label_uid = label_uid.ctypes.data_as(u32)
+        self.ctx.call("gpe_query_clusters", C.byref(res))
+        return ClusterResult(label[:n], size[:n], label_uid[:n] if with_uids else None, res.count, res.largest_size,
+                             res.largest_label)
+
+    def count_clusters(self):
+        """gpe_query_clusters with no arrays: the number of clusters, singletons included."""
+        res = L.GpeClusterResult(struct_size=C.sizeof(L.GpeClusterResult))
+        self.ctx.call("gpe_query_clusters", C.byref(res))
+        return res.count
+
+    def cluster_of(self, index=None, uid=None, capacity=None):
+        """gpe_query_cluster_of -> QueryResult of the cluster that holds the particle named by storage `index` or by
+        `uid` -- exactly one of the two -- in ascending storage index; at most `capacity` rows, all of them with
+        capacity=None (one counting call first).  An unknown uid gives no rows."""
+        if (index is None) == (uid is None):
+            raise ValueError("cluster_of: give exactly one of index and uid")
+        kind, key = (L.CLUSTER_BY_INDEX, int(index)) if uid is None else (L.CLUSTER_BY_UID, int(uid))
+        if capacity is None:
+            capacity = self._count("gpe_query_cluster_of", (kind, key))
+        with_uids = self._uids_on()
+        cap = int(capacity)
+        room = max(cap, 1)
+        idx = np.empty(room, np.uint32)
+        uids = np.empty(room, np.uint32) if with_uids else None
+        pos, prev = np.empty((room, 2), np.float32), np.empty((room, 2), np.float32)
+        rad = np.empty(room, np.float32)
+        res = L.GpeQueryResult(struct_size=C.sizeof(L.GpeQueryResult), capacity=cap)
+        res.index = idx.ctypes.data_as(C.POINTER(C.c_uint32))
+        if with_uids:
+            res.uid = uids.ctypes.data_as(C.POINTER(C.c_uint32))
+        res.pos_xy = pos.ctypes.data_as(C.POINTER(C.c_float))
+        res.prev_xy = prev.ctypes.data_as(C.POINTER(C.c_float))
+        res.radius = rad.ctypes.data_as(C.POINTER(C.c_float))
+        self.ctx.call("gpe_query_cluster_of", kind, key, C.byref(res))
+        k = min(res.count, cap)
+        return QueryResult(idx[:k], uids[:k] if with_uids else None, pos[:k], prev[:k], rad[:k])
+
     # Editing particles in place (not in the reference; include/gpe.h): new pos / prev / radius for particles named by
     # storage index or by uid, and velocity kicks of every particle in a circle or a box -- all on the device, the
     # uids, the order and the native counters kept.
@@ -750,6 +805,18 @@ class State:
     def contact_degrees(self):
         """ParticleSystem.contact_degrees -> u32[len], the contacts of every particle."""
         return self.particles.contact_degrees()
+
+    def clusters(self):
+        """ParticleSystem.clusters -> ClusterResult(label, size, label_uid, count, largest_size, largest_label)."""
+        return self.particles.clusters()
+
+    def count_clusters(self):
+        """ParticleSystem.count_clusters -> the number of contact clusters, singletons included."""
+        return self.particles.count_clusters()
+
+    def cluster_of(self, index=None, uid=None, capacity=None):
+        """ParticleSystem.cluster_of -> QueryResult of the cluster that holds the particle `index` or `uid`."""
+        return self.particles.cluster_of(index=index, uid=uid, capacity=capacity)
 
     def count_circle(self, center, radius):
         return self.particles.count_circle(center, radius)

@@ -305,6 +305,46 @@ class ParticleSystem {
         ctx_->call(gpe_query_contacts(ctx_->raw(), &r));
         return degree;
     }
+    // not in the reference: which particles make up one clump -- the connected components of the contact graph
+    // (include/gpe.h), labelled on the device.  clusters(): per particle the lowest storage index of its cluster, that
+    // cluster's size and, while uids are on, the uid of particle label[i]; cluster_of(): the rows of the cluster that holds
+    // the particle `key` names (a storage index, or a uid with by_uid), ascending storage index -- none for an unknown uid.
+    struct ClusterResult {
+        std::vector<uint32_t> label, size, label_uid;
+        uint64_t count = 0;
+        uint32_t largest_size = 0, largest_label = 0;
+    };
+    ClusterResult clusters() const
+    {
+        uint64_t next = 0;
+        const bool with_uids = gpe_next_uid(ctx_->raw(), &next) == GPE_OK;
+        const size_t n = len();
+        uint32_t none = 0;
+        ClusterResult q;
+        q.label.resize(n);
+        q.size.resize(n);
+        q.label_uid.resize(with_uids ? n : 0);
+        gpe_cluster_result r = empty_clusters();
+        r.label = n ? q.label.data() : &none;
+        r.size = n ? q.size.data() : &none;
+        r.label_uid = with_uids ? (n ? q.label_uid.data() : &none) : nullptr;
+        ctx_->call(gpe_query_clusters(ctx_->raw(), &r));
+        q.count = r.count;
+        q.largest_size = r.largest_size;
+        q.largest_label = r.largest_label;
+        return q;
+    }
+    uint64_t count_clusters() const
+    {
+        gpe_cluster_result r = empty_clusters();
+        ctx_->call(gpe_query_clusters(ctx_->raw(), &r));
+        return r.count;
+    }
+    QueryResult cluster_of(uint32_t key, bool by_uid = false) const
+    {
+        const uint32_t kind = by_uid ? GPE_CLUSTER_BY_UID : GPE_CLUSTER_BY_INDEX;
+        return query([&](gpe_query_result *r) { return gpe_query_cluster_of(ctx_->raw(), kind, key, r); });
+    }
     // not in the reference: edit particles in place on the device (include/gpe.h).  The particles named by `keys` --
     // storage indices, or uids with by_uid -- take row i of every array given (NULL: that field stays; positions without
     // previous: at rest, prev = pos).  Unknown uids are skipped.  Returns the number of particles written.
@@ -383,6 +423,12 @@ class ParticleSystem {
     {
         gpe_contact_result r{};
         r.struct_size = sizeof(gpe_contact_result);
+        return r;
+    }
+    static gpe_cluster_result empty_clusters()
+    {
+        gpe_cluster_result r{};
+        r.struct_size = sizeof(gpe_cluster_result);
         return r;
     }
     // one call with `capacity` rows, a second with capacity = count only if the first ran over

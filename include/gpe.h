@@ -282,6 +282,58 @@ typedef struct gpe_contact_result {
 } gpe_contact_result;       /* 72 bytes */
 gpe_status gpe_query_contacts(gpe_ctx *ctx, gpe_contact_result *out);
 
+/* ---- contact clusters (not in the reference) -----------------------------------------------------------------
+ * Which particles make up one clump: the connected components of the graph whose edges are the contacts of
+ * gpe_query_contacts, labelled on the device (csrc/k_clusters.hip) in scratch of its own, without downloading the pair
+ * list for a union-find on the host -- a settled pile may have more contacts than can be listed at all.
+ *  - Two particles are in one cluster when a chain of contacts joins them.  "Contact" is exactly the predicate of
+ *    gpe_query_contacts: the same binary32 operations, radii as stored, a NaN anywhere compares false.
+ *  - The search uses the contact query's own cell size, gpe_compute_cell_size(|gpe_max_radius|): a
+ *    gpe_grid_set_max_radius override changes nothing about the result.
+ *  - label[i] = the lowest storage index among the particles of i's cluster.  A particle without contacts is its own
+ *    cluster, label[i] == i.  size[i] = the number of particles in i's cluster.  label_uid[i] = the uid of particle
+ *    label[i].  count = the number of i with label[i] == i, singletons included.  largest_size / largest_label: the
+ *    size of the largest cluster and its label, the lowest label among the clusters of that size.
+ *  - The per-particle arrays always have gpe_len entries.
+ *  - The result is a function of the particles alone: everything is integers, and the lowest index of a component does
+ *    not depend on the launch geometry or on which wave wins a race.  Two calls return identical arrays.
+ *  - Positions may be anything gpe_set_particles accepts, as for gpe_query_contacts.
+ *  - The query changes nothing on the context: positions, prev, radii, uids, the uid map, GPE_HOME_CELL_IDS and the
+ *    other scratch index arrays, the native step / sort counters, the kept block table and the rosters are left alone;
+ *    the steps after a query are bit-identical to those of a context that was never queried.  It works in both modes
+ *    and at any point between steps, and blocks like gpe_download.
+ *  - No particles: GPE_OK, count 0.  One particle, or every radius 0 (a cell size of 0): every particle is its own
+ *    cluster -- count = gpe_len, largest_size = 1, largest_label = 0; the arrays are filled on the host.
+ *  - Errors, as gpe_query_contacts: a NULL context, a NULL out or a struct_size below sizeof(gpe_cluster_result):
+ *    GPE_ERR_INVALID_ARG; label_uid requested while uids are off: GPE_ERR_STATE; a sharded context (gpe_shard_*, order
+ *    keys or an active cell box), more than 2^32 - 1 particles, and a cell size that is not finite (an infinite radius)
+ *    with more than one particle: GPE_ERR_UNSUPPORTED.  On any error count is 0 (when out is usable) and no array is
+ *    written. */
+typedef struct gpe_cluster_result {
+    uint32_t struct_size;    /* in: sizeof(gpe_cluster_result)                                        */
+    uint32_t reserved;       /* in: 0                                                                 */
+    uint64_t count;          /* out: number of clusters, singletons included                          */
+    uint32_t largest_size;   /* out: particles in the largest cluster                                 */
+    uint32_t largest_label;  /* out: its label (the lowest label among clusters of that size)         */
+    uint32_t *label;         /* out, may be NULL: u32[gpe_len]                                        */
+    uint32_t *size;          /* out, may be NULL: u32[gpe_len] particles in i's cluster               */
+    uint32_t *label_uid;     /* out, may be NULL: u32[gpe_len] uid of particle label[i]; uids off: GPE_ERR_STATE */
+} gpe_cluster_result;        /* 48 bytes */
+gpe_status gpe_query_clusters(gpe_ctx *ctx, gpe_cluster_result *out);
+
+/* Flood select: the members of the cluster that holds the particle named by storage index (GPE_CLUSTER_BY_INDEX) or by
+ * uid (GPE_CLUSTER_BY_UID), delivered exactly as the region queries deliver rows.  count may exceed capacity; the first
+ * min(count, capacity) members, in ascending storage index, go into every non-NULL array; host memory past those
+ * entries is left untouched; with every array NULL the call only counts.  A particle without contacts is the one member
+ * of its cluster.  An absent uid: GPE_OK with count 0.
+ *  - Errors: GPE_CLUSTER_BY_INDEX with key >= gpe_len, or an unknown key_kind: GPE_ERR_INVALID_ARG;
+ *    GPE_CLUSTER_BY_UID while uids are off: GPE_ERR_STATE; otherwise those of gpe_query_circle and of
+ *    gpe_query_clusters above.  On any error count is 0 (when out is usable) and no array is written.
+ *  - The context is left untouched as by gpe_query_clusters, except that a lookup by uid may rebuild a stale uid ->
+ *    index map, as gpe_find_uids does. */
+enum { GPE_CLUSTER_BY_INDEX = 0, GPE_CLUSTER_BY_UID = 1 };
+gpe_status gpe_query_cluster_of(gpe_ctx *ctx, uint32_t key_kind, uint32_t key, gpe_query_result *out);
+
 /* ---- editing particles in place (not in the reference) --------------------------------------------------------
  * Change particles that exist, on the device (csrc/k_edit.hip), without the download / gpe_set_particles detour that
  * would drop the uids, the kept block table and the native counters.  Two kinds of call:
