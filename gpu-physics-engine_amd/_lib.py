@@ -42,6 +42,8 @@ UID_ABSENT = 0xFFFFFFFF
 EDIT_BY_INDEX, EDIT_BY_UID = 0, 1
 CLUSTER_BY_INDEX, CLUSTER_BY_UID = 0, 1
 VEL_ADD, VEL_SET, VEL_SCALE = 0, 1, 2
+SPAWN_SEPARATE, SPAWN_INSIDE_WORLD, SPAWN_DRY_RUN = 1, 2, 4
+SPAWN_ADDED, SPAWN_BLOCKED_BY_PARTICLE, SPAWN_BLOCKED_BY_CANDIDATE, SPAWN_OUTSIDE_WORLD = 0, 1, 2, 3
 
 
 class GpeConfig(C.Structure):
@@ -146,6 +148,13 @@ class GpeParticleEdit(C.Structure):
                 ("radius", C.POINTER(C.c_float)), ("edited", C.c_uint64)]
 
 
+class GpeParticleSpawn(C.Structure):
+    """gpe_particle_spawn: in struct_size / flags / k and the candidate arrays, out verdict (may be NULL) and added."""
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("k", C.c_uint64),
+                ("pos_xy", C.POINTER(C.c_float)), ("radius", C.POINTER(C.c_float)), ("verdict", C.POINTER(C.c_uint8)),
+                ("added", C.c_uint64)]
+
+
 GUARD_MAX_ZONES = 8
 GUARD_FRONT, GUARD_REAR = 0, 1
 
@@ -192,6 +201,7 @@ SYMBOLS = [
     ("gpe_query_clusters", _I32, [_VP, C.POINTER(GpeClusterResult)]),
     ("gpe_query_cluster_of", _I32, [_VP, _U32, _U32, C.POINTER(GpeQueryResult)]),
     ("gpe_edit_particles", _I32, [_VP, C.POINTER(GpeParticleEdit)]),
+    ("gpe_add_particles_free", _I32, [_VP, C.POINTER(GpeParticleSpawn)]),
     ("gpe_kick_circle", _I32, [_VP, _F, _F, _F, _U32, _F, _F, C.POINTER(_U64)]),
     ("gpe_kick_box", _I32, [_VP, _F, _F, _F, _F, _U32, _F, _F, C.POINTER(_U64)]),
     ("gpe_len", _I32, [_VP, C.POINTER(_U64)]),

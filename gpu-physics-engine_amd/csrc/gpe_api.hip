@@ -8,6 +8,7 @@
 #include <algorithm>
 #include <functional>
 #include <mutex>
+#include <new>
 
 #include "gpe_internal.h"
 #include "k_uids.h"
@@ -302,6 +303,10 @@ static void free_particle_buffers(gpe_ctx *c)
     dev_free(c, e.keys); dev_free(c, e.slots); dev_free(c, e.fields); dev_free(c, e.flag);
     dev_free(c, e.tile_key); dev_free(c, e.max_key); dev_free(c, e.count);
     e.keys_cap = e.fields_cap = e.tiles_cap = 0;
+    SpawnWorkspace &w = c->spawn_ws;
+    dev_free(c, w.pos); dev_free(c, w.radius); dev_free(c, w.keys); dev_free(c, w.vals); dev_free(c, w.rec);
+    dev_free(c, w.blocked); dev_free(c, w.state); dev_free(c, w.rank); dev_free(c, w.verdict); dev_free(c, w.ctl);
+    w.cap = 0;
     free_uid_buffers(c);
     c->cap = 0;
 }
@@ -1772,6 +1777,166 @@ gpe_status gpe_query_cluster_of(gpe_ctx *c, uint32_t key_kind, uint32_t key, gpe
                              return launch_clusters_member_gather(c, ws.label, want, c->query_ws.tile_count, m, d_index,
                                                                   d_uid, d_pos, d_prev, d_radius);
                          });
+}
+
+// ---- overlap-checked adds (k_spawn.hip) --------------------------------------------------------------------
+static gpe_status spawn_alloc(gpe_ctx *c, void **p, uint64_t payload, uint64_t slack, const char *tag)
+{
+    const hipError_t e = gpe_dev_reserve(c, p, payload, slack, tag);
+    if (e == hipErrorOutOfMemory) return fail(c, GPE_ERR_OOM, "gpe_add_particles_free: out of device memory");
+    if (e != hipSuccess) return fail(c, GPE_ERR_HIP, std::string("gpe_add_particles_free: ") + hipGetErrorName(e));
+    return GPE_OK;
+}
+
+// Scratch of the call's own: nothing of the contact or cluster workspaces is used, so a later query finds its buffers
+// as it left them.
+static gpe_status spawn_reserve(gpe_ctx *c, uint64_t k)
+{
+    SpawnWorkspace &ws = c->spawn_ws;
+    if (ws.cap < k) {
+        dev_free(c, ws.pos); dev_free(c, ws.radius); dev_free(c, ws.keys); dev_free(c, ws.vals); dev_free(c, ws.rec);
+        dev_free(c, ws.blocked); dev_free(c, ws.state); dev_free(c, ws.rank); dev_free(c, ws.verdict);
+        ws.cap = 0;
+        // pos / radius: the k uploaded candidates, read by index below k.  no slack
+        GPE_TRY(spawn_alloc(c, (void **)&ws.pos, k * sizeof(float2), 0, "spawn.pos"));
+        GPE_TRY(spawn_alloc(c, (void **)&ws.radius, k * sizeof(float), 0, "spawn.radius"));
+        // keys / vals: k words each.  slack: the 16 words sort_pairs' tile loads may read behind the k pairs
+        GPE_TRY(spawn_alloc(c, (void **)&ws.keys, k * sizeof(uint32_t), 16 * sizeof(uint32_t), "spawn.keys"));
+        GPE_TRY(spawn_alloc(c, (void **)&ws.vals, k * sizeof(uint32_t), 16 * sizeof(uint32_t), "spawn.vals"));
+        // rec: k 16-byte records, read one at a time below k.  no slack
+        GPE_TRY(spawn_alloc(c, (void **)&ws.rec, k * sizeof(uint4), 0, "spawn.rec"));
+        // blocked / state: k words each, written and read by index below k.  no slack
+        GPE_TRY(spawn_alloc(c, (void **)&ws.blocked, k * sizeof(uint32_t), 0, "spawn.blocked"));
+        GPE_TRY(spawn_alloc(c, (void **)&ws.state, k * sizeof(uint32_t), 0, "spawn.state"));
+        // rank: k words, scanned in place.  slack: the 16 words the scan's tile loads may read behind them
+        GPE_TRY(spawn_alloc(c, (void **)&ws.rank, k * sizeof(uint32_t), 16 * sizeof(uint32_t), "spawn.rank"));
+        // verdict: k bytes, written and copied out below k.  no slack
+        GPE_TRY(spawn_alloc(c, (void **)&ws.verdict, k, 0, "spawn.verdict"));
+        ws.cap = k;
+    }
+    // ctl: kSpawnCtlWords words.  no slack
+    if (!ws.ctl) GPE_TRY(spawn_alloc(c, (void **)&ws.ctl, kSpawnCtlWords * sizeof(uint32_t), 0, "spawn.ctl"));
+    GPE_TRY(sort_reserve(c, k));
+    return scan_reserve(c, k);
+}
+
+// The separation rounds: batches of kSpawnRoundsPerLook launches, then one look at the batch's undecided counters.
+static gpe_status spawn_separate(gpe_ctx *c, uint32_t k, float cell_size)
+{
+    const SpawnWorkspace &ws = c->spawn_ws;
+    uint32_t *left = ws.ctl + kSpawnCtlRounds, h_left[kSpawnRoundsPerLook];
+    for (uint64_t rounds = 0;; rounds += kSpawnRoundsPerLook) {
+        // (every round settles one more workgroup block at least, and the lowest undecided index: k rounds always suffice)
+        if (rounds > (uint64_t)k + kSpawnRoundsPerLook) return fail(c, GPE_ERR_HIP, "gpe_add_particles_free: the separation did not settle");
+        GPE_HIP(c, hipMemsetAsync(left, 0, sizeof(h_left), c->stream));
+        for (int r = 0; r < kSpawnRoundsPerLook; ++r) {
+            Scope s(c, "spawn/round");
+            GPE_TRY(launch_spawn_round(c, ws, k, cell_size, left + r));
+        }
+        GPE_HIP(c, hipMemcpyAsync(h_left, left, sizeof(h_left), hipMemcpyDeviceToHost, c->stream));
+        GPE_HIP(c, hipStreamSynchronize(c->stream));
+        if (h_left[kSpawnRoundsPerLook - 1] == 0) return GPE_OK;
+    }
+}
+
+gpe_status gpe_add_particles_free(gpe_ctx *c, gpe_particle_spawn *sp)
+{
+    const char *who = "gpe_add_particles_free";
+    if (!c) return GPE_ERR_INVALID_ARG;
+    if (!sp) return fail(c, GPE_ERR_INVALID_ARG, std::string(who) + ": NULL spawn");
+    if (sp->struct_size < sizeof(gpe_particle_spawn))                  // (`added` is the last field: such a struct has none)
+        return fail(c, GPE_ERR_INVALID_ARG, std::string(who) + ": struct_size is smaller than gpe_particle_spawn");
+    sp->added = 0;
+    const uint32_t known = GPE_SPAWN_SEPARATE | GPE_SPAWN_INSIDE_WORLD | GPE_SPAWN_DRY_RUN;
+    if (sp->flags & ~known) return fail(c, GPE_ERR_INVALID_ARG, std::string(who) + ": unknown flag bits");
+    GPE_TRY(need_particles(c));
+    if (is_sharded(c))
+        return fail(c, GPE_ERR_UNSUPPORTED, std::string(who) + ": not supported on a sharded context (gpe_shard_*, "
+                                                                "order keys or an active cell box)");
+    const uint64_t k = sp->k;
+    if (k == 0) return GPE_OK;
+    if (!sp->pos_xy || !sp->radius) return fail(c, GPE_ERR_INVALID_ARG, std::string(who) + ": NULL array");
+    if (k > (1ull << 30) - 1 || c->n + k > (1ull << 30) - 1)
+        return fail(c, GPE_ERR_UNSUPPORTED, std::string(who) + ": 4 (gpe_len + k) must fit in u32");
+    // the search's own cell size: a contact implies a centre distance below 2 R, less than one cell of 2.2 R
+    float big = fabsf(c->max_radius);
+    bool finite = isfinite(big);
+    for (uint64_t i = 0; i < k; ++i) {
+        const float a = fabsf(sp->radius[i]);
+        finite = finite && isfinite(a);
+        big = a > big ? a : big;
+    }
+    const float cell_size = gpe_compute_cell_size(big);
+    if (!finite || !isfinite(cell_size))
+        return fail(c, GPE_ERR_UNSUPPORTED, std::string(who) + ": the largest radius is not finite");
+    const bool search = big > 0.0f;                                // every radius 0: nothing touches
+    const bool separate = (sp->flags & GPE_SPAWN_SEPARATE) != 0 && search;
+    const uint32_t k32 = (uint32_t)k;
+    GPE_HIP(c, hipSetDevice(c->device));
+    GPE_HIP(c, hipStreamSynchronize(c->stream));
+    std::vector<uint8_t> state;                                    // the verdicts: the user's array is written at the end only
+    try {
+        state.resize(k);
+    } catch (const std::bad_alloc &) {
+        return fail(c, GPE_ERR_OOM, std::string(who) + ": out of host memory for the verdicts");
+    }
+    {
+        Scope s(c, "Spawn check");
+        GPE_TRY(spawn_reserve(c, k));
+        const SpawnWorkspace &ws = c->spawn_ws;
+        GPE_HIP(c, hipMemcpyAsync(ws.pos, sp->pos_xy, k * sizeof(float2), hipMemcpyHostToDevice, c->stream));
+        GPE_HIP(c, hipMemcpyAsync(ws.radius, sp->radius, k * sizeof(float), hipMemcpyHostToDevice, c->stream));
+        {
+            Scope b(c, "spawn/bin");
+            GPE_TRY(launch_spawn_keys(c, ws, k32, cell_size, (sp->flags & GPE_SPAWN_INSIDE_WORLD) != 0));
+            if (search) {
+                GPE_TRY(sort_pairs(c, ws.keys, ws.vals, k));
+                GPE_TRY(launch_contacts_records_of(c, ws.pos, ws.radius, ws.vals, k, ws.rec));
+            }
+        }
+        {
+            Scope p(c, "spawn/pass");
+            GPE_TRY(launch_spawn_pass(c, ws, k32, cell_size, search));
+        }
+        GPE_TRY(launch_spawn_resolve(c, ws, k32, separate));
+        if (separate) {
+            Scope r(c, "spawn/separate");
+            GPE_TRY(spawn_separate(c, k32, cell_size));
+        }
+        GPE_TRY(launch_spawn_flags(c, ws, k32));
+        GPE_HIP(c, hipMemcpyAsync(state.data(), ws.verdict, k, hipMemcpyDeviceToHost, c->stream));
+        GPE_HIP(c, hipStreamSynchronize(c->stream));
+    }
+    uint64_t added = 0;
+    for (uint64_t i = 0; i < k; ++i) added += state[i] == GPE_SPAWN_ADDED ? 1u : 0u;
+    const bool append = added > 0 && !(sp->flags & GPE_SPAWN_DRY_RUN);
+    if (append) {
+        const uint64_t old_n = c->n, new_n = c->n + added;
+        if (c->uid.on && c->uid.next + added > kUidLimit)
+            return fail(c, GPE_ERR_STATE, std::string(who) + ": the new particles' uids would pass 2^32 - 1");
+        if (new_n > c->cap) GPE_TRY(grow_particle_buffers(c, std::max<uint64_t>(new_n, c->cap * 2)));
+        Scope s(c, "spawn/append");
+        const SpawnWorkspace &ws = c->spawn_ws;
+        GPE_TRY(inclusive_scan(c, ws.rank, k));                    // (the flags: launch_spawn_flags above)
+        GPE_TRY(launch_spawn_scatter(c, ws, k32, old_n));
+        c->n = new_n;
+        c->n_owned = new_n;
+        GPE_TRY(init_index_buffers(c, old_n, new_n));
+        if (c->uid.on) {                                   // next .. next + added - 1, in input order
+            GPE_TRY(launch_uid_iota(c, c->uid.uids, old_n, new_n, (uint32_t)c->uid.next));
+            c->uid.next += added;
+            c->uid.map_valid = false;
+        }
+        // as gpe_add_particles of the added candidates: max_radius = max(max_radius, r), in input order
+        for (uint64_t i = 0; i < k; ++i)
+            if (state[i] == GPE_SPAWN_ADDED) c->max_radius = fmaxf(c->max_radius, sp->radius[i]);
+        c->grid_max_radius = c->max_radius;
+        refresh_cell_size(c);
+        GPE_HIP(c, hipStreamSynchronize(c->stream));
+    }
+    if (sp->verdict) std::copy(state.begin(), state.end(), sp->verdict);
+    sp->added = added;
+    return append ? reconfigure(c) : GPE_OK;
 }
 
 // ---- editing particles in place (k_edit.hip) ---------------------------------------------------------------

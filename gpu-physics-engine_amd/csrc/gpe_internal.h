@@ -302,6 +302,24 @@ struct ClustersWorkspace {       // gpe_query_clusters / gpe_query_cluster_of (k
     unsigned long long *words = nullptr;         // [0] the number of clusters, [1] the largest size << 32 | ~label
 };
 
+struct SpawnWorkspace {          // gpe_add_particles_free (k_spawn.hip); allocated at first use, freed with the particles
+    float2 *pos = nullptr;                       // the uploaded candidates, input order
+    float *radius = nullptr;
+    uint32_t *keys = nullptr, *vals = nullptr;   // clamped cell key and input index per candidate, sorted by the key
+    uint4 *rec = nullptr;                        // per sorted slot: bits of x, y, radius and the input index
+    uint32_t *blocked = nullptr;                 // per candidate: 1 when a particle of the context touches it
+    uint32_t *state = nullptr;                   // per candidate: its verdict (GPE_SPAWN_*), or kSpawnUndecided
+    uint32_t *rank = nullptr;                    // per candidate: 1 when added, scanned in place
+    uint8_t *verdict = nullptr;                  // per candidate: its verdict as the byte the host downloads
+    uint64_t cap = 0;                            // candidates the nine arrays above hold
+    uint32_t *ctl = nullptr;                     // kSpawnCtlWords: the candidates' cell box, the rounds' undecided counters
+};
+constexpr uint32_t kSpawnUndecided = 4u;         // SpawnWorkspace::state: waits for a candidate of lower index
+constexpr int kSpawnRoundsPerLook = 8;           // separation rounds between two host reads of the undecided counters
+// ctl words: [0] min cx, [1] min cy, [2] 65535 - max cx, [3] 65535 - max cy of the candidates inside the world test
+// (one atomicMin each, all ones = no candidate); [kSpawnCtlRounds + r]: candidates still undecided after round r of a batch
+constexpr int kSpawnCtlRounds = 4, kSpawnCtlWords = kSpawnCtlRounds + kSpawnRoundsPerLook;
+
 struct EditWorkspace {           // gpe_edit_particles / gpe_kick_* (k_edit.hip); allocated at first use, freed with the particles
     uint32_t *keys = nullptr;                    // the caller's keys, resolved to storage indices in place, then sorted
     uint32_t *slots = nullptr;                   // each key's position in the caller's arrays, sorted with it
@@ -673,6 +691,7 @@ struct gpe_ctx {
     gpe::ContactsWorkspace contacts_ws;
     gpe::ClustersWorkspace clusters_ws;
     gpe::EditWorkspace edit_ws;
+    gpe::SpawnWorkspace spawn_ws;
     gpe::ScanWorkspace scan_ws;
     gpe::OnesweepWorkspace os_ws;
     gpe::NativeState native;
@@ -818,6 +837,9 @@ uint64_t contacts_tiles(uint64_t n);
 gpe_status launch_contacts_keys(gpe_ctx *c, float cell_size, uint32_t *keys, uint32_t *vals);
 // rec[t] = the particle vals[t] (vals: sorted by key)
 gpe_status launch_contacts_records(gpe_ctx *c, const uint32_t *vals, uint4 *rec);
+// ... of any n rows (pos, radius): the candidates of gpe_add_particles_free
+gpe_status launch_contacts_records_of(gpe_ctx *c, const float2 *pos, const float *radius, const uint32_t *vals, uint64_t n,
+                                      uint4 *rec);
 // degree[i], upper[i] = contacts of particle i / those of higher index; *total = the sum of upper (tile_sum: contacts_tiles(n))
 gpe_status launch_contacts_count(gpe_ctx *c, const uint32_t *keys, const uint4 *rec, uint32_t *degree, uint32_t *upper,
                                  unsigned long long *tile_sum, unsigned long long *total);
@@ -840,6 +862,21 @@ gpe_status launch_clusters_member_count(gpe_ctx *c, const uint32_t *label, uint3
 gpe_status launch_clusters_member_gather(gpe_ctx *c, const uint32_t *label, uint32_t want, const uint32_t *tile_scanned,
                                          uint32_t capacity, uint32_t *index_out, uint32_t *uid_out, float2 *pos_out,
                                          float2 *prev_out, float *radius_out);
+// overlap-checked adds (k_spawn.hip); ws: the spawn workspace, k candidates uploaded into ws.pos / ws.radius
+// keys[i] = candidate i's clamped cell under cell_size, vals[i] = i, state[i] = OUTSIDE_WORLD or kSpawnUndecided (the
+// world test only when inside_world), ctl[0..3] = the cell box of the candidates that passed (set to all ones first)
+gpe_status launch_spawn_keys(gpe_ctx *c, const SpawnWorkspace &ws, uint32_t k, float cell_size, bool inside_world);
+// blocked[i] = 1 for every candidate i a particle of the context touches, 0 for the others (keys / rec sorted);
+// search false (every radius 0): nothing touches, no pass
+gpe_status launch_spawn_pass(gpe_ctx *c, const SpawnWorkspace &ws, uint32_t k, float cell_size, bool search);
+// state[i]: undecided becomes BLOCKED_BY_PARTICLE when blocked[i], else stays (separate) or becomes ADDED
+gpe_status launch_spawn_resolve(gpe_ctx *c, const SpawnWorkspace &ws, uint32_t k, bool separate);
+// one round of the separation over the undecided candidates; *left += those still undecided afterwards
+gpe_status launch_spawn_round(gpe_ctx *c, const SpawnWorkspace &ws, uint32_t k, float cell_size, uint32_t *left);
+// rank[i] = 1 when state[i] is ADDED (to be scanned), verdict[i] = state[i] as a byte; then the added candidates go to
+// old_n + rank[i] - 1 (rank scanned)
+gpe_status launch_spawn_flags(gpe_ctx *c, const SpawnWorkspace &ws, uint32_t k);
+gpe_status launch_spawn_scatter(gpe_ctx *c, const SpawnWorkspace &ws, uint32_t k, uint64_t old_n);
 // in-place edits (k_edit.hip).  Keyed edits: keys[i] becomes the storage index key i names (by_uid: looked up in the
 // sorted uid map of n entries; GPE_UID_ABSENT for an absent uid or an index >= n, the latter also sets kEditBadIndex in
 // flag[0]), slots[i] = i, flag[1] += the keys that name a particle.  flag zeroed by the caller.

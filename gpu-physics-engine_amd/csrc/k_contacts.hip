@@ -209,12 +209,18 @@ gpe_status launch_contacts_keys(gpe_ctx *c, float cell_size, uint32_t *keys, uin
     return GPE_OK;
 }
 
-gpe_status launch_contacts_records(gpe_ctx *c, const uint32_t *vals, uint4 *rec)
+gpe_status launch_contacts_records_of(gpe_ctx *c, const float2 *pos, const float *radius, const uint32_t *vals, uint64_t n,
+                                      uint4 *rec)
 {
-    hipLaunchKernelGGL(k_contacts_records, dim3(stream_grid(c->n)), dim3(kStreamBlock), 0, c->stream, c->pos, c->radius,
-                       vals, c->n, rec);
+    hipLaunchKernelGGL(k_contacts_records, dim3(stream_grid(n)), dim3(kStreamBlock), 0, c->stream, pos, radius, vals, n,
+                       rec);
     GPE_HIP(c, hipGetLastError());
     return GPE_OK;
+}
+
+gpe_status launch_contacts_records(gpe_ctx *c, const uint32_t *vals, uint4 *rec)
+{
+    return launch_contacts_records_of(c, c->pos, c->radius, vals, c->n, rec);
 }
 
 gpe_status launch_contacts_count(gpe_ctx *c, const uint32_t *keys, const uint4 *rec, uint32_t *degree, uint32_t *upper,

@@ -104,6 +104,27 @@ class Context:
     def call(self, name, *args):
         L.check(getattr(self.lib, name)(self.h, *args), self.h)
 
+    def add_particles_free(self, positions, radii, separate=False, inside_world=False, dry_run=False):
+        """gpe_add_particles_free: of the candidates (positions f32[k,2], radii f32[k]) append those with room -- not
+        touching a particle of the context, with `inside_world` inside the world by their radius, with `separate` not
+        touching an earlier accepted candidate either.  dry_run decides without appending.  Returns (added, verdict):
+        the number accepted and u8[k] of L.SPAWN_* per candidate, in input order."""
+        pos = np.ascontiguousarray(positions, np.float32).reshape(-1)
+        rad = np.ascontiguousarray(radii, np.float32).reshape(-1)
+        k = rad.shape[0]
+        if pos.shape[0] != 2 * k:
+            raise ValueError("positions and radii differ in length")
+        verdict = np.zeros(k, np.uint8)
+        flags = (L.SPAWN_SEPARATE if separate else 0) | (L.SPAWN_INSIDE_WORLD if inside_world else 0) | \
+            (L.SPAWN_DRY_RUN if dry_run else 0)
+        sp = L.GpeParticleSpawn(struct_size=C.sizeof(L.GpeParticleSpawn), flags=flags, k=k)
+        if k:
+            sp.pos_xy = pos.ctypes.data_as(C.POINTER(C.c_float))
+            sp.radius = rad.ctypes.data_as(C.POINTER(C.c_float))
+            sp.verdict = verdict.ctypes.data_as(C.POINTER(C.c_uint8))
+        self.call("gpe_add_particles_free", C.byref(sp))
+        return sp.added, verdict
+
     def sync(self):
         self.call("gpe_sync")
 
@@ -302,6 +323,11 @@ class ParticleSystem:
         pos = np.ascontiguousarray(positions, np.float32).reshape(-1, 2)
         rad = np.ascontiguousarray(radii, np.float32).reshape(-1)
         self.ctx.call("gpe_add_particles", _ptr(pos), _ptr(rad), pos.shape[0])
+
+    def add_particles_free(self, positions, radii, separate=False, inside_world=False, dry_run=False):
+        """Context.add_particles_free (gpe_add_particles_free, not in the reference) -> (added, verdict)."""
+        return self.ctx.add_particles_free(positions, radii, separate=separate, inside_world=inside_world,
+                                           dry_run=dry_run)
 
     def remove_particles(self, mask):
         """gpe_remove_particles (not in the reference): remove every particle i (storage order, as
@@ -749,6 +775,11 @@ class State:
     def add_particles(self, positions, radii):
         """state.rs:187-200."""
         self.particles.add_particles(positions, radii)
+
+    def add_particles_free(self, positions, radii, separate=False, inside_world=False, dry_run=False):
+        """Context.add_particles_free: append the candidates that have room -> (added, verdict)."""
+        return self.ctx.add_particles_free(positions, radii, separate=separate, inside_world=inside_world,
+                                           dry_run=dry_run)
 
     def remove_particles(self, mask):
         """ParticleSystem.remove_particles: the particles with mask[i] set leave; returns how many."""

@@ -175,6 +175,27 @@ class ParticleSystem {
     {
         ctx_->call(gpe_add_particles(ctx_->raw(), &positions[0].x, radii.data(), positions.size()));
     }
+    // not in the reference: of the candidates, append those that have room (include/gpe.h, gpe_add_particles_free) --
+    // not touching a particle; with GPE_SPAWN_INSIDE_WORLD inside the world by their radius; with GPE_SPAWN_SEPARATE not
+    // touching an earlier accepted candidate either.  GPE_SPAWN_DRY_RUN decides without appending.  Returns the number
+    // accepted; verdict (may be NULL) receives one GPE_SPAWN_* per candidate, in input order.
+    uint64_t add_particles_free(const std::vector<Vec2> &positions, const std::vector<float> &radii, uint32_t flags = 0,
+                                std::vector<uint8_t> *verdict = nullptr)
+    {
+        if (positions.size() != radii.size()) throw std::invalid_argument("positions and radii differ in length");
+        if (verdict) verdict->assign(radii.size(), 0);
+        gpe_particle_spawn sp{};
+        sp.struct_size = sizeof(gpe_particle_spawn);
+        sp.flags = flags;
+        sp.k = radii.size();
+        if (sp.k) {                                                          // (k == 0: the arrays are not read)
+            sp.pos_xy = &positions[0].x;
+            sp.radius = radii.data();
+            sp.verdict = verdict ? verdict->data() : nullptr;
+        }
+        ctx_->call(gpe_add_particles_free(ctx_->raw(), &sp));
+        return sp.added;
+    }
     // not in the reference: remove every particle i with remove[i] != 0 (storage order, len() entries) / every particle
     // whose centre lies in the disc around `center`; the survivors keep their order.  Returns the number removed.
     uint64_t remove_particles(const std::vector<uint8_t> &remove)

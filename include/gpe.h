@@ -395,6 +395,60 @@ gpe_status gpe_kick_circle(gpe_ctx *ctx, float x, float y, float radius,
 gpe_status gpe_kick_box(gpe_ctx *ctx, float x0, float y0, float x1, float y1,
                         uint32_t op, float ax, float ay, uint64_t *n_kicked);
 
+/* ---- adding particles where there is room (not in the reference) -----------------------------------------------
+ * gpe_add_particles appends whatever it is given, as the reference's add_particles does (particle_system.rs:163-220) --
+ * also on top of particles that exist, the commonest way to blow a pile apart.  gpe_add_particles_free filters the k
+ * candidates of a brush on the device first (csrc/k_spawn.hip): the candidates are binned by cell, the particles of the
+ * context stream past them once, and only the candidates with room are appended.  Nothing is downloaded but k verdicts.
+ *
+ * Every candidate gets exactly one verdict; the first rule that applies wins:
+ *  1. GPE_SPAWN_OUTSIDE_WORLD, only with GPE_SPAWN_INSIDE_WORLD: with a = fabsf(r) the candidate passes when
+ *     x >= a && x <= W - a && y >= a && y <= H - a, in IEEE binary32 with one rounding per operation, W and H as gpe_world
+ *     returns them.  A NaN fails the test.  Without the flag nothing is rejected here, as gpe_add_particles rejects
+ *     nothing.
+ *  2. GPE_SPAWN_BLOCKED_BY_PARTICLE: the candidate is in contact with at least one particle of the context.  "In contact"
+ *     is the predicate of gpe_query_contacts -- dx*dx + dy*dy < (ri + rj)*(ri + rj), the same binary32 operations, radii
+ *     as stored, a NaN anywhere compares false (such a candidate is never blocked).
+ *  3. GPE_SPAWN_BLOCKED_BY_CANDIDATE, only with GPE_SPAWN_SEPARATE: of the candidates rules 1 and 2 left, taken in
+ *     ascending input index, a candidate is blocked when it is in contact with a candidate of lower input index that was
+ *     itself ADDED.  This sequential greedy rule defines the result; the device reaches it in rounds whose number, but
+ *     not whose outcome, depends on the launch geometry and on the order in which waves run.
+ *  4. GPE_SPAWN_ADDED otherwise.
+ * Without GPE_SPAWN_DRY_RUN the ADDED candidates are appended in input order, and the context is what
+ * gpe_add_particles(those candidates' pos, radius) would have left: gpe_len, prev = pos, gpe_max_radius = fmaxf over the
+ * appended radii only, the grid max radius and the cell size, the index buffers, growth by doubling, the native
+ * re-derivation; with uids on the appended particles get next .. next + added - 1 in input order (next + added > 2^32:
+ * GPE_ERR_STATE, nothing added).  Every later step, in either mode, with or without re-sorts, is bit-identical to that of
+ * a twin context that made the plain add.  added == 0 and a dry run leave the context untouched, as gpe_query_contacts
+ * does: nothing a step can see changes, and the counters, the kept block table, the rosters, the uid map and the scratch
+ * index arrays stay as they were.  Synchronises, like gpe_add_particles.
+ *  - The search uses a cell size of its own, gpe_compute_cell_size(R), R = the larger of |gpe_max_radius| and the largest
+ *    |radius| among the candidates: a contact implies a centre distance below 2 R, so the 3 x 3 cell neighbourhood is
+ *    complete.  A gpe_grid_set_max_radius override plays no part.  R (or that cell size) not finite:
+ *    GPE_ERR_UNSUPPORTED.  R == 0: nothing touches, rules 2 and 3 block nobody.
+ *  - Positions of particles and of candidates may be anything gpe_set_particles accepts -- 1e30, +-inf, NaN, negative:
+ *    the verdicts are exactly the predicate's, and the search never reads or writes out of bounds for them.
+ *  - Errors: a NULL ctx or spawn, a NULL pos_xy or radius with k > 0, unknown flag bits, a struct_size below
+ *    sizeof(gpe_particle_spawn): GPE_ERR_INVALID_ARG; no particles yet: GPE_ERR_STATE, as gpe_add_particles; a sharded
+ *    context (gpe_shard_*, order keys or an active cell box), or gpe_len + k above the 2^30 - 1 particles
+ *    gpe_add_particles allows: GPE_ERR_UNSUPPORTED.  k == 0: GPE_OK, added = 0.  On any error added = 0, verdict is not
+ *    written and the context is untouched -- except that a NULL ctx and a struct_size below sizeof(gpe_particle_spawn)
+ *    leave `added` as it was too: the first is refused before the struct is looked at, and the second declares a struct
+ *    that ends before `added`, its last field. */
+enum { GPE_SPAWN_SEPARATE = 1u, GPE_SPAWN_INSIDE_WORLD = 2u, GPE_SPAWN_DRY_RUN = 4u };
+enum { GPE_SPAWN_ADDED = 0, GPE_SPAWN_BLOCKED_BY_PARTICLE = 1, GPE_SPAWN_BLOCKED_BY_CANDIDATE = 2,
+       GPE_SPAWN_OUTSIDE_WORLD = 3 };
+typedef struct gpe_particle_spawn {
+    uint32_t struct_size;     /* in: sizeof(gpe_particle_spawn)                                       */
+    uint32_t flags;           /* in: GPE_SPAWN_*; unknown bits: GPE_ERR_INVALID_ARG                   */
+    uint64_t k;               /* in: number of candidates                                             */
+    const float *pos_xy;      /* in: f32[2k]                                                          */
+    const float *radius;      /* in: f32[k]                                                           */
+    uint8_t  *verdict;        /* out, may be NULL: u8[k], GPE_SPAWN_* per candidate, input order      */
+    uint64_t added;           /* out: candidates with verdict ADDED (also in a dry run)               */
+} gpe_particle_spawn;         /* 48 bytes */
+gpe_status gpe_add_particles_free(gpe_ctx *ctx, gpe_particle_spawn *spawn);
+
 /* ---- grid (src/grid/grid.rs) ---------------------------------------------------------------- */
 /* Grid::compute_cell_size (:159-161) */
 float gpe_compute_cell_size(float max_obj_radius);
