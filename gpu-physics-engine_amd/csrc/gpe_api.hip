@@ -27,18 +27,6 @@ gpe_status fail(gpe_ctx *ctx, gpe_status code, const std::string &msg)
 }
 
 // ---- profiling scopes ---------------------------------------------------------------------------
-static hipEvent_t take_event(gpe_ctx *c)
-{
-    if (!c->event_pool.empty()) {
-        hipEvent_t e = c->event_pool.back();
-        c->event_pool.pop_back();
-        return e;
-    }
-    hipEvent_t e = nullptr;
-    if (hipEventCreate(&e) != hipSuccess) return nullptr;
-    return e;
-}
-
 static int stat_index(gpe_ctx *c, const char *name)
 {
     for (size_t i = 0; i < c->stats.size(); ++i)
@@ -49,48 +37,40 @@ static int stat_index(gpe_ctx *c, const char *name)
     return (int)c->stats.size() - 1;
 }
 
-Scope::Scope(gpe_ctx *ctx, const char *name) : ctx_(ctx)
+Scope::Scope(gpe_ctx *ctx, const char *name, Boundaries b) : ctx_(ctx), shared_(b == kSharedBoundaries)
 {
     if (!ctx_ || !ctx_->profiling) return;
     stat_ = stat_index(ctx_, name);
-    start_ = take_event(ctx_);
-    if (start_) (void)hipEventRecord(start_, ctx_->stream);
+    HipScopeBackend be{ctx_->stream};
+    start_ = ctx_->scope_events.open(be, shared_);
 }
 
 Scope::~Scope()
 {
-    if (!ctx_ || !start_) return;
-    hipEvent_t stop = take_event(ctx_);
-    if (!stop) { ctx_->event_pool.push_back(start_); return; }
-    (void)hipEventRecord(stop, ctx_->stream);
-    PendingEvent p;
-    p.stat = stat_;
-    p.start = start_;
-    p.stop = stop;
-    ctx_->pending.push_back(p);
+    if (!ctx_ || start_ < 0) return;
+    HipScopeBackend be{ctx_->stream};
+    ctx_->scope_events.close(be, start_, stat_, shared_);
 }
 
 constexpr size_t kTraceCap = 1u << 16;
 
+// (after a stream synchronisation) reads the pending pairs into the statistics and the trace; their events go back to
+// the pool, a shared one when the last pair that uses it has been read
 static void resolve_pending(gpe_ctx *c)
 {
-    for (const PendingEvent &p : c->pending) {
+    c->scope_events.resolve([c](int stat, hipEvent_t start, hipEvent_t stop) {
         float ms = 0.f;
-        if (hipEventElapsedTime(&ms, p.start, p.stop) == hipSuccess) {
-            c->stats[p.stat].total_ms += ms;
-            c->stats[p.stat].calls += 1;
-            float t0 = 0.f;
-            if (c->trace_origin && hipEventElapsedTime(&t0, c->trace_origin, p.start) == hipSuccess) {
-                if (c->trace.size() >= kTraceCap) c->trace.erase(c->trace.begin(), c->trace.begin() + kTraceCap / 2);
-                TraceEvent e;
-                e.stat = p.stat; e.start_ms = t0; e.dur_ms = ms;
-                c->trace.push_back(e);
-            }
+        if (hipEventElapsedTime(&ms, start, stop) != hipSuccess) return;
+        c->stats[stat].total_ms += ms;
+        c->stats[stat].calls += 1;
+        float t0 = 0.f;
+        if (c->trace_origin && hipEventElapsedTime(&t0, c->trace_origin, start) == hipSuccess) {
+            if (c->trace.size() >= kTraceCap) c->trace.erase(c->trace.begin(), c->trace.begin() + kTraceCap / 2);
+            TraceEvent e;
+            e.stat = stat; e.start_ms = t0; e.dur_ms = ms;
+            c->trace.push_back(e);
         }
-        c->event_pool.push_back(p.start);
-        c->event_pool.push_back(p.stop);
-    }
-    c->pending.clear();
+    });
 }
 
 // ---- device memory: payload, slack, red zones ------------------------------------------
@@ -898,7 +878,10 @@ gpe_status gpe_destroy(gpe_ctx *c)
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     resolve_pending(c);
-    for (hipEvent_t e : c->event_pool) (void)hipEventDestroy(e);
+    {
+        HipScopeBackend be{c->stream};
+        c->scope_events.destroy_all(be);
+    }
     if (c->trace_origin) (void)hipEventDestroy(c->trace_origin);
     free_particle_buffers(c);
     sort_release(c);

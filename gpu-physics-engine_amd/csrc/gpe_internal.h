@@ -10,6 +10,7 @@
 
 #include "../../include/gpe.h"
 #include "native_policy.h"
+#include "scope_events.h"
 
 namespace gpe {
 
@@ -246,9 +247,12 @@ struct ScopeStat {
     double total_ms = 0.0;
     uint64_t calls = 0;
 };
-struct PendingEvent {
-    int stat;
-    hipEvent_t start, stop;
+struct HipScopeBackend {             // the event calls behind ScopeEvents (scope_events.h), on the context's stream
+    using Event = hipEvent_t;
+    hipStream_t stream;
+    bool create(hipEvent_t *e) { return hipEventCreate(e) == hipSuccess; }
+    void record(hipEvent_t e) { (void)hipEventRecord(e, stream); }
+    void destroy(hipEvent_t e) { (void)hipEventDestroy(e); }
 };
 struct TraceEvent {                  // one resolved scope instance (gpe_get_trace)
     int stat;
@@ -705,8 +709,7 @@ struct gpe_ctx {
     uint32_t profile_every = 0;      // 0 off, 1 every call, k > 1: every k-th step (gpe_set_profiling)
     uint64_t profile_step = 0;
     std::vector<gpe::ScopeStat> stats;
-    std::vector<gpe::PendingEvent> pending;
-    std::vector<hipEvent_t> event_pool;
+    gpe::ScopeEvents<gpe::HipScopeBackend> scope_events;   // the scopes' events: pool, pending pairs, shared boundaries
     hipEvent_t trace_origin = nullptr;            // recorded when profiling is switched on / timings are reset
     std::vector<gpe::TraceEvent> trace;           // the last kTraceCap resolved scopes, oldest first
 };
@@ -750,16 +753,35 @@ inline hipError_t dev_release(gpe_ctx *c, T *&p)
     return gpe_dev_release(c, (void **)&p);
 }
 
-// profiling scope: a hipEvent pair on ctx->stream when ctx->profiling, else nothing.
+// profiling scope: a hipEvent pair on ctx->stream when ctx->profiling, else nothing.  kSharedBoundaries: inside a
+// ScopeRegion the scope takes the event a neighbouring scope recorded where nothing was enqueued between the two
+// (scope_events.h); the timings and the trace read the same, a sampled step records fewer events.
 class Scope {
    public:
-    Scope(gpe_ctx *ctx, const char *name);
+    enum Boundaries { kOwnEvents, kSharedBoundaries };
+    Scope(gpe_ctx *ctx, const char *name, Boundaries b = kOwnEvents);
     ~Scope();
 
    private:
     gpe_ctx *ctx_;
     int stat_ = -1;
-    hipEvent_t start_ = nullptr;
+    int start_ = -1;                 // slot of ctx->scope_events
+    bool shared_;
+};
+// Every enqueue onto c->stream inside a ScopeRegion says so (launches, async copies and memsets, event records other
+// than the scopes' own): that is what lets two scopes there share a boundary event.
+inline void note_enqueue(gpe_ctx *c) { c->scope_events.note_enqueue(); }
+// A stretch of host code whose enqueues all call note_enqueue (native_collide).  Boundaries are never shared across
+// its ends: the code outside enqueues without saying so.
+class ScopeRegion {
+   public:
+    explicit ScopeRegion(gpe_ctx *c) : c_(c) { c_->scope_events.enter_region(); }
+    ~ScopeRegion() { c_->scope_events.leave_region(); }
+    ScopeRegion(const ScopeRegion &) = delete;
+    ScopeRegion &operator=(const ScopeRegion &) = delete;
+
+   private:
+    gpe_ctx *c_;
 };
 
 // kernel launchers (one translation unit each) --------------------------------------------------

@@ -125,6 +125,7 @@ static gpe_status native_prepare_step(gpe_ctx *c, uint32_t **sorted_ids, bool al
     const uint64_t n = c->n;
     constexpr size_t kHistSet = (size_t)kHistCopies * 4 * 256;          // words of one set of digit histograms
     if (!c->os_ws.hist_clean) {                                        // another sort used the histograms since
+        note_enqueue(c);
         GPE_HIP(c, hipMemsetAsync(c->os_ws.hist4, 0, 2 * kHistSet * sizeof(uint32_t), c->stream));
         c->os_ws.hist_clean = true;
         c->os_ws.hist_set = 0;
@@ -187,7 +188,7 @@ static gpe_status native_prepare_step(gpe_ctx *c, uint32_t **sorted_ids, bool al
     // (block key / blocks_x = key * magic >> 40: OnesweepGate::key_div_magic)
     const uint64_t div_magic = ((1ull << 40) + (uint64_t)N.blocks_x - 1) / (uint64_t)N.blocks_x;
     {
-        Scope s(c, "native/hash");
+        Scope s(c, "native/hash", Scope::kSharedBoundaries);
         // at least 4 keys per lane (measured: profiles/r01/tune_hash.txt)
         // (two particles per thread until the grid is full: 14.0 against 14.3 us at 1 M with four, 15.2 with one --
         // the kernel is launch and latency there; from 4 M particles on the grid is kHashGridMax either way)
@@ -202,14 +203,14 @@ static gpe_status native_prepare_step(gpe_ctx *c, uint32_t **sorted_ids, bool al
                            N.exc_count ? N.exc_entry + (size_t)parity * N.exc_tiles * kExcSlots : nullptr,
                            N.exc_count ? N.exc_count + (size_t)(parity ^ 1u) * N.exc_tiles : nullptr, N.tb,
                            (uint32_t)std::max<uint64_t>(64, n >> 11),       // more stragglers than 0.05 % of the particles: sort
-                           fuse_hist ? 1u : 0u, hg);
+                           fuse_hist ? 1u : 0u, hg, (c->cfg.flags & GPE_FLAG_HASH_INDEX64) != 0);
         GPE_HIP(c, hipGetLastError());
     }
     uint32_t *sk = nullptr, *sv = nullptr;
     {
         // the last radix pass also fills the block table (first / one-past-last position of every block, by
         // atomic min / max at the ends of each tile's key runs); every pass derives its digit bases from hist_now
-        Scope s(c, "native/sort");
+        Scope s(c, "native/sort", Scope::kSharedBoundaries);
         OnesweepGate g;
         g.need = N.tile_ctl + kCtlNeedSort + parity;
         if (reuse && !fuse_hist) {
@@ -235,7 +236,7 @@ static gpe_status native_prepare_step(gpe_ctx *c, uint32_t **sorted_ids, bool al
     if (kept_sharded && g_bound > 0) {
         // the ghosts' own grouping: (block key, particle index) pairs written by the hash, sorted every step; the last
         // pass fills the ghosts' block table
-        Scope s(c, "shard/ghost-sort");
+        Scope s(c, "shard/ghost-sort", Scope::kSharedBoundaries);
         uint32_t *gk = nullptr, *gv = nullptr;
         OnesweepGate gg;                                               // (its own tile tickets; runs when a ghost list ran over,
         gg.ticket_base = 8;                                            //  or always when there are no lists)
@@ -544,6 +545,9 @@ gpe_status native_collide(gpe_ctx *c, const float2 *pos_in, float2 *pos_out, con
 {
     NativeState &N = c->native;
     uint32_t *sorted_ids = nullptr;
+    // Everything this function enqueues says so (note_enqueue: here, the launchers of k_native.hip, onesweep_sort), so
+    // its scopes share the events at their common boundaries: 7 records on a sampled kept-table step instead of 12.
+    ScopeRegion region(c);
     GPE_TRY(native_prepare_step(c, &sorted_ids));
     CollideArgs A;
     A.pos_in = pos_in;
@@ -607,6 +611,7 @@ gpe_status native_collide(gpe_ctx *c, const float2 *pos_in, float2 *pos_out, con
     A.pack = PackArgs();
     if (c->shard.on && c->shard.active && c->shard.have_rect && verlet && A.order_keys) shard_pack_args(c, &A.pack);
 #ifdef GPE_TILE_STAMPS
+    note_enqueue(c);                                                   // (it may copy and clear the stamps)
     A.stamps = native_tile_stamps(c);
 #endif
     int32_t cx0 = 0, cy0 = 0, cx1 = N.gx - 1, cy1 = N.gy - 1;
@@ -623,7 +628,7 @@ gpe_status native_collide(gpe_ctx *c, const float2 *pos_in, float2 *pos_out, con
     const NativeStats stats = native_read_stats(N);                   // (this call's decisions all read this one)
     bool direct_form = false;                                          // the dense launch runs direct-slot tiles
     {
-        Scope s(c, verlet ? "native/collide+verlet" : "native/collide");
+        Scope s(c, verlet ? "native/collide+verlet" : "native/collide", Scope::kSharedBoundaries);
         A.band_tiles = dense_launch_band((uint32_t)A.tiles_x, (uint32_t)A.tiles_y, (c->cfg.flags & GPE_FLAG_XCD_EIGHTHS) != 0);
         const uint32_t grid = dense_launch_grid((uint32_t)A.tiles_x, (uint32_t)A.tiles_y, A.band_tiles);
         // Which form of the tile?  The direct-slot form is the faster one while tiles fit it; it holds 928 particles and
@@ -676,6 +681,7 @@ gpe_status native_collide(gpe_ctx *c, const float2 *pos_in, float2 *pos_out, con
                         launch_collide(c, CollideForm::BorderOrd, frame, A);
                         GPE_HIP(c, hipGetLastError());
                     }
+                    note_enqueue(c);
                     GPE_HIP(c, hipEventRecord(SH.ev_packed, c->stream));
                     SH.packed_recorded = true;
                     // the interior: a tile box of its own (bands as above), nothing to pack
@@ -710,7 +716,7 @@ gpe_status native_collide(gpe_ctx *c, const float2 *pos_in, float2 *pos_out, con
         // workgroups (8 waves and 36 KB of LDS each) costs ~6 us, 8 % of the 1 M step.  While the tiles have reported no
         // over-capacity tile for a while (the statistic lags by the steps in flight) the grid is 128 workgroups; the
         // first reported tile brings the full grid back.  A surprise only makes that one step's launch slower.
-        Scope s(c, "native/collide-dense-regions");
+        Scope s(c, "native/collide-dense-regions", Scope::kSharedBoundaries);
         // (quiet_steps: since the dense launch last handed a tile on ITSELF -- hinted tiles do not count, they never reach
         // list 1; dense_quiet: since anything reached list 1 or list 2)
         // The half-tile launch: while the direct-slot launch has handed tiles on lately (lagged; either way is exact --
@@ -746,6 +752,7 @@ gpe_status native_collide(gpe_ctx *c, const float2 *pos_in, float2 *pos_out, con
     }
     // (a sharded step that did not split its tiles: everything has packed now)
     if (A.pack.on == 1u && c->shard.overlap && c->shard.ev_packed) {
+        note_enqueue(c);
         GPE_HIP(c, hipEventRecord(c->shard.ev_packed, c->stream));
         c->shard.packed_recorded = true;
     }

@@ -149,9 +149,13 @@ constexpr uint32_t kWindowReport = 512;     // tiles report windows above this p
 // (kHashBlock, kHashGridMax and HashGhosts: native_launch.h)
 constexpr int kHashBatch = 2;                  // positions loaded per lane before any of them is ranked
 // GHOSTS: a sharded run with its counts on the device (HashGhosts); the ordinary instantiation carries none of that code.
-template <bool GHOSTS>
+// Index: the type of the particle indices, the stride and the round counters.  uint32_t while every index the loop forms
+// stays below 2^31 (launch_native_hash: 1 M and 100 M particles both do) -- an address is then base + zero-extended index,
+// where the 64-bit form multiplies, shifts and adds register pairs on the VALU for each of the five arrays a particle
+// touches; uint64_t beyond that.  Same stores, same atomics in the same order, same bits either way.
+template <bool GHOSTS, typename Index>
 __global__ __launch_bounds__(kHashBlock, 8) void k_native_hash(const float2 *__restrict__ pos,
-                                                            const float *__restrict__ radius, uint64_t n,
+                                                            const float *__restrict__ radius, uint64_t n64,
                                                             const uint32_t *__restrict__ n_valid_ptr,
                                                             float cell_size, int32_t gx, int32_t gy,
                                                             int32_t bx0, int32_t by0, int32_t blocks_x,
@@ -179,7 +183,14 @@ __global__ __launch_bounds__(kHashBlock, 8) void k_native_hash(const float2 *__r
     __shared__ uint32_t s_hist[4 * 256];
     __shared__ uint32_t s_ghist[GHOSTS ? 4 * 256 : 1];                 // (the ghosts' keys, sharded runs)
     __shared__ uint32_t s_sort_known;                                  // a wave of this workgroup has seen the straggler limit passed
-    s_hist[threadIdx.x] = 0;
+    // The digit histograms of the owned particles' keys feed the radix passes -- which run on ~1 % of the steps of a run
+    // that keeps its block table (7-12 % at 100 M in free fall).  Such a run leaves them to a gated launch of its own
+    // behind this kernel (k_native_hist_gated: it returns at once unless need_sort was raised); only a step that sorts
+    // anyway (no kept table: first step, sort_hold, a run that sorts every step) counts them here, fused.
+    const bool fuse_hist = sorted_key == nullptr || fuse_always != 0u;   // (fuse_always: the host asks for the fused count as rounds 1-3 had it)
+    // (kernel-uniform) a step that counts nothing here neither zeroes s_hist nor reads it back in the flush
+    const bool ghost_hist = GHOSTS && (G.gkeys != nullptr || G.ghist_now != nullptr);
+    if (fuse_hist) s_hist[threadIdx.x] = 0;
     if (GHOSTS) s_ghist[threadIdx.x] = 0;
     if (threadIdx.x == 0) s_sort_known = 0u;
     // What a step accumulates into is reset here instead of by a launch of its own (a launch costs ~6 us, 5 % of
@@ -234,55 +245,53 @@ __global__ __launch_bounds__(kHashBlock, 8) void k_native_hash(const float2 *__r
         }
     }
     __syncthreads();
-    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    const uint64_t rounds = (n + stride - 1) / stride;
+    const Index n = (Index)n64;
+    const Index stride = (Index)gridDim.x * (Index)blockDim.x;
+    const Index rounds = (n + stride - 1) / stride;
+    const Index first_idx = (Index)blockIdx.x * (Index)blockDim.x + (Index)threadIdx.x;
     // Sharded runs keep the particle count on the device (the exchange changes it every step without a host
     // round trip): the host passes an upper bound n, slots [nv, n) are padding that sorts behind every block.
-    uint64_t nv = n;
+    Index nv = n;
     if (n_valid_ptr) {
-        nv = *n_valid_ptr;
-        if (nv > n) { nv = n; if (threadIdx.x == 0) atomicOr(&tile_ctl[kCtlError], kErrBoundExceeded); }
+        const uint32_t have = *n_valid_ptr;
+        if ((uint64_t)have > n64) { if (threadIdx.x == 0) atomicOr(&tile_ctl[kCtlError], kErrBoundExceeded); }
+        else nv = (Index)have;
     }
     // owned particles [0, n_own), ghosts [n_own, nv); indices from sorted_cnt on are not in the kept grouping
-    uint64_t n_own = nv;
-    if (GHOSTS && G.owned) n_own = min((uint64_t)*G.owned, nv);
-    const uint64_t sorted_cnt = (sorted_key && G.sorted_count) ? (uint64_t)*G.sorted_count : ~0ull;
+    Index n_own = nv;
+    if (GHOSTS && G.owned) n_own = min((Index)*G.owned, nv);
+    const Index sorted_cnt = (sorted_key && G.sorted_count) ? (Index)*G.sorted_count : ~(Index)0;
     if (GHOSTS && G.gkeys) {
         // ghost slots behind the last one the particle loop below reaches: padding (sorts behind every block)
-        const uint64_t first = n - n_own;
+        const uint64_t first = (uint64_t)(n - n_own);
         for (uint64_t j = first + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; j < G.g_bound; j += (uint64_t)gridDim.x * blockDim.x) {
             G.gkeys[j] = pad_key; G.gids[j] = 0u;
         }
-        if (nv - n_own > G.g_bound && threadIdx.x == 0) atomicOr(&tile_ctl[kCtlError], kErrBoundExceeded);
+        if ((uint64_t)(nv - n_own) > G.g_bound && threadIdx.x == 0) atomicOr(&tile_ctl[kCtlError], kErrBoundExceeded);
     }
     bool oob = false, drifted = false;
     bool sort_known = sorted_key == nullptr;                           // (wave-uniform) the radix passes will run this step
-    // The digit histograms of the owned particles' keys feed the radix passes -- which run on ~1 % of the steps of a run
-    // that keeps its block table (7-12 % at 100 M in free fall).  Such a run leaves them to a gated launch of its own
-    // behind this kernel (k_native_hist_gated: it returns at once unless need_sort was raised); only a step that sorts
-    // anyway (no kept table: first step, sort_hold, a run that sorts every step) counts them here, fused.
-    const bool fuse_hist = sorted_key == nullptr || fuse_always != 0u;   // (fuse_always: the host asks for the fused count as rounds 1-3 had it)
-    for (uint64_t r0 = 0; r0 < rounds; r0 += kHashBatch) {
+    for (Index r0 = 0; r0 < rounds; r0 += kHashBatch) {
         float2 p[kHashBatch];
         float rad[kHashBatch];
-        uint64_t idx[kHashBatch];
+        Index idx[kHashBatch];
         uint32_t okey[kHashBatch];
 #pragma unroll
         for (int u = 0; u < kHashBatch; ++u) {                        // the loads of a batch are in flight together
-            idx[u] = (r0 + u) * stride + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-            const bool in = r0 + u < rounds && idx[u] < nv;
+            idx[u] = (r0 + (Index)u) * stride + first_idx;
+            const bool in = r0 + (Index)u < rounds && idx[u] < nv;
             p[u] = in ? pos[idx[u]] : make_float2(0.f, 0.f);
             rad[u] = in ? radius[idx[u]] : 0.f;
             okey[u] = (in && sorted_key) ? sorted_key[idx[u]] : 0u;
         }
 #pragma unroll
         for (int u = 0; u < kHashBatch; ++u) {
-            if (r0 + u >= rounds) break;                               // wave-uniform
+            if (r0 + (Index)u >= rounds) break;                        // wave-uniform
             const bool valid = idx[u] < n;
             uint32_t key = pad_key;
             if (valid && idx[u] >= nv) {
                 keys[idx[u]] = pad_key; codes[idx[u]] = 0u;
-                if (GHOSTS && G.gkeys && idx[u] - n_own < G.g_bound) { G.gkeys[idx[u] - n_own] = pad_key; G.gids[idx[u] - n_own] = 0u; }
+                if (GHOSTS && G.gkeys && (uint64_t)(idx[u] - n_own) < G.g_bound) { G.gkeys[idx[u] - n_own] = pad_key; G.gids[idx[u] - n_own] = 0u; }
             }
             const bool ghost = GHOSTS && idx[u] >= n_own;
             uint32_t gkey = 0;
@@ -299,7 +308,7 @@ __global__ __launch_bounds__(kHashBlock, 8) void k_native_hash(const float2 *__r
                 key = out ? 0u : __umul24((uint32_t)lby, (uint32_t)blocks_x) + (uint32_t)lbx;
                 if (GHOSTS && ghost && G.gkeys) {
                     // a ghost: grouped by the ghosts' own sort; in the owned particles' sort it is padding
-                    const uint64_t j = idx[u] - n_own;
+                    const uint64_t j = (uint64_t)(idx[u] - n_own);
                     if (j < G.g_bound) { G.gkeys[j] = key; G.gids[j] = (uint32_t)idx[u]; gkey = key; gvalid = true; }
                     key = pad_key;
                 }
@@ -377,7 +386,7 @@ __global__ __launch_bounds__(kHashBlock, 8) void k_native_hash(const float2 *__r
         // The ghosts once more, for the tiles: every ghost is listed for each 32x32 tile whose window holds its cell (as
         // the stragglers above).  A loop of its own over the few thousand ghosts -- inside the particle loop the routing
         // pushed the kernel over its 64 registers.
-        for (uint64_t i = n_own + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += stride) {
+        for (Index i = n_own + first_idx; i < nv; i += stride) {
             const float2 p = pos[i];
             const int32_t cx = cell_coord(p.x, cell_size), cy = cell_coord(p.y, cell_size);
             if ((cx < 0) | (cx >= gx) | (cy < 0) | (cy >= gy)) continue;
@@ -394,21 +403,24 @@ __global__ __launch_bounds__(kHashBlock, 8) void k_native_hash(const float2 *__r
     }
     if (GHOSTS && G.gkeys && blockIdx.x == 0 && threadIdx.x < (uint32_t)digits) {
         // the ghost sort covers g_bound slots: those behind the ghosts hold the padding key
-        const uint64_t ng = min(nv - n_own, G.g_bound);
+        const uint64_t ng = min((uint64_t)(nv - n_own), G.g_bound);
         atomicAdd(&s_ghist[threadIdx.x * 256 + ((pad_key >> (8 * threadIdx.x)) & 255u)], (uint32_t)(G.g_bound - ng));
     }
     if (oob) atomicOr(&tile_ctl[kCtlError], kErrOutOfBox);
     if (ballot64(drifted) != 0 && lane_id() == 0) atomicOr(&tile_ctl[kCtlNeedSort + parity], 1u);
+    if (!fuse_hist && !ghost_hist) return;                             // (kernel-uniform) nothing was counted: nothing to flush
     __syncthreads();
     // Flush: fire-and-forget device-scope atomics (the kernel boundary makes them visible); the radix passes turn the
     // histograms into digit bases themselves (k_os_pass, hist_src), so no workgroup waits for the others here.
     if ((threadIdx.x & 1u) == 0) {
         // two neighbouring bins per 64-bit atomic (no bin reaches 2^32, so nothing carries into the upper one)
-        const uint32_t lo = s_hist[threadIdx.x], hi = s_hist[threadIdx.x + 1];   // index = digit * 256 + bin
-        if (fuse_hist && (lo | hi))
-            __hip_atomic_fetch_add(
-                reinterpret_cast<unsigned long long *>(&hist4[(blockIdx.x % kHistCopies) * 1024 + threadIdx.x]),
-                (unsigned long long)lo | ((unsigned long long)hi << 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (fuse_hist) {
+            const uint32_t lo = s_hist[threadIdx.x], hi = s_hist[threadIdx.x + 1];   // index = digit * 256 + bin
+            if (lo | hi)
+                __hip_atomic_fetch_add(
+                    reinterpret_cast<unsigned long long *>(&hist4[(blockIdx.x % kHistCopies) * 1024 + threadIdx.x]),
+                    (unsigned long long)lo | ((unsigned long long)hi << 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
         if (GHOSTS && G.ghist_now) {
             const uint32_t glo = s_ghist[threadIdx.x], ghi = s_ghist[threadIdx.x + 1];
             if (glo | ghi)
@@ -2874,9 +2886,14 @@ void launch_native_hash(gpe_ctx *c, bool ghosts, int grid, const float2 *pos, co
                         uint32_t *hist4, uint32_t *hist_next, uint32_t *os_ctl, uint32_t *tile_ctl, uint4 *table2,
                         uint64_t table_pairs, uint32_t *host_stat, const uint32_t *sorted_key, uint32_t parity,
                         uint64_t div_magic, uint32_t *exc_count, uint2 *exc_entry, uint32_t *exc_count_next, TileBox tb,
-                        uint32_t straggler_limit, uint32_t fuse_always, const HashGhosts &G)
+                        uint32_t straggler_limit, uint32_t fuse_always, const HashGhosts &G, bool index64)
 {
-    const auto hash_kernel = ghosts ? k_native_hash<true> : k_native_hash<false>;
+    note_enqueue(c);
+    // 32-bit indices while every index the kernel's loop forms -- up to kHashBatch strides past n -- stays below 2^31
+    // (index64: GPE_FLAG_HASH_INDEX64 asks for the 64-bit form regardless; the two give the same bits)
+    const bool narrow = !index64 && n + (uint64_t)grid * kHashBlock * kHashBatch < (1ull << 31);
+    const auto hash_kernel = ghosts ? (narrow ? k_native_hash<true, uint32_t> : k_native_hash<true, uint64_t>)
+                                    : (narrow ? k_native_hash<false, uint32_t> : k_native_hash<false, uint64_t>);
     hipLaunchKernelGGL(hash_kernel, dim3(grid), dim3(kHashBlock), 0, c->stream, pos, radius, n, n_valid_ptr, cell_size, gx,
                        gy, bx0, by0, blocks_x, blocks_y, pad_key, keys, codes, digits, hist4, hist_next, os_ctl, tile_ctl,
                        table2, table_pairs, host_stat, sorted_key, parity, div_magic, exc_count, exc_entry, exc_count_next,
@@ -2886,12 +2903,14 @@ void launch_native_hash(gpe_ctx *c, bool ghosts, int grid, const float2 *pos, co
 void launch_native_hist_gated(gpe_ctx *c, int grid, const uint32_t *keys, uint64_t n, int digits, uint32_t *hist4,
                               const uint32_t *need)
 {
+    note_enqueue(c);
     hipLaunchKernelGGL(k_native_hist_gated, dim3(grid), dim3(kHistGatedBlock), 0, c->stream, keys, n, digits, hist4, need);
 }
 
 void launch_native_check_box(gpe_ctx *c, const float2 *pos, uint64_t n, const uint32_t *n_valid_ptr, float cell_size,
                              int32_t gx, int32_t gy, uint32_t *flag)
 {
+    note_enqueue(c);
     hipLaunchKernelGGL(k_native_check_box, dim3(stream_grid(n)), dim3(kStreamBlock), 0, c->stream, pos, n, n_valid_ptr,
                        cell_size, gx, gy, flag);
 }
@@ -2899,12 +2918,14 @@ void launch_native_check_box(gpe_ctx *c, const float2 *pos, uint64_t n, const ui
 void launch_native_window_max(gpe_ctx *c, const uint2 *table, uint32_t entries, int32_t blocks_x, int32_t blocks_y,
                               uint32_t *out_max)
 {
+    note_enqueue(c);
     hipLaunchKernelGGL(k_native_window_max, dim3(stream_grid(entries)), dim3(kStreamBlock), 0, c->stream, table, entries,
                        blocks_x, blocks_y, out_max);
 }
 
 void launch_native_publish_probe(gpe_ctx *c, uint32_t *tile_ctl, uint32_t *host_stat)
 {
+    note_enqueue(c);
     hipLaunchKernelGGL(k_native_publish_probe, dim3(1), dim3(64), 0, c->stream, tile_ctl, host_stat);
 }
 
@@ -2912,6 +2933,7 @@ void launch_native_publish_probe(gpe_ctx *c, uint32_t *tile_ctl, uint32_t *host_
 // labels numbered, in that order, and scripts/kernel_isa_diff.sh compares the labels too.)
 void launch_collide(gpe_ctx *c, CollideForm form, uint32_t grid, const CollideArgs &A)
 {
+    note_enqueue(c);
     switch (form) {
     case CollideForm::DenseOrd:
         hipLaunchKernelGGL((k_collide_dense<kTileMain, kCapOrd, true>), dim3(grid), dim3(kNatThreads), 0, c->stream, A);

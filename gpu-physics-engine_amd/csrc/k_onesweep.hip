@@ -453,6 +453,7 @@ void onesweep_release(gpe_ctx *c)
 
 gpe_status onesweep_zero_hist(gpe_ctx *c)
 {
+    note_enqueue(c);
     GPE_HIP(c, hipMemsetAsync(c->os_ws.hist_plain, 0, 4 * 256 * sizeof(uint32_t), c->stream));
     return GPE_OK;
 }
@@ -476,14 +477,16 @@ gpe_status onesweep_sort(gpe_ctx *c, uint32_t *keys, uint32_t *vals, uint32_t *k
     OnesweepWorkspace &ws = c->os_ws;
     const uint64_t tiles = os_tiles(n);
     if (!hist_ready) {
-        Scope s(c, "sort/hist");
+        Scope s(c, "sort/hist", Scope::kSharedBoundaries);
         GPE_TRY(onesweep_zero_hist(c));
+        note_enqueue(c);
         hipLaunchKernelGGL(k_os_hist4, dim3(stream_grid(n, kStreamBlock)), dim3(kStreamBlock), 0, c->stream, keys, n,
                            ws.hist_plain);
         GPE_HIP(c, hipGetLastError());
     }
     if (!(hist_ready && bases_ready)) {
-        Scope s(c, "sort/prepare");
+        Scope s(c, "sort/prepare", Scope::kSharedBoundaries);
+        note_enqueue(c);
         hipLaunchKernelGGL(k_os_prepare, dim3(1), dim3(256), 0, c->stream, hist_ready ? ws.hist4 : ws.hist_plain, ws.bases4,
                            ws.ctl);
         GPE_HIP(c, hipGetLastError());
@@ -492,10 +495,11 @@ gpe_status onesweep_sort(gpe_ctx *c, uint32_t *keys, uint32_t *vals, uint32_t *k
     for (int p = 0; p < passes; ++p) {
         ws.epoch += 1;
         if (ws.epoch >= (1u << 30)) {             // epoch field is 30 bits: restart from a clean array
+            note_enqueue(c);
             GPE_HIP(c, hipMemsetAsync(ws.status, 0, ws.status_cap * sizeof(uint64_t), c->stream));
             ws.epoch = 1;
         }
-        Scope s(c, "sort/onesweep");
+        Scope s(c, "sort/onesweep", Scope::kSharedBoundaries);
         const bool iota = (p == 0 && iota_vals);
         const bool small = os_items(n) == kOsItemsSmall;
         const auto kern = small ? (iota ? k_os_pass<true, kOsItemsSmall> : k_os_pass<false, kOsItemsSmall>)
@@ -512,6 +516,7 @@ gpe_status onesweep_sort(gpe_ctx *c, uint32_t *keys, uint32_t *vals, uint32_t *k
             }
             if (last) { g.fresh = gate->fresh; g.sorts = gate->sorts; g.sorts_seen = gate->sorts_seen; }
         }
+        note_enqueue(c);
         hipLaunchKernelGGL(kern, dim3((uint32_t)tiles), dim3(kOsBlock), 0, c->stream, ka, va, kb, vb, n,
                            (uint32_t)(8 * p), (uint32_t)p, ws.bases4, (u64 *)ws.status, ws.ctl, ws.epoch,
                            last ? table : nullptr, table_entries, (hist_ready && bases_ready) ? hist_src : nullptr, g);
@@ -533,6 +538,7 @@ gpe_status onesweep_sort(gpe_ctx *c, uint32_t *keys, uint32_t *vals, uint32_t *k
                             " hops/tile %.1f spins/tile %.1f\n", (unsigned long long)n, passes, h[26], h[16] / nt, h[17] / nt,
                     h[18] / nt, h[19] / nt, h[20] / nt, h[24] / nt, h[25] / nt);
         }
+        note_enqueue(c);
         (void)hipMemsetAsync(ws.ctl + 16, 0, 16 * sizeof(uint32_t), c->stream);
     }
 #endif

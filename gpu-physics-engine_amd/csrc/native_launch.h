@@ -163,7 +163,7 @@ void launch_native_hash(gpe_ctx *c, bool ghosts, int grid, const float2 *pos, co
                         uint32_t *hist4, uint32_t *hist_next, uint32_t *os_ctl, uint32_t *tile_ctl, uint4 *table2,
                         uint64_t table_pairs, uint32_t *host_stat, const uint32_t *sorted_key, uint32_t parity,
                         uint64_t div_magic, uint32_t *exc_count, uint2 *exc_entry, uint32_t *exc_count_next, TileBox tb,
-                        uint32_t straggler_limit, uint32_t fuse_always, const HashGhosts &G);
+                        uint32_t straggler_limit, uint32_t fuse_always, const HashGhosts &G, bool index64);
 void launch_native_hist_gated(gpe_ctx *c, int grid, const uint32_t *keys, uint64_t n, int digits, uint32_t *hist4,
                               const uint32_t *need);
 // (these two cover their n / entries with a grid-stride loop: stream_grid)

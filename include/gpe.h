@@ -92,8 +92,10 @@ enum {
                                      /* one GPU the two cross-stream waits cost more than the exchange they hide)    */
     GPE_FLAG_FUSED_HISTOGRAMS = 512u,/* NATIVE: the hash kernel counts the radix digits every step (rounds 1-3)      */
                                      /* instead of a gated launch counting them when a sort is due; for A/B timing   */
-    GPE_FLAG_GUARD_ALLOCS = 1024u    /* tests: every device allocation of the context sits between two red zones     */
+    GPE_FLAG_GUARD_ALLOCS = 1024u,   /* tests: every device allocation of the context sits between two red zones     */
                                      /* filled with a canary, its fresh payload is poisoned (gpe_guard_check)        */
+    GPE_FLAG_HASH_INDEX64 = 2048u    /* NATIVE, diagnostic: the hash kernel indexes with 64 bits at every particle    */
+                                     /* count (by default only where an index could pass 2^31); for tests, A/B timing */
 };
 
 /* Fills *cfg with the reference's compile-time constants. */
