@@ -7,9 +7,19 @@ Whenever a constant or the arrays change on the host side, the next step builds 
 (with prev=), so a Sim never sees stale constants.  The step keeps no hidden state between calls (home cells and
 particle ids are rebuilt by every re-sort), which tests/test_oracle_model_cpu.py checks against one long-lived Sim.
 """
+import collections
+
 import numpy as np
 
+from tests import _clusters_model, _contacts_model, _spawn_model
+
 F32 = np.float32
+VEL_ADD, VEL_SET, VEL_SCALE = 0, 1, 2    # GPE_VEL_*
+# what the read-only calls deliver (the engine's QueryResult / ContactResult / ClusterResult, uid fields None while
+# uids are off)
+Rows = collections.namedtuple("Rows", "index uid pos prev radius")
+Contacts = collections.namedtuple("Contacts", "count degree a b uid_a uid_b overlap")
+Clusters = collections.namedtuple("Clusters", "label size label_uid count largest_size largest_label")
 CELL_SIZE_MULTIPLIER = F32(2.2)          # gpe_config_default, grid.rs:20
 
 
@@ -31,6 +41,41 @@ def circle_mask(pos, x, y, radius):
     return (dx * dx + dy * dy) <= F32(radius) * F32(radius)
 
 
+def box_mask(pos, x0, y0, x1, y1):
+    p = np.ascontiguousarray(pos, F32).reshape(-1, 2)
+    return (F32(x0) <= p[:, 0]) & (p[:, 0] <= F32(x1)) & (F32(y0) <= p[:, 1]) & (p[:, 1] <= F32(y1))
+
+
+def pick_oracle(pos, rad, x, y):
+    """argmin over (bits(d2), index) of the particles whose own disc contains (x, y), binary32 without FMA"""
+    p = np.ascontiguousarray(pos, F32).reshape(-1, 2)
+    r = np.ascontiguousarray(rad, F32)
+    dx = p[:, 0] - F32(x)
+    dy = p[:, 1] - F32(y)
+    d2 = dx * dx + dy * dy
+    inside = np.nonzero(d2 <= r * r)[0]
+    if inside.size == 0:
+        return None
+    keys = (d2[inside].view(np.uint32).astype(np.uint64) << np.uint64(32)) | inside.astype(np.uint64)
+    return int(inside[np.argmin(keys)])
+
+
+def kicked_prev(op, pos, prev, mask, a):
+    """The numpy float32 formula of include/gpe.h on the masked set, one rounding per operation."""
+    out = prev.copy()
+    for c in (0, 1):
+        p, q, ac = pos[mask, c], prev[mask, c], F32(a[c])
+        if op == VEL_ADD:
+            out[mask, c] = q - ac
+        elif op == VEL_SET:
+            out[mask, c] = p - ac
+        else:
+            v = p - q
+            v = v * ac
+            out[mask, c] = p - v
+    return out
+
+
 class OracleModel:
     def __init__(self, oracle, pos, radius, world=(3048.0, 1048.0), gravity=(0.0, 0.0), prev=None):
         self.o = oracle
@@ -46,6 +91,7 @@ class OracleModel:
         self.uids = None                                       # None: uids off
         self.next_uid = None
         self._sim = None
+        self._searched = None
 
     # ---- the state as a context reports it ----------------------------------------------------------------------
     def __len__(self):
@@ -155,6 +201,120 @@ class OracleModel:
     def remove_uids(self, uids):
         assert self.uids is not None
         return self._remove(np.isin(self.uids, np.asarray(uids, np.uint32)))
+
+    def add_free(self, cpos, crad, separate=False, inside_world=False, dry_run=False):
+        """gpe_add_particles_free -> (verdict u8[k], added): the verdicts of tests/_spawn_model.spawn against the
+        particles as they are, then -- unless dry_run -- add() of the ADDED rows.  A dry run and added == 0 change
+        nothing, a grid override included (add() of no rows returns before it touches anything)."""
+        self._pull()
+        verdict, p_new, r_new = _spawn_model.spawn(self.pos, self.radius, cpos, crad, self.world, separate=separate,
+                                                   inside_world=inside_world)
+        if not dry_run:
+            self.add(p_new, r_new)
+        return verdict, int(r_new.shape[0])
+
+    def edit(self, keys, by, pos=None, prev=None, radius=None):
+        """gpe_edit_particles -> edited.  by: "index" or "uid"; absent uids are skipped; row i of every array given goes
+        to the particle key i names; pos without prev puts the particle at rest (prev = pos).  radius given: max_radius
+        is recomputed over all particles and the grid radius follows it; radius None: both untouched, an override
+        included.  Uids and order are kept."""
+        assert by in ("index", "uid") and not (pos is None and prev is None and radius is None)
+        keys = np.asarray(keys, np.uint32).reshape(-1)
+        if by == "uid":
+            assert self.uids is not None
+            order = np.argsort(self.uids, kind="stable")
+            at = np.searchsorted(self.uids[order], keys)
+            at[at == len(order)] = 0
+            found = self.uids[order[at]] == keys
+            rows, who = np.nonzero(found)[0], order[at[found]]
+        else:
+            assert (keys < len(self)).all()
+            rows, who = np.arange(len(keys)), keys.astype(np.int64)
+        assert len(np.unique(who)) == len(who), "two keys name one particle: the context refuses that"
+        if len(keys) == 0:
+            return 0
+        self._pull()
+        if pos is not None:
+            p = np.asarray(pos, F32).reshape(-1, 2)[rows]
+            self.pos = self.pos.copy(); self.pos[who] = p
+            if prev is None:
+                self.prev = self.prev.copy(); self.prev[who] = p
+        if prev is not None:
+            self.prev = self.prev.copy(); self.prev[who] = np.asarray(prev, F32).reshape(-1, 2)[rows]
+        if radius is not None:
+            self.radius = self.radius.copy(); self.radius[who] = np.asarray(radius, F32).reshape(-1)[rows]
+            self.max_radius = max_abs_radius(self.radius)
+            self.grid_max_radius = self.max_radius
+        return int(len(who))
+
+    def kick(self, mask, op, ax, ay):
+        """gpe_kick_circle / gpe_kick_box on the particles of `mask` (circle_mask / box_mask of the current positions):
+        prev only, by the float32 formulas of GPE_VEL_ADD / SET / SCALE.  Returns the number kicked."""
+        self._pull()
+        mask = np.asarray(mask, bool)
+        self.prev = kicked_prev(op, self.pos, self.prev, mask, (ax, ay))
+        return int(mask.sum())
+
+    # ---- read-only queries: the rows a context returns ----------------------------------------------------------
+    def rows(self, index):
+        self._pull()
+        index = np.asarray(index, np.int64).reshape(-1)
+        return Rows(index.astype(np.uint32), None if self.uids is None else self.uids[index], self.pos[index],
+                    self.prev[index], self.radius[index])
+
+    def query_circle(self, x, y, radius):
+        self._pull()
+        return self.rows(np.nonzero(circle_mask(self.pos, x, y, radius))[0])
+
+    def query_box(self, x0, y0, x1, y1):
+        self._pull()
+        return self.rows(np.nonzero(box_mask(self.pos, x0, y0, x1, y1))[0])
+
+    def pick(self, x, y):
+        """gpe_pick: the rows of the one particle picked, or None."""
+        self._pull()
+        i = pick_oracle(self.pos, np.abs(self.radius), x, y)
+        return None if i is None else self.rows([i])
+
+    def _contacts(self):
+        """The brute-force search, kept for as long as pos and radius hold the same bits (a contact and a cluster
+        query on one state search once)."""
+        self._pull()
+        key = (self.pos.tobytes(), self.radius.tobytes())
+        if self._searched is None or self._searched[0] != key:
+            found = _contacts_model.contacts(self.pos, self.radius)
+            label = _clusters_model.labels_from_pairs(len(self), found[2], found[3])
+            self._searched = (key, found, label)
+        return self._searched[1]
+
+    def contacts(self):
+        """gpe_query_contacts: every pair (a caller cuts the per-pair arrays to its capacity)."""
+        count, degree, a, b, overlap = self._contacts()
+        ua = ub = None
+        if self.uids is not None:
+            ua, ub = self.uids[a], self.uids[b]
+        return Contacts(count, degree, a, b, ua, ub, overlap)
+
+    def clusters(self):
+        self._contacts()
+        label = self._searched[2]
+        size, count, largest_size, largest_label = _clusters_model.summary(label)
+        return Clusters(label, size, None if self.uids is None else self.uids[label], count, largest_size,
+                        largest_label)
+
+    def cluster_of(self, index=None, uid=None, label=None):
+        """gpe_query_cluster_of: the members of the cluster of particle `index`, or of the particle with `uid` (no rows
+        for an absent uid), ascending.  label: the labels of clusters(), when the caller has them already."""
+        assert (index is None) != (uid is None)
+        self._pull()
+        if uid is not None:
+            at = np.nonzero(self.uids == np.uint32(uid))[0]
+            if at.size == 0:
+                return self.rows([])
+            index = int(at[0])
+        if label is None:
+            label = self.clusters().label
+        return self.rows(np.nonzero(label == label[index])[0])
 
     # ---- constants ----------------------------------------------------------------------------------------------
     def set_world(self, w, h):

@@ -13,6 +13,7 @@ import tempfile
 import numpy as np
 import pytest
 
+import _interactive_sequences as interactive
 from _oracle_model import OracleModel, circle_mask
 
 pytestmark = pytest.mark.gpu
@@ -249,6 +250,31 @@ def test_random_api_sequences_match_the_oracle(gpe, oracle, seed, mode_name):
             assert counters.compat_steps > 0, log
     finally:
         st.close(); model.close(); tmp.cleanup()
+
+
+@pytest.mark.parametrize("seed", interactive.SEEDS)
+@pytest.mark.parametrize("mode_name", ["native", "compat"])
+def test_random_interactive_sequences_match_the_oracle(gpe, oracle, seed, mode_name):
+    """65-70 host calls on one State, planned by tests/_interactive_sequences.py: the calls of the test above, and between
+    them keyed edits by index and by uid (every field subset, absent uids, particles moved outside the world and back, a
+    new largest radius and the largest shrunk, with and without a grid override pending), kicks of all three ops (counted,
+    and uncounted with the next step enqueued behind them), gpe_add_particles_free with every flag combination, region
+    queries, picks, contact and cluster queries and flood selections at capacities below, at and above their counts.
+    After every call the State holds the model's bits; every query returns the model's rows and writes nothing behind
+    them; read-only calls, dry runs, adds of nothing and kicks leave native_sorts, roster_stamp and the step counters
+    alone; and the sequence reached what tests/test_interactive_sequences_cpu.py says it reaches."""
+    run = interactive.Sequence(interactive.plan(seed), oracle, gpe=gpe, mode_name=mode_name, compare=_compare)
+    try:
+        run.run()
+        print("\nseed %d %s: %d ops, native %d / compat %d steps, %d particles at the end; coverage %s" % (
+            seed, mode_name, len(run.plan.ops), run.native_steps, run.compat_steps, len(run.model), dict(run.cov)))
+        if mode_name == "native":
+            assert run.native_steps > 0, run.log
+        else:
+            assert run.compat_steps > 0, run.log
+        run.cov.check(run.plan.spawn_flags)
+    finally:
+        run.close()
 
 
 # ------------------------------------------------------------------------------------------------------------------------

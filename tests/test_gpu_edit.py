@@ -9,7 +9,7 @@ import importlib
 import numpy as np
 import pytest
 
-from tests._oracle_model import OracleModel, circle_mask
+from tests._oracle_model import OracleModel, box_mask, circle_mask, kicked_prev
 
 pytestmark = pytest.mark.gpu
 DT = 1.0 / 60.0
@@ -37,11 +37,6 @@ def _status_of(fn):
     with pytest.raises(_gpe().GpeError) as e:
         fn()
     return e.value.status
-
-
-def box_mask(pos, x0, y0, x1, y1):
-    p = np.ascontiguousarray(pos, F32).reshape(-1, 2)
-    return (F32(x0) <= p[:, 0]) & (p[:, 0] <= F32(x1)) & (F32(y0) <= p[:, 1]) & (p[:, 1] <= F32(y1))
 
 
 def _arrays(st):
@@ -383,23 +378,6 @@ def _kick_regions(pos, world):
              (-INF, -INF, INF, INF),                                     # everything
              (-1e6, -1e6, -1e5, -1e5)]                                   # nothing
     return circles, boxes
-
-
-def kicked_prev(op, pos, prev, mask, a):
-    """The numpy float32 formula of include/gpe.h on the masked set, one rounding per operation."""
-    L = _gpe()._lib
-    out = prev.copy()
-    for c in (0, 1):
-        p, q, ac = pos[mask, c], prev[mask, c], F32(a[c])
-        if op == L.VEL_ADD:
-            out[mask, c] = q - ac
-        elif op == L.VEL_SET:
-            out[mask, c] = p - ac
-        else:
-            v = p - q
-            v = v * ac
-            out[mask, c] = p - v
-    return out
 
 
 def _case_kicks(mode, n, flags=0):

@@ -310,6 +310,8 @@ QUERIES = _cases([
 SEQUENCES = _cases(
     [("native-equals-compat-%d" % s, "test_gpu_native", "test_random_api_sequences_native_equals_compat", dict(seed=s)) for s in (1, 2, 3)]
     + [("against-the-oracle-%s-%d" % (m, s), "test_gpu_api_sequences", "test_random_api_sequences_match_the_oracle", dict(seed=s, mode_name=m))
+       for m, s in (("native", 1), ("native", 2), ("compat", 2))]
+    + [("interactive-%s-%d" % (m, s), "test_gpu_api_sequences", "test_random_interactive_sequences_match_the_oracle", dict(seed=s, mode_name=m))
        for m, s in (("native", 1), ("native", 2), ("compat", 2))])
 
 _LG = "test_local_group_in_one_process_equals_single_context"

@@ -8,7 +8,7 @@ import importlib
 import numpy as np
 import pytest
 
-from tests._oracle_model import circle_mask
+from tests._oracle_model import box_mask, circle_mask, pick_oracle
 
 pytestmark = pytest.mark.gpu
 DT = 1.0 / 60.0
@@ -26,25 +26,6 @@ def _status_of(fn):
     with pytest.raises(gpe.GpeError) as e:
         fn()
     return e.value.status
-
-
-def box_mask(pos, x0, y0, x1, y1):
-    p = np.ascontiguousarray(pos, F32).reshape(-1, 2)
-    return (F32(x0) <= p[:, 0]) & (p[:, 0] <= F32(x1)) & (F32(y0) <= p[:, 1]) & (p[:, 1] <= F32(y1))
-
-
-def pick_oracle(pos, rad, x, y):
-    """argmin over (bits(d2), index) of the particles whose own disc contains (x, y), binary32 without FMA"""
-    p = np.ascontiguousarray(pos, F32).reshape(-1, 2)
-    r = np.ascontiguousarray(rad, F32)
-    dx = p[:, 0] - F32(x)
-    dy = p[:, 1] - F32(y)
-    d2 = dx * dx + dy * dy
-    inside = np.nonzero(d2 <= r * r)[0]
-    if inside.size == 0:
-        return None
-    keys = (d2[inside].view(np.uint32).astype(np.uint64) << np.uint64(32)) | inside.astype(np.uint64)
-    return int(inside[np.argmin(keys)])
 
 
 def _check_rows(st, got, want_index, uids_on):
