@@ -40,6 +40,7 @@ COUNTING_CHUNK_SIZE = 4
 POS, PREV, RADIUS, HOME_CELL_IDS, PARTICLE_IDS, CELL_IDS, OBJECT_IDS, COLLISION_CELLS, \
     NUM_COLLISION_CELLS, CHUNK_OBJ_COUNT, INDIRECT_ARGS, ORDER_KEYS, UIDS = range(13)
 UID_ABSENT = 0xFFFFFFFF
+RAY_MISS = 0xFFFFFFFF
 EDIT_BY_INDEX, EDIT_BY_UID = 0, 1
 CLUSTER_BY_INDEX, CLUSTER_BY_UID = 0, 1
 VEL_ADD, VEL_SET, VEL_SCALE = 0, 1, 2
@@ -142,6 +143,14 @@ class GpeClusterResult(C.Structure):
                 ("size", C.POINTER(C.c_uint32)), ("label_uid", C.POINTER(C.c_uint32))]
 
 
+class GpeRayCast(C.Structure):
+    """gpe_ray_cast: in struct_size / flags / k and the endpoint arrays, out hits; every output pointer may be NULL."""
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("k", C.c_uint64),
+                ("from_xy", C.POINTER(C.c_float)), ("to_xy", C.POINTER(C.c_float)), ("index", C.POINTER(C.c_uint32)),
+                ("uid", C.POINTER(C.c_uint32)), ("t", C.POINTER(C.c_float)), ("pos_xy", C.POINTER(C.c_float)),
+                ("radius", C.POINTER(C.c_float)), ("hits", C.c_uint64)]
+
+
 class GpeParticleEdit(C.Structure):
     """gpe_particle_edit: in struct_size / key_kind / k / keys and the field arrays (each may be NULL), out edited."""
     _fields_ = [("struct_size", C.c_uint32), ("key_kind", C.c_uint32), ("k", C.c_uint64),
@@ -201,6 +210,8 @@ SYMBOLS = [
     ("gpe_query_contacts", _I32, [_VP, C.POINTER(GpeContactResult)]),
     ("gpe_query_clusters", _I32, [_VP, C.POINTER(GpeClusterResult)]),
     ("gpe_query_cluster_of", _I32, [_VP, _U32, _U32, C.POINTER(GpeQueryResult)]),
+    ("gpe_cast_rays", _I32, [_VP, C.POINTER(GpeRayCast)]),
+    ("gpe_query_segment", _I32, [_VP, _F, _F, _F, _F, C.POINTER(GpeQueryResult)]),
     ("gpe_edit_particles", _I32, [_VP, C.POINTER(GpeParticleEdit)]),
     ("gpe_add_particles_free", _I32, [_VP, C.POINTER(GpeParticleSpawn)]),
     ("gpe_kick_circle", _I32, [_VP, _F, _F, _F, _U32, _F, _F, C.POINTER(_U64)]),

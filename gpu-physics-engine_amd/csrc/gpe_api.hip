@@ -7,6 +7,7 @@
 
 #include <algorithm>
 #include <functional>
+#include <limits>
 #include <mutex>
 #include <new>
 
@@ -275,6 +276,10 @@ static void free_particle_buffers(gpe_ctx *c)
     dev_free(c, k.keys); dev_free(c, k.vals); dev_free(c, k.rec); dev_free(c, k.degree); dev_free(c, k.upper);
     dev_free(c, k.tile_sum); dev_free(c, k.total); dev_free(c, k.stage);
     k.cap = k.tiles_cap = k.stage_cap = 0;
+    RayWorkspace &y = c->ray_ws;
+    dev_free(c, y.row_start); dev_free(c, y.from); dev_free(c, y.to); dev_free(c, y.index); dev_free(c, y.uid);
+    dev_free(c, y.t); dev_free(c, y.pos); dev_free(c, y.radius);
+    y.cap = 0;
     ClustersWorkspace &u = c->clusters_ws;
     dev_free(c, u.parent); dev_free(c, u.label); dev_free(c, u.root_size); dev_free(c, u.size);
     dev_free(c, u.tile_word); dev_free(c, u.words);
@@ -1324,8 +1329,8 @@ static gpe_status query_deliver(gpe_ctx *c, gpe_query_result *out, uint32_t tota
     return GPE_OK;
 }
 
-// Count (and, for requested rows, gather) the particles in the region; region as launch_query_count takes it.
-static gpe_status do_query(gpe_ctx *c, bool box, const float *region, gpe_query_result *out)
+// Count (and, for requested rows, gather) the particles in the region; kind and region as launch_query_count takes them.
+static gpe_status do_query(gpe_ctx *c, int kind, const float *region, gpe_query_result *out)
 {
     GPE_HIP(c, hipSetDevice(c->device));
     GPE_HIP(c, hipStreamSynchronize(c->stream));
@@ -1336,7 +1341,7 @@ static gpe_status do_query(gpe_ctx *c, bool box, const float *region, gpe_query_
     Scope s(c, "Query particles");
     {
         Scope k(c, "query/count");
-        GPE_TRY(launch_query_count(c, box, region, ws.tile_count));
+        GPE_TRY(launch_query_count(c, kind, region, ws.tile_count));
     }
     {
         Scope k(c, "query/scan");
@@ -1346,7 +1351,7 @@ static gpe_status do_query(gpe_ctx *c, bool box, const float *region, gpe_query_
     GPE_HIP(c, hipStreamSynchronize(c->stream));
     return query_deliver(c, out, total, "query/gather",
                          [&](uint32_t m, uint32_t *d_index, uint32_t *d_uid, float2 *d_pos, float2 *d_prev, float *d_radius) {
-                             return launch_query_gather(c, box, region, c->query_ws.tile_count, m, d_index, d_uid, d_pos,
+                             return launch_query_gather(c, kind, region, c->query_ws.tile_count, m, d_index, d_uid, d_pos,
                                                         d_prev, d_radius);
                          });
 }
@@ -1380,7 +1385,7 @@ gpe_status gpe_query_circle(gpe_ctx *c, float x, float y, float radius, gpe_quer
     GPE_TRY(query_begin(c, out, "gpe_query_circle", &go));
     GPE_TRY(circle_region(c, "gpe_query_circle", x, y, radius, region));
     if (!go) return GPE_OK;
-    return do_query(c, false, region, out);
+    return do_query(c, 0, region, out);
 }
 
 gpe_status gpe_query_box(gpe_ctx *c, float x0, float y0, float x1, float y1, gpe_query_result *out)
@@ -1391,7 +1396,18 @@ gpe_status gpe_query_box(gpe_ctx *c, float x0, float y0, float x1, float y1, gpe
     GPE_TRY(query_begin(c, out, "gpe_query_box", &go));
     GPE_TRY(box_region(c, "gpe_query_box", x0, y0, x1, y1, region, &empty));
     if (!go || empty) return GPE_OK;                              // an empty box holds nothing
-    return do_query(c, true, region, out);
+    return do_query(c, 1, region, out);
+}
+
+gpe_status gpe_query_segment(gpe_ctx *c, float x0, float y0, float x1, float y1, gpe_query_result *out)
+{
+    bool go = false;
+    GPE_TRY(query_begin(c, out, "gpe_query_segment", &go));
+    if (!isfinite(x0) || !isfinite(y0) || !isfinite(x1) || !isfinite(y1))
+        return fail(c, GPE_ERR_INVALID_ARG, "gpe_query_segment: an endpoint is not finite");
+    if (!go) return GPE_OK;
+    const float region[5] = {x0, y0, x1, y1, 0.f};
+    return do_query(c, 2, region, out);
 }
 
 gpe_status gpe_pick(gpe_ctx *c, float x, float y, gpe_query_result *out)
@@ -1760,6 +1776,116 @@ gpe_status gpe_query_cluster_of(gpe_ctx *c, uint32_t key_kind, uint32_t key, gpe
                              return launch_clusters_member_gather(c, ws.label, want, c->query_ws.tile_count, m, d_index,
                                                                   d_uid, d_pos, d_prev, d_radius);
                          });
+}
+
+// ---- ray casts (k_raycast.hip) ------------------------------------------------------------------------------
+static gpe_status ray_alloc(gpe_ctx *c, void **p, uint64_t payload, const char *tag)
+{
+    const hipError_t e = gpe_dev_reserve(c, p, payload, 0, tag);
+    if (e == hipErrorOutOfMemory) return fail(c, GPE_ERR_OOM, "gpe_cast_rays: out of device memory");
+    if (e != hipSuccess) return fail(c, GPE_ERR_HIP, std::string("gpe_cast_rays: ") + hipGetErrorName(e));
+    return GPE_OK;
+}
+
+// room for a batch of k rays; every array is read and written by index below k or kRayRowWords.  no slack
+static gpe_status ray_reserve(gpe_ctx *c, uint64_t k)
+{
+    RayWorkspace &ws = c->ray_ws;
+    if (!ws.row_start) GPE_TRY(ray_alloc(c, (void **)&ws.row_start, kRayRowWords * sizeof(uint32_t), "ray.row_start"));
+    if (ws.cap < k) {
+        dev_free(c, ws.from); dev_free(c, ws.to); dev_free(c, ws.index); dev_free(c, ws.uid); dev_free(c, ws.t);
+        dev_free(c, ws.pos); dev_free(c, ws.radius);
+        ws.cap = 0;
+        GPE_TRY(ray_alloc(c, (void **)&ws.from, k * sizeof(float2), "ray.from"));
+        GPE_TRY(ray_alloc(c, (void **)&ws.to, k * sizeof(float2), "ray.to"));
+        GPE_TRY(ray_alloc(c, (void **)&ws.index, k * sizeof(uint32_t), "ray.index"));
+        GPE_TRY(ray_alloc(c, (void **)&ws.uid, k * sizeof(uint32_t), "ray.uid"));
+        GPE_TRY(ray_alloc(c, (void **)&ws.t, k * sizeof(float), "ray.t"));
+        GPE_TRY(ray_alloc(c, (void **)&ws.pos, k * sizeof(float2), "ray.pos"));
+        GPE_TRY(ray_alloc(c, (void **)&ws.radius, k * sizeof(float), "ray.radius"));
+        ws.cap = k;
+    }
+    return GPE_OK;
+}
+
+// every ray misses: the host fills the requested outputs
+static void ray_fill_misses(gpe_ray_cast *r)
+{
+    const uint64_t k = r->k;
+    const float nan = std::numeric_limits<float>::quiet_NaN();
+    if (r->index) std::fill(r->index, r->index + k, GPE_RAY_MISS);
+    if (r->uid) std::fill(r->uid, r->uid + k, GPE_UID_ABSENT);
+    if (r->t) std::fill(r->t, r->t + k, nan);
+    if (r->pos_xy) std::fill(r->pos_xy, r->pos_xy + 2 * k, nan);
+    if (r->radius) std::fill(r->radius, r->radius + k, nan);
+}
+
+gpe_status gpe_cast_rays(gpe_ctx *c, gpe_ray_cast *r)
+{
+    const char *who = "gpe_cast_rays";
+    if (!c) return GPE_ERR_INVALID_ARG;
+    if (!r) return fail(c, GPE_ERR_INVALID_ARG, std::string(who) + ": NULL cast");
+    if (r->struct_size < sizeof(gpe_ray_cast))             // hits is the last field: a smaller struct has none
+        return fail(c, GPE_ERR_INVALID_ARG, std::string(who) + ": struct_size is smaller than gpe_ray_cast");
+    r->hits = 0;
+    if (r->flags != 0) return fail(c, GPE_ERR_INVALID_ARG, std::string(who) + ": flags must be 0");
+    const uint64_t k = r->k;
+    if (k > 0 && (!r->from_xy || !r->to_xy)) return fail(c, GPE_ERR_INVALID_ARG, std::string(who) + ": NULL endpoints");
+    if (is_sharded(c))
+        return fail(c, GPE_ERR_UNSUPPORTED, std::string(who) + ": not supported on a sharded context (gpe_shard_*, "
+                                                                "order keys or an active cell box)");
+    if (r->uid && !c->uid.on) return fail(c, GPE_ERR_STATE, std::string(who) + ": uid requested while uids are off");
+    if (c->n > 0xFFFFFFFFull) return fail(c, GPE_ERR_UNSUPPORTED, std::string(who) + ": more than 2^32 - 1 particles");
+    if (k == 0) return GPE_OK;
+    const bool any = c->n > 0 && c->pos;
+    // the contact query's own cell size: a touched centre lies within max|r| = cell / 2.2 of its segment
+    const float cell_size = any ? gpe_compute_cell_size(fabsf(c->max_radius)) : 0.0f;
+    if (!isfinite(cell_size)) return fail(c, GPE_ERR_UNSUPPORTED, std::string(who) + ": the largest radius is not finite");
+    const float bound = cell_size > 0.0f ? 131072.0f * cell_size : std::numeric_limits<float>::infinity();
+    for (uint64_t i = 0; i < 2 * k; ++i) {
+        const float a = r->from_xy[i], b = r->to_xy[i];
+        if (!isfinite(a) || !isfinite(b) || !(fabsf(a) <= bound) || !(fabsf(b) <= bound))
+            return fail(c, GPE_ERR_INVALID_ARG, std::string(who) + ": an endpoint is not finite or lies more than 131072 "
+                                                                   "cells from the origin");
+    }
+    if (!any || !(cell_size > 0.0f)) {                          // no particles, or every radius 0: nothing can be hit
+        ray_fill_misses(r);
+        return GPE_OK;
+    }
+    GPE_HIP(c, hipSetDevice(c->device));
+    GPE_HIP(c, hipStreamSynchronize(c->stream));
+    const uint64_t batch = std::min<uint64_t>(k, kRayMaxBatch);
+    GPE_TRY(ray_reserve(c, batch));
+    RayWorkspace &ws = c->ray_ws;
+    Scope s(c, "Cast rays");
+    GPE_TRY(contacts_bin(c, cell_size));
+    {
+        Scope q(c, "rays/rows");
+        GPE_TRY(launch_ray_row_start(c, c->contacts_ws.keys, ws.row_start));
+    }
+    std::vector<uint32_t> index(batch);
+    uint64_t hits = 0;
+    for (uint64_t base = 0; base < k; base += batch) {
+        const uint64_t m = std::min<uint64_t>(batch, k - base);
+        GPE_HIP(c, hipMemcpyAsync(ws.from, r->from_xy + 2 * base, m * sizeof(float2), hipMemcpyHostToDevice, c->stream));
+        GPE_HIP(c, hipMemcpyAsync(ws.to, r->to_xy + 2 * base, m * sizeof(float2), hipMemcpyHostToDevice, c->stream));
+        {
+            Scope q(c, "rays/cast");
+            GPE_TRY(launch_ray_cast(c, ws.from, ws.to, (uint32_t)m, cell_size, c->contacts_ws.keys, c->contacts_ws.rec,
+                                    ws.row_start, ws.index, r->uid ? ws.uid : nullptr, r->t ? ws.t : nullptr,
+                                    r->pos_xy ? ws.pos : nullptr, r->radius ? ws.radius : nullptr));
+        }
+        GPE_HIP(c, hipMemcpyAsync(index.data(), ws.index, m * 4, hipMemcpyDeviceToHost, c->stream));
+        if (r->uid) GPE_HIP(c, hipMemcpyAsync(r->uid + base, ws.uid, m * 4, hipMemcpyDeviceToHost, c->stream));
+        if (r->t) GPE_HIP(c, hipMemcpyAsync(r->t + base, ws.t, m * 4, hipMemcpyDeviceToHost, c->stream));
+        if (r->pos_xy) GPE_HIP(c, hipMemcpyAsync(r->pos_xy + 2 * base, ws.pos, m * 8, hipMemcpyDeviceToHost, c->stream));
+        if (r->radius) GPE_HIP(c, hipMemcpyAsync(r->radius + base, ws.radius, m * 4, hipMemcpyDeviceToHost, c->stream));
+        GPE_HIP(c, hipStreamSynchronize(c->stream));
+        for (uint64_t i = 0; i < m; ++i) hits += index[i] != GPE_RAY_MISS;
+        if (r->index) std::copy(index.begin(), index.begin() + m, r->index + base);
+    }
+    r->hits = hits;
+    return GPE_OK;
 }
 
 // ---- overlap-checked adds (k_spawn.hip) --------------------------------------------------------------------

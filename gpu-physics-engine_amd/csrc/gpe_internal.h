@@ -295,6 +295,17 @@ struct ContactsWorkspace {       // gpe_query_contacts (k_contacts.hip); allocat
     uint64_t stage_cap = 0;                      // bytes
 };
 
+struct RayWorkspace {            // gpe_cast_rays (k_raycast.hip); allocated at first use, freed with the particles
+    uint32_t *row_start = nullptr;               // kRayRowWords: per clamped row, its first slot of the sorted keys
+    float2 *from = nullptr, *to = nullptr;       // the uploaded endpoints of one batch of rays
+    uint32_t *index = nullptr, *uid = nullptr;   // per ray of the batch: the first hit's row
+    float *t = nullptr, *radius = nullptr;
+    float2 *pos = nullptr;
+    uint64_t cap = 0;                            // rays the seven arrays above hold
+};
+constexpr uint32_t kRayRowWords = 65537;         // rows 0 .. 65535 of the clamped key and the end of the last one
+constexpr uint32_t kRayMaxBatch = 1u << 20;      // rays per launch; gpe_cast_rays walks a longer list in batches
+
 struct ClustersWorkspace {       // gpe_query_clusters / gpe_query_cluster_of (k_clusters.hip); allocated at first use, freed with the particles
     uint32_t *parent = nullptr;                  // the union-find forest: parent[i] <= i; after the flatten free for label_uid
     uint32_t *label = nullptr;                   // per particle: the lowest index of its cluster
@@ -694,6 +705,7 @@ struct gpe_ctx {
     gpe::QueryWorkspace query_ws;
     gpe::ContactsWorkspace contacts_ws;
     gpe::ClustersWorkspace clusters_ws;
+    gpe::RayWorkspace ray_ws;
     gpe::EditWorkspace edit_ws;
     gpe::SpawnWorkspace spawn_ws;
     gpe::ScanWorkspace scan_ws;
@@ -845,11 +857,12 @@ gpe_status launch_max_key_fold(gpe_ctx *c, const unsigned long long *tile_key, u
 gpe_status launch_remove_scatter(gpe_ctx *c, const uint8_t *mask, float x, float y, float rr,
                                  const uint32_t *tile_scanned, const uint32_t *uids = nullptr,
                                  uint32_t *uids_out = nullptr);
-// region queries and picking (k_query.hip): region = {x, y, -, -, radius^2} (circle) or {x0, y0, x1, y1, -} (box)
+// region queries and picking (k_query.hip): kind = a QueryKind of k_region.h (0 circle, 1 box, 2 segment); region =
+// {x, y, -, -, radius^2} (circle), {x0, y0, x1, y1, -} (box) or {from x, from y, to x, to y, -} (segment)
 uint64_t query_tiles(uint64_t n);
-gpe_status launch_query_count(gpe_ctx *c, bool box, const float *region, uint32_t *tile_count);
+gpe_status launch_query_count(gpe_ctx *c, int kind, const float *region, uint32_t *tile_count);
 // the matches ranked below capacity into the non-NULL outputs (uid_out: from c->uid.uids)
-gpe_status launch_query_gather(gpe_ctx *c, bool box, const float *region, const uint32_t *tile_scanned,
+gpe_status launch_query_gather(gpe_ctx *c, int kind, const float *region, const uint32_t *tile_scanned,
                                uint32_t capacity, uint32_t *index_out, uint32_t *uid_out, float2 *pos_out,
                                float2 *prev_out, float *radius_out);
 // *pick = min over the particles whose disc contains (x, y) of bits(d2) << 32 | index (~0 for none)
@@ -869,6 +882,14 @@ gpe_status launch_contacts_count(gpe_ctx *c, const uint32_t *keys, const uint4 *
 gpe_status launch_contacts_gather(gpe_ctx *c, const uint32_t *keys, const uint4 *rec, const uint32_t *scanned,
                                   uint32_t capacity, uint32_t *index_a, uint32_t *index_b, uint32_t *uid_a, uint32_t *uid_b,
                                   float *overlap);
+// ray casts (k_raycast.hip); keys / rec: the contact query's sorted cell keys and records under cell_size
+// row_start[y] = the first sorted slot with key >= y << 16, y = 0 .. 65536 (kRayRowWords words)
+gpe_status launch_ray_row_start(gpe_ctx *c, const uint32_t *keys, uint32_t *row_start);
+// the first hit of each of the k <= kRayMaxBatch rays from[i] -> to[i] into row i of the non-NULL outputs (index
+// GPE_RAY_MISS, uid GPE_UID_ABSENT and NaN for a miss; uid_out: from c->uid.uids).  Endpoints finite, within 131072 cells
+gpe_status launch_ray_cast(gpe_ctx *c, const float2 *from, const float2 *to, uint32_t k, float cell_size,
+                           const uint32_t *keys, const uint4 *rec, const uint32_t *row_start, uint32_t *index_out,
+                           uint32_t *uid_out, float *t_out, float2 *pos_out, float *radius_out);
 // contact clusters (k_clusters.hip); keys / rec: the contact query's sorted cell keys and records
 // parent[i] = i, then every contact (i, j < i) unites the trees of i and j: parent[x] <= x, a component's root is its lowest index
 gpe_status launch_clusters_hook(gpe_ctx *c, const uint32_t *keys, const uint4 *rec, uint32_t *parent);

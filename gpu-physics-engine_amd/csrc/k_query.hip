@@ -1,5 +1,5 @@
-// k_query.hip -- region queries and point picking (gpe_query_circle / gpe_query_box / gpe_pick): full passes over the
-// live set on the device (gfx950, wave64) that read the particles and change nothing.
+// k_query.hip -- region queries and point picking (gpe_query_circle / gpe_query_box / gpe_query_segment / gpe_pick):
+// full passes over the live set on the device (gfx950, wave64) that read the particles and change nothing.
 //
 // Not on the per-step path, so the plain form:
 //   (1) k_query_count: each workgroup takes one tile of kQueryBlock x kQueryRounds consecutive particles, in rounds of
@@ -15,7 +15,8 @@
 //       k_pick_fold folds the tiles' keys into one word with at most kPickFoldBlocks 64-bit atomics (device-scope
 //       atomics on one address serialise; see k_remove_max_key).
 // Bytes per particle: count R 8 B (pos); gather R 8 B per particle of a tile it does not skip, plus R 4 + 8 + 8 + 4 + 4 B
-// and W 4 + 8 + 8 + 4 + 4 B per written match for index / pos / prev / radius / uid; pick R 12 B (pos, radius).
+// and W 4 + 8 + 8 + 4 + 4 B per written match for index / pos / prev / radius / uid; pick R 12 B (pos, radius).  The
+// segment kind (gpe_query_segment: ray_touches of k_ray.h) reads the radius too: count and gather R 12 B.
 // 100 M particles: count 0.124 ms, pick 0.190 ms, about 0.8 of the HBM peak (profiles/query/).
 #include <algorithm>
 
@@ -25,14 +26,15 @@ namespace gpe {
 
 // (1) matches per tile
 template <int KIND>
-__global__ __launch_bounds__(kQueryBlock) void k_query_count(QueryRegion Q, const float2 *__restrict__ pos, uint64_t n,
+__global__ __launch_bounds__(kQueryBlock) void k_query_count(QueryRegion Q, const float2 *__restrict__ pos,
+                                                             const float *__restrict__ radius, uint64_t n,
                                                              uint32_t *__restrict__ tile_count)
 {
     __shared__ uint32_t s_cnt[kQueryWaves];
     const uint64_t first = (uint64_t)blockIdx.x * kQueryTile + threadIdx.x;
     float2 p[kQueryRounds];
     bool hit[kQueryRounds];
-    matches_of_tile<KIND>(Q, pos, n, first, p, hit);
+    matches_of_tile<KIND>(Q, pos, n, first, p, hit, radius);
     uint32_t cnt = 0;                                          // wave-uniform
 #pragma unroll
     for (int r = 0; r < kQueryRounds; ++r) cnt += (uint32_t)__popcll(ballot64(hit[r]));
@@ -72,7 +74,7 @@ __global__ __launch_bounds__(kQueryBlock) void k_query_gather(QueryRegion Q, con
     const int w = (int)(threadIdx.x >> 6);
     float2 p[kQueryRounds];
     bool hit[kQueryRounds];
-    matches_of_tile<KIND>(Q, pos, n, first, p, hit);
+    matches_of_tile<KIND>(Q, pos, n, first, p, hit, radius);
     uint64_t vote[kQueryRounds];
 #pragma unroll
     for (int r = 0; r < kQueryRounds; ++r) {
@@ -184,18 +186,20 @@ static gpe_status check_tiles(gpe_ctx *c, uint64_t tiles)
     return GPE_OK;
 }
 
-gpe_status launch_query_count(gpe_ctx *c, bool box, const float *region, uint32_t *tile_count)
+gpe_status launch_query_count(gpe_ctx *c, int kind, const float *region, uint32_t *tile_count)
 {
     const uint64_t tiles = query_tiles(c->n);
     GPE_TRY(check_tiles(c, tiles));
     const QueryRegion Q{region[0], region[1], region[2], region[3], region[4]};
-    const auto kern = box ? k_query_count<kQueryBox> : k_query_count<kQueryCircle>;
-    hipLaunchKernelGGL(kern, dim3((uint32_t)tiles), dim3(kQueryBlock), 0, c->stream, Q, c->pos, c->n, tile_count);
+    const auto kern = kind == kQuerySegment ? k_query_count<kQuerySegment>
+                      : kind == kQueryBox   ? k_query_count<kQueryBox>
+                                            : k_query_count<kQueryCircle>;
+    hipLaunchKernelGGL(kern, dim3((uint32_t)tiles), dim3(kQueryBlock), 0, c->stream, Q, c->pos, c->radius, c->n, tile_count);
     GPE_HIP(c, hipGetLastError());
     return GPE_OK;
 }
 
-gpe_status launch_query_gather(gpe_ctx *c, bool box, const float *region, const uint32_t *tile_scanned,
+gpe_status launch_query_gather(gpe_ctx *c, int kind, const float *region, const uint32_t *tile_scanned,
                                uint32_t capacity, uint32_t *index_out, uint32_t *uid_out, float2 *pos_out,
                                float2 *prev_out, float *radius_out)
 {
@@ -203,7 +207,9 @@ gpe_status launch_query_gather(gpe_ctx *c, bool box, const float *region, const 
     GPE_TRY(check_tiles(c, tiles));
     const QueryRegion Q{region[0], region[1], region[2], region[3], region[4]};
     const QueryOut O{index_out, uid_out, pos_out, prev_out, radius_out};
-    const auto kern = box ? k_query_gather<kQueryBox> : k_query_gather<kQueryCircle>;
+    const auto kern = kind == kQuerySegment ? k_query_gather<kQuerySegment>
+                      : kind == kQueryBox   ? k_query_gather<kQueryBox>
+                                            : k_query_gather<kQueryCircle>;
     hipLaunchKernelGGL(kern, dim3((uint32_t)tiles), dim3(kQueryBlock), 0, c->stream, Q, c->pos, c->prev, c->radius,
                        (const uint32_t *)c->uid.uids, c->n, tile_scanned, capacity, O);
     GPE_HIP(c, hipGetLastError());

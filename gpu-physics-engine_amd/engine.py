@@ -37,6 +37,8 @@ ContactResult = collections.namedtuple("ContactResult", "a b uid_a uid_b overlap
 # gpe_query_clusters: per particle the lowest index of its contact cluster, that cluster's size and the uid of particle
 # label[i] (None while uids are off); the number of clusters, and the size and label of the largest one
 ClusterResult = collections.namedtuple("ClusterResult", "label size label_uid count largest_size largest_label")
+# cast_rays: one row per ray; index L.RAY_MISS, uid L.UID_ABSENT and NaN for a miss; uid / pos / radius None unless requested
+RayHits = collections.namedtuple("RayHits", "index t uid pos radius hits")
 
 
 class Context:
@@ -452,6 +454,43 @@ class ParticleSystem:
         """gpe_query_box with no outputs: the number of particles query_box would return."""
         return self._count("gpe_query_box", (float(lo[0]), float(lo[1]), float(hi[0]), float(hi[1])))
 
+    # Ray casts and segment queries (not in the reference; include/gpe.h): what each ray hits first, walked on the device
+    # along the contact query's cell table, and everything one segment crosses.  The context is left exactly as it was.
+    def cast_rays(self, origins, ends, uids=False, rows=False):
+        """gpe_cast_rays -> RayHits(index, t, uid, pos, radius, hits): per ray from origins[i] to ends[i] the storage
+        index of the first particle it touches (L.RAY_MISS for none) and the fraction t of the way there (NaN for none);
+        uids=True adds the uids, rows=True the hit particles' centres and stored radii."""
+        origins = np.ascontiguousarray(origins, np.float32)
+        ends = np.ascontiguousarray(ends, np.float32)
+        if origins.ndim != 2 or origins.shape[1] != 2 or origins.shape != ends.shape:
+            raise ValueError("cast_rays: origins and ends must both be (k, 2), got %r and %r" % (origins.shape, ends.shape))
+        k = origins.shape[0]
+        room = max(k, 1)
+        f32, u32 = C.POINTER(C.c_float), C.POINTER(C.c_uint32)
+        index, t = np.empty(room, np.uint32), np.empty(room, np.float32)
+        uid = np.empty(room, np.uint32) if uids else None
+        pos = np.empty((room, 2), np.float32) if rows else None
+        rad = np.empty(room, np.float32) if rows else None
+        cast = L.GpeRayCast(struct_size=C.sizeof(L.GpeRayCast), flags=0, k=k)
+        cast.from_xy, cast.to_xy = origins.ctypes.data_as(f32), ends.ctypes.data_as(f32)
+        cast.index, cast.t = index.ctypes.data_as(u32), t.ctypes.data_as(f32)
+        if uids:
+            cast.uid = uid.ctypes.data_as(u32)
+        if rows:
+            cast.pos_xy, cast.radius = pos.ctypes.data_as(f32), rad.ctypes.data_as(f32)
+        self.ctx.call("gpe_cast_rays", C.byref(cast))
+        return RayHits(index[:k], t[:k], uid[:k] if uids else None, pos[:k] if rows else None,
+                       rad[:k] if rows else None, cast.hits)
+
+    def query_segment(self, a, b):
+        """gpe_query_segment -> QueryResult of every particle the segment from a to b touches (the function cast_rays
+        applies), ascending by index."""
+        return self._query("gpe_query_segment", (float(a[0]), float(a[1]), float(b[0]), float(b[1])))
+
+    def count_segment(self, a, b):
+        """gpe_query_segment with no outputs: the number of particles query_segment would return."""
+        return self._count("gpe_query_segment", (float(a[0]), float(a[1]), float(b[0]), float(b[1])))
+
     # Contact queries (not in the reference; include/gpe.h): which particles touch -- dx*dx + dy*dy < (ri + rj)^2 in
     # float32 -- and how many neighbours each one has, searched on the device.  The context is left exactly as it was.
     def contacts(self, capacity=None, overlap=False):
@@ -848,6 +887,17 @@ class State:
     def cluster_of(self, index=None, uid=None, capacity=None):
         """ParticleSystem.cluster_of -> QueryResult of the cluster that holds the particle `index` or `uid`."""
         return self.particles.cluster_of(index=index, uid=uid, capacity=capacity)
+
+    def cast_rays(self, origins, ends, uids=False, rows=False):
+        """ParticleSystem.cast_rays -> RayHits(index, t, uid, pos, radius, hits): the first hit of every ray."""
+        return self.particles.cast_rays(origins, ends, uids=uids, rows=rows)
+
+    def query_segment(self, a, b):
+        """ParticleSystem.query_segment -> QueryResult of everything the segment from a to b touches."""
+        return self.particles.query_segment(a, b)
+
+    def count_segment(self, a, b):
+        return self.particles.count_segment(a, b)
 
     def count_circle(self, center, radius):
         return self.particles.count_circle(center, radius)

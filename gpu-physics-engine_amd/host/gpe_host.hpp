@@ -366,6 +366,50 @@ class ParticleSystem {
         const uint32_t kind = by_uid ? GPE_CLUSTER_BY_UID : GPE_CLUSTER_BY_INDEX;
         return query([&](gpe_query_result *r) { return gpe_query_cluster_of(ctx_->raw(), kind, key, r); });
     }
+    // not in the reference: what each ray from origins[i] to ends[i] touches first, and everything one segment crosses
+    // (include/gpe.h), on the device.  cast_rays(): one row per ray -- index GPE_RAY_MISS, uid GPE_UID_ABSENT and NaN for a
+    // miss; uid only with with_uids (uids must be on), pos / radius only with rows.
+    struct RayHits {
+        std::vector<uint32_t> index, uid;
+        std::vector<float> t, radius;
+        std::vector<Vec2> pos;
+        uint64_t hits = 0;
+    };
+    RayHits cast_rays(const std::vector<Vec2> &origins, const std::vector<Vec2> &ends, bool with_uids = false,
+                      bool rows = false) const
+    {
+        if (origins.size() != ends.size()) throw std::invalid_argument("cast_rays: origins and ends differ in length");
+        const size_t k = origins.size();
+        RayHits q;
+        q.index.resize(k);
+        q.t.resize(k);
+        q.uid.resize(with_uids ? k : 0);
+        q.pos.resize(rows ? k : 0);
+        q.radius.resize(rows ? k : 0);
+        gpe_ray_cast r{};
+        r.struct_size = sizeof(r);
+        r.k = k;
+        r.from_xy = k ? &origins[0].x : nullptr;
+        r.to_xy = k ? &ends[0].x : nullptr;
+        r.index = k ? q.index.data() : nullptr;
+        r.t = k ? q.t.data() : nullptr;
+        r.uid = with_uids && k ? q.uid.data() : nullptr;
+        r.pos_xy = rows && k ? &q.pos[0].x : nullptr;
+        r.radius = rows && k ? q.radius.data() : nullptr;
+        ctx_->call(gpe_cast_rays(ctx_->raw(), &r));
+        q.hits = r.hits;
+        return q;
+    }
+    QueryResult query_segment(Vec2 a, Vec2 b) const
+    {
+        return query([&](gpe_query_result *r) { return gpe_query_segment(ctx_->raw(), a.x, a.y, b.x, b.y, r); });
+    }
+    uint64_t count_segment(Vec2 a, Vec2 b) const
+    {
+        gpe_query_result r = empty_query();
+        ctx_->call(gpe_query_segment(ctx_->raw(), a.x, a.y, b.x, b.y, &r));
+        return r.count;
+    }
     // not in the reference: edit particles in place on the device (include/gpe.h).  The particles named by `keys` --
     // storage indices, or uids with by_uid -- take row i of every array given (NULL: that field stays; positions without
     // previous: at rest, prev = pos).  Unknown uids are skipped.  Returns the number of particles written.

@@ -336,6 +336,69 @@ gpe_status gpe_query_clusters(gpe_ctx *ctx, gpe_cluster_result *out);
 enum { GPE_CLUSTER_BY_INDEX = 0, GPE_CLUSTER_BY_UID = 1 };
 gpe_status gpe_query_cluster_of(gpe_ctx *ctx, uint32_t key_kind, uint32_t key, gpe_query_result *out);
 
+/* ---- ray casts and segment queries (not in the reference) -----------------------------------------------------
+ * What a ray hits first (line of sight, a laser, a fan of distance sensors) and which particles a stroke crosses (a
+ * cut, a line eraser), without downloading positions and radii: gpe_cast_rays walks the contact query's cell-binned
+ * table along each ray on the device (csrc/k_raycast.hip), gpe_query_segment is a full pass (csrc/k_query.hip).
+ *  - Both apply one function (csrc/k_ray.h) to the segment from o = (ox, oy) to e = (ex, ey) and a particle with centre
+ *    c and stored radius r, in IEEE binary32, one rounding per operation, left to right, no FMA, `/` and sqrtf
+ *    correctly rounded (numpy float32 gives the same bits):
+ *        a = |r|;  rr = a*a;                     if !(a > 0): miss         (radius 0 or NaN is never hit; a negative
+ *        dx = ex-ox; dy = ey-oy; fx = ox-cx; fy = oy-cy                     radius acts as its magnitude, as in gpe_pick)
+ *        A = dx*dx + dy*dy;  C = fx*fx + fy*fy
+ *        if C <= rr: touched, t = +0             (the origin lies in the closed disc; also the zero-length ray)
+ *        if !(A > 0): miss
+ *        B = fx*dx + fy*dy;  u = (-B) / A
+ *        qx = fx + u*dx;  qy = fy + u*dy;  h = qx*qx + qy*qy
+ *        if !(h <= rr): miss
+ *        w = sqrtf((rr - h) / A);  t = u - w
+ *        touched iff t >= 0 && t <= 1            (a t of -0 counts as, and is delivered as, +0)
+ *    A NaN anywhere makes a comparison false: a miss.  This is the closest-approach form; it has no B*B - A*C
+ *    cancellation.
+ *  - gpe_cast_rays: for ray i the result is the touched particle with the smallest t, the lowest storage index on a
+ *    tie.  Every output array may be NULL; hits is always set.  A miss delivers GPE_RAY_MISS, GPE_UID_ABSENT and quiet
+ *    NaNs.
+ *  - The cast's search uses the contact query's own cell size, gpe_compute_cell_size(|gpe_max_radius|): a
+ *    gpe_grid_set_max_radius override plays no part, and the caveat about a negative radius of larger magnitude added
+ *    later is that of gpe_query_contacts.  That cell size not finite (an infinite radius): GPE_ERR_UNSUPPORTED.  0
+ *    (every radius 0): GPE_OK, every ray misses.
+ *  - Endpoints, checked on the host over the caller's arrays before anything is written: every coordinate must be
+ *    finite and, while the cell size is positive, satisfy |v| <= 131072 * cell_size; else GPE_ERR_INVALID_ARG.  Any
+ *    supported world passes (65 000 cells per axis is the native limit); a host clips longer rays itself.  The bound
+ *    keeps the rounding of the walk's own arithmetic a small fraction of a cell, which is what makes the walk complete.
+ *  - Particle positions may be anything gpe_set_particles accepts -- outside the world, 1e30, +-inf, NaN: the result
+ *    is exactly the function's, and nothing reads or writes out of bounds for them.
+ *  - Both calls change nothing on the context, as gpe_query_contacts: positions, prev, radii, uids, the uid map, the
+ *    scratch index arrays, the native step / sort counters, the kept block table and the rosters are left alone; the
+ *    steps after a call are bit-identical to those of a context that was never queried.  They work in both modes and at
+ *    any point between steps, and block like gpe_download.
+ *  - Errors of gpe_cast_rays: a NULL context, a NULL cast, a struct_size below sizeof(gpe_ray_cast), non-zero flags, a
+ *    NULL from_xy or to_xy with k > 0: GPE_ERR_INVALID_ARG; uid requested while uids are off: GPE_ERR_STATE; a sharded
+ *    context (gpe_shard_*, order keys or an active cell box) and more than 2^32 - 1 particles: GPE_ERR_UNSUPPORTED.  On
+ *    every error hits is 0 (when the struct is usable) and no output is written.
+ *  - k == 0: GPE_OK, hits 0.  No particles: GPE_OK, every ray misses. */
+#define GPE_RAY_MISS 0xffffffffu
+typedef struct gpe_ray_cast {
+    uint32_t struct_size;   /* in: sizeof(gpe_ray_cast)                                       */
+    uint32_t flags;         /* in: 0; anything else GPE_ERR_INVALID_ARG                       */
+    uint64_t k;             /* in: number of rays                                             */
+    const float *from_xy;   /* in: f32[2k]                                                    */
+    const float *to_xy;     /* in: f32[2k]                                                    */
+    uint32_t *index;        /* out, may be NULL: storage index of the first hit, GPE_RAY_MISS */
+    uint32_t *uid;          /* out, may be NULL: its uid, GPE_UID_ABSENT for a miss           */
+    float    *t;            /* out, may be NULL: fraction of the way from `from` to `to`; quiet NaN for a miss */
+    float    *pos_xy;       /* out, may be NULL: f32[2k] the hit particle's centre; NaN for a miss */
+    float    *radius;       /* out, may be NULL: f32[k] its stored radius; NaN for a miss     */
+    uint64_t hits;          /* out: rays that hit something                                   */
+} gpe_ray_cast;             /* 80 bytes */
+gpe_status gpe_cast_rays(gpe_ctx *ctx, gpe_ray_cast *cast);
+
+/* Everything the segment from (x0, y0) to (x1, y1) crosses: a particle matches when the function above says touched.
+ * Delivery, errors and the untouched context are exactly those of gpe_query_box.  A non-finite endpoint:
+ * GPE_ERR_INVALID_ARG; there is no bound on its magnitude, the full pass needs none.  The first hit of gpe_cast_rays
+ * for the same segment is the member of this set with the least t; a miss there means the set is empty. */
+gpe_status gpe_query_segment(gpe_ctx *ctx, float x0, float y0, float x1, float y1, gpe_query_result *out);
+
 /* ---- editing particles in place (not in the reference) --------------------------------------------------------
  * Change particles that exist, on the device (csrc/k_edit.hip), without the download / gpe_set_particles detour that
  * would drop the uids, the kept block table and the native counters.  Two kinds of call:
