@@ -41,6 +41,8 @@ POS, PREV, RADIUS, HOME_CELL_IDS, PARTICLE_IDS, CELL_IDS, OBJECT_IDS, COLLISION_
     NUM_COLLISION_CELLS, CHUNK_OBJ_COUNT, INDIRECT_ARGS, ORDER_KEYS, UIDS = range(13)
 UID_ABSENT = 0xFFFFFFFF
 RAY_MISS = 0xFFFFFFFF
+NEAREST_NONE = 0xFFFFFFFF
+NEAREST_MAX_M = 64
 EDIT_BY_INDEX, EDIT_BY_UID = 0, 1
 CLUSTER_BY_INDEX, CLUSTER_BY_UID = 0, 1
 VEL_ADD, VEL_SET, VEL_SCALE = 0, 1, 2
@@ -151,6 +153,16 @@ class GpeRayCast(C.Structure):
                 ("radius", C.POINTER(C.c_float)), ("hits", C.c_uint64)]
 
 
+class GpeNearestQuery(C.Structure):
+    """gpe_nearest_query: in struct_size / flags / k / point_xy / m / max_distance, out found; every output pointer may be
+    NULL (count u32[k], the others m slots per point)."""
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("k", C.c_uint64),
+                ("point_xy", C.POINTER(C.c_float)), ("m", C.c_uint32), ("max_distance", C.c_float),
+                ("count", C.POINTER(C.c_uint32)), ("index", C.POINTER(C.c_uint32)), ("uid", C.POINTER(C.c_uint32)),
+                ("dist2", C.POINTER(C.c_float)), ("pos_xy", C.POINTER(C.c_float)), ("radius", C.POINTER(C.c_float)),
+                ("found", C.c_uint64)]
+
+
 class GpeParticleEdit(C.Structure):
     """gpe_particle_edit: in struct_size / key_kind / k / keys and the field arrays (each may be NULL), out edited."""
     _fields_ = [("struct_size", C.c_uint32), ("key_kind", C.c_uint32), ("k", C.c_uint64),
@@ -212,6 +224,7 @@ SYMBOLS = [
     ("gpe_query_cluster_of", _I32, [_VP, _U32, _U32, C.POINTER(GpeQueryResult)]),
     ("gpe_cast_rays", _I32, [_VP, C.POINTER(GpeRayCast)]),
     ("gpe_query_segment", _I32, [_VP, _F, _F, _F, _F, C.POINTER(GpeQueryResult)]),
+    ("gpe_query_nearest", _I32, [_VP, C.POINTER(GpeNearestQuery)]),
     ("gpe_edit_particles", _I32, [_VP, C.POINTER(GpeParticleEdit)]),
     ("gpe_add_particles_free", _I32, [_VP, C.POINTER(GpeParticleSpawn)]),
     ("gpe_kick_circle", _I32, [_VP, _F, _F, _F, _U32, _F, _F, C.POINTER(_U64)]),

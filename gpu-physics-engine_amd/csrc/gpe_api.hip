@@ -280,6 +280,10 @@ static void free_particle_buffers(gpe_ctx *c)
     dev_free(c, y.row_start); dev_free(c, y.from); dev_free(c, y.to); dev_free(c, y.index); dev_free(c, y.uid);
     dev_free(c, y.t); dev_free(c, y.pos); dev_free(c, y.radius);
     y.cap = 0;
+    NearestWorkspace &nn = c->nearest_ws;
+    dev_free(c, nn.row_start); dev_free(c, nn.points); dev_free(c, nn.count); dev_free(c, nn.index); dev_free(c, nn.uid);
+    dev_free(c, nn.dist2); dev_free(c, nn.pos); dev_free(c, nn.radius);
+    nn.cap = nn.slots_cap = 0;
     ClustersWorkspace &u = c->clusters_ws;
     dev_free(c, u.parent); dev_free(c, u.label); dev_free(c, u.root_size); dev_free(c, u.size);
     dev_free(c, u.tile_word); dev_free(c, u.words);
@@ -1885,6 +1889,135 @@ gpe_status gpe_cast_rays(gpe_ctx *c, gpe_ray_cast *r)
         if (r->index) std::copy(index.begin(), index.begin() + m, r->index + base);
     }
     r->hits = hits;
+    return GPE_OK;
+}
+
+// ---- nearest neighbours (k_nearest.hip) -------------------------------------------------------------------------
+static gpe_status nearest_alloc(gpe_ctx *c, void **p, uint64_t payload, const char *tag)
+{
+    const hipError_t e = gpe_dev_reserve(c, p, payload, 0, tag);
+    if (e == hipErrorOutOfMemory) return fail(c, GPE_ERR_OOM, "gpe_query_nearest: out of device memory");
+    if (e != hipSuccess) return fail(c, GPE_ERR_HIP, std::string("gpe_query_nearest: ") + hipGetErrorName(e));
+    return GPE_OK;
+}
+
+// room for a batch of k points of m slots each; every array is read and written by index below k, k * m or
+// kRayRowWords.  no slack
+static gpe_status nearest_reserve(gpe_ctx *c, uint64_t k, uint64_t m)
+{
+    NearestWorkspace &ws = c->nearest_ws;
+    if (!ws.row_start)
+        GPE_TRY(nearest_alloc(c, (void **)&ws.row_start, kRayRowWords * sizeof(uint32_t), "nearest.row_start"));
+    if (ws.cap < k) {
+        dev_free(c, ws.points); dev_free(c, ws.count);
+        ws.cap = 0;
+        GPE_TRY(nearest_alloc(c, (void **)&ws.points, k * sizeof(float2), "nearest.points"));
+        GPE_TRY(nearest_alloc(c, (void **)&ws.count, k * sizeof(uint32_t), "nearest.count"));
+        ws.cap = k;
+    }
+    const uint64_t slots = k * m;
+    if (ws.slots_cap < slots) {
+        dev_free(c, ws.index); dev_free(c, ws.uid); dev_free(c, ws.dist2); dev_free(c, ws.pos); dev_free(c, ws.radius);
+        ws.slots_cap = 0;
+        GPE_TRY(nearest_alloc(c, (void **)&ws.index, slots * sizeof(uint32_t), "nearest.index"));
+        GPE_TRY(nearest_alloc(c, (void **)&ws.uid, slots * sizeof(uint32_t), "nearest.uid"));
+        GPE_TRY(nearest_alloc(c, (void **)&ws.dist2, slots * sizeof(float), "nearest.dist2"));
+        GPE_TRY(nearest_alloc(c, (void **)&ws.pos, slots * sizeof(float2), "nearest.pos"));
+        GPE_TRY(nearest_alloc(c, (void **)&ws.radius, slots * sizeof(float), "nearest.radius"));
+        ws.slots_cap = slots;
+    }
+    return GPE_OK;
+}
+
+// no point has a neighbour: the host fills the requested outputs
+static void nearest_fill_none(gpe_nearest_query *q)
+{
+    const uint64_t k = q->k, slots = q->k * q->m;
+    const float nan = std::numeric_limits<float>::quiet_NaN();
+    if (q->count) std::fill(q->count, q->count + k, 0u);
+    if (q->index) std::fill(q->index, q->index + slots, GPE_NEAREST_NONE);
+    if (q->uid) std::fill(q->uid, q->uid + slots, GPE_UID_ABSENT);
+    if (q->dist2) std::fill(q->dist2, q->dist2 + slots, nan);
+    if (q->pos_xy) std::fill(q->pos_xy, q->pos_xy + 2 * slots, nan);
+    if (q->radius) std::fill(q->radius, q->radius + slots, nan);
+}
+
+gpe_status gpe_query_nearest(gpe_ctx *c, gpe_nearest_query *q)
+{
+    const char *who = "gpe_query_nearest";
+    if (!c) return GPE_ERR_INVALID_ARG;
+    if (!q) return fail(c, GPE_ERR_INVALID_ARG, std::string(who) + ": NULL query");
+    if (q->struct_size < sizeof(gpe_nearest_query))        // found is the last field: a smaller struct has none
+        return fail(c, GPE_ERR_INVALID_ARG, std::string(who) + ": struct_size is smaller than gpe_nearest_query");
+    q->found = 0;
+    if (q->flags != 0) return fail(c, GPE_ERR_INVALID_ARG, std::string(who) + ": flags must be 0");
+    if (q->m == 0 || q->m > GPE_NEAREST_MAX_M) return fail(c, GPE_ERR_INVALID_ARG, std::string(who) + ": m must be 1 .. 64");
+    const float md = q->max_distance;
+    if (!(md >= 0.0f)) return fail(c, GPE_ERR_INVALID_ARG, std::string(who) + ": max_distance is NaN or negative");
+    const uint64_t k = q->k, m = q->m;
+    if (k > 0 && !q->point_xy) return fail(c, GPE_ERR_INVALID_ARG, std::string(who) + ": NULL points");
+    if (is_sharded(c))
+        return fail(c, GPE_ERR_UNSUPPORTED, std::string(who) + ": not supported on a sharded context (gpe_shard_*, "
+                                                                "order keys or an active cell box)");
+    if (q->uid && !c->uid.on) return fail(c, GPE_ERR_STATE, std::string(who) + ": uid requested while uids are off");
+    if (c->n > 0xFFFFFFFFull) return fail(c, GPE_ERR_UNSUPPORTED, std::string(who) + ": more than 2^32 - 1 particles");
+    if (k == 0) return GPE_OK;
+    const bool any = c->n > 0 && c->pos;
+    // the contact query's own cell while it is usable; the result never depends on it, only the points' bound does
+    float cell_size = 0.0f;
+    if (any) {
+        cell_size = gpe_compute_cell_size(fabsf(c->max_radius));
+        if (!(isfinite(cell_size) && cell_size > 0.0f)) cell_size = fmaxf(c->cfg.world_width, c->cfg.world_height) / 1024.0f;
+        if (!(isfinite(cell_size) && cell_size > 0.0f))
+            return fail(c, GPE_ERR_UNSUPPORTED, std::string(who) + ": neither the largest radius nor the world gives a "
+                                                                   "finite positive cell size");
+    }
+    const float bound = any ? 131072.0f * cell_size : std::numeric_limits<float>::infinity();
+    for (uint64_t i = 0; i < 2 * k; ++i) {
+        const float a = q->point_xy[i];
+        if (!isfinite(a) || !(fabsf(a) <= bound))
+            return fail(c, GPE_ERR_INVALID_ARG, std::string(who) + ": a point is not finite or lies more than 131072 "
+                                                                   "cells from the origin");
+    }
+    if (!any) {                                                 // no particles: nothing to find
+        nearest_fill_none(q);
+        return GPE_OK;
+    }
+    GPE_HIP(c, hipSetDevice(c->device));
+    GPE_HIP(c, hipStreamSynchronize(c->stream));
+    const uint64_t batch = std::min<uint64_t>(k, kNearestMaxSlots / m);
+    GPE_TRY(nearest_reserve(c, batch, m));
+    NearestWorkspace &ws = c->nearest_ws;
+    Scope s(c, "Nearest");
+    GPE_TRY(contacts_bin(c, cell_size));
+    {
+        Scope r(c, "nearest/rows");
+        GPE_TRY(launch_ray_row_start(c, c->contacts_ws.keys, ws.row_start));
+    }
+    std::vector<uint32_t> count(batch);
+    uint64_t found = 0;
+    for (uint64_t base = 0; base < k; base += batch) {
+        const uint64_t b = std::min<uint64_t>(batch, k - base), slots = b * m;
+        GPE_HIP(c, hipMemcpyAsync(ws.points, q->point_xy + 2 * base, b * sizeof(float2), hipMemcpyHostToDevice, c->stream));
+        {
+            Scope r(c, "nearest/search");
+            GPE_TRY(launch_nearest(c, ws.points, (uint32_t)b, (uint32_t)m, md, cell_size, c->contacts_ws.keys,
+                                   c->contacts_ws.rec, ws.row_start, ws.count, q->index ? ws.index : nullptr,
+                                   q->uid ? ws.uid : nullptr, q->dist2 ? ws.dist2 : nullptr, q->pos_xy ? ws.pos : nullptr,
+                                   q->radius ? ws.radius : nullptr));
+        }
+        const uint64_t at = base * m;
+        GPE_HIP(c, hipMemcpyAsync(count.data(), ws.count, b * 4, hipMemcpyDeviceToHost, c->stream));
+        if (q->index) GPE_HIP(c, hipMemcpyAsync(q->index + at, ws.index, slots * 4, hipMemcpyDeviceToHost, c->stream));
+        if (q->uid) GPE_HIP(c, hipMemcpyAsync(q->uid + at, ws.uid, slots * 4, hipMemcpyDeviceToHost, c->stream));
+        if (q->dist2) GPE_HIP(c, hipMemcpyAsync(q->dist2 + at, ws.dist2, slots * 4, hipMemcpyDeviceToHost, c->stream));
+        if (q->pos_xy) GPE_HIP(c, hipMemcpyAsync(q->pos_xy + 2 * at, ws.pos, slots * 8, hipMemcpyDeviceToHost, c->stream));
+        if (q->radius) GPE_HIP(c, hipMemcpyAsync(q->radius + at, ws.radius, slots * 4, hipMemcpyDeviceToHost, c->stream));
+        GPE_HIP(c, hipStreamSynchronize(c->stream));
+        for (uint64_t i = 0; i < b; ++i) found += count[i];
+        if (q->count) std::copy(count.begin(), count.begin() + b, q->count + base);
+    }
+    q->found = found;
     return GPE_OK;
 }
 

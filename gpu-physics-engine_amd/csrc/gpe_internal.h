@@ -306,6 +306,19 @@ struct RayWorkspace {            // gpe_cast_rays (k_raycast.hip); allocated at 
 constexpr uint32_t kRayRowWords = 65537;         // rows 0 .. 65535 of the clamped key and the end of the last one
 constexpr uint32_t kRayMaxBatch = 1u << 20;      // rays per launch; gpe_cast_rays walks a longer list in batches
 
+struct NearestWorkspace {        // gpe_query_nearest (k_nearest.hip); allocated at first use, freed with the particles
+    uint32_t *row_start = nullptr;               // kRayRowWords: per clamped row, its first slot of the sorted keys
+    float2 *points = nullptr;                    // the uploaded query points of one batch
+    uint32_t *count = nullptr;                   // per point of the batch: neighbours delivered
+    uint32_t *index = nullptr, *uid = nullptr;   // per slot (point x m) of the batch: the neighbours' rows
+    float *dist2 = nullptr, *radius = nullptr;
+    float2 *pos = nullptr;
+    uint64_t cap = 0;                            // points the first two arrays hold
+    uint64_t slots_cap = 0;                      // slots the five per-slot arrays hold
+};
+constexpr uint32_t kNearestMaxM = 64;            // GPE_NEAREST_MAX_M: the wave keeps one neighbour per lane
+constexpr uint64_t kNearestMaxSlots = 1ull << 22;    // batch x m per launch; gpe_query_nearest walks a longer list in batches
+
 struct ClustersWorkspace {       // gpe_query_clusters / gpe_query_cluster_of (k_clusters.hip); allocated at first use, freed with the particles
     uint32_t *parent = nullptr;                  // the union-find forest: parent[i] <= i; after the flatten free for label_uid
     uint32_t *label = nullptr;                   // per particle: the lowest index of its cluster
@@ -706,6 +719,7 @@ struct gpe_ctx {
     gpe::ContactsWorkspace contacts_ws;
     gpe::ClustersWorkspace clusters_ws;
     gpe::RayWorkspace ray_ws;
+    gpe::NearestWorkspace nearest_ws;
     gpe::EditWorkspace edit_ws;
     gpe::SpawnWorkspace spawn_ws;
     gpe::ScanWorkspace scan_ws;
@@ -890,6 +904,13 @@ gpe_status launch_ray_row_start(gpe_ctx *c, const uint32_t *keys, uint32_t *row_
 gpe_status launch_ray_cast(gpe_ctx *c, const float2 *from, const float2 *to, uint32_t k, float cell_size,
                            const uint32_t *keys, const uint4 *rec, const uint32_t *row_start, uint32_t *index_out,
                            uint32_t *uid_out, float *t_out, float2 *pos_out, float *radius_out);
+// nearest neighbours (k_nearest.hip); keys / rec / row_start as the ray cast takes them.  For each of the k points
+// (k * m <= kNearestMaxSlots, 1 <= m <= kNearestMaxM; finite, within 131072 cells) the m candidates (d2 <= rr) with the
+// least bits(d2) << 32 | index, ascending, into row i of the non-NULL per-slot outputs (GPE_NEAREST_NONE, GPE_UID_ABSENT
+// and NaN past count_out[i]; uid_out: from c->uid.uids).  count_out is always written
+gpe_status launch_nearest(gpe_ctx *c, const float2 *points, uint32_t k, uint32_t m, float max_distance, float cell_size,
+                          const uint32_t *keys, const uint4 *rec, const uint32_t *row_start, uint32_t *count_out,
+                          uint32_t *index_out, uint32_t *uid_out, float *dist2_out, float2 *pos_out, float *radius_out);
 // contact clusters (k_clusters.hip); keys / rec: the contact query's sorted cell keys and records
 // parent[i] = i, then every contact (i, j < i) unites the trees of i and j: parent[x] <= x, a component's root is its lowest index
 gpe_status launch_clusters_hook(gpe_ctx *c, const uint32_t *keys, const uint4 *rec, uint32_t *parent);

@@ -39,6 +39,9 @@ ContactResult = collections.namedtuple("ContactResult", "a b uid_a uid_b overlap
 ClusterResult = collections.namedtuple("ClusterResult", "label size label_uid count largest_size largest_label")
 # cast_rays: one row per ray; index L.RAY_MISS, uid L.UID_ABSENT and NaN for a miss; uid / pos / radius None unless requested
 RayHits = collections.namedtuple("RayHits", "index t uid pos radius hits")
+# nearest: one row of m slots per point, ascending by (d2, index); count (k,), index / dist2 / uid / radius (k, m), pos
+# (k, m, 2); past count[i] index L.NEAREST_NONE, uid L.UID_ABSENT and NaN; uid / pos / radius None unless requested
+Neighbours = collections.namedtuple("Neighbours", "count index dist2 uid pos radius found")
 
 
 class Context:
@@ -482,6 +485,39 @@ class ParticleSystem:
         return RayHits(index[:k], t[:k], uid[:k] if uids else None, pos[:k] if rows else None,
                        rad[:k] if rows else None, cast.hits)
 
+    # Nearest neighbours (not in the reference; include/gpe.h): the m particles whose centres are closest to each point,
+    # searched on the device outward from the point along the contact query's cell table.  The context is left as it was.
+    def nearest(self, points, m=1, max_distance=float("inf"), uids=False, rows=False):
+        """gpe_query_nearest -> Neighbours(count, index, dist2, uid, pos, radius, found): per point the storage indices of
+        the min(m, candidates) particles with the least squared centre distance d2 <= max_distance^2 (float32; the
+        lowest index on a tie), ascending, and those d2; the slots past count[i] hold L.NEAREST_NONE and NaN.  uids=True
+        adds the uids, rows=True the neighbours' centres and stored radii.  A point on a particle finds it at d2 = 0: for
+        the neighbours of a particle ask for m + 1 and drop the first."""
+        points = np.ascontiguousarray(points, np.float32)
+        if points.ndim != 2 or points.shape[1] != 2:
+            raise ValueError("nearest: points must be (k, 2), got %r" % (points.shape,))
+        m = int(m)
+        if not 1 <= m <= L.NEAREST_MAX_M:
+            raise ValueError("nearest: m must be 1 .. %d, got %d" % (L.NEAREST_MAX_M, m))
+        k = points.shape[0]
+        room = max(k, 1)
+        f32, u32 = C.POINTER(C.c_float), C.POINTER(C.c_uint32)
+        count = np.empty(room, np.uint32)
+        index, dist2 = np.empty((room, m), np.uint32), np.empty((room, m), np.float32)
+        uid = np.empty((room, m), np.uint32) if uids else None
+        pos = np.empty((room, m, 2), np.float32) if rows else None
+        rad = np.empty((room, m), np.float32) if rows else None
+        q = L.GpeNearestQuery(struct_size=C.sizeof(L.GpeNearestQuery), flags=0, k=k, m=m, max_distance=float(max_distance))
+        q.point_xy = points.ctypes.data_as(f32)
+        q.count, q.index, q.dist2 = count.ctypes.data_as(u32), index.ctypes.data_as(u32), dist2.ctypes.data_as(f32)
+        if uids:
+            q.uid = uid.ctypes.data_as(u32)
+        if rows:
+            q.pos_xy, q.radius = pos.ctypes.data_as(f32), rad.ctypes.data_as(f32)
+        self.ctx.call("gpe_query_nearest", C.byref(q))
+        return Neighbours(count[:k], index[:k], dist2[:k], uid[:k] if uids else None, pos[:k] if rows else None,
+                          rad[:k] if rows else None, q.found)
+
     def query_segment(self, a, b):
         """gpe_query_segment -> QueryResult of every particle the segment from a to b touches (the function cast_rays
         applies), ascending by index."""
@@ -891,6 +927,10 @@ class State:
     def cast_rays(self, origins, ends, uids=False, rows=False):
         """ParticleSystem.cast_rays -> RayHits(index, t, uid, pos, radius, hits): the first hit of every ray."""
         return self.particles.cast_rays(origins, ends, uids=uids, rows=rows)
+
+    def nearest(self, points, m=1, max_distance=float("inf"), uids=False, rows=False):
+        """ParticleSystem.nearest -> Neighbours(count, index, dist2, uid, pos, radius, found): the m closest particles."""
+        return self.particles.nearest(points, m=m, max_distance=max_distance, uids=uids, rows=rows)
 
     def query_segment(self, a, b):
         """ParticleSystem.query_segment -> QueryResult of everything the segment from a to b touches."""

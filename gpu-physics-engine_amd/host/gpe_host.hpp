@@ -18,6 +18,7 @@
 #include <algorithm>
 #include <chrono>
 #include <cstdint>
+#include <limits>
 #include <stdexcept>
 #include <string>
 #include <utility>
@@ -398,6 +399,47 @@ class ParticleSystem {
         r.radius = rows && k ? q.radius.data() : nullptr;
         ctx_->call(gpe_cast_rays(ctx_->raw(), &r));
         q.hits = r.hits;
+        return q;
+    }
+    // not in the reference: the m particles whose centres are closest to each point (include/gpe.h), searched on the
+    // device.  One row of m slots per point, ascending by (d2, index): past count[i] index GPE_NEAREST_NONE, uid
+    // GPE_UID_ABSENT and NaN; uid only with with_uids (uids must be on), pos / radius only with rows.  A point on a
+    // particle finds it at d2 = 0: for the neighbours of a particle ask for m + 1 and drop the first.
+    struct Neighbours {
+        uint32_t m = 0;
+        std::vector<uint32_t> count, index, uid;
+        std::vector<float> dist2, radius;
+        std::vector<Vec2> pos;
+        uint64_t found = 0;
+    };
+    Neighbours nearest(const std::vector<Vec2> &points, uint32_t m = 1,
+                       float max_distance = std::numeric_limits<float>::infinity(), bool with_uids = false,
+                       bool rows = false) const
+    {
+        if (m == 0 || m > GPE_NEAREST_MAX_M) throw std::invalid_argument("nearest: m must be 1 .. 64");
+        const size_t k = points.size(), slots = k * m;
+        Neighbours q;
+        q.m = m;
+        q.count.resize(k);
+        q.index.resize(slots);
+        q.dist2.resize(slots);
+        q.uid.resize(with_uids ? slots : 0);
+        q.pos.resize(rows ? slots : 0);
+        q.radius.resize(rows ? slots : 0);
+        gpe_nearest_query r{};
+        r.struct_size = sizeof(r);
+        r.k = k;
+        r.m = m;
+        r.max_distance = max_distance;
+        r.point_xy = k ? &points[0].x : nullptr;
+        r.count = k ? q.count.data() : nullptr;
+        r.index = k ? q.index.data() : nullptr;
+        r.dist2 = k ? q.dist2.data() : nullptr;
+        r.uid = with_uids && k ? q.uid.data() : nullptr;
+        r.pos_xy = rows && k ? &q.pos[0].x : nullptr;
+        r.radius = rows && k ? q.radius.data() : nullptr;
+        ctx_->call(gpe_query_nearest(ctx_->raw(), &r));
+        q.found = r.found;
         return q;
     }
     QueryResult query_segment(Vec2 a, Vec2 b) const

@@ -399,6 +399,64 @@ gpe_status gpe_cast_rays(gpe_ctx *ctx, gpe_ray_cast *cast);
  * for the same segment is the member of this set with the least t; a miss there means the set is empty. */
 gpe_status gpe_query_segment(gpe_ctx *ctx, float x0, float y0, float x1, float y1, gpe_query_result *out);
 
+/* ---- nearest neighbours (not in the reference) -----------------------------------------------------------------
+ * Which particles are closest to this point (a snapping cursor, a proximity sensor, the 8 neighbours of each tracer, an
+ * agent that looks around), without downloading the positions: gpe_query_nearest walks the contact query's cell-binned
+ * table outward from each of k points on the device (csrc/k_nearest.hip) and keeps the m closest.
+ *  - The predicate is the circle query's.  For the point (x, y) and a particle centre p, in IEEE binary32, one rounding
+ *    per operation, left to right, no FMA (numpy float32 gives the same bits):
+ *        d2 = (p.x-x)*(p.x-x) + (p.y-y)*(p.y-y);  rr = max_distance*max_distance
+ *        candidate iff d2 <= rr                   (a NaN anywhere compares false; +inf <= +inf holds)
+ *    Radii play no part: this is the distance between the point and the centre.  gpe_pick remains the call for "what is
+ *    under the cursor".
+ *  - For point i the neighbours are the min(m, candidates) candidates with the least key bits(d2) << 32 | index: d2 is
+ *    at least +0, so its bits order as its values, and the lowest storage index wins a tie.  They are delivered in
+ *    ascending key order into row i (m slots) of every non-NULL array; the slots count[i] .. m-1 of a row get
+ *    GPE_NEAREST_NONE, GPE_UID_ABSENT and quiet NaNs.  found is always set.
+ *  - For a finite max_distance the candidates are exactly the members of gpe_query_circle(x, y, max_distance), and
+ *    count[i] = min(m, that count).  +inf means no cutoff (particles whose d2 overflows to +inf are then candidates, and
+ *    come last); -0.0 is accepted as 0.
+ *  - A point that coincides with a particle finds that particle at d2 = +0.  A host that wants the neighbours OF a
+ *    particle asks for m + 1 and drops the first row entry (the lowest index among coincident particles comes first).
+ *  - The cell size of the search is gpe_compute_cell_size(|gpe_max_radius|), the contact query's own, when that is
+ *    finite and > 0; a gpe_grid_set_max_radius override plays no part.  Otherwise (every radius 0, or an infinite
+ *    radius) it is max(world_width, world_height) / 1024 in binary32, and when that is not finite and positive either:
+ *    GPE_ERR_UNSUPPORTED.  The result never depends on the cell size; only the bound on the query points does.
+ *  - Query points, checked on the host over the caller's array before anything is written: every coordinate must be
+ *    finite and satisfy |v| <= 131072 * cell_size, else GPE_ERR_INVALID_ARG (the rule of gpe_cast_rays, for the same
+ *    reason: it keeps the rounding of the walk's own arithmetic a small fraction of a cell).  A context without
+ *    particles has no cell size: the coordinates need only be finite there.
+ *  - Particle positions may be anything gpe_set_particles accepts -- outside the world, 1e30, +-inf, NaN: the result
+ *    is exactly the predicate's, and nothing reads or writes out of bounds for them.
+ *  - The call changes nothing on the context, as gpe_query_contacts: positions, prev, radii, uids, the uid map, the
+ *    scratch index arrays, the native step / sort counters, the kept block table and the rosters are left alone; the
+ *    steps after a call are bit-identical to those of a context that was never asked.  It works in both modes and at any
+ *    point between steps, and blocks like gpe_download.
+ *  - Errors: a NULL context, a NULL query, a struct_size below sizeof(gpe_nearest_query), non-zero flags, m == 0 or
+ *    m > GPE_NEAREST_MAX_M, a max_distance that is NaN or negative, a NULL point_xy with k > 0: GPE_ERR_INVALID_ARG; uid
+ *    requested while uids are off: GPE_ERR_STATE; a sharded context (gpe_shard_*, order keys or an active cell box) and
+ *    more than 2^32 - 1 particles: GPE_ERR_UNSUPPORTED.  On every error found is 0 (when the struct is usable) and no
+ *    output is written.
+ *  - k == 0: GPE_OK, found 0.  No particles: GPE_OK, every count 0, the rows filled with the values above. */
+#define GPE_NEAREST_NONE 0xffffffffu
+#define GPE_NEAREST_MAX_M 64
+typedef struct gpe_nearest_query {
+    uint32_t struct_size;   /* in: sizeof(gpe_nearest_query)                                   */
+    uint32_t flags;         /* in: 0; anything else GPE_ERR_INVALID_ARG                         */
+    uint64_t k;             /* in: number of query points                                       */
+    const float *point_xy;  /* in: f32[2k]                                                      */
+    uint32_t m;             /* in: neighbours wanted per point, 1 .. GPE_NEAREST_MAX_M          */
+    float    max_distance;  /* in: >= 0 or +inf (no cutoff)                                     */
+    uint32_t *count;        /* out, may be NULL: u32[k] neighbours delivered for point i (<= m) */
+    uint32_t *index;        /* out, may be NULL: u32[k*m] storage indices, row i = point i      */
+    uint32_t *uid;          /* out, may be NULL: u32[k*m]                                       */
+    float    *dist2;        /* out, may be NULL: f32[k*m] the d2 above                          */
+    float    *pos_xy;       /* out, may be NULL: f32[2*k*m]                                     */
+    float    *radius;       /* out, may be NULL: f32[k*m] stored radius                         */
+    uint64_t found;         /* out: sum of count over all points                                */
+} gpe_nearest_query;        /* 88 bytes */
+gpe_status gpe_query_nearest(gpe_ctx *ctx, gpe_nearest_query *q);
+
 /* ---- editing particles in place (not in the reference) --------------------------------------------------------
  * Change particles that exist, on the device (csrc/k_edit.hip), without the download / gpe_set_particles detour that
  * would drop the uids, the kept block table and the native counters.  Two kinds of call:
