@@ -42,6 +42,9 @@ POS, PREV, RADIUS, HOME_CELL_IDS, PARTICLE_IDS, CELL_IDS, OBJECT_IDS, COLLISION_
 UID_ABSENT = 0xFFFFFFFF
 RAY_MISS = 0xFFFFFFFF
 NEAREST_NONE = 0xFFFFFFFF
+TRACERS_MAX = 65536
+TRACER_POS, TRACER_PREV, TRACER_INDEX = 1, 2, 4
+TRACERS_CONSUME = 1
 NEAREST_MAX_M = 64
 EDIT_BY_INDEX, EDIT_BY_UID = 0, 1
 CLUSTER_BY_INDEX, CLUSTER_BY_UID = 0, 1
@@ -163,6 +166,21 @@ class GpeNearestQuery(C.Structure):
                 ("found", C.c_uint64)]
 
 
+class GpeTracerConfig(C.Structure):
+    """gpe_tracer_config: all in -- fields (TRACER_*), the k uids to follow, a frame after every every-th step, a ring of
+    `frames` frames."""
+    _fields_ = [("struct_size", C.c_uint32), ("fields", C.c_uint32), ("k", C.c_uint64),
+                ("uids", C.POINTER(C.c_uint32)), ("every", C.c_uint64), ("frames", C.c_uint64)]
+
+
+class GpeTracerFrames(C.Structure):
+    """gpe_tracer_frames: in struct_size / flags / capacity, out count / recorded; every array may be NULL (step
+    u64[capacity], pos_xy / prev_xy f32[capacity * k * 2], index u32[capacity * k])."""
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("capacity", C.c_uint64),
+                ("count", C.c_uint64), ("recorded", C.c_uint64), ("step", C.POINTER(C.c_uint64)),
+                ("pos_xy", C.POINTER(C.c_float)), ("prev_xy", C.POINTER(C.c_float)), ("index", C.POINTER(C.c_uint32))]
+
+
 class GpeParticleEdit(C.Structure):
     """gpe_particle_edit: in struct_size / key_kind / k / keys and the field arrays (each may be NULL), out edited."""
     _fields_ = [("struct_size", C.c_uint32), ("key_kind", C.c_uint32), ("k", C.c_uint64),
@@ -216,6 +234,10 @@ SYMBOLS = [
     ("gpe_set_next_uid", _I32, [_VP, _U64]),
     ("gpe_find_uids", _I32, [_VP, _VP, _U64, _VP, _VP, _VP, _VP]),
     ("gpe_remove_particles_by_uid", _I32, [_VP, _VP, _U64, C.POINTER(_U64)]),
+    ("gpe_tracers_begin", _I32, [_VP, C.POINTER(GpeTracerConfig)]),
+    ("gpe_tracers_sample", _I32, [_VP]),
+    ("gpe_tracers_read", _I32, [_VP, C.POINTER(GpeTracerFrames)]),
+    ("gpe_tracers_end", _I32, [_VP]),
     ("gpe_query_circle", _I32, [_VP, _F, _F, _F, C.POINTER(GpeQueryResult)]),
     ("gpe_query_box", _I32, [_VP, _F, _F, _F, _F, C.POINTER(GpeQueryResult)]),
     ("gpe_pick", _I32, [_VP, _F, _F, C.POINTER(GpeQueryResult)]),

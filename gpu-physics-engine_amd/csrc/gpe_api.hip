@@ -256,6 +256,7 @@ static void free_uid_buffers(gpe_ctx *c)
     dev_free(c, u.map_keys); dev_free(c, u.map_vals); dev_free(c, u.dup); dev_free(c, u.query);
     u.map_cap = u.query_cap = 0;
     u.map_valid = false;
+    c->tracers.stale = true;
 }
 
 static void free_particle_buffers(gpe_ctx *c)
@@ -580,6 +581,7 @@ static gpe_status do_remove(gpe_ctx *c, const uint8_t *mask, float x, float y, f
     if (c->uid.on) {
         std::swap(c->uid.uids, c->uid.uids_copy);
         c->uid.map_valid = false;
+        c->tracers.stale = true;
     }
     c->n = survivors;
     c->n_owned = survivors;
@@ -614,6 +616,7 @@ static gpe_status uids_switch_on(gpe_ctx *c)
     }
     u.on = true;
     u.map_valid = false;
+    c->tracers.stale = true;
     return GPE_OK;
 }
 
@@ -673,6 +676,57 @@ static gpe_status uid_query_reserve(gpe_ctx *c, uint64_t bytes)
     return GPE_OK;
 }
 
+// ---- tracers (k_tracers.hip) ---------------------------------------------------------------------------------
+static gpe_status tracers_alloc(gpe_ctx *c, void **p, uint64_t payload, const char *tag)
+{
+    const hipError_t e = gpe_dev_reserve(c, p, payload, 0, tag);
+    if (e == hipErrorOutOfMemory) return fail(c, GPE_ERR_OOM, "gpe_tracers_begin: out of device memory");
+    if (e != hipSuccess) return fail(c, GPE_ERR_HIP, std::string("gpe_tracers_begin: ") + hipGetErrorName(e));
+    return GPE_OK;
+}
+
+static void tracers_release(gpe_ctx *c)
+{
+    TracerState &t = c->tracers;
+    dev_free(c, t.keys); dev_free(c, t.perm); dev_free(c, t.slot_index);
+    dev_free(c, t.ring_pos); dev_free(c, t.ring_prev); dev_free(c, t.ring_index);
+    t = TracerState();
+}
+
+// One frame at the current steps_seen into ring slot recorded % frames.  Enqueues only: a memset and the resolve pass
+// when the slot table is stale, then the sample.  The step numbers stay on the host, which issues every frame.
+static gpe_status tracers_take_frame(gpe_ctx *c)
+{
+    TracerState &t = c->tracers;
+    const uint32_t k = (uint32_t)t.k;
+    if (t.stale) {
+        Scope s(c, "tracers/resolve");
+        GPE_HIP(c, hipMemsetAsync(t.slot_index, 0xff, k * sizeof(uint32_t), c->stream));
+        if (c->uid.on && c->uid.uids)                                  // uids off: nothing to read, every tracer is absent
+            GPE_TRY(launch_tracers_resolve(c, c->uid.uids, c->n, t.keys, t.perm, k, t.lo, t.hi, t.slot_index));
+        t.stale = false;
+    }
+    const uint64_t slot = t.recorded % t.frames, row = slot * t.k;
+    {
+        Scope s(c, "tracers/sample");
+        GPE_TRY(launch_tracers_sample(c, t.slot_index, k, c->pos, c->prev, c->n, t.ring_pos ? t.ring_pos + row : nullptr,
+                                      t.ring_prev ? t.ring_prev + row : nullptr,
+                                      t.ring_index ? t.ring_index + row : nullptr));
+    }
+    t.step_of[slot] = t.steps_seen;
+    t.recorded += 1;
+    t.held = std::min(t.held + 1, t.frames);
+    return GPE_OK;
+}
+
+// After every step of gpe_step / gpe_run on an armed context.
+static gpe_status tracers_after_step(gpe_ctx *c)
+{
+    TracerState &t = c->tracers;
+    t.steps_seen += 1;
+    return t.steps_seen % t.every == 0 ? tracers_take_frame(c) : GPE_OK;
+}
+
 // ---- in-place edits (k_edit.hip) ---------------------------------------------------------------------------
 // One buffer of the edit workspace (tags "edit.*"): allocated at first use and, with a capacity word, regrown when
 // `count` passes it (cap == NULL: a buffer of fixed size).  payload: count elements; slack_bytes: stated at the call
@@ -704,6 +758,7 @@ static gpe_status do_resort(gpe_ctx *c)
                                       c->prev_copy, c->radius_copy, c->uid.uids_copy));
         std::swap(c->uid.uids, c->uid.uids_copy);
         c->uid.map_valid = false;
+        c->tracers.stale = true;
     } else {
         GPE_TRY(launch_rearrange(c, c->pos, c->prev, c->radius, c->particle_ids, c->n, c->pos_copy,
                                  c->prev_copy, c->radius_copy));
@@ -893,6 +948,7 @@ gpe_status gpe_destroy(gpe_ctx *c)
     }
     if (c->trace_origin) (void)hipEventDestroy(c->trace_origin);
     free_particle_buffers(c);
+    tracers_release(c);
     sort_release(c);
     scan_release(c);
     onesweep_release(c);
@@ -1023,6 +1079,7 @@ gpe_status gpe_set_particles(gpe_ctx *c, const float *pos_xy, const float *prev_
         GPE_TRY(launch_uid_iota(c, c->uid.uids, 0, n, 0u));
         c->uid.next = n;
         c->uid.map_valid = false;
+        c->tracers.stale = true;
     }
     c->max_radius = max_abs_radius(radius, n, radius[0]);
     c->grid_max_radius = c->max_radius;       // Grid::new (grid.rs:66-71)
@@ -1053,6 +1110,7 @@ gpe_status gpe_add_particles(gpe_ctx *c, const float *pos_xy, const float *radiu
         GPE_TRY(launch_uid_iota(c, c->uid.uids, old_n, new_n, (uint32_t)c->uid.next));
         c->uid.next += n_add;
         c->uid.map_valid = false;
+        c->tracers.stale = true;
     }
     // particle_system.rs:198: max_radius = max(max_radius, r)
     for (uint64_t i = 0; i < n_add; ++i) c->max_radius = fmaxf(c->max_radius, radius[i]);
@@ -1153,6 +1211,7 @@ gpe_status gpe_set_uids(gpe_ctx *c, const uint32_t *uids, uint64_t n)
     std::swap(u.uids, u.uids_copy);
     u.next = (uint64_t)u.map_max + 1;
     u.map_valid = true;                                        // the map just built is the new uids'
+    c->tracers.stale = true;                                   // (uid_map_build cleared map_valid on the way)
     return GPE_OK;
 }
 
@@ -1248,6 +1307,126 @@ gpe_status gpe_remove_particles_by_uid(gpe_ctx *c, const uint32_t *uids, uint64_
         GPE_TRY(launch_uid_mark(c, c->uid.map_keys, c->uid.map_vals, c->n, d_query, k, c->remove_ws.mask));
     }
     return do_remove(c, c->remove_ws.mask, 0.f, 0.f, 0.f, n_removed);
+}
+
+// ---- tracers (k_tracers.hip) ---------------------------------------------------------------------------------
+gpe_status gpe_tracers_begin(gpe_ctx *c, const gpe_tracer_config *cfg)
+{
+    if (!c) return GPE_ERR_INVALID_ARG;
+    if (!cfg || cfg->struct_size < sizeof(gpe_tracer_config))
+        return fail(c, GPE_ERR_INVALID_ARG, "gpe_tracers_begin: NULL cfg or bad struct_size");
+    if (is_sharded(c))
+        return fail(c, GPE_ERR_UNSUPPORTED, "gpe_tracers_begin: not supported on a sharded context (gpe_shard_*, order "
+                                            "keys or an active cell box)");
+    constexpr uint32_t kFields = GPE_TRACER_POS | GPE_TRACER_PREV | GPE_TRACER_INDEX;
+    if (!cfg->uids) return fail(c, GPE_ERR_INVALID_ARG, "gpe_tracers_begin: NULL uids");
+    if (cfg->k == 0 || cfg->k > GPE_TRACERS_MAX)
+        return fail(c, GPE_ERR_INVALID_ARG, "gpe_tracers_begin: k must be 1 .. GPE_TRACERS_MAX");
+    if (cfg->every == 0 || cfg->frames == 0) return fail(c, GPE_ERR_INVALID_ARG, "gpe_tracers_begin: every and frames must be >= 1");
+    if (cfg->fields == 0 || (cfg->fields & ~kFields))
+        return fail(c, GPE_ERR_INVALID_ARG, "gpe_tracers_begin: fields must be GPE_TRACER_* bits, at least one");
+    const uint32_t k = (uint32_t)cfg->k;
+    // the tracked uids ascending with the tracer each one is: what the resolve pass searches
+    std::vector<uint32_t> perm(k), keys(k);
+    for (uint32_t j = 0; j < k; ++j) perm[j] = j;
+    std::sort(perm.begin(), perm.end(), [cfg](uint32_t a, uint32_t b) { return cfg->uids[a] < cfg->uids[b]; });
+    for (uint32_t j = 0; j < k; ++j) keys[j] = cfg->uids[perm[j]];
+    for (uint32_t j = 1; j < k; ++j)
+        if (keys[j] == keys[j - 1]) return fail(c, GPE_ERR_INVALID_ARG, "gpe_tracers_begin: two tracers share a uid");
+    if (c->tracers.armed) return fail(c, GPE_ERR_STATE, "gpe_tracers_begin: already armed (gpe_tracers_end first)");
+    if (!c->uid.on) return fail(c, GPE_ERR_STATE, "gpe_tracers_begin: uids are off (gpe_enable_uids)");
+    GPE_TRY(need_particles(c));
+    if (cfg->frames > (1ull << 40) / k)                                // (frames * k * 8 bytes is far past any device)
+        return fail(c, GPE_ERR_OOM, "gpe_tracers_begin: the ring does not fit in device memory");
+    GPE_HIP(c, hipSetDevice(c->device));
+    TracerState &t = c->tracers;
+    const uint64_t rows = cfg->frames * cfg->k;
+    // every array is read and written by index below k or frames * k (the resolve pass reads keys by single words
+    // below k, the uids by 16-byte groups below n / 4 and single words below n).  no slack
+    gpe_status st = tracers_alloc(c, (void **)&t.keys, k * sizeof(uint32_t), "tracers.keys");
+    if (st == GPE_OK) st = tracers_alloc(c, (void **)&t.perm, k * sizeof(uint32_t), "tracers.perm");
+    if (st == GPE_OK) st = tracers_alloc(c, (void **)&t.slot_index, k * sizeof(uint32_t), "tracers.slot_index");
+    if (st == GPE_OK && (cfg->fields & GPE_TRACER_POS))
+        st = tracers_alloc(c, (void **)&t.ring_pos, rows * sizeof(float2), "tracers.ring_pos");
+    if (st == GPE_OK && (cfg->fields & GPE_TRACER_PREV))
+        st = tracers_alloc(c, (void **)&t.ring_prev, rows * sizeof(float2), "tracers.ring_prev");
+    if (st == GPE_OK && (cfg->fields & GPE_TRACER_INDEX))
+        st = tracers_alloc(c, (void **)&t.ring_index, rows * sizeof(uint32_t), "tracers.ring_index");
+    if (st == GPE_OK) {
+        hipError_t e = hipMemcpyAsync(t.keys, keys.data(), k * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(t.perm, perm.data(), k * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);      // the host vectors go away on return
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            st = fail(c, GPE_ERR_HIP, std::string("gpe_tracers_begin: upload: ") + hipGetErrorName(e));
+        }
+    }
+    if (st != GPE_OK) {
+        const std::string why = c->last_error;
+        tracers_release(c);                                            // unarmed, as before
+        c->last_error = why;
+        return st;
+    }
+    t.armed = true;
+    t.stale = true;
+    t.fields = cfg->fields;
+    t.k = cfg->k; t.every = cfg->every; t.frames = cfg->frames;
+    t.steps_seen = t.recorded = t.held = 0;
+    t.lo = keys.front(); t.hi = keys.back();
+    t.step_of.assign((size_t)cfg->frames, 0);
+    return GPE_OK;
+}
+
+gpe_status gpe_tracers_sample(gpe_ctx *c)
+{
+    if (!c) return GPE_ERR_INVALID_ARG;
+    if (!c->tracers.armed) return fail(c, GPE_ERR_STATE, "gpe_tracers_sample: not armed (gpe_tracers_begin)");
+    GPE_HIP(c, hipSetDevice(c->device));
+    return tracers_take_frame(c);
+}
+
+gpe_status gpe_tracers_read(gpe_ctx *c, gpe_tracer_frames *out)
+{
+    if (!c) return GPE_ERR_INVALID_ARG;
+    if (!out || out->struct_size < sizeof(gpe_tracer_frames))
+        return fail(c, GPE_ERR_INVALID_ARG, "gpe_tracers_read: NULL out or bad struct_size");
+    out->count = out->recorded = 0;
+    TracerState &t = c->tracers;
+    if (!t.armed) return fail(c, GPE_ERR_STATE, "gpe_tracers_read: not armed (gpe_tracers_begin)");
+    if (out->flags & ~(uint32_t)GPE_TRACERS_CONSUME) return fail(c, GPE_ERR_INVALID_ARG, "gpe_tracers_read: unknown flag");
+    if ((out->pos_xy && !t.ring_pos) || (out->prev_xy && !t.ring_prev) || (out->index && !t.ring_index))
+        return fail(c, GPE_ERR_INVALID_ARG, "gpe_tracers_read: an array for a field the recorder was not configured with");
+    GPE_HIP(c, hipSetDevice(c->device));
+    const uint64_t m = std::min(t.held, out->capacity), first = t.recorded - m;   // frames first .. recorded - 1
+    // the frames lie in at most two runs of ring slots
+    for (uint64_t done = 0; done < m;) {
+        const uint64_t slot = (first + done) % t.frames, run = std::min(m - done, t.frames - slot);
+        const uint64_t src = slot * t.k, dst = done * t.k, rows = run * t.k;
+        if (out->pos_xy)
+            GPE_HIP(c, hipMemcpyAsync(out->pos_xy + 2 * dst, t.ring_pos + src, rows * sizeof(float2), hipMemcpyDeviceToHost, c->stream));
+        if (out->prev_xy)
+            GPE_HIP(c, hipMemcpyAsync(out->prev_xy + 2 * dst, t.ring_prev + src, rows * sizeof(float2), hipMemcpyDeviceToHost, c->stream));
+        if (out->index)
+            GPE_HIP(c, hipMemcpyAsync(out->index + dst, t.ring_index + src, rows * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        if (out->step)
+            for (uint64_t f = 0; f < run; ++f) out->step[done + f] = t.step_of[slot + f];
+        done += run;
+    }
+    GPE_HIP(c, hipStreamSynchronize(c->stream));
+    out->count = t.held;
+    out->recorded = t.recorded;
+    if (out->flags & GPE_TRACERS_CONSUME) t.held = 0;
+    return check_device_errors(c);
+}
+
+gpe_status gpe_tracers_end(gpe_ctx *c)
+{
+    if (!c) return GPE_ERR_INVALID_ARG;
+    if (!c->tracers.armed) return fail(c, GPE_ERR_STATE, "gpe_tracers_end: not armed (gpe_tracers_begin)");
+    GPE_HIP(c, hipSetDevice(c->device));
+    GPE_HIP(c, hipStreamSynchronize(c->stream));                       // (frames in flight still write the ring)
+    tracers_release(c);
+    return GPE_OK;
 }
 
 // ---- region queries and picking (k_query.hip) -------------------------------------------------------------
@@ -2168,6 +2347,7 @@ gpe_status gpe_add_particles_free(gpe_ctx *c, gpe_particle_spawn *sp)
             GPE_TRY(launch_uid_iota(c, c->uid.uids, old_n, new_n, (uint32_t)c->uid.next));
             c->uid.next += added;
             c->uid.map_valid = false;
+            c->tracers.stale = true;
         }
         // as gpe_add_particles of the added candidates: max_radius = max(max_radius, r), in input order
         for (uint64_t i = 0; i < k; ++i)
@@ -2492,7 +2672,8 @@ gpe_status gpe_step(gpe_ctx *c, float dt, uint32_t flags)
 {
     GPE_TRY(need_particles(c));
     GPE_HIP(c, hipSetDevice(c->device));
-    return do_step(c, dt, flags);
+    GPE_TRY(do_step(c, dt, flags));
+    return c->tracers.armed ? tracers_after_step(c) : GPE_OK;
 }
 
 gpe_status gpe_run(gpe_ctx *c, float dt, uint64_t steps, uint64_t resort_every, int32_t resort_first)
@@ -2514,6 +2695,7 @@ gpe_status gpe_run(gpe_ctx *c, float dt, uint64_t steps, uint64_t resort_every, 
         }
         const bool resort = (s == 0 && resort_first) || (resort_every && s > 0 && (s % resort_every) == 0);
         rc = do_step(c, dt, resort ? GPE_STEP_RESORT : 0u);
+        if (rc == GPE_OK && c->tracers.armed) rc = tracers_after_step(c);
     }
     for (hipEvent_t e : fence) if (e) (void)hipEventDestroy(e);
     return rc;

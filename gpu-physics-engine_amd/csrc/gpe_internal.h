@@ -378,6 +378,21 @@ struct UidState {               // opt-in particle uids (gpe_enable_uids; k_uids
     uint64_t query_cap = 0;                      // bytes
 };
 
+struct TracerState {            // the tracer recorder (gpe_tracers_*; k_tracers.hip).  Observation state: no step reads it
+    bool armed = false;
+    bool stale = true;                           // the slot table is out of date: set wherever uid.map_valid is cleared
+    uint32_t fields = 0;                         // GPE_TRACER_*
+    uint64_t k = 0, every = 1, frames = 0;       // the configuration of gpe_tracers_begin
+    uint64_t steps_seen = 0;                     // steps since begin
+    uint64_t recorded = 0, held = 0;             // frames taken since begin / of them still in the ring (<= frames)
+    uint32_t *keys = nullptr, *perm = nullptr;   // k each: the tracked uids ascending / the tracer each one is
+    uint32_t lo = 0, hi = 0;                     // keys[0], keys[k - 1]
+    uint32_t *slot_index = nullptr;              // k: each tracer's storage index, 0xffffffff for none (valid unless stale)
+    float2 *ring_pos = nullptr, *ring_prev = nullptr;   // frames * k rows each, only the configured fields
+    uint32_t *ring_index = nullptr;
+    std::vector<uint64_t> step_of;               // host side of the ring: steps_seen when frame slot f was taken
+};
+
 struct SortWorkspace {
     uint32_t *keys_b = nullptr, *vals_b = nullptr;   // ping-pong partners, cap entries each
     uint64_t cap = 0;
@@ -715,6 +730,7 @@ struct gpe_ctx {
     gpe::SortWorkspace sort_ws;
     gpe::RemoveWorkspace remove_ws;
     gpe::UidState uid;
+    gpe::TracerState tracers;
     gpe::QueryWorkspace query_ws;
     gpe::ContactsWorkspace contacts_ws;
     gpe::ClustersWorkspace clusters_ws;
@@ -955,6 +971,13 @@ gpe_status launch_edit_max_radius(gpe_ctx *c, unsigned long long *tile_key, unsi
 // region as launch_query_count; op GPE_VEL_*; count != NULL: *count (zeroed here) receives the particles kicked
 gpe_status launch_kick(gpe_ctx *c, bool box, const float *region, uint32_t op, float ax, float ay,
                        unsigned long long *count);
+// tracer recorder (k_tracers.hip).  slot_index[perm[t]] = i for every particle i < n whose uid is keys[t] (keys: the k
+// tracked uids ascending, lo / hi its ends); the other slots are left as they are (set to 0xffffffff by the caller)
+gpe_status launch_tracers_resolve(gpe_ctx *c, const uint32_t *uids, uint64_t n, const uint32_t *keys, const uint32_t *perm,
+                                  uint32_t k, uint32_t lo, uint32_t hi, uint32_t *slot_index);
+// row j of the non-NULL frame arrays = pos / prev / index of particle slot_index[j] (< n), or quiet NaN / GPE_UID_ABSENT
+gpe_status launch_tracers_sample(gpe_ctx *c, const uint32_t *slot_index, uint32_t k, const float2 *pos, const float2 *prev,
+                                 uint64_t n, float2 *pos_row, float2 *prev_row, uint32_t *index_row);
 // native pipeline: its host side (gpe_native.hip; the kernels and their launchers: k_native.hip, native_launch.h)
 gpe_status native_configure(gpe_ctx *c);
 bool native_should_run(gpe_ctx *c);

@@ -42,6 +42,10 @@ RayHits = collections.namedtuple("RayHits", "index t uid pos radius hits")
 # nearest: one row of m slots per point, ascending by (d2, index); count (k,), index / dist2 / uid / radius (k, m), pos
 # (k, m, 2); past count[i] index L.NEAREST_NONE, uid L.UID_ABSENT and NaN; uid / pos / radius None unless requested
 Neighbours = collections.namedtuple("Neighbours", "count index dist2 uid pos radius found")
+# tracers_read: the frames held in the ring, oldest first; step (count,) u64 = steps since tracers_begin, pos / prev
+# (count, k, 2), index (count, k); row j belongs to uids[j], NaN / L.UID_ABSENT while no such particle exists; prev /
+# index None unless recorded; recorded = frames taken since begin
+TracerFrames = collections.namedtuple("TracerFrames", "step pos prev index recorded")
 
 
 class Context:
@@ -399,6 +403,68 @@ class ParticleSystem:
         removed = C.c_uint64()
         self.ctx.call("gpe_remove_particles_by_uid", _ptr(qq), q.shape[0], C.byref(removed))
         return removed.value
+
+    # Tracers (not in the reference; include/gpe.h): the path of k particles named by uid, recorded on the device while
+    # update() / run() go on -- a frame after every every-th step into a ring of `frames` frames, no synchronisation until
+    # tracers_read.  Nothing a step can see changes.
+    def tracers_begin(self, uids, every=1, frames=1024, prev=False, index=False):
+        """gpe_tracers_begin: follow the particles with these uids (1 .. L.TRACERS_MAX of them, pairwise distinct; row j of
+        every frame belongs to uids[j]).  Positions are always recorded, prev=True / index=True add the previous
+        positions / the storage indices.  Needs uids on."""
+        u = np.asarray(uids)
+        if u.ndim != 1 or u.dtype.kind not in "iu":
+            raise ValueError("tracers_begin: uids must be a 1-d integer array, got %s %r" % (u.dtype, u.shape))
+        if not 1 <= u.shape[0] <= L.TRACERS_MAX:
+            raise ValueError("tracers_begin: 1 .. %d uids, got %d" % (L.TRACERS_MAX, u.shape[0]))
+        if int(u.min()) < 0 or int(u.max()) > 0xFFFFFFFF:
+            raise ValueError("tracers_begin: a uid is a u32")
+        u = np.ascontiguousarray(u, np.uint32)
+        if np.unique(u).shape[0] != u.shape[0]:
+            raise ValueError("tracers_begin: two tracers share a uid")
+        every, frames = int(every), int(frames)
+        if every < 1 or frames < 1:
+            raise ValueError("tracers_begin: every and frames must be >= 1, got %d and %d" % (every, frames))
+        fields = L.TRACER_POS | (L.TRACER_PREV if prev else 0) | (L.TRACER_INDEX if index else 0)
+        cfg = L.GpeTracerConfig(struct_size=C.sizeof(L.GpeTracerConfig), fields=fields, k=u.shape[0], every=every,
+                                frames=frames)
+        cfg.uids = u.ctypes.data_as(C.POINTER(C.c_uint32))
+        self.ctx.call("gpe_tracers_begin", C.byref(cfg))
+        self._tracers = (u.shape[0], bool(prev), bool(index))
+
+    def tracers_sample(self):
+        """gpe_tracers_sample: one frame now, at the current step count (the frame at step 0).  Does not synchronise."""
+        self.ctx.call("gpe_tracers_sample")
+
+    def tracers_read(self, consume=False):
+        """gpe_tracers_read -> TracerFrames(step, pos, prev, index, recorded): the frames the ring holds, oldest first.
+        consume=True empties the ring afterwards.  Blocks like a download."""
+        if getattr(self, "_tracers", None) is None:
+            raise ValueError("tracers_read: tracers_begin has not been called")
+        k, with_prev, with_index = self._tracers
+        flags = L.TRACERS_CONSUME if consume else 0
+        fr = L.GpeTracerFrames(struct_size=C.sizeof(L.GpeTracerFrames), flags=0, capacity=0)
+        self.ctx.call("gpe_tracers_read", C.byref(fr))                 # every array NULL: count only
+        count = fr.count
+        room = max(count, 1)
+        step = np.empty(room, np.uint64)
+        pos = np.empty((room, k, 2), np.float32)
+        prev = np.empty((room, k, 2), np.float32) if with_prev else None
+        index = np.empty((room, k), np.uint32) if with_index else None
+        fr = L.GpeTracerFrames(struct_size=C.sizeof(L.GpeTracerFrames), flags=flags, capacity=count)
+        fr.step = step.ctypes.data_as(C.POINTER(C.c_uint64))
+        fr.pos_xy = pos.ctypes.data_as(C.POINTER(C.c_float))
+        if with_prev:
+            fr.prev_xy = prev.ctypes.data_as(C.POINTER(C.c_float))
+        if with_index:
+            fr.index = index.ctypes.data_as(C.POINTER(C.c_uint32))
+        self.ctx.call("gpe_tracers_read", C.byref(fr))
+        return TracerFrames(step[:count], pos[:count], prev[:count] if with_prev else None,
+                            index[:count] if with_index else None, fr.recorded)
+
+    def tracers_end(self):
+        """gpe_tracers_end: stop recording and free the ring (frames not read are lost)."""
+        self.ctx.call("gpe_tracers_end")
+        self._tracers = None
 
     # Region queries and picking (not in the reference; include/gpe.h): which particles lie in a circle or a box, or
     # under a point, counted and gathered on the device.  The context is left exactly as it was.
@@ -888,6 +954,22 @@ class State:
         """ParticleSystem.remove_particles_by_uid: returns how many left."""
         return self.particles.remove_particles_by_uid(uids)
 
+    def tracers_begin(self, uids, every=1, frames=1024, prev=False, index=False):
+        """ParticleSystem.tracers_begin: record the path of the particles with these uids while update() / run() go on."""
+        self.particles.tracers_begin(uids, every=every, frames=frames, prev=prev, index=index)
+
+    def tracers_sample(self):
+        """ParticleSystem.tracers_sample: one frame now."""
+        self.particles.tracers_sample()
+
+    def tracers_read(self, consume=False):
+        """ParticleSystem.tracers_read -> TracerFrames(step, pos, prev, index, recorded)."""
+        return self.particles.tracers_read(consume=consume)
+
+    def tracers_end(self):
+        """ParticleSystem.tracers_end."""
+        self.particles.tracers_end()
+
     def query_circle(self, center, radius):
         """ParticleSystem.query_circle -> QueryResult(index, uid, pos, prev, radius)."""
         return self.particles.query_circle(center, radius)
@@ -982,7 +1064,9 @@ class State:
     def save(self, path):
         """Binary snapshot (numpy .npz, no pickle): positions, previous positions, radii, world, gravity; with uids on
         also the uids and next_uid; with the mouse pressed its position (`mouse`); with a grid radius other than the
-        one gpe_set_particles derives from the saved radii (Grid.new_without_camera) that radius (`grid_max_radius`)."""
+        one gpe_set_particles derives from the saved radii (Grid.new_without_camera) that radius (`grid_max_radius`).
+        A tracer recorder (tracers_begin) is not stored: it is observation state, not step state -- a loaded State steps
+        the same bits without it and is armed again by its host."""
         extra = {}
         if self._uids_on():
             extra.update(uids=self.uids(), next_uid=np.array([self.next_uid()], np.uint64))

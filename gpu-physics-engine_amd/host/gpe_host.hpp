@@ -246,6 +246,54 @@ class ParticleSystem {
         ctx_->call(gpe_remove_particles_by_uid(ctx_->raw(), uids.empty() ? &none : uids.data(), uids.size(), &removed));
         return removed;
     }
+    // not in the reference: the path of k particles named by uid, recorded on the device while the steps go on
+    // (include/gpe.h): a frame after every every-th step into a ring of `frames` frames, no synchronisation until
+    // tracers_read.  Row j of a frame belongs to uids[j]; NaN / GPE_UID_ABSENT while no such particle exists.
+    struct TracerFrames {
+        uint64_t k = 0;                          // rows per frame
+        std::vector<uint64_t> step;              // per frame: steps since tracers_begin
+        std::vector<Vec2> pos, prev;             // count * k rows, oldest frame first; prev / index empty unless recorded
+        std::vector<uint32_t> index;
+        uint64_t recorded = 0;                   // frames taken since tracers_begin
+    };
+    void tracers_begin(const std::vector<uint32_t> &uids, uint64_t every = 1, uint64_t frames = 1024, bool prev = false,
+                       bool index = false)
+    {
+        gpe_tracer_config cfg{};
+        cfg.struct_size = sizeof(cfg);
+        cfg.fields = GPE_TRACER_POS | (prev ? GPE_TRACER_PREV : 0u) | (index ? GPE_TRACER_INDEX : 0u);
+        cfg.k = uids.size();
+        cfg.uids = uids.data();
+        cfg.every = every;
+        cfg.frames = frames;
+        ctx_->call(gpe_tracers_begin(ctx_->raw(), &cfg));
+        tracers_k_ = uids.size();
+        tracers_fields_ = cfg.fields;
+    }
+    void tracers_sample() { ctx_->call(gpe_tracers_sample(ctx_->raw())); }
+    TracerFrames tracers_read(bool consume = false)
+    {
+        gpe_tracer_frames f{};
+        f.struct_size = sizeof(f);
+        ctx_->call(gpe_tracers_read(ctx_->raw(), &f));          // every array NULL: the count
+        TracerFrames r;
+        r.k = tracers_k_;
+        const size_t rows = f.count * tracers_k_;
+        r.step.resize(f.count);
+        r.pos.resize(rows);
+        r.prev.resize(tracers_fields_ & GPE_TRACER_PREV ? rows : 0);
+        r.index.resize(tracers_fields_ & GPE_TRACER_INDEX ? rows : 0);
+        f.flags = consume ? GPE_TRACERS_CONSUME : 0u;
+        f.capacity = f.count;
+        f.step = r.step.data();
+        f.pos_xy = rows ? &r.pos[0].x : nullptr;
+        f.prev_xy = r.prev.empty() ? nullptr : &r.prev[0].x;
+        f.index = r.index.empty() ? nullptr : r.index.data();
+        ctx_->call(gpe_tracers_read(ctx_->raw(), &f));
+        r.recorded = f.recorded;
+        return r;
+    }
+    void tracers_end() { ctx_->call(gpe_tracers_end(ctx_->raw())); tracers_k_ = 0; tracers_fields_ = 0; }
     // not in the reference: every particle in a circle / box, or the one under a point (include/gpe.h), ascending
     // storage index; uid stays empty while uids are off.  pick() returns no rows when no disc contains the point.
     struct QueryResult {
@@ -572,6 +620,8 @@ class ParticleSystem {
         }
     }
     const Context *ctx_;
+    uint64_t tracers_k_ = 0;                 // tracers_begin's k and fields: the shape of the frames tracers_read sizes
+    uint32_t tracers_fields_ = 0;
     bool mouse_pressed_ = false;
     bool sorted_once_ = false;
     std::chrono::steady_clock::time_point last_sort_time_{};

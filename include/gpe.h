@@ -196,6 +196,67 @@ gpe_status gpe_find_uids(gpe_ctx *ctx, const uint32_t *uids, uint64_t k, uint32_
  * untouched, removing every particle is GPE_ERR_INVALID_ARG.  GPE_ERR_STATE while uids are off. */
 gpe_status gpe_remove_particles_by_uid(gpe_ctx *ctx, const uint32_t *uids, uint64_t k, uint64_t *n_removed);
 
+/* ---- tracers (not in the reference) ----------------------------------------------------------------------------
+ * Where k particles named by uid were during a run, without stopping it: an opt-in recorder that writes one frame
+ * -- one row per tracer -- into a device-resident ring after every every-th step (csrc/k_tracers.hip).  The writes are
+ * stream-ordered: gpe_step and gpe_run stay as asynchronous as they are, and only gpe_tracers_read synchronises.  A
+ * context that is not armed launches exactly what it launches without this section.
+ *  - Steps: a step is one gpe_step or one iteration of gpe_run.  The per-module calls (gpe_integrate,
+ *    gpe_solve_collisions, gpe_grid_*, gpe_morton_resort, ...) and the steps of a sharded run are not steps.  The
+ *    recorder keeps steps_seen: 0 at gpe_tracers_begin, + 1 after each step, across calls -- gpe_run(7) followed by
+ *    gpe_run(5) samples like gpe_run(12).
+ *  - Frames: a frame is taken after a step when steps_seen % every == 0 and holds the state that step left behind.
+ *    gpe_tracers_sample takes a frame at the current steps_seen without changing it (the frame at step 0).
+ *  - Rows: row j of a frame belongs to uids[j].  If a particle with that uid exists at that moment the row holds the
+ *    bits of its pos, the bits of its prev and its storage index -- copied, no arithmetic.  Otherwise it holds quiet
+ *    NaNs and GPE_UID_ABSENT: a particle that was removed, one not yet added (it shows up in the first frame after
+ *    gpe_add_particles has handed out that uid), or uids switched off in the meantime.  Tracers are followed through
+ *    re-sorts, removals, adds, growth, gpe_set_particles and gpe_set_uids.
+ *  - Ring: the ring keeps the newest `frames` frames.  gpe_tracers_read delivers the newest min(count, capacity) of
+ *    them, oldest first, into every non-NULL array; host memory past those entries is left untouched.  With every array
+ *    NULL the call only reports count and recorded.  GPE_TRACERS_CONSUME empties the ring after delivery; recorded
+ *    keeps counting.  An array for a field that was not configured: GPE_ERR_INVALID_ARG, nothing written.  Blocks like
+ *    gpe_download.
+ *  - Nothing a step can see changes: positions, prev, radii, uids, the uid -> index map and its validity, the native
+ *    step / sort counters, the kept block table and the rosters are left alone; the recorder neither builds nor
+ *    invalidates the uid map (it keeps a table of its own: each tracer's storage index, re-resolved on the stream by one
+ *    pass over the uids before the first frame after anything has moved the particles or changed their uids).  An armed
+ *    context steps bit for bit like one that is not.
+ *  - Errors: a NULL ctx / cfg / uids / out, a struct_size below the struct's, k == 0, k > GPE_TRACERS_MAX, every == 0,
+ *    frames == 0, no field or an unknown field bit, an unknown read flag, or two equal uids (checked on the host, before
+ *    anything is allocated): GPE_ERR_INVALID_ARG.  A sharded context (gpe_shard_*, order keys or an active cell box):
+ *    GPE_ERR_UNSUPPORTED.  gpe_tracers_begin while uids are off, with no particles or while already armed, and
+ *    gpe_tracers_sample / _read / _end while not armed: GPE_ERR_STATE.  A ring that does not fit: GPE_ERR_OOM, and the
+ *    context stays unarmed.  gpe_destroy frees the recorder; it is observation state, not step state. */
+#define GPE_TRACERS_MAX 65536u
+enum { GPE_TRACER_POS = 1u, GPE_TRACER_PREV = 2u, GPE_TRACER_INDEX = 4u };   /* fields */
+enum { GPE_TRACERS_CONSUME = 1u };                                           /* read flag */
+typedef struct gpe_tracer_config {
+    uint32_t struct_size;   /* in: sizeof(gpe_tracer_config)                          */
+    uint32_t fields;        /* in: GPE_TRACER_*, at least one, no unknown bit         */
+    uint64_t k;             /* in: 1 .. GPE_TRACERS_MAX                               */
+    const uint32_t *uids;   /* in: u32[k], pairwise distinct; row j of a frame = uids[j] */
+    uint64_t every;         /* in: >= 1: a frame after every every-th step            */
+    uint64_t frames;        /* in: >= 1: ring capacity in frames                      */
+} gpe_tracer_config;        /* 40 bytes */
+typedef struct gpe_tracer_frames {
+    uint32_t struct_size;   /* in */
+    uint32_t flags;         /* in: 0 or GPE_TRACERS_CONSUME                           */
+    uint64_t capacity;      /* in: frames each non-NULL array has room for            */
+    uint64_t count;         /* out: frames held in the ring (<= config.frames)        */
+    uint64_t recorded;      /* out: frames taken since begin (held + overwritten + consumed) */
+    uint64_t *step;         /* out, may be NULL: u64[capacity], steps since begin at which the frame was taken */
+    float    *pos_xy;       /* out, may be NULL: f32[capacity * k * 2]                */
+    float    *prev_xy;      /* out, may be NULL: f32[capacity * k * 2]                */
+    uint32_t *index;        /* out, may be NULL: u32[capacity * k] storage index at that moment */
+} gpe_tracer_frames;        /* 64 bytes */
+/* Arms the recorder: steps_seen = recorded = 0, the ring empty.  Synchronises (the uids are uploaded). */
+gpe_status gpe_tracers_begin(gpe_ctx *ctx, const gpe_tracer_config *cfg);
+gpe_status gpe_tracers_sample(gpe_ctx *ctx);            /* one frame now, stream-ordered, no sync */
+gpe_status gpe_tracers_read(gpe_ctx *ctx, gpe_tracer_frames *out);
+/* Disarms the recorder and frees its buffers (the frames not read are lost).  Synchronises. */
+gpe_status gpe_tracers_end(gpe_ctx *ctx);
+
 /* ---- region queries and picking (not in the reference) ------------------------------------------------------
  * Which particles lie in a region, or under a point, without downloading every position: full passes over the
  * particles on the device (csrc/k_query.hip) that change nothing on the context.  Positions, prev, radii, uids, the
