@@ -45,6 +45,7 @@ NEAREST_NONE = 0xFFFFFFFF
 TRACERS_MAX = 65536
 TRACER_POS, TRACER_PREV, TRACER_INDEX = 1, 2, 4
 TRACERS_CONSUME = 1
+MONITOR_CONSUME = 1
 NEAREST_MAX_M = 64
 EDIT_BY_INDEX, EDIT_BY_UID = 0, 1
 CLUSTER_BY_INDEX, CLUSTER_BY_UID = 0, 1
@@ -181,6 +182,30 @@ class GpeTracerFrames(C.Structure):
                 ("pos_xy", C.POINTER(C.c_float)), ("prev_xy", C.POINTER(C.c_float)), ("index", C.POINTER(C.c_uint32))]
 
 
+class GpeMeasures(C.Structure):
+    """gpe_measures: one record of the run monitor, 120 bytes (all out)."""
+    _fields_ = [("step", C.c_uint64), ("n", C.c_uint64), ("irregular", C.c_uint64), ("moving", C.c_uint64),
+                ("outside", C.c_uint64), ("sum_x", C.c_double), ("sum_y", C.c_double), ("sum_vx", C.c_double),
+                ("sum_vy", C.c_double), ("sum_v2", C.c_double), ("min_x", C.c_float), ("min_y", C.c_float),
+                ("max_x", C.c_float), ("max_y", C.c_float), ("max_v2", C.c_float), ("max_v2_index", C.c_uint32),
+                ("max_v2_uid", C.c_uint32), ("first_irregular", C.c_uint32), ("first_irregular_uid", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+class GpeMonitorConfig(C.Structure):
+    """gpe_monitor_config: all in -- flags 0, a frame after every every-th step, a ring of `frames` records, the moving
+    threshold rest_speed (displacement per step)."""
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("every", C.c_uint64), ("frames", C.c_uint64),
+                ("rest_speed", C.c_float), ("reserved", C.c_uint32)]
+
+
+class GpeMonitorFrames(C.Structure):
+    """gpe_monitor_frames: in struct_size / flags / capacity, out count / recorded; frames (gpe_measures[capacity]) may
+    be NULL."""
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("capacity", C.c_uint64), ("count", C.c_uint64),
+                ("recorded", C.c_uint64), ("frames", C.POINTER(GpeMeasures))]
+
+
 class GpeParticleEdit(C.Structure):
     """gpe_particle_edit: in struct_size / key_kind / k / keys and the field arrays (each may be NULL), out edited."""
     _fields_ = [("struct_size", C.c_uint32), ("key_kind", C.c_uint32), ("k", C.c_uint64),
@@ -238,6 +263,11 @@ SYMBOLS = [
     ("gpe_tracers_sample", _I32, [_VP]),
     ("gpe_tracers_read", _I32, [_VP, C.POINTER(GpeTracerFrames)]),
     ("gpe_tracers_end", _I32, [_VP]),
+    ("gpe_measure", _I32, [_VP, _F, C.POINTER(GpeMeasures)]),
+    ("gpe_monitor_begin", _I32, [_VP, C.POINTER(GpeMonitorConfig)]),
+    ("gpe_monitor_sample", _I32, [_VP]),
+    ("gpe_monitor_read", _I32, [_VP, C.POINTER(GpeMonitorFrames)]),
+    ("gpe_monitor_end", _I32, [_VP]),
     ("gpe_query_circle", _I32, [_VP, _F, _F, _F, C.POINTER(GpeQueryResult)]),
     ("gpe_query_box", _I32, [_VP, _F, _F, _F, _F, C.POINTER(GpeQueryResult)]),
     ("gpe_pick", _I32, [_VP, _F, _F, C.POINTER(GpeQueryResult)]),

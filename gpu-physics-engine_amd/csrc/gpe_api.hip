@@ -727,6 +727,64 @@ static gpe_status tracers_after_step(gpe_ctx *c)
     return t.steps_seen % t.every == 0 ? tracers_take_frame(c) : GPE_OK;
 }
 
+// ---- run monitor (k_monitor.hip) -------------------------------------------------------------------------------
+static void monitor_release(gpe_ctx *c)
+{
+    dev_free(c, c->monitor.ring); dev_free(c, c->monitor.partials);
+    c->monitor = MonitorState();
+}
+
+static gpe_status monitor_alloc(gpe_ctx *c, const char *who, void **p, uint64_t payload, const char *tag)
+{
+    const hipError_t e = gpe_dev_reserve(c, p, payload, 0, tag);
+    if (e == hipErrorOutOfMemory) return fail(c, GPE_ERR_OOM, std::string(who) + ": does not fit in device memory");
+    if (e != hipSuccess) return fail(c, GPE_ERR_HIP, std::string(who) + ": " + hipGetErrorName(e));
+    return GPE_OK;
+}
+
+// The scratch of every record: the partial records, then the device record of gpe_measure.  Written by index below
+// monitor_grid(n) <= kMonitorMaxBlocks and whole records.  no slack
+static gpe_status monitor_reserve(gpe_ctx *c, const char *who)
+{
+    if (c->monitor.partials) return GPE_OK;
+    return monitor_alloc(c, who, (void **)&c->monitor.partials,
+                         kMonitorMaxBlocks * kMonitorPartialBytes + sizeof(gpe_measures), "monitor.partials");
+}
+
+// One record of the particles as they are now into *out (device memory).  Enqueues only.  Reads whichever pos / prev /
+// uids are live (the native step swaps pos with its copy partner), gpe_len and the world at this moment.
+static gpe_status monitor_record(gpe_ctx *c, const char *who, float rest_speed, uint64_t step, gpe_measures *out)
+{
+    if (c->n > 0xFFFFFFFFull)
+        return fail(c, GPE_ERR_UNSUPPORTED, std::string(who) + ": more than 2^32 - 1 particles");
+    const float rs2 = rest_speed * rest_speed;                         // binary32 (-0.0 -> +0, +inf -> +inf)
+    if (c->n) {
+        Scope s(c, "monitor/partial");
+        GPE_TRY(launch_monitor_partial(c, c->pos, c->prev, c->n, rs2, c->cfg.world_width, c->cfg.world_height,
+                                       c->monitor.partials));
+    }
+    Scope s(c, "monitor/final");
+    return launch_monitor_final(c, c->monitor.partials, c->n, step, c->uid.on ? c->uid.uids : nullptr, out);
+}
+
+// One frame at the current steps_seen into ring slot recorded % frames.
+static gpe_status monitor_take_frame(gpe_ctx *c)
+{
+    MonitorState &m = c->monitor;
+    GPE_TRY(monitor_record(c, "gpe_monitor", m.rest_speed, m.steps_seen, m.ring + m.recorded % m.frames));
+    m.recorded += 1;
+    m.held = std::min(m.held + 1, m.frames);
+    return GPE_OK;
+}
+
+// After every step of gpe_step / gpe_run on an armed context.
+static gpe_status monitor_after_step(gpe_ctx *c)
+{
+    MonitorState &m = c->monitor;
+    m.steps_seen += 1;
+    return m.steps_seen % m.every == 0 ? monitor_take_frame(c) : GPE_OK;
+}
+
 // ---- in-place edits (k_edit.hip) ---------------------------------------------------------------------------
 // One buffer of the edit workspace (tags "edit.*"): allocated at first use and, with a capacity word, regrown when
 // `count` passes it (cap == NULL: a buffer of fixed size).  payload: count elements; slack_bytes: stated at the call
@@ -949,6 +1007,7 @@ gpe_status gpe_destroy(gpe_ctx *c)
     if (c->trace_origin) (void)hipEventDestroy(c->trace_origin);
     free_particle_buffers(c);
     tracers_release(c);
+    monitor_release(c);
     sort_release(c);
     scan_release(c);
     onesweep_release(c);
@@ -1426,6 +1485,111 @@ gpe_status gpe_tracers_end(gpe_ctx *c)
     GPE_HIP(c, hipSetDevice(c->device));
     GPE_HIP(c, hipStreamSynchronize(c->stream));                       // (frames in flight still write the ring)
     tracers_release(c);
+    return GPE_OK;
+}
+
+// ---- run monitor (k_monitor.hip) -------------------------------------------------------------------------------
+static bool monitor_rest_speed_ok(float r) { return r >= 0.0f; }      // NaN and negatives fail; -0.0 and +inf pass
+
+gpe_status gpe_measure(gpe_ctx *c, float rest_speed, gpe_measures *out)
+{
+    if (!c) return GPE_ERR_INVALID_ARG;
+    if (!out) return fail(c, GPE_ERR_INVALID_ARG, "gpe_measure: NULL out");
+    if (!monitor_rest_speed_ok(rest_speed)) return fail(c, GPE_ERR_INVALID_ARG, "gpe_measure: rest_speed is NaN or negative");
+    if (is_sharded(c))
+        return fail(c, GPE_ERR_UNSUPPORTED, "gpe_measure: not supported on a sharded context (gpe_shard_*, order keys or "
+                                            "an active cell box)");
+    if (c->n > 0xFFFFFFFFull) return fail(c, GPE_ERR_UNSUPPORTED, "gpe_measure: more than 2^32 - 1 particles");
+    gpe_measures r;
+    if (c->n == 0) {                                                   // nothing to read: the "none" values
+        memset(&r, 0, sizeof(r));
+        r.min_x = r.min_y = INFINITY;
+        r.max_x = r.max_y = -INFINITY;
+        r.max_v2_index = r.first_irregular = 0xFFFFFFFFu;
+        r.max_v2_uid = r.first_irregular_uid = GPE_UID_ABSENT;
+        *out = r;
+        return GPE_OK;
+    }
+    GPE_HIP(c, hipSetDevice(c->device));
+    GPE_TRY(monitor_reserve(c, "gpe_measure"));
+    gpe_measures *dev = (gpe_measures *)(c->monitor.partials + kMonitorMaxBlocks * kMonitorPartialBytes);
+    GPE_TRY(monitor_record(c, "gpe_measure", rest_speed, 0, dev));
+    GPE_HIP(c, hipMemcpyAsync(&r, dev, sizeof(r), hipMemcpyDeviceToHost, c->stream));
+    GPE_TRY(check_device_errors(c));                                   // (synchronises the stream)
+    *out = r;
+    return GPE_OK;
+}
+
+gpe_status gpe_monitor_begin(gpe_ctx *c, const gpe_monitor_config *cfg)
+{
+    if (!c) return GPE_ERR_INVALID_ARG;
+    if (!cfg || cfg->struct_size < sizeof(gpe_monitor_config))
+        return fail(c, GPE_ERR_INVALID_ARG, "gpe_monitor_begin: NULL cfg or bad struct_size");
+    if (cfg->flags) return fail(c, GPE_ERR_INVALID_ARG, "gpe_monitor_begin: flags must be 0");
+    if (cfg->every == 0 || cfg->frames == 0) return fail(c, GPE_ERR_INVALID_ARG, "gpe_monitor_begin: every and frames must be >= 1");
+    if (!monitor_rest_speed_ok(cfg->rest_speed))
+        return fail(c, GPE_ERR_INVALID_ARG, "gpe_monitor_begin: rest_speed is NaN or negative");
+    if (is_sharded(c))
+        return fail(c, GPE_ERR_UNSUPPORTED, "gpe_monitor_begin: not supported on a sharded context (gpe_shard_*, order "
+                                            "keys or an active cell box)");
+    if (c->n > 0xFFFFFFFFull) return fail(c, GPE_ERR_UNSUPPORTED, "gpe_monitor_begin: more than 2^32 - 1 particles");
+    MonitorState &m = c->monitor;
+    if (m.armed) return fail(c, GPE_ERR_STATE, "gpe_monitor_begin: already armed (gpe_monitor_end first)");
+    GPE_TRY(need_particles(c));
+    if (cfg->frames > (1ull << 40) / sizeof(gpe_measures))             // (far past any device)
+        return fail(c, GPE_ERR_OOM, "gpe_monitor_begin: the ring does not fit in device memory");
+    GPE_HIP(c, hipSetDevice(c->device));
+    GPE_TRY(monitor_reserve(c, "gpe_monitor_begin"));
+    // written one whole record at a time, at slot recorded % frames.  no slack
+    GPE_TRY(monitor_alloc(c, "gpe_monitor_begin: the ring", (void **)&m.ring, cfg->frames * sizeof(gpe_measures), "monitor.ring"));
+    m.armed = true;
+    m.every = cfg->every; m.frames = cfg->frames; m.rest_speed = cfg->rest_speed;
+    m.steps_seen = m.recorded = m.held = 0;
+    return GPE_OK;
+}
+
+gpe_status gpe_monitor_sample(gpe_ctx *c)
+{
+    if (!c) return GPE_ERR_INVALID_ARG;
+    if (!c->monitor.armed) return fail(c, GPE_ERR_STATE, "gpe_monitor_sample: not armed (gpe_monitor_begin)");
+    GPE_HIP(c, hipSetDevice(c->device));
+    return monitor_take_frame(c);
+}
+
+gpe_status gpe_monitor_read(gpe_ctx *c, gpe_monitor_frames *out)
+{
+    if (!c) return GPE_ERR_INVALID_ARG;
+    if (!out || out->struct_size < sizeof(gpe_monitor_frames))
+        return fail(c, GPE_ERR_INVALID_ARG, "gpe_monitor_read: NULL out or bad struct_size");
+    MonitorState &m = c->monitor;
+    if (!m.armed) return fail(c, GPE_ERR_STATE, "gpe_monitor_read: not armed (gpe_monitor_begin)");
+    if (out->flags & ~(uint32_t)GPE_MONITOR_CONSUME) return fail(c, GPE_ERR_INVALID_ARG, "gpe_monitor_read: unknown flag");
+    GPE_HIP(c, hipSetDevice(c->device));
+    const uint64_t want = out->frames ? std::min(m.held, out->capacity) : 0, first = m.recorded - want;
+    // records first .. recorded - 1 lie in at most two runs of ring slots
+    for (uint64_t done = 0; done < want;) {
+        const uint64_t slot = (first + done) % m.frames, run = std::min(want - done, m.frames - slot);
+        GPE_HIP(c, hipMemcpyAsync(out->frames + done, m.ring + slot, run * sizeof(gpe_measures), hipMemcpyDeviceToHost, c->stream));
+        done += run;
+    }
+    GPE_HIP(c, hipStreamSynchronize(c->stream));
+    out->count = m.held;
+    out->recorded = m.recorded;
+    if (out->flags & GPE_MONITOR_CONSUME) m.held = 0;
+    return check_device_errors(c);
+}
+
+gpe_status gpe_monitor_end(gpe_ctx *c)
+{
+    if (!c) return GPE_ERR_INVALID_ARG;
+    MonitorState &m = c->monitor;
+    if (!m.armed) return fail(c, GPE_ERR_STATE, "gpe_monitor_end: not armed (gpe_monitor_begin)");
+    GPE_HIP(c, hipSetDevice(c->device));
+    GPE_HIP(c, hipStreamSynchronize(c->stream));                       // (frames in flight still write the ring)
+    dev_free(c, m.ring);
+    uint8_t *keep = m.partials;                                        // gpe_measure goes on using the scratch
+    m = MonitorState();
+    m.partials = keep;
     return GPE_OK;
 }
 
@@ -2673,7 +2837,8 @@ gpe_status gpe_step(gpe_ctx *c, float dt, uint32_t flags)
     GPE_TRY(need_particles(c));
     GPE_HIP(c, hipSetDevice(c->device));
     GPE_TRY(do_step(c, dt, flags));
-    return c->tracers.armed ? tracers_after_step(c) : GPE_OK;
+    if (c->tracers.armed) GPE_TRY(tracers_after_step(c));
+    return c->monitor.armed ? monitor_after_step(c) : GPE_OK;
 }
 
 gpe_status gpe_run(gpe_ctx *c, float dt, uint64_t steps, uint64_t resort_every, int32_t resort_first)
@@ -2696,6 +2861,7 @@ gpe_status gpe_run(gpe_ctx *c, float dt, uint64_t steps, uint64_t resort_every, 
         const bool resort = (s == 0 && resort_first) || (resort_every && s > 0 && (s % resort_every) == 0);
         rc = do_step(c, dt, resort ? GPE_STEP_RESORT : 0u);
         if (rc == GPE_OK && c->tracers.armed) rc = tracers_after_step(c);
+        if (rc == GPE_OK && c->monitor.armed) rc = monitor_after_step(c);
     }
     for (hipEvent_t e : fence) if (e) (void)hipEventDestroy(e);
     return rc;

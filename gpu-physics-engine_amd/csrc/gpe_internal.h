@@ -393,6 +393,21 @@ struct TracerState {            // the tracer recorder (gpe_tracers_*; k_tracers
     std::vector<uint64_t> step_of;               // host side of the ring: steps_seen when frame slot f was taken
 };
 
+// the run monitor (gpe_measure / gpe_monitor_*; k_monitor.hip).  Observation state: no step reads it
+constexpr uint32_t kMonitorMaxBlocks = 2048;     // grid cap of the partial pass (256 CUs x 8 workgroups): one partial record each
+constexpr uint64_t kMonitorPartialBytes = 80;    // sizeof(MonitorAcc), k_monitor.hip
+struct MonitorState {
+    bool armed = false;
+    uint64_t every = 1, frames = 0;              // the configuration of gpe_monitor_begin
+    float rest_speed = 0.f;
+    uint64_t steps_seen = 0;                     // steps since begin
+    uint64_t recorded = 0, held = 0;             // records taken since begin / of them still in the ring (<= frames)
+    gpe_measures *ring = nullptr;                // frames records, written whole by k_monitor_final
+    // kMonitorMaxBlocks partial records, then one gpe_measures: the device record of gpe_measure.  Allocated by the
+    // first record taken, kept until gpe_destroy (a fixed size: no frame ever has to reallocate it)
+    uint8_t *partials = nullptr;
+};
+
 struct SortWorkspace {
     uint32_t *keys_b = nullptr, *vals_b = nullptr;   // ping-pong partners, cap entries each
     uint64_t cap = 0;
@@ -731,6 +746,7 @@ struct gpe_ctx {
     gpe::RemoveWorkspace remove_ws;
     gpe::UidState uid;
     gpe::TracerState tracers;
+    gpe::MonitorState monitor;
     gpe::QueryWorkspace query_ws;
     gpe::ContactsWorkspace contacts_ws;
     gpe::ClustersWorkspace clusters_ws;
@@ -978,6 +994,14 @@ gpe_status launch_tracers_resolve(gpe_ctx *c, const uint32_t *uids, uint64_t n, 
 // row j of the non-NULL frame arrays = pos / prev / index of particle slot_index[j] (< n), or quiet NaN / GPE_UID_ABSENT
 gpe_status launch_tracers_sample(gpe_ctx *c, const uint32_t *slot_index, uint32_t k, const float2 *pos, const float2 *prev,
                                  uint64_t n, float2 *pos_row, float2 *prev_row, uint32_t *index_row);
+// run monitor (k_monitor.hip).  partial: one partial record per workgroup of monitor_grid(n) <= kMonitorMaxBlocks into
+// `partials`, from pos / prev [0, n), 1 <= n < 2^32; rs2 = rest_speed * rest_speed, W / H the world.  final: folds the
+// monitor_grid(n) partials (none for n == 0) in index order and writes *out whole, uids (NULL: off) read at two indices
+uint32_t monitor_grid(uint64_t n);
+gpe_status launch_monitor_partial(gpe_ctx *c, const float2 *pos, const float2 *prev, uint64_t n, float rs2, float W,
+                                  float H, void *partials);
+gpe_status launch_monitor_final(gpe_ctx *c, const void *partials, uint64_t n, uint64_t step, const uint32_t *uids,
+                                gpe_measures *out);
 // native pipeline: its host side (gpe_native.hip; the kernels and their launchers: k_native.hip, native_launch.h)
 gpe_status native_configure(gpe_ctx *c);
 bool native_should_run(gpe_ctx *c);

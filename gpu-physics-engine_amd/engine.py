@@ -46,6 +46,12 @@ Neighbours = collections.namedtuple("Neighbours", "count index dist2 uid pos rad
 # (count, k, 2), index (count, k); row j belongs to uids[j], NaN / L.UID_ABSENT while no such particle exists; prev /
 # index None unless recorded; recorded = frames taken since begin
 TracerFrames = collections.namedtuple("TracerFrames", "step pos prev index recorded")
+# measure: one gpe_measures record (include/gpe.h) field for field; monitor_read delivers the same fields as a numpy
+# structured array of dtype MEASURES_DTYPE (120 bytes per record, the struct's layout)
+MEASURES_DTYPE = np.dtype([(name, {C.c_uint64: np.uint64, C.c_double: np.float64, C.c_float: np.float32,
+                                   C.c_uint32: np.uint32}[ctype]) for name, ctype in L.GpeMeasures._fields_])
+assert MEASURES_DTYPE.itemsize == C.sizeof(L.GpeMeasures)
+Measures = collections.namedtuple("Measures", [name for name, _ in L.GpeMeasures._fields_])
 
 
 class Context:
@@ -465,6 +471,56 @@ class ParticleSystem:
         """gpe_tracers_end: stop recording and free the ring (frames not read are lost)."""
         self.ctx.call("gpe_tracers_end")
         self._tracers = None
+
+    # Run monitor (not in the reference; include/gpe.h): scalars of the whole system -- motion, extent, health -- from a
+    # full-pass reduction on the device: one record now (measure), or one per frame into a ring while update() / run()
+    # go on, no synchronisation until monitor_read.  Nothing a step can see changes.
+    @staticmethod
+    def _rest_speed(who, rest_speed):
+        r = float(rest_speed)
+        if not r >= 0.0:
+            raise ValueError("%s: rest_speed must be >= 0 (or +inf), got %r" % (who, rest_speed))
+        return r
+
+    def measure(self, rest_speed=0.0):
+        """gpe_measure -> Measures: one record of the particles as they are now (step = 0).  rest_speed: a particle
+        counts as moving when its squared displacement per step exceeds rest_speed ** 2.  Blocks like a download."""
+        r = self._rest_speed("measure", rest_speed)
+        out = L.GpeMeasures()
+        self.ctx.call("gpe_measure", C.c_float(r), C.byref(out))
+        return Measures(*[getattr(out, name) for name in Measures._fields])
+
+    def monitor_begin(self, every=1, frames=1024, rest_speed=0.0):
+        """gpe_monitor_begin: a record after every every-th step into a ring of `frames` records."""
+        every, frames = int(every), int(frames)
+        if every < 1 or frames < 1:
+            raise ValueError("monitor_begin: every and frames must be >= 1, got %d and %d" % (every, frames))
+        r = self._rest_speed("monitor_begin", rest_speed)
+        cfg = L.GpeMonitorConfig(struct_size=C.sizeof(L.GpeMonitorConfig), flags=0, every=every, frames=frames,
+                                 rest_speed=r)
+        self.ctx.call("gpe_monitor_begin", C.byref(cfg))
+
+    def monitor_sample(self):
+        """gpe_monitor_sample: one record now, at the current step count (the frame at step 0).  Does not synchronise."""
+        self.ctx.call("gpe_monitor_sample")
+
+    def monitor_read(self, consume=False):
+        """gpe_monitor_read -> (records, recorded): the records the ring holds, oldest first, as a structured array of
+        MEASURES_DTYPE, and the number taken since monitor_begin.  consume=True empties the ring afterwards.  Blocks
+        like a download."""
+        fr = L.GpeMonitorFrames(struct_size=C.sizeof(L.GpeMonitorFrames), flags=0, capacity=0)
+        self.ctx.call("gpe_monitor_read", C.byref(fr))                 # frames NULL: count only
+        count = fr.count
+        records = np.zeros(max(count, 1), MEASURES_DTYPE)
+        fr = L.GpeMonitorFrames(struct_size=C.sizeof(L.GpeMonitorFrames), flags=L.MONITOR_CONSUME if consume else 0,
+                                capacity=count)
+        fr.frames = records.ctypes.data_as(C.POINTER(L.GpeMeasures))
+        self.ctx.call("gpe_monitor_read", C.byref(fr))
+        return records[:count], fr.recorded
+
+    def monitor_end(self):
+        """gpe_monitor_end: stop recording and free the ring (records not read are lost)."""
+        self.ctx.call("gpe_monitor_end")
 
     # Region queries and picking (not in the reference; include/gpe.h): which particles lie in a circle or a box, or
     # under a point, counted and gathered on the device.  The context is left exactly as it was.
@@ -970,6 +1026,26 @@ class State:
         """ParticleSystem.tracers_end."""
         self.particles.tracers_end()
 
+    def measure(self, rest_speed=0.0):
+        """ParticleSystem.measure -> Measures: motion, extent and health of the whole system, reduced on the device."""
+        return self.particles.measure(rest_speed=rest_speed)
+
+    def monitor_begin(self, every=1, frames=1024, rest_speed=0.0):
+        """ParticleSystem.monitor_begin: record one Measures per frame while update() / run() go on."""
+        self.particles.monitor_begin(every=every, frames=frames, rest_speed=rest_speed)
+
+    def monitor_sample(self):
+        """ParticleSystem.monitor_sample: one record now."""
+        self.particles.monitor_sample()
+
+    def monitor_read(self, consume=False):
+        """ParticleSystem.monitor_read -> (records, recorded)."""
+        return self.particles.monitor_read(consume=consume)
+
+    def monitor_end(self):
+        """ParticleSystem.monitor_end."""
+        self.particles.monitor_end()
+
     def query_circle(self, center, radius):
         """ParticleSystem.query_circle -> QueryResult(index, uid, pos, prev, radius)."""
         return self.particles.query_circle(center, radius)
@@ -1066,7 +1142,8 @@ class State:
         also the uids and next_uid; with the mouse pressed its position (`mouse`); with a grid radius other than the
         one gpe_set_particles derives from the saved radii (Grid.new_without_camera) that radius (`grid_max_radius`).
         A tracer recorder (tracers_begin) is not stored: it is observation state, not step state -- a loaded State steps
-        the same bits without it and is armed again by its host."""
+        the same bits without it and is armed again by its host.  The run monitor (monitor_begin) is not stored either,
+        for the same reason."""
         extra = {}
         if self._uids_on():
             extra.update(uids=self.uids(), next_uid=np.array([self.next_uid()], np.uint64))

@@ -294,6 +294,44 @@ class ParticleSystem {
         return r;
     }
     void tracers_end() { ctx_->call(gpe_tracers_end(ctx_->raw())); tracers_k_ = 0; tracers_fields_ = 0; }
+    // not in the reference: scalars of the whole system -- motion, extent, health -- from a full-pass reduction on the
+    // device (include/gpe.h): one gpe_measures record now, or one per frame into a ring while the steps go on, with no
+    // synchronisation until monitor_read.
+    struct MonitorFrames {
+        std::vector<gpe_measures> records;       // the records the ring holds, oldest first
+        uint64_t recorded = 0;                   // records taken since monitor_begin
+    };
+    gpe_measures measure(float rest_speed = 0.f) const
+    {
+        gpe_measures m{};
+        ctx_->call(gpe_measure(ctx_->raw(), rest_speed, &m));
+        return m;
+    }
+    void monitor_begin(uint64_t every = 1, uint64_t frames = 1024, float rest_speed = 0.f)
+    {
+        gpe_monitor_config cfg{};
+        cfg.struct_size = sizeof(cfg);
+        cfg.every = every;
+        cfg.frames = frames;
+        cfg.rest_speed = rest_speed;
+        ctx_->call(gpe_monitor_begin(ctx_->raw(), &cfg));
+    }
+    void monitor_sample() { ctx_->call(gpe_monitor_sample(ctx_->raw())); }
+    MonitorFrames monitor_read(bool consume = false)
+    {
+        gpe_monitor_frames f{};
+        f.struct_size = sizeof(f);
+        ctx_->call(gpe_monitor_read(ctx_->raw(), &f));          // frames NULL: the count
+        MonitorFrames r;
+        r.records.resize(f.count);
+        f.flags = consume ? GPE_MONITOR_CONSUME : 0u;
+        f.capacity = f.count;
+        f.frames = r.records.empty() ? nullptr : r.records.data();
+        ctx_->call(gpe_monitor_read(ctx_->raw(), &f));
+        r.recorded = f.recorded;
+        return r;
+    }
+    void monitor_end() { ctx_->call(gpe_monitor_end(ctx_->raw())); }
     // not in the reference: every particle in a circle / box, or the one under a point (include/gpe.h), ascending
     // storage index; uid stays empty while uids are off.  pick() returns no rows when no disc contains the point.
     struct QueryResult {

@@ -257,6 +257,89 @@ gpe_status gpe_tracers_read(gpe_ctx *ctx, gpe_tracer_frames *out);
 /* Disarms the recorder and frees its buffers (the frames not read are lost).  Synchronises. */
 gpe_status gpe_tracers_end(gpe_ctx *ctx);
 
+/* ---- run monitor (not in the reference) ------------------------------------------------------------------------
+ * What the whole system is doing while it runs -- has it settled, is it blowing up, did a NaN appear and where, how far
+ * does the cloud extend, what are the total momentum and kinetic energy -- without stopping the run: one fixed record
+ * of scalars, computed by a full-pass reduction on the device (csrc/k_monitor.hip).  gpe_measure takes one record now;
+ * gpe_monitor_begin arms a recorder that writes one record per frame into a device-resident ring after every every-th
+ * step, stream-ordered: only gpe_monitor_read and gpe_monitor_end synchronise.  A context that is not armed launches
+ * exactly what it launches without this section.
+ *  - The record.  For storage index i, p = pos[i], q = prev[i]:  vx = p.x - q.x; vy = p.y - q.y; v2 = vx*vx + vy*vy,
+ *    IEEE binary32, one rounding per operation, left to right, no FMA.  That is the displacement per step: the recorder
+ *    does not know dt and does not divide.  A particle is irregular when any of p.x, p.y, q.x, q.y is not finite or v2
+ *    is not finite (an overflowing difference or square); every other particle is regular.  All fields except n,
+ *    irregular and first_irregular* range over the regular particles only: every term is finite, no sum can turn NaN.
+ *  - Extent: min and max in the total order of the sign-magnitude bit pattern, so -0 < +0; the delivered bits are
+ *    those of an actual particle coordinate.  Fastest particle: selected by the key
+ *    bits(v2) << 32 | (0xFFFFFFFF - index): the largest v2, the lowest storage index on a tie.
+ *  - Absent values: an index that does not exist is 0xFFFFFFFF; a uid is GPE_UID_ABSENT while uids are off or when
+ *    the index does not exist, otherwise uids[index] at that moment -- the handle that stays valid after the next
+ *    re-sort.
+ *  - Sums: each binary32 term converted exactly to double and added in double.  For a sum S of terms t_i over m
+ *    regular particles the delivered D satisfies |D - S| <= m * 2^-52 * sum|t_i|; where every partial sum is exactly
+ *    representable D is exact.  No floating-point atomics: the launch geometry and the order in which partial sums are
+ *    combined are functions of n alone, so two measurements of the same arrays give identical bytes -- in either mode,
+ *    on any context, by gpe_measure or as a monitor frame.
+ *  - Steps: a step is one gpe_step or one iteration of gpe_run.  The per-module calls and the steps of a sharded run
+ *    are not steps.  The recorder keeps steps_seen: 0 at gpe_monitor_begin, + 1 after each step, across calls --
+ *    gpe_run(7) followed by gpe_run(5) samples like gpe_run(12).
+ *  - Frames: a frame is taken after a step when steps_seen % every == 0 and measures the state that step left behind:
+ *    whichever pos / prev / uids are live, gpe_len and the world at that moment, so frames follow removals, adds,
+ *    growth, edits, gpe_set_particles and uids being switched on or off between runs.  gpe_monitor_sample takes a frame
+ *    at the current steps_seen without changing it (the frame at step 0).
+ *  - Ring: the ring keeps the newest `frames` records.  gpe_monitor_read delivers the newest min(count, capacity) of
+ *    them, oldest first; host memory past those entries is left untouched.  With frames == NULL the call only reports
+ *    count and recorded.  GPE_MONITOR_CONSUME empties the ring after delivery; recorded keeps counting.  Blocks like
+ *    gpe_download.
+ *  - Nothing a step can see changes: an armed context steps bit for bit like one that is not; counters, the kept block
+ *    table, the rosters and the uid map are left alone.  Tracers and the monitor may be armed together and are
+ *    independent.
+ *  - Errors: a NULL ctx / cfg / out, a struct_size below the struct's, every == 0, frames == 0, non-zero config flags,
+ *    an unknown read flag, a rest_speed that is NaN or negative (+inf and -0.0 are accepted): GPE_ERR_INVALID_ARG.  A
+ *    sharded context (gpe_shard_*, order keys or an active cell box) or more than 2^32 - 1 particles:
+ *    GPE_ERR_UNSUPPORTED.  gpe_monitor_begin while armed or with no particles, gpe_monitor_sample / _read / _end while
+ *    not armed: GPE_ERR_STATE.  A ring that does not fit: GPE_ERR_OOM, and the context stays unarmed.  gpe_measure with
+ *    no particles returns GPE_OK with n = 0 and the "none" values; on any error of gpe_measure the record is not
+ *    written.  gpe_destroy frees the recorder; it is observation state, not step state. */
+enum { GPE_MONITOR_CONSUME = 1u };                                           /* read flag */
+typedef struct gpe_measures {
+    uint64_t step;        /* monitor frame: steps since gpe_monitor_begin; gpe_measure: 0                   */
+    uint64_t n;           /* gpe_len at that moment                                                         */
+    uint64_t irregular;   /* number of irregular particles                                                  */
+    uint64_t moving;      /* regular particles with v2 > rest_speed*rest_speed (binary32 product; == is at rest) */
+    uint64_t outside;     /* regular particles with !(p.x >= 0 && p.x <= W && p.y >= 0 && p.y <= H), W,H as gpe_world */
+    double   sum_x, sum_y, sum_vx, sum_vy, sum_v2;   /* sums of the binary32 terms, each converted exactly to double */
+    float    min_x, min_y, max_x, max_y;             /* extent of the regular centres; none: +inf,+inf,-inf,-inf     */
+    float    max_v2;      /* largest v2 among the regular particles; none: +0                              */
+    uint32_t max_v2_index, max_v2_uid;               /* its storage index (lowest on a tie) and uid                 */
+    uint32_t first_irregular, first_irregular_uid;   /* lowest irregular storage index and its uid                  */
+    uint32_t reserved;    /* 0 */
+} gpe_measures;           /* 120 bytes */
+typedef struct gpe_monitor_config {
+    uint32_t struct_size;   /* in: sizeof(gpe_monitor_config)                         */
+    uint32_t flags;         /* in: 0                                                  */
+    uint64_t every;         /* in: >= 1: a frame after every every-th step            */
+    uint64_t frames;        /* in: >= 1: ring capacity in records                     */
+    float    rest_speed;    /* in: >= 0 (+inf, -0.0 accepted): the moving threshold, displacement per step */
+    uint32_t reserved;      /* in: ignored                                            */
+} gpe_monitor_config;       /* 32 bytes */
+typedef struct gpe_monitor_frames {
+    uint32_t struct_size;   /* in */
+    uint32_t flags;         /* in: 0 or GPE_MONITOR_CONSUME                           */
+    uint64_t capacity;      /* in: records `frames` has room for                      */
+    uint64_t count;         /* out: records held in the ring (<= config.frames)       */
+    uint64_t recorded;      /* out: records taken since begin (held + overwritten + consumed) */
+    gpe_measures *frames;   /* out, may be NULL: gpe_measures[capacity]               */
+} gpe_monitor_frames;       /* 40 bytes */
+/* One record now, step = 0.  Blocks like gpe_download. */
+gpe_status gpe_measure(gpe_ctx *ctx, float rest_speed, gpe_measures *out);
+/* Arms the recorder: steps_seen = recorded = 0, the ring empty. */
+gpe_status gpe_monitor_begin(gpe_ctx *ctx, const gpe_monitor_config *cfg);
+gpe_status gpe_monitor_sample(gpe_ctx *ctx);            /* a frame now at the current steps_seen, stream-ordered, no sync */
+gpe_status gpe_monitor_read(gpe_ctx *ctx, gpe_monitor_frames *out);
+/* Disarms the recorder and frees the ring (the records not read are lost).  Synchronises. */
+gpe_status gpe_monitor_end(gpe_ctx *ctx);
+
 /* ---- region queries and picking (not in the reference) ------------------------------------------------------
  * Which particles lie in a region, or under a point, without downloading every position: full passes over the
  * particles on the device (csrc/k_query.hip) that change nothing on the context.  Positions, prev, radii, uids, the
