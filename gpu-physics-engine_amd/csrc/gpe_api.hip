@@ -1,13 +1,12 @@
-// gpe_api.hip -- the extern "C" boundary of include/gpe.h: context, buffers, step ordering,
-// downloads, profiling.  All device work goes to one in-order hipStream per context.
+// gpe_api.hip -- the extern "C" boundary of include/gpe.h: context, device memory, particle buffers, set / add / remove,
+// uids, step ordering, downloads, profiling.  The queries are in gpe_queries.hip, the checked add, edits and kicks in
+// gpe_edits.hip, the tracers and the monitor in gpe_observe.hip.  All device work goes to one in-order hipStream per context.
 #include <math.h>
 #include <stddef.h>
 #include <stdlib.h>
 #include <string.h>
 
 #include <algorithm>
-#include <functional>
-#include <limits>
 #include <mutex>
 #include <new>
 
@@ -230,34 +229,31 @@ hipError_t gpe_dev_release(gpe_ctx *c, void **ptr)
     return hipFree(a.base);
 }
 
-template <typename T>
-static gpe_status dev_alloc(gpe_ctx *c, T **p, uint64_t count, const char *tag)
+// ---- the refusals several entry points word alike (gpe_internal.h) -----------------------------------------------
+gpe_status refuse_sharded(gpe_ctx *c, const char *who)
 {
-    // payload: count elements.  slack: the round-up to 4 elements and 64 bytes -- no kernel is known to read them; they
-    // keep the unguarded allocation at the size it always had (max(count, 4) * sizeof(T) + 64)
-    const uint64_t payload = count * sizeof(T);
-    hipError_t e = dev_reserve(c, p, payload, std::max<uint64_t>(count, 4) * sizeof(T) + 64 - payload, tag);
-    if (e == hipErrorOutOfMemory) return fail(c, GPE_ERR_OOM, "hipMalloc: out of device memory");
-    if (e != hipSuccess) return fail(c, GPE_ERR_HIP, std::string("hipMalloc: ") + hipGetErrorName(e));
-    return GPE_OK;
+    return fail(c, GPE_ERR_UNSUPPORTED, std::string(who) + ": not supported on a sharded context (gpe_shard_*, order keys "
+                                                            "or an active cell box)");
 }
 
-template <typename T>
-static void dev_free(gpe_ctx *c, T *&p)
+gpe_status refuse_too_many(gpe_ctx *c, const char *who)
 {
-    (void)dev_release(c, p);
+    return fail(c, GPE_ERR_UNSUPPORTED, std::string(who) + ": more than 2^32 - 1 particles");
 }
 
-// The uid buffers, the uid -> index map and the lookup staging (the uid switch itself stays as it is).
-static void free_uid_buffers(gpe_ctx *c)
+gpe_status refuse_uid_off(gpe_ctx *c, const char *who)
 {
-    UidState &u = c->uid;
-    dev_free(c, u.uids); dev_free(c, u.uids_copy);
-    dev_free(c, u.map_keys); dev_free(c, u.map_vals); dev_free(c, u.dup); dev_free(c, u.query);
-    u.map_cap = u.query_cap = 0;
-    u.map_valid = false;
-    c->tracers.stale = true;
+    return fail(c, GPE_ERR_STATE, std::string(who) + ": uid requested while uids are off");
 }
+
+gpe_status refuse_radius_not_finite(gpe_ctx *c, const char *who)
+{
+    return fail(c, GPE_ERR_UNSUPPORTED, std::string(who) + ": the largest radius is not finite");
+}
+
+// ---- particle buffers --------------------------------------------------------------------------------------------
+static void remove_release(gpe_ctx *c);            // below, each with its reserve functions
+static void uid_release(gpe_ctx *c);
 
 static void free_particle_buffers(gpe_ctx *c)
 {
@@ -267,37 +263,9 @@ static void free_particle_buffers(gpe_ctx *c)
     dev_free(c, c->cell_ids); dev_free(c, c->object_ids);
     dev_free(c, c->chunk_obj_count); dev_free(c, c->collision_cells); dev_free(c, c->indirect_args);
     dev_free(c, c->order_keys);
-    dev_free(c, c->remove_ws.tile_count); dev_free(c, c->remove_ws.tile_key); dev_free(c, c->remove_ws.max_key);
-    dev_free(c, c->remove_ws.mask);
-    c->remove_ws.tiles_cap = c->remove_ws.mask_cap = 0;
-    dev_free(c, c->query_ws.tile_count); dev_free(c, c->query_ws.tile_key); dev_free(c, c->query_ws.pick);
-    dev_free(c, c->query_ws.stage);
-    c->query_ws.tiles_cap = c->query_ws.stage_cap = 0;
-    ContactsWorkspace &k = c->contacts_ws;
-    dev_free(c, k.keys); dev_free(c, k.vals); dev_free(c, k.rec); dev_free(c, k.degree); dev_free(c, k.upper);
-    dev_free(c, k.tile_sum); dev_free(c, k.total); dev_free(c, k.stage);
-    k.cap = k.tiles_cap = k.stage_cap = 0;
-    RayWorkspace &y = c->ray_ws;
-    dev_free(c, y.row_start); dev_free(c, y.from); dev_free(c, y.to); dev_free(c, y.index); dev_free(c, y.uid);
-    dev_free(c, y.t); dev_free(c, y.pos); dev_free(c, y.radius);
-    y.cap = 0;
-    NearestWorkspace &nn = c->nearest_ws;
-    dev_free(c, nn.row_start); dev_free(c, nn.points); dev_free(c, nn.count); dev_free(c, nn.index); dev_free(c, nn.uid);
-    dev_free(c, nn.dist2); dev_free(c, nn.pos); dev_free(c, nn.radius);
-    nn.cap = nn.slots_cap = 0;
-    ClustersWorkspace &u = c->clusters_ws;
-    dev_free(c, u.parent); dev_free(c, u.label); dev_free(c, u.root_size); dev_free(c, u.size);
-    dev_free(c, u.tile_word); dev_free(c, u.words);
-    u.cap = u.tiles_cap = 0;
-    EditWorkspace &e = c->edit_ws;
-    dev_free(c, e.keys); dev_free(c, e.slots); dev_free(c, e.fields); dev_free(c, e.flag);
-    dev_free(c, e.tile_key); dev_free(c, e.max_key); dev_free(c, e.count);
-    e.keys_cap = e.fields_cap = e.tiles_cap = 0;
-    SpawnWorkspace &w = c->spawn_ws;
-    dev_free(c, w.pos); dev_free(c, w.radius); dev_free(c, w.keys); dev_free(c, w.vals); dev_free(c, w.rec);
-    dev_free(c, w.blocked); dev_free(c, w.state); dev_free(c, w.rank); dev_free(c, w.verdict); dev_free(c, w.ctl);
-    w.cap = 0;
-    free_uid_buffers(c);
+    remove_release(c); query_release(c); contacts_release(c); ray_release(c); nearest_release(c);
+    clusters_release(c); edit_release(c); spawn_release(c);
+    uid_release(c);
     c->cap = 0;
 }
 
@@ -372,7 +340,7 @@ static gpe_status alloc_particle_buffers(gpe_ctx *c, uint64_t cap, bool with_gri
 }
 
 // Initial values of the index buffers for particles [lo, hi).
-static gpe_status init_index_buffers(gpe_ctx *c, uint64_t lo, uint64_t hi)
+gpe_status init_index_buffers(gpe_ctx *c, uint64_t lo, uint64_t hi)
 {
     if (hi <= lo) return GPE_OK;
     const uint64_t cnt = hi - lo;
@@ -463,7 +431,7 @@ static gpe_status copy_into_new_buffers(gpe_ctx *c, const ParticleBufferSet &old
     return GPE_OK;
 }
 
-static gpe_status grow_particle_buffers(gpe_ctx *c, uint64_t cap)
+gpe_status grow_particle_buffers(gpe_ctx *c, uint64_t cap)
 {
     const uint64_t old_n = c->n;
     GPE_HIP(c, hipStreamSynchronize(c->stream));
@@ -497,12 +465,12 @@ static float max_abs_radius(const float *radius, uint64_t n, float start)
     return best;
 }
 
-static void refresh_cell_size(gpe_ctx *c)
+void refresh_cell_size(gpe_ctx *c)
 {
     c->cell_size = c->grid_max_radius * c->cfg.cell_size_multiplier;        // grid.rs:159-161
 }
 
-static gpe_status need_particles(gpe_ctx *c)
+gpe_status need_particles(gpe_ctx *c)
 {
     if (!c) return GPE_ERR_INVALID_ARG;
     if (c->n == 0 || !c->pos) return fail(c, GPE_ERR_STATE, "no particles: call gpe_set_particles first");
@@ -513,9 +481,7 @@ static gpe_status need_particles(gpe_ctx *c)
 static gpe_status check_removable(gpe_ctx *c, const char *who)
 {
     GPE_TRY(need_particles(c));
-    if (c->shard.on || c->use_order_keys || c->has_active_box)
-        return fail(c, GPE_ERR_UNSUPPORTED, std::string(who) + ": not supported on a sharded context (gpe_shard_*, "
-                                                                "order keys or an active cell box)");
+    if (is_sharded(c)) return refuse_sharded(c, who);
     return GPE_OK;
 }
 
@@ -540,6 +506,13 @@ static gpe_status remove_reserve(gpe_ctx *c, uint64_t mask_bytes)
         ws.mask_cap = want;
     }
     return scan_reserve(c, tiles);
+}
+
+static void remove_release(gpe_ctx *c)
+{
+    RemoveWorkspace &ws = c->remove_ws;
+    dev_free(c, ws.tile_count); dev_free(c, ws.tile_key); dev_free(c, ws.max_key); dev_free(c, ws.mask);
+    ws.tiles_cap = ws.mask_cap = 0;
 }
 
 // Stable compaction of the particles that survive `mask` (device bytes, != 0: removed) or, mask == NULL, the disc
@@ -598,10 +571,6 @@ static gpe_status do_remove(gpe_ctx *c, const uint8_t *mask, float x, float y, f
 }
 
 // ---- uids (k_uids.hip) ----------------------------------------------------------------------------------
-constexpr uint64_t kUidLimit = 1ull << 32;                     // next_uid may reach 2^32: then no particle can be added
-
-static bool is_sharded(const gpe_ctx *c) { return c->shard.on || c->use_order_keys || c->has_active_box; }
-
 // Off -> on: the uid buffers for the current capacity (none yet without particles).
 static gpe_status uids_switch_on(gpe_ctx *c)
 {
@@ -610,7 +579,7 @@ static gpe_status uids_switch_on(gpe_ctx *c)
         gpe_status st = dev_alloc(c, &u.uids, c->cap, "uid.uids");
         if (st == GPE_OK) st = dev_alloc(c, &u.uids_copy, c->cap, "uid.uids_copy");
         if (st != GPE_OK) {
-            free_uid_buffers(c);
+            uid_release(c);
             return st;
         }
     }
@@ -655,7 +624,7 @@ static gpe_status uid_map_build(gpe_ctx *c, const uint32_t *src, bool *dup)
 }
 
 // The live uids' map, rebuilt only when something has made it stale.  Needs c->n >= 1.
-static gpe_status uid_map_ready(gpe_ctx *c)
+gpe_status uid_map_ready(gpe_ctx *c)
 {
     if (c->uid.map_valid) return GPE_OK;
     bool dup = false;
@@ -665,7 +634,7 @@ static gpe_status uid_map_ready(gpe_ctx *c)
     return GPE_OK;
 }
 
-static gpe_status uid_query_reserve(gpe_ctx *c, uint64_t bytes)
+gpe_status uid_query_reserve(gpe_ctx *c, uint64_t bytes)
 {
     UidState &u = c->uid;
     if (u.query_cap >= bytes) return GPE_OK;
@@ -676,130 +645,15 @@ static gpe_status uid_query_reserve(gpe_ctx *c, uint64_t bytes)
     return GPE_OK;
 }
 
-// ---- tracers (k_tracers.hip) ---------------------------------------------------------------------------------
-static gpe_status tracers_alloc(gpe_ctx *c, void **p, uint64_t payload, const char *tag)
+// The uid buffers, the uid -> index map and the lookup staging (the uid switch itself stays as it is).
+static void uid_release(gpe_ctx *c)
 {
-    const hipError_t e = gpe_dev_reserve(c, p, payload, 0, tag);
-    if (e == hipErrorOutOfMemory) return fail(c, GPE_ERR_OOM, "gpe_tracers_begin: out of device memory");
-    if (e != hipSuccess) return fail(c, GPE_ERR_HIP, std::string("gpe_tracers_begin: ") + hipGetErrorName(e));
-    return GPE_OK;
-}
-
-static void tracers_release(gpe_ctx *c)
-{
-    TracerState &t = c->tracers;
-    dev_free(c, t.keys); dev_free(c, t.perm); dev_free(c, t.slot_index);
-    dev_free(c, t.ring_pos); dev_free(c, t.ring_prev); dev_free(c, t.ring_index);
-    t = TracerState();
-}
-
-// One frame at the current steps_seen into ring slot recorded % frames.  Enqueues only: a memset and the resolve pass
-// when the slot table is stale, then the sample.  The step numbers stay on the host, which issues every frame.
-static gpe_status tracers_take_frame(gpe_ctx *c)
-{
-    TracerState &t = c->tracers;
-    const uint32_t k = (uint32_t)t.k;
-    if (t.stale) {
-        Scope s(c, "tracers/resolve");
-        GPE_HIP(c, hipMemsetAsync(t.slot_index, 0xff, k * sizeof(uint32_t), c->stream));
-        if (c->uid.on && c->uid.uids)                                  // uids off: nothing to read, every tracer is absent
-            GPE_TRY(launch_tracers_resolve(c, c->uid.uids, c->n, t.keys, t.perm, k, t.lo, t.hi, t.slot_index));
-        t.stale = false;
-    }
-    const uint64_t slot = t.recorded % t.frames, row = slot * t.k;
-    {
-        Scope s(c, "tracers/sample");
-        GPE_TRY(launch_tracers_sample(c, t.slot_index, k, c->pos, c->prev, c->n, t.ring_pos ? t.ring_pos + row : nullptr,
-                                      t.ring_prev ? t.ring_prev + row : nullptr,
-                                      t.ring_index ? t.ring_index + row : nullptr));
-    }
-    t.step_of[slot] = t.steps_seen;
-    t.recorded += 1;
-    t.held = std::min(t.held + 1, t.frames);
-    return GPE_OK;
-}
-
-// After every step of gpe_step / gpe_run on an armed context.
-static gpe_status tracers_after_step(gpe_ctx *c)
-{
-    TracerState &t = c->tracers;
-    t.steps_seen += 1;
-    return t.steps_seen % t.every == 0 ? tracers_take_frame(c) : GPE_OK;
-}
-
-// ---- run monitor (k_monitor.hip) -------------------------------------------------------------------------------
-static void monitor_release(gpe_ctx *c)
-{
-    dev_free(c, c->monitor.ring); dev_free(c, c->monitor.partials);
-    c->monitor = MonitorState();
-}
-
-static gpe_status monitor_alloc(gpe_ctx *c, const char *who, void **p, uint64_t payload, const char *tag)
-{
-    const hipError_t e = gpe_dev_reserve(c, p, payload, 0, tag);
-    if (e == hipErrorOutOfMemory) return fail(c, GPE_ERR_OOM, std::string(who) + ": does not fit in device memory");
-    if (e != hipSuccess) return fail(c, GPE_ERR_HIP, std::string(who) + ": " + hipGetErrorName(e));
-    return GPE_OK;
-}
-
-// The scratch of every record: the partial records, then the device record of gpe_measure.  Written by index below
-// monitor_grid(n) <= kMonitorMaxBlocks and whole records.  no slack
-static gpe_status monitor_reserve(gpe_ctx *c, const char *who)
-{
-    if (c->monitor.partials) return GPE_OK;
-    return monitor_alloc(c, who, (void **)&c->monitor.partials,
-                         kMonitorMaxBlocks * kMonitorPartialBytes + sizeof(gpe_measures), "monitor.partials");
-}
-
-// One record of the particles as they are now into *out (device memory).  Enqueues only.  Reads whichever pos / prev /
-// uids are live (the native step swaps pos with its copy partner), gpe_len and the world at this moment.
-static gpe_status monitor_record(gpe_ctx *c, const char *who, float rest_speed, uint64_t step, gpe_measures *out)
-{
-    if (c->n > 0xFFFFFFFFull)
-        return fail(c, GPE_ERR_UNSUPPORTED, std::string(who) + ": more than 2^32 - 1 particles");
-    const float rs2 = rest_speed * rest_speed;                         // binary32 (-0.0 -> +0, +inf -> +inf)
-    if (c->n) {
-        Scope s(c, "monitor/partial");
-        GPE_TRY(launch_monitor_partial(c, c->pos, c->prev, c->n, rs2, c->cfg.world_width, c->cfg.world_height,
-                                       c->monitor.partials));
-    }
-    Scope s(c, "monitor/final");
-    return launch_monitor_final(c, c->monitor.partials, c->n, step, c->uid.on ? c->uid.uids : nullptr, out);
-}
-
-// One frame at the current steps_seen into ring slot recorded % frames.
-static gpe_status monitor_take_frame(gpe_ctx *c)
-{
-    MonitorState &m = c->monitor;
-    GPE_TRY(monitor_record(c, "gpe_monitor", m.rest_speed, m.steps_seen, m.ring + m.recorded % m.frames));
-    m.recorded += 1;
-    m.held = std::min(m.held + 1, m.frames);
-    return GPE_OK;
-}
-
-// After every step of gpe_step / gpe_run on an armed context.
-static gpe_status monitor_after_step(gpe_ctx *c)
-{
-    MonitorState &m = c->monitor;
-    m.steps_seen += 1;
-    return m.steps_seen % m.every == 0 ? monitor_take_frame(c) : GPE_OK;
-}
-
-// ---- in-place edits (k_edit.hip) ---------------------------------------------------------------------------
-// One buffer of the edit workspace (tags "edit.*"): allocated at first use and, with a capacity word, regrown when
-// `count` passes it (cap == NULL: a buffer of fixed size).  payload: count elements; slack_bytes: stated at the call
-// with its reader.
-template <typename T>
-static gpe_status edit_buffer(gpe_ctx *c, T **p, uint64_t *cap, uint64_t count, uint64_t slack_bytes, const char *tag)
-{
-    if (*p && (!cap || *cap >= count)) return GPE_OK;
-    dev_free(c, *p);
-    if (cap) *cap = 0;
-    const hipError_t e = dev_reserve(c, p, count * sizeof(T), slack_bytes, tag);
-    if (e == hipErrorOutOfMemory) return fail(c, GPE_ERR_OOM, "hipMalloc: out of device memory");
-    if (e != hipSuccess) return fail(c, GPE_ERR_HIP, std::string("hipMalloc: ") + hipGetErrorName(e));
-    if (cap) *cap = count;
-    return GPE_OK;
+    UidState &u = c->uid;
+    dev_free(c, u.uids); dev_free(c, u.uids_copy);
+    dev_free(c, u.map_keys); dev_free(c, u.map_vals); dev_free(c, u.dup); dev_free(c, u.query);
+    u.map_cap = u.query_cap = 0;
+    u.map_valid = false;
+    c->tracers.stale = true;
 }
 
 // ---- step pieces ------------------------------------------------------------------------------------
@@ -897,6 +751,41 @@ static gpe_status do_step(gpe_ctx *c, float dt, uint32_t flags)
     if (c->profile_every > 1) c->profiling = true;
     return st;
 }
+
+// Device-side error words (sticky): reported at the synchronising entry points.
+gpe_status check_device_errors(gpe_ctx *c)
+{
+    uint32_t words[3] = {0, 0, 0};
+    if (c->shard.counts)
+        GPE_HIP(c, hipMemcpyAsync(&words[2], c->shard.counts + kShardError, 4, hipMemcpyDeviceToHost, c->stream));
+    if (c->native.tile_ctl)
+        GPE_HIP(c, hipMemcpyAsync(&words[0], c->native.tile_ctl + 8, 4, hipMemcpyDeviceToHost, c->stream));
+    if (c->os_ws.ctl)
+        GPE_HIP(c, hipMemcpyAsync(&words[1], c->os_ws.ctl + 4, 4, hipMemcpyDeviceToHost, c->stream));
+    GPE_HIP(c, hipStreamSynchronize(c->stream));
+    if (words[1]) return fail(c, GPE_ERR_HIP, "radix sort: decoupled look-back timed out");
+    if (words[0] & 2u)
+        return fail(c, GPE_ERR_UNSUPPORTED,
+                    "native collide: a region of 24x24 cells holds more particles than the LDS cell window "
+                    "takes; results of that step are unresolved there -- use GPE_MODE_COMPAT for this scene");
+    if (words[0] & 5u)
+        return fail(c, GPE_ERR_STATE, "native collide: a particle left the world box between steps");
+    if (words[0] & 16u)
+        return fail(c, GPE_ERR_STATE, "sharded run: the device-side particle count passed the host's bound");
+    if (words[2])
+        return fail(c, GPE_ERR_UNSUPPORTED, shard_error_text(words[2]));
+    return GPE_OK;
+}
+
+// (Re)derive the native pipeline's cell box after anything it depends on changed.
+gpe_status reconfigure(gpe_ctx *c)
+{
+    if (c->cfg.mode == GPE_MODE_NATIVE && c->n > 0) return native_configure(c);
+    c->native.policy.eligible = false;
+    return GPE_OK;
+}
+
+gpe_status reconfigure_native(gpe_ctx *c) { return reconfigure(c); }
 
 gpe_status step_for_shard(gpe_ctx *c, float dt) { return do_step(c, dt, 0u); }
 gpe_status resort_for_shard(gpe_ctx *c) { return do_resort(c); }
@@ -1006,8 +895,7 @@ gpe_status gpe_destroy(gpe_ctx *c)
     }
     if (c->trace_origin) (void)hipEventDestroy(c->trace_origin);
     free_particle_buffers(c);
-    tracers_release(c);
-    monitor_release(c);
+    observers_release(c);
     sort_release(c);
     scan_release(c);
     onesweep_release(c);
@@ -1021,45 +909,6 @@ gpe_status gpe_destroy(gpe_ctx *c)
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     delete c;
     return GPE_OK;
-}
-
-// Device-side error words (sticky): reported at the synchronising entry points.
-static gpe_status check_device_errors(gpe_ctx *c)
-{
-    uint32_t words[3] = {0, 0, 0};
-    if (c->shard.counts)
-        GPE_HIP(c, hipMemcpyAsync(&words[2], c->shard.counts + kShardError, 4, hipMemcpyDeviceToHost, c->stream));
-    if (c->native.tile_ctl)
-        GPE_HIP(c, hipMemcpyAsync(&words[0], c->native.tile_ctl + 8, 4, hipMemcpyDeviceToHost, c->stream));
-    if (c->os_ws.ctl)
-        GPE_HIP(c, hipMemcpyAsync(&words[1], c->os_ws.ctl + 4, 4, hipMemcpyDeviceToHost, c->stream));
-    GPE_HIP(c, hipStreamSynchronize(c->stream));
-    if (words[1]) return fail(c, GPE_ERR_HIP, "radix sort: decoupled look-back timed out");
-    if (words[0] & 2u)
-        return fail(c, GPE_ERR_UNSUPPORTED,
-                    "native collide: a region of 24x24 cells holds more particles than the LDS cell window "
-                    "takes; results of that step are unresolved there -- use GPE_MODE_COMPAT for this scene");
-    if (words[0] & 5u)
-        return fail(c, GPE_ERR_STATE, "native collide: a particle left the world box between steps");
-    if (words[0] & 16u)
-        return fail(c, GPE_ERR_STATE, "sharded run: the device-side particle count passed the host's bound");
-    if (words[2])
-        return fail(c, GPE_ERR_UNSUPPORTED, shard_error_text(words[2]));
-    return GPE_OK;
-}
-
-// (Re)derive the native pipeline's cell box after anything it depends on changed.
-static gpe_status reconfigure(gpe_ctx *c)
-{
-    if (c->cfg.mode == GPE_MODE_NATIVE && c->n > 0) return native_configure(c);
-    c->native.policy.eligible = false;
-    return GPE_OK;
-}
-
-extern "C++" {
-namespace gpe {
-gpe_status reconfigure_native(gpe_ctx *c) { return reconfigure(c); }
-}
 }
 
 gpe_status gpe_sync(gpe_ctx *c)
@@ -1214,21 +1063,19 @@ gpe_status gpe_enable_uids(gpe_ctx *c, int32_t enable)
         if (!u.on) return GPE_OK;
         GPE_HIP(c, hipSetDevice(c->device));
         GPE_HIP(c, hipStreamSynchronize(c->stream));           // (a re-sort in flight may still read them)
-        free_uid_buffers(c);
+        uid_release(c);
         u.on = false;
         u.next = 0;
         return GPE_OK;
     }
     if (u.on) return GPE_OK;                                   // keeps the current uids
-    if (is_sharded(c))
-        return fail(c, GPE_ERR_UNSUPPORTED, "gpe_enable_uids: not supported on a sharded context (gpe_shard_*, order "
-                                            "keys or an active cell box)");
+    if (is_sharded(c)) return refuse_sharded(c, "gpe_enable_uids");
     GPE_HIP(c, hipSetDevice(c->device));
     GPE_HIP(c, hipStreamSynchronize(c->stream));
     GPE_TRY(uids_switch_on(c));
     const gpe_status st = launch_uid_iota(c, u.uids, 0, c->n, 0u);
     if (st != GPE_OK) {
-        free_uid_buffers(c);
+        uid_release(c);
         u.on = false;
         return st;
     }
@@ -1239,9 +1086,7 @@ gpe_status gpe_enable_uids(gpe_ctx *c, int32_t enable)
 gpe_status gpe_set_uids(gpe_ctx *c, const uint32_t *uids, uint64_t n)
 {
     if (!c) return GPE_ERR_INVALID_ARG;
-    if (is_sharded(c))
-        return fail(c, GPE_ERR_UNSUPPORTED, "gpe_set_uids: not supported on a sharded context (gpe_shard_*, order "
-                                            "keys or an active cell box)");
+    if (is_sharded(c)) return refuse_sharded(c, "gpe_set_uids");
     if (!uids) return fail(c, GPE_ERR_INVALID_ARG, "gpe_set_uids: NULL uids");
     if (n != c->n) return fail(c, GPE_ERR_INVALID_ARG, "gpe_set_uids: n must equal gpe_len");
     GPE_TRY(need_particles(c));
@@ -1262,7 +1107,7 @@ gpe_status gpe_set_uids(gpe_ctx *c, const uint32_t *uids, uint64_t n)
     if (st == GPE_OK && dup) st = fail(c, GPE_ERR_INVALID_ARG, "gpe_set_uids: two particles would share a uid");
     if (st != GPE_OK) {
         if (!was_on) {                                         // off as before
-            free_uid_buffers(c);
+            uid_release(c);
             u.on = false;
         }
         return st;
@@ -1366,1331 +1211,6 @@ gpe_status gpe_remove_particles_by_uid(gpe_ctx *c, const uint32_t *uids, uint64_
         GPE_TRY(launch_uid_mark(c, c->uid.map_keys, c->uid.map_vals, c->n, d_query, k, c->remove_ws.mask));
     }
     return do_remove(c, c->remove_ws.mask, 0.f, 0.f, 0.f, n_removed);
-}
-
-// ---- tracers (k_tracers.hip) ---------------------------------------------------------------------------------
-gpe_status gpe_tracers_begin(gpe_ctx *c, const gpe_tracer_config *cfg)
-{
-    if (!c) return GPE_ERR_INVALID_ARG;
-    if (!cfg || cfg->struct_size < sizeof(gpe_tracer_config))
-        return fail(c, GPE_ERR_INVALID_ARG, "gpe_tracers_begin: NULL cfg or bad struct_size");
-    if (is_sharded(c))
-        return fail(c, GPE_ERR_UNSUPPORTED, "gpe_tracers_begin: not supported on a sharded context (gpe_shard_*, order "
-                                            "keys or an active cell box)");
-    constexpr uint32_t kFields = GPE_TRACER_POS | GPE_TRACER_PREV | GPE_TRACER_INDEX;
-    if (!cfg->uids) return fail(c, GPE_ERR_INVALID_ARG, "gpe_tracers_begin: NULL uids");
-    if (cfg->k == 0 || cfg->k > GPE_TRACERS_MAX)
-        return fail(c, GPE_ERR_INVALID_ARG, "gpe_tracers_begin: k must be 1 .. GPE_TRACERS_MAX");
-    if (cfg->every == 0 || cfg->frames == 0) return fail(c, GPE_ERR_INVALID_ARG, "gpe_tracers_begin: every and frames must be >= 1");
-    if (cfg->fields == 0 || (cfg->fields & ~kFields))
-        return fail(c, GPE_ERR_INVALID_ARG, "gpe_tracers_begin: fields must be GPE_TRACER_* bits, at least one");
-    const uint32_t k = (uint32_t)cfg->k;
-    // the tracked uids ascending with the tracer each one is: what the resolve pass searches
-    std::vector<uint32_t> perm(k), keys(k);
-    for (uint32_t j = 0; j < k; ++j) perm[j] = j;
-    std::sort(perm.begin(), perm.end(), [cfg](uint32_t a, uint32_t b) { return cfg->uids[a] < cfg->uids[b]; });
-    for (uint32_t j = 0; j < k; ++j) keys[j] = cfg->uids[perm[j]];
-    for (uint32_t j = 1; j < k; ++j)
-        if (keys[j] == keys[j - 1]) return fail(c, GPE_ERR_INVALID_ARG, "gpe_tracers_begin: two tracers share a uid");
-    if (c->tracers.armed) return fail(c, GPE_ERR_STATE, "gpe_tracers_begin: already armed (gpe_tracers_end first)");
-    if (!c->uid.on) return fail(c, GPE_ERR_STATE, "gpe_tracers_begin: uids are off (gpe_enable_uids)");
-    GPE_TRY(need_particles(c));
-    if (cfg->frames > (1ull << 40) / k)                                // (frames * k * 8 bytes is far past any device)
-        return fail(c, GPE_ERR_OOM, "gpe_tracers_begin: the ring does not fit in device memory");
-    GPE_HIP(c, hipSetDevice(c->device));
-    TracerState &t = c->tracers;
-    const uint64_t rows = cfg->frames * cfg->k;
-    // every array is read and written by index below k or frames * k (the resolve pass reads keys by single words
-    // below k, the uids by 16-byte groups below n / 4 and single words below n).  no slack
-    gpe_status st = tracers_alloc(c, (void **)&t.keys, k * sizeof(uint32_t), "tracers.keys");
-    if (st == GPE_OK) st = tracers_alloc(c, (void **)&t.perm, k * sizeof(uint32_t), "tracers.perm");
-    if (st == GPE_OK) st = tracers_alloc(c, (void **)&t.slot_index, k * sizeof(uint32_t), "tracers.slot_index");
-    if (st == GPE_OK && (cfg->fields & GPE_TRACER_POS))
-        st = tracers_alloc(c, (void **)&t.ring_pos, rows * sizeof(float2), "tracers.ring_pos");
-    if (st == GPE_OK && (cfg->fields & GPE_TRACER_PREV))
-        st = tracers_alloc(c, (void **)&t.ring_prev, rows * sizeof(float2), "tracers.ring_prev");
-    if (st == GPE_OK && (cfg->fields & GPE_TRACER_INDEX))
-        st = tracers_alloc(c, (void **)&t.ring_index, rows * sizeof(uint32_t), "tracers.ring_index");
-    if (st == GPE_OK) {
-        hipError_t e = hipMemcpyAsync(t.keys, keys.data(), k * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(t.perm, perm.data(), k * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);      // the host vectors go away on return
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            st = fail(c, GPE_ERR_HIP, std::string("gpe_tracers_begin: upload: ") + hipGetErrorName(e));
-        }
-    }
-    if (st != GPE_OK) {
-        const std::string why = c->last_error;
-        tracers_release(c);                                            // unarmed, as before
-        c->last_error = why;
-        return st;
-    }
-    t.armed = true;
-    t.stale = true;
-    t.fields = cfg->fields;
-    t.k = cfg->k; t.every = cfg->every; t.frames = cfg->frames;
-    t.steps_seen = t.recorded = t.held = 0;
-    t.lo = keys.front(); t.hi = keys.back();
-    t.step_of.assign((size_t)cfg->frames, 0);
-    return GPE_OK;
-}
-
-gpe_status gpe_tracers_sample(gpe_ctx *c)
-{
-    if (!c) return GPE_ERR_INVALID_ARG;
-    if (!c->tracers.armed) return fail(c, GPE_ERR_STATE, "gpe_tracers_sample: not armed (gpe_tracers_begin)");
-    GPE_HIP(c, hipSetDevice(c->device));
-    return tracers_take_frame(c);
-}
-
-gpe_status gpe_tracers_read(gpe_ctx *c, gpe_tracer_frames *out)
-{
-    if (!c) return GPE_ERR_INVALID_ARG;
-    if (!out || out->struct_size < sizeof(gpe_tracer_frames))
-        return fail(c, GPE_ERR_INVALID_ARG, "gpe_tracers_read: NULL out or bad struct_size");
-    out->count = out->recorded = 0;
-    TracerState &t = c->tracers;
-    if (!t.armed) return fail(c, GPE_ERR_STATE, "gpe_tracers_read: not armed (gpe_tracers_begin)");
-    if (out->flags & ~(uint32_t)GPE_TRACERS_CONSUME) return fail(c, GPE_ERR_INVALID_ARG, "gpe_tracers_read: unknown flag");
-    if ((out->pos_xy && !t.ring_pos) || (out->prev_xy && !t.ring_prev) || (out->index && !t.ring_index))
-        return fail(c, GPE_ERR_INVALID_ARG, "gpe_tracers_read: an array for a field the recorder was not configured with");
-    GPE_HIP(c, hipSetDevice(c->device));
-    const uint64_t m = std::min(t.held, out->capacity), first = t.recorded - m;   // frames first .. recorded - 1
-    // the frames lie in at most two runs of ring slots
-    for (uint64_t done = 0; done < m;) {
-        const uint64_t slot = (first + done) % t.frames, run = std::min(m - done, t.frames - slot);
-        const uint64_t src = slot * t.k, dst = done * t.k, rows = run * t.k;
-        if (out->pos_xy)
-            GPE_HIP(c, hipMemcpyAsync(out->pos_xy + 2 * dst, t.ring_pos + src, rows * sizeof(float2), hipMemcpyDeviceToHost, c->stream));
-        if (out->prev_xy)
-            GPE_HIP(c, hipMemcpyAsync(out->prev_xy + 2 * dst, t.ring_prev + src, rows * sizeof(float2), hipMemcpyDeviceToHost, c->stream));
-        if (out->index)
-            GPE_HIP(c, hipMemcpyAsync(out->index + dst, t.ring_index + src, rows * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-        if (out->step)
-            for (uint64_t f = 0; f < run; ++f) out->step[done + f] = t.step_of[slot + f];
-        done += run;
-    }
-    GPE_HIP(c, hipStreamSynchronize(c->stream));
-    out->count = t.held;
-    out->recorded = t.recorded;
-    if (out->flags & GPE_TRACERS_CONSUME) t.held = 0;
-    return check_device_errors(c);
-}
-
-gpe_status gpe_tracers_end(gpe_ctx *c)
-{
-    if (!c) return GPE_ERR_INVALID_ARG;
-    if (!c->tracers.armed) return fail(c, GPE_ERR_STATE, "gpe_tracers_end: not armed (gpe_tracers_begin)");
-    GPE_HIP(c, hipSetDevice(c->device));
-    GPE_HIP(c, hipStreamSynchronize(c->stream));                       // (frames in flight still write the ring)
-    tracers_release(c);
-    return GPE_OK;
-}
-
-// ---- run monitor (k_monitor.hip) -------------------------------------------------------------------------------
-static bool monitor_rest_speed_ok(float r) { return r >= 0.0f; }      // NaN and negatives fail; -0.0 and +inf pass
-
-gpe_status gpe_measure(gpe_ctx *c, float rest_speed, gpe_measures *out)
-{
-    if (!c) return GPE_ERR_INVALID_ARG;
-    if (!out) return fail(c, GPE_ERR_INVALID_ARG, "gpe_measure: NULL out");
-    if (!monitor_rest_speed_ok(rest_speed)) return fail(c, GPE_ERR_INVALID_ARG, "gpe_measure: rest_speed is NaN or negative");
-    if (is_sharded(c))
-        return fail(c, GPE_ERR_UNSUPPORTED, "gpe_measure: not supported on a sharded context (gpe_shard_*, order keys or "
-                                            "an active cell box)");
-    if (c->n > 0xFFFFFFFFull) return fail(c, GPE_ERR_UNSUPPORTED, "gpe_measure: more than 2^32 - 1 particles");
-    gpe_measures r;
-    if (c->n == 0) {                                                   // nothing to read: the "none" values
-        memset(&r, 0, sizeof(r));
-        r.min_x = r.min_y = INFINITY;
-        r.max_x = r.max_y = -INFINITY;
-        r.max_v2_index = r.first_irregular = 0xFFFFFFFFu;
-        r.max_v2_uid = r.first_irregular_uid = GPE_UID_ABSENT;
-        *out = r;
-        return GPE_OK;
-    }
-    GPE_HIP(c, hipSetDevice(c->device));
-    GPE_TRY(monitor_reserve(c, "gpe_measure"));
-    gpe_measures *dev = (gpe_measures *)(c->monitor.partials + kMonitorMaxBlocks * kMonitorPartialBytes);
-    GPE_TRY(monitor_record(c, "gpe_measure", rest_speed, 0, dev));
-    GPE_HIP(c, hipMemcpyAsync(&r, dev, sizeof(r), hipMemcpyDeviceToHost, c->stream));
-    GPE_TRY(check_device_errors(c));                                   // (synchronises the stream)
-    *out = r;
-    return GPE_OK;
-}
-
-gpe_status gpe_monitor_begin(gpe_ctx *c, const gpe_monitor_config *cfg)
-{
-    if (!c) return GPE_ERR_INVALID_ARG;
-    if (!cfg || cfg->struct_size < sizeof(gpe_monitor_config))
-        return fail(c, GPE_ERR_INVALID_ARG, "gpe_monitor_begin: NULL cfg or bad struct_size");
-    if (cfg->flags) return fail(c, GPE_ERR_INVALID_ARG, "gpe_monitor_begin: flags must be 0");
-    if (cfg->every == 0 || cfg->frames == 0) return fail(c, GPE_ERR_INVALID_ARG, "gpe_monitor_begin: every and frames must be >= 1");
-    if (!monitor_rest_speed_ok(cfg->rest_speed))
-        return fail(c, GPE_ERR_INVALID_ARG, "gpe_monitor_begin: rest_speed is NaN or negative");
-    if (is_sharded(c))
-        return fail(c, GPE_ERR_UNSUPPORTED, "gpe_monitor_begin: not supported on a sharded context (gpe_shard_*, order "
-                                            "keys or an active cell box)");
-    if (c->n > 0xFFFFFFFFull) return fail(c, GPE_ERR_UNSUPPORTED, "gpe_monitor_begin: more than 2^32 - 1 particles");
-    MonitorState &m = c->monitor;
-    if (m.armed) return fail(c, GPE_ERR_STATE, "gpe_monitor_begin: already armed (gpe_monitor_end first)");
-    GPE_TRY(need_particles(c));
-    if (cfg->frames > (1ull << 40) / sizeof(gpe_measures))             // (far past any device)
-        return fail(c, GPE_ERR_OOM, "gpe_monitor_begin: the ring does not fit in device memory");
-    GPE_HIP(c, hipSetDevice(c->device));
-    GPE_TRY(monitor_reserve(c, "gpe_monitor_begin"));
-    // written one whole record at a time, at slot recorded % frames.  no slack
-    GPE_TRY(monitor_alloc(c, "gpe_monitor_begin: the ring", (void **)&m.ring, cfg->frames * sizeof(gpe_measures), "monitor.ring"));
-    m.armed = true;
-    m.every = cfg->every; m.frames = cfg->frames; m.rest_speed = cfg->rest_speed;
-    m.steps_seen = m.recorded = m.held = 0;
-    return GPE_OK;
-}
-
-gpe_status gpe_monitor_sample(gpe_ctx *c)
-{
-    if (!c) return GPE_ERR_INVALID_ARG;
-    if (!c->monitor.armed) return fail(c, GPE_ERR_STATE, "gpe_monitor_sample: not armed (gpe_monitor_begin)");
-    GPE_HIP(c, hipSetDevice(c->device));
-    return monitor_take_frame(c);
-}
-
-gpe_status gpe_monitor_read(gpe_ctx *c, gpe_monitor_frames *out)
-{
-    if (!c) return GPE_ERR_INVALID_ARG;
-    if (!out || out->struct_size < sizeof(gpe_monitor_frames))
-        return fail(c, GPE_ERR_INVALID_ARG, "gpe_monitor_read: NULL out or bad struct_size");
-    MonitorState &m = c->monitor;
-    if (!m.armed) return fail(c, GPE_ERR_STATE, "gpe_monitor_read: not armed (gpe_monitor_begin)");
-    if (out->flags & ~(uint32_t)GPE_MONITOR_CONSUME) return fail(c, GPE_ERR_INVALID_ARG, "gpe_monitor_read: unknown flag");
-    GPE_HIP(c, hipSetDevice(c->device));
-    const uint64_t want = out->frames ? std::min(m.held, out->capacity) : 0, first = m.recorded - want;
-    // records first .. recorded - 1 lie in at most two runs of ring slots
-    for (uint64_t done = 0; done < want;) {
-        const uint64_t slot = (first + done) % m.frames, run = std::min(want - done, m.frames - slot);
-        GPE_HIP(c, hipMemcpyAsync(out->frames + done, m.ring + slot, run * sizeof(gpe_measures), hipMemcpyDeviceToHost, c->stream));
-        done += run;
-    }
-    GPE_HIP(c, hipStreamSynchronize(c->stream));
-    out->count = m.held;
-    out->recorded = m.recorded;
-    if (out->flags & GPE_MONITOR_CONSUME) m.held = 0;
-    return check_device_errors(c);
-}
-
-gpe_status gpe_monitor_end(gpe_ctx *c)
-{
-    if (!c) return GPE_ERR_INVALID_ARG;
-    MonitorState &m = c->monitor;
-    if (!m.armed) return fail(c, GPE_ERR_STATE, "gpe_monitor_end: not armed (gpe_monitor_begin)");
-    GPE_HIP(c, hipSetDevice(c->device));
-    GPE_HIP(c, hipStreamSynchronize(c->stream));                       // (frames in flight still write the ring)
-    dev_free(c, m.ring);
-    uint8_t *keep = m.partials;                                        // gpe_measure goes on using the scratch
-    m = MonitorState();
-    m.partials = keep;
-    return GPE_OK;
-}
-
-// ---- region queries and picking (k_query.hip) -------------------------------------------------------------
-static gpe_status query_reserve(gpe_ctx *c, uint64_t stage_bytes)
-{
-    QueryWorkspace &ws = c->query_ws;
-    const uint64_t tiles = query_tiles(c->n);
-    if (ws.tiles_cap < tiles) {
-        dev_free(c, ws.tile_count);
-        dev_free(c, ws.tile_key);
-        ws.tiles_cap = 0;
-        GPE_TRY(dev_alloc(c, &ws.tile_count, tiles, "query.tile_count"));
-        GPE_TRY(dev_alloc(c, &ws.tile_key, tiles, "query.tile_key"));
-        ws.tiles_cap = tiles;
-    }
-    if (!ws.pick) GPE_TRY(dev_alloc(c, &ws.pick, 1, "query.pick"));
-    if (ws.stage_cap < stage_bytes) {
-        dev_free(c, ws.stage);
-        ws.stage_cap = 0;
-        GPE_TRY(dev_alloc(c, &ws.stage, stage_bytes, "query.stage"));
-        ws.stage_cap = stage_bytes;
-    }
-    return scan_reserve(c, tiles);
-}
-
-static bool query_wants_rows(const gpe_query_result *out)
-{
-    return out->index || out->uid || out->pos_xy || out->prev_xy || out->radius;
-}
-
-// The checks every query shares, in this order: the result struct (nothing written when it is unusable), then
-// out->count = 0, the sharded refusal and uids for a uid output.  *go = false: GPE_OK with count 0 (no particles).
-static gpe_status query_begin(gpe_ctx *c, gpe_query_result *out, const char *who, bool *go)
-{
-    *go = false;
-    if (!c) return GPE_ERR_INVALID_ARG;
-    if (!out) return fail(c, GPE_ERR_INVALID_ARG, std::string(who) + ": NULL result");
-    if (out->struct_size < sizeof(gpe_query_result))
-        return fail(c, GPE_ERR_INVALID_ARG, std::string(who) + ": struct_size is smaller than gpe_query_result");
-    out->count = 0;
-    if (is_sharded(c))
-        return fail(c, GPE_ERR_UNSUPPORTED, std::string(who) + ": not supported on a sharded context (gpe_shard_*, "
-                                                                "order keys or an active cell box)");
-    if (out->uid && !c->uid.on) return fail(c, GPE_ERR_STATE, std::string(who) + ": uid requested while uids are off");
-    if (c->n > 0xFFFFFFFFull) return fail(c, GPE_ERR_UNSUPPORTED, std::string(who) + ": more than 2^32 - 1 particles");
-    *go = c->n > 0 && c->pos;
-    return GPE_OK;
-}
-
-// The first min(total, capacity) rows of a selection into the requested arrays of `out`, and out->count = total.
-// gather(m, index, uid, pos, prev, radius) launches the kernel that fills the staging parts (NULL: not requested).
-using QueryGather = std::function<gpe_status(uint32_t, uint32_t *, uint32_t *, float2 *, float2 *, float *)>;
-static gpe_status query_deliver(gpe_ctx *c, gpe_query_result *out, uint32_t total, const char *scope,
-                                const QueryGather &gather)
-{
-    QueryWorkspace &ws = c->query_ws;
-    const uint64_t m = std::min<uint64_t>(total, out->capacity);
-    if (m > 0 && query_wants_rows(out)) {
-        // staging, 256-byte aligned parts, only the requested fields: pos | prev | radius | index | uid
-        auto part = [m](bool on, uint64_t width) { return on ? (m * width + 255) / 256 * 256 : 0; };
-        const uint64_t o_prev = part(out->pos_xy, 8), o_radius = o_prev + part(out->prev_xy, 8),
-                       o_index = o_radius + part(out->radius, 4), o_uid = o_index + part(out->index, 4),
-                       bytes = o_uid + part(out->uid, 4);
-        GPE_TRY(query_reserve(c, bytes));
-        uint8_t *st = ws.stage;
-        float2 *d_pos = out->pos_xy ? reinterpret_cast<float2 *>(st) : nullptr;
-        float2 *d_prev = out->prev_xy ? reinterpret_cast<float2 *>(st + o_prev) : nullptr;
-        float *d_radius = out->radius ? reinterpret_cast<float *>(st + o_radius) : nullptr;
-        uint32_t *d_index = out->index ? reinterpret_cast<uint32_t *>(st + o_index) : nullptr;
-        uint32_t *d_uid = out->uid ? reinterpret_cast<uint32_t *>(st + o_uid) : nullptr;
-        {
-            Scope k(c, scope);
-            GPE_TRY(gather((uint32_t)m, d_index, d_uid, d_pos, d_prev, d_radius));
-        }
-        if (d_index) GPE_HIP(c, hipMemcpyAsync(out->index, d_index, m * 4, hipMemcpyDeviceToHost, c->stream));
-        if (d_uid) GPE_HIP(c, hipMemcpyAsync(out->uid, d_uid, m * 4, hipMemcpyDeviceToHost, c->stream));
-        if (d_pos) GPE_HIP(c, hipMemcpyAsync(out->pos_xy, d_pos, m * 8, hipMemcpyDeviceToHost, c->stream));
-        if (d_prev) GPE_HIP(c, hipMemcpyAsync(out->prev_xy, d_prev, m * 8, hipMemcpyDeviceToHost, c->stream));
-        if (d_radius) GPE_HIP(c, hipMemcpyAsync(out->radius, d_radius, m * 4, hipMemcpyDeviceToHost, c->stream));
-        GPE_HIP(c, hipStreamSynchronize(c->stream));
-    }
-    out->count = total;
-    return GPE_OK;
-}
-
-// Count (and, for requested rows, gather) the particles in the region; kind and region as launch_query_count takes them.
-static gpe_status do_query(gpe_ctx *c, int kind, const float *region, gpe_query_result *out)
-{
-    GPE_HIP(c, hipSetDevice(c->device));
-    GPE_HIP(c, hipStreamSynchronize(c->stream));
-    GPE_TRY(query_reserve(c, 0));
-    QueryWorkspace &ws = c->query_ws;
-    const uint64_t tiles = query_tiles(c->n);
-    uint32_t total = 0;
-    Scope s(c, "Query particles");
-    {
-        Scope k(c, "query/count");
-        GPE_TRY(launch_query_count(c, kind, region, ws.tile_count));
-    }
-    {
-        Scope k(c, "query/scan");
-        GPE_TRY(inclusive_scan(c, ws.tile_count, tiles));
-    }
-    GPE_HIP(c, hipMemcpyAsync(&total, ws.tile_count + (tiles - 1), sizeof(total), hipMemcpyDeviceToHost, c->stream));
-    GPE_HIP(c, hipStreamSynchronize(c->stream));
-    return query_deliver(c, out, total, "query/gather",
-                         [&](uint32_t m, uint32_t *d_index, uint32_t *d_uid, float2 *d_pos, float2 *d_prev, float *d_radius) {
-                             return launch_query_gather(c, kind, region, c->query_ws.tile_count, m, d_index, d_uid, d_pos,
-                                                        d_prev, d_radius);
-                         });
-}
-
-// The argument checks and the region words (as launch_query_count takes them) of the circle and box calls: the
-// queries and the kicks (gpe_kick_*) share them, so that both select the same particles.
-static gpe_status circle_region(gpe_ctx *c, const char *who, float x, float y, float radius, float (&region)[5])
-{
-    if (!(radius >= 0.0f) || !isfinite(radius))
-        return fail(c, GPE_ERR_INVALID_ARG, std::string(who) + ": radius must be finite and >= 0");
-    const float words[5] = {x, y, 0.f, 0.f, radius * radius};     // binary32, as gpe_remove_particles_in_circle
-    std::copy(words, words + 5, region);
-    return GPE_OK;
-}
-
-// *empty: x0 > x1 or y0 > y1, a box that holds nothing
-static gpe_status box_region(gpe_ctx *c, const char *who, float x0, float y0, float x1, float y1, float (&region)[5],
-                             bool *empty)
-{
-    if (isnan(x0) || isnan(y0) || isnan(x1) || isnan(y1)) return fail(c, GPE_ERR_INVALID_ARG, std::string(who) + ": NaN bound");
-    const float words[5] = {x0, y0, x1, y1, 0.f};
-    std::copy(words, words + 5, region);
-    *empty = x0 > x1 || y0 > y1;
-    return GPE_OK;
-}
-
-gpe_status gpe_query_circle(gpe_ctx *c, float x, float y, float radius, gpe_query_result *out)
-{
-    bool go = false;
-    float region[5];
-    GPE_TRY(query_begin(c, out, "gpe_query_circle", &go));
-    GPE_TRY(circle_region(c, "gpe_query_circle", x, y, radius, region));
-    if (!go) return GPE_OK;
-    return do_query(c, 0, region, out);
-}
-
-gpe_status gpe_query_box(gpe_ctx *c, float x0, float y0, float x1, float y1, gpe_query_result *out)
-{
-    bool go = false;
-    float region[5];
-    bool empty = false;
-    GPE_TRY(query_begin(c, out, "gpe_query_box", &go));
-    GPE_TRY(box_region(c, "gpe_query_box", x0, y0, x1, y1, region, &empty));
-    if (!go || empty) return GPE_OK;                              // an empty box holds nothing
-    return do_query(c, 1, region, out);
-}
-
-gpe_status gpe_query_segment(gpe_ctx *c, float x0, float y0, float x1, float y1, gpe_query_result *out)
-{
-    bool go = false;
-    GPE_TRY(query_begin(c, out, "gpe_query_segment", &go));
-    if (!isfinite(x0) || !isfinite(y0) || !isfinite(x1) || !isfinite(y1))
-        return fail(c, GPE_ERR_INVALID_ARG, "gpe_query_segment: an endpoint is not finite");
-    if (!go) return GPE_OK;
-    const float region[5] = {x0, y0, x1, y1, 0.f};
-    return do_query(c, 2, region, out);
-}
-
-gpe_status gpe_pick(gpe_ctx *c, float x, float y, gpe_query_result *out)
-{
-    bool go = false;
-    GPE_TRY(query_begin(c, out, "gpe_pick", &go));
-    if (!go) return GPE_OK;
-    GPE_HIP(c, hipSetDevice(c->device));
-    GPE_HIP(c, hipStreamSynchronize(c->stream));
-    GPE_TRY(query_reserve(c, 0));
-    QueryWorkspace &ws = c->query_ws;
-    unsigned long long key = 0;
-    {
-        Scope s(c, "Query particles");
-        Scope k(c, "query/pick");
-        GPE_TRY(launch_pick(c, x, y, ws.tile_key, ws.pick));
-    }
-    GPE_HIP(c, hipMemcpyAsync(&key, ws.pick, sizeof(key), hipMemcpyDeviceToHost, c->stream));
-    GPE_HIP(c, hipStreamSynchronize(c->stream));
-    if (key == ~0ull) return GPE_OK;                               // no disc contains the point
-    const uint32_t i = (uint32_t)(key & 0xFFFFFFFFull);
-    if (i >= c->n) return fail(c, GPE_ERR_STATE, "gpe_pick: bad index");
-    if (out->capacity >= 1) {                                     // one row: straight from the particle buffers
-        if (out->uid) GPE_HIP(c, hipMemcpyAsync(out->uid, c->uid.uids + i, 4, hipMemcpyDeviceToHost, c->stream));
-        if (out->pos_xy) GPE_HIP(c, hipMemcpyAsync(out->pos_xy, c->pos + i, 8, hipMemcpyDeviceToHost, c->stream));
-        if (out->prev_xy) GPE_HIP(c, hipMemcpyAsync(out->prev_xy, c->prev + i, 8, hipMemcpyDeviceToHost, c->stream));
-        if (out->radius) GPE_HIP(c, hipMemcpyAsync(out->radius, c->radius + i, 4, hipMemcpyDeviceToHost, c->stream));
-        GPE_HIP(c, hipStreamSynchronize(c->stream));
-        if (out->index) out->index[0] = i;
-    }
-    out->count = 1;
-    return GPE_OK;
-}
-
-// ---- contact queries (k_contacts.hip) ----------------------------------------------------------------------
-static gpe_status contacts_alloc(gpe_ctx *c, void **p, uint64_t payload, uint64_t slack, const char *tag)
-{
-    const hipError_t e = gpe_dev_reserve(c, p, payload, slack, tag);
-    if (e == hipErrorOutOfMemory) return fail(c, GPE_ERR_OOM, "gpe_query_contacts: out of device memory");
-    if (e != hipSuccess) return fail(c, GPE_ERR_HIP, std::string("gpe_query_contacts: ") + hipGetErrorName(e));
-    return GPE_OK;
-}
-
-static gpe_status contacts_reserve(gpe_ctx *c, uint64_t stage_bytes)
-{
-    ContactsWorkspace &ws = c->contacts_ws;
-    const uint64_t n = c->n, tiles = contacts_tiles(n);
-    if (ws.cap < n) {
-        dev_free(c, ws.keys); dev_free(c, ws.vals); dev_free(c, ws.rec); dev_free(c, ws.degree); dev_free(c, ws.upper);
-        ws.cap = 0;
-        // keys / vals: n words each.  slack: the 16 words sort_pairs' tile loads may read behind the n pairs
-        GPE_TRY(contacts_alloc(c, (void **)&ws.keys, n * sizeof(uint32_t), 16 * sizeof(uint32_t), "contacts.keys"));
-        GPE_TRY(contacts_alloc(c, (void **)&ws.vals, n * sizeof(uint32_t), 16 * sizeof(uint32_t), "contacts.vals"));
-        // rec: n 16-byte records, read one at a time below n.  no slack
-        GPE_TRY(contacts_alloc(c, (void **)&ws.rec, n * sizeof(uint4), 0, "contacts.rec"));
-        // degree: n words, written and read by index below n.  no slack
-        GPE_TRY(contacts_alloc(c, (void **)&ws.degree, n * sizeof(uint32_t), 0, "contacts.degree"));
-        // upper: n words, scanned in place.  slack: the 16 words the scan's tile loads may read behind them
-        GPE_TRY(contacts_alloc(c, (void **)&ws.upper, n * sizeof(uint32_t), 16 * sizeof(uint32_t), "contacts.upper"));
-        ws.cap = n;
-    }
-    if (ws.tiles_cap < tiles) {
-        dev_free(c, ws.tile_sum);
-        ws.tiles_cap = 0;
-        // tile_sum: one 64-bit word per workgroup of the count.  no slack
-        GPE_TRY(contacts_alloc(c, (void **)&ws.tile_sum, tiles * sizeof(unsigned long long), 0, "contacts.tile_sum"));
-        ws.tiles_cap = tiles;
-    }
-    // total: one 64-bit word.  no slack
-    if (!ws.total) GPE_TRY(contacts_alloc(c, (void **)&ws.total, sizeof(unsigned long long), 0, "contacts.total"));
-    if (ws.stage_cap < stage_bytes) {
-        dev_free(c, ws.stage);
-        ws.stage_cap = 0;
-        // stage: the 256-byte aligned parts of the requested per-pair arrays, written below capacity.  no slack
-        GPE_TRY(contacts_alloc(c, (void **)&ws.stage, stage_bytes, 0, "contacts.stage"));
-        ws.stage_cap = stage_bytes;
-    }
-    GPE_TRY(sort_reserve(c, n));
-    return scan_reserve(c, n);
-}
-
-// Stages (1) and (2) of the contact query, shared with the cluster query: the workspace, the cell keys under
-// `cell_size`, the sort and the 16-byte records.  Leaves contacts_ws.keys / .rec sorted by cell.  Call inside the
-// query's own scope, after the stream is idle.
-static gpe_status contacts_bin(gpe_ctx *c, float cell_size)
-{
-    GPE_TRY(contacts_reserve(c, 0));
-    ContactsWorkspace &ws = c->contacts_ws;
-    {
-        Scope k(c, "contacts/keys");
-        GPE_TRY(launch_contacts_keys(c, cell_size, ws.keys, ws.vals));
-    }
-    {
-        Scope k(c, "contacts/sort");
-        GPE_TRY(sort_pairs(c, ws.keys, ws.vals, c->n));
-        GPE_TRY(launch_contacts_records(c, ws.vals, ws.rec));
-    }
-    return GPE_OK;
-}
-
-gpe_status gpe_query_contacts(gpe_ctx *c, gpe_contact_result *out)
-{
-    const char *who = "gpe_query_contacts";
-    if (!c) return GPE_ERR_INVALID_ARG;
-    if (!out) return fail(c, GPE_ERR_INVALID_ARG, std::string(who) + ": NULL result");
-    if (out->struct_size < sizeof(gpe_contact_result)) {
-        if (out->struct_size >= offsetof(gpe_contact_result, count) + sizeof(out->count)) out->count = 0;   // it has one
-        return fail(c, GPE_ERR_INVALID_ARG, std::string(who) + ": struct_size is smaller than gpe_contact_result");
-    }
-    out->count = 0;
-    if (is_sharded(c))
-        return fail(c, GPE_ERR_UNSUPPORTED, std::string(who) + ": not supported on a sharded context (gpe_shard_*, "
-                                                                "order keys or an active cell box)");
-    if ((out->uid_a || out->uid_b) && !c->uid.on)
-        return fail(c, GPE_ERR_STATE, std::string(who) + ": uid requested while uids are off");
-    if (c->n > 0xFFFFFFFFull) return fail(c, GPE_ERR_UNSUPPORTED, std::string(who) + ": more than 2^32 - 1 particles");
-    const uint64_t n = c->n;
-    if (n == 0 || !c->pos) return GPE_OK;
-    // the query's own cell size: a contact implies a centre distance below 2 max|r|, less than one cell of 2.2 max|r|
-    const float cell_size = gpe_compute_cell_size(fabsf(c->max_radius));
-    if (n > 1 && !isfinite(cell_size))
-        return fail(c, GPE_ERR_UNSUPPORTED, std::string(who) + ": the largest radius is not finite");
-    if (n == 1 || cell_size == 0.0f) {                             // one particle, or every radius 0: nothing touches
-        if (out->degree) std::fill(out->degree, out->degree + n, 0u);
-        return GPE_OK;
-    }
-    const bool want_pairs = out->index_a || out->index_b || out->uid_a || out->uid_b || out->overlap;
-    GPE_HIP(c, hipSetDevice(c->device));
-    GPE_HIP(c, hipStreamSynchronize(c->stream));
-    ContactsWorkspace &ws = c->contacts_ws;
-    unsigned long long total = 0;
-    Scope s(c, "Query contacts");
-    GPE_TRY(contacts_bin(c, cell_size));
-    {
-        Scope k(c, "contacts/count");
-        GPE_TRY(launch_contacts_count(c, ws.keys, ws.rec, ws.degree, ws.upper, ws.tile_sum, ws.total));
-    }
-    GPE_HIP(c, hipMemcpyAsync(&total, ws.total, sizeof(total), hipMemcpyDeviceToHost, c->stream));
-    if (out->degree) GPE_HIP(c, hipMemcpyAsync(out->degree, ws.degree, n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    GPE_HIP(c, hipStreamSynchronize(c->stream));
-    if (want_pairs && total > 0xFFFFFFFFull) {                    // the one error that leaves count (and degree) set
-        out->count = total;
-        return fail(c, GPE_ERR_UNSUPPORTED, std::string(who) + ": more than 2^32 - 1 contacts cannot be listed");
-    }
-    const uint64_t m = std::min<uint64_t>(total, out->capacity);
-    if (m > 0 && want_pairs) {
-        // staging, 256-byte aligned parts, only the requested arrays: index_a | index_b | uid_a | uid_b | overlap
-        auto part = [m](bool on) { return on ? (m * 4 + 255) / 256 * 256 : 0; };
-        const uint64_t o_b = part(out->index_a), o_ua = o_b + part(out->index_b), o_ub = o_ua + part(out->uid_a),
-                       o_ov = o_ub + part(out->uid_b), bytes = o_ov + part(out->overlap);
-        GPE_TRY(contacts_reserve(c, bytes));
-        uint8_t *st = ws.stage;
-        uint32_t *d_a = out->index_a ? reinterpret_cast<uint32_t *>(st) : nullptr;
-        uint32_t *d_b = out->index_b ? reinterpret_cast<uint32_t *>(st + o_b) : nullptr;
-        uint32_t *d_ua = out->uid_a ? reinterpret_cast<uint32_t *>(st + o_ua) : nullptr;
-        uint32_t *d_ub = out->uid_b ? reinterpret_cast<uint32_t *>(st + o_ub) : nullptr;
-        float *d_ov = out->overlap ? reinterpret_cast<float *>(st + o_ov) : nullptr;
-        {
-            Scope k(c, "contacts/scan");
-            GPE_TRY(inclusive_scan(c, ws.upper, n));
-        }
-        {
-            Scope k(c, "contacts/gather");
-            GPE_TRY(launch_contacts_gather(c, ws.keys, ws.rec, ws.upper, (uint32_t)m, d_a, d_b, d_ua, d_ub, d_ov));
-        }
-        if (d_a) GPE_HIP(c, hipMemcpyAsync(out->index_a, d_a, m * 4, hipMemcpyDeviceToHost, c->stream));
-        if (d_b) GPE_HIP(c, hipMemcpyAsync(out->index_b, d_b, m * 4, hipMemcpyDeviceToHost, c->stream));
-        if (d_ua) GPE_HIP(c, hipMemcpyAsync(out->uid_a, d_ua, m * 4, hipMemcpyDeviceToHost, c->stream));
-        if (d_ub) GPE_HIP(c, hipMemcpyAsync(out->uid_b, d_ub, m * 4, hipMemcpyDeviceToHost, c->stream));
-        if (d_ov) GPE_HIP(c, hipMemcpyAsync(out->overlap, d_ov, m * 4, hipMemcpyDeviceToHost, c->stream));
-        GPE_HIP(c, hipStreamSynchronize(c->stream));
-    }
-    out->count = total;
-    return GPE_OK;
-}
-
-// ---- contact clusters (k_clusters.hip) ---------------------------------------------------------------------
-static gpe_status clusters_alloc(gpe_ctx *c, void **p, uint64_t payload, const char *tag)
-{
-    const hipError_t e = gpe_dev_reserve(c, p, payload, 0, tag);
-    if (e == hipErrorOutOfMemory) return fail(c, GPE_ERR_OOM, "gpe_query_clusters: out of device memory");
-    if (e != hipSuccess) return fail(c, GPE_ERR_HIP, std::string("gpe_query_clusters: ") + hipGetErrorName(e));
-    return GPE_OK;
-}
-
-static gpe_status clusters_reserve(gpe_ctx *c)
-{
-    ClustersWorkspace &ws = c->clusters_ws;
-    const uint64_t n = c->n, tiles = contacts_tiles(n);
-    if (ws.cap < n) {
-        dev_free(c, ws.parent); dev_free(c, ws.label); dev_free(c, ws.root_size); dev_free(c, ws.size);
-        ws.cap = 0;
-        // parent: n words, read and written by index below n (the indices of the sorted records).  no slack
-        GPE_TRY(clusters_alloc(c, (void **)&ws.parent, n * sizeof(uint32_t), "clusters.parent"));
-        // label: n words, written by index below n; the member kernels read it by index below n (guarded tile loads).  no slack
-        GPE_TRY(clusters_alloc(c, (void **)&ws.label, n * sizeof(uint32_t), "clusters.label"));
-        // root_size: n words, indexed by a label, which is an index below n.  no slack
-        GPE_TRY(clusters_alloc(c, (void **)&ws.root_size, n * sizeof(uint32_t), "clusters.root_size"));
-        // size: n words, written by index below n.  no slack (nothing here is scanned; the members' scan runs on
-        // query.tile_count)
-        GPE_TRY(clusters_alloc(c, (void **)&ws.size, n * sizeof(uint32_t), "clusters.size"));
-        ws.cap = n;
-    }
-    if (ws.tiles_cap < tiles) {
-        dev_free(c, ws.tile_word);
-        ws.tiles_cap = 0;
-        // tile_word: one 64-bit word per workgroup of the flatten / sizes kernels.  no slack
-        GPE_TRY(clusters_alloc(c, (void **)&ws.tile_word, tiles * sizeof(unsigned long long), "clusters.tile_word"));
-        ws.tiles_cap = tiles;
-    }
-    // words: two 64-bit words.  no slack
-    if (!ws.words) GPE_TRY(clusters_alloc(c, (void **)&ws.words, 2 * sizeof(unsigned long long), "clusters.words"));
-    return GPE_OK;
-}
-
-// The checks the two cluster queries share once the result struct is usable and its count is 0: the refusals of
-// gpe_query_contacts.  *cell_size = the contact query's own cell size.
-static gpe_status clusters_begin(gpe_ctx *c, const char *who, float *cell_size)
-{
-    if (is_sharded(c))
-        return fail(c, GPE_ERR_UNSUPPORTED, std::string(who) + ": not supported on a sharded context (gpe_shard_*, "
-                                                                "order keys or an active cell box)");
-    if (c->n > 0xFFFFFFFFull) return fail(c, GPE_ERR_UNSUPPORTED, std::string(who) + ": more than 2^32 - 1 particles");
-    *cell_size = gpe_compute_cell_size(fabsf(c->max_radius));
-    if (c->n > 1 && !isfinite(*cell_size))
-        return fail(c, GPE_ERR_UNSUPPORTED, std::string(who) + ": the largest radius is not finite");
-    return GPE_OK;
-}
-
-// The labels of all particles into clusters_ws.label and the number of clusters into *count (read back; the stream is
-// idle afterwards).  n > 1 and a finite non-zero cell size.  Call inside the "Query clusters" scope.
-static gpe_status clusters_label(gpe_ctx *c, float cell_size, unsigned long long *count)
-{
-    GPE_TRY(clusters_reserve(c));
-    GPE_TRY(contacts_bin(c, cell_size));
-    ClustersWorkspace &ws = c->clusters_ws;
-    {
-        Scope k(c, "clusters/hook");
-        GPE_TRY(launch_clusters_hook(c, c->contacts_ws.keys, c->contacts_ws.rec, ws.parent));
-    }
-    {
-        Scope k(c, "clusters/flatten");
-        GPE_TRY(launch_clusters_flatten(c, ws.parent, ws.label, ws.tile_word, ws.words));
-    }
-    GPE_HIP(c, hipMemcpyAsync(count, ws.words, sizeof(*count), hipMemcpyDeviceToHost, c->stream));
-    GPE_HIP(c, hipStreamSynchronize(c->stream));
-    return GPE_OK;
-}
-
-gpe_status gpe_query_clusters(gpe_ctx *c, gpe_cluster_result *out)
-{
-    const char *who = "gpe_query_clusters";
-    if (!c) return GPE_ERR_INVALID_ARG;
-    if (!out) return fail(c, GPE_ERR_INVALID_ARG, std::string(who) + ": NULL result");
-    if (out->struct_size < sizeof(gpe_cluster_result)) {
-        if (out->struct_size >= offsetof(gpe_cluster_result, count) + sizeof(out->count)) out->count = 0;   // it has one
-        return fail(c, GPE_ERR_INVALID_ARG, std::string(who) + ": struct_size is smaller than gpe_cluster_result");
-    }
-    out->count = 0;
-    out->largest_size = out->largest_label = 0;
-    float cell_size = 0.0f;
-    GPE_TRY(clusters_begin(c, who, &cell_size));
-    if (out->label_uid && !c->uid.on)
-        return fail(c, GPE_ERR_STATE, std::string(who) + ": label_uid requested while uids are off");
-    const uint64_t n = c->n;
-    if (n == 0 || !c->pos) return GPE_OK;
-    GPE_HIP(c, hipSetDevice(c->device));
-    GPE_HIP(c, hipStreamSynchronize(c->stream));
-    if (n == 1 || cell_size == 0.0f) {                             // one particle, or every radius 0: nothing touches
-        if (out->label_uid) {                                      // label[i] = i: the particles' own uids
-            GPE_HIP(c, hipMemcpyAsync(out->label_uid, c->uid.uids, n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-            GPE_HIP(c, hipStreamSynchronize(c->stream));
-        }
-        if (out->label) for (uint64_t i = 0; i < n; ++i) out->label[i] = (uint32_t)i;
-        if (out->size) std::fill(out->size, out->size + n, 1u);
-        out->count = n;
-        out->largest_size = 1;
-        out->largest_label = 0;
-        return GPE_OK;
-    }
-    ClustersWorkspace &ws = c->clusters_ws;
-    unsigned long long count = 0, largest = 0;
-    Scope s(c, "Query clusters");
-    GPE_TRY(clusters_label(c, cell_size, &count));
-    {
-        Scope k(c, "clusters/sizes");
-        // parent is free after the flatten: it takes the uid of every particle's label
-        GPE_TRY(launch_clusters_sizes(c, ws.label, ws.root_size, ws.size, out->label_uid ? ws.parent : nullptr, ws.tile_word,
-                                      ws.words + 1));
-    }
-    GPE_HIP(c, hipMemcpyAsync(&largest, ws.words + 1, sizeof(largest), hipMemcpyDeviceToHost, c->stream));
-    if (out->label) GPE_HIP(c, hipMemcpyAsync(out->label, ws.label, n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    if (out->size) GPE_HIP(c, hipMemcpyAsync(out->size, ws.size, n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    if (out->label_uid)
-        GPE_HIP(c, hipMemcpyAsync(out->label_uid, ws.parent, n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    GPE_HIP(c, hipStreamSynchronize(c->stream));
-    out->count = count;
-    out->largest_size = (uint32_t)(largest >> 32);
-    out->largest_label = 0xFFFFFFFFu - (uint32_t)(largest & 0xFFFFFFFFull);
-    return GPE_OK;
-}
-
-gpe_status gpe_query_cluster_of(gpe_ctx *c, uint32_t key_kind, uint32_t key, gpe_query_result *out)
-{
-    const char *who = "gpe_query_cluster_of";
-    bool go = false;
-    GPE_TRY(query_begin(c, out, who, &go));
-    if (key_kind != GPE_CLUSTER_BY_INDEX && key_kind != GPE_CLUSTER_BY_UID)
-        return fail(c, GPE_ERR_INVALID_ARG, std::string(who) + ": unknown key_kind");
-    if (key_kind == GPE_CLUSTER_BY_UID && !c->uid.on)
-        return fail(c, GPE_ERR_STATE, std::string(who) + ": GPE_CLUSTER_BY_UID while uids are off");
-    if (key_kind == GPE_CLUSTER_BY_INDEX && key >= c->n)
-        return fail(c, GPE_ERR_INVALID_ARG, std::string(who) + ": index >= gpe_len");
-    float cell_size = 0.0f;
-    GPE_TRY(clusters_begin(c, who, &cell_size));
-    if (!go) return GPE_OK;                                        // no particles: every uid is absent
-    const uint64_t n = c->n;
-    GPE_HIP(c, hipSetDevice(c->device));
-    GPE_HIP(c, hipStreamSynchronize(c->stream));
-    uint32_t seed = key;
-    if (key_kind == GPE_CLUSTER_BY_UID) {                          // through the uid -> index map, as gpe_find_uids
-        GPE_TRY(uid_map_ready(c));
-        GPE_TRY(uid_query_reserve(c, 2 * sizeof(uint32_t)));
-        uint32_t *d_index = reinterpret_cast<uint32_t *>(c->uid.query), *d_query = d_index + 1;
-        GPE_HIP(c, hipMemcpyAsync(d_query, &key, sizeof(key), hipMemcpyHostToDevice, c->stream));
-        {
-            Scope k(c, "uids/find");
-            GPE_TRY(launch_uid_find(c, c->uid.map_keys, c->uid.map_vals, n, d_query, 1, d_index, nullptr, nullptr, nullptr));
-        }
-        GPE_HIP(c, hipMemcpyAsync(&seed, d_index, sizeof(seed), hipMemcpyDeviceToHost, c->stream));
-        GPE_HIP(c, hipStreamSynchronize(c->stream));
-        if (seed == GPE_UID_ABSENT) return GPE_OK;                 // an absent uid: count 0
-        if (seed >= n) return fail(c, GPE_ERR_STATE, std::string(who) + ": bad index");
-    }
-    if (n == 1 || cell_size == 0.0f) {                             // nothing touches: the seed alone, from the particle buffers
-        const uint32_t i = seed;
-        if (out->capacity >= 1) {
-            if (out->uid) GPE_HIP(c, hipMemcpyAsync(out->uid, c->uid.uids + i, 4, hipMemcpyDeviceToHost, c->stream));
-            if (out->pos_xy) GPE_HIP(c, hipMemcpyAsync(out->pos_xy, c->pos + i, 8, hipMemcpyDeviceToHost, c->stream));
-            if (out->prev_xy) GPE_HIP(c, hipMemcpyAsync(out->prev_xy, c->prev + i, 8, hipMemcpyDeviceToHost, c->stream));
-            if (out->radius) GPE_HIP(c, hipMemcpyAsync(out->radius, c->radius + i, 4, hipMemcpyDeviceToHost, c->stream));
-            GPE_HIP(c, hipStreamSynchronize(c->stream));
-            if (out->index) out->index[0] = i;
-        }
-        out->count = 1;
-        return GPE_OK;
-    }
-    GPE_TRY(query_reserve(c, 0));
-    ClustersWorkspace &ws = c->clusters_ws;
-    const uint64_t tiles = query_tiles(n);
-    unsigned long long count = 0;
-    uint32_t want = 0, total = 0;
-    Scope s(c, "Query clusters");
-    GPE_TRY(clusters_label(c, cell_size, &count));
-    GPE_HIP(c, hipMemcpyAsync(&want, ws.label + seed, sizeof(want), hipMemcpyDeviceToHost, c->stream));
-    GPE_HIP(c, hipStreamSynchronize(c->stream));
-    {
-        Scope k(c, "clusters/gather");
-        GPE_TRY(launch_clusters_member_count(c, ws.label, want, c->query_ws.tile_count));
-        GPE_TRY(inclusive_scan(c, c->query_ws.tile_count, tiles));
-    }
-    GPE_HIP(c, hipMemcpyAsync(&total, c->query_ws.tile_count + (tiles - 1), sizeof(total), hipMemcpyDeviceToHost, c->stream));
-    GPE_HIP(c, hipStreamSynchronize(c->stream));
-    return query_deliver(c, out, total, "clusters/gather",
-                         [&](uint32_t m, uint32_t *d_index, uint32_t *d_uid, float2 *d_pos, float2 *d_prev, float *d_radius) {
-                             return launch_clusters_member_gather(c, ws.label, want, c->query_ws.tile_count, m, d_index,
-                                                                  d_uid, d_pos, d_prev, d_radius);
-                         });
-}
-
-// ---- ray casts (k_raycast.hip) ------------------------------------------------------------------------------
-static gpe_status ray_alloc(gpe_ctx *c, void **p, uint64_t payload, const char *tag)
-{
-    const hipError_t e = gpe_dev_reserve(c, p, payload, 0, tag);
-    if (e == hipErrorOutOfMemory) return fail(c, GPE_ERR_OOM, "gpe_cast_rays: out of device memory");
-    if (e != hipSuccess) return fail(c, GPE_ERR_HIP, std::string("gpe_cast_rays: ") + hipGetErrorName(e));
-    return GPE_OK;
-}
-
-// room for a batch of k rays; every array is read and written by index below k or kRayRowWords.  no slack
-static gpe_status ray_reserve(gpe_ctx *c, uint64_t k)
-{
-    RayWorkspace &ws = c->ray_ws;
-    if (!ws.row_start) GPE_TRY(ray_alloc(c, (void **)&ws.row_start, kRayRowWords * sizeof(uint32_t), "ray.row_start"));
-    if (ws.cap < k) {
-        dev_free(c, ws.from); dev_free(c, ws.to); dev_free(c, ws.index); dev_free(c, ws.uid); dev_free(c, ws.t);
-        dev_free(c, ws.pos); dev_free(c, ws.radius);
-        ws.cap = 0;
-        GPE_TRY(ray_alloc(c, (void **)&ws.from, k * sizeof(float2), "ray.from"));
-        GPE_TRY(ray_alloc(c, (void **)&ws.to, k * sizeof(float2), "ray.to"));
-        GPE_TRY(ray_alloc(c, (void **)&ws.index, k * sizeof(uint32_t), "ray.index"));
-        GPE_TRY(ray_alloc(c, (void **)&ws.uid, k * sizeof(uint32_t), "ray.uid"));
-        GPE_TRY(ray_alloc(c, (void **)&ws.t, k * sizeof(float), "ray.t"));
-        GPE_TRY(ray_alloc(c, (void **)&ws.pos, k * sizeof(float2), "ray.pos"));
-        GPE_TRY(ray_alloc(c, (void **)&ws.radius, k * sizeof(float), "ray.radius"));
-        ws.cap = k;
-    }
-    return GPE_OK;
-}
-
-// every ray misses: the host fills the requested outputs
-static void ray_fill_misses(gpe_ray_cast *r)
-{
-    const uint64_t k = r->k;
-    const float nan = std::numeric_limits<float>::quiet_NaN();
-    if (r->index) std::fill(r->index, r->index + k, GPE_RAY_MISS);
-    if (r->uid) std::fill(r->uid, r->uid + k, GPE_UID_ABSENT);
-    if (r->t) std::fill(r->t, r->t + k, nan);
-    if (r->pos_xy) std::fill(r->pos_xy, r->pos_xy + 2 * k, nan);
-    if (r->radius) std::fill(r->radius, r->radius + k, nan);
-}
-
-gpe_status gpe_cast_rays(gpe_ctx *c, gpe_ray_cast *r)
-{
-    const char *who = "gpe_cast_rays";
-    if (!c) return GPE_ERR_INVALID_ARG;
-    if (!r) return fail(c, GPE_ERR_INVALID_ARG, std::string(who) + ": NULL cast");
-    if (r->struct_size < sizeof(gpe_ray_cast))             // hits is the last field: a smaller struct has none
-        return fail(c, GPE_ERR_INVALID_ARG, std::string(who) + ": struct_size is smaller than gpe_ray_cast");
-    r->hits = 0;
-    if (r->flags != 0) return fail(c, GPE_ERR_INVALID_ARG, std::string(who) + ": flags must be 0");
-    const uint64_t k = r->k;
-    if (k > 0 && (!r->from_xy || !r->to_xy)) return fail(c, GPE_ERR_INVALID_ARG, std::string(who) + ": NULL endpoints");
-    if (is_sharded(c))
-        return fail(c, GPE_ERR_UNSUPPORTED, std::string(who) + ": not supported on a sharded context (gpe_shard_*, "
-                                                                "order keys or an active cell box)");
-    if (r->uid && !c->uid.on) return fail(c, GPE_ERR_STATE, std::string(who) + ": uid requested while uids are off");
-    if (c->n > 0xFFFFFFFFull) return fail(c, GPE_ERR_UNSUPPORTED, std::string(who) + ": more than 2^32 - 1 particles");
-    if (k == 0) return GPE_OK;
-    const bool any = c->n > 0 && c->pos;
-    // the contact query's own cell size: a touched centre lies within max|r| = cell / 2.2 of its segment
-    const float cell_size = any ? gpe_compute_cell_size(fabsf(c->max_radius)) : 0.0f;
-    if (!isfinite(cell_size)) return fail(c, GPE_ERR_UNSUPPORTED, std::string(who) + ": the largest radius is not finite");
-    const float bound = cell_size > 0.0f ? 131072.0f * cell_size : std::numeric_limits<float>::infinity();
-    for (uint64_t i = 0; i < 2 * k; ++i) {
-        const float a = r->from_xy[i], b = r->to_xy[i];
-        if (!isfinite(a) || !isfinite(b) || !(fabsf(a) <= bound) || !(fabsf(b) <= bound))
-            return fail(c, GPE_ERR_INVALID_ARG, std::string(who) + ": an endpoint is not finite or lies more than 131072 "
-                                                                   "cells from the origin");
-    }
-    if (!any || !(cell_size > 0.0f)) {                          // no particles, or every radius 0: nothing can be hit
-        ray_fill_misses(r);
-        return GPE_OK;
-    }
-    GPE_HIP(c, hipSetDevice(c->device));
-    GPE_HIP(c, hipStreamSynchronize(c->stream));
-    const uint64_t batch = std::min<uint64_t>(k, kRayMaxBatch);
-    GPE_TRY(ray_reserve(c, batch));
-    RayWorkspace &ws = c->ray_ws;
-    Scope s(c, "Cast rays");
-    GPE_TRY(contacts_bin(c, cell_size));
-    {
-        Scope q(c, "rays/rows");
-        GPE_TRY(launch_ray_row_start(c, c->contacts_ws.keys, ws.row_start));
-    }
-    std::vector<uint32_t> index(batch);
-    uint64_t hits = 0;
-    for (uint64_t base = 0; base < k; base += batch) {
-        const uint64_t m = std::min<uint64_t>(batch, k - base);
-        GPE_HIP(c, hipMemcpyAsync(ws.from, r->from_xy + 2 * base, m * sizeof(float2), hipMemcpyHostToDevice, c->stream));
-        GPE_HIP(c, hipMemcpyAsync(ws.to, r->to_xy + 2 * base, m * sizeof(float2), hipMemcpyHostToDevice, c->stream));
-        {
-            Scope q(c, "rays/cast");
-            GPE_TRY(launch_ray_cast(c, ws.from, ws.to, (uint32_t)m, cell_size, c->contacts_ws.keys, c->contacts_ws.rec,
-                                    ws.row_start, ws.index, r->uid ? ws.uid : nullptr, r->t ? ws.t : nullptr,
-                                    r->pos_xy ? ws.pos : nullptr, r->radius ? ws.radius : nullptr));
-        }
-        GPE_HIP(c, hipMemcpyAsync(index.data(), ws.index, m * 4, hipMemcpyDeviceToHost, c->stream));
-        if (r->uid) GPE_HIP(c, hipMemcpyAsync(r->uid + base, ws.uid, m * 4, hipMemcpyDeviceToHost, c->stream));
-        if (r->t) GPE_HIP(c, hipMemcpyAsync(r->t + base, ws.t, m * 4, hipMemcpyDeviceToHost, c->stream));
-        if (r->pos_xy) GPE_HIP(c, hipMemcpyAsync(r->pos_xy + 2 * base, ws.pos, m * 8, hipMemcpyDeviceToHost, c->stream));
-        if (r->radius) GPE_HIP(c, hipMemcpyAsync(r->radius + base, ws.radius, m * 4, hipMemcpyDeviceToHost, c->stream));
-        GPE_HIP(c, hipStreamSynchronize(c->stream));
-        for (uint64_t i = 0; i < m; ++i) hits += index[i] != GPE_RAY_MISS;
-        if (r->index) std::copy(index.begin(), index.begin() + m, r->index + base);
-    }
-    r->hits = hits;
-    return GPE_OK;
-}
-
-// ---- nearest neighbours (k_nearest.hip) -------------------------------------------------------------------------
-static gpe_status nearest_alloc(gpe_ctx *c, void **p, uint64_t payload, const char *tag)
-{
-    const hipError_t e = gpe_dev_reserve(c, p, payload, 0, tag);
-    if (e == hipErrorOutOfMemory) return fail(c, GPE_ERR_OOM, "gpe_query_nearest: out of device memory");
-    if (e != hipSuccess) return fail(c, GPE_ERR_HIP, std::string("gpe_query_nearest: ") + hipGetErrorName(e));
-    return GPE_OK;
-}
-
-// room for a batch of k points of m slots each; every array is read and written by index below k, k * m or
-// kRayRowWords.  no slack
-static gpe_status nearest_reserve(gpe_ctx *c, uint64_t k, uint64_t m)
-{
-    NearestWorkspace &ws = c->nearest_ws;
-    if (!ws.row_start)
-        GPE_TRY(nearest_alloc(c, (void **)&ws.row_start, kRayRowWords * sizeof(uint32_t), "nearest.row_start"));
-    if (ws.cap < k) {
-        dev_free(c, ws.points); dev_free(c, ws.count);
-        ws.cap = 0;
-        GPE_TRY(nearest_alloc(c, (void **)&ws.points, k * sizeof(float2), "nearest.points"));
-        GPE_TRY(nearest_alloc(c, (void **)&ws.count, k * sizeof(uint32_t), "nearest.count"));
-        ws.cap = k;
-    }
-    const uint64_t slots = k * m;
-    if (ws.slots_cap < slots) {
-        dev_free(c, ws.index); dev_free(c, ws.uid); dev_free(c, ws.dist2); dev_free(c, ws.pos); dev_free(c, ws.radius);
-        ws.slots_cap = 0;
-        GPE_TRY(nearest_alloc(c, (void **)&ws.index, slots * sizeof(uint32_t), "nearest.index"));
-        GPE_TRY(nearest_alloc(c, (void **)&ws.uid, slots * sizeof(uint32_t), "nearest.uid"));
-        GPE_TRY(nearest_alloc(c, (void **)&ws.dist2, slots * sizeof(float), "nearest.dist2"));
-        GPE_TRY(nearest_alloc(c, (void **)&ws.pos, slots * sizeof(float2), "nearest.pos"));
-        GPE_TRY(nearest_alloc(c, (void **)&ws.radius, slots * sizeof(float), "nearest.radius"));
-        ws.slots_cap = slots;
-    }
-    return GPE_OK;
-}
-
-// no point has a neighbour: the host fills the requested outputs
-static void nearest_fill_none(gpe_nearest_query *q)
-{
-    const uint64_t k = q->k, slots = q->k * q->m;
-    const float nan = std::numeric_limits<float>::quiet_NaN();
-    if (q->count) std::fill(q->count, q->count + k, 0u);
-    if (q->index) std::fill(q->index, q->index + slots, GPE_NEAREST_NONE);
-    if (q->uid) std::fill(q->uid, q->uid + slots, GPE_UID_ABSENT);
-    if (q->dist2) std::fill(q->dist2, q->dist2 + slots, nan);
-    if (q->pos_xy) std::fill(q->pos_xy, q->pos_xy + 2 * slots, nan);
-    if (q->radius) std::fill(q->radius, q->radius + slots, nan);
-}
-
-gpe_status gpe_query_nearest(gpe_ctx *c, gpe_nearest_query *q)
-{
-    const char *who = "gpe_query_nearest";
-    if (!c) return GPE_ERR_INVALID_ARG;
-    if (!q) return fail(c, GPE_ERR_INVALID_ARG, std::string(who) + ": NULL query");
-    if (q->struct_size < sizeof(gpe_nearest_query))        // found is the last field: a smaller struct has none
-        return fail(c, GPE_ERR_INVALID_ARG, std::string(who) + ": struct_size is smaller than gpe_nearest_query");
-    q->found = 0;
-    if (q->flags != 0) return fail(c, GPE_ERR_INVALID_ARG, std::string(who) + ": flags must be 0");
-    if (q->m == 0 || q->m > GPE_NEAREST_MAX_M) return fail(c, GPE_ERR_INVALID_ARG, std::string(who) + ": m must be 1 .. 64");
-    const float md = q->max_distance;
-    if (!(md >= 0.0f)) return fail(c, GPE_ERR_INVALID_ARG, std::string(who) + ": max_distance is NaN or negative");
-    const uint64_t k = q->k, m = q->m;
-    if (k > 0 && !q->point_xy) return fail(c, GPE_ERR_INVALID_ARG, std::string(who) + ": NULL points");
-    if (is_sharded(c))
-        return fail(c, GPE_ERR_UNSUPPORTED, std::string(who) + ": not supported on a sharded context (gpe_shard_*, "
-                                                                "order keys or an active cell box)");
-    if (q->uid && !c->uid.on) return fail(c, GPE_ERR_STATE, std::string(who) + ": uid requested while uids are off");
-    if (c->n > 0xFFFFFFFFull) return fail(c, GPE_ERR_UNSUPPORTED, std::string(who) + ": more than 2^32 - 1 particles");
-    if (k == 0) return GPE_OK;
-    const bool any = c->n > 0 && c->pos;
-    // the contact query's own cell while it is usable; the result never depends on it, only the points' bound does
-    float cell_size = 0.0f;
-    if (any) {
-        cell_size = gpe_compute_cell_size(fabsf(c->max_radius));
-        if (!(isfinite(cell_size) && cell_size > 0.0f)) cell_size = fmaxf(c->cfg.world_width, c->cfg.world_height) / 1024.0f;
-        if (!(isfinite(cell_size) && cell_size > 0.0f))
-            return fail(c, GPE_ERR_UNSUPPORTED, std::string(who) + ": neither the largest radius nor the world gives a "
-                                                                   "finite positive cell size");
-    }
-    const float bound = any ? 131072.0f * cell_size : std::numeric_limits<float>::infinity();
-    for (uint64_t i = 0; i < 2 * k; ++i) {
-        const float a = q->point_xy[i];
-        if (!isfinite(a) || !(fabsf(a) <= bound))
-            return fail(c, GPE_ERR_INVALID_ARG, std::string(who) + ": a point is not finite or lies more than 131072 "
-                                                                   "cells from the origin");
-    }
-    if (!any) {                                                 // no particles: nothing to find
-        nearest_fill_none(q);
-        return GPE_OK;
-    }
-    GPE_HIP(c, hipSetDevice(c->device));
-    GPE_HIP(c, hipStreamSynchronize(c->stream));
-    const uint64_t batch = std::min<uint64_t>(k, kNearestMaxSlots / m);
-    GPE_TRY(nearest_reserve(c, batch, m));
-    NearestWorkspace &ws = c->nearest_ws;
-    Scope s(c, "Nearest");
-    GPE_TRY(contacts_bin(c, cell_size));
-    {
-        Scope r(c, "nearest/rows");
-        GPE_TRY(launch_ray_row_start(c, c->contacts_ws.keys, ws.row_start));
-    }
-    std::vector<uint32_t> count(batch);
-    uint64_t found = 0;
-    for (uint64_t base = 0; base < k; base += batch) {
-        const uint64_t b = std::min<uint64_t>(batch, k - base), slots = b * m;
-        GPE_HIP(c, hipMemcpyAsync(ws.points, q->point_xy + 2 * base, b * sizeof(float2), hipMemcpyHostToDevice, c->stream));
-        {
-            Scope r(c, "nearest/search");
-            GPE_TRY(launch_nearest(c, ws.points, (uint32_t)b, (uint32_t)m, md, cell_size, c->contacts_ws.keys,
-                                   c->contacts_ws.rec, ws.row_start, ws.count, q->index ? ws.index : nullptr,
-                                   q->uid ? ws.uid : nullptr, q->dist2 ? ws.dist2 : nullptr, q->pos_xy ? ws.pos : nullptr,
-                                   q->radius ? ws.radius : nullptr));
-        }
-        const uint64_t at = base * m;
-        GPE_HIP(c, hipMemcpyAsync(count.data(), ws.count, b * 4, hipMemcpyDeviceToHost, c->stream));
-        if (q->index) GPE_HIP(c, hipMemcpyAsync(q->index + at, ws.index, slots * 4, hipMemcpyDeviceToHost, c->stream));
-        if (q->uid) GPE_HIP(c, hipMemcpyAsync(q->uid + at, ws.uid, slots * 4, hipMemcpyDeviceToHost, c->stream));
-        if (q->dist2) GPE_HIP(c, hipMemcpyAsync(q->dist2 + at, ws.dist2, slots * 4, hipMemcpyDeviceToHost, c->stream));
-        if (q->pos_xy) GPE_HIP(c, hipMemcpyAsync(q->pos_xy + 2 * at, ws.pos, slots * 8, hipMemcpyDeviceToHost, c->stream));
-        if (q->radius) GPE_HIP(c, hipMemcpyAsync(q->radius + at, ws.radius, slots * 4, hipMemcpyDeviceToHost, c->stream));
-        GPE_HIP(c, hipStreamSynchronize(c->stream));
-        for (uint64_t i = 0; i < b; ++i) found += count[i];
-        if (q->count) std::copy(count.begin(), count.begin() + b, q->count + base);
-    }
-    q->found = found;
-    return GPE_OK;
-}
-
-// ---- overlap-checked adds (k_spawn.hip) --------------------------------------------------------------------
-static gpe_status spawn_alloc(gpe_ctx *c, void **p, uint64_t payload, uint64_t slack, const char *tag)
-{
-    const hipError_t e = gpe_dev_reserve(c, p, payload, slack, tag);
-    if (e == hipErrorOutOfMemory) return fail(c, GPE_ERR_OOM, "gpe_add_particles_free: out of device memory");
-    if (e != hipSuccess) return fail(c, GPE_ERR_HIP, std::string("gpe_add_particles_free: ") + hipGetErrorName(e));
-    return GPE_OK;
-}
-
-// Scratch of the call's own: nothing of the contact or cluster workspaces is used, so a later query finds its buffers
-// as it left them.
-static gpe_status spawn_reserve(gpe_ctx *c, uint64_t k)
-{
-    SpawnWorkspace &ws = c->spawn_ws;
-    if (ws.cap < k) {
-        dev_free(c, ws.pos); dev_free(c, ws.radius); dev_free(c, ws.keys); dev_free(c, ws.vals); dev_free(c, ws.rec);
-        dev_free(c, ws.blocked); dev_free(c, ws.state); dev_free(c, ws.rank); dev_free(c, ws.verdict);
-        ws.cap = 0;
-        // pos / radius: the k uploaded candidates, read by index below k.  no slack
-        GPE_TRY(spawn_alloc(c, (void **)&ws.pos, k * sizeof(float2), 0, "spawn.pos"));
-        GPE_TRY(spawn_alloc(c, (void **)&ws.radius, k * sizeof(float), 0, "spawn.radius"));
-        // keys / vals: k words each.  slack: the 16 words sort_pairs' tile loads may read behind the k pairs
-        GPE_TRY(spawn_alloc(c, (void **)&ws.keys, k * sizeof(uint32_t), 16 * sizeof(uint32_t), "spawn.keys"));
-        GPE_TRY(spawn_alloc(c, (void **)&ws.vals, k * sizeof(uint32_t), 16 * sizeof(uint32_t), "spawn.vals"));
-        // rec: k 16-byte records, read one at a time below k.  no slack
-        GPE_TRY(spawn_alloc(c, (void **)&ws.rec, k * sizeof(uint4), 0, "spawn.rec"));
-        // blocked / state: k words each, written and read by index below k.  no slack
-        GPE_TRY(spawn_alloc(c, (void **)&ws.blocked, k * sizeof(uint32_t), 0, "spawn.blocked"));
-        GPE_TRY(spawn_alloc(c, (void **)&ws.state, k * sizeof(uint32_t), 0, "spawn.state"));
-        // rank: k words, scanned in place.  slack: the 16 words the scan's tile loads may read behind them
-        GPE_TRY(spawn_alloc(c, (void **)&ws.rank, k * sizeof(uint32_t), 16 * sizeof(uint32_t), "spawn.rank"));
-        // verdict: k bytes, written and copied out below k.  no slack
-        GPE_TRY(spawn_alloc(c, (void **)&ws.verdict, k, 0, "spawn.verdict"));
-        ws.cap = k;
-    }
-    // ctl: kSpawnCtlWords words.  no slack
-    if (!ws.ctl) GPE_TRY(spawn_alloc(c, (void **)&ws.ctl, kSpawnCtlWords * sizeof(uint32_t), 0, "spawn.ctl"));
-    GPE_TRY(sort_reserve(c, k));
-    return scan_reserve(c, k);
-}
-
-// The separation rounds: batches of kSpawnRoundsPerLook launches, then one look at the batch's undecided counters.
-static gpe_status spawn_separate(gpe_ctx *c, uint32_t k, float cell_size)
-{
-    const SpawnWorkspace &ws = c->spawn_ws;
-    uint32_t *left = ws.ctl + kSpawnCtlRounds, h_left[kSpawnRoundsPerLook];
-    for (uint64_t rounds = 0;; rounds += kSpawnRoundsPerLook) {
-        // (every round settles one more workgroup block at least, and the lowest undecided index: k rounds always suffice)
-        if (rounds > (uint64_t)k + kSpawnRoundsPerLook) return fail(c, GPE_ERR_HIP, "gpe_add_particles_free: the separation did not settle");
-        GPE_HIP(c, hipMemsetAsync(left, 0, sizeof(h_left), c->stream));
-        for (int r = 0; r < kSpawnRoundsPerLook; ++r) {
-            Scope s(c, "spawn/round");
-            GPE_TRY(launch_spawn_round(c, ws, k, cell_size, left + r));
-        }
-        GPE_HIP(c, hipMemcpyAsync(h_left, left, sizeof(h_left), hipMemcpyDeviceToHost, c->stream));
-        GPE_HIP(c, hipStreamSynchronize(c->stream));
-        if (h_left[kSpawnRoundsPerLook - 1] == 0) return GPE_OK;
-    }
-}
-
-gpe_status gpe_add_particles_free(gpe_ctx *c, gpe_particle_spawn *sp)
-{
-    const char *who = "gpe_add_particles_free";
-    if (!c) return GPE_ERR_INVALID_ARG;
-    if (!sp) return fail(c, GPE_ERR_INVALID_ARG, std::string(who) + ": NULL spawn");
-    if (sp->struct_size < sizeof(gpe_particle_spawn))                  // (`added` is the last field: such a struct has none)
-        return fail(c, GPE_ERR_INVALID_ARG, std::string(who) + ": struct_size is smaller than gpe_particle_spawn");
-    sp->added = 0;
-    const uint32_t known = GPE_SPAWN_SEPARATE | GPE_SPAWN_INSIDE_WORLD | GPE_SPAWN_DRY_RUN;
-    if (sp->flags & ~known) return fail(c, GPE_ERR_INVALID_ARG, std::string(who) + ": unknown flag bits");
-    GPE_TRY(need_particles(c));
-    if (is_sharded(c))
-        return fail(c, GPE_ERR_UNSUPPORTED, std::string(who) + ": not supported on a sharded context (gpe_shard_*, "
-                                                                "order keys or an active cell box)");
-    const uint64_t k = sp->k;
-    if (k == 0) return GPE_OK;
-    if (!sp->pos_xy || !sp->radius) return fail(c, GPE_ERR_INVALID_ARG, std::string(who) + ": NULL array");
-    if (k > (1ull << 30) - 1 || c->n + k > (1ull << 30) - 1)
-        return fail(c, GPE_ERR_UNSUPPORTED, std::string(who) + ": 4 (gpe_len + k) must fit in u32");
-    // the search's own cell size: a contact implies a centre distance below 2 R, less than one cell of 2.2 R
-    float big = fabsf(c->max_radius);
-    bool finite = isfinite(big);
-    for (uint64_t i = 0; i < k; ++i) {
-        const float a = fabsf(sp->radius[i]);
-        finite = finite && isfinite(a);
-        big = a > big ? a : big;
-    }
-    const float cell_size = gpe_compute_cell_size(big);
-    if (!finite || !isfinite(cell_size))
-        return fail(c, GPE_ERR_UNSUPPORTED, std::string(who) + ": the largest radius is not finite");
-    const bool search = big > 0.0f;                                // every radius 0: nothing touches
-    const bool separate = (sp->flags & GPE_SPAWN_SEPARATE) != 0 && search;
-    const uint32_t k32 = (uint32_t)k;
-    GPE_HIP(c, hipSetDevice(c->device));
-    GPE_HIP(c, hipStreamSynchronize(c->stream));
-    std::vector<uint8_t> state;                                    // the verdicts: the user's array is written at the end only
-    try {
-        state.resize(k);
-    } catch (const std::bad_alloc &) {
-        return fail(c, GPE_ERR_OOM, std::string(who) + ": out of host memory for the verdicts");
-    }
-    {
-        Scope s(c, "Spawn check");
-        GPE_TRY(spawn_reserve(c, k));
-        const SpawnWorkspace &ws = c->spawn_ws;
-        GPE_HIP(c, hipMemcpyAsync(ws.pos, sp->pos_xy, k * sizeof(float2), hipMemcpyHostToDevice, c->stream));
-        GPE_HIP(c, hipMemcpyAsync(ws.radius, sp->radius, k * sizeof(float), hipMemcpyHostToDevice, c->stream));
-        {
-            Scope b(c, "spawn/bin");
-            GPE_TRY(launch_spawn_keys(c, ws, k32, cell_size, (sp->flags & GPE_SPAWN_INSIDE_WORLD) != 0));
-            if (search) {
-                GPE_TRY(sort_pairs(c, ws.keys, ws.vals, k));
-                GPE_TRY(launch_contacts_records_of(c, ws.pos, ws.radius, ws.vals, k, ws.rec));
-            }
-        }
-        {
-            Scope p(c, "spawn/pass");
-            GPE_TRY(launch_spawn_pass(c, ws, k32, cell_size, search));
-        }
-        GPE_TRY(launch_spawn_resolve(c, ws, k32, separate));
-        if (separate) {
-            Scope r(c, "spawn/separate");
-            GPE_TRY(spawn_separate(c, k32, cell_size));
-        }
-        GPE_TRY(launch_spawn_flags(c, ws, k32));
-        GPE_HIP(c, hipMemcpyAsync(state.data(), ws.verdict, k, hipMemcpyDeviceToHost, c->stream));
-        GPE_HIP(c, hipStreamSynchronize(c->stream));
-    }
-    uint64_t added = 0;
-    for (uint64_t i = 0; i < k; ++i) added += state[i] == GPE_SPAWN_ADDED ? 1u : 0u;
-    const bool append = added > 0 && !(sp->flags & GPE_SPAWN_DRY_RUN);
-    if (append) {
-        const uint64_t old_n = c->n, new_n = c->n + added;
-        if (c->uid.on && c->uid.next + added > kUidLimit)
-            return fail(c, GPE_ERR_STATE, std::string(who) + ": the new particles' uids would pass 2^32 - 1");
-        if (new_n > c->cap) GPE_TRY(grow_particle_buffers(c, std::max<uint64_t>(new_n, c->cap * 2)));
-        Scope s(c, "spawn/append");
-        const SpawnWorkspace &ws = c->spawn_ws;
-        GPE_TRY(inclusive_scan(c, ws.rank, k));                    // (the flags: launch_spawn_flags above)
-        GPE_TRY(launch_spawn_scatter(c, ws, k32, old_n));
-        c->n = new_n;
-        c->n_owned = new_n;
-        GPE_TRY(init_index_buffers(c, old_n, new_n));
-        if (c->uid.on) {                                   // next .. next + added - 1, in input order
-            GPE_TRY(launch_uid_iota(c, c->uid.uids, old_n, new_n, (uint32_t)c->uid.next));
-            c->uid.next += added;
-            c->uid.map_valid = false;
-            c->tracers.stale = true;
-        }
-        // as gpe_add_particles of the added candidates: max_radius = max(max_radius, r), in input order
-        for (uint64_t i = 0; i < k; ++i)
-            if (state[i] == GPE_SPAWN_ADDED) c->max_radius = fmaxf(c->max_radius, sp->radius[i]);
-        c->grid_max_radius = c->max_radius;
-        refresh_cell_size(c);
-        GPE_HIP(c, hipStreamSynchronize(c->stream));
-    }
-    if (sp->verdict) std::copy(state.begin(), state.end(), sp->verdict);
-    sp->added = added;
-    return append ? reconfigure(c) : GPE_OK;
-}
-
-// ---- editing particles in place (k_edit.hip) ---------------------------------------------------------------
-// staging rows, 256-byte aligned parts, only the requested fields: pos | prev | radius
-struct EditRows {
-    uint64_t o_prev = 0, o_radius = 0, bytes = 0;
-};
-static EditRows edit_rows(const gpe_particle_edit *e)
-{
-    const uint64_t k = e->k;
-    auto part = [k](bool on, uint64_t width) { return on ? (k * width + 255) / 256 * 256 : 0; };
-    EditRows r;
-    r.o_prev = part(e->pos_xy, 8);
-    r.o_radius = r.o_prev + part(e->prev_xy, 8);
-    r.bytes = r.o_radius + part(e->radius, 4);
-    return r;
-}
-
-static gpe_status do_edit(gpe_ctx *c, gpe_particle_edit *e)
-{
-    EditWorkspace &ws = c->edit_ws;
-    const uint64_t k = e->k, n = c->n;
-    const bool by_uid = e->key_kind == GPE_EDIT_BY_UID;
-    const EditRows rows = edit_rows(e);
-    if (by_uid) GPE_TRY(uid_map_ready(c));
-    // keys / slots (one capacity): sorted by sort_pairs, whose tile loads may read 16 words behind the k pairs
-    uint64_t cap_keys = ws.keys ? ws.keys_cap : 0, cap_slots = ws.slots ? ws.keys_cap : 0;
-    ws.keys_cap = 0;
-    GPE_TRY(edit_buffer(c, &ws.keys, &cap_keys, k, 16 * sizeof(uint32_t), "edit.keys"));
-    GPE_TRY(edit_buffer(c, &ws.slots, &cap_slots, k, 16 * sizeof(uint32_t), "edit.slots"));
-    ws.keys_cap = std::min(cap_keys, cap_slots);
-    GPE_TRY(edit_buffer(c, &ws.fields, &ws.fields_cap, rows.bytes, 0, "edit.fields"));
-    GPE_TRY(edit_buffer(c, &ws.flag, nullptr, 2, 0, "edit.flag"));
-    if (k > 1) GPE_TRY(sort_reserve(c, k));
-    Scope s(c, "Edit particles");
-    uint32_t flag[2] = {0, 0};
-    {
-        Scope sk(c, "edit/check");
-        GPE_HIP(c, hipMemcpyAsync(ws.keys, e->keys, k * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-        GPE_HIP(c, hipMemsetAsync(ws.flag, 0, sizeof(flag), c->stream));
-        GPE_TRY(launch_edit_check(c, by_uid, ws.keys, ws.slots, k, ws.flag));
-        if (k > 1) {                                             // two keys naming one particle become neighbours
-            GPE_TRY(sort_pairs(c, ws.keys, ws.slots, k));
-            GPE_TRY(launch_edit_adjacent(c, ws.keys, k, ws.flag));
-        }
-    }
-    GPE_HIP(c, hipMemcpyAsync(flag, ws.flag, sizeof(flag), hipMemcpyDeviceToHost, c->stream));
-    GPE_HIP(c, hipStreamSynchronize(c->stream));
-    if (flag[0] & kEditBadIndex) return fail(c, GPE_ERR_INVALID_ARG, "gpe_edit_particles: an index is not below gpe_len");
-    if (flag[0] & kEditDuplicate) return fail(c, GPE_ERR_INVALID_ARG, "gpe_edit_particles: two keys name the same particle");
-    if (flag[1] == 0) return GPE_OK;                             // every uid absent: nothing to write
-    // from here on the particles change
-    uint8_t *st = ws.fields;
-    const float2 *d_pos = e->pos_xy ? reinterpret_cast<const float2 *>(st) : nullptr;
-    const float2 *d_prev = e->prev_xy ? reinterpret_cast<const float2 *>(st + rows.o_prev) : nullptr;
-    const float *d_radius = e->radius ? reinterpret_cast<const float *>(st + rows.o_radius) : nullptr;
-    {
-        Scope sk(c, "edit/apply");
-        if (d_pos) GPE_HIP(c, hipMemcpyAsync(st, e->pos_xy, k * 8, hipMemcpyHostToDevice, c->stream));
-        if (d_prev) GPE_HIP(c, hipMemcpyAsync(st + rows.o_prev, e->prev_xy, k * 8, hipMemcpyHostToDevice, c->stream));
-        if (d_radius) GPE_HIP(c, hipMemcpyAsync(st + rows.o_radius, e->radius, k * 4, hipMemcpyHostToDevice, c->stream));
-        GPE_TRY(launch_edit_apply(c, ws.keys, ws.slots, k, d_pos, d_prev, d_radius));
-    }
-    if (d_radius) {
-        const uint64_t tiles = query_tiles(n);
-        GPE_TRY(edit_buffer(c, &ws.tile_key, &ws.tiles_cap, tiles, 0, "edit.tile_key"));
-        GPE_TRY(edit_buffer(c, &ws.max_key, nullptr, 1, 0, "edit.max_key"));
-        unsigned long long key = 0;
-        {
-            Scope sk(c, "edit/max radius");
-            GPE_TRY(launch_edit_max_radius(c, ws.tile_key, ws.max_key));
-        }
-        GPE_HIP(c, hipMemcpyAsync(&key, ws.max_key, sizeof(key), hipMemcpyDeviceToHost, c->stream));
-        GPE_HIP(c, hipStreamSynchronize(c->stream));
-        const uint32_t winner = (uint32_t)(key & 0xFFFFFFFFull);   // index of the max |radius|, the last on ties
-        if (winner >= n) return fail(c, GPE_ERR_STATE, "gpe_edit_particles: bad max-radius index");
-        float max_r = 0.f;
-        GPE_HIP(c, hipMemcpyAsync(&max_r, c->radius + winner, sizeof(max_r), hipMemcpyDeviceToHost, c->stream));
-        GPE_HIP(c, hipStreamSynchronize(c->stream));
-        c->max_radius = max_r;                                   // sign kept
-        c->grid_max_radius = c->max_radius;
-        refresh_cell_size(c);
-    }
-    GPE_HIP(c, hipStreamSynchronize(c->stream));                 // the host arrays may be released on return
-    if (d_pos || d_radius) GPE_TRY(reconfigure_native(c));       // (prev alone is part of no kept structure)
-    e->edited = flag[1];
-    return GPE_OK;
-}
-
-gpe_status gpe_edit_particles(gpe_ctx *c, gpe_particle_edit *e)
-{
-    if (!c) return GPE_ERR_INVALID_ARG;
-    if (!e) return fail(c, GPE_ERR_INVALID_ARG, "gpe_edit_particles: NULL edit");
-    if (e->struct_size < sizeof(gpe_particle_edit))
-        return fail(c, GPE_ERR_INVALID_ARG, "gpe_edit_particles: struct_size is smaller than gpe_particle_edit");
-    e->edited = 0;
-    if (!e->keys) return fail(c, GPE_ERR_INVALID_ARG, "gpe_edit_particles: NULL keys");
-    if (e->key_kind != GPE_EDIT_BY_INDEX && e->key_kind != GPE_EDIT_BY_UID)
-        return fail(c, GPE_ERR_INVALID_ARG, "gpe_edit_particles: unknown key_kind");
-    if (!e->pos_xy && !e->prev_xy && !e->radius)
-        return fail(c, GPE_ERR_INVALID_ARG, "gpe_edit_particles: every field array is NULL");
-    if (is_sharded(c))
-        return fail(c, GPE_ERR_UNSUPPORTED, "gpe_edit_particles: not supported on a sharded context (gpe_shard_*, order "
-                                            "keys or an active cell box)");
-    if (e->key_kind == GPE_EDIT_BY_UID && !c->uid.on) return fail(c, GPE_ERR_STATE, "gpe_edit_particles: uids are off");
-    if (e->k == 0) return GPE_OK;
-    GPE_TRY(need_particles(c));
-    // (more indices than particles repeat one; a list of uids may be padded with absent ones)
-    if (e->key_kind == GPE_EDIT_BY_INDEX && e->k > c->n)
-        return fail(c, GPE_ERR_INVALID_ARG, "gpe_edit_particles: two keys name the same particle");
-    if (e->k > (1ull << 30) - 1) return fail(c, GPE_ERR_INVALID_ARG, "gpe_edit_particles: k too large");
-    GPE_HIP(c, hipSetDevice(c->device));
-    GPE_HIP(c, hipStreamSynchronize(c->stream));
-    return do_edit(c, e);
-}
-
-// The checks the two kicks share, in this order: *n_kicked = 0, the sharded refusal, op and a.
-static gpe_status kick_begin(gpe_ctx *c, const char *who, uint32_t op, float ax, float ay, uint64_t *n_kicked)
-{
-    if (!c) return GPE_ERR_INVALID_ARG;
-    if (n_kicked) *n_kicked = 0;
-    if (is_sharded(c))
-        return fail(c, GPE_ERR_UNSUPPORTED, std::string(who) + ": not supported on a sharded context (gpe_shard_*, "
-                                                                "order keys or an active cell box)");
-    if (op != GPE_VEL_ADD && op != GPE_VEL_SET && op != GPE_VEL_SCALE)
-        return fail(c, GPE_ERR_INVALID_ARG, std::string(who) + ": unknown operation");
-    if (!isfinite(ax) || !isfinite(ay)) return fail(c, GPE_ERR_INVALID_ARG, std::string(who) + ": ax and ay must be finite");
-    return GPE_OK;
-}
-
-static gpe_status do_kick(gpe_ctx *c, bool box, const float *region, uint32_t op, float ax, float ay, uint64_t *n_kicked)
-{
-    if (c->n == 0 || !c->pos) return GPE_OK;                      // nothing to kick
-    GPE_HIP(c, hipSetDevice(c->device));
-    unsigned long long *d_count = nullptr;
-    if (n_kicked) {
-        GPE_TRY(edit_buffer(c, &c->edit_ws.count, nullptr, 1, 0, "edit.count"));
-        d_count = c->edit_ws.count;
-    }
-    {
-        Scope s(c, "Kick particles");
-        GPE_TRY(launch_kick(c, box, region, op, ax, ay, d_count));
-    }
-    if (!n_kicked) return GPE_OK;                                 // stream-ordered, like gpe_step
-    unsigned long long kicked = 0;
-    GPE_HIP(c, hipMemcpyAsync(&kicked, d_count, sizeof(kicked), hipMemcpyDeviceToHost, c->stream));
-    GPE_HIP(c, hipStreamSynchronize(c->stream));
-    *n_kicked = kicked;
-    return GPE_OK;
-}
-
-gpe_status gpe_kick_circle(gpe_ctx *c, float x, float y, float radius, uint32_t op, float ax, float ay, uint64_t *n_kicked)
-{
-    float region[5];
-    GPE_TRY(kick_begin(c, "gpe_kick_circle", op, ax, ay, n_kicked));
-    GPE_TRY(circle_region(c, "gpe_kick_circle", x, y, radius, region));
-    return do_kick(c, false, region, op, ax, ay, n_kicked);
-}
-
-gpe_status gpe_kick_box(gpe_ctx *c, float x0, float y0, float x1, float y1, uint32_t op, float ax, float ay,
-                        uint64_t *n_kicked)
-{
-    float region[5];
-    bool empty = false;
-    GPE_TRY(kick_begin(c, "gpe_kick_box", op, ax, ay, n_kicked));
-    GPE_TRY(box_region(c, "gpe_kick_box", x0, y0, x1, y1, region, &empty));
-    if (empty) return GPE_OK;                                     // an empty box holds nothing
-    return do_kick(c, true, region, op, ax, ay, n_kicked);
 }
 
 gpe_status gpe_len(const gpe_ctx *c, uint64_t *n)
@@ -2837,8 +1357,7 @@ gpe_status gpe_step(gpe_ctx *c, float dt, uint32_t flags)
     GPE_TRY(need_particles(c));
     GPE_HIP(c, hipSetDevice(c->device));
     GPE_TRY(do_step(c, dt, flags));
-    if (c->tracers.armed) GPE_TRY(tracers_after_step(c));
-    return c->monitor.armed ? monitor_after_step(c) : GPE_OK;
+    return observers_after_step(c);
 }
 
 gpe_status gpe_run(gpe_ctx *c, float dt, uint64_t steps, uint64_t resort_every, int32_t resort_first)
@@ -2860,8 +1379,7 @@ gpe_status gpe_run(gpe_ctx *c, float dt, uint64_t steps, uint64_t resort_every, 
         }
         const bool resort = (s == 0 && resort_first) || (resort_every && s > 0 && (s % resort_every) == 0);
         rc = do_step(c, dt, resort ? GPE_STEP_RESORT : 0u);
-        if (rc == GPE_OK && c->tracers.armed) rc = tracers_after_step(c);
-        if (rc == GPE_OK && c->monitor.armed) rc = monitor_after_step(c);
+        if (rc == GPE_OK) rc = observers_after_step(c);
     }
     for (hipEvent_t e : fence) if (e) (void)hipEventDestroy(e);
     return rc;

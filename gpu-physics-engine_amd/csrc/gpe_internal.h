@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <algorithm>
 #include <string>
 #include <vector>
 
@@ -810,6 +811,79 @@ inline hipError_t dev_release(gpe_ctx *c, T *&p)
 {
     return gpe_dev_release(c, (void **)&p);
 }
+
+// the API's host side (gpe_api.hip, gpe_queries.hip, gpe_edits.hip, gpe_observe.hip): what the four files share ----
+// One workspace buffer: payload exactly count elements, slack as stated at the call with its reader.  A failure reads
+// "<who>: out of device memory" (or what `oom` says instead) / "<who>: <hipGetErrorName>".
+template <typename T>
+gpe_status ws_alloc(gpe_ctx *c, const char *who, T **p, uint64_t count, uint64_t slack_bytes, const char *tag,
+                    const char *oom = "out of device memory")
+{
+    const hipError_t e = dev_reserve(c, p, count * sizeof(T), slack_bytes, tag);
+    if (e == hipErrorOutOfMemory) return fail(c, GPE_ERR_OOM, std::string(who) + ": " + oom);
+    if (e != hipSuccess) return fail(c, GPE_ERR_HIP, std::string(who) + ": " + hipGetErrorName(e));
+    return GPE_OK;
+}
+
+template <typename T>
+gpe_status dev_alloc(gpe_ctx *c, T **p, uint64_t count, const char *tag)
+{
+    // payload: count elements.  slack: the round-up to 4 elements and 64 bytes -- no kernel is known to read them; they
+    // keep the unguarded allocation at the size it always had (max(count, 4) * sizeof(T) + 64)
+    // ("hipMalloc" is no caller's name: it keeps the text dev_alloc's failures always had, "hipMalloc: ...")
+    const uint64_t payload = count * sizeof(T);
+    return ws_alloc(c, "hipMalloc", p, count, std::max<uint64_t>(count, 4) * sizeof(T) + 64 - payload, tag);
+}
+
+template <typename T>
+void dev_free(gpe_ctx *c, T *&p)
+{
+    (void)dev_release(c, p);
+}
+
+// The 256-byte aligned staging layout of a result's requested parts: part() = the offset of the next part, which takes
+// room only when it is requested; bytes = what the parts so far take.
+struct StageLayout {
+    uint64_t bytes = 0;
+    uint64_t part(bool on, uint64_t len)
+    {
+        const uint64_t at = bytes;
+        if (on) bytes += (len + 255) / 256 * 256;
+        return at;
+    }
+};
+
+constexpr uint64_t kUidLimit = 1ull << 32;                     // next_uid may reach 2^32: then no particle can be added
+inline bool is_sharded(const gpe_ctx *c) { return c->shard.on || c->use_order_keys || c->has_active_box; }
+
+// the refusals several entry points word alike (gpe_api.hip): fail() with "<who>: ..."
+gpe_status refuse_sharded(gpe_ctx *c, const char *who);             // GPE_ERR_UNSUPPORTED: is_sharded(c)
+gpe_status refuse_too_many(gpe_ctx *c, const char *who);            // GPE_ERR_UNSUPPORTED: more than 2^32 - 1 particles
+gpe_status refuse_uid_off(gpe_ctx *c, const char *who);             // GPE_ERR_STATE: a uid output while uids are off
+gpe_status refuse_radius_not_finite(gpe_ctx *c, const char *who);   // GPE_ERR_UNSUPPORTED
+// gpe_api.hip
+gpe_status need_particles(gpe_ctx *c);
+gpe_status check_device_errors(gpe_ctx *c);        // the sticky device-side error words; synchronises
+gpe_status grow_particle_buffers(gpe_ctx *c, uint64_t cap);
+gpe_status init_index_buffers(gpe_ctx *c, uint64_t lo, uint64_t hi);
+void refresh_cell_size(gpe_ctx *c);
+gpe_status reconfigure(gpe_ctx *c);
+gpe_status uid_map_ready(gpe_ctx *c);
+gpe_status uid_query_reserve(gpe_ctx *c, uint64_t bytes);
+// gpe_queries.hip (the region words of the circle and box calls are shared with the kicks), gpe_edits.hip
+void query_release(gpe_ctx *c);
+void contacts_release(gpe_ctx *c);
+void clusters_release(gpe_ctx *c);
+void ray_release(gpe_ctx *c);
+void nearest_release(gpe_ctx *c);
+void spawn_release(gpe_ctx *c);
+void edit_release(gpe_ctx *c);
+gpe_status circle_region(gpe_ctx *c, const char *who, float x, float y, float radius, float (&region)[5]);
+gpe_status box_region(gpe_ctx *c, const char *who, float x0, float y0, float x1, float y1, float (&region)[5],
+                      bool *empty);
+// gpe_observe.hip: the tracers and the monitor of an armed context
+gpe_status observers_after_step(gpe_ctx *c);       // after every step of gpe_step / gpe_run
+void observers_release(gpe_ctx *c);
 
 // profiling scope: a hipEvent pair on ctx->stream when ctx->profiling, else nothing.  kSharedBoundaries: inside a
 // ScopeRegion the scope takes the event a neighbouring scope recorded where nothing was enqueued between the two

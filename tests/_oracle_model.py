@@ -2,7 +2,8 @@
 
 OracleModel holds what a context holds, in storage order: pos, prev, radius, the uids and next_uid (uids on), and the
 constants a step depends on (world, gravity, mouse, the grid radius and the max radius).  Each public operation of
-include/gpe.h is applied as the header and csrc/gpe_api.hip define it; the steps themselves run through oracle.Sim.
+include/gpe.h is applied as the header and the API's host side (csrc/gpe_api.hip, gpe_queries.hip, gpe_edits.hip,
+gpe_observe.hip) define it; the steps themselves run through oracle.Sim.
 Whenever a constant or the arrays change on the host side, the next step builds a new Sim from the current arrays
 (with prev=), so a Sim never sees stale constants.  The step keeps no hidden state between calls (home cells and
 particle ids are rebuilt by every re-sort), which tests/test_oracle_model_cpu.py checks against one long-lived Sim.

@@ -38,7 +38,8 @@ def test_pinned_host_memory_stays_where_it_was():
     assert hits == ["gpe_native.hip", "k_shard.hip"], hits
 
 
-TAG = r'"(?:particles|grid|uid|remove|query|user|sort|scan|onesweep|native|shard|ctl|group)\.[a-z0-9_]+"'
+TAG = (r'"(?:particles|grid|uid|remove|query|user|sort|scan|onesweep|native|shard|ctl|group'
+       r'|contacts|clusters|ray|nearest|spawn|edit|tracers|monitor)\.[a-z0-9_]+"')
 
 
 def _calls(code, name):
@@ -58,13 +59,13 @@ def _calls(code, name):
 
 
 def test_every_allocation_site_names_a_tag():
-    """Every call of an allocating helper (gpe_dev_reserve, dev_reserve, dev_alloc, gpe_native.hip's reserve,
-    ensure_words) ends in a tag: a literal of the registry's naming scheme, or an expression made of such literals
+    """Every call of an allocating helper (gpe_dev_reserve, dev_reserve, dev_alloc, ws_alloc, gpe_edits.hip's
+    edit_buffer, gpe_native.hip's reserve, ensure_words) ends in a tag: a literal of the registry's naming scheme, or an expression made of such literals
     (a choice between tags), or the tag parameter a wrapper hands on.  No tag is longer than gpe_guard_zone.tag holds."""
     sites, tags = 0, set()
     for path in _sources():
         code = _code(path)
-        names = ["gpe_dev_reserve", "dev_reserve", "dev_alloc", "ensure_words"]
+        names = ["gpe_dev_reserve", "dev_reserve", "dev_alloc", "ws_alloc", "edit_buffer", "ensure_words"]
         if os.path.basename(path) == "gpe_native.hip":
             names.append("reserve")
         for name in names:
@@ -75,5 +76,52 @@ def test_every_allocation_site_names_a_tag():
                 assert found or last in ("tag", "b.second"), (os.path.basename(path), name, args)
                 sites += 1
                 tags.update(t.strip('"') for t in found)
-    assert sites >= 60, sites
+    assert sites >= 127, sites
     assert all(len(t) < 32 for t in tags), sorted(tags)          # gpe_guard_zone.tag is char[32]
+
+
+def _body(code, name):
+    """The body of the function `name` defined at the left margin of code."""
+    m = re.search(r"^[\w:<> \*]*\b%s\([^{;]*\)\n\{\n(.*?)\n\}" % re.escape(name), code, flags=re.S | re.M)
+    assert m, name
+    return m.group(1)
+
+
+# workspace: (file, the functions that allocate its buffers, its release function)
+WORKSPACES = {
+    "remove": ("gpe_api.hip", ["remove_reserve"], "remove_release"),
+    "uid": ("gpe_api.hip", ["alloc_particle_buffers", "uids_switch_on", "uid_map_build", "uid_query_reserve"], "uid_release"),
+    "query": ("gpe_queries.hip", ["query_reserve"], "gpe::query_release"),
+    "contacts": ("gpe_queries.hip", ["contacts_reserve"], "gpe::contacts_release"),
+    "clusters": ("gpe_queries.hip", ["clusters_reserve"], "gpe::clusters_release"),
+    "ray": ("gpe_queries.hip", ["ray_reserve"], "gpe::ray_release"),
+    "nearest": ("gpe_queries.hip", ["nearest_reserve"], "gpe::nearest_release"),
+    "spawn": ("gpe_edits.hip", ["spawn_reserve"], "gpe::spawn_release"),
+    "edit": ("gpe_edits.hip", ["do_edit", "do_kick"], "gpe::edit_release"),
+    "tracers": ("gpe_observe.hip", ["gpe_tracers_begin"], "tracers_release"),
+    "monitor": ("gpe_observe.hip", ["monitor_reserve", "gpe_monitor_begin"], "monitor_release"),
+}
+
+
+def test_every_workspace_releases_exactly_what_it_reserves():
+    """For each workspace the fields its reserve functions allocate (the pointer handed to dev_alloc / ws_alloc /
+    edit_buffer, next to a tag of that workspace) are the fields its release function hands to dev_free, no more and no
+    fewer -- and free_particle_buffers / observers_release call every release function."""
+    api = _code(os.path.join(CSRC, "gpe_api.hip"))
+    observe = _code(os.path.join(CSRC, "gpe_observe.hip"))
+    callers = _body(api, "free_particle_buffers") + _body(observe, "gpe::observers_release")
+    for prefix, (fname, reserves, release) in WORKSPACES.items():
+        code = _code(os.path.join(CSRC, fname))
+        reserved = set()
+        for fn in reserves:
+            for name in ("dev_alloc", "ws_alloc", "edit_buffer"):
+                for args in _calls(_body(code, fn), name):
+                    tag = re.search(r'"%s\.([a-z0-9_]+)"' % prefix, args)
+                    if not tag:
+                        continue                                        # (another owner's buffer)
+                    field = re.search(r"&[\w>.-]*?(\w+),", args).group(1)
+                    assert field == tag.group(1), (prefix, args)          # the tag names the field
+                    reserved.add(field)
+        freed = re.findall(r"dev_free\(c, [\w>.-]*?(\w+)\)", _body(code, release))
+        assert len(freed) == len(set(freed)) and set(freed) == reserved and reserved, (prefix, sorted(reserved), sorted(freed))
+        assert re.search(r"\b%s\(c\)" % release.split("::")[-1], callers), release

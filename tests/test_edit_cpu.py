@@ -133,11 +133,16 @@ def test_host_layers_mirror_the_edit_api(gpe):
 
 
 def test_edit_workspaces_are_tagged_and_freed_with_the_particles():
-    """The edit.* buffers go through the one allocator with a tag each, and free_particle_buffers releases them."""
-    api = open(os.path.join(ROOT, "gpu-physics-engine_amd", "csrc", "gpe_api.hip")).read()
-    tags = set(re.findall(r'"(edit\.[a-z_]+)"', api))
+    """The edit.* buffers go through the one allocator with a tag each, edit_release frees every one of them, and
+    free_particle_buffers calls edit_release."""
+    csrc = os.path.join(ROOT, "gpu-physics-engine_amd", "csrc")
+    edits = open(os.path.join(csrc, "gpe_edits.hip")).read()
+    tags = set(re.findall(r'"(edit\.[a-z_]+)"', edits))
     assert tags == {"edit.keys", "edit.slots", "edit.fields", "edit.flag", "edit.tile_key", "edit.max_key", "edit.count"}
     assert all(len(t) < 32 for t in tags)
-    free = re.search(r"static void free_particle_buffers\(gpe_ctx \*c\)\s*\{(.*?)\n\}", api, flags=re.S).group(1)
+    release = re.search(r"void gpe::edit_release\(gpe_ctx \*c\)\s*\{(.*?)\n\}", edits, flags=re.S).group(1)
     for field in ("keys", "slots", "fields", "flag", "tile_key", "max_key", "count"):
-        assert re.search(r"dev_free\(c, e\.%s\)" % field, free), field
+        assert re.search(r"dev_free\(c, ws\.%s\)" % field, release), field
+    api = open(os.path.join(csrc, "gpe_api.hip")).read()
+    free = re.search(r"static void free_particle_buffers\(gpe_ctx \*c\)\s*\{(.*?)\n\}", api, flags=re.S).group(1)
+    assert re.search(r"\bedit_release\(c\)", free)

@@ -165,6 +165,85 @@ def test_words_must_keep_a_consumed_poison_harmless(gpe):
         gpe.Context(flags=gpe._lib.FLAG_GUARD_ALLOCS, guard_words=good).close()
 
 
+# ---- the workspaces' allocations: tag, payload and slack --------------------------------------------------------------
+# What the registry must hold once every workspace has been used once on WS_N particles in touching pairs, uids on.
+# Written out from the reserve functions as they stood before the API's host side was split by feature: 300 particles
+# are query_tiles = 1 tile of 2048 and contacts_tiles = 2 workgroups of 256; 64 bytes (16 words) of slack behind what
+# sort_pairs sorts and what the scan runs on in place, none elsewhere; the query.* buffers keep dev_alloc's historical
+# slack, max(count, 4) elements + 64 bytes less the payload.
+WS_N, WS_PAIRS = 300, 150
+WS_ROW_WORDS = 65537                                       # ray.row_start / nearest.row_start: one word per clamped row + 1
+WS_TABLE = {
+    # a circle query that returns all 300 rows with every field: 2 parts of 2400 -> 2560 bytes, 3 of 1200 -> 1280
+    "query.tile_count": (4, 76), "query.tile_key": (8, 88), "query.pick": (8, 88), "query.stage": (8960, 64),
+    # 150 pairs with index_a, index_b, uid_a, uid_b and overlap: 5 parts of 600 -> 768 bytes
+    "contacts.keys": (1200, 64), "contacts.vals": (1200, 64), "contacts.rec": (4800, 0), "contacts.degree": (1200, 0),
+    "contacts.upper": (1200, 64), "contacts.tile_sum": (16, 0), "contacts.total": (8, 0), "contacts.stage": (3840, 0),
+    "clusters.parent": (1200, 0), "clusters.label": (1200, 0), "clusters.root_size": (1200, 0), "clusters.size": (1200, 0),
+    "clusters.tile_word": (16, 0), "clusters.words": (16, 0),
+    # 5 rays
+    "ray.row_start": (4 * WS_ROW_WORDS, 0), "ray.from": (40, 0), "ray.to": (40, 0), "ray.index": (20, 0), "ray.uid": (20, 0),
+    "ray.t": (20, 0), "ray.pos": (40, 0), "ray.radius": (20, 0),
+    # 5 points of 3 slots
+    "nearest.row_start": (4 * WS_ROW_WORDS, 0), "nearest.points": (40, 0), "nearest.count": (20, 0), "nearest.index": (60, 0),
+    "nearest.uid": (60, 0), "nearest.dist2": (60, 0), "nearest.pos": (120, 0), "nearest.radius": (60, 0),
+    # 7 candidates; ctl: 4 box words + 8 round counters
+    "spawn.pos": (56, 0), "spawn.radius": (28, 0), "spawn.keys": (28, 64), "spawn.vals": (28, 64), "spawn.rec": (112, 0),
+    "spawn.blocked": (28, 0), "spawn.state": (28, 0), "spawn.rank": (28, 64), "spawn.verdict": (7, 0), "spawn.ctl": (48, 0),
+    # 4 keys with pos, prev and radius: 3 parts of 256 bytes; the radius edit's tile keys (1 tile) and their maximum
+    "edit.keys": (16, 64), "edit.slots": (16, 64), "edit.fields": (768, 0), "edit.flag": (8, 0), "edit.tile_key": (8, 0),
+    "edit.max_key": (8, 0),
+    # 3 tracers x 2 frames with pos, prev and index
+    "tracers.keys": (12, 0), "tracers.perm": (12, 0), "tracers.slot_index": (12, 0), "tracers.ring_pos": (48, 0),
+    "tracers.ring_prev": (48, 0), "tracers.ring_index": (24, 0),
+    # 2048 partial records of 80 bytes and one gpe_measures of 120
+    "monitor.partials": (2048 * 80 + 120, 0),
+}
+
+
+def test_workspace_allocations_keep_their_tags_payloads_and_slack(gpe):
+    """Every workspace used once on a guarded context: the registry lists each buffer of WS_TABLE with exactly that
+    payload and slack and no other workspace buffer, the tracers' go to "released" unchanged at tracers_end, no red zone
+    is damaged, and the context closes."""
+    L = gpe._lib
+    i = np.arange(WS_N)
+    # rows of 10 pairs: partners 1.5 apart (radius 1: touching), pairs 6 and rows 3 apart (not touching)
+    pos = np.stack([10.0 + 6.0 * ((i % 20) // 2) + 1.5 * (i % 2), 10.0 + 3.0 * (i // 20)], axis=1).astype(np.float32)
+    rad = np.ones(WS_N, np.float32)
+    st = gpe.State(pos, rad, world=(80.0, 64.0), flags=L.FLAG_GUARD_ALLOCS)
+    st.enable_uids()
+    assert len(st.query_circle((40.0, 30.0), 1000.0).index) == WS_N
+    assert st.pick((10.0, 10.0)).index[0] == 0
+    assert len(st.contacts(capacity=1000, overlap=True).a) == WS_PAIRS
+    assert st.clusters().count == WS_PAIRS
+    ends = np.array([[10.0, 5.0], [16.0, 5.0], [22.0, 5.0], [28.0, 5.0], [3.0, 3.0]], np.float32)
+    assert st.cast_rays(ends, ends + np.float32([0.0, 10.0]), uids=True, rows=True).hits == 4
+    assert st.nearest(ends, m=3, uids=True, rows=True).found == 15
+    cand = np.concatenate([ends, [[70.0, 60.0], [75.0, 60.0]]]).astype(np.float32)
+    added, verdict = st.add_particles_free(cand, np.ones(7, np.float32), dry_run=True)
+    assert len(verdict) == 7 and st.positions().shape[0] == WS_N
+    keys = np.array([0, 7, 150, 299])
+    assert st.edit_particles(indices=keys, positions=pos[keys], previous=pos[keys], radii=rad[keys]) == 4
+    st.tracers_begin(np.array([3, 4, 298]), every=1, frames=2, prev=True, index=True)
+    st.update(1 / 60); st.update(1 / 60)
+    assert st.tracers_read().recorded == 2
+    assert st.measure().n == WS_N
+
+    def workspace(state):
+        rows = [(t, p, s) for t, p, s, when in st.ctx.guard_registry() if when == state and t.split(".")[0] in
+                ("query", "contacts", "clusters", "ray", "nearest", "spawn", "edit", "tracers", "monitor")]
+        assert len(rows) == len(set(t for t, _, _ in rows)), rows
+        return {t: (p, s) for t, p, s in rows}
+    live = workspace("live")
+    assert live == WS_TABLE
+    st.tracers_end()
+    gone = workspace("released")
+    assert {t: v for t, v in gone.items() if t.startswith("tracers.")} == {t: v for t, v in WS_TABLE.items() if t.startswith("tracers.")}
+    assert not any(t.startswith("tracers.") for t in workspace("live"))
+    assert st.ctx.guard_check() == [] and st.ctx.guard_damaged == 0
+    st.close()
+
+
 # ---- primitives on user buffers of exactly n elements ---------------------------------------------------------------
 SORT_SIZES = [1, 63, 64, 65, 4095, 4096, 4097, 8191, 8193, (3 << 20) - 1, (3 << 20) + 1]
 
