@@ -617,6 +617,7 @@ struct TileLds {
     uint32_t hm[CAP];          // bits 0-10 index of the home cell in the padded cell array; bits 11-18 overlap mask of
                                // the 8 neighbour cells (k_native_hash); bit 19 the home cell lies in the tile (the
                                // particle is the tile's own)
+    __device__ __forceinline__ bool is_own(uint32_t s) const { return (hm[s] & (1u << 19)) != 0; }
     // cell[lc + 1]: members of cell lc (P1) -> first slot of its list (P2) -> one past its last slot (P3);
     // cell[0] = 0, so from P3 on the list of cell lc is mem[cell[lc] .. cell[lc + 1]).  Values stay below
     // 4 * CAP < 65536: two cells share a word (LDS atomics are 32 bit, so cell_inc adds 1 or 1 << 16 --
@@ -1214,19 +1215,252 @@ __device__ __forceinline__ int neighbour_offset(const int k)
     return (int)(int8_t)(uint8_t)(packed >> (8 * k));
 }
 
-// Consecutive slots for the particles a wave keeps (`mask`: the lanes that keep theirs): one atomic on the counter word
-// per wave, by lane 0 -- the order of the slots is free.  A slot at or beyond `cap` is not kept; the counter then tells
-// the tile that it ran over.  (The straggler and ghost intake of the direct-slot form.  Its gather, which takes the
-// slots of two rounds with one atomic, and process_tile's three intake paths keep their own copies: with a shared helper
-// k_collide_border<true> and the order-key counting-sort kernels compile to different code, which nobody has timed.)
+// Consecutive slots for the particles a wave keeps (`mask`: the lanes that keep theirs, one mask per round of the gather):
+// one atomic on the counter word per wave, by lane 0 -- the order of the slots is free.  A slot at or beyond `cap` is not
+// kept; the counter then tells the tile that it ran over.  (Both tile forms, gather and list intake: the kernels this
+// changed were timed against their parent, profiles/tile_phases/.)
+template <int Q>
+__device__ __forceinline__ void take_slots(uint32_t *counter, const int lane, const uint32_t cap, const uint64_t (&mask)[Q],
+                                           uint32_t (&slot)[Q], bool (&keep)[Q])
+{
+    uint32_t cnt = 0;
+#pragma unroll
+    for (int q = 0; q < Q; ++q) cnt += (uint32_t)__popcll(mask[q]);
+    uint32_t base = 0;
+    if (lane == 0 && cnt) base = atomicAdd(counter, cnt);
+    base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
+#pragma unroll
+    for (int q = 0; q < Q; ++q) {
+        slot[q] = base + popc_below_lane(mask[q]);
+        base += (uint32_t)__popcll(mask[q]);
+        keep[q] = keep[q] && slot[q] < cap;
+    }
+}
 __device__ __forceinline__ uint32_t take_slots(uint32_t *counter, const int lane, const uint32_t cap, const uint64_t mask, bool &keep)
 {
-    uint32_t base = 0;
-    if (lane == 0 && mask) base = atomicAdd(counter, (uint32_t)__popcll(mask));
-    base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
-    const uint32_t slot = base + popc_below_lane(mask);
-    keep = keep && slot < cap;
-    return slot;
+    const uint64_t m[1] = {mask};
+    uint32_t slot[1];
+    bool k[1] = {keep};
+    take_slots(counter, lane, cap, m, slot, k);
+    keep = k[0];
+    return slot[0];
+}
+
+// P1 of the counting-sort windows, one staged particle the window keeps: its arrays, the count of its home cell, and of
+// up to three phantom cells.
+template <class L>
+__device__ __forceinline__ void file_kept(L &S, const uint32_t s, const float2 pp, const float pr, const uint32_t pid, const uint32_t lid,
+                                          const int lx, const int ly, const uint32_t code)
+{
+    constexpr int T = L::TILE, HX = L::HXL, HY = L::HYL, PX = L::PX;
+    S.px[s] = pp.x; S.py[s] = pp.y; S.rad[s] = pr; S.id[s] = pid;
+    if constexpr (L::kLid) S.lid[s] = lid;
+    const int home = (ly + 1) * PX + lx + 1;                          // index in the padded cell array
+    S.cell_inc(home + 1);
+    // phantom cells: the first three set bits of the overlap mask (grid.wgsl:68-90 keeps at most three)
+    uint32_t over = (code >> kCodeOverlapShift) & 0xFFu;
+    const uint32_t own = (lx >= HX && lx < HX + T && ly >= HY && ly < HY + T) ? (1u << 19) : 0u;
+    S.hm[s] = (uint32_t)home | (over << 11) | own;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        if (over == 0) break;
+        const int k = __ffs((int)over) - 1;
+        over &= over - 1u;
+        S.cell_inc(home + neighbour_offset<PX>(k) + 1);               // (always inside the padded array)
+    }
+}
+// ... and one the spill window does not keep.  The spill window's slots are the looked-up slots (the stragglers and the
+// listed ghosts sit behind them): a particle that has drifted out of the looked-up region (it is listed under its old
+// block) still owns one.  Filed under ring cell 0 -- outside every colour's zone, never walked, never written back -- so
+// that the loops over the slots find a valid entry.
+template <class L>
+__device__ __forceinline__ void file_dropped(L &S, const uint32_t s, const float2 pp, const float pr, const uint32_t pid)
+{
+    S.px[s] = pp.x; S.py[s] = pp.y; S.rad[s] = pr; S.id[s] = pid;
+    S.cell_inc(0 + 1);
+    S.hm[s] = 0u;
+}
+
+// The tile's own particles (S.is_own) and, when K12 is fused into the write-back, their previous positions, into one
+// register per round of NT slots.  Branch-free like the gather of P1: every lane loads -- a lane without a particle of
+// the tile reads element 0 -- and the loads of all rounds are issued before anything uses one of them, so they are in
+// flight together and nothing waits for them before write_own_back.  Rounds from QSKIP on are skipped by a scalar test
+// when the window holds no slot of theirs (PS >= 1).
+template <bool ORD, int NT, int QSKIP, class L, int QOWN>
+__device__ __forceinline__ void fetch_own(const L &S, const CollideArgs &A, const int tid, const uint32_t PS, const uint32_t n_owned,
+                                          uint32_t (&own_id)[QOWN], float2 (&own_prev)[QOWN])
+{
+    static_assert(!ORD || L::kLid, "order-key windows keep the local indices");
+    uint32_t fetch[QOWN];
+#pragma unroll
+    for (int q = 0; q < QOWN; ++q) {
+        const uint32_t s = (uint32_t)tid + (uint32_t)q * NT;
+        own_id[q] = 0xFFFFFFFFu;
+        fetch[q] = 0u;
+        if (q >= QSKIP && PS <= (uint32_t)q * NT) continue;            // (scalar)
+        const uint32_t sc = min(s, PS - 1u);
+        const bool own = s < PS && S.is_own(sc);
+        uint32_t id = S.id[sc];
+        asm volatile("" : "+v"(id));                                 // keep this an LDS read (no pointer select -> flat load)
+        if constexpr (ORD) id = S.lid[sc];                             // S.id holds the order key; the local index was kept
+        own_id[q] = own ? id : 0xFFFFFFFFu;
+        fetch[q] = (own && id < n_owned) ? id : 0u;
+    }
+#pragma unroll
+    for (int q = 0; q < QOWN; ++q) {
+        own_prev[q] = make_float2(0.f, 0.f);
+        if (q >= QSKIP && PS <= (uint32_t)q * NT) continue;
+#ifdef GPE_DBG_SKIP
+        if (GPE_DBG_SKIP & 32) continue;                               // diagnostic builds: phase cost by omission (results wrong)
+#endif
+        if (A.fuse_verlet) own_prev[q] = A.prev[fetch[q]];
+    }
+}
+// P6: what fetch_own found, written back with K12 applied -- the integrated position becomes the live one, the resolved
+// position the previous one (particle_integration.wgsl:64,76).  A sharded step (`packs`, scalar) packs the tile's
+// particles for the neighbours on the way (S.id holds the order key).
+template <bool ORD, int NT, int QSKIP, class L, int QOWN>
+__device__ __forceinline__ void write_own_back(const L &S, const CollideArgs &A, const int tid, const uint32_t PS, const uint32_t n_owned,
+                                               const bool packs, const uint32_t (&own_id)[QOWN], const float2 (&own_prev)[QOWN])
+{
+#pragma unroll
+    for (int q = 0; q < QOWN; ++q) {
+#ifdef GPE_DBG_SKIP
+        if (GPE_DBG_SKIP & 32) continue;
+#endif
+        if (q >= QSKIP && PS <= (uint32_t)q * NT) continue;            // (scalar, as where own_id was filled)
+        const uint32_t id = own_id[q];
+        const bool have = id != 0xFFFFFFFFu;
+        const uint32_t s = min((uint32_t)tid + (uint32_t)q * NT, (uint32_t)L::kSlots - 1u);
+        const float2 c = make_float2(S.px[s], S.py[s]);
+        const float rr = S.rad[s];
+        float2 o = c;
+        const bool mine = have && A.fuse_verlet && id < n_owned;
+        if (mine) {
+            verlet_one(c.x, c.y, own_prev[q].x, own_prev[q].y, rr, A.vp, o.x, o.y);
+            A.prev[id] = c;
+            A.pos_out[id] = o;
+        } else if (have) {
+            A.pos_out[id] = c;
+        }
+        if constexpr (ORD) {
+            if (packs) pack_if_near_border(A.pack, mine, id, o, c, rr, S.id[s], A.cell_size);
+        }
+    }
+}
+
+// ---- P0 of both tile forms ---------------------------------------------------------------------------------------------
+// The control words a tile reads at its entry, for its 32x32 parent tile (ptx, pty): the straggler and ghost lists are
+// kept per parent.  Issued in front of P0, consumed behind it: a crowded scene runs tens of thousands of short-lived tiles
+// and sub-tiles, and a global round trip exposed in each of them cost the dense launch a quarter of its time again (5.95
+// -> 7.5 ms at step 1000 of the 100 M soak).
+struct TileWords {
+    bool in_tb;                // the parent has lists (always, for the tiles of the dense launch)
+    uint32_t pt;               // ... at this index
+    uint32_t fresh, owned, exc, gho, gsort;
+};
+template <bool ORD>
+__device__ __forceinline__ TileWords read_tile_words(const CollideArgs &A, const int ptx, const int pty)
+{
+    TileWords w;
+    w.fresh = *A.fresh;
+    w.owned = A.counts ? A.counts[0] : (uint32_t)(A.n_owned < 0xFFFFFFFFull ? A.n_owned : 0xFFFFFFFFull);
+    w.in_tb = A.tb.holds(ptx, pty);
+    w.pt = w.in_tb ? A.tb.index(ptx, pty) : 0u;
+    w.exc = (A.exc_count && w.in_tb) ? A.exc_count[w.pt] : 0u;
+    w.gho = 0; w.gsort = 0;
+    if constexpr (ORD) {
+        if (A.ghost_sort) w.gsort = *A.ghost_sort;
+        if (A.gho_count && w.in_tb) w.gho = A.gho_count[w.pt];
+    }
+    return w;
+}
+// The region's NBX x NBY blocks from (box, boy) on, looked up in the block table: S.bstart / S.bcnt.  GHOST_TABLE: an
+// order-key counting-sort window looks every block up a second time, among the ghosts (virtual blocks [NBLK, 2 NBLK)) --
+// through their block table only when a ghost list ran over this step (gsort), or there are no lists.
+template <int NBX, int NBY, bool GHOST_TABLE, class L>
+__device__ __forceinline__ void look_blocks_up(L &S, const CollideArgs &A, const int tid, const int box, const int boy, const uint32_t gsort)
+{
+    constexpr int NBLK = NBX * NBY, VB = GHOST_TABLE ? 2 * NBLK : NBLK;
+    if (tid < VB) {
+        const int rb = tid % NBLK;                                     // the block; tid >= NBLK: among the ghosts
+        const int bi = rb % NBX, bj = rb / NBX;
+        const int lbx = box + bi - A.bx0, lby = boy + bj - A.by0;
+        uint32_t start = 0, count = 0;
+        const uint2 *tab = A.table;
+        if constexpr (GHOST_TABLE) {
+            const bool ghosts_by_table = A.gho_count == nullptr || __builtin_amdgcn_readfirstlane((int)gsort) != 0;
+            if (tid >= NBLK) tab = ghosts_by_table ? A.gtable : nullptr;
+        }
+        if (tab && lbx >= 0 && lby >= 0 && lbx < A.blocks_x && lby < A.blocks_y) {
+            const uint32_t mb = (uint32_t)(lby * A.blocks_x + lbx);
+            if (mb < A.entries) {
+                const uint2 se = tab[mb];                            // empty blocks hold (0xFFFFFFFF, 0)
+                if (se.y > se.x) { start = se.x; count = se.y - se.x; }
+            }
+        }
+        S.bstart[tid] = start;
+        S.bcnt[tid] = count;
+    }
+}
+// Behind a barrier: wave 0 scans the block populations (S.boff; S.misc[0] all looked-up particles, S.misc[1] those of the
+// tile's own blocks, the ones not on the region's rim); the threads behind it take the population of each 3x3-block
+// window of the tile (what an 8x8-cell sub-tile would stage): the host reads the step's maximum (lagged) to leave the
+// native path before windows overfill, `tile_max` (LDS, or null) keeps the tile's for its roster.  ZERO: the words of
+// S.misc (bits 2..4) that the tile starts at 0.
+template <int NBX, int NBY, int VB, uint32_t ZERO, class L>
+__device__ __forceinline__ void scan_blocks(L &S, const CollideArgs &A, const int tid, uint32_t *tile_max)
+{
+    constexpr int NBLK = NBX * NBY;
+    const int lane = tid & 63;
+    if (tid < 64) {
+        uint32_t carry = 0, own = 0;
+        for (int base = 0; base < VB; base += 64) {
+            const int b = base + lane;
+            const uint32_t cb = (b < VB) ? S.bcnt[b] : 0u;
+            const uint32_t inc = wave_inclusive_scan(cb);
+            if (b < VB) {
+                S.boff[b] = carry + inc - cb;
+                const int bi = (b % NBLK) % NBX, bj = (b % NBLK) / NBX;
+                if (bi >= 1 && bi < NBX - 1 && bj >= 1 && bj < NBY - 1) own += cb;
+            }
+            carry += (uint32_t)__builtin_amdgcn_readlane((int)inc, 63);
+        }
+        own = wave_sum(own);
+        if (lane == 0) {
+            S.boff[VB] = carry; S.misc[0] = carry; S.misc[1] = own;
+#pragma unroll
+            for (int k = 2; k < 5; ++k)
+                if (ZERO & (1u << k)) S.misc[k] = 0;
+        }
+    } else if (tid < 64 + (NBX - 2) * (NBY - 2)) {
+        const int wi = (tid - 64) % (NBX - 2), wj = (tid - 64) / (NBX - 2);
+        uint32_t w = 0;
+#pragma unroll
+        for (int dj = 0; dj < 3; ++dj)
+#pragma unroll
+            for (int di = 0; di < 3; ++di) w += S.bcnt[(wj + dj) * NBX + wi + di];
+        if (w > kWindowReport) atomicMax(&A.tile_ctl[kCtlWindowMax], w);
+        if (tile_max && w > kWindowReport) atomicMax(tile_max, w);
+    }
+}
+// Slot -> block map (S.sblk) of the looked-up slots: NT / VB threads share each block's slots.
+template <int NT, int VB, class L>
+__device__ __forceinline__ void map_slots_to_blocks(L &S, const int tid)
+{
+    constexpr int SHARE = (NT / VB) > 0 ? (NT / VB) : 1;
+    for (int b = tid % VB, sub = tid / VB; sub < SHARE && b < VB; b += NT) {
+        const uint32_t lo = S.boff[b], hi = S.boff[b + 1];
+        for (uint32_t i = lo + sub; i < hi; i += SHARE) S.sblk[i] = (uint8_t)b;
+    }
+}
+
+// A tile this launch has no room for, appended to the list of a launch behind it (thread 0; CollideArgs::overflow1 / 2).
+__device__ __forceinline__ void hand_tile_on(const CollideArgs &A, const int counter, uint32_t *list, const uint32_t cap, const int tx, const int ty)
+{
+    const uint32_t slot = atomicAdd(&A.tile_ctl[counter], 1u);
+    if (slot < cap) list[slot] = ((uint32_t)ty << 16) | (uint32_t)tx;
+    else atomicOr(&A.tile_ctl[kCtlError], kErrTileOverflow);
 }
 
 // One tile: returns false when the region exceeds the window's capacity (nothing written).
@@ -1255,87 +1489,29 @@ __device__ __forceinline__ bool process_tile(L &S, const CollideArgs &A, const i
     const int ox = tx * T - HX, oy = ty * T - HY;                      // origin of the cell window
     const int box = (tx * T - kHalo) >> 3, boy = (ty * T - kHalo) >> 3;   // first looked-up block
     GPE_STAMP_BEGIN();
-    // (issued here, consumed behind P0: a crowded scene runs tens of thousands of short-lived tiles and sub-tiles, and a
-    // global round trip exposed in each of them cost the dense launch a quarter of its time again: 5.95 -> 7.5 ms at
-    // step 1000 of the 100 M soak)
-    const uint32_t fresh_word = *A.fresh;
-    const uint32_t owned_word = A.counts ? A.counts[0] : (uint32_t)(A.n_owned < 0xFFFFFFFFull ? A.n_owned : 0xFFFFFFFFull);
-    uint32_t exc_word = 0;
     const int ptx = (tx * T) >> 5, pty = (ty * T) >> 5;                // the 32x32 parent tile (lists are kept per parent)
-    const bool in_tb = A.tb.holds(ptx, pty);
-    const uint32_t pt = in_tb ? A.tb.index(ptx, pty) : 0u;
-    if (A.exc_count && in_tb) exc_word = A.exc_count[pt];
-    uint32_t gho_word = 0, gsort_word = 0;
-    if constexpr (ORD) {
-        if (A.ghost_sort) gsort_word = *A.ghost_sort;
-        if (A.gho_count && in_tb) gho_word = A.gho_count[pt];
-    }
+    const TileWords W = read_tile_words<ORD>(A, ptx, pty);
+    const uint32_t pt = W.pt;
 
     // ---- P0: clear, look the region's blocks up, slot -> block map ---------------------------------
     S.cell_clear(tid);
     if (tid < 20) S.lcnt[tid] = 0;
-    if (tid < VB) {
-        const int rb = tid % NBLK;                                     // the block; tid >= NBLK: among the ghosts
-        const int bi = rb % NB, bj = rb / NB;
-        const int bx = box + bi, by = boy + bj;
-        uint32_t start = 0, count = 0;
-        const int lbx = bx - A.bx0, lby = by - A.by0;
-        // (the ghosts: through their block table only when a ghost list ran over this step, or there are no lists)
-        const bool ghosts_by_table = ORD && (A.gho_count == nullptr || __builtin_amdgcn_readfirstlane((int)gsort_word) != 0);
-        const uint2 *tab = (ORD && tid >= NBLK) ? (ghosts_by_table ? A.gtable : nullptr) : A.table;
-        if (tab && lbx >= 0 && lby >= 0 && lbx < A.blocks_x && lby < A.blocks_y) {
-            const uint32_t mb = (uint32_t)(lby * A.blocks_x + lbx);
-            if (mb < A.entries) {
-                const uint2 se = tab[mb];                            // empty blocks hold (0xFFFFFFFF, 0)
-                if (se.y > se.x) { start = se.x; count = se.y - se.x; }
-            }
-        }
-        S.bstart[tid] = start;
-        S.bcnt[tid] = count;
-    }
+    look_blocks_up<NB, NB, ORD>(S, A, tid, box, boy, W.gsort);
     __syncthreads();
-    if (tid < 64) {
-        // exclusive scan of the block populations by one wave; particles of the tile's own blocks
-        uint32_t carry = 0, own = 0;
-        for (int base = 0; base < VB; base += 64) {
-            const int b = base + lane;
-            const uint32_t cb = (b < VB) ? S.bcnt[b] : 0u;
-            const uint32_t inc = wave_inclusive_scan(cb);
-            if (b < VB) {
-                S.boff[b] = carry + inc - cb;
-                const int bi = (b % NBLK) % NB, bj = (b % NBLK) / NB;
-                if (bi >= 1 && bi < NB - 1 && bj >= 1 && bj < NB - 1) own += cb;
-            }
-            carry += (uint32_t)__builtin_amdgcn_readlane((int)inc, 63);
-        }
-        own = wave_sum(own);
-        if (lane == 0) {
-            S.boff[VB] = carry; S.misc[0] = carry; S.misc[1] = own; S.misc[3] = 0;
-            if (!L::kGlobal) S.misc[2] = 0;                            // main tile: "a cell of more than 64 members"
-        }
-    } else if (tid < 64 + (NB - 2) * (NB - 2)) {
-        // population of each 3x3-block window of this tile (what an 8x8-cell sub-tile would stage):
-        // the host reads the step's maximum (lagged) to leave the native path before windows overfill
-        const int wi = (tid - 64) % (NB - 2), wj = (tid - 64) / (NB - 2);
-        uint32_t w = 0;
-#pragma unroll
-        for (int dj = 0; dj < 3; ++dj)
-#pragma unroll
-            for (int di = 0; di < 3; ++di) w += S.bcnt[(wj + dj) * NB + wi + di];
-        if (w > kWindowReport) atomicMax(&A.tile_ctl[kCtlWindowMax], w);
-    }
+    // (misc[3], the kept particles, starts at 0; in a main tile misc[2] as well: "a cell of more than 64 members")
+    scan_blocks<NB, NB, VB, L::kGlobal ? 8u : 12u>(S, A, tid, nullptr);
     __syncthreads();
     const uint32_t P = (uint32_t)__builtin_amdgcn_readfirstlane((int)S.misc[0]);   // the same in every lane: keep it scalar
-    const bool stale = __builtin_amdgcn_readfirstlane((int)fresh_word) == 0;
-    const uint32_t n_owned_now = (uint32_t)__builtin_amdgcn_readfirstlane((int)owned_word);
+    const bool stale = __builtin_amdgcn_readfirstlane((int)W.fresh) == 0;
+    const uint32_t n_owned_now = (uint32_t)__builtin_amdgcn_readfirstlane((int)W.owned);
     const uint32_t straggler_bit = stale ? kCodeStraggler : 0u;       // (listed under a block it is out of reach of: skipped)
     // stragglers handed to this tile's 32x32 parent by the hash kernel (P1 files them behind the looked-up particles)
-    const uint32_t n_exc = stale ? min((uint32_t)__builtin_amdgcn_readfirstlane((int)exc_word), kExcSlots) : 0u;
+    const uint32_t n_exc = stale ? min((uint32_t)__builtin_amdgcn_readfirstlane((int)W.exc), kExcSlots) : 0u;
     // ghosts listed for the tile's parent (sharded runs; none when the ghosts come through their block table this step)
     uint32_t n_gho = 0;
     if constexpr (ORD) {
-        if (A.gho_count != nullptr && __builtin_amdgcn_readfirstlane((int)gsort_word) == 0)
-            n_gho = min((uint32_t)__builtin_amdgcn_readfirstlane((int)gho_word), kGhostSlots);
+        if (A.gho_count != nullptr && __builtin_amdgcn_readfirstlane((int)W.gsort) == 0)
+            n_gho = min((uint32_t)__builtin_amdgcn_readfirstlane((int)W.gho), kGhostSlots);
     }
     // Nothing of its own to write?  With the table of this step: no particle in the tile's own blocks.  With a kept
     // table a particle may have drifted up to kDrift* cells out of the block that lists it, so only an empty lookup
@@ -1358,14 +1534,7 @@ __device__ __forceinline__ bool process_tile(L &S, const CollideArgs &A, const i
     } else {
         if (P > (uint32_t)L::RAWCAP) return false;                     // more looked-up particles than slots
     }
-    {
-        // slot -> block map: kNatThreads / NBLK threads share each block's slots
-        constexpr int SHARE = (kNatThreads / VB) > 0 ? (kNatThreads / VB) : 1;
-        for (int b = tid % VB, sub = tid / VB; sub < SHARE && b < VB; b += kNatThreads) {
-            const uint32_t lo = S.boff[b], hi = S.boff[b + 1];
-            for (uint32_t i = lo + sub; i < hi; i += SHARE) S.sblk[i] = (uint8_t)b;
-        }
-    }
+    map_slots_to_blocks<kNatThreads, VB>(S, tid);
     __syncthreads();
     GPE_STAMP(0);
 
@@ -1434,138 +1603,49 @@ __device__ __forceinline__ bool process_tile(L &S, const CollideArgs &A, const i
             keep[q] = lanes_of(mq[q]);
             slot[q] = s;
         }
-        if constexpr (kTrim) {
-            // kept particles get consecutive slots: one LDS atomic per wave (the order of the slots is free)
-            uint32_t cnt = 0;
-#pragma unroll
-            for (int q = 0; q < QP; ++q) cnt += (uint32_t)__popcll(mq[q]);
-            uint32_t base = 0;
-            if (lane == 0 && cnt) base = atomicAdd(&S.misc[3], cnt);
-            base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
-#pragma unroll
-            for (int q = 0; q < QP; ++q) {
-                slot[q] = base + popc_below_lane(mq[q]);
-                base += (uint32_t)__popcll(mq[q]);
-                keep[q] = keep[q] && slot[q] < (uint32_t)(sizeof(S.px) / sizeof(float));   // over capacity: see below
-            }
-        }
+        // kept particles get consecutive slots (over capacity: see below); the spill window's are the looked-up ones
+        if constexpr (kTrim) take_slots(&S.misc[3], lane, (uint32_t)L::kSlots, mq, slot, keep);
 #pragma unroll
         for (int q = 0; q < QP; ++q) {
             if constexpr (!kTrim) {
-                // The spill window's slots are the looked-up slots: a particle that has drifted out of the looked-up
-                // region (it is listed under its old block) still owns one.  File it under ring cell 0 -- outside every
-                // colour's zone, never walked, never written back -- so that the loops over the slots find a valid entry.
-                if (!keep[q] && s0 + (uint32_t)tid + (uint32_t)q * kNatThreads < P) {
-                    const uint32_t s = slot[q];
-                    S.px[s] = pp[q].x; S.py[s] = pp[q].y; S.rad[s] = pr[q]; S.id[s] = pid[q];
-                    S.cell_inc(0 + 1);
-                    S.hm[s] = 0u;
-                }
+                if (!keep[q] && s0 + (uint32_t)tid + (uint32_t)q * kNatThreads < P) file_dropped(S, slot[q], pp[q], pr[q], pid[q]);
             }
             if (!keep[q]) continue;
-            const uint32_t s = slot[q];
-            const int lx = lxq[q], ly = lyq[q];
-            S.px[s] = pp[q].x; S.py[s] = pp[q].y; S.rad[s] = pr[q]; S.id[s] = pid[q];
-            if constexpr (L::kLid) S.lid[s] = lidq[q];
-            const int home = (ly + 1) * PX + lx + 1;                  // index in the padded cell array
-            S.cell_inc(home + 1);
-            // phantom cells: the first three set bits of the overlap mask (grid.wgsl:68-90 keeps at most three)
-            uint32_t over = (cc[q] >> kCodeOverlapShift) & 0xFFu;
-            const uint32_t own = (lx >= HX && lx < HX + T && ly >= HY && ly < HY + T) ? (1u << 19) : 0u;
-            S.hm[s] = (uint32_t)home | (over << 11) | own;
-#pragma unroll
-            for (int j = 0; j < 3; ++j) {
-                if (over == 0) break;
-                const int k = __ffs((int)over) - 1;
-                over &= over - 1u;
-                S.cell_inc(home + neighbour_offset<PX>(k) + 1);       // (always inside the padded array)
-            }
+            file_kept(S, slot[q], pp[q], pr[q], pid[q], lidq[q], lxq[q], lyq[q], cc[q]);
         }
     }
+    // One entry of a list the hash kernel handed to the tile's parent -- a straggler, a listed ghost: fetched, placed by its
+    // cell (`cell_of`: the entry's or the code word's), given a slot (`spill_slot`: the spill window's, behind the
+    // looked-up ones), filed.  (Called by whole waves: the slots use ballots.)
+    auto take_listed = [&](const bool have, const uint32_t lidv, const uint32_t spill_slot, auto cell_of) {
+        const float2 pp = A.pos_in[lidv];
+        const float pr = A.radius[lidv];
+        const uint32_t cc = A.codes[lidv];
+        uint32_t pid = lidv;
+        if constexpr (ORD) pid = A.order_keys[lidv];
+        int lx, ly;
+        cell_of(cc, lx, ly);
+        bool keep = have && lx >= 0 && lx < RWX && ly >= 0 && ly < RWY;
+        uint32_t sl = spill_slot;
+        if constexpr (kTrim) sl = take_slots(&S.misc[3], lane, (uint32_t)L::kSlots, ballot64(keep), keep);
+        if (keep) file_kept(S, sl, pp, pr, pid, lidv, lx, ly, cc);
+        else if (!kTrim && have) file_dropped(S, sl, pp, pr, pid);
+    };
     if (n_exc != 0 && tid < 64) {                                      // (scalar condition; one wave files them)
         // Stragglers: particles out of reach of the block the table lists them under, handed over with their cell.
         const bool have = (uint32_t)tid < n_exc;
         const uint2 en = A.exc_entry[(uint64_t)pt * kExcSlots + (have ? (uint32_t)tid : 0u)];
-        uint32_t pid = en.x;
-        const float2 pp = A.pos_in[pid];
-        const float pr = A.radius[pid];
-        const uint32_t cc = A.codes[pid];
-        const uint32_t lidq = pid;
-        if constexpr (ORD) pid = A.order_keys[pid];
-        const int lx = (int)(en.y & 0xFFFFu) - ox, ly = (int)(en.y >> 16) - oy;
-        bool keep = have && lx >= 0 && lx < RWX && ly >= 0 && ly < RWY;
-        uint32_t sl = P + (uint32_t)tid;                               // the spill window: slots behind the looked-up ones
-        if constexpr (kTrim) {
-            const uint64_t mk = ballot64(keep);
-            uint32_t base = 0;
-            if (lane == 0 && mk) base = atomicAdd(&S.misc[3], (uint32_t)__popcll(mk));
-            base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
-            sl = base + popc_below_lane(mk);
-            keep = keep && sl < (uint32_t)(sizeof(S.px) / sizeof(float));
-        } else if (have && !keep) {
-            S.px[sl] = pp.x; S.py[sl] = pp.y; S.rad[sl] = pr; S.id[sl] = pid;
-            S.cell_inc(0 + 1);
-            S.hm[sl] = 0u;
-        }
-        if (keep) {
-            S.px[sl] = pp.x; S.py[sl] = pp.y; S.rad[sl] = pr; S.id[sl] = pid;
-            if constexpr (L::kLid) S.lid[sl] = lidq;
-            const int home = (ly + 1) * PX + lx + 1;
-            S.cell_inc(home + 1);
-            uint32_t over = (cc >> kCodeOverlapShift) & 0xFFu;
-            const uint32_t own = (lx >= HX && lx < HX + T && ly >= HY && ly < HY + T) ? (1u << 19) : 0u;
-            S.hm[sl] = (uint32_t)home | (over << 11) | own;
-#pragma unroll
-            for (int j = 0; j < 3; ++j) {
-                if (over == 0) break;
-                const int k = __ffs((int)over) - 1;
-                over &= over - 1u;
-                S.cell_inc(home + neighbour_offset<PX>(k) + 1);
-            }
-        }
+        take_listed(have, en.x, P + (uint32_t)tid,
+                    [&](uint32_t, int &lx, int &ly) { lx = (int)(en.y & 0xFFFFu) - ox; ly = (int)(en.y >> 16) - oy; });
     }
     if constexpr (ORD) {
-        // Ghosts listed for the tile's parent by the hash kernel: filed like the stragglers, placed by the cell in their
-        // code word (a listed ghost lies in the parent's window, so its cell mod 128 names one cell of this window or none).
-        for (uint32_t g0 = 0; g0 < n_gho; g0 += kNatThreads) {         // (scalar bounds: whole waves, the slots use ballots)
+        // Ghosts listed for the tile's parent by the hash kernel: placed by the cell in their code word (a listed ghost
+        // lies in the parent's window, so its cell mod 128 names one cell of this window or none); behind the stragglers.
+        for (uint32_t g0 = 0; g0 < n_gho; g0 += kNatThreads) {         // (scalar bounds: whole waves)
             const uint32_t gi = g0 + (uint32_t)tid;
             const bool have = gi < n_gho;
-            const uint32_t lidq = A.gho_entry[(uint64_t)pt * kGhostSlots + (have ? gi : 0u)];
-            const float2 pp = A.pos_in[lidq];
-            const float pr = A.radius[lidq];
-            const uint32_t cc = A.codes[lidq];
-            const uint32_t pid = A.order_keys[lidq];
-            const int lx = code_window_x(cc, ox), ly = code_window_y(cc, oy);
-            bool keep = have && lx < RWX && ly < RWY;
-            uint32_t sl = P + n_exc + gi;                               // the spill window: behind the stragglers
-            if constexpr (kTrim) {
-                const uint64_t mk = ballot64(keep);
-                uint32_t base = 0;
-                if (lane == 0 && mk) base = atomicAdd(&S.misc[3], (uint32_t)__popcll(mk));
-                base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
-                sl = base + popc_below_lane(mk);
-                keep = keep && sl < (uint32_t)(sizeof(S.px) / sizeof(float));
-            } else if (have && !keep) {
-                S.px[sl] = pp.x; S.py[sl] = pp.y; S.rad[sl] = pr; S.id[sl] = pid;
-                S.cell_inc(0 + 1);
-                S.hm[sl] = 0u;
-            }
-            if (keep) {
-                S.px[sl] = pp.x; S.py[sl] = pp.y; S.rad[sl] = pr; S.id[sl] = pid;
-                if constexpr (L::kLid) S.lid[sl] = lidq;
-                const int home = (ly + 1) * PX + lx + 1;
-                S.cell_inc(home + 1);
-                uint32_t over = (cc >> kCodeOverlapShift) & 0xFFu;
-                const uint32_t own = (lx >= HX && lx < HX + T && ly >= HY && ly < HY + T) ? (1u << 19) : 0u;
-                S.hm[sl] = (uint32_t)home | (over << 11) | own;
-#pragma unroll
-                for (int j = 0; j < 3; ++j) {
-                    if (over == 0) break;
-                    const int k = __ffs((int)over) - 1;
-                    over &= over - 1u;
-                    S.cell_inc(home + neighbour_offset<PX>(k) + 1);
-                }
-            }
+            take_listed(have, A.gho_entry[(uint64_t)pt * kGhostSlots + (have ? gi : 0u)], P + n_exc + gi,
+                        [&](uint32_t cc, int &lx, int &ly) { lx = code_window_x(cc, ox); ly = code_window_y(cc, oy); });
         }
     }
     __syncthreads();
@@ -1627,34 +1707,8 @@ __device__ __forceinline__ bool process_tile(L &S, const CollideArgs &A, const i
     constexpr bool kFetchEarly = T >= 32;
     uint32_t own_id[QOWN];
     float2 own_prev[QOWN];
-    if constexpr (kTrim && kFetchEarly) {
-        // Branch-free (see P1): every lane loads -- a lane without a particle of the tile reads element 0 -- and
-        // the loads of all rounds are issued before anything uses one of them, so they are in flight together and
-        // nothing waits for them before P6.
-        uint32_t fetch[QOWN];
-#pragma unroll
-        for (int q = 0; q < QOWN; ++q) {
-            const uint32_t s = (uint32_t)tid + (uint32_t)q * kNatThreads;
-            own_id[q] = 0xFFFFFFFFu;
-            fetch[q] = 0u;
-            if (q >= 2 && PS <= (uint32_t)q * kNatThreads) continue;   // (scalar: the third round is nearly always empty)
-            const uint32_t sc = min(s, PS - 1u);                       // PS >= 1 (checked behind P1)
-            const uint32_t hm = S.hm[sc];
-            const bool own = s < PS && (hm & (1u << 19)) != 0;
-            uint32_t id = S.id[sc];
-            asm volatile("" : "+v"(id));                             // keep this an LDS read (no pointer select -> flat load)
-            static_assert(!ORD || L::kLid, "order-key windows keep the local indices");
-            if constexpr (ORD) id = S.lid[sc];                         // S.id holds the order key; the local index was kept
-            own_id[q] = own ? id : 0xFFFFFFFFu;
-            fetch[q] = (own && id < n_owned) ? id : 0u;
-        }
-#pragma unroll
-        for (int q = 0; q < QOWN; ++q) {
-            own_prev[q] = make_float2(0.f, 0.f);
-            if (q >= 2 && PS <= (uint32_t)q * kNatThreads) continue;
-            if (A.fuse_verlet) own_prev[q] = A.prev[fetch[q]];
-        }
-    }
+    constexpr int QSKIP = kFetchEarly ? 2 : 1;                         // (the third round of a 32x32 tile is nearly always empty)
+    if constexpr (kTrim && kFetchEarly) fetch_own<ORD, kNatThreads, QSKIP>(S, A, tid, PS, n_owned, own_id, own_prev);
 
 #ifdef GPE_DBG_SKIP
     if (!(GPE_DBG_SKIP & 2))
@@ -1873,55 +1927,9 @@ __device__ __forceinline__ bool process_tile(L &S, const CollideArgs &A, const i
 
     // ---- P6: write the tile's own particles back ------------------------------------------------------
     const bool packs = ORD && A.pack.on != 0u;                         // (scalar) a sharded step: the tiles pack
-    if constexpr (kTrim && !kFetchEarly) {
-        uint32_t fetch[QOWN];
-#pragma unroll
-        for (int q = 0; q < QOWN; ++q) {
-            const uint32_t s = (uint32_t)tid + (uint32_t)q * kNatThreads;
-            own_id[q] = 0xFFFFFFFFu;
-            fetch[q] = 0u;
-            if (q >= 1 && PS <= (uint32_t)q * kNatThreads) continue;   // (scalar)
-            const uint32_t sc = min(s, PS - 1u);
-            const uint32_t hm = S.hm[sc];
-            const bool own = s < PS && (hm & (1u << 19)) != 0;
-            uint32_t id = S.id[sc];
-            asm volatile("" : "+v"(id));                             // keep this an LDS read (no pointer select -> flat load)
-            if constexpr (ORD) id = S.lid[sc];
-            own_id[q] = own ? id : 0xFFFFFFFFu;
-            fetch[q] = (own && id < n_owned) ? id : 0u;
-        }
-#pragma unroll
-        for (int q = 0; q < QOWN; ++q) {
-            own_prev[q] = make_float2(0.f, 0.f);
-            if (q >= 1 && PS <= (uint32_t)q * kNatThreads) continue;
-            if (A.fuse_verlet) own_prev[q] = A.prev[fetch[q]];
-        }
-    }
-    if constexpr (kTrim) {
-#pragma unroll
-        for (int q = 0; q < QOWN; ++q) {
-            if (q >= (kFetchEarly ? 2 : 1) && PS <= (uint32_t)q * kNatThreads) continue;   // (scalar, as where own_id was filled)
-            const uint32_t id = own_id[q];
-            const bool have = id != 0xFFFFFFFFu;
-            const uint32_t s = min((uint32_t)tid + (uint32_t)q * kNatThreads, (uint32_t)L::kSlots - 1u);
-            const float2 c = make_float2(S.px[s], S.py[s]);
-            const float rr = S.rad[s];
-            float2 o = c;
-            const bool mine = have && A.fuse_verlet && id < n_owned;
-            if (mine) {
-                // K12 on the resolved position: the integrated position becomes the live one, the resolved
-                // position the previous one (particle_integration.wgsl:64,76)
-                verlet_one(c.x, c.y, own_prev[q].x, own_prev[q].y, rr, A.vp, o.x, o.y);
-                A.prev[id] = c;
-                A.pos_out[id] = o;
-            } else if (have) {
-                A.pos_out[id] = c;
-            }
-            if constexpr (ORD) {
-                if (packs) pack_if_near_border(A.pack, mine, id, o, c, rr, S.id[s], A.cell_size);
-            }
-        }
-    } else
+    if constexpr (kTrim && !kFetchEarly) fetch_own<ORD, kNatThreads, QSKIP>(S, A, tid, PS, n_owned, own_id, own_prev);
+    if constexpr (kTrim) write_own_back<ORD, kNatThreads, QSKIP>(S, A, tid, PS, n_owned, packs, own_id, own_prev);
+    else
     for (uint32_t s0 = 0; s0 < PS; s0 += kNatThreads) {                // (whole waves: the pack uses ballots)
         const uint32_t s = s0 + (uint32_t)tid;
         const bool own = s < PS && (S.hm[min(s, PS - 1u)] & (1u << 19)) != 0;
@@ -2097,6 +2105,7 @@ struct TileDirect {
     float px[CAP], py[CAP], rad[CAP];
     uint32_t id[CAP];
     uint8_t own[CAP];          // the particle's home cell lies in the tile
+    __device__ __forceinline__ bool is_own(uint32_t s) const { return own[s] != 0; }
     // member slots a zone cell owns: six; an order-key (sharded) window keeps a local index per particle as well and
     // pays for it with the sixth slot (its cells of six members go to the side list and a wave, like cells of seven)
     static constexpr int kMemSlots = LID ? kDirectSlots - 1 : kDirectSlots;
@@ -2140,19 +2149,11 @@ __device__ __forceinline__ bool process_tile_direct(L &S, const CollideArgs &A, 
     const int ox = tx * TX - HX, oy = ty * TY - HY;                    // origin of the cell window
     const int box = (tx * TX - kHalo) >> 3, boy = (ty * TY - kHalo) >> 3;   // first looked-up block
     GPE_STAMP_BEGIN();
-    const uint32_t fresh_word = *A.fresh;                              // (issued here, consumed behind P0: see process_tile)
-    const uint32_t owned_word = A.counts ? A.counts[0] : (uint32_t)(A.n_owned < 0xFFFFFFFFull ? A.n_owned : 0xFFFFFFFFull);
     // stragglers handed to this tile by the hash kernel (the lists are kept per 32x32 tile: a half reads its parent's)
     static_assert(TX == 32 && (TY == 32 || TY == 16), "straggler lists, ghost lists and rosters are kept per 32x32 tile");
-    const int ptx = tx, pty = (ty * TY) >> 5;
-    const bool in_tb = A.tb.holds(ptx, pty);                           // (always, for the tiles of the dense launch)
-    const uint32_t pt = in_tb ? A.tb.index(ptx, pty) : 0u;
-    const uint32_t exc_word = (A.exc_count && in_tb) ? A.exc_count[pt] : 0u;
-    uint32_t gho_word = 0, gsort_word = 0;
-    if constexpr (ORD) {
-        if (A.ghost_sort) gsort_word = *A.ghost_sort;
-        if (A.gho_count && in_tb) gho_word = A.gho_count[pt];
-    }
+    const TileWords W = read_tile_words<ORD>(A, tx, (ty * TY) >> 5);
+    const bool in_tb = W.in_tb;
+    const uint32_t pt = W.pt;
     // the tile's roster (CollideArgs): header, and the first ids on the chance that it is valid
     constexpr bool kRoster = TX == 32 && TY == 32 && NT == 512;
     constexpr int QP = QMAX >= 2 ? 2 : 1;
@@ -2171,10 +2172,10 @@ __device__ __forceinline__ bool process_tile_direct(L &S, const CollideArgs &A, 
         for (int q = 0; q < QP; ++q) first_ids[q] = A.roster_ids[roster_base + (uint32_t)tid + (uint32_t)q * NT];
     }
 
-    // ---- P0: clear the counters, look the region's blocks up, slot -> block map (as process_tile) ------------------
+    // ---- P0: clear the counters, look the region's blocks up, slot -> block map ------------------------------------
     for (int i = tid; i < (NZ + 1) / 2; i += NT) S.cntw[i] = 0;
     if (tid < 12) S.lcnt[tid] = 0;
-    const bool stale = __builtin_amdgcn_readfirstlane((int)fresh_word) == 0;
+    const bool stale = __builtin_amdgcn_readfirstlane((int)W.fresh) == 0;
     if constexpr (kRoster && HINTS) {
         // A hinted tile (kCtlHints): two of the launch's first workgroups redo it as halves.  (In front of every other way
         // out: a sharded tile must not be taken twice -- it would pack its particles twice.)
@@ -2185,7 +2186,7 @@ __device__ __forceinline__ bool process_tile_direct(L &S, const CollideArgs &A, 
         // a ghost list ran over this step: the ghosts come through their block table, which only the counting-sort
         // windows of the over-capacity launch look up -- hand the tile on (a crowded border; the host's `crowded` policy
         // moves such scenes to those windows altogether)
-        if (A.gho_count == nullptr || __builtin_amdgcn_readfirstlane((int)gsort_word) != 0) return false;
+        if (A.gho_count == nullptr || __builtin_amdgcn_readfirstlane((int)W.gsort) != 0) return false;
     }
     const uint32_t stamp_now = (uint32_t)__builtin_amdgcn_readfirstlane((int)sorts_word) + 1u;
     // (scalar) the roster is of the table in use: no lookup
@@ -2200,61 +2201,18 @@ __device__ __forceinline__ bool process_tile_direct(L &S, const CollideArgs &A, 
             if (wmax > kWindowReport) atomicMax(&A.tile_ctl[kCtlWindowMax], wmax);
         }
     } else {
-    if (tid == 0) S.misc[5] = 0;
-    if (tid < VB) {
-        const int rb = tid % NBLK;
-        const int bi = rb % NBX, bj = rb / NBX;
-        const int lbx = box + bi - A.bx0, lby = boy + bj - A.by0;
-        uint32_t start = 0, count = 0;
-        const uint2 *tab = A.table;
-        if (tab && lbx >= 0 && lby >= 0 && lbx < A.blocks_x && lby < A.blocks_y) {
-            const uint32_t mb = (uint32_t)(lby * A.blocks_x + lbx);
-            if (mb < A.entries) {
-                const uint2 se = tab[mb];                            // empty blocks hold (0xFFFFFFFF, 0)
-                if (se.y > se.x) { start = se.x; count = se.y - se.x; }
-            }
-        }
-        S.bstart[tid] = start;
-        S.bcnt[tid] = count;
-    }
-    __syncthreads();
-    if (tid < 64) {
-        uint32_t carry = 0;
-        for (int base = 0; base < VB; base += 64) {
-            const int b = base + lane;
-            const uint32_t cb = (b < VB) ? S.bcnt[b] : 0u;
-            const uint32_t inc = wave_inclusive_scan(cb);
-            if (b < VB) S.boff[b] = carry + inc - cb;
-            carry += (uint32_t)__builtin_amdgcn_readlane((int)inc, 63);
-        }
-        if (lane == 0) { S.boff[VB] = carry; S.misc[0] = carry; S.misc[2] = 0; S.misc[3] = 0; S.misc[4] = 0; }
-        {                                                              // particles in the tile's own blocks (misc[1])
-            static_assert(NBLK <= 64, "one lane per block");
-            const int bi = lane % NBX, bj = lane / NBX;
-            const bool own_blk = lane < NBLK && bi >= 1 && bi < NBX - 1 && bj >= 1 && bj < NBY - 1;
-            uint32_t v = 0;
-            if (own_blk) v = S.bcnt[lane];
-            const uint32_t own = wave_sum(v);                          // (all 64 lanes of wave 0 take part)
-            if (lane == 0) S.misc[1] = own;
-        }
-    } else if (tid < 64 + (NBX - 2) * (NBY - 2)) {
-        const int wi = (tid - 64) % (NBX - 2), wj = (tid - 64) / (NBX - 2);
-        uint32_t w = 0;
-#pragma unroll
-        for (int dj = 0; dj < 3; ++dj)
-#pragma unroll
-            for (int di = 0; di < 3; ++di) w += S.bcnt[(wj + dj) * NBX + wi + di];
-        if (w > kWindowReport) atomicMax(&A.tile_ctl[kCtlWindowMax], w);
-        if (record && w > kWindowReport) atomicMax(&S.misc[5], w);
-    }
-    __syncthreads();
+        if (tid == 0) S.misc[5] = 0;
+        look_blocks_up<NBX, NBY, false>(S, A, tid, box, boy, 0u);
+        __syncthreads();
+        scan_blocks<NBX, NBY, VB, 4u | 8u | 16u>(S, A, tid, record ? &S.misc[5] : nullptr);
+        __syncthreads();
     }
     const uint32_t P = listed ? (uint32_t)__builtin_amdgcn_readfirstlane((int)hdr.x)
                               : (uint32_t)__builtin_amdgcn_readfirstlane((int)S.misc[0]);
-    const uint32_t n_owned = (uint32_t)__builtin_amdgcn_readfirstlane((int)owned_word);
+    const uint32_t n_owned = (uint32_t)__builtin_amdgcn_readfirstlane((int)W.owned);
     const uint32_t straggler_bit = stale ? kCodeStraggler : 0u;
-    const uint32_t n_exc = stale ? min((uint32_t)__builtin_amdgcn_readfirstlane((int)exc_word), kExcSlots) : 0u;
-    const uint32_t n_gho = ORD ? min((uint32_t)__builtin_amdgcn_readfirstlane((int)gho_word), kGhostSlots) : 0u;   // listed ghosts
+    const uint32_t n_exc = stale ? min((uint32_t)__builtin_amdgcn_readfirstlane((int)W.exc), kExcSlots) : 0u;
+    const uint32_t n_gho = ORD ? min((uint32_t)__builtin_amdgcn_readfirstlane((int)W.gho), kGhostSlots) : 0u;   // listed ghosts
     if (record && tid == 0) {
         // the header of the roster the gather below writes (an empty lookup is a valid, empty roster)
         const uint32_t count = P > (uint32_t)L::RAWCAP ? 0xFFFFFFFFu : P;
@@ -2268,13 +2226,7 @@ __device__ __forceinline__ bool process_tile_direct(L &S, const CollideArgs &A, 
         if (stale ? (P == 0 && any_exc == 0) : (S.misc[1] == 0 && !(record && P != 0))) return true;
     }
     if (P > (uint32_t)L::RAWCAP) { GPE_BAIL(1); return false; }        // more looked-up particles than slots
-    if (!listed) {
-        constexpr int SHARE = (NT / VB) > 0 ? (NT / VB) : 1;
-        for (int b = tid % VB, sub = tid / VB; sub < SHARE && b < VB; b += NT) {
-            const uint32_t lo = S.boff[b], hi = S.boff[b + 1];
-            for (uint32_t i = lo + sub; i < hi; i += SHARE) S.sblk[i] = (uint8_t)b;
-        }
-    }
+    if (!listed) map_slots_to_blocks<NT, VB>(S, tid);
     __syncthreads();
     GPE_STAMP(0);
 
@@ -2364,7 +2316,6 @@ __device__ __forceinline__ bool process_tile_direct(L &S, const CollideArgs &A, 
         bool keep[QP];
         uint32_t slot[QP];
         uint64_t mq[QP];
-        uint32_t cnt = 0;
 #pragma unroll
         for (int q = 0; q < QP; ++q) {
             const uint32_t s = s0 + (uint32_t)tid + (uint32_t)q * NT;
@@ -2376,51 +2327,39 @@ __device__ __forceinline__ bool process_tile_direct(L &S, const CollideArgs &A, 
             // range has shrunk below: those particles are ghosts now, or gone; they come through the ghost list, or not at all)
             if constexpr (ORD) mq[q] &= ballot64(lidq[q] < n_owned);
             keep[q] = lanes_of(mq[q]);
-            cnt += (uint32_t)__popcll(mq[q]);
         }
-        uint32_t base = 0;
-        if (lane == 0 && cnt) base = atomicAdd(&S.misc[3], cnt);       // kept particles get consecutive slots
-        base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
-#pragma unroll
-        for (int q = 0; q < QP; ++q) {
-            slot[q] = base + popc_below_lane(mq[q]);
-            base += (uint32_t)__popcll(mq[q]);
-            keep[q] = keep[q] && slot[q] < (uint32_t)L::kSlots;          // over capacity: handed on below
-        }
+        take_slots(&S.misc[3], lane, (uint32_t)L::kSlots, mq, slot, keep);   // (over capacity: handed on below)
 #pragma unroll
         for (int q = 0; q < QP; ++q)
             if (keep[q]) insert(slot[q], pp[q], pr[q], pid[q], lidq[q], lxq[q], lyq[q], ph[q]);
     }
-    if (n_exc != 0 && tid < 64) {                                      // stragglers handed to the tile (see process_tile)
-        const bool have = (uint32_t)tid < n_exc;
-        const uint2 en = A.exc_entry[(uint64_t)pt * kExcSlots + (have ? (uint32_t)tid : 0u)];
-        uint32_t pid = en.x;
-        const float2 pp = A.pos_in[pid];
-        const float pr = A.radius[pid];
-        const uint32_t cc = A.codes[pid];
-        const uint32_t lidq = pid;
-        if constexpr (ORD) pid = A.order_keys[pid];
-        const int lx = (int)(en.y & 0xFFFFu) - ox, ly = (int)(en.y >> 16) - oy;
+    // One entry of a list the hash kernel handed to the tile -- a straggler, a listed ghost: fetched, placed by its cell
+    // (`cell_of`: the entry's or the code word's), given a slot, filed.  (Called by whole waves: the slots use ballots.)
+    auto take_listed = [&](const bool have, const uint32_t lidv, auto cell_of) {
+        const float2 pp = A.pos_in[lidv];
+        const float pr = A.radius[lidv];
+        const uint32_t cc = A.codes[lidv];
+        uint32_t pid = lidv;
+        if constexpr (ORD) pid = A.order_keys[lidv];
+        int lx, ly;
+        cell_of(cc, lx, ly);
         const uint64_t mk = ballot64(have) & ballot64((uint32_t)lx < (uint32_t)RWX) & ballot64((uint32_t)ly < (uint32_t)RWY);
         bool keep = lanes_of(mk);
         const uint32_t sl = take_slots(&S.misc[3], lane, (uint32_t)L::kSlots, mk, keep);
-        if (keep) insert(sl, pp, pr, pid, lidq, lx, ly, phantoms_of(cc));
+        if (keep) insert(sl, pp, pr, pid, lidv, lx, ly, phantoms_of(cc));
+    };
+    if (n_exc != 0 && tid < 64) {                                      // stragglers: out of reach of the block that lists them
+        const bool have = (uint32_t)tid < n_exc;
+        const uint2 en = A.exc_entry[(uint64_t)pt * kExcSlots + (have ? (uint32_t)tid : 0u)];
+        take_listed(have, en.x, [&](uint32_t, int &lx, int &ly) { lx = (int)(en.y & 0xFFFFu) - ox; ly = (int)(en.y >> 16) - oy; });
     }
     if constexpr (ORD) {
-        // ghosts listed for the tile by the hash kernel (see process_tile)
-        for (uint32_t g0 = 0; g0 < n_gho; g0 += (uint32_t)NT) {        // (scalar bounds: whole waves, the slots use ballots)
+        // the ghosts listed for the tile: placed by the cell in their code word
+        for (uint32_t g0 = 0; g0 < n_gho; g0 += (uint32_t)NT) {        // (scalar bounds: whole waves)
             const uint32_t gi = g0 + (uint32_t)tid;
             const bool have = gi < n_gho;
-            const uint32_t lidq = A.gho_entry[(uint64_t)pt * kGhostSlots + (have ? gi : 0u)];
-            const float2 pp = A.pos_in[lidq];
-            const float pr = A.radius[lidq];
-            const uint32_t cc = A.codes[lidq];
-            const uint32_t pid = A.order_keys[lidq];
-            const int lx = code_window_x(cc, ox), ly = code_window_y(cc, oy);
-            const uint64_t mk = ballot64(have) & ballot64(lx < RWX) & ballot64(ly < RWY);
-            bool keep = lanes_of(mk);
-            const uint32_t sl = take_slots(&S.misc[3], lane, (uint32_t)L::kSlots, mk, keep);
-            if (keep) insert(sl, pp, pr, pid, lidq, lx, ly, phantoms_of(cc));
+            take_listed(have, A.gho_entry[(uint64_t)pt * kGhostSlots + (have ? gi : 0u)],
+                        [&](uint32_t cc, int &lx, int &ly) { lx = code_window_x(cc, ox); ly = code_window_y(cc, oy); });
         }
     }
     __syncthreads();
@@ -2431,36 +2370,11 @@ __device__ __forceinline__ bool process_tile_direct(L &S, const CollideArgs &A, 
     const uint32_t n_big = (uint32_t)__builtin_amdgcn_readfirstlane((int)S.misc[4]);
     if (n_big > (uint32_t)L::kBig) { GPE_BAIL(3); return false; }      // crowded cells: process_tile's windows take it
 
-    // the tile's own particles and their previous positions: fetched here, used in P6 (as process_tile)
+    // the tile's own particles and their previous positions: fetched here, used in P6
     constexpr int QOWN = (L::kSlots + NT - 1) / NT;
     uint32_t own_id[QOWN];
     float2 own_prev[QOWN];
-    {
-        uint32_t fetch[QOWN];
-#pragma unroll
-        for (int q = 0; q < QOWN; ++q) {
-            const uint32_t s = (uint32_t)tid + (uint32_t)q * NT;
-            own_id[q] = 0xFFFFFFFFu;
-            fetch[q] = 0u;
-            if (q >= 1 && PS <= (uint32_t)q * NT) continue;   // (scalar)
-            const uint32_t sc = min(s, PS - 1u);
-            const bool own = s < PS && S.own[sc] != 0;
-            uint32_t id = S.id[sc];
-            asm volatile("" : "+v"(id));                             // keep this an LDS read (no pointer select -> flat load)
-            if constexpr (ORD) id = S.lid[sc];
-            own_id[q] = own ? id : 0xFFFFFFFFu;
-            fetch[q] = (own && id < n_owned) ? id : 0u;
-        }
-#pragma unroll
-        for (int q = 0; q < QOWN; ++q) {
-            own_prev[q] = make_float2(0.f, 0.f);
-            if (q >= 1 && PS <= (uint32_t)q * NT) continue;
-#ifdef GPE_DBG_SKIP
-            if (GPE_DBG_SKIP & 32) continue;
-#endif
-            if (A.fuse_verlet) own_prev[q] = A.prev[fetch[q]];
-        }
-    }
+    fetch_own<ORD, NT, 1>(S, A, tid, PS, n_owned, own_id, own_prev);
 
     // ---- P4: active cells per colour (the walk of process_tile over the 2 x 2 colour groups; a cell's member count is
     //          its counter).  List entry: zone cell | class data << 12: cells of 2-3 members (one lane each; bit 12: three)
@@ -2586,32 +2500,8 @@ __device__ __forceinline__ bool process_tile_direct(L &S, const CollideArgs &A, 
         GPE_STAMP(9 + k);
     }
 
-    // ---- P6: write the tile's own particles back, K12 applied (as process_tile) ---------------------------------------
-#pragma unroll
-    for (int q = 0; q < QOWN; ++q) {
-#ifdef GPE_DBG_SKIP
-        if (GPE_DBG_SKIP & 32) continue;
-#endif
-        if (q >= 1 && PS <= (uint32_t)q * NT) continue;                  // (scalar, as where own_id was filled)
-        const uint32_t id = own_id[q];
-        const bool have = id != 0xFFFFFFFFu;
-        const uint32_t s = min((uint32_t)tid + (uint32_t)q * NT, (uint32_t)L::kSlots - 1u);
-        const float2 c = make_float2(S.px[s], S.py[s]);
-        const float rr = S.rad[s];
-        float2 o = c;
-        const bool mine = have && A.fuse_verlet && id < n_owned;
-        if (mine) {
-            verlet_one(c.x, c.y, own_prev[q].x, own_prev[q].y, rr, A.vp, o.x, o.y);
-            A.prev[id] = c;
-            A.pos_out[id] = o;
-        } else if (have) {
-            A.pos_out[id] = c;
-        }
-        if constexpr (ORD) {
-            // a sharded step: the tiles pack their own particles for the neighbours (S.id holds the order key)
-            if (A.pack.on) pack_if_near_border(A.pack, mine, id, o, c, rr, S.id[s], A.cell_size);
-        }
-    }
+    // ---- P6: write the tile's own particles back, K12 applied ----------------------------------------------------------
+    write_own_back<ORD, NT, 1>(S, A, tid, PS, n_owned, ORD && A.pack.on != 0u, own_id, own_prev);
     __syncthreads();
     GPE_STAMP(6);
     return true;
@@ -2713,11 +2603,7 @@ __global__ __launch_bounds__(NT, 8) void k_collide_direct(CollideArgs A)
             const int hy = hty * 2 + (int)(wg & 1u);
             const bool done = process_tile_direct<ORD>(*reinterpret_cast<Half *>(&S), A, htx, hy);
             if (threadIdx.x == 0) {
-                if (!done) {
-                    const uint32_t slot = atomicAdd(&A.tile_ctl[kCtlOverflow2], 1u);
-                    if (slot < 2u * A.overflow1_cap) A.overflow2[slot] = ((uint32_t)hy << 16) | (uint32_t)htx;
-                    else atomicOr(&A.tile_ctl[kCtlError], kErrTileOverflow);
-                }
+                if (!done) hand_tile_on(A, kCtlOverflow2, A.overflow2, 2u * A.overflow1_cap, htx, hy);
                 // again in the next launch, kHintAge launches long
                 if ((wg & 1u) == 0u && age + 1u < kHintAge) hint_tile(A, htx, hty, age + 1u);
             }
@@ -2739,11 +2625,7 @@ __global__ __launch_bounds__(NT, 8) void k_collide_direct(CollideArgs A)
 #endif
     if (!done) {
         // (the launch that takes the tile off list 1 -- half tiles or over-capacity windows -- registers it: kCtlHints)
-        if (threadIdx.x == 0) {
-            const uint32_t slot = atomicAdd(&A.tile_ctl[kCtlOverflow1], 1u);
-            if (slot < A.overflow1_cap) A.overflow1[slot] = ((uint32_t)ty << 16) | (uint32_t)tx;
-            else atomicOr(&A.tile_ctl[kCtlError], kErrTileOverflow);
-        }
+        if (threadIdx.x == 0) hand_tile_on(A, kCtlOverflow1, A.overflow1, A.overflow1_cap, tx, ty);
     }
 }
 
@@ -2787,11 +2669,7 @@ __global__ __launch_bounds__(kNatThreads, 2048 / kNatThreads * 2) void k_collide
     // here, quarter by quarter, on steps whose statistics let the host skip that launch: the extra code costs this
     // kernel 3 % at 1 M and 5 % at 100 M, more than the 4.5 us launch: profiles/r02/ab_inline_fallback_rejected.txt.)
     if (!process_tile<ORD>(S, A, tx, ty)) {
-        if (threadIdx.x == 0) {
-            const uint32_t slot = atomicAdd(&A.tile_ctl[kCtlOverflow1], 1u);
-            if (slot < A.overflow1_cap) A.overflow1[slot] = ((uint32_t)ty << 16) | (uint32_t)tx;
-            else atomicOr(&A.tile_ctl[kCtlError], kErrTileOverflow);
-        }
+        if (threadIdx.x == 0) hand_tile_on(A, kCtlOverflow1, A.overflow1, A.overflow1_cap, tx, ty);
     }
 }
 
@@ -2820,11 +2698,7 @@ __global__ __launch_bounds__(512, 6) void k_collide_halves(CollideArgs A)
         if ((i & 1u) == 0u && threadIdx.x == 0) hint_tile(A, tx, (int)(parent >> 16));   // (for the next dense launch: kCtlHints)
         const bool done = process_tile_direct<ORD>(S, A, tx, ty);
         __syncthreads();
-        if (!done && threadIdx.x == 0) {
-            const uint32_t slot = atomicAdd(&A.tile_ctl[kCtlOverflow2], 1u);
-            if (slot < 2u * A.overflow1_cap) A.overflow2[slot] = ((uint32_t)ty << 16) | (uint32_t)tx;
-            else atomicOr(&A.tile_ctl[kCtlError], kErrTileOverflow);
-        }
+        if (!done && threadIdx.x == 0) hand_tile_on(A, kCtlOverflow2, A.overflow2, 2u * A.overflow1_cap, tx, ty);
     }
 }
 

@@ -783,6 +783,51 @@ def test_stragglers_flying_into_empty_space_are_not_lost(gpe, oracle):
     st.close(); sim.close()
 
 
+def _blob_with_fast_arrivals(cell, world):
+    """The sparse background of test_native_crushed_cells_are_exact (1500 particles per 40 x 40) with one blob of 1600
+    particles inside the cell (19, 11) -- the middle of its 8x8-cell block, so that what the blob throws out at step 0 is
+    still within the kept table's reach at step 1 -- and eight particles 6.8 to 7.6 cells left and right of it, each moving
+    its whole distance per step towards the blob: across kDriftLeft / kDriftRight, whatever their block.
+    (Measured on the MI355X with the 40 x 40 world and 1100 particles in the blob: the block keys of so small a world sort
+    in one radix pass, which never keeps its table -- native_sorts 2, 3, 4 after the three steps -- and the blob's 8x8
+    window holds 1348 particles, by the CPU oracle's count, of the 1600 it has room for -- overflow_tiles 1,
+    overflow_spills 0.  Hence 200 x 200, two passes, and 1600: the oracle counts 1746 particles in that window at step 1
+    and 9 stragglers in the tile.)"""
+    rng = np.random.default_rng(21)
+    bg = (rng.random((1500 * 25, 2), dtype=np.float32) * np.float32(world)).astype(np.float32)
+    corner = np.array((19, 11), np.float32) * np.float32(cell) + np.float32(0.1)
+    blob = corner + rng.random((1600, 2), dtype=np.float32) * np.float32(0.9)
+    off = np.array([(7, 0), (7, 1), (7.5, -1), (6.5, 2), (-7, 0), (-7, 1), (-7.5, -1), (-7, -2)], np.float32) * np.float32(cell)
+    fast = (corner + np.float32(0.45) + off).astype(np.float32)
+    pos = np.concatenate([bg, blob, fast]).astype(np.float32)
+    prev = pos.copy()
+    prev[-8:] = fast + off
+    return pos, prev
+
+
+def test_stragglers_reach_a_spill_arena_window(gpe, oracle):
+    """Stragglers filed into a window whose particle arrays lie in the global spill arena (slots behind the looked-up
+    ones; those outside the window under ring cell 0): the blob's 8x8 sub-tile overflows both LDS windows, and at step 1
+    -- the table of step 0 is kept -- eight fast particles arrive next to it through its parent's straggler list, eight
+    of the list's sixteen slots.  Same bits as the oracle after every step."""
+    world = (200.0, 200.0)
+    pos, prev = _blob_with_fast_arrivals(oracle.compute_cell_size(0.5), world[0])
+    rad = np.full(len(pos), 0.5, np.float32)
+    st = _native(gpe, pos, rad, world, flags=gpe._lib.FLAG_NATIVE_FORCE, prev=prev)
+    sim = oracle.Sim(pos, rad, oracle.default_params(world[0], world[1], 0.5), prev=prev)
+    sorts = []
+    for s in range(3):
+        st.update(1 / 60, resort=(s == 0)); sim.step(1 / 60, resort=(s == 0))
+        _assert_positions(st.positions(), sim.pos, "stragglers into a spill window, step %d" % s)
+        sorts.append(st.ctx.pipeline_info()["native_sorts"])
+    st.ctx.sync()
+    info = st.ctx.pipeline_info()
+    print("native_sorts per step", sorts, info)
+    assert info["overflow_spills"] > 0, info              # (lagged by a step: the windows of step 1)
+    assert sorts[1] == sorts[0], sorts                    # step 1 kept the table: the fast particles came through the list
+    st.close(); sim.close()
+
+
 def test_roster_stamp_follows_every_sort(gpe):
     """The tile rosters (ids written down by the tiles of a sort step) are valid only under the sort count they were
     stamped with; the tiles compare against their own copy of that count, which every sort must bump -- whoever ran it:
