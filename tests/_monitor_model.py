@@ -111,7 +111,8 @@ def same(got, want, exact_sums=False, skip=()):
 
 
 class MonitorModel:
-    """Wraps an OracleModel: drive the steps through step() / run() here, everything else on the model itself."""
+    """Wraps an OracleModel: drive the steps through step() / run() here -- or step the model itself and call after_step()
+    after each step, as tests/_interactive_sequences.py does -- and everything else on the model itself."""
 
     def __init__(self, model, every=1, frames=1024, rest_speed=0.0):
         assert every >= 1 and frames >= 1 and rest_speed >= 0.0
@@ -127,11 +128,15 @@ class MonitorModel:
         self.ring.append(measure(pos, prev, m.uids, m.world, self.rest_speed, step=self.steps_seen))
         self.recorded += 1
 
-    def step(self, dt, resort=False):
-        self.m.step(dt, resort=resort)
+    def after_step(self):
+        """The model has made one step (whoever drove it): count it, and take a frame on every every-th."""
         self.steps_seen += 1
         if self.steps_seen % self.every == 0:
             self.sample()
+
+    def step(self, dt, resort=False):
+        self.m.step(dt, resort=resort)
+        self.after_step()
 
     def run(self, dt, steps, resort_every=0, resort_first=True):
         for s in range(steps):

@@ -33,7 +33,8 @@ def frame_of(uids, pos, prev, tracked):
 
 
 class TracerModel:
-    """Wraps an OracleModel: drive the steps through step() / run() here, everything else on the model itself."""
+    """Wraps an OracleModel: drive the steps through step() / run() here -- or step the model itself and call after_step()
+    after each step, as tests/_interactive_sequences.py does -- and everything else on the model itself."""
 
     def __init__(self, model, uids, every=1, frames=1024):
         self.m = model
@@ -54,11 +55,15 @@ class TracerModel:
         self.ring.append((self.steps_seen,) + frame_of(m.uids, pos, prev, self.tracked))
         self.recorded += 1
 
-    def step(self, dt, resort=False):
-        self.m.step(dt, resort=resort)
+    def after_step(self):
+        """The model has made one step (whoever drove it): count it, and take a frame on every every-th."""
         self.steps_seen += 1
         if self.steps_seen % self.every == 0:
             self.sample()
+
+    def step(self, dt, resort=False):
+        self.m.step(dt, resort=resort)
+        self.after_step()
 
     def run(self, dt, steps, resort_every=0, resort_first=True):
         for s in range(steps):

@@ -125,3 +125,58 @@ def test_every_workspace_releases_exactly_what_it_reserves():
         freed = re.findall(r"dev_free\(c, [\w>.-]*?(\w+)\)", _body(code, release))
         assert len(freed) == len(set(freed)) and set(freed) == reserved and reserved, (prefix, sorted(reserved), sorted(freed))
         assert re.search(r"\b%s\(c\)" % release.split("::")[-1], callers), release
+
+
+# ---- the hand-kept pairing of the uid map's validity and the tracers' slot table --------------------------------------
+def _statements(code):
+    """(statement, the statement after it) of a source without comments: split at ';', braces dropped, blanks folded."""
+    parts = [" ".join(p.replace("{", " ").replace("}", " ").split()) for p in code.split(";")]
+    return list(zip(parts, parts[1:] + [""]))
+
+
+def unpaired_map_invalidations(csrc=CSRC):
+    """Where csrc/*.hip clears uid.map_valid (outside uid_map_build, whose callers decide), or sets it true outside
+    uid_map_ready (which rebuilds the map of uids that have not changed), without `tracers.stale = true` as the next
+    statement: [(file, statement)].  A site that forgets it lets later frames read rows through the storage indices of
+    an older order, and past n after a removal (gpe_internal.h, TracerState::stale)."""
+    bad, sites = [], 0
+    for path in sorted(glob.glob(os.path.join(csrc, "*.hip"))):
+        code = _code(path)
+        for fn in ("uid_map_build", "uid_map_ready"):
+            if re.search(r"^[\w:<> \*]*\b%s\([^{;]*\)\n\{" % fn, code, flags=re.M):
+                code = code.replace(_body(code, fn), "")
+        for stmt, after in _statements(code):
+            if re.search(r"\bmap_valid\s*=\s*(false|true)$", stmt):
+                sites += 1
+                if not re.search(r"\btracers\.stale\s*=\s*true$", after):
+                    bad.append((os.path.basename(path), stmt))
+    return bad, sites
+
+
+def test_every_map_invalidation_marks_the_tracers_slot_table_stale():
+    """Every `map_valid = false` outside uid_map_build, and the one `map_valid = true` outside uid_map_ready
+    (gpe_set_uids, whose map is that of new uids), is followed at once by `tracers.stale = true`.  Deleting any one of
+    those lines from a copy of the sources makes unpaired_map_invalidations() name the site (tried with each in turn)."""
+    bad, sites = unpaired_map_invalidations()
+    assert not bad, bad
+    assert sites >= 8, sites                # (seven clear it, gpe_set_uids sets it; gpe_tracers_begin's own stale = true has no pair)
+
+
+def test_the_pairing_check_notices_each_missing_line(tmp_path):
+    """The check above on copies of csrc/ with one `tracers.stale = true` line after a map_valid assignment removed:
+    each copy fails, and names one site."""
+    lines = {}
+    for path in sorted(glob.glob(os.path.join(CSRC, "*.hip"))):
+        src = open(path).read().split("\n")
+        for i, line in enumerate(src):
+            if re.search(r"tracers\.stale = true;", line) and i and re.search(r"map_valid = (false|true);", src[i - 1]):
+                lines[(path, i)] = src
+    assert len(lines) >= 8, len(lines)
+    for n, ((path, i), src) in enumerate(sorted(lines.items())):
+        copy = tmp_path / ("csrc_%d" % n)
+        copy.mkdir()
+        for other in glob.glob(os.path.join(CSRC, "*.hip")):
+            text = open(other).read() if other != path else "\n".join(src[:i] + src[i + 1:])
+            (copy / os.path.basename(other)).write_text(text)
+        bad, _ = unpaired_map_invalidations(str(copy))
+        assert len(bad) == 1 and bad[0][0] == os.path.basename(path), (path, i, bad)

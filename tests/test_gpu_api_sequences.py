@@ -277,6 +277,35 @@ def test_random_interactive_sequences_match_the_oracle(gpe, oracle, seed, mode_n
         run.close()
 
 
+@pytest.mark.parametrize("seed", interactive.SEEDS)
+@pytest.mark.parametrize("mode_name", ["native", "compat"])
+def test_random_observed_sequences_match_the_oracle(gpe, oracle, seed, mode_name):
+    """The sequences of the test above with the observers in them (interactive.plan_observed: the same operations, and
+    some 150 more between them): the tracer recorder and the run monitor armed all along, with different `every`, ended
+    and begun anew three times and around every save / load; a frame and a gpe_tracers_read straight after each thing
+    that leaves the tracers' slot table stale; frames and reads of both across the growth, the spell in the other mode,
+    the shrunken world, teleports, stops, edits outside the world and kicks; rings that wrap; consuming reads; reads at
+    capacities below, at and above the held count into sentinel-filled arrays; the refused begins; gpe_measure; and
+    gpe_cast_rays, gpe_query_segment and gpe_query_nearest straight after the growth, the shrink, a removal, a radius
+    edit and a grid override, and in the other mode.  Every frame, record, hit, row and neighbour equals the models of
+    tests/_tracers_model.py, _monitor_model.py, _ray_model.py and _nearest_model.py (the monitor's five sums within the
+    header's bound, everything else bit for bit); none of these calls moves a counter or a particle; and the sequence
+    reached what tests/test_interactive_sequences_cpu.py says it reaches."""
+    run = interactive.ObservedSequence(interactive.plan_observed(seed), oracle, gpe=gpe, mode_name=mode_name, compare=_compare)
+    try:
+        run.run()
+        print("\nobserved seed %d %s: %d ops, native %d / compat %d steps, %d particles at the end; coverage %s" % (
+            seed, mode_name, len(run.plan.ops), run.native_steps, run.compat_steps, len(run.model), dict(run.cov)))
+        if mode_name == "native":
+            assert run.native_steps > 0, run.log
+        else:
+            assert run.compat_steps > 0, run.log
+        run.cov.check(run.plan.spawn_flags)
+        run.cov.check_observed()
+    finally:
+        run.close()
+
+
 # ------------------------------------------------------------------------------------------------------------------------
 # 2. an understated grid radius: 2r > cell size, a particle overlaps up to eight neighbour cells and keeps three
 # ------------------------------------------------------------------------------------------------------------------------

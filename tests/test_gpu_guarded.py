@@ -391,7 +391,9 @@ SEQUENCES = _cases(
     + [("against-the-oracle-%s-%d" % (m, s), "test_gpu_api_sequences", "test_random_api_sequences_match_the_oracle", dict(seed=s, mode_name=m))
        for m, s in (("native", 1), ("native", 2), ("compat", 2))]
     + [("interactive-%s-%d" % (m, s), "test_gpu_api_sequences", "test_random_interactive_sequences_match_the_oracle", dict(seed=s, mode_name=m))
-       for m, s in (("native", 1), ("native", 2), ("compat", 2))])
+       for m, s in (("native", 1), ("native", 2), ("compat", 2))]
+    + [("observed-%s-%d" % (m, s), "test_gpu_api_sequences", "test_random_observed_sequences_match_the_oracle", dict(seed=s, mode_name=m))
+       for m, s in (("native", 1), ("compat", 2))])
 
 _LG = "test_local_group_in_one_process_equals_single_context"
 SHARDED = _cases(
