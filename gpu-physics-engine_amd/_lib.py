@@ -47,6 +47,7 @@ TRACER_POS, TRACER_PREV, TRACER_INDEX = 1, 2, 4
 TRACERS_CONSUME = 1
 MONITOR_CONSUME = 1
 NEAREST_MAX_M = 64
+COLLIDERS_MAX = 4096
 EDIT_BY_INDEX, EDIT_BY_UID = 0, 1
 CLUSTER_BY_INDEX, CLUSTER_BY_UID = 0, 1
 VEL_ADD, VEL_SET, VEL_SCALE = 0, 1, 2
@@ -206,6 +207,19 @@ class GpeMonitorFrames(C.Structure):
                 ("recorded", C.c_uint64), ("frames", C.POINTER(GpeMeasures))]
 
 
+class GpeCollider(C.Structure):
+    """gpe_collider: a capsule, the segment a -> b thickened by radius; flags 0.  24 bytes."""
+    _fields_ = [("ax", C.c_float), ("ay", C.c_float), ("bx", C.c_float), ("by", C.c_float), ("radius", C.c_float),
+                ("flags", C.c_uint32)]
+
+
+class GpeCollidersInfo(C.Structure):
+    """gpe_colliders_info: in struct_size; out the colliders set, the passes run and particles moved since the last
+    gpe_set_colliders, the lookup grid in use and its (cell, collider) entries."""
+    _fields_ = [("struct_size", C.c_uint32), ("k", C.c_uint32), ("passes", C.c_uint64), ("pushed", C.c_uint64),
+                ("grid_x", C.c_uint32), ("grid_y", C.c_uint32), ("list_entries", C.c_uint64)]
+
+
 class GpeParticleEdit(C.Structure):
     """gpe_particle_edit: in struct_size / key_kind / k / keys and the field arrays (each may be NULL), out edited."""
     _fields_ = [("struct_size", C.c_uint32), ("key_kind", C.c_uint32), ("k", C.c_uint64),
@@ -268,6 +282,10 @@ SYMBOLS = [
     ("gpe_monitor_sample", _I32, [_VP]),
     ("gpe_monitor_read", _I32, [_VP, C.POINTER(GpeMonitorFrames)]),
     ("gpe_monitor_end", _I32, [_VP]),
+    ("gpe_set_colliders", _I32, [_VP, C.POINTER(GpeCollider), _U64]),
+    ("gpe_get_colliders", _I32, [_VP, C.POINTER(GpeCollider), _U64, C.POINTER(_U64)]),
+    ("gpe_apply_colliders", _I32, [_VP]),
+    ("gpe_get_colliders_info", _I32, [_VP, C.POINTER(GpeCollidersInfo)]),
     ("gpe_query_circle", _I32, [_VP, _F, _F, _F, C.POINTER(GpeQueryResult)]),
     ("gpe_query_box", _I32, [_VP, _F, _F, _F, _F, C.POINTER(GpeQueryResult)]),
     ("gpe_pick", _I32, [_VP, _F, _F, C.POINTER(GpeQueryResult)]),

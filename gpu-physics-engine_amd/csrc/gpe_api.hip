@@ -1,6 +1,6 @@
 // gpe_api.hip -- the extern "C" boundary of include/gpe.h: context, device memory, particle buffers, set / add / remove,
 // uids, step ordering, downloads, profiling.  The queries are in gpe_queries.hip, the checked add, edits and kicks in
-// gpe_edits.hip, the tracers and the monitor in gpe_observe.hip.  All device work goes to one in-order hipStream per context.
+// gpe_edits.hip, the tracers and the monitor in gpe_observe.hip, the static colliders in gpe_colliders.hip.  All device work goes to one in-order hipStream per context.
 #include <math.h>
 #include <stddef.h>
 #include <stdlib.h>
@@ -896,6 +896,7 @@ gpe_status gpe_destroy(gpe_ctx *c)
     if (c->trace_origin) (void)hipEventDestroy(c->trace_origin);
     free_particle_buffers(c);
     observers_release(c);
+    colliders_release(c);
     sort_release(c);
     scan_release(c);
     onesweep_release(c);
@@ -1357,6 +1358,7 @@ gpe_status gpe_step(gpe_ctx *c, float dt, uint32_t flags)
     GPE_TRY(need_particles(c));
     GPE_HIP(c, hipSetDevice(c->device));
     GPE_TRY(do_step(c, dt, flags));
+    GPE_TRY(colliders_after_step(c));
     return observers_after_step(c);
 }
 
@@ -1379,6 +1381,7 @@ gpe_status gpe_run(gpe_ctx *c, float dt, uint64_t steps, uint64_t resort_every, 
         }
         const bool resort = (s == 0 && resort_first) || (resort_every && s > 0 && (s % resort_every) == 0);
         rc = do_step(c, dt, resort ? GPE_STEP_RESORT : 0u);
+        if (rc == GPE_OK) rc = colliders_after_step(c);
         if (rc == GPE_OK) rc = observers_after_step(c);
     }
     for (hipEvent_t e : fence) if (e) (void)hipEventDestroy(e);
@@ -1600,6 +1603,7 @@ gpe_status gpe_set_counts(gpe_ctx *c, uint64_t n_total, uint64_t n_owned)
     if (n_total == 0 || n_total > c->cap || n_owned > n_total)
         return fail(c, GPE_ERR_INVALID_ARG, "gpe_set_counts: need 0 < n_owned <= n_total <= capacity");
     if (c->uid.on) return fail(c, GPE_ERR_UNSUPPORTED, "gpe_set_counts: not supported while uids are on");
+    if (has_colliders(c)) return refuse_colliders(c, "gpe_set_counts");
     c->n = n_total;
     c->n_owned = n_owned;
     return GPE_OK;
@@ -1610,6 +1614,7 @@ gpe_status gpe_use_order_keys(gpe_ctx *c, int32_t enable)
     if (!c) return GPE_ERR_INVALID_ARG;
     if (enable && c->uid.on)
         return fail(c, GPE_ERR_UNSUPPORTED, "gpe_use_order_keys: sharded runs carry order keys, not uids (uids are on)");
+    if (enable && has_colliders(c)) return refuse_colliders(c, "gpe_use_order_keys");
     c->use_order_keys = enable != 0;
     return GPE_OK;
 }

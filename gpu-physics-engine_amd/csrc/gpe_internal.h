@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/gpe.h"
+#include "k_collider.h"
 #include "native_policy.h"
 #include "scope_events.h"
 
@@ -409,6 +410,20 @@ struct MonitorState {
     uint8_t *partials = nullptr;
 };
 
+// the static colliders (gpe_set_colliders; gpe_colliders.hip, k_colliders.hip).  Step state: gpe_step / gpe_run apply them
+struct ColliderState {
+    std::vector<gpe_collider> set;               // the colliders as the host gave them (empty: none, nothing is launched)
+    float4 *rec = nullptr;                       // 2 per collider: (ax, ay, bx, by), (R, 0, 0, 0)
+    unsigned long long *pushed = nullptr;        // one word: particles moved since the last gpe_set_colliders
+    uint64_t passes = 0;                         // passes enqueued since then
+    // the lookup grid (collider_grid.h), rebuilt before the next pass when what it was built for has changed
+    bool grid_valid = false;
+    float grid_rb = 0.f, grid_w = 0.f, grid_h = 0.f;   // gpe_max_radius and the world at the build (compared by bits)
+    ColliderGridView view;
+    uint32_t *cell_start = nullptr, *items = nullptr;
+    uint64_t entries = 0;
+};
+
 struct SortWorkspace {
     uint32_t *keys_b = nullptr, *vals_b = nullptr;   // ping-pong partners, cap entries each
     uint64_t cap = 0;
@@ -748,6 +763,7 @@ struct gpe_ctx {
     gpe::UidState uid;
     gpe::TracerState tracers;
     gpe::MonitorState monitor;
+    gpe::ColliderState colliders;
     gpe::QueryWorkspace query_ws;
     gpe::ContactsWorkspace contacts_ws;
     gpe::ClustersWorkspace clusters_ws;
@@ -884,6 +900,11 @@ gpe_status box_region(gpe_ctx *c, const char *who, float x0, float y0, float x1,
 // gpe_observe.hip: the tracers and the monitor of an armed context
 gpe_status observers_after_step(gpe_ctx *c);       // after every step of gpe_step / gpe_run
 void observers_release(gpe_ctx *c);
+// gpe_colliders.hip: the static colliders of a context that holds some
+inline bool has_colliders(const gpe_ctx *c) { return !c->colliders.set.empty(); }
+gpe_status refuse_colliders(gpe_ctx *c, const char *who);   // GPE_ERR_UNSUPPORTED: sharding a context that holds colliders
+gpe_status colliders_after_step(gpe_ctx *c);       // after every step of gpe_step / gpe_run, before the observers
+void colliders_release(gpe_ctx *c);
 
 // profiling scope: a hipEvent pair on ctx->stream when ctx->profiling, else nothing.  kSharedBoundaries: inside a
 // ScopeRegion the scope takes the event a neighbouring scope recorded where nothing was enqueued between the two
@@ -1076,6 +1097,11 @@ gpe_status launch_monitor_partial(gpe_ctx *c, const float2 *pos, const float2 *p
                                   float H, void *partials);
 gpe_status launch_monitor_final(gpe_ctx *c, const void *partials, uint64_t n, uint64_t step, const uint32_t *uids,
                                 gpe_measures *out);
+// static colliders (k_colliders.hip): one pass over pos[0, n) in place.  cell_start / items: the lookup grid `view`
+// describes (view.gx * view.gy + 1 words; every item < k); rec: 2 k records; *pushed += the particles moved
+gpe_status launch_colliders_pass(gpe_ctx *c, float2 *pos, const float *radius, uint64_t n, const uint32_t *cell_start,
+                                 const uint32_t *items, const float4 *rec, uint32_t k, const ColliderGridView &view,
+                                 unsigned long long *pushed);
 // native pipeline: its host side (gpe_native.hip; the kernels and their launchers: k_native.hip, native_launch.h)
 gpe_status native_configure(gpe_ctx *c);
 bool native_should_run(gpe_ctx *c);

@@ -52,6 +52,9 @@ MEASURES_DTYPE = np.dtype([(name, {C.c_uint64: np.uint64, C.c_double: np.float64
                                    C.c_uint32: np.uint32}[ctype]) for name, ctype in L.GpeMeasures._fields_])
 assert MEASURES_DTYPE.itemsize == C.sizeof(L.GpeMeasures)
 Measures = collections.namedtuple("Measures", [name for name, _ in L.GpeMeasures._fields_])
+# set_colliders / colliders: the rows of gpe_collider (24 bytes each, the struct's layout)
+COLLIDER_DTYPE = np.dtype([(name, np.uint32 if ctype is C.c_uint32 else np.float32) for name, ctype in L.GpeCollider._fields_])
+assert COLLIDER_DTYPE.itemsize == C.sizeof(L.GpeCollider)
 
 
 class Context:
@@ -521,6 +524,45 @@ class ParticleSystem:
     def monitor_end(self):
         """gpe_monitor_end: stop recording and free the ring (records not read are lost)."""
         self.ctx.call("gpe_monitor_end")
+
+    # Static colliders (not in the reference; include/gpe.h): capsules the particles cannot enter, applied on the device
+    # after every update() / step of run(), before the tracers and the monitor.  Step state: save() keeps them.
+    def set_colliders(self, capsules):
+        """gpe_set_colliders: replace the set by the rows (ax, ay, bx, by, radius) of a (k, 5) float array; k == 0
+        clears it."""
+        caps = np.ascontiguousarray(capsules, np.float32)
+        if caps.size == 0:
+            caps = caps.reshape(0, 5)
+        if caps.ndim != 2 or caps.shape[1] != 5:
+            raise ValueError("set_colliders: capsules must have shape (k, 5), got %r" % (caps.shape,))
+        k = len(caps)
+        rows = np.zeros(k, COLLIDER_DTYPE)
+        for col, name in enumerate(("ax", "ay", "bx", "by", "radius")):
+            rows[name] = caps[:, col]
+        self.ctx.call("gpe_set_colliders", rows.ctypes.data_as(C.POINTER(L.GpeCollider)) if k else None, k)
+
+    def colliders(self):
+        """gpe_get_colliders -> f32[k, 5]: the rows (ax, ay, bx, by, radius) of the set."""
+        k = C.c_uint64()
+        self.ctx.call("gpe_get_colliders", None, 0, C.byref(k))
+        rows = np.zeros(max(k.value, 1), COLLIDER_DTYPE)
+        self.ctx.call("gpe_get_colliders", rows.ctypes.data_as(C.POINTER(L.GpeCollider)), k.value, C.byref(k))
+        rows = rows[:k.value]
+        return np.stack([rows[name] for name in ("ax", "ay", "bx", "by", "radius")], axis=1).astype(np.float32)
+
+    def clear_colliders(self):
+        """gpe_set_colliders with k = 0."""
+        self.ctx.call("gpe_set_colliders", None, 0)
+
+    def apply_colliders(self):
+        """gpe_apply_colliders: one pass now (the hook of a host that steps module by module).  Does not synchronise."""
+        self.ctx.call("gpe_apply_colliders")
+
+    def colliders_info(self):
+        """gpe_get_colliders_info -> dict(k, passes, pushed, grid_x, grid_y, list_entries).  Blocks like a download."""
+        info = L.GpeCollidersInfo(struct_size=C.sizeof(L.GpeCollidersInfo))
+        self.ctx.call("gpe_get_colliders_info", C.byref(info))
+        return {name: getattr(info, name) for name, _ in L.GpeCollidersInfo._fields_ if name != "struct_size"}
 
     # Region queries and picking (not in the reference; include/gpe.h): which particles lie in a circle or a box, or
     # under a point, counted and gathered on the device.  The context is left exactly as it was.
@@ -1046,6 +1088,26 @@ class State:
         """ParticleSystem.monitor_end."""
         self.particles.monitor_end()
 
+    def set_colliders(self, capsules):
+        """ParticleSystem.set_colliders: static capsules (ax, ay, bx, by, radius) applied after every step."""
+        self.particles.set_colliders(capsules)
+
+    def colliders(self):
+        """ParticleSystem.colliders -> f32[k, 5]."""
+        return self.particles.colliders()
+
+    def clear_colliders(self):
+        """ParticleSystem.clear_colliders."""
+        self.particles.clear_colliders()
+
+    def apply_colliders(self):
+        """ParticleSystem.apply_colliders: one pass now."""
+        self.particles.apply_colliders()
+
+    def colliders_info(self):
+        """ParticleSystem.colliders_info -> dict(k, passes, pushed, grid_x, grid_y, list_entries)."""
+        return self.particles.colliders_info()
+
     def query_circle(self, center, radius):
         """ParticleSystem.query_circle -> QueryResult(index, uid, pos, prev, radius)."""
         return self.particles.query_circle(center, radius)
@@ -1143,8 +1205,11 @@ class State:
         one gpe_set_particles derives from the saved radii (Grid.new_without_camera) that radius (`grid_max_radius`).
         A tracer recorder (tracers_begin) is not stored: it is observation state, not step state -- a loaded State steps
         the same bits without it and is armed again by its host.  The run monitor (monitor_begin) is not stored either,
-        for the same reason."""
+        for the same reason.  Static colliders are step state: a set that is present is written (`colliders`)."""
         extra = {}
+        caps = self.colliders()
+        if len(caps):
+            extra.update(colliders=caps)
         if self._uids_on():
             extra.update(uids=self.uids(), next_uid=np.array([self.next_uid()], np.uint64))
         pressed, at = self.ctx.mouse()
@@ -1163,14 +1228,14 @@ class State:
                  gravity=np.array(self.ctx.gravity(), np.float32), **extra)
 
     @classmethod
-    def load(cls, path, mode=None, device=-1):
+    def load(cls, path, mode=None, device=-1, flags=0):
         """A State that continues from a snapshot written by save(): the next update() yields the same bits as
         the saved run's next update() would have (the step has no hidden state beyond these arrays and constants)."""
         with np.load(path, allow_pickle=False) as d:
             if int(d["format"][0]) != 1:
                 raise ValueError("unknown snapshot format")
             st = cls(d["pos"], d["radius"], world=tuple(d["world"]), gravity=tuple(d["gravity"]), mode=mode,
-                     prev=d["prev"], device=device)
+                     prev=d["prev"], device=device, flags=flags)
             if "uids" in d.files:
                 st.set_uids(d["uids"])
                 st.set_next_uid(int(d["next_uid"][0]))
@@ -1178,6 +1243,8 @@ class State:
                 st.particles.mouse_click_callback(True, tuple(d["mouse"]))
             if "grid_max_radius" in d.files:
                 st.ctx.call("gpe_grid_set_max_radius", float(d["grid_max_radius"][0]))
+            if "colliders" in d.files:
+                st.set_colliders(d["colliders"])
             return st
 
     def close(self):

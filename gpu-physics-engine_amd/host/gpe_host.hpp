@@ -332,6 +332,29 @@ class ParticleSystem {
         return r;
     }
     void monitor_end() { ctx_->call(gpe_monitor_end(ctx_->raw())); }
+    // not in the reference: static capsules the particles cannot enter (include/gpe.h), applied on the device after
+    // every step of gpe_step / gpe_run, before the tracers and the monitor.  Step state: a snapshot keeps them.
+    void set_colliders(const std::vector<gpe_collider> &capsules)
+    {
+        ctx_->call(gpe_set_colliders(ctx_->raw(), capsules.empty() ? nullptr : capsules.data(), capsules.size()));
+    }
+    std::vector<gpe_collider> colliders() const
+    {
+        uint64_t k = 0;
+        ctx_->call(gpe_get_colliders(ctx_->raw(), nullptr, 0, &k));
+        std::vector<gpe_collider> out(k);
+        ctx_->call(gpe_get_colliders(ctx_->raw(), out.empty() ? nullptr : out.data(), k, &k));
+        return out;
+    }
+    void clear_colliders() { ctx_->call(gpe_set_colliders(ctx_->raw(), nullptr, 0)); }
+    void apply_colliders() { ctx_->call(gpe_apply_colliders(ctx_->raw())); }   // one pass now: the hook of the per-module calls
+    gpe_colliders_info colliders_info() const
+    {
+        gpe_colliders_info info{};
+        info.struct_size = sizeof(info);
+        ctx_->call(gpe_get_colliders_info(ctx_->raw(), &info));
+        return info;
+    }
     // not in the reference: every particle in a circle / box, or the one under a point (include/gpe.h), ascending
     // storage index; uid stays empty while uids are off.  pick() returns no rows when no disc contains the point.
     struct QueryResult {

@@ -340,6 +340,58 @@ gpe_status gpe_monitor_read(gpe_ctx *ctx, gpe_monitor_frames *out);
 /* Disarms the recorder and frees the ring (the records not read are lost).  Synchronises. */
 gpe_status gpe_monitor_end(gpe_ctx *ctx);
 
+/* ---- static colliders (not in the reference) ----------------------------------------------------------------------
+ * Obstacles the particles cannot enter: a floor, a funnel, a shelf, a peg.  A collider is a capsule, the segment a -> b
+ * thickened by radius R >= 0 (a == b: a disc; R == 0: a thin wall; a chain: a polyline).  While a context holds a set,
+ * gpe_step and every iteration of gpe_run run one pass over the particles after the step and before the tracers and
+ * the monitor, stream-ordered, on the device (csrc/k_colliders.hip); a tracer or monitor frame sees the projected
+ * state.  The per-module calls (gpe_integrate and the rest) run no pass: gpe_apply_colliders is their hook.  A context
+ * without colliders launches exactly what it launches without this section.
+ *  - The pass.  For a particle with centre p and stored radius r and collider j, in IEEE binary32, one rounding per
+ *    operation, left to right, no FMA, `/` and sqrtf correctly rounded (csrc/k_collider.h is the one definition):
+ *      a = |r|;  dx = bx-ax; dy = by-ay; fx = px-ax; fy = py-ay;  A = dx*dx + dy*dy
+ *      u = 0; if A > 0: u = (fx*dx + fy*dy) / A;  u = (u > 0) ? u : 0;  u = (u < 1) ? u : 1          (NaN -> 0)
+ *      qx = fx - u*dx; qy = fy - u*dy;  h = qx*qx + qy*qy;  s = R + a
+ *      touched when h < s*s (strict; a NaN anywhere: not touched);  d = sqrtf(h);  depth = s - d
+ *      normal: d > 0: (qx/d, qy/d);  else A > 0: L = sqrtf(A), ((-dy)/L, dx/L);  else (1, 0)
+ *    Every collider is judged from the position the pass starts with, and only the touched collider with the largest
+ *    key bits(depth) << 32 | (0xFFFFFFFF - j) acts: the deepest penetration, the lowest index on a tie.  The particle
+ *    moves to (px + nx*depth, py + ny*depth), then K12's clamp: clamp(x, r, W - r), clamp(y, r, H - r), W, H as
+ *    gpe_world.  Only pos is written, prev stays: the Verlet velocity loses its component into the obstacle
+ *    (inelastic).  A particle no collider touches keeps every bit.  Deepest-only makes the result a function of
+ *    (p, r, colliders) alone: the overlapping capsules of a polyline do not push twice at a joint; a corner is
+ *    resolved over two steps.
+ *  - No swept test: a wall thinner than one step's displacement is tunnelled through.  Make walls thick.
+ *  - Colliders are step state, not observation state: the set survives gpe_set_particles, adds, removals, edits,
+ *    re-sorts, growth, gpe_set_world and uids being switched on or off; gpe_destroy frees it.
+ *  - The pass finds a particle's colliders through a coarse grid over the world, rebuilt before the next pass when
+ *    |gpe_max_radius| or the world has changed (that rebuild synchronises).  No result depends on the grid: a particle
+ *    outside it, with a NaN coordinate or with a radius above the bound it was built for is tested against every
+ *    collider.
+ *  - gpe_set_colliders replaces the set (k == 0 clears it and frees its buffers) and zeroes passes and pushed; it may be
+ *    called before there are particles and synchronises like gpe_add_particles.  A host that moves an obstacle calls
+ *    it once a frame.  gpe_get_colliders delivers the first min(k, capacity) colliders into out (may be NULL with
+ *    capacity 0) and the number set into *k.  gpe_apply_colliders with no colliders or no particles: GPE_OK, nothing
+ *    done.
+ *  - Errors (the previous set stays untouched): a NULL ctx, NULL colliders with k > 0, k > GPE_COLLIDERS_MAX, a
+ *    non-finite coordinate, a radius that is NaN, infinite or negative (-0.0 is accepted as 0), non-zero flags, a
+ *    struct_size below the struct's: GPE_ERR_INVALID_ARG.  gpe_set_colliders on a sharded context (gpe_shard_*, order
+ *    keys or an active cell box), and gpe_shard_set_particles, gpe_use_order_keys(ctx, 1) and gpe_set_counts on a
+ *    context that holds colliders: GPE_ERR_UNSUPPORTED. */
+#define GPE_COLLIDERS_MAX 4096u
+typedef struct gpe_collider { float ax, ay, bx, by, radius; uint32_t flags; } gpe_collider;   /* 24 bytes; flags = 0 */
+typedef struct gpe_colliders_info {
+    uint32_t struct_size, k;          /* in / colliders set                                             */
+    uint64_t passes;                  /* passes run since the last gpe_set_colliders                    */
+    uint64_t pushed;                  /* particles moved by those passes, summed (integer atomics only) */
+    uint32_t grid_x, grid_y;          /* the lookup grid in use (diagnostic; no result depends on it)   */
+    uint64_t list_entries;            /* (cell, collider) entries in it                                 */
+} gpe_colliders_info;                 /* 40 bytes */
+gpe_status gpe_set_colliders(gpe_ctx *ctx, const gpe_collider *colliders, uint64_t k);
+gpe_status gpe_get_colliders(const gpe_ctx *ctx, gpe_collider *out, uint64_t capacity, uint64_t *k);
+gpe_status gpe_apply_colliders(gpe_ctx *ctx);                              /* one pass now, stream-ordered, no sync */
+gpe_status gpe_get_colliders_info(gpe_ctx *ctx, gpe_colliders_info *info); /* synchronises (reads the device counters) */
+
 /* ---- region queries and picking (not in the reference) ------------------------------------------------------
  * Which particles lie in a region, or under a point, without downloading every position: full passes over the
  * particles on the device (csrc/k_query.hip) that change nothing on the context.  Positions, prev, radii, uids, the
