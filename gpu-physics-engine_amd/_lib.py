@@ -27,6 +27,7 @@ FLAG_SHARD_OVERLAP = 256
 FLAG_FUSED_HISTOGRAMS = 512
 FLAG_GUARD_ALLOCS = 1024
 FLAG_HASH_INDEX64 = 2048
+FLAG_EVENT_SCOPES = 4096
 PIPELINE_COMPAT, PIPELINE_NATIVE = 0, 1
 (REASON_NONE, REASON_MODE_COMPAT, REASON_NO_PARTICLES, REASON_OUT_OF_BOX, REASON_GRID_TOO_WIDE,
  REASON_TABLE_TOO_LARGE, REASON_DENSE_WINDOWS) = range(7)

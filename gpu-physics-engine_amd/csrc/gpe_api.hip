@@ -37,10 +37,20 @@ static int stat_index(gpe_ctx *c, const char *name)
     return (int)c->stats.size() - 1;
 }
 
-Scope::Scope(gpe_ctx *ctx, const char *name, Boundaries b) : ctx_(ctx), shared_(b == kSharedBoundaries)
+static void stamps_make_room(gpe_ctx *c, uint32_t need);
+
+Scope::Scope(gpe_ctx *ctx, const char *name, Boundaries b, unsigned carry)
+    : ctx_(ctx), shared_(b == kSharedBoundaries), carry_(carry)
 {
     if (!ctx_ || !ctx_->profiling) return;
     stat_ = stat_index(ctx_, name);
+    stamps_ = scope_uses_stamps(ctx_);
+    if (stamps_) {
+        if (!ctx_->scope_stamps.in_region()) stamps_make_room(ctx_, 2);      // (the step makes its own room: do_step)
+        StampRecorder<HipStampDev> be{ctx_->stamp_be, shared_ && (carry_ & kCarryStart) && ctx_->scope_stamps.in_region()};
+        start_ = ctx_->scope_stamps.open(be, shared_);
+        return;
+    }
     HipScopeBackend be{ctx_->stream};
     start_ = ctx_->scope_events.open(be, shared_);
 }
@@ -48,28 +58,93 @@ Scope::Scope(gpe_ctx *ctx, const char *name, Boundaries b) : ctx_(ctx), shared_(
 Scope::~Scope()
 {
     if (!ctx_ || start_ < 0) return;
+    if (stamps_) {
+        StampRecorder<HipStampDev> be{ctx_->stamp_be, shared_ && (carry_ & kCarryStop) && ctx_->scope_stamps.in_region()};
+        ctx_->scope_stamps.close(be, start_, stat_, shared_);
+        return;
+    }
     HipScopeBackend be{ctx_->stream};
     ctx_->scope_events.close(be, start_, stat_, shared_);
 }
 
 constexpr size_t kTraceCap = 1u << 16;
 
-// (after a stream synchronisation) reads the pending pairs into the statistics and the trace; their events go back to
-// the pool, a shared one when the last pair that uses it has been read
+static void resolved(gpe_ctx *c, int stat, float ms, bool has_origin, float t0)
+{
+    c->stats[stat].total_ms += ms;
+    c->stats[stat].calls += 1;
+    if (!has_origin) return;
+    if (c->trace.size() >= kTraceCap) c->trace.erase(c->trace.begin(), c->trace.begin() + kTraceCap / 2);
+    TraceEvent e;
+    e.stat = stat; e.start_ms = t0; e.dur_ms = ms;
+    c->trace.push_back(e);
+}
+
+// (after a stream synchronisation) reads the pending pairs into the statistics and the trace; their events or slots go
+// back to the pool, a shared one when the last pair that uses it has been read.  The slots are read with one copy.
 static void resolve_pending(gpe_ctx *c)
 {
     c->scope_events.resolve([c](int stat, hipEvent_t start, hipEvent_t stop) {
         float ms = 0.f;
         if (hipEventElapsedTime(&ms, start, stop) != hipSuccess) return;
-        c->stats[stat].total_ms += ms;
-        c->stats[stat].calls += 1;
         float t0 = 0.f;
-        if (c->trace_origin && hipEventElapsedTime(&t0, c->trace_origin, start) == hipSuccess) {
-            if (c->trace.size() >= kTraceCap) c->trace.erase(c->trace.begin(), c->trace.begin() + kTraceCap / 2);
-            TraceEvent e;
-            e.stat = stat; e.start_ms = t0; e.dur_ms = ms;
-            c->trace.push_back(e);
-        }
+        const bool has_origin = c->trace_origin && hipEventElapsedTime(&t0, c->trace_origin, start) == hipSuccess;
+        resolved(c, stat, ms, has_origin, t0);
+    });
+    if (c->scope_stamps.pending() == 0) return;
+    auto &be = c->stamp_be;
+    std::vector<unsigned long long> ticks(be.next);
+    const bool read = be.dev.buf && c->stamp_khz > 0.0 &&
+                      hipMemcpy(ticks.data(), be.dev.buf, ticks.size() * sizeof(ticks[0]), hipMemcpyDeviceToHost) == hipSuccess;
+    if (!read) (void)hipGetLastError();
+    c->scope_stamps.resolve([&](int stat, uint32_t start, uint32_t stop) {
+        if (!read) return;
+        // milliseconds as binary32, as hipEventElapsedTime hands them out
+        const float ms = (float)((double)(long long)(ticks[stop] - ticks[start]) / c->stamp_khz);
+        const float t0 = (float)((double)(long long)(ticks[start] - ticks[kStampOrigin]) / c->stamp_khz);
+        resolved(c, stat, ms, c->stamp_origin, t0);
+    });
+}
+
+// ---- the timestamp slots behind the scopes (scope_stamps.h) ---------------------------------------------------------
+__global__ void k_scope_stamp(unsigned long long *slot) { *slot = wall_clock64(); }
+
+void HipStampDev::stamp(uint32_t slot)
+{
+    hipLaunchKernelGGL(k_scope_stamp, dim3(1), dim3(1), 0, c->stream, buf + slot);
+    (void)hipGetLastError();
+}
+
+// Nothing references a slot (StampBackend::grow) and the stream has been synchronised: only the origin's is kept.
+bool HipStampDev::grow(uint32_t old_slots, uint32_t new_slots)
+{
+    unsigned long long *fresh = nullptr;
+    if (dev_reserve(c, &fresh, (uint64_t)new_slots * sizeof(*fresh), 0, "native.scope_stamps") != hipSuccess) return false;
+    if (old_slots && hipMemcpy(fresh, buf, sizeof(*fresh), hipMemcpyDeviceToDevice) != hipSuccess) {
+        (void)hipGetLastError();
+        (void)dev_release(c, fresh);
+        return false;
+    }
+    (void)dev_release(c, buf);
+    buf = fresh;
+    return true;
+}
+
+// Outside the step path: at least `need` slots can be handed out afterwards, if that can be had (StampBackend::make_room).
+static void stamps_make_room(gpe_ctx *c, uint32_t need)
+{
+    auto &be = c->stamp_be;
+    if (be.room(c->scope_stamps.pooled()) >= need) return;
+    if (c->stamp_khz <= 0.0) {
+        int khz = 0;
+        if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, c->device) != hipSuccess || khz <= 0) khz = 100000;
+        c->stamp_khz = (double)khz;
+    }
+    be.dev.c = c;
+    be.make_room(c->scope_stamps, need, [c] {
+        if (hipStreamSynchronize(c->stream) != hipSuccess) { (void)hipGetLastError(); return false; }
+        resolve_pending(c);
+        return true;
     });
 }
 
@@ -747,15 +822,28 @@ static gpe_status do_step_scoped(gpe_ctx *c, float dt, uint32_t flags)
 static gpe_status do_step(gpe_ctx *c, float dt, uint32_t flags)
 {
     if (c->profile_every > 1) c->profiling = (c->profile_step++ % c->profile_every) == 0;
+    if (c->profiling && scope_uses_stamps(c)) stamps_make_room(c, 64);      // (more slots than a step's scopes take)
     const gpe_status st = do_step_scoped(c, dt, flags);
     if (c->profile_every > 1) c->profiling = true;
     return st;
 }
 
-// Device-side error words (sticky): reported at the synchronising entry points.
-gpe_status check_device_errors(gpe_ctx *c)
+// Device-side error words (sticky): reported at the synchronising entry points.  The three copies go to pinned words
+// and are enqueued behind the context's work, so the one wait for the stream is also the wait for them.
+// wait_exchange (gpe_sync alone, as before): the exchange stream of a sharded run is waited for first -- whatever it was
+// given has then run, whatever of the context's stream it waited for included, and the copies behind the context's
+// stream see what either of them wrote.  Where that wait fails, the context's own stream is asked first, as it used to
+// be, so that a failure of both is reported as the same call's.
+gpe_status check_device_errors(gpe_ctx *c, bool wait_exchange)
 {
-    uint32_t words[3] = {0, 0, 0};
+    GPE_TRY(error_words_reserve(c));
+    uint32_t *words = c->err_words;
+    words[0] = words[1] = words[2] = 0u;
+    if (wait_exchange && c->shard.xstream && hipStreamSynchronize(c->shard.xstream) != hipSuccess) {
+        (void)hipGetLastError();
+        GPE_HIP(c, hipStreamSynchronize(c->stream));
+        GPE_HIP(c, hipStreamSynchronize(c->shard.xstream));
+    }
     if (c->shard.counts)
         GPE_HIP(c, hipMemcpyAsync(&words[2], c->shard.counts + kShardError, 4, hipMemcpyDeviceToHost, c->stream));
     if (c->native.tile_ctl)
@@ -893,7 +981,13 @@ gpe_status gpe_destroy(gpe_ctx *c)
         HipScopeBackend be{c->stream};
         c->scope_events.destroy_all(be);
     }
+    {
+        StampRecorder<HipStampDev> be{c->stamp_be};
+        c->scope_stamps.destroy_all(be);
+    }
+    (void)dev_release(c, c->stamp_be.dev.buf);
     if (c->trace_origin) (void)hipEventDestroy(c->trace_origin);
+    error_words_release(c);
     free_particle_buffers(c);
     observers_release(c);
     colliders_release(c);
@@ -915,9 +1009,7 @@ gpe_status gpe_destroy(gpe_ctx *c)
 gpe_status gpe_sync(gpe_ctx *c)
 {
     if (!c) return GPE_ERR_INVALID_ARG;
-    GPE_HIP(c, hipStreamSynchronize(c->stream));
-    if (c->shard.xstream) GPE_HIP(c, hipStreamSynchronize(c->shard.xstream));   // (a sharded run's exchange stream)
-    return check_device_errors(c);
+    return check_device_errors(c, true);               // (one wait per stream, the error words' copies behind the work)
 }
 
 gpe_status gpe_get_pipeline_info(gpe_ctx *c, gpe_pipeline_info *info)
@@ -1486,6 +1578,8 @@ gpe_status gpe_guard_registry(gpe_ctx *c, char *text, uint64_t capacity, uint64_
         for (const DevAlloc &a : *list)
             all += std::string(a.tag) + " " + std::to_string(a.payload) + " " + std::to_string(a.slack) +
                    (list == &c->guard.live ? " live\n" : " released\n");
+    for (const DevAlloc &a : c->guard.pinned)                          // (host blocks: one line per block that exists)
+        all += std::string(a.tag) + " " + std::to_string(a.payload) + " 0 pinned\n";
     if (needed) *needed = all.size() + 1;
     if (capacity) {
         const size_t k = std::min<size_t>(all.size(), capacity - 1);
@@ -1637,6 +1731,8 @@ gpe_status gpe_stream_handle(gpe_ctx *c, void **hip_stream)
     return GPE_OK;
 }
 
+static gpe_status mark_trace_origin(gpe_ctx *c);        // below, with the profiling entry points
+
 gpe_status gpe_set_stream(gpe_ctx *c, void *hip_stream)
 {
     if (!c) return GPE_ERR_INVALID_ARG;
@@ -1644,7 +1740,7 @@ gpe_status gpe_set_stream(gpe_ctx *c, void *hip_stream)
     GPE_HIP(c, hipStreamSynchronize(c->stream));
     resolve_pending(c);                                   // event pairs recorded on the stream being left
     c->stream = hip_stream ? (hipStream_t)hip_stream : c->own_stream;
-    if (c->trace_origin) (void)hipEventRecord(c->trace_origin, c->stream);
+    if (c->trace_origin || c->stamp_origin) (void)mark_trace_origin(c);    // (in the form the scopes on this stream take)
     for (int i = 0; i < 2; ++i) c->shard.armed[i] = false;
     return GPE_OK;
 }
@@ -1672,6 +1768,12 @@ gpe_status gpe_shard_classify(gpe_ctx *c, const uint8_t *d_owner_of_block, const
 // ---- profiling ---------------------------------------------------------------------------------------------
 static gpe_status mark_trace_origin(gpe_ctx *c)
 {
+    if (scope_uses_stamps(c)) {
+        stamps_make_room(c, 1);                                            // (the buffer, at the first call)
+        c->stamp_origin = c->stamp_be.capacity != 0;
+        if (c->stamp_origin) c->stamp_be.dev.stamp(kStampOrigin);
+        return GPE_OK;
+    }
     if (!c->trace_origin) GPE_HIP(c, hipEventCreate(&c->trace_origin));
     GPE_HIP(c, hipEventRecord(c->trace_origin, c->stream));
     return GPE_OK;
@@ -1683,7 +1785,7 @@ gpe_status gpe_set_profiling(gpe_ctx *c, uint32_t on)
     c->profiling = on != 0;
     c->profile_every = on;
     c->profile_step = 0;
-    if (on && !c->trace_origin) GPE_TRY(mark_trace_origin(c));
+    if (on && !(scope_uses_stamps(c) ? c->stamp_origin : c->trace_origin != nullptr)) GPE_TRY(mark_trace_origin(c));
     return GPE_OK;
 }
 

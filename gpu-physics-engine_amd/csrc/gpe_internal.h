@@ -13,6 +13,7 @@
 #include "k_collider.h"
 #include "native_policy.h"
 #include "scope_events.h"
+#include "scope_stamps.h"
 
 namespace gpe {
 
@@ -255,6 +256,12 @@ struct HipScopeBackend {             // the event calls behind ScopeEvents (scop
     bool create(hipEvent_t *e) { return hipEventCreate(e) == hipSuccess; }
     void record(hipEvent_t e) { (void)hipEventRecord(e, stream); }
     void destroy(hipEvent_t e) { (void)hipEventDestroy(e); }
+};
+struct HipStampDev {                 // the device side of StampBackend (scope_stamps.h): gpe_api.hip
+    gpe_ctx *c = nullptr;
+    unsigned long long *buf = nullptr;           // "native.scope_stamps": one 64-bit timestamp per slot
+    bool grow(uint32_t old_slots, uint32_t new_slots);
+    void stamp(uint32_t slot);
 };
 struct TraceEvent {                  // one resolved scope instance (gpe_get_trace)
     int stat;
@@ -716,6 +723,7 @@ struct GuardState {
     bool on = false;                 // GPE_FLAG_GUARD_ALLOCS
     uint32_t canary = 0, poison = 0; // gpe_config.guard_canary / guard_poison
     std::vector<DevAlloc> live;
+    std::vector<DevAlloc> pinned;    // pinned host blocks the registry lists (state "pinned"): never scanned, one entry per block that exists
     std::vector<DevAlloc> released;  // guarded: one entry per tag that has been released, the last such allocation (ptr = base = NULL)
     hipError_t scan_failed = hipSuccess;   // a check at release could not run: that buffer's evidence is lost (sticky)
     std::vector<gpe_guard_zone> kept;   // damage found when a buffer was released (the first GPE_GUARD_MAX_ZONES)
@@ -784,8 +792,15 @@ struct gpe_ctx {
     uint32_t profile_every = 0;      // 0 off, 1 every call, k > 1: every k-th step (gpe_set_profiling)
     uint64_t profile_step = 0;
     std::vector<gpe::ScopeStat> stats;
-    gpe::ScopeEvents<gpe::HipScopeBackend> scope_events;   // the scopes' events: pool, pending pairs, shared boundaries
+    // The scopes' boundaries: pool, pending pairs, shared boundaries.  On the context's own stream they are timestamp
+    // slots (scope_stamps); on a stream lent by gpe_set_stream, or under GPE_FLAG_EVENT_SCOPES, events (scope_events).
+    gpe::ScopeEvents<gpe::HipScopeBackend> scope_events;
+    gpe::StampBackend<gpe::HipStampDev> stamp_be;
+    gpe::ScopeEvents<gpe::StampRecorder<gpe::HipStampDev>> scope_stamps;
+    double stamp_khz = 0.0;                       // the timestamp counter's rate (hipDeviceAttributeWallClockRate)
+    bool stamp_origin = false;                    // slot 0 holds the trace origin
     hipEvent_t trace_origin = nullptr;            // recorded when profiling is switched on / timings are reset
+    uint32_t *err_words = nullptr;                // pinned, 16 words: check_device_errors reads the sticky error words into it
     std::vector<gpe::TraceEvent> trace;           // the last kTraceCap resolved scopes, oldest first
 };
 
@@ -879,7 +894,10 @@ gpe_status refuse_uid_off(gpe_ctx *c, const char *who);             // GPE_ERR_S
 gpe_status refuse_radius_not_finite(gpe_ctx *c, const char *who);   // GPE_ERR_UNSUPPORTED
 // gpe_api.hip
 gpe_status need_particles(gpe_ctx *c);
-gpe_status check_device_errors(gpe_ctx *c);        // the sticky device-side error words; synchronises
+// the sticky device-side error words; synchronises the context's stream once (wait_exchange: and the exchange stream, once)
+gpe_status check_device_errors(gpe_ctx *c, bool wait_exchange = false);
+gpe_status error_words_reserve(gpe_ctx *c);        // gpe_native.hip: c->err_words, once per context
+void error_words_release(gpe_ctx *c);
 gpe_status grow_particle_buffers(gpe_ctx *c, uint64_t cap);
 gpe_status init_index_buffers(gpe_ctx *c, uint64_t lo, uint64_t hi);
 void refresh_cell_size(gpe_ctx *c);
@@ -906,30 +924,56 @@ gpe_status refuse_colliders(gpe_ctx *c, const char *who);   // GPE_ERR_UNSUPPORT
 gpe_status colliders_after_step(gpe_ctx *c);       // after every step of gpe_step / gpe_run, before the observers
 void colliders_release(gpe_ctx *c);
 
-// profiling scope: a hipEvent pair on ctx->stream when ctx->profiling, else nothing.  kSharedBoundaries: inside a
-// ScopeRegion the scope takes the event a neighbouring scope recorded where nothing was enqueued between the two
-// (scope_events.h); the timings and the trace read the same, a sampled step records fewer events.
+// profiling scope: a pair of timestamps on ctx->stream when ctx->profiling, else nothing -- slots of the stamp buffer
+// (scope_stamps.h), or hipEvents where scope_uses_stamps() says no.  kSharedBoundaries: inside a ScopeRegion the scope
+// takes the boundary a neighbouring scope recorded where nothing was enqueued between the two (scope_events.h); the
+// timings and the trace read the same, a sampled step records fewer boundaries.
+inline bool scope_uses_stamps(const gpe_ctx *c)
+{
+    return (c->cfg.flags & GPE_FLAG_EVENT_SCOPES) == 0 && c->stream == c->own_stream;
+}
 class Scope {
    public:
     enum Boundaries { kOwnEvents, kSharedBoundaries };
-    Scope(gpe_ctx *ctx, const char *name, Boundaries b = kOwnEvents);
+    // Timestamp slots, shared boundaries: the stamp of the scope's opening / closing is owed to the enqueue that
+    // follows (scope_stamps.h) -- written by that launch's first workgroup when it is one of the two gated sort
+    // kernels, by a kernel of its own right in front of it otherwise.  For boundaries whose next launch comes at once
+    // and in front of short launches; without the hint a boundary is stamped at once, which is what the end of a long
+    // kernel needs (the host must not delay it).  Timing only: the stamp lies between the same two launches either way.
+    enum Carry : unsigned { kCarryNone = 0u, kCarryStart = 1u, kCarryStop = 2u };
+    Scope(gpe_ctx *ctx, const char *name, Boundaries b = kOwnEvents, unsigned carry = kCarryNone);
     ~Scope();
 
    private:
     gpe_ctx *ctx_;
     int stat_ = -1;
-    int start_ = -1;                 // slot of ctx->scope_events
+    int start_ = -1;                 // slot of ctx->scope_events / ctx->scope_stamps
     bool shared_;
+    bool stamps_ = false;
+    unsigned carry_ = kCarryNone;
 };
 // Every enqueue onto c->stream inside a ScopeRegion says so (launches, async copies and memsets, event records other
 // than the scopes' own): that is what lets two scopes there share a boundary event.
-inline void note_enqueue(gpe_ctx *c) { c->scope_events.note_enqueue(); }
+// A boundary's timestamp that is still owed is written first, by a kernel of its own (scope_stamps.h).
+inline void note_enqueue(gpe_ctx *c)
+{
+    c->scope_events.note_enqueue();
+    c->scope_stamps.note_enqueue();
+    c->stamp_be.flush();
+}
+// For the launchers of the two gated sort kernels, BEFORE their note_enqueue: where the kernel's first workgroup writes
+// the owed timestamp (the kernel starts at that boundary), or NULL when none is owed.
+inline unsigned long long *scope_stamp_for_next_launch(gpe_ctx *c)
+{
+    const int64_t slot = c->stamp_be.take();
+    return slot < 0 ? nullptr : c->stamp_be.dev.buf + slot;
+}
 // A stretch of host code whose enqueues all call note_enqueue (native_collide).  Boundaries are never shared across
 // its ends: the code outside enqueues without saying so.
 class ScopeRegion {
    public:
-    explicit ScopeRegion(gpe_ctx *c) : c_(c) { c_->scope_events.enter_region(); }
-    ~ScopeRegion() { c_->scope_events.leave_region(); }
+    explicit ScopeRegion(gpe_ctx *c) : c_(c) { c_->scope_events.enter_region(); c_->scope_stamps.enter_region(); }
+    ~ScopeRegion() { c_->stamp_be.flush(); c_->scope_events.leave_region(); c_->scope_stamps.leave_region(); }
     ScopeRegion(const ScopeRegion &) = delete;
     ScopeRegion &operator=(const ScopeRegion &) = delete;
 
@@ -981,6 +1025,7 @@ struct OnesweepGate {
     int ticket_base = 0;                   // tile tickets at ctl[ticket_base + pass]
     const uint32_t *count_now = nullptr;   // first pass: *sorted_count = *count_now (NULL: n) -- the particles the grouping covers
     uint32_t *sorted_count = nullptr;
+    unsigned long long *stamp = nullptr;   // a profiling boundary at this launch: its first workgroup stores wall_clock64() here
 };
 gpe_status onesweep_sort(gpe_ctx *c, uint32_t *keys, uint32_t *vals, uint32_t *keys_b, uint32_t *vals_b,
                          uint64_t n, int passes, bool hist_ready, bool iota_vals, uint32_t **out_keys,

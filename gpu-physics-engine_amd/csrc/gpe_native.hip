@@ -48,6 +48,30 @@ void native_release(gpe_ctx *c)
 
 static gpe_status arena_reserve(gpe_ctx *c, uint64_t want);
 
+// The pinned words check_device_errors (gpe_api.hip) copies the sticky device-side error words into: once per context,
+// at the first synchronising call, so that gpe_sync enqueues its copies before it waits and waits once.  (Here, beside
+// the step's own pinned statistics: pinned host memory has two homes in the library, this file and k_shard.hip.)
+gpe_status error_words_reserve(gpe_ctx *c)
+{
+    if (c->err_words) return GPE_OK;
+    GPE_HIP(c, hipHostMalloc((void **)&c->err_words, 64, hipHostMallocDefault));
+    memset(c->err_words, 0, 64);
+    DevAlloc a;                                        // listed by gpe_guard_registry, state "pinned"
+    a.ptr = a.base = c->err_words; a.payload = a.total = 64; a.tag = "ctl.error_words";
+    c->guard.pinned.push_back(a);
+    return GPE_OK;
+}
+
+void error_words_release(gpe_ctx *c)
+{
+    if (!c->err_words) return;
+    auto &pinned = c->guard.pinned;                    // (the registry lists blocks that exist)
+    for (size_t i = pinned.size(); i-- > 0;)
+        if (pinned[i].ptr == c->err_words) pinned.erase(pinned.begin() + i);
+    (void)hipHostFree(c->err_words);
+    c->err_words = nullptr;
+}
+
 // The words the tiles publish (k_native_hash, k_native_publish_probe) while the host reads them: each word on its own.
 NativeStats native_read_stats(const NativeState &N)
 {
@@ -188,7 +212,9 @@ static gpe_status native_prepare_step(gpe_ctx *c, uint32_t **sorted_ids, bool al
     // (block key / blocks_x = key * magic >> 40: OnesweepGate::key_div_magic)
     const uint64_t div_magic = ((1ull << 40) + (uint64_t)N.blocks_x - 1) / (uint64_t)N.blocks_x;
     {
-        Scope s(c, "native/hash", Scope::kSharedBoundaries);
+        // (what follows the hash is the gated histogram or the first gated radix pass: either carries the boundary
+        // behind it)
+        Scope s(c, "native/hash", Scope::kSharedBoundaries, Scope::kCarryStop);
         // at least 4 keys per lane (measured: profiles/r01/tune_hash.txt)
         // (two particles per thread until the grid is full: 14.0 against 14.3 us at 1 M with four, 15.2 with one --
         // the kernel is launch and latency there; from 4 M particles on the grid is kHashGridMax either way)

@@ -436,8 +436,11 @@ __global__ __launch_bounds__(kHashBlock, 8) void k_native_hash(const float2 *__r
 // layout as the hash's flush (kHistCopies copies of 4 x 256 bins, two bins per 64-bit atomic).
 __global__ __launch_bounds__(kHistGatedBlock) void k_native_hist_gated(const uint32_t *__restrict__ keys, uint64_t n, int digits,
                                                                        uint32_t *__restrict__ hist4,
-                                                                       const uint32_t *__restrict__ need)
+                                                                       const uint32_t *__restrict__ need,
+                                                                       unsigned long long *stamp)
 {
+    // (a sampled step's boundary in front of this launch: scope_stamps.h)
+    if (stamp && blockIdx.x == 0 && threadIdx.x == 0) *stamp = wall_clock64();
     if (*need == 0u) return;
     __shared__ uint32_t s_hist[4 * 256];
     s_hist[threadIdx.x] = 0;
@@ -2777,8 +2780,10 @@ void launch_native_hash(gpe_ctx *c, bool ghosts, int grid, const float2 *pos, co
 void launch_native_hist_gated(gpe_ctx *c, int grid, const uint32_t *keys, uint64_t n, int digits, uint32_t *hist4,
                               const uint32_t *need)
 {
+    unsigned long long *stamp = scope_stamp_for_next_launch(c);
     note_enqueue(c);
-    hipLaunchKernelGGL(k_native_hist_gated, dim3(grid), dim3(kHistGatedBlock), 0, c->stream, keys, n, digits, hist4, need);
+    hipLaunchKernelGGL(k_native_hist_gated, dim3(grid), dim3(kHistGatedBlock), 0, c->stream, keys, n, digits, hist4, need,
+                       stamp);
 }
 
 void launch_native_check_box(gpe_ctx *c, const float2 *pos, uint64_t n, const uint32_t *n_valid_ptr, float cell_size,

@@ -154,6 +154,8 @@ __global__ __launch_bounds__(kOsBlock, GPE_OS_MINWAVES) void k_os_pass(const uin
     // Gated sort (the native step): the producer of the keys decides on the device whether this sort is needed at all
     // (k_native_hash: has any particle left the reach of the old block table?).  The passes are enqueued every step
     // and return here when the word is 0 -- the host never waits for the decision.
+    // (G.stamp: a sampled step's boundary in front of this launch, scope_stamps.h)
+    if (G.stamp && blockIdx.x == 0 && threadIdx.x == 0) *G.stamp = wall_clock64();
     if (G.need && *G.need == 0u) return;
     constexpr int kOsItems = ITEMS, kOsTile = kOsBlock * ITEMS, kOsWaveSpan = 64 * ITEMS;   // shadow the defaults
     __shared__ uint32_t s_stage[kOsTile];
@@ -499,7 +501,9 @@ gpe_status onesweep_sort(gpe_ctx *c, uint32_t *keys, uint32_t *vals, uint32_t *k
             GPE_HIP(c, hipMemsetAsync(ws.status, 0, ws.status_cap * sizeof(uint64_t), c->stream));
             ws.epoch = 1;
         }
-        Scope s(c, "sort/onesweep", Scope::kSharedBoundaries);
+        // (the pass carries the boundary in front of it, the next pass the one behind it; behind the last pass, which
+        // returns at once on most steps, it goes right in front of whatever is launched next)
+        Scope s(c, "sort/onesweep", Scope::kSharedBoundaries, Scope::kCarryStart | Scope::kCarryStop);
         const bool iota = (p == 0 && iota_vals);
         const bool small = os_items(n) == kOsItemsSmall;
         const auto kern = small ? (iota ? k_os_pass<true, kOsItemsSmall> : k_os_pass<false, kOsItemsSmall>)
@@ -516,6 +520,7 @@ gpe_status onesweep_sort(gpe_ctx *c, uint32_t *keys, uint32_t *vals, uint32_t *k
             }
             if (last) { g.fresh = gate->fresh; g.sorts = gate->sorts; g.sorts_seen = gate->sorts_seen; }
         }
+        g.stamp = scope_stamp_for_next_launch(c);
         note_enqueue(c);
         hipLaunchKernelGGL(kern, dim3((uint32_t)tiles), dim3(kOsBlock), 0, c->stream, ka, va, kb, vb, n,
                            (uint32_t)(8 * p), (uint32_t)p, ws.bases4, (u64 *)ws.status, ws.ctl, ws.epoch,

@@ -167,8 +167,9 @@ class Context:
                  "payload_bytes": z.payload_bytes} for z in rep.zones[:rep.listed]]
 
     def guard_registry(self):
-        """gpe_guard_registry: [(tag, payload bytes, slack bytes, "live" / "released")] -- the context's live device
-        allocations, then the last released one of every tag that has seen a release."""
+        """gpe_guard_registry: [(tag, payload bytes, slack bytes, "live" / "released" / "pinned")] -- the context's live
+        device allocations, then the last released one of every tag that has seen a release, then its pinned host blocks
+        (one entry per allocation made)."""
         need = C.c_uint64()
         self.call("gpe_guard_registry", None, 0, C.byref(need))
         buf = C.create_string_buffer(need.value)

@@ -94,8 +94,11 @@ enum {
                                      /* instead of a gated launch counting them when a sort is due; for A/B timing   */
     GPE_FLAG_GUARD_ALLOCS = 1024u,   /* tests: every device allocation of the context sits between two red zones     */
                                      /* filled with a canary, its fresh payload is poisoned (gpe_guard_check)        */
-    GPE_FLAG_HASH_INDEX64 = 2048u    /* NATIVE, diagnostic: the hash kernel indexes with 64 bits at every particle    */
+    GPE_FLAG_HASH_INDEX64 = 2048u,   /* NATIVE, diagnostic: the hash kernel indexes with 64 bits at every particle    */
                                      /* count (by default only where an index could pass 2^31); for tests, A/B timing */
+    GPE_FLAG_EVENT_SCOPES = 4096u    /* profiling scopes record hipEvents (as they did up to now) instead of writing  */
+                                     /* the GPU's timestamp counter into a device buffer; for A/B timing.  A context  */
+                                     /* on a stream lent by gpe_set_stream records events either way                  */
 };
 
 /* Fills *cfg with the reference's compile-time constants. */
@@ -1142,7 +1145,9 @@ gpe_status gpe_guard_check(gpe_ctx *ctx, gpe_guard_report *out);
 /* The registry of the context's device allocations (kept with and without the flag): one line
  * "tag payload_bytes slack_bytes live\n" per live allocation, then, with the flag, one
  * "tag payload_bytes slack_bytes released\n" per tag of which an allocation has been released (its last one; those
- * were checked when they went).  What the tests prove a growth with, and the coverage list of profiles/guard/ is from.
+ * were checked when they went), then one "tag bytes 0 pinned\n" per pinned host block the context has allocated (the
+ * error words gpe_sync reads: one per context).  What the tests prove a growth with, and the coverage list of
+ * profiles/guard/ is from.
  * NUL-terminated, truncated to capacity; *needed (may be NULL) receives the bytes the whole text takes. */
 gpe_status gpe_guard_registry(gpe_ctx *ctx, char *text, uint64_t capacity, uint64_t *needed);
 
