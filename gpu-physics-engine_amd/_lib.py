@@ -49,6 +49,8 @@ TRACERS_CONSUME = 1
 MONITOR_CONSUME = 1
 NEAREST_MAX_M = 64
 COLLIDERS_MAX = 4096
+BONDS_MAX, BOND_MAX_DEGREE, BOND_ITER_MAX = 4194304, 1024, 32
+BOND_ANCHOR, BOND_BROKEN = 1, 2
 EDIT_BY_INDEX, EDIT_BY_UID = 0, 1
 CLUSTER_BY_INDEX, CLUSTER_BY_UID = 0, 1
 VEL_ADD, VEL_SET, VEL_SCALE = 0, 1, 2
@@ -221,6 +223,20 @@ class GpeCollidersInfo(C.Structure):
                 ("grid_x", C.c_uint32), ("grid_y", C.c_uint32), ("list_entries", C.c_uint64)]
 
 
+class GpeBond(C.Structure):
+    """gpe_bond: particle uid_a tied to particle uid_b, or (BOND_ANCHOR, uid_b = UID_ABSENT) to the point (anchor_x,
+    anchor_y), at rest_length.  32 bytes."""
+    _fields_ = [("uid_a", C.c_uint32), ("uid_b", C.c_uint32), ("rest_length", C.c_float), ("stiffness", C.c_float),
+                ("max_length", C.c_float), ("flags", C.c_uint32), ("anchor_x", C.c_float), ("anchor_y", C.c_float)]
+
+
+class GpeBondsInfo(C.Structure):
+    """gpe_bonds_info: in struct_size; out the relaxations per pass, the bonds set and the distinct uids they name, and
+    since the last gpe_set_bonds the passes run, the bonds not broken / broken and the times the uids were looked up."""
+    _fields_ = [("struct_size", C.c_uint32), ("iterations", C.c_uint32), ("k", C.c_uint64), ("nodes", C.c_uint64),
+                ("passes", C.c_uint64), ("live", C.c_uint64), ("broken", C.c_uint64), ("resolves", C.c_uint64)]
+
+
 class GpeParticleEdit(C.Structure):
     """gpe_particle_edit: in struct_size / key_kind / k / keys and the field arrays (each may be NULL), out edited."""
     _fields_ = [("struct_size", C.c_uint32), ("key_kind", C.c_uint32), ("k", C.c_uint64),
@@ -287,6 +303,10 @@ SYMBOLS = [
     ("gpe_get_colliders", _I32, [_VP, C.POINTER(GpeCollider), _U64, C.POINTER(_U64)]),
     ("gpe_apply_colliders", _I32, [_VP]),
     ("gpe_get_colliders_info", _I32, [_VP, C.POINTER(GpeCollidersInfo)]),
+    ("gpe_set_bonds", _I32, [_VP, C.POINTER(GpeBond), _U64, C.c_uint32]),
+    ("gpe_get_bonds", _I32, [_VP, C.POINTER(GpeBond), C.POINTER(C.c_uint8), _U64, C.POINTER(_U64)]),
+    ("gpe_apply_bonds", _I32, [_VP]),
+    ("gpe_get_bonds_info", _I32, [_VP, C.POINTER(GpeBondsInfo)]),
     ("gpe_query_circle", _I32, [_VP, _F, _F, _F, C.POINTER(GpeQueryResult)]),
     ("gpe_query_box", _I32, [_VP, _F, _F, _F, _F, C.POINTER(GpeQueryResult)]),
     ("gpe_pick", _I32, [_VP, _F, _F, C.POINTER(GpeQueryResult)]),

@@ -431,6 +431,26 @@ struct ColliderState {
     uint64_t entries = 0;
 };
 
+// the distance bonds (gpe_set_bonds; gpe_bonds.hip, k_bonds.hip, bond_graph.h).  Step state: gpe_step / gpe_run relax them
+struct BondState {
+    std::vector<gpe_bond> set;                   // the bonds as the host gave them (empty: none, nothing is launched)
+    uint32_t iterations = 1;
+    uint64_t nodes = 0;                          // m: the distinct uids the bonds name
+    bool stale = true;                           // node_slot is out of date: set wherever tracers.stale is (behind it)
+    uint64_t passes = 0, resolves = 0;           // since the last gpe_set_bonds
+    // device side, read by index below the stated count
+    uint4 *rec = nullptr;                        // k: (node a, node b | anchor index, rest, w), bond_graph.h BondRecord
+    float *max_length = nullptr;                 // k, or NULL when no bond can break
+    float2 *anchors = nullptr;                   // one per anchor bond, or NULL
+    uint32_t n_anchors = 0;
+    uint32_t *node_uid = nullptr;                // m: the nodes' uids, ascending
+    uint32_t *node_slot = nullptr;               // m: each node's storage index, 0xffffffff for none (valid unless stale)
+    uint32_t *row_start = nullptr, *inc = nullptr;   // m + 1 / row_start[m]: a node's bonds, bond << 1 | side
+    float2 *corr = nullptr;                      // k: this relaxation's corrections
+    uint8_t *state = nullptr;                    // k: 0 acted, 1 broken (sticky), 2 inert in this relaxation
+    unsigned long long *broken = nullptr;        // one word: bonds broken
+};
+
 struct SortWorkspace {
     uint32_t *keys_b = nullptr, *vals_b = nullptr;   // ping-pong partners, cap entries each
     uint64_t cap = 0;
@@ -772,6 +792,7 @@ struct gpe_ctx {
     gpe::TracerState tracers;
     gpe::MonitorState monitor;
     gpe::ColliderState colliders;
+    gpe::BondState bonds;
     gpe::QueryWorkspace query_ws;
     gpe::ContactsWorkspace contacts_ws;
     gpe::ClustersWorkspace clusters_ws;
@@ -923,6 +944,11 @@ inline bool has_colliders(const gpe_ctx *c) { return !c->colliders.set.empty(); 
 gpe_status refuse_colliders(gpe_ctx *c, const char *who);   // GPE_ERR_UNSUPPORTED: sharding a context that holds colliders
 gpe_status colliders_after_step(gpe_ctx *c);       // after every step of gpe_step / gpe_run, before the observers
 void colliders_release(gpe_ctx *c);
+// gpe_bonds.hip: the distance bonds of a context that holds some
+inline bool has_bonds(const gpe_ctx *c) { return !c->bonds.set.empty(); }
+gpe_status refuse_bonds(gpe_ctx *c, const char *who);       // GPE_ERR_UNSUPPORTED: taking the uids from a context that holds bonds
+gpe_status bonds_after_step(gpe_ctx *c);           // after every step of gpe_step / gpe_run, before the colliders
+void bonds_release(gpe_ctx *c);
 
 // profiling scope: a pair of timestamps on ctx->stream when ctx->profiling, else nothing -- slots of the stamp buffer
 // (scope_stamps.h), or hipEvents where scope_uses_stamps() says no.  kSharedBoundaries: inside a ScopeRegion the scope
@@ -1147,6 +1173,9 @@ gpe_status launch_monitor_final(gpe_ctx *c, const void *partials, uint64_t n, ui
 gpe_status launch_colliders_pass(gpe_ctx *c, float2 *pos, const float *radius, uint64_t n, const uint32_t *cell_start,
                                  const uint32_t *items, const float4 *rec, uint32_t k, const ColliderGridView &view,
                                  unsigned long long *pushed);
+// distance bonds (k_bonds.hip): `iterations` relaxations of the k bonds of B over pos[0, n) in place, two launches each
+gpe_status launch_bonds_pass(gpe_ctx *c, float2 *pos, const float *radius, uint64_t n, const BondState &B, uint32_t k,
+                             uint32_t m, uint32_t iterations);
 // native pipeline: its host side (gpe_native.hip; the kernels and their launchers: k_native.hip, native_launch.h)
 gpe_status native_configure(gpe_ctx *c);
 bool native_should_run(gpe_ctx *c);

@@ -55,6 +55,29 @@ Measures = collections.namedtuple("Measures", [name for name, _ in L.GpeMeasures
 # set_colliders / colliders: the rows of gpe_collider (24 bytes each, the struct's layout)
 COLLIDER_DTYPE = np.dtype([(name, np.uint32 if ctype is C.c_uint32 else np.float32) for name, ctype in L.GpeCollider._fields_])
 assert COLLIDER_DTYPE.itemsize == C.sizeof(L.GpeCollider)
+# set_bonds / bonds: the rows of gpe_bond (32 bytes each, the struct's layout)
+BOND_DTYPE = np.dtype([(name, np.uint32 if ctype is C.c_uint32 else np.float32) for name, ctype in L.GpeBond._fields_])
+assert BOND_DTYPE.itemsize == C.sizeof(L.GpeBond)
+
+
+def pair_bonds(uid_a, uid_b, rest_length, stiffness=1.0, max_length=0.0):
+    """Rows of BOND_DTYPE that tie particle uid_a[i] to particle uid_b[i] (scalars are broadcast)."""
+    ua = np.asarray(uid_a, np.uint32).reshape(-1)
+    rows = np.zeros(len(ua), BOND_DTYPE)
+    rows["uid_a"], rows["uid_b"] = ua, uid_b
+    rows["rest_length"], rows["stiffness"], rows["max_length"] = rest_length, stiffness, max_length
+    return rows
+
+
+def anchor_bonds(uids, points, rest_length=0.0, stiffness=1.0, max_length=0.0):
+    """Rows of BOND_DTYPE that tie particle uids[i] to the fixed point points[i] (GPE_BOND_ANCHOR)."""
+    ua = np.asarray(uids, np.uint32).reshape(-1)
+    pts = np.asarray(points, np.float32).reshape(-1, 2)
+    rows = np.zeros(len(ua), BOND_DTYPE)
+    rows["uid_a"], rows["uid_b"], rows["flags"] = ua, L.UID_ABSENT, L.BOND_ANCHOR
+    rows["rest_length"], rows["stiffness"], rows["max_length"] = rest_length, stiffness, max_length
+    rows["anchor_x"], rows["anchor_y"] = pts[:, 0], pts[:, 1]
+    return rows
 
 
 class Context:
@@ -564,6 +587,39 @@ class ParticleSystem:
         info = L.GpeCollidersInfo(struct_size=C.sizeof(L.GpeCollidersInfo))
         self.ctx.call("gpe_get_colliders_info", C.byref(info))
         return {name: getattr(info, name) for name, _ in L.GpeCollidersInfo._fields_ if name != "struct_size"}
+
+    # Distance bonds (not in the reference; include/gpe.h): particles tied to each other, or to a fixed point, by uid,
+    # relaxed on the device after every update() / step of run(), before the colliders.  Step state: save() keeps them.
+    def set_bonds(self, bonds, iterations=1):
+        """gpe_set_bonds: replace the set by the rows of a BOND_DTYPE array (pair_bonds / anchor_bonds build them),
+        relaxed `iterations` times per pass; no rows clear it.  The broken flags and the counters start anew."""
+        rows = np.ascontiguousarray(bonds, BOND_DTYPE).reshape(-1)
+        k = len(rows)
+        self.ctx.call("gpe_set_bonds", rows.ctypes.data_as(C.POINTER(L.GpeBond)) if k else None, k, int(iterations))
+
+    def bonds(self):
+        """gpe_get_bonds -> (records BOND_DTYPE[k], broken bool[k])."""
+        k = C.c_uint64()
+        self.ctx.call("gpe_get_bonds", None, None, 0, C.byref(k))
+        rows = np.zeros(max(k.value, 1), BOND_DTYPE)
+        broken = np.zeros(max(k.value, 1), np.uint8)
+        self.ctx.call("gpe_get_bonds", rows.ctypes.data_as(C.POINTER(L.GpeBond)),
+                      broken.ctypes.data_as(C.POINTER(C.c_uint8)), k.value, C.byref(k))
+        return rows[:k.value], broken[:k.value].astype(bool)
+
+    def clear_bonds(self):
+        """gpe_set_bonds with k = 0."""
+        self.ctx.call("gpe_set_bonds", None, 0, 1)
+
+    def apply_bonds(self):
+        """gpe_apply_bonds: one pass now (the hook of a host that steps module by module).  Does not synchronise."""
+        self.ctx.call("gpe_apply_bonds")
+
+    def bonds_info(self):
+        """gpe_get_bonds_info -> dict(iterations, k, nodes, passes, live, broken, resolves).  Blocks like a download."""
+        info = L.GpeBondsInfo(struct_size=C.sizeof(L.GpeBondsInfo))
+        self.ctx.call("gpe_get_bonds_info", C.byref(info))
+        return {name: getattr(info, name) for name, _ in L.GpeBondsInfo._fields_ if name != "struct_size"}
 
     # Region queries and picking (not in the reference; include/gpe.h): which particles lie in a circle or a box, or
     # under a point, counted and gathered on the device.  The context is left exactly as it was.
@@ -1109,6 +1165,26 @@ class State:
         """ParticleSystem.colliders_info -> dict(k, passes, pushed, grid_x, grid_y, list_entries)."""
         return self.particles.colliders_info()
 
+    def set_bonds(self, bonds, iterations=1):
+        """ParticleSystem.set_bonds: distance bonds (rows of BOND_DTYPE) relaxed after every step, before the colliders."""
+        self.particles.set_bonds(bonds, iterations)
+
+    def bonds(self):
+        """ParticleSystem.bonds -> (records BOND_DTYPE[k], broken bool[k])."""
+        return self.particles.bonds()
+
+    def clear_bonds(self):
+        """ParticleSystem.clear_bonds."""
+        self.particles.clear_bonds()
+
+    def apply_bonds(self):
+        """ParticleSystem.apply_bonds: one pass now."""
+        self.particles.apply_bonds()
+
+    def bonds_info(self):
+        """ParticleSystem.bonds_info -> dict(iterations, k, nodes, passes, live, broken, resolves)."""
+        return self.particles.bonds_info()
+
     def query_circle(self, center, radius):
         """ParticleSystem.query_circle -> QueryResult(index, uid, pos, prev, radius)."""
         return self.particles.query_circle(center, radius)
@@ -1206,8 +1282,13 @@ class State:
         one gpe_set_particles derives from the saved radii (Grid.new_without_camera) that radius (`grid_max_radius`).
         A tracer recorder (tracers_begin) is not stored: it is observation state, not step state -- a loaded State steps
         the same bits without it and is armed again by its host.  The run monitor (monitor_begin) is not stored either,
-        for the same reason.  Static colliders are step state: a set that is present is written (`colliders`)."""
+        for the same reason.  Static colliders are step state: a set that is present is written (`colliders`), and so
+        are distance bonds with their relaxation count and broken flags (`bonds`, `bond_iterations`, `bonds_broken`)."""
         extra = {}
+        bonds, broken = self.bonds()
+        if len(bonds):
+            extra.update(bonds=bonds, bond_iterations=np.array([self.bonds_info()["iterations"]], np.uint32),
+                         bonds_broken=broken)
         caps = self.colliders()
         if len(caps):
             extra.update(colliders=caps)
@@ -1246,6 +1327,10 @@ class State:
                 st.ctx.call("gpe_grid_set_max_radius", float(d["grid_max_radius"][0]))
             if "colliders" in d.files:
                 st.set_colliders(d["colliders"])
+            if "bonds" in d.files:                                 # (after the uids they name; a broken bond starts broken)
+                rows = d["bonds"].astype(BOND_DTYPE)
+                rows["flags"] |= np.where(d["bonds_broken"], L.BOND_BROKEN, 0).astype(np.uint32)
+                st.set_bonds(rows, int(d["bond_iterations"][0]))
             return st
 
     def close(self):

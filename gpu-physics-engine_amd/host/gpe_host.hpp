@@ -355,6 +355,36 @@ class ParticleSystem {
         ctx_->call(gpe_get_colliders_info(ctx_->raw(), &info));
         return info;
     }
+    // not in the reference: distance bonds between particles named by uid, or from a particle to a fixed point
+    // (include/gpe.h), relaxed on the device after every step of gpe_step / gpe_run, before the static colliders.
+    // Step state: a snapshot keeps the set and the broken flags (a broken bond is given back with GPE_BOND_BROKEN).
+    void set_bonds(const std::vector<gpe_bond> &bonds, uint32_t iterations = 1)
+    {
+        ctx_->call(gpe_set_bonds(ctx_->raw(), bonds.empty() ? nullptr : bonds.data(), bonds.size(), iterations));
+    }
+    struct Bonds {
+        std::vector<gpe_bond> records;
+        std::vector<uint8_t> broken;
+    };
+    Bonds bonds() const
+    {
+        uint64_t k = 0;
+        ctx_->call(gpe_get_bonds(ctx_->raw(), nullptr, nullptr, 0, &k));
+        Bonds out;
+        out.records.resize(k);
+        out.broken.resize(k);
+        ctx_->call(gpe_get_bonds(ctx_->raw(), k ? out.records.data() : nullptr, k ? out.broken.data() : nullptr, k, &k));
+        return out;
+    }
+    void clear_bonds() { ctx_->call(gpe_set_bonds(ctx_->raw(), nullptr, 0, 1)); }
+    void apply_bonds() { ctx_->call(gpe_apply_bonds(ctx_->raw())); }   // one pass now: the hook of the per-module calls
+    gpe_bonds_info bonds_info() const
+    {
+        gpe_bonds_info info{};
+        info.struct_size = sizeof(info);
+        ctx_->call(gpe_get_bonds_info(ctx_->raw(), &info));
+        return info;
+    }
     // not in the reference: every particle in a circle / box, or the one under a point (include/gpe.h), ascending
     // storage index; uid stays empty while uids are off.  pick() returns no rows when no disc contains the point.
     struct QueryResult {

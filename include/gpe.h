@@ -395,6 +395,74 @@ gpe_status gpe_get_colliders(const gpe_ctx *ctx, gpe_collider *out, uint64_t cap
 gpe_status gpe_apply_colliders(gpe_ctx *ctx);                              /* one pass now, stream-ordered, no sync */
 gpe_status gpe_get_colliders_info(gpe_ctx *ctx, gpe_colliders_info *info); /* synchronises (reads the device counters) */
 
+/* ---- distance bonds (not in the reference) ------------------------------------------------------------------------
+ * Ties between particles: a rope, a chain, a cloth, a soft body, a pinned object, a sheet that tears.  A bond holds two
+ * particles, named by uid (gpe_enable_uids must be on), at a rest length; an anchor bond (GPE_BOND_ANCHOR) holds one
+ * particle to a fixed point.  While a context holds a set, gpe_step and every iteration of gpe_run run one pass after
+ * the step, BEFORE the static colliders (walls keep the last word) and the tracers and the monitor, stream-ordered, on
+ * the device (csrc/k_bonds.hip): step -> bonds -> colliders -> tracers / monitor.  The per-module calls run no pass:
+ * gpe_apply_bonds is their hook.  A context without bonds launches and allocates exactly what it does without this
+ * section.
+ *  - One relaxation (csrc/k_bond.h is the one definition).  Every bond is judged from the positions the relaxation
+ *    starts with, in IEEE binary32, one rounding per operation, left to right, no FMA, `/` and sqrtf correctly
+ *    rounded; a = particle uid_a, b = particle uid_b or the anchor point:
+ *      dx = bx-ax; dy = by-ay;  h = dx*dx + dy*dy;  d = sqrtf(h)
+ *      inert this relaxation unless d > 0 and d < +inf         (NaN, coincident centres, overflow: left alone)
+ *      if max_length > 0 and d > max_length: the bond breaks   (strict; sticky: it never acts again)
+ *      e = d - rest_length;  f = e / d;  g = f * w;  cx = g*dx;  cy = g*dy
+ *    a receives (+cx, +cy), b (-cx, -cy); w = 0.5f * stiffness for a pair, stiffness for an anchor (whose point
+ *    receives nothing).  A bond one of whose uids names no live particle is inert and NOT broken: it acts again when
+ *    the uid reappears (gpe_set_uids).  A particle with at least one acting bond moves to p + acc, acc summed from
+ *    +0.0f over its acting bonds in ascending bond index (inert and broken bonds are skipped, not added as zero), then
+ *    K12's clamp with its stored radius: clamp(x, r, W - r), clamp(y, r, H - r).  Only pos is written: prev and radius
+ *    never, so the velocity change is the one Verlet implies.  Every other particle keeps every bit, unclamped.
+ *  - A pass relaxes the set `iterations` times (Jacobi: no relaxation reads what it has written itself), so the
+ *    result depends on the set and the particles alone, never on launch order, storage order or mode.
+ *  - What a bond is not: there is no angular constraint (a chain folds freely); Jacobi relaxation converges slowly
+ *    along stiff long chains, which need iterations; a rest length below the sum of the two radii fights the collision
+ *    solver, which pushes the pair apart again in the next step.
+ *  - The set and its broken flags are step state: they survive adds, removals, edits, kicks, re-sorts, growth,
+ *    gpe_set_mode and gpe_set_particles (which renumbers the uids from 0: the bonds then name the new particles).  After
+ *    a call that moves, adds or removes particles the next pass looks its uids up again (that synchronises once); every
+ *    other pass only enqueues.
+ *  - gpe_set_bonds replaces the set (k == 0 clears it and frees its buffers), clears the broken flags and zeroes the
+ *    counters; it synchronises.  A bond given with GPE_BOND_BROKEN starts broken: that is how a snapshot restores one;
+ *    the bit is not kept in the record.  -0.0 in rest_length / max_length is stored as +0.  The same pair may be
+ *    listed twice: both bonds act.  gpe_get_bonds delivers the first min(k, capacity) records into out and their
+ *    broken flags (1 / 0) into broken_out (each may be NULL) and the number set into *k; it synchronises.
+ *    gpe_apply_bonds with no bonds or no particles: GPE_OK, nothing done.
+ *  - Errors (the previous set stays untouched): a NULL ctx, NULL bonds with k > 0, k > GPE_BONDS_MAX, iterations
+ *    outside 1 .. GPE_BOND_ITER_MAX, a rest_length or max_length that is NaN, infinite or negative, a stiffness that is
+ *    NaN or outside [0, 1], unknown flag bits, uid_a == GPE_UID_ABSENT, uid_a == uid_b, an anchor whose uid_b is not
+ *    GPE_UID_ABSENT or a pair whose uid_b is, a non-finite anchor coordinate, a uid with more than GPE_BOND_MAX_DEGREE
+ *    bonds, a struct_size below the struct's: GPE_ERR_INVALID_ARG.  Uids off: GPE_ERR_STATE.  gpe_set_bonds on a
+ *    sharded context, and gpe_enable_uids(ctx, 0), gpe_shard_set_particles, gpe_use_order_keys(ctx, 1) and
+ *    gpe_set_counts on a context that holds bonds: GPE_ERR_UNSUPPORTED. */
+#define GPE_BONDS_MAX        4194304u   /* a 1 M-particle sheet has about 2 M structural bonds */
+#define GPE_BOND_MAX_DEGREE  1024u      /* bonds per particle: one lane walks them in order */
+#define GPE_BOND_ITER_MAX    32u
+#define GPE_BOND_ANCHOR      1u         /* flags: uid_b unused, a is tied to (anchor_x, anchor_y) */
+#define GPE_BOND_BROKEN      2u         /* flags, gpe_set_bonds only: the bond starts broken */
+typedef struct gpe_bond {               /* 32 bytes */
+    uint32_t uid_a, uid_b;              /* uid_b == GPE_UID_ABSENT iff GPE_BOND_ANCHOR */
+    float rest_length;                  /* finite, >= 0 */
+    float stiffness;                    /* in [0, 1]: the share of the error removed per relaxation */
+    float max_length;                   /* finite, >= 0; 0: never breaks; else breaks once its length > max_length */
+    uint32_t flags;
+    float anchor_x, anchor_y;           /* finite; read only with GPE_BOND_ANCHOR */
+} gpe_bond;
+typedef struct gpe_bonds_info {
+    uint32_t struct_size, iterations;  /* in / relaxations per pass                                        */
+    uint64_t k, nodes;                 /* bonds set / distinct uids they name                              */
+    uint64_t passes;                   /* passes enqueued since the last gpe_set_bonds                     */
+    uint64_t live, broken;             /* bonds not broken / broken (integer atomics only); live + broken = k */
+    uint64_t resolves;                 /* times the uids were looked up again since the last gpe_set_bonds */
+} gpe_bonds_info;                      /* 56 bytes */
+gpe_status gpe_set_bonds(gpe_ctx *ctx, const gpe_bond *bonds, uint64_t k, uint32_t iterations);
+gpe_status gpe_get_bonds(gpe_ctx *ctx, gpe_bond *out, uint8_t *broken_out, uint64_t capacity, uint64_t *k);
+gpe_status gpe_apply_bonds(gpe_ctx *ctx);                          /* one pass now, stream-ordered, no sync */
+gpe_status gpe_get_bonds_info(gpe_ctx *ctx, gpe_bonds_info *info); /* synchronises (reads the device counter) */
+
 /* ---- region queries and picking (not in the reference) ------------------------------------------------------
  * Which particles lie in a region, or under a point, without downloading every position: full passes over the
  * particles on the device (csrc/k_query.hip) that change nothing on the context.  Positions, prev, radii, uids, the
