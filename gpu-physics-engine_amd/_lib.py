@@ -51,6 +51,8 @@ NEAREST_MAX_M = 64
 COLLIDERS_MAX = 4096
 BONDS_MAX, BOND_MAX_DEGREE, BOND_ITER_MAX = 4194304, 1024, 32
 BOND_ANCHOR, BOND_BROKEN = 1, 2
+BODIES_MAX, BODY_MAX_MEMBERS, BODY_MEMBERS_MAX = 1048576, 4096, 16777216
+BODY_BROKEN = 1
 EDIT_BY_INDEX, EDIT_BY_UID = 0, 1
 CLUSTER_BY_INDEX, CLUSTER_BY_UID = 0, 1
 VEL_ADD, VEL_SET, VEL_SCALE = 0, 1, 2
@@ -237,6 +239,19 @@ class GpeBondsInfo(C.Structure):
                 ("passes", C.c_uint64), ("live", C.c_uint64), ("broken", C.c_uint64), ("resolves", C.c_uint64)]
 
 
+class GpeBody(C.Structure):
+    """gpe_body: members [first, first + count) of the set's member arrays keep their rest shape.  24 bytes."""
+    _fields_ = [("first", C.c_uint32), ("count", C.c_uint32), ("stiffness", C.c_float), ("break_distance", C.c_float),
+                ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class GpeBodiesInfo(C.Structure):
+    """gpe_bodies_info: in struct_size; out the bodies set and their members, and since the last gpe_set_bodies the
+    passes run, the bodies not broken / broken and the times the uids were looked up."""
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("k", C.c_uint64), ("members", C.c_uint64),
+                ("passes", C.c_uint64), ("live", C.c_uint64), ("broken", C.c_uint64), ("resolves", C.c_uint64)]
+
+
 class GpeParticleEdit(C.Structure):
     """gpe_particle_edit: in struct_size / key_kind / k / keys and the field arrays (each may be NULL), out edited."""
     _fields_ = [("struct_size", C.c_uint32), ("key_kind", C.c_uint32), ("k", C.c_uint64),
@@ -307,6 +322,12 @@ SYMBOLS = [
     ("gpe_get_bonds", _I32, [_VP, C.POINTER(GpeBond), C.POINTER(C.c_uint8), _U64, C.POINTER(_U64)]),
     ("gpe_apply_bonds", _I32, [_VP]),
     ("gpe_get_bonds_info", _I32, [_VP, C.POINTER(GpeBondsInfo)]),
+    ("gpe_set_bodies", _I32, [_VP, C.POINTER(GpeBody), _U64, C.POINTER(C.c_uint32), C.POINTER(C.c_float), _U64]),
+    ("gpe_get_bodies", _I32, [_VP, C.POINTER(GpeBody), C.POINTER(C.c_uint8), _U64, C.POINTER(_U64),
+                              C.POINTER(C.c_uint32), C.POINTER(C.c_float), _U64, C.POINTER(_U64)]),
+    ("gpe_apply_bodies", _I32, [_VP]),
+    ("gpe_get_body_poses", _I32, [_VP, C.POINTER(C.c_float), _U64, C.POINTER(_U64)]),
+    ("gpe_get_bodies_info", _I32, [_VP, C.POINTER(GpeBodiesInfo)]),
     ("gpe_query_circle", _I32, [_VP, _F, _F, _F, C.POINTER(GpeQueryResult)]),
     ("gpe_query_box", _I32, [_VP, _F, _F, _F, _F, C.POINTER(GpeQueryResult)]),
     ("gpe_pick", _I32, [_VP, _F, _F, C.POINTER(GpeQueryResult)]),

@@ -1,6 +1,6 @@
 // gpe_api.hip -- the extern "C" boundary of include/gpe.h: context, device memory, particle buffers, set / add / remove,
 // uids, step ordering, downloads, profiling.  The queries are in gpe_queries.hip, the checked add, edits and kicks in
-// gpe_edits.hip, the tracers and the monitor in gpe_observe.hip, the static colliders in gpe_colliders.hip, the distance bonds in gpe_bonds.hip.  All device work goes to one in-order hipStream per context.
+// gpe_edits.hip, the tracers and the monitor in gpe_observe.hip, the static colliders in gpe_colliders.hip, the distance bonds in gpe_bonds.hip, the rigid and soft bodies in gpe_bodies.hip.  All device work goes to one in-order hipStream per context.
 #include <math.h>
 #include <stddef.h>
 #include <stdlib.h>
@@ -631,6 +631,7 @@ static gpe_status do_remove(gpe_ctx *c, const uint8_t *mask, float x, float y, f
         c->uid.map_valid = false;
         c->tracers.stale = true;
         c->bonds.stale = true;
+        c->bodies.stale = true;
     }
     c->n = survivors;
     c->n_owned = survivors;
@@ -663,6 +664,7 @@ static gpe_status uids_switch_on(gpe_ctx *c)
     u.map_valid = false;
     c->tracers.stale = true;
     c->bonds.stale = true;
+    c->bodies.stale = true;
     return GPE_OK;
 }
 
@@ -732,6 +734,7 @@ static void uid_release(gpe_ctx *c)
     u.map_valid = false;
     c->tracers.stale = true;
     c->bonds.stale = true;
+    c->bodies.stale = true;
 }
 
 // ---- step pieces ------------------------------------------------------------------------------------
@@ -750,6 +753,7 @@ static gpe_status do_resort(gpe_ctx *c)
         c->uid.map_valid = false;
         c->tracers.stale = true;
         c->bonds.stale = true;
+        c->bodies.stale = true;
     } else {
         GPE_TRY(launch_rearrange(c, c->pos, c->prev, c->radius, c->particle_ids, c->n, c->pos_copy,
                                  c->prev_copy, c->radius_copy));
@@ -996,6 +1000,7 @@ gpe_status gpe_destroy(gpe_ctx *c)
     observers_release(c);
     colliders_release(c);
     bonds_release(c);
+    bodies_release(c);
     sort_release(c);
     scan_release(c);
     onesweep_release(c);
@@ -1087,6 +1092,7 @@ gpe_status gpe_set_particles(gpe_ctx *c, const float *pos_xy, const float *prev_
         c->uid.map_valid = false;
         c->tracers.stale = true;
         c->bonds.stale = true;
+        c->bodies.stale = true;
     }
     c->max_radius = max_abs_radius(radius, n, radius[0]);
     c->grid_max_radius = c->max_radius;       // Grid::new (grid.rs:66-71)
@@ -1119,6 +1125,7 @@ gpe_status gpe_add_particles(gpe_ctx *c, const float *pos_xy, const float *radiu
         c->uid.map_valid = false;
         c->tracers.stale = true;
         c->bonds.stale = true;
+        c->bodies.stale = true;
     }
     // particle_system.rs:198: max_radius = max(max_radius, r)
     for (uint64_t i = 0; i < n_add; ++i) c->max_radius = fmaxf(c->max_radius, radius[i]);
@@ -1162,6 +1169,7 @@ gpe_status gpe_enable_uids(gpe_ctx *c, int32_t enable)
     if (!enable) {
         if (!u.on) return GPE_OK;
         if (has_bonds(c)) return refuse_bonds(c, "gpe_enable_uids");   // (they name their particles by uid)
+        if (has_bodies(c)) return refuse_bodies(c, "gpe_enable_uids"); // (and so do they)
         GPE_HIP(c, hipSetDevice(c->device));
         GPE_HIP(c, hipStreamSynchronize(c->stream));           // (a re-sort in flight may still read them)
         uid_release(c);
@@ -1218,6 +1226,7 @@ gpe_status gpe_set_uids(gpe_ctx *c, const uint32_t *uids, uint64_t n)
     u.map_valid = true;                                        // the map just built is the new uids'
     c->tracers.stale = true;                                   // (uid_map_build cleared map_valid on the way)
     c->bonds.stale = true;
+    c->bodies.stale = true;
     return GPE_OK;
 }
 
@@ -1460,6 +1469,7 @@ gpe_status gpe_step(gpe_ctx *c, float dt, uint32_t flags)
     GPE_HIP(c, hipSetDevice(c->device));
     GPE_TRY(do_step(c, dt, flags));
     GPE_TRY(bonds_after_step(c));
+    GPE_TRY(bodies_after_step(c));
     GPE_TRY(colliders_after_step(c));
     return observers_after_step(c);
 }
@@ -1484,6 +1494,7 @@ gpe_status gpe_run(gpe_ctx *c, float dt, uint64_t steps, uint64_t resort_every, 
         const bool resort = (s == 0 && resort_first) || (resort_every && s > 0 && (s % resort_every) == 0);
         rc = do_step(c, dt, resort ? GPE_STEP_RESORT : 0u);
         if (rc == GPE_OK) rc = bonds_after_step(c);
+        if (rc == GPE_OK) rc = bodies_after_step(c);
         if (rc == GPE_OK) rc = colliders_after_step(c);
         if (rc == GPE_OK) rc = observers_after_step(c);
     }
@@ -1708,6 +1719,7 @@ gpe_status gpe_set_counts(gpe_ctx *c, uint64_t n_total, uint64_t n_owned)
     if (n_total == 0 || n_total > c->cap || n_owned > n_total)
         return fail(c, GPE_ERR_INVALID_ARG, "gpe_set_counts: need 0 < n_owned <= n_total <= capacity");
     if (has_bonds(c)) return refuse_bonds(c, "gpe_set_counts");        // (before the uids they need: the more telling refusal)
+    if (has_bodies(c)) return refuse_bodies(c, "gpe_set_counts");
     if (c->uid.on) return fail(c, GPE_ERR_UNSUPPORTED, "gpe_set_counts: not supported while uids are on");
     if (has_colliders(c)) return refuse_colliders(c, "gpe_set_counts");
     c->n = n_total;
@@ -1719,6 +1731,7 @@ gpe_status gpe_use_order_keys(gpe_ctx *c, int32_t enable)
 {
     if (!c) return GPE_ERR_INVALID_ARG;
     if (enable && has_bonds(c)) return refuse_bonds(c, "gpe_use_order_keys");
+    if (enable && has_bodies(c)) return refuse_bodies(c, "gpe_use_order_keys");
     if (enable && c->uid.on)
         return fail(c, GPE_ERR_UNSUPPORTED, "gpe_use_order_keys: sharded runs carry order keys, not uids (uids are on)");
     if (enable && has_colliders(c)) return refuse_colliders(c, "gpe_use_order_keys");

@@ -157,6 +157,7 @@ gpe_status gpe_add_particles_free(gpe_ctx *c, gpe_particle_spawn *sp)
             c->uid.map_valid = false;
             c->tracers.stale = true;
             c->bonds.stale = true;
+            c->bodies.stale = true;
         }
         // as gpe_add_particles of the added candidates: max_radius = max(max_radius, r), in input order
         for (uint64_t i = 0; i < k; ++i)

@@ -451,6 +451,26 @@ struct BondState {
     unsigned long long *broken = nullptr;        // one word: bonds broken
 };
 
+// the rigid and soft bodies (gpe_set_bodies; gpe_bodies.hip, k_bodies.hip, body_table.h).  Step state: gpe_step / gpe_run match them
+struct BodyState {
+    std::vector<gpe_body> set;                   // the bodies as the host gave them (empty: none, nothing is launched)
+    std::vector<uint32_t> member_uid_host;       // members: as the host gave them (gpe_get_bodies)
+    std::vector<float> member_rest_host;         // 2 * members
+    uint64_t members = 0;
+    bool stale = true;                           // member_slot is out of date: set wherever bonds.stale is (behind it)
+    uint64_t passes = 0, resolves = 0;           // since the last gpe_set_bodies
+    uint32_t class_start[7] = {0, 0, 0, 0, 0, 0, 0};   // order[class_start[q], class_start[q + 1]): the bodies of width 2 << q
+    // device side, read by index below the stated count
+    uint4 *rec = nullptr;                        // k: (first, count, stiffness, bd2), body_table.h BodyRecord
+    uint32_t *order = nullptr;                   // k: body indices by width class
+    uint32_t *member_uid = nullptr;              // members
+    uint32_t *member_slot = nullptr;             // members: each member's storage index, 0xffffffff for none (valid unless stale)
+    float2 *member_rest = nullptr;               // members
+    float4 *pose = nullptr;                      // k: (cx, cy, co, si) of the last pass, NaNs while inert or broken
+    uint8_t *state = nullptr;                    // k: 0 acted, 1 broken (sticky), 2 inert in the last pass
+    unsigned long long *broken = nullptr;        // one word: bodies broken
+};
+
 struct SortWorkspace {
     uint32_t *keys_b = nullptr, *vals_b = nullptr;   // ping-pong partners, cap entries each
     uint64_t cap = 0;
@@ -793,6 +813,7 @@ struct gpe_ctx {
     gpe::MonitorState monitor;
     gpe::ColliderState colliders;
     gpe::BondState bonds;
+    gpe::BodyState bodies;
     gpe::QueryWorkspace query_ws;
     gpe::ContactsWorkspace contacts_ws;
     gpe::ClustersWorkspace clusters_ws;
@@ -949,6 +970,11 @@ inline bool has_bonds(const gpe_ctx *c) { return !c->bonds.set.empty(); }
 gpe_status refuse_bonds(gpe_ctx *c, const char *who);       // GPE_ERR_UNSUPPORTED: taking the uids from a context that holds bonds
 gpe_status bonds_after_step(gpe_ctx *c);           // after every step of gpe_step / gpe_run, before the colliders
 void bonds_release(gpe_ctx *c);
+// gpe_bodies.hip: the rigid and soft bodies of a context that holds some
+inline bool has_bodies(const gpe_ctx *c) { return !c->bodies.set.empty(); }
+gpe_status refuse_bodies(gpe_ctx *c, const char *who);      // GPE_ERR_UNSUPPORTED: taking the uids from a context that holds bodies
+gpe_status bodies_after_step(gpe_ctx *c);          // after every step of gpe_step / gpe_run, behind the bonds, before the colliders
+void bodies_release(gpe_ctx *c);
 
 // profiling scope: a pair of timestamps on ctx->stream when ctx->profiling, else nothing -- slots of the stamp buffer
 // (scope_stamps.h), or hipEvents where scope_uses_stamps() says no.  kSharedBoundaries: inside a ScopeRegion the scope
@@ -1176,6 +1202,9 @@ gpe_status launch_colliders_pass(gpe_ctx *c, float2 *pos, const float *radius, u
 // distance bonds (k_bonds.hip): `iterations` relaxations of the k bonds of B over pos[0, n) in place, two launches each
 gpe_status launch_bonds_pass(gpe_ctx *c, float2 *pos, const float *radius, uint64_t n, const BondState &B, uint32_t k,
                              uint32_t m, uint32_t iterations);
+// rigid and soft bodies (k_bodies.hip): one shape matching pass of the k bodies of B over pos[0, n) in place, one launch
+// per non-empty width class
+gpe_status launch_bodies_pass(gpe_ctx *c, float2 *pos, const float *radius, uint64_t n, const BodyState &B, uint32_t k);
 // native pipeline: its host side (gpe_native.hip; the kernels and their launchers: k_native.hip, native_launch.h)
 gpe_status native_configure(gpe_ctx *c);
 bool native_should_run(gpe_ctx *c);

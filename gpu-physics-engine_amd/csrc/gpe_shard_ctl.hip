@@ -742,6 +742,7 @@ gpe_status gpe_shard_set_particles(gpe_ctx *c, const float *pos_xy, const float 
 {
     if (!c) return GPE_ERR_INVALID_ARG;
     if (has_bonds(c)) return refuse_bonds(c, "gpe_shard_set_particles");
+    if (has_bodies(c)) return refuse_bodies(c, "gpe_shard_set_particles");
     if (c->uid.on)
         return fail(c, GPE_ERR_UNSUPPORTED, "gpe_shard_set_particles: sharded runs carry order keys, not uids (uids are on)");
     if (has_colliders(c)) return refuse_colliders(c, "gpe_shard_set_particles");

@@ -80,6 +80,22 @@ def anchor_bonds(uids, points, rest_length=0.0, stiffness=1.0, max_length=0.0):
     return rows
 
 
+# set_bodies / bodies: the rows of gpe_body (24 bytes each, the struct's layout)
+BODY_DTYPE = np.dtype([(name, np.uint32 if ctype is C.c_uint32 else np.float32) for name, ctype in L.GpeBody._fields_])
+assert BODY_DTYPE.itemsize == C.sizeof(L.GpeBody)
+
+
+def body_rows(counts, stiffness=1.0, break_distance=0.0):
+    """Rows of BODY_DTYPE for bodies of counts[i] members each, laid out one behind the other in the member arrays
+    (stiffness and break_distance: scalars, or one value per body)."""
+    counts = np.asarray(counts, np.uint32).reshape(-1)
+    rows = np.zeros(len(counts), BODY_DTYPE)
+    rows["count"] = counts
+    rows["first"] = np.cumsum(counts, dtype=np.uint64) - counts
+    rows["stiffness"], rows["break_distance"] = stiffness, break_distance
+    return rows
+
+
 class Context:
     """WgpuContext::new_for_test() stand-in (wgpu_context.rs:73-101): device + queue == HIP stream."""
 
@@ -620,6 +636,71 @@ class ParticleSystem:
         info = L.GpeBondsInfo(struct_size=C.sizeof(L.GpeBondsInfo))
         self.ctx.call("gpe_get_bonds_info", C.byref(info))
         return {name: getattr(info, name) for name, _ in L.GpeBondsInfo._fields_ if name != "struct_size"}
+
+    # Rigid and soft bodies (not in the reference; include/gpe.h): groups of particles, named by uid, that keep their rest
+    # shape: one shape matching pass on the device after every update() / step of run(), behind the bonds and before the
+    # colliders.  Step state: save() keeps them.
+    def set_bodies(self, bodies, member_uid, member_rest):
+        """gpe_set_bodies: replace the set by the rows of a BODY_DTYPE array (bodies_from_groups builds them) over the
+        members' uids u32[m] and rest positions f32[m, 2]; no rows clear it.  The broken flags and the counters start
+        anew."""
+        rows = np.ascontiguousarray(bodies, BODY_DTYPE).reshape(-1)
+        uid = np.ascontiguousarray(member_uid, np.uint32).reshape(-1)
+        rest = np.ascontiguousarray(member_rest, np.float32).reshape(-1)
+        if len(rest) != 2 * len(uid):
+            raise ValueError("set_bodies: member_rest must hold two coordinates per member uid")
+        k = len(rows)
+        self.ctx.call("gpe_set_bodies", rows.ctypes.data_as(C.POINTER(L.GpeBody)) if k else None, k,
+                      uid.ctypes.data_as(C.POINTER(C.c_uint32)) if k else None,
+                      rest.ctypes.data_as(C.POINTER(C.c_float)) if k else None, len(uid))
+
+    def bodies_from_groups(self, uid_groups, stiffness=1.0, break_distance=0.0):
+        """(rows of BODY_DTYPE, member_uid u32[m], member_rest f32[m, 2]) for set_bodies: one body per group of uids,
+        the particles' current positions captured as the rest shape.  stiffness and break_distance: scalars, or one
+        value per group."""
+        groups = [np.asarray(g, np.uint32).reshape(-1) for g in uid_groups]
+        member_uid = np.concatenate(groups) if groups else np.zeros(0, np.uint32)
+        index, pos, _, _ = self.find_uids(member_uid)
+        if (index == L.UID_ABSENT).any():
+            raise ValueError("bodies_from_groups: a uid names no live particle")
+        return body_rows([len(g) for g in groups], stiffness, break_distance), member_uid, pos.copy()
+
+    def bodies(self):
+        """gpe_get_bodies -> (records BODY_DTYPE[k], broken bool[k], member_uid u32[m], member_rest f32[m, 2])."""
+        k, m = C.c_uint64(), C.c_uint64()
+        self.ctx.call("gpe_get_bodies", None, None, 0, C.byref(k), None, None, 0, C.byref(m))
+        rows = np.zeros(max(k.value, 1), BODY_DTYPE)
+        broken = np.zeros(max(k.value, 1), np.uint8)
+        uid = np.zeros(max(m.value, 1), np.uint32)
+        rest = np.zeros((max(m.value, 1), 2), np.float32)
+        self.ctx.call("gpe_get_bodies", rows.ctypes.data_as(C.POINTER(L.GpeBody)),
+                      broken.ctypes.data_as(C.POINTER(C.c_uint8)), k.value, C.byref(k),
+                      uid.ctypes.data_as(C.POINTER(C.c_uint32)), rest.ctypes.data_as(C.POINTER(C.c_float)), m.value,
+                      C.byref(m))
+        return rows[:k.value], broken[:k.value].astype(bool), uid[:m.value], rest[:m.value]
+
+    def clear_bodies(self):
+        """gpe_set_bodies with k = 0."""
+        self.ctx.call("gpe_set_bodies", None, 0, None, None, 0)
+
+    def apply_bodies(self):
+        """gpe_apply_bodies: one pass now (the hook of a host that steps module by module).  Does not synchronise."""
+        self.ctx.call("gpe_apply_bodies")
+
+    def body_poses(self):
+        """gpe_get_body_poses -> f32[k, 4]: (cx, cy, cos, sin) of every body as of the last pass, NaNs while a body is
+        inert or broken and before the first pass.  Blocks like a download."""
+        k = C.c_uint64()
+        self.ctx.call("gpe_get_body_poses", None, 0, C.byref(k))
+        out = np.zeros((max(k.value, 1), 4), np.float32)
+        self.ctx.call("gpe_get_body_poses", out.ctypes.data_as(C.POINTER(C.c_float)), k.value, C.byref(k))
+        return out[:k.value]
+
+    def bodies_info(self):
+        """gpe_get_bodies_info -> dict(k, members, passes, live, broken, resolves).  Blocks like a download."""
+        info = L.GpeBodiesInfo(struct_size=C.sizeof(L.GpeBodiesInfo))
+        self.ctx.call("gpe_get_bodies_info", C.byref(info))
+        return {name: getattr(info, name) for name, _ in L.GpeBodiesInfo._fields_ if name not in ("struct_size", "reserved")}
 
     # Region queries and picking (not in the reference; include/gpe.h): which particles lie in a circle or a box, or
     # under a point, counted and gathered on the device.  The context is left exactly as it was.
@@ -1185,6 +1266,35 @@ class State:
         """ParticleSystem.bonds_info -> dict(iterations, k, nodes, passes, live, broken, resolves)."""
         return self.particles.bonds_info()
 
+    def set_bodies(self, bodies, member_uid, member_rest):
+        """ParticleSystem.set_bodies: groups of particles (rows of BODY_DTYPE) matched to their rest shape after every
+        step, behind the bonds and before the colliders."""
+        self.particles.set_bodies(bodies, member_uid, member_rest)
+
+    def bodies_from_groups(self, uid_groups, stiffness=1.0, break_distance=0.0):
+        """ParticleSystem.bodies_from_groups -> (rows, member_uid, member_rest): the current positions as the rest shape."""
+        return self.particles.bodies_from_groups(uid_groups, stiffness, break_distance)
+
+    def bodies(self):
+        """ParticleSystem.bodies -> (records BODY_DTYPE[k], broken bool[k], member_uid u32[m], member_rest f32[m, 2])."""
+        return self.particles.bodies()
+
+    def clear_bodies(self):
+        """ParticleSystem.clear_bodies."""
+        self.particles.clear_bodies()
+
+    def apply_bodies(self):
+        """ParticleSystem.apply_bodies: one pass now."""
+        self.particles.apply_bodies()
+
+    def body_poses(self):
+        """ParticleSystem.body_poses -> f32[k, 4]: (cx, cy, cos, sin) as of the last pass."""
+        return self.particles.body_poses()
+
+    def bodies_info(self):
+        """ParticleSystem.bodies_info -> dict(k, members, passes, live, broken, resolves)."""
+        return self.particles.bodies_info()
+
     def query_circle(self, center, radius):
         """ParticleSystem.query_circle -> QueryResult(index, uid, pos, prev, radius)."""
         return self.particles.query_circle(center, radius)
@@ -1283,8 +1393,13 @@ class State:
         A tracer recorder (tracers_begin) is not stored: it is observation state, not step state -- a loaded State steps
         the same bits without it and is armed again by its host.  The run monitor (monitor_begin) is not stored either,
         for the same reason.  Static colliders are step state: a set that is present is written (`colliders`), and so
-        are distance bonds with their relaxation count and broken flags (`bonds`, `bond_iterations`, `bonds_broken`)."""
+        are distance bonds with their relaxation count and broken flags (`bonds`, `bond_iterations`, `bonds_broken`) and
+        bodies with their members and broken flags (`bodies`, `bodies_broken`, `body_member_uid`, `body_member_rest`)."""
         extra = {}
+        bodies, bodies_broken, member_uid, member_rest = self.bodies()
+        if len(bodies):
+            extra.update(bodies=bodies, bodies_broken=bodies_broken, body_member_uid=member_uid,
+                         body_member_rest=member_rest)
         bonds, broken = self.bonds()
         if len(bonds):
             extra.update(bonds=bonds, bond_iterations=np.array([self.bonds_info()["iterations"]], np.uint32),
@@ -1331,6 +1446,10 @@ class State:
                 rows = d["bonds"].astype(BOND_DTYPE)
                 rows["flags"] |= np.where(d["bonds_broken"], L.BOND_BROKEN, 0).astype(np.uint32)
                 st.set_bonds(rows, int(d["bond_iterations"][0]))
+            if "bodies" in d.files:                                # (after the uids and the bonds; a broken body starts broken)
+                rows = d["bodies"].astype(BODY_DTYPE)
+                rows["flags"] |= np.where(d["bodies_broken"], L.BODY_BROKEN, 0).astype(np.uint32)
+                st.set_bodies(rows, d["body_member_uid"], d["body_member_rest"])
             return st
 
     def close(self):

@@ -385,6 +385,79 @@ class ParticleSystem {
         ctx_->call(gpe_get_bonds_info(ctx_->raw(), &info));
         return info;
     }
+    // not in the reference: rigid and soft bodies (include/gpe.h): groups of particles named by uid that keep their rest
+    // shape, matched on the device after every step of gpe_step / gpe_run, behind the bonds and before the static
+    // colliders.  Step state: a snapshot keeps the set, its members and the broken flags (a broken body is given back
+    // with GPE_BODY_BROKEN).
+    void set_bodies(const std::vector<gpe_body> &bodies, const std::vector<uint32_t> &member_uid,
+                    const std::vector<float> &member_rest_xy)
+    {
+        if (member_rest_xy.size() != 2 * member_uid.size())
+            throw std::invalid_argument("set_bodies: member_rest_xy must hold two coordinates per member uid");
+        ctx_->call(gpe_set_bodies(ctx_->raw(), bodies.empty() ? nullptr : bodies.data(), bodies.size(),
+                                  member_uid.empty() ? nullptr : member_uid.data(),
+                                  member_rest_xy.empty() ? nullptr : member_rest_xy.data(), member_uid.size()));
+    }
+    struct Bodies {
+        std::vector<gpe_body> records;
+        std::vector<uint8_t> broken;
+        std::vector<uint32_t> member_uid;
+        std::vector<float> member_rest_xy;
+    };
+    Bodies bodies() const
+    {
+        uint64_t k = 0, m = 0;
+        ctx_->call(gpe_get_bodies(ctx_->raw(), nullptr, nullptr, 0, &k, nullptr, nullptr, 0, &m));
+        Bodies out;
+        out.records.resize(k);
+        out.broken.resize(k);
+        out.member_uid.resize(m);
+        out.member_rest_xy.resize(2 * m);
+        ctx_->call(gpe_get_bodies(ctx_->raw(), k ? out.records.data() : nullptr, k ? out.broken.data() : nullptr, k, &k,
+                                  m ? out.member_uid.data() : nullptr, m ? out.member_rest_xy.data() : nullptr, m, &m));
+        return out;
+    }
+    // one body per group of uids, the particles' current positions captured as the rest shape
+    Bodies bodies_from_groups(const std::vector<std::vector<uint32_t>> &uid_groups, float stiffness = 1.0f,
+                              float break_distance = 0.0f)
+    {
+        Bodies out;
+        for (const std::vector<uint32_t> &g : uid_groups) {
+            gpe_body b{};
+            b.first = (uint32_t)out.member_uid.size();
+            b.count = (uint32_t)g.size();
+            b.stiffness = stiffness;
+            b.break_distance = break_distance;
+            out.records.push_back(b);
+            out.member_uid.insert(out.member_uid.end(), g.begin(), g.end());
+        }
+        out.broken.assign(out.records.size(), 0);
+        out.member_rest_xy.resize(2 * out.member_uid.size());
+        std::vector<uint32_t> index(out.member_uid.size());
+        if (!out.member_uid.empty())
+            ctx_->call(gpe_find_uids(ctx_->raw(), out.member_uid.data(), out.member_uid.size(), index.data(),
+                                     out.member_rest_xy.data(), nullptr, nullptr));
+        for (uint32_t i : index)
+            if (i == GPE_UID_ABSENT) throw std::invalid_argument("bodies_from_groups: a uid names no live particle");
+        return out;
+    }
+    void clear_bodies() { ctx_->call(gpe_set_bodies(ctx_->raw(), nullptr, 0, nullptr, nullptr, 0)); }
+    void apply_bodies() { ctx_->call(gpe_apply_bodies(ctx_->raw())); }   // one pass now: the hook of the per-module calls
+    std::vector<float> body_poses() const                                 // (cx, cy, cos, sin) per body, as of the last pass
+    {
+        uint64_t k = 0;
+        ctx_->call(gpe_get_body_poses(ctx_->raw(), nullptr, 0, &k));
+        std::vector<float> out(4 * k);
+        if (k) ctx_->call(gpe_get_body_poses(ctx_->raw(), out.data(), k, &k));
+        return out;
+    }
+    gpe_bodies_info bodies_info() const
+    {
+        gpe_bodies_info info{};
+        info.struct_size = sizeof(info);
+        ctx_->call(gpe_get_bodies_info(ctx_->raw(), &info));
+        return info;
+    }
     // not in the reference: every particle in a circle / box, or the one under a point (include/gpe.h), ascending
     // storage index; uid stays empty while uids are off.  pick() returns no rows when no disc contains the point.
     struct QueryResult {

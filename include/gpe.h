@@ -463,6 +463,82 @@ gpe_status gpe_get_bonds(gpe_ctx *ctx, gpe_bond *out, uint8_t *broken_out, uint6
 gpe_status gpe_apply_bonds(gpe_ctx *ctx);                          /* one pass now, stream-ordered, no sync */
 gpe_status gpe_get_bonds_info(gpe_ctx *ctx, gpe_bonds_info *info); /* synchronises (reads the device counter) */
 
+/* ---- rigid and soft bodies (not in the reference) ------------------------------------------------------------------
+ * Groups of particles that keep their shape: a box, a wheel, a brick, a jelly blob.  A body is `count` members (2 ..
+ * GPE_BODY_MAX_MEMBERS), each a particle named by uid (gpe_enable_uids must be on) with a rest position (rx, ry) in any
+ * frame (only the offsets matter), a stiffness in [0, 1] and a break_distance >= 0 (0: never breaks).  A uid appears
+ * at most once in the whole set.  While a context holds a set, gpe_step and every iteration of gpe_run run one shape
+ * matching pass (Mueller et al. 2005) after the step, behind the distance bonds and BEFORE the static colliders, on
+ * the device (csrc/k_bodies.hip): step -> bonds -> bodies -> colliders -> tracers / monitor.  A bond can hang a body
+ * from an anchor; walls keep the last word.  The per-module calls run no pass: gpe_apply_bodies is their hook.  A
+ * context without bodies launches and allocates exactly what it does without this section.
+ *  - The pass (csrc/k_body.h is the one definition), IEEE binary32, one rounding per operation, left to right, no
+ *    FMA, `/` and sqrtf correctly rounded.  A member whose uid names no live particle is absent in this pass; L is the
+ *    number of live members; a body with L < 2 is inert in this pass (not broken).
+ *    S(v), the canonical sum over the body's members, depends on count alone: G = the smallest power of two >= count,
+ *    at most 64; partial[l] = +0.0f; lane l adds v_l, v_(l+G), v_(l+2G), ... in that order (an absent member adds
+ *    +0.0f); then for off = G/2 .. 1: partial[l] = partial[l] + partial[l + off] for l < off; S = partial[0].
+ *      fL = (float)L;  rbar = (S(rx)/fL, S(ry)/fL);  c = (S(px)/fL, S(py)/fL)
+ *      per live member: q = r - rbar;  d = p - c;  a = qx*dx + qy*dy;  b = qx*dy - qy*dx
+ *      A = S(a);  B = S(b);  h = sqrtf(A*A + B*B);  inert unless h > 0 and h < +inf   (NaN, overflow, coincident
+ *      members, underflow);  co = A/h;  si = B/h
+ *      per live member: gx = cx + (co*qx - si*qy);  gy = cy + (si*qx + co*qy);  e = g - p;  e2 = ex*ex + ey*ey
+ *      with break_distance > 0: any live member with e2 > bd2 (bd2 = break_distance*break_distance, rounded once on
+ *      the host; strict) breaks the body: sticky, it never acts again, nothing moves in the pass in which it breaks
+ *      otherwise every live member moves to (px + stiffness*ex, py + stiffness*ey), then K12's clamp with its stored
+ *      radius: clamp(x, r, W - r), clamp(y, r, H - r).  Only pos is written: prev and radius never, so the velocity
+ *      change is the one Verlet implies.
+ *    The body's pose (cx, cy, co, si) is kept per body: four NaNs while the body is inert or broken, and before the
+ *    first pass.  The result depends on the set and the particles alone, never on storage order or mode.
+ *  - What a body is not: a collider or a collision deforms a body until the next pass; bodies whose members overlap at
+ *    rest fight the collision solver; a break_distance below one step's collision push breaks at the first touch;
+ *    there is no per-member mass (every member weighs the same, as in the collision response), no joint between
+ *    bodies and no swept test.
+ *  - The set and its broken flags are step state: they survive adds, removals, edits, kicks, re-sorts, growth,
+ *    gpe_set_mode and gpe_set_particles (which renumbers the uids from 0: the bodies then name the new particles).
+ *    After a call that moves, adds or removes particles the next pass looks its uids up again (that synchronises
+ *    once); every other pass only enqueues.
+ *  - gpe_set_bodies replaces the set (k == 0 clears it and frees its buffers), clears the broken flags and zeroes the
+ *    counters; it synchronises.  Body j owns members [first, first + count) of member_uid and member_rest_xy (x, y
+ *    interleaved).  A body given with GPE_BODY_BROKEN starts broken: that is how a snapshot restores one; the bit is
+ *    not kept in the record.  -0.0 in break_distance is stored as +0.  gpe_get_bodies delivers the first min(k,
+ *    capacity) records and their broken flags (1 / 0), the first min(members, member_capacity) member uids and rest
+ *    positions (each output may be NULL) and the numbers set into *k and *members; it synchronises.
+ *    gpe_get_body_poses delivers the first min(k, capacity) poses as of the last pass, 4 floats each; it synchronises.
+ *    gpe_apply_bodies with no bodies or no particles: GPE_OK, nothing done.
+ *  - Errors (the previous set stays untouched): a NULL ctx, NULL arrays with k > 0, k > GPE_BODIES_MAX, members >
+ *    GPE_BODY_MEMBERS_MAX, a count outside 2 .. GPE_BODY_MAX_MEMBERS, member ranges that overlap, run past `members` or
+ *    leave members unused, a uid equal to GPE_UID_ABSENT or named twice, a non-finite rest coordinate, a stiffness that
+ *    is NaN or outside [0, 1], a break_distance that is NaN, infinite or negative, unknown flag bits, a non-zero
+ *    reserved, a struct_size below the struct's: GPE_ERR_INVALID_ARG.  Uids off: GPE_ERR_STATE.  gpe_set_bodies on a
+ *    sharded context, and gpe_enable_uids(ctx, 0), gpe_shard_set_particles, gpe_use_order_keys(ctx, 1) and
+ *    gpe_set_counts on a context that holds bodies: GPE_ERR_UNSUPPORTED. */
+#define GPE_BODIES_MAX        1048576u
+#define GPE_BODY_MAX_MEMBERS  4096u
+#define GPE_BODY_MEMBERS_MAX  16777216u   /* members of the whole set */
+#define GPE_BODY_BROKEN       1u          /* flags, gpe_set_bodies only: the body starts broken */
+typedef struct gpe_body {                 /* 24 bytes */
+    uint32_t first, count;                /* members [first, first + count) */
+    float stiffness;                      /* in [0, 1]: the share of the way to the matched pose per pass */
+    float break_distance;                 /* finite, >= 0; 0: never breaks */
+    uint32_t flags, reserved;
+} gpe_body;
+typedef struct gpe_bodies_info {
+    uint32_t struct_size, reserved;    /* in / 0                                                             */
+    uint64_t k, members;               /* bodies set / members of the whole set                              */
+    uint64_t passes;                   /* passes enqueued since the last gpe_set_bodies                      */
+    uint64_t live, broken;             /* bodies not broken / broken (an integer counter); live + broken = k */
+    uint64_t resolves;                 /* times the uids were looked up again since the last gpe_set_bodies  */
+} gpe_bodies_info;                     /* 56 bytes */
+gpe_status gpe_set_bodies(gpe_ctx *ctx, const gpe_body *bodies, uint64_t k, const uint32_t *member_uid,
+                          const float *member_rest_xy, uint64_t members);
+gpe_status gpe_get_bodies(gpe_ctx *ctx, gpe_body *out, uint8_t *broken_out, uint64_t capacity, uint64_t *k,
+                          uint32_t *member_uid_out, float *member_rest_xy_out, uint64_t member_capacity,
+                          uint64_t *members);
+gpe_status gpe_apply_bodies(gpe_ctx *ctx);                            /* one pass now, stream-ordered, no sync */
+gpe_status gpe_get_body_poses(gpe_ctx *ctx, float *pose_xycs, uint64_t capacity, uint64_t *k);   /* synchronises */
+gpe_status gpe_get_bodies_info(gpe_ctx *ctx, gpe_bodies_info *info);  /* synchronises (reads the device counter) */
+
 /* ---- region queries and picking (not in the reference) ------------------------------------------------------
  * Which particles lie in a region, or under a point, without downloading every position: full passes over the
  * particles on the device (csrc/k_query.hip) that change nothing on the context.  Positions, prev, radii, uids, the
