@@ -53,6 +53,10 @@ BONDS_MAX, BOND_MAX_DEGREE, BOND_ITER_MAX = 4194304, 1024, 32
 BOND_ANCHOR, BOND_BROKEN = 1, 2
 BODIES_MAX, BODY_MAX_MEMBERS, BODY_MEMBERS_MAX = 1048576, 4096, 16777216
 BODY_BROKEN = 1
+FIELDS_MAX = 4096
+FIELD_EVERYWHERE, FIELD_CIRCLE, FIELD_BOX = 0, 1, 2
+FIELD_UNIFORM, FIELD_RADIAL, FIELD_VORTEX, FIELD_DRAG = 0, 1, 2, 3
+FALLOFF_NONE, FALLOFF_LINEAR = 0, 1
 EDIT_BY_INDEX, EDIT_BY_UID = 0, 1
 CLUSTER_BY_INDEX, CLUSTER_BY_UID = 0, 1
 VEL_ADD, VEL_SET, VEL_SCALE = 0, 1, 2
@@ -252,6 +256,22 @@ class GpeBodiesInfo(C.Structure):
                 ("passes", C.c_uint64), ("live", C.c_uint64), ("broken", C.c_uint64), ("resolves", C.c_uint64)]
 
 
+class GpeField(C.Structure):
+    """gpe_field: a region (shape; x0, y0, x1, y1) and what it does to the particles whose centre lies in it (kind,
+    falloff; the pole px, py; the acceleration fx, fy; strength; reach); flags 0.  56 bytes."""
+    _fields_ = [("shape", C.c_uint32), ("kind", C.c_uint32), ("falloff", C.c_uint32), ("flags", C.c_uint32),
+                ("x0", C.c_float), ("y0", C.c_float), ("x1", C.c_float), ("y1", C.c_float),
+                ("px", C.c_float), ("py", C.c_float), ("fx", C.c_float), ("fy", C.c_float),
+                ("strength", C.c_float), ("reach", C.c_float)]
+
+
+class GpeFieldsInfo(C.Structure):
+    """gpe_fields_info: in struct_size; out the fields set, the passes run and the particles whose prev they wrote since
+    the last gpe_set_fields, the lookup grid in use and its (cell, field) entries."""
+    _fields_ = [("struct_size", C.c_uint32), ("k", C.c_uint32), ("passes", C.c_uint64), ("touched", C.c_uint64),
+                ("grid_x", C.c_uint32), ("grid_y", C.c_uint32), ("list_entries", C.c_uint64)]
+
+
 class GpeParticleEdit(C.Structure):
     """gpe_particle_edit: in struct_size / key_kind / k / keys and the field arrays (each may be NULL), out edited."""
     _fields_ = [("struct_size", C.c_uint32), ("key_kind", C.c_uint32), ("k", C.c_uint64),
@@ -328,6 +348,10 @@ SYMBOLS = [
     ("gpe_apply_bodies", _I32, [_VP]),
     ("gpe_get_body_poses", _I32, [_VP, C.POINTER(C.c_float), _U64, C.POINTER(_U64)]),
     ("gpe_get_bodies_info", _I32, [_VP, C.POINTER(GpeBodiesInfo)]),
+    ("gpe_set_fields", _I32, [_VP, C.POINTER(GpeField), _U64]),
+    ("gpe_get_fields", _I32, [_VP, C.POINTER(GpeField), _U64, C.POINTER(_U64)]),
+    ("gpe_apply_fields", _I32, [_VP, _F]),
+    ("gpe_get_fields_info", _I32, [_VP, C.POINTER(GpeFieldsInfo)]),
     ("gpe_query_circle", _I32, [_VP, _F, _F, _F, C.POINTER(GpeQueryResult)]),
     ("gpe_query_box", _I32, [_VP, _F, _F, _F, _F, C.POINTER(GpeQueryResult)]),
     ("gpe_pick", _I32, [_VP, _F, _F, C.POINTER(GpeQueryResult)]),

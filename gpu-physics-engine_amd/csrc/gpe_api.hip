@@ -1,6 +1,6 @@
 // gpe_api.hip -- the extern "C" boundary of include/gpe.h: context, device memory, particle buffers, set / add / remove,
 // uids, step ordering, downloads, profiling.  The queries are in gpe_queries.hip, the checked add, edits and kicks in
-// gpe_edits.hip, the tracers and the monitor in gpe_observe.hip, the static colliders in gpe_colliders.hip, the distance bonds in gpe_bonds.hip, the rigid and soft bodies in gpe_bodies.hip.  All device work goes to one in-order hipStream per context.
+// gpe_edits.hip, the tracers and the monitor in gpe_observe.hip, the static colliders in gpe_colliders.hip, the distance bonds in gpe_bonds.hip, the rigid and soft bodies in gpe_bodies.hip, the force fields in gpe_fields.hip.  All device work goes to one in-order hipStream per context.
 #include <math.h>
 #include <stddef.h>
 #include <stdlib.h>
@@ -1001,6 +1001,7 @@ gpe_status gpe_destroy(gpe_ctx *c)
     colliders_release(c);
     bonds_release(c);
     bodies_release(c);
+    fields_release(c);
     sort_release(c);
     scan_release(c);
     onesweep_release(c);
@@ -1352,6 +1353,7 @@ gpe_status gpe_set_world(gpe_ctx *c, float w, float h)
     if (!c) return GPE_ERR_INVALID_ARG;
     c->cfg.world_width = w;
     c->cfg.world_height = h;
+    fields_world_changed(c);
     return reconfigure(c);
 }
 
@@ -1471,6 +1473,7 @@ gpe_status gpe_step(gpe_ctx *c, float dt, uint32_t flags)
     GPE_TRY(bonds_after_step(c));
     GPE_TRY(bodies_after_step(c));
     GPE_TRY(colliders_after_step(c));
+    GPE_TRY(fields_after_step(c, dt));
     return observers_after_step(c);
 }
 
@@ -1496,6 +1499,7 @@ gpe_status gpe_run(gpe_ctx *c, float dt, uint64_t steps, uint64_t resort_every, 
         if (rc == GPE_OK) rc = bonds_after_step(c);
         if (rc == GPE_OK) rc = bodies_after_step(c);
         if (rc == GPE_OK) rc = colliders_after_step(c);
+        if (rc == GPE_OK) rc = fields_after_step(c, dt);
         if (rc == GPE_OK) rc = observers_after_step(c);
     }
     for (hipEvent_t e : fence) if (e) (void)hipEventDestroy(e);
@@ -1722,6 +1726,7 @@ gpe_status gpe_set_counts(gpe_ctx *c, uint64_t n_total, uint64_t n_owned)
     if (has_bodies(c)) return refuse_bodies(c, "gpe_set_counts");
     if (c->uid.on) return fail(c, GPE_ERR_UNSUPPORTED, "gpe_set_counts: not supported while uids are on");
     if (has_colliders(c)) return refuse_colliders(c, "gpe_set_counts");
+    if (has_fields(c)) return refuse_fields(c, "gpe_set_counts");
     c->n = n_total;
     c->n_owned = n_owned;
     return GPE_OK;
@@ -1735,6 +1740,7 @@ gpe_status gpe_use_order_keys(gpe_ctx *c, int32_t enable)
     if (enable && c->uid.on)
         return fail(c, GPE_ERR_UNSUPPORTED, "gpe_use_order_keys: sharded runs carry order keys, not uids (uids are on)");
     if (enable && has_colliders(c)) return refuse_colliders(c, "gpe_use_order_keys");
+    if (enable && has_fields(c)) return refuse_fields(c, "gpe_use_order_keys");
     c->use_order_keys = enable != 0;
     return GPE_OK;
 }

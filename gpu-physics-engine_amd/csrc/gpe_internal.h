@@ -471,6 +471,20 @@ struct BodyState {
     unsigned long long *broken = nullptr;        // one word: bodies broken
 };
 
+// the force fields (gpe_set_fields; gpe_fields.hip, k_fields.hip, field_grid.h).  Step state: gpe_step / gpe_run apply them
+struct FieldState {
+    std::vector<gpe_field> set;                  // the fields as the host gave them (empty: none, nothing is launched)
+    float4 *rec = nullptr;                       // 3 per field: k_field.h FieldRecord
+    unsigned long long *touched = nullptr;       // one word: particles whose prev was written since the last gpe_set_fields
+    uint64_t passes = 0;                         // passes enqueued since then
+    // the lookup grid (field_grid.h), rebuilt before the next pass when the world it was built for has changed
+    bool grid_valid = false;
+    float grid_w = 0.f, grid_h = 0.f;            // the world at the build (compared by bits)
+    ColliderGridView view;
+    uint32_t *cell_start = nullptr, *items = nullptr;
+    uint64_t entries = 0;
+};
+
 struct SortWorkspace {
     uint32_t *keys_b = nullptr, *vals_b = nullptr;   // ping-pong partners, cap entries each
     uint64_t cap = 0;
@@ -814,6 +828,7 @@ struct gpe_ctx {
     gpe::ColliderState colliders;
     gpe::BondState bonds;
     gpe::BodyState bodies;
+    gpe::FieldState fields;
     gpe::QueryWorkspace query_ws;
     gpe::ContactsWorkspace contacts_ws;
     gpe::ClustersWorkspace clusters_ws;
@@ -975,6 +990,12 @@ inline bool has_bodies(const gpe_ctx *c) { return !c->bodies.set.empty(); }
 gpe_status refuse_bodies(gpe_ctx *c, const char *who);      // GPE_ERR_UNSUPPORTED: taking the uids from a context that holds bodies
 gpe_status bodies_after_step(gpe_ctx *c);          // after every step of gpe_step / gpe_run, behind the bonds, before the colliders
 void bodies_release(gpe_ctx *c);
+// gpe_fields.hip: the force fields of a context that holds some
+inline bool has_fields(const gpe_ctx *c) { return !c->fields.set.empty(); }
+gpe_status refuse_fields(gpe_ctx *c, const char *who);      // GPE_ERR_UNSUPPORTED: sharding a context that holds fields
+gpe_status fields_after_step(gpe_ctx *c, float dt);         // after every step of gpe_step / gpe_run, behind the colliders, before the observers
+void fields_world_changed(gpe_ctx *c);                      // gpe_set_world: the lookup grid follows before the next pass
+void fields_release(gpe_ctx *c);
 
 // profiling scope: a pair of timestamps on ctx->stream when ctx->profiling, else nothing -- slots of the stamp buffer
 // (scope_stamps.h), or hipEvents where scope_uses_stamps() says no.  kSharedBoundaries: inside a ScopeRegion the scope
@@ -1205,6 +1226,11 @@ gpe_status launch_bonds_pass(gpe_ctx *c, float2 *pos, const float *radius, uint6
 // rigid and soft bodies (k_bodies.hip): one shape matching pass of the k bodies of B over pos[0, n) in place, one launch
 // per non-empty width class
 gpe_status launch_bodies_pass(gpe_ctx *c, float2 *pos, const float *radius, uint64_t n, const BodyState &B, uint32_t k);
+// force fields (k_fields.hip): one pass over prev[0, n) in place, pos read only.  cell_start / items: the lookup grid
+// `view`, rec: 3 float4 per field.  *touched += the particles whose prev was written
+gpe_status launch_fields_pass(gpe_ctx *c, const float2 *pos, float2 *prev, uint64_t n, const uint32_t *cell_start,
+                              const uint32_t *items, const float4 *rec, uint32_t k, const ColliderGridView &view, float dt2,
+                              unsigned long long *touched);
 // native pipeline: its host side (gpe_native.hip; the kernels and their launchers: k_native.hip, native_launch.h)
 gpe_status native_configure(gpe_ctx *c);
 bool native_should_run(gpe_ctx *c);

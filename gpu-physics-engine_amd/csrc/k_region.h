@@ -6,6 +6,7 @@
 
 #include "gpe_internal.h"
 #include "k_ray.h"
+#include "k_region_pred.h"
 
 namespace gpe {
 
@@ -23,24 +24,20 @@ struct QueryRegion {
 };
 
 // The disc test of k_remove.hip (in_disc), restated: IEEE binary32, one rounding per operation, left to right, no FMA
-// (the build also compiles with -ffp-contract=off).  The circle query returns what the eraser removes.
+// (the build also compiles with -ffp-contract=off).  The circle query returns what the eraser removes.  The arithmetic
+// itself is k_region_pred.h's, which the force fields share.
 __device__ __forceinline__ float dist2(const float2 p, float x, float y)
 {
-#pragma clang fp contract(off)
-    const float dx = p.x - x;
-    const float dy = p.y - y;
-    const float dxx = dx * dx;
-    const float dyy = dy * dy;
-    return dxx + dyy;
+    return region_dist2(p.x, p.y, x, y);
 }
 
 template <int KIND>
 __device__ __forceinline__ bool in_region(const float2 p, const QueryRegion &Q)
 {
     if constexpr (KIND == kQueryCircle)
-        return dist2(p, Q.x0, Q.y0) <= Q.rr;
+        return region_in_disc(p.x, p.y, Q.x0, Q.y0, Q.rr);
     else
-        return Q.x0 <= p.x && p.x <= Q.x1 && Q.y0 <= p.y && p.y <= Q.y1;
+        return region_in_box(p.x, p.y, Q.x0, Q.y0, Q.x1, Q.y1);
 }
 
 // hit[r] for the rounds of this thread's tile (false past n); the positions of all rounds are loaded first, so that

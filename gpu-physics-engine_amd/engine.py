@@ -81,6 +81,9 @@ def anchor_bonds(uids, points, rest_length=0.0, stiffness=1.0, max_length=0.0):
 
 
 # set_bodies / bodies: the rows of gpe_body (24 bytes each, the struct's layout)
+# set_fields / fields: the rows of gpe_field (56 bytes each, the struct's layout)
+FIELD_DTYPE = np.dtype([(name, np.uint32 if ctype is C.c_uint32 else np.float32) for name, ctype in L.GpeField._fields_])
+assert FIELD_DTYPE.itemsize == C.sizeof(L.GpeField) == 56
 BODY_DTYPE = np.dtype([(name, np.uint32 if ctype is C.c_uint32 else np.float32) for name, ctype in L.GpeBody._fields_])
 assert BODY_DTYPE.itemsize == C.sizeof(L.GpeBody)
 
@@ -696,6 +699,38 @@ class ParticleSystem:
         self.ctx.call("gpe_get_body_poses", out.ctypes.data_as(C.POINTER(C.c_float)), k.value, C.byref(k))
         return out[:k.value]
 
+    # Force fields (not in the reference; include/gpe.h): regions that push the particles whose centre lies in them -- a
+    # uniform acceleration, a pull toward a pole, a swirl around one, a drag -- applied to prev on the device after every
+    # update() / step of run(), behind the colliders and before the tracers and the monitor.  Step state: save() keeps them.
+    def set_fields(self, fields):
+        """gpe_set_fields: replace the set by the rows of a FIELD_DTYPE array; no rows clear it.  The counters start
+        anew."""
+        rows = np.ascontiguousarray(fields, FIELD_DTYPE).reshape(-1)
+        k = len(rows)
+        self.ctx.call("gpe_set_fields", rows.ctypes.data_as(C.POINTER(L.GpeField)) if k else None, k)
+
+    def fields(self):
+        """gpe_get_fields -> FIELD_DTYPE[k]: the set."""
+        k = C.c_uint64()
+        self.ctx.call("gpe_get_fields", None, 0, C.byref(k))
+        rows = np.zeros(max(k.value, 1), FIELD_DTYPE)
+        self.ctx.call("gpe_get_fields", rows.ctypes.data_as(C.POINTER(L.GpeField)), k.value, C.byref(k))
+        return rows[:k.value]
+
+    def clear_fields(self):
+        """gpe_set_fields with k = 0."""
+        self.ctx.call("gpe_set_fields", None, 0)
+
+    def apply_fields(self, dt):
+        """gpe_apply_fields: one pass now (the hook of a host that steps module by module).  Does not synchronise."""
+        self.ctx.call("gpe_apply_fields", float(dt))
+
+    def fields_info(self):
+        """gpe_get_fields_info -> dict(k, passes, touched, grid_x, grid_y, list_entries).  Blocks like a download."""
+        info = L.GpeFieldsInfo(struct_size=C.sizeof(L.GpeFieldsInfo))
+        self.ctx.call("gpe_get_fields_info", C.byref(info))
+        return {name: getattr(info, name) for name, _ in L.GpeFieldsInfo._fields_ if name != "struct_size"}
+
     def bodies_info(self):
         """gpe_get_bodies_info -> dict(k, members, passes, live, broken, resolves).  Blocks like a download."""
         info = L.GpeBodiesInfo(struct_size=C.sizeof(L.GpeBodiesInfo))
@@ -1295,6 +1330,27 @@ class State:
         """ParticleSystem.bodies_info -> dict(k, members, passes, live, broken, resolves)."""
         return self.particles.bodies_info()
 
+    def set_fields(self, fields):
+        """ParticleSystem.set_fields: force fields (rows of FIELD_DTYPE) applied to prev after every step, behind the
+        colliders."""
+        self.particles.set_fields(fields)
+
+    def fields(self):
+        """ParticleSystem.fields -> FIELD_DTYPE[k]."""
+        return self.particles.fields()
+
+    def clear_fields(self):
+        """ParticleSystem.clear_fields."""
+        self.particles.clear_fields()
+
+    def apply_fields(self, dt):
+        """ParticleSystem.apply_fields: one pass now."""
+        self.particles.apply_fields(dt)
+
+    def fields_info(self):
+        """ParticleSystem.fields_info -> dict(k, passes, touched, grid_x, grid_y, list_entries)."""
+        return self.particles.fields_info()
+
     def query_circle(self, center, radius):
         """ParticleSystem.query_circle -> QueryResult(index, uid, pos, prev, radius)."""
         return self.particles.query_circle(center, radius)
@@ -1394,8 +1450,12 @@ class State:
         the same bits without it and is armed again by its host.  The run monitor (monitor_begin) is not stored either,
         for the same reason.  Static colliders are step state: a set that is present is written (`colliders`), and so
         are distance bonds with their relaxation count and broken flags (`bonds`, `bond_iterations`, `bonds_broken`) and
-        bodies with their members and broken flags (`bodies`, `bodies_broken`, `body_member_uid`, `body_member_rest`)."""
+        bodies with their members and broken flags (`bodies`, `bodies_broken`, `body_member_uid`, `body_member_rest`) and
+        force fields (`fields`)."""
         extra = {}
+        fields = self.fields()
+        if len(fields):
+            extra.update(fields=fields)
         bodies, bodies_broken, member_uid, member_rest = self.bodies()
         if len(bodies):
             extra.update(bodies=bodies, bodies_broken=bodies_broken, body_member_uid=member_uid,
@@ -1450,6 +1510,8 @@ class State:
                 rows = d["bodies"].astype(BODY_DTYPE)
                 rows["flags"] |= np.where(d["bodies_broken"], L.BODY_BROKEN, 0).astype(np.uint32)
                 st.set_bodies(rows, d["body_member_uid"], d["body_member_rest"])
+            if "fields" in d.files:
+                st.set_fields(d["fields"].astype(FIELD_DTYPE))
             return st
 
     def close(self):

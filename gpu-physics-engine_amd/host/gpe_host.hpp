@@ -458,6 +458,31 @@ class ParticleSystem {
         ctx_->call(gpe_get_bodies_info(ctx_->raw(), &info));
         return info;
     }
+    // not in the reference: force fields (include/gpe.h) -- regions that push the particles whose centre lies in them: a
+    // uniform acceleration, a pull toward a pole, a swirl around one, a drag.  Applied to prev on the device after every
+    // step of update() / run(), behind the colliders and before the tracers and the monitor.  Step state: a snapshot
+    // keeps the set.
+    void set_fields(const std::vector<gpe_field> &fields)
+    {
+        ctx_->call(gpe_set_fields(ctx_->raw(), fields.empty() ? nullptr : fields.data(), fields.size()));
+    }
+    std::vector<gpe_field> fields() const
+    {
+        uint64_t k = 0;
+        ctx_->call(gpe_get_fields(ctx_->raw(), nullptr, 0, &k));
+        std::vector<gpe_field> out(k);
+        ctx_->call(gpe_get_fields(ctx_->raw(), out.empty() ? nullptr : out.data(), k, &k));
+        return out;
+    }
+    void clear_fields() { ctx_->call(gpe_set_fields(ctx_->raw(), nullptr, 0)); }
+    void apply_fields(float dt) { ctx_->call(gpe_apply_fields(ctx_->raw(), dt)); }   // one pass now: the hook of the per-module calls
+    gpe_fields_info fields_info() const
+    {
+        gpe_fields_info info{};
+        info.struct_size = sizeof(info);
+        ctx_->call(gpe_get_fields_info(ctx_->raw(), &info));
+        return info;
+    }
     // not in the reference: every particle in a circle / box, or the one under a point (include/gpe.h), ascending
     // storage index; uid stays empty while uids are off.  pick() returns no rows when no disc contains the point.
     struct QueryResult {

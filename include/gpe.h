@@ -539,6 +539,83 @@ gpe_status gpe_apply_bodies(gpe_ctx *ctx);                            /* one pas
 gpe_status gpe_get_body_poses(gpe_ctx *ctx, float *pose_xycs, uint64_t capacity, uint64_t *k);   /* synchronises */
 gpe_status gpe_get_bodies_info(gpe_ctx *ctx, gpe_bodies_info *info);  /* synchronises (reads the device counter) */
 
+/* ---- force fields (not in the reference) ----------------------------------------------------------------------------
+ * What pushes the particles inside a run: a fan, a gravity well, a whirlpool, a pool of mud, a conveyor belt.  A field
+ * is a region (everywhere, a closed disc, a closed box) and a kind (a uniform acceleration, a pull toward a pole, a
+ * swirl around a pole, a drag).  While a context holds a set, gpe_step and every iteration of gpe_run run one pass over
+ * the particles after the step, BEHIND the static colliders and before the tracers and the monitor, stream-ordered, on
+ * the device (csrc/k_fields.hip): step -> bonds -> bodies -> colliders -> fields -> tracers / monitor.  A field is
+ * judged at the position the step ends with; a tracer or monitor frame sees the new velocity; the velocity acts from
+ * the next step on.  The per-module calls (gpe_integrate and the rest) run no pass: gpe_apply_fields is their hook.  A
+ * context without fields launches and allocates exactly what it does without this section.
+ *  - The pass.  For a particle with c = pos and q = prev, and dt2 = dt * dt (one binary32 product, as the step forms
+ *    it), in IEEE binary32, one rounding per operation, left to right, no FMA, `/` and sqrtf correctly rounded
+ *    (csrc/k_field.h is the one definition).  Field j MATCHES by the predicates of the region queries and the kicks on
+ *    the centre c alone (csrc/k_region_pred.h): CIRCLE the closed disc (c.x-x0)*(c.x-x0) + (c.y-y0)*(c.y-y0) <= rr
+ *    with rr = x1 * x1; BOX the closed box x0 <= c.x && c.x <= x1 && y0 <= c.y && c.y <= y1; EVERYWHERE always (a NaN
+ *    coordinate included).  The particle's radius plays no part.  Start with A = (0, 0), s = 1, accel = drag = false;
+ *    over the matching fields in ASCENDING index:
+ *      UNIFORM: g = (fx, fy)
+ *      RADIAL:  dx = px - c.x; dy = py - c.y; len = sqrtf(dx*dx + dy*dy); w = strength
+ *               LINEAR falloff: t = len / reach; w1 = 1 - t; w1 = (w1 > 0) ? w1 : 0; w = strength * w1
+ *               g = ((dx / len) * w, (dy / len) * w);  if !(len > 0): g = (0, 0)
+ *               (on its pole a field contributes nothing; the reference's mouse attractor divides by its zero length
+ *               there and yields NaN)
+ *      VORTEX:  as RADIAL with g = (((-dy) / len) * w, (dx / len) * w): strength > 0 turns counter-clockwise where x
+ *               points right and y up
+ *      UNIFORM, RADIAL, VORTEX: A.x = A.x + g.x; A.y = A.y + g.y; accel = true
+ *      DRAG:    s = s * strength; drag = true
+ *    Then drags act first, accelerations second:
+ *      if drag:  v = c - q; v = v * s; q = c - v            (gpe_kick_* with GPE_VEL_SCALE)
+ *      if accel: q.x = q.x - A.x * dt2; q.y = q.y - A.y * dt2   (gpe_kick_* with GPE_VEL_ADD)
+ *    A particle no field matches keeps every bit of prev and is not stored.  The order is part of the result: the
+ *    sums are not associative.  pos, radii, uids, the kept block table, the rosters and the native step / sort counters
+ *    are never touched, exactly as after a kick.  The payload of a NaN that the arithmetic itself produces is not
+ *    specified.
+ *  - An EVERYWHERE UNIFORM field is gravity delayed by one step: the step adds gravity before it moves the particle,
+ *    a field changes the velocity the NEXT step moves it with.  It is therefore not bit-identical to gpe_set_gravity.
+ *  - Fields are step state, not observation state: the set survives gpe_set_particles, adds, removals, edits,
+ *    re-sorts, growth, gpe_set_world and uids being switched on or off; gpe_destroy frees it.
+ *  - The pass finds a particle's fields through a coarse grid over the world that depends on the set and the world
+ *    alone, rebuilt before the next pass when the world has changed (that rebuild synchronises).  No result depends on
+ *    the grid: a particle outside it or with a NaN coordinate is tested against every field.
+ *  - gpe_set_fields replaces the set (k == 0 clears it and frees its buffers) and zeroes passes and touched; it may be
+ *    called before there are particles and synchronises like gpe_add_particles.  Fields do not move or vary in time: a
+ *    host that wants that calls it once a frame.  -0.0 as a circle's radius is stored as +0.  gpe_get_fields delivers
+ *    the first min(k, capacity) fields into out (may be NULL with capacity 0) and the number set into *k.
+ *    gpe_apply_fields with no fields or no particles: GPE_OK, nothing done.
+ *  - Errors (the previous set stays untouched): a NULL ctx, NULL fields with k > 0, k > GPE_FIELDS_MAX, an unknown
+ *    shape, kind or falloff, non-zero flags, any float that is not finite, a negative circle radius (-0.0 is accepted
+ *    as 0), a falloff other than NONE on UNIFORM or DRAG, LINEAR with a reach that is not > 0, a DRAG strength outside
+ *    [0, 1], a dt that is not finite in gpe_apply_fields, a struct_size below the struct's: GPE_ERR_INVALID_ARG.  A box
+ *    with x0 > x1 or y0 > y1 is accepted and matches nothing.  gpe_set_fields on a sharded context (gpe_shard_*, order
+ *    keys or an active cell box), and gpe_shard_set_particles, gpe_use_order_keys(ctx, 1) and gpe_set_counts on a
+ *    context that holds fields: GPE_ERR_UNSUPPORTED. */
+#define GPE_FIELDS_MAX 4096u
+enum { GPE_FIELD_EVERYWHERE = 0, GPE_FIELD_CIRCLE = 1, GPE_FIELD_BOX = 2 };                      /* shape   */
+enum { GPE_FIELD_UNIFORM = 0, GPE_FIELD_RADIAL = 1, GPE_FIELD_VORTEX = 2, GPE_FIELD_DRAG = 3 };  /* kind    */
+enum { GPE_FALLOFF_NONE = 0, GPE_FALLOFF_LINEAR = 1 };                                           /* falloff */
+typedef struct gpe_field {
+    uint32_t shape, kind, falloff, flags;   /* flags = 0                                                              */
+    float x0, y0, x1, y1;   /* CIRCLE: centre (x0, y0), radius x1, y1 = 0.  BOX: [x0, x1] x [y0, y1].  EVERYWHERE: all 0 */
+    float px, py;           /* RADIAL / VORTEX: the pole                                                              */
+    float fx, fy;           /* UNIFORM: the acceleration, in gravity's units                                          */
+    float strength;         /* RADIAL: > 0 toward the pole.  VORTEX: > 0 counter-clockwise.  DRAG: the share of the
+                               velocity kept per step, in [0, 1]                                                      */
+    float reach;            /* LINEAR falloff: the distance from the pole at which the field has faded to 0           */
+} gpe_field;                /* 56 bytes */
+typedef struct gpe_fields_info {
+    uint32_t struct_size, k;          /* in / fields set                                                 */
+    uint64_t passes;                  /* passes run since the last gpe_set_fields                        */
+    uint64_t touched;                 /* particles whose prev those passes wrote, summed (integer atomics only) */
+    uint32_t grid_x, grid_y;          /* the lookup grid in use (diagnostic; no result depends on it)    */
+    uint64_t list_entries;            /* (cell, field) entries in it                                     */
+} gpe_fields_info;                    /* 40 bytes */
+gpe_status gpe_set_fields(gpe_ctx *ctx, const gpe_field *fields, uint64_t k);
+gpe_status gpe_get_fields(const gpe_ctx *ctx, gpe_field *out, uint64_t capacity, uint64_t *k);
+gpe_status gpe_apply_fields(gpe_ctx *ctx, float dt);                 /* one pass now, stream-ordered, no sync */
+gpe_status gpe_get_fields_info(gpe_ctx *ctx, gpe_fields_info *info); /* synchronises (reads the device counter) */
+
 /* ---- region queries and picking (not in the reference) ------------------------------------------------------
  * Which particles lie in a region, or under a point, without downloading every position: full passes over the
  * particles on the device (csrc/k_query.hip) that change nothing on the context.  Positions, prev, radii, uids, the
