@@ -28,6 +28,7 @@ FLAG_FUSED_HISTOGRAMS = 512
 FLAG_GUARD_ALLOCS = 1024
 FLAG_HASH_INDEX64 = 2048
 FLAG_EVENT_SCOPES = 4096
+FLAG_GENERAL_RADII = 8192
 PIPELINE_COMPAT, PIPELINE_NATIVE = 0, 1
 (REASON_NONE, REASON_MODE_COMPAT, REASON_NO_PARTICLES, REASON_OUT_OF_BOX, REASON_GRID_TOO_WIDE,
  REASON_TABLE_TOO_LARGE, REASON_DENSE_WINDOWS) = range(7)
@@ -82,6 +83,12 @@ class GpePipelineInfo(C.Structure):
                 ("native_sorts", C.c_uint64), ("window_max", C.c_uint32), ("roster_stamp", C.c_uint32),
                 ("overflow_tiles", C.c_uint32), ("overflow_subtiles", C.c_uint32), ("overflow_spills", C.c_uint32),
                 ("arena_slots", C.c_uint32)]
+
+
+class GpePipelineInfoUniform(C.Structure):
+    """gpe_pipeline_info as it stands; GpePipelineInfo is the shorter layout up to arena_slots, which the library still
+    serves by its struct_size."""
+    _fields_ = GpePipelineInfo._fields_ + [("uniform_radius", C.c_uint32)]
 
 
 class GpeTiming(C.Structure):
@@ -388,7 +395,7 @@ SYMBOLS = [
     ("gpe_run", _I32, [_VP, _F, _U64, _U64, _I32]),
     ("gpe_sync", _I32, [_VP]),
     ("gpe_set_mode", _I32, [_VP, _U32]),
-    ("gpe_get_pipeline_info", _I32, [_VP, C.POINTER(GpePipelineInfo)]),
+    ("gpe_get_pipeline_info", _I32, [_VP, _VP]),                 # (either layout of gpe_pipeline_info)
     ("gpe_download", _I32, [_VP, C.c_int, _VP, _U64]),
     ("gpe_array_bytes", _I32, [_VP, C.c_int, C.POINTER(_U64)]),
     ("gpe_device_ptr", _I32, [_VP, C.c_int, C.POINTER(_VP), C.POINTER(_U64)]),

@@ -1045,6 +1045,7 @@ gpe_status gpe_get_pipeline_info(gpe_ctx *c, gpe_pipeline_info *info)
         out.arena_slots = s.arena; out.overflow_tiles = s.overflow;
         out.overflow_subtiles = s.sub_tiles; out.overflow_spills = s.spills;
     }
+    out.uniform_radius = (out.pipeline == GPE_PIPELINE_NATIVE && N.uniform) ? 1u : 0u;
     if (N.tile_ctl) {
         uint32_t sorts = 0, seen = 0;
         GPE_HIP(c, hipMemcpyAsync(&sorts, N.tile_ctl + kNativeCtlSorts, sizeof(sorts), hipMemcpyDeviceToHost, c->stream));
@@ -1554,6 +1555,8 @@ gpe_status gpe_device_ptr(gpe_ctx *c, gpe_array what, void **device_ptr, uint64_
     const void *p;
     uint64_t b;
     GPE_TRY(locate(c, what, &p, &b));
+    // (the caller may write radii through it: the step reads every particle's radius again until the next configuration)
+    if (what == GPE_RADIUS) c->native.uniform = false;
     *device_ptr = const_cast<void *>(p);
     if (bytes) *bytes = b;
     return GPE_OK;
@@ -1729,6 +1732,7 @@ gpe_status gpe_set_counts(gpe_ctx *c, uint64_t n_total, uint64_t n_owned)
     if (has_fields(c)) return refuse_fields(c, "gpe_set_counts");
     c->n = n_total;
     c->n_owned = n_owned;
+    c->native.uniform = false;                 // (slots the configuration has not looked at: NativeState::uniform)
     return GPE_OK;
 }
 
@@ -1742,6 +1746,7 @@ gpe_status gpe_use_order_keys(gpe_ctx *c, int32_t enable)
     if (enable && has_colliders(c)) return refuse_colliders(c, "gpe_use_order_keys");
     if (enable && has_fields(c)) return refuse_fields(c, "gpe_use_order_keys");
     c->use_order_keys = enable != 0;
+    if (enable) c->native.uniform = false;     // (order-key tiles keep the general path: NativeState::uniform)
     return GPE_OK;
 }
 

@@ -566,6 +566,12 @@ struct NativeState {
     uint32_t reason = GPE_REASON_NO_PARTICLES;   // why the native kernels do not run (GPE_REASON_*), NONE when they do
     uint64_t native_steps = 0, compat_steps = 0;
     bool always_sort = false;        // GPE_FLAG_SORT_EVERY_STEP (A/B measurements, tests): sort every step as rounds 1-2 did
+    // Every radius was this one number, in plain_radius_lanes' range [1e-30, 1e30], when native_configure last looked
+    // (every entry point that changes radii comes through it), and nothing has been able to change one since: the step
+    // runs the kernels that take it as a constant.  Off on sharded contexts (order keys, an active box), once
+    // gpe_device_ptr(GPE_RADIUS) has been handed out (native_radius_exposed) and under GPE_FLAG_GENERAL_RADII.
+    bool uniform = false;
+    float uniform_r = 0.0f;
     int32_t blocks_x = 0, blocks_y = 0;   // 8x8-cell blocks of the block box: table index = (by - by0) * blocks_x + (bx - bx0)
     int32_t bx0 = 0, by0 = 0;        // first block of the box (sharded runs: the rank's active box; else 0, 0)
     uint32_t *tile_ctl = nullptr;    // device control words (native_launch.h kCtl*)
@@ -1009,8 +1015,8 @@ class Scope {
    public:
     enum Boundaries { kOwnEvents, kSharedBoundaries };
     // Timestamp slots, shared boundaries: the stamp of the scope's opening / closing is owed to the enqueue that
-    // follows (scope_stamps.h) -- written by that launch's first workgroup when it is one of the two gated sort
-    // kernels, by a kernel of its own right in front of it otherwise.  For boundaries whose next launch comes at once
+    // follows (scope_stamps.h) -- written by that launch's first workgroup when it is the hash or one of the two gated
+    // sort kernels, by a kernel of its own right in front of it otherwise.  For boundaries whose next launch comes at once
     // and in front of short launches; without the hint a boundary is stamped at once, which is what the end of a long
     // kernel needs (the host must not delay it).  Timing only: the stamp lies between the same two launches either way.
     enum Carry : unsigned { kCarryNone = 0u, kCarryStart = 1u, kCarryStop = 2u };
@@ -1034,7 +1040,7 @@ inline void note_enqueue(gpe_ctx *c)
     c->scope_stamps.note_enqueue();
     c->stamp_be.flush();
 }
-// For the launchers of the two gated sort kernels, BEFORE their note_enqueue: where the kernel's first workgroup writes
+// For the launchers of the hash and of the two gated sort kernels, BEFORE their note_enqueue: where the kernel's first workgroup writes
 // the owed timestamp (the kernel starts at that boundary), or NULL when none is owed.
 inline unsigned long long *scope_stamp_for_next_launch(gpe_ctx *c)
 {

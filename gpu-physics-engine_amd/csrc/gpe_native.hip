@@ -181,6 +181,12 @@ static gpe_status native_prepare_step(gpe_ctx *c, uint32_t **sorted_ids, bool al
                        N.exc_count != nullptr;                         // (no room for the straggler lists: sort every step)
     const uint64_t pairs = ((uint64_t)N.table_entries + 1) / 2;        // the table is allocated in 16-byte units
     const bool fuse_hist = plan.fuse_hist;
+    // The keys have two readers, the gated histogram and the first radix pass, and both return at once on a step that does
+    // not sort.  So a step that keeps its table and leaves the digits to the gated launch stores none (4 of the 24 B the
+    // hash moves per particle): the gated launch forms them from the positions when it runs.  Not on sharded set-ups
+    // (padding keys, ghosts); steps that fuse the histogram or sort unconditionally store them as they always did.
+    const bool late_keys = reuse && !fuse_hist && !sharded;
+    const bool uniform = N.uniform && !sharded;                        // (sharded: switched off where it begins, and here)
     HashGhosts hg;
     hg.sorted_count = N.tile_ctl + kCtlSortedCount;
     uint64_t g_bound = 0;
@@ -213,15 +219,18 @@ static gpe_status native_prepare_step(gpe_ctx *c, uint32_t **sorted_ids, bool al
     const uint64_t div_magic = ((1ull << 40) + (uint64_t)N.blocks_x - 1) / (uint64_t)N.blocks_x;
     {
         // (what follows the hash is the gated histogram or the first gated radix pass: either carries the boundary
-        // behind it)
-        Scope s(c, "native/hash", Scope::kSharedBoundaries, Scope::kCarryStop);
+        // behind it; the hash carries the one in front of itself -- stamped at once by a kernel of its own, that boundary
+        // put the host's time to marshal the hash's launch into the scope whenever the GPU had caught up with the host,
+        // which a small scene does the more often the faster its kernels are)
+        Scope s(c, "native/hash", Scope::kSharedBoundaries, Scope::kCarryStart | Scope::kCarryStop);
         // at least 4 keys per lane (measured: profiles/r01/tune_hash.txt)
         // (two particles per thread until the grid is full: 14.0 against 14.3 us at 1 M with four, 15.2 with one --
         // the kernel is launch and latency there; from 4 M particles on the grid is kHashGridMax either way)
         const int grid = (int)std::min<uint64_t>(kHashGridMax, std::max<uint64_t>(1, n / (2ull * kHashBlock)));
         const uint32_t *n_valid = (c->shard.on && c->shard.active) ? c->shard.counts_now() + kShardTotal : nullptr;
-        launch_native_hash(c, kept_sharded, grid, c->pos, c->radius, n, n_valid,
-                           c->cell_size, N.gx, N.gy, N.bx0, N.by0, N.blocks_x, N.blocks_y, N.table_entries, N.keys,
+        launch_native_hash(c, kept_sharded, grid, c->pos, c->radius, uniform, N.uniform_r, n, n_valid,
+                           c->cell_size, N.gx, N.gy, N.bx0, N.by0, N.blocks_x, N.blocks_y, N.table_entries,
+                           late_keys ? nullptr : N.keys,
                            N.codes, N.passes, hist_now, hist_next, c->os_ws.ctl, N.tile_ctl,
                            (uint4 *)N.block_table, gated ? 0ull : pairs,    // gated: the first radix pass resets the table
                            N.host_stat, reuse ? N.sorted_key : nullptr, parity, div_magic,
@@ -242,7 +251,12 @@ static gpe_status native_prepare_step(gpe_ctx *c, uint32_t **sorted_ids, bool al
         if (reuse && !fuse_hist) {
             // (the hash kernel counted nothing: see fuse_hist there)
             const int hgrid = (int)std::min<uint64_t>(kHistGatedGridMax, std::max<uint64_t>(1, n / (4ull * kHistGatedBlock)));
-            launch_native_hist_gated(c, hgrid, N.keys, n, N.passes, hist_now, g.need);
+            HistKeys hk;
+            if (late_keys) {
+                hk.pos = c->pos; hk.cell_size = c->cell_size;
+                hk.gx = N.gx; hk.gy = N.gy; hk.bx0 = N.bx0; hk.by0 = N.by0; hk.blocks_x = N.blocks_x; hk.blocks_y = N.blocks_y;
+            }
+            launch_native_hist_gated(c, hgrid, N.keys, n, N.passes, hist_now, g.need, hk);
             GPE_HIP(c, hipGetLastError());
         }
         g.fresh = N.tile_ctl + kCtlFresh + parity;
@@ -293,6 +307,7 @@ gpe_status native_configure(gpe_ctx *c)
     NativeState &N = c->native;
     N.policy.configure(N.host_stat ? native_read_stats(N).sorts : 0u);   // (host_stat: from an earlier configuration)
     N.in_box = false;
+    N.uniform = false;                   // (decided below, from the radii as they are now)
     N.sort_state_valid = false;          // particles, box or keys changed: the kept grouping is of something else
     N.always_sort = (c->cfg.flags & GPE_FLAG_SORT_EVERY_STEP) != 0;
     N.reason = GPE_REASON_NO_PARTICLES;
@@ -452,13 +467,26 @@ gpe_status native_configure(gpe_ctx *c)
     memset(N.host_stat, 0, 64);
     GPE_TRY(onesweep_reserve(c, c->cap));
     GPE_HIP(c, hipMemsetAsync(N.tile_ctl, 0, kCtlSorts * sizeof(uint32_t), c->stream));
+    // One radius for all?  The same pass over the particles answers it.  Not asked where the general kernels stay anyway:
+    // sharded contexts (ghosts arrive with radii of their own; order-key tiles), GPE_FLAG_GENERAL_RADII.
+    const bool ask_radii = !c->shard.on && !c->use_order_keys && !c->has_active_box && (c->cfg.flags & GPE_FLAG_GENERAL_RADII) == 0;
+    GPE_HIP(c, hipMemsetAsync(N.tile_ctl + kCtlRadiusBits, 0, 2 * sizeof(uint32_t), c->stream));
     launch_native_check_box(c, c->pos, c->n,
                             (c->shard.on && c->shard.active) ? c->shard.counts_now() + kShardTotal : nullptr, c->cell_size, N.gx, N.gy,
-                            N.tile_ctl + kCtlError);
+                            N.tile_ctl + kCtlError, ask_radii ? c->radius : nullptr, N.tile_ctl + kCtlRadiusBits);
     GPE_HIP(c, hipGetLastError());
     uint32_t flag = 1;
+    uint32_t radius_bits[2] = {0u, 0u};
     GPE_HIP(c, hipMemcpyAsync(&flag, N.tile_ctl + kCtlError, sizeof(flag), hipMemcpyDeviceToHost, c->stream));
+    GPE_HIP(c, hipMemcpyAsync(radius_bits, N.tile_ctl + kCtlRadiusBits, sizeof(radius_bits), hipMemcpyDeviceToHost, c->stream));
     GPE_HIP(c, hipStreamSynchronize(c->stream));
+    if (ask_radii && ~radius_bits[0] == radius_bits[1]) {
+        // (plain_radius_lanes' range, k_pair.h: positive, finite, 1 / r finite -- the radii for which equal radii make
+        // both weights of a pair exactly 0.5)
+        float r;
+        memcpy(&r, &radius_bits[1], sizeof(r));
+        if (r >= 1e-30f && r <= 1e30f) { N.uniform = true; N.uniform_r = r; }
+    }
     GPE_HIP(c, hipMemsetAsync(N.tile_ctl, 0, kCtlSorts * sizeof(uint32_t), c->stream));         // the check's verdict is not a step error
     N.reason = GPE_REASON_OUT_OF_BOX;
     if (flag != 0) return GPE_OK;                                      // a particle outside the box: compat kernels
@@ -578,6 +606,8 @@ gpe_status native_collide(gpe_ctx *c, const float2 *pos_in, float2 *pos_out, con
     CollideArgs A;
     A.pos_in = pos_in;
     A.radius = c->radius;
+    A.uniform = (N.uniform && !c->shard.on && !c->use_order_keys && !c->has_active_box) ? 1u : 0u;
+    A.uniform_r = N.uniform_r;
     A.pos_out = pos_out;
     A.sorted_ids = sorted_ids;
     A.codes = N.codes;

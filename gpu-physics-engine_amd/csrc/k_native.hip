@@ -133,7 +133,11 @@ constexpr uint32_t kWindowReport = 512;     // tiles report windows above this p
 // (the handover and eligibility populations, kWindowHandover / kWindowEligible, are the step policy's: native_policy.h)
 
 // ---------------------------------------------------------------------------------------------------
-// hash: R pos 8 B, W key 4 B per particle; fused 4-digit histogram for the onesweep passes.
+// hash: per particle R pos 8 B, radius 4 B, old key 4 B (kept table); W code 4 B, key 4 B -- 24 B.  Two of the five never
+// change the result on the steps of a run that keeps its table: the UNIFORM instantiation takes the one radius all
+// particles have as a kernel argument (NativeState::uniform), and a kept-table step whose digits the gated launch counts
+// stores no key (keys == NULL: k_native_hist_gated derives the keys itself on the steps that sort) -- 16 B.
+// Fused 4-digit histogram for the onesweep passes on the steps that sort anyway.
 // (home_cell_ids.wgsl:24-31 computes the Morton id of the home cell; the key kept here is the row-major index
 // of its 8x8-cell block; the particle id is implicit in the first pass.)
 // The workgroup that flushes its histogram last also turns the histograms into the digit bases of the four
@@ -148,12 +152,28 @@ constexpr uint32_t kWindowReport = 512;     // tiles report windows above this p
 // (profiles/r02/ab_hash_occupancy.txt).
 // (kHashBlock, kHashGridMax and HashGhosts: native_launch.h)
 constexpr int kHashBatch = 2;                  // positions loaded per lane before any of them is ranked
+// The sort key of a particle at p: its 8x8-cell block, row-major over the block box; 0 and `out` for a particle outside
+// the cell box or the block box (flagged by the hash).  cx, cy: its home cell.  One expression for the two kernels that
+// form keys -- the hash, and the gated histogram on the steps whose hash stored none.
+__device__ __forceinline__ uint32_t block_key_of(const float2 p, const float cell_size, const int32_t gx, const int32_t gy,
+                                                 const int32_t bx0, const int32_t by0, const int32_t blocks_x,
+                                                 const int32_t blocks_y, int32_t &cx, int32_t &cy, bool &out)
+{
+    cx = cell_coord(p.x, cell_size);
+    cy = cell_coord(p.y, cell_size);
+    const int32_t lbx = (cx >> 3) - bx0, lby = (cy >> 3) - by0;
+    out = (cx < 0) | (cx >= gx) | (cy < 0) | (cy >= gy) | (lbx < 0) | (lbx >= blocks_x) | (lby < 0) | (lby >= blocks_y);
+    // (24-bit multiply-add: both factors are below 2^13 for an in-box cell; a full-rate instruction where the 32-bit
+    // multiply takes four issue slots -- the hash is bound by issue at 100 M, not by HBM)
+    return out ? 0u : __umul24((uint32_t)lby, (uint32_t)blocks_x) + (uint32_t)lbx;
+}
 // GHOSTS: a sharded run with its counts on the device (HashGhosts); the ordinary instantiation carries none of that code.
 // Index: the type of the particle indices, the stride and the round counters.  uint32_t while every index the loop forms
 // stays below 2^31 (launch_native_hash: 1 M and 100 M particles both do) -- an address is then base + zero-extended index,
 // where the 64-bit form multiplies, shifts and adds register pairs on the VALU for each of the five arrays a particle
 // touches; uint64_t beyond that.  Same stores, same atomics in the same order, same bits either way.
-template <bool GHOSTS, typename Index>
+// UNIFORM: every particle has the radius uniform_r (NativeState::uniform): `radius` is not read.
+template <bool GHOSTS, typename Index, bool UNIFORM = false>
 __global__ __launch_bounds__(kHashBlock, 8) void k_native_hash(const float2 *__restrict__ pos,
                                                             const float *__restrict__ radius, uint64_t n64,
                                                             const uint32_t *__restrict__ n_valid_ptr,
@@ -167,11 +187,14 @@ __global__ __launch_bounds__(kHashBlock, 8) void k_native_hash(const float2 *__r
                                                             uint4 *__restrict__ table2, uint64_t table_pairs,
                                                             uint32_t *__restrict__ host_stat,
                                                             const uint32_t *__restrict__ sorted_key, uint32_t parity,
-                                                            uint64_t div_magic, uint32_t *__restrict__ exc_count,
+                                                            float uniform_r, uint32_t *__restrict__ exc_count,
                                                             uint2 *__restrict__ exc_entry,
                                                             uint32_t *__restrict__ exc_count_next, TileBox tb,
-                                                            uint32_t straggler_limit, uint32_t fuse_always, HashGhosts G)
+                                                            uint32_t straggler_limit, uint32_t fuse_always, HashGhosts G,
+                                                            unsigned long long *stamp)
 {
+    // (a sampled step's boundary in front of this launch: scope_stamps.h)
+    if (stamp && blockIdx.x == 0 && threadIdx.x == 0) *stamp = wall_clock64();
     // sorted_key[i] = the block key particle i had when the radix passes last ran (they keep it up to date,
     // k_onesweep.hip): the sorted ids and the block table still describe THAT grouping.  As long as every particle
     // is within kDrift* cells of its old block, the tiles find it through the old table (they look up more than they
@@ -179,7 +202,9 @@ __global__ __launch_bounds__(kHashBlock, 8) void k_native_hash(const float2 *__r
     // beyond that go to per-tile straggler lists (kExcSlots); a list running over raises tile_ctl[kCtlNeedSort +
     // parity]; the radix passes that follow look at the word and return at once when it is 0.
     // sorted_key == NULL: always sort (first step, sharded runs, one-pass sorts).
-    (void)div_magic;                                                   // (the division moved to the radix pass that writes sorted_key)
+    // (uniform_r stands where the block key's division magic stood until the division moved to the radix pass that
+    // writes sorted_key: the kernel takes as many arguments as it did -- on a small scene the host's time to marshal a
+    // launch is on the step's critical path)
     __shared__ uint32_t s_hist[4 * 256];
     __shared__ uint32_t s_ghist[GHOSTS ? 4 * 256 : 1];                 // (the ghosts' keys, sharded runs)
     __shared__ uint32_t s_sort_known;                                  // a wave of this workgroup has seen the straggler limit passed
@@ -281,7 +306,8 @@ __global__ __launch_bounds__(kHashBlock, 8) void k_native_hash(const float2 *__r
             idx[u] = (r0 + (Index)u) * stride + first_idx;
             const bool in = r0 + (Index)u < rounds && idx[u] < nv;
             p[u] = in ? pos[idx[u]] : make_float2(0.f, 0.f);
-            rad[u] = in ? radius[idx[u]] : 0.f;
+            if constexpr (UNIFORM) rad[u] = uniform_r;
+            else rad[u] = in ? radius[idx[u]] : 0.f;
             okey[u] = (in && sorted_key) ? sorted_key[idx[u]] : 0u;
         }
 #pragma unroll
@@ -290,29 +316,26 @@ __global__ __launch_bounds__(kHashBlock, 8) void k_native_hash(const float2 *__r
             const bool valid = idx[u] < n;
             uint32_t key = pad_key;
             if (valid && idx[u] >= nv) {
-                keys[idx[u]] = pad_key; codes[idx[u]] = 0u;
+                if (keys) keys[idx[u]] = pad_key;
+                codes[idx[u]] = 0u;
                 if (GHOSTS && G.gkeys && (uint64_t)(idx[u] - n_own) < G.g_bound) { G.gkeys[idx[u] - n_own] = pad_key; G.gids[idx[u] - n_own] = 0u; }
             }
             const bool ghost = GHOSTS && idx[u] >= n_own;
             uint32_t gkey = 0;
             bool gvalid = false;
             if (idx[u] < nv) {
-                const int32_t cx = cell_coord(p[u].x, cell_size), cy = cell_coord(p[u].y, cell_size);
                 // the particle's 8x8-cell block, row-major over the block box (0 for a particle outside it: flagged)
-                const int32_t lbx = (cx >> 3) - bx0, lby = (cy >> 3) - by0;
-                const bool out = (cx < 0) | (cx >= gx) | (cy < 0) | (cy >= gy) | (lbx < 0) | (lbx >= blocks_x) |
-                                 (lby < 0) | (lby >= blocks_y);
+                int32_t cx, cy;
+                bool out;
+                key = block_key_of(p[u], cell_size, gx, gy, bx0, by0, blocks_x, blocks_y, cx, cy, out);
                 oob |= out;
-                // (24-bit multiply-add: both factors are below 2^13 for an in-box cell; a full-rate instruction where
-                // the 32-bit multiply takes four issue slots -- the kernel is bound by issue at 100 M, not by HBM)
-                key = out ? 0u : __umul24((uint32_t)lby, (uint32_t)blocks_x) + (uint32_t)lbx;
                 if (GHOSTS && ghost && G.gkeys) {
                     // a ghost: grouped by the ghosts' own sort; in the owned particles' sort it is padding
                     const uint64_t j = (uint64_t)(idx[u] - n_own);
                     if (j < G.g_bound) { G.gkeys[j] = key; G.gids[j] = (uint32_t)idx[u]; gkey = key; gvalid = true; }
                     key = pad_key;
                 }
-                keys[idx[u]] = key;
+                if (keys) keys[idx[u]] = key;                          // (kernel-uniform; NULL: nobody reads them unless the step sorts)
                 // The particle's cell relative to the first cell of the block it was SORTED into: is it still within the
                 // reach of the tiles that find it through that block?
                 bool straggler = false;
@@ -434,10 +457,13 @@ __global__ __launch_bounds__(kHashBlock, 8) void k_native_hash(const float2 *__r
 // The digit histograms of the keys when the hash kernel has left them out (a run that keeps its block table): gated like
 // the radix passes behind it -- every workgroup looks at need_sort first and returns at once when no sort is due.  Same
 // layout as the hash's flush (kHistCopies copies of 4 x 256 bins, two bins per 64-bit atomic).
-__global__ __launch_bounds__(kHistGatedBlock) void k_native_hist_gated(const uint32_t *__restrict__ keys, uint64_t n, int digits,
+// K.pos != NULL: the hash stored no keys this step (nobody reads them on a step that does not sort); this kernel runs exactly
+// when the radix passes behind it will (the same word gates both), so it forms the keys from the positions -- the hash's
+// own expression, block_key_of -- stores them for the first pass and counts them.  K.pos == NULL: the hash stored them.
+__global__ __launch_bounds__(kHistGatedBlock) void k_native_hist_gated(uint32_t *__restrict__ keys, uint64_t n, int digits,
                                                                        uint32_t *__restrict__ hist4,
                                                                        const uint32_t *__restrict__ need,
-                                                                       unsigned long long *stamp)
+                                                                       unsigned long long *stamp, HistKeys K)
 {
     // (a sampled step's boundary in front of this launch: scope_stamps.h)
     if (stamp && blockIdx.x == 0 && threadIdx.x == 0) *stamp = wall_clock64();
@@ -450,7 +476,15 @@ __global__ __launch_bounds__(kHistGatedBlock) void k_native_hist_gated(const uin
     for (uint64_t r = 0; r < rounds; ++r) {
         const uint64_t idx = r * stride + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
         const bool valid = idx < n;
-        const uint32_t key = valid ? keys[idx] : 0u;
+        uint32_t key = 0u;
+        if (K.pos) {                                                   // (kernel-uniform)
+            if (valid) {
+                int32_t cx, cy;
+                bool out;
+                key = block_key_of(K.pos[idx], K.cell_size, K.gx, K.gy, K.bx0, K.by0, K.blocks_x, K.blocks_y, cx, cy, out);
+                keys[idx] = key;
+            }
+        } else if (valid) key = keys[idx];
 #pragma unroll
         for (int q = 0; q < 4; ++q)
             if (q < digits) hist_add(s_hist + q * 256, (key >> (8 * q)) & 255u, valid);
@@ -500,20 +534,37 @@ __global__ void k_native_publish_probe(uint32_t *__restrict__ tile_ctl, uint32_t
 }
 
 // every particle inside the cell box?  (configuration-time check, not on the step path)
+// radius != NULL: also the range of the radii's BIT PATTERNS, as maxima into radius_bits (cleared by the caller):
+// [0] = ~(smallest pattern), [1] = largest pattern.  Equal patterns: every particle has that one radius (NativeState::uniform).
 __global__ __launch_bounds__(kStreamBlock) void k_native_check_box(const float2 *__restrict__ pos, uint64_t n,
                                                                    const uint32_t *__restrict__ n_valid_ptr,
                                                                    float cell_size, int32_t gx, int32_t gy,
-                                                                   uint32_t *__restrict__ flag)
+                                                                   uint32_t *__restrict__ flag,
+                                                                   const float *__restrict__ radius,
+                                                                   uint32_t *__restrict__ radius_bits)
 {
     if (n_valid_ptr && *n_valid_ptr < n) n = *n_valid_ptr;           // sharded run: the count lives on the device
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
     bool oob = false;
+    uint32_t lo = 0xFFFFFFFFu, hi = 0u;
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
         const float2 p = pos[i];
         const int32_t cx = cell_coord(p.x, cell_size), cy = cell_coord(p.y, cell_size);
         oob |= (cx < 0) | (cx >= gx) | (cy < 0) | (cy >= gy);
+        if (radius) {                                                  // (kernel-uniform)
+            const uint32_t bits = __float_as_uint(radius[i]);
+            lo = min(lo, bits);
+            hi = max(hi, bits);
+        }
     }
     if (oob) atomicOr(flag, kErrOutOfBox);
+    if (radius) {
+        for (int d = 32; d >= 1; d >>= 1) {
+            lo = min(lo, (uint32_t)__shfl_xor((int)lo, d, 64));
+            hi = max(hi, (uint32_t)__shfl_xor((int)hi, d, 64));
+        }
+        if (lane_id() == 0 && lo <= hi) { atomicMax(&radius_bits[0], ~lo); atomicMax(&radius_bits[1], hi); }
+    }
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -616,6 +667,9 @@ struct TileLds {
     static_assert(NCELL < 2048, "hm packs home (11 bit) | overlap mask (8) | own (1)");
     static constexpr int QZ = (T + 8) * (T + 4) / 4;                      // cells of one colour inside its zone
     float px[CAP], py[CAP], rad[CAP];
+    // (a radius per staged particle; TileDirect can do without: kUniform there)
+    static constexpr bool kUniform = false;
+    __device__ __forceinline__ float radius_of(const uint32_t s, const UniformRadii &) const { return rad[s]; }
     uint32_t id[CAP];
     uint32_t hm[CAP];          // bits 0-10 index of the home cell in the padded cell array; bits 11-18 overlap mask of
                                // the 8 neighbour cells (k_native_hash); bit 19 the home cell lies in the tile (the
@@ -685,6 +739,8 @@ struct TileGlobal {
     static constexpr int QMAX = 1;
     static constexpr int QZ = (T + 8) * (T + 4) / 4;
     float *px, *py, *rad;
+    static constexpr bool kUniform = false;
+    __device__ __forceinline__ float radius_of(const uint32_t s, const UniformRadii &) const { return rad[s]; }
     uint32_t *id, *hm, *mem;
     uint8_t *sblk;
     uint32_t cell[NCELL + 1];      // 32-bit cells: the member count is not bounded by an LDS capacity here
@@ -760,6 +816,23 @@ __device__ __forceinline__ void sort_members(L &S, const uint32_t b, const uint3
     }
 }
 
+// One pair, in the form the window's layout L asks for: a layout without a radius array (L::kUniform, TileDirect) takes
+// the uniform pair_response with the kernel's UniformRadii; every other layout the general one with the two radii its
+// resolver read (S.radius_of) and the `plain` vote (plain_lanes).  The resolvers below are written once for both.
+template <class L>
+__device__ __forceinline__ uint64_t plain_lanes(const float r)
+{
+    if constexpr (L::kUniform) return 0ull; else return plain_radius_lanes(r);
+}
+template <class L, bool BOTH = true>
+__device__ __forceinline__ uint64_t respond(const uint64_t active, f32x2 &p1, std::conditional_t<BOTH, f32x2 &, const f32x2 &> p2,
+                                            const float r1, const float r2, const uint64_t plain, const UniformRadii &U,
+                                            const float stiffness, const uint64_t lower = ~0ull, const uint64_t careful = 0)
+{
+    if constexpr (L::kUniform) return pair_response<BOTH>(active, p1, p2, U, stiffness, lower, careful);
+    else return pair_response<BOTH>(active, p1, p2, r1, r2, plain, stiffness, lower, careful);
+}
+
 // The reference's pair resolution (collision_solver.wgsl:66-118), on LDS-resident positions: one lane walks the
 // pairs (a, b), a < b, of its cell.  Bit-exact restatements that shorten the dependent chain:
 //  * the next partner's position is fetched while the current pair is computed: within one `a` loop every pair
@@ -768,23 +841,23 @@ __device__ __forceinline__ void sort_members(L &S, const uint32_t b, const uint3
 // (Called under divergent control flow -- the lanes walk cells of different sizes: the votes cover the lanes that are
 // in the same iteration.)
 template <class L>
-__device__ __forceinline__ void resolve_cell(L &S, const uint32_t b, const uint32_t e, const float stiffness)
+__device__ __forceinline__ void resolve_cell(L &S, const uint32_t b, const uint32_t e, const float stiffness, const UniformRadii &U)
 {
     for (uint32_t ia = b; ia + 1 < e; ++ia) {                         // :68
         const uint32_t a = S.mem[ia];
         uint32_t nb = S.mem[ia + 1];
         f32x2 p1 = {S.px[a], S.py[a]};
-        const float r1 = S.rad[a];
+        const float r1 = S.radius_of(a, U);
         f32x2 nxt = {S.px[nb], S.py[nb]};
-        float nr = S.rad[nb];
-        const uint64_t plain = plain_radius_lanes(r1);
+        float nr = S.radius_of(nb, U);
+        const uint64_t plain = plain_lanes<L>(r1);
         bool dirty = false;
         for (uint32_t ib = ia + 1; ib < e; ++ib) {                    // :77
             const uint32_t bb = nb;
             f32x2 p2 = nxt;                                           // :86 live position
             const float r2 = nr;
-            if (ib + 1 < e) { nb = S.mem[ib + 1]; nxt = (f32x2){S.px[nb], S.py[nb]}; nr = S.rad[nb]; }
-            const uint64_t hit = pair_response(ballot64(true), p1, p2, r1, r2, plain, stiffness);
+            if (ib + 1 < e) { nb = S.mem[ib + 1]; nxt = (f32x2){S.px[nb], S.py[nb]}; nr = S.radius_of(nb, U); }
+            const uint64_t hit = respond<L>(ballot64(true), p1, p2, r1, r2, plain, U, stiffness);
             if (hit != 0) {
                 if (lanes_of(hit)) { S.px[bb] = p2.x; S.py[bb] = p2.y; dirty = true; }
             }
@@ -803,7 +876,7 @@ __device__ __forceinline__ void resolve_cell(L &S, const uint32_t b, const uint3
 // `on`, `n <= 3` ... must reach this function as comparisons (they are voted on one by one, see pair_response).
 template <class L>
 __device__ __forceinline__ void resolve_small_cells(L &S, const bool on, const uint32_t b, const uint32_t n,
-                                                    const float stiffness)
+                                                    const float stiffness, const UniformRadii &U)
 {
     const uint64_t on_m = ballot64(on);
     const uint64_t small_m = on_m & ballot64(n <= 3u), three_m = on_m & ballot64(n == 3u);
@@ -829,18 +902,18 @@ __device__ __forceinline__ void resolve_small_cells(L &S, const bool on, const u
 #undef GPE_CSWAP
     }
     if (small) {
-        p0 = (f32x2){S.px[m0], S.py[m0]}; r0 = S.rad[m0];
-        p1 = (f32x2){S.px[m1], S.py[m1]}; r1 = S.rad[m1];
+        p0 = (f32x2){S.px[m0], S.py[m0]}; r0 = S.radius_of(m0, U);
+        p1 = (f32x2){S.px[m1], S.py[m1]}; r1 = S.radius_of(m1, U);
     }
     if (any3) {
-        if (three) { p2 = (f32x2){S.px[m2], S.py[m2]}; r2 = S.rad[m2]; }
+        if (three) { p2 = (f32x2){S.px[m2], S.py[m2]}; r2 = S.radius_of(m2, U); }
     }
-    const uint64_t plain0 = plain_radius_lanes(r0);
+    const uint64_t plain0 = plain_lanes<L>(r0);
     uint64_t h01 = 0, h02 = 0, h12 = 0;
-    h01 = pair_response(small_m, p0, p1, r0, r1, plain0, stiffness);
+    h01 = respond<L>(small_m, p0, p1, r0, r1, plain0, U, stiffness);
     if (any3) {
-        h02 = pair_response(three_m, p0, p2, r0, r2, plain0, stiffness);
-        h12 = pair_response(three_m, p1, p2, r1, r2, plain_radius_lanes(r1), stiffness);
+        h02 = respond<L>(three_m, p0, p2, r0, r2, plain0, U, stiffness);
+        h12 = respond<L>(three_m, p1, p2, r1, r2, plain_lanes<L>(r1), U, stiffness);
     }
     if ((h01 | h02 | h12) != 0) {                                      // wave-uniform
         if (lanes_of(h01 | h02)) { S.px[m0] = p0.x; S.py[m0] = p0.y; }
@@ -849,7 +922,7 @@ __device__ __forceinline__ void resolve_small_cells(L &S, const bool on, const u
     }
     if (on && n > 3u) {                                                // a pile in the one-lane list: the general walk
         sort_members(S, b, b + n);
-        resolve_cell(S, b, b + n, stiffness);
+        resolve_cell(S, b, b + n, stiffness, U);
     }
 }
 
@@ -904,7 +977,7 @@ __device__ __forceinline__ void for_each_group_step(F &&f)
 // NMAX: the most members a group cell of this window form can have
 template <int NMAX, class L>
 __device__ __forceinline__ void resolve_group(L &S, const uint32_t b, const uint32_t n, const int a,
-                                              const float stiffness)
+                                              const float stiffness, const UniformRadii &U)
 {
     static_assert(NMAX >= (int)kGroupMin && NMAX <= (int)kGroupLanes, "group cells: 4 .. 8 members");
     const int group_base = lane_id() & ~((int)kGroupLanes - 1);
@@ -921,11 +994,12 @@ __device__ __forceinline__ void resolve_group(L &S, const uint32_t b, const uint
                                                                   (int)my_slot);
     f32x2 o = {0.f, 0.f};                                             // step-start state of the lane's particle
     float r1 = 1.f;
-    if (has) { o = (f32x2){S.px[a_slot], S.py[a_slot]}; r1 = S.rad[a_slot]; }
+    if (has) { o = (f32x2){S.px[a_slot], S.py[a_slot]}; r1 = S.radius_of(a_slot, U); }
     f32x2 p1 = o;
-    const uint64_t plain = plain_radius_lanes(r1);
+    const uint64_t plain = plain_lanes<L>(r1);
     const uint64_t careful = neg_zero_lanes(p1);                      // (see pair_response<false>)
-    const float r_mirrored = dpp_mov<kDppHalfMirror>(r1);
+    float r_mirrored = 0.f;                                           // (one radius for all: no partner's radius to fetch)
+    if constexpr (!L::kUniform) r_mirrored = dpp_mov<kDppHalfMirror>(r1);
     const uint32_t n_plus_a = n + (uint32_t)a;                        // partner s - a exists while s - a < n
     // how long the longest schedule of the wave is (the cells of a wave differ): steps beyond 2 * 4 - 3 are skipped
     // by a scalar test unless some cell has the members for them
@@ -940,11 +1014,12 @@ __device__ __forceinline__ void resolve_group(L &S, const uint32_t b, const uint
         }
         const f32x2 ip = {dpp_reflect_from_mirrored<s>(dpp_mov<kDppHalfMirror>(p1.x)),
                           dpp_reflect_from_mirrored<s>(dpp_mov<kDppHalfMirror>(p1.y))};
-        const float ir = dpp_reflect_from_mirrored<s>(r_mirrored);
+        float ir = 0.f;
+        if constexpr (!L::kUniform) ir = dpp_reflect_from_mirrored<s>(r_mirrored);
         constexpr uint64_t kStepLanes = group_step_lanes<s>();
         const uint64_t pairing = has_m & kStepLanes & ballot64((uint32_t)s < n_plus_a);
         constexpr uint64_t kLower = group_step_lanes<s, true>();      // (the lane with the smaller index of each pair)
-        (void)pair_response<false>(pairing, p1, ip, r1, ir, plain, stiffness, kLower, careful);
+        (void)respond<L, false>(pairing, p1, ip, r1, ir, plain, U, stiffness, kLower, careful);
     });
     if (has && (__float_as_uint(p1.x) != __float_as_uint(o.x) || __float_as_uint(p1.y) != __float_as_uint(o.y))) {
         S.px[a_slot] = p1.x;
@@ -989,7 +1064,8 @@ __device__ __forceinline__ uint32_t row_rank(const uint32_t id)
 }
 // every lane of the wave calls (n == 0: no cell in this row); a = lane & 15
 template <class L>
-__device__ __forceinline__ void resolve_row(L &S, const uint32_t b, const uint32_t n, const int a, const float stiffness)
+__device__ __forceinline__ void resolve_row(L &S, const uint32_t b, const uint32_t n, const int a, const float stiffness,
+                                            const UniformRadii &U)
 {
     const int row_base = lane_id() & ~((int)kRowLanes - 1);
     const uint64_t has_m = ballot64((uint32_t)a < n);
@@ -1001,11 +1077,12 @@ __device__ __forceinline__ void resolve_row(L &S, const uint32_t b, const uint32
     const uint32_t a_slot = (uint32_t)__builtin_amdgcn_ds_permute((row_base + (int)(has ? rank : (uint32_t)a)) << 2, (int)my_slot);
     f32x2 o = {0.f, 0.f};
     float r1 = 1.f;
-    if (has) { o = (f32x2){S.px[a_slot], S.py[a_slot]}; r1 = S.rad[a_slot]; }
+    if (has) { o = (f32x2){S.px[a_slot], S.py[a_slot]}; r1 = S.radius_of(a_slot, U); }
     f32x2 p1 = o;
-    const uint64_t plain = plain_radius_lanes(r1);
+    const uint64_t plain = plain_lanes<L>(r1);
     const uint64_t careful = neg_zero_lanes(p1);                      // (see pair_response<false>)
-    const float r_mirrored = dpp_mov<kDppRowMirror>(r1);
+    float r_mirrored = 0.f;
+    if constexpr (!L::kUniform) r_mirrored = dpp_mov<kDppRowMirror>(r1);
     const uint32_t n_plus_a = n + (uint32_t)a;                        // partner s - a exists while s - a < n
     for_each_group_step<1, 2 * (int)kRowLanes - 3>([&](auto sc) {
         constexpr int s = decltype(sc)::value;
@@ -1015,11 +1092,12 @@ __device__ __forceinline__ void resolve_row(L &S, const uint32_t b, const uint32
         }
         const f32x2 ip = {dpp_reflect_from_row_mirrored<s>(dpp_mov<kDppRowMirror>(p1.x)),
                           dpp_reflect_from_row_mirrored<s>(dpp_mov<kDppRowMirror>(p1.y))};
-        const float ir = dpp_reflect_from_row_mirrored<s>(r_mirrored);
+        float ir = 0.f;
+        if constexpr (!L::kUniform) ir = dpp_reflect_from_row_mirrored<s>(r_mirrored);
         constexpr uint64_t kStepLanes = row_step_lanes<s>();
         const uint64_t pairing = has_m & kStepLanes & ballot64((uint32_t)s < n_plus_a);
         constexpr uint64_t kLower = row_step_lanes<s, true>();
-        (void)pair_response<false>(pairing, p1, ip, r1, ir, plain, stiffness, kLower, careful);
+        (void)respond<L, false>(pairing, p1, ip, r1, ir, plain, U, stiffness, kLower, careful);
     });
     if (has && (__float_as_uint(p1.x) != __float_as_uint(o.x) || __float_as_uint(p1.y) != __float_as_uint(o.y))) {
         S.px[a_slot] = p1.x;
@@ -1046,7 +1124,7 @@ __device__ __forceinline__ float wave_from_lane_above(float v)
 __device__ __forceinline__ f32x2 wave_from_lane_below(f32x2 v) { return (f32x2){wave_from_lane_below(v.x), wave_from_lane_below(v.y)}; }
 __device__ __forceinline__ f32x2 wave_from_lane_above(f32x2 v) { return (f32x2){wave_from_lane_above(v.x), wave_from_lane_above(v.y)}; }
 template <class L>
-__device__ __forceinline__ void resolve_wave(L &S, const uint32_t b, const uint32_t n, const float stiffness)
+__device__ __forceinline__ void resolve_wave(L &S, const uint32_t b, const uint32_t n, const float stiffness, const UniformRadii &U)
 {
     const int a = lane_id();
     const uint64_t has_m = ballot64((uint32_t)a < n);
@@ -1059,25 +1137,28 @@ __device__ __forceinline__ void resolve_wave(L &S, const uint32_t b, const uint3
     const uint32_t a_slot = (uint32_t)__builtin_amdgcn_ds_permute((int)(has ? rank : (uint32_t)a) << 2, (int)my_slot);
     f32x2 o = {0.f, 0.f};
     float r1 = 1.f;
-    if (has) { o = (f32x2){S.px[a_slot], S.py[a_slot]}; r1 = S.rad[a_slot]; }
+    if (has) { o = (f32x2){S.px[a_slot], S.py[a_slot]}; r1 = S.radius_of(a_slot, U); }
     f32x2 p1 = o;
-    const uint64_t plain = plain_radius_lanes(r1);
+    const uint64_t plain = plain_lanes<L>(r1);
     f32x2 qp = {0.f, 0.f};
     float qr = 1.f;
     int qb = -1;
     const int last = 2 * (int)n - 3;
     const bool first = a == 0;
     f32x2 fp = wave_from_lane_above(o);
-    float fr = wave_from_lane_above(r1);
+    float fr = 1.f;                                                    // (the radii travel with the positions unless all are one)
+    if constexpr (!L::kUniform) fr = wave_from_lane_above(r1);
     for (int t = 0; t <= last; ++t) {
         f32x2 ip = wave_from_lane_below(qp);
-        float ir = wave_from_lane_below(qr);
+        float ir = 1.f;
+        if constexpr (!L::kUniform) ir = wave_from_lane_below(qr);
         int ib = wave_from_lane_below(qb);
         if (first) { ip = fp; ir = fr; ib = (t + 1 < (int)n) ? t + 1 : -1; }
-        fp = wave_from_lane_above(fp); fr = wave_from_lane_above(fr);
+        fp = wave_from_lane_above(fp);
+        if constexpr (!L::kUniform) fr = wave_from_lane_above(fr);
         if (ib == a) p1 = ip;                                          // the lane's own particle has arrived
         const uint64_t pairing_m = has_m & ballot64(ib > a);
-        (void)pair_response(pairing_m, p1, ip, r1, ir, plain, stiffness);
+        (void)respond<L>(pairing_m, p1, ip, r1, ir, plain, U, stiffness);
         // (what a lane without a pair passes on is marked "none" and never looked at)
         qp = ip; qr = ir; qb = lanes_of(pairing_m) ? ib : -1;
     }
@@ -1101,7 +1182,8 @@ __device__ __forceinline__ void resolve_wave(L &S, const uint32_t b, const uint3
 // whole balanced duration; profiles/r04/tile_cycles_tail.txt.)
 constexpr uint32_t kWaveCellMax = 1024;
 template <class L>
-__device__ __forceinline__ void resolve_wave_blocked(L &S, const uint32_t b, const uint32_t n, const float stiffness)
+__device__ __forceinline__ void resolve_wave_blocked(L &S, const uint32_t b, const uint32_t n, const float stiffness,
+                                                     const UniformRadii &U)
 {
     const int a = lane_id();
     constexpr int K = (int)kWaveCellMax / 64;
@@ -1147,7 +1229,7 @@ __device__ __forceinline__ void resolve_wave_blocked(L &S, const uint32_t b, con
     }
     for (uint32_t I = 0; I < chunks; ++I) {
         const uint32_t bI = b + 64u * I, cI = min(64u, n - 64u * I);
-        resolve_wave(S, bI, cI, stiffness);                            // pairs inside chunk I (it re-ranks: already sorted)
+        resolve_wave(S, bI, cI, stiffness, U);                         // pairs inside chunk I (it re-ranks: already sorted)
         if (I + 1 == chunks) break;
         wave_lds_order();
         // the owners of this block row
@@ -1156,9 +1238,9 @@ __device__ __forceinline__ void resolve_wave_blocked(L &S, const uint32_t b, con
         const uint32_t o_slot = has ? (uint32_t)S.mem[bI + a] : 0u;
         f32x2 p1 = {0.f, 0.f};
         float r1 = 1.f;
-        if (has) { p1 = (f32x2){S.px[o_slot], S.py[o_slot]}; r1 = S.rad[o_slot]; }
+        if (has) { p1 = (f32x2){S.px[o_slot], S.py[o_slot]}; r1 = S.radius_of(o_slot, U); }
         const f32x2 o = p1;
-        const uint64_t plain = plain_radius_lanes(r1);
+        const uint64_t plain = plain_lanes<L>(r1);
         const bool first = a == 0;
         for (uint32_t J = I + 1; J < chunks; ++J) {
             const uint32_t bJ = b + 64u * J, cJ = min(64u, n - 64u * J);
@@ -1168,7 +1250,7 @@ __device__ __forceinline__ void resolve_wave_blocked(L &S, const uint32_t b, con
             int vs = 0;
             f32x2 vp = {0.f, 0.f};
             float vr = 1.f;
-            if ((uint32_t)a < cJ) { vs = (int)S.mem[bJ + a]; vp = (f32x2){S.px[vs], S.py[vs]}; vr = S.rad[vs]; }
+            if ((uint32_t)a < cJ) { vs = (int)S.mem[bJ + a]; vp = (f32x2){S.px[vs], S.py[vs]}; vr = S.radius_of((uint32_t)vs, U); }
             f32x2 qp = {0.f, 0.f};
             float qr = 1.f;
             int qb = -1, qs = 0;
@@ -1187,7 +1269,7 @@ __device__ __forceinline__ void resolve_wave_blocked(L &S, const uint32_t b, con
                     ib = t < (int)cJ ? t : -1;
                 }
                 const uint64_t pairing_m = has_m & ballot64(ib >= 0);
-                (void)pair_response(pairing_m, p1, ip, r1, ir, plain, stiffness);
+                (void)respond<L>(pairing_m, p1, ip, r1, ir, plain, U, stiffness);
                 const bool pairing = lanes_of(pairing_m);
                 // the visitor leaves the block behind the last owner: store it (it may have been moved by lower
                 // lanes; an unchanged store is harmless)
@@ -1324,7 +1406,8 @@ __device__ __forceinline__ void fetch_own(const L &S, const CollideArgs &A, cons
 // particles for the neighbours on the way (S.id holds the order key).
 template <bool ORD, int NT, int QSKIP, class L, int QOWN>
 __device__ __forceinline__ void write_own_back(const L &S, const CollideArgs &A, const int tid, const uint32_t PS, const uint32_t n_owned,
-                                               const bool packs, const uint32_t (&own_id)[QOWN], const float2 (&own_prev)[QOWN])
+                                               const bool packs, const uint32_t (&own_id)[QOWN], const float2 (&own_prev)[QOWN],
+                                               const UniformRadii &U)
 {
 #pragma unroll
     for (int q = 0; q < QOWN; ++q) {
@@ -1336,7 +1419,7 @@ __device__ __forceinline__ void write_own_back(const L &S, const CollideArgs &A,
         const bool have = id != 0xFFFFFFFFu;
         const uint32_t s = min((uint32_t)tid + (uint32_t)q * NT, (uint32_t)L::kSlots - 1u);
         const float2 c = make_float2(S.px[s], S.py[s]);
-        const float rr = S.rad[s];
+        const float rr = S.radius_of(s, U);
         float2 o = c;
         const bool mine = have && A.fuse_verlet && id < n_owned;
         if (mine) {
@@ -1474,6 +1557,7 @@ __device__ __forceinline__ void hand_tile_on(const CollideArgs &A, const int cou
 template <bool ORD, class L>
 __device__ __forceinline__ bool process_tile(L &S, const CollideArgs &A, const int tx, const int ty)
 {
+    const UniformRadii U = UniformRadii();                             // (not used: these windows keep a radius per particle)
     constexpr int T = L::TILE;
     constexpr int RWX = L::RWX, RWY = L::RWY, PX = L::PX, NCELL = L::NCELL, NB = L::NB, NBLK = L::NBLK, PER = L::PER, QMAX = L::QMAX;
     // virtual blocks: an order-key (sharded) window looks every block up among the owned particles AND among the ghosts
@@ -1837,7 +1921,7 @@ __device__ __forceinline__ bool process_tile(L &S, const CollideArgs &A, const i
                 if (!(GPE_DBG_SKIP & 8))
 #endif
                 if (!GPE_RT_SKIP(1u))
-                resolve_group<(int)kGroupLanes>(S, b, e - b, (int)(i % kGroupLanes), A.stiffness);
+                resolve_group<(int)kGroupLanes>(S, b, e - b, (int)(i % kGroupLanes), A.stiffness, U);
             } else if (i >= single_base && (i & ~63u) < work) {         // (whole waves: the walk uses ballots)
                 const bool on = i < work;
                 uint32_t b = 0, e = 0;
@@ -1849,7 +1933,7 @@ __device__ __forceinline__ bool process_tile(L &S, const CollideArgs &A, const i
                 if (!(GPE_DBG_SKIP & 16))
 #endif
                 if (!GPE_RT_SKIP(2u)) {
-                    resolve_small_cells(S, on, b, e - b, A.stiffness);
+                    resolve_small_cells(S, on, b, e - b, A.stiffness, U);
                 }
             }
         }
@@ -1871,8 +1955,8 @@ __device__ __forceinline__ bool process_tile(L &S, const CollideArgs &A, const i
                 if (t < nw) {
                     const int lc = S.wlist[k * L::WC + t];
                     const uint32_t b = S.cell_get(lc), e = S.cell_get(lc + 1);
-                    if (e - b <= 64u) resolve_wave(S, b, e - b, A.stiffness);
-                    else resolve_wave_blocked(S, b, e - b, A.stiffness);
+                    if (e - b <= 64u) resolve_wave(S, b, e - b, A.stiffness, U);
+                    else resolve_wave_blocked(S, b, e - b, A.stiffness, U);
                 } else {
                     const uint32_t ci = 4u * (t - nw) + (uint32_t)(lane >> 4);
                     uint32_t b = 0, e = 0;
@@ -1880,7 +1964,7 @@ __device__ __forceinline__ bool process_tile(L &S, const CollideArgs &A, const i
                         const int lc = S.rlist[k * L::WC + ci];
                         b = S.cell_get(lc); e = S.cell_get(lc + 1);
                     }
-                    resolve_row(S, b, e - b, lane & 15, A.stiffness);
+                    resolve_row(S, b, e - b, lane & 15, A.stiffness, U);
                 }
             }
         } else
@@ -1888,7 +1972,7 @@ __device__ __forceinline__ bool process_tile(L &S, const CollideArgs &A, const i
             if (GPE_RT_SKIP(4u)) break;
             const int lc = S.wlist[k * L::WC + i];
             const uint32_t b = S.cell_get(lc), e = S.cell_get(lc + 1);
-            if (e - b <= 64u) resolve_wave(S, b, e - b, A.stiffness);
+            if (e - b <= 64u) resolve_wave(S, b, e - b, A.stiffness, U);
         }
 #ifdef GPE_TILE_STAMPS
         GPE_STAMP(9 + k);
@@ -1931,7 +2015,7 @@ __device__ __forceinline__ bool process_tile(L &S, const CollideArgs &A, const i
     // ---- P6: write the tile's own particles back ------------------------------------------------------
     const bool packs = ORD && A.pack.on != 0u;                         // (scalar) a sharded step: the tiles pack
     if constexpr (kTrim && !kFetchEarly) fetch_own<ORD, kNatThreads, QSKIP>(S, A, tid, PS, n_owned, own_id, own_prev);
-    if constexpr (kTrim) write_own_back<ORD, kNatThreads, QSKIP>(S, A, tid, PS, n_owned, packs, own_id, own_prev);
+    if constexpr (kTrim) write_own_back<ORD, kNatThreads, QSKIP>(S, A, tid, PS, n_owned, packs, own_id, own_prev, U);
     else
     for (uint32_t s0 = 0; s0 < PS; s0 += kNatThreads) {                // (whole waves: the pack uses ballots)
         const uint32_t s = s0 + (uint32_t)tid;
@@ -2084,8 +2168,9 @@ constexpr PhantomTable make_phantom_table()
 __device__ const PhantomTable kPhantomTable = make_phantom_table();
 constexpr int kDirectSlots = 6;                // member slots a zone cell owns
 constexpr int kBigCap = 96;                    // memberships beyond that, per tile
-template <int TX_, int TY_, int CAP, bool LID, int NT_>
+template <int TX_, int TY_, int CAP, bool LID, int NT_, bool UNI = false>
 struct TileDirect {
+    static_assert(!(UNI && LID), "order-key windows keep the general path");
     static constexpr int TX = TX_, TY = TY_, NT = NT_, NW = NT_ / 64;   // tile (cells), threads, waves
     static constexpr bool kGlobal = false;
     static constexpr bool kLid = LID;
@@ -2105,7 +2190,15 @@ struct TileDirect {
     static constexpr int WC = TY >= 32 ? 16 : 32;
     static constexpr int kBig = TY >= 32 ? kBigCap : 2 * kBigCap;
     uint32_t lid[LID ? CAP : 1];
-    float px[CAP], py[CAP], rad[CAP];
+    float px[CAP], py[CAP];
+    // UNI: every particle has the kernel's one radius (CollideArgs::uniform_r, NativeState::uniform): no radius array --
+    // 4 B per slot less to gather, store and read back -- and the resolvers take the uniform pair_response (respond)
+    static constexpr bool kUniform = UNI;
+    float rad[UNI ? 1 : CAP];
+    __device__ __forceinline__ float radius_of(const uint32_t s, const UniformRadii &U) const
+    {
+        if constexpr (UNI) return U.r; else return rad[s];
+    }
     uint32_t id[CAP];
     uint8_t own[CAP];          // the particle's home cell lies in the tile
     __device__ __forceinline__ bool is_own(uint32_t s) const { return own[s] != 0; }
@@ -2151,6 +2244,9 @@ __device__ __forceinline__ bool process_tile_direct(L &S, const CollideArgs &A, 
     const int lane = tid & 63;
     const int ox = tx * TX - HX, oy = ty * TY - HY;                    // origin of the cell window
     const int box = (tx * TX - kHalo) >> 3, boy = (ty * TY - kHalo) >> 3;   // first looked-up block
+    // the one radius, its double, that squared and the prefilter's bound: formed here, once, as pair_response forms them
+    UniformRadii U = UniformRadii();
+    if constexpr (L::kUniform) U = uniform_radii(A.uniform_r);
     GPE_STAMP_BEGIN();
     // stragglers handed to this tile by the hash kernel (the lists are kept per 32x32 tile: a half reads its parent's)
     static_assert(TX == 32 && (TY == 32 || TY == 16), "straggler lists, ghost lists and rosters are kept per 32x32 tile");
@@ -2251,7 +2347,8 @@ __device__ __forceinline__ bool process_tile_direct(L &S, const CollideArgs &A, 
     };
     auto insert = [&](const uint32_t s, const float2 pp, const float pr, const uint32_t pid, const uint32_t lidv,
                       const int lx, const int ly, uint32_t over) {
-        S.px[s] = pp.x; S.py[s] = pp.y; S.rad[s] = pr; S.id[s] = pid;
+        S.px[s] = pp.x; S.py[s] = pp.y; S.id[s] = pid;
+        if constexpr (!L::kUniform) S.rad[s] = pr;
         if constexpr (L::kLid) S.lid[s] = lidv;
         S.own[s] = (lx >= HX && lx < HX + TX && ly >= HY && ly < HY + TY) ? 1 : 0;
         const int zx = lx - L::ZOX, zy = ly - L::ZOY;
@@ -2302,7 +2399,7 @@ __device__ __forceinline__ bool process_tile_direct(L &S, const CollideArgs &A, 
 #pragma unroll
         for (int q = 0; q < QP; ++q) {
             pp[q] = A.pos_in[pid[q]];
-            pr[q] = A.radius[pid[q]];
+            if constexpr (L::kUniform) pr[q] = 0.f; else pr[q] = A.radius[pid[q]];
             cc[q] = A.codes[pid[q]];
         }
         uint32_t lidq[QP];
@@ -2340,7 +2437,8 @@ __device__ __forceinline__ bool process_tile_direct(L &S, const CollideArgs &A, 
     // (`cell_of`: the entry's or the code word's), given a slot, filed.  (Called by whole waves: the slots use ballots.)
     auto take_listed = [&](const bool have, const uint32_t lidv, auto cell_of) {
         const float2 pp = A.pos_in[lidv];
-        const float pr = A.radius[lidv];
+        float pr = 0.f;
+        if constexpr (!L::kUniform) pr = A.radius[lidv];
         const uint32_t cc = A.codes[lidv];
         uint32_t pid = lidv;
         if constexpr (ORD) pid = A.order_keys[lidv];
@@ -2468,7 +2566,7 @@ __device__ __forceinline__ bool process_tile_direct(L &S, const CollideArgs &A, 
 #endif
             if (i < group_lanes) {
                 const uint32_t en = S.list[k * QZ + (QZ - 1) - (i / kGroupLanes)];
-                resolve_group<MS>(S, (en & 0xFFFu) * MS, (en >> 12) + kGroupMin, (int)(i % kGroupLanes), A.stiffness);
+                resolve_group<MS>(S, (en & 0xFFFu) * MS, (en >> 12) + kGroupMin, (int)(i % kGroupLanes), A.stiffness, U);
             } else if (i >= single_base && (i & ~63u) < work) {         // (whole waves: the walk uses ballots)
                 const bool on = i < work;
                 uint32_t b = 0, n = 0;
@@ -2476,7 +2574,7 @@ __device__ __forceinline__ bool process_tile_direct(L &S, const CollideArgs &A, 
                     const uint32_t en = S.list[k * QZ + (i - single_base)];
                     b = (en & 0xFFFu) * MS; n = 2u + (en >> 12);
                 }
-                resolve_small_cells(S, on, b, n, A.stiffness);
+                resolve_small_cells(S, on, b, n, A.stiffness, U);
             }
         }
         for (uint32_t i = (uint32_t)(NW - 1 - (tid >> 6)); i < nw; i += NW) {     // wave-uniform
@@ -2496,7 +2594,7 @@ __device__ __forceinline__ bool process_tile_direct(L &S, const CollideArgs &A, 
                 filled += (uint32_t)__popcll(mh);
             }
             wave_lds_order();
-            resolve_wave(S, wb, n, A.stiffness);                       // (filled == n: every membership is in one of the two)
+            resolve_wave(S, wb, n, A.stiffness, U);                    // (filled == n: every membership is in one of the two)
             wave_lds_order();
         }
         __syncthreads();
@@ -2504,7 +2602,7 @@ __device__ __forceinline__ bool process_tile_direct(L &S, const CollideArgs &A, 
     }
 
     // ---- P6: write the tile's own particles back, K12 applied ----------------------------------------------------------
-    write_own_back<ORD, NT, 1>(S, A, tid, PS, n_owned, ORD && A.pack.on != 0u, own_id, own_prev);
+    write_own_back<ORD, NT, 1>(S, A, tid, PS, n_owned, ORD && A.pack.on != 0u, own_id, own_prev, U);
     __syncthreads();
     GPE_STAMP(6);
     return true;
@@ -2581,16 +2679,23 @@ __device__ __forceinline__ void hint_tile(const CollideArgs &A, const int tx, co
 
 // HINTS: the launch carries front workgroups for the registered tiles (kCtlHints) -- a kernel of its own, launched only
 // while such tiles exist: the plain kernel is 3 % faster without the code (48.0 against 49.5 us at 1 M).
-template <int TX, int CAP, bool ORD, int NT, bool HINTS = false>
+// UNI: the windows without a radius array (TileDirect), the hinted halves included: launched while the context's radii are
+// one ordinary number (CollideArgs::uniform).
+template <int TX, int CAP, bool ORD, int NT, bool HINTS = false, bool UNI = false>
 __global__ __launch_bounds__(NT, 8) void k_collide_direct(CollideArgs A)
 {
     // (The half-tile form of the hinted tiles lives in the tile's own LDS: 40 928 bytes, four workgroups per CU, hold a
     // half of 1392 particles -- 59 % of a tile's window at 1.5 x its capacity; the half-tile launch's 2000 would make it
     // 51 KB and three per CU: 54.2 instead of 47.8 us at 1 M, profiles/r04/ab_hints_bisect.txt.)
     struct NoHalf { char unused; };
-    using Half = typename std::conditional<HINTS, TileDirect<32, 16, ORD ? GPE_CAP_HALF_FRONT_ORD : GPE_CAP_HALF_FRONT, ORD, 512>, NoHalf>::type;
-    __shared__ TileDirect<TX, 32, CAP, ORD, NT> S;
-    static_assert(sizeof(Half) <= sizeof(S) && alignof(Half) <= alignof(TileDirect<TX, 32, CAP, ORD, NT>), "the half form fits the tile's LDS");
+    using Half = typename std::conditional<HINTS, TileDirect<32, 16, ORD ? GPE_CAP_HALF_FRONT_ORD : GPE_CAP_HALF_FRONT, ORD, 512, UNI>, NoHalf>::type;
+    using Tile = TileDirect<TX, 32, CAP, ORD, NT, UNI>;
+    // (the uniform window has no radius array and is 3.7 KB smaller; the half form was sized for the general tile's LDS,
+    // which four workgroups per CU have room for either way)
+    __shared__ union { Tile tile; Half half; } u;
+    Tile &S = u.tile;
+    static_assert(UNI || (sizeof(Half) <= sizeof(Tile) && alignof(Half) <= alignof(Tile)), "the half form fits the tile's LDS");
+    static_assert(sizeof(u) <= 40960, "four workgroups per CU");
     uint32_t wg = blockIdx.x;
     if constexpr (HINTS) {
         if (wg < A.front_wgs) {
@@ -2604,7 +2709,7 @@ __global__ __launch_bounds__(NT, 8) void k_collide_direct(CollideArgs A)
             const uint32_t hinted_for = A.roster_hdr[A.tb.index(htx, hty)].w;   // (not registered for this launch: its own workgroup takes it)
             if (hinted_for != A.step_stamp && hinted_for != A.step_stamp + 1u) return;
             const int hy = hty * 2 + (int)(wg & 1u);
-            const bool done = process_tile_direct<ORD>(*reinterpret_cast<Half *>(&S), A, htx, hy);
+            const bool done = process_tile_direct<ORD>(u.half, A, htx, hy);
             if (threadIdx.x == 0) {
                 if (!done) hand_tile_on(A, kCtlOverflow2, A.overflow2, 2u * A.overflow1_cap, htx, hy);
                 // again in the next launch, kHintAge launches long
@@ -2619,7 +2724,7 @@ __global__ __launch_bounds__(NT, 8) void k_collide_direct(CollideArgs A)
 #ifdef GPE_TILE_CYCLES
     const long long tc0 = clock64();
 #endif
-    const bool done = process_tile_direct<ORD, TileDirect<TX, 32, CAP, ORD, NT>, HINTS>(S, A, tx, ty);
+    const bool done = process_tile_direct<ORD, Tile, HINTS>(S, A, tx, ty);
 #ifdef GPE_TILE_CYCLES
     if (g_tile_cycles && threadIdx.x == 0 && A.tb.holds(tx, ty)) {
         uint4 *e = &g_tile_cycles[A.tb.index(tx, ty)];
@@ -2682,10 +2787,10 @@ __global__ __launch_bounds__(kNatThreads, 2048 / kNatThreads * 2) void k_collide
 // (Why: one tile a little over 928 particles used to cost the step a whole over-capacity launch -- a counting-sort 16x16
 // window takes ~30 us whatever it holds, behind the dense launch: +40 % on the 1 M step once the undamped benchmark cloud
 // has clumped, from step ~1000 on.  A half costs what a dense-launch tile costs, ~10 us.)
-template <bool ORD>
+template <bool ORD, bool UNI = false>
 __global__ __launch_bounds__(512, 6) void k_collide_halves(CollideArgs A)
 {
-    __shared__ TileDirect<32, 16, ORD ? GPE_CAP_HALF_ORD : GPE_CAP_HALF, ORD, 512> S;
+    __shared__ TileDirect<32, 16, ORD ? GPE_CAP_HALF_ORD : GPE_CAP_HALF, ORD, 512, UNI> S;
     __shared__ uint32_t s_item;
     uint32_t count = A.tile_ctl[kCtlOverflow1];
     if (count > A.overflow1_cap) count = A.overflow1_cap;
@@ -2757,41 +2862,45 @@ __global__ __launch_bounds__(kNatThreads, GPE_OVF_WAVES) void k_collide_overflow
 // ---------------------------------------------------------------------------------------------------
 // launchers (native_launch.h): the host side of the native step (gpe_native.hip) starts the kernels through these
 // ---------------------------------------------------------------------------------------------------
-void launch_native_hash(gpe_ctx *c, bool ghosts, int grid, const float2 *pos, const float *radius, uint64_t n,
-                        const uint32_t *n_valid_ptr, float cell_size, int32_t gx, int32_t gy, int32_t bx0, int32_t by0,
+void launch_native_hash(gpe_ctx *c, bool ghosts, int grid, const float2 *pos, const float *radius, bool uniform,
+                        float uniform_r, uint64_t n, const uint32_t *n_valid_ptr, float cell_size, int32_t gx, int32_t gy, int32_t bx0, int32_t by0,
                         int32_t blocks_x, int32_t blocks_y, uint32_t pad_key, uint32_t *keys, uint32_t *codes, int digits,
                         uint32_t *hist4, uint32_t *hist_next, uint32_t *os_ctl, uint32_t *tile_ctl, uint4 *table2,
                         uint64_t table_pairs, uint32_t *host_stat, const uint32_t *sorted_key, uint32_t parity,
                         uint64_t div_magic, uint32_t *exc_count, uint2 *exc_entry, uint32_t *exc_count_next, TileBox tb,
                         uint32_t straggler_limit, uint32_t fuse_always, const HashGhosts &G, bool index64)
 {
+    unsigned long long *stamp = scope_stamp_for_next_launch(c);
     note_enqueue(c);
     // 32-bit indices while every index the kernel's loop forms -- up to kHashBatch strides past n -- stays below 2^31
     // (index64: GPE_FLAG_HASH_INDEX64 asks for the 64-bit form regardless; the two give the same bits)
     const bool narrow = !index64 && n + (uint64_t)grid * kHashBlock * kHashBatch < (1ull << 31);
+    // (uniform: the ordinary instantiation's only; a sharded run keeps the general kernels)
     const auto hash_kernel = ghosts ? (narrow ? k_native_hash<true, uint32_t> : k_native_hash<true, uint64_t>)
-                                    : (narrow ? k_native_hash<false, uint32_t> : k_native_hash<false, uint64_t>);
+                             : uniform ? (narrow ? k_native_hash<false, uint32_t, true> : k_native_hash<false, uint64_t, true>)
+                                       : (narrow ? k_native_hash<false, uint32_t> : k_native_hash<false, uint64_t>);
+    (void)div_magic;                                                   // (the kernel has not divided since the radix pass does)
     hipLaunchKernelGGL(hash_kernel, dim3(grid), dim3(kHashBlock), 0, c->stream, pos, radius, n, n_valid_ptr, cell_size, gx,
                        gy, bx0, by0, blocks_x, blocks_y, pad_key, keys, codes, digits, hist4, hist_next, os_ctl, tile_ctl,
-                       table2, table_pairs, host_stat, sorted_key, parity, div_magic, exc_count, exc_entry, exc_count_next,
-                       tb, straggler_limit, fuse_always, G);
+                       table2, table_pairs, host_stat, sorted_key, parity, uniform_r, exc_count, exc_entry, exc_count_next,
+                       tb, straggler_limit, fuse_always, G, stamp);
 }
 
-void launch_native_hist_gated(gpe_ctx *c, int grid, const uint32_t *keys, uint64_t n, int digits, uint32_t *hist4,
-                              const uint32_t *need)
+void launch_native_hist_gated(gpe_ctx *c, int grid, uint32_t *keys, uint64_t n, int digits, uint32_t *hist4,
+                              const uint32_t *need, const HistKeys &K)
 {
     unsigned long long *stamp = scope_stamp_for_next_launch(c);
     note_enqueue(c);
     hipLaunchKernelGGL(k_native_hist_gated, dim3(grid), dim3(kHistGatedBlock), 0, c->stream, keys, n, digits, hist4, need,
-                       stamp);
+                       stamp, K);
 }
 
 void launch_native_check_box(gpe_ctx *c, const float2 *pos, uint64_t n, const uint32_t *n_valid_ptr, float cell_size,
-                             int32_t gx, int32_t gy, uint32_t *flag)
+                             int32_t gx, int32_t gy, uint32_t *flag, const float *radius, uint32_t *radius_bits)
 {
     note_enqueue(c);
     hipLaunchKernelGGL(k_native_check_box, dim3(stream_grid(n)), dim3(kStreamBlock), 0, c->stream, pos, n, n_valid_ptr,
-                       cell_size, gx, gy, flag);
+                       cell_size, gx, gy, flag, radius, radius_bits);
 }
 
 void launch_native_window_max(gpe_ctx *c, const uint2 *table, uint32_t entries, int32_t blocks_x, int32_t blocks_y,
@@ -2829,17 +2938,26 @@ void launch_collide(gpe_ctx *c, CollideForm form, uint32_t grid, const CollideAr
     case CollideForm::DirectOrdFront:
         hipLaunchKernelGGL((k_collide_direct<32, GPE_CAP_DIRECT_ORD, true, 512, true>), dim3(grid), dim3(512), 0, c->stream, A);
         break;
+    // (A.uniform: the windows without a radius array; the forms that have no such variant gather radii as ever -- a step may
+    // mix the two, every pair's arithmetic is the same)
     case CollideForm::DirectFront:
-        hipLaunchKernelGGL((k_collide_direct<32, GPE_CAP_DIRECT, false, 512, true>), dim3(grid), dim3(512), 0, c->stream, A);
+        if (A.uniform)
+            hipLaunchKernelGGL((k_collide_direct<32, GPE_CAP_DIRECT, false, 512, true, true>), dim3(grid), dim3(512), 0, c->stream, A);
+        else
+            hipLaunchKernelGGL((k_collide_direct<32, GPE_CAP_DIRECT, false, 512, true>), dim3(grid), dim3(512), 0, c->stream, A);
         break;
     case CollideForm::Direct:
-        hipLaunchKernelGGL((k_collide_direct<32, GPE_CAP_DIRECT, false, 512>), dim3(grid), dim3(512), 0, c->stream, A);
+        if (A.uniform)
+            hipLaunchKernelGGL((k_collide_direct<32, GPE_CAP_DIRECT, false, 512, false, true>), dim3(grid), dim3(512), 0, c->stream, A);
+        else
+            hipLaunchKernelGGL((k_collide_direct<32, GPE_CAP_DIRECT, false, 512>), dim3(grid), dim3(512), 0, c->stream, A);
         break;
     case CollideForm::HalvesOrd:
         hipLaunchKernelGGL(k_collide_halves<true>, dim3(grid), dim3(512), 0, c->stream, A);
         break;
     case CollideForm::Halves:
-        hipLaunchKernelGGL(k_collide_halves<false>, dim3(grid), dim3(512), 0, c->stream, A);
+        if (A.uniform) hipLaunchKernelGGL((k_collide_halves<false, true>), dim3(grid), dim3(512), 0, c->stream, A);
+        else hipLaunchKernelGGL(k_collide_halves<false>, dim3(grid), dim3(512), 0, c->stream, A);
         break;
     case CollideForm::OverflowOrd:
         hipLaunchKernelGGL(k_collide_overflow<true>, dim3(grid), dim3(kNatThreads), 0, c->stream, A);

@@ -62,23 +62,44 @@ __device__ __forceinline__ uint64_t neg_zero_lanes(const f32x2 p)
 // p1 - c w with c from v = p2 - p1.  c' == -c exactly except when a component of v is 0: then the two zeros can have
 // the same sign, and p1 - c w != p1 + c' w where that component of p1 is -0 (both particles at -0).  `careful`: lanes
 // that may hold such a particle (neg_zero_lanes); their pairs take the IEEE path below in the oracle's orientation.
-template <bool BOTH = true>
-__device__ __forceinline__ uint64_t pair_response(const uint64_t active, f32x2 &p1, std::conditional_t<BOTH, f32x2 &, const f32x2 &> p2,
-                                                  const float r1, const float r2, const uint64_t plain,
-                                                  const float stiffness, const uint64_t lower = ~0ull,
-                                                  const uint64_t careful = 0)
+//
+// The UNIFORM form: every particle has the one radius r, an ordinary number (plain_radius_lanes' range -- the host checks
+// it once per configuration, NativeState::uniform).  Then the first shortcut above holds for every pair, and r1 + r2, its
+// square and the prefilter's bound are the same three numbers for every pair: UniformRadii holds them, formed once per
+// kernel by the very operations the general form performs per pair.  No r1 / r2, no `plain`, no general branch, weights
+// of 0.5; every other line is shared with the general form, which every order-key kernel keeps.
+struct UniformRadii { float r, sum, sum2, bound; };
+__device__ __forceinline__ UniformRadii uniform_radii(const float r)
+{
+    UniformRadii U;
+    U.r = r;
+    U.sum = r + r;                                                    // :61
+    U.sum2 = U.sum * U.sum;
+    U.bound = U.sum2 * 1.000001f;
+    return U;
+}
+template <bool BOTH, bool UNIFORM>
+__device__ __forceinline__ uint64_t pair_response_core(const uint64_t active, f32x2 &p1, std::conditional_t<BOTH, f32x2 &, const f32x2 &> p2,
+                                                       const float r1, const float r2, const uint64_t plain, const UniformRadii &U,
+                                                       const float stiffness, const uint64_t lower, const uint64_t careful)
 {
     (void)lower;
     (void)careful;
+    (void)r1; (void)r2; (void)plain; (void)U;
 #ifdef GPE_COUNT_PAIRS
     count_pairs(g_pairs_walked, active & lower);
 #endif
     const f32x2 v = p1 - p2;                                          // :91 (live positions, :86)
     const f32x2 vv = v * v;
     const float q = vv.x + vv.y;
-    const float radius_sum = r1 + r2;                                 // :61
-    const float rs2 = radius_sum * radius_sum;
-    const uint64_t cand = active & ballot64(q <= rs2 * 1.000001f) & ballot64(q >= 9.9e-9f);
+    float radius_sum, rs2, bound;
+    if constexpr (UNIFORM) { radius_sum = U.sum; rs2 = U.sum2; bound = U.bound; }
+    else {
+        radius_sum = r1 + r2;                                         // :61
+        rs2 = radius_sum * radius_sum;
+        bound = rs2 * 1.000001f;
+    }
+    const uint64_t cand = active & ballot64(q <= bound) & ballot64(q >= 9.9e-9f);
     if (cand == 0) return 0;                                          // wave-uniform
     // The correctly rounded square root and quotients WITHOUT the steps hipcc's sequences spend on scaling and
     // specials.  A candidate has q in [9.9e-9, 1.000001 rs^2], so the square root's operand is a normal number and a
@@ -138,12 +159,14 @@ __device__ __forceinline__ uint64_t pair_response(const uint64_t active, f32x2 &
     }
     const f32x2 c = (u * splat2(depth)) * splat2(stiffness);          // :98,101
     float w1 = 0.5f, w2 = 0.5f;                                       // == inv1 / (inv1 + inv1), exactly
-    const uint64_t general = hit & ~(ballot64(r1 == r2) & plain);     // unequal (or odd) radii somewhere
-    if (general != 0) {                                               // wave-uniform
-        if (lanes_of(general)) {
-            const float inv1 = 1.0f / r1, inv2 = 1.0f / r2;           // :103,104
-            w1 = inv1 / (inv1 + inv2);                                // :107
-            w2 = inv2 / (inv1 + inv2);                                // :108
+    if constexpr (!UNIFORM) {
+        const uint64_t general = hit & ~(ballot64(r1 == r2) & plain); // unequal (or odd) radii somewhere
+        if (general != 0) {                                           // wave-uniform
+            if (lanes_of(general)) {
+                const float inv1 = 1.0f / r1, inv2 = 1.0f / r2;       // :103,104
+                w1 = inv1 / (inv1 + inv2);                            // :107
+                w2 = inv2 / (inv1 + inv2);                            // :108
+            }
         }
     }
     const bool mine = lanes_of(hit);
@@ -153,6 +176,21 @@ __device__ __forceinline__ uint64_t pair_response(const uint64_t active, f32x2 &
     count_pairs(g_pairs_hit, hit & lower);
 #endif
     return hit;
+}
+template <bool BOTH = true>
+__device__ __forceinline__ uint64_t pair_response(const uint64_t active, f32x2 &p1, std::conditional_t<BOTH, f32x2 &, const f32x2 &> p2,
+                                                  const float r1, const float r2, const uint64_t plain,
+                                                  const float stiffness, const uint64_t lower = ~0ull,
+                                                  const uint64_t careful = 0)
+{
+    return pair_response_core<BOTH, false>(active, p1, p2, r1, r2, plain, UniformRadii(), stiffness, lower, careful);
+}
+template <bool BOTH = true>
+__device__ __forceinline__ uint64_t pair_response(const uint64_t active, f32x2 &p1, std::conditional_t<BOTH, f32x2 &, const f32x2 &> p2,
+                                                  const UniformRadii &U, const float stiffness, const uint64_t lower = ~0ull,
+                                                  const uint64_t careful = 0)
+{
+    return pair_response_core<BOTH, true>(active, p1, p2, 0.f, 0.f, 0ull, U, stiffness, lower, careful);
 }
 
 }  // namespace gpe

@@ -47,6 +47,7 @@ constexpr int kCtlSorts = kNativeCtlSorts;     // steps whose radix passes ran (
 constexpr int kCtlStragglers0 = 9, kCtlStragglers1 = 15;   // [parity] stragglers found by the step's hash so far
 constexpr int kCtlSortedCount = 32;            // particles the kept grouping covers (written by the first radix pass)
 constexpr int kCtlSortsSeen = kNativeCtlSortsSeen;   // copy of kCtlSorts in the line the tiles only read (written by the last radix pass)
+constexpr int kCtlRadiusBits = 42;             // [2] configuration time only: ~(smallest), largest bit pattern of the radii (k_native_check_box)
 constexpr int kCtlGhostSort = 40;              // [parity] sharded: a tile's ghost list ran over -- the ghosts' radix passes run and the tiles look the ghosts up in their block table
 constexpr int kCtlWords = 64;                  // tile_ctl is this long (two 128-byte lines)
 // A particle beyond that reach (a straggler: in a cloud without damping a few particles are always fast) does not
@@ -77,6 +78,14 @@ struct HashGhosts {
     uint32_t *gl_count = nullptr, *gl_entry = nullptr, *gl_count_next = nullptr;
     uint32_t *ghost_sort = nullptr, *ghost_sort_next = nullptr;   // tile_ctl[kCtlGhostSort + parity], ... of the next step
 };
+// What the gated histogram launch needs to form the keys itself (block_key_of) on a step whose hash stored none; pos ==
+// NULL: the hash stored them.  One kernel argument: the launch sits between the hash and the radix passes of every step,
+// and on a small scene the host's time to marshal it is on the step's critical path.
+struct HistKeys {
+    const float2 *pos = nullptr;
+    float cell_size = 0.0f;
+    int32_t gx = 0, gy = 0, bx0 = 0, by0 = 0, blocks_x = 0, blocks_y = 0;
+};
 constexpr int kHashBlock = 1024;
 constexpr int kHashGridMax = 2048;
 constexpr int kHistGatedBlock = 1024, kHistGatedGridMax = 2048;
@@ -86,6 +95,10 @@ constexpr int kHistGatedBlock = 1024, kHistGatedGridMax = 2048;
 struct CollideArgs {
     const float2 *pos_in;
     const float *radius;
+    // every particle has the radius uniform_r (NativeState::uniform): the direct-slot launches and the half-tile launch run
+    // their windows without a radius array; the other forms read `radius` as ever
+    uint32_t uniform;
+    float uniform_r;
     float2 *pos_out;
     const uint32_t *sorted_ids;
     const uint32_t *codes;       // per particle: cell mod 128 (7 + 7 bits) | neighbour overlap mask (8 bits) | kCodeStraggler
@@ -157,18 +170,21 @@ constexpr int kRosterCap = GPE_QMAX_MAIN_VALUE * 512;   // == TileDirect<32, ..,
 
 // The launchers (k_native.hip): each enqueues one kernel on c->stream and does nothing else -- the caller checks
 // hipGetLastError where it always did.  The block size belongs to the kernel, so the launcher supplies it.
-void launch_native_hash(gpe_ctx *c, bool ghosts, int grid, const float2 *pos, const float *radius, uint64_t n,
-                        const uint32_t *n_valid_ptr, float cell_size, int32_t gx, int32_t gy, int32_t bx0, int32_t by0,
+// (uniform: the instantiation that takes uniform_r for every particle's radius -- NativeState::uniform; keys == NULL: a
+// kept-table step whose keys nobody reads unless it sorts, launch_native_hist_gated forms them then)
+void launch_native_hash(gpe_ctx *c, bool ghosts, int grid, const float2 *pos, const float *radius, bool uniform,
+                        float uniform_r, uint64_t n, const uint32_t *n_valid_ptr, float cell_size, int32_t gx, int32_t gy, int32_t bx0, int32_t by0,
                         int32_t blocks_x, int32_t blocks_y, uint32_t pad_key, uint32_t *keys, uint32_t *codes, int digits,
                         uint32_t *hist4, uint32_t *hist_next, uint32_t *os_ctl, uint32_t *tile_ctl, uint4 *table2,
                         uint64_t table_pairs, uint32_t *host_stat, const uint32_t *sorted_key, uint32_t parity,
                         uint64_t div_magic, uint32_t *exc_count, uint2 *exc_entry, uint32_t *exc_count_next, TileBox tb,
                         uint32_t straggler_limit, uint32_t fuse_always, const HashGhosts &G, bool index64);
-void launch_native_hist_gated(gpe_ctx *c, int grid, const uint32_t *keys, uint64_t n, int digits, uint32_t *hist4,
-                              const uint32_t *need);
+// (K.pos != NULL: the hash stored no keys; the launch forms them from the positions, stores and counts them)
+void launch_native_hist_gated(gpe_ctx *c, int grid, uint32_t *keys, uint64_t n, int digits, uint32_t *hist4,
+                              const uint32_t *need, const HistKeys &K);
 // (these two cover their n / entries with a grid-stride loop: stream_grid)
 void launch_native_check_box(gpe_ctx *c, const float2 *pos, uint64_t n, const uint32_t *n_valid_ptr, float cell_size,
-                             int32_t gx, int32_t gy, uint32_t *flag);
+                             int32_t gx, int32_t gy, uint32_t *flag, const float *radius, uint32_t *radius_bits);
 void launch_native_window_max(gpe_ctx *c, const uint2 *table, uint32_t entries, int32_t blocks_x, int32_t blocks_y,
                               uint32_t *out_max);
 void launch_native_publish_probe(gpe_ctx *c, uint32_t *tile_ctl, uint32_t *host_stat);

@@ -9,11 +9,11 @@
 // boundary nothing measurable.  So a record is written at once by the one-thread kernel, unless its scope says
 // that the stamp is OWED to the enqueue that follows (Scope::kCarryStart / kCarryStop, handed to record() through the
 // StampRecorder of that open or close; inside a tracked region of scope_events.h only: there every enqueue is
-// announced).  The launchers of the two gated sort kernels, which return at once on most steps, take an owed stamp --
-// take() -- and the kernel's first workgroup writes it; any other enqueue, and the region's end, pays it with the
-// one-thread kernel first -- flush(), from note_enqueue().  The native step owes the boundaries behind the hash and
-// around the radix passes and stamps at once the one in front of the hash, whose launch follows at once anyway, and
-// those behind the two collide launches: owing a record stamps the scope that ends there only when the host has
+// announced).  The launchers of the hash and of the two gated sort kernels, which return at once on most steps, take an
+// owed stamp -- take() -- and the kernel's first workgroup writes it; any other enqueue, and the region's end, pays it
+// with the one-thread kernel first -- flush(), from note_enqueue().  The native step owes the boundaries around the hash
+// (the one in front of it too: stamped at once, it counted the host's time to launch the hash as the hash's whenever the
+// GPU was waiting for the host) and around the radix passes, and stamps at once those behind the two collide launches: owing a record stamps the scope that ends there only when the host has
 // prepared the next launch, and on a small scene, where the GPU waits for the host, that time would count as the long
 // kernel's.
 //

@@ -190,10 +190,10 @@ class Context:
 
     def pipeline_info(self):
         """gpe_get_pipeline_info: which kernels the next step runs (L.PIPELINE_*), why (L.REASON_*), and the counts."""
-        info = L.GpePipelineInfo()
-        info.struct_size = C.sizeof(L.GpePipelineInfo)
+        info = L.GpePipelineInfoUniform()
+        info.struct_size = C.sizeof(L.GpePipelineInfoUniform)
         self.call("gpe_get_pipeline_info", C.byref(info))
-        return {k: getattr(info, k) for k, _ in L.GpePipelineInfo._fields_ if k not in ("struct_size", "reserved")}
+        return {k: getattr(info, k) for k, _ in L.GpePipelineInfoUniform._fields_ if k not in ("struct_size", "reserved")}
 
     def guard_check(self):
         """gpe_guard_check: the damaged red zones of the context's device allocations, as dicts (tag, side "front" /

@@ -96,9 +96,11 @@ enum {
                                      /* filled with a canary, its fresh payload is poisoned (gpe_guard_check)        */
     GPE_FLAG_HASH_INDEX64 = 2048u,   /* NATIVE, diagnostic: the hash kernel indexes with 64 bits at every particle    */
                                      /* count (by default only where an index could pass 2^31); for tests, A/B timing */
-    GPE_FLAG_EVENT_SCOPES = 4096u    /* profiling scopes record hipEvents (as they did up to now) instead of writing  */
+    GPE_FLAG_EVENT_SCOPES = 4096u,   /* profiling scopes record hipEvents (as they did up to now) instead of writing  */
                                      /* the GPU's timestamp counter into a device buffer; for A/B timing.  A context  */
                                      /* on a stream lent by gpe_set_stream records events either way                  */
+    GPE_FLAG_GENERAL_RADII = 8192u   /* NATIVE: keep the kernels that read every particle's radius even when all radii */
+                                     /* are one ordinary number (gpe_pipeline_info.uniform_radius); for tests, A/B timing */
 };
 
 /* Fills *cfg with the reference's compile-time constants. */
@@ -1058,6 +1060,10 @@ typedef struct gpe_pipeline_info {
     uint32_t overflow_subtiles;  /* 16x16 quarters of those redone as four 8x8 tiles                                */
     uint32_t overflow_spills;    /* 8x8 tiles staged in the global spill arena                                      */
     uint32_t arena_slots;        /* spill-arena slots handed out                                                    */
+    /* (a host that fills in a struct_size up to arena_slots gets the fields above only)                            */
+    uint32_t uniform_radius;     /* NATIVE: 1 while the step runs the kernels that take ONE radius as a constant -- */
+                                 /* every radius was the same number in [1e-30, 1e30] when the context was last    */
+                                 /* configured, on one device, and gpe_device_ptr(GPE_RADIUS) not handed out since */
 } gpe_pipeline_info;
 gpe_status gpe_get_pipeline_info(gpe_ctx *ctx, gpe_pipeline_info *info);
 
