@@ -772,6 +772,9 @@ gpe_status native_collide(gpe_ctx *c, const float2 *pos_in, float2 *pos_out, con
         // workgroups (8 waves and 36 KB of LDS each) costs ~6 us, 8 % of the 1 M step.  While the tiles have reported no
         // over-capacity tile for a while (the statistic lags by the steps in flight) the grid is 128 workgroups; the
         // first reported tile brings the full grid back.  A surprise only makes that one step's launch slower.
+        // A context whose windows were thin when it was configured (at most kWindowQuietStart: NativePolicy::admit) starts
+        // that way -- small grid, no half-tile launch -- instead of paying both for its first 96 and 32 steps, and after
+        // every gpe_add_particles / gpe_set_particles again; one that was dense then starts with both.
         Scope s(c, "native/collide-dense-regions", Scope::kSharedBoundaries);
         // (quiet_steps: since the dense launch last handed a tile on ITSELF -- hinted tiles do not count, they never reach
         // list 1; dense_quiet: since anything reached list 1 or list 2)

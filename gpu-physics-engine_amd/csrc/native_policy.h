@@ -25,6 +25,10 @@ constexpr uint64_t kArenaMaxSlots = 1ull << 30; // the arena's slot numbers are 
 #endif
 constexpr uint32_t kWindowHandover = GPE_WINDOW_HANDOVER;              // above it the context leaves the native path
 constexpr uint32_t kWindowEligible = GPE_WINDOW_HANDOVER * 3 / 2;      // a scene whose windows exceed this never enters it
+// A scene whose largest 24x24-cell window holds at most this many particles when it is configured starts without the
+// precautionary launches (admit).  The population above which the tiles report a window (kWindowReport, k_native.hip):
+// 2.3 x the mean of the benchmark density; a direct-slot tile runs over around 350 per window.
+constexpr uint32_t kWindowQuietStart = 512;
 
 // One reading of the pinned words (native_read_stats).
 struct NativeStats {
@@ -81,8 +85,9 @@ struct NativePolicy {
     uint32_t calm_steps = 0;         // steps without an over-capacity tile or a crowded window while `crowded`
     uint32_t hint_quiet = 0xFFFFFFFFu; // native steps since a tile last ran over, hinted ones included (lagged): the dense launch's front workgroups
     uint32_t quiet_steps = 0;        // native steps since the dense launch last handed a tile on itself (lagged)
+    bool handed_on_seen = false;     // ... and it has done so since the last configuration (or the scene was dense then)
     uint32_t new_streak = 0;         // consecutive native steps whose (lagged) list 1 was not empty
-    uint32_t dense_quiet = 0;        // native steps since list 1 or list 2 last had an entry (lagged): the over-capacity launch's grid
+    uint32_t dense_quiet = 0xFFFFFFFFu; // native steps since list 1 or list 2 last had an entry (lagged): the over-capacity launch's grid
 
     // native_configure, before anything is measured.  sorts: the passes' counter as last published (the histogram
     // window counts from it).  (hint_quiet, new_streak, dense_quiet and calm_steps carry over.)
@@ -92,14 +97,20 @@ struct NativePolicy {
         dense_hold = false;
         steps_since_check = 0;
         quiet_steps = 0;
+        handed_on_seen = false;
         crowded = false;
         hist_fused = false; hist_watch_steps = 0; hist_watch_sorts = sorts;
         sort_hold = 0; watch_steps = 0; watch_valid = false;
     }
 
-    // native_configure, once the box check passed and the windows are measured (force: GPE_FLAG_NATIVE_FORCE)
+    // native_configure, once the box check passed and the windows are measured (force: GPE_FLAG_NATIVE_FORCE).
+    // The statistics lag: the host may be ~64 steps ahead of the first report.  A scene whose windows are thin now
+    // (at most kWindowQuietStart) runs those steps without the precautionary launches -- no half-tile launch before a tile
+    // has been handed on, the small over-capacity grid while the lists have never had an entry; a scene that is dense
+    // from the start takes both from its first step.
     bool admit(uint32_t window_max, bool force)
     {
+        if (window_max > kWindowQuietStart) { handed_on_seen = true; dense_quiet = 0; }
         eligible = window_max <= kWindowEligible || force;
         return eligible;
     }
@@ -201,18 +212,19 @@ struct NativePolicy {
     // native_collide, after the dense launch.  front_wgs: what hints() chose (0 when it was not asked); direct_form:
     // the dense launch ran direct-slot tiles.  The half-tile launch runs behind direct-slot tiles only: with front
     // workgroups after 4 steps in a row that handed tiles on, without them while tiles were handed on in the last 32
-    // steps.  The over-capacity launch takes 128 workgroups up to 4 M particles while the lists have been empty for
-    // 96 steps or, with front workgroups, held at most 128 work items; else 1024.
+    // steps (and, since the last configuration, only once a tile has been handed on or when the scene was dense then:
+    // admit).  The over-capacity launch takes 128 workgroups up to 4 M particles while the lists have been empty for
+    // 96 steps -- or have never had an entry -- or, with front workgroups, held at most 128 work items; else 1024.
     OverflowPlan overflow(const NativeStats &s, uint32_t front_wgs, bool direct_form, bool no_half_tiles, uint64_t n)
     {
         const uint32_t handed_on = front_wgs ? s.overflow_new : s.overflow;
-        if (handed_on != 0) quiet_steps = 0;
+        if (handed_on != 0) { quiet_steps = 0; handed_on_seen = true; }
         else if (quiet_steps < 0xFFFFFFFFu) ++quiet_steps;
         if (s.overflow_new != 0 || s.halves_over != 0 || (!front_wgs && s.overflow != 0)) dense_quiet = 0;
         else if (dense_quiet < 0xFFFFFFFFu) ++dense_quiet;
         if (s.overflow_new != 0) { if (new_streak < 0xFFFFFFFFu) ++new_streak; } else new_streak = 0;
         OverflowPlan p;
-        const bool halves_wanted = front_wgs ? new_streak >= 4u : quiet_steps < 32u;
+        const bool halves_wanted = front_wgs ? new_streak >= 4u : (handed_on_seen && quiet_steps < 32u);
         if (direct_form && halves_wanted && !no_half_tiles)
             p.halves_grid = (uint32_t)std::min<uint64_t>(1024, std::max<uint64_t>(64, 2ull * handed_on + 32));
         const uint64_t items = 4ull * s.overflow_new + 2ull * s.halves_over;
