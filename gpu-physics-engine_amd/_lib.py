@@ -58,6 +58,8 @@ FIELDS_MAX = 4096
 FIELD_EVERYWHERE, FIELD_CIRCLE, FIELD_BOX = 0, 1, 2
 FIELD_UNIFORM, FIELD_RADIAL, FIELD_VORTEX, FIELD_DRAG = 0, 1, 2, 3
 FALLOFF_NONE, FALLOFF_LINEAR = 0, 1
+MOVERS_MAX = 1024
+MOVER_LINEAR, MOVER_ROTATE = 0, 1
 EDIT_BY_INDEX, EDIT_BY_UID = 0, 1
 CLUSTER_BY_INDEX, CLUSTER_BY_UID = 0, 1
 VEL_ADD, VEL_SET, VEL_SCALE = 0, 1, 2
@@ -279,6 +281,27 @@ class GpeFieldsInfo(C.Structure):
                 ("grid_x", C.c_uint32), ("grid_y", C.c_uint32), ("list_entries", C.c_uint64)]
 
 
+class GpeMover(C.Structure):
+    """gpe_mover: a capsule at rest (ax, ay, bx, by, radius) and its motion: kind LINEAR (vx, vy; travel) or ROTATE (the
+    pivot px, py; omega); flags and reserved 0.  56 bytes."""
+    _fields_ = [("ax", C.c_float), ("ay", C.c_float), ("bx", C.c_float), ("by", C.c_float), ("radius", C.c_float),
+                ("kind", C.c_uint32), ("vx", C.c_float), ("vy", C.c_float), ("travel", C.c_float),
+                ("px", C.c_float), ("py", C.c_float), ("omega", C.c_float), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class GpeMoverPose(C.Structure):
+    """gpe_mover_pose: the posed capsule and the motion state (LINEAR: g, sgn; ROTATE: c, s).  24 bytes."""
+    _fields_ = [("ax", C.c_float), ("ay", C.c_float), ("bx", C.c_float), ("by", C.c_float), ("q0", C.c_float), ("q1", C.c_float)]
+
+
+class GpeMoversInfo(C.Structure):
+    """gpe_movers_info: in struct_size; out the movers set, the passes run and particles moved since the last
+    gpe_set_movers, the lookup grid of the last build, its mask words per cell and the (cell, mover) bits it set."""
+    _fields_ = [("struct_size", C.c_uint32), ("k", C.c_uint32), ("passes", C.c_uint64), ("pushed", C.c_uint64),
+                ("grid_x", C.c_uint32), ("grid_y", C.c_uint32), ("mask_words", C.c_uint32), ("reserved", C.c_uint32),
+                ("listed", C.c_uint64)]
+
+
 class GpeParticleEdit(C.Structure):
     """gpe_particle_edit: in struct_size / key_kind / k / keys and the field arrays (each may be NULL), out edited."""
     _fields_ = [("struct_size", C.c_uint32), ("key_kind", C.c_uint32), ("k", C.c_uint64),
@@ -359,6 +382,12 @@ SYMBOLS = [
     ("gpe_get_fields", _I32, [_VP, C.POINTER(GpeField), _U64, C.POINTER(_U64)]),
     ("gpe_apply_fields", _I32, [_VP, _F]),
     ("gpe_get_fields_info", _I32, [_VP, C.POINTER(GpeFieldsInfo)]),
+    ("gpe_set_movers", _I32, [_VP, C.POINTER(GpeMover), _U64]),
+    ("gpe_get_movers", _I32, [_VP, C.POINTER(GpeMover), _U64, C.POINTER(_U64)]),
+    ("gpe_get_mover_poses", _I32, [_VP, C.POINTER(GpeMoverPose), _U64, C.POINTER(_U64)]),
+    ("gpe_set_mover_poses", _I32, [_VP, C.POINTER(GpeMoverPose), _U64]),
+    ("gpe_apply_movers", _I32, [_VP, _F]),
+    ("gpe_get_movers_info", _I32, [_VP, C.POINTER(GpeMoversInfo)]),
     ("gpe_query_circle", _I32, [_VP, _F, _F, _F, C.POINTER(GpeQueryResult)]),
     ("gpe_query_box", _I32, [_VP, _F, _F, _F, _F, C.POINTER(GpeQueryResult)]),
     ("gpe_pick", _I32, [_VP, _F, _F, C.POINTER(GpeQueryResult)]),

@@ -1,6 +1,6 @@
 // gpe_api.hip -- the extern "C" boundary of include/gpe.h: context, device memory, particle buffers, set / add / remove,
 // uids, step ordering, downloads, profiling.  The queries are in gpe_queries.hip, the checked add, edits and kicks in
-// gpe_edits.hip, the tracers and the monitor in gpe_observe.hip, the static colliders in gpe_colliders.hip, the distance bonds in gpe_bonds.hip, the rigid and soft bodies in gpe_bodies.hip, the force fields in gpe_fields.hip.  All device work goes to one in-order hipStream per context.
+// gpe_edits.hip, the tracers and the monitor in gpe_observe.hip, the static colliders in gpe_colliders.hip, the distance bonds in gpe_bonds.hip, the rigid and soft bodies in gpe_bodies.hip, the force fields in gpe_fields.hip, the moving colliders in gpe_movers.hip.  All device work goes to one in-order hipStream per context.
 #include <math.h>
 #include <stddef.h>
 #include <stdlib.h>
@@ -1002,6 +1002,7 @@ gpe_status gpe_destroy(gpe_ctx *c)
     bonds_release(c);
     bodies_release(c);
     fields_release(c);
+    movers_release(c);
     sort_release(c);
     scan_release(c);
     onesweep_release(c);
@@ -1469,10 +1470,12 @@ gpe_status gpe_solve_collisions(gpe_ctx *c)
 gpe_status gpe_step(gpe_ctx *c, float dt, uint32_t flags)
 {
     GPE_TRY(need_particles(c));
+    GPE_TRY(movers_check_dt(c, dt, "gpe_step"));
     GPE_HIP(c, hipSetDevice(c->device));
     GPE_TRY(do_step(c, dt, flags));
     GPE_TRY(bonds_after_step(c));
     GPE_TRY(bodies_after_step(c));
+    GPE_TRY(movers_after_step(c, dt));
     GPE_TRY(colliders_after_step(c));
     GPE_TRY(fields_after_step(c, dt));
     return observers_after_step(c);
@@ -1481,6 +1484,7 @@ gpe_status gpe_step(gpe_ctx *c, float dt, uint32_t flags)
 gpe_status gpe_run(gpe_ctx *c, float dt, uint64_t steps, uint64_t resort_every, int32_t resort_first)
 {
     GPE_TRY(need_particles(c));
+    GPE_TRY(movers_check_dt(c, dt, "gpe_run"));
     GPE_HIP(c, hipSetDevice(c->device));
     // The host may run at most ~64 steps ahead of the device: bounds the queue and the lag of the
     // device-side statistics the step policy reads (native_should_run).
@@ -1499,6 +1503,7 @@ gpe_status gpe_run(gpe_ctx *c, float dt, uint64_t steps, uint64_t resort_every, 
         rc = do_step(c, dt, resort ? GPE_STEP_RESORT : 0u);
         if (rc == GPE_OK) rc = bonds_after_step(c);
         if (rc == GPE_OK) rc = bodies_after_step(c);
+        if (rc == GPE_OK) rc = movers_after_step(c, dt);
         if (rc == GPE_OK) rc = colliders_after_step(c);
         if (rc == GPE_OK) rc = fields_after_step(c, dt);
         if (rc == GPE_OK) rc = observers_after_step(c);
@@ -1730,6 +1735,7 @@ gpe_status gpe_set_counts(gpe_ctx *c, uint64_t n_total, uint64_t n_owned)
     if (c->uid.on) return fail(c, GPE_ERR_UNSUPPORTED, "gpe_set_counts: not supported while uids are on");
     if (has_colliders(c)) return refuse_colliders(c, "gpe_set_counts");
     if (has_fields(c)) return refuse_fields(c, "gpe_set_counts");
+    if (has_movers(c)) return refuse_movers(c, "gpe_set_counts");
     c->n = n_total;
     c->n_owned = n_owned;
     c->native.uniform = false;                 // (slots the configuration has not looked at: NativeState::uniform)
@@ -1745,6 +1751,7 @@ gpe_status gpe_use_order_keys(gpe_ctx *c, int32_t enable)
         return fail(c, GPE_ERR_UNSUPPORTED, "gpe_use_order_keys: sharded runs carry order keys, not uids (uids are on)");
     if (enable && has_colliders(c)) return refuse_colliders(c, "gpe_use_order_keys");
     if (enable && has_fields(c)) return refuse_fields(c, "gpe_use_order_keys");
+    if (enable && has_movers(c)) return refuse_movers(c, "gpe_use_order_keys");
     c->use_order_keys = enable != 0;
     if (enable) c->native.uniform = false;     // (order-key tiles keep the general path: NativeState::uniform)
     return GPE_OK;

@@ -11,6 +11,7 @@
 
 #include "../../include/gpe.h"
 #include "k_collider.h"
+#include "k_mover.h"
 #include "native_policy.h"
 #include "scope_events.h"
 #include "scope_stamps.h"
@@ -485,6 +486,47 @@ struct FieldState {
     uint64_t entries = 0;
 };
 
+// the moving colliders (gpe_set_movers; gpe_movers.hip, k_movers.hip, k_mover.h, mover_grid.h).  Step state: gpe_step /
+// gpe_run advance them on the device, rebuild their lookup grid there and apply them, behind the bodies and before the
+// static colliders
+struct MoverState {
+    std::vector<gpe_mover> set;                  // the movers as the host gave them (empty: none, nothing is launched)
+    MoverDef *def = nullptr;                     // one per mover: the rest capsule and the motion (k_mover.h)
+    float *pose = nullptr;                       // 6 per mover: gpe_mover_pose, the posed capsule and the motion state
+    float4 *rec = nullptr;                       // 2 per mover: the posed (ax, ay, bx, by), (R, 0, 0, 0): the pass's records
+    unsigned long long *pushed = nullptr;        // one word: particles moved since the last gpe_set_movers
+    // the lookup grid, allocated once for the largest grid (kMoverGridMaxDim^2 cells): the masks (cells * words 64-bit
+    // words), the summary (cells 32-bit words) and one 64-bit word `listed`, laid out for the view of the last build
+    unsigned char *grid = nullptr;
+    uint32_t words = 0;                          // mask words per cell: ceil(k / 64)
+    uint64_t passes = 0;                         // passes enqueued since the last gpe_set_movers
+    MoverGridView view;                          // the view of the last build
+    bool built = false;                          // false: no pass has built a grid yet
+    MoverLimits limits;                          // the dt contract's side of the set (k_mover.h)
+};
+
+struct MoverBuildArgs {
+    const MoverDef *def = nullptr;
+    float *pose = nullptr;
+    float4 *rec = nullptr;
+    uint32_t k = 0, words = 0;
+    MoverGridView g;
+    float rb = 0.f, dt = 0.f;
+    unsigned long long *masks = nullptr;
+    uint32_t *summary = nullptr;
+    unsigned long long *listed = nullptr;
+};
+
+struct MoverPassArgs {
+    const unsigned long long *masks = nullptr;   // view.gx * view.gy * words
+    const uint32_t *summary = nullptr;           // view.gx * view.gy
+    const float4 *rec = nullptr;                 // 2 per mover
+    uint32_t k = 0, words = 0;
+    ColliderGridView view;
+    float world_w = 0.f, world_h = 0.f;
+    unsigned long long *pushed = nullptr;
+};
+
 struct SortWorkspace {
     uint32_t *keys_b = nullptr, *vals_b = nullptr;   // ping-pong partners, cap entries each
     uint64_t cap = 0;
@@ -835,6 +877,7 @@ struct gpe_ctx {
     gpe::BondState bonds;
     gpe::BodyState bodies;
     gpe::FieldState fields;
+    gpe::MoverState movers;
     gpe::QueryWorkspace query_ws;
     gpe::ContactsWorkspace contacts_ws;
     gpe::ClustersWorkspace clusters_ws;
@@ -1002,6 +1045,13 @@ gpe_status refuse_fields(gpe_ctx *c, const char *who);      // GPE_ERR_UNSUPPORT
 gpe_status fields_after_step(gpe_ctx *c, float dt);         // after every step of gpe_step / gpe_run, behind the colliders, before the observers
 void fields_world_changed(gpe_ctx *c);                      // gpe_set_world: the lookup grid follows before the next pass
 void fields_release(gpe_ctx *c);
+
+// gpe_movers.hip: the moving colliders of a context that holds some
+inline bool has_movers(const gpe_ctx *c) { return !c->movers.set.empty(); }
+gpe_status refuse_movers(gpe_ctx *c, const char *who);      // GPE_ERR_UNSUPPORTED: sharding a context that holds movers
+gpe_status movers_check_dt(gpe_ctx *c, float dt, const char *who);  // GPE_ERR_INVALID_ARG: dt breaks the set's contract; before anything is launched
+gpe_status movers_after_step(gpe_ctx *c, float dt);         // after every step of gpe_step / gpe_run, behind the bodies, before the colliders
+void movers_release(gpe_ctx *c);
 
 // profiling scope: a pair of timestamps on ctx->stream when ctx->profiling, else nothing -- slots of the stamp buffer
 // (scope_stamps.h), or hipEvents where scope_uses_stamps() says no.  kSharedBoundaries: inside a ScopeRegion the scope
@@ -1237,6 +1287,10 @@ gpe_status launch_bodies_pass(gpe_ctx *c, float2 *pos, const float *radius, uint
 gpe_status launch_fields_pass(gpe_ctx *c, const float2 *pos, float2 *prev, uint64_t n, const uint32_t *cell_start,
                               const uint32_t *items, const float4 *rec, uint32_t k, const ColliderGridView &view, float dt2,
                               unsigned long long *touched);
+// moving colliders (k_movers.hip): the build advances, poses and lists the movers (the grid zeroed before it), the pass
+// pushes pos[0, n) in place
+gpe_status launch_movers_build(gpe_ctx *c, const MoverBuildArgs &B);
+gpe_status launch_movers_pass(gpe_ctx *c, float2 *pos, const float *radius, uint64_t n, const MoverPassArgs &P);
 // native pipeline: its host side (gpe_native.hip; the kernels and their launchers: k_native.hip, native_launch.h)
 gpe_status native_configure(gpe_ctx *c);
 bool native_should_run(gpe_ctx *c);

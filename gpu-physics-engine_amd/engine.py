@@ -80,6 +80,10 @@ def anchor_bonds(uids, points, rest_length=0.0, stiffness=1.0, max_length=0.0):
     return rows
 
 
+# set_movers / movers: the rows of gpe_mover (56 bytes each); mover_poses: the rows of gpe_mover_pose (24 bytes each)
+MOVER_DTYPE = np.dtype([(name, np.uint32 if ctype is C.c_uint32 else np.float32) for name, ctype in L.GpeMover._fields_])
+MOVER_POSE_DTYPE = np.dtype([(name, np.float32) for name, _ in L.GpeMoverPose._fields_])
+assert MOVER_DTYPE.itemsize == C.sizeof(L.GpeMover) == 56 and MOVER_POSE_DTYPE.itemsize == C.sizeof(L.GpeMoverPose) == 24
 # set_bodies / bodies: the rows of gpe_body (24 bytes each, the struct's layout)
 # set_fields / fields: the rows of gpe_field (56 bytes each, the struct's layout)
 FIELD_DTYPE = np.dtype([(name, np.uint32 if ctype is C.c_uint32 else np.float32) for name, ctype in L.GpeField._fields_])
@@ -606,6 +610,55 @@ class ParticleSystem:
         info = L.GpeCollidersInfo(struct_size=C.sizeof(L.GpeCollidersInfo))
         self.ctx.call("gpe_get_colliders_info", C.byref(info))
         return {name: getattr(info, name) for name, _ in L.GpeCollidersInfo._fields_ if name != "struct_size"}
+
+    # Moving colliders (not in the reference; include/gpe.h): capsules with a motion -- pistons and rotors -- advanced,
+    # listed and applied on the device after every update() / step of run(), behind the bodies and before the static
+    # colliders.  Step state: save() keeps the set and the poses.
+    def set_movers(self, movers):
+        """gpe_set_movers: replace the set by the rows of a MOVER_DTYPE array; no rows clear it.  Every pose starts
+        fresh, the counters anew."""
+        rows = np.ascontiguousarray(movers, MOVER_DTYPE).reshape(-1)
+        k = len(rows)
+        self.ctx.call("gpe_set_movers", rows.ctypes.data_as(C.POINTER(L.GpeMover)) if k else None, k)
+
+    def movers(self):
+        """gpe_get_movers -> MOVER_DTYPE[k]: the set."""
+        k = C.c_uint64()
+        self.ctx.call("gpe_get_movers", None, 0, C.byref(k))
+        rows = np.zeros(max(k.value, 1), MOVER_DTYPE)
+        self.ctx.call("gpe_get_movers", rows.ctypes.data_as(C.POINTER(L.GpeMover)), k.value, C.byref(k))
+        return rows[:k.value]
+
+    def clear_movers(self):
+        """gpe_set_movers with k = 0."""
+        self.ctx.call("gpe_set_movers", None, 0)
+
+    def apply_movers(self, dt):
+        """gpe_apply_movers: advance once and run one pass now (the hook of a host that steps module by module).  Does
+        not synchronise."""
+        self.ctx.call("gpe_apply_movers", float(dt))
+
+    def mover_poses(self):
+        """gpe_get_mover_poses -> MOVER_POSE_DTYPE[k]: the posed capsule and the state of every mover.  Blocks like a
+        download."""
+        k = C.c_uint64()
+        self.ctx.call("gpe_get_mover_poses", None, 0, C.byref(k))
+        rows = np.zeros(max(k.value, 1), MOVER_POSE_DTYPE)
+        self.ctx.call("gpe_get_mover_poses", rows.ctypes.data_as(C.POINTER(L.GpeMoverPose)), k.value, C.byref(k))
+        return rows[:k.value]
+
+    def set_mover_poses(self, poses):
+        """gpe_set_mover_poses: restore the states q0, q1 of a MOVER_POSE_DTYPE array, one row per mover; the capsules are
+        recomputed from them."""
+        rows = np.ascontiguousarray(poses, MOVER_POSE_DTYPE).reshape(-1)
+        k = len(rows)
+        self.ctx.call("gpe_set_mover_poses", rows.ctypes.data_as(C.POINTER(L.GpeMoverPose)) if k else None, k)
+
+    def movers_info(self):
+        """gpe_get_movers_info -> dict(k, passes, pushed, grid_x, grid_y, mask_words, listed).  Blocks like a download."""
+        info = L.GpeMoversInfo(struct_size=C.sizeof(L.GpeMoversInfo))
+        self.ctx.call("gpe_get_movers_info", C.byref(info))
+        return {name: getattr(info, name) for name, _ in L.GpeMoversInfo._fields_ if name not in ("struct_size", "reserved")}
 
     # Distance bonds (not in the reference; include/gpe.h): particles tied to each other, or to a fixed point, by uid,
     # relaxed on the device after every update() / step of run(), before the colliders.  Step state: save() keeps them.
@@ -1281,6 +1334,35 @@ class State:
         """ParticleSystem.colliders_info -> dict(k, passes, pushed, grid_x, grid_y, list_entries)."""
         return self.particles.colliders_info()
 
+    def set_movers(self, movers):
+        """ParticleSystem.set_movers: moving colliders (rows of MOVER_DTYPE) advanced and applied after every step, behind
+        the bodies and before the static colliders."""
+        self.particles.set_movers(movers)
+
+    def movers(self):
+        """ParticleSystem.movers -> MOVER_DTYPE[k]."""
+        return self.particles.movers()
+
+    def clear_movers(self):
+        """ParticleSystem.clear_movers."""
+        self.particles.clear_movers()
+
+    def apply_movers(self, dt):
+        """ParticleSystem.apply_movers: advance once and run one pass now."""
+        self.particles.apply_movers(dt)
+
+    def mover_poses(self):
+        """ParticleSystem.mover_poses -> MOVER_POSE_DTYPE[k]."""
+        return self.particles.mover_poses()
+
+    def set_mover_poses(self, poses):
+        """ParticleSystem.set_mover_poses."""
+        self.particles.set_mover_poses(poses)
+
+    def movers_info(self):
+        """ParticleSystem.movers_info -> dict(k, passes, pushed, grid_x, grid_y, mask_words, listed)."""
+        return self.particles.movers_info()
+
     def set_bonds(self, bonds, iterations=1):
         """ParticleSystem.set_bonds: distance bonds (rows of BOND_DTYPE) relaxed after every step, before the colliders."""
         self.particles.set_bonds(bonds, iterations)
@@ -1451,8 +1533,11 @@ class State:
         for the same reason.  Static colliders are step state: a set that is present is written (`colliders`), and so
         are distance bonds with their relaxation count and broken flags (`bonds`, `bond_iterations`, `bonds_broken`) and
         bodies with their members and broken flags (`bodies`, `bodies_broken`, `body_member_uid`, `body_member_rest`) and
-        force fields (`fields`)."""
+        force fields (`fields`) and moving colliders with their poses (`movers`, `mover_poses`)."""
         extra = {}
+        movers = self.movers()
+        if len(movers):
+            extra.update(movers=movers, mover_poses=self.mover_poses())
         fields = self.fields()
         if len(fields):
             extra.update(fields=fields)
@@ -1512,6 +1597,9 @@ class State:
                 st.set_bodies(rows, d["body_member_uid"], d["body_member_rest"])
             if "fields" in d.files:
                 st.set_fields(d["fields"].astype(FIELD_DTYPE))
+            if "movers" in d.files:
+                st.set_movers(d["movers"].astype(MOVER_DTYPE))
+                st.set_mover_poses(d["mover_poses"].astype(MOVER_POSE_DTYPE))
             return st
 
     def close(self):

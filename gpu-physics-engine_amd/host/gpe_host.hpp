@@ -483,6 +483,43 @@ class ParticleSystem {
         ctx_->call(gpe_get_fields_info(ctx_->raw(), &info));
         return info;
     }
+    // not in the reference: moving colliders (include/gpe.h) -- capsules with a motion: a piston slides (back and forth
+    // or for ever), a rotor turns about a pivot.  Advanced, listed and applied on the device after every step of
+    // update() / run(), behind the bodies and before the static colliders.  Step state: a snapshot keeps the set and
+    // the poses (movers(), mover_poses() -> set_movers, set_mover_poses).
+    void set_movers(const std::vector<gpe_mover> &movers)
+    {
+        ctx_->call(gpe_set_movers(ctx_->raw(), movers.empty() ? nullptr : movers.data(), movers.size()));
+    }
+    std::vector<gpe_mover> movers() const
+    {
+        uint64_t k = 0;
+        ctx_->call(gpe_get_movers(ctx_->raw(), nullptr, 0, &k));
+        std::vector<gpe_mover> out(k);
+        ctx_->call(gpe_get_movers(ctx_->raw(), out.empty() ? nullptr : out.data(), k, &k));
+        return out;
+    }
+    void clear_movers() { ctx_->call(gpe_set_movers(ctx_->raw(), nullptr, 0)); }
+    void apply_movers(float dt) { ctx_->call(gpe_apply_movers(ctx_->raw(), dt)); }   // advance + one pass now: the hook of the per-module calls
+    std::vector<gpe_mover_pose> mover_poses() const
+    {
+        uint64_t k = 0;
+        ctx_->call(gpe_get_mover_poses(ctx_->raw(), nullptr, 0, &k));
+        std::vector<gpe_mover_pose> out(k);
+        ctx_->call(gpe_get_mover_poses(ctx_->raw(), out.empty() ? nullptr : out.data(), k, &k));
+        return out;
+    }
+    void set_mover_poses(const std::vector<gpe_mover_pose> &poses)
+    {
+        ctx_->call(gpe_set_mover_poses(ctx_->raw(), poses.empty() ? nullptr : poses.data(), poses.size()));
+    }
+    gpe_movers_info movers_info() const
+    {
+        gpe_movers_info info{};
+        info.struct_size = sizeof(info);
+        ctx_->call(gpe_get_movers_info(ctx_->raw(), &info));
+        return info;
+    }
     // not in the reference: every particle in a circle / box, or the one under a point (include/gpe.h), ascending
     // storage index; uid stays empty while uids are off.  pick() returns no rows when no disc contains the point.
     struct QueryResult {

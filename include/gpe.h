@@ -375,7 +375,7 @@ gpe_status gpe_monitor_end(gpe_ctx *ctx);
  *    collider.
  *  - gpe_set_colliders replaces the set (k == 0 clears it and frees its buffers) and zeroes passes and pushed; it may be
  *    called before there are particles and synchronises like gpe_add_particles.  A host that moves an obstacle calls
- *    it once a frame.  gpe_get_colliders delivers the first min(k, capacity) colliders into out (may be NULL with
+ *    it once a frame, or makes it a mover (below).  gpe_get_colliders delivers the first min(k, capacity) colliders into out (may be NULL with
  *    capacity 0) and the number set into *k.  gpe_apply_colliders with no colliders or no particles: GPE_OK, nothing
  *    done.
  *  - Errors (the previous set stays untouched): a NULL ctx, NULL colliders with k > 0, k > GPE_COLLIDERS_MAX, a
@@ -397,12 +397,96 @@ gpe_status gpe_get_colliders(const gpe_ctx *ctx, gpe_collider *out, uint64_t cap
 gpe_status gpe_apply_colliders(gpe_ctx *ctx);                              /* one pass now, stream-ordered, no sync */
 gpe_status gpe_get_colliders_info(gpe_ctx *ctx, gpe_colliders_info *info); /* synchronises (reads the device counters) */
 
+/* ---- moving colliders (not in the reference) ----------------------------------------------------------------------
+ * Obstacles that move: a piston, a lift, a sliding gate, a paddle wheel, a mixer blade.  A mover is a capsule at rest
+ * (as gpe_collider) plus a motion: GPE_MOVER_LINEAR slides it along a velocity, for ever (travel == 0) or back and forth
+ * over a distance (travel > 0); GPE_MOVER_ROTATE turns it about a pivot at omega radians per second, counter-clockwise,
+ * full turns.  The movers are a second set beside the static colliders, independent of them.  While a context holds a
+ * set, gpe_step and every iteration of gpe_run advance every mover by dt ON THE DEVICE, rebuild the movers' lookup grid
+ * there and run one pass over the particles, stream-ordered, no host round trip (csrc/k_movers.hip): a memset and two
+ * launches per step.  Order: step -> bonds -> bodies -> movers -> colliders -> fields -> tracers / monitor: the static
+ * walls keep the last word over a piston that squeezes particles against them.  The per-module calls run no pass:
+ * gpe_apply_movers(dt) is their hook.  A context without movers launches and allocates exactly what it does without
+ * this section.
+ *  - The motion (csrc/k_mover.h is the one definition), in IEEE binary32, one rounding per operation, left to right, no
+ *    FMA, `/` and sqrtf correctly rounded, no libm sin / cos.  The state of a mover is (q0, q1).
+ *    At set time: speed = sqrtf(vx*vx + vy*vy);  u = v / speed, or (0, 0) when speed == 0.
+ *    LINEAR, (q0, q1) = (g, sgn), fresh (0, +1):  d = speed*dt;  g1 = g + sgn*d;  with travel > 0: if g1 > travel:
+ *      g1 = travel - (g1 - travel), sgn = -sgn; else if g1 < 0: g1 = -g1, sgn = -sgn; then g1 is clamped into
+ *      [0, travel].  The posed end points are rest + (g1*ux, g1*uy).
+ *    ROTATE, (q0, q1) = (c, s), fresh (1, 0):  x = omega*dt;  x == 0 keeps the state bit for bit;  else x2 = x*x,
+ *      sa = x + x*(x2*(S0 + x2*(S1 + x2*(S2 + x2*S3)))),  S = -1/6, 1/120, -1/5040, 1/362880 as binary32,
+ *      ca = 1 + x2*(C0 + x2*(C1 + x2*(C2 + x2*(C3 + x2*C4)))),  C = -1/2, 1/24, -1/720, 1/40320, -1/3628800,
+ *      c2 = c*ca - s*sa;  s2 = s*ca + c*sa;  m = sqrtf(c2*c2 + s2*s2);  (c, s) = (c2/m, s2/m).
+ *      A posed end point is p + (rx*c - ry*s, rx*s + ry*c) with r = rest - p.
+ *    Over |x| <= 0.5 the polynomial is within 3.9e-8 of sin and cos; the orientation stays within 2^-21 of unit length
+ *    and its angle within steps * 2^-22 rad of steps * omega*dt.
+ *  - The dt contract: |omega*dt| <= 0.5 for every ROTATE mover (the polynomial's range), and speed*|dt| <= travel for
+ *    every LINEAR mover with travel > 0 (one reflection per step suffices); dt is finite.  It is checked on the host,
+ *    against the set's largest |omega| and, among the movers that go back and forth, the largest speed and the smallest
+ *    travel, before gpe_step, gpe_run and gpe_apply_movers launch anything: a violation is GPE_ERR_INVALID_ARG and the
+ *    context is as if the call had not been made.
+ *  - The pass.  After the advance every particle is pushed out of the posed mover it penetrates deepest: the static
+ *    colliders' touch, key, normal and clamp (above), unchanged, every mover judged from the position the pass starts
+ *    with.  Only pos is written, prev stays: in a Verlet engine that hands the particle the wall's velocity.  A particle
+ *    no mover touches keeps every bit.
+ *  - No swept test: a mover must be thicker than one step's relative displacement of mover and particle.  Make movers
+ *    thick.
+ *  - The set and the poses are step state: they survive gpe_set_particles, adds, removals, edits, re-sorts, growth and
+ *    gpe_set_world; gpe_destroy frees them.  Movers name no particle.
+ *  - The pass finds a particle's movers through a coarse grid (at most 128 x 128 cells) of bit masks, built on the
+ *    device every step from the posed capsules for |gpe_max_radius| and the world as they are then.  No result depends
+ *    on the grid: a particle outside it, with a NaN coordinate or with a radius above the bound is tested against every
+ *    mover.
+ *  - gpe_set_movers replaces the set (k == 0 clears it and frees its buffers), resets every pose to its fresh state and
+ *    zeroes passes and pushed; it synchronises like gpe_add_particles.  gpe_get_movers delivers the first
+ *    min(k, capacity) movers into out (may be NULL with capacity 0) and the number set into *k; a radius of -0.0 reads
+ *    back as +0.  gpe_get_mover_poses does the same with the current capsule and state of every mover, and
+ *    synchronises.  gpe_set_mover_poses restores the states (k must be the set's size): ax .. by of the input are
+ *    ignored and recomputed from the state.  gpe_apply_movers(dt) advances once and runs one pass now, stream-ordered,
+ *    no sync; with no movers or no particles: GPE_OK, nothing done.  gpe_get_movers_info synchronises; `listed` is the
+ *    number of (cell, mover) bits the last build set.
+ *  - Errors (the previous set and poses stay untouched): a NULL ctx, NULL movers with k > 0, k > GPE_MOVERS_MAX, a value
+ *    that is not finite (a velocity whose speed overflows included), a radius that is NaN or negative (-0.0 is accepted
+ *    as 0), an unknown kind, flags or reserved not 0, travel < 0; for gpe_set_mover_poses a k that is not the set's
+ *    size, a state that is not finite, a LINEAR sgn that is not +1 or -1, a g outside [0, travel] when travel > 0; a
+ *    struct_size below the struct's: GPE_ERR_INVALID_ARG.  gpe_set_movers on a sharded context, and
+ *    gpe_shard_set_particles, gpe_use_order_keys(ctx, 1) and gpe_set_counts on a context that holds movers:
+ *    GPE_ERR_UNSUPPORTED. */
+#define GPE_MOVERS_MAX 1024u
+enum { GPE_MOVER_LINEAR = 0, GPE_MOVER_ROTATE = 1 };
+typedef struct gpe_mover {
+    float ax, ay, bx, by, radius;     /* the capsule at rest (as gpe_collider)                               */
+    uint32_t kind;                    /* GPE_MOVER_*                                                         */
+    float vx, vy;                     /* LINEAR: velocity, world units per second                            */
+    float travel;                     /* LINEAR: > 0: back and forth over this distance along v; 0: for ever */
+    float px, py;                     /* ROTATE: the pivot                                                   */
+    float omega;                      /* ROTATE: radians per second, counter-clockwise, full turns           */
+    uint32_t flags;                   /* 0                                                                   */
+    uint32_t reserved;                /* 0                                                                   */
+} gpe_mover;                          /* 56 bytes */
+typedef struct gpe_mover_pose { float ax, ay, bx, by, q0, q1; } gpe_mover_pose;   /* 24 bytes: the posed capsule, the state */
+typedef struct gpe_movers_info {
+    uint32_t struct_size, k;          /* in / movers set                                                */
+    uint64_t passes;                  /* passes run since the last gpe_set_movers                       */
+    uint64_t pushed;                  /* particles moved by those passes, summed (integer atomics only) */
+    uint32_t grid_x, grid_y;          /* the lookup grid of the last build (diagnostic)                 */
+    uint32_t mask_words, reserved;    /* 64-bit mask words per cell: ceil(k / 64)                       */
+    uint64_t listed;                  /* (cell, mover) bits the last build set                          */
+} gpe_movers_info;                    /* 48 bytes */
+gpe_status gpe_set_movers(gpe_ctx *ctx, const gpe_mover *movers, uint64_t k);
+gpe_status gpe_get_movers(const gpe_ctx *ctx, gpe_mover *out, uint64_t capacity, uint64_t *k);
+gpe_status gpe_get_mover_poses(gpe_ctx *ctx, gpe_mover_pose *out, uint64_t capacity, uint64_t *k);   /* synchronises */
+gpe_status gpe_set_mover_poses(gpe_ctx *ctx, const gpe_mover_pose *poses, uint64_t k);
+gpe_status gpe_apply_movers(gpe_ctx *ctx, float dt);                       /* advance + one pass now, stream-ordered, no sync */
+gpe_status gpe_get_movers_info(gpe_ctx *ctx, gpe_movers_info *info);       /* synchronises (reads the device counters) */
+
 /* ---- distance bonds (not in the reference) ------------------------------------------------------------------------
  * Ties between particles: a rope, a chain, a cloth, a soft body, a pinned object, a sheet that tears.  A bond holds two
  * particles, named by uid (gpe_enable_uids must be on), at a rest length; an anchor bond (GPE_BOND_ANCHOR) holds one
  * particle to a fixed point.  While a context holds a set, gpe_step and every iteration of gpe_run run one pass after
  * the step, BEFORE the static colliders (walls keep the last word) and the tracers and the monitor, stream-ordered, on
- * the device (csrc/k_bonds.hip): step -> bonds -> colliders -> tracers / monitor.  The per-module calls run no pass:
+ * the device (csrc/k_bonds.hip): step -> bonds -> bodies -> movers -> colliders -> fields -> tracers / monitor.  The per-module calls run no pass:
  * gpe_apply_bonds is their hook.  A context without bonds launches and allocates exactly what it does without this
  * section.
  *  - One relaxation (csrc/k_bond.h is the one definition).  Every bond is judged from the positions the relaxation
@@ -471,7 +555,7 @@ gpe_status gpe_get_bonds_info(gpe_ctx *ctx, gpe_bonds_info *info); /* synchronis
  * frame (only the offsets matter), a stiffness in [0, 1] and a break_distance >= 0 (0: never breaks).  A uid appears
  * at most once in the whole set.  While a context holds a set, gpe_step and every iteration of gpe_run run one shape
  * matching pass (Mueller et al. 2005) after the step, behind the distance bonds and BEFORE the static colliders, on
- * the device (csrc/k_bodies.hip): step -> bonds -> bodies -> colliders -> tracers / monitor.  A bond can hang a body
+ * the device (csrc/k_bodies.hip): step -> bonds -> bodies -> movers -> colliders -> fields -> tracers / monitor.  A bond can hang a body
  * from an anchor; walls keep the last word.  The per-module calls run no pass: gpe_apply_bodies is their hook.  A
  * context without bodies launches and allocates exactly what it does without this section.
  *  - The pass (csrc/k_body.h is the one definition), IEEE binary32, one rounding per operation, left to right, no
@@ -546,7 +630,7 @@ gpe_status gpe_get_bodies_info(gpe_ctx *ctx, gpe_bodies_info *info);  /* synchro
  * is a region (everywhere, a closed disc, a closed box) and a kind (a uniform acceleration, a pull toward a pole, a
  * swirl around a pole, a drag).  While a context holds a set, gpe_step and every iteration of gpe_run run one pass over
  * the particles after the step, BEHIND the static colliders and before the tracers and the monitor, stream-ordered, on
- * the device (csrc/k_fields.hip): step -> bonds -> bodies -> colliders -> fields -> tracers / monitor.  A field is
+ * the device (csrc/k_fields.hip): step -> bonds -> bodies -> movers -> colliders -> fields -> tracers / monitor.  A field is
  * judged at the position the step ends with; a tracer or monitor frame sees the new velocity; the velocity acts from
  * the next step on.  The per-module calls (gpe_integrate and the rest) run no pass: gpe_apply_fields is their hook.  A
  * context without fields launches and allocates exactly what it does without this section.
