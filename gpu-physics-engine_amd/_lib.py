@@ -60,6 +60,8 @@ FIELD_UNIFORM, FIELD_RADIAL, FIELD_VORTEX, FIELD_DRAG = 0, 1, 2, 3
 FALLOFF_NONE, FALLOFF_LINEAR = 0, 1
 MOVERS_MAX = 1024
 MOVER_LINEAR, MOVER_ROTATE = 0, 1
+SURFACES_OF_COLLIDERS, SURFACES_OF_MOVERS = 0, 1
+SURFACE_PLAIN = 1
 EDIT_BY_INDEX, EDIT_BY_UID = 0, 1
 CLUSTER_BY_INDEX, CLUSTER_BY_UID = 0, 1
 VEL_ADD, VEL_SET, VEL_SCALE = 0, 1, 2
@@ -302,6 +304,12 @@ class GpeMoversInfo(C.Structure):
                 ("listed", C.c_uint64)]
 
 
+class GpeSurface(C.Structure):
+    """gpe_surface: the material of one static collider or mover: restitution in [0, 1], friction >= 0, flags
+    (SURFACE_PLAIN: this obstacle keeps the plain rule), reserved 0.  16 bytes."""
+    _fields_ = [("restitution", C.c_float), ("friction", C.c_float), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class GpeParticleEdit(C.Structure):
     """gpe_particle_edit: in struct_size / key_kind / k / keys and the field arrays (each may be NULL), out edited."""
     _fields_ = [("struct_size", C.c_uint32), ("key_kind", C.c_uint32), ("k", C.c_uint64),
@@ -388,6 +396,8 @@ SYMBOLS = [
     ("gpe_set_mover_poses", _I32, [_VP, C.POINTER(GpeMoverPose), _U64]),
     ("gpe_apply_movers", _I32, [_VP, _F]),
     ("gpe_get_movers_info", _I32, [_VP, C.POINTER(GpeMoversInfo)]),
+    ("gpe_set_surfaces", _I32, [_VP, _U32, C.POINTER(GpeSurface), _U64]),
+    ("gpe_get_surfaces", _I32, [_VP, _U32, C.POINTER(GpeSurface), _U64, C.POINTER(_U64)]),
     ("gpe_query_circle", _I32, [_VP, _F, _F, _F, C.POINTER(GpeQueryResult)]),
     ("gpe_query_box", _I32, [_VP, _F, _F, _F, _F, C.POINTER(GpeQueryResult)]),
     ("gpe_pick", _I32, [_VP, _F, _F, C.POINTER(GpeQueryResult)]),

@@ -29,6 +29,7 @@ void gpe::colliders_release(gpe_ctx *c)
 {
     ColliderState &S = c->colliders;
     colliders_grid_release(c);
+    surfaces_drop(c, GPE_SURFACES_OF_COLLIDERS);
     dev_free(c, S.rec); dev_free(c, S.pushed);
     S = ColliderState();
 }
@@ -89,7 +90,7 @@ static gpe_status colliders_pass(gpe_ctx *c, const char *who)
     GPE_TRY(colliders_grid_ready(c, who));
     Scope s(c, "Colliders");
     GPE_TRY(launch_colliders_pass(c, c->pos, c->radius, c->n, S.cell_start, S.items, S.rec, (uint32_t)S.set.size(), S.view,
-                                  S.pushed));
+                                  S.pushed, S.surf, c->prev));
     S.passes += 1;
     return GPE_OK;
 }
@@ -148,6 +149,7 @@ gpe_status gpe_set_colliders(gpe_ctx *c, const gpe_collider *colliders, uint64_t
     }
     dev_free(c, S.rec);
     colliders_grid_release(c);                                         // built before the next pass
+    surfaces_drop(c, GPE_SURFACES_OF_COLLIDERS);                       // a new set gets new surfaces
     S.rec = d_rec;
     S.set.swap(set);
     S.passes = 0;

@@ -423,6 +423,9 @@ struct ColliderState {
     std::vector<gpe_collider> set;               // the colliders as the host gave them (empty: none, nothing is launched)
     float4 *rec = nullptr;                       // 2 per collider: (ax, ay, bx, by), (R, 0, 0, 0)
     unsigned long long *pushed = nullptr;        // one word: particles moved since the last gpe_set_colliders
+    // the surfaces (gpe_set_surfaces; gpe_surfaces.hip, k_surface.h): empty / null: none, the plain pass is launched
+    std::vector<gpe_surface> surfaces;           // one row per collider, as the host gave them (-0.0 stored as +0)
+    float4 *surf = nullptr;                      // the same rows on the device
     uint64_t passes = 0;                         // passes enqueued since then
     // the lookup grid (collider_grid.h), rebuilt before the next pass when what it was built for has changed
     bool grid_valid = false;
@@ -495,6 +498,10 @@ struct MoverState {
     float *pose = nullptr;                       // 6 per mover: gpe_mover_pose, the posed capsule and the motion state
     float4 *rec = nullptr;                       // 2 per mover: the posed (ax, ay, bx, by), (R, 0, 0, 0): the pass's records
     unsigned long long *pushed = nullptr;        // one word: particles moved since the last gpe_set_movers
+    // the surfaces (gpe_set_surfaces; gpe_surfaces.hip, k_surface.h): empty / null: none, the plain build and pass
+    std::vector<gpe_surface> surfaces;           // one row per mover, as the host gave them (-0.0 stored as +0)
+    float4 *surf = nullptr;                      // the same rows on the device
+    float4 *old = nullptr;                       // one per mover: the posed capsule before the last advance (the build writes it)
     // the lookup grid, allocated once for the largest grid (kMoverGridMaxDim^2 cells): the masks (cells * words 64-bit
     // words), the summary (cells 32-bit words) and one 64-bit word `listed`, laid out for the view of the last build
     unsigned char *grid = nullptr;
@@ -509,6 +516,7 @@ struct MoverBuildArgs {
     const MoverDef *def = nullptr;
     float *pose = nullptr;
     float4 *rec = nullptr;
+    float4 *old = nullptr;                       // with surfaces: the capsule before the advance, one per mover; else null
     uint32_t k = 0, words = 0;
     MoverGridView g;
     float rb = 0.f, dt = 0.f;
@@ -525,6 +533,9 @@ struct MoverPassArgs {
     ColliderGridView view;
     float world_w = 0.f, world_h = 0.f;
     unsigned long long *pushed = nullptr;
+    const float4 *surf = nullptr;                // the surface form: one row per mover (e, mu, flags, reserved), ...
+    const float4 *old = nullptr;                 // ... the capsules before the advance ...
+    float2 *prev = nullptr;                      // ... and the previous positions it rewrites under a hit
 };
 
 struct SortWorkspace {
@@ -1029,6 +1040,8 @@ inline bool has_colliders(const gpe_ctx *c) { return !c->colliders.set.empty(); 
 gpe_status refuse_colliders(gpe_ctx *c, const char *who);   // GPE_ERR_UNSUPPORTED: sharding a context that holds colliders
 gpe_status colliders_after_step(gpe_ctx *c);       // after every step of gpe_step / gpe_run, before the observers
 void colliders_release(gpe_ctx *c);
+// gpe_surfaces.hip: the surfaces of the two sets; a new set drops its target's
+void surfaces_drop(gpe_ctx *c, uint32_t target);   // GPE_SURFACES_OF_*: frees the rows, the next pass is the plain one
 // gpe_bonds.hip: the distance bonds of a context that holds some
 inline bool has_bonds(const gpe_ctx *c) { return !c->bonds.set.empty(); }
 gpe_status refuse_bonds(gpe_ctx *c, const char *who);       // GPE_ERR_UNSUPPORTED: taking the uids from a context that holds bonds
@@ -1275,7 +1288,7 @@ gpe_status launch_monitor_final(gpe_ctx *c, const void *partials, uint64_t n, ui
 // describes (view.gx * view.gy + 1 words; every item < k); rec: 2 k records; *pushed += the particles moved
 gpe_status launch_colliders_pass(gpe_ctx *c, float2 *pos, const float *radius, uint64_t n, const uint32_t *cell_start,
                                  const uint32_t *items, const float4 *rec, uint32_t k, const ColliderGridView &view,
-                                 unsigned long long *pushed);
+                                 unsigned long long *pushed, const float4 *surf = nullptr, float2 *prev = nullptr);
 // distance bonds (k_bonds.hip): `iterations` relaxations of the k bonds of B over pos[0, n) in place, two launches each
 gpe_status launch_bonds_pass(gpe_ctx *c, float2 *pos, const float *radius, uint64_t n, const BondState &B, uint32_t k,
                              uint32_t m, uint32_t iterations);

@@ -30,6 +30,8 @@ static uint64_t grid_listed_offset(uint64_t cells, uint32_t words)
 static void movers_buffers_free(gpe_ctx *c, MoverState &S)
 {
     dev_free(c, S.def); dev_free(c, S.pose); dev_free(c, S.rec); dev_free(c, S.pushed); dev_free(c, S.grid);
+    dev_free(c, S.surf); dev_free(c, S.old);                           // (a new set gets new surfaces)
+    S.surfaces.clear();
 }
 
 void gpe::movers_release(gpe_ctx *c)
@@ -64,6 +66,7 @@ static gpe_status movers_pass(gpe_ctx *c, float dt)
     GPE_HIP(c, hipMemsetAsync(S.grid, 0, at_listed + 8, c->stream));
     MoverBuildArgs B;
     B.def = S.def; B.pose = S.pose; B.rec = S.rec;
+    B.old = S.surf ? S.old : nullptr;
     B.k = k; B.words = S.words;
     B.g = g;
     B.rb = g.view.rb; B.dt = dt;
@@ -79,6 +82,9 @@ static gpe_status movers_pass(gpe_ctx *c, float dt)
     P.view = g.view;
     P.world_w = c->cfg.world_width; P.world_h = c->cfg.world_height;
     P.pushed = S.pushed;
+    if (S.surf) {
+        P.surf = S.surf; P.old = S.old; P.prev = c->prev;
+    }
     GPE_TRY(launch_movers_pass(c, c->pos, c->radius, c->n, P));
     S.passes += 1;
     return GPE_OK;

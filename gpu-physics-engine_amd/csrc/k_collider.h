@@ -26,6 +26,7 @@ struct ColliderTouch {
     float depth;                 // s - d: how far the particle is pushed
     float qx, qy, d;             // the offset from the segment's nearest point to the centre, and its length
     float dx, dy, A;             // b - a and its squared length
+    float u;                     // the clamped parameter of the nearest point on a -> b (k_surface.h: where a wall moves)
 };
 
 // The particle (centre p, stored radius r) against the capsule a -> b of radius R.  true: touched, *t filled.
@@ -69,6 +70,7 @@ GPE_COLLIDER_FN bool collider_touch(float px, float py, float r, float ax, float
     t->depth = s - d;
     t->qx = qx; t->qy = qy; t->d = d;
     t->dx = dx; t->dy = dy; t->A = A;
+    t->u = u;
     return true;
 }
 

@@ -6,8 +6,13 @@
 // radius is loaded only under a non-empty list, pos stored only for a particle that moved.  The colliders are 32-byte
 // records (ax, ay, bx, by | R, padding): 4096 of them are 128 KB and stay in an XCD's L2; cell_start is read at the
 // particles' own locality (they are kept in Morton order).
+//
+// The surface form (k_colliders_pass_surface, launched only while the set holds surfaces: k_surface.h) is the same
+// lookup and the same winner; under a hit it also loads the winner's surface row (one float4: 4096 rows are 64 KB) and
+// prev[i], and stores prev[i] beside pos[i].  The common lane costs what it costs in the plain form.
 #include "gpe_internal.h"
 #include "k_collider.h"
+#include "k_surface.h"
 
 namespace gpe {
 
@@ -19,6 +24,8 @@ struct ColliderPassArgs {
     ColliderGridView view;
     float world_w = 0.f, world_h = 0.f;
     unsigned long long *pushed = nullptr;
+    const float4 *surf = nullptr;                // the surface form: one row per collider (e, mu, flags, reserved) ...
+    float2 *prev = nullptr;                      // ... and the previous positions it rewrites under a hit
 };
 
 __device__ __forceinline__ void collider_try(const ColliderPassArgs &P, uint32_t j, float px, float py, float r,
@@ -32,7 +39,9 @@ __device__ __forceinline__ void collider_try(const ColliderPassArgs &P, uint32_t
     best = key > best ? key : best;
 }
 
-// particle i at (px, py).  true: it moved, (ox, oy) is its new position
+// particle i at (px, py).  true: it moved, (ox, oy) is its new position.  SURF: the winner's surface is applied, and
+// prev[i] written here, unless the row is PLAIN or p - prev is not finite
+template <bool SURF>
 __device__ __forceinline__ bool collider_resolve(const ColliderPassArgs &P, const float *__restrict__ radius, uint64_t i,
                                                  float px, float py, float &ox, float &oy)
 {
@@ -60,6 +69,20 @@ __device__ __forceinline__ bool collider_resolve(const ColliderPassArgs &P, cons
     (void)collider_touch(px, py, r, s.x, s.y, s.z, s.w, P.rec[2 * j + 1].x, &t);   // the winner again: the same bits
     float nx, ny;
     collider_normal(t, &nx, &ny);
+    if constexpr (SURF) {
+        const float4 row = P.surf[j];
+        if (!(__float_as_uint(row.z) & kSurfacePlain)) {
+            const float2 pv = P.prev[i];
+            if (surface_velocity_finite(px, py, pv.x, pv.y)) {
+                float o[4];
+                surface_apply(px, py, pv.x, pv.y, r, nx, ny, t.depth, 0.0f, 0.0f, row.x, row.y, P.world_w, P.world_h, o);
+                ox = o[0];
+                oy = o[1];
+                P.prev[i] = make_float2(o[2], o[3]);
+                return true;
+            }
+        }
+    }
     const float mx = nx * t.depth;
     const float my = ny * t.depth;
     const float qx = px + mx;
@@ -69,8 +92,9 @@ __device__ __forceinline__ bool collider_resolve(const ColliderPassArgs &P, cons
     return true;
 }
 
-__global__ __launch_bounds__(kStreamBlock) void k_colliders_pass(float2 *__restrict__ pos, const float *__restrict__ radius,
-                                                                 uint64_t n, ColliderPassArgs P)
+template <bool SURF>
+__device__ __forceinline__ void colliders_pass_body(float2 *__restrict__ pos, const float *__restrict__ radius, uint64_t n,
+                                                    const ColliderPassArgs &P)
 {
     const uint64_t pairs = n >> 1;
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
@@ -81,8 +105,8 @@ __global__ __launch_bounds__(kStreamBlock) void k_colliders_pass(float2 *__restr
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < pairs; i += stride) {
         const float4 c = pos4[i];
         float2 o0, o1;
-        const bool m0 = collider_resolve(P, radius, 2 * i, c.x, c.y, o0.x, o0.y);
-        const bool m1 = collider_resolve(P, radius, 2 * i + 1, c.z, c.w, o1.x, o1.y);
+        const bool m0 = collider_resolve<SURF>(P, radius, 2 * i, c.x, c.y, o0.x, o0.y);
+        const bool m1 = collider_resolve<SURF>(P, radius, 2 * i + 1, c.z, c.w, o1.x, o1.y);
         if (m0) pos[2 * i] = o0;
         if (m1) pos[2 * i + 1] = o1;
         moved += (uint32_t)__popcll(ballot64(m0)) + (uint32_t)__popcll(ballot64(m1));
@@ -91,7 +115,7 @@ __global__ __launch_bounds__(kStreamBlock) void k_colliders_pass(float2 *__restr
         const uint64_t i = n - 1;
         const float2 c = pos[i];
         float2 o;
-        if (collider_resolve(P, radius, i, c.x, c.y, o.x, o.y)) {
+        if (collider_resolve<SURF>(P, radius, i, c.x, c.y, o.x, o.y)) {
             pos[i] = o;
             moved += 1;
         }
@@ -99,11 +123,26 @@ __global__ __launch_bounds__(kStreamBlock) void k_colliders_pass(float2 *__restr
     if (lane_id() == 0 && moved) atomicAdd(P.pushed, (unsigned long long)moved);
 }
 
+__global__ __launch_bounds__(kStreamBlock) void k_colliders_pass(float2 *__restrict__ pos, const float *__restrict__ radius,
+                                                                 uint64_t n, ColliderPassArgs P)
+{
+    colliders_pass_body<false>(pos, radius, n, P);
+}
+
+// (pos and P.prev are different arrays; P.prev[i] is read and written by the lane that owns particle i alone)
+__global__ __launch_bounds__(kStreamBlock) void k_colliders_pass_surface(float2 *__restrict__ pos,
+                                                                         const float *__restrict__ radius, uint64_t n,
+                                                                         ColliderPassArgs P)
+{
+    colliders_pass_body<true>(pos, radius, n, P);
+}
+
 // One pass over pos[0, n) in place.  cell_start / items / rec: device memory of view.gx * view.gy + 1 words, the
-// entries cell_start's last word counts (each < k) and 2 k records.  *pushed += the particles moved
+// entries cell_start's last word counts (each < k) and 2 k records.  *pushed += the particles moved.  surf != nullptr:
+// the surface form, k rows of surf and prev[0, n) read and written under a hit
 gpe_status launch_colliders_pass(gpe_ctx *c, float2 *pos, const float *radius, uint64_t n, const uint32_t *cell_start,
                                  const uint32_t *items, const float4 *rec, uint32_t k, const ColliderGridView &view,
-                                 unsigned long long *pushed)
+                                 unsigned long long *pushed, const float4 *surf, float2 *prev)
 {
     if (n == 0 || k == 0) return GPE_OK;
     ColliderPassArgs P;
@@ -111,7 +150,13 @@ gpe_status launch_colliders_pass(gpe_ctx *c, float2 *pos, const float *radius, u
     P.view = view;
     P.world_w = c->cfg.world_width; P.world_h = c->cfg.world_height;
     P.pushed = pushed;
-    hipLaunchKernelGGL(k_colliders_pass, dim3(stream_grid((n + 1) >> 1)), dim3(kStreamBlock), 0, c->stream, pos, radius, n, P);
+    if (surf) {
+        if (!prev) return fail(c, GPE_ERR_STATE, "launch_colliders_pass: surfaces without prev");
+        P.surf = surf; P.prev = prev;
+        hipLaunchKernelGGL(k_colliders_pass_surface, dim3(stream_grid((n + 1) >> 1)), dim3(kStreamBlock), 0, c->stream, pos, radius, n, P);
+    } else {
+        hipLaunchKernelGGL(k_colliders_pass, dim3(stream_grid((n + 1) >> 1)), dim3(kStreamBlock), 0, c->stream, pos, radius, n, P);
+    }
     GPE_HIP(c, hipGetLastError());
     return GPE_OK;
 }

@@ -7,8 +7,13 @@
 // of at most 128 x 128 cells.  A mask needs no count / scan / fill, has no capacity to run over, and an integer atomicOr
 // is order-free.  One summary word per cell names the mask words that are not zero: the common lane, whose cell has no
 // mover near, reads those 4 bytes and retires -- no radius load, no store.
+//
+// With surfaces (k_surface.h) the build also writes the capsule the OLD state poses (B.old, null otherwise), and the
+// pass has a sibling, k_movers_pass_surface: the same lookup and winner; under a hit it also loads the winner's surface
+// row, its old capsule and prev[i], and stores prev[i] beside pos[i].
 #include "gpe_internal.h"
 #include "k_mover.h"
+#include "k_surface.h"
 
 namespace gpe {
 
@@ -24,8 +29,12 @@ __global__ __launch_bounds__(kMoverBuildBlock) void k_movers_build(MoverBuildArg
     if (threadIdx.x == 0) {
         float *pose = B.pose + 6ull * j;
         float q0 = pose[4], q1 = pose[5];
-        mover_advance(m, B.dt, &q0, &q1);
         float cap[4];
+        if (B.old) {                                            // the capsule before the advance: a function of the state alone
+            mover_pose(m, q0, q1, cap);
+            B.old[j] = make_float4(cap[0], cap[1], cap[2], cap[3]);
+        }
+        mover_advance(m, B.dt, &q0, &q1);
         mover_pose(m, q0, q1, cap);
         pose[0] = cap[0]; pose[1] = cap[1]; pose[2] = cap[2]; pose[3] = cap[3];
         pose[4] = q0; pose[5] = q1;
@@ -70,7 +79,10 @@ __device__ __forceinline__ void mover_try(const MoverPassArgs &P, uint32_t j, fl
 }
 
 // particle i at (px, py).  true: it moved, (ox, oy) is its new position.  (collider_resolve of k_colliders.hip with
-// the masks in the place of the lists: the same touch, key, normal and clamp)
+// the masks in the place of the lists: the same touch, key, normal and clamp).  SURF: the winner's surface is applied
+// against the wall's displacement at the contact, and prev[i] written here, unless the row is PLAIN or p - prev is not
+// finite
+template <bool SURF>
 __device__ __forceinline__ bool mover_resolve(const MoverPassArgs &P, const float *__restrict__ radius, uint64_t i,
                                               float px, float py, float &ox, float &oy)
 {
@@ -107,6 +119,24 @@ __device__ __forceinline__ bool mover_resolve(const MoverPassArgs &P, const floa
     (void)collider_touch(px, py, r, s.x, s.y, s.z, s.w, P.rec[2 * j + 1].x, &t);   // the winner again: the same bits
     float nx, ny;
     collider_normal(t, &nx, &ny);
+    if constexpr (SURF) {
+        const float4 row = P.surf[j];
+        if (!(__float_as_uint(row.z) & kSurfacePlain)) {
+            const float2 pv = P.prev[i];
+            if (surface_velocity_finite(px, py, pv.x, pv.y)) {
+                const float4 b = P.old[j];
+                const float before[4] = {b.x, b.y, b.z, b.w}, after[4] = {s.x, s.y, s.z, s.w};
+                float wx, wy;
+                surface_wall_move(before, after, t.u, &wx, &wy);
+                float o[4];
+                surface_apply(px, py, pv.x, pv.y, r, nx, ny, t.depth, wx, wy, row.x, row.y, P.world_w, P.world_h, o);
+                ox = o[0];
+                oy = o[1];
+                P.prev[i] = make_float2(o[2], o[3]);
+                return true;
+            }
+        }
+    }
     const float mx = nx * t.depth;
     const float my = ny * t.depth;
     const float qx = px + mx;
@@ -117,8 +147,9 @@ __device__ __forceinline__ bool mover_resolve(const MoverPassArgs &P, const floa
 }
 
 // The shape of k_colliders_pass: two particles per lane, pos read 16 B per lane, the odd tail, the wave-voted counter.
-__global__ __launch_bounds__(kStreamBlock) void k_movers_pass(float2 *__restrict__ pos, const float *__restrict__ radius,
-                                                              uint64_t n, MoverPassArgs P)
+template <bool SURF>
+__device__ __forceinline__ void movers_pass_body(float2 *__restrict__ pos, const float *__restrict__ radius, uint64_t n,
+                                                 const MoverPassArgs &P)
 {
     const uint64_t pairs = n >> 1;
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
@@ -129,8 +160,8 @@ __global__ __launch_bounds__(kStreamBlock) void k_movers_pass(float2 *__restrict
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < pairs; i += stride) {
         const float4 c = pos4[i];
         float2 o0, o1;
-        const bool m0 = mover_resolve(P, radius, 2 * i, c.x, c.y, o0.x, o0.y);
-        const bool m1 = mover_resolve(P, radius, 2 * i + 1, c.z, c.w, o1.x, o1.y);
+        const bool m0 = mover_resolve<SURF>(P, radius, 2 * i, c.x, c.y, o0.x, o0.y);
+        const bool m1 = mover_resolve<SURF>(P, radius, 2 * i + 1, c.z, c.w, o1.x, o1.y);
         if (m0) pos[2 * i] = o0;
         if (m1) pos[2 * i + 1] = o1;
         moved += (uint32_t)__popcll(ballot64(m0)) + (uint32_t)__popcll(ballot64(m1));
@@ -139,7 +170,7 @@ __global__ __launch_bounds__(kStreamBlock) void k_movers_pass(float2 *__restrict
         const uint64_t i = n - 1;
         const float2 c = pos[i];
         float2 o;
-        if (mover_resolve(P, radius, i, c.x, c.y, o.x, o.y)) {
+        if (mover_resolve<SURF>(P, radius, i, c.x, c.y, o.x, o.y)) {
             pos[i] = o;
             moved += 1;
         }
@@ -147,8 +178,22 @@ __global__ __launch_bounds__(kStreamBlock) void k_movers_pass(float2 *__restrict
     if (lane_id() == 0 && moved) atomicAdd(P.pushed, (unsigned long long)moved);
 }
 
+__global__ __launch_bounds__(kStreamBlock) void k_movers_pass(float2 *__restrict__ pos, const float *__restrict__ radius,
+                                                              uint64_t n, MoverPassArgs P)
+{
+    movers_pass_body<false>(pos, radius, n, P);
+}
+
+// (pos and P.prev are different arrays; P.prev[i] is read and written by the lane that owns particle i alone)
+__global__ __launch_bounds__(kStreamBlock) void k_movers_pass_surface(float2 *__restrict__ pos, const float *__restrict__ radius,
+                                                                      uint64_t n, MoverPassArgs P)
+{
+    movers_pass_body<true>(pos, radius, n, P);
+}
+
 // Advances the B.k movers by B.dt and lists them: B.def 3 float4, B.pose 6 floats and B.rec 2 float4 per mover; B.masks
-// gx * gy * words words and B.summary gx * gy words, both zero when the kernel starts; *B.listed += the bits set
+// gx * gy * words words and B.summary gx * gy words, both zero when the kernel starts; *B.listed += the bits set.  B.old
+// (may be null): one float4 per mover, the capsule before the advance
 gpe_status launch_movers_build(gpe_ctx *c, const MoverBuildArgs &B)
 {
     if (B.k == 0) return GPE_OK;
@@ -158,11 +203,17 @@ gpe_status launch_movers_build(gpe_ctx *c, const MoverBuildArgs &B)
 }
 
 // One pass over pos[0, n) in place against the posed movers P.rec, found through P.masks / P.summary.  *P.pushed += the
-// particles moved
+// particles moved.  P.surf != nullptr: the surface form, P.k rows of P.surf and of P.old, P.prev[0, n) read and written
+// under a hit
 gpe_status launch_movers_pass(gpe_ctx *c, float2 *pos, const float *radius, uint64_t n, const MoverPassArgs &P)
 {
     if (n == 0 || P.k == 0) return GPE_OK;
-    hipLaunchKernelGGL(k_movers_pass, dim3(stream_grid((n + 1) >> 1)), dim3(kStreamBlock), 0, c->stream, pos, radius, n, P);
+    if (P.surf) {
+        if (!P.old || !P.prev) return fail(c, GPE_ERR_STATE, "launch_movers_pass: surfaces without the old capsules or prev");
+        hipLaunchKernelGGL(k_movers_pass_surface, dim3(stream_grid((n + 1) >> 1)), dim3(kStreamBlock), 0, c->stream, pos, radius, n, P);
+    } else {
+        hipLaunchKernelGGL(k_movers_pass, dim3(stream_grid((n + 1) >> 1)), dim3(kStreamBlock), 0, c->stream, pos, radius, n, P);
+    }
     GPE_HIP(c, hipGetLastError());
     return GPE_OK;
 }

@@ -84,6 +84,19 @@ def anchor_bonds(uids, points, rest_length=0.0, stiffness=1.0, max_length=0.0):
 MOVER_DTYPE = np.dtype([(name, np.uint32 if ctype is C.c_uint32 else np.float32) for name, ctype in L.GpeMover._fields_])
 MOVER_POSE_DTYPE = np.dtype([(name, np.float32) for name, _ in L.GpeMoverPose._fields_])
 assert MOVER_DTYPE.itemsize == C.sizeof(L.GpeMover) == 56 and MOVER_POSE_DTYPE.itemsize == C.sizeof(L.GpeMoverPose) == 24
+# set_surfaces / surfaces: the rows of gpe_surface (16 bytes each), one per static collider or per mover
+SURFACE_DTYPE = np.dtype([(name, np.uint32 if ctype is C.c_uint32 else np.float32) for name, ctype in L.GpeSurface._fields_])
+assert SURFACE_DTYPE.itemsize == C.sizeof(L.GpeSurface) == 16
+SURFACE_TARGETS = {"colliders": L.SURFACES_OF_COLLIDERS, "movers": L.SURFACES_OF_MOVERS}
+
+
+def surface_rows(k, restitution=0.0, friction=0.0, flags=0):
+    """k rows of SURFACE_DTYPE with the same material (each argument may also be an array of k)."""
+    rows = np.zeros(k, SURFACE_DTYPE)
+    rows["restitution"], rows["friction"], rows["flags"] = restitution, friction, flags
+    return rows
+
+
 # set_bodies / bodies: the rows of gpe_body (24 bytes each, the struct's layout)
 # set_fields / fields: the rows of gpe_field (56 bytes each, the struct's layout)
 FIELD_DTYPE = np.dtype([(name, np.uint32 if ctype is C.c_uint32 else np.float32) for name, ctype in L.GpeField._fields_])
@@ -659,6 +672,36 @@ class ParticleSystem:
         info = L.GpeMoversInfo(struct_size=C.sizeof(L.GpeMoversInfo))
         self.ctx.call("gpe_get_movers_info", C.byref(info))
         return {name: getattr(info, name) for name, _ in L.GpeMoversInfo._fields_ if name not in ("struct_size", "reserved")}
+
+    # Surface materials (not in the reference; include/gpe.h): bounce and friction per static collider or per mover.  While
+    # a set holds surfaces its pass also rewrites prev for the particles an obstacle touches.  Step state: save() keeps
+    # them; set_colliders / set_movers drop their target's.
+    @staticmethod
+    def _surface_target(target):
+        if target not in SURFACE_TARGETS:
+            raise ValueError("target must be 'colliders' or 'movers'")
+        return SURFACE_TARGETS[target]
+
+    def set_surfaces(self, target, rows):
+        """gpe_set_surfaces: one SURFACE_DTYPE row per collider (target "colliders") or per mover ("movers") of the set
+        held now; no rows clear them."""
+        t = self._surface_target(target)
+        rows = np.ascontiguousarray(rows, SURFACE_DTYPE).reshape(-1)
+        k = len(rows)
+        self.ctx.call("gpe_set_surfaces", t, rows.ctypes.data_as(C.POINTER(L.GpeSurface)) if k else None, k)
+
+    def surfaces(self, target):
+        """gpe_get_surfaces -> SURFACE_DTYPE[k]: the rows of the target's surfaces (k = 0: none)."""
+        t = self._surface_target(target)
+        k = C.c_uint64()
+        self.ctx.call("gpe_get_surfaces", t, None, 0, C.byref(k))
+        rows = np.zeros(max(k.value, 1), SURFACE_DTYPE)
+        self.ctx.call("gpe_get_surfaces", t, rows.ctypes.data_as(C.POINTER(L.GpeSurface)), k.value, C.byref(k))
+        return rows[:k.value]
+
+    def clear_surfaces(self, target):
+        """gpe_set_surfaces with k = 0."""
+        self.ctx.call("gpe_set_surfaces", self._surface_target(target), None, 0)
 
     # Distance bonds (not in the reference; include/gpe.h): particles tied to each other, or to a fixed point, by uid,
     # relaxed on the device after every update() / step of run(), before the colliders.  Step state: save() keeps them.
@@ -1363,6 +1406,19 @@ class State:
         """ParticleSystem.movers_info -> dict(k, passes, pushed, grid_x, grid_y, mask_words, listed)."""
         return self.particles.movers_info()
 
+    def set_surfaces(self, target, rows):
+        """ParticleSystem.set_surfaces: bounce and friction (rows of SURFACE_DTYPE) per collider ("colliders") or per
+        mover ("movers")."""
+        self.particles.set_surfaces(target, rows)
+
+    def surfaces(self, target):
+        """ParticleSystem.surfaces -> SURFACE_DTYPE[k]."""
+        return self.particles.surfaces(target)
+
+    def clear_surfaces(self, target):
+        """ParticleSystem.clear_surfaces."""
+        self.particles.clear_surfaces(target)
+
     def set_bonds(self, bonds, iterations=1):
         """ParticleSystem.set_bonds: distance bonds (rows of BOND_DTYPE) relaxed after every step, before the colliders."""
         self.particles.set_bonds(bonds, iterations)
@@ -1533,8 +1589,13 @@ class State:
         for the same reason.  Static colliders are step state: a set that is present is written (`colliders`), and so
         are distance bonds with their relaxation count and broken flags (`bonds`, `bond_iterations`, `bonds_broken`) and
         bodies with their members and broken flags (`bodies`, `bodies_broken`, `body_member_uid`, `body_member_rest`) and
-        force fields (`fields`) and moving colliders with their poses (`movers`, `mover_poses`)."""
+        force fields (`fields`) and moving colliders with their poses (`movers`, `mover_poses`), and the surfaces of
+        the two sets where present (`collider_surfaces`, `mover_surfaces`)."""
         extra = {}
+        for target in ("colliders", "movers"):
+            rows = self.surfaces(target)
+            if len(rows):
+                extra[target[:-1] + "_surfaces"] = rows
         movers = self.movers()
         if len(movers):
             extra.update(movers=movers, mover_poses=self.mover_poses())
@@ -1587,6 +1648,8 @@ class State:
                 st.ctx.call("gpe_grid_set_max_radius", float(d["grid_max_radius"][0]))
             if "colliders" in d.files:
                 st.set_colliders(d["colliders"])
+            if "collider_surfaces" in d.files:                     # (after their set)
+                st.set_surfaces("colliders", d["collider_surfaces"].astype(SURFACE_DTYPE))
             if "bonds" in d.files:                                 # (after the uids they name; a broken bond starts broken)
                 rows = d["bonds"].astype(BOND_DTYPE)
                 rows["flags"] |= np.where(d["bonds_broken"], L.BOND_BROKEN, 0).astype(np.uint32)
@@ -1600,6 +1663,8 @@ class State:
             if "movers" in d.files:
                 st.set_movers(d["movers"].astype(MOVER_DTYPE))
                 st.set_mover_poses(d["mover_poses"].astype(MOVER_POSE_DTYPE))
+            if "mover_surfaces" in d.files:                        # (after their set and its poses)
+                st.set_surfaces("movers", d["mover_surfaces"].astype(SURFACE_DTYPE))
             return st
 
     def close(self):

@@ -520,6 +520,23 @@ class ParticleSystem {
         ctx_->call(gpe_get_movers_info(ctx_->raw(), &info));
         return info;
     }
+    // not in the reference: surface materials (include/gpe.h) -- bounce and friction, one row per static collider
+    // (GPE_SURFACES_OF_COLLIDERS) or per mover (GPE_SURFACES_OF_MOVERS) of the set held now.  While a set holds surfaces
+    // its pass also rewrites prev for the particles an obstacle touches.  set_colliders / set_movers drop their
+    // target's surfaces.  Step state: a snapshot keeps surfaces(target) and restores it after the set and the poses.
+    void set_surfaces(uint32_t target, const std::vector<gpe_surface> &rows)
+    {
+        ctx_->call(gpe_set_surfaces(ctx_->raw(), target, rows.empty() ? nullptr : rows.data(), rows.size()));
+    }
+    std::vector<gpe_surface> surfaces(uint32_t target) const
+    {
+        uint64_t k = 0;
+        ctx_->call(gpe_get_surfaces(ctx_->raw(), target, nullptr, 0, &k));
+        std::vector<gpe_surface> out(k);
+        ctx_->call(gpe_get_surfaces(ctx_->raw(), target, out.empty() ? nullptr : out.data(), k, &k));
+        return out;
+    }
+    void clear_surfaces(uint32_t target) { ctx_->call(gpe_set_surfaces(ctx_->raw(), target, nullptr, 0)); }
     // not in the reference: every particle in a circle / box, or the one under a point (include/gpe.h), ascending
     // storage index; uid stays empty while uids are off.  pick() returns no rows when no disc contains the point.
     struct QueryResult {

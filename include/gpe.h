@@ -481,6 +481,62 @@ gpe_status gpe_set_mover_poses(gpe_ctx *ctx, const gpe_mover_pose *poses, uint64
 gpe_status gpe_apply_movers(gpe_ctx *ctx, float dt);                       /* advance + one pass now, stream-ordered, no sync */
 gpe_status gpe_get_movers_info(gpe_ctx *ctx, gpe_movers_info *info);       /* synchronises (reads the device counters) */
 
+/* ---- surface materials (not in the reference) ----------------------------------------------------------------------
+ * Bounce and friction, per obstacle: a ball that rebounds from the floor, a particle that slides to a halt, a shelf
+ * things stay on, a drum or a plate that drags its load along.  A surface is one row per static collider or per mover:
+ * restitution e in [0, 1], friction mu >= 0, flags.  Without surfaces the two passes write pos only (above).  While a
+ * set holds surfaces its pass runs in a second form (csrc/k_colliders.hip, csrc/k_movers.hip: the same lookup, the same
+ * winner) that also reads and writes prev for the particles an obstacle touches -- and for no others: a particle
+ * nothing touches costs what it costs without surfaces.  gpe_step, gpe_run, gpe_apply_colliders and gpe_apply_movers
+ * all pick it up; the order of the passes stays.  A context that sets no surface launches, allocates and computes
+ * exactly what it does without this section.
+ *  - The rule (csrc/k_surface.h is the one definition).  The acting obstacle is chosen exactly as above: the deepest
+ *    penetration, the lowest index on a tie, every obstacle judged from the position the pass starts with.  Inputs: that
+ *    position p, the previous position prev, the radius r, the normal n and the depth of the touch, its clamped
+ *    parameter u, and the wall's displacement w at the contact over this step.  IEEE binary32, one rounding per
+ *    operation, left to right, no FMA, `/` and sqrtf correctly rounded:
+ *      q   = (px + nx*depth, py + ny*depth)                      the plain pass's push, the same bits
+ *      v   = p - prev;   rel = v - w
+ *      vn  = relx*nx + rely*ny
+ *      t   = (relx - vn*nx, rely - vn*ny)                        the tangential part, t0 = t
+ *      on  = (vn < 0) ? (-e)*vn : vn                             approaching: reflected and damped; separating: kept
+ *      jn  = on - vn                                             the normal velocity change, >= 0
+ *      tl  = sqrtf(tx*tx + ty*ty);   s = mu*jn
+ *      if s < tl:  k = (tl - s)/tl;  t = (tx*k, ty*k)            sliding: Coulomb, the change bounded by mu*jn
+ *      else:       t = (0, 0)                                    sticking
+ *      out = ((wx + on*nx) + tx, (wy + on*ny) + ty)              the velocity the particle leaves with
+ *      pos' = clamp(q - (t0 - t))                                K12's clamp as in the plain pass
+ *      prev' = pos' - out
+ *    The tangential velocity that friction removes is taken out of the position too; without that a particle that
+ *    sticks on a slope creeps down by g*dt^2*sin every step.  With mu = 0, t0 - t is +0 and pos' carries the bits of
+ *    the plain pass.  A particle nothing touches keeps every bit of pos and prev.
+ *  - The wall's displacement.  A static collider: w = (0, 0).  A mover: what the contact point moved in this step's
+ *    advance.  The posed capsule before the advance is (a0, b0), after it (a1, b1), the touch is taken against
+ *    (a1, b1):  wa = a1 - a0; wb = b1 - b0; w = wa + u*(wb - wa)  per component.  The old capsule is a function of the
+ *    state (q0, q1) alone: gpe_get_mover_poses / gpe_set_mover_poses carry all a host needs to continue a run.
+ *  - Two escapes keep the bits of the plain rule, pos pushed and prev untouched: a row whose flags has
+ *    GPE_SURFACE_PLAIN (a host gives a material to some obstacles only), and a particle whose p - prev is not finite
+ *    in either component.
+ *  - What a surface is not.  It has no effect on particle-particle contacts: a pile above its bottom layer is as
+ *    slippery as before.  There is no rolling and no spin.  A corner is still resolved by the deepest obstacle, over
+ *    two steps; there is still no swept test.  Friction sees the normal velocity change of this pass only: a particle
+ *    pressed on a wall by its neighbours and not by its own velocity feels little of it.
+ *  - gpe_set_surfaces: row j belongs to collider j (GPE_SURFACES_OF_COLLIDERS) or mover j (GPE_SURFACES_OF_MOVERS) of
+ *    the set held at the call; k must equal that set's size; k == 0 clears the surfaces and frees their buffer.  It
+ *    synchronises like gpe_set_colliders.  gpe_set_colliders and gpe_set_movers drop their target's surfaces (k == 0
+ *    included): a new set gets new surfaces.  Surfaces are step state: they survive everything their set survives.
+ *    gpe_get_surfaces delivers the first min(k, capacity) rows into out (may be NULL with capacity 0) and the number
+ *    set into *k (0: none); -0.0 reads back as +0.
+ *  - Errors (the previous surfaces stay untouched): a NULL ctx, NULL rows with k > 0, an unknown target, a k that is
+ *    not 0 and not the set's size, a restitution that is NaN or outside [0, 1], a friction that is NaN, infinite or
+ *    negative, an unknown flag, a non-zero reserved; for gpe_get_surfaces a NULL k or NULL out with a capacity:
+ *    GPE_ERR_INVALID_ARG.  gpe_set_surfaces with k > 0 on a sharded context: GPE_ERR_UNSUPPORTED. */
+enum { GPE_SURFACES_OF_COLLIDERS = 0, GPE_SURFACES_OF_MOVERS = 1 };
+enum { GPE_SURFACE_PLAIN = 1u };
+typedef struct gpe_surface { float restitution, friction; uint32_t flags, reserved; } gpe_surface;   /* 16 bytes */
+gpe_status gpe_set_surfaces(gpe_ctx *ctx, uint32_t target, const gpe_surface *rows, uint64_t k);
+gpe_status gpe_get_surfaces(const gpe_ctx *ctx, uint32_t target, gpe_surface *out, uint64_t capacity, uint64_t *k);
+
 /* ---- distance bonds (not in the reference) ------------------------------------------------------------------------
  * Ties between particles: a rope, a chain, a cloth, a soft body, a pinned object, a sheet that tears.  A bond holds two
  * particles, named by uid (gpe_enable_uids must be on), at a rest length; an anchor bond (GPE_BOND_ANCHOR) holds one
