@@ -1300,6 +1300,25 @@ __device__ __forceinline__ int neighbour_offset(const int k)
     return (int)(int8_t)(uint8_t)(packed >> (8 * k));
 }
 
+// a * B + c for a, c < 2^24 and a small constant B, as the one full-rate v_mad_u32_u24.  (Written out: __umul24 does not
+// survive where the compiler has proved its operands small -- it drops the 24-bit form for a plain multiply, and the
+// instruction selector, which does not know the range any more, emits the quarter-rate v_mul_lo_u32.)
+template <int B>
+__device__ __forceinline__ uint32_t mad_u24(const uint32_t a, const uint32_t c)
+{
+    static_assert(B >= 0 && B <= 64, "an inline constant");
+    uint32_t r;
+    asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(r) : "v"(a), "n"(B), "v"(c));
+    return r;
+}
+
+// The wave's first thread, as a scalar: what a wave compares to skip, by a scalar branch, a round in which none of its
+// lanes has work -- an idle wave then issues nothing, where lane predicates alone leave it the whole straight-line body.
+__device__ __forceinline__ uint32_t wave_first_thread(const int tid)
+{
+    return (uint32_t)__builtin_amdgcn_readfirstlane(tid & ~63);
+}
+
 // Consecutive slots for the particles a wave keeps (`mask`: the lanes that keep theirs, one mask per round of the gather):
 // one atomic on the counter word per wave, by lane 0 -- the order of the slots is free.  A slot at or beyond `cap` is not
 // kept; the counter then tells the tile that it ran over.  (Both tile forms, gather and list intake: the kernels this
@@ -1369,20 +1388,22 @@ __device__ __forceinline__ void file_dropped(L &S, const uint32_t s, const float
 // The tile's own particles (S.is_own) and, when K12 is fused into the write-back, their previous positions, into one
 // register per round of NT slots.  Branch-free like the gather of P1: every lane loads -- a lane without a particle of
 // the tile reads element 0 -- and the loads of all rounds are issued before anything uses one of them, so they are in
-// flight together and nothing waits for them before write_own_back.  Rounds from QSKIP on are skipped by a scalar test
-// when the window holds no slot of theirs (PS >= 1).
+// flight together and nothing waits for them before write_own_back.  Rounds from QSKIP on are skipped by a scalar test,
+// wave by wave, when the window holds no slot for the wave in them (PS >= 1): a wave whose slots of the round all lie
+// beyond PS issues nothing for it -- with ~575 kept particles on 512 threads the second round is wave 0's alone.
 template <bool ORD, int NT, int QSKIP, class L, int QOWN>
 __device__ __forceinline__ void fetch_own(const L &S, const CollideArgs &A, const int tid, const uint32_t PS, const uint32_t n_owned,
                                           uint32_t (&own_id)[QOWN], float2 (&own_prev)[QOWN])
 {
     static_assert(!ORD || L::kLid, "order-key windows keep the local indices");
     uint32_t fetch[QOWN];
+    const uint32_t wave_s = wave_first_thread(tid);
 #pragma unroll
     for (int q = 0; q < QOWN; ++q) {
         const uint32_t s = (uint32_t)tid + (uint32_t)q * NT;
         own_id[q] = 0xFFFFFFFFu;
         fetch[q] = 0u;
-        if (q >= QSKIP && PS <= (uint32_t)q * NT) continue;            // (scalar)
+        if (q >= QSKIP && PS <= wave_s + (uint32_t)q * NT) continue;   // (scalar)
         const uint32_t sc = min(s, PS - 1u);
         const bool own = s < PS && S.is_own(sc);
         uint32_t id = S.id[sc];
@@ -1394,7 +1415,7 @@ __device__ __forceinline__ void fetch_own(const L &S, const CollideArgs &A, cons
 #pragma unroll
     for (int q = 0; q < QOWN; ++q) {
         own_prev[q] = make_float2(0.f, 0.f);
-        if (q >= QSKIP && PS <= (uint32_t)q * NT) continue;
+        if (q >= QSKIP && PS <= wave_s + (uint32_t)q * NT) continue;
 #ifdef GPE_DBG_SKIP
         if (GPE_DBG_SKIP & 32) continue;                               // diagnostic builds: phase cost by omission (results wrong)
 #endif
@@ -1409,12 +1430,13 @@ __device__ __forceinline__ void write_own_back(const L &S, const CollideArgs &A,
                                                const bool packs, const uint32_t (&own_id)[QOWN], const float2 (&own_prev)[QOWN],
                                                const UniformRadii &U)
 {
+    const uint32_t wave_s = wave_first_thread(tid);
 #pragma unroll
     for (int q = 0; q < QOWN; ++q) {
 #ifdef GPE_DBG_SKIP
         if (GPE_DBG_SKIP & 32) continue;
 #endif
-        if (q >= QSKIP && PS <= (uint32_t)q * NT) continue;            // (scalar, as where own_id was filled)
+        if (q >= QSKIP && PS <= wave_s + (uint32_t)q * NT) continue;   // (scalar, the test that filled own_id)
         const uint32_t id = own_id[q];
         const bool have = id != 0xFFFFFFFFu;
         const uint32_t s = min((uint32_t)tid + (uint32_t)q * NT, (uint32_t)L::kSlots - 1u);
@@ -1812,6 +1834,7 @@ __device__ __forceinline__ bool process_tile(L &S, const CollideArgs &A, const i
         static_assert(kConeLeft % 2 == 0 && kConeDown % 2 == 0 && T % 2 == 0, "groups start at even cells");
         static_assert(HX > kConeLeft && HY > kConeDown && L::HXR > kConeRight && L::HYR > kConeUp, "zones inside the window");
         for (int base = 0; base < QC; base += kNatThreads) {
+            if (base + (int)wave_first_thread(tid) >= QC) continue;    // (scalar) no colour group for this wave: see process_tile_direct
             const int i = base + tid;
             const int hx = 2 * (i % ZW) + (HX - kConeLeft), hy = 2 * (i / ZW) + (HY - kConeDown);
             int lc[4];
@@ -2205,13 +2228,27 @@ struct TileDirect {
     // member slots a zone cell owns: six; an order-key (sharded) window keeps a local index per particle as well and
     // pays for it with the sixth slot (its cells of six members go to the side list and a wave, like cells of seven)
     static constexpr int kMemSlots = LID ? kDirectSlots - 1 : kDirectSlots;
-    uint32_t cntw[(NZ + 1) / 2];   // members per zone cell, two 16-bit counters per word (LDS atomics are 32 bit)
+    // members per zone cell.  Two 16-bit counters per word (LDS atomics are 32 bit) cost every membership a shift by the
+    // cell's parity on the way in and a shift and a mask on the way out; the uniform windows have no radius array and
+    // spend 2 NZ of the bytes that frees on a word per cell -- the general and the order-key windows have no such room
+    // (the general 32x32 window is 40 928 B of the 40 960 that four workgroups per CU leave each)
+    static constexpr bool kWordCounters = UNI;
+    static constexpr int kCntWords = kWordCounters ? NZ : (NZ + 1) / 2;
+    static_assert(!kWordCounters || NZ % 4 == 0, "cleared four words at a time");
+    alignas(kWordCounters ? 16 : 4) uint32_t cntw[kCntWords];
     __device__ __forceinline__ uint32_t cnt_inc(int i)                // returns the value before the add
     {
-        const uint32_t sh = (uint32_t)(i & 1) * 16u;
-        return (atomicAdd(&cntw[i >> 1], 1u << sh) >> sh) & 0xFFFFu;
+        if constexpr (kWordCounters) return atomicAdd(&cntw[i], 1u);
+        else {
+            const uint32_t sh = (uint32_t)(i & 1) * 16u;
+            return (atomicAdd(&cntw[i >> 1], 1u << sh) >> sh) & 0xFFFFu;
+        }
     }
-    __device__ __forceinline__ uint32_t cnt_get(int i) const { return (cntw[i >> 1] >> ((uint32_t)(i & 1) * 16u)) & 0xFFFFu; }
+    __device__ __forceinline__ uint32_t cnt_get(int i) const
+    {
+        if constexpr (kWordCounters) return cntw[i];
+        else return (cntw[i >> 1] >> ((uint32_t)(i & 1) * 16u)) & 0xFFFFu;
+    }
     // members: kDirectSlots per zone cell, then 64 per wave for the cells gathered from the side list.  (Named like
     // TileLds' member array: the resolvers index S.mem[b + k].)
     uint16_t mem[kMemSlots * NZ + NW * 64];
@@ -2272,7 +2309,11 @@ __device__ __forceinline__ bool process_tile_direct(L &S, const CollideArgs &A, 
     }
 
     // ---- P0: clear the counters, look the region's blocks up, slot -> block map ------------------------------------
-    for (int i = tid; i < (NZ + 1) / 2; i += NT) S.cntw[i] = 0;
+    if constexpr (L::kWordCounters) {
+        for (int i = tid; i < NZ / 4; i += NT) reinterpret_cast<uint4 *>(S.cntw)[i] = make_uint4(0u, 0u, 0u, 0u);
+    } else {
+        for (int i = tid; i < L::kCntWords; i += NT) S.cntw[i] = 0;
+    }
     if (tid < 12) S.lcnt[tid] = 0;
     const bool stale = __builtin_amdgcn_readfirstlane((int)W.fresh) == 0;
     if constexpr (kRoster && HINTS) {
@@ -2336,12 +2377,13 @@ __device__ __forceinline__ bool process_tile_direct(L &S, const CollideArgs &A, 
         if (GPE_DBG_SKIP & 4) return;
 #endif
         if ((unsigned)zx < (unsigned)ZX && (unsigned)zy < (unsigned)ZY) {
-            const int zc = zy * ZX + zx;
-            const uint32_t k = S.cnt_inc(zc);
-            if (k < (uint32_t)MS) S.mem[zc * MS + (int)k] = (uint16_t)s;
+            // (zc < 4096: 24-bit multiply-adds, full rate, where the 32-bit multiply takes four issue slots)
+            const uint32_t zc = mad_u24<ZX>((uint32_t)zy, (uint32_t)zx);
+            const uint32_t k = S.cnt_inc((int)zc);
+            if (k < (uint32_t)MS) S.mem[mad_u24<MS>(zc, k)] = (uint16_t)s;
             else {
                 const uint32_t e = atomicAdd(&S.misc[4], 1u);
-                if (e < (uint32_t)L::kBig) S.big[e] = ((uint32_t)zc << 16) | s;
+                if (e < (uint32_t)L::kBig) S.big[e] = (zc << 16) | s;
             }
         }
     };
@@ -2372,61 +2414,79 @@ __device__ __forceinline__ bool process_tile_direct(L &S, const CollideArgs &A, 
         uint32_t pid[QP], blk[QP], cc[QP];
         float2 pp[QP];
         float pr[QP];
-        if (listed) {                                                  // (scalar)
-#pragma unroll
-            for (int q = 0; q < QP; ++q) {
-                const uint32_t sr = s0 + (uint32_t)tid + (uint32_t)q * NT;
-                blk[q] = 0u;
-                uint32_t v = first_ids[q];
-                if (s0 != 0) v = A.roster_ids[roster_base + min(sr, P - 1u)];
-                pid[q] = sr < P ? v : 0u;                              // (what lies behind the roster's end is not an id)
-            }
-        } else {
-#pragma unroll
-        for (int q = 0; q < QP; ++q) {                                 // branch-free, all loads in flight: see process_tile
-            const uint32_t s = min(s0 + (uint32_t)tid + (uint32_t)q * NT, P - 1u);
-            blk[q] = S.sblk[s];
-            pid[q] = A.sorted_ids[S.bstart[blk[q]] + (s - S.boff[blk[q]])];
-        }
-        if (record) {
-#pragma unroll
-            for (int q = 0; q < QP; ++q) {
-                const uint32_t sr = s0 + (uint32_t)tid + (uint32_t)q * NT;
-                if (sr < P) A.roster_ids[roster_base + sr] = pid[q];
-            }
-        }
-        }
-#pragma unroll
-        for (int q = 0; q < QP; ++q) {
-            pp[q] = A.pos_in[pid[q]];
-            if constexpr (L::kUniform) pr[q] = 0.f; else pr[q] = A.radius[pid[q]];
-            cc[q] = A.codes[pid[q]];
-        }
-        uint32_t lidq[QP];
-#pragma unroll
-        for (int q = 0; q < QP; ++q) lidq[q] = pid[q];
-        if constexpr (ORD) {
-#pragma unroll
-            for (int q = 0; q < QP; ++q) pid[q] = A.order_keys[pid[q]];
-        }
-        uint32_t ph[QP];                                               // (issued here: in flight under the keep votes)
-#pragma unroll
-        for (int q = 0; q < QP; ++q) ph[q] = phantoms_of(cc[q]);
+        uint32_t lidq[QP], ph[QP];
         int lxq[QP], lyq[QP];
         bool keep[QP];
         uint32_t slot[QP];
         uint64_t mq[QP];
 #pragma unroll
         for (int q = 0; q < QP; ++q) {
-            const uint32_t s = s0 + (uint32_t)tid + (uint32_t)q * NT;
-            lxq[q] = code_window_x(cc[q], ox);
-            lyq[q] = code_window_y(cc[q], oy);
-            // (voted comparison by comparison: see pair_response)
-            mq[q] = ballot64(s < P) & ballot64(lxq[q] < RWX) & ballot64(lyq[q] < RWY) & ballot64((cc[q] & straggler_bit) == 0u);
-            // (an order-key window: the kept table -- or the roster written from it -- may still list indices the owned
-            // range has shrunk below: those particles are ghosts now, or gone; they come through the ghost list, or not at all)
-            if constexpr (ORD) mq[q] &= ballot64(lidq[q] < n_owned);
-            keep[q] = lanes_of(mq[q]);
+            pid[q] = 0u; blk[q] = 0u; cc[q] = 0u; pr[q] = 0.f; lidq[q] = 0u; ph[q] = 0u;
+            pp[q] = make_float2(0.f, 0.f);
+            lxq[q] = 0; lyq[q] = 0; mq[q] = 0; keep[q] = false;
+        }
+        // the first NQ slots of the batch, from the ids to the keep votes: branch-free, each stage's loads issued together
+        auto stage = [&](auto nq) {
+            constexpr int NQ = decltype(nq)::value;
+            if (listed) {                                              // (scalar)
+#pragma unroll
+                for (int q = 0; q < NQ; ++q) {
+                    const uint32_t sr = s0 + (uint32_t)tid + (uint32_t)q * NT;
+                    uint32_t v = first_ids[q];
+                    if (s0 != 0) v = A.roster_ids[roster_base + min(sr, P - 1u)];
+                    pid[q] = sr < P ? v : 0u;                          // (what lies behind the roster's end is not an id)
+                }
+            } else {
+#pragma unroll
+                for (int q = 0; q < NQ; ++q) {                         // branch-free, all loads in flight: see process_tile
+                    const uint32_t s = min(s0 + (uint32_t)tid + (uint32_t)q * NT, P - 1u);
+                    blk[q] = S.sblk[s];
+                    pid[q] = A.sorted_ids[S.bstart[blk[q]] + (s - S.boff[blk[q]])];
+                }
+                if (record) {
+#pragma unroll
+                    for (int q = 0; q < NQ; ++q) {
+                        const uint32_t sr = s0 + (uint32_t)tid + (uint32_t)q * NT;
+                        if (sr < P) A.roster_ids[roster_base + sr] = pid[q];
+                    }
+                }
+            }
+#pragma unroll
+            for (int q = 0; q < NQ; ++q) {
+                pp[q] = A.pos_in[pid[q]];
+                if constexpr (L::kUniform) pr[q] = 0.f; else pr[q] = A.radius[pid[q]];
+                cc[q] = A.codes[pid[q]];
+            }
+#pragma unroll
+            for (int q = 0; q < NQ; ++q) lidq[q] = pid[q];
+            if constexpr (ORD) {
+#pragma unroll
+                for (int q = 0; q < NQ; ++q) pid[q] = A.order_keys[pid[q]];
+            }
+#pragma unroll
+            for (int q = 0; q < NQ; ++q) ph[q] = phantoms_of(cc[q]);   // (issued here: in flight under the keep votes)
+#pragma unroll
+            for (int q = 0; q < NQ; ++q) {
+                const uint32_t s = s0 + (uint32_t)tid + (uint32_t)q * NT;
+                lxq[q] = code_window_x(cc[q], ox);
+                lyq[q] = code_window_y(cc[q], oy);
+                // (voted comparison by comparison: see pair_response)
+                mq[q] = ballot64(s < P) & ballot64(lxq[q] < RWX) & ballot64(lyq[q] < RWY) & ballot64((cc[q] & straggler_bit) == 0u);
+                // (an order-key window: the kept table -- or the roster written from it -- may still list indices the owned
+                // range has shrunk below: those particles are ghosts now, or gone; they come through the ghost list, or not at all)
+                if constexpr (ORD) mq[q] &= ballot64(lidq[q] < n_owned);
+                keep[q] = lanes_of(mq[q]);
+            }
+        };
+        // (scalar) the slots of the batch that lie wholly beyond P for this wave -- ~873 looked-up ids on 512 threads: the
+        // second slot of waves 6 and 7 -- are not loaded, decoded or voted on: nothing of them is kept (mq = 0).  One
+        // copy of the stages per number of slots, so that the slots that run still issue each stage's loads together.
+        const uint32_t wave_s0 = s0 + wave_first_thread(tid);
+        if constexpr (QP == 2) {
+            if (wave_s0 + (uint32_t)NT < P) stage(std::integral_constant<int, 2>());
+            else if (wave_s0 < P) stage(std::integral_constant<int, 1>());
+        } else {
+            if (wave_s0 < P) stage(std::integral_constant<int, QP>());
         }
         take_slots(&S.misc[3], lane, (uint32_t)L::kSlots, mq, slot, keep);   // (over capacity: handed on below)
 #pragma unroll
@@ -2487,6 +2547,9 @@ __device__ __forceinline__ bool process_tile_direct(L &S, const CollideArgs &A, 
         constexpr int ZW = ZX / 2, ZH = ZY / 2, QC = ZW * ZH;
         static_assert(QC == QZ && NZ < 4096, "list entries: 12 bits of cell");
         for (int base = 0; base < QC; base += NT) {
+            // (scalar) a wave without a colour group in this round -- QC = 360 groups on 512 threads: waves 6 and 7 -- goes
+            // on to the barrier: its masks and their eight counts would all be 0, it adds to no counter and stores nothing
+            if (base + (int)wave_first_thread(tid) >= QC) continue;
             const int i = base + tid;
             const int gx2 = 2 * (i % ZW), gy2 = 2 * (i / ZW);          // zone coordinates of the group's first cell
             int zc[4];
@@ -2494,9 +2557,19 @@ __device__ __forceinline__ bool process_tile_direct(L &S, const CollideArgs &A, 
             static_assert(ZX % 2 == 0, "the two cells of a group's row share a counter word");
             {
                 const int z0 = gy2 * ZX + gx2;                         // even
-                const uint32_t w0 = (i < QC) ? S.cntw[z0 >> 1] : 0u, w1 = (i < QC) ? S.cntw[(z0 + ZX) >> 1] : 0u;
                 zc[0] = z0; zc[1] = z0 + 1; zc[2] = z0 + ZX; zc[3] = z0 + ZX + 1;
-                cnt[0] = w0 & 0xFFFFu; cnt[1] = w0 >> 16; cnt[2] = w1 & 0xFFFFu; cnt[3] = w1 >> 16;
+                if constexpr (L::kWordCounters) {
+                    // a row's two counters are one aligned 64-bit read
+                    uint2 r0 = make_uint2(0u, 0u), r1 = make_uint2(0u, 0u);
+                    if (i < QC) {
+                        r0 = *reinterpret_cast<const uint2 *>(&S.cntw[z0]);
+                        r1 = *reinterpret_cast<const uint2 *>(&S.cntw[z0 + ZX]);
+                    }
+                    cnt[0] = r0.x; cnt[1] = r0.y; cnt[2] = r1.x; cnt[3] = r1.y;
+                } else {
+                    const uint32_t w0 = (i < QC) ? S.cntw[z0 >> 1] : 0u, w1 = (i < QC) ? S.cntw[(z0 + ZX) >> 1] : 0u;
+                    cnt[0] = w0 & 0xFFFFu; cnt[1] = w0 >> 16; cnt[2] = w1 & 0xFFFFu; cnt[3] = w1 >> 16;
+                }
             }
             // (the classes as lane masks, voted comparison by comparison: see pair_response)
             uint64_t ms[4], mg[4];
@@ -2566,13 +2639,13 @@ __device__ __forceinline__ bool process_tile_direct(L &S, const CollideArgs &A, 
 #endif
             if (i < group_lanes) {
                 const uint32_t en = S.list[k * QZ + (QZ - 1) - (i / kGroupLanes)];
-                resolve_group<MS>(S, (en & 0xFFFu) * MS, (en >> 12) + kGroupMin, (int)(i % kGroupLanes), A.stiffness, U);
+                resolve_group<MS>(S, __umul24(en & 0xFFFu, (uint32_t)MS), (en >> 12) + kGroupMin, (int)(i % kGroupLanes), A.stiffness, U);
             } else if (i >= single_base && (i & ~63u) < work) {         // (whole waves: the walk uses ballots)
                 const bool on = i < work;
                 uint32_t b = 0, n = 0;
                 if (on) {
                     const uint32_t en = S.list[k * QZ + (i - single_base)];
-                    b = (en & 0xFFFu) * MS; n = 2u + (en >> 12);
+                    b = __umul24(en & 0xFFFu, (uint32_t)MS); n = 2u + (en >> 12);
                 }
                 resolve_small_cells(S, on, b, n, A.stiffness, U);
             }
@@ -2583,7 +2656,7 @@ __device__ __forceinline__ bool process_tile_direct(L &S, const CollideArgs &A, 
             const uint32_t zc = S.wlist[k * L::WC + i];
             const uint32_t n = S.cnt_get((int)zc);
             const uint32_t wb = (uint32_t)(MS * NZ) + (uint32_t)(tid >> 6) * 64u;
-            if (lane < MS) S.mem[wb + lane] = S.mem[zc * MS + lane];
+            if (lane < MS) S.mem[wb + lane] = S.mem[__umul24(zc, (uint32_t)MS) + (uint32_t)lane];
             uint32_t filled = MS;
             for (uint32_t e0 = 0; e0 < n_big; e0 += 64u) {
                 const uint32_t e = e0 + (uint32_t)lane;
@@ -2666,6 +2739,11 @@ uint32_t dense_launch_grid(uint32_t tiles_x, uint32_t tiles_y, uint32_t band_til
 #ifndef GPE_CAP_HALF_FRONT_ORD
 #define GPE_CAP_HALF_FRONT_ORD 1192             // ... of an order-key (sharded) run: 21 bytes per particle in 40 748
 #endif
+// The uniform windows carry a word per zone-cell counter (TileDirect::kWordCounters): the tile still leaves four workgroups
+// a CU their LDS, the half of the half-tile launch three, as before.
+static_assert(sizeof(TileDirect<32, 32, GPE_CAP_DIRECT, false, 512, true>) <= 40960, "uniform tile: four workgroups per CU");
+static_assert(sizeof(TileDirect<32, 16, GPE_CAP_HALF, false, 512, true>) <= 163840 / 3, "uniform half: three workgroups per CU");
+static_assert(sizeof(TileDirect<32, 16, GPE_CAP_HALF_FRONT, false, 512, true>) <= 40960, "uniform half of a hinted tile: in the tile's LDS");
 // Registers a tile that ran over for the front workgroups of the next step's dense launch (kCtlHints).
 __device__ __forceinline__ void hint_tile(const CollideArgs &A, const int tx, const int ty, const uint32_t age = 0u)
 {
