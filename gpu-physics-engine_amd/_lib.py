@@ -62,6 +62,7 @@ MOVERS_MAX = 1024
 MOVER_LINEAR, MOVER_ROTATE = 0, 1
 SURFACES_OF_COLLIDERS, SURFACES_OF_MOVERS = 0, 1
 SURFACE_PLAIN = 1
+SWEEP_OFF, SWEEP_ON = 0, 1
 EDIT_BY_INDEX, EDIT_BY_UID = 0, 1
 CLUSTER_BY_INDEX, CLUSTER_BY_UID = 0, 1
 VEL_ADD, VEL_SET, VEL_SCALE = 0, 1, 2
@@ -240,6 +241,13 @@ class GpeCollidersInfo(C.Structure):
                 ("grid_x", C.c_uint32), ("grid_y", C.c_uint32), ("list_entries", C.c_uint64)]
 
 
+class GpeSweepInfo(C.Structure):
+    """gpe_sweep_info: in struct_size; out the sweep mode of the static colliders' pass, the swept passes run since the
+    last gpe_set_collider_sweep, the particles swept (winner at 0 < t < 1) and stopped by them.  32 bytes."""
+    _fields_ = [("struct_size", C.c_uint32), ("mode", C.c_uint32), ("passes", C.c_uint64), ("swept", C.c_uint64),
+                ("stopped", C.c_uint64)]
+
+
 class GpeBond(C.Structure):
     """gpe_bond: particle uid_a tied to particle uid_b, or (BOND_ANCHOR, uid_b = UID_ABSENT) to the point (anchor_x,
     anchor_y), at rest_length.  32 bytes."""
@@ -376,6 +384,9 @@ SYMBOLS = [
     ("gpe_get_colliders", _I32, [_VP, C.POINTER(GpeCollider), _U64, C.POINTER(_U64)]),
     ("gpe_apply_colliders", _I32, [_VP]),
     ("gpe_get_colliders_info", _I32, [_VP, C.POINTER(GpeCollidersInfo)]),
+    ("gpe_set_collider_sweep", _I32, [_VP, _U32]),
+    ("gpe_get_collider_sweep", _I32, [_VP, C.POINTER(_U32)]),
+    ("gpe_get_sweep_info", _I32, [_VP, C.POINTER(GpeSweepInfo)]),
     ("gpe_set_bonds", _I32, [_VP, C.POINTER(GpeBond), _U64, C.c_uint32]),
     ("gpe_get_bonds", _I32, [_VP, C.POINTER(GpeBond), C.POINTER(C.c_uint8), _U64, C.POINTER(_U64)]),
     ("gpe_apply_bonds", _I32, [_VP]),

@@ -999,6 +999,7 @@ gpe_status gpe_destroy(gpe_ctx *c)
     free_particle_buffers(c);
     observers_release(c);
     colliders_release(c);
+    sweep_release(c);
     bonds_release(c);
     bodies_release(c);
     fields_release(c);

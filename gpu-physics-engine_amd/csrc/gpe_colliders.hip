@@ -89,6 +89,11 @@ static gpe_status colliders_pass(gpe_ctx *c, const char *who)
     if (S.set.empty() || c->n == 0 || !c->pos) return GPE_OK;
     GPE_TRY(colliders_grid_ready(c, who));
     Scope s(c, "Colliders");
+    if (c->sweep.mode == GPE_SWEEP_ON) {
+        GPE_TRY(sweep_pass(c));
+        S.passes += 1;
+        return GPE_OK;
+    }
     GPE_TRY(launch_colliders_pass(c, c->pos, c->radius, c->n, S.cell_start, S.items, S.rec, (uint32_t)S.set.size(), S.view,
                                   S.pushed, S.surf, c->prev));
     S.passes += 1;

@@ -435,6 +435,14 @@ struct ColliderState {
     uint64_t entries = 0;
 };
 
+// the sweep of the static colliders (gpe_set_collider_sweep; gpe_sweep.hip, k_sweep.hip, k_sweep.h).  A mode of their
+// pass, like gravity: it outlives gpe_set_colliders and gpe_set_surfaces
+struct SweepState {
+    uint32_t mode = 0;                           // GPE_SWEEP_OFF / GPE_SWEEP_ON
+    uint64_t passes = 0;                         // swept passes enqueued since the last gpe_set_collider_sweep
+    unsigned long long *counts = nullptr;        // two words: particles swept, particles stopped, since then (null: never on)
+};
+
 // the distance bonds (gpe_set_bonds; gpe_bonds.hip, k_bonds.hip, bond_graph.h).  Step state: gpe_step / gpe_run relax them
 struct BondState {
     std::vector<gpe_bond> set;                   // the bonds as the host gave them (empty: none, nothing is launched)
@@ -885,6 +893,7 @@ struct gpe_ctx {
     gpe::TracerState tracers;
     gpe::MonitorState monitor;
     gpe::ColliderState colliders;
+    gpe::SweepState sweep;
     gpe::BondState bonds;
     gpe::BodyState bodies;
     gpe::FieldState fields;
@@ -1040,6 +1049,9 @@ inline bool has_colliders(const gpe_ctx *c) { return !c->colliders.set.empty(); 
 gpe_status refuse_colliders(gpe_ctx *c, const char *who);   // GPE_ERR_UNSUPPORTED: sharding a context that holds colliders
 gpe_status colliders_after_step(gpe_ctx *c);       // after every step of gpe_step / gpe_run, before the observers
 void colliders_release(gpe_ctx *c);
+// gpe_sweep.hip: the swept form of that pass
+gpe_status sweep_pass(gpe_ctx *c);                 // colliders_pass while the mode is on: the grid is ready
+void sweep_release(gpe_ctx *c);
 // gpe_surfaces.hip: the surfaces of the two sets; a new set drops its target's
 void surfaces_drop(gpe_ctx *c, uint32_t target);   // GPE_SURFACES_OF_*: frees the rows, the next pass is the plain one
 // gpe_bonds.hip: the distance bonds of a context that holds some
@@ -1300,6 +1312,11 @@ gpe_status launch_bodies_pass(gpe_ctx *c, float2 *pos, const float *radius, uint
 gpe_status launch_fields_pass(gpe_ctx *c, const float2 *pos, float2 *prev, uint64_t n, const uint32_t *cell_start,
                               const uint32_t *items, const float4 *rec, uint32_t k, const ColliderGridView &view, float dt2,
                               unsigned long long *touched);
+// the swept form (k_sweep.hip): prev[0, n) is read for every particle; counts: two words, swept and stopped
+gpe_status launch_colliders_sweep(gpe_ctx *c, float2 *pos, float2 *prev, const float *radius, uint64_t n,
+                                  const uint32_t *cell_start, const uint32_t *items, const float4 *rec, uint32_t k,
+                                  const ColliderGridView &view, unsigned long long *pushed, unsigned long long *counts,
+                                  const float4 *surf);
 // moving colliders (k_movers.hip): the build advances, poses and lists the movers (the grid zeroed before it), the pass
 // pushes pos[0, n) in place
 gpe_status launch_movers_build(gpe_ctx *c, const MoverBuildArgs &B);

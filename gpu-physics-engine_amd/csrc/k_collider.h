@@ -7,8 +7,9 @@
 // them: a polyline).  One pass resolves, for every particle, ONLY the collider it penetrates deepest, every collider
 // judged from the position the pass starts with.  The result is therefore a function of (p, r, colliders) alone:
 // order-free across particles and exactly binnable; the overlapping capsules of a polyline do not push twice at their
-// joints; a particle in a corner is resolved over two steps.  There is no swept test: a wall thinner than one step's
-// displacement is tunnelled through -- hosts make walls thick.
+// joints; a particle in a corner is resolved over two steps.  There is no swept test in this rule: a wall thinner than
+// one step's displacement is tunnelled through -- hosts make walls thick, or switch on the swept form of the pass
+// (k_sweep.h: the path prev -> pos against the static colliders; not the movers, not the collision solver's pushes).
 #pragma once
 
 #include <math.h>

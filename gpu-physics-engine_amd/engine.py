@@ -624,6 +624,24 @@ class ParticleSystem:
         self.ctx.call("gpe_get_colliders_info", C.byref(info))
         return {name: getattr(info, name) for name, _ in L.GpeCollidersInfo._fields_ if name != "struct_size"}
 
+    def set_collider_sweep(self, on):
+        """gpe_set_collider_sweep: on, the static colliders' pass judges every particle by its path prev -> pos of the step
+        (csrc/k_sweep.h), so walls thinner than a step's displacement hold.  A mode of the pass: it outlives
+        set_colliders and set_surfaces.  Zeroes the sweep's counters; blocks."""
+        self.ctx.call("gpe_set_collider_sweep", L.SWEEP_ON if on else L.SWEEP_OFF)
+
+    def collider_sweep(self):
+        """gpe_get_collider_sweep -> bool."""
+        mode = C.c_uint32(0)
+        self.ctx.call("gpe_get_collider_sweep", C.byref(mode))
+        return mode.value == L.SWEEP_ON
+
+    def sweep_info(self):
+        """gpe_get_sweep_info -> dict(mode, passes, swept, stopped).  Blocks like a download."""
+        info = L.GpeSweepInfo(struct_size=C.sizeof(L.GpeSweepInfo))
+        self.ctx.call("gpe_get_sweep_info", C.byref(info))
+        return {name: getattr(info, name) for name, _ in L.GpeSweepInfo._fields_ if name != "struct_size"}
+
     # Moving colliders (not in the reference; include/gpe.h): capsules with a motion -- pistons and rotors -- advanced,
     # listed and applied on the device after every update() / step of run(), behind the bodies and before the static
     # colliders.  Step state: save() keeps the set and the poses.
@@ -1377,6 +1395,18 @@ class State:
         """ParticleSystem.colliders_info -> dict(k, passes, pushed, grid_x, grid_y, list_entries)."""
         return self.particles.colliders_info()
 
+    def set_collider_sweep(self, on):
+        """ParticleSystem.set_collider_sweep: the static colliders' pass judges the path prev -> pos while on."""
+        self.particles.set_collider_sweep(on)
+
+    def collider_sweep(self):
+        """ParticleSystem.collider_sweep -> bool."""
+        return self.particles.collider_sweep()
+
+    def sweep_info(self):
+        """ParticleSystem.sweep_info -> dict(mode, passes, swept, stopped)."""
+        return self.particles.sweep_info()
+
     def set_movers(self, movers):
         """ParticleSystem.set_movers: moving colliders (rows of MOVER_DTYPE) advanced and applied after every step, behind
         the bodies and before the static colliders."""
@@ -1590,8 +1620,11 @@ class State:
         are distance bonds with their relaxation count and broken flags (`bonds`, `bond_iterations`, `bonds_broken`) and
         bodies with their members and broken flags (`bodies`, `bodies_broken`, `body_member_uid`, `body_member_rest`) and
         force fields (`fields`) and moving colliders with their poses (`movers`, `mover_poses`), and the surfaces of
-        the two sets where present (`collider_surfaces`, `mover_surfaces`)."""
+        the two sets where present (`collider_surfaces`, `mover_surfaces`), and the static colliders' sweep where it is
+        on (`collider_sweep`)."""
         extra = {}
+        if self.collider_sweep():
+            extra.update(collider_sweep=np.array([L.SWEEP_ON], np.uint32))
         for target in ("colliders", "movers"):
             rows = self.surfaces(target)
             if len(rows):
@@ -1650,6 +1683,8 @@ class State:
                 st.set_colliders(d["colliders"])
             if "collider_surfaces" in d.files:                     # (after their set)
                 st.set_surfaces("colliders", d["collider_surfaces"].astype(SURFACE_DTYPE))
+            if "collider_sweep" in d.files:                        # (a file without it: off)
+                st.set_collider_sweep(bool(d["collider_sweep"][0]))
             if "bonds" in d.files:                                 # (after the uids they name; a broken bond starts broken)
                 rows = d["bonds"].astype(BOND_DTYPE)
                 rows["flags"] |= np.where(d["bonds_broken"], L.BOND_BROKEN, 0).astype(np.uint32)

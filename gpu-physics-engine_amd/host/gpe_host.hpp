@@ -355,6 +355,22 @@ class ParticleSystem {
         ctx_->call(gpe_get_colliders_info(ctx_->raw(), &info));
         return info;
     }
+    // the sweep: the static colliders' pass judges the path prev -> pos of the step, so a thin wall is not tunnelled
+    // through (csrc/k_sweep.h).  A mode of the pass: it outlives set_colliders / set_surfaces; a snapshot keeps it.
+    void set_collider_sweep(bool on) { ctx_->call(gpe_set_collider_sweep(ctx_->raw(), on ? GPE_SWEEP_ON : GPE_SWEEP_OFF)); }
+    bool collider_sweep() const
+    {
+        uint32_t mode = GPE_SWEEP_OFF;
+        ctx_->call(gpe_get_collider_sweep(ctx_->raw(), &mode));
+        return mode == GPE_SWEEP_ON;
+    }
+    gpe_sweep_info sweep_info() const
+    {
+        gpe_sweep_info info{};
+        info.struct_size = sizeof(info);
+        ctx_->call(gpe_get_sweep_info(ctx_->raw(), &info));
+        return info;
+    }
     // not in the reference: distance bonds between particles named by uid, or from a particle to a fixed point
     // (include/gpe.h), relaxed on the device after every step of gpe_step / gpe_run, before the static colliders.
     // Step state: a snapshot keeps the set and the broken flags (a broken bond is given back with GPE_BOND_BROKEN).

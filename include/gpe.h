@@ -366,7 +366,34 @@ gpe_status gpe_monitor_end(gpe_ctx *ctx);
  *    (inelastic).  A particle no collider touches keeps every bit.  Deepest-only makes the result a function of
  *    (p, r, colliders) alone: the overlapping capsules of a polyline do not push twice at a joint; a corner is
  *    resolved over two steps.
- *  - No swept test: a wall thinner than one step's displacement is tunnelled through.  Make walls thick.
+ *  - Without the sweep (below) there is no swept test: a wall thinner than one step's displacement is tunnelled
+ *    through.  Make walls thick, or switch the sweep on.
+ *  - The sweep.  gpe_set_collider_sweep(ctx, GPE_SWEEP_ON) makes the pass judge a particle by its path prev -> pos of
+ *    this step instead of by pos alone (csrc/k_sweep.h is the one definition, csrc/k_sweep.hip the pass; the same
+ *    arithmetic rules).  With m = pos - prev and s_j = R_j + |r|:
+ *      1. m not finite, or exactly zero in both components: the rule above, on pos (a resting particle gets its bits).
+ *      2. the contact of collider j on x(t) = prev + t m: t_j = 0 where prev is touched; else the least t in [0, 1] at
+ *         which the path, approaching, meets the band's side or the discs about a and b and the capsule's distance
+ *         there obeys d_j <= s_j + 2^-19 (|prevx| + |prevy| + |posx| + |posy|); else t_j = 1 where pos is touched.  With
+ *         x_j = x(t_j), d_j and the normal n_j taken there: depth_j = (s_j - d_j) + n_j . (x_j - pos); the contact
+ *         counts when depth_j > 0 (a particle moving out of an obstacle it started in has none).
+ *      3. the least t_j wins, then the greatest depth_j, then the lowest j.
+ *      4. q = clamp(pos + n * depth) as above; with surfaces on the set and a row not flagged GPE_SURFACE_PLAIN, the
+ *         surface rule with that normal and depth gives q and prev'.
+ *      5. if any collider has a contact on prev -> q with depth_j > 2^-10 * s_j, the particle stops at its first
+ *         contact: pos = clamp(x_1 + n_1 * max(s_1 - d_1, 0)), prev untouched, no surface.  Otherwise pos = q (and
+ *         prev = prev' where a surface acted).
+ *    So a particle ends at a point whose path from prev enters nothing deeper than that slop, or at the first point where
+ *    it touched anything; a corner still takes two steps.  What stays a limit: the movers have no sweep; prev is the
+ *    position after the step's collision response, so a particle the collision solver shoves across a wall in one step
+ *    is not caught (a wall has to be thicker than one collision push, not than one displacement); a particle that
+ *    starts on the wrong side of a wall stays there.  The sweep is a mode of the pass, like gravity: allowed with no
+ *    colliders set, kept by gpe_set_colliders, gpe_set_surfaces and everything colliders survive.  Off (the default),
+ *    the kernels and the bits are those of a context that never heard of it.  gpe_set_collider_sweep waits for the
+ *    stream and zeroes the sweep's counters; a mode other than GPE_SWEEP_OFF / GPE_SWEEP_ON: GPE_ERR_INVALID_ARG; on a
+ *    sharded context: GPE_ERR_UNSUPPORTED.  gpe_get_sweep_info: passes run in the swept form since the last
+ *    gpe_set_collider_sweep, the particles whose winner had 0 < t < 1 (swept) and those that stopped (step 5), summed;
+ *    it synchronises.
  *  - Colliders are step state, not observation state: the set survives gpe_set_particles, adds, removals, edits,
  *    re-sorts, growth, gpe_set_world and uids being switched on or off; gpe_destroy frees it.
  *  - The pass finds a particle's colliders through a coarse grid over the world, rebuilt before the next pass when
@@ -396,6 +423,17 @@ gpe_status gpe_set_colliders(gpe_ctx *ctx, const gpe_collider *colliders, uint64
 gpe_status gpe_get_colliders(const gpe_ctx *ctx, gpe_collider *out, uint64_t capacity, uint64_t *k);
 gpe_status gpe_apply_colliders(gpe_ctx *ctx);                              /* one pass now, stream-ordered, no sync */
 gpe_status gpe_get_colliders_info(gpe_ctx *ctx, gpe_colliders_info *info); /* synchronises (reads the device counters) */
+#define GPE_SWEEP_OFF 0u
+#define GPE_SWEEP_ON 1u
+typedef struct gpe_sweep_info {
+    uint32_t struct_size, mode;       /* in / GPE_SWEEP_*                                               */
+    uint64_t passes;                  /* swept passes run since the last gpe_set_collider_sweep         */
+    uint64_t swept;                   /* particles whose winning contact lay at 0 < t < 1, summed       */
+    uint64_t stopped;                 /* particles that stopped at their first contact, summed          */
+} gpe_sweep_info;                     /* 32 bytes */
+gpe_status gpe_set_collider_sweep(gpe_ctx *ctx, uint32_t mode);            /* synchronises */
+gpe_status gpe_get_collider_sweep(const gpe_ctx *ctx, uint32_t *mode);
+gpe_status gpe_get_sweep_info(gpe_ctx *ctx, gpe_sweep_info *info);         /* synchronises (reads the device counters) */
 
 /* ---- moving colliders (not in the reference) ----------------------------------------------------------------------
  * Obstacles that move: a piston, a lift, a sliding gate, a paddle wheel, a mixer blade.  A mover is a capsule at rest
