@@ -1,0 +1,654 @@
+"""Every pass behind a step armed at once: bonds -> bodies -> movers -> static colliders (plain / surfaces / swept) ->
+fields, the order of gpe_step and gpe_run (csrc/gpe_api.hip).  TEST INFRASTRUCTURE ONLY.
+
+Everything is one twin over the two chains of twins the features' own tests use (tests/_bodies_model.Twin: bonds,
+bodies, plain colliders; tests/_sweep_model.Twin: movers, surfaces, sweep, fields).  It writes no physics: every pass is
+the model function its feature's tests pin against the device, and tests/test_everything_cpu.py ties it bit for bit to
+the two existing twins.  THE NEXT PASS BEHIND A STEP IS ADDED HERE: its twin into the bases, its call into step().
+
+scene() is the staged scene of the CPU and GPU tests, arm() sets its features on a twin or on a State (their methods
+share names), plan(seed) a list of operations and Sequence the thing that applies them to a twin and, when it has one, to
+a State.  Every draw comes from one generator and depends on nothing but the twin's state, so a plan runs with the twin
+alone on a CPU, where Coverage.check() is met before any GPU time is spent."""
+import collections
+import ctypes as C
+import os
+import tempfile
+
+import numpy as np
+
+from tests import _bodies_model as BD
+from tests import _bonds_model as BM
+from tests import _fields_model as FM
+from tests import _movers_model as MM
+from tests import _surfaces_model as SM
+from tests import _sweep_model as SW
+from tests._oracle_model import OracleModel, VEL_ADD, VEL_SET, circle_mask
+
+F32 = np.float32
+U32 = np.uint32
+DT = 1.0 / 60.0
+DTS = (1.0 / 60.0, 1.0 / 120.0)
+STEPS = 40
+SEEDS = (1, 2, 3)
+ARMS = ("bonds", "bodies", "movers", "mover_surfaces", "colliders", "collider_surfaces", "sweep", "fields")
+# the arrays of a snapshot that holds all nine optional groups (State.save)
+GROUPS = ("colliders", "collider_surfaces", "collider_sweep", "bonds", "bodies", "fields", "movers", "mover_poses",
+          "mover_surfaces", "uids")
+
+
+class Everything(BD.Twin, SW.Twin):
+    """One context with all seven features: the MRO runs through both chains once, every constructor is cooperative."""
+
+    def __init__(self, *a, **kw):
+        super().__init__(*a, **kw)
+        self.field_passes = self.field_touched = self.field_changed = 0
+
+    def set_fields(self, fields):
+        super().set_fields(fields)
+        self.field_passes = self.field_touched = 0
+
+    def apply_fields(self, dt):
+        """gpe_apply_fields: tests/_fields_model.apply on prev; field_changed counts the rows whose prev bits changed"""
+        if len(self.fields) == 0:
+            return
+        self._pull()
+        new, touched = FM.apply(self.pos, self.prev, self.fields, dt)
+        self.field_changed += int((np.ascontiguousarray(new).view(U32) != np.ascontiguousarray(self.prev, F32).view(U32))
+                                  .any(axis=1).sum())
+        self.prev = new
+        self.field_passes += 1
+        self.field_touched += int(touched.sum())
+
+    def step(self, dt, resort=False):
+        OracleModel.step(self, dt, resort=resort)
+        self.apply_bonds()
+        self.apply_bodies()
+        self.apply_movers(dt)
+        self.apply_colliders()
+        self.apply_fields(dt)
+
+    def armed(self):
+        """-> the arms that are set"""
+        on = dict(bonds=len(self.bonds) > 0, bodies=len(self.bodies) > 0, movers=len(self.m) > 0,
+                  mover_surfaces=self.m.surfaces is not None, colliders=len(self.colliders) > 0,
+                  collider_surfaces=self.collider_surfaces is not None, sweep=self.sweep, fields=len(self.fields) > 0)
+        return tuple(a for a in ARMS if on[a])
+
+    def fully_armed(self):
+        return self.armed() == ARMS and self.uids is not None
+
+    def reloaded(self):
+        """State.save() / State.load(): every set is set anew (its counters start again, the body poses are unknown
+        until a pass), the broken flags, the movers' states and the sweep's mode are kept"""
+        self.passes = self.pushed = 0
+        self.bond_passes = self.body_passes = 0
+        self.poses = np.full((len(self.bodies), 4), np.nan, F32)
+        self.m.passes = self.m.pushed = 0
+        self.sweep_passes = self.swept = self.stopped = 0
+        self.field_passes = self.field_touched = 0
+
+    def counters(self):
+        """what the info calls of a context report, as far as the model knows it"""
+        return dict(colliders=dict(k=len(self.colliders), passes=self.passes, pushed=self.pushed),
+                    movers=dict(k=len(self.m), passes=self.m.passes, pushed=self.m.pushed),
+                    sweep=dict(mode=int(self.sweep), passes=self.sweep_passes, swept=self.swept, stopped=self.stopped),
+                    bonds=self.bonds_info(), bodies=self.bodies_info(),
+                    fields=dict(k=len(self.fields), passes=self.field_passes if len(self.fields) else 0,
+                                touched=self.field_touched if len(self.fields) else 0))
+
+
+def state_counters(st):
+    """the same dict from a State (the grids' sizes and the uid lookups, which the model does not have, left out)"""
+    pick = lambda info, names: {k: info[k] for k in names}
+    bonds, bodies = st.bonds_info(), st.bodies_info()
+    bonds.pop("resolves"); bodies.pop("resolves")
+    return dict(colliders=pick(st.colliders_info(), ("k", "passes", "pushed")),
+                movers=pick(st.movers_info(), ("k", "passes", "pushed")), sweep=st.sweep_info(), bonds=bonds, bodies=bodies,
+                fields=pick(st.fields_info(), ("k", "passes", "touched")))
+
+
+# ---- the scene: test_gpu_bodies' yard filled up to 1025 particles, with a piston, a paddle, a corner and a field set ----
+WORLD, GRAVITY = (60.0, 60.0), (0.0, 100.0)
+N = 1025                                                               # odd, past two blocks of 512
+CORNER = np.array([[50, 31, 57, 31, 0], [57, 31, 57, 38, 0]], F32)     # two zero-radius capsules: apex (57, 31), open to the lower left
+SHOTS = 8
+SHOT_SPEED = 6.0                                                       # units per step: thinner walls than a step's path
+Scene = collections.namedtuple("Scene", "pos prev rad bonds iterations bodies member_uid member_rest colliders "
+                                        "collider_surfaces movers mover_surfaces fields")
+
+
+def scene():
+    """uid = storage index at the start.  The yard (a pendulum, six bricks of which one is brittle, a soft blob, 120
+    loose particles; a floor and a peg; two bonds relaxed twice), 823 more loose particles on a jittered lattice above
+    the floor, and eight shots: particles below the corner that leave for its apex at 6 units per step."""
+    from tests.test_gpu_bodies import YARD_COLLIDERS, yard_scene
+    pos, rad, bodies, member_uid, member_rest, bonds = yard_scene()
+    bodies["break_distance"][3] = 0.05                                 # the brittle brick breaks on the 15th step, as it lands
+    rng = np.random.default_rng(31)
+    k = N - len(pos) - SHOTS
+    i = np.arange(56 * 29)
+    x, y = 2.5 + 1.0 * (i % 56), 39.4 - 1.02 * (i // 56)               # rows from the floor (centres rest at 39.5) upward
+    far = lambda cx, cy, r: (x - cx) ** 2 + (y - cy) ** 2 > r * r
+    free = ((y < 25.5) | (y > 32.5)) & far(30, 15, 3.8) & far(40, 30, 3.8)          # the bricks' band, the blob, the peg
+    free &= ~((x > 8.5) & (x < 13.5) & (y < 16.0))                     # the pendulum
+    free &= ~((x < 7.8) & (y > 25.0)) & ~((x > 37.5) & (x < 50.5) & (y > 29.5) & (y < 34.5))     # the piston, the paddle
+    free &= ~((x > 48.5) & (y > 30.0) & (y < 39.0))                    # the corner and the lane of the shots
+    assert free.sum() >= k
+    fill = np.stack([x, y], axis=1)[free][:k] + rng.uniform(-0.08, 0.08, (k, 2))
+    j = np.arange(SHOTS)
+    shots = np.stack([50.5 + 1.1 * (j % 4), 36.0 + 1.1 * (j // 4)], axis=1)
+    pos = np.concatenate([pos, fill, shots]).astype(F32)
+    prev = pos.copy()
+    d = np.array([57.0, 31.0]) - shots                                 # toward the apex
+    d /= np.linalg.norm(d, axis=1)[:, None]
+    prev[-SHOTS:] = (shots - SHOT_SPEED * d).astype(F32)
+    assert len(pos) == N
+    colliders = np.concatenate([YARD_COLLIDERS, CORNER]).astype(F32)
+    movers = MM.run_movers()
+    return Scene(pos, prev, np.full(N, 0.5, F32), bonds, 2, bodies, member_uid, member_rest, colliders,
+                 SM.scene_surfaces(len(colliders)), movers, SM.scene_surfaces(len(movers), seed=5), FM.POOL_FIELDS)
+
+
+def arm(h, sc, arms=ARMS):
+    """set the features of `arms` on a twin or a State (uids on already); a set left out leaves its surfaces out"""
+    if "bonds" in arms:
+        h.set_bonds(sc.bonds, sc.iterations)
+    if "bodies" in arms:
+        h.set_bodies(sc.bodies, sc.member_uid, sc.member_rest)
+    if "colliders" in arms:
+        h.set_colliders(sc.colliders)
+        if "collider_surfaces" in arms:
+            h.set_surfaces("colliders", sc.collider_surfaces)
+    if "sweep" in arms:
+        h.set_collider_sweep(True)
+    if "movers" in arms:
+        h.set_movers(sc.movers)
+        if "mover_surfaces" in arms:
+            h.set_surfaces("movers", sc.mover_surfaces)
+    if "fields" in arms:
+        h.set_fields(sc.fields)
+    return h
+
+
+def twin(oracle, arms=ARMS, sc=None):
+    sc = scene() if sc is None else sc
+    tw = Everything(oracle, sc.pos, sc.rad, world=WORLD, gravity=GRAVITY, prev=sc.prev)
+    tw.enable_uids()
+    return arm(tw, sc, arms)
+
+
+Frame = collections.namedtuple("Frame", "pos prev uids body_poses bodies_broken bonds_broken mover_poses")
+
+
+def frame(tw):
+    pos, prev, _ = tw.arrays()
+    return Frame(pos.copy(), prev.copy(), tw.uids.copy(), tw.poses.copy(), tw.bodies_broken.copy(), tw.broken.copy(),
+                 tw.m.poses())
+
+
+def frames(tw, steps=STEPS, dt=DT, resort_every=0, resort_first=False):
+    """-> the frames after every step, the re-sorts taken as gpe_run(steps, resort_every, resort_first) takes them"""
+    out = []
+    for s in range(steps):
+        resort = (s == 0 and resort_first) or (resort_every and s > 0 and s % resort_every == 0)
+        tw.step(dt, resort=bool(resort))
+        out.append(frame(tw))
+    return out
+
+
+# ---- the random interleaving -------------------------------------------------------------------------------------------
+Plan = collections.namedtuple("Plan", "seed ops")
+SETS = ("bonds", "bodies", "fields", "collider_surfaces", "mover_surfaces")
+BLOCKS = ([["set_" + s, "step", "clear_" + s, "step", "set_" + s] for s in SETS] + [
+    ["set_colliders", "set_collider_surfaces", "step", "clear_colliders", "step", "set_colliders", "set_collider_surfaces"],
+    ["set_movers", "set_mover_surfaces", "step", "clear_movers", "step", "set_movers", "set_mover_surfaces"],
+    ["sweep_off", "step", "sweep_on"], ["set_mover_poses", "step"],
+    ["run"], ["run"], ["run_resort_mid"], ["resort", "step"], ["add_few", "step"], ["add_grow", "step"],
+    ["remove_circle", "step"], ["remove_members", "step"], ["remove_uid"], ["edit_pos", "step"],
+    ["radius_up", "step", "radius_down", "step"], ["kick", "step"], ["world_grow", "step", "world_back", "step"], ["gravity"],
+    ["other_mode"], ["save_load", "step"], ["apply_bonds"], ["apply_bodies"], ["apply_movers"], ["apply_colliders"],
+    ["apply_fields"]])
+REPLACING = (["set_" + s for s in SETS + ("colliders", "movers", "mover_poses")] + ["clear_" + s for s in SETS + ("colliders", "movers")]
+             + ["sweep_off", "sweep_on"])
+
+
+def plan(seed):
+    """BLOCKS in a random order behind a run of the scene as it starts (its shots and the brittle brick act there).  A
+    block leaves every arm set, so every block starts fully armed; what its operations draw when they run comes from
+    Sequence.rng."""
+    rng = np.random.default_rng(7100 + seed)
+    order = rng.permutation(len(BLOCKS))
+    ops = ["run_start"] + [op for i in order for op in BLOCKS[i]]
+    assert 60 <= len(ops) <= 80
+    return Plan(seed, ops)
+
+
+class Coverage(collections.Counter):
+    """What a sequence reached, counted on the twin's side."""
+
+    def check(self):
+        need = (["armed_" + k for k in ("colliders_pushed", "movers_pushed", "swept", "stopped", "body_broke", "field_changed",
+                                        "resort", "growth", "removal_of_member_and_bonded", "radius_up")]
+                + ["set_world_with_grids", "save_load_nine_groups", "run_resorts_in_its_middle"] + ["op_" + op for op in REPLACING])
+        missing = [k for k in need if self[k] == 0]
+        assert not missing, "the sequence never reached: %s\n%s" % (", ".join(missing), dict(self))
+        assert self["armed_steps"] >= 30, "only %d steps with all eight arms set" % self["armed_steps"]
+
+
+class Sequence:
+    """One plan applied to the twin and (gpe given) to a State under GPE_FLAG_GUARD_ALLOCS.  compare(st, twin, where) is
+    called after every operation, end(st) with every State that leaves."""
+
+    def __init__(self, plan_, oracle, gpe=None, mode_name="native", compare=None, end=None):
+        self.plan, self.gpe, self.compare, self.end, self.mode_name = plan_, gpe, compare, end, mode_name
+        self.rng = np.random.default_rng(7200 + plan_.seed)
+        self.sc = scene()
+        self.tw = twin(oracle, sc=self.sc)
+        self.world = WORLD
+        self.cov = Coverage()
+        self.log = []
+        self.cap = len(self.tw)
+        self.steps = 0
+        self.native_steps = self.compat_steps = self.other_steps = 0
+        self.st = self.L = None
+        self.tmp = tempfile.TemporaryDirectory()
+        if gpe is not None:
+            self.L = gpe._lib
+            self.mode = self.L.MODE_NATIVE if mode_name == "native" else self.L.MODE_COMPAT
+            self.other = self.L.MODE_COMPAT if mode_name == "native" else self.L.MODE_NATIVE
+            self.st = gpe.State(self.sc.pos, self.sc.rad, world=WORLD, gravity=GRAVITY, prev=self.sc.prev, mode=self.mode,
+                                flags=self.L.FLAG_GUARD_ALLOCS)
+            self.st.enable_uids()
+            arm(self.st, self.sc)
+
+    # ---- plumbing -----------------------------------------------------------------------------------------------------
+    def where(self, i, op):
+        return "seed %d %s op #%d (%s)\n  %s" % (self.plan.seed, self.mode_name, i, op, "\n  ".join(self.log))
+
+    def both(self):
+        return [h for h in (self.st, self.tw) if h is not None]
+
+    def retire(self):
+        info = self.st.ctx.pipeline_info()
+        self.native_steps += info["native_steps"]
+        self.compat_steps += info["compat_steps"]
+
+    def close(self):
+        if self.st is not None:
+            self.retire()
+            self.end(self.st)
+            self.st = None
+        self.tw.close()
+        self.tmp.cleanup()
+
+    def run(self):
+        for i, op in enumerate(self.plan.ops):
+            self.cov["op_" + op] += 1
+            getattr(self, "op_" + op)()
+            if self.st is not None:
+                cap = C.c_uint64()
+                self.st.ctx.call("gpe_capacity", C.byref(cap))
+                assert cap.value == self.cap, "capacity %d, expected %d\n%s" % (cap.value, self.cap, self.where(i, op))
+                self.compare(self.st, self.tw, self.where(i, op))
+
+    def _a_particle(self):
+        p = self.tw.arrays()[0]
+        return p[int(self.rng.integers(0, len(p)))]
+
+    def _inside(self, k, y1=35.0):
+        return np.stack([self.rng.uniform(2, 58, k), self.rng.uniform(2, y1, k)], axis=1).astype(F32)
+
+    # ---- steps --------------------------------------------------------------------------------------------------------
+    def _watch(self):
+        tw = self.tw
+        return dict(colliders_pushed=tw.pushed, movers_pushed=tw.m.pushed, swept=tw.swept, stopped=tw.stopped,
+                    body_broke=int(tw.bodies_broken.sum()), field_changed=tw.field_changed)
+
+    def _twin_step(self, dt, resort):
+        armed = self.tw.fully_armed()
+        before = self._watch()
+        self.tw.step(dt, resort=resort)
+        self.steps += 1
+        if armed:
+            self.cov["armed_steps"] += 1
+            for k, v in self._watch().items():
+                self.cov["armed_" + k] += v - before[k]
+            if resort:
+                self.cov["armed_resort"] += 1
+
+    def _dt(self):
+        dt = DTS[int(self.rng.integers(0, 2))]
+        assert MM.dt_allowed(self.tw.m.movers, dt)
+        return dt
+
+    def _steps(self, k, dt=None):
+        for s in range(k):
+            d = self._dt() if dt is None else dt
+            resort = bool(self.rng.integers(0, 4) == 0)
+            if self.st is not None:
+                self.st.update(d, resort=resort)
+            self._twin_step(d, resort)
+            self.log.append("step dt 1/%d%s" % (round(1 / d), " resort" if resort else ""))
+
+    def op_step(self):
+        self._steps(int(self.rng.integers(1, 4)))
+
+    def _run(self, k, every, first, dt):
+        if self.st is not None:
+            self.st.run(dt, k, resort_every=every, resort_first=first)
+        for s in range(k):
+            self._twin_step(dt, bool((s == 0 and first) or (every and s > 0 and s % every == 0)))
+        if every and k > every:
+            self.cov["run_resorts_in_its_middle"] += 1
+        self.log.append("run %d dt 1/%d every %d first %s" % (k, round(1 / dt), every, first))
+
+    def op_run_start(self):
+        self._run(16, 0, False, DT)
+
+    def op_run(self):
+        self._run(int(self.rng.integers(5, 13)), int(self.rng.choice([0, 4])), bool(self.rng.integers(0, 2)), self._dt())
+
+    def op_run_resort_mid(self):
+        self._run(int(self.rng.integers(9, 14)), 4, bool(self.rng.integers(0, 2)), self._dt())
+
+    def op_resort(self):
+        if self.st is not None:
+            self.st.particles.sort_by_cell_id()
+        self.tw.morton_resort()
+        if self.tw.fully_armed():
+            self.cov["armed_resort"] += 1
+        self.log.append("morton resort")
+
+    def op_other_mode(self):
+        k = int(self.rng.integers(1, 4))
+        if self.st is not None:
+            self.st.ctx.call("gpe_set_mode", self.other)
+        self._steps(k)
+        self.other_steps += k
+        if self.st is not None:
+            self.st.ctx.call("gpe_set_mode", self.mode)
+        self.log.append("(%d steps in the other mode)" % k)
+
+    # ---- particles come and go, and are edited ------------------------------------------------------------------------
+    def _add(self, p, r, what):
+        n = len(self.tw)
+        for h in self.both():
+            (h.add_particles if h is self.st else h.add)(p, r)
+        grew = n + len(r) > self.cap
+        if grew:
+            self.cap = max(n + len(r), 2 * self.cap)
+            if self.tw.fully_armed():
+                self.cov["armed_growth"] += 1
+        self.log.append("%s %d%s" % (what, len(r), " (grew to %d)" % self.cap if grew else ""))
+
+    def op_add_few(self):
+        k = int(self.rng.integers(1, 20))
+        self._add(self._inside(k, 25.0), np.full(k, 0.5, F32), "add")
+
+    def op_add_grow(self):
+        k = self.cap - len(self.tw) + 30
+        self._add(self._inside(k, 30.0), np.full(k, 0.25, F32), "add past the capacity")
+
+    def op_remove_circle(self):
+        c = self._a_particle()
+        c, r = (float(c[0]), float(c[1])), float(F32(self.rng.uniform(1.0, 3.0)))
+        if circle_mask(self.tw.arrays()[0], c[0], c[1], r).all():
+            r = 0.0
+        want = self.tw.remove_circle(c[0], c[1], r)
+        if self.st is not None:
+            assert self.st.remove_particles_in_circle(c, r) == want
+        self.log.append("remove circle %s r %g: %d" % (c, r, want))
+
+    def _remove_uids(self, q, what):
+        want = self.tw.remove_uids(q)
+        if self.st is not None:
+            assert self.st.remove_particles_by_uid(q) == want
+        self.log.append("%s: %d of %d uids" % (what, want, len(q)))
+
+    def op_remove_members(self):
+        """a live member of a body, a live bonded particle, two more and one nobody has"""
+        tw, rng = self.tw, self.rng
+        armed = tw.fully_armed()
+        live = lambda u: u[np.isin(u, tw.uids)]
+        member, bonded = live(tw.member_uid), live(np.concatenate([tw.bonds["uid_a"], tw.bonds["uid_b"]]))
+        q = [rng.choice(member)] if len(member) else []
+        q += [rng.choice(bonded)] if len(bonded) else []
+        if armed and len(member) and len(bonded):
+            self.cov["armed_removal_of_member_and_bonded"] += 1
+        q = np.unique(np.concatenate([q, rng.choice(tw.uids, 2, replace=False), [tw.next_uid + 3]]).astype(U32))
+        self._remove_uids(q, "remove a member and a bonded uid")
+
+    def op_remove_uid(self):
+        q = np.unique(np.append(self.rng.choice(self.tw.uids, 3, replace=False), 0xFFFFFFF0).astype(U32))
+        self._remove_uids(q, "remove uids")
+
+    def _edit(self, who, what, **kw):
+        want = self.tw.edit(who, "index", **kw)
+        if self.st is not None:
+            got = self.st.edit_particles(indices=who, positions=kw.get("pos"), previous=kw.get("prev"), radii=kw.get("radius"))
+            assert got == want
+        self.log.append("%s: %d" % (what, want))
+
+    def op_edit_pos(self):
+        k = int(self.rng.integers(1, 30))
+        who = self.rng.choice(len(self.tw), k, replace=False).astype(U32)
+        self._edit(who, "edit positions", pos=self._inside(k))
+
+    def op_radius_up(self):
+        """one particle gets a new largest radius: every grid that depends on the radius bound is stale"""
+        tw = self.tw
+        armed = tw.fully_armed()
+        who = int(self.rng.integers(0, len(tw)))
+        new = F32(F32(abs(tw.max_radius)) * F32(2.0))
+        self._edit(np.array([who], U32), "radius up to %g" % new, radius=np.array([new], F32))
+        assert tw.max_radius == new
+        if armed:
+            self.cov["armed_radius_up"] += 1
+
+    def op_radius_down(self):
+        tw = self.tw
+        r = tw.arrays()[2]
+        who = int(np.nonzero(np.abs(r) == abs(tw.max_radius))[0][-1])
+        self._edit(np.array([who], U32), "radius down", radius=np.array([0.5], F32))
+
+    def op_kick(self):
+        """a kick of a random disc, and a volley at the corner: the particles below it leave for its apex at SHOT_SPEED"""
+        rng, tw = self.rng, self.tw
+        c = self._a_particle()
+        c, r = (float(c[0]), float(c[1])), float(F32(rng.uniform(2.0, 8.0)))
+        a = (float(F32(rng.uniform(-2, 2))), float(F32(rng.uniform(-2, 2))))
+        s = float(F32(SHOT_SPEED / np.sqrt(2.0)))
+        for centre, radius, op, acc in ((c, r, VEL_ADD, a), ((53.5, 34.5), 2.5, VEL_SET, (s, -s))):
+            want = tw.kick(circle_mask(tw.arrays()[0], centre[0], centre[1], radius), op, *acc)
+            if self.st is not None:
+                assert self.st.kick_circle(centre, radius, op, acc) == want
+            self.log.append("kick %s r %g op %d %s: %d" % (centre, radius, op, acc, want))
+
+    # ---- constants ----------------------------------------------------------------------------------------------------
+    def _world(self, w):
+        tw = self.tw
+        if len(tw.colliders) and len(tw.m) and len(tw.fields):
+            self.cov["set_world_with_grids"] += 1
+        if self.st is not None:
+            self.st.ctx.call("gpe_set_world", w[0], w[1])
+        tw.set_world(*w)
+        self.world = w
+        self.log.append("world %s" % (w,))
+
+    def op_world_grow(self):
+        """twice the size; one particle put on the floor's end and one into the well, both in the newly covered part"""
+        self._world((2 * WORLD[0], 2 * WORLD[1]))
+        who = self.rng.choice(len(self.tw), 2, replace=False).astype(U32)
+        self._edit(who, "edit into the new part", pos=np.array([[63.0, 39.75], [85.0, 45.0]], F32))
+
+    def op_world_back(self):
+        self._world(WORLD)
+
+    def op_gravity(self):
+        g = (float(self.rng.choice([0.0, 20.0, -20.0])), float(self.rng.choice([100.0, 60.0, 140.0])))
+        if self.st is not None:
+            self.st.ctx.call("gpe_set_gravity", g[0], g[1])
+        self.tw.set_gravity(*g)
+        self.log.append("gravity %s" % (g,))
+
+    def op_save_load(self):
+        tw = self.tw
+        nine = tw.fully_armed()
+        if nine:
+            self.cov["save_load_nine_groups"] += 1
+        if self.st is not None:
+            path = os.path.join(self.tmp.name, "snap_%d.npz" % len(self.log))
+            self.st.save(path)
+            with np.load(path) as d:
+                if nine:
+                    assert set(GROUPS) <= set(d.files), sorted(d.files)
+            self.retire()
+            self.end(self.st)
+            self.st = self.gpe.State.load(path, mode=self.mode, flags=self.L.FLAG_GUARD_ALLOCS)
+        tw.reloaded()
+        self.cap = len(tw)
+        self.log.append("save / load%s" % (" (all nine groups)" if nine else ""))
+
+    # ---- the passes called directly -----------------------------------------------------------------------------------
+    def _apply(self, name, *args):
+        for h in self.both():
+            getattr(h, name)(*args)
+        self.log.append("%s%s" % (name, args if args else ""))
+
+    def op_apply_bonds(self):
+        self._apply("apply_bonds")
+
+    def op_apply_bodies(self):
+        self._apply("apply_bodies")
+
+    def op_apply_movers(self):
+        self._apply("apply_movers", self._dt())
+
+    def op_apply_colliders(self):
+        self._apply("apply_colliders")
+
+    def op_apply_fields(self):
+        self._apply("apply_fields", self._dt())
+
+    # ---- the sets: replaced, cleared, set again -----------------------------------------------------------------------
+    def _set(self, name, *args, what=None):
+        for h in self.both():
+            getattr(h, name)(*args)
+        self.log.append(what or name)
+
+    def _near(self, seed, count, free):
+        p = self.tw.arrays()[0]
+        near = np.argsort(((p - p[seed]) ** 2).sum(axis=1), kind="stable")
+        return near[free[near]][:count]
+
+    def op_set_bonds(self):
+        """anchors that hold particles where they are, pairs of neighbours (some that snap), one uid nobody has"""
+        rng, tw = self.rng, self.tw
+        p = tw.arrays()[0]
+        pins = rng.choice(len(tw), 4, replace=False)
+        rows = [BM.anchors(tw.uids[pins], p[pins], 0.0, 0.5)]
+        for _ in range(5):
+            a = int(rng.integers(0, len(tw)))
+            near = self._near(a, 3, np.ones(len(tw), bool))
+            b = int(near[near != a][0])
+            rows.append(BM.pairs([tw.uids[a]], [tw.uids[b]], 1.0, float(rng.choice([0.25, 1.0])), float(rng.choice([0.0, 1.6]))))
+        rows.append(BM.pairs([tw.uids[pins[0]]], [tw.next_uid + 7], 1.0))
+        self._set("set_bonds", np.concatenate(rows), int(rng.integers(1, 4)))
+
+    def op_clear_bonds(self):
+        self._set("set_bonds", np.zeros(0, BM.BOND_DTYPE), 1, what="clear bonds")
+
+    def op_set_bodies(self):
+        """bodies over particles that are close now, their shape a little off; some brittle; one uid nobody has"""
+        rng, tw = self.rng, self.tw
+        p = tw.arrays()[0]
+        free = np.ones(len(tw), bool)
+        groups = []
+        for _ in range(int(rng.integers(4, 10))):
+            g = self._near(int(rng.integers(0, len(tw))), int(rng.choice([2, 3, 4, 5, 9, 17, 33])), free)
+            if len(g) >= 2:
+                free[g] = False
+                groups.append(g)
+        counts = [len(g) for g in groups]
+        slot = np.concatenate(groups)
+        member_uid = tw.uids[slot].copy()
+        member_uid[int(rng.integers(0, len(slot)))] = tw.next_uid + 11
+        rest = (p[slot] + rng.uniform(-0.15, 0.15, (len(slot), 2))).astype(F32)
+        bodies = BD.rows(counts, rng.choice(np.array([1.0, 0.5, 0.25], F32), len(counts)),
+                         np.where(np.arange(len(counts)) % 2 == 0, 0.3, 0.0).astype(F32))
+        self._set("set_bodies", bodies, member_uid, rest)
+
+    def op_clear_bodies(self):
+        self._set("set_bodies", np.zeros(0, BD.BODY_DTYPE), np.zeros(0, U32), np.zeros((0, 2), F32), what="clear bodies")
+
+    def op_set_colliders(self):
+        """the floor, a peg somewhere, the corner, and sometimes a thin shelf"""
+        rng = self.rng
+        x, y = float(rng.uniform(15, 45)), float(rng.uniform(28, 34))
+        rows = [[-5, 45, 65, 45, 5], [x, y, x, y, float(rng.uniform(1, 3))]] + CORNER.tolist()
+        if rng.integers(0, 2):
+            rows.append([float(rng.uniform(5, 25)), 36.0, float(rng.uniform(26, 40)), 37.0, 0.0])
+        self._set("set_colliders", np.array(rows, F32))
+
+    def op_clear_colliders(self):
+        self._set("set_colliders", np.zeros((0, 5), F32), what="clear colliders")
+
+    def op_set_collider_surfaces(self):
+        self._set("set_surfaces", "colliders", SM.scene_surfaces(len(self.tw.colliders), seed=int(self.rng.integers(0, 1000))),
+                  what="set collider surfaces")
+
+    def op_clear_collider_surfaces(self):
+        self._set("set_surfaces", "colliders", np.zeros(0, SM.SURFACE_DTYPE), what="clear collider surfaces")
+
+    def op_set_movers(self):
+        rng = self.rng
+        x, y = float(rng.uniform(4, 8)), float(rng.uniform(26, 30))
+        px, py = float(rng.uniform(30, 46)), float(rng.uniform(30, 36))
+        movers = MM.rows(MM.linear((x, y), (x, y + 13), 2.0, v=(float(rng.uniform(15, 30)), 0.0), travel=float(rng.uniform(6, 12))),
+                         MM.rotor((px, py), (px + 7, py), 1.5, (px, py), float(rng.choice([-6.0, 4.0, 6.0]))))
+        assert all(MM.dt_allowed(movers, dt) for dt in DTS)
+        self._set("set_movers", movers)
+
+    def op_clear_movers(self):
+        self._set("set_movers", np.zeros(0, MM.MOVER_DTYPE), what="clear movers")
+
+    def op_set_mover_surfaces(self):
+        self._set("set_surfaces", "movers", SM.scene_surfaces(len(self.tw.m), seed=int(self.rng.integers(0, 1000))),
+                  what="set mover surfaces")
+
+    def op_clear_mover_surfaces(self):
+        self._set("set_surfaces", "movers", np.zeros(0, SM.SURFACE_DTYPE), what="clear mover surfaces")
+
+    def op_set_mover_poses(self):
+        """the states a fresh copy of the set reaches after a few steps: valid ones, other than those held"""
+        ahead = MM.Movers(self.tw.m.movers)
+        for _ in range(int(self.rng.integers(3, 30))):
+            ahead.q0, ahead.q1 = MM.advance(ahead.movers, ahead.q0, ahead.q1, DT)
+        poses = ahead.poses()
+        if self.st is not None:
+            self.st.set_mover_poses(poses)
+        self.tw.m.set_poses(poses)
+        self.log.append("set mover poses")
+
+    def op_set_fields(self):
+        """a vortex, a well and a wind inside the yard, the drag pool over the floor, and the pool scene's own set behind
+        them (it acts once the world has grown)"""
+        rng = self.rng
+        at = lambda: (float(rng.uniform(10, 50)), float(rng.uniform(25, 38)))
+        v, w = at(), at()
+        rows = FM.rows(FM.field(FM.CIRCLE, FM.VORTEX, FM.NONE, (v[0], v[1], 9.0, 0), pole=v, strength=float(rng.uniform(40, 120))),
+                       FM.field(FM.CIRCLE, FM.RADIAL, FM.LINEAR, (w[0], w[1], 8.0, 0), pole=w, strength=150.0, reach=8.0),
+                       FM.field(FM.BOX, FM.DRAG, FM.NONE, (5, 36, 55, 41), strength=float(rng.choice([0.9, 0.98]))),
+                       FM.field(FM.BOX, FM.UNIFORM, FM.NONE, (0, 0, 60, 30), f=(float(rng.uniform(-30, 30)), -10.0)),
+                       FM.POOL_FIELDS)
+        self._set("set_fields", rows)
+
+    def op_clear_fields(self):
+        self._set("set_fields", np.zeros(0, FM.DTYPE), what="clear fields")
+
+    def op_sweep_off(self):
+        self._set("set_collider_sweep", False, what="sweep off")
+
+    def op_sweep_on(self):
+        self._set("set_collider_sweep", True, what="sweep on")

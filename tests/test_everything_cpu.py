@@ -1,0 +1,133 @@
+"""CPU: the composed twin of tests/_everything_model.py (bonds, bodies, movers, static colliders with surfaces and the
+sweep, fields, all behind one step) before any GPU time is spent on it: it is no new oracle (bit for bit the two existing
+twins where only their features are set), its scene acts and tells every arm apart, and its random plans reach what
+tests/test_gpu_everything.py needs them to reach."""
+import numpy as np
+import pytest
+
+from tests import _bodies_model as BD
+from tests import _everything_model as E
+from tests import _sweep_model as SW
+
+F32 = np.float32
+U32 = np.uint32
+
+
+def same_bits(a, b):
+    a, b = np.ascontiguousarray(a, F32), np.ascontiguousarray(b, F32)
+    return a.shape == b.shape and bool(((a.view(U32) == b.view(U32)) | (np.isnan(a) & np.isnan(b))).all())
+
+
+@pytest.fixture(scope="module")
+def full(oracle):
+    """scene(), all arms, 40 steps -> (frames, counters, the step after which a body was first broken, field_changed)"""
+    tw = E.twin(oracle)
+    frames = E.frames(tw)
+    out = frames, tw.counters(), next(s for s, f in enumerate(frames) if f.bodies_broken.any()), tw.field_changed
+    tw.close()
+    return out
+
+
+def test_with_the_yards_features_alone_it_is_the_bodies_twin(oracle):
+    """bonds, bodies and the yard's colliders: the frames of tests/_bodies_model.Twin over the yard's 60 steps"""
+    from tests.test_gpu_bodies import STEPS, YARD_COLLIDERS, YARD_GRAVITY, YARD_WORLD, yard_scene
+    pos, rad, bodies, member_uid, member_rest, bonds = yard_scene()
+    twins = []
+    for cls in (BD.Twin, E.Everything):
+        tw = cls(oracle, pos, rad, world=YARD_WORLD, gravity=YARD_GRAVITY)
+        tw.enable_uids()
+        tw.set_bonds(bonds, 2); tw.set_bodies(bodies, member_uid, member_rest); tw.set_colliders(YARD_COLLIDERS)
+        twins.append(tw)
+    old, new = twins
+    for s in range(STEPS):
+        old.step(E.DT); new.step(E.DT)
+        for a, b in zip(old.arrays(), new.arrays()):
+            assert same_bits(a, b), s
+        assert same_bits(old.poses, new.poses) and np.array_equal(old.bodies_broken, new.bodies_broken), s
+    assert old.bodies_broken.any() and old.pushed == new.pushed > 0
+    assert old.bonds_info() == new.bonds_info() and old.bodies_info() == new.bodies_info()
+    assert new.armed() == ("bonds", "bodies", "colliders")
+    old.close(); new.close()
+
+
+def test_with_the_sweeps_features_alone_it_is_the_sweep_twin(oracle):
+    """movers, colliders, both surfaces, the sweep and fields over scene(): the frames of tests/_sweep_model.Twin"""
+    sc = E.scene()
+    arms = tuple(a for a in E.ARMS if a not in ("bonds", "bodies"))
+    twins = []
+    for cls in (SW.Twin, E.Everything):
+        tw = cls(oracle, sc.pos, sc.rad, world=E.WORLD, gravity=E.GRAVITY, prev=sc.prev)
+        tw.enable_uids()
+        twins.append(E.arm(tw, sc, arms))
+    old, new = twins
+    for s in range(E.STEPS):
+        resort = s % 16 == 0
+        old.step(E.DT, resort=resort); new.step(E.DT, resort=resort)
+        for a, b in zip(old.arrays(), new.arrays()):
+            assert same_bits(a, b), s
+        assert old.m.poses().tobytes() == new.m.poses().tobytes() and np.array_equal(old.uids, new.uids), s
+    assert (old.pushed, old.m.pushed, old.swept, old.stopped) == (new.pushed, new.m.pushed, new.swept, new.stopped)
+    assert old.swept > 0 and old.stopped > 0 and old.m.pushed > 0 and new.field_changed > 0 and new.armed() == arms
+    old.close(); new.close()
+
+
+def test_the_scene_acts(full):
+    frames, counters, first_break, field_changed = full
+    sc = E.scene()
+    assert len(sc.rad) == E.N == 1025 and (sc.collider_surfaces["flags"] == 1).any()
+    assert all(np.isfinite(f.pos).all() and np.isfinite(f.prev).all() for f in frames)
+    print(counters, "first break after step", first_break)
+    assert counters["colliders"]["pushed"] > 0 and counters["movers"]["pushed"] > 0
+    assert counters["sweep"]["swept"] > 0 and counters["sweep"]["stopped"] > 0 and field_changed > 0
+    assert counters["bodies"]["broken"] >= 1 and first_break < 15       # (test_gpu_everything saves after 15 steps)
+    assert counters["bonds"]["passes"] == counters["bodies"]["passes"] == counters["sweep"]["passes"] == E.STEPS
+    assert counters["movers"]["passes"] == counters["fields"]["passes"] == E.STEPS
+
+
+@pytest.mark.parametrize("out", E.ARMS)
+def test_every_arm_matters(oracle, full, out):
+    """leaving one arm out changes the bits after 40 steps: the leave-one-out cases on the GPU can tell the arms apart"""
+    tw = E.twin(oracle, tuple(a for a in E.ARMS if a != out))
+    assert out not in tw.armed()
+    last = E.frames(tw)[-1]
+    tw.close()
+    assert not (same_bits(last.pos, full[0][-1].pos) and same_bits(last.prev, full[0][-1].prev))
+
+
+PASSES = ("bonds", "bodies", "movers", "colliders", "fields")
+
+
+@pytest.mark.parametrize("first", range(len(PASSES) - 1))
+def test_the_order_of_the_passes_matters(oracle, full, first):
+    """two neighbouring passes swapped behind every step change the bits after 40 steps: the all-arms case on the GPU
+    pins the order of gpe_step, not only the presence of every pass"""
+    order = list(PASSES)
+    order[first], order[first + 1] = order[first + 1], order[first]
+
+    class Swapped(E.Everything):
+        def step(self, dt, resort=False):
+            E.OracleModel.step(self, dt, resort=resort)
+            for name in order:
+                getattr(self, "apply_" + name)(*((dt,) if name in ("movers", "fields") else ()))
+
+    sc = E.scene()
+    tw = Swapped(oracle, sc.pos, sc.rad, world=E.WORLD, gravity=E.GRAVITY, prev=sc.prev)
+    tw.enable_uids()
+    last = E.frames(E.arm(tw, sc))[-1]
+    tw.close()
+    assert not (same_bits(last.pos, full[0][-1].pos) and same_bits(last.prev, full[0][-1].prev)), order
+
+
+@pytest.mark.parametrize("seed", E.SEEDS)
+def test_the_plans_reach_what_they_are_for(oracle, seed):
+    plan = E.plan(seed)
+    assert 60 <= len(plan.ops) <= 80 and plan.ops == E.plan(seed).ops
+    seq = E.Sequence(plan, oracle)
+    try:
+        seq.run()
+        print("\n".join(seq.log))
+        print(dict(seq.cov))
+        seq.cov.check()
+        assert np.isfinite(seq.tw.arrays()[0]).all()
+    finally:
+        seq.close()

@@ -1,0 +1,327 @@
+"""GPU (-m gpu): every pass behind a step armed at once -- bonds -> bodies -> movers -> static colliders (surfaces,
+swept) -> fields -> observers, the order of gpe_step / gpe_run -- against the one composed twin of
+tests/_everything_model.py, which is made of nothing but the model functions each feature's own tests pin against the
+device (tests/test_everything_cpu.py ties it to the two existing twins).
+
+Every comparison is bit for bit on uint32 views, a NaN for a NaN.  Every context runs under GPE_FLAG_GUARD_ALLOCS and
+ends with no damaged red zone.  A mismatch that goes away when one arm is left out (test_every_step_equals_the_twin's
+leave-one-out cases) points at the library's hook -- the order of the passes, a stale grid, a stale pointer after a
+growth, the order of restoration in State.load -- not at a model."""
+import numpy as np
+import pytest
+
+from tests import _bonds_model as BM
+from tests import _colliders_model as CM
+from tests import _everything_model as E
+from tests import _fields_model as FM
+
+pytestmark = pytest.mark.gpu
+F32 = np.float32
+U32 = np.uint32
+DT = E.DT
+STEPS = E.STEPS
+CASES = ["all"] + ["no_" + a for a in E.ARMS] + ["none"]
+TRACKED = np.array([0, 4, 9, 30, 33, 60, 100, 500, 1017, 1024], U32)    # pendulum, bricks (the brittle one), loose, shots
+
+
+def bits(a):
+    return np.ascontiguousarray(a, F32).view(U32)
+
+
+def same_bits(a, b):
+    """the same bits; where the twin has a NaN the device has a NaN"""
+    a, b = np.ascontiguousarray(a, F32), np.ascontiguousarray(b, F32)
+    return a.shape == b.shape and bool(((bits(a) == bits(b)) | (np.isnan(a) & np.isnan(b))).all())
+
+
+def same_rows(a, b):
+    """two structured arrays of one layout, byte for byte"""
+    return a.dtype.itemsize == b.dtype.itemsize and a.shape == b.shape and a.tobytes() == b.tobytes()
+
+
+def _differ(got, want):
+    if got.shape != want.shape:
+        return "shapes %r %r" % (got.shape, want.shape)
+    bad = np.nonzero(~((bits(got) == bits(want)) | (np.isnan(got) & np.isnan(want))).all(axis=1))[0]
+    return bad[:5], got[bad[:5]], want[bad[:5]]
+
+
+def _mode(gpe, mode):
+    return gpe.MODE_COMPAT if mode == "compat" else gpe.MODE_NATIVE
+
+
+def _arms(case):
+    return {"all": E.ARMS, "none": ()}.get(case, tuple(a for a in E.ARMS if "no_" + a != case))
+
+
+def _state(gpe, mode, arms=E.ARMS, sc=None):
+    sc = E.scene() if sc is None else sc
+    st = gpe.State(sc.pos, sc.rad, world=E.WORLD, gravity=E.GRAVITY, prev=sc.prev, mode=_mode(gpe, mode),
+                   flags=gpe._lib.FLAG_GUARD_ALLOCS)
+    st.enable_uids()
+    return E.arm(st, sc, arms)
+
+
+def _end(st):
+    """every context ends here: no red zone of a live or a released buffer is damaged"""
+    zones = st.ctx.guard_check()
+    assert st.ctx.guard_damaged == 0, zones
+    st.close()
+
+
+def _ran_native(gpe, st, mode, steps):
+    pipe = st.ctx.pipeline_info()
+    if mode == "native":
+        assert pipe["pipeline"] == gpe._lib.PIPELINE_NATIVE and pipe["native_steps"] == steps and pipe["compat_steps"] == 0, pipe
+    else:
+        assert pipe["compat_steps"] == steps and pipe["native_steps"] == 0, pipe
+
+
+def _same_particles(st, tw, what):
+    pos, prev, rad = tw.arrays()
+    got = st.positions(), st.previous_positions(), st.radii()
+    assert same_bits(got[0], pos), (what, "pos", _differ(got[0], pos))
+    assert same_bits(got[1], prev), (what, "prev", _differ(got[1], prev))
+    assert same_bits(got[2], rad) and np.array_equal(st.uids(), tw.uids), what
+
+
+def _same_flags_and_poses(st, body_poses, bodies_broken, bonds_broken, mover_poses, what):
+    assert same_bits(st.body_poses(), body_poses), (what, "body poses")
+    assert np.array_equal(st.bodies()[1], bodies_broken) and np.array_equal(st.bonds()[1], bonds_broken), (what, "broken flags")
+    assert same_rows(st.mover_poses(), mover_poses), (what, "mover poses", st.mover_poses(), mover_poses)
+
+
+def _same_as_twin(st, tw, what):
+    """the particles, every stored set read back, the poses, the flags and the counters"""
+    _same_particles(st, tw, what)
+    assert same_bits(st.colliders(), tw.colliders) and same_rows(st.movers(), tw.m.movers), (what, "colliders / movers")
+    for target in ("colliders", "movers"):
+        assert same_rows(st.surfaces(target), tw.surfaces(target)), (what, target, "surfaces")
+    assert same_rows(st.fields(), tw.fields) and st.collider_sweep() is tw.sweep, (what, "fields / sweep")
+    rec, _ = st.bonds()
+    assert same_rows(rec, tw.bonds), (what, "bonds")
+    rec, _, uid, rest = st.bodies()
+    assert same_rows(rec, tw.bodies) and np.array_equal(uid, tw.member_uid) and same_bits(rest, tw.member_rest), (what, "bodies")
+    _same_flags_and_poses(st, tw.poses, tw.bodies_broken, tw.broken, tw.m.poses(), what)
+    got, want = E.state_counters(st), tw.counters()
+    assert got == want, (what, {k: (got[k], want[k]) for k in got if got[k] != want[k]})
+
+
+# ---- the references: the twin alone, once per configuration ---------------------------------------------------------
+@pytest.fixture(scope="module")
+def reference(oracle):
+    """reference(case) -> (frames after each of the 40 steps, counters at the end) of the twin armed as the case says"""
+    done = {}
+
+    def get(case):
+        if case not in done:
+            arms = _arms(case)
+            tw = E.twin(oracle, arms)
+            assert tw.armed() == tuple(a for a in arms if a.split("_")[0] + "s" in arms or "_" not in a)   # (no set, no surfaces)
+            done[case] = (E.frames(tw), tw.counters())
+            tw.close()
+        return done[case]
+    return get
+
+
+@pytest.fixture(scope="module")
+def resorted(oracle):
+    """all arms, the re-sorts of gpe_run(40, resort_every = 16, resort_first)"""
+    tw = E.twin(oracle)
+    out = E.frames(tw, resort_every=16, resort_first=True), tw.counters()
+    tw.close()
+    return out
+
+
+# ---- 1, 2. every step equals the twin: all arms, each one left out, none ---------------------------------------------
+@pytest.mark.parametrize("mode", ["native", "compat"])
+@pytest.mark.parametrize("case", CASES)
+def test_every_step_equals_the_twin(gpe, reference, case, mode):
+    """40 gpe_step calls over scene(): pos and prev after each, the poses and the broken flags after every tenth, every
+    counter at the end.  `all` pins the order of the six passes; the other cases are bit-identical to the twin configured
+    the same way and bisect a failure of `all`."""
+    frames, counters = reference(case)
+    if case == "all":
+        assert counters["sweep"]["stopped"] > 0 and counters["bodies"]["broken"] > 0 and counters["movers"]["pushed"] > 0
+    st = _state(gpe, mode, _arms(case))
+    for s in range(STEPS):
+        st.update(DT)
+        f = frames[s]
+        pos, prev = st.positions(), st.previous_positions()
+        assert same_bits(pos, f.pos), (case, s, "pos", _differ(pos, f.pos))
+        assert same_bits(prev, f.prev), (case, s, "prev", _differ(prev, f.prev))
+        if s % 10 == 9:
+            _same_flags_and_poses(st, f.body_poses, f.bodies_broken, f.bonds_broken, f.mover_poses, (case, s))
+    got = E.state_counters(st)
+    assert got == counters, {k: (got[k], counters[k]) for k in got if got[k] != counters[k]}
+    _ran_native(gpe, st, mode, STEPS)
+    _end(st)
+
+
+# ---- 3. one run equals the loop, and the observers see the end of the chain -------------------------------------------
+@pytest.mark.parametrize("mode", ["native", "compat"])
+def test_one_run_equals_the_loop_and_the_observers_see_the_end_of_the_chain(gpe, resorted, mode):
+    frames, counters = resorted
+    st = _state(gpe, mode)
+    st.tracers_begin(TRACKED, every=1, frames=64, prev=True, index=True)
+    st.monitor_begin(every=1, frames=64)
+    st.run(DT, STEPS, resort_every=16, resort_first=True)
+    last = frames[-1]
+    pos, prev = st.positions(), st.previous_positions()
+    assert same_bits(pos, last.pos), _differ(pos, last.pos)
+    assert same_bits(prev, last.prev), _differ(prev, last.prev)
+    assert np.array_equal(st.uids(), last.uids) and not np.array_equal(last.uids, np.arange(E.N))
+    _same_flags_and_poses(st, last.body_poses, last.bodies_broken, last.bonds_broken, last.mover_poses, "run")
+    got = E.state_counters(st)
+    assert got == counters, {k: (got[k], counters[k]) for k in got if got[k] != counters[k]}
+    assert st.bonds_info()["resolves"] == st.bodies_info()["resolves"] == 3          # before steps 0, 16, 32
+    tr = st.tracers_read()
+    rec, recorded = st.monitor_read()
+    assert len(tr.step) == STEPS and recorded == STEPS
+    for s, f in enumerate(frames):                                     # frames taken behind all six passes
+        slot = BM.slots_of(f.uids, TRACKED)
+        assert (slot >= 0).all() and np.array_equal(tr.index[s], slot), s
+        assert same_bits(tr.pos[s], f.pos[slot]) and same_bits(tr.prev[s], f.prev[slot]), s
+        assert rec["min_y"][s] == f.pos[:, 1].min() and rec["max_y"][s] == f.pos[:, 1].max() and rec["n"][s] == E.N, s
+    st.tracers_end(); st.monitor_end()
+    _ran_native(gpe, st, mode, STEPS)
+    _end(st)
+
+
+# ---- 4. one event, every structure ------------------------------------------------------------------------------------
+@pytest.mark.parametrize("mode", ["native", "compat"])
+def test_one_event_invalidates_every_structure(gpe, oracle, mode):
+    """Fully armed and stepping: a radius edit to three times the largest and back, gpe_set_world to twice the size and
+    back, an add past the capacity, the removal of a body member and of a bonded uid, a re-sort, a spell in the other
+    mode; three steps and a full comparison behind each."""
+    from tests.test_gpu_fields import grid_dims
+    L = gpe._lib
+    st = _state(gpe, mode)
+    tw = E.twin(oracle)
+    rng = np.random.default_rng(5)
+    total = [0]
+
+    def steps(what, k=3):
+        for _ in range(k):
+            st.update(DT); tw.step(DT)
+        total[0] += k
+        _same_as_twin(st, tw, what)
+        assert tw.fully_armed(), what
+        return st.colliders_info(), st.movers_info(), st.fields_info()
+
+    def grids(infos):
+        return [(i["grid_x"], i["grid_y"]) for i in infos]
+
+    start = steps("start", 6)
+    assert grids(start)[2] == grid_dims(E.WORLD)[1:]
+    # a new largest radius: the particle grid, the colliders' and the movers' grids are cut anew in one step
+    who = np.array([700], U32)
+    st.edit_particles(indices=who, radii=np.array([1.5], F32)); tw.edit(who, "index", radius=np.array([1.5], F32))
+    up = steps("radius up")
+    assert grids(up)[0] != grids(start)[0] and grids(up)[1] != grids(start)[1], (grids(start), grids(up))
+    assert grids(up)[2] == grid_dims(E.WORLD)[1:]                       # (the fields' grid follows the world alone)
+    st.edit_particles(indices=who, radii=np.array([0.5], F32)); tw.edit(who, "index", radius=np.array([0.5], F32))
+    down = steps("radius down")
+    assert grids(down) == grids(start)
+    # the world doubles: one particle put on the floor's end and one into the well, both in the newly covered part
+    big = (2 * E.WORLD[0], 2 * E.WORLD[1])
+    st.ctx.call("gpe_set_world", *big); tw.set_world(*big)
+    who, where = np.array([300, 301], U32), np.array([[63.0, 39.75], [85.0, 45.0]], F32)
+    st.edit_particles(indices=who, positions=where); tw.edit(who, "index", pos=where)
+    half = np.full(1, 0.5, F32)
+    assert (where[:, 0] > E.WORLD[0]).all() and CM.touch(where[:1], half, tw.colliders[0])[0][0] and FM.matches(where[1:], tw.fields[1])[0]
+    wide = steps("world grown")
+    assert grids(wide)[0] != grids(start)[0] and grids(wide)[1] != grids(start)[1], (grids(start), grids(wide))
+    assert grids(wide)[2] == grid_dims(big)[1:]
+    home = np.array([[30.0, 20.0], [32.0, 20.0]], F32)
+    st.edit_particles(indices=who, positions=home); tw.edit(who, "index", pos=home)
+    st.ctx.call("gpe_set_world", *E.WORLD); tw.set_world(*E.WORLD)
+    back = steps("world back")
+    assert grids(back) == grids(start)
+    # an add past the capacity: every particle buffer moves
+    k = 1100
+    grow = np.stack([rng.uniform(2, 58, k), rng.uniform(2, 28, k)], axis=1).astype(F32)
+    st.add_particles(grow, np.full(k, 0.25, F32)); tw.add(grow, np.full(k, 0.25, F32))
+    steps("growth")
+    # a member of a live body and a bonded particle leave
+    assert not tw.bodies_broken[1] and not tw.broken.any()
+    gone = np.array([10, 17, 1], U32)                                  # of the first brick; the pair bond's end; the anchored one
+    assert st.remove_particles_by_uid(gone) == tw.remove_uids(gone) == 3
+    steps("removal")
+    assert not np.isnan(tw.poses[1]).any()                             # the brick goes on with seven members
+    resolves = st.bonds_info()["resolves"], st.bodies_info()["resolves"]
+    st.particles.sort_by_cell_id(); tw.morton_resort()
+    steps("sort_by_cell_id")
+    assert st.bonds_info()["resolves"] > resolves[0] and st.bodies_info()["resolves"] > resolves[1]
+    other = L.MODE_NATIVE if mode == "compat" else L.MODE_COMPAT
+    st.ctx.call("gpe_set_mode", other)
+    steps("the other mode")
+    st.ctx.call("gpe_set_mode", _mode(gpe, mode))
+    steps("the mode back")
+    # (a native step that finds particles outside a world that shrank back is the compat pipeline's: no exact split)
+    pipe = st.ctx.pipeline_info()
+    print(pipe)
+    assert pipe["native_steps"] + pipe["compat_steps"] == total[0], pipe
+    assert pipe["compat_steps" if mode == "native" else "native_steps"] >= 3 and pipe["native_steps"] > 0, pipe
+    tw.close()
+    _end(st)
+
+
+# ---- 5. save and load with everything ---------------------------------------------------------------------------------
+@pytest.mark.parametrize("mode", ["native", "compat"])
+def test_save_and_load_with_all_nine_groups(gpe, reference, tmp_path, mode):
+    """saved after 15 steps, loaded into a fresh context of each mode, 15 more steps: the bits of the uninterrupted twin"""
+    L = gpe._lib
+    frames, _ = reference("all")
+    st = _state(gpe, mode)
+    for s in range(15):
+        st.update(DT)
+    assert frames[14].bodies_broken.any() and not frames[14].bodies_broken.all()
+    path = str(tmp_path / "snap.npz")
+    st.save(path)
+    with np.load(path) as d:
+        assert set(E.GROUPS) <= set(d.files), sorted(d.files)
+        assert np.array_equal(d["bodies_broken"], frames[14].bodies_broken) and d["collider_sweep"].tolist() == [1]
+        assert same_rows(d["mover_poses"], frames[14].mover_poses)
+    backs = [gpe.State.load(path, mode=m, flags=L.FLAG_GUARD_ALLOCS) for m in (_mode(gpe, mode), _mode(gpe, "compat" if mode == "native" else "native"))]
+    for h in backs:
+        assert h.collider_sweep() is True and np.array_equal(h.bodies()[1], frames[14].bodies_broken)
+        assert same_rows(h.mover_poses(), frames[14].mover_poses)
+        for target in ("colliders", "movers"):
+            assert same_rows(h.surfaces(target), st.surfaces(target)) and len(h.surfaces(target)) > 0
+    for s in range(15, 30):
+        for h in [st] + backs:
+            h.update(DT)
+            pos, prev = h.positions(), h.previous_positions()
+            assert same_bits(pos, frames[s].pos), (s, h is st, "pos", _differ(pos, frames[s].pos))
+            assert same_bits(prev, frames[s].prev), (s, h is st, "prev", _differ(prev, frames[s].prev))
+    f = frames[29]
+    for h in [st] + backs:
+        _same_flags_and_poses(h, f.body_poses, f.bodies_broken, f.bonds_broken, f.mover_poses, "after load")
+    _ran_native(gpe, st, mode, 30)
+    _ran_native(gpe, backs[0], mode, 15)
+    _ran_native(gpe, backs[1], "compat" if mode == "native" else "native", 15)
+    for h in [st] + backs:
+        _end(h)
+
+
+# ---- 6. the random interleaving ---------------------------------------------------------------------------------------
+@pytest.mark.parametrize("mode", ["native", "compat"])
+@pytest.mark.parametrize("seed", E.SEEDS)
+def test_a_random_interleaving_against_the_twin(gpe, oracle, seed, mode):
+    """plan(seed) against a State and the twin: after every operation the particles, every stored set read back, the
+    sweep's mode, the poses, the broken flags and the counters"""
+    seq = E.Sequence(E.plan(seed), oracle, gpe=gpe, mode_name=mode, compare=_same_as_twin, end=_end)
+    try:
+        seq.run()
+    finally:
+        print("\n".join(seq.log))
+        print(dict(seq.cov))
+        seq.close()
+    seq.cov.check()
+    # (no exact split: the spell in the other mode apart, a native step that finds particles outside a world that shrank
+    # back is the compat pipeline's)
+    print("native steps %d, compat steps %d, in the other mode %d" % (seq.native_steps, seq.compat_steps, seq.other_steps))
+    assert seq.native_steps + seq.compat_steps == seq.steps and seq.native_steps > 0
+    if mode == "compat":
+        assert seq.native_steps <= seq.other_steps
