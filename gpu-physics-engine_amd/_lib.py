@@ -387,6 +387,9 @@ SYMBOLS = [
     ("gpe_set_collider_sweep", _I32, [_VP, _U32]),
     ("gpe_get_collider_sweep", _I32, [_VP, C.POINTER(_U32)]),
     ("gpe_get_sweep_info", _I32, [_VP, C.POINTER(GpeSweepInfo)]),
+    ("gpe_set_mover_sweep", _I32, [_VP, _U32]),
+    ("gpe_get_mover_sweep", _I32, [_VP, C.POINTER(_U32)]),
+    ("gpe_get_mover_sweep_info", _I32, [_VP, C.POINTER(GpeSweepInfo)]),
     ("gpe_set_bonds", _I32, [_VP, C.POINTER(GpeBond), _U64, C.c_uint32]),
     ("gpe_get_bonds", _I32, [_VP, C.POINTER(GpeBond), C.POINTER(C.c_uint8), _U64, C.POINTER(_U64)]),
     ("gpe_apply_bonds", _I32, [_VP]),

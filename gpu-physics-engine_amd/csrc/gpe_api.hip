@@ -1004,6 +1004,7 @@ gpe_status gpe_destroy(gpe_ctx *c)
     bodies_release(c);
     fields_release(c);
     movers_release(c);
+    mover_sweep_release(c);
     sort_release(c);
     scan_release(c);
     onesweep_release(c);

@@ -546,6 +546,25 @@ struct MoverPassArgs {
     float2 *prev = nullptr;                      // ... and the previous positions it rewrites under a hit
 };
 
+// the sweep of the movers (gpe_set_mover_sweep; gpe_movers.hip, k_mover_sweep.hip, k_mover_sweep.h).  A mode of their
+// pass, like gravity: not part of MoverState, so a new mover set leaves it alone.  The three buffers are allocated when
+// the mode is first switched on, for kMoversMax movers, and kept until gpe_destroy
+struct MoverCarry;
+struct MoverSweepState {
+    uint32_t mode = 0;                           // GPE_SWEEP_OFF / GPE_SWEEP_ON
+    uint64_t passes = 0;                         // swept passes enqueued since the last gpe_set_mover_sweep
+    unsigned long long *counts = nullptr;        // two words: particles swept, particles stopped, since then (null: never on)
+    MoverCarry *carry = nullptr;                 // kMoversMax: what each mover carries a point by in the last step
+    float4 *old = nullptr;                       // kMoversMax: the posed capsules before the last advance
+};
+
+// what the swept build and the swept pass take beside MoverBuildArgs / MoverPassArgs (P.old, P.surf and P.prev as there)
+struct MoverSweepArgs {
+    MoverCarry *carry = nullptr;                 // one per mover: written by the build, read by the pass
+    float2 *prev = nullptr;                      // the pass: read for every particle, written where a surface acted
+    unsigned long long *counts = nullptr;        // the pass: two words, swept and stopped
+};
+
 struct SortWorkspace {
     uint32_t *keys_b = nullptr, *vals_b = nullptr;   // ping-pong partners, cap entries each
     uint64_t cap = 0;
@@ -898,6 +917,7 @@ struct gpe_ctx {
     gpe::BodyState bodies;
     gpe::FieldState fields;
     gpe::MoverState movers;
+    gpe::MoverSweepState mover_sweep;
     gpe::QueryWorkspace query_ws;
     gpe::ContactsWorkspace contacts_ws;
     gpe::ClustersWorkspace clusters_ws;
@@ -1077,6 +1097,7 @@ gpe_status refuse_movers(gpe_ctx *c, const char *who);      // GPE_ERR_UNSUPPORT
 gpe_status movers_check_dt(gpe_ctx *c, float dt, const char *who);  // GPE_ERR_INVALID_ARG: dt breaks the set's contract; before anything is launched
 gpe_status movers_after_step(gpe_ctx *c, float dt);         // after every step of gpe_step / gpe_run, behind the bodies, before the colliders
 void movers_release(gpe_ctx *c);
+void mover_sweep_release(gpe_ctx *c);                       // gpe_destroy: the mode's counters and records
 
 // profiling scope: a pair of timestamps on ctx->stream when ctx->profiling, else nothing -- slots of the stamp buffer
 // (scope_stamps.h), or hipEvents where scope_uses_stamps() says no.  kSharedBoundaries: inside a ScopeRegion the scope
@@ -1321,6 +1342,12 @@ gpe_status launch_colliders_sweep(gpe_ctx *c, float2 *pos, float2 *prev, const f
 // pushes pos[0, n) in place
 gpe_status launch_movers_build(gpe_ctx *c, const MoverBuildArgs &B);
 gpe_status launch_movers_pass(gpe_ctx *c, float2 *pos, const float *radius, uint64_t n, const MoverPassArgs &P);
+// their swept form (k_mover_sweep.hip): the build also writes B.old (never null here) and W.carry and lists every mover
+// where its motion reaches; the pass judges the paths relative to each mover.  P.old as the build wrote it; P.surf may
+// be null; P.prev is unused (W.prev)
+gpe_status launch_movers_sweep_build(gpe_ctx *c, const MoverBuildArgs &B, const MoverSweepArgs &W);
+gpe_status launch_movers_sweep(gpe_ctx *c, float2 *pos, const float *radius, uint64_t n, const MoverPassArgs &P,
+                               const MoverSweepArgs &W);
 // native pipeline: its host side (gpe_native.hip; the kernels and their launchers: k_native.hip, native_launch.h)
 gpe_status native_configure(gpe_ctx *c);
 bool native_should_run(gpe_ctx *c);

@@ -3,7 +3,8 @@
 // k_movers_pass (k_movers.hip).  Nothing in a step synchronises or asks the host for more than the grid's view
 // (mover_grid.h: host arithmetic on the world and the radius bound).  gpe_api.hip calls movers_check_dt before a step
 // launches anything, movers_after_step from gpe_step / gpe_run behind the bodies and before the static colliders, and
-// movers_release from gpe_destroy.
+// movers_release from gpe_destroy.  The movers' sweep (gpe_set_mover_sweep, at the end of this file) is a mode of the
+// same three enqueues: while it is on, the build and the pass are k_mover_sweep.hip's.
 #include <math.h>
 #include <string.h>
 
@@ -58,6 +59,10 @@ static gpe_status movers_pass(gpe_ctx *c, float dt)
 {
     MoverState &S = c->movers;
     if (S.set.empty() || c->n == 0 || !c->pos) return GPE_OK;
+    MoverSweepState &M = c->mover_sweep;
+    const bool swept = M.mode == GPE_SWEEP_ON;                         // the swept build and pass (k_mover_sweep.hip)
+    if (swept && (!c->prev || !M.counts || !M.carry || !M.old))
+        return fail(c, GPE_ERR_STATE, "the swept movers' pass: no previous positions, counters or records");
     const uint32_t k = (uint32_t)S.set.size();
     const MoverGridView g = mover_grid_choose(c->max_radius, c->cfg.world_width, c->cfg.world_height);
     const uint64_t cells = (uint64_t)g.view.gx * g.view.gy;            // <= kMoverGridMaxCells: what S.grid was sized for
@@ -73,7 +78,14 @@ static gpe_status movers_pass(gpe_ctx *c, float dt)
     B.masks = reinterpret_cast<unsigned long long *>(S.grid);
     B.summary = reinterpret_cast<uint32_t *>(S.grid + cells * 8ull * S.words);
     B.listed = reinterpret_cast<unsigned long long *>(S.grid + at_listed);
-    GPE_TRY(launch_movers_build(c, B));
+    MoverSweepArgs W;
+    if (swept) {                                                       // old also without surfaces, the carry records, the motion's cells
+        B.old = M.old;
+        W.carry = M.carry; W.prev = c->prev; W.counts = M.counts;
+        GPE_TRY(launch_movers_sweep_build(c, B, W));
+    } else {
+        GPE_TRY(launch_movers_build(c, B));
+    }
     S.view = g;
     S.built = true;
     MoverPassArgs P;
@@ -85,7 +97,14 @@ static gpe_status movers_pass(gpe_ctx *c, float dt)
     if (S.surf) {
         P.surf = S.surf; P.old = S.old; P.prev = c->prev;
     }
-    GPE_TRY(launch_movers_pass(c, c->pos, c->radius, c->n, P));
+    if (swept) {
+        P.old = M.old;
+        P.prev = nullptr;
+        GPE_TRY(launch_movers_sweep(c, c->pos, c->radius, c->n, P, W));
+        M.passes += 1;
+    } else {
+        GPE_TRY(launch_movers_pass(c, c->pos, c->radius, c->n, P));
+    }
     S.passes += 1;
     return GPE_OK;
 }
@@ -254,6 +273,82 @@ gpe_status gpe_get_movers_info(gpe_ctx *c, gpe_movers_info *info)
         GPE_TRY(check_device_errors(c));                               // (synchronises the stream)
         out.pushed = pushed;
         out.listed = listed;
+    }
+    *info = out;
+    return GPE_OK;
+}
+
+// ---- the sweep of the movers: a mode of the pass above and its two counters ---------------------------------------------
+void gpe::mover_sweep_release(gpe_ctx *c)
+{
+    MoverSweepState &M = c->mover_sweep;
+    dev_free(c, M.counts); dev_free(c, M.carry); dev_free(c, M.old);
+    M = MoverSweepState();
+}
+
+gpe_status gpe_set_mover_sweep(gpe_ctx *c, uint32_t mode)
+{
+    if (!c) return GPE_ERR_INVALID_ARG;
+    if (mode != GPE_SWEEP_OFF && mode != GPE_SWEEP_ON)
+        return fail(c, GPE_ERR_INVALID_ARG, "gpe_set_mover_sweep: mode must be GPE_SWEEP_OFF or GPE_SWEEP_ON");
+    if (is_sharded(c)) return refuse_sharded(c, "gpe_set_mover_sweep");
+    GPE_HIP(c, hipSetDevice(c->device));
+    GPE_HIP(c, hipStreamSynchronize(c->stream));                       // (a pass in flight counts into the old words)
+    MoverSweepState &M = c->mover_sweep;
+    if (mode == GPE_SWEEP_ON && !(M.counts && M.carry && M.old)) {
+        // counts: two words, written by index 0 and 1 alone; carry and old: one row per mover, written and read below the
+        // set's size <= kMoversMax.  no slack.  Kept until gpe_destroy once the mode has been on: a new set needs no new ones
+        MoverSweepState N;
+        gpe_status st = ws_alloc(c, "gpe_set_mover_sweep", &N.counts, 2, 0, "grid.msweep_counts");
+        if (st == GPE_OK) st = ws_alloc(c, "gpe_set_mover_sweep", &N.carry, kMoversMax, 0, "grid.msweep_carry");
+        if (st == GPE_OK) st = ws_alloc(c, "gpe_set_mover_sweep", &N.old, kMoversMax, 0, "grid.msweep_old");
+        if (st != GPE_OK) {
+            const std::string why = c->last_error;
+            dev_free(c, N.counts); dev_free(c, N.carry); dev_free(c, N.old);
+            c->last_error = why;
+            return st;
+        }
+        dev_free(c, M.counts); dev_free(c, M.carry); dev_free(c, M.old);
+        M.counts = N.counts; M.carry = N.carry; M.old = N.old;
+    }
+    if (M.counts) {
+        hipError_t e = hipMemsetAsync(M.counts, 0, 2 * sizeof(unsigned long long), c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(c, GPE_ERR_HIP, std::string("gpe_set_mover_sweep: ") + hipGetErrorName(e));
+        }
+    }
+    M.mode = mode;
+    M.passes = 0;
+    return GPE_OK;
+}
+
+gpe_status gpe_get_mover_sweep(const gpe_ctx *c, uint32_t *mode)
+{
+    if (!c || !mode) return GPE_ERR_INVALID_ARG;
+    *mode = c->mover_sweep.mode;
+    return GPE_OK;
+}
+
+gpe_status gpe_get_mover_sweep_info(gpe_ctx *c, gpe_sweep_info *info)
+{
+    if (!c) return GPE_ERR_INVALID_ARG;
+    if (!info || info->struct_size < sizeof(gpe_sweep_info))
+        return fail(c, GPE_ERR_INVALID_ARG, "gpe_get_mover_sweep_info: NULL info or bad struct_size");
+    const MoverSweepState &M = c->mover_sweep;
+    gpe_sweep_info out;
+    memset(&out, 0, sizeof(out));
+    out.struct_size = info->struct_size;
+    out.mode = M.mode;
+    out.passes = M.passes;
+    if (M.counts) {
+        GPE_HIP(c, hipSetDevice(c->device));
+        unsigned long long counts[2] = {0, 0};
+        GPE_HIP(c, hipMemcpyAsync(counts, M.counts, sizeof(counts), hipMemcpyDeviceToHost, c->stream));
+        GPE_TRY(check_device_errors(c));                               // (synchronises the stream)
+        out.swept = counts[0];
+        out.stopped = counts[1];
     }
     *info = out;
     return GPE_OK;

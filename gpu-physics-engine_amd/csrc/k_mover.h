@@ -9,8 +9,9 @@
 //
 // The posed capsule pushes particles exactly as a static collider does (collider_touch, collider_normal, collider_key:
 // the deepest mover only, judged from the position the pass starts with).  The pass writes pos only, which in a Verlet
-// engine hands the particle the wall's velocity.  There is no swept test: a mover must be thicker than one step's
-// relative displacement of mover and particle, or particles are tunnelled through -- hosts make movers thick.
+// engine hands the particle the wall's velocity.  This plain pass has no swept test: a mover must be thicker than one
+// step's relative displacement of mover and particle, or particles are tunnelled through -- hosts make movers thick, or
+// switch the movers' sweep on (gpe_set_mover_sweep; k_mover_sweep.h: the particle's path relative to each mover).
 #pragma once
 
 #include <math.h>
@@ -31,7 +32,7 @@ struct MoverDef {
     float travel;                // LINEAR: > 0: back and forth over this distance; 0: for ever
     float rate;                  // LINEAR: speed = sqrtf(vx*vx + vy*vy); ROTATE: omega
     float ux, uy;                // LINEAR: v / speed ((0, 0) when speed == 0); ROTATE: the pivot
-    float pad0, pad1;
+    float pad0, pad1;            // pad0: mover_arm (k_mover_sweep.h), read by the swept form alone; pad1: 0
 };
 
 // The dt contract's side of a set: the largest |omega|, and among the LINEAR movers that go back and forth (travel > 0;

@@ -14,6 +14,7 @@
 
 #include "../../include/gpe.h"
 #include "k_mover.h"
+#include "k_mover_sweep.h"
 
 namespace gpe {
 
@@ -61,6 +62,7 @@ inline MoverDef mover_define(const gpe_mover &q)
         d.rate = q.omega;
         d.ux = q.px; d.uy = q.py;
     }
+    d.pad0 = mover_arm(d);                                             // (k_mover_sweep.h: the swept pass's gate and listing)
     return d;
 }
 

@@ -691,6 +691,25 @@ class ParticleSystem:
         self.ctx.call("gpe_get_movers_info", C.byref(info))
         return {name: getattr(info, name) for name, _ in L.GpeMoversInfo._fields_ if name not in ("struct_size", "reserved")}
 
+    def set_mover_sweep(self, on):
+        """gpe_set_mover_sweep: on, the movers' pass judges every particle by its path relative to each mover over the step
+        (csrc/k_mover_sweep.h), so a thin piston or blade no longer jumps across particles.  A mode of the pass,
+        independent of set_collider_sweep: it outlives set_movers, set_surfaces and set_mover_poses.  Zeroes the mode's
+        counters; blocks."""
+        self.ctx.call("gpe_set_mover_sweep", L.SWEEP_ON if on else L.SWEEP_OFF)
+
+    def mover_sweep(self):
+        """gpe_get_mover_sweep -> bool."""
+        mode = C.c_uint32(0)
+        self.ctx.call("gpe_get_mover_sweep", C.byref(mode))
+        return mode.value == L.SWEEP_ON
+
+    def mover_sweep_info(self):
+        """gpe_get_mover_sweep_info -> dict(mode, passes, swept, stopped).  Blocks like a download."""
+        info = L.GpeSweepInfo(struct_size=C.sizeof(L.GpeSweepInfo))
+        self.ctx.call("gpe_get_mover_sweep_info", C.byref(info))
+        return {name: getattr(info, name) for name, _ in L.GpeSweepInfo._fields_ if name != "struct_size"}
+
     # Surface materials (not in the reference; include/gpe.h): bounce and friction per static collider or per mover.  While
     # a set holds surfaces its pass also rewrites prev for the particles an obstacle touches.  Step state: save() keeps
     # them; set_colliders / set_movers drop their target's.
@@ -1436,6 +1455,21 @@ class State:
         """ParticleSystem.movers_info -> dict(k, passes, pushed, grid_x, grid_y, mask_words, listed)."""
         return self.particles.movers_info()
 
+    _mover_sweep_on = False                                            # what save() writes: set_mover_sweep is the one way in
+
+    def set_mover_sweep(self, on):
+        """ParticleSystem.set_mover_sweep: the movers' pass judges the path relative to each mover while on."""
+        self.particles.set_mover_sweep(on)
+        self._mover_sweep_on = bool(on)
+
+    def mover_sweep(self):
+        """ParticleSystem.mover_sweep -> bool."""
+        return self.particles.mover_sweep()
+
+    def mover_sweep_info(self):
+        """ParticleSystem.mover_sweep_info -> dict(mode, passes, swept, stopped)."""
+        return self.particles.mover_sweep_info()
+
     def set_surfaces(self, target, rows):
         """ParticleSystem.set_surfaces: bounce and friction (rows of SURFACE_DTYPE) per collider ("colliders") or per
         mover ("movers")."""
@@ -1621,8 +1655,10 @@ class State:
         bodies with their members and broken flags (`bodies`, `bodies_broken`, `body_member_uid`, `body_member_rest`) and
         force fields (`fields`) and moving colliders with their poses (`movers`, `mover_poses`), and the surfaces of
         the two sets where present (`collider_surfaces`, `mover_surfaces`), and the static colliders' sweep where it is
-        on (`collider_sweep`)."""
+        on (`collider_sweep`), and the movers' sweep where it is on (`mover_sweep`)."""
         extra = {}
+        if self._mover_sweep_on:
+            extra.update(mover_sweep=np.array([L.SWEEP_ON], np.uint32))
         if self.collider_sweep():
             extra.update(collider_sweep=np.array([L.SWEEP_ON], np.uint32))
         for target in ("colliders", "movers"):
@@ -1700,6 +1736,8 @@ class State:
                 st.set_mover_poses(d["mover_poses"].astype(MOVER_POSE_DTYPE))
             if "mover_surfaces" in d.files:                        # (after their set and its poses)
                 st.set_surfaces("movers", d["mover_surfaces"].astype(SURFACE_DTYPE))
+            if "mover_sweep" in d.files:                           # (a file without it: off)
+                st.set_mover_sweep(bool(d["mover_sweep"][0]))
             return st
 
     def close(self):

@@ -536,6 +536,23 @@ class ParticleSystem {
         ctx_->call(gpe_get_movers_info(ctx_->raw(), &info));
         return info;
     }
+    // the movers' sweep: the pass judges every particle by its path relative to each mover over the step, so a thin
+    // piston or an R = 0 blade does not jump across particles (csrc/k_mover_sweep.h).  A mode of the pass, independent
+    // of set_collider_sweep: it outlives set_movers / set_surfaces / set_mover_poses.
+    void set_mover_sweep(bool on) { ctx_->call(gpe_set_mover_sweep(ctx_->raw(), on ? GPE_SWEEP_ON : GPE_SWEEP_OFF)); }
+    bool mover_sweep() const
+    {
+        uint32_t mode = GPE_SWEEP_OFF;
+        ctx_->call(gpe_get_mover_sweep(ctx_->raw(), &mode));
+        return mode == GPE_SWEEP_ON;
+    }
+    gpe_sweep_info mover_sweep_info() const
+    {
+        gpe_sweep_info info{};
+        info.struct_size = sizeof(info);
+        ctx_->call(gpe_get_mover_sweep_info(ctx_->raw(), &info));
+        return info;
+    }
     // not in the reference: surface materials (include/gpe.h) -- bounce and friction, one row per static collider
     // (GPE_SURFACES_OF_COLLIDERS) or per mover (GPE_SURFACES_OF_MOVERS) of the set held now.  While a set holds surfaces
     // its pass also rewrites prev for the particles an obstacle touches.  set_colliders / set_movers drop their

@@ -384,7 +384,8 @@ gpe_status gpe_monitor_end(gpe_ctx *ctx);
  *         contact: pos = clamp(x_1 + n_1 * max(s_1 - d_1, 0)), prev untouched, no surface.  Otherwise pos = q (and
  *         prev = prev' where a surface acted).
  *    So a particle ends at a point whose path from prev enters nothing deeper than that slop, or at the first point where
- *    it touched anything; a corner still takes two steps.  What stays a limit: the movers have no sweep; prev is the
+ *    it touched anything; a corner still takes two steps.  What stays a limit: the movers have no sweep
+ *    of this mode's making (GPE_SWEEP_ON here leaves their pass plain; theirs is gpe_set_mover_sweep, below); prev is the
  *    position after the step's collision response, so a particle the collision solver shoves across a wall in one step
  *    is not caught (a wall has to be thicker than one collision push, not than one displacement); a particle that
  *    starts on the wrong side of a wall stays there.  The sweep is a mode of the pass, like gravity: allowed with no
@@ -468,8 +469,38 @@ gpe_status gpe_get_sweep_info(gpe_ctx *ctx, gpe_sweep_info *info);         /* sy
  *    colliders' touch, key, normal and clamp (above), unchanged, every mover judged from the position the pass starts
  *    with.  Only pos is written, prev stays: in a Verlet engine that hands the particle the wall's velocity.  A particle
  *    no mover touches keeps every bit.
- *  - No swept test: a mover must be thicker than one step's relative displacement of mover and particle.  Make movers
- *    thick.
+ *  - Without the movers' sweep (next item) there is no swept test: a mover must be thicker than one step's relative
+ *    displacement of mover and particle.  Make movers thick, or switch their sweep on.
+ *  - The movers' sweep.  gpe_set_mover_sweep(ctx, GPE_SWEEP_ON) makes the pass judge a particle by its path RELATIVE TO
+ *    EACH MOVER over the step (csrc/k_mover_sweep.h is the one definition, csrc/k_mover_sweep.hip the build and the
+ *    pass; the same arithmetic rules).  With C0_j and C1_j mover j's capsule before and after this step's advance:
+ *      1. y0_j = prev carried rigidly with mover j over the step: LINEAR: prev + (a1 - a0); ROTATE: prev turned about
+ *         the pivot by (cd, sd) = (c1*c0 + s1*s0, s1*c0 - c1*s0).  A mover whose state did not change: y0_j = prev,
+ *         bit for bit.  The relative path is taken as the chord y0_j -> pos.
+ *      2. pos - y0_j not finite, or exactly zero: mover j judges the particle by the plain touch at pos, a contact with
+ *         t = 1.  (A particle at rest under a mover at rest: the plain pass's contact.)
+ *      3. a turning ROTATE mover is considered only if the world path prev -> pos comes within (arm_j + R_j) + |r| of
+ *         its pivot, arm_j the farthest end of the rest capsule from the pivot: the chord of a fast particle can cut
+ *         through a disc its true path never enters.
+ *      4. the contact of the static sweep (above) on y0_j -> pos against C1_j; the least t wins, then the greatest depth,
+ *         then the lowest j.
+ *      5. q = clamp(pos + n * depth); with a surface on the winner (not GPE_SURFACE_PLAIN, pos - prev finite) the
+ *         surface rule with that normal and depth and the wall's displacement at the contact gives q and prev'.
+ *      6. verified once: if any mover has a contact (1 to 4 with q for pos) deeper than 2^-10 * s_j the particle stops
+ *         at its first contact, prev untouched, no surface.
+ *    Guaranteed: a particle that starts the step on one side of a blade, relative to the blade, and whose chord crosses
+ *    the blade's stretch does not end on the other side.  Not: the chord is off by up to |omega*dt| * |pos - prev| / 4
+ *    between its ends (fast particles near rotors); the collision solver's own pushes are not swept; a particle that
+ *    starts inside the capsule is pushed as before; two movers closing on one particle are resolved by the first
+ *    contact and the one verification, no further.  In this mode the build lists a mover in every cell its motion
+ *    reaches (a LINEAR mover's parallelogram, a ROTATE mover's disc); no result depends on the grid.  The mode is step
+ *    state like gravity, independent of gpe_set_collider_sweep: allowed with no movers set, kept by gpe_set_movers
+ *    (also with k == 0), gpe_set_surfaces, gpe_set_mover_poses and everything movers survive; gpe_apply_movers follows
+ *    it.  Off (the default), the kernels and the bits are those of a context that never heard of it.
+ *    gpe_set_mover_sweep waits for the stream and zeroes the two counters; a mode other than GPE_SWEEP_OFF /
+ *    GPE_SWEEP_ON: GPE_ERR_INVALID_ARG; on a sharded context: GPE_ERR_UNSUPPORTED.  gpe_get_mover_sweep_info fills a
+ *    gpe_sweep_info: passes run in the swept form since the last gpe_set_mover_sweep, the particles whose winner had
+ *    0 < t < 1 (swept) and those that stopped (6), summed; it synchronises.
  *  - The set and the poses are step state: they survive gpe_set_particles, adds, removals, edits, re-sorts, growth and
  *    gpe_set_world; gpe_destroy frees them.  Movers name no particle.
  *  - The pass finds a particle's movers through a coarse grid (at most 128 x 128 cells) of bit masks, built on the
@@ -518,6 +549,9 @@ gpe_status gpe_get_mover_poses(gpe_ctx *ctx, gpe_mover_pose *out, uint64_t capac
 gpe_status gpe_set_mover_poses(gpe_ctx *ctx, const gpe_mover_pose *poses, uint64_t k);
 gpe_status gpe_apply_movers(gpe_ctx *ctx, float dt);                       /* advance + one pass now, stream-ordered, no sync */
 gpe_status gpe_get_movers_info(gpe_ctx *ctx, gpe_movers_info *info);       /* synchronises (reads the device counters) */
+gpe_status gpe_set_mover_sweep(gpe_ctx *ctx, uint32_t mode);               /* GPE_SWEEP_*; synchronises */
+gpe_status gpe_get_mover_sweep(const gpe_ctx *ctx, uint32_t *mode);
+gpe_status gpe_get_mover_sweep_info(gpe_ctx *ctx, gpe_sweep_info *info);   /* synchronises (reads the device counters) */
 
 /* ---- surface materials (not in the reference) ----------------------------------------------------------------------
  * Bounce and friction, per obstacle: a ball that rebounds from the floor, a particle that slides to a halt, a shelf
