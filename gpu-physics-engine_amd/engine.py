@@ -1455,12 +1455,9 @@ class State:
         """ParticleSystem.movers_info -> dict(k, passes, pushed, grid_x, grid_y, mask_words, listed)."""
         return self.particles.movers_info()
 
-    _mover_sweep_on = False                                            # what save() writes: set_mover_sweep is the one way in
-
     def set_mover_sweep(self, on):
         """ParticleSystem.set_mover_sweep: the movers' pass judges the path relative to each mover while on."""
         self.particles.set_mover_sweep(on)
-        self._mover_sweep_on = bool(on)
 
     def mover_sweep(self):
         """ParticleSystem.mover_sweep -> bool."""
@@ -1657,7 +1654,7 @@ class State:
         the two sets where present (`collider_surfaces`, `mover_surfaces`), and the static colliders' sweep where it is
         on (`collider_sweep`), and the movers' sweep where it is on (`mover_sweep`)."""
         extra = {}
-        if self._mover_sweep_on:
+        if self.mover_sweep():
             extra.update(mover_sweep=np.array([L.SWEEP_ON], np.uint32))
         if self.collider_sweep():
             extra.update(collider_sweep=np.array([L.SWEEP_ON], np.uint32))

@@ -1,10 +1,10 @@
-"""Every pass behind a step armed at once: bonds -> bodies -> movers -> static colliders (plain / surfaces / swept) ->
-fields, the order of gpe_step and gpe_run (csrc/gpe_api.hip).  TEST INFRASTRUCTURE ONLY.
+"""Every pass behind a step armed at once: bonds -> bodies -> movers (plain / surfaces / swept) -> static colliders
+(plain / surfaces / swept) -> fields, the order of gpe_step and gpe_run (csrc/gpe_api.hip).  TEST INFRASTRUCTURE ONLY.
 
 Everything is one twin over the two chains of twins the features' own tests use (tests/_bodies_model.Twin: bonds,
-bodies, plain colliders; tests/_sweep_model.Twin: movers, surfaces, sweep, fields).  It writes no physics: every pass is
-the model function its feature's tests pin against the device, and tests/test_everything_cpu.py ties it bit for bit to
-the two existing twins.  THE NEXT PASS BEHIND A STEP IS ADDED HERE: its twin into the bases, its call into step().
+bodies, plain colliders; tests/_sweep_model.Twin: movers, surfaces, sweep, fields) with the movers' sweep of
+tests/_mover_sweep_model.Mixin in front.  It writes no physics: every pass is the model function its feature's tests pin
+against the device, and tests/test_everything_cpu.py ties it bit for bit to the three existing twins.  THE NEXT PASS BEHIND A STEP IS ADDED HERE: its twin into the bases, its call into step().
 
 scene() is the staged scene of the CPU and GPU tests, arm() sets its features on a twin or on a State (their methods
 share names), plan(seed) a list of operations and Sequence the thing that applies them to a twin and, when it has one, to
@@ -20,6 +20,7 @@ import numpy as np
 from tests import _bodies_model as BD
 from tests import _bonds_model as BM
 from tests import _fields_model as FM
+from tests import _mover_sweep_model as MS
 from tests import _movers_model as MM
 from tests import _surfaces_model as SM
 from tests import _sweep_model as SW
@@ -31,14 +32,15 @@ DT = 1.0 / 60.0
 DTS = (1.0 / 60.0, 1.0 / 120.0)
 STEPS = 40
 SEEDS = (1, 2, 3)
-ARMS = ("bonds", "bodies", "movers", "mover_surfaces", "colliders", "collider_surfaces", "sweep", "fields")
-# the arrays of a snapshot that holds all nine optional groups (State.save)
+ARMS = ("bonds", "bodies", "movers", "mover_surfaces", "mover_sweep", "colliders", "collider_surfaces", "sweep", "fields")
+# the arrays of a snapshot that holds all ten optional groups (State.save; the movers' poses belong to the movers' group)
 GROUPS = ("colliders", "collider_surfaces", "collider_sweep", "bonds", "bodies", "fields", "movers", "mover_poses",
-          "mover_surfaces", "uids")
+          "mover_surfaces", "mover_sweep", "uids")
 
 
-class Everything(BD.Twin, SW.Twin):
-    """One context with all seven features: the MRO runs through both chains once, every constructor is cooperative."""
+class Everything(MS.Mixin, BD.Twin, SW.Twin):
+    """One context with all eight features: the MRO runs through both chains once, every constructor is cooperative;
+    the mixin in front makes self.m a set that holds the movers' sweep (a mode of the context, not of the set)."""
 
     def __init__(self, *a, **kw):
         super().__init__(*a, **kw)
@@ -71,7 +73,7 @@ class Everything(BD.Twin, SW.Twin):
     def armed(self):
         """-> the arms that are set"""
         on = dict(bonds=len(self.bonds) > 0, bodies=len(self.bodies) > 0, movers=len(self.m) > 0,
-                  mover_surfaces=self.m.surfaces is not None, colliders=len(self.colliders) > 0,
+                  mover_surfaces=self.m.surfaces is not None, mover_sweep=self.m.sweep, colliders=len(self.colliders) > 0,
                   collider_surfaces=self.collider_surfaces is not None, sweep=self.sweep, fields=len(self.fields) > 0)
         return tuple(a for a in ARMS if on[a])
 
@@ -80,11 +82,12 @@ class Everything(BD.Twin, SW.Twin):
 
     def reloaded(self):
         """State.save() / State.load(): every set is set anew (its counters start again, the body poses are unknown
-        until a pass), the broken flags, the movers' states and the sweep's mode are kept"""
+        until a pass), the broken flags, the movers' states and the two sweeps' modes are kept"""
         self.passes = self.pushed = 0
         self.bond_passes = self.body_passes = 0
         self.poses = np.full((len(self.bodies), 4), np.nan, F32)
         self.m.passes = self.m.pushed = 0
+        self.m.sweep_passes = self.m.swept = self.m.stopped = 0
         self.sweep_passes = self.swept = self.stopped = 0
         self.field_passes = self.field_touched = 0
 
@@ -93,6 +96,7 @@ class Everything(BD.Twin, SW.Twin):
         return dict(colliders=dict(k=len(self.colliders), passes=self.passes, pushed=self.pushed),
                     movers=dict(k=len(self.m), passes=self.m.passes, pushed=self.m.pushed),
                     sweep=dict(mode=int(self.sweep), passes=self.sweep_passes, swept=self.swept, stopped=self.stopped),
+                    mover_sweep=self.mover_sweep_info(),
                     bonds=self.bonds_info(), bodies=self.bodies_info(),
                     fields=dict(k=len(self.fields), passes=self.field_passes if len(self.fields) else 0,
                                 touched=self.field_touched if len(self.fields) else 0))
@@ -104,16 +108,22 @@ def state_counters(st):
     bonds, bodies = st.bonds_info(), st.bodies_info()
     bonds.pop("resolves"); bodies.pop("resolves")
     return dict(colliders=pick(st.colliders_info(), ("k", "passes", "pushed")),
-                movers=pick(st.movers_info(), ("k", "passes", "pushed")), sweep=st.sweep_info(), bonds=bonds, bodies=bodies,
+                movers=pick(st.movers_info(), ("k", "passes", "pushed")), sweep=st.sweep_info(),
+                mover_sweep=st.mover_sweep_info(), bonds=bonds, bodies=bodies,
                 fields=pick(st.fields_info(), ("k", "passes", "touched")))
 
 
-# ---- the scene: test_gpu_bodies' yard filled up to 1025 particles, with a piston, a paddle, a corner and a field set ----
+# ---- the scene: test_gpu_bodies' yard filled up to 1025 particles, with a piston, a paddle, a thin gate, a thin blade,
+# ---- a corner and a field set ------------------------------------------------------------------------------------------
 WORLD, GRAVITY = (60.0, 60.0), (0.0, 100.0)
 N = 1025                                                               # odd, past two blocks of 512
 CORNER = np.array([[50, 31, 57, 31, 0], [57, 31, 57, 38, 0]], F32)     # two zero-radius capsules: apex (57, 31), open to the lower left
 SHOTS = 8
 SHOT_SPEED = 6.0                                                       # units per step: thinner walls than a step's path
+# thinner than one step's displacement, where the plain pass skips particles: an R = 0 gate at 2 units per step through the
+# lattice on the floor, an R = 0 blade at 0.4 rad per step that reaches the bricks' band
+THIN_MOVERS = MM.rows(MM.linear((14, 30), (14, 39.4), 0.0, v=(120.0, 0.0), travel=12.0),
+                      MM.rotor((30, 36), (36, 36), 0.0, (30, 36), 24.0))
 Scene = collections.namedtuple("Scene", "pos prev rad bonds iterations bodies member_uid member_rest colliders "
                                         "collider_surfaces movers mover_surfaces fields")
 
@@ -121,7 +131,8 @@ Scene = collections.namedtuple("Scene", "pos prev rad bonds iterations bodies me
 def scene():
     """uid = storage index at the start.  The yard (a pendulum, six bricks of which one is brittle, a soft blob, 120
     loose particles; a floor and a peg; two bonds relaxed twice), 823 more loose particles on a jittered lattice above
-    the floor, and eight shots: particles below the corner that leave for its apex at 6 units per step."""
+    the floor, and eight shots: particles below the corner that leave for its apex at 6 units per step.  The movers are
+    tests/_movers_model.run_movers' thick piston and paddle, then THIN_MOVERS."""
     from tests.test_gpu_bodies import YARD_COLLIDERS, yard_scene
     pos, rad, bodies, member_uid, member_rest, bonds = yard_scene()
     bodies["break_distance"][3] = 0.05                                 # the brittle brick breaks on the 15th step, as it lands
@@ -145,13 +156,15 @@ def scene():
     prev[-SHOTS:] = (shots - SHOT_SPEED * d).astype(F32)
     assert len(pos) == N
     colliders = np.concatenate([YARD_COLLIDERS, CORNER]).astype(F32)
-    movers = MM.run_movers()
+    movers = np.concatenate([MM.run_movers(), THIN_MOVERS])
+    assert all(MM.dt_allowed(movers, dt) for dt in DTS)
     return Scene(pos, prev, np.full(N, 0.5, F32), bonds, 2, bodies, member_uid, member_rest, colliders,
                  SM.scene_surfaces(len(colliders)), movers, SM.scene_surfaces(len(movers), seed=5), FM.POOL_FIELDS)
 
 
 def arm(h, sc, arms=ARMS):
-    """set the features of `arms` on a twin or a State (uids on already); a set left out leaves its surfaces out"""
+    """set the features of `arms` on a twin or a State (uids on already); a set left out leaves its surfaces out, but
+    not the movers' sweep: the mode is the context's, on with no movers held as well"""
     if "bonds" in arms:
         h.set_bonds(sc.bonds, sc.iterations)
     if "bodies" in arms:
@@ -166,6 +179,8 @@ def arm(h, sc, arms=ARMS):
         h.set_movers(sc.movers)
         if "mover_surfaces" in arms:
             h.set_surfaces("movers", sc.mover_surfaces)
+    if "mover_sweep" in arms:
+        h.set_mover_sweep(True)
     if "fields" in arms:
         h.set_fields(sc.fields)
     return h
@@ -203,14 +218,14 @@ SETS = ("bonds", "bodies", "fields", "collider_surfaces", "mover_surfaces")
 BLOCKS = ([["set_" + s, "step", "clear_" + s, "step", "set_" + s] for s in SETS] + [
     ["set_colliders", "set_collider_surfaces", "step", "clear_colliders", "step", "set_colliders", "set_collider_surfaces"],
     ["set_movers", "set_mover_surfaces", "step", "clear_movers", "step", "set_movers", "set_mover_surfaces"],
-    ["sweep_off", "step", "sweep_on"], ["set_mover_poses", "step"],
+    ["sweep_off", "step", "sweep_on"], ["mover_sweep_off", "step", "mover_sweep_on"], ["set_mover_poses", "step"],
     ["run"], ["run"], ["run_resort_mid"], ["resort", "step"], ["add_few", "step"], ["add_grow", "step"],
     ["remove_circle", "step"], ["remove_members", "step"], ["remove_uid"], ["edit_pos", "step"],
     ["radius_up", "step", "radius_down", "step"], ["kick", "step"], ["world_grow", "step", "world_back", "step"], ["gravity"],
     ["other_mode"], ["save_load", "step"], ["apply_bonds"], ["apply_bodies"], ["apply_movers"], ["apply_colliders"],
     ["apply_fields"]])
 REPLACING = (["set_" + s for s in SETS + ("colliders", "movers", "mover_poses")] + ["clear_" + s for s in SETS + ("colliders", "movers")]
-             + ["sweep_off", "sweep_on"])
+             + ["sweep_off", "sweep_on", "mover_sweep_off", "mover_sweep_on"])
 
 
 def plan(seed):
@@ -220,7 +235,7 @@ def plan(seed):
     rng = np.random.default_rng(7100 + seed)
     order = rng.permutation(len(BLOCKS))
     ops = ["run_start"] + [op for i in order for op in BLOCKS[i]]
-    assert 60 <= len(ops) <= 80
+    assert 60 <= len(ops) <= 83
     return Plan(seed, ops)
 
 
@@ -228,12 +243,13 @@ class Coverage(collections.Counter):
     """What a sequence reached, counted on the twin's side."""
 
     def check(self):
-        need = (["armed_" + k for k in ("colliders_pushed", "movers_pushed", "swept", "stopped", "body_broke", "field_changed",
-                                        "resort", "growth", "removal_of_member_and_bonded", "radius_up")]
-                + ["set_world_with_grids", "save_load_nine_groups", "run_resorts_in_its_middle"] + ["op_" + op for op in REPLACING])
+        need = (["armed_" + k for k in ("colliders_pushed", "movers_pushed", "swept", "stopped", "mover_swept", "mover_stopped",
+                                        "body_broke", "field_changed", "resort", "growth", "removal_of_member_and_bonded",
+                                        "radius_up")]
+                + ["set_world_with_grids", "save_load_ten_groups", "run_resorts_in_its_middle"] + ["op_" + op for op in REPLACING])
         missing = [k for k in need if self[k] == 0]
         assert not missing, "the sequence never reached: %s\n%s" % (", ".join(missing), dict(self))
-        assert self["armed_steps"] >= 30, "only %d steps with all eight arms set" % self["armed_steps"]
+        assert self["armed_steps"] >= 30, "only %d steps with all nine arms set" % self["armed_steps"]
 
 
 class Sequence:
@@ -303,6 +319,7 @@ class Sequence:
     def _watch(self):
         tw = self.tw
         return dict(colliders_pushed=tw.pushed, movers_pushed=tw.m.pushed, swept=tw.swept, stopped=tw.stopped,
+                    mover_swept=tw.m.swept, mover_stopped=tw.m.stopped,
                     body_broke=int(tw.bodies_broken.sum()), field_changed=tw.field_changed)
 
     def _twin_step(self, dt, resort):
@@ -494,21 +511,21 @@ class Sequence:
 
     def op_save_load(self):
         tw = self.tw
-        nine = tw.fully_armed()
-        if nine:
-            self.cov["save_load_nine_groups"] += 1
+        ten = tw.fully_armed()
+        if ten:
+            self.cov["save_load_ten_groups"] += 1
         if self.st is not None:
             path = os.path.join(self.tmp.name, "snap_%d.npz" % len(self.log))
             self.st.save(path)
             with np.load(path) as d:
-                if nine:
+                if ten:
                     assert set(GROUPS) <= set(d.files), sorted(d.files)
             self.retire()
             self.end(self.st)
             self.st = self.gpe.State.load(path, mode=self.mode, flags=self.L.FLAG_GUARD_ALLOCS)
         tw.reloaded()
         self.cap = len(tw)
-        self.log.append("save / load%s" % (" (all nine groups)" if nine else ""))
+        self.log.append("save / load%s" % (" (all ten groups)" if ten else ""))
 
     # ---- the passes called directly -----------------------------------------------------------------------------------
     def _apply(self, name, *args):
@@ -602,11 +619,17 @@ class Sequence:
         self._set("set_surfaces", "colliders", np.zeros(0, SM.SURFACE_DTYPE), what="clear collider surfaces")
 
     def op_set_movers(self):
+        """a thick piston and a thick paddle, and thinner than a step's displacement a gate near the piston and a blade
+        near the paddle, either way round"""
         rng = self.rng
         x, y = float(rng.uniform(4, 8)), float(rng.uniform(26, 30))
         px, py = float(rng.uniform(30, 46)), float(rng.uniform(30, 36))
+        gx, bx = x + float(rng.uniform(6, 12)), px - float(rng.uniform(4, 10))
         movers = MM.rows(MM.linear((x, y), (x, y + 13), 2.0, v=(float(rng.uniform(15, 30)), 0.0), travel=float(rng.uniform(6, 12))),
-                         MM.rotor((px, py), (px + 7, py), 1.5, (px, py), float(rng.choice([-6.0, 4.0, 6.0]))))
+                         MM.rotor((px, py), (px + 7, py), 1.5, (px, py), float(rng.choice([-6.0, 4.0, 6.0]))),
+                         MM.linear((gx, y + 2), (gx, 39.4), 0.0, v=(float(rng.choice([-150.0, -90.0, 90.0, 120.0])), 0.0),
+                                   travel=float(rng.uniform(8, 12))),
+                         MM.rotor((bx, py + 2), (bx + 6, py + 2), 0.0, (bx, py + 2), float(rng.choice([-24.0, -18.0, 18.0, 24.0]))))
         assert all(MM.dt_allowed(movers, dt) for dt in DTS)
         self._set("set_movers", movers)
 
@@ -652,3 +675,17 @@ class Sequence:
 
     def op_sweep_on(self):
         self._set("set_collider_sweep", True, what="sweep on")
+
+    # the movers' sweep goes off through the C entry point and on through the module class, neither through State: with
+    # arm() and State.load, which use State, a later save_load covers every way in
+    def op_mover_sweep_off(self):
+        if self.st is not None:
+            self.st.ctx.call("gpe_set_mover_sweep", self.L.SWEEP_OFF)
+        self.tw.set_mover_sweep(False)
+        self.log.append("mover sweep off (ctx.call)")
+
+    def op_mover_sweep_on(self):
+        if self.st is not None:
+            self.st.particles.set_mover_sweep(True)
+        self.tw.set_mover_sweep(True)
+        self.log.append("mover sweep on (ParticleSystem)")

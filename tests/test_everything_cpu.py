@@ -1,12 +1,13 @@
-"""CPU: the composed twin of tests/_everything_model.py (bonds, bodies, movers, static colliders with surfaces and the
-sweep, fields, all behind one step) before any GPU time is spent on it: it is no new oracle (bit for bit the two existing
-twins where only their features are set), its scene acts and tells every arm apart, and its random plans reach what
-tests/test_gpu_everything.py needs them to reach."""
+"""CPU: the composed twin of tests/_everything_model.py (bonds, bodies, movers with surfaces and their sweep, static
+colliders with surfaces and the sweep, fields, all behind one step) before any GPU time is spent on it: it is no new
+oracle (bit for bit the three existing twins where only their features are set), its scene acts and tells every arm
+apart, and its random plans reach what tests/test_gpu_everything.py needs them to reach."""
 import numpy as np
 import pytest
 
 from tests import _bodies_model as BD
 from tests import _everything_model as E
+from tests import _mover_sweep_model as MS
 from tests import _sweep_model as SW
 
 F32 = np.float32
@@ -51,9 +52,10 @@ def test_with_the_yards_features_alone_it_is_the_bodies_twin(oracle):
 
 
 def test_with_the_sweeps_features_alone_it_is_the_sweep_twin(oracle):
-    """movers, colliders, both surfaces, the sweep and fields over scene(): the frames of tests/_sweep_model.Twin"""
+    """movers, colliders, both surfaces, the sweep and fields over scene(): the frames of tests/_sweep_model.Twin (which
+    has no movers' sweep: the thin movers run the plain pass)"""
     sc = E.scene()
-    arms = tuple(a for a in E.ARMS if a not in ("bonds", "bodies"))
+    arms = tuple(a for a in E.ARMS if a not in ("bonds", "bodies", "mover_sweep"))
     twins = []
     for cls in (SW.Twin, E.Everything):
         tw = cls(oracle, sc.pos, sc.rad, world=E.WORLD, gravity=E.GRAVITY, prev=sc.prev)
@@ -71,17 +73,57 @@ def test_with_the_sweeps_features_alone_it_is_the_sweep_twin(oracle):
     old.close(); new.close()
 
 
+def test_with_both_sweeps_and_no_bonds_or_bodies_it_is_the_mover_sweep_twin(oracle):
+    """movers, both surfaces, colliders, both sweeps and fields over scene(): the frames, the mover poses and the swept
+    pass's counters of tests/_mover_sweep_model.Twin"""
+    sc = E.scene()
+    arms = tuple(a for a in E.ARMS if a not in ("bonds", "bodies"))
+    twins = []
+    for cls in (MS.Twin, E.Everything):
+        tw = cls(oracle, sc.pos, sc.rad, world=E.WORLD, gravity=E.GRAVITY, prev=sc.prev)
+        tw.enable_uids()
+        twins.append(E.arm(tw, sc, arms))
+    old, new = twins
+    for s in range(E.STEPS):
+        resort = s % 16 == 0
+        old.step(E.DT, resort=resort); new.step(E.DT, resort=resort)
+        for a, b in zip(old.arrays(), new.arrays()):
+            assert same_bits(a, b), s
+        assert old.m.poses().tobytes() == new.m.poses().tobytes() and np.array_equal(old.uids, new.uids), s
+        assert old.mover_sweep_info() == new.mover_sweep_info(), s
+    assert (old.pushed, old.m.pushed, old.swept, old.stopped) == (new.pushed, new.m.pushed, new.swept, new.stopped)
+    info = new.mover_sweep_info()
+    assert info["mode"] == 1 and info["passes"] == E.STEPS and info["swept"] > 0 and info["stopped"] > 0
+    assert old.swept > 0 and old.stopped > 0 and new.field_changed > 0 and new.armed() == arms
+    old.close(); new.close()
+
+
 def test_the_scene_acts(full):
     frames, counters, first_break, field_changed = full
     sc = E.scene()
     assert len(sc.rad) == E.N == 1025 and (sc.collider_surfaces["flags"] == 1).any()
+    assert len(E.ARMS) == 9 and len(sc.movers) == 4 and (sc.movers["radius"] == 0).sum() == 2
     assert all(np.isfinite(f.pos).all() and np.isfinite(f.prev).all() for f in frames)
     print(counters, "first break after step", first_break)
     assert counters["colliders"]["pushed"] > 0 and counters["movers"]["pushed"] > 0
     assert counters["sweep"]["swept"] > 0 and counters["sweep"]["stopped"] > 0 and field_changed > 0
+    assert counters["mover_sweep"]["swept"] > 0 and counters["mover_sweep"]["stopped"] > 0
     assert counters["bodies"]["broken"] >= 1 and first_break < 15       # (test_gpu_everything saves after 15 steps)
+    assert counters["bodies"]["broken"] < counters["bodies"]["k"]      # (... and needs a body that is not broken)
     assert counters["bonds"]["passes"] == counters["bodies"]["passes"] == counters["sweep"]["passes"] == E.STEPS
-    assert counters["movers"]["passes"] == counters["fields"]["passes"] == E.STEPS
+    assert counters["movers"]["passes"] == counters["fields"]["passes"] == counters["mover_sweep"]["passes"] == E.STEPS
+
+
+def test_the_thin_movers_skip_particles_under_the_plain_pass(oracle, full):
+    """the composed scene with the movers' sweep off: the gate and the blade jump across particles the swept form
+    pushes, so `pushed` of the movers differs (and the swept form's counters stay 0)"""
+    tw = E.twin(oracle, tuple(a for a in E.ARMS if a != "mover_sweep"))
+    E.frames(tw)
+    off, on = tw.counters(), full[1]
+    tw.close()
+    print("movers pushed: swept", on["movers"]["pushed"], "plain", off["movers"]["pushed"])
+    assert off["mover_sweep"] == dict(mode=0, passes=0, swept=0, stopped=0) and off["movers"]["passes"] == E.STEPS
+    assert off["movers"]["pushed"] != on["movers"]["pushed"]
 
 
 @pytest.mark.parametrize("out", E.ARMS)
@@ -121,7 +163,7 @@ def test_the_order_of_the_passes_matters(oracle, full, first):
 @pytest.mark.parametrize("seed", E.SEEDS)
 def test_the_plans_reach_what_they_are_for(oracle, seed):
     plan = E.plan(seed)
-    assert 60 <= len(plan.ops) <= 80 and plan.ops == E.plan(seed).ops
+    assert 60 <= len(plan.ops) <= 83 and plan.ops == E.plan(seed).ops
     seq = E.Sequence(plan, oracle)
     try:
         seq.run()

@@ -1,7 +1,7 @@
-"""GPU (-m gpu): every pass behind a step armed at once -- bonds -> bodies -> movers -> static colliders (surfaces,
-swept) -> fields -> observers, the order of gpe_step / gpe_run -- against the one composed twin of
+"""GPU (-m gpu): every pass behind a step armed at once -- bonds -> bodies -> movers (surfaces, swept) -> static
+colliders (surfaces, swept) -> fields -> observers, the order of gpe_step / gpe_run -- against the one composed twin of
 tests/_everything_model.py, which is made of nothing but the model functions each feature's own tests pin against the
-device (tests/test_everything_cpu.py ties it to the two existing twins).
+device (tests/test_everything_cpu.py ties it to the three existing twins).
 
 Every comparison is bit for bit on uint32 views, a NaN for a NaN.  Every context runs under GPE_FLAG_GUARD_ALLOCS and
 ends with no damaged red zone.  A mismatch that goes away when one arm is left out (test_every_step_equals_the_twin's
@@ -98,6 +98,7 @@ def _same_as_twin(st, tw, what):
     for target in ("colliders", "movers"):
         assert same_rows(st.surfaces(target), tw.surfaces(target)), (what, target, "surfaces")
     assert same_rows(st.fields(), tw.fields) and st.collider_sweep() is tw.sweep, (what, "fields / sweep")
+    assert st.mover_sweep() is tw.m.sweep, (what, "the movers' sweep")
     rec, _ = st.bonds()
     assert same_rows(rec, tw.bonds), (what, "bonds")
     rec, _, uid, rest = st.bodies()
@@ -117,7 +118,8 @@ def reference(oracle):
         if case not in done:
             arms = _arms(case)
             tw = E.twin(oracle, arms)
-            assert tw.armed() == tuple(a for a in arms if a.split("_")[0] + "s" in arms or "_" not in a)   # (no set, no surfaces)
+            # (no set, no surfaces; the movers' sweep is the context's mode: on with no movers held, off with thin ones)
+            assert tw.armed() == tuple(a for a in arms if a.split("_")[0] + "s" in arms or "_" not in a or a == "mover_sweep")
             done[case] = (E.frames(tw), tw.counters())
             tw.close()
         return done[case]
@@ -138,11 +140,14 @@ def resorted(oracle):
 @pytest.mark.parametrize("case", CASES)
 def test_every_step_equals_the_twin(gpe, reference, case, mode):
     """40 gpe_step calls over scene(): pos and prev after each, the poses and the broken flags after every tenth, every
-    counter at the end.  `all` pins the order of the six passes; the other cases are bit-identical to the twin configured
-    the same way and bisect a failure of `all`."""
+    counter at the end.  `all` pins the order of the five passes in the forms the nine arms give them (the movers' and
+    the static colliders' with surfaces and swept) and of the observers behind them; the other cases are bit-identical to
+    the twin configured the same way and bisect a failure of `all`.  `no_movers` keeps the movers' sweep on with no movers
+    held; under `no_mover_sweep` the thin movers run the plain pass."""
     frames, counters = reference(case)
     if case == "all":
         assert counters["sweep"]["stopped"] > 0 and counters["bodies"]["broken"] > 0 and counters["movers"]["pushed"] > 0
+        assert counters["mover_sweep"]["stopped"] > 0
     st = _state(gpe, mode, _arms(case))
     for s in range(STEPS):
         st.update(DT)
@@ -178,7 +183,7 @@ def test_one_run_equals_the_loop_and_the_observers_see_the_end_of_the_chain(gpe,
     tr = st.tracers_read()
     rec, recorded = st.monitor_read()
     assert len(tr.step) == STEPS and recorded == STEPS
-    for s, f in enumerate(frames):                                     # frames taken behind all six passes
+    for s, f in enumerate(frames):                                     # frames taken behind every pass, the swept ones too
         slot = BM.slots_of(f.uids, TRACKED)
         assert (slot >= 0).all() and np.array_equal(tr.index[s], slot), s
         assert same_bits(tr.pos[s], f.pos[slot]) and same_bits(tr.prev[s], f.prev[slot]), s
@@ -193,7 +198,9 @@ def test_one_run_equals_the_loop_and_the_observers_see_the_end_of_the_chain(gpe,
 def test_one_event_invalidates_every_structure(gpe, oracle, mode):
     """Fully armed and stepping: a radius edit to three times the largest and back, gpe_set_world to twice the size and
     back, an add past the capacity, the removal of a body member and of a bonded uid, a re-sort, a spell in the other
-    mode; three steps and a full comparison behind each."""
+    mode; three steps and a full comparison (the movers' sweep and its counters in it) behind each.  A grid of the
+    movers that is cut anew must not drop the swept form: its pass counter goes on behind the radius edit and the new
+    world."""
     from tests.test_gpu_fields import grid_dims
     L = gpe._lib
     st = _state(gpe, mode)
@@ -212,14 +219,21 @@ def test_one_event_invalidates_every_structure(gpe, oracle, mode):
     def grids(infos):
         return [(i["grid_x"], i["grid_y"]) for i in infos]
 
+    def still_swept(what):
+        """the mode is on and every step so far ran the movers' pass in its swept form"""
+        info = st.mover_sweep_info()
+        assert st.mover_sweep() is True and info["mode"] == L.SWEEP_ON and info["passes"] == total[0], (what, info, total[0])
+
     start = steps("start", 6)
     assert grids(start)[2] == grid_dims(E.WORLD)[1:]
+    still_swept("start")
     # a new largest radius: the particle grid, the colliders' and the movers' grids are cut anew in one step
     who = np.array([700], U32)
     st.edit_particles(indices=who, radii=np.array([1.5], F32)); tw.edit(who, "index", radius=np.array([1.5], F32))
     up = steps("radius up")
     assert grids(up)[0] != grids(start)[0] and grids(up)[1] != grids(start)[1], (grids(start), grids(up))
     assert grids(up)[2] == grid_dims(E.WORLD)[1:]                       # (the fields' grid follows the world alone)
+    still_swept("radius up")
     st.edit_particles(indices=who, radii=np.array([0.5], F32)); tw.edit(who, "index", radius=np.array([0.5], F32))
     down = steps("radius down")
     assert grids(down) == grids(start)
@@ -233,6 +247,7 @@ def test_one_event_invalidates_every_structure(gpe, oracle, mode):
     wide = steps("world grown")
     assert grids(wide)[0] != grids(start)[0] and grids(wide)[1] != grids(start)[1], (grids(start), grids(wide))
     assert grids(wide)[2] == grid_dims(big)[1:]
+    still_swept("world grown")
     home = np.array([[30.0, 20.0], [32.0, 20.0]], F32)
     st.edit_particles(indices=who, positions=home); tw.edit(who, "index", pos=home)
     st.ctx.call("gpe_set_world", *E.WORLD); tw.set_world(*E.WORLD)
@@ -258,6 +273,7 @@ def test_one_event_invalidates_every_structure(gpe, oracle, mode):
     steps("the other mode")
     st.ctx.call("gpe_set_mode", _mode(gpe, mode))
     steps("the mode back")
+    still_swept("the end")
     # (a native step that finds particles outside a world that shrank back is the compat pipeline's: no exact split)
     pipe = st.ctx.pipeline_info()
     print(pipe)
@@ -269,7 +285,7 @@ def test_one_event_invalidates_every_structure(gpe, oracle, mode):
 
 # ---- 5. save and load with everything ---------------------------------------------------------------------------------
 @pytest.mark.parametrize("mode", ["native", "compat"])
-def test_save_and_load_with_all_nine_groups(gpe, reference, tmp_path, mode):
+def test_save_and_load_with_all_ten_groups(gpe, reference, tmp_path, mode):
     """saved after 15 steps, loaded into a fresh context of each mode, 15 more steps: the bits of the uninterrupted twin"""
     L = gpe._lib
     frames, _ = reference("all")
@@ -282,10 +298,11 @@ def test_save_and_load_with_all_nine_groups(gpe, reference, tmp_path, mode):
     with np.load(path) as d:
         assert set(E.GROUPS) <= set(d.files), sorted(d.files)
         assert np.array_equal(d["bodies_broken"], frames[14].bodies_broken) and d["collider_sweep"].tolist() == [1]
-        assert same_rows(d["mover_poses"], frames[14].mover_poses)
+        assert same_rows(d["mover_poses"], frames[14].mover_poses) and d["mover_sweep"].tolist() == [1]
     backs = [gpe.State.load(path, mode=m, flags=L.FLAG_GUARD_ALLOCS) for m in (_mode(gpe, mode), _mode(gpe, "compat" if mode == "native" else "native"))]
     for h in backs:
         assert h.collider_sweep() is True and np.array_equal(h.bodies()[1], frames[14].bodies_broken)
+        assert h.mover_sweep() is True and h.mover_sweep_info()["passes"] == 0     # (its counters start anew)
         assert same_rows(h.mover_poses(), frames[14].mover_poses)
         for target in ("colliders", "movers"):
             assert same_rows(h.surfaces(target), st.surfaces(target)) and len(h.surfaces(target)) > 0
@@ -298,6 +315,7 @@ def test_save_and_load_with_all_nine_groups(gpe, reference, tmp_path, mode):
     f = frames[29]
     for h in [st] + backs:
         _same_flags_and_poses(h, f.body_poses, f.bodies_broken, f.bonds_broken, f.mover_poses, "after load")
+        assert h.mover_sweep_info()["passes"] == (30 if h is st else 15)
     _ran_native(gpe, st, mode, 30)
     _ran_native(gpe, backs[0], mode, 15)
     _ran_native(gpe, backs[1], "compat" if mode == "native" else "native", 15)
@@ -310,7 +328,7 @@ def test_save_and_load_with_all_nine_groups(gpe, reference, tmp_path, mode):
 @pytest.mark.parametrize("seed", E.SEEDS)
 def test_a_random_interleaving_against_the_twin(gpe, oracle, seed, mode):
     """plan(seed) against a State and the twin: after every operation the particles, every stored set read back, the
-    sweep's mode, the poses, the broken flags and the counters"""
+    two sweeps' modes, the poses, the broken flags and the counters"""
     seq = E.Sequence(E.plan(seed), oracle, gpe=gpe, mode_name=mode, compare=_same_as_twin, end=_end)
     try:
         seq.run()

@@ -526,25 +526,56 @@ def test_save_and_load_keep_the_mode(gpe, tmp_path):
     _end(st)
 
 
+@pytest.mark.parametrize("way", ["particles", "ctx_call"])
+def test_save_keeps_a_mode_set_below_the_state(gpe, tmp_path, way):
+    """save() asks the context for the mode: one switched on through ParticleSystem.set_mover_sweep or through ctx.call,
+    not through State, is written and loaded, and the saved and the loaded state step the same bits"""
+    L = gpe._lib
+    st = _step_state(gpe, sweep=False)
+    if way == "particles":
+        st.particles.set_mover_sweep(True)
+    else:
+        st.ctx.call("gpe_set_mover_sweep", L.SWEEP_ON)
+    assert st.mover_sweep() is True
+    path = str(tmp_path / "snap.npz")
+    st.save(path)
+    with np.load(path) as d:
+        assert "mover_sweep" in d.files and d["mover_sweep"].tolist() == [1]
+    back = gpe.State.load(path, mode=L.MODE_NATIVE, flags=L.FLAG_GUARD_ALLOCS)
+    assert back.mover_sweep() is True
+    for h in (st, back):
+        _kick(gpe, h, 0)
+        h.run(DT, 6, resort_every=0, resort_first=False)
+    assert all(same_bits(a, b) for a, b in zip(_arrays(st), _arrays(back)))
+    assert same_rows(st.mover_poses(), back.mover_poses())
+    assert st.mover_sweep_info() == back.mover_sweep_info() and back.mover_sweep_info()["passes"] == 6
+    assert back.mover_sweep_info()["swept"] > 0
+    _end(back)
+    # the converse: on through State, off through ctx.call -- no key, and the loaded state is off
+    st.set_mover_sweep(True)
+    st.ctx.call("gpe_set_mover_sweep", L.SWEEP_OFF)
+    assert st.mover_sweep() is False
+    st.save(path)
+    with np.load(path) as d:
+        assert "mover_sweep" not in d.files
+    back = gpe.State.load(path, mode=L.MODE_NATIVE, flags=L.FLAG_GUARD_ALLOCS)
+    assert back.mover_sweep() is False and back.collider_sweep() is True
+    _end(back)
+    _end(st)
+
+
 # ---- 6. composition with every other pass ----------------------------------------------------------------------------
-class EverythingSwept(MS.Mixin, E.Everything):
-    """tests/_everything_model.Everything with the movers' pass in its swept form"""
-
-
 def test_every_pass_armed_with_both_sweeps_equals_the_composed_twin(gpe, oracle):
     """bonds -> bodies -> movers (swept) -> static colliders (swept) -> fields -> observers, 16 steps of the everything
-    scene bit for bit; the tracer and monitor frames show the swept positions"""
+    scene (tests/_everything_model.py arms the movers' sweep itself) bit for bit; the tracer and monitor frames show the
+    swept positions"""
     sc = E.scene()
-    tw = EverythingSwept(oracle, sc.pos, sc.rad, world=E.WORLD, gravity=E.GRAVITY, prev=sc.prev)
-    tw.enable_uids()
-    E.arm(tw, sc)
-    tw.set_mover_sweep(True)
+    tw = E.twin(oracle, sc=sc)
     st = gpe.State(sc.pos, sc.rad, world=E.WORLD, gravity=E.GRAVITY, prev=sc.prev, mode=gpe.MODE_NATIVE,
                    flags=gpe._lib.FLAG_GUARD_ALLOCS)
     st.enable_uids()
     E.arm(st, sc)
-    st.set_mover_sweep(True)
-    assert tw.fully_armed() and st.collider_sweep() and st.mover_sweep()
+    assert tw.fully_armed() and tw.m.sweep and st.collider_sweep() and st.mover_sweep()
     steps = 16
     watch = np.arange(0, E.N, 97, dtype=U32)
     st.tracers_begin(watch, every=1, frames=steps)

@@ -262,8 +262,15 @@ def test_save_writes_the_key_only_when_on_and_load_accepts_files_without_it(gpe,
     calls = []
 
     class Particles:
+        """answers mover_sweep() from what set_mover_sweep was last told, as the context does"""
+        on = False
+
         def set_mover_sweep(self, on):
             calls.append(("mover_sweep", bool(on)))
+            self.on = bool(on)
+
+        def mover_sweep(self):
+            return self.on
 
     class Ctx:
         def mouse(self):
@@ -315,3 +322,23 @@ def test_save_writes_the_key_only_when_on_and_load_accepts_files_without_it(gpe,
     del calls[:]
     Fake.load(on)
     assert calls == ["init", ("mover_sweep", True)]
+    # save() asks the context, not a mirror in State: a mode set below State (ParticleSystem.set_mover_sweep, ctx.call)
+    # is written, and one set through State and unset below it is not
+    below, unset = str(tmp_path / "below.npz"), str(tmp_path / "unset.npz")
+    st = Fake([(1, 1), (2, 2)], [0.5, 0.5])
+    st.particles.set_mover_sweep(True)
+    st.save(below)
+    with np.load(below) as d:
+        assert "mover_sweep" in d.files and d["mover_sweep"].tolist() == [1]
+    st = Fake([(1, 1), (2, 2)], [0.5, 0.5])
+    st.set_mover_sweep(True)
+    st.particles.set_mover_sweep(False)
+    st.save(unset)
+    with np.load(unset) as d:
+        assert "mover_sweep" not in d.files
+    del calls[:]
+    Fake.load(below)
+    assert calls == ["init", ("mover_sweep", True)]
+    del calls[:]
+    Fake.load(unset)
+    assert calls == ["init"]

@@ -208,6 +208,7 @@ def test_save_writes_the_key_only_when_on_and_load_accepts_files_without_it(gpe,
     empty = lambda self, *a: np.zeros(0, F32)
     for name in ("movers", "fields", "colliders"):
         monkeypatch.setattr(Fake, name, empty)
+    monkeypatch.setattr(Fake, "mover_sweep", lambda self: False)       # (save() asks the context for this mode too)
     monkeypatch.setattr(Fake, "surfaces", lambda self, target: np.zeros(0, gpe.SURFACE_DTYPE))
     monkeypatch.setattr(Fake, "bodies", lambda self: (np.zeros(0), np.zeros(0), np.zeros(0), np.zeros(0)))
     monkeypatch.setattr(Fake, "bonds", lambda self: (np.zeros(0), np.zeros(0)))
