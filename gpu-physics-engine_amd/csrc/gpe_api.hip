@@ -311,6 +311,17 @@ gpe_status refuse_sharded(gpe_ctx *c, const char *who)
                                                             "or an active cell box)");
 }
 
+gpe_status refuse_step_sets(gpe_ctx *c, const char *who, const char *uid_refusal)
+{
+    if (has_bonds(c)) return refuse_bonds(c, who);
+    if (has_bodies(c)) return refuse_bodies(c, who);
+    if (c->uid.on) return fail(c, GPE_ERR_UNSUPPORTED, std::string(who) + ": " + uid_refusal);
+    if (has_colliders(c)) return refuse_colliders(c, who);
+    if (has_fields(c)) return refuse_fields(c, who);
+    if (has_movers(c)) return refuse_movers(c, who);
+    return GPE_OK;
+}
+
 gpe_status refuse_too_many(gpe_ctx *c, const char *who)
 {
     return fail(c, GPE_ERR_UNSUPPORTED, std::string(who) + ": more than 2^32 - 1 particles");
@@ -629,9 +640,7 @@ static gpe_status do_remove(gpe_ctx *c, const uint8_t *mask, float x, float y, f
     if (c->uid.on) {
         std::swap(c->uid.uids, c->uid.uids_copy);
         c->uid.map_valid = false;
-        c->tracers.stale = true;
-        c->bonds.stale = true;
-        c->bodies.stale = true;
+        uid_slots_stale(c);
     }
     c->n = survivors;
     c->n_owned = survivors;
@@ -662,9 +671,7 @@ static gpe_status uids_switch_on(gpe_ctx *c)
     }
     u.on = true;
     u.map_valid = false;
-    c->tracers.stale = true;
-    c->bonds.stale = true;
-    c->bodies.stale = true;
+    uid_slots_stale(c);
     return GPE_OK;
 }
 
@@ -732,9 +739,7 @@ static void uid_release(gpe_ctx *c)
     dev_free(c, u.map_keys); dev_free(c, u.map_vals); dev_free(c, u.dup); dev_free(c, u.query);
     u.map_cap = u.query_cap = 0;
     u.map_valid = false;
-    c->tracers.stale = true;
-    c->bonds.stale = true;
-    c->bodies.stale = true;
+    uid_slots_stale(c);
 }
 
 // ---- step pieces ------------------------------------------------------------------------------------
@@ -751,9 +756,7 @@ static gpe_status do_resort(gpe_ctx *c)
                                       c->prev_copy, c->radius_copy, c->uid.uids_copy));
         std::swap(c->uid.uids, c->uid.uids_copy);
         c->uid.map_valid = false;
-        c->tracers.stale = true;
-        c->bonds.stale = true;
-        c->bodies.stale = true;
+        uid_slots_stale(c);
     } else {
         GPE_TRY(launch_rearrange(c, c->pos, c->prev, c->radius, c->particle_ids, c->n, c->pos_copy,
                                  c->prev_copy, c->radius_copy));
@@ -1095,9 +1098,7 @@ gpe_status gpe_set_particles(gpe_ctx *c, const float *pos_xy, const float *prev_
         GPE_TRY(launch_uid_iota(c, c->uid.uids, 0, n, 0u));
         c->uid.next = n;
         c->uid.map_valid = false;
-        c->tracers.stale = true;
-        c->bonds.stale = true;
-        c->bodies.stale = true;
+        uid_slots_stale(c);
     }
     c->max_radius = max_abs_radius(radius, n, radius[0]);
     c->grid_max_radius = c->max_radius;       // Grid::new (grid.rs:66-71)
@@ -1128,9 +1129,7 @@ gpe_status gpe_add_particles(gpe_ctx *c, const float *pos_xy, const float *radiu
         GPE_TRY(launch_uid_iota(c, c->uid.uids, old_n, new_n, (uint32_t)c->uid.next));
         c->uid.next += n_add;
         c->uid.map_valid = false;
-        c->tracers.stale = true;
-        c->bonds.stale = true;
-        c->bodies.stale = true;
+        uid_slots_stale(c);
     }
     // particle_system.rs:198: max_radius = max(max_radius, r)
     for (uint64_t i = 0; i < n_add; ++i) c->max_radius = fmaxf(c->max_radius, radius[i]);
@@ -1229,9 +1228,7 @@ gpe_status gpe_set_uids(gpe_ctx *c, const uint32_t *uids, uint64_t n)
     std::swap(u.uids, u.uids_copy);
     u.next = (uint64_t)u.map_max + 1;
     u.map_valid = true;                                        // the map just built is the new uids'
-    c->tracers.stale = true;                                   // (uid_map_build cleared map_valid on the way)
-    c->bonds.stale = true;
-    c->bodies.stale = true;
+    uid_slots_stale(c);                                        // (uid_map_build cleared map_valid on the way)
     return GPE_OK;
 }
 
@@ -1469,18 +1466,28 @@ gpe_status gpe_solve_collisions(gpe_ctx *c)
 }
 
 // ---- step ------------------------------------------------------------------------------------------------
+// The passes behind every step of gpe_step / gpe_run, in the one order they have (a test arms them all):
+// bonds, then bodies (a bond can hang a body from an anchor), then the obstacles, which keep the last word over both --
+// the movers first, the static walls behind them (a piston squeezes particles against a wall, the wall wins) -- then
+// the fields, which write prev only and so are judged where the step and the obstacles left the particle, then the
+// observers, whose frames see the result.  A context without a set pays that set's flag test and no call.
+static inline gpe_status after_step(gpe_ctx *c, float dt)
+{
+    if (has_bonds(c)) GPE_TRY(bonds_after_step(c));
+    if (has_bodies(c)) GPE_TRY(bodies_after_step(c));
+    if (has_movers(c)) GPE_TRY(movers_after_step(c, dt));
+    if (has_colliders(c)) GPE_TRY(colliders_after_step(c));
+    if (has_fields(c)) GPE_TRY(fields_after_step(c, dt));
+    return observers_after_step(c);
+}
+
 gpe_status gpe_step(gpe_ctx *c, float dt, uint32_t flags)
 {
     GPE_TRY(need_particles(c));
     GPE_TRY(movers_check_dt(c, dt, "gpe_step"));
     GPE_HIP(c, hipSetDevice(c->device));
     GPE_TRY(do_step(c, dt, flags));
-    GPE_TRY(bonds_after_step(c));
-    GPE_TRY(bodies_after_step(c));
-    GPE_TRY(movers_after_step(c, dt));
-    GPE_TRY(colliders_after_step(c));
-    GPE_TRY(fields_after_step(c, dt));
-    return observers_after_step(c);
+    return after_step(c, dt);
 }
 
 gpe_status gpe_run(gpe_ctx *c, float dt, uint64_t steps, uint64_t resort_every, int32_t resort_first)
@@ -1503,12 +1510,7 @@ gpe_status gpe_run(gpe_ctx *c, float dt, uint64_t steps, uint64_t resort_every, 
         }
         const bool resort = (s == 0 && resort_first) || (resort_every && s > 0 && (s % resort_every) == 0);
         rc = do_step(c, dt, resort ? GPE_STEP_RESORT : 0u);
-        if (rc == GPE_OK) rc = bonds_after_step(c);
-        if (rc == GPE_OK) rc = bodies_after_step(c);
-        if (rc == GPE_OK) rc = movers_after_step(c, dt);
-        if (rc == GPE_OK) rc = colliders_after_step(c);
-        if (rc == GPE_OK) rc = fields_after_step(c, dt);
-        if (rc == GPE_OK) rc = observers_after_step(c);
+        if (rc == GPE_OK) rc = after_step(c, dt);
     }
     for (hipEvent_t e : fence) if (e) (void)hipEventDestroy(e);
     return rc;
@@ -1732,12 +1734,7 @@ gpe_status gpe_set_counts(gpe_ctx *c, uint64_t n_total, uint64_t n_owned)
     GPE_TRY(need_particles(c));
     if (n_total == 0 || n_total > c->cap || n_owned > n_total)
         return fail(c, GPE_ERR_INVALID_ARG, "gpe_set_counts: need 0 < n_owned <= n_total <= capacity");
-    if (has_bonds(c)) return refuse_bonds(c, "gpe_set_counts");        // (before the uids they need: the more telling refusal)
-    if (has_bodies(c)) return refuse_bodies(c, "gpe_set_counts");
-    if (c->uid.on) return fail(c, GPE_ERR_UNSUPPORTED, "gpe_set_counts: not supported while uids are on");
-    if (has_colliders(c)) return refuse_colliders(c, "gpe_set_counts");
-    if (has_fields(c)) return refuse_fields(c, "gpe_set_counts");
-    if (has_movers(c)) return refuse_movers(c, "gpe_set_counts");
+    GPE_TRY(refuse_step_sets(c, "gpe_set_counts", "not supported while uids are on"));
     c->n = n_total;
     c->n_owned = n_owned;
     c->native.uniform = false;                 // (slots the configuration has not looked at: NativeState::uniform)
@@ -1747,13 +1744,7 @@ gpe_status gpe_set_counts(gpe_ctx *c, uint64_t n_total, uint64_t n_owned)
 gpe_status gpe_use_order_keys(gpe_ctx *c, int32_t enable)
 {
     if (!c) return GPE_ERR_INVALID_ARG;
-    if (enable && has_bonds(c)) return refuse_bonds(c, "gpe_use_order_keys");
-    if (enable && has_bodies(c)) return refuse_bodies(c, "gpe_use_order_keys");
-    if (enable && c->uid.on)
-        return fail(c, GPE_ERR_UNSUPPORTED, "gpe_use_order_keys: sharded runs carry order keys, not uids (uids are on)");
-    if (enable && has_colliders(c)) return refuse_colliders(c, "gpe_use_order_keys");
-    if (enable && has_fields(c)) return refuse_fields(c, "gpe_use_order_keys");
-    if (enable && has_movers(c)) return refuse_movers(c, "gpe_use_order_keys");
+    if (enable) GPE_TRY(refuse_step_sets(c, "gpe_use_order_keys", "sharded runs carry order keys, not uids (uids are on)"));
     c->use_order_keys = enable != 0;
     if (enable) c->native.uniform = false;     // (order-key tiles keep the general path: NativeState::uniform)
     return GPE_OK;

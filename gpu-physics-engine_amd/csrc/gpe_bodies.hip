@@ -1,7 +1,6 @@
 // gpe_bodies.hip -- the rigid and soft bodies of a context (gpe_set_bodies and the rest): the set, its tables
 // (body_table.h), the members' storage slots (looked up again only when stale) and the pass behind every step
-// (k_bodies.hip).  gpe_api.hip calls bodies_after_step from gpe_step / gpe_run, behind the bonds and before the
-// colliders and the observers, and bodies_release from gpe_destroy.
+// (k_bodies.hip).  gpe_api.hip calls bodies_after_step from after_step and bodies_release from gpe_destroy.
 #include <string.h>
 
 #include "body_table.h"
@@ -29,12 +28,6 @@ gpe_status gpe::refuse_bodies(gpe_ctx *c, const char *who)
                                                             "(gpe_set_bodies with k = 0 clears them)");
 }
 
-template <typename T, typename U>
-static hipError_t upload(gpe_ctx *c, T *dst, const U *src, uint64_t count)
-{
-    return hipMemcpyAsync(dst, src, count * sizeof(U), hipMemcpyHostToDevice, c->stream);
-}
-
 // One pass over the particles as they are now.  Enqueues only, unless the members' slots are stale: then the uid map
 // is made ready first (its build synchronises) and one lookup per member is enqueued.
 static gpe_status bodies_pass(gpe_ctx *c)
@@ -57,7 +50,7 @@ static gpe_status bodies_pass(gpe_ctx *c)
 
 gpe_status gpe::bodies_after_step(gpe_ctx *c)
 {
-    return has_bodies(c) ? bodies_pass(c) : GPE_OK;
+    return bodies_pass(c);                                            // (after_step has looked: the set is not empty)
 }
 
 gpe_status gpe_set_bodies(gpe_ctx *c, const gpe_body *bodies, uint64_t k, const uint32_t *member_uid,
@@ -76,40 +69,28 @@ gpe_status gpe_set_bodies(gpe_ctx *c, const gpe_body *bodies, uint64_t k, const 
     }
     BodyTable t;
     body_table_build(bodies, k, &t);
-    // the new tables beside the old ones: a failure leaves the previous set as it was.  Every array is read and written
-    // by index below the count it is allocated with.  no slack
-    const char *who = "gpe_set_bodies";
+    // the new tables beside the old ones (set_upload.h).  Every array is read and written by index below the count it
+    // is allocated with.  no slack
+    const unsigned long long broken = t.broken;
     BodyState N;
-    gpe_status st = ws_alloc(c, who, &N.rec, k, 0, "uid.body_rec");
-    if (st == GPE_OK) st = ws_alloc(c, who, &N.order, k, 0, "uid.body_order");
-    if (st == GPE_OK) st = ws_alloc(c, who, &N.member_uid, members, 0, "uid.body_member_uid");
-    if (st == GPE_OK) st = ws_alloc(c, who, &N.member_slot, members, 0, "uid.body_member_slot");
-    if (st == GPE_OK) st = ws_alloc(c, who, &N.member_rest, members, 0, "uid.body_member_rest");
-    if (st == GPE_OK) st = ws_alloc(c, who, &N.pose, k, 0, "uid.body_pose");
-    if (st == GPE_OK) st = ws_alloc(c, who, &N.state, k, 0, "uid.body_state");
-    if (st == GPE_OK) st = ws_alloc(c, who, &N.broken, 1, 0, "uid.body_broken");
-    if (st == GPE_OK) {
-        const unsigned long long broken = t.broken;
-        hipError_t e = upload(c, N.rec, t.rec.data(), k);
-        if (e == hipSuccess) e = upload(c, N.order, t.order.data(), k);
-        if (e == hipSuccess) e = upload(c, N.member_uid, member_uid, members);
-        if (e == hipSuccess) e = upload(c, N.member_rest, member_rest_xy, 2 * members);
-        if (e == hipSuccess) e = upload(c, N.state, t.state.data(), k);
-        if (e == hipSuccess) e = hipMemsetAsync(N.member_slot, 0xff, members * sizeof(uint32_t), c->stream);
-        if (e == hipSuccess) e = hipMemsetAsync(N.pose, 0xff, k * sizeof(float4), c->stream);      // (all ones: a NaN)
-        if (e == hipSuccess) e = hipMemcpyAsync(N.broken, &broken, sizeof(broken), hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);      // the host arrays go away on return
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            st = fail(c, GPE_ERR_HIP, std::string("gpe_set_bodies: upload: ") + hipGetErrorName(e));
-        }
-    }
-    if (st != GPE_OK) {
-        const std::string why = c->last_error;
-        bodies_free(c, N);
-        c->last_error = why;
-        return st;
-    }
+    HipSetUpload up({c}, "gpe_set_bodies");
+    up.reserve(&N.rec, k, "uid.body_rec");
+    up.reserve(&N.order, k, "uid.body_order");
+    up.reserve(&N.member_uid, members, "uid.body_member_uid");
+    up.reserve(&N.member_slot, members, "uid.body_member_slot");
+    up.reserve(&N.member_rest, members, "uid.body_member_rest");
+    up.reserve(&N.pose, k, "uid.body_pose");
+    up.reserve(&N.state, k, "uid.body_state");
+    up.reserve(&N.broken, 1, "uid.body_broken");
+    up.copy(N.rec, t.rec.data(), k);
+    up.copy(N.order, t.order.data(), k);
+    up.copy(N.member_uid, member_uid, members);
+    up.copy(N.member_rest, member_rest_xy, 2 * members);
+    up.copy(N.state, t.state.data(), k);
+    up.fill(N.member_slot, 0xff, members * sizeof(uint32_t));
+    up.fill(N.pose, 0xff, k * sizeof(float4));                         // (all ones: a NaN)
+    up.copy(N.broken, &broken, 1);
+    GPE_TRY(up.finish());
     bodies_free(c, c->bodies);
     N.set.assign(bodies, bodies + k);
     for (gpe_body &q : N.set) {
@@ -143,8 +124,7 @@ gpe_status gpe_get_bodies(gpe_ctx *c, gpe_body *out, uint8_t *broken_out, uint64
     if (broken_out) {
         GPE_HIP(c, hipSetDevice(c->device));
         std::vector<uint8_t> state(m);
-        GPE_HIP(c, hipMemcpyAsync(state.data(), S.state, m, hipMemcpyDeviceToHost, c->stream));
-        GPE_TRY(check_device_errors(c));                               // (synchronises the stream)
+        GPE_TRY(read_back(c, S.state, state.data(), m));
         for (uint64_t j = 0; j < m; ++j) broken_out[j] = state[j] == kBodyBroken ? 1 : 0;
     }
     return GPE_OK;
@@ -167,8 +147,7 @@ gpe_status gpe_get_body_poses(gpe_ctx *c, float *pose_xycs, uint64_t capacity, u
     const uint64_t m = std::min<uint64_t>(S.set.size(), capacity);
     if (m == 0 || !pose_xycs) return GPE_OK;
     GPE_HIP(c, hipSetDevice(c->device));
-    GPE_HIP(c, hipMemcpyAsync(pose_xycs, S.pose, m * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
-    return check_device_errors(c);                                     // (synchronises the stream)
+    return read_back(c, S.pose, pose_xycs, m * sizeof(float4));
 }
 
 gpe_status gpe_get_bodies_info(gpe_ctx *c, gpe_bodies_info *info)
@@ -183,8 +162,7 @@ gpe_status gpe_get_bodies_info(gpe_ctx *c, gpe_bodies_info *info)
     if (has_bodies(c)) {
         GPE_HIP(c, hipSetDevice(c->device));
         unsigned long long broken = 0;
-        GPE_HIP(c, hipMemcpyAsync(&broken, S.broken, sizeof(broken), hipMemcpyDeviceToHost, c->stream));
-        GPE_TRY(check_device_errors(c));                               // (synchronises the stream)
+        GPE_TRY(read_back(c, S.broken, &broken, sizeof(broken)));
         out.k = S.set.size();
         out.members = S.members;
         out.passes = S.passes;

@@ -1,7 +1,6 @@
 // gpe_bonds.hip -- the distance bonds of a context (gpe_set_bonds and the rest): the set, its graph (bond_graph.h), the
 // nodes' storage slots (looked up again only when stale) and the pass behind every step (k_bonds.hip).  gpe_api.hip
-// calls bonds_after_step from gpe_step / gpe_run, before the colliders and the observers, and bonds_release from
-// gpe_destroy.
+// calls bonds_after_step from after_step and bonds_release from gpe_destroy.
 #include <string.h>
 
 #include "bond_graph.h"
@@ -30,13 +29,6 @@ gpe_status gpe::refuse_bonds(gpe_ctx *c, const char *who)
                                                             "(gpe_set_bonds with k = 0 clears them)");
 }
 
-template <typename T, typename U>
-static hipError_t upload(gpe_ctx *c, T *dst, const std::vector<U> &src)
-{
-    if (src.empty()) return hipSuccess;
-    return hipMemcpyAsync(dst, src.data(), src.size() * sizeof(U), hipMemcpyHostToDevice, c->stream);
-}
-
 // One pass over the particles as they are now.  Enqueues only, unless the nodes' slots are stale: then the uid map is
 // made ready first (its build synchronises) and one lookup per node is enqueued.
 static gpe_status bonds_pass(gpe_ctx *c)
@@ -59,7 +51,7 @@ static gpe_status bonds_pass(gpe_ctx *c)
 
 gpe_status gpe::bonds_after_step(gpe_ctx *c)
 {
-    return has_bonds(c) ? bonds_pass(c) : GPE_OK;
+    return bonds_pass(c);                                             // (after_step has looked: the set is not empty)
 }
 
 gpe_status gpe_set_bonds(gpe_ctx *c, const gpe_bond *bonds, uint64_t k, uint32_t iterations)
@@ -78,46 +70,34 @@ gpe_status gpe_set_bonds(gpe_ctx *c, const gpe_bond *bonds, uint64_t k, uint32_t
         bonds_release(c);
         return GPE_OK;
     }
-    // the new tables beside the old ones: a failure leaves the previous set as it was.  Every array is read and written
-    // by index below the count it is allocated with.  no slack
-    const char *who = "gpe_set_bonds";
+    // the new tables beside the old ones (set_upload.h).  Every array is read and written by index below the count it
+    // is allocated with.  no slack
     const uint64_t m = g.nodes.size();
+    const unsigned long long broken = g.broken;
     BondState N;
     N.n_anchors = (uint32_t)(g.anchors.size() / 2);
-    gpe_status st = ws_alloc(c, who, &N.rec, k, 0, "uid.bond_rec");
-    if (st == GPE_OK && !g.max_length.empty()) st = ws_alloc(c, who, &N.max_length, k, 0, "uid.bond_max_length");
-    if (st == GPE_OK && N.n_anchors) st = ws_alloc(c, who, &N.anchors, N.n_anchors, 0, "uid.bond_anchors");
-    if (st == GPE_OK) st = ws_alloc(c, who, &N.node_uid, m, 0, "uid.bond_node_uid");
-    if (st == GPE_OK) st = ws_alloc(c, who, &N.node_slot, m, 0, "uid.bond_node_slot");
-    if (st == GPE_OK) st = ws_alloc(c, who, &N.row_start, m + 1, 0, "uid.bond_row_start");
-    if (st == GPE_OK) st = ws_alloc(c, who, &N.inc, g.inc.size(), 0, "uid.bond_inc");
-    if (st == GPE_OK) st = ws_alloc(c, who, &N.corr, k, 0, "uid.bond_corr");
-    if (st == GPE_OK) st = ws_alloc(c, who, &N.state, k, 0, "uid.bond_state");
-    if (st == GPE_OK) st = ws_alloc(c, who, &N.broken, 1, 0, "uid.bond_broken");
-    if (st == GPE_OK) {
-        const unsigned long long broken = g.broken;
-        hipError_t e = upload(c, N.rec, g.rec);
-        if (e == hipSuccess) e = upload(c, N.max_length, g.max_length);
-        if (e == hipSuccess) e = upload(c, N.anchors, g.anchors);
-        if (e == hipSuccess) e = upload(c, N.node_uid, g.nodes);
-        if (e == hipSuccess) e = upload(c, N.row_start, g.row_start);
-        if (e == hipSuccess) e = upload(c, N.inc, g.inc);
-        if (e == hipSuccess) e = upload(c, N.state, g.state);
-        if (e == hipSuccess) e = hipMemsetAsync(N.node_slot, 0xff, m * sizeof(uint32_t), c->stream);
-        if (e == hipSuccess) e = hipMemsetAsync(N.corr, 0, k * sizeof(float2), c->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(N.broken, &broken, sizeof(broken), hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);      // the host vectors go away on return
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            st = fail(c, GPE_ERR_HIP, std::string("gpe_set_bonds: upload: ") + hipGetErrorName(e));
-        }
-    }
-    if (st != GPE_OK) {
-        const std::string why = c->last_error;
-        bonds_free(c, N);
-        c->last_error = why;
-        return st;
-    }
+    HipSetUpload up({c}, "gpe_set_bonds");
+    up.reserve(&N.rec, k, "uid.bond_rec");
+    up.reserve(&N.max_length, g.max_length.empty() ? 0 : k, "uid.bond_max_length");
+    up.reserve(&N.anchors, N.n_anchors, "uid.bond_anchors");
+    up.reserve(&N.node_uid, m, "uid.bond_node_uid");
+    up.reserve(&N.node_slot, m, "uid.bond_node_slot");
+    up.reserve(&N.row_start, m + 1, "uid.bond_row_start");
+    up.reserve(&N.inc, g.inc.size(), "uid.bond_inc");
+    up.reserve(&N.corr, k, "uid.bond_corr");
+    up.reserve(&N.state, k, "uid.bond_state");
+    up.reserve(&N.broken, 1, "uid.bond_broken");
+    up.copy(N.rec, g.rec.data(), g.rec.size());
+    up.copy(N.max_length, g.max_length.data(), g.max_length.size());
+    up.copy(N.anchors, g.anchors.data(), g.anchors.size());
+    up.copy(N.node_uid, g.nodes.data(), g.nodes.size());
+    up.copy(N.row_start, g.row_start.data(), g.row_start.size());
+    up.copy(N.inc, g.inc.data(), g.inc.size());
+    up.copy(N.state, g.state.data(), g.state.size());
+    up.fill(N.node_slot, 0xff, m * sizeof(uint32_t));
+    up.fill(N.corr, 0, k * sizeof(float2));
+    up.copy(N.broken, &broken, 1);
+    GPE_TRY(up.finish());
     bonds_free(c, c->bonds);
     N.set.assign(bonds, bonds + k);
     for (gpe_bond &q : N.set) {
@@ -144,8 +124,7 @@ gpe_status gpe_get_bonds(gpe_ctx *c, gpe_bond *out, uint8_t *broken_out, uint64_
     if (broken_out) {
         GPE_HIP(c, hipSetDevice(c->device));
         std::vector<uint8_t> state(m);
-        GPE_HIP(c, hipMemcpyAsync(state.data(), S.state, m, hipMemcpyDeviceToHost, c->stream));
-        GPE_TRY(check_device_errors(c));                               // (synchronises the stream)
+        GPE_TRY(read_back(c, S.state, state.data(), m));
         for (uint64_t j = 0; j < m; ++j) broken_out[j] = state[j] == kBondBroken ? 1 : 0;
     }
     return GPE_OK;
@@ -171,8 +150,7 @@ gpe_status gpe_get_bonds_info(gpe_ctx *c, gpe_bonds_info *info)
     if (has_bonds(c)) {
         GPE_HIP(c, hipSetDevice(c->device));
         unsigned long long broken = 0;
-        GPE_HIP(c, hipMemcpyAsync(&broken, S.broken, sizeof(broken), hipMemcpyDeviceToHost, c->stream));
-        GPE_TRY(check_device_errors(c));                               // (synchronises the stream)
+        GPE_TRY(read_back(c, S.broken, &broken, sizeof(broken)));
         out.iterations = S.iterations;
         out.k = S.set.size();
         out.nodes = S.nodes;

@@ -1,6 +1,7 @@
 // gpe_colliders.hip -- the static colliders of a context (gpe_set_colliders and the rest): the set, its lookup grid
 // (collider_grid.h, rebuilt lazily) and the pass behind every step (k_colliders.hip).  gpe_api.hip calls
-// colliders_after_step from gpe_step / gpe_run, before the observers, and colliders_release from gpe_destroy.
+// colliders_after_step from after_step and colliders_release from gpe_destroy.  Also the cell-list grid holder the
+// fields share (CellListGrid: its release and its upload).
 #include <math.h>
 #include <string.h>
 
@@ -16,19 +17,39 @@ static uint32_t bits_of(float f)
     return u;
 }
 
-static void colliders_grid_release(gpe_ctx *c)
+void gpe::cell_grid_release(gpe_ctx *c, CellListGrid &G)
 {
-    ColliderState &S = c->colliders;
-    dev_free(c, S.cell_start); dev_free(c, S.items);
-    S.grid_valid = false;
-    S.entries = 0;
-    S.view = ColliderGridView();
+    dev_free(c, G.cell_start); dev_free(c, G.items);
+    G.valid = false;
+    G.entries = 0;
+    G.view = ColliderGridView();
+}
+
+gpe_status gpe::cell_grid_upload(gpe_ctx *c, const char *who, CellListGrid &G, const ColliderGridView &view,
+                                 const std::vector<uint32_t> &cell_start, const std::vector<uint32_t> &items,
+                                 const char *cell_start_tag, const char *items_tag)
+{
+    GPE_HIP(c, hipStreamSynchronize(c->stream));                       // (a pass in flight reads the old tables)
+    cell_grid_release(c, G);
+    // read by index: cell_start below gx * gy + 1 (the pass reads the words of a cell collider_cell_of names and the
+    // one behind it), items below cell_start's last word.  no slack
+    HipSetUpload up({c}, who, "grid upload");
+    up.reserve(&G.cell_start, cell_start.size(), cell_start_tag);
+    up.reserve(&G.items, std::max<uint64_t>(items.size(), 1), items_tag);
+    up.copy(G.cell_start, cell_start.data(), cell_start.size());
+    up.copy(G.items, items.data(), items.size());
+    GPE_TRY(up.finish());                                              // (the host's vectors go away on return)
+    G.view = view;
+    G.entries = items.size();
+    G.w = c->cfg.world_width; G.h = c->cfg.world_height;
+    G.valid = true;
+    return GPE_OK;
 }
 
 void gpe::colliders_release(gpe_ctx *c)
 {
     ColliderState &S = c->colliders;
-    colliders_grid_release(c);
+    cell_grid_release(c, S.grid);
     surfaces_drop(c, GPE_SURFACES_OF_COLLIDERS);
     dev_free(c, S.rec); dev_free(c, S.pushed);
     S = ColliderState();
@@ -41,44 +62,19 @@ gpe_status gpe::refuse_colliders(gpe_ctx *c, const char *who)
 }
 
 // The grid for the radius bound and the world as they are now.  Builds only when one of them has changed since the last
-// build; that synchronises (a pass in flight reads the old tables, the host's vectors go away on return).
+// build; that synchronises.
 static gpe_status colliders_grid_ready(gpe_ctx *c, const char *who)
 {
     ColliderState &S = c->colliders;
+    CellListGrid &G = S.grid;
     const float rb = c->max_radius, W = c->cfg.world_width, H = c->cfg.world_height;
-    if (S.grid_valid && bits_of(rb) == bits_of(S.grid_rb) && bits_of(W) == bits_of(S.grid_w) && bits_of(H) == bits_of(S.grid_h))
-        return GPE_OK;
-    GPE_HIP(c, hipStreamSynchronize(c->stream));
-    colliders_grid_release(c);
+    if (G.valid && bits_of(rb) == bits_of(G.rb) && bits_of(W) == bits_of(G.w) && bits_of(H) == bits_of(G.h)) return GPE_OK;
     const uint32_t k = (uint32_t)S.set.size();
     std::vector<ColliderCapsule> caps(k);
     for (uint32_t j = 0; j < k; ++j) caps[j] = {S.set[j].ax, S.set[j].ay, S.set[j].bx, S.set[j].by, S.set[j].radius};
     const ColliderGrid g = collider_grid_build(caps.data(), k, rb, W, H);
-    // read by index: cell_start below gx * gy + 1 (the pass reads the words of a cell collider_cell_of names and the
-    // one behind it), items below cell_start's last word.  no slack
-    gpe_status st = ws_alloc(c, who, &S.cell_start, g.cell_start.size(), 0, "grid.collider_cell_start");
-    if (st == GPE_OK) st = ws_alloc(c, who, &S.items, std::max<uint64_t>(g.items.size(), 1), 0, "grid.collider_items");
-    if (st == GPE_OK) {
-        hipError_t e = hipMemcpyAsync(S.cell_start, g.cell_start.data(), g.cell_start.size() * sizeof(uint32_t),
-                                      hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess && !g.items.empty())
-            e = hipMemcpyAsync(S.items, g.items.data(), g.items.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            st = fail(c, GPE_ERR_HIP, std::string(who) + ": grid upload: " + hipGetErrorName(e));
-        }
-    }
-    if (st != GPE_OK) {
-        const std::string why = c->last_error;
-        colliders_grid_release(c);                                     // no grid: the next pass tries again
-        c->last_error = why;
-        return st;
-    }
-    S.view = g.view;
-    S.entries = g.items.size();
-    S.grid_rb = rb; S.grid_w = W; S.grid_h = H;
-    S.grid_valid = true;
+    GPE_TRY(cell_grid_upload(c, who, G, g.view, g.cell_start, g.items, "grid.collider_cell_start", "grid.collider_items"));
+    G.rb = rb;
     return GPE_OK;
 }
 
@@ -94,7 +90,7 @@ static gpe_status colliders_pass(gpe_ctx *c, const char *who)
         S.passes += 1;
         return GPE_OK;
     }
-    GPE_TRY(launch_colliders_pass(c, c->pos, c->radius, c->n, S.cell_start, S.items, S.rec, (uint32_t)S.set.size(), S.view,
+    GPE_TRY(launch_colliders_pass(c, c->pos, c->radius, c->n, S.grid.cell_start, S.grid.items, S.rec, (uint32_t)S.set.size(), S.grid.view,
                                   S.pushed, S.surf, c->prev));
     S.passes += 1;
     return GPE_OK;
@@ -102,7 +98,7 @@ static gpe_status colliders_pass(gpe_ctx *c, const char *who)
 
 gpe_status gpe::colliders_after_step(gpe_ctx *c)
 {
-    return has_colliders(c) ? colliders_pass(c, "gpe_step") : GPE_OK;
+    return colliders_pass(c, "gpe_step");                             // (after_step has looked: the set is not empty)
 }
 
 gpe_status gpe_set_colliders(gpe_ctx *c, const gpe_collider *colliders, uint64_t k)
@@ -133,28 +129,19 @@ gpe_status gpe_set_colliders(gpe_ctx *c, const gpe_collider *colliders, uint64_t
         rec[2 * j] = make_float4(set[j].ax, set[j].ay, set[j].bx, set[j].by);
         rec[2 * j + 1] = make_float4(set[j].radius, 0.f, 0.f, 0.f);
     }
-    // the new records beside the old ones: a failure leaves the previous set as it was.  Read by index below 2 k.  no slack
+    // the new records and a counter word at 0 beside the old ones (set_upload.h).  Read by index below 2 k.  no slack
     float4 *d_rec = nullptr;
-    gpe_status st = ws_alloc(c, "gpe_set_colliders", &d_rec, 2 * k, 0, "grid.collider_rec");
-    if (st == GPE_OK && !S.pushed) st = ws_alloc(c, "gpe_set_colliders", &S.pushed, 1, 0, "grid.collider_pushed");
-    if (st == GPE_OK) {
-        hipError_t e = hipMemcpyAsync(d_rec, rec.data(), rec.size() * sizeof(float4), hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess) e = hipMemsetAsync(S.pushed, 0, sizeof(unsigned long long), c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);      // the host vector goes away on return
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            st = fail(c, GPE_ERR_HIP, std::string("gpe_set_colliders: upload: ") + hipGetErrorName(e));
-        }
-    }
-    if (st != GPE_OK) {
-        const std::string why = c->last_error;
-        dev_free(c, d_rec);
-        c->last_error = why;
-        return st;
-    }
-    dev_free(c, S.rec);
-    colliders_grid_release(c);                                         // built before the next pass
+    unsigned long long *d_pushed = nullptr;
+    HipSetUpload up({c}, "gpe_set_colliders");
+    up.reserve(&d_rec, 2 * k, "grid.collider_rec");
+    up.reserve(&d_pushed, 1, "grid.collider_pushed");
+    up.copy(d_rec, rec.data(), rec.size());
+    up.fill(d_pushed, 0, sizeof(unsigned long long));
+    GPE_TRY(up.finish());
+    dev_free(c, S.rec); dev_free(c, S.pushed);
+    cell_grid_release(c, S.grid);                                      // built before the next pass
     surfaces_drop(c, GPE_SURFACES_OF_COLLIDERS);                       // a new set gets new surfaces
+    S.pushed = d_pushed;
     S.rec = d_rec;
     S.set.swap(set);
     S.passes = 0;
@@ -164,11 +151,7 @@ gpe_status gpe_set_colliders(gpe_ctx *c, const gpe_collider *colliders, uint64_t
 gpe_status gpe_get_colliders(const gpe_ctx *c, gpe_collider *out, uint64_t capacity, uint64_t *k)
 {
     if (!c || !k || (capacity > 0 && !out)) return GPE_ERR_INVALID_ARG;
-    const std::vector<gpe_collider> &set = c->colliders.set;
-    *k = set.size();
-    const uint64_t m = std::min<uint64_t>(set.size(), capacity);
-    if (m) memcpy(out, set.data(), m * sizeof(gpe_collider));
-    return GPE_OK;
+    return rows_out(c->colliders.set, out, capacity, k);
 }
 
 gpe_status gpe_apply_colliders(gpe_ctx *c)
@@ -193,12 +176,11 @@ gpe_status gpe_get_colliders_info(gpe_ctx *c, gpe_colliders_info *info)
     if (has_colliders(c)) {
         GPE_HIP(c, hipSetDevice(c->device));
         unsigned long long pushed = 0;
-        GPE_HIP(c, hipMemcpyAsync(&pushed, S.pushed, sizeof(pushed), hipMemcpyDeviceToHost, c->stream));
-        GPE_TRY(check_device_errors(c));                               // (synchronises the stream)
+        GPE_TRY(read_back(c, S.pushed, &pushed, sizeof(pushed)));
         out.pushed = pushed;
-        if (S.grid_valid) {                                            // (none yet: no pass has needed it)
-            out.grid_x = S.view.gx; out.grid_y = S.view.gy;
-            out.list_entries = S.entries;
+        if (S.grid.valid) {                                            // (none yet: no pass has needed it)
+            out.grid_x = S.grid.view.gx; out.grid_y = S.grid.view.gy;
+            out.list_entries = S.grid.entries;
         }
     }
     *info = out;

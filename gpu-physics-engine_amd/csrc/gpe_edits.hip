@@ -155,9 +155,7 @@ gpe_status gpe_add_particles_free(gpe_ctx *c, gpe_particle_spawn *sp)
             GPE_TRY(launch_uid_iota(c, c->uid.uids, old_n, new_n, (uint32_t)c->uid.next));
             c->uid.next += added;
             c->uid.map_valid = false;
-            c->tracers.stale = true;
-            c->bonds.stale = true;
-            c->bodies.stale = true;
+            uid_slots_stale(c);
         }
         // as gpe_add_particles of the added candidates: max_radius = max(max_radius, r), in input order
         for (uint64_t i = 0; i < k; ++i)

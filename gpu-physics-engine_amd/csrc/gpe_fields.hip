@@ -1,7 +1,6 @@
 // gpe_fields.hip -- the force fields of a context (gpe_set_fields and the rest): the set, its lookup grid (field_grid.h,
-// rebuilt lazily) and the pass behind every step (k_fields.hip).  gpe_api.hip calls fields_after_step from gpe_step /
-// gpe_run, behind the colliders and before the observers, fields_world_changed from gpe_set_world and fields_release
-// from gpe_destroy.
+// rebuilt lazily) and the pass behind every step (k_fields.hip).  gpe_api.hip calls fields_after_step from after_step,
+// fields_world_changed from gpe_set_world and fields_release from gpe_destroy.
 #include <math.h>
 #include <string.h>
 
@@ -24,26 +23,17 @@ static uint32_t bits_of(float f)
     return u;
 }
 
-static void fields_grid_release(gpe_ctx *c)
-{
-    FieldState &S = c->fields;
-    dev_free(c, S.cell_start); dev_free(c, S.items);
-    S.grid_valid = false;
-    S.entries = 0;
-    S.view = ColliderGridView();
-}
-
 void gpe::fields_release(gpe_ctx *c)
 {
     FieldState &S = c->fields;
-    fields_grid_release(c);
+    cell_grid_release(c, S.grid);
     dev_free(c, S.rec); dev_free(c, S.touched);
     S = FieldState();
 }
 
 void gpe::fields_world_changed(gpe_ctx *c)
 {
-    c->fields.grid_valid = false;                                      // (the tables stay until the next pass replaces them)
+    c->fields.grid.valid = false;                                      // (the tables stay until the next pass replaces them)
 }
 
 gpe_status gpe::refuse_fields(gpe_ctx *c, const char *who)
@@ -52,48 +42,21 @@ gpe_status gpe::refuse_fields(gpe_ctx *c, const char *who)
                                                             "(gpe_set_fields with k = 0 clears them)");
 }
 
-// The grid for the world as it is now.  Builds only when the world has changed since the last build; that synchronises
-// (a pass in flight reads the old tables, the host's vectors go away on return).
+// The grid for the world as it is now.  Builds only when the world has changed since the last build; that synchronises.
 static gpe_status fields_grid_ready(gpe_ctx *c, const char *who)
 {
     FieldState &S = c->fields;
+    CellListGrid &G = S.grid;
     const float W = c->cfg.world_width, H = c->cfg.world_height;
-    if (S.cell_start && bits_of(W) == bits_of(S.grid_w) && bits_of(H) == bits_of(S.grid_h)) {
-        S.grid_valid = true;                                           // (gpe_set_world with the world it had)
+    if (G.cell_start && bits_of(W) == bits_of(G.w) && bits_of(H) == bits_of(G.h)) {
+        G.valid = true;                                                // (gpe_set_world with the world it had)
         return GPE_OK;
     }
-    GPE_HIP(c, hipStreamSynchronize(c->stream));
-    fields_grid_release(c);
     const uint32_t k = (uint32_t)S.set.size();
     std::vector<FieldRegion> regions(k);
     for (uint32_t j = 0; j < k; ++j) regions[j] = {S.set[j].shape, S.set[j].x0, S.set[j].y0, S.set[j].x1, S.set[j].y1};
     const FieldGrid g = field_grid_build(regions.data(), k, W, H);
-    // read by index: cell_start below gx * gy + 1 (the pass reads the words of a cell collider_cell_of names and the
-    // one behind it), items below cell_start's last word.  no slack
-    gpe_status st = ws_alloc(c, who, &S.cell_start, g.cell_start.size(), 0, "grid.field_cell_start");
-    if (st == GPE_OK) st = ws_alloc(c, who, &S.items, std::max<uint64_t>(g.items.size(), 1), 0, "grid.field_items");
-    if (st == GPE_OK) {
-        hipError_t e = hipMemcpyAsync(S.cell_start, g.cell_start.data(), g.cell_start.size() * sizeof(uint32_t),
-                                      hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess && !g.items.empty())
-            e = hipMemcpyAsync(S.items, g.items.data(), g.items.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            st = fail(c, GPE_ERR_HIP, std::string(who) + ": grid upload: " + hipGetErrorName(e));
-        }
-    }
-    if (st != GPE_OK) {
-        const std::string why = c->last_error;
-        fields_grid_release(c);                                        // no grid: the next pass tries again
-        c->last_error = why;
-        return st;
-    }
-    S.view = g.view;
-    S.entries = g.items.size();
-    S.grid_w = W; S.grid_h = H;
-    S.grid_valid = true;
-    return GPE_OK;
+    return cell_grid_upload(c, who, G, g.view, g.cell_start, g.items, "grid.field_cell_start", "grid.field_items");
 }
 
 // One pass over the particles as they are now.  Enqueues only, unless the grid has to be rebuilt first.
@@ -101,10 +64,10 @@ static gpe_status fields_pass(gpe_ctx *c, float dt, const char *who)
 {
     FieldState &S = c->fields;
     if (S.set.empty() || c->n == 0 || !c->pos) return GPE_OK;
-    if (!S.grid_valid) GPE_TRY(fields_grid_ready(c, who));
+    if (!S.grid.valid) GPE_TRY(fields_grid_ready(c, who));
     const float dt2 = dt * dt;                                         // as verlet_params forms it
     Scope s(c, "Fields");
-    GPE_TRY(launch_fields_pass(c, c->pos, c->prev, c->n, S.cell_start, S.items, S.rec, (uint32_t)S.set.size(), S.view, dt2,
+    GPE_TRY(launch_fields_pass(c, c->pos, c->prev, c->n, S.grid.cell_start, S.grid.items, S.rec, (uint32_t)S.set.size(), S.grid.view, dt2,
                                S.touched));
     S.passes += 1;
     return GPE_OK;
@@ -112,7 +75,7 @@ static gpe_status fields_pass(gpe_ctx *c, float dt, const char *who)
 
 gpe_status gpe::fields_after_step(gpe_ctx *c, float dt)
 {
-    return has_fields(c) ? fields_pass(c, dt, "gpe_step") : GPE_OK;
+    return fields_pass(c, dt, "gpe_step");                            // (after_step has looked: the set is not empty)
 }
 
 static const char *field_fault(const gpe_field &f)
@@ -160,28 +123,18 @@ gpe_status gpe_set_fields(gpe_ctx *c, const gpe_field *fields, uint64_t k)
         r.rr = field_rr(f.x1);
         r.code = field_code(f.shape, f.kind, f.falloff);
     }
-    // the new records beside the old ones: a failure leaves the previous set as it was.  Read by index below 3 k.  no slack
+    // the new records and a counter word at 0 beside the old ones (set_upload.h).  Read by index below 3 k.  no slack
     float4 *d_rec = nullptr;
-    gpe_status st = ws_alloc(c, "gpe_set_fields", &d_rec, 3 * k, 0, "grid.field_rec");
-    if (st == GPE_OK && !S.touched) st = ws_alloc(c, "gpe_set_fields", &S.touched, 1, 0, "grid.field_touched");
-    if (st == GPE_OK) {
-        hipError_t e = hipMemcpyAsync(d_rec, rec.data(), rec.size() * sizeof(FieldRecord), hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess) e = hipMemsetAsync(S.touched, 0, sizeof(unsigned long long), c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);      // the host vector goes away on return
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            st = fail(c, GPE_ERR_HIP, std::string("gpe_set_fields: upload: ") + hipGetErrorName(e));
-        }
-    }
-    if (st != GPE_OK) {
-        const std::string why = c->last_error;
-        dev_free(c, d_rec);
-        if (S.set.empty()) dev_free(c, S.touched);                     // (a context without fields holds no buffer of theirs)
-        c->last_error = why;
-        return st;
-    }
-    dev_free(c, S.rec);
-    fields_grid_release(c);                                            // built before the next pass
+    unsigned long long *d_touched = nullptr;
+    HipSetUpload up({c}, "gpe_set_fields");
+    up.reserve(&d_rec, 3 * k, "grid.field_rec");
+    up.reserve(&d_touched, 1, "grid.field_touched");
+    up.copy(d_rec, rec.data(), rec.size());
+    up.fill(d_touched, 0, sizeof(unsigned long long));
+    GPE_TRY(up.finish());
+    dev_free(c, S.rec); dev_free(c, S.touched);
+    cell_grid_release(c, S.grid);                                      // built before the next pass
+    S.touched = d_touched;
     S.rec = d_rec;
     S.set.swap(set);
     S.passes = 0;
@@ -191,11 +144,7 @@ gpe_status gpe_set_fields(gpe_ctx *c, const gpe_field *fields, uint64_t k)
 gpe_status gpe_get_fields(const gpe_ctx *c, gpe_field *out, uint64_t capacity, uint64_t *k)
 {
     if (!c || !k || (capacity > 0 && !out)) return GPE_ERR_INVALID_ARG;
-    const std::vector<gpe_field> &set = c->fields.set;
-    *k = set.size();
-    const uint64_t m = std::min<uint64_t>(set.size(), capacity);
-    if (m) memcpy(out, set.data(), m * sizeof(gpe_field));
-    return GPE_OK;
+    return rows_out(c->fields.set, out, capacity, k);
 }
 
 gpe_status gpe_apply_fields(gpe_ctx *c, float dt)
@@ -221,12 +170,11 @@ gpe_status gpe_get_fields_info(gpe_ctx *c, gpe_fields_info *info)
     if (has_fields(c)) {
         GPE_HIP(c, hipSetDevice(c->device));
         unsigned long long touched = 0;
-        GPE_HIP(c, hipMemcpyAsync(&touched, S.touched, sizeof(touched), hipMemcpyDeviceToHost, c->stream));
-        GPE_TRY(check_device_errors(c));                               // (synchronises the stream)
+        GPE_TRY(read_back(c, S.touched, &touched, sizeof(touched)));
         out.touched = touched;
-        if (S.cell_start) {                                            // (none yet: no pass has needed it)
-            out.grid_x = S.view.gx; out.grid_y = S.view.gy;
-            out.list_entries = S.entries;
+        if (S.grid.cell_start) {                                       // (none yet: no pass has needed it)
+            out.grid_x = S.grid.view.gx; out.grid_y = S.grid.view.gy;
+            out.list_entries = S.grid.entries;
         }
     }
     *info = out;

@@ -4,8 +4,10 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <string.h>
 
 #include <algorithm>
+#include <initializer_list>
 #include <string>
 #include <vector>
 
@@ -15,6 +17,7 @@
 #include "native_policy.h"
 #include "scope_events.h"
 #include "scope_stamps.h"
+#include "set_upload.h"
 
 namespace gpe {
 
@@ -390,7 +393,7 @@ struct UidState {               // opt-in particle uids (gpe_enable_uids; k_uids
 
 struct TracerState {            // the tracer recorder (gpe_tracers_*; k_tracers.hip).  Observation state: no step reads it
     bool armed = false;
-    bool stale = true;                           // the slot table is out of date: set wherever uid.map_valid is cleared
+    bool stale = true;                           // the slot table is out of date (uid_slots_stale)
     uint32_t fields = 0;                         // GPE_TRACER_*
     uint64_t k = 0, every = 1, frames = 0;       // the configuration of gpe_tracers_begin
     uint64_t steps_seen = 0;                     // steps since begin
@@ -418,6 +421,16 @@ struct MonitorState {
     uint8_t *partials = nullptr;
 };
 
+// The cell-list lookup grid of the static colliders and of the force fields (collider_grid.h, field_grid.h; the holder
+// and its upload: gpe_colliders.hip).  Rebuilt before the next pass when what it was built for has changed
+struct CellListGrid {
+    bool valid = false;
+    float rb = 0.f, w = 0.f, h = 0.f;            // the radius bound (colliders only) and the world at the build (compared by bits)
+    ColliderGridView view;
+    uint32_t *cell_start = nullptr, *items = nullptr;
+    uint64_t entries = 0;
+};
+
 // the static colliders (gpe_set_colliders; gpe_colliders.hip, k_colliders.hip).  Step state: gpe_step / gpe_run apply them
 struct ColliderState {
     std::vector<gpe_collider> set;               // the colliders as the host gave them (empty: none, nothing is launched)
@@ -427,19 +440,14 @@ struct ColliderState {
     std::vector<gpe_surface> surfaces;           // one row per collider, as the host gave them (-0.0 stored as +0)
     float4 *surf = nullptr;                      // the same rows on the device
     uint64_t passes = 0;                         // passes enqueued since then
-    // the lookup grid (collider_grid.h), rebuilt before the next pass when what it was built for has changed
-    bool grid_valid = false;
-    float grid_rb = 0.f, grid_w = 0.f, grid_h = 0.f;   // gpe_max_radius and the world at the build (compared by bits)
-    ColliderGridView view;
-    uint32_t *cell_start = nullptr, *items = nullptr;
-    uint64_t entries = 0;
+    CellListGrid grid;                           // built for gpe_max_radius and the world
 };
 
 // the sweep of the static colliders (gpe_set_collider_sweep; gpe_sweep.hip, k_sweep.hip, k_sweep.h).  A mode of their
 // pass, like gravity: it outlives gpe_set_colliders and gpe_set_surfaces
 struct SweepState {
     uint32_t mode = 0;                           // GPE_SWEEP_OFF / GPE_SWEEP_ON
-    uint64_t passes = 0;                         // swept passes enqueued since the last gpe_set_collider_sweep
+    uint64_t passes = 0;                         // swept passes enqueued since the mode was last set
     unsigned long long *counts = nullptr;        // two words: particles swept, particles stopped, since then (null: never on)
 };
 
@@ -448,7 +456,7 @@ struct BondState {
     std::vector<gpe_bond> set;                   // the bonds as the host gave them (empty: none, nothing is launched)
     uint32_t iterations = 1;
     uint64_t nodes = 0;                          // m: the distinct uids the bonds name
-    bool stale = true;                           // node_slot is out of date: set wherever tracers.stale is (behind it)
+    bool stale = true;                           // node_slot is out of date (uid_slots_stale)
     uint64_t passes = 0, resolves = 0;           // since the last gpe_set_bonds
     // device side, read by index below the stated count
     uint4 *rec = nullptr;                        // k: (node a, node b | anchor index, rest, w), bond_graph.h BondRecord
@@ -469,7 +477,7 @@ struct BodyState {
     std::vector<uint32_t> member_uid_host;       // members: as the host gave them (gpe_get_bodies)
     std::vector<float> member_rest_host;         // 2 * members
     uint64_t members = 0;
-    bool stale = true;                           // member_slot is out of date: set wherever bonds.stale is (behind it)
+    bool stale = true;                           // member_slot is out of date (uid_slots_stale)
     uint64_t passes = 0, resolves = 0;           // since the last gpe_set_bodies
     uint32_t class_start[7] = {0, 0, 0, 0, 0, 0, 0};   // order[class_start[q], class_start[q + 1]): the bodies of width 2 << q
     // device side, read by index below the stated count
@@ -489,17 +497,11 @@ struct FieldState {
     float4 *rec = nullptr;                       // 3 per field: k_field.h FieldRecord
     unsigned long long *touched = nullptr;       // one word: particles whose prev was written since the last gpe_set_fields
     uint64_t passes = 0;                         // passes enqueued since then
-    // the lookup grid (field_grid.h), rebuilt before the next pass when the world it was built for has changed
-    bool grid_valid = false;
-    float grid_w = 0.f, grid_h = 0.f;            // the world at the build (compared by bits)
-    ColliderGridView view;
-    uint32_t *cell_start = nullptr, *items = nullptr;
-    uint64_t entries = 0;
+    CellListGrid grid;                           // built for the world; gpe_set_world clears `valid`, the tables stay
 };
 
 // the moving colliders (gpe_set_movers; gpe_movers.hip, k_movers.hip, k_mover.h, mover_grid.h).  Step state: gpe_step /
-// gpe_run advance them on the device, rebuild their lookup grid there and apply them, behind the bodies and before the
-// static colliders
+// gpe_run advance them on the device, rebuild their lookup grid there and apply them
 struct MoverState {
     std::vector<gpe_mover> set;                  // the movers as the host gave them (empty: none, nothing is launched)
     MoverDef *def = nullptr;                     // one per mover: the rest capsule and the motion (k_mover.h)
@@ -550,10 +552,7 @@ struct MoverPassArgs {
 // pass, like gravity: not part of MoverState, so a new mover set leaves it alone.  The three buffers are allocated when
 // the mode is first switched on, for kMoversMax movers, and kept until gpe_destroy
 struct MoverCarry;
-struct MoverSweepState {
-    uint32_t mode = 0;                           // GPE_SWEEP_OFF / GPE_SWEEP_ON
-    uint64_t passes = 0;                         // swept passes enqueued since the last gpe_set_mover_sweep
-    unsigned long long *counts = nullptr;        // two words: particles swept, particles stopped, since then (null: never on)
+struct MoverSweepState : SweepState {
     MoverCarry *carry = nullptr;                 // kMoversMax: what each mover carries a point by in the last step
     float4 *old = nullptr;                       // kMoversMax: the posed capsules before the last advance
 };
@@ -1018,6 +1017,32 @@ void dev_free(gpe_ctx *c, T *&p)
     (void)dev_release(c, p);
 }
 
+// The device calls behind SetUpload (set_upload.h), on the context's stream: tables through ws_alloc / dev_free, so tags,
+// messages and guard zones are what they are everywhere.  A failing copy, fill or wait reads "<who>: <stage>: <hip name>".
+struct HipUploadBackend {
+    using Status = gpe_status;
+    gpe_ctx *c;
+    std::string &last_error() { return c->last_error; }
+    gpe_status reserve(const char *who, void **p, uint64_t bytes, const char *tag) { return ws_alloc(c, who, (uint8_t **)p, bytes, 0, tag); }
+    void release(void *p) { dev_free(c, p); }
+    gpe_status done(const char *who, const char *stage, hipError_t e)
+    {
+        if (e == hipSuccess) return GPE_OK;
+        (void)hipGetLastError();
+        return fail(c, GPE_ERR_HIP, std::string(who) + ": " + (stage ? std::string(stage) + ": " : "") + hipGetErrorName(e));
+    }
+    gpe_status copy(const char *who, const char *stage, void *dst, const void *src, uint64_t bytes)
+    {
+        return done(who, stage, hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->stream));
+    }
+    gpe_status fill(const char *who, const char *stage, void *dst, int byte, uint64_t bytes)
+    {
+        return done(who, stage, hipMemsetAsync(dst, byte, bytes, c->stream));
+    }
+    gpe_status wait(const char *who, const char *stage) { return done(who, stage, hipStreamSynchronize(c->stream)); }
+};
+using HipSetUpload = SetUpload<HipUploadBackend>;
+
 // The 256-byte aligned staging layout of a result's requested parts: part() = the offset of the next part, which takes
 // room only when it is requested; bytes = what the parts so far take.
 struct StageLayout {
@@ -1046,6 +1071,23 @@ gpe_status error_words_reserve(gpe_ctx *c);        // gpe_native.hip: c->err_wor
 void error_words_release(gpe_ctx *c);
 gpe_status grow_particle_buffers(gpe_ctx *c, uint64_t cap);
 gpe_status init_index_buffers(gpe_ctx *c, uint64_t lo, uint64_t hi);
+// `bytes` from the device into host memory, then the sticky error words (that synchronises the stream)
+inline gpe_status read_back(gpe_ctx *c, const void *device_ptr, void *host_ptr, uint64_t bytes)
+{
+    GPE_HIP(c, hipMemcpyAsync(host_ptr, device_ptr, bytes, hipMemcpyDeviceToHost, c->stream));
+    return check_device_errors(c);
+}
+// a get call of a set the host keeps: *k = its size, its first min(k, capacity) rows to out
+template <typename T>
+gpe_status rows_out(const std::vector<T> &set, T *out, uint64_t capacity, uint64_t *k)
+{
+    *k = set.size();
+    const uint64_t m = std::min<uint64_t>(set.size(), capacity);
+    if (m) memcpy(out, set.data(), m * sizeof(T));
+    return GPE_OK;
+}
+// The storage order or the uids have changed: whatever keeps storage slots by uid looks them up again before its next use
+inline void uid_slots_stale(gpe_ctx *c) { c->tracers.stale = c->bonds.stale = c->bodies.stale = true; }
 void refresh_cell_size(gpe_ctx *c);
 gpe_status reconfigure(gpe_ctx *c);
 gpe_status uid_map_ready(gpe_ctx *c);
@@ -1064,30 +1106,41 @@ gpe_status box_region(gpe_ctx *c, const char *who, float x0, float y0, float x1,
 // gpe_observe.hip: the tracers and the monitor of an armed context
 gpe_status observers_after_step(gpe_ctx *c);       // after every step of gpe_step / gpe_run
 void observers_release(gpe_ctx *c);
+// The step sets (the X_after_step calls: see after_step, gpe_api.hip).
 // gpe_colliders.hip: the static colliders of a context that holds some
 inline bool has_colliders(const gpe_ctx *c) { return !c->colliders.set.empty(); }
 gpe_status refuse_colliders(gpe_ctx *c, const char *who);   // GPE_ERR_UNSUPPORTED: sharding a context that holds colliders
-gpe_status colliders_after_step(gpe_ctx *c);       // after every step of gpe_step / gpe_run, before the observers
+gpe_status colliders_after_step(gpe_ctx *c);
 void colliders_release(gpe_ctx *c);
-// gpe_sweep.hip: the swept form of that pass
+// ... and the cell-list grid they share with the fields: G = the host tables under the two tags (synchronises); a
+// failure reads "<who>: grid upload: ..." and leaves no grid, so the next pass tries again
+void cell_grid_release(gpe_ctx *c, CellListGrid &G);
+gpe_status cell_grid_upload(gpe_ctx *c, const char *who, CellListGrid &G, const ColliderGridView &view,
+                            const std::vector<uint32_t> &cell_start, const std::vector<uint32_t> &items,
+                            const char *cell_start_tag, const char *items_tag);
+// gpe_sweep.hip: the swept form of that pass; the mode setter and the info getter it shares with the movers' sweep
 gpe_status sweep_pass(gpe_ctx *c);                 // colliders_pass while the mode is on: the grid is ready
 void sweep_release(gpe_ctx *c);
+struct SweepTable { void **p; uint64_t bytes; const char *tag; };   // a buffer a mode keeps beside its counters
+gpe_status sweep_mode_set(gpe_ctx *c, const char *who, SweepState &W, uint32_t mode, const char *tag,
+                          std::initializer_list<SweepTable> more = {});
+gpe_status sweep_mode_info(gpe_ctx *c, const char *who, const SweepState &W, gpe_sweep_info *info);
 // gpe_surfaces.hip: the surfaces of the two sets; a new set drops its target's
 void surfaces_drop(gpe_ctx *c, uint32_t target);   // GPE_SURFACES_OF_*: frees the rows, the next pass is the plain one
 // gpe_bonds.hip: the distance bonds of a context that holds some
 inline bool has_bonds(const gpe_ctx *c) { return !c->bonds.set.empty(); }
 gpe_status refuse_bonds(gpe_ctx *c, const char *who);       // GPE_ERR_UNSUPPORTED: taking the uids from a context that holds bonds
-gpe_status bonds_after_step(gpe_ctx *c);           // after every step of gpe_step / gpe_run, before the colliders
+gpe_status bonds_after_step(gpe_ctx *c);
 void bonds_release(gpe_ctx *c);
 // gpe_bodies.hip: the rigid and soft bodies of a context that holds some
 inline bool has_bodies(const gpe_ctx *c) { return !c->bodies.set.empty(); }
 gpe_status refuse_bodies(gpe_ctx *c, const char *who);      // GPE_ERR_UNSUPPORTED: taking the uids from a context that holds bodies
-gpe_status bodies_after_step(gpe_ctx *c);          // after every step of gpe_step / gpe_run, behind the bonds, before the colliders
+gpe_status bodies_after_step(gpe_ctx *c);
 void bodies_release(gpe_ctx *c);
 // gpe_fields.hip: the force fields of a context that holds some
 inline bool has_fields(const gpe_ctx *c) { return !c->fields.set.empty(); }
 gpe_status refuse_fields(gpe_ctx *c, const char *who);      // GPE_ERR_UNSUPPORTED: sharding a context that holds fields
-gpe_status fields_after_step(gpe_ctx *c, float dt);         // after every step of gpe_step / gpe_run, behind the colliders, before the observers
+gpe_status fields_after_step(gpe_ctx *c, float dt);
 void fields_world_changed(gpe_ctx *c);                      // gpe_set_world: the lookup grid follows before the next pass
 void fields_release(gpe_ctx *c);
 
@@ -1095,9 +1148,12 @@ void fields_release(gpe_ctx *c);
 inline bool has_movers(const gpe_ctx *c) { return !c->movers.set.empty(); }
 gpe_status refuse_movers(gpe_ctx *c, const char *who);      // GPE_ERR_UNSUPPORTED: sharding a context that holds movers
 gpe_status movers_check_dt(gpe_ctx *c, float dt, const char *who);  // GPE_ERR_INVALID_ARG: dt breaks the set's contract; before anything is launched
-gpe_status movers_after_step(gpe_ctx *c, float dt);         // after every step of gpe_step / gpe_run, behind the bodies, before the colliders
+gpe_status movers_after_step(gpe_ctx *c, float dt);
 void movers_release(gpe_ctx *c);
 void mover_sweep_release(gpe_ctx *c);                       // gpe_destroy: the mode's counters and records
+// The sharding entry points refuse a context that holds step sets: bonds and bodies (they name their particles by uid:
+// the more telling refusal), then the call's own uid refusal when uids are on, then colliders, fields and movers
+gpe_status refuse_step_sets(gpe_ctx *c, const char *who, const char *uid_refusal);
 
 // profiling scope: a pair of timestamps on ctx->stream when ctx->profiling, else nothing -- slots of the stamp buffer
 // (scope_stamps.h), or hipEvents where scope_uses_stamps() says no.  kSharedBoundaries: inside a ScopeRegion the scope

@@ -2,9 +2,9 @@
 // and the three enqueues behind every step -- a memset of the lookup grid, k_movers_build (advance, pose, list) and
 // k_movers_pass (k_movers.hip).  Nothing in a step synchronises or asks the host for more than the grid's view
 // (mover_grid.h: host arithmetic on the world and the radius bound).  gpe_api.hip calls movers_check_dt before a step
-// launches anything, movers_after_step from gpe_step / gpe_run behind the bodies and before the static colliders, and
-// movers_release from gpe_destroy.  The movers' sweep (gpe_set_mover_sweep, at the end of this file) is a mode of the
-// same three enqueues: while it is on, the build and the pass are k_mover_sweep.hip's.
+// launches anything, movers_after_step from after_step, and movers_release from gpe_destroy.  The movers' sweep
+// (gpe_set_mover_sweep, at the end of this file) is a mode of the same three enqueues: while it is on, the build and the
+// pass are k_mover_sweep.hip's.
 #include <math.h>
 #include <string.h>
 
@@ -111,7 +111,7 @@ static gpe_status movers_pass(gpe_ctx *c, float dt)
 
 gpe_status gpe::movers_after_step(gpe_ctx *c, float dt)
 {
-    return has_movers(c) ? movers_pass(c, dt) : GPE_OK;
+    return movers_pass(c, dt);                                        // (after_step has looked: the set is not empty)
 }
 
 // the poses of the states q (2 per mover) as the device holds them: 6 floats per mover, and the pass's records
@@ -162,30 +162,20 @@ gpe_status gpe_set_movers(gpe_ctx *c, const gpe_mover *movers, uint64_t k)
     }
     movers_pose_all(def, fresh.data(), 2, pose, rec);
     N.words = mover_mask_words((uint32_t)k);
-    // read by index: def below k, pose below 6 k, rec below 2 k; the grid below the bytes of the largest view (every view
-    // mover_grid_choose returns has at most kMoverGridMaxDim cells per axis).  no slack
-    gpe_status st = ws_alloc(c, "gpe_set_movers", &N.def, k, 0, "grid.mover_def");
-    if (st == GPE_OK) st = ws_alloc(c, "gpe_set_movers", &N.pose, 6 * k, 0, "grid.mover_pose");
-    if (st == GPE_OK) st = ws_alloc(c, "gpe_set_movers", &N.rec, 2 * k, 0, "grid.mover_rec");
-    if (st == GPE_OK) st = ws_alloc(c, "gpe_set_movers", &N.pushed, 1, 0, "grid.mover_pushed");
-    if (st == GPE_OK) st = ws_alloc(c, "gpe_set_movers", &N.grid, grid_listed_offset(kMoverGridMaxCells, N.words) + 8, 0, "grid.mover_masks");
-    if (st == GPE_OK) {
-        hipError_t e = hipMemcpyAsync(N.def, def.data(), k * sizeof(MoverDef), hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(N.pose, pose.data(), pose.size() * sizeof(float), hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(N.rec, rec.data(), rec.size() * sizeof(float4), hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess) e = hipMemsetAsync(N.pushed, 0, sizeof(unsigned long long), c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);      // the host vectors go away on return
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            st = fail(c, GPE_ERR_HIP, std::string("gpe_set_movers: upload: ") + hipGetErrorName(e));
-        }
-    }
-    if (st != GPE_OK) {
-        const std::string why = c->last_error;
-        movers_buffers_free(c, N);
-        c->last_error = why;
-        return st;
-    }
+    // the new tables beside the old ones (set_upload.h).  Read by index: def below k, pose below 6 k, rec below 2 k; the
+    // grid below the bytes of the largest view (every view mover_grid_choose returns has at most kMoverGridMaxDim cells
+    // per axis).  no slack
+    HipSetUpload up({c}, "gpe_set_movers");
+    up.reserve(&N.def, k, "grid.mover_def");
+    up.reserve(&N.pose, 6 * k, "grid.mover_pose");
+    up.reserve(&N.rec, 2 * k, "grid.mover_rec");
+    up.reserve(&N.pushed, 1, "grid.mover_pushed");
+    up.reserve(&N.grid, grid_listed_offset(kMoverGridMaxCells, N.words) + 8, "grid.mover_masks");
+    up.copy(N.def, def.data(), k);
+    up.copy(N.pose, pose.data(), pose.size());
+    up.copy(N.rec, rec.data(), rec.size());
+    up.fill(N.pushed, 0, sizeof(unsigned long long));
+    GPE_TRY(up.finish());
     movers_buffers_free(c, S);
     N.set.swap(set);
     S = N;
@@ -195,11 +185,7 @@ gpe_status gpe_set_movers(gpe_ctx *c, const gpe_mover *movers, uint64_t k)
 gpe_status gpe_get_movers(const gpe_ctx *c, gpe_mover *out, uint64_t capacity, uint64_t *k)
 {
     if (!c || !k || (capacity > 0 && !out)) return GPE_ERR_INVALID_ARG;
-    const std::vector<gpe_mover> &set = c->movers.set;
-    *k = set.size();
-    const uint64_t m = std::min<uint64_t>(set.size(), capacity);
-    if (m) memcpy(out, set.data(), m * sizeof(gpe_mover));
-    return GPE_OK;
+    return rows_out(c->movers.set, out, capacity, k);
 }
 
 gpe_status gpe_get_mover_poses(gpe_ctx *c, gpe_mover_pose *out, uint64_t capacity, uint64_t *k)
@@ -211,8 +197,7 @@ gpe_status gpe_get_mover_poses(gpe_ctx *c, gpe_mover_pose *out, uint64_t capacit
     const uint64_t m = std::min<uint64_t>(S.set.size(), capacity);
     if (m == 0) return GPE_OK;
     GPE_HIP(c, hipSetDevice(c->device));
-    GPE_HIP(c, hipMemcpyAsync(out, S.pose, m * sizeof(gpe_mover_pose), hipMemcpyDeviceToHost, c->stream));
-    return check_device_errors(c);                                     // (synchronises the stream)
+    return read_back(c, S.pose, out, m * sizeof(gpe_mover_pose));
 }
 
 gpe_status gpe_set_mover_poses(gpe_ctx *c, const gpe_mover_pose *poses, uint64_t k)
@@ -264,13 +249,12 @@ gpe_status gpe_get_movers_info(gpe_ctx *c, gpe_movers_info *info)
         GPE_HIP(c, hipSetDevice(c->device));
         out.mask_words = S.words;
         unsigned long long pushed = 0, listed = 0;
-        GPE_HIP(c, hipMemcpyAsync(&pushed, S.pushed, sizeof(pushed), hipMemcpyDeviceToHost, c->stream));
         if (S.built) {                                                 // (no grid yet: no pass has built one)
             const uint64_t at = grid_listed_offset((uint64_t)S.view.view.gx * S.view.view.gy, S.words);
             GPE_HIP(c, hipMemcpyAsync(&listed, S.grid + at, sizeof(listed), hipMemcpyDeviceToHost, c->stream));
             out.grid_x = S.view.view.gx; out.grid_y = S.view.view.gy;
         }
-        GPE_TRY(check_device_errors(c));                               // (synchronises the stream)
+        GPE_TRY(read_back(c, S.pushed, &pushed, sizeof(pushed)));
         out.pushed = pushed;
         out.listed = listed;
     }
@@ -289,39 +273,12 @@ void gpe::mover_sweep_release(gpe_ctx *c)
 gpe_status gpe_set_mover_sweep(gpe_ctx *c, uint32_t mode)
 {
     if (!c) return GPE_ERR_INVALID_ARG;
-    if (mode != GPE_SWEEP_OFF && mode != GPE_SWEEP_ON)
-        return fail(c, GPE_ERR_INVALID_ARG, "gpe_set_mover_sweep: mode must be GPE_SWEEP_OFF or GPE_SWEEP_ON");
-    if (is_sharded(c)) return refuse_sharded(c, "gpe_set_mover_sweep");
-    GPE_HIP(c, hipSetDevice(c->device));
-    GPE_HIP(c, hipStreamSynchronize(c->stream));                       // (a pass in flight counts into the old words)
+    // carry and old: one row per mover, written and read below the set's size <= kMoversMax.  no slack.  A new set needs
+    // no new ones
     MoverSweepState &M = c->mover_sweep;
-    if (mode == GPE_SWEEP_ON && !(M.counts && M.carry && M.old)) {
-        // counts: two words, written by index 0 and 1 alone; carry and old: one row per mover, written and read below the
-        // set's size <= kMoversMax.  no slack.  Kept until gpe_destroy once the mode has been on: a new set needs no new ones
-        MoverSweepState N;
-        gpe_status st = ws_alloc(c, "gpe_set_mover_sweep", &N.counts, 2, 0, "grid.msweep_counts");
-        if (st == GPE_OK) st = ws_alloc(c, "gpe_set_mover_sweep", &N.carry, kMoversMax, 0, "grid.msweep_carry");
-        if (st == GPE_OK) st = ws_alloc(c, "gpe_set_mover_sweep", &N.old, kMoversMax, 0, "grid.msweep_old");
-        if (st != GPE_OK) {
-            const std::string why = c->last_error;
-            dev_free(c, N.counts); dev_free(c, N.carry); dev_free(c, N.old);
-            c->last_error = why;
-            return st;
-        }
-        dev_free(c, M.counts); dev_free(c, M.carry); dev_free(c, M.old);
-        M.counts = N.counts; M.carry = N.carry; M.old = N.old;
-    }
-    if (M.counts) {
-        hipError_t e = hipMemsetAsync(M.counts, 0, 2 * sizeof(unsigned long long), c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(c, GPE_ERR_HIP, std::string("gpe_set_mover_sweep: ") + hipGetErrorName(e));
-        }
-    }
-    M.mode = mode;
-    M.passes = 0;
-    return GPE_OK;
+    return sweep_mode_set(c, "gpe_set_mover_sweep", M, mode, "grid.msweep_counts",
+                          {{(void **)&M.carry, kMoversMax * sizeof(MoverCarry), "grid.msweep_carry"},
+                           {(void **)&M.old, kMoversMax * sizeof(float4), "grid.msweep_old"}});
 }
 
 gpe_status gpe_get_mover_sweep(const gpe_ctx *c, uint32_t *mode)
@@ -333,23 +290,5 @@ gpe_status gpe_get_mover_sweep(const gpe_ctx *c, uint32_t *mode)
 
 gpe_status gpe_get_mover_sweep_info(gpe_ctx *c, gpe_sweep_info *info)
 {
-    if (!c) return GPE_ERR_INVALID_ARG;
-    if (!info || info->struct_size < sizeof(gpe_sweep_info))
-        return fail(c, GPE_ERR_INVALID_ARG, "gpe_get_mover_sweep_info: NULL info or bad struct_size");
-    const MoverSweepState &M = c->mover_sweep;
-    gpe_sweep_info out;
-    memset(&out, 0, sizeof(out));
-    out.struct_size = info->struct_size;
-    out.mode = M.mode;
-    out.passes = M.passes;
-    if (M.counts) {
-        GPE_HIP(c, hipSetDevice(c->device));
-        unsigned long long counts[2] = {0, 0};
-        GPE_HIP(c, hipMemcpyAsync(counts, M.counts, sizeof(counts), hipMemcpyDeviceToHost, c->stream));
-        GPE_TRY(check_device_errors(c));                               // (synchronises the stream)
-        out.swept = counts[0];
-        out.stopped = counts[1];
-    }
-    *info = out;
-    return GPE_OK;
+    return c ? sweep_mode_info(c, "gpe_get_mover_sweep_info", c->mover_sweep, info) : GPE_ERR_INVALID_ARG;
 }

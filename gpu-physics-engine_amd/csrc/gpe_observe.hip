@@ -76,28 +76,16 @@ gpe_status gpe_tracers_begin(gpe_ctx *c, const gpe_tracer_config *cfg)
     const uint64_t rows = cfg->frames * cfg->k;
     // every array is read and written by index below k or frames * k (the resolve pass reads keys by single words
     // below k, the uids by 16-byte groups below n / 4 and single words below n).  no slack
-    const char *who = "gpe_tracers_begin";
-    gpe_status st = ws_alloc(c, who, &t.keys, k, 0, "tracers.keys");
-    if (st == GPE_OK) st = ws_alloc(c, who, &t.perm, k, 0, "tracers.perm");
-    if (st == GPE_OK) st = ws_alloc(c, who, &t.slot_index, k, 0, "tracers.slot_index");
-    if (st == GPE_OK && (cfg->fields & GPE_TRACER_POS)) st = ws_alloc(c, who, &t.ring_pos, rows, 0, "tracers.ring_pos");
-    if (st == GPE_OK && (cfg->fields & GPE_TRACER_PREV)) st = ws_alloc(c, who, &t.ring_prev, rows, 0, "tracers.ring_prev");
-    if (st == GPE_OK && (cfg->fields & GPE_TRACER_INDEX)) st = ws_alloc(c, who, &t.ring_index, rows, 0, "tracers.ring_index");
-    if (st == GPE_OK) {
-        hipError_t e = hipMemcpyAsync(t.keys, keys.data(), k * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(t.perm, perm.data(), k * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);      // the host vectors go away on return
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            st = fail(c, GPE_ERR_HIP, std::string("gpe_tracers_begin: upload: ") + hipGetErrorName(e));
-        }
-    }
-    if (st != GPE_OK) {
-        const std::string why = c->last_error;
-        tracers_release(c);                                            // unarmed, as before
-        c->last_error = why;
-        return st;
-    }
+    HipSetUpload up({c}, "gpe_tracers_begin");                         // (a failure leaves the recorder unarmed, as before)
+    up.reserve(&t.keys, k, "tracers.keys");
+    up.reserve(&t.perm, k, "tracers.perm");
+    up.reserve(&t.slot_index, k, "tracers.slot_index");
+    up.reserve(&t.ring_pos, (cfg->fields & GPE_TRACER_POS) ? rows : 0, "tracers.ring_pos");
+    up.reserve(&t.ring_prev, (cfg->fields & GPE_TRACER_PREV) ? rows : 0, "tracers.ring_prev");
+    up.reserve(&t.ring_index, (cfg->fields & GPE_TRACER_INDEX) ? rows : 0, "tracers.ring_index");
+    up.copy(t.keys, keys.data(), k);
+    up.copy(t.perm, perm.data(), k);
+    GPE_TRY(up.finish());
     t.armed = true;
     t.stale = true;
     t.fields = cfg->fields;

@@ -741,13 +741,7 @@ gpe_status gpe_shard_set_particles(gpe_ctx *c, const float *pos_xy, const float 
                                    const uint32_t *order_key, uint64_t n, uint64_t capacity)
 {
     if (!c) return GPE_ERR_INVALID_ARG;
-    if (has_bonds(c)) return refuse_bonds(c, "gpe_shard_set_particles");
-    if (has_bodies(c)) return refuse_bodies(c, "gpe_shard_set_particles");
-    if (c->uid.on)
-        return fail(c, GPE_ERR_UNSUPPORTED, "gpe_shard_set_particles: sharded runs carry order keys, not uids (uids are on)");
-    if (has_colliders(c)) return refuse_colliders(c, "gpe_shard_set_particles");
-    if (has_fields(c)) return refuse_fields(c, "gpe_shard_set_particles");
-    if (has_movers(c)) return refuse_movers(c, "gpe_shard_set_particles");
+    GPE_TRY(refuse_step_sets(c, "gpe_shard_set_particles", "sharded runs carry order keys, not uids (uids are on)"));
     if (!order_key) return fail(c, GPE_ERR_INVALID_ARG, "gpe_shard_set_particles: order_key is NULL");
     GPE_TRY(gpe_set_particles(c, pos_xy, prev_xy, radius, n));
     GPE_TRY(gpe_use_order_keys(c, 1));

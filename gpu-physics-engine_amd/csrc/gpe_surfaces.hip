@@ -47,26 +47,15 @@ gpe_status gpe_set_surfaces(gpe_ctx *c, uint32_t target, const gpe_surface *rows
         surfaces_drop(c, target);
         return GPE_OK;
     }
-    // the new rows beside the old ones: a failure leaves the previous surfaces as they were.  Read by index below k (the
-    // winner's index, always a member of the set).  no slack
+    // the new rows beside the old ones (set_upload.h).  Read by index below k (the winner's index, always a member of
+    // the set).  no slack
     float4 *d_surf = nullptr, *d_old = nullptr;
-    gpe_status st = ws_alloc(c, "gpe_set_surfaces", &d_surf, k, 0, of_movers ? "grid.mover_surf" : "grid.collider_surf");
-    if (st == GPE_OK && of_movers) st = ws_alloc(c, "gpe_set_surfaces", &d_old, k, 0, "grid.mover_old");
-    if (st == GPE_OK) {
-        hipError_t e = hipMemcpyAsync(d_surf, set.data(), k * sizeof(gpe_surface), hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess && d_old) e = hipMemsetAsync(d_old, 0, k * sizeof(float4), c->stream);   // (the build writes it before a pass reads it)
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);      // the host vector goes away on return
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            st = fail(c, GPE_ERR_HIP, std::string("gpe_set_surfaces: upload: ") + hipGetErrorName(e));
-        }
-    }
-    if (st != GPE_OK) {
-        const std::string why = c->last_error;
-        dev_free(c, d_surf); dev_free(c, d_old);
-        c->last_error = why;
-        return st;
-    }
+    HipSetUpload up({c}, "gpe_set_surfaces");
+    up.reserve(&d_surf, k, of_movers ? "grid.mover_surf" : "grid.collider_surf");
+    up.reserve(&d_old, of_movers ? k : 0, "grid.mover_old");
+    up.copy(d_surf, set.data(), k);
+    if (d_old) up.fill(d_old, 0, k * sizeof(float4));                  // (the build writes it before a pass reads it)
+    GPE_TRY(up.finish());
     surfaces_drop(c, target);
     if (of_movers) {
         c->movers.surf = d_surf; c->movers.old = d_old;
@@ -82,9 +71,5 @@ gpe_status gpe_get_surfaces(const gpe_ctx *c, uint32_t target, gpe_surface *out,
 {
     if (!c || !k || (capacity > 0 && !out)) return GPE_ERR_INVALID_ARG;
     if (target != GPE_SURFACES_OF_COLLIDERS && target != GPE_SURFACES_OF_MOVERS) return GPE_ERR_INVALID_ARG;
-    const std::vector<gpe_surface> &set = target == GPE_SURFACES_OF_MOVERS ? c->movers.surfaces : c->colliders.surfaces;
-    *k = set.size();
-    const uint64_t m = std::min<uint64_t>(set.size(), capacity);
-    if (m) memcpy(out, set.data(), m * sizeof(gpe_surface));
-    return GPE_OK;
+    return rows_out(target == GPE_SURFACES_OF_MOVERS ? c->movers.surfaces : c->colliders.surfaces, out, capacity, k);
 }

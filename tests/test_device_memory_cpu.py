@@ -59,13 +59,14 @@ def _calls(code, name):
 
 
 def test_every_allocation_site_names_a_tag():
-    """Every call of an allocating helper (gpe_dev_reserve, dev_reserve, dev_alloc, ws_alloc, gpe_edits.hip's
-    edit_buffer, gpe_native.hip's reserve, ensure_words) ends in a tag: a literal of the registry's naming scheme, or an expression made of such literals
+    """Every call of an allocating helper (gpe_dev_reserve, dev_reserve, dev_alloc, ws_alloc, a set upload's
+    up.reserve, gpe_edits.hip's edit_buffer, gpe_native.hip's reserve, ensure_words) ends in a tag: a literal of the registry's naming scheme, or an expression made of such literals
     (a choice between tags), or the tag parameter a wrapper hands on.  No tag is longer than gpe_guard_zone.tag holds."""
     sites, tags = 0, set()
     for path in _sources():
         code = _code(path)
-        names = ["gpe_dev_reserve", "dev_reserve", "dev_alloc", "ws_alloc", "edit_buffer", "ensure_words"]
+        names = ["gpe_dev_reserve", "dev_reserve", "dev_alloc", "ws_alloc", r"up\.reserve", "edit_buffer", "ensure_words",
+                 "cell_grid_upload", "sweep_mode_set"]             # (the last two hand their tags on to up.reserve)
         if os.path.basename(path) == "gpe_native.hip":
             names.append("reserve")
         for name in names:
@@ -73,7 +74,7 @@ def test_every_allocation_site_names_a_tag():
                 last = args.rsplit(",", 1)[1].strip() if "," in args else args
                 # (a ?: choice between tags holds no comma; its literals are what counts)
                 found = re.findall(TAG, args.split(",", 3)[-1] if name != "ensure_words" else last)
-                assert found or last in ("tag", "b.second"), (os.path.basename(path), name, args)
+                assert found or last in ("tag", "t.tag", "cell_start_tag", "items_tag", "b.second"), (os.path.basename(path), name, args)
                 sites += 1
                 tags.update(t.strip('"') for t in found)
     assert sites >= 127, sites
@@ -105,7 +106,7 @@ WORKSPACES = {
 
 def test_every_workspace_releases_exactly_what_it_reserves():
     """For each workspace the fields its reserve functions allocate (the pointer handed to dev_alloc / ws_alloc /
-    edit_buffer, next to a tag of that workspace) are the fields its release function hands to dev_free, no more and no
+    edit_buffer / a set upload's up.reserve, next to a tag of that workspace) are the fields its release function hands to dev_free, no more and no
     fewer -- and free_particle_buffers / observers_release call every release function."""
     api = _code(os.path.join(CSRC, "gpe_api.hip"))
     observe = _code(os.path.join(CSRC, "gpe_observe.hip"))
@@ -114,7 +115,7 @@ def test_every_workspace_releases_exactly_what_it_reserves():
         code = _code(os.path.join(CSRC, fname))
         reserved = set()
         for fn in reserves:
-            for name in ("dev_alloc", "ws_alloc", "edit_buffer"):
+            for name in ("dev_alloc", "ws_alloc", "edit_buffer", r"up\.reserve"):
                 for args in _calls(_body(code, fn), name):
                     tag = re.search(r'"%s\.([a-z0-9_]+)"' % prefix, args)
                     if not tag:
@@ -136,9 +137,9 @@ def _statements(code):
 
 def unpaired_map_invalidations(csrc=CSRC):
     """Where csrc/*.hip clears uid.map_valid (outside uid_map_build, whose callers decide), or sets it true outside
-    uid_map_ready (which rebuilds the map of uids that have not changed), without `tracers.stale = true` as the next
-    statement: [(file, statement)].  A site that forgets it lets later frames read rows through the storage indices of
-    an older order, and past n after a removal (gpe_internal.h, TracerState::stale)."""
+    uid_map_ready (which rebuilds the map of uids that have not changed), without `uid_slots_stale(c)` as the next
+    statement: [(file, statement)].  A site that forgets it lets later frames, bonds and bodies read rows through the
+    storage indices of an older order, and past n after a removal (gpe_internal.h, TracerState::stale)."""
     bad, sites = [], 0
     for path in sorted(glob.glob(os.path.join(csrc, "*.hip"))):
         code = _code(path)
@@ -148,28 +149,32 @@ def unpaired_map_invalidations(csrc=CSRC):
         for stmt, after in _statements(code):
             if re.search(r"\bmap_valid\s*=\s*(false|true)$", stmt):
                 sites += 1
-                if not re.search(r"\btracers\.stale\s*=\s*true$", after):
+                if not re.search(r"\buid_slots_stale\(c\)$", after):
                     bad.append((os.path.basename(path), stmt))
     return bad, sites
 
 
 def test_every_map_invalidation_marks_the_tracers_slot_table_stale():
     """Every `map_valid = false` outside uid_map_build, and the one `map_valid = true` outside uid_map_ready
-    (gpe_set_uids, whose map is that of new uids), is followed at once by `tracers.stale = true`.  Deleting any one of
-    those lines from a copy of the sources makes unpaired_map_invalidations() name the site (tried with each in turn)."""
+    (gpe_set_uids, whose map is that of new uids), is followed at once by `uid_slots_stale(c)`, which sets the stale flag
+    of the tracers, the bonds and the bodies.  Deleting any one of those lines from a copy of the sources makes
+    unpaired_map_invalidations() name the site (tried with each in turn)."""
+    helper = re.search(r"inline void uid_slots_stale\(gpe_ctx \*c\) \{([^}]*)\}", _code(os.path.join(CSRC, "gpe_internal.h")))
+    assert helper and all(re.search(r"c->%s\.stale\b" % s, helper.group(1)) for s in ("tracers", "bonds", "bodies"))
+    assert re.search(r"=\s*true;\s*$", helper.group(1)), helper.group(1)
     bad, sites = unpaired_map_invalidations()
     assert not bad, bad
     assert sites >= 8, sites                # (seven clear it, gpe_set_uids sets it; gpe_tracers_begin's own stale = true has no pair)
 
 
 def test_the_pairing_check_notices_each_missing_line(tmp_path):
-    """The check above on copies of csrc/ with one `tracers.stale = true` line after a map_valid assignment removed:
+    """The check above on copies of csrc/ with one `uid_slots_stale(c)` line after a map_valid assignment removed:
     each copy fails, and names one site."""
     lines = {}
     for path in sorted(glob.glob(os.path.join(CSRC, "*.hip"))):
         src = open(path).read().split("\n")
         for i, line in enumerate(src):
-            if re.search(r"tracers\.stale = true;", line) and i and re.search(r"map_valid = (false|true);", src[i - 1]):
+            if re.search(r"uid_slots_stale\(c\);", line) and i and re.search(r"map_valid = (false|true);", src[i - 1]):
                 lines[(path, i)] = src
     assert len(lines) >= 8, len(lines)
     for n, ((path, i), src) in enumerate(sorted(lines.items())):

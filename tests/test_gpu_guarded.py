@@ -244,6 +244,93 @@ def test_workspace_allocations_keep_their_tags_payloads_and_slack(gpe):
     st.close()
 
 
+# ---- the step sets: replacing one leaks nothing and frees nothing twice ----------------------------------------------
+def _step_set_case(gpe, st, feature):
+    """(set(k), clear(), the feature's tags as a predicate, the tags that stay live behind the clear) of one step set on
+    the 8 x 8 lattice of _step_set_state: k walls / fields / pistons, k pair bonds, k bodies of 4 members."""
+    L = gpe._lib
+
+    def walls(k):
+        return np.float32([[5.0 + 10.0 * j, 2.0, 5.0 + 10.0 * j, 50.0, 0.5] for j in range(k)])
+
+    def pistons(k):
+        m = np.zeros(k, gpe.MOVER_DTYPE)
+        m["ax"] = m["bx"] = 5.0 + 10.0 * np.arange(k)
+        m["ay"], m["by"], m["radius"] = 2.0, 20.0, 0.5
+        m["kind"], m["vx"], m["travel"] = L.MOVER_LINEAR, 1.0, 10.0
+        return m
+
+    def winds(k):
+        f = np.zeros(k, gpe.FIELD_DTYPE)
+        f["shape"], f["kind"], f["falloff"], f["fx"] = L.FIELD_EVERYWHERE, L.FIELD_UNIFORM, L.FALLOFF_NONE, 1.0
+        return f
+
+    def bodies(k):
+        return st.bodies_from_groups([[16 * g, 16 * g + 1, 16 * g + 8, 16 * g + 9] for g in range(k)])
+
+    def surfaces_of(target, obstacles):
+        def set_(k):
+            obstacles(k)                                   # (a new set drops its surfaces: the rows are always new ones)
+            st.set_surfaces(target, gpe.surface_rows(k, restitution=0.5, friction=0.1))
+        return set_
+
+    def sweep_of(obstacles, switch):
+        def set_(k):
+            obstacles(k)
+            switch(True)
+        return set_
+
+    def set_walls(k): st.set_colliders(walls(k))
+    def set_pistons(k): st.set_movers(pistons(k))
+    msweep = {"grid.msweep_counts", "grid.msweep_carry", "grid.msweep_old"}
+    return {
+        "colliders": (set_walls, st.clear_colliders, lambda t: t.startswith("grid.collider_"), set()),
+        "fields": (lambda k: st.set_fields(winds(k)), st.clear_fields, lambda t: t.startswith("grid.field_"), set()),
+        "movers": (set_pistons, st.clear_movers, lambda t: t.startswith("grid.mover_"), set()),
+        "bonds": (lambda k: st.set_bonds(gpe.pair_bonds(2 * np.arange(k), 2 * np.arange(k) + 1, 3.0)), st.clear_bonds,
+                  lambda t: t.startswith("uid.bond_"), set()),
+        "bodies": (lambda k: st.set_bodies(*bodies(k)), st.clear_bodies, lambda t: t.startswith("uid.body_"), set()),
+        "surfaces-of-colliders": (surfaces_of("colliders", set_walls), lambda: st.clear_surfaces("colliders"),
+                                  lambda t: t == "grid.collider_surf", set()),
+        "surfaces-of-movers": (surfaces_of("movers", set_pistons), lambda: st.clear_surfaces("movers"),
+                               lambda t: t in ("grid.mover_surf", "grid.mover_old"), set()),
+        # the two modes keep their buffers until the context goes: live exactly once each behind the switch-off
+        "collider-sweep": (sweep_of(set_walls, st.set_collider_sweep), lambda: st.set_collider_sweep(False),
+                           lambda t: t == "grid.sweep_counts", {"grid.sweep_counts"}),
+        "mover-sweep": (sweep_of(set_pistons, st.set_mover_sweep), lambda: st.set_mover_sweep(False),
+                        lambda t: t in msweep, msweep),
+    }[feature]
+
+
+@pytest.mark.parametrize("feature", ["colliders", "fields", "movers", "bonds", "bodies", "surfaces-of-colliders",
+                                     "surfaces-of-movers", "collider-sweep", "mover-sweep"])
+def test_replacing_a_step_set_leaks_nothing_and_frees_nothing_twice(gpe, feature):
+    """64 particles with uids on, guarded.  The set with k = 1, a step, replaced with k = 3, a step, with k = 1 again, a
+    step, cleared: after every call guard_check() reports no damage and no tag of the feature is live more than once
+    (a leak of the commit path shows as a second live entry, a double free as a damaged report or a fault); after the
+    clear no tag of the feature is live -- the two sweep modes, which keep their buffers, hold each of theirs once."""
+    i = np.arange(64)
+    pos = np.stack([10.0 + 3.0 * (i % 8), 10.0 + 3.0 * (i // 8)], axis=1).astype(np.float32)
+    st = gpe.State(pos, np.ones(64, np.float32), world=(60.0, 60.0), flags=gpe._lib.FLAG_GUARD_ALLOCS)
+    st.enable_uids()
+    set_, clear, mine, kept = _step_set_case(gpe, st, feature)
+
+    def live():
+        assert st.ctx.guard_check() == [] and st.ctx.guard_damaged == 0
+        tags = [t for t, _, _, state in st.ctx.guard_registry() if state == "live" and mine(t)]
+        assert len(tags) == len(set(tags)), tags
+        return set(tags)
+    assert live() == set()
+    for k in (1, 3, 1):
+        set_(k)
+        assert live(), (feature, k)                        # (the predicate names tags the feature really uses)
+        st.update(1 / 60)
+        assert live(), (feature, k)
+    clear()
+    assert live() == kept
+    st.close()
+
+
 # ---- primitives on user buffers of exactly n elements ---------------------------------------------------------------
 SORT_SIZES = [1, 63, 64, 65, 4095, 4096, 4097, 8191, 8193, (3 << 20) - 1, (3 << 20) + 1]
 
