@@ -52,6 +52,7 @@ NEAREST_MAX_M = 64
 COLLIDERS_MAX = 4096
 BONDS_MAX, BOND_MAX_DEGREE, BOND_ITER_MAX = 4194304, 1024, 32
 BOND_ANCHOR, BOND_BROKEN = 1, 2
+BENDS_MAX, BEND_MAX_DEGREE, BEND_ITER_MAX = 4194304, 1024, 32
 BODIES_MAX, BODY_MAX_MEMBERS, BODY_MEMBERS_MAX = 1048576, 4096, 16777216
 BODY_BROKEN = 1
 FIELDS_MAX = 4096
@@ -262,6 +263,20 @@ class GpeBondsInfo(C.Structure):
                 ("passes", C.c_uint64), ("live", C.c_uint64), ("broken", C.c_uint64), ("resolves", C.c_uint64)]
 
 
+class GpeBend(C.Structure):
+    """gpe_bend: the angle at the hinge uid_b from (uid_a - uid_b) to (uid_c - uid_b) held at the rest angle
+    (rest_cos, rest_sin).  32 bytes."""
+    _fields_ = [("uid_a", C.c_uint32), ("uid_b", C.c_uint32), ("uid_c", C.c_uint32), ("rest_cos", C.c_float),
+                ("rest_sin", C.c_float), ("stiffness", C.c_float), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class GpeBendsInfo(C.Structure):
+    """gpe_bends_info: in struct_size; out the relaxations per pass, the bends set and the distinct uids they name, and
+    since the last gpe_set_bends the passes run and the times the uids were looked up.  40 bytes."""
+    _fields_ = [("struct_size", C.c_uint32), ("iterations", C.c_uint32), ("k", C.c_uint64), ("nodes", C.c_uint64),
+                ("passes", C.c_uint64), ("resolves", C.c_uint64)]
+
+
 class GpeBody(C.Structure):
     """gpe_body: members [first, first + count) of the set's member arrays keep their rest shape.  24 bytes."""
     _fields_ = [("first", C.c_uint32), ("count", C.c_uint32), ("stiffness", C.c_float), ("break_distance", C.c_float),
@@ -394,6 +409,10 @@ SYMBOLS = [
     ("gpe_get_bonds", _I32, [_VP, C.POINTER(GpeBond), C.POINTER(C.c_uint8), _U64, C.POINTER(_U64)]),
     ("gpe_apply_bonds", _I32, [_VP]),
     ("gpe_get_bonds_info", _I32, [_VP, C.POINTER(GpeBondsInfo)]),
+    ("gpe_set_bends", _I32, [_VP, C.POINTER(GpeBend), _U64, C.c_uint32]),
+    ("gpe_get_bends", _I32, [_VP, C.POINTER(GpeBend), _U64, C.POINTER(_U64)]),
+    ("gpe_apply_bends", _I32, [_VP]),
+    ("gpe_get_bends_info", _I32, [_VP, C.POINTER(GpeBendsInfo)]),
     ("gpe_set_bodies", _I32, [_VP, C.POINTER(GpeBody), _U64, C.POINTER(C.c_uint32), C.POINTER(C.c_float), _U64]),
     ("gpe_get_bodies", _I32, [_VP, C.POINTER(GpeBody), C.POINTER(C.c_uint8), _U64, C.POINTER(_U64),
                               C.POINTER(C.c_uint32), C.POINTER(C.c_float), _U64, C.POINTER(_U64)]),

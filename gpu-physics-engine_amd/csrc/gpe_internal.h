@@ -471,6 +471,23 @@ struct BondState {
     unsigned long long *broken = nullptr;        // one word: bonds broken
 };
 
+// the bend constraints (gpe_set_bends; gpe_bends.hip, k_bends.hip, bend_graph.h).  Step state: gpe_step / gpe_run relax
+// them in front of the bonds
+struct BendState {
+    std::vector<gpe_bend> set;                   // the bends as the host gave them (empty: none, nothing is launched)
+    uint32_t iterations = 1;
+    uint64_t nodes = 0;                          // m: the distinct uids the bends name
+    bool stale = true;                           // node_slot is out of date (uid_slots_stale)
+    uint64_t passes = 0, resolves = 0;           // since the last gpe_set_bends
+    // device side, read by index below the stated count
+    uint4 *rec = nullptr;                        // 2 k: (node a, hinge b, node c, rc), (rs, stiffness, 0, 0), bend_graph.h BendRecord
+    uint32_t *node_uid = nullptr;                // m: the nodes' uids, ascending
+    uint32_t *node_slot = nullptr;               // m: each node's storage index, 0xffffffff for none (valid unless stale)
+    uint32_t *row_start = nullptr, *inc = nullptr;   // m + 1 / row_start[m]: a node's bends, bend << 2 | role
+    float4 *corr = nullptr;                      // k: this relaxation's corrections (da.x, da.y, dc.x, dc.y)
+    uint8_t *state = nullptr;                    // k: 0 acted, 2 inert in this relaxation
+};
+
 // the rigid and soft bodies (gpe_set_bodies; gpe_bodies.hip, k_bodies.hip, body_table.h).  Step state: gpe_step / gpe_run match them
 struct BodyState {
     std::vector<gpe_body> set;                   // the bodies as the host gave them (empty: none, nothing is launched)
@@ -913,6 +930,7 @@ struct gpe_ctx {
     gpe::ColliderState colliders;
     gpe::SweepState sweep;
     gpe::BondState bonds;
+    gpe::BendState bends;
     gpe::BodyState bodies;
     gpe::FieldState fields;
     gpe::MoverState movers;
@@ -1087,7 +1105,7 @@ gpe_status rows_out(const std::vector<T> &set, T *out, uint64_t capacity, uint64
     return GPE_OK;
 }
 // The storage order or the uids have changed: whatever keeps storage slots by uid looks them up again before its next use
-inline void uid_slots_stale(gpe_ctx *c) { c->tracers.stale = c->bonds.stale = c->bodies.stale = true; }
+inline void uid_slots_stale(gpe_ctx *c) { c->tracers.stale = c->bonds.stale = c->bends.stale = c->bodies.stale = true; }
 void refresh_cell_size(gpe_ctx *c);
 gpe_status reconfigure(gpe_ctx *c);
 gpe_status uid_map_ready(gpe_ctx *c);
@@ -1132,6 +1150,11 @@ inline bool has_bonds(const gpe_ctx *c) { return !c->bonds.set.empty(); }
 gpe_status refuse_bonds(gpe_ctx *c, const char *who);       // GPE_ERR_UNSUPPORTED: taking the uids from a context that holds bonds
 gpe_status bonds_after_step(gpe_ctx *c);
 void bonds_release(gpe_ctx *c);
+// gpe_bends.hip: the bend constraints of a context that holds some
+inline bool has_bends(const gpe_ctx *c) { return !c->bends.set.empty(); }
+gpe_status refuse_bends(gpe_ctx *c, const char *who);       // GPE_ERR_UNSUPPORTED: taking the uids from a context that holds bends
+gpe_status bends_after_step(gpe_ctx *c);
+void bends_release(gpe_ctx *c);
 // gpe_bodies.hip: the rigid and soft bodies of a context that holds some
 inline bool has_bodies(const gpe_ctx *c) { return !c->bodies.set.empty(); }
 gpe_status refuse_bodies(gpe_ctx *c, const char *who);      // GPE_ERR_UNSUPPORTED: taking the uids from a context that holds bodies
@@ -1151,7 +1174,7 @@ gpe_status movers_check_dt(gpe_ctx *c, float dt, const char *who);  // GPE_ERR_I
 gpe_status movers_after_step(gpe_ctx *c, float dt);
 void movers_release(gpe_ctx *c);
 void mover_sweep_release(gpe_ctx *c);                       // gpe_destroy: the mode's counters and records
-// The sharding entry points refuse a context that holds step sets: bonds and bodies (they name their particles by uid:
+// The sharding entry points refuse a context that holds step sets: bonds, bodies and bends (they name their particles by uid:
 // the more telling refusal), then the call's own uid refusal when uids are on, then colliders, fields and movers
 gpe_status refuse_step_sets(gpe_ctx *c, const char *who, const char *uid_refusal);
 
@@ -1380,6 +1403,9 @@ gpe_status launch_colliders_pass(gpe_ctx *c, float2 *pos, const float *radius, u
                                  unsigned long long *pushed, const float4 *surf = nullptr, float2 *prev = nullptr);
 // distance bonds (k_bonds.hip): `iterations` relaxations of the k bonds of B over pos[0, n) in place, two launches each
 gpe_status launch_bonds_pass(gpe_ctx *c, float2 *pos, const float *radius, uint64_t n, const BondState &B, uint32_t k,
+                             uint32_t m, uint32_t iterations);
+// bend constraints (k_bends.hip): `iterations` relaxations of the k bends of B over pos[0, n) in place, two launches each
+gpe_status launch_bends_pass(gpe_ctx *c, float2 *pos, const float *radius, uint64_t n, const BendState &B, uint32_t k,
                              uint32_t m, uint32_t iterations);
 // rigid and soft bodies (k_bodies.hip): one shape matching pass of the k bodies of B over pos[0, n) in place, one launch
 // per non-empty width class

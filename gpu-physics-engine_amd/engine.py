@@ -80,6 +80,22 @@ def anchor_bonds(uids, points, rest_length=0.0, stiffness=1.0, max_length=0.0):
     return rows
 
 
+# set_bends / bends: the rows of gpe_bend (32 bytes each, the struct's layout)
+BEND_DTYPE = np.dtype([(name, np.uint32 if ctype is C.c_uint32 else np.float32) for name, ctype in L.GpeBend._fields_])
+assert BEND_DTYPE.itemsize == C.sizeof(L.GpeBend)
+
+
+def bends_from_angles(uid_a, uid_b, uid_c, angle, stiffness=1.0):
+    """Rows of BEND_DTYPE that hold the angle at the hinge uid_b[i] from (uid_a[i] - uid_b[i]) to (uid_c[i] - uid_b[i])
+    at angle[i] radians (scalars are broadcast): cos and sin in float64, rounded once to float32."""
+    ua = np.asarray(uid_a, np.uint32).reshape(-1)
+    rows = np.zeros(len(ua), BEND_DTYPE)
+    rows["uid_a"], rows["uid_b"], rows["uid_c"] = ua, uid_b, uid_c
+    theta = np.broadcast_to(np.asarray(angle, np.float64), ua.shape)
+    rows["rest_cos"], rows["rest_sin"], rows["stiffness"] = np.cos(theta), np.sin(theta), stiffness
+    return rows
+
+
 # set_movers / movers: the rows of gpe_mover (56 bytes each); mover_poses: the rows of gpe_mover_pose (24 bytes each)
 MOVER_DTYPE = np.dtype([(name, np.uint32 if ctype is C.c_uint32 else np.float32) for name, ctype in L.GpeMover._fields_])
 MOVER_POSE_DTYPE = np.dtype([(name, np.float32) for name, _ in L.GpeMoverPose._fields_])
@@ -772,6 +788,37 @@ class ParticleSystem:
         info = L.GpeBondsInfo(struct_size=C.sizeof(L.GpeBondsInfo))
         self.ctx.call("gpe_get_bonds_info", C.byref(info))
         return {name: getattr(info, name) for name, _ in L.GpeBondsInfo._fields_ if name != "struct_size"}
+
+    # Bend constraints (not in the reference; include/gpe.h): the angle at a hinge particle between two others, by uid,
+    # relaxed on the device after every update() / step of run(), in front of the bonds.  Step state: save() keeps them.
+    def set_bends(self, bends, iterations=1):
+        """gpe_set_bends: replace the set by the rows of a BEND_DTYPE array (bends_from_angles / bends_from_positions
+        build them), relaxed `iterations` times per pass; no rows clear it.  The counters start anew."""
+        rows = np.ascontiguousarray(bends, BEND_DTYPE).reshape(-1)
+        k = len(rows)
+        self.ctx.call("gpe_set_bends", rows.ctypes.data_as(C.POINTER(L.GpeBend)) if k else None, k, int(iterations))
+
+    def bends(self):
+        """gpe_get_bends -> records BEND_DTYPE[k]."""
+        k = C.c_uint64()
+        self.ctx.call("gpe_get_bends", None, 0, C.byref(k))
+        rows = np.zeros(max(k.value, 1), BEND_DTYPE)
+        self.ctx.call("gpe_get_bends", rows.ctypes.data_as(C.POINTER(L.GpeBend)), k.value, C.byref(k))
+        return rows[:k.value]
+
+    def clear_bends(self):
+        """gpe_set_bends with k = 0."""
+        self.ctx.call("gpe_set_bends", None, 0, 1)
+
+    def apply_bends(self):
+        """gpe_apply_bends: one pass now (the hook of a host that steps module by module).  Does not synchronise."""
+        self.ctx.call("gpe_apply_bends")
+
+    def bends_info(self):
+        """gpe_get_bends_info -> dict(iterations, k, nodes, passes, resolves)."""
+        info = L.GpeBendsInfo(struct_size=C.sizeof(L.GpeBendsInfo))
+        self.ctx.call("gpe_get_bends_info", C.byref(info))
+        return {name: getattr(info, name) for name, _ in L.GpeBendsInfo._fields_ if name != "struct_size"}
 
     # Rigid and soft bodies (not in the reference; include/gpe.h): groups of particles, named by uid, that keep their rest
     # shape: one shape matching pass on the device after every update() / step of run(), behind the bonds and before the
@@ -1500,6 +1547,48 @@ class State:
         """ParticleSystem.bonds_info -> dict(iterations, k, nodes, passes, live, broken, resolves)."""
         return self.particles.bonds_info()
 
+    def set_bends(self, bends, iterations=1):
+        """ParticleSystem.set_bends: bend constraints (rows of BEND_DTYPE) relaxed after every step, in front of the bonds."""
+        self.particles.set_bends(bends, iterations)
+
+    def bends(self):
+        """ParticleSystem.bends -> records BEND_DTYPE[k]."""
+        return self.particles.bends()
+
+    def clear_bends(self):
+        """ParticleSystem.clear_bends."""
+        self.particles.clear_bends()
+
+    def apply_bends(self):
+        """ParticleSystem.apply_bends: one pass now."""
+        self.particles.apply_bends()
+
+    def bends_info(self):
+        """ParticleSystem.bends_info -> dict(iterations, k, nodes, passes, resolves)."""
+        return self.particles.bends_info()
+
+    def bends_from_positions(self, triples, stiffness=1.0):
+        """Rows of BEND_DTYPE for the uid triples (a, hinge b, c) whose rest angles are the angles the particles hold
+        now: the cosine and sine of the angle from a - b to c - b in float64 from the downloaded positions, rounded once
+        to float32.  Every uid must name a live particle and no arm may have length 0."""
+        t = np.asarray(triples, np.uint32).reshape(-1, 3)
+        uids = self.uids()
+        order = np.argsort(uids, kind="stable")
+        at = np.searchsorted(uids[order], t)
+        if (at >= len(uids)).any() or (uids[order[np.minimum(at, len(uids) - 1)]] != t).any():
+            raise ValueError("bends_from_positions: a uid names no particle")
+        p = self.positions().astype(np.float64)[order[at]]             # (k, 3, 2)
+        u, v = p[:, 0] - p[:, 1], p[:, 2] - p[:, 1]
+        den = np.sqrt((u * u).sum(axis=1) * (v * v).sum(axis=1))
+        if not (den > 0).all():
+            raise ValueError("bends_from_positions: an arm of length 0")
+        rows = np.zeros(len(t), BEND_DTYPE)
+        rows["uid_a"], rows["uid_b"], rows["uid_c"] = t[:, 0], t[:, 1], t[:, 2]
+        rows["rest_cos"] = (u[:, 0] * v[:, 0] + u[:, 1] * v[:, 1]) / den
+        rows["rest_sin"] = (u[:, 0] * v[:, 1] - u[:, 1] * v[:, 0]) / den
+        rows["stiffness"] = stiffness
+        return rows
+
     def set_bodies(self, bodies, member_uid, member_rest):
         """ParticleSystem.set_bodies: groups of particles (rows of BODY_DTYPE) matched to their rest shape after every
         step, behind the bonds and before the colliders."""
@@ -1649,6 +1738,7 @@ class State:
         the same bits without it and is armed again by its host.  The run monitor (monitor_begin) is not stored either,
         for the same reason.  Static colliders are step state: a set that is present is written (`colliders`), and so
         are distance bonds with their relaxation count and broken flags (`bonds`, `bond_iterations`, `bonds_broken`) and
+        bend constraints with their relaxation count (`bends`, `bend_iterations`) and
         bodies with their members and broken flags (`bodies`, `bodies_broken`, `body_member_uid`, `body_member_rest`) and
         force fields (`fields`) and moving colliders with their poses (`movers`, `mover_poses`), and the surfaces of
         the two sets where present (`collider_surfaces`, `mover_surfaces`), and the static colliders' sweep where it is
@@ -1681,6 +1771,9 @@ class State:
             extra.update(colliders=caps)
         if self._uids_on():
             extra.update(uids=self.uids(), next_uid=np.array([self.next_uid()], np.uint64))
+            bends = self.bends()                                       # (they name particles by uid: none without uids)
+            if len(bends):
+                extra.update(bends=bends, bend_iterations=np.array([self.bends_info()["iterations"]], np.uint32))
         pressed, at = self.ctx.mouse()
         if pressed:
             extra.update(mouse=np.array(at, np.float32))
@@ -1722,6 +1815,8 @@ class State:
                 rows = d["bonds"].astype(BOND_DTYPE)
                 rows["flags"] |= np.where(d["bonds_broken"], L.BOND_BROKEN, 0).astype(np.uint32)
                 st.set_bonds(rows, int(d["bond_iterations"][0]))
+            if "bends" in d.files:                                 # (after the uids they name)
+                st.set_bends(d["bends"].astype(BEND_DTYPE), int(d["bend_iterations"][0]))
             if "bodies" in d.files:                                # (after the uids and the bonds; a broken body starts broken)
                 rows = d["bodies"].astype(BODY_DTYPE)
                 rows["flags"] |= np.where(d["bodies_broken"], L.BODY_BROKEN, 0).astype(np.uint32)

@@ -401,6 +401,30 @@ class ParticleSystem {
         ctx_->call(gpe_get_bonds_info(ctx_->raw(), &info));
         return info;
     }
+    // not in the reference: bend constraints (include/gpe.h): the angle at a hinge particle between two others, all named
+    // by uid, held at a rest angle given as (rest_cos, rest_sin); relaxed on the device after every step of gpe_step /
+    // gpe_run, in front of the bonds.  Step state: a snapshot keeps the set and its relaxation count.
+    void set_bends(const std::vector<gpe_bend> &bends, uint32_t iterations = 1)
+    {
+        ctx_->call(gpe_set_bends(ctx_->raw(), bends.empty() ? nullptr : bends.data(), bends.size(), iterations));
+    }
+    std::vector<gpe_bend> bends() const
+    {
+        uint64_t k = 0;
+        ctx_->call(gpe_get_bends(ctx_->raw(), nullptr, 0, &k));
+        std::vector<gpe_bend> out(k);
+        ctx_->call(gpe_get_bends(ctx_->raw(), k ? out.data() : nullptr, k, &k));
+        return out;
+    }
+    void clear_bends() { ctx_->call(gpe_set_bends(ctx_->raw(), nullptr, 0, 1)); }
+    void apply_bends() { ctx_->call(gpe_apply_bends(ctx_->raw())); }   // one pass now: before apply_bonds
+    gpe_bends_info bends_info() const
+    {
+        gpe_bends_info info{};
+        info.struct_size = sizeof(info);
+        ctx_->call(gpe_get_bends_info(ctx_->raw(), &info));
+        return info;
+    }
     // not in the reference: rigid and soft bodies (include/gpe.h): groups of particles named by uid that keep their rest
     // shape, matched on the device after every step of gpe_step / gpe_run, behind the bonds and before the static
     // colliders.  Step state: a snapshot keeps the set, its members and the broken flags (a broken body is given back

@@ -443,7 +443,7 @@ gpe_status gpe_get_sweep_info(gpe_ctx *ctx, gpe_sweep_info *info);         /* sy
  * full turns.  The movers are a second set beside the static colliders, independent of them.  While a context holds a
  * set, gpe_step and every iteration of gpe_run advance every mover by dt ON THE DEVICE, rebuild the movers' lookup grid
  * there and run one pass over the particles, stream-ordered, no host round trip (csrc/k_movers.hip): a memset and two
- * launches per step.  Order: step -> bonds -> bodies -> movers -> colliders -> fields -> tracers / monitor: the static
+ * launches per step.  Order: step -> bends -> bonds -> bodies -> movers -> colliders -> fields -> tracers / monitor: the static
  * walls keep the last word over a piston that squeezes particles against them.  The per-module calls run no pass:
  * gpe_apply_movers(dt) is their hook.  A context without movers launches and allocates exactly what it does without
  * this section.
@@ -614,7 +614,7 @@ gpe_status gpe_get_surfaces(const gpe_ctx *ctx, uint32_t target, gpe_surface *ou
  * particles, named by uid (gpe_enable_uids must be on), at a rest length; an anchor bond (GPE_BOND_ANCHOR) holds one
  * particle to a fixed point.  While a context holds a set, gpe_step and every iteration of gpe_run run one pass after
  * the step, BEFORE the static colliders (walls keep the last word) and the tracers and the monitor, stream-ordered, on
- * the device (csrc/k_bonds.hip): step -> bonds -> bodies -> movers -> colliders -> fields -> tracers / monitor.  The per-module calls run no pass:
+ * the device (csrc/k_bonds.hip): step -> bends -> bonds -> bodies -> movers -> colliders -> fields -> tracers / monitor.  The per-module calls run no pass:
  * gpe_apply_bonds is their hook.  A context without bonds launches and allocates exactly what it does without this
  * section.
  *  - One relaxation (csrc/k_bond.h is the one definition).  Every bond is judged from the positions the relaxation
@@ -632,7 +632,8 @@ gpe_status gpe_get_surfaces(const gpe_ctx *ctx, uint32_t target, gpe_surface *ou
  *    never, so the velocity change is the one Verlet implies.  Every other particle keeps every bit, unclamped.
  *  - A pass relaxes the set `iterations` times (Jacobi: no relaxation reads what it has written itself), so the
  *    result depends on the set and the particles alone, never on launch order, storage order or mode.
- *  - What a bond is not: there is no angular constraint (a chain folds freely); Jacobi relaxation converges slowly
+ *  - What a bond is not: there is no angular constraint (a chain folds freely: the bends below, gpe_set_bends, hold
+ *    angles); Jacobi relaxation converges slowly
  *    along stiff long chains, which need iterations; a rest length below the sum of the two radii fights the collision
  *    solver, which pushes the pair apart again in the next step.
  *  - The set and its broken flags are step state: they survive adds, removals, edits, kicks, re-sorts, growth,
@@ -677,13 +678,89 @@ gpe_status gpe_get_bonds(gpe_ctx *ctx, gpe_bond *out, uint8_t *broken_out, uint6
 gpe_status gpe_apply_bonds(gpe_ctx *ctx);                          /* one pass now, stream-ordered, no sync */
 gpe_status gpe_get_bonds_info(gpe_ctx *ctx, gpe_bonds_info *info); /* synchronises (reads the device counter) */
 
+/* ---- bend constraints (not in the reference) ----------------------------------------------------------------------
+ * Angles between bonded particles: a rope with stiffness, grass and hair that spring back, a cloth that resists
+ * folding, an articulated shape that holds a rest angle.  A bend names three distinct particles by uid (gpe_enable_uids
+ * must be on): a, the hinge b, and c, and holds the angle from u = a - b to v = c - b at a rest angle, given as
+ * (rest_cos, rest_sin) so that neither side needs libm.  It tells a fold to the left from a fold to the right, and
+ * is stiff to first order at a straight rest pose; a distance bond from a to c is neither.  While a context holds a
+ * set, gpe_step and every iteration of gpe_run run one pass after the step, IN FRONT OF the distance bonds (lengths
+ * keep the last word over angles, walls over both), stream-ordered, on the device (csrc/k_bends.hip):
+ * step -> bends -> bonds -> bodies -> movers -> colliders -> fields -> tracers / monitor.  The per-module calls run no
+ * pass: gpe_apply_bends is their hook.  A context without bends launches and allocates exactly what it does without
+ * this section.
+ *  - One relaxation (csrc/k_bend.h is the one definition).  Every bend is judged from the positions the relaxation
+ *    starts with, in IEEE binary32, one rounding per operation, left to right, no FMA, `/` and sqrtf correctly
+ *    rounded; rc = rest_cos, rs = rest_sin:
+ *      ux = ax-bx; uy = ay-by; vx = cx-bx; vy = cy-by
+ *      lu = ux*ux + uy*uy;  lv = vx*vx + vy*vy
+ *      tx = rc*ux - rs*uy;  ty = rs*ux + rc*uy            (u turned by the rest angle)
+ *      cr = tx*vy - ty*vx;  dt = tx*vx + ty*vy
+ *      den = sqrtf(lu*lv)
+ *      inert this relaxation unless lu > 0, lv > 0, den > 0 and den < +inf   (NaN fails every comparison)
+ *      s = cr / den;  if dt < 0: s = (cr < 0) ? -1 : +1   (more than 90 degrees off: the largest correction)
+ *      inert if s != s
+ *      gax = uy/lu; gay = -ux/lu;  gcx = -vy/lv; gcy = vx/lv;  gbx = -(gax+gcx); gby = -(gay+gcy)
+ *      q = ((gax*gax + gay*gay) + (gcx*gcx + gcy*gcy)) + (gbx*gbx + gby*gby)
+ *      inert unless q > 0 and q < +inf
+ *      m = s * stiffness;  lam = -m / q
+ *      da = (lam*gax, lam*gay);  dc = (lam*gcx, lam*gcy);  db = (-(da.x + dc.x), -(da.y + dc.y))
+ *    This is the position-based-dynamics step on C = sin(deviation) with equal masses: the three corrections sum to
+ *    zero.  An exact fold-back (cr == 0, dt < 0) turns with s = +1.  A bend one of whose uids names no live particle
+ *    is inert: it acts again when the uid reappears (gpe_set_uids).  A particle with at least one acting bend moves to
+ *    p + acc, acc summed from +0.0f over its acting bends in ascending bend index (inert bends are skipped, not added
+ *    as zero; the hinge's share is formed as -(da + dc) where it is added), then K12's clamp with its stored radius:
+ *    clamp(x, r, W - r), clamp(y, r, H - r).  Only pos is written: prev and radius never.  Every other particle keeps
+ *    every bit, unclamped.  Bends do not break.
+ *  - A pass relaxes the set `iterations` times (Jacobi: no relaxation reads what it has written itself), so the
+ *    result depends on the set and the particles alone, never on launch order, storage order or mode.
+ *  - What a bend is not: Jacobi relaxation is weak along long chains (a 32-particle cantilever droops almost as
+ *    without bends); a stiffness above about 0.5 on a chain overshoots, because each interior particle sits in three
+ *    bends; a bend shortens its arms to second order, and the bonds behind it restore them.  There are no breaking
+ *    bends, no motorised rest angles, no per-particle mass, no bends in sharded runs, and bend and bond relaxations
+ *    are not interleaved.
+ *  - The set is step state: it survives adds, removals, edits, kicks, re-sorts, growth, gpe_set_mode, gpe_set_world
+ *    and gpe_set_particles (which renumbers the uids from 0: the bends then name the new particles).  After a call
+ *    that moves, adds or removes particles the next pass looks its uids up again (that synchronises once); every other
+ *    pass only enqueues.
+ *  - gpe_set_bends replaces the set (k == 0 clears it and frees its buffers) and zeroes the counters; it
+ *    synchronises.  -0.0 in rest_cos / rest_sin / stiffness is stored as +0.  The same triple may be listed twice:
+ *    both bends act.  gpe_get_bends delivers the first min(k, capacity) records into out and the number set into *k.
+ *    gpe_apply_bends with no bends or no particles: GPE_OK, nothing done.
+ *  - Errors (the previous set stays untouched): a NULL ctx, NULL bends with k > 0, k > GPE_BENDS_MAX, iterations
+ *    outside 1 .. GPE_BEND_ITER_MAX, a uid that is GPE_UID_ABSENT, two of the three uids equal, a rest_cos or rest_sin
+ *    that is not finite or |rest_cos^2 + rest_sin^2 - 1| > 2^-20 in binary32, a stiffness that is NaN or outside
+ *    [0, 1], nonzero flags or reserved, a uid with more than GPE_BEND_MAX_DEGREE bends, a struct_size below the
+ *    struct's: GPE_ERR_INVALID_ARG.  Uids off: GPE_ERR_STATE.  gpe_set_bends on a sharded context, and
+ *    gpe_enable_uids(ctx, 0), gpe_shard_set_particles, gpe_use_order_keys(ctx, 1) and gpe_set_counts on a context
+ *    that holds bends: GPE_ERR_UNSUPPORTED. */
+#define GPE_BENDS_MAX        4194304u   /* a 1 M-particle sheet has about 2 M bends along rows and columns */
+#define GPE_BEND_MAX_DEGREE  1024u      /* bends per particle, any role: one lane walks them in order */
+#define GPE_BEND_ITER_MAX    32u
+typedef struct gpe_bend {               /* 32 bytes */
+    uint32_t uid_a, uid_b, uid_c;       /* distinct, none GPE_UID_ABSENT; b is the hinge */
+    float rest_cos, rest_sin;           /* finite; |rest_cos^2 + rest_sin^2 - 1| <= 2^-20 in binary32 */
+    float stiffness;                    /* in [0, 1] */
+    uint32_t flags, reserved;           /* both 0 */
+} gpe_bend;
+typedef struct gpe_bends_info {
+    uint32_t struct_size, iterations;  /* in / relaxations per pass                                        */
+    uint64_t k, nodes;                 /* bends set / distinct uids they name                              */
+    uint64_t passes;                   /* passes enqueued since the last gpe_set_bends                     */
+    uint64_t resolves;                 /* times the uids were looked up again since the last gpe_set_bends */
+} gpe_bends_info;                      /* 40 bytes */
+gpe_status gpe_set_bends(gpe_ctx *ctx, const gpe_bend *bends, uint64_t k, uint32_t iterations);
+gpe_status gpe_get_bends(const gpe_ctx *ctx, gpe_bend *out, uint64_t capacity, uint64_t *k);
+gpe_status gpe_apply_bends(gpe_ctx *ctx);                          /* one pass now, stream-ordered, no sync */
+gpe_status gpe_get_bends_info(gpe_ctx *ctx, gpe_bends_info *info);
+
 /* ---- rigid and soft bodies (not in the reference) ------------------------------------------------------------------
  * Groups of particles that keep their shape: a box, a wheel, a brick, a jelly blob.  A body is `count` members (2 ..
  * GPE_BODY_MAX_MEMBERS), each a particle named by uid (gpe_enable_uids must be on) with a rest position (rx, ry) in any
  * frame (only the offsets matter), a stiffness in [0, 1] and a break_distance >= 0 (0: never breaks).  A uid appears
  * at most once in the whole set.  While a context holds a set, gpe_step and every iteration of gpe_run run one shape
  * matching pass (Mueller et al. 2005) after the step, behind the distance bonds and BEFORE the static colliders, on
- * the device (csrc/k_bodies.hip): step -> bonds -> bodies -> movers -> colliders -> fields -> tracers / monitor.  A bond can hang a body
+ * the device (csrc/k_bodies.hip): step -> bends -> bonds -> bodies -> movers -> colliders -> fields -> tracers / monitor.  A bond can hang a body
  * from an anchor; walls keep the last word.  The per-module calls run no pass: gpe_apply_bodies is their hook.  A
  * context without bodies launches and allocates exactly what it does without this section.
  *  - The pass (csrc/k_body.h is the one definition), IEEE binary32, one rounding per operation, left to right, no
@@ -758,7 +835,7 @@ gpe_status gpe_get_bodies_info(gpe_ctx *ctx, gpe_bodies_info *info);  /* synchro
  * is a region (everywhere, a closed disc, a closed box) and a kind (a uniform acceleration, a pull toward a pole, a
  * swirl around a pole, a drag).  While a context holds a set, gpe_step and every iteration of gpe_run run one pass over
  * the particles after the step, BEHIND the static colliders and before the tracers and the monitor, stream-ordered, on
- * the device (csrc/k_fields.hip): step -> bonds -> bodies -> movers -> colliders -> fields -> tracers / monitor.  A field is
+ * the device (csrc/k_fields.hip): step -> bends -> bonds -> bodies -> movers -> colliders -> fields -> tracers / monitor.  A field is
  * judged at the position the step ends with; a tracer or monitor frame sees the new velocity; the velocity acts from
  * the next step on.  The per-module calls (gpe_integrate and the rest) run no pass: gpe_apply_fields is their hook.  A
  * context without fields launches and allocates exactly what it does without this section.
