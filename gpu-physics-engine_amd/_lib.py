@@ -53,6 +53,7 @@ COLLIDERS_MAX = 4096
 BONDS_MAX, BOND_MAX_DEGREE, BOND_ITER_MAX = 4194304, 1024, 32
 BOND_ANCHOR, BOND_BROKEN = 1, 2
 BENDS_MAX, BEND_MAX_DEGREE, BEND_ITER_MAX = 4194304, 1024, 32
+AREAS_MAX, AREA_MAX_MEMBERS, AREA_MEMBERS_MAX, AREA_MAX_DEGREE, AREA_ITER_MAX = 4194304, 4096, 16777216, 64, 32
 BODIES_MAX, BODY_MAX_MEMBERS, BODY_MEMBERS_MAX = 1048576, 4096, 16777216
 BODY_BROKEN = 1
 FIELDS_MAX = 4096
@@ -277,6 +278,20 @@ class GpeBendsInfo(C.Structure):
                 ("passes", C.c_uint64), ("resolves", C.c_uint64)]
 
 
+class GpeArea(C.Structure):
+    """gpe_area: members [first, first + count) of the set's member uids, in order around a closed polygon, keep the
+    signed rest_area.  24 bytes."""
+    _fields_ = [("first", C.c_uint32), ("count", C.c_uint32), ("rest_area", C.c_float), ("stiffness", C.c_float),
+                ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class GpeAreasInfo(C.Structure):
+    """gpe_areas_info: in struct_size; out the relaxations per pass, the loops set, their members and the distinct uids
+    they name, and since the last gpe_set_areas the passes run and the times the uids were looked up.  48 bytes."""
+    _fields_ = [("struct_size", C.c_uint32), ("iterations", C.c_uint32), ("k", C.c_uint64), ("members", C.c_uint64),
+                ("nodes", C.c_uint64), ("passes", C.c_uint64), ("resolves", C.c_uint64)]
+
+
 class GpeBody(C.Structure):
     """gpe_body: members [first, first + count) of the set's member arrays keep their rest shape.  24 bytes."""
     _fields_ = [("first", C.c_uint32), ("count", C.c_uint32), ("stiffness", C.c_float), ("break_distance", C.c_float),
@@ -413,6 +428,12 @@ SYMBOLS = [
     ("gpe_get_bends", _I32, [_VP, C.POINTER(GpeBend), _U64, C.POINTER(_U64)]),
     ("gpe_apply_bends", _I32, [_VP]),
     ("gpe_get_bends_info", _I32, [_VP, C.POINTER(GpeBendsInfo)]),
+    ("gpe_set_areas", _I32, [_VP, C.POINTER(GpeArea), _U64, C.POINTER(C.c_uint32), _U64, C.c_uint32]),
+    ("gpe_get_areas", _I32, [_VP, C.POINTER(GpeArea), _U64, C.POINTER(_U64), C.POINTER(C.c_uint32), _U64, C.POINTER(_U64)]),
+    ("gpe_apply_areas", _I32, [_VP]),
+    ("gpe_get_areas_info", _I32, [_VP, C.POINTER(GpeAreasInfo)]),
+    ("gpe_get_area_values", _I32, [_VP, C.POINTER(C.c_float), _U64, C.POINTER(_U64)]),
+    ("gpe_set_area_targets", _I32, [_VP, _U64, _U64, C.POINTER(C.c_float)]),
     ("gpe_set_bodies", _I32, [_VP, C.POINTER(GpeBody), _U64, C.POINTER(C.c_uint32), C.POINTER(C.c_float), _U64]),
     ("gpe_get_bodies", _I32, [_VP, C.POINTER(GpeBody), C.POINTER(C.c_uint8), _U64, C.POINTER(_U64),
                               C.POINTER(C.c_uint32), C.POINTER(C.c_float), _U64, C.POINTER(_U64)]),

@@ -1,6 +1,6 @@
 // gpe_api.hip -- the extern "C" boundary of include/gpe.h: context, device memory, particle buffers, set / add / remove,
 // uids, step ordering, downloads, profiling.  The queries are in gpe_queries.hip, the checked add, edits and kicks in
-// gpe_edits.hip, the tracers and the monitor in gpe_observe.hip, the static colliders in gpe_colliders.hip, the distance bonds in gpe_bonds.hip, the bend constraints in gpe_bends.hip, the rigid and soft bodies in gpe_bodies.hip, the force fields in gpe_fields.hip, the moving colliders in gpe_movers.hip.  All device work goes to one in-order hipStream per context.
+// gpe_edits.hip, the tracers and the monitor in gpe_observe.hip, the static colliders in gpe_colliders.hip, the distance bonds in gpe_bonds.hip, the bend constraints in gpe_bends.hip, the area constraints in gpe_areas.hip, the rigid and soft bodies in gpe_bodies.hip, the force fields in gpe_fields.hip, the moving colliders in gpe_movers.hip.  All device work goes to one in-order hipStream per context.
 #include <math.h>
 #include <stddef.h>
 #include <stdlib.h>
@@ -316,6 +316,7 @@ gpe_status refuse_step_sets(gpe_ctx *c, const char *who, const char *uid_refusal
     if (has_bonds(c)) return refuse_bonds(c, who);
     if (has_bodies(c)) return refuse_bodies(c, who);
     if (has_bends(c)) return refuse_bends(c, who);
+    if (has_areas(c)) return refuse_areas(c, who);
     if (c->uid.on) return fail(c, GPE_ERR_UNSUPPORTED, std::string(who) + ": " + uid_refusal);
     if (has_colliders(c)) return refuse_colliders(c, who);
     if (has_fields(c)) return refuse_fields(c, who);
@@ -1006,6 +1007,7 @@ gpe_status gpe_destroy(gpe_ctx *c)
     sweep_release(c);
     bonds_release(c);
     bends_release(c);
+    areas_release(c);
     bodies_release(c);
     fields_release(c);
     movers_release(c);
@@ -1177,6 +1179,7 @@ gpe_status gpe_enable_uids(gpe_ctx *c, int32_t enable)
         if (has_bonds(c)) return refuse_bonds(c, "gpe_enable_uids");   // (they name their particles by uid)
         if (has_bodies(c)) return refuse_bodies(c, "gpe_enable_uids"); // (and so do they)
         if (has_bends(c)) return refuse_bends(c, "gpe_enable_uids");
+        if (has_areas(c)) return refuse_areas(c, "gpe_enable_uids");
         GPE_HIP(c, hipSetDevice(c->device));
         GPE_HIP(c, hipStreamSynchronize(c->stream));           // (a re-sort in flight may still read them)
         uid_release(c);
@@ -1470,7 +1473,7 @@ gpe_status gpe_solve_collisions(gpe_ctx *c)
 
 // ---- step ------------------------------------------------------------------------------------------------
 // The passes behind every step of gpe_step / gpe_run, in the one order they have (a test arms them all):
-// bends, then bonds (lengths keep the last word over angles), then bodies (a bond can hang a body from an anchor), then
+// bends, then areas, then bonds (lengths keep the last word over angles and areas), then bodies (a bond can hang a body from an anchor), then
 // the obstacles, which keep the last word over all three --
 // the movers first, the static walls behind them (a piston squeezes particles against a wall, the wall wins) -- then
 // the fields, which write prev only and so are judged where the step and the obstacles left the particle, then the
@@ -1478,6 +1481,7 @@ gpe_status gpe_solve_collisions(gpe_ctx *c)
 static inline gpe_status after_step(gpe_ctx *c, float dt)
 {
     if (has_bends(c)) GPE_TRY(bends_after_step(c));
+    if (has_areas(c)) GPE_TRY(areas_after_step(c));
     if (has_bonds(c)) GPE_TRY(bonds_after_step(c));
     if (has_bodies(c)) GPE_TRY(bodies_after_step(c));
     if (has_movers(c)) GPE_TRY(movers_after_step(c, dt));

@@ -488,6 +488,31 @@ struct BendState {
     uint8_t *state = nullptr;                    // k: 0 acted, 2 inert in this relaxation
 };
 
+// the area constraints (gpe_set_areas; gpe_areas.hip, k_areas.hip, area_table.h).  Step state: gpe_step / gpe_run relax
+// them behind the bends and in front of the bonds
+struct AreaState {
+    std::vector<gpe_area> set;                   // the loops as the host gave them (empty: none, nothing is launched)
+    std::vector<uint32_t> member_uid_host;       // members: what gpe_get_areas gives back
+    uint32_t iterations = 1;
+    uint64_t members = 0;
+    uint64_t nodes = 0;                          // m: the distinct uids the members name
+    bool stale = true;                           // node_slot and member_slot are out of date (uid_slots_stale)
+    uint64_t passes = 0, resolves = 0;           // since the last gpe_set_areas
+    uint32_t class_start[6] = {0, 0, 0, 0, 0, 0};   // order[class_start[q], class_start[q + 1]): the loops of width 4 << q
+    // device side, read by index below the stated count
+    uint4 *rec = nullptr;                        // k: (first, count, rest_area, stiffness), area_table.h AreaRecord
+    uint32_t *order = nullptr;                   // k: loop indices by width class
+    uint32_t *member_node = nullptr;             // members: each member's node index
+    uint32_t *member_slot = nullptr;             // members: node_slot of its node (valid unless stale)
+    uint32_t *node_uid = nullptr;                // m: the nodes' uids, ascending
+    uint32_t *node_slot = nullptr;               // m: each node's storage index, 0xffffffff for none (valid unless stale)
+    uint32_t *row_start = nullptr;               // m + 1
+    uint2 *inc = nullptr;                        // row_start[m] = members: a node's memberships, (member, loop)
+    float2 *corr = nullptr;                      // members: this relaxation's corrections
+    uint8_t *state = nullptr;                    // k: 0 acted, 2 inert in this relaxation
+    float2 *value = nullptr;                     // k: (area, lambda) of the last relaxation, NaNs for an inert loop
+};
+
 // the rigid and soft bodies (gpe_set_bodies; gpe_bodies.hip, k_bodies.hip, body_table.h).  Step state: gpe_step / gpe_run match them
 struct BodyState {
     std::vector<gpe_body> set;                   // the bodies as the host gave them (empty: none, nothing is launched)
@@ -931,6 +956,7 @@ struct gpe_ctx {
     gpe::SweepState sweep;
     gpe::BondState bonds;
     gpe::BendState bends;
+    gpe::AreaState areas;
     gpe::BodyState bodies;
     gpe::FieldState fields;
     gpe::MoverState movers;
@@ -1105,7 +1131,7 @@ gpe_status rows_out(const std::vector<T> &set, T *out, uint64_t capacity, uint64
     return GPE_OK;
 }
 // The storage order or the uids have changed: whatever keeps storage slots by uid looks them up again before its next use
-inline void uid_slots_stale(gpe_ctx *c) { c->tracers.stale = c->bonds.stale = c->bends.stale = c->bodies.stale = true; }
+inline void uid_slots_stale(gpe_ctx *c) { c->tracers.stale = c->bonds.stale = c->bends.stale = c->areas.stale = c->bodies.stale = true; }
 void refresh_cell_size(gpe_ctx *c);
 gpe_status reconfigure(gpe_ctx *c);
 gpe_status uid_map_ready(gpe_ctx *c);
@@ -1155,6 +1181,11 @@ inline bool has_bends(const gpe_ctx *c) { return !c->bends.set.empty(); }
 gpe_status refuse_bends(gpe_ctx *c, const char *who);       // GPE_ERR_UNSUPPORTED: taking the uids from a context that holds bends
 gpe_status bends_after_step(gpe_ctx *c);
 void bends_release(gpe_ctx *c);
+// gpe_areas.hip: the area constraints of a context that holds some
+inline bool has_areas(const gpe_ctx *c) { return !c->areas.set.empty(); }
+gpe_status refuse_areas(gpe_ctx *c, const char *who);       // GPE_ERR_UNSUPPORTED: taking the uids from a context that holds areas
+gpe_status areas_after_step(gpe_ctx *c);
+void areas_release(gpe_ctx *c);
 // gpe_bodies.hip: the rigid and soft bodies of a context that holds some
 inline bool has_bodies(const gpe_ctx *c) { return !c->bodies.set.empty(); }
 gpe_status refuse_bodies(gpe_ctx *c, const char *who);      // GPE_ERR_UNSUPPORTED: taking the uids from a context that holds bodies
@@ -1174,7 +1205,7 @@ gpe_status movers_check_dt(gpe_ctx *c, float dt, const char *who);  // GPE_ERR_I
 gpe_status movers_after_step(gpe_ctx *c, float dt);
 void movers_release(gpe_ctx *c);
 void mover_sweep_release(gpe_ctx *c);                       // gpe_destroy: the mode's counters and records
-// The sharding entry points refuse a context that holds step sets: bonds, bodies and bends (they name their particles by uid:
+// The sharding entry points refuse a context that holds step sets: bonds, bodies, bends and areas (they name their particles by uid:
 // the more telling refusal), then the call's own uid refusal when uids are on, then colliders, fields and movers
 gpe_status refuse_step_sets(gpe_ctx *c, const char *who, const char *uid_refusal);
 
@@ -1407,6 +1438,11 @@ gpe_status launch_bonds_pass(gpe_ctx *c, float2 *pos, const float *radius, uint6
 // bend constraints (k_bends.hip): `iterations` relaxations of the k bends of B over pos[0, n) in place, two launches each
 gpe_status launch_bends_pass(gpe_ctx *c, float2 *pos, const float *radius, uint64_t n, const BendState &B, uint32_t k,
                              uint32_t m, uint32_t iterations);
+// area constraints (k_areas.hip): `iterations` relaxations of the k loops of A over pos[0, n) in place: one launch per
+// non-empty width class, then one over the m nodes; launch_areas_expand: member_slot[i] = node_slot[member_node[i]]
+gpe_status launch_areas_pass(gpe_ctx *c, float2 *pos, const float *radius, uint64_t n, const AreaState &A, uint32_t k,
+                             uint32_t m, uint32_t iterations);
+gpe_status launch_areas_expand(gpe_ctx *c, const AreaState &A);
 // rigid and soft bodies (k_bodies.hip): one shape matching pass of the k bodies of B over pos[0, n) in place, one launch
 // per non-empty width class
 gpe_status launch_bodies_pass(gpe_ctx *c, float2 *pos, const float *radius, uint64_t n, const BodyState &B, uint32_t k);

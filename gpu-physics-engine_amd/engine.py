@@ -96,6 +96,11 @@ def bends_from_angles(uid_a, uid_b, uid_c, angle, stiffness=1.0):
     return rows
 
 
+# set_areas / areas: the rows of gpe_area (24 bytes each, the struct's layout)
+AREA_DTYPE = np.dtype([(name, np.uint32 if ctype is C.c_uint32 else np.float32) for name, ctype in L.GpeArea._fields_])
+assert AREA_DTYPE.itemsize == C.sizeof(L.GpeArea)
+
+
 # set_movers / movers: the rows of gpe_mover (56 bytes each); mover_poses: the rows of gpe_mover_pose (24 bytes each)
 MOVER_DTYPE = np.dtype([(name, np.uint32 if ctype is C.c_uint32 else np.float32) for name, ctype in L.GpeMover._fields_])
 MOVER_POSE_DTYPE = np.dtype([(name, np.float32) for name, _ in L.GpeMoverPose._fields_])
@@ -819,6 +824,56 @@ class ParticleSystem:
         info = L.GpeBendsInfo(struct_size=C.sizeof(L.GpeBendsInfo))
         self.ctx.call("gpe_get_bends_info", C.byref(info))
         return {name: getattr(info, name) for name, _ in L.GpeBendsInfo._fields_ if name != "struct_size"}
+
+    # Area constraints (not in the reference; include/gpe.h): closed loops of particles, named by uid in order around a
+    # polygon, that keep a signed rest area; relaxed on the device after every update() / step of run(), behind the bends
+    # and in front of the bonds.  Step state: save() keeps them.
+    def set_areas(self, areas, member_uid, iterations=1):
+        """gpe_set_areas: replace the set by the rows of an AREA_DTYPE array (State.areas_from_loops builds them) over
+        the members' uids u32[m], relaxed `iterations` times per pass; no rows clear it.  The counters start anew."""
+        rows = np.ascontiguousarray(areas, AREA_DTYPE).reshape(-1)
+        uid = np.ascontiguousarray(member_uid, np.uint32).reshape(-1)
+        k = len(rows)
+        self.ctx.call("gpe_set_areas", rows.ctypes.data_as(C.POINTER(L.GpeArea)) if k else None, k,
+                      uid.ctypes.data_as(C.POINTER(C.c_uint32)) if k else None, len(uid) if k else 0, int(iterations))
+
+    def areas(self):
+        """gpe_get_areas -> (records AREA_DTYPE[k], member_uid u32[m])."""
+        k, m = C.c_uint64(), C.c_uint64()
+        self.ctx.call("gpe_get_areas", None, 0, C.byref(k), None, 0, C.byref(m))
+        rows = np.zeros(max(k.value, 1), AREA_DTYPE)
+        uid = np.zeros(max(m.value, 1), np.uint32)
+        self.ctx.call("gpe_get_areas", rows.ctypes.data_as(C.POINTER(L.GpeArea)), k.value, C.byref(k),
+                      uid.ctypes.data_as(C.POINTER(C.c_uint32)), m.value, C.byref(m))
+        return rows[:k.value], uid[:m.value]
+
+    def clear_areas(self):
+        """gpe_set_areas with k = 0."""
+        self.ctx.call("gpe_set_areas", None, 0, None, 0, 1)
+
+    def apply_areas(self):
+        """gpe_apply_areas: one pass now (the hook of a host that steps module by module).  Does not synchronise."""
+        self.ctx.call("gpe_apply_areas")
+
+    def areas_info(self):
+        """gpe_get_areas_info -> dict(iterations, k, members, nodes, passes, resolves)."""
+        info = L.GpeAreasInfo(struct_size=C.sizeof(L.GpeAreasInfo))
+        self.ctx.call("gpe_get_areas_info", C.byref(info))
+        return {name: getattr(info, name) for name, _ in L.GpeAreasInfo._fields_ if name != "struct_size"}
+
+    def area_values(self):
+        """gpe_get_area_values -> f32[k, 2]: (area, lambda) of every loop as of the last relaxation, NaNs for a loop
+        that was inert in it and before the first pass.  Blocks like a download."""
+        k = C.c_uint64()
+        self.ctx.call("gpe_get_area_values", None, 0, C.byref(k))
+        out = np.zeros((max(k.value, 1), 2), np.float32)
+        self.ctx.call("gpe_get_area_values", out.ctypes.data_as(C.POINTER(C.c_float)), k.value, C.byref(k))
+        return out[:k.value]
+
+    def set_area_targets(self, first, rest_area):
+        """gpe_set_area_targets: new rest areas for loops first .. first + len(rest_area) - 1, in place (the pump)."""
+        t = np.ascontiguousarray(rest_area, np.float32).reshape(-1)
+        self.ctx.call("gpe_set_area_targets", int(first), len(t), t.ctypes.data_as(C.POINTER(C.c_float)))
 
     # Rigid and soft bodies (not in the reference; include/gpe.h): groups of particles, named by uid, that keep their rest
     # shape: one shape matching pass on the device after every update() / step of run(), behind the bonds and before the
@@ -1589,6 +1644,62 @@ class State:
         rows["stiffness"] = stiffness
         return rows
 
+    def set_areas(self, areas, member_uid, iterations=1):
+        """ParticleSystem.set_areas: area constraints (rows of AREA_DTYPE over member uids) relaxed after every step,
+        behind the bends and in front of the bonds."""
+        self.particles.set_areas(areas, member_uid, iterations)
+
+    def areas(self):
+        """ParticleSystem.areas -> (records AREA_DTYPE[k], member_uid u32[m])."""
+        return self.particles.areas()
+
+    def clear_areas(self):
+        """ParticleSystem.clear_areas."""
+        self.particles.clear_areas()
+
+    def apply_areas(self):
+        """ParticleSystem.apply_areas: one pass now."""
+        self.particles.apply_areas()
+
+    def areas_info(self):
+        """ParticleSystem.areas_info -> dict(iterations, k, members, nodes, passes, resolves)."""
+        return self.particles.areas_info()
+
+    def area_values(self):
+        """ParticleSystem.area_values -> f32[k, 2]: (area, lambda) per loop as of the last relaxation."""
+        return self.particles.area_values()
+
+    def set_area_targets(self, first, rest_area):
+        """ParticleSystem.set_area_targets: new rest areas for loops first .. first + len(rest_area) - 1."""
+        self.particles.set_area_targets(first, rest_area)
+
+    def areas_from_loops(self, loops, stiffness=1.0, pressure=1.0):
+        """(rows of AREA_DTYPE, member_uid u32[m]) for set_areas: one loop per sequence of uids, in order around its
+        polygon; the rest area is the signed area the particles enclose now (the shoelace sum in float64 from the
+        downloaded positions, taken from member 0) times `pressure`, rounded once to float32.  stiffness and pressure:
+        scalars, or one value per loop.  Every uid must name a live particle."""
+        groups = [np.asarray(g, np.uint32).reshape(-1) for g in loops]
+        member_uid = np.concatenate(groups) if groups else np.zeros(0, np.uint32)
+        uids = self.uids()
+        order = np.argsort(uids, kind="stable")
+        at = np.searchsorted(uids[order], member_uid)
+        if len(member_uid) and ((at >= len(uids)).any() or (uids[order[np.minimum(at, len(uids) - 1)]] != member_uid).any()):
+            raise ValueError("areas_from_loops: a uid names no particle")
+        p = self.positions().astype(np.float64)
+        rows = np.zeros(len(groups), AREA_DTYPE)
+        first = 0
+        area = np.zeros(len(groups), np.float64)
+        for j, g in enumerate(groups):
+            q = p[order[at[first:first + len(g)]]]
+            q = q - q[:1]
+            nx, ny = np.roll(q[:, 0], -1), np.roll(q[:, 1], -1)
+            area[j] = 0.5 * float((q[:, 0] * ny - nx * q[:, 1]).sum())
+            rows["first"][j], rows["count"][j] = first, len(g)
+            first += len(g)
+        rows["rest_area"] = area * np.broadcast_to(np.asarray(pressure, np.float64), area.shape)
+        rows["stiffness"] = stiffness
+        return rows, member_uid
+
     def set_bodies(self, bodies, member_uid, member_rest):
         """ParticleSystem.set_bodies: groups of particles (rows of BODY_DTYPE) matched to their rest shape after every
         step, behind the bonds and before the colliders."""
@@ -1739,6 +1850,7 @@ class State:
         for the same reason.  Static colliders are step state: a set that is present is written (`colliders`), and so
         are distance bonds with their relaxation count and broken flags (`bonds`, `bond_iterations`, `bonds_broken`) and
         bend constraints with their relaxation count (`bends`, `bend_iterations`) and
+        area constraints with their members and relaxation count (`areas`, `area_member_uid`, `area_iterations`) and
         bodies with their members and broken flags (`bodies`, `bodies_broken`, `body_member_uid`, `body_member_rest`) and
         force fields (`fields`) and moving colliders with their poses (`movers`, `mover_poses`), and the surfaces of
         the two sets where present (`collider_surfaces`, `mover_surfaces`), and the static colliders' sweep where it is
@@ -1774,6 +1886,10 @@ class State:
             bends = self.bends()                                       # (they name particles by uid: none without uids)
             if len(bends):
                 extra.update(bends=bends, bend_iterations=np.array([self.bends_info()["iterations"]], np.uint32))
+            areas, area_member_uid = self.areas()
+            if len(areas):
+                extra.update(areas=areas, area_member_uid=area_member_uid,
+                             area_iterations=np.array([self.areas_info()["iterations"]], np.uint32))
         pressed, at = self.ctx.mouse()
         if pressed:
             extra.update(mouse=np.array(at, np.float32))
@@ -1817,6 +1933,8 @@ class State:
                 st.set_bonds(rows, int(d["bond_iterations"][0]))
             if "bends" in d.files:                                 # (after the uids they name)
                 st.set_bends(d["bends"].astype(BEND_DTYPE), int(d["bend_iterations"][0]))
+            if "areas" in d.files:                                 # (after the uids they name)
+                st.set_areas(d["areas"].astype(AREA_DTYPE), d["area_member_uid"], int(d["area_iterations"][0]))
             if "bodies" in d.files:                                # (after the uids and the bonds; a broken body starts broken)
                 rows = d["bodies"].astype(BODY_DTYPE)
                 rows["flags"] |= np.where(d["bodies_broken"], L.BODY_BROKEN, 0).astype(np.uint32)

@@ -425,6 +425,44 @@ class ParticleSystem {
         ctx_->call(gpe_get_bends_info(ctx_->raw(), &info));
         return info;
     }
+    // not in the reference: area constraints (include/gpe.h): closed loops of particles named by uid, in order around a
+    // polygon, that keep a signed rest area; relaxed on the device after every step of gpe_step / gpe_run, behind the
+    // bends and in front of the bonds.  Step state: a snapshot keeps the set, its members and its relaxation count.
+    void set_areas(const std::vector<gpe_area> &areas, const std::vector<uint32_t> &member_uid, uint32_t iterations = 1)
+    {
+        ctx_->call(gpe_set_areas(ctx_->raw(), areas.empty() ? nullptr : areas.data(), areas.size(),
+                                 member_uid.empty() ? nullptr : member_uid.data(), member_uid.size(), iterations));
+    }
+    std::pair<std::vector<gpe_area>, std::vector<uint32_t>> areas() const
+    {
+        uint64_t k = 0, m = 0;
+        ctx_->call(gpe_get_areas(ctx_->raw(), nullptr, 0, &k, nullptr, 0, &m));
+        std::vector<gpe_area> out(k);
+        std::vector<uint32_t> uid(m);
+        ctx_->call(gpe_get_areas(ctx_->raw(), k ? out.data() : nullptr, k, &k, m ? uid.data() : nullptr, m, &m));
+        return {out, uid};
+    }
+    void clear_areas() { ctx_->call(gpe_set_areas(ctx_->raw(), nullptr, 0, nullptr, 0, 1)); }
+    void apply_areas() { ctx_->call(gpe_apply_areas(ctx_->raw())); }   // one pass now: behind apply_bends, before apply_bonds
+    gpe_areas_info areas_info() const
+    {
+        gpe_areas_info info{};
+        info.struct_size = sizeof(info);
+        ctx_->call(gpe_get_areas_info(ctx_->raw(), &info));
+        return info;
+    }
+    std::vector<float> area_values() const                              // (area, lambda) per loop; blocks like a download
+    {
+        uint64_t k = 0;
+        ctx_->call(gpe_get_area_values(ctx_->raw(), nullptr, 0, &k));
+        std::vector<float> out(2 * k);
+        ctx_->call(gpe_get_area_values(ctx_->raw(), k ? out.data() : nullptr, k, &k));
+        return out;
+    }
+    void set_area_targets(uint64_t first, const std::vector<float> &rest_area)   // the pump
+    {
+        ctx_->call(gpe_set_area_targets(ctx_->raw(), first, rest_area.size(), rest_area.empty() ? nullptr : rest_area.data()));
+    }
     // not in the reference: rigid and soft bodies (include/gpe.h): groups of particles named by uid that keep their rest
     // shape, matched on the device after every step of gpe_step / gpe_run, behind the bonds and before the static
     // colliders.  Step state: a snapshot keeps the set, its members and the broken flags (a broken body is given back

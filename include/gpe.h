@@ -443,7 +443,7 @@ gpe_status gpe_get_sweep_info(gpe_ctx *ctx, gpe_sweep_info *info);         /* sy
  * full turns.  The movers are a second set beside the static colliders, independent of them.  While a context holds a
  * set, gpe_step and every iteration of gpe_run advance every mover by dt ON THE DEVICE, rebuild the movers' lookup grid
  * there and run one pass over the particles, stream-ordered, no host round trip (csrc/k_movers.hip): a memset and two
- * launches per step.  Order: step -> bends -> bonds -> bodies -> movers -> colliders -> fields -> tracers / monitor: the static
+ * launches per step.  Order: step -> bends -> areas -> bonds -> bodies -> movers -> colliders -> fields -> tracers / monitor: the static
  * walls keep the last word over a piston that squeezes particles against them.  The per-module calls run no pass:
  * gpe_apply_movers(dt) is their hook.  A context without movers launches and allocates exactly what it does without
  * this section.
@@ -614,7 +614,7 @@ gpe_status gpe_get_surfaces(const gpe_ctx *ctx, uint32_t target, gpe_surface *ou
  * particles, named by uid (gpe_enable_uids must be on), at a rest length; an anchor bond (GPE_BOND_ANCHOR) holds one
  * particle to a fixed point.  While a context holds a set, gpe_step and every iteration of gpe_run run one pass after
  * the step, BEFORE the static colliders (walls keep the last word) and the tracers and the monitor, stream-ordered, on
- * the device (csrc/k_bonds.hip): step -> bends -> bonds -> bodies -> movers -> colliders -> fields -> tracers / monitor.  The per-module calls run no pass:
+ * the device (csrc/k_bonds.hip): step -> bends -> areas -> bonds -> bodies -> movers -> colliders -> fields -> tracers / monitor.  The per-module calls run no pass:
  * gpe_apply_bonds is their hook.  A context without bonds launches and allocates exactly what it does without this
  * section.
  *  - One relaxation (csrc/k_bond.h is the one definition).  Every bond is judged from the positions the relaxation
@@ -686,7 +686,8 @@ gpe_status gpe_get_bonds_info(gpe_ctx *ctx, gpe_bonds_info *info); /* synchronis
  * is stiff to first order at a straight rest pose; a distance bond from a to c is neither.  While a context holds a
  * set, gpe_step and every iteration of gpe_run run one pass after the step, IN FRONT OF the distance bonds (lengths
  * keep the last word over angles, walls over both), stream-ordered, on the device (csrc/k_bends.hip):
- * step -> bends -> bonds -> bodies -> movers -> colliders -> fields -> tracers / monitor.  The per-module calls run no
+ * step -> bends -> bonds -> bodies -> movers -> colliders -> fields -> tracers / monitor (area constraints, where held,
+ * run between the bends and the bonds: step -> bends -> areas -> bonds).  The per-module calls run no
  * pass: gpe_apply_bends is their hook.  A context without bends launches and allocates exactly what it does without
  * this section.
  *  - One relaxation (csrc/k_bend.h is the one definition).  Every bend is judged from the positions the relaxation
@@ -754,13 +755,93 @@ gpe_status gpe_get_bends(const gpe_ctx *ctx, gpe_bend *out, uint64_t capacity, u
 gpe_status gpe_apply_bends(gpe_ctx *ctx);                          /* one pass now, stream-ordered, no sync */
 gpe_status gpe_get_bends_info(gpe_ctx *ctx, gpe_bends_info *info);
 
+/* ---- area constraints (not in the reference) -----------------------------------------------------------------------
+ * Closed loops of particles that keep their area: a balloon, a tyre, a water drop, a jelly cell that squashes under
+ * load and recovers, a foam of cells that share walls, an inflatable that is pumped up while the run goes on.  A loop
+ * is `count` members (3 .. GPE_AREA_MAX_MEMBERS), each a particle named by uid (gpe_enable_uids must be on), in order
+ * around a closed polygon, with a signed rest_area (positive when the members turn from +x towards +y) and a stiffness
+ * in [0, 1].  Inside one loop a uid appears once; a uid may be a member of up to GPE_AREA_MAX_DEGREE loops (shared
+ * cell walls, a two-chamber balloon).  While a context holds a set, gpe_step and every iteration of gpe_run run one
+ * pass after the step, behind the bends and IN FRONT OF the distance bonds (lengths keep the last word over areas as
+ * over angles, walls over all three), stream-ordered, on the device (csrc/k_areas.hip):
+ * step -> bends -> areas -> bonds -> bodies -> movers -> colliders -> fields -> tracers / monitor.  The per-module
+ * calls run no pass: gpe_apply_areas is their hook.  A context without areas launches and allocates exactly what it
+ * does without this section.
+ *  - One relaxation (csrc/k_area.h is the one definition).  Every loop is judged from the positions the relaxation
+ *    starts with, in IEEE binary32, one rounding per operation, left to right, no FMA, `/` correctly rounded.  For
+ *    member j let n = (j + 1) % count and m = (j + count - 1) % count:
+ *      q_j = p_j - p_0                                     (componentwise: member 0 is the origin)
+ *      t_j = q_j.x * q_n.y - q_n.x * q_j.y;   A2 = S(t);   area = 0.5f * A2;   C = area - rest_area
+ *      g_j = (0.5f * (q_n.y - q_m.y), 0.5f * (q_m.x - q_n.x));   D = S(g_j.x * g_j.x + g_j.y * g_j.y)
+ *      inert this relaxation unless 0 < D < +inf and C is finite   (NaN fails every comparison)
+ *      s = C * stiffness;   lambda = -(s / D);   corr_j = (lambda * g_j.x, lambda * g_j.y)
+ *    S is the canonical sum of the bodies (csrc/k_body.h): with G = the smallest power of two >= count, at most 64,
+ *    lane l of G adds v_l, v_(l+G), ... from +0.0f, then the halving tree partial[l] += partial[l + off], off = G/2
+ *    .. 1.  Its order depends on count alone.  A loop with a member whose uid names no live particle is inert: it is
+ *    not broken and acts again when the uid reappears (gpe_set_uids).  A particle with at least one acting loop moves
+ *    to p + acc, acc summed from +0.0f over its memberships of acting loops in ascending member index (inert loops
+ *    are skipped, not added as zero), then K12's clamp with its stored radius: clamp(x, r, W - r), clamp(y, r, H - r).
+ *    Only pos is written: prev and radius never.  Every other particle keeps every bit, unclamped.  Loops do not
+ *    break: a balloon tears through its bonds' max_length.
+ *  - A pass relaxes the set `iterations` times (Jacobi: no relaxation reads what it has written itself), so the
+ *    result depends on the set and the particles alone, never on launch order, storage order or mode.
+ *  - What an area is not: it is Jacobi, so a stiffness above 1 / (loops per particle) overshoots; a rest_area whose
+ *    sign differs from the current area drives the loop through a fold; there is no per-member mass, no breaking, no
+ *    areas in sharded runs, and area and bond relaxations are not interleaved.
+ *  - The set is step state: it survives adds, removals, edits, kicks, re-sorts, growth, gpe_set_mode, gpe_set_world
+ *    and gpe_set_particles (which renumbers the uids from 0: the loops then name the new particles).  After a call
+ *    that moves, adds or removes particles the next pass looks its uids up again (that synchronises once); every other
+ *    pass only enqueues.
+ *  - gpe_set_areas replaces the set (k == 0 clears it and frees its buffers) and zeroes the counters; it synchronises.
+ *    areas[j] owns member_uid[first .. first + count); the ranges tile [0, members) in any order.  -0.0 in rest_area /
+ *    stiffness is stored as +0.  gpe_get_areas delivers the first min(k, capacity) records into out, the first
+ *    min(members, member_capacity) uids into member_uid_out, and the numbers set into *k and *members.
+ *    gpe_apply_areas with no areas or no particles: GPE_OK, nothing done.  gpe_get_area_values delivers (area, lambda)
+ *    per loop as of the last relaxation run, two NaNs for a loop that was inert in it or has not run yet; it
+ *    synchronises.  gpe_set_area_targets replaces the rest areas of loops first .. first + k - 1 in place (the pump):
+ *    it may synchronise, allocates nothing, and keeps the looked-up slots and every counter; gpe_get_areas delivers
+ *    the new values.
+ *  - Errors (the previous set stays untouched): a NULL ctx, NULL areas or member_uid with k > 0, k > GPE_AREAS_MAX,
+ *    members > GPE_AREA_MEMBERS_MAX, a count outside 3 .. GPE_AREA_MAX_MEMBERS, ranges that overlap, leave members
+ *    unused or run past `members`, a uid that is GPE_UID_ABSENT, a uid twice in one loop, a uid in more than
+ *    GPE_AREA_MAX_DEGREE loops, a rest_area that is not finite, a stiffness that is NaN or outside [0, 1], iterations
+ *    outside 1 .. GPE_AREA_ITER_MAX, nonzero flags or reserved, a struct_size below the struct's, a target range past
+ *    the set: GPE_ERR_INVALID_ARG.  Uids off: GPE_ERR_STATE.  gpe_set_areas on a sharded context, and
+ *    gpe_enable_uids(ctx, 0), gpe_shard_set_particles, gpe_use_order_keys(ctx, 1) and gpe_set_counts on a context
+ *    that holds areas: GPE_ERR_UNSUPPORTED. */
+#define GPE_AREAS_MAX         4194304u  /* loops in a set */
+#define GPE_AREA_MAX_MEMBERS  4096u     /* members of one loop: 64 rounds of one wave */
+#define GPE_AREA_MEMBERS_MAX  16777216u /* members of all loops together */
+#define GPE_AREA_MAX_DEGREE   64u       /* loops per uid: one lane walks them in order */
+#define GPE_AREA_ITER_MAX     32u
+typedef struct gpe_area {               /* 24 bytes */
+    uint32_t first, count;              /* members [first, first + count) of member_uid, in order around the polygon */
+    float rest_area;                    /* finite, signed */
+    float stiffness;                    /* in [0, 1] */
+    uint32_t flags, reserved;           /* both 0 */
+} gpe_area;
+typedef struct gpe_areas_info {
+    uint32_t struct_size, iterations;  /* in / relaxations per pass                                        */
+    uint64_t k, members, nodes;        /* loops set / members of all loops / distinct uids they name       */
+    uint64_t passes;                   /* passes enqueued since the last gpe_set_areas                     */
+    uint64_t resolves;                 /* times the uids were looked up again since the last gpe_set_areas */
+} gpe_areas_info;                      /* 48 bytes */
+gpe_status gpe_set_areas(gpe_ctx *ctx, const gpe_area *areas, uint64_t k, const uint32_t *member_uid, uint64_t members,
+                         uint32_t iterations);
+gpe_status gpe_get_areas(const gpe_ctx *ctx, gpe_area *out, uint64_t capacity, uint64_t *k, uint32_t *member_uid_out,
+                         uint64_t member_capacity, uint64_t *members);
+gpe_status gpe_apply_areas(gpe_ctx *ctx);                          /* one pass now, stream-ordered, no sync */
+gpe_status gpe_get_areas_info(gpe_ctx *ctx, gpe_areas_info *info);
+gpe_status gpe_get_area_values(gpe_ctx *ctx, float *area_lambda, uint64_t capacity, uint64_t *k);   /* synchronises */
+gpe_status gpe_set_area_targets(gpe_ctx *ctx, uint64_t first, uint64_t k, const float *rest_area);
+
 /* ---- rigid and soft bodies (not in the reference) ------------------------------------------------------------------
  * Groups of particles that keep their shape: a box, a wheel, a brick, a jelly blob.  A body is `count` members (2 ..
  * GPE_BODY_MAX_MEMBERS), each a particle named by uid (gpe_enable_uids must be on) with a rest position (rx, ry) in any
  * frame (only the offsets matter), a stiffness in [0, 1] and a break_distance >= 0 (0: never breaks).  A uid appears
  * at most once in the whole set.  While a context holds a set, gpe_step and every iteration of gpe_run run one shape
  * matching pass (Mueller et al. 2005) after the step, behind the distance bonds and BEFORE the static colliders, on
- * the device (csrc/k_bodies.hip): step -> bends -> bonds -> bodies -> movers -> colliders -> fields -> tracers / monitor.  A bond can hang a body
+ * the device (csrc/k_bodies.hip): step -> bends -> areas -> bonds -> bodies -> movers -> colliders -> fields -> tracers / monitor.  A bond can hang a body
  * from an anchor; walls keep the last word.  The per-module calls run no pass: gpe_apply_bodies is their hook.  A
  * context without bodies launches and allocates exactly what it does without this section.
  *  - The pass (csrc/k_body.h is the one definition), IEEE binary32, one rounding per operation, left to right, no
@@ -835,7 +916,7 @@ gpe_status gpe_get_bodies_info(gpe_ctx *ctx, gpe_bodies_info *info);  /* synchro
  * is a region (everywhere, a closed disc, a closed box) and a kind (a uniform acceleration, a pull toward a pole, a
  * swirl around a pole, a drag).  While a context holds a set, gpe_step and every iteration of gpe_run run one pass over
  * the particles after the step, BEHIND the static colliders and before the tracers and the monitor, stream-ordered, on
- * the device (csrc/k_fields.hip): step -> bends -> bonds -> bodies -> movers -> colliders -> fields -> tracers / monitor.  A field is
+ * the device (csrc/k_fields.hip): step -> bends -> areas -> bonds -> bodies -> movers -> colliders -> fields -> tracers / monitor.  A field is
  * judged at the position the step ends with; a tracer or monitor frame sees the new velocity; the velocity acts from
  * the next step on.  The per-module calls (gpe_integrate and the rest) run no pass: gpe_apply_fields is their hook.  A
  * context without fields launches and allocates exactly what it does without this section.
