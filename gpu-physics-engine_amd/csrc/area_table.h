@@ -8,7 +8,8 @@
 //   - nodes: the distinct uids the members name, ascending (a uid may be a member of several loops);
 //   - per member its node index;
 //   - a CSR of incidences per node, in ascending member index: entry = (member index, loop index), so the node phase
-//     finds the member's correction and its loop's state byte without a search.
+//     finds the member's correction and its loop's state byte without a search.  The nodes and the rows are
+//     uid_nodes.h's.
 // The loop phase serves 64 / G loops of class G per wave, and a node adds its shares in the order of its row, so which
 // lane adds what, and in which order, is a function of the set alone.
 #pragma once
@@ -22,6 +23,7 @@
 
 #include "../../include/gpe.h"
 #include "k_area.h"
+#include "uid_nodes.h"
 
 namespace gpe {
 
@@ -127,8 +129,8 @@ inline void area_table_build(const gpe_area *areas, uint64_t k, const uint32_t *
         AreaRecord &r = t->rec[j];
         r.first = q.first;
         r.count = q.count;
-        r.rest_area = q.rest_area == 0.0f ? 0.0f : q.rest_area;         // -0.0 -> +0
-        r.stiffness = q.stiffness == 0.0f ? 0.0f : q.stiffness;
+        r.rest_area = plus_zero(q.rest_area);
+        r.stiffness = plus_zero(q.stiffness);
         per_class[area_class(q.count)] += 1;
     }
     for (uint32_t q = 0; q < kAreaClasses; ++q) t->class_start[q + 1] = t->class_start[q] + per_class[q];
@@ -136,29 +138,18 @@ inline void area_table_build(const gpe_area *areas, uint64_t k, const uint32_t *
     for (uint32_t q = 0; q < kAreaClasses; ++q) at[q] = t->class_start[q];
     for (uint64_t j = 0; j < k; ++j) t->order[at[area_class(areas[j].count)]++] = (uint32_t)j;   // ascending j per class
 
-    std::vector<uint32_t> &nodes = t->nodes;
-    nodes.assign(member_uid, member_uid + members);
-    std::sort(nodes.begin(), nodes.end());
-    nodes.erase(std::unique(nodes.begin(), nodes.end()), nodes.end());
-    const size_t m = nodes.size();
-    t->member_node.resize(members);
-    t->row_start.assign(m + 1, 0);
-    for (uint64_t i = 0; i < members; ++i) {
-        const uint32_t v = (uint32_t)(std::lower_bound(nodes.begin(), nodes.end(), member_uid[i]) - nodes.begin());
-        t->member_node[i] = v;
-        t->row_start[v + 1] += 1;
-    }
-    for (size_t v = 0; v < m; ++v) {
-        t->max_degree = std::max(t->max_degree, t->row_start[v + 1]);
-        t->row_start[v + 1] += t->row_start[v];
-    }
-    std::vector<uint32_t> member_loop(members);
-    for (uint64_t j = 0; j < k; ++j)
-        for (uint32_t i = 0; i < areas[j].count; ++i) member_loop[(uint64_t)areas[j].first + i] = (uint32_t)j;
+    UidNodes u;                                                         // the member array as it stands
+    uid_nodes_build(member_uid, members, &u);
+    t->nodes = std::move(u.nodes);
+    t->member_node = std::move(u.node_of);
+    t->row_start = std::move(u.row_start);
+    t->max_degree = u.max_degree;
     t->inc.resize(members);
-    std::vector<uint32_t> fill(t->row_start.begin(), t->row_start.end() - 1);
-    for (uint64_t i = 0; i < members; ++i)                              // ascending i: every row ends up in member order
-        t->inc[fill[t->member_node[i]]++] = AreaIncidence{(uint32_t)i, member_loop[i]};
+    for (uint64_t j = 0; j < k; ++j)
+        for (uint32_t i = 0; i < areas[j].count; ++i) {
+            const uint32_t member = areas[j].first + i;
+            t->inc[u.at[member]] = AreaIncidence{member, (uint32_t)j};
+        }
 }
 
 }  // namespace gpe

@@ -5,7 +5,8 @@
 //   - nodes: the distinct uids the bends name, ascending (m <= 3 k);
 //   - per bend its three particles as node indices, with the rest angle and the stiffness (-0.0 stored as +0);
 //   - a CSR of incidences per node, in ascending bend index: entry = bend << 2 | role (0: the node is the bend's a,
-//     1: its hinge b, 2: its c).  A bend listed twice appears twice, in all three rows.
+//     1: its hinge b, 2: its c).  A bend listed twice appears twice, in all three rows.  The nodes and the rows are
+//     uid_nodes.h's.
 // What the pass adds up per particle, and in which order, is therefore a function of the set alone.
 #pragma once
 
@@ -17,6 +18,7 @@
 #include <vector>
 
 #include "../../include/gpe.h"
+#include "uid_nodes.h"
 
 namespace gpe {
 
@@ -65,47 +67,34 @@ inline const char *bend_set_problem(const gpe_bend *bends, uint64_t k, uint32_t 
 inline bool bend_graph_build(const gpe_bend *bends, uint64_t k, BendGraph *g)
 {
     *g = BendGraph();
-    std::vector<uint32_t> &nodes = g->nodes;
-    nodes.reserve(3 * k);
+    std::vector<uint32_t> uids;                                         // a, b, c per bend
+    uids.reserve(3 * k);
     for (uint64_t j = 0; j < k; ++j) {
-        nodes.push_back(bends[j].uid_a);
-        nodes.push_back(bends[j].uid_b);
-        nodes.push_back(bends[j].uid_c);
+        uids.push_back(bends[j].uid_a);
+        uids.push_back(bends[j].uid_b);
+        uids.push_back(bends[j].uid_c);
     }
-    std::sort(nodes.begin(), nodes.end());
-    nodes.erase(std::unique(nodes.begin(), nodes.end()), nodes.end());
-    const size_t m = nodes.size();
-    auto node_of = [&nodes](uint32_t uid) {
-        return (uint32_t)(std::lower_bound(nodes.begin(), nodes.end(), uid) - nodes.begin());
-    };
+    UidNodes u;
+    uid_nodes_build(uids.data(), uids.size(), &u);
+    g->nodes = std::move(u.nodes);
+    g->row_start = std::move(u.row_start);
+    g->max_degree = u.max_degree;
+    if (g->max_degree > GPE_BEND_MAX_DEGREE) return false;
     g->rec.resize(k);
-    g->row_start.assign(m + 1, 0);
+    g->inc.resize(3 * k);
     for (uint64_t j = 0; j < k; ++j) {
         const gpe_bend &q = bends[j];
         BendRecord &r = g->rec[j];
-        r.a = node_of(q.uid_a);
-        r.b = node_of(q.uid_b);
-        r.c = node_of(q.uid_c);
-        r.rc = q.rest_cos == 0.0f ? 0.0f : q.rest_cos;                  // -0.0 -> +0
-        r.rs = q.rest_sin == 0.0f ? 0.0f : q.rest_sin;
-        r.stiffness = q.stiffness == 0.0f ? 0.0f : q.stiffness;
+        r.a = u.node_of[3 * j];
+        r.b = u.node_of[3 * j + 1];
+        r.c = u.node_of[3 * j + 2];
+        r.rc = plus_zero(q.rest_cos);
+        r.rs = plus_zero(q.rest_sin);
+        r.stiffness = plus_zero(q.stiffness);
         r.pad0 = r.pad1 = 0;
-        g->row_start[r.a + 1] += 1;
-        g->row_start[r.b + 1] += 1;
-        g->row_start[r.c + 1] += 1;
-    }
-    for (size_t v = 0; v < m; ++v) {
-        g->max_degree = std::max(g->max_degree, g->row_start[v + 1]);
-        g->row_start[v + 1] += g->row_start[v];
-    }
-    if (g->max_degree > GPE_BEND_MAX_DEGREE) return false;
-    g->inc.resize(g->row_start[m]);
-    std::vector<uint32_t> at(g->row_start.begin(), g->row_start.end() - 1);
-    for (uint64_t j = 0; j < k; ++j) {                                  // ascending j: every row ends up in bend order
-        const BendRecord &r = g->rec[j];
-        g->inc[at[r.a]++] = (uint32_t)(j << 2) | kBendRoleA;
-        g->inc[at[r.b]++] = (uint32_t)(j << 2) | kBendRoleHinge;
-        g->inc[at[r.c]++] = (uint32_t)(j << 2) | kBendRoleC;
+        g->inc[u.at[3 * j]] = (uint32_t)(j << 2) | kBendRoleA;
+        g->inc[u.at[3 * j + 1]] = (uint32_t)(j << 2) | kBendRoleHinge;
+        g->inc[u.at[3 * j + 2]] = (uint32_t)(j << 2) | kBendRoleC;
     }
     return true;
 }

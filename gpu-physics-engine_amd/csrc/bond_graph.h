@@ -5,7 +5,7 @@
 //   - nodes: the distinct uids the bonds name, ascending (m <= 2 k).  An anchor's point is no node;
 //   - per bond its two ends as node indices (an anchor: its index in `anchors`, with kBondAnchorBit);
 //   - a CSR of incidences per node, in ascending bond index: entry = bond << 1 | side (0: the node is the bond's a,
-//     1: its b).  A bond listed twice appears twice, in both rows.
+//     1: its b).  A bond listed twice appears twice, in both rows.  The nodes and the rows are uid_nodes.h's.
 // What the pass adds up per particle, and in which order, is therefore a function of the set alone.
 #pragma once
 
@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "../../include/gpe.h"
+#include "uid_nodes.h"
 
 namespace gpe {
 
@@ -69,57 +70,46 @@ inline const char *bond_set_problem(const gpe_bond *bonds, uint64_t k, uint32_t 
 inline bool bond_graph_build(const gpe_bond *bonds, uint64_t k, BondGraph *g)
 {
     *g = BondGraph();
-    std::vector<uint32_t> &nodes = g->nodes;
-    nodes.reserve(2 * k);
+    std::vector<uint32_t> uids;                                         // a, then b unless the bond is an anchor, per bond
+    uids.reserve(2 * k);
     bool breakable = false;
     for (uint64_t j = 0; j < k; ++j) {
-        nodes.push_back(bonds[j].uid_a);
-        if (!(bonds[j].flags & GPE_BOND_ANCHOR)) nodes.push_back(bonds[j].uid_b);
+        uids.push_back(bonds[j].uid_a);
+        if (!(bonds[j].flags & GPE_BOND_ANCHOR)) uids.push_back(bonds[j].uid_b);
         breakable |= bonds[j].max_length > 0.0f;
     }
-    std::sort(nodes.begin(), nodes.end());
-    nodes.erase(std::unique(nodes.begin(), nodes.end()), nodes.end());
-    const size_t m = nodes.size();
-    auto node_of = [&nodes](uint32_t uid) {
-        return (uint32_t)(std::lower_bound(nodes.begin(), nodes.end(), uid) - nodes.begin());
-    };
+    UidNodes u;
+    uid_nodes_build(uids.data(), uids.size(), &u);
+    g->nodes = std::move(u.nodes);
+    g->row_start = std::move(u.row_start);
+    g->max_degree = u.max_degree;
+    if (g->max_degree > GPE_BOND_MAX_DEGREE) return false;
     g->rec.resize(k);
     g->state.assign(k, 0);
     if (breakable) g->max_length.resize(k);
-    g->row_start.assign(m + 1, 0);
+    g->inc.resize(uids.size());
+    size_t e = 0;
     for (uint64_t j = 0; j < k; ++j) {
         const gpe_bond &q = bonds[j];
         BondRecord &r = g->rec[j];
-        r.a = node_of(q.uid_a);
-        r.rest = q.rest_length == 0.0f ? 0.0f : q.rest_length;          // -0.0 -> +0
-        g->row_start[r.a + 1] += 1;
+        r.a = u.node_of[e];
+        r.rest = plus_zero(q.rest_length);
+        g->inc[u.at[e++]] = (uint32_t)(j << 1);
         if (q.flags & GPE_BOND_ANCHOR) {
             r.b = kBondAnchorBit | (uint32_t)(g->anchors.size() / 2);
             r.w = q.stiffness;
             g->anchors.push_back(q.anchor_x);
             g->anchors.push_back(q.anchor_y);
         } else {
-            r.b = node_of(q.uid_b);
+            r.b = u.node_of[e];
             r.w = 0.5f * q.stiffness;
-            g->row_start[r.b + 1] += 1;
+            g->inc[u.at[e++]] = (uint32_t)(j << 1) | 1u;
         }
-        if (breakable) g->max_length[j] = q.max_length == 0.0f ? 0.0f : q.max_length;
+        if (breakable) g->max_length[j] = plus_zero(q.max_length);
         if (q.flags & GPE_BOND_BROKEN) {
             g->state[j] = 1;
             g->broken += 1;
         }
-    }
-    for (size_t v = 0; v < m; ++v) {
-        g->max_degree = std::max(g->max_degree, g->row_start[v + 1]);
-        g->row_start[v + 1] += g->row_start[v];
-    }
-    if (g->max_degree > GPE_BOND_MAX_DEGREE) return false;
-    g->inc.resize(g->row_start[m]);
-    std::vector<uint32_t> at(g->row_start.begin(), g->row_start.end() - 1);
-    for (uint64_t j = 0; j < k; ++j) {                                  // ascending j: every row ends up in bond order
-        const BondRecord &r = g->rec[j];
-        g->inc[at[r.a]++] = (uint32_t)(j << 1);
-        if (!(r.b & kBondAnchorBit)) g->inc[at[r.b]++] = (uint32_t)(j << 1) | 1u;
     }
     return true;
 }

@@ -1,6 +1,10 @@
 // gpe_api.hip -- the extern "C" boundary of include/gpe.h: context, device memory, particle buffers, set / add / remove,
 // uids, step ordering, downloads, profiling.  The queries are in gpe_queries.hip, the checked add, edits and kicks in
-// gpe_edits.hip, the tracers and the monitor in gpe_observe.hip, the static colliders in gpe_colliders.hip, the distance bonds in gpe_bonds.hip, the bend constraints in gpe_bends.hip, the area constraints in gpe_areas.hip, the rigid and soft bodies in gpe_bodies.hip, the force fields in gpe_fields.hip, the moving colliders in gpe_movers.hip.  All device work goes to one in-order hipStream per context.
+// gpe_edits.hip, the tracers and the monitor in gpe_observe.hip, the static colliders in gpe_colliders.hip, the force fields in gpe_fields.hip, the moving colliders in gpe_movers.hip.
+// The sets that name their particles by uid -- the distance bonds in gpe_bonds.hip, the bend constraints in
+// gpe_bends.hip, the area constraints in gpe_areas.hip, the rigid and soft bodies in gpe_bodies.hip -- share their
+// node table (gpe_internal.h UidNodeTable; uid_nodes.h builds it, k_uid_nodes.h walks it) and the edges of their entry
+// points (uid_sets.h); this file lists them once (kUidSets).  All device work goes to one in-order hipStream per context.
 #include <math.h>
 #include <stddef.h>
 #include <stdlib.h>
@@ -311,12 +315,40 @@ gpe_status refuse_sharded(gpe_ctx *c, const char *who)
                                                             "or an active cell box)");
 }
 
+gpe_status refuse_holds(gpe_ctx *c, const char *who, const char *sets, const char *setter)
+{
+    return fail(c, GPE_ERR_UNSUPPORTED, std::string(who) + ": not supported while the context holds " + sets + " (" +
+                                            setter + " with k = 0 clears them)");
+}
+
+// The sets that name their particles by uid, in the order of their passes behind a step (after_step).  refusal: the
+// set's rank when a context that holds several is refused -- bonds, bodies, bends, areas: which text the caller sees
+struct UidSet {
+    const char *name, *setter;
+    int refusal;
+    bool (*has)(const gpe_ctx *);
+    void (*release)(gpe_ctx *);
+    gpe_status (*pass)(gpe_ctx *);
+};
+static const UidSet kUidSets[] = {
+    {"bends", "gpe_set_bends", 2, has_bends, bends_release, bends_pass},
+    {"areas", "gpe_set_areas", 3, has_areas, areas_release, areas_pass},
+    {"bonds", "gpe_set_bonds", 0, has_bonds, bonds_release, bonds_pass},
+    {"bodies", "gpe_set_bodies", 1, has_bodies, bodies_release, bodies_pass},
+};
+
+// GPE_ERR_UNSUPPORTED when the context holds one of them (taking the uids away, sharding)
+static gpe_status refuse_uid_sets(gpe_ctx *c, const char *who)
+{
+    const UidSet *first = nullptr;
+    for (const UidSet &s : kUidSets)
+        if (s.has(c) && (!first || s.refusal < first->refusal)) first = &s;
+    return first ? refuse_holds(c, who, first->name, first->setter) : GPE_OK;
+}
+
 gpe_status refuse_step_sets(gpe_ctx *c, const char *who, const char *uid_refusal)
 {
-    if (has_bonds(c)) return refuse_bonds(c, who);
-    if (has_bodies(c)) return refuse_bodies(c, who);
-    if (has_bends(c)) return refuse_bends(c, who);
-    if (has_areas(c)) return refuse_areas(c, who);
+    GPE_TRY(refuse_uid_sets(c, who));
     if (c->uid.on) return fail(c, GPE_ERR_UNSUPPORTED, std::string(who) + ": " + uid_refusal);
     if (has_colliders(c)) return refuse_colliders(c, who);
     if (has_fields(c)) return refuse_fields(c, who);
@@ -1005,10 +1037,7 @@ gpe_status gpe_destroy(gpe_ctx *c)
     observers_release(c);
     colliders_release(c);
     sweep_release(c);
-    bonds_release(c);
-    bends_release(c);
-    areas_release(c);
-    bodies_release(c);
+    for (const UidSet &s : kUidSets) s.release(c);
     fields_release(c);
     movers_release(c);
     mover_sweep_release(c);
@@ -1176,10 +1205,7 @@ gpe_status gpe_enable_uids(gpe_ctx *c, int32_t enable)
     UidState &u = c->uid;
     if (!enable) {
         if (!u.on) return GPE_OK;
-        if (has_bonds(c)) return refuse_bonds(c, "gpe_enable_uids");   // (they name their particles by uid)
-        if (has_bodies(c)) return refuse_bodies(c, "gpe_enable_uids"); // (and so do they)
-        if (has_bends(c)) return refuse_bends(c, "gpe_enable_uids");
-        if (has_areas(c)) return refuse_areas(c, "gpe_enable_uids");
+        GPE_TRY(refuse_uid_sets(c, "gpe_enable_uids"));         // (they name their particles by uid)
         GPE_HIP(c, hipSetDevice(c->device));
         GPE_HIP(c, hipStreamSynchronize(c->stream));           // (a re-sort in flight may still read them)
         uid_release(c);
@@ -1480,10 +1506,8 @@ gpe_status gpe_solve_collisions(gpe_ctx *c)
 // observers, whose frames see the result.  A context without a set pays that set's flag test and no call.
 static inline gpe_status after_step(gpe_ctx *c, float dt)
 {
-    if (has_bends(c)) GPE_TRY(bends_after_step(c));
-    if (has_areas(c)) GPE_TRY(areas_after_step(c));
-    if (has_bonds(c)) GPE_TRY(bonds_after_step(c));
-    if (has_bodies(c)) GPE_TRY(bodies_after_step(c));
+    for (const UidSet &s : kUidSets)
+        if (s.has(c)) GPE_TRY(s.pass(c));
     if (has_movers(c)) GPE_TRY(movers_after_step(c, dt));
     if (has_colliders(c)) GPE_TRY(colliders_after_step(c));
     if (has_fields(c)) GPE_TRY(fields_after_step(c, dt));

@@ -1,60 +1,39 @@
 // gpe_areas.hip -- the area constraints of a context (gpe_set_areas and the rest): the set, its tables (area_table.h),
 // the nodes' and members' storage slots (looked up again only when stale) and the pass behind every step
-// (k_areas.hip).  gpe_api.hip calls areas_after_step from after_step and areas_release from gpe_destroy.
+// (k_areas.hip).  What the entry points share with the other sets that name their particles by uid is uid_sets.h's;
+// gpe_api.hip lists the set in its table (after_step, gpe_destroy, the refusals).
 #include <string.h>
 
 #include "area_table.h"
-#include "gpe_internal.h"
 #include "k_area.h"
-#include "k_uids.h"
+#include "uid_sets.h"
 
 using namespace gpe;               // (the entry points take their C linkage from their declarations in include/gpe.h)
 
 static_assert(kAreaClasses + 1 == sizeof(AreaState().class_start) / sizeof(uint32_t), "AreaState keeps every class start");
 
-static void areas_free(gpe_ctx *c, AreaState &S)
-{
-    dev_free(c, S.rec); dev_free(c, S.order); dev_free(c, S.member_node); dev_free(c, S.member_slot);
-    dev_free(c, S.node_uid); dev_free(c, S.node_slot); dev_free(c, S.row_start); dev_free(c, S.inc);
-    dev_free(c, S.corr); dev_free(c, S.state); dev_free(c, S.value);
-}
-
 void gpe::areas_release(gpe_ctx *c)
 {
-    areas_free(c, c->areas);
-    c->areas = AreaState();
+    AreaState &S = c->areas;
+    dev_free(c, S.rec); dev_free(c, S.order); dev_free(c, S.member_node); dev_free(c, S.member_slot);
+    node_table_free(c, S.nt); dev_free(c, S.inc);
+    dev_free(c, S.corr); dev_free(c, S.state); dev_free(c, S.value);
+    S = AreaState();
 }
 
-gpe_status gpe::refuse_areas(gpe_ctx *c, const char *who)
-{
-    return fail(c, GPE_ERR_UNSUPPORTED, std::string(who) + ": not supported while the context holds areas "
-                                                            "(gpe_set_areas with k = 0 clears them)");
-}
-
-// One pass over the particles as they are now.  Enqueues only, unless the slots are stale: then the uid map is made
-// ready first (its build synchronises), one lookup per node is enqueued and the members take their nodes' slots.
-static gpe_status areas_pass(gpe_ctx *c)
+// (a stale set: the members take their nodes' slots behind the lookup)
+gpe_status gpe::areas_pass(gpe_ctx *c)
 {
     AreaState &S = c->areas;
-    if (S.set.empty() || c->n == 0 || !c->pos || !c->uid.on || !c->uid.uids) return GPE_OK;
-    if (S.stale) {
-        GPE_TRY(uid_map_ready(c));
-        Scope s(c, "areas/resolve");
-        GPE_TRY(launch_uid_find(c, c->uid.map_keys, c->uid.map_vals, c->n, S.node_uid, S.nodes, S.node_slot, nullptr,
-                                nullptr, nullptr));
-        GPE_TRY(launch_areas_expand(c, S));
-        S.stale = false;
-        S.resolves += 1;
-    }
-    Scope s(c, "Areas");
-    GPE_TRY(launch_areas_pass(c, c->pos, c->radius, c->n, S, (uint32_t)S.set.size(), (uint32_t)S.nodes, S.iterations));
-    S.passes += 1;
-    return GPE_OK;
-}
-
-gpe_status gpe::areas_after_step(gpe_ctx *c)
-{
-    return areas_pass(c);                                             // (after_step has looked: the set is not empty)
+    return uid_set_pass(c, S.set.empty(), S.nt.stale, "Areas", &S.passes,
+                        [&] {
+                            return uid_slots_resolve(c, "areas/resolve", S.nt,
+                                                     [](gpe_ctx *x) { return launch_areas_expand(x, x->areas); });
+                        },
+                        [&] {
+                            return launch_areas_pass(c, c->pos, c->radius, c->n, S, (uint32_t)S.set.size(),
+                                                     (uint32_t)S.nt.nodes, S.iterations);
+                        });
 }
 
 gpe_status gpe_set_areas(gpe_ctx *c, const gpe_area *areas, uint64_t k, const uint32_t *member_uid, uint64_t members,
@@ -63,28 +42,19 @@ gpe_status gpe_set_areas(gpe_ctx *c, const gpe_area *areas, uint64_t k, const ui
     if (!c) return GPE_ERR_INVALID_ARG;
     if (const char *why = area_set_problem(areas, k, member_uid, members, iterations))
         return fail(c, GPE_ERR_INVALID_ARG, std::string("gpe_set_areas: ") + why);
-    if (is_sharded(c)) return refuse_sharded(c, "gpe_set_areas");
-    if (k > 0 && !c->uid.on) return fail(c, GPE_ERR_STATE, "gpe_set_areas: uids are off (gpe_enable_uids)");
-    GPE_HIP(c, hipSetDevice(c->device));
-    GPE_HIP(c, hipStreamSynchronize(c->stream));                       // (a pass in flight reads the old set)
-    if (k == 0) {
-        areas_release(c);
-        return GPE_OK;
-    }
+    GPE_TRY(uid_set_open(c, "gpe_set_areas", k, areas_release));
+    if (k == 0) return GPE_OK;
     AreaTable t;
     area_table_build(areas, k, member_uid, members, &t);
     // the new tables beside the old ones (set_upload.h).  Every array is read and written by index below the count it
     // is allocated with.  no slack
-    const uint64_t m = t.nodes.size();
     AreaState N;
     HipSetUpload up({c}, "gpe_set_areas");
     up.reserve(&N.rec, k, "uid.area_rec");
     up.reserve(&N.order, k, "uid.area_order");
     up.reserve(&N.member_node, members, "uid.area_member_node");
     up.reserve(&N.member_slot, members, "uid.area_member_slot");
-    up.reserve(&N.node_uid, m, "uid.area_node_uid");
-    up.reserve(&N.node_slot, m, "uid.area_node_slot");
-    up.reserve(&N.row_start, m + 1, "uid.area_row_start");
+    node_table_upload(up, &N.nt, t.nodes, t.row_start, "uid.area_node_uid", "uid.area_node_slot", "uid.area_row_start");
     up.reserve(&N.inc, members, "uid.area_inc");
     up.reserve(&N.corr, members, "uid.area_corr");
     up.reserve(&N.state, k, "uid.area_state");
@@ -92,27 +62,22 @@ gpe_status gpe_set_areas(gpe_ctx *c, const gpe_area *areas, uint64_t k, const ui
     up.copy(N.rec, t.rec.data(), k);
     up.copy(N.order, t.order.data(), k);
     up.copy(N.member_node, t.member_node.data(), members);
-    up.copy(N.node_uid, t.nodes.data(), m);
-    up.copy(N.row_start, t.row_start.data(), m + 1);
     up.copy(N.inc, t.inc.data(), members);
     up.fill(N.member_slot, 0xff, members * sizeof(uint32_t));
-    up.fill(N.node_slot, 0xff, m * sizeof(uint32_t));
     up.fill(N.corr, 0, members * sizeof(float2));
     up.fill(N.state, (int)kAreaInert, k);
     up.fill(N.value, 0xff, k * sizeof(float2));                        // (all ones: a NaN)
     GPE_TRY(up.finish());
-    areas_free(c, c->areas);
+    areas_release(c);
     N.set.assign(areas, areas + k);
     for (gpe_area &q : N.set) {
-        if (q.rest_area == 0.0f) q.rest_area = 0.0f;                   // -0.0 -> +0
-        if (q.stiffness == 0.0f) q.stiffness = 0.0f;
+        q.rest_area = plus_zero(q.rest_area);
+        q.stiffness = plus_zero(q.stiffness);
     }
     N.member_uid_host.assign(member_uid, member_uid + members);
     N.iterations = iterations;
     N.members = members;
-    N.nodes = m;
     memcpy(N.class_start, t.class_start, sizeof(N.class_start));
-    N.stale = true;
     c->areas = std::move(N);
     return GPE_OK;
 }
@@ -131,28 +96,21 @@ gpe_status gpe_get_areas(const gpe_ctx *c, gpe_area *out, uint64_t capacity, uin
 
 gpe_status gpe_apply_areas(gpe_ctx *c)
 {
-    if (!c) return GPE_ERR_INVALID_ARG;
-    if (!has_areas(c) || c->n == 0) return GPE_OK;
-    GPE_HIP(c, hipSetDevice(c->device));
-    return areas_pass(c);
+    return uid_set_apply(c, has_areas, areas_pass);
 }
 
 gpe_status gpe_get_areas_info(gpe_ctx *c, gpe_areas_info *info)
 {
-    if (!c) return GPE_ERR_INVALID_ARG;
-    if (!info || info->struct_size < sizeof(gpe_areas_info))
-        return fail(c, GPE_ERR_INVALID_ARG, "gpe_get_areas_info: NULL info or bad struct_size");
-    const AreaState &S = c->areas;
     gpe_areas_info out;
-    memset(&out, 0, sizeof(out));
-    out.struct_size = info->struct_size;
+    GPE_TRY(info_open(c, "gpe_get_areas_info", info, &out));
+    const AreaState &S = c->areas;
     if (has_areas(c)) {
         out.iterations = S.iterations;
         out.k = S.set.size();
         out.members = S.members;
-        out.nodes = S.nodes;
+        out.nodes = S.nt.nodes;
         out.passes = S.passes;
-        out.resolves = S.resolves;
+        out.resolves = S.nt.resolves;
     }
     *info = out;
     return GPE_OK;
@@ -180,7 +138,7 @@ gpe_status gpe_set_area_targets(gpe_ctx *c, uint64_t first, uint64_t k, const fl
     if (k == 0) return GPE_OK;
     GPE_HIP(c, hipSetDevice(c->device));
     GPE_HIP(c, hipStreamSynchronize(c->stream));                       // (a pass in flight reads the old targets)
-    for (uint64_t j = 0; j < k; ++j) S.set[first + j].rest_area = rest_area[j] == 0.0f ? 0.0f : rest_area[j];
+    for (uint64_t j = 0; j < k; ++j) S.set[first + j].rest_area = plus_zero(rest_area[j]);
     // the records of the range again, as area_table_build wrote them: only their rest areas differ
     std::vector<AreaRecord> rows(k);
     for (uint64_t j = 0; j < k; ++j) {

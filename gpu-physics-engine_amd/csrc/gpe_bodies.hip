@@ -1,56 +1,33 @@
 // gpe_bodies.hip -- the rigid and soft bodies of a context (gpe_set_bodies and the rest): the set, its tables
 // (body_table.h), the members' storage slots (looked up again only when stale) and the pass behind every step
-// (k_bodies.hip).  gpe_api.hip calls bodies_after_step from after_step and bodies_release from gpe_destroy.
+// (k_bodies.hip).  What the entry points share with the other sets that name their particles by uid is uid_sets.h's;
+// gpe_api.hip lists the set in its table (after_step, gpe_destroy, the refusals).
 #include <string.h>
 
 #include "body_table.h"
-#include "gpe_internal.h"
 #include "k_body.h"
-#include "k_uids.h"
+#include "uid_sets.h"
 
 using namespace gpe;               // (the entry points take their C linkage from their declarations in include/gpe.h)
 
-static void bodies_free(gpe_ctx *c, BodyState &S)
-{
-    dev_free(c, S.rec); dev_free(c, S.order); dev_free(c, S.member_uid); dev_free(c, S.member_slot);
-    dev_free(c, S.member_rest); dev_free(c, S.pose); dev_free(c, S.state); dev_free(c, S.broken);
-}
-
 void gpe::bodies_release(gpe_ctx *c)
 {
-    bodies_free(c, c->bodies);
-    c->bodies = BodyState();
+    BodyState &S = c->bodies;
+    dev_free(c, S.rec); dev_free(c, S.order); dev_free(c, S.member_uid); dev_free(c, S.member_slot);
+    dev_free(c, S.member_rest); dev_free(c, S.pose); dev_free(c, S.state); dev_free(c, S.broken);
+    S = BodyState();
 }
 
-gpe_status gpe::refuse_bodies(gpe_ctx *c, const char *who)
-{
-    return fail(c, GPE_ERR_UNSUPPORTED, std::string(who) + ": not supported while the context holds bodies "
-                                                            "(gpe_set_bodies with k = 0 clears them)");
-}
-
-// One pass over the particles as they are now.  Enqueues only, unless the members' slots are stale: then the uid map
-// is made ready first (its build synchronises) and one lookup per member is enqueued.
-static gpe_status bodies_pass(gpe_ctx *c)
+// (no node table: a uid is a member of one body, so the members are looked up directly)
+gpe_status gpe::bodies_pass(gpe_ctx *c)
 {
     BodyState &S = c->bodies;
-    if (S.set.empty() || c->n == 0 || !c->pos || !c->uid.on || !c->uid.uids) return GPE_OK;
-    if (S.stale) {
-        GPE_TRY(uid_map_ready(c));
-        Scope s(c, "bodies/resolve");
-        GPE_TRY(launch_uid_find(c, c->uid.map_keys, c->uid.map_vals, c->n, S.member_uid, S.members, S.member_slot,
-                                nullptr, nullptr, nullptr));
-        S.stale = false;
-        S.resolves += 1;
-    }
-    Scope s(c, "Bodies");
-    GPE_TRY(launch_bodies_pass(c, c->pos, c->radius, c->n, S, (uint32_t)S.set.size()));
-    S.passes += 1;
-    return GPE_OK;
-}
-
-gpe_status gpe::bodies_after_step(gpe_ctx *c)
-{
-    return bodies_pass(c);                                            // (after_step has looked: the set is not empty)
+    return uid_set_pass(c, S.set.empty(), S.stale, "Bodies", &S.passes,
+                        [&] {
+                            return uid_slots_resolve(c, "bodies/resolve", S.member_uid, S.members, S.member_slot,
+                                                     &S.stale, &S.resolves);
+                        },
+                        [&] { return launch_bodies_pass(c, c->pos, c->radius, c->n, S, (uint32_t)S.set.size()); });
 }
 
 gpe_status gpe_set_bodies(gpe_ctx *c, const gpe_body *bodies, uint64_t k, const uint32_t *member_uid,
@@ -59,14 +36,8 @@ gpe_status gpe_set_bodies(gpe_ctx *c, const gpe_body *bodies, uint64_t k, const 
     if (!c) return GPE_ERR_INVALID_ARG;
     if (const char *why = body_set_problem(bodies, k, member_uid, member_rest_xy, members))
         return fail(c, GPE_ERR_INVALID_ARG, std::string("gpe_set_bodies: ") + why);
-    if (is_sharded(c)) return refuse_sharded(c, "gpe_set_bodies");
-    if (k > 0 && !c->uid.on) return fail(c, GPE_ERR_STATE, "gpe_set_bodies: uids are off (gpe_enable_uids)");
-    GPE_HIP(c, hipSetDevice(c->device));
-    GPE_HIP(c, hipStreamSynchronize(c->stream));                       // (a pass in flight reads the old set)
-    if (k == 0) {
-        bodies_release(c);
-        return GPE_OK;
-    }
+    GPE_TRY(uid_set_open(c, "gpe_set_bodies", k, bodies_release));
+    if (k == 0) return GPE_OK;
     BodyTable t;
     body_table_build(bodies, k, &t);
     // the new tables beside the old ones (set_upload.h).  Every array is read and written by index below the count it
@@ -91,11 +62,11 @@ gpe_status gpe_set_bodies(gpe_ctx *c, const gpe_body *bodies, uint64_t k, const 
     up.fill(N.pose, 0xff, k * sizeof(float4));                         // (all ones: a NaN)
     up.copy(N.broken, &broken, 1);
     GPE_TRY(up.finish());
-    bodies_free(c, c->bodies);
+    bodies_release(c);
     N.set.assign(bodies, bodies + k);
     for (gpe_body &q : N.set) {
         q.flags &= ~(uint32_t)GPE_BODY_BROKEN;                         // (it set the state byte; the record does not keep it)
-        if (q.break_distance == 0.0f) q.break_distance = 0.0f;         // -0.0 -> +0
+        q.break_distance = plus_zero(q.break_distance);
     }
     N.member_uid_host.assign(member_uid, member_uid + members);
     N.member_rest_host.assign(member_rest_xy, member_rest_xy + 2 * members);
@@ -121,21 +92,12 @@ gpe_status gpe_get_bodies(gpe_ctx *c, gpe_body *out, uint8_t *broken_out, uint64
     if (mm && member_rest_xy_out) memcpy(member_rest_xy_out, S.member_rest_host.data(), 2 * mm * sizeof(float));
     if (m == 0) return GPE_OK;
     if (out) memcpy(out, S.set.data(), m * sizeof(gpe_body));
-    if (broken_out) {
-        GPE_HIP(c, hipSetDevice(c->device));
-        std::vector<uint8_t> state(m);
-        GPE_TRY(read_back(c, S.state, state.data(), m));
-        for (uint64_t j = 0; j < m; ++j) broken_out[j] = state[j] == kBodyBroken ? 1 : 0;
-    }
-    return GPE_OK;
+    return broken_out ? gpe::broken_out(c, S.state, m, kBodyBroken, broken_out) : GPE_OK;
 }
 
 gpe_status gpe_apply_bodies(gpe_ctx *c)
 {
-    if (!c) return GPE_ERR_INVALID_ARG;
-    if (!has_bodies(c) || c->n == 0) return GPE_OK;
-    GPE_HIP(c, hipSetDevice(c->device));
-    return bodies_pass(c);
+    return uid_set_apply(c, has_bodies, bodies_pass);
 }
 
 gpe_status gpe_get_body_poses(gpe_ctx *c, float *pose_xycs, uint64_t capacity, uint64_t *k)
@@ -152,23 +114,15 @@ gpe_status gpe_get_body_poses(gpe_ctx *c, float *pose_xycs, uint64_t capacity, u
 
 gpe_status gpe_get_bodies_info(gpe_ctx *c, gpe_bodies_info *info)
 {
-    if (!c) return GPE_ERR_INVALID_ARG;
-    if (!info || info->struct_size < sizeof(gpe_bodies_info))
-        return fail(c, GPE_ERR_INVALID_ARG, "gpe_get_bodies_info: NULL info or bad struct_size");
-    BodyState &S = c->bodies;
     gpe_bodies_info out;
-    memset(&out, 0, sizeof(out));
-    out.struct_size = info->struct_size;
+    GPE_TRY(info_open(c, "gpe_get_bodies_info", info, &out));
+    const BodyState &S = c->bodies;
     if (has_bodies(c)) {
-        GPE_HIP(c, hipSetDevice(c->device));
-        unsigned long long broken = 0;
-        GPE_TRY(read_back(c, S.broken, &broken, sizeof(broken)));
         out.k = S.set.size();
         out.members = S.members;
         out.passes = S.passes;
-        out.broken = broken;
-        out.live = out.k - broken;
         out.resolves = S.resolves;
+        GPE_TRY(info_broken(c, S.broken, &out));
     }
     *info = out;
     return GPE_OK;

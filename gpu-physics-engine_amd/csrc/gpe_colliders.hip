@@ -57,8 +57,7 @@ void gpe::colliders_release(gpe_ctx *c)
 
 gpe_status gpe::refuse_colliders(gpe_ctx *c, const char *who)
 {
-    return fail(c, GPE_ERR_UNSUPPORTED, std::string(who) + ": not supported while the context holds colliders "
-                                                            "(gpe_set_colliders with k = 0 clears them)");
+    return refuse_holds(c, who, "colliders", "gpe_set_colliders");
 }
 
 // The grid for the radius bound and the world as they are now.  Builds only when one of them has changed since the last

@@ -38,8 +38,7 @@ void gpe::fields_world_changed(gpe_ctx *c)
 
 gpe_status gpe::refuse_fields(gpe_ctx *c, const char *who)
 {
-    return fail(c, GPE_ERR_UNSUPPORTED, std::string(who) + ": not supported while the context holds force fields "
-                                                            "(gpe_set_fields with k = 0 clears them)");
+    return refuse_holds(c, who, "force fields", "gpe_set_fields");
 }
 
 // The grid for the world as it is now.  Builds only when the world has changed since the last build; that synchronises.

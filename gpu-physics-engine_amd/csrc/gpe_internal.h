@@ -451,21 +451,30 @@ struct SweepState {
     unsigned long long *counts = nullptr;        // two words: particles swept, particles stopped, since then (null: never on)
 };
 
+// The node table of a step set that names its particles by uid (bonds, bends, areas): the distinct uids the set names,
+// their storage slots and a CSR of each node's incidences (uid_nodes.h builds it, k_uid_nodes.h walks it; the set keeps
+// its own incidence words beside it).  Device side, read by index below the stated count
+struct UidNodeTable {
+    uint64_t nodes = 0;                          // m: the distinct uids the set names
+    bool stale = true;                           // node_slot is out of date (uid_slots_stale)
+    uint64_t resolves = 0;                       // lookups since the set was given
+    uint32_t *node_uid = nullptr;                // m: the nodes' uids, ascending
+    uint32_t *node_slot = nullptr;               // m: each node's storage index, 0xffffffff for none (valid unless stale)
+    uint32_t *row_start = nullptr;               // m + 1
+};
+
 // the distance bonds (gpe_set_bonds; gpe_bonds.hip, k_bonds.hip, bond_graph.h).  Step state: gpe_step / gpe_run relax them
 struct BondState {
     std::vector<gpe_bond> set;                   // the bonds as the host gave them (empty: none, nothing is launched)
     uint32_t iterations = 1;
-    uint64_t nodes = 0;                          // m: the distinct uids the bonds name
-    bool stale = true;                           // node_slot is out of date (uid_slots_stale)
-    uint64_t passes = 0, resolves = 0;           // since the last gpe_set_bonds
+    uint64_t passes = 0;                         // since the last gpe_set_bonds
+    UidNodeTable nt;                             // the uids the bonds name
     // device side, read by index below the stated count
     uint4 *rec = nullptr;                        // k: (node a, node b | anchor index, rest, w), bond_graph.h BondRecord
     float *max_length = nullptr;                 // k, or NULL when no bond can break
     float2 *anchors = nullptr;                   // one per anchor bond, or NULL
     uint32_t n_anchors = 0;
-    uint32_t *node_uid = nullptr;                // m: the nodes' uids, ascending
-    uint32_t *node_slot = nullptr;               // m: each node's storage index, 0xffffffff for none (valid unless stale)
-    uint32_t *row_start = nullptr, *inc = nullptr;   // m + 1 / row_start[m]: a node's bonds, bond << 1 | side
+    uint32_t *inc = nullptr;                     // row_start[m] = 2 k - n_anchors: a node's bonds, bond << 1 | side
     float2 *corr = nullptr;                      // k: this relaxation's corrections
     uint8_t *state = nullptr;                    // k: 0 acted, 1 broken (sticky), 2 inert in this relaxation
     unsigned long long *broken = nullptr;        // one word: bonds broken
@@ -476,14 +485,11 @@ struct BondState {
 struct BendState {
     std::vector<gpe_bend> set;                   // the bends as the host gave them (empty: none, nothing is launched)
     uint32_t iterations = 1;
-    uint64_t nodes = 0;                          // m: the distinct uids the bends name
-    bool stale = true;                           // node_slot is out of date (uid_slots_stale)
-    uint64_t passes = 0, resolves = 0;           // since the last gpe_set_bends
+    uint64_t passes = 0;                         // since the last gpe_set_bends
+    UidNodeTable nt;                             // the uids the bends name
     // device side, read by index below the stated count
     uint4 *rec = nullptr;                        // 2 k: (node a, hinge b, node c, rc), (rs, stiffness, 0, 0), bend_graph.h BendRecord
-    uint32_t *node_uid = nullptr;                // m: the nodes' uids, ascending
-    uint32_t *node_slot = nullptr;               // m: each node's storage index, 0xffffffff for none (valid unless stale)
-    uint32_t *row_start = nullptr, *inc = nullptr;   // m + 1 / row_start[m]: a node's bends, bend << 2 | role
+    uint32_t *inc = nullptr;                     // row_start[m] = 3 k: a node's bends, bend << 2 | role
     float4 *corr = nullptr;                      // k: this relaxation's corrections (da.x, da.y, dc.x, dc.y)
     uint8_t *state = nullptr;                    // k: 0 acted, 2 inert in this relaxation
 };
@@ -495,18 +501,14 @@ struct AreaState {
     std::vector<uint32_t> member_uid_host;       // members: what gpe_get_areas gives back
     uint32_t iterations = 1;
     uint64_t members = 0;
-    uint64_t nodes = 0;                          // m: the distinct uids the members name
-    bool stale = true;                           // node_slot and member_slot are out of date (uid_slots_stale)
-    uint64_t passes = 0, resolves = 0;           // since the last gpe_set_areas
+    uint64_t passes = 0;                         // since the last gpe_set_areas
+    UidNodeTable nt;                             // the uids the members name; nt.stale: member_slot is out of date too
     uint32_t class_start[6] = {0, 0, 0, 0, 0, 0};   // order[class_start[q], class_start[q + 1]): the loops of width 4 << q
     // device side, read by index below the stated count
     uint4 *rec = nullptr;                        // k: (first, count, rest_area, stiffness), area_table.h AreaRecord
     uint32_t *order = nullptr;                   // k: loop indices by width class
     uint32_t *member_node = nullptr;             // members: each member's node index
     uint32_t *member_slot = nullptr;             // members: node_slot of its node (valid unless stale)
-    uint32_t *node_uid = nullptr;                // m: the nodes' uids, ascending
-    uint32_t *node_slot = nullptr;               // m: each node's storage index, 0xffffffff for none (valid unless stale)
-    uint32_t *row_start = nullptr;               // m + 1
     uint2 *inc = nullptr;                        // row_start[m] = members: a node's memberships, (member, loop)
     float2 *corr = nullptr;                      // members: this relaxation's corrections
     uint8_t *state = nullptr;                    // k: 0 acted, 2 inert in this relaxation
@@ -1087,6 +1089,28 @@ struct HipUploadBackend {
 };
 using HipSetUpload = SetUpload<HipUploadBackend>;
 
+// A set's node table inside its upload transaction: the three tables reserved, the nodes and the rows copied, node_slot
+// all ones (no node has a slot until the first pass looks them up).  The tags are literals, as everywhere: the registry
+// keeps the pointers
+inline void node_table_upload(HipSetUpload &up, UidNodeTable *T, const std::vector<uint32_t> &nodes,
+                              const std::vector<uint32_t> &row_start, const char *node_uid_tag,
+                              const char *node_slot_tag, const char *row_start_tag)
+{
+    const uint64_t m = nodes.size();
+    up.reserve(&T->node_uid, m, node_uid_tag);
+    up.reserve(&T->node_slot, m, node_slot_tag);
+    up.reserve(&T->row_start, m + 1, row_start_tag);
+    up.copy(T->node_uid, nodes.data(), m);
+    up.copy(T->row_start, row_start.data(), m + 1);
+    up.fill(T->node_slot, 0xff, m * sizeof(uint32_t));
+    T->nodes = m;
+    T->stale = true;
+}
+inline void node_table_free(gpe_ctx *c, UidNodeTable &T)
+{
+    dev_free(c, T.node_uid); dev_free(c, T.node_slot); dev_free(c, T.row_start);
+}
+
 // The 256-byte aligned staging layout of a result's requested parts: part() = the offset of the next part, which takes
 // room only when it is requested; bytes = what the parts so far take.
 struct StageLayout {
@@ -1107,6 +1131,8 @@ gpe_status refuse_sharded(gpe_ctx *c, const char *who);             // GPE_ERR_U
 gpe_status refuse_too_many(gpe_ctx *c, const char *who);            // GPE_ERR_UNSUPPORTED: more than 2^32 - 1 particles
 gpe_status refuse_uid_off(gpe_ctx *c, const char *who);             // GPE_ERR_STATE: a uid output while uids are off
 gpe_status refuse_radius_not_finite(gpe_ctx *c, const char *who);   // GPE_ERR_UNSUPPORTED
+// GPE_ERR_UNSUPPORTED: the context holds <sets>, which <setter> with k = 0 clears (the one wording of every such refusal)
+gpe_status refuse_holds(gpe_ctx *c, const char *who, const char *sets, const char *setter);
 // gpe_api.hip
 gpe_status need_particles(gpe_ctx *c);
 // the sticky device-side error words; synchronises the context's stream once (wait_exchange: and the exchange stream, once)
@@ -1131,7 +1157,7 @@ gpe_status rows_out(const std::vector<T> &set, T *out, uint64_t capacity, uint64
     return GPE_OK;
 }
 // The storage order or the uids have changed: whatever keeps storage slots by uid looks them up again before its next use
-inline void uid_slots_stale(gpe_ctx *c) { c->tracers.stale = c->bonds.stale = c->bends.stale = c->areas.stale = c->bodies.stale = true; }
+inline void uid_slots_stale(gpe_ctx *c) { c->tracers.stale = c->bonds.nt.stale = c->bends.nt.stale = c->areas.nt.stale = c->bodies.stale = true; }
 void refresh_cell_size(gpe_ctx *c);
 gpe_status reconfigure(gpe_ctx *c);
 gpe_status uid_map_ready(gpe_ctx *c);
@@ -1171,25 +1197,20 @@ gpe_status sweep_mode_set(gpe_ctx *c, const char *who, SweepState &W, uint32_t m
 gpe_status sweep_mode_info(gpe_ctx *c, const char *who, const SweepState &W, gpe_sweep_info *info);
 // gpe_surfaces.hip: the surfaces of the two sets; a new set drops its target's
 void surfaces_drop(gpe_ctx *c, uint32_t target);   // GPE_SURFACES_OF_*: frees the rows, the next pass is the plain one
-// gpe_bonds.hip: the distance bonds of a context that holds some
-inline bool has_bonds(const gpe_ctx *c) { return !c->bonds.set.empty(); }
-gpe_status refuse_bonds(gpe_ctx *c, const char *who);       // GPE_ERR_UNSUPPORTED: taking the uids from a context that holds bonds
-gpe_status bonds_after_step(gpe_ctx *c);
+// The sets that name their particles by uid (uid_sets.h has what their entry points share; gpe_api.hip lists them in
+// one table: their refusals, their passes behind a step, their release).  X_pass: one pass over the particles as they
+// are now; X_release: the set and its tables go
+inline bool has_bonds(const gpe_ctx *c) { return !c->bonds.set.empty(); }        // gpe_bonds.hip
+gpe_status bonds_pass(gpe_ctx *c);
 void bonds_release(gpe_ctx *c);
-// gpe_bends.hip: the bend constraints of a context that holds some
-inline bool has_bends(const gpe_ctx *c) { return !c->bends.set.empty(); }
-gpe_status refuse_bends(gpe_ctx *c, const char *who);       // GPE_ERR_UNSUPPORTED: taking the uids from a context that holds bends
-gpe_status bends_after_step(gpe_ctx *c);
+inline bool has_bends(const gpe_ctx *c) { return !c->bends.set.empty(); }        // gpe_bends.hip
+gpe_status bends_pass(gpe_ctx *c);
 void bends_release(gpe_ctx *c);
-// gpe_areas.hip: the area constraints of a context that holds some
-inline bool has_areas(const gpe_ctx *c) { return !c->areas.set.empty(); }
-gpe_status refuse_areas(gpe_ctx *c, const char *who);       // GPE_ERR_UNSUPPORTED: taking the uids from a context that holds areas
-gpe_status areas_after_step(gpe_ctx *c);
+inline bool has_areas(const gpe_ctx *c) { return !c->areas.set.empty(); }        // gpe_areas.hip
+gpe_status areas_pass(gpe_ctx *c);
 void areas_release(gpe_ctx *c);
-// gpe_bodies.hip: the rigid and soft bodies of a context that holds some
-inline bool has_bodies(const gpe_ctx *c) { return !c->bodies.set.empty(); }
-gpe_status refuse_bodies(gpe_ctx *c, const char *who);      // GPE_ERR_UNSUPPORTED: taking the uids from a context that holds bodies
-gpe_status bodies_after_step(gpe_ctx *c);
+inline bool has_bodies(const gpe_ctx *c) { return !c->bodies.set.empty(); }      // gpe_bodies.hip
+gpe_status bodies_pass(gpe_ctx *c);
 void bodies_release(gpe_ctx *c);
 // gpe_fields.hip: the force fields of a context that holds some
 inline bool has_fields(const gpe_ctx *c) { return !c->fields.set.empty(); }

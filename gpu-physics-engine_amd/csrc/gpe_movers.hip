@@ -43,8 +43,7 @@ void gpe::movers_release(gpe_ctx *c)
 
 gpe_status gpe::refuse_movers(gpe_ctx *c, const char *who)
 {
-    return fail(c, GPE_ERR_UNSUPPORTED, std::string(who) + ": not supported while the context holds moving colliders "
-                                                            "(gpe_set_movers with k = 0 clears them)");
+    return refuse_holds(c, who, "moving colliders", "gpe_set_movers");
 }
 
 gpe_status gpe::movers_check_dt(gpe_ctx *c, float dt, const char *who)

@@ -3,7 +3,7 @@
 // builds the tables on the host).
 //
 // One relaxation must not read a position it has written itself (Jacobi), and a uid may be a member of several loops,
-// so it is two phases on the context's in-order stream, as in k_bonds.hip and k_bends.hip:
+// so it is two phases on the context's in-order stream:
 //   - k_areas_loop<G>.  A wave serves 64 / G loops of class G at once, one sub-group of G lanes each; lane l of a
 //     sub-group is lane l of the canonical sum (k_body.h).  The reductions are xor butterflies (offsets below G: they
 //     never leave the sub-group); binary32 addition commutes, so every lane ends with the bits the halving tree leaves
@@ -22,17 +22,16 @@
 //     Lane 0 of a sub-group writes value[loop] = (area, lambda), two NaNs for an inert loop, and the state byte when
 //     it changes: 0 acted, 2 inert in this relaxation.  A loop's lanes are the only writers of its members' corr, of
 //     its value and of its state byte.
-//   - k_areas_node, one lane per node v (a distinct uid the loops name).  Reads node_slot[v] (4 B; an absent uid ends
-//     there), row_start[v], row_start[v + 1], then per membership, in ascending member index, inc (8 B: member, loop),
-//     state (1 B) and for an acting loop corr (8 B).  A node with an acting loop reads pos (8 B) and radius (4 B) of its
-//     particle and writes pos (8 B) once; nothing else is written.  One lane walks a node's whole row (at most
-//     GPE_AREA_MAX_DEGREE).  Two nodes never share a particle (the uids of the map are distinct).
+//   - the node phase, one lane per node v (a distinct uid the loops name): k_uid_nodes.h's kernel, which asks
+//     AreaPassArgs::share.  Per membership, in ascending member index, that reads inc (8 B: member, loop), state (1 B)
+//     and for an acting loop corr (8 B).  One lane walks a node's whole row (at most GPE_AREA_MAX_DEGREE).
 // corr cannot carry the "did not act" mark itself (a correction of zero still counts: its particle is clamped), so the
 // mark is the state byte.  No LDS, no float atomics.  Every slot is checked against n, every index against the count of
 // its array, before it indexes anything.
 #include "gpe_internal.h"
 #include "area_table.h"
 #include "k_area.h"
+#include "k_uid_nodes.h"
 
 namespace gpe {
 
@@ -51,6 +50,16 @@ struct AreaPassArgs {
     uint32_t loops = 0;                          // in this class
     uint32_t k = 0, members = 0, m = 0, n = 0;
     float world_w = 0.f, world_h = 0.f;
+    // the node phase's shares (k_uid_nodes.h): every member is one incidence
+    __device__ __forceinline__ uint32_t incidences() const { return members; }
+    template <class Add>
+    __device__ __forceinline__ void share(uint32_t e, Add add) const
+    {
+        const uint2 w = inc[e];                                         // (member, loop)
+        if (w.x >= members || w.y >= k || state[w.y] != kAreaActs) return;
+        const float2 c = corr[w.x];
+        add(c.x, c.y);
+    }
 };
 
 // S over the G lanes of a sub-group: every lane receives the sum.
@@ -218,33 +227,6 @@ __global__ __launch_bounds__(kStreamBlock) void k_areas_loop(const float2 *__res
     }
 }
 
-__global__ __launch_bounds__(kStreamBlock) void k_areas_node(float2 *__restrict__ pos, const float *__restrict__ radius,
-                                                             AreaPassArgs P)
-{
-#pragma clang fp contract(off)
-    const uint32_t stride = gridDim.x * blockDim.x;
-    for (uint32_t v = blockIdx.x * blockDim.x + threadIdx.x; v < P.m; v += stride) {
-        const uint32_t slot = P.node_slot[v];
-        if (slot >= P.n) continue;
-        const uint32_t lo = P.row_start[v], hi = P.row_start[v + 1];
-        float accx = 0.0f, accy = 0.0f;
-        bool any = false;
-        for (uint32_t e = lo; e < hi && e < P.members; ++e) {
-            const uint2 w = P.inc[e];                                   // (member, loop)
-            if (w.x >= P.members || w.y >= P.k || P.state[w.y] != kAreaActs) continue;
-            const float2 c = P.corr[w.x];
-            accx = accx + c.x;
-            accy = accy + c.y;
-            any = true;
-        }
-        if (!any) continue;
-        const float2 p = pos[slot];
-        float2 o;
-        bond_move(p.x, p.y, radius[slot], accx, accy, P.world_w, P.world_h, &o.x, &o.y);
-        pos[slot] = o;
-    }
-}
-
 // member_slot[i] = node_slot[member_node[i]]: the loop phase gathers through one table
 __global__ __launch_bounds__(kStreamBlock) void k_areas_expand(const uint32_t *__restrict__ member_node,
                                                                const uint32_t *__restrict__ node_slot,
@@ -260,9 +242,9 @@ __global__ __launch_bounds__(kStreamBlock) void k_areas_expand(const uint32_t *_
 
 gpe_status launch_areas_expand(gpe_ctx *c, const AreaState &A)
 {
-    if (A.members == 0 || A.nodes == 0) return GPE_OK;
+    if (A.members == 0 || A.nt.nodes == 0) return GPE_OK;
     hipLaunchKernelGGL(k_areas_expand, dim3(stream_grid(A.members)), dim3(kStreamBlock), 0, c->stream, A.member_node,
-                       A.node_slot, A.member_slot, (uint32_t)A.members, (uint32_t)A.nodes);
+                       A.nt.node_slot, A.member_slot, (uint32_t)A.members, (uint32_t)A.nt.nodes);
     GPE_HIP(c, hipGetLastError());
     return GPE_OK;
 }
@@ -287,7 +269,7 @@ gpe_status launch_areas_pass(gpe_ctx *c, float2 *pos, const float *radius, uint6
     if (n > 0xFFFFFFFFull) return refuse_too_many(c, "areas");
     AreaPassArgs P;
     P.rec = A.rec; P.member_slot = A.member_slot;
-    P.node_slot = A.node_slot; P.row_start = A.row_start; P.inc = A.inc;
+    P.node_slot = A.nt.node_slot; P.row_start = A.nt.row_start; P.inc = A.inc;
     P.corr = A.corr; P.state = A.state; P.value = A.value;
     P.k = k; P.members = (uint32_t)A.members; P.m = m; P.n = (uint32_t)n;
     P.world_w = c->cfg.world_width; P.world_h = c->cfg.world_height;
@@ -305,9 +287,7 @@ gpe_status launch_areas_pass(gpe_ctx *c, float2 *pos, const float *radius, uint6
             default: GPE_TRY(launch_class<64>(c, pos, P)); break;
             }
         }
-        Scope s(c, "areas/node");
-        hipLaunchKernelGGL(k_areas_node, dim3(stream_grid(m)), dim3(kStreamBlock), 0, c->stream, pos, radius, P);
-        GPE_HIP(c, hipGetLastError());
+        GPE_TRY(launch_uid_nodes(c, "areas/node", pos, radius, P));
     }
     return GPE_OK;
 }

@@ -8,18 +8,19 @@
 //     one position and 8 B of anchors), max_length[j] (4 B) only when the set holds a breakable bond.  Writes corr[j]
 //     (8 B) when the bond acts and state[j] (1 B) when it changes: 0 acted, 1 broken, 2 inert in this relaxation.  The
 //     bond's own lane is the only writer of both.  A break adds 1 to the integer counter (atomicAdd: order-free).
-//   - k_bonds_node, one lane per node v (a distinct uid the bonds name).  Reads node_slot[v] (4 B; an absent uid ends
-//     there), row_start[v], row_start[v + 1], then per incidence, in ascending bond index, inc (4 B), state (1 B) and
-//     for an acting bond corr (8 B).  A node with an acting bond reads pos (8 B) and radius (4 B) of its particle and
-//     writes pos (8 B); nothing else is written.  One lane walks a node's whole row (at most GPE_BOND_MAX_DEGREE).
+//   - the node phase, one lane per node v (a distinct uid the bonds name): k_uid_nodes.h's kernel, which asks
+//     BondPassArgs::share.  Per incidence, in ascending bond index, that reads inc (4 B: bond << 1 | side), state (1 B)
+//     and for an acting bond corr (8 B): side a adds the correction, side b its negation.  One lane walks a node's
+//     whole row (at most GPE_BOND_MAX_DEGREE).
 // corr cannot carry the "no correction" mark itself: every binary32 pattern is a possible product, and a correction of
-// zero still counts (its particle is clamped), so the mark is the state byte.  Two nodes never share a particle (the
-// uids of the map are distinct), so no position has two writers.
+// zero still counts (its particle is clamped), so the mark is the state byte.
 // Bonded particles are neighbours in space and the arrays are kept in Morton order: the gathers of a wave mostly hit
-// lines it has fetched already.  No LDS, no float atomics.  Slots are checked against n before they index anything.
+// lines it has fetched already.  No LDS, no float atomics.  Slots are checked against n, indices against the count of
+// their array, before they index anything.
 #include "gpe_internal.h"
 #include "bond_graph.h"
 #include "k_bond.h"
+#include "k_uid_nodes.h"
 
 namespace gpe {
 
@@ -35,6 +36,17 @@ struct BondPassArgs {
     unsigned long long *broken = nullptr;
     uint32_t k = 0, m = 0, n = 0, n_anchors = 0;
     float world_w = 0.f, world_h = 0.f;
+    // the node phase's shares (k_uid_nodes.h): a pair has two incidences, an anchor one
+    __device__ __forceinline__ uint32_t incidences() const { return 2u * k - n_anchors; }
+    template <class Add>
+    __device__ __forceinline__ void share(uint32_t e, Add add) const
+    {
+        const uint32_t w = inc[e];
+        const uint32_t j = w >> 1;
+        if (j >= k || state[j] != kBondActs) return;
+        const float2 c = corr[j];
+        add((w & 1u) ? -c.x : c.x, (w & 1u) ? -c.y : c.y);
+    }
 };
 
 __global__ __launch_bounds__(kStreamBlock) void k_bonds_bond(const float2 *__restrict__ pos, BondPassArgs P)
@@ -63,34 +75,6 @@ __global__ __launch_bounds__(kStreamBlock) void k_bonds_bond(const float2 *__res
     }
 }
 
-__global__ __launch_bounds__(kStreamBlock) void k_bonds_node(float2 *__restrict__ pos, const float *__restrict__ radius,
-                                                             BondPassArgs P)
-{
-#pragma clang fp contract(off)
-    const uint32_t stride = gridDim.x * blockDim.x;
-    for (uint32_t v = blockIdx.x * blockDim.x + threadIdx.x; v < P.m; v += stride) {
-        const uint32_t slot = P.node_slot[v];
-        if (slot >= P.n) continue;
-        const uint32_t lo = P.row_start[v], hi = P.row_start[v + 1];
-        float accx = 0.0f, accy = 0.0f;
-        bool any = false;
-        for (uint32_t e = lo; e < hi; ++e) {
-            const uint32_t w = P.inc[e];
-            const uint32_t j = w >> 1;
-            if (P.state[j] != kBondActs) continue;
-            const float2 c = P.corr[j];
-            accx = accx + ((w & 1u) ? -c.x : c.x);
-            accy = accy + ((w & 1u) ? -c.y : c.y);
-            any = true;
-        }
-        if (!any) continue;
-        const float2 p = pos[slot];
-        float2 o;
-        bond_move(p.x, p.y, radius[slot], accx, accy, P.world_w, P.world_h, &o.x, &o.y);
-        pos[slot] = o;
-    }
-}
-
 // B's tables as gpe_set_bonds uploaded them for k bonds and m nodes (every node index < m, every anchor index <
 // B.n_anchors, every inc entry >> 1 < k), node_slot resolved for the particles as they are.
 gpe_status launch_bonds_pass(gpe_ctx *c, float2 *pos, const float *radius, uint64_t n, const BondState &B, uint32_t k,
@@ -100,7 +84,7 @@ gpe_status launch_bonds_pass(gpe_ctx *c, float2 *pos, const float *radius, uint6
     if (n > 0xFFFFFFFFull) return refuse_too_many(c, "bonds");
     BondPassArgs P;
     P.rec = B.rec; P.max_length = B.max_length; P.anchors = B.anchors;
-    P.node_slot = B.node_slot; P.row_start = B.row_start; P.inc = B.inc;
+    P.node_slot = B.nt.node_slot; P.row_start = B.nt.row_start; P.inc = B.inc;
     P.corr = B.corr; P.state = B.state; P.broken = B.broken;
     P.k = k; P.m = m; P.n = (uint32_t)n; P.n_anchors = B.n_anchors;
     P.world_w = c->cfg.world_width; P.world_h = c->cfg.world_height;
@@ -110,11 +94,7 @@ gpe_status launch_bonds_pass(gpe_ctx *c, float2 *pos, const float *radius, uint6
             hipLaunchKernelGGL(k_bonds_bond, dim3(stream_grid(k)), dim3(kStreamBlock), 0, c->stream, pos, P);
             GPE_HIP(c, hipGetLastError());
         }
-        {
-            Scope s(c, "bonds/node");
-            hipLaunchKernelGGL(k_bonds_node, dim3(stream_grid(m)), dim3(kStreamBlock), 0, c->stream, pos, radius, P);
-            GPE_HIP(c, hipGetLastError());
-        }
+        GPE_TRY(launch_uid_nodes(c, "bonds/node", pos, radius, P));
     }
     return GPE_OK;
 }

@@ -48,7 +48,7 @@ def _calls(code, name):
     for m in re.finditer(r"(?<![\w:])%s\(" % name, code):
         line_start = code.rfind("\n", 0, m.start()) + 1
         head = code[line_start:m.start()]
-        if re.search(r"\b(static|inline|hipError_t|gpe_status)\s+$", head):      # a definition / declaration
+        if re.search(r"\b(static|inline|hipError_t|gpe_status|void)\s+$", head):  # a definition / declaration
             continue
         depth, i = 1, m.end()
         while depth:
@@ -60,13 +60,13 @@ def _calls(code, name):
 
 def test_every_allocation_site_names_a_tag():
     """Every call of an allocating helper (gpe_dev_reserve, dev_reserve, dev_alloc, ws_alloc, a set upload's
-    up.reserve, gpe_edits.hip's edit_buffer, gpe_native.hip's reserve, ensure_words) ends in a tag: a literal of the registry's naming scheme, or an expression made of such literals
+    up.reserve, node_table_upload, gpe_edits.hip's edit_buffer, gpe_native.hip's reserve, ensure_words) ends in a tag: a literal of the registry's naming scheme, or an expression made of such literals
     (a choice between tags), or the tag parameter a wrapper hands on.  No tag is longer than gpe_guard_zone.tag holds."""
     sites, tags = 0, set()
     for path in _sources():
         code = _code(path)
         names = ["gpe_dev_reserve", "dev_reserve", "dev_alloc", "ws_alloc", r"up\.reserve", "edit_buffer", "ensure_words",
-                 "cell_grid_upload", "sweep_mode_set"]             # (the last two hand their tags on to up.reserve)
+                 "cell_grid_upload", "sweep_mode_set", "node_table_upload"]   # (the last three hand their tags on to up.reserve)
         if os.path.basename(path) == "gpe_native.hip":
             names.append("reserve")
         for name in names:
@@ -74,7 +74,8 @@ def test_every_allocation_site_names_a_tag():
                 last = args.rsplit(",", 1)[1].strip() if "," in args else args
                 # (a ?: choice between tags holds no comma; its literals are what counts)
                 found = re.findall(TAG, args.split(",", 3)[-1] if name != "ensure_words" else last)
-                assert found or last in ("tag", "t.tag", "cell_start_tag", "items_tag", "b.second"), (os.path.basename(path), name, args)
+                assert found or last in ("tag", "t.tag", "cell_start_tag", "items_tag", "b.second", "node_uid_tag",
+                                         "node_slot_tag", "row_start_tag"), (os.path.basename(path), name, args)
                 sites += 1
                 tags.update(t.strip('"') for t in found)
     assert sites >= 127, sites
@@ -129,6 +130,15 @@ def test_every_workspace_releases_exactly_what_it_reserves():
 
 
 # ---- the hand-kept pairing of the uid map's validity and the tracers' slot table --------------------------------------
+STALE_TABLES = ("tracers", "bonds.nt", "bends.nt", "areas.nt", "bodies")      # what keeps storage slots by uid
+
+
+def marks_every_slot_table(helper_body):
+    """The body of uid_slots_stale sets c->X.stale of every table of STALE_TABLES, and sets them true."""
+    return (all(re.search(r"c->%s\.stale\s*=" % re.escape(s), helper_body) for s in STALE_TABLES)
+            and bool(re.search(r"=\s*true;\s*$", helper_body)))
+
+
 def _statements(code):
     """(statement, the statement after it) of a source without comments: split at ';', braces dropped, blanks folded."""
     parts = [" ".join(p.replace("{", " ").replace("}", " ").split()) for p in code.split(";")]
@@ -157,11 +167,16 @@ def unpaired_map_invalidations(csrc=CSRC):
 def test_every_map_invalidation_marks_the_tracers_slot_table_stale():
     """Every `map_valid = false` outside uid_map_build, and the one `map_valid = true` outside uid_map_ready
     (gpe_set_uids, whose map is that of new uids), is followed at once by `uid_slots_stale(c)`, which sets the stale flag
-    of the tracers, the bonds and the bodies.  Deleting any one of those lines from a copy of the sources makes
-    unpaired_map_invalidations() name the site (tried with each in turn)."""
+    of all five slot tables: the tracers', the bonds', the bends' and the areas' node tables and the bodies' members.
+    Deleting any one of those lines from a copy of the sources makes unpaired_map_invalidations() name the site (tried
+    with each in turn), and a copy of the helper with any one of the five flags dropped fails the check here (tried
+    below, with each in turn)."""
     helper = re.search(r"inline void uid_slots_stale\(gpe_ctx \*c\) \{([^}]*)\}", _code(os.path.join(CSRC, "gpe_internal.h")))
-    assert helper and all(re.search(r"c->%s\.stale\b" % s, helper.group(1)) for s in ("tracers", "bonds", "bodies"))
-    assert re.search(r"=\s*true;\s*$", helper.group(1)), helper.group(1)
+    assert helper and marks_every_slot_table(helper.group(1)), helper
+    for s in STALE_TABLES:
+        without = helper.group(1).replace("c->%s.stale = " % s, "")
+        assert without != helper.group(1) and not marks_every_slot_table(without), s
+    assert not marks_every_slot_table(helper.group(1).replace("true", "false"))
     bad, sites = unpaired_map_invalidations()
     assert not bad, bad
     assert sites >= 8, sites                # (seven clear it, gpe_set_uids sets it; gpe_tracers_begin's own stale = true has no pair)

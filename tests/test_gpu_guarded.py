@@ -268,6 +268,13 @@ def _step_set_case(gpe, st, feature):
     def bodies(k):
         return st.bodies_from_groups([[16 * g, 16 * g + 1, 16 * g + 8, 16 * g + 9] for g in range(k)])
 
+    def hinges(k):                                         # particles 4 g, 4 g + 1, 4 g + 2 of the first two rows: straight
+        g = 4 * np.arange(k)
+        return gpe.bends_from_angles(g, g + 1, g + 2, np.pi, 0.5)
+
+    def triangles(k):                                      # (g, g + 1, g + 8): neighbours share two uids
+        return st.areas_from_loops([[g, g + 1, g + 8] for g in range(k)], stiffness=0.5)
+
     def surfaces_of(target, obstacles):
         def set_(k):
             obstacles(k)                                   # (a new set drops its surfaces: the rows are always new ones)
@@ -289,6 +296,8 @@ def _step_set_case(gpe, st, feature):
         "movers": (set_pistons, st.clear_movers, lambda t: t.startswith("grid.mover_"), set()),
         "bonds": (lambda k: st.set_bonds(gpe.pair_bonds(2 * np.arange(k), 2 * np.arange(k) + 1, 3.0)), st.clear_bonds,
                   lambda t: t.startswith("uid.bond_"), set()),
+        "bends": (lambda k: st.set_bends(hinges(k)), st.clear_bends, lambda t: t.startswith("uid.bend_"), set()),
+        "areas": (lambda k: st.set_areas(*triangles(k)), st.clear_areas, lambda t: t.startswith("uid.area_"), set()),
         "bodies": (lambda k: st.set_bodies(*bodies(k)), st.clear_bodies, lambda t: t.startswith("uid.body_"), set()),
         "surfaces-of-colliders": (surfaces_of("colliders", set_walls), lambda: st.clear_surfaces("colliders"),
                                   lambda t: t == "grid.collider_surf", set()),
@@ -302,8 +311,8 @@ def _step_set_case(gpe, st, feature):
     }[feature]
 
 
-@pytest.mark.parametrize("feature", ["colliders", "fields", "movers", "bonds", "bodies", "surfaces-of-colliders",
-                                     "surfaces-of-movers", "collider-sweep", "mover-sweep"])
+@pytest.mark.parametrize("feature", ["colliders", "fields", "movers", "bonds", "bends", "areas", "bodies",
+                                     "surfaces-of-colliders", "surfaces-of-movers", "collider-sweep", "mover-sweep"])
 def test_replacing_a_step_set_leaks_nothing_and_frees_nothing_twice(gpe, feature):
     """64 particles with uids on, guarded.  The set with k = 1, a step, replaced with k = 3, a step, with k = 1 again, a
     step, cleared: after every call guard_check() reports no damage and no tag of the feature is live more than once
