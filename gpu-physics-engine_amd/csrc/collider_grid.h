@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "k_collider.h"
+#include "lookup_grid.h"
 
 namespace gpe {
 
@@ -29,12 +30,7 @@ constexpr double kColliderFarCells = 131072.0;                 // 2^17: past thi
 
 struct ColliderCapsule { float ax, ay, bx, by, radius; };
 
-struct ColliderGrid {
-    ColliderGridView view;                 // what the pass is handed
-    double cell = 1.0;                     // the exact cell size: 1 / (double)view.inv_cell (one cell: unused)
-    std::vector<uint32_t> cell_start;      // gx * gy + 1
-    std::vector<uint32_t> items;
-};
+using ColliderGrid = LookupGrid;
 
 inline double collider_point_segment_distance(double px, double py, double ax, double ay, double bx, double by)
 {
@@ -73,120 +69,58 @@ inline bool collider_row_span(const ColliderCapsule &c, double cell, double reac
     return *x0 <= *x1;
 }
 
-// One attempt at a resolution.  false: more than max_entries entries (the grid is left unusable).
-inline bool collider_grid_fill(ColliderGrid &g, const ColliderCapsule *cs, uint32_t k, double rb, uint64_t max_entries)
-{
-    const uint32_t gx = g.view.gx, gy = g.view.gy;
-    const uint64_t cells = (uint64_t)gx * gy;
-    const double cell = g.cell, half_diag = cell * 0.70710678118654757;
-    std::vector<uint8_t> far(k, 0);
-    std::vector<uint32_t> row0(k, 1), row1(k, 0);              // the rows a near collider can reach (empty: none)
-    for (uint32_t j = 0; j < k; ++j) {
-        const ColliderCapsule &c = cs[j];
-        const double m = std::max(std::max(fabs((double)c.ax), fabs((double)c.ay)), std::max(fabs((double)c.bx), fabs((double)c.by)));
-        if (!(m + c.radius + rb <= kColliderFarCells * cell)) { far[j] = 1; continue; }
-        const double reach = (double)c.radius + rb + cell + half_diag + 0.01 * cell;
-        const double ylo = std::min((double)c.ay, (double)c.by) - reach, yhi = std::max((double)c.ay, (double)c.by) + reach;
-        if (yhi < 0.0 || ylo >= (double)gy * cell) continue;
-        const double r0 = floor(ylo / cell), r1 = floor(yhi / cell);
-        row0[j] = r0 > 0.0 ? (uint32_t)r0 : 0u;
-        row1[j] = r1 < (double)(gy - 1) ? (uint32_t)r1 : gy - 1;
-    }
-    // two sweeps over the same candidates: count, then fill.  Collider by collider, so every cell's list ascends
-    g.cell_start.assign(cells + 1, 0);
-    g.items.clear();
-    for (int sweep = 0; sweep < 2; ++sweep) {
-        uint64_t total = 0;
-        for (uint32_t j = 0; j < k; ++j) {
-            const ColliderCapsule &c = cs[j];
-            if (far[j]) {
-                total += cells;
-                if (sweep == 0 && total > max_entries) return false;
-                for (uint64_t cell_i = 0; cell_i < cells; ++cell_i) {
-                    if (sweep == 0) g.cell_start[cell_i + 1] += 1;
-                    else g.items[g.cell_start[cell_i]++] = j;
-                }
-                continue;
-            }
-            const double keep = (double)c.radius + rb + cell + half_diag;
-            for (uint32_t cy = row0[j]; cy <= row1[j] && row0[j] <= row1[j]; ++cy) {
-                uint32_t x0, x1;
-                if (!collider_row_span(c, cell, keep + 0.01 * cell, cy, gx, &x0, &x1)) continue;
-                for (uint32_t cx = x0; cx <= x1; ++cx) {
-                    const double d = collider_point_segment_distance(((double)cx + 0.5) * cell, ((double)cy + 0.5) * cell,
-                                                                     c.ax, c.ay, c.bx, c.by);
-                    if (!(d <= keep)) continue;
-                    const uint64_t cell_i = (uint64_t)cy * gx + cx;
-                    total += 1;
-                    if (sweep == 0) {
-                        if (total > max_entries) return false;
-                        g.cell_start[cell_i + 1] += 1;
-                    } else {
-                        g.items[g.cell_start[cell_i]++] = j;
-                    }
-                }
-            }
-        }
-        if (sweep == 0) {
-            // counts -> starts; the fill advances cell_start[i] to the end of cell i, which is the start of cell i + 1:
-            // shifting by one afterwards restores it
-            for (uint64_t i = 0; i < cells; ++i) g.cell_start[i + 1] += g.cell_start[i];
-            g.items.assign((size_t)total, 0);
-        }
-    }
-    for (uint64_t i = cells; i > 0; --i) g.cell_start[i] = g.cell_start[i - 1];
-    g.cell_start[0] = 0;
-    return true;
-}
-
-// The grid of one cell: every collider, whatever the world and rb are.
-// extent: the size of the cell, twice the world's (0: there is no usable world).
-inline void collider_grid_one_cell(ColliderGrid &g, uint32_t k, float rb, double extent)
-{
-    g.view = ColliderGridView();
-    g.view.rb = rb;
-    const float cell = (float)extent;
-    const float inv = 1.0f / cell;
-    // anything but a cell with a normal reciprocal leaves inv_cell = 0: every finite p lands in the cell, every other
-    // one walks all colliders, which is the same list
-    if (extent > 0.0 && isfinite(cell) && isfinite(inv) && inv >= 1e-30f) g.view.inv_cell = inv;
-    g.cell = g.view.inv_cell > 0.0f ? 1.0 / (double)g.view.inv_cell : 1.0;
-    g.cell_start.assign(2, 0);
-    g.cell_start[1] = k;
-    g.items.resize(k);
-    for (uint32_t j = 0; j < k; ++j) g.items[j] = j;
-}
+// what a collider can reach at one resolution
+struct ColliderSpan {
+    uint8_t far = 0;                       // listed in every cell
+    uint32_t row0 = 1, row1 = 0;           // the rows a near collider can reach (row0 > row1: none)
+};
 
 // The grid for k <= GPE_COLLIDERS_MAX validated colliders (finite coordinates, finite radius >= 0), the radius bound
 // rb = |gpe_max_radius| and the world W x H, all as the context holds them (rb, W and H may be anything).  The
-// resolution: cells of max(4 rb, max(W, H) / 1024), doubled until items[] holds at most max_entries entries.
+// resolution: cells of max(4 rb, max(W, H) / 1024), doubled until items[] holds at most max_entries entries
+// (lookup_grid.h).
 inline ColliderGrid collider_grid_build(const ColliderCapsule *cs, uint32_t k, float rb_in, float W, float H,
                                         uint64_t max_entries = kColliderGridMaxEntries)
 {
-    ColliderGrid g;
-    const float rb = fabsf(rb_in);
-    const double w = W, h = H, world = std::max(w, h);
-    if (!(w > 0.0 && h > 0.0 && isfinite(world) && isfinite(rb) && world >= 1e-20 && world <= 1e20)) {
-        collider_grid_one_cell(g, k, rb, world > 0.0 && isfinite(world) ? world * 2.0 : 0.0);
-        return g;
-    }
-    double want = std::max(4.0 * (double)rb, world / 1024.0);
-    for (;; want *= 2.0) {
-        // the pass multiplies by a binary32 reciprocal: the cell IS 1 / that number
-        const float inv = 1.0f / (float)want;
-        const double cell = 1.0 / (double)inv;
-        const double nx = floor(w / cell) + 1.0, ny = floor(h / cell) + 1.0;      // W and H lie strictly inside the grid
-        if (nx <= 1.0 && ny <= 1.0) break;
-        if (nx > (double)kColliderGridMaxDim || ny > (double)kColliderGridMaxDim) continue;
-        g.view.inv_cell = inv;
-        g.view.gx = (uint32_t)nx; g.view.gy = (uint32_t)ny;
-        g.view.gxf = (float)g.view.gx; g.view.gyf = (float)g.view.gy;
-        g.view.rb = rb;
-        g.cell = cell;
-        if (collider_grid_fill(g, cs, k, rb, max_entries)) return g;
-    }
-    collider_grid_one_cell(g, k, rb, world * 2.0);
-    return g;
+    const float rbf = fabsf(rb_in);
+    const double rb = rbf;
+    std::vector<ColliderSpan> span(k);
+    uint32_t gx = 1, gy = 1;
+    double cell = 1.0, half_diag = 0.0;
+    auto prepare = [&](const LookupView &v) {
+        gx = v.view.gx; gy = v.view.gy;
+        cell = v.cell; half_diag = cell * 0.70710678118654757;
+        for (uint32_t j = 0; j < k; ++j) {
+            const ColliderCapsule &c = cs[j];
+            ColliderSpan &s = span[j] = ColliderSpan();
+            const double m = std::max(std::max(fabs((double)c.ax), fabs((double)c.ay)), std::max(fabs((double)c.bx), fabs((double)c.by)));
+            if (!(m + c.radius + rb <= kColliderFarCells * cell)) { s.far = 1; continue; }
+            const double reach = (double)c.radius + rb + cell + half_diag + 0.01 * cell;
+            const double ylo = std::min((double)c.ay, (double)c.by) - reach, yhi = std::max((double)c.ay, (double)c.by) + reach;
+            if (yhi < 0.0 || ylo >= (double)gy * cell) continue;
+            const double r0 = floor(ylo / cell), r1 = floor(yhi / cell);
+            s.row0 = r0 > 0.0 ? (uint32_t)r0 : 0u;
+            s.row1 = r1 < (double)(gy - 1) ? (uint32_t)r1 : gy - 1;
+        }
+    };
+    auto cells_of = [&](uint32_t j, auto emit) {
+        const ColliderCapsule &c = cs[j];
+        const ColliderSpan &s = span[j];
+        if (s.far) { emit(0, (uint64_t)gx * gy - 1); return; }
+        const double keep = (double)c.radius + rb + cell + half_diag;
+        for (uint32_t cy = s.row0; cy <= s.row1 && s.row0 <= s.row1; ++cy) {
+            uint32_t x0, x1;
+            if (!collider_row_span(c, cell, keep + 0.01 * cell, cy, gx, &x0, &x1)) continue;
+            for (uint32_t cx = x0; cx <= x1; ++cx) {
+                const double d = collider_point_segment_distance(((double)cx + 0.5) * cell, ((double)cy + 0.5) * cell,
+                                                                 c.ax, c.ay, c.bx, c.by);
+                if (!(d <= keep)) continue;
+                const uint64_t cell_i = (uint64_t)cy * gx + cx;
+                if (!emit(cell_i, cell_i)) return;
+            }
+        }
+    };
+    return lookup_grid_build(k, rbf, W, H, kColliderGridMaxDim, 1e-20, max_entries, prepare, cells_of);
 }
 
 }  // namespace gpe

@@ -24,6 +24,7 @@
 
 #include "k_collider.h"
 #include "k_field.h"
+#include "lookup_grid.h"
 
 namespace gpe {
 
@@ -32,12 +33,7 @@ constexpr double kFieldFarCells = 131072.0;                    // 2^17: past thi
 
 struct FieldRegion { uint32_t shape; float x0, y0, x1, y1; };
 
-struct FieldGrid {
-    ColliderGridView view;                 // what the pass is handed (rb unused: 0)
-    double cell = 1.0;                     // the exact cell size: 1 / (double)view.inv_cell (one cell: unused)
-    std::vector<uint32_t> cell_start;      // gx * gy + 1
-    std::vector<uint32_t> items;
-};
+using FieldGrid = LookupGrid;              // (view.rb unused: 0)
 
 // what a field covers at one resolution
 struct FieldSpan {
@@ -67,116 +63,48 @@ inline bool field_circle_row(const FieldRegion &f, double cell, uint32_t cy, uin
     return field_cells_of((double)f.x0 - hw, (double)f.x0 + hw, cell, gx, c0, c1);
 }
 
-// One attempt at a resolution.  false: more than max_entries entries (the grid is left unusable).
-inline bool field_grid_fill(FieldGrid &g, const FieldRegion *fs, uint32_t k, uint64_t max_entries)
-{
-    const uint32_t gx = g.view.gx, gy = g.view.gy;
-    const uint64_t cells = (uint64_t)gx * gy;
-    const double cell = g.cell;
-    std::vector<FieldSpan> span(k);
-    for (uint32_t j = 0; j < k; ++j) {
-        const FieldRegion &f = fs[j];
-        FieldSpan &s = span[j];
-        if (f.shape == kFieldEverywhere) { s.everywhere = 1; continue; }
-        if (f.shape == kFieldBox && (f.x0 > f.x1 || f.y0 > f.y1)) continue;            // accepts nothing
-        const double m = f.shape == kFieldCircle ? fabs((double)f.x0) + fabs((double)f.y0) + fabs((double)f.x1)
-                                                 : std::max(std::max(fabs((double)f.x0), fabs((double)f.y0)),
-                                                            std::max(fabs((double)f.x1), fabs((double)f.y1)));
-        if (!(m <= kFieldFarCells * cell)) { s.everywhere = 1; continue; }
-        const double pad = 1.01 * cell;
-        if (f.shape == kFieldCircle) {
-            const double R = (double)f.x1 + pad;
-            if (!field_cells_of((double)f.y0 - R, (double)f.y0 + R, cell, gy, &s.row0, &s.row1)) { s.row0 = 1; s.row1 = 0; }
-        } else {
-            if (!field_cells_of((double)f.y0 - pad, (double)f.y1 + pad, cell, gy, &s.row0, &s.row1) ||
-                !field_cells_of((double)f.x0 - pad, (double)f.x1 + pad, cell, gx, &s.col0, &s.col1)) { s.row0 = 1; s.row1 = 0; }
-        }
-    }
-    // two sweeps over the same candidates: count, then fill.  Field by field, so every cell's list ascends
-    g.cell_start.assign(cells + 1, 0);
-    g.items.clear();
-    for (int sweep = 0; sweep < 2; ++sweep) {
-        uint64_t total = 0;
-        for (uint32_t j = 0; j < k; ++j) {
-            const FieldSpan &s = span[j];
-            if (s.everywhere) {
-                total += cells;
-                if (sweep == 0 && total > max_entries) return false;
-                for (uint64_t cell_i = 0; cell_i < cells; ++cell_i) {
-                    if (sweep == 0) g.cell_start[cell_i + 1] += 1;
-                    else g.items[g.cell_start[cell_i]++] = j;
-                }
-                continue;
-            }
-            for (uint32_t cy = s.row0; cy <= s.row1 && s.row0 <= s.row1; ++cy) {
-                uint32_t c0 = s.col0, c1 = s.col1;
-                if (fs[j].shape == kFieldCircle && !field_circle_row(fs[j], cell, cy, gx, &c0, &c1)) continue;
-                total += (uint64_t)(c1 - c0) + 1;
-                if (sweep == 0 && total > max_entries) return false;
-                for (uint32_t cx = c0; cx <= c1; ++cx) {
-                    const uint64_t cell_i = (uint64_t)cy * gx + cx;
-                    if (sweep == 0) g.cell_start[cell_i + 1] += 1;
-                    else g.items[g.cell_start[cell_i]++] = j;
-                }
-            }
-        }
-        if (sweep == 0) {
-            // counts -> starts; the fill advances cell_start[i] to the end of cell i, which is the start of cell i + 1:
-            // shifting by one afterwards restores it
-            for (uint64_t i = 0; i < cells; ++i) g.cell_start[i + 1] += g.cell_start[i];
-            g.items.assign((size_t)total, 0);
-        }
-    }
-    for (uint64_t i = cells; i > 0; --i) g.cell_start[i] = g.cell_start[i - 1];
-    g.cell_start[0] = 0;
-    return true;
-}
-
-// The grid of one cell: every field, whatever the world is.
-// extent: the size of the cell, twice the world's (0: there is no usable world).
-inline void field_grid_one_cell(FieldGrid &g, uint32_t k, double extent)
-{
-    g.view = ColliderGridView();
-    const float cell = (float)extent;
-    const float inv = 1.0f / cell;
-    // anything but a cell with a normal reciprocal leaves inv_cell = 0: every finite p lands in the cell, every other
-    // one walks all fields, which is the same list
-    if (extent > 0.0 && isfinite(cell) && isfinite(inv) && inv >= 1e-30f) g.view.inv_cell = inv;
-    g.cell = g.view.inv_cell > 0.0f ? 1.0 / (double)g.view.inv_cell : 1.0;
-    g.cell_start.assign(2, 0);
-    g.cell_start[1] = k;
-    g.items.resize(k);
-    for (uint32_t j = 0; j < k; ++j) g.items[j] = j;
-}
-
 // The grid for k <= GPE_FIELDS_MAX validated fields (finite coordinates, a circle's radius >= 0) and the world W x H
 // as the context holds it (W and H may be anything).  The resolution: cells of max(W, H) / 1024, doubled until items[]
-// holds at most max_entries entries.  A world outside [1e-6, 1e20] gets the one cell.
+// holds at most max_entries entries (lookup_grid.h, with a radius bound of 0).  A world outside [1e-6, 1e20] gets the
+// one cell.
 inline FieldGrid field_grid_build(const FieldRegion *fs, uint32_t k, float W, float H,
                                   uint64_t max_entries = kFieldGridMaxEntries)
 {
-    FieldGrid g;
-    const double w = W, h = H, world = std::max(w, h);
-    if (!(w > 0.0 && h > 0.0 && isfinite(world) && world >= 1e-6 && world <= 1e20)) {
-        field_grid_one_cell(g, k, world > 0.0 && isfinite(world) ? world * 2.0 : 0.0);
-        return g;
-    }
-    for (double want = world / 1024.0;; want *= 2.0) {
-        // the pass multiplies by a binary32 reciprocal: the cell IS 1 / that number
-        const float inv = 1.0f / (float)want;
-        const double cell = 1.0 / (double)inv;
-        const double nx = floor(w / cell) + 1.0, ny = floor(h / cell) + 1.0;      // W and H lie strictly inside the grid
-        if (nx <= 1.0 && ny <= 1.0) break;
-        if (nx > (double)kColliderGridMaxDim || ny > (double)kColliderGridMaxDim) continue;
-        g.view = ColliderGridView();
-        g.view.inv_cell = inv;
-        g.view.gx = (uint32_t)nx; g.view.gy = (uint32_t)ny;
-        g.view.gxf = (float)g.view.gx; g.view.gyf = (float)g.view.gy;
-        g.cell = cell;
-        if (field_grid_fill(g, fs, k, max_entries)) return g;
-    }
-    field_grid_one_cell(g, k, world * 2.0);
-    return g;
+    std::vector<FieldSpan> span(k);
+    uint32_t gx = 1, gy = 1;
+    double cell = 1.0;
+    auto prepare = [&](const LookupView &v) {
+        gx = v.view.gx; gy = v.view.gy;
+        cell = v.cell;
+        for (uint32_t j = 0; j < k; ++j) {
+            const FieldRegion &f = fs[j];
+            FieldSpan &s = span[j] = FieldSpan();
+            if (f.shape == kFieldEverywhere) { s.everywhere = 1; continue; }
+            if (f.shape == kFieldBox && (f.x0 > f.x1 || f.y0 > f.y1)) continue;            // accepts nothing
+            const double m = f.shape == kFieldCircle ? fabs((double)f.x0) + fabs((double)f.y0) + fabs((double)f.x1)
+                                                     : std::max(std::max(fabs((double)f.x0), fabs((double)f.y0)),
+                                                                std::max(fabs((double)f.x1), fabs((double)f.y1)));
+            if (!(m <= kFieldFarCells * cell)) { s.everywhere = 1; continue; }
+            const double pad = 1.01 * cell;
+            if (f.shape == kFieldCircle) {
+                const double R = (double)f.x1 + pad;
+                if (!field_cells_of((double)f.y0 - R, (double)f.y0 + R, cell, gy, &s.row0, &s.row1)) { s.row0 = 1; s.row1 = 0; }
+            } else {
+                if (!field_cells_of((double)f.y0 - pad, (double)f.y1 + pad, cell, gy, &s.row0, &s.row1) ||
+                    !field_cells_of((double)f.x0 - pad, (double)f.x1 + pad, cell, gx, &s.col0, &s.col1)) { s.row0 = 1; s.row1 = 0; }
+            }
+        }
+    };
+    auto cells_of = [&](uint32_t j, auto emit) {
+        const FieldSpan &s = span[j];
+        if (s.everywhere) { emit(0, (uint64_t)gx * gy - 1); return; }
+        for (uint32_t cy = s.row0; cy <= s.row1 && s.row0 <= s.row1; ++cy) {
+            uint32_t c0 = s.col0, c1 = s.col1;
+            if (fs[j].shape == kFieldCircle && !field_circle_row(fs[j], cell, cy, gx, &c0, &c1)) continue;
+            if (!emit((uint64_t)cy * gx + c0, (uint64_t)cy * gx + c1)) return;
+        }
+    };
+    return lookup_grid_build(k, 0.0f, W, H, kColliderGridMaxDim, 1e-6, max_entries, prepare, cells_of);
 }
 
 }  // namespace gpe

@@ -10,13 +10,6 @@
 
 using namespace gpe;               // (the entry points take their C linkage from their declarations in include/gpe.h)
 
-static uint32_t bits_of(float f)
-{
-    uint32_t u;
-    memcpy(&u, &f, sizeof(u));
-    return u;
-}
-
 void gpe::cell_grid_release(gpe_ctx *c, CellListGrid &G)
 {
     dev_free(c, G.cell_start); dev_free(c, G.items);

@@ -16,13 +16,6 @@ static_assert(kFieldEverywhere == GPE_FIELD_EVERYWHERE && kFieldCircle == GPE_FI
               kFieldDrag == GPE_FIELD_DRAG && kFalloffNone == GPE_FALLOFF_NONE && kFalloffLinear == GPE_FALLOFF_LINEAR,
               "k_field.h restates the enums of include/gpe.h");
 
-static uint32_t bits_of(float f)
-{
-    uint32_t u;
-    memcpy(&u, &f, sizeof(u));
-    return u;
-}
-
 void gpe::fields_release(gpe_ctx *c)
 {
     FieldState &S = c->fields;

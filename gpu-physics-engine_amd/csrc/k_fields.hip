@@ -2,14 +2,16 @@
 // summed and their drags multiplied in ascending field index, then prev rewritten (k_field.h says what a field
 // contributes and how the sum is applied).  pos is only read.
 //
-// A streaming pass shaped like k_colliders_pass: two particles per lane, so pos is read 16 B per lane.  The common lane
+// A streaming pass over the pair loop of k_stream_pairs.h, called from the kernel function itself.  The common lane
 // finds an empty list: it has read its pos and two words of cell_start per particle and is done -- no prev load, no
 // store.  prev is loaded only under a non-empty list and stored only for a particle some field matched.  The fields
 // are 48-byte records (three float4: region | pole, uniform | strength, reach, rr, code): 4096 of them are 192 KB and
 // stay in an XCD's L2; cell_start is read at the particles' own locality (they are kept in Morton order).  A particle
 // outside the grid or with a NaN coordinate walks all k fields: no result rests on the grid.
 #include "gpe_internal.h"
+#include "k_capsule_pass.h"
 #include "k_field.h"
+#include "k_stream_pairs.h"
 
 namespace gpe {
 
@@ -47,17 +49,17 @@ __device__ __forceinline__ bool field_resolve(const FieldPassArgs &P, const floa
 #pragma clang fp contract(off)
     uint32_t cell = 0, lo = 0, hi = 0;
     const bool in_grid = collider_cell_of(P.view, cx, cy, &cell);
+    const CsrCellLookup L{P.cell_start, P.items};
     if (in_grid) {
-        lo = P.cell_start[cell];
-        hi = P.cell_start[cell + 1];
-        if (lo == hi) return false;
+        if (L.empty(cell, lo, hi)) return false;
     }
     q = prev[i];                                               // in flight while the list is walked
     FieldSum sum;
+    auto attempt = [&](uint32_t j) { field_try(P, j, cx, cy, sum); };
     if (!in_grid) {
-        for (uint32_t j = 0; j < P.k; ++j) field_try(P, j, cx, cy, sum);
+        for (uint32_t j = 0; j < P.k; ++j) attempt(j);
     } else {
-        for (uint32_t e = lo; e < hi; ++e) field_try(P, P.items[e], cx, cy, sum);
+        L.each(cell, lo, hi, attempt);
     }
     return field_finish(sum, P.dt2, cx, cy, &q.x, &q.y);
 }
@@ -65,30 +67,17 @@ __device__ __forceinline__ bool field_resolve(const FieldPassArgs &P, const floa
 __global__ __launch_bounds__(kStreamBlock) void k_fields_pass(const float2 *__restrict__ pos, float2 *__restrict__ prev,
                                                               uint64_t n, FieldPassArgs P)
 {
-    const uint64_t pairs = n >> 1;
-    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    const float4 *pos4 = reinterpret_cast<const float4 *>(pos);
-    // particles this wave touched: wave-uniform among the lanes still in the loop.  Lane 0 holds the wave's lowest
-    // index, leaves the loop last and so has seen every vote
-    uint32_t touched = 0;
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < pairs; i += stride) {
-        const float4 c = pos4[i];
-        float2 q0, q1;
-        const bool t0 = field_resolve(P, prev, 2 * i, c.x, c.y, q0);
-        const bool t1 = field_resolve(P, prev, 2 * i + 1, c.z, c.w, q1);
-        if (t0) prev[2 * i] = q0;
-        if (t1) prev[2 * i + 1] = q1;
-        touched += (uint32_t)__popcll(ballot64(t0)) + (uint32_t)__popcll(ballot64(t1));
-    }
-    if ((n & 1ull) && blockIdx.x == 0 && threadIdx.x == 0) {
-        const uint64_t i = n - 1;
-        const float2 c = pos[i];
-        float2 q;
-        if (field_resolve(P, prev, i, c.x, c.y, q)) {
-            prev[i] = q;
-            touched += 1;
-        }
-    }
+    const PairCounts<1> count = stream_pairs<1, false>(
+        pos, nullptr, n,
+        [&](uint64_t i, float cx, float cy, float, float, float4 &o) -> bool {
+            float2 q;
+            const bool hit = field_resolve(P, prev, i, cx, cy, q);
+            o.x = q.x;
+            o.y = q.y;
+            return hit;
+        },
+        [&](uint64_t i, bool, const float4 &o, float, float, float, float) { prev[i] = make_float2(o.x, o.y); });
+    const uint32_t touched = count.of[0];
     // the waves' totals folded through LDS: one integer atomic per workgroup that touched anything (as k_kick counts;
     // one per wave, all on one word, cost more than the pass itself where every wave touches something)
     __shared__ uint32_t s_touched[kStreamBlock / kWave];

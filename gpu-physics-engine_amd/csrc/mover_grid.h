@@ -15,6 +15,7 @@
 #include "../../include/gpe.h"
 #include "k_mover.h"
 #include "k_mover_sweep.h"
+#include "lookup_grid.h"
 
 namespace gpe {
 
@@ -87,44 +88,26 @@ inline const char *mover_dt_refusal(const MoverLimits &L, float dt)
     return nullptr;
 }
 
-// The grid of one cell: every mover, whatever the world and rb are (collider_grid_one_cell's rule).
+// The grid of one cell: every mover, whatever the world and rb are (lookup_grid.h).
 inline MoverGridView mover_grid_one_cell(float rb, double extent)
 {
+    const LookupView v = lookup_grid_one_cell(rb, extent);
     MoverGridView g;
-    g.view.rb = rb;
-    const float cell = (float)extent;
-    const float inv = 1.0f / cell;
-    if (extent > 0.0 && isfinite(cell) && isfinite(inv) && inv >= 1e-30f) g.view.inv_cell = inv;
-    g.cell = g.view.inv_cell > 0.0f ? 1.0 / (double)g.view.inv_cell : 1.0;
+    g.view = v.view;
+    g.cell = v.cell;
     return g;
 }
 
 // The view for the radius bound rb = |gpe_max_radius| and the world W x H, all as the context holds them (anything
-// goes).  The arithmetic of collider_grid_build with at most kMoverGridMaxDim cells per axis: cells of
-// max(4 rb, max(W, H) / 128), doubled until both axes fit.  A mask has no capacity, so the first fit is taken.
+// goes).  The chooser of lookup_grid.h with at most kMoverGridMaxDim cells per axis: cells of max(4 rb, max(W, H) / 128),
+// doubled until both axes fit.  A mask has no capacity, so the first fit is taken.
 inline MoverGridView mover_grid_choose(float rb_in, float W, float H)
 {
-    const float rb = fabsf(rb_in);
-    const double w = W, h = H, world = std::max(w, h);
-    if (!(w > 0.0 && h > 0.0 && isfinite(world) && isfinite(rb) && world >= 1e-20 && world <= 1e20))
-        return mover_grid_one_cell(rb, world > 0.0 && isfinite(world) ? world * 2.0 : 0.0);
-    double want = std::max(4.0 * (double)rb, world / (double)kMoverGridMaxDim);
-    for (;; want *= 2.0) {
-        // the pass multiplies by a binary32 reciprocal: the cell IS 1 / that number
-        const float inv = 1.0f / (float)want;
-        const double cell = 1.0 / (double)inv;
-        const double nx = floor(w / cell) + 1.0, ny = floor(h / cell) + 1.0;      // W and H lie strictly inside the grid
-        if (nx <= 1.0 && ny <= 1.0) break;
-        if (nx > (double)kMoverGridMaxDim || ny > (double)kMoverGridMaxDim) continue;
-        MoverGridView g;
-        g.view.inv_cell = inv;
-        g.view.gx = (uint32_t)nx; g.view.gy = (uint32_t)ny;
-        g.view.gxf = (float)g.view.gx; g.view.gyf = (float)g.view.gy;
-        g.view.rb = rb;
-        g.cell = cell;
-        return g;
-    }
-    return mover_grid_one_cell(rb, world * 2.0);
+    const LookupView v = lookup_grid_choose(fabsf(rb_in), W, H, kMoverGridMaxDim, 1e-20, [](const LookupView &) { return true; });
+    MoverGridView g;
+    g.view = v.view;
+    g.cell = v.cell;
+    return g;
 }
 
 inline uint32_t mover_mask_words(uint32_t k) { return (k + 63u) / 64u; }

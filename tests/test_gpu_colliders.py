@@ -107,6 +107,7 @@ def _scene_particles(n, cs, seed):
         u = rng.random(m)[:, None]
         on = cs[j, 0:2] + u * (cs[j, 2:4] - cs[j, 0:2])
         pos[:m] = (on + rng.uniform(-1.1, 1.1, (m, 2)) * (cs[j, 4] + 0.5)[:, None]).astype(F32)
+    if n >= 2000:                                                      # (the fixed rows below need 1955; a smaller n is all near surfaces)
         # exactly on axes (u = 0.25, 0.5, 0.75 and the end points), on discs' centres, on cell borders (cells of 2.0)
         k = 0
         for c in cs[30:37]:
@@ -127,16 +128,17 @@ def _scene_particles(n, cs, seed):
         pos[m + k + 407] = (-0.0, 150.0)
         rad[m + k + 410:m + k + 420] = -0.5                            # negative radii
         pos[m + k + 410:m + k + 420] = pos[:10] + F32(0.25)
-    else:
+    if n == 1:
         pos[0] = (100.0, 103.0)                                        # inside the disc
     return pos, rad
 
 
 @pytest.mark.parametrize("mode", ["native", "compat"])
-@pytest.mark.parametrize("n", [4000, 3999, 1])
+@pytest.mark.parametrize("n", [4000, 3999, 1, 2, 3, 511, 512, 513])
 def test_one_pass_equals_the_model(gpe, n, mode):
     """apply_colliders() alone on ~40 colliders: pos bit for bit as the model, prev and radius untouched, pushed the
-    model's count.  Even n, odd n (the single-particle tail) and the tail alone; then a radius above the grid's bound
+    model's count.  Even n, odd n (the single-particle tail) and the tail alone; the edges of the pair loop (one pair
+    without and with the tail, one workgroup of pairs less one, exactly one, one and the tail); then a radius above the grid's bound
     (a particle of radius -3 added afterwards: max_radius keeps 0.5), which takes the walk over every collider."""
     cs = _scene_colliders()
     assert len(cs) == 40
@@ -156,9 +158,13 @@ def test_one_pass_equals_the_model(gpe, n, mode):
     assert info["k"] == 40 and info["passes"] == 1 and info["pushed"] == int(moved.sum())
     assert info["grid_x"] == 101 and info["grid_y"] == 101             # cells of max(4 * 0.5, 200 / 1024) = 2
     assert 0 < info["list_entries"] < 101 * 101 * 40 // 4
-    if n > 1:
+    if n >= 2000:
         assert 300 < moved.sum() < n - 300                             # the scene exercises both outcomes
         assert not same_bits(got, pos)
+    elif n >= 511:
+        assert 0 < moved.sum() < n                                 # both outcomes among the few
+    elif n > 1:
+        assert moved.any()                                         # (not the empty-cell path alone)
     # a second pass starts from the first one's result
     want2, moved2 = M.apply(want, rad, cs, WORLD)
     st.apply_colliders()

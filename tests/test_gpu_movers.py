@@ -125,11 +125,12 @@ def _scene_movers():
 
 
 @pytest.mark.parametrize("mode", ["native", "compat"])
-@pytest.mark.parametrize("n", [4000, 3999, 1])
+@pytest.mark.parametrize("n", [4000, 3999, 1, 2, 3, 511, 512, 513])
 def test_one_pass_equals_the_model(gpe, n, mode):
     """apply_movers(dt) on 40 movers, checked after 1, 2 and 7 advances with the particles placed around the POSED
     surfaces: pos bit for bit as the model, prev and radius untouched, pushed the model's count, the poses the model's.
-    Even n, odd n and the tail alone; then particles that walk every mover: a radius above the bound, outside the grid."""
+    Even n, odd n and the tail alone; the edges of the pair loop (2, 3, 511, 512, 513); then particles that walk every
+    mover: a radius above the bound, outside the grid."""
     movers = _scene_movers()
     assert len(movers) == 40 and M.dt_allowed(movers, DT)
     mv = M.Movers(movers)
@@ -164,8 +165,12 @@ def test_one_pass_equals_the_model(gpe, n, mode):
         assert (info["k"], info["passes"], info["pushed"], info["mask_words"]) == (40, advances, pushed, 1)
         assert info["grid_x"] == 101 and info["grid_y"] == 101         # cells of max(4 * 0.5, 200 / 128) = 2
         assert 2 * 101 * 101 <= info["listed"] < 101 * 101 * 40 // 4   # (two movers are listed everywhere)
-        if n > 1:
+        if n >= 2000:
             assert 300 < moved.sum() < n - 300                         # the scene exercises both outcomes
+        elif n >= 511:
+            assert 0 < moved.sum() < n                                 # both outcomes among the few
+        elif n > 1:
+            assert moved.any()                                         # (not the empty-cell path alone)
         pos = want
     # |r| = 3 > rb = 0.5 (add_particles keeps fmaxf(0.5, -3) = 0.5) and a particle outside the grid: every mover is walked
     caps = mv.capsules()
