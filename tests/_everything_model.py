@@ -1,10 +1,12 @@
-"""Every pass behind a step armed at once: bonds -> bodies -> movers (plain / surfaces / swept) -> static colliders
-(plain / surfaces / swept) -> fields, the order of gpe_step and gpe_run (csrc/gpe_api.hip).  TEST INFRASTRUCTURE ONLY.
+"""Every pass behind a step armed at once: bends -> areas -> bonds -> bodies -> movers (plain / surfaces / swept) ->
+static colliders (plain / surfaces / swept) -> fields, the order of gpe_step and gpe_run (csrc/gpe_api.hip).  TEST
+INFRASTRUCTURE ONLY.
 
-Everything is one twin over the two chains of twins the features' own tests use (tests/_bodies_model.Twin: bonds,
-bodies, plain colliders; tests/_sweep_model.Twin: movers, surfaces, sweep, fields) with the movers' sweep of
-tests/_mover_sweep_model.Mixin in front.  It writes no physics: every pass is the model function its feature's tests pin
-against the device, and tests/test_everything_cpu.py ties it bit for bit to the three existing twins.  THE NEXT PASS BEHIND A STEP IS ADDED HERE: its twin into the bases, its call into step().
+Everything is one twin over the three chains of twins the features' own tests use (tests/_bodies_model.Twin: bonds,
+bodies, plain colliders; tests/_areas_model.Twin: bends, areas, bonds, plain colliders; tests/_sweep_model.Twin: movers,
+surfaces, sweep, fields) with the movers' sweep of tests/_mover_sweep_model.Mixin in front.  It writes no physics: every
+pass is the model function its feature's tests pin against the device, and tests/test_everything_cpu.py ties it bit for
+bit to the four existing twins.  THE NEXT PASS BEHIND A STEP IS ADDED HERE: its twin into the bases, its call into step().
 
 scene() is the staged scene of the CPU and GPU tests, arm() sets its features on a twin or on a State (their methods
 share names), plan(seed) a list of operations and Sequence the thing that applies them to a twin and, when it has one, to
@@ -17,6 +19,8 @@ import tempfile
 
 import numpy as np
 
+from tests import _areas_model as AM
+from tests import _bends_model as NM
 from tests import _bodies_model as BD
 from tests import _bonds_model as BM
 from tests import _fields_model as FM
@@ -32,19 +36,37 @@ DT = 1.0 / 60.0
 DTS = (1.0 / 60.0, 1.0 / 120.0)
 STEPS = 40
 SEEDS = (1, 2, 3)
-ARMS = ("bonds", "bodies", "movers", "mover_surfaces", "mover_sweep", "colliders", "collider_surfaces", "sweep", "fields")
-# the arrays of a snapshot that holds all ten optional groups (State.save; the movers' poses belong to the movers' group)
-GROUPS = ("colliders", "collider_surfaces", "collider_sweep", "bonds", "bodies", "fields", "movers", "mover_poses",
-          "mover_surfaces", "mover_sweep", "uids")
+ARMS = ("bends", "areas", "bonds", "bodies", "movers", "mover_surfaces", "mover_sweep", "colliders", "collider_surfaces",
+        "sweep", "fields")
+# the arrays of a snapshot that holds all twelve optional groups (State.save; the movers' poses belong to the movers'
+# group, the relaxation counts and the loops' members to the bends' and the areas')
+GROUPS = ("colliders", "collider_surfaces", "collider_sweep", "bonds", "bends", "bend_iterations", "areas",
+          "area_member_uid", "area_iterations", "bodies", "fields", "movers", "mover_poses", "mover_surfaces", "mover_sweep",
+          "uids")
 
 
-class Everything(MS.Mixin, BD.Twin, SW.Twin):
-    """One context with all eight features: the MRO runs through both chains once, every constructor is cooperative;
+class Everything(MS.Mixin, BD.Twin, AM.Twin, SW.Twin):
+    """One context with all ten features: the MRO runs through the three chains once, every constructor is cooperative;
     the mixin in front makes self.m a set that holds the movers' sweep (a mode of the context, not of the set)."""
 
     def __init__(self, *a, **kw):
         super().__init__(*a, **kw)
         self.field_passes = self.field_touched = self.field_changed = 0
+        self.bend_changed = self.area_changed = 0
+
+    def _changed_by(self, apply):
+        """run a pass of a twin below -> the rows whose pos bits it changed"""
+        before = np.ascontiguousarray(self.arrays()[0], F32).view(U32).copy()
+        apply()
+        return int((np.ascontiguousarray(self.arrays()[0], F32).view(U32) != before).any(axis=1).sum())
+
+    def apply_bends(self):
+        """gpe_apply_bends: the bends' twin's pass (tests/_bends_model.apply); bend_changed counts the rows it changed"""
+        self.bend_changed += self._changed_by(super().apply_bends)
+
+    def apply_areas(self):
+        """gpe_apply_areas: the areas' twin's pass (tests/_areas_model.apply); area_changed counts the rows it changed"""
+        self.area_changed += self._changed_by(super().apply_areas)
 
     def set_fields(self, fields):
         super().set_fields(fields)
@@ -64,6 +86,8 @@ class Everything(MS.Mixin, BD.Twin, SW.Twin):
 
     def step(self, dt, resort=False):
         OracleModel.step(self, dt, resort=resort)
+        self.apply_bends()
+        self.apply_areas()
         self.apply_bonds()
         self.apply_bodies()
         self.apply_movers(dt)
@@ -72,7 +96,8 @@ class Everything(MS.Mixin, BD.Twin, SW.Twin):
 
     def armed(self):
         """-> the arms that are set"""
-        on = dict(bonds=len(self.bonds) > 0, bodies=len(self.bodies) > 0, movers=len(self.m) > 0,
+        on = dict(bends=len(self.bends) > 0, areas=len(self.areas) > 0,
+                  bonds=len(self.bonds) > 0, bodies=len(self.bodies) > 0, movers=len(self.m) > 0,
                   mover_surfaces=self.m.surfaces is not None, mover_sweep=self.m.sweep, colliders=len(self.colliders) > 0,
                   collider_surfaces=self.collider_surfaces is not None, sweep=self.sweep, fields=len(self.fields) > 0)
         return tuple(a for a in ARMS if on[a])
@@ -84,6 +109,8 @@ class Everything(MS.Mixin, BD.Twin, SW.Twin):
         """State.save() / State.load(): every set is set anew (its counters start again, the body poses are unknown
         until a pass), the broken flags, the movers' states and the two sweeps' modes are kept"""
         self.passes = self.pushed = 0
+        self.bend_passes = self.area_passes = 0
+        self.area_value = np.full((len(self.areas), 2), np.nan, F32)   # (as set_areas leaves it: no pass yet)
         self.bond_passes = self.body_passes = 0
         self.poses = np.full((len(self.bodies), 4), np.nan, F32)
         self.m.passes = self.m.pushed = 0
@@ -97,7 +124,7 @@ class Everything(MS.Mixin, BD.Twin, SW.Twin):
                     movers=dict(k=len(self.m), passes=self.m.passes, pushed=self.m.pushed),
                     sweep=dict(mode=int(self.sweep), passes=self.sweep_passes, swept=self.swept, stopped=self.stopped),
                     mover_sweep=self.mover_sweep_info(),
-                    bonds=self.bonds_info(), bodies=self.bodies_info(),
+                    bends=self.bends_info(), areas=self.areas_info(), bonds=self.bonds_info(), bodies=self.bodies_info(),
                     fields=dict(k=len(self.fields), passes=self.field_passes if len(self.fields) else 0,
                                 touched=self.field_touched if len(self.fields) else 0))
 
@@ -105,11 +132,12 @@ class Everything(MS.Mixin, BD.Twin, SW.Twin):
 def state_counters(st):
     """the same dict from a State (the grids' sizes and the uid lookups, which the model does not have, left out)"""
     pick = lambda info, names: {k: info[k] for k in names}
-    bonds, bodies = st.bonds_info(), st.bodies_info()
-    bonds.pop("resolves"); bodies.pop("resolves")
+    bends, areas, bonds, bodies = st.bends_info(), st.areas_info(), st.bonds_info(), st.bodies_info()
+    for info in (bends, areas, bonds, bodies):
+        info.pop("resolves")
     return dict(colliders=pick(st.colliders_info(), ("k", "passes", "pushed")),
                 movers=pick(st.movers_info(), ("k", "passes", "pushed")), sweep=st.sweep_info(),
-                mover_sweep=st.mover_sweep_info(), bonds=bonds, bodies=bodies,
+                mover_sweep=st.mover_sweep_info(), bends=bends, areas=areas, bonds=bonds, bodies=bodies,
                 fields=pick(st.fields_info(), ("k", "passes", "touched")))
 
 
@@ -124,20 +152,41 @@ SHOT_SPEED = 6.0                                                       # units p
 # lattice on the floor, an R = 0 blade at 0.4 rad per step that reaches the bricks' band
 THIN_MOVERS = MM.rows(MM.linear((14, 30), (14, 39.4), 0.0, v=(120.0, 0.0), travel=12.0),
                       MM.rotor((30, 36), (36, 36), 0.0, (30, 36), 24.0))
+# rings of RING members (centre, clockwise): one in the bricks' band in front of the piston, under the lattice's upper
+# rows; two above the lattice, over the paddle and over the bricks, inside the vortex once they have fallen
+RING = 16
+RINGS = (((11.5, 29.0), False), ((42.0, 13.0), True), ((22.5, 13.0), False))
+RING_PRESSURE = (1.0, 1.1, 0.9)
+RING_FIRST = N - SHOTS - RING * len(RINGS)                             # the rings' uids: behind the fill, before the shots
+BLOB = 7                                                               # the yard's soft body: its 16 outer members carry a loop
+BEND_STIFFNESS, AREA_STIFFNESS, EDGE_STIFFNESS = 0.1, 0.8, 0.25
 Scene = collections.namedtuple("Scene", "pos prev rad bonds iterations bodies member_uid member_rest colliders "
-                                        "collider_surfaces movers mover_surfaces fields")
+                                        "collider_surfaces movers mover_surfaces fields bends bend_iterations areas "
+                                        "area_member_uid area_iterations")
+
+
+def scene_loops(bodies):
+    """-> the uids of the scene's four loops, in order around each: the three rings, then the blob's outer members"""
+    first = int(bodies["first"][BLOB])
+    assert bodies["count"][BLOB] == 1 + RING
+    return ([np.arange(RING_FIRST + RING * q, RING_FIRST + RING * (q + 1), dtype=U32) for q in range(len(RINGS))]
+            + [np.arange(first + 1, first + 1 + RING, dtype=U32)])
 
 
 def scene():
     """uid = storage index at the start.  The yard (a pendulum, six bricks of which one is brittle, a soft blob, 120
-    loose particles; a floor and a peg; two bonds relaxed twice), 823 more loose particles on a jittered lattice above
-    the floor, and eight shots: particles below the corner that leave for its apex at 6 units per step.  The movers are
-    tests/_movers_model.run_movers' thick piston and paddle, then THIN_MOVERS."""
+    loose particles; a floor and a peg; two bonds relaxed twice), 775 more loose particles on a jittered lattice above
+    the floor, three RINGS, and eight shots: particles below the corner that leave for its apex at 6 units per step.
+    Every ring, and the ring of the blob's 16 outer members, carries bonds along its edge, a bend at every member (one
+    relaxation) and one area constraint (two): a member of the blob's ring is a bend node, an area member, a bond end
+    and a body member at once.  The movers are tests/_movers_model.run_movers' thick piston and paddle, then
+    THIN_MOVERS."""
+    from tests.test_gpu_areas import ring
     from tests.test_gpu_bodies import YARD_COLLIDERS, yard_scene
     pos, rad, bodies, member_uid, member_rest, bonds = yard_scene()
-    bodies["break_distance"][3] = 0.05                                 # the brittle brick breaks on the 15th step, as it lands
+    bodies["break_distance"][3] = 0.05                                 # the brittle brick breaks well before the 15th step
     rng = np.random.default_rng(31)
-    k = N - len(pos) - SHOTS
+    k = RING_FIRST - len(pos)
     i = np.arange(56 * 29)
     x, y = 2.5 + 1.0 * (i % 56), 39.4 - 1.02 * (i // 56)               # rows from the floor (centres rest at 39.5) upward
     far = lambda cx, cy, r: (x - cx) ** 2 + (y - cy) ** 2 > r * r
@@ -145,26 +194,43 @@ def scene():
     free &= ~((x > 8.5) & (x < 13.5) & (y < 16.0))                     # the pendulum
     free &= ~((x < 7.8) & (y > 25.0)) & ~((x > 37.5) & (x < 50.5) & (y > 29.5) & (y < 34.5))     # the piston, the paddle
     free &= ~((x > 48.5) & (y > 30.0) & (y < 39.0))                    # the corner and the lane of the shots
+    rings = [ring(RING, c, seed=40 + q, wobble=0.05, clockwise=cw) for q, (c, cw) in enumerate(RINGS)]
+    for c, _ in RINGS:
+        free &= far(c[0], c[1], 3.9)
     assert free.sum() >= k
     fill = np.stack([x, y], axis=1)[free][:k] + rng.uniform(-0.08, 0.08, (k, 2))
     j = np.arange(SHOTS)
     shots = np.stack([50.5 + 1.1 * (j % 4), 36.0 + 1.1 * (j // 4)], axis=1)
-    pos = np.concatenate([pos, fill, shots]).astype(F32)
+    pos = np.concatenate([pos, fill] + rings + [shots]).astype(F32)
     prev = pos.copy()
     d = np.array([57.0, 31.0]) - shots                                 # toward the apex
     d /= np.linalg.norm(d, axis=1)[:, None]
     prev[-SHOTS:] = (shots - SHOT_SPEED * d).astype(F32)
     assert len(pos) == N
+    loops = scene_loops(bodies)
+    uid = np.stack(loops)
+    nxt, prv = np.roll(uid, -1, axis=1), np.roll(uid, 1, axis=1)
+    rest = np.repeat([1.1] * len(RINGS) + [1.05], RING)                # a little over the spacing the loops start with
+    bonds = np.concatenate([bonds, BM.pairs(uid.ravel(), nxt.ravel(), rest, EDGE_STIFFNESS)])
+    start = np.arange(N, dtype=U32)
+    bends = NM.captured(pos, start, np.stack([prv.ravel(), uid.ravel(), nxt.ravel()], axis=1), BEND_STIFFNESS)
+    areas, area_member_uid = AM.captured(pos, start, loops, AREA_STIFFNESS, RING_PRESSURE + (1.0,))
+    assert sorted(np.sign(areas["rest_area"][:len(RINGS)]).tolist()) == [-1, 1, 1]    # either sense of rotation
     colliders = np.concatenate([YARD_COLLIDERS, CORNER]).astype(F32)
     movers = np.concatenate([MM.run_movers(), THIN_MOVERS])
     assert all(MM.dt_allowed(movers, dt) for dt in DTS)
     return Scene(pos, prev, np.full(N, 0.5, F32), bonds, 2, bodies, member_uid, member_rest, colliders,
-                 SM.scene_surfaces(len(colliders)), movers, SM.scene_surfaces(len(movers), seed=5), FM.POOL_FIELDS)
+                 SM.scene_surfaces(len(colliders)), movers, SM.scene_surfaces(len(movers), seed=5), FM.POOL_FIELDS,
+                 bends, 1, areas, area_member_uid, 2)
 
 
 def arm(h, sc, arms=ARMS):
     """set the features of `arms` on a twin or a State (uids on already); a set left out leaves its surfaces out, but
     not the movers' sweep: the mode is the context's, on with no movers held as well"""
+    if "bends" in arms:
+        h.set_bends(sc.bends, sc.bend_iterations)
+    if "areas" in arms:
+        h.set_areas(sc.areas, sc.area_member_uid, sc.area_iterations)
     if "bonds" in arms:
         h.set_bonds(sc.bonds, sc.iterations)
     if "bodies" in arms:
@@ -193,13 +259,13 @@ def twin(oracle, arms=ARMS, sc=None):
     return arm(tw, sc, arms)
 
 
-Frame = collections.namedtuple("Frame", "pos prev uids body_poses bodies_broken bonds_broken mover_poses")
+Frame = collections.namedtuple("Frame", "pos prev uids body_poses bodies_broken bonds_broken mover_poses area_value")
 
 
 def frame(tw):
     pos, prev, _ = tw.arrays()
     return Frame(pos.copy(), prev.copy(), tw.uids.copy(), tw.poses.copy(), tw.bodies_broken.copy(), tw.broken.copy(),
-                 tw.m.poses())
+                 tw.m.poses(), tw.area_value.copy())
 
 
 def frames(tw, steps=STEPS, dt=DT, resort_every=0, resort_first=False):
@@ -214,7 +280,7 @@ def frames(tw, steps=STEPS, dt=DT, resort_every=0, resort_first=False):
 
 # ---- the random interleaving -------------------------------------------------------------------------------------------
 Plan = collections.namedtuple("Plan", "seed ops")
-SETS = ("bonds", "bodies", "fields", "collider_surfaces", "mover_surfaces")
+SETS = ("bends", "areas", "bonds", "bodies", "fields", "collider_surfaces", "mover_surfaces")
 BLOCKS = ([["set_" + s, "step", "clear_" + s, "step", "set_" + s] for s in SETS] + [
     ["set_colliders", "set_collider_surfaces", "step", "clear_colliders", "step", "set_colliders", "set_collider_surfaces"],
     ["set_movers", "set_mover_surfaces", "step", "clear_movers", "step", "set_movers", "set_mover_surfaces"],
@@ -222,8 +288,8 @@ BLOCKS = ([["set_" + s, "step", "clear_" + s, "step", "set_" + s] for s in SETS]
     ["run"], ["run"], ["run_resort_mid"], ["resort", "step"], ["add_few", "step"], ["add_grow", "step"],
     ["remove_circle", "step"], ["remove_members", "step"], ["remove_uid"], ["edit_pos", "step"],
     ["radius_up", "step", "radius_down", "step"], ["kick", "step"], ["world_grow", "step", "world_back", "step"], ["gravity"],
-    ["other_mode"], ["save_load", "step"], ["apply_bonds"], ["apply_bodies"], ["apply_movers"], ["apply_colliders"],
-    ["apply_fields"]])
+    ["other_mode"], ["save_load", "step"], ["pump", "step"], ["apply_bends"], ["apply_areas"], ["apply_bonds"],
+    ["apply_bodies"], ["apply_movers"], ["apply_colliders"], ["apply_fields"]])
 REPLACING = (["set_" + s for s in SETS + ("colliders", "movers", "mover_poses")] + ["clear_" + s for s in SETS + ("colliders", "movers")]
              + ["sweep_off", "sweep_on", "mover_sweep_off", "mover_sweep_on"])
 
@@ -235,7 +301,9 @@ def plan(seed):
     rng = np.random.default_rng(7100 + seed)
     order = rng.permutation(len(BLOCKS))
     ops = ["run_start"] + [op for i in order for op in BLOCKS[i]]
-    assert 60 <= len(ops) <= 83
+    # the opening run and every block once: seven sets of 5, two of 7, 2 x 3 + 2 for the modes and the poses, 3 runs,
+    # 9 blocks of 2 (the pump's among them), 2 of 4, 3 single operations and the 7 passes
+    assert len(ops) == 1 + 7 * 5 + 2 * 7 + 8 + 3 + 9 * 2 + 2 * 4 + 3 + 7 == 97
     return Plan(seed, ops)
 
 
@@ -244,12 +312,12 @@ class Coverage(collections.Counter):
 
     def check(self):
         need = (["armed_" + k for k in ("colliders_pushed", "movers_pushed", "swept", "stopped", "mover_swept", "mover_stopped",
-                                        "body_broke", "field_changed", "resort", "growth", "removal_of_member_and_bonded",
-                                        "radius_up")]
-                + ["set_world_with_grids", "save_load_ten_groups", "run_resorts_in_its_middle"] + ["op_" + op for op in REPLACING])
+                                        "body_broke", "field_changed", "bend_changed", "area_changed", "resort", "growth",
+                                        "removal_of_member_and_bonded", "loop_lost_a_member", "pump", "radius_up")]
+                + ["set_world_with_grids", "save_load_every_group", "run_resorts_in_its_middle"] + ["op_" + op for op in REPLACING])
         missing = [k for k in need if self[k] == 0]
         assert not missing, "the sequence never reached: %s\n%s" % (", ".join(missing), dict(self))
-        assert self["armed_steps"] >= 30, "only %d steps with all nine arms set" % self["armed_steps"]
+        assert self["armed_steps"] >= 30, "only %d steps with all eleven arms set" % self["armed_steps"]
 
 
 class Sequence:
@@ -320,7 +388,8 @@ class Sequence:
         tw = self.tw
         return dict(colliders_pushed=tw.pushed, movers_pushed=tw.m.pushed, swept=tw.swept, stopped=tw.stopped,
                     mover_swept=tw.m.swept, mover_stopped=tw.m.stopped,
-                    body_broke=int(tw.bodies_broken.sum()), field_changed=tw.field_changed)
+                    body_broke=int(tw.bodies_broken.sum()), field_changed=tw.field_changed,
+                    bend_changed=tw.bend_changed, area_changed=tw.area_changed)
 
     def _twin_step(self, dt, resort):
         armed = self.tw.fully_armed()
@@ -424,17 +493,24 @@ class Sequence:
         self.log.append("%s: %d of %d uids" % (what, want, len(q)))
 
     def op_remove_members(self):
-        """a live member of a body, a live bonded particle, two more and one nobody has"""
+        """a live member of a body, a live bonded particle, a live member of a loop (the loop is inert from here on), a
+        live node of a bend, two more and one nobody has"""
         tw, rng = self.tw, self.rng
         armed = tw.fully_armed()
         live = lambda u: u[np.isin(u, tw.uids)]
         member, bonded = live(tw.member_uid), live(np.concatenate([tw.bonds["uid_a"], tw.bonds["uid_b"]]))
+        looped = live(tw.area_member_uid)
+        node = live(np.concatenate([tw.bends["uid_a"], tw.bends["uid_b"], tw.bends["uid_c"]]))
         q = [rng.choice(member)] if len(member) else []
         q += [rng.choice(bonded)] if len(bonded) else []
+        q += [rng.choice(looped)] if len(looped) else []
+        q += [rng.choice(node)] if len(node) else []
         if armed and len(member) and len(bonded):
             self.cov["armed_removal_of_member_and_bonded"] += 1
+        if armed and len(looped) and len(node):
+            self.cov["armed_loop_lost_a_member"] += 1
         q = np.unique(np.concatenate([q, rng.choice(tw.uids, 2, replace=False), [tw.next_uid + 3]]).astype(U32))
-        self._remove_uids(q, "remove a member and a bonded uid")
+        self._remove_uids(q, "remove a member, a bonded uid, a loop's member and a bend's node")
 
     def op_remove_uid(self):
         q = np.unique(np.append(self.rng.choice(self.tw.uids, 3, replace=False), 0xFFFFFFF0).astype(U32))
@@ -511,27 +587,48 @@ class Sequence:
 
     def op_save_load(self):
         tw = self.tw
-        ten = tw.fully_armed()
-        if ten:
-            self.cov["save_load_ten_groups"] += 1
+        every = tw.fully_armed()
+        if every:
+            self.cov["save_load_every_group"] += 1
         if self.st is not None:
             path = os.path.join(self.tmp.name, "snap_%d.npz" % len(self.log))
             self.st.save(path)
             with np.load(path) as d:
-                if ten:
+                if every:
                     assert set(GROUPS) <= set(d.files), sorted(d.files)
             self.retire()
             self.end(self.st)
             self.st = self.gpe.State.load(path, mode=self.mode, flags=self.L.FLAG_GUARD_ALLOCS)
         tw.reloaded()
         self.cap = len(tw)
-        self.log.append("save / load%s" % (" (all ten groups)" if ten else ""))
+        self.log.append("save / load%s" % (" (every group)" if every else ""))
+
+    def op_pump(self):
+        """gpe_set_area_targets between two steps: new rest areas for a sub-range of the loops, the set's slots and
+        counters kept"""
+        tw, rng = self.tw, self.rng
+        k = len(tw.areas)
+        assert k > 0                                                   # (every block leaves the areas set)
+        first = int(rng.integers(0, k))
+        count = int(rng.integers(1, max(k - first, 2)))                # (less than the whole set where it has two loops)
+        t = (tw.areas["rest_area"][first:first + count] * rng.uniform(0.7, 1.4, count)).astype(F32)
+        for h in self.both():
+            h.set_area_targets(first, t)
+        if tw.fully_armed():
+            self.cov["armed_pump"] += 1
+        self.log.append("pump loops %d .. %d of %d" % (first, first + count - 1, k))
 
     # ---- the passes called directly -----------------------------------------------------------------------------------
     def _apply(self, name, *args):
         for h in self.both():
             getattr(h, name)(*args)
         self.log.append("%s%s" % (name, args if args else ""))
+
+    def op_apply_bends(self):
+        self._apply("apply_bends")
+
+    def op_apply_areas(self):
+        self._apply("apply_areas")
 
     def op_apply_bonds(self):
         self._apply("apply_bonds")
@@ -558,6 +655,43 @@ class Sequence:
         p = self.tw.arrays()[0]
         near = np.argsort(((p - p[seed]) ** 2).sum(axis=1), kind="stable")
         return near[free[near]][:count]
+
+    def op_set_bends(self):
+        """chains of particles that are neighbours now, bent towards angles they do not hold (a chain's inner particles
+        are hinge of one bend and arm of the next), and one bend with a uid nobody has"""
+        rng, tw = self.rng, self.tw
+        rows = []
+        for _ in range(int(rng.integers(4, 9))):
+            chain = self._near(int(rng.integers(0, len(tw))), int(rng.choice([3, 4, 6])), np.ones(len(tw), bool))
+            u = tw.uids[chain]
+            rows.append(NM.bends(u[:-2], u[1:-1], u[2:], rng.uniform(-np.pi, np.pi, len(u) - 2), float(rng.choice([0.1, 0.5]))))
+        rows.append(NM.bends([u[0]], [tw.next_uid + 5], [u[1]], 1.0, 0.5))
+        self._set("set_bends", np.concatenate(rows), int(rng.integers(1, 4)))
+
+    def op_clear_bends(self):
+        self._set("set_bends", np.zeros(0, NM.BEND_DTYPE), 1, what="clear bends")
+
+    def op_set_areas(self):
+        """loops round groups of particles that are close now, in either sense, pumped a little off the area they hold;
+        some share members with a later loop; one uid nobody has"""
+        rng, tw = self.rng, self.tw
+        p = tw.arrays()[0]
+        free = np.ones(len(tw), bool)
+        loops = []
+        for _ in range(int(rng.integers(3, 8))):
+            g = self._near(int(rng.integers(0, len(tw))), int(rng.choice([3, 4, 5, 8, 17])), free)
+            if len(g) >= 3:
+                if rng.integers(0, 2):
+                    free[g] = False
+                c = p[g].astype(np.float64).mean(axis=0)
+                g = g[np.argsort(np.arctan2(p[g, 1] - c[1], p[g, 0] - c[0]), kind="stable")]     # round their centre
+                loops.append(tw.uids[g[::-1] if rng.integers(0, 2) else g])
+        rows, member = AM.captured(p, tw.uids, loops, rng.choice([0.25, 0.8, 1.0], len(loops)), rng.uniform(0.8, 1.3, len(loops)))
+        member[int(rng.integers(0, len(member)))] = tw.next_uid + 9
+        self._set("set_areas", rows, member, int(rng.integers(1, 4)))
+
+    def op_clear_areas(self):
+        self._set("set_areas", np.zeros(0, AM.AREA_DTYPE), np.zeros(0, U32), 1, what="clear areas")
 
     def op_set_bonds(self):
         """anchors that hold particles where they are, pairs of neighbours (some that snap), one uid nobody has"""

@@ -1,10 +1,11 @@
-"""CPU: the composed twin of tests/_everything_model.py (bonds, bodies, movers with surfaces and their sweep, static
-colliders with surfaces and the sweep, fields, all behind one step) before any GPU time is spent on it: it is no new
-oracle (bit for bit the three existing twins where only their features are set), its scene acts and tells every arm
-apart, and its random plans reach what tests/test_gpu_everything.py needs them to reach."""
+"""CPU: the composed twin of tests/_everything_model.py (bends, areas, bonds, bodies, movers with surfaces and their
+sweep, static colliders with surfaces and the sweep, fields, all behind one step) before any GPU time is spent on it: it
+is no new oracle (bit for bit the four existing twins where only their features are set), its scene acts and tells every
+arm apart, and its random plans reach what tests/test_gpu_everything.py needs them to reach."""
 import numpy as np
 import pytest
 
+from tests import _areas_model as AM
 from tests import _bodies_model as BD
 from tests import _everything_model as E
 from tests import _mover_sweep_model as MS
@@ -55,7 +56,7 @@ def test_with_the_sweeps_features_alone_it_is_the_sweep_twin(oracle):
     """movers, colliders, both surfaces, the sweep and fields over scene(): the frames of tests/_sweep_model.Twin (which
     has no movers' sweep: the thin movers run the plain pass)"""
     sc = E.scene()
-    arms = tuple(a for a in E.ARMS if a not in ("bonds", "bodies", "mover_sweep"))
+    arms = tuple(a for a in E.ARMS if a not in ("bends", "areas", "bonds", "bodies", "mover_sweep"))
     twins = []
     for cls in (SW.Twin, E.Everything):
         tw = cls(oracle, sc.pos, sc.rad, world=E.WORLD, gravity=E.GRAVITY, prev=sc.prev)
@@ -77,7 +78,7 @@ def test_with_both_sweeps_and_no_bonds_or_bodies_it_is_the_mover_sweep_twin(orac
     """movers, both surfaces, colliders, both sweeps and fields over scene(): the frames, the mover poses and the swept
     pass's counters of tests/_mover_sweep_model.Twin"""
     sc = E.scene()
-    arms = tuple(a for a in E.ARMS if a not in ("bonds", "bodies"))
+    arms = tuple(a for a in E.ARMS if a not in ("bends", "areas", "bonds", "bodies"))
     twins = []
     for cls in (MS.Twin, E.Everything):
         tw = cls(oracle, sc.pos, sc.rad, world=E.WORLD, gravity=E.GRAVITY, prev=sc.prev)
@@ -98,11 +99,46 @@ def test_with_both_sweeps_and_no_bonds_or_bodies_it_is_the_mover_sweep_twin(orac
     old.close(); new.close()
 
 
+def test_with_the_rings_features_alone_it_is_the_areas_twin(oracle):
+    """areas, bends, bonds and the floor over test_gpu_areas' rings: the frames, the (area, lambda) rows and the
+    counters of tests/_areas_model.Twin over that file's 50 steps"""
+    from tests import test_gpu_areas as TA
+    pos, rad, bonds, bends, rows, member = TA.ring_scene()
+    twins = []
+    for cls in (AM.Twin, E.Everything):
+        tw = cls(oracle, pos, rad, world=TA.RING_WORLD, gravity=TA.RING_GRAVITY)
+        tw.enable_uids()
+        tw.set_areas(rows, member, TA.AREA_ITERATIONS); tw.set_bends(bends, TA.BEND_ITERATIONS)
+        tw.set_bonds(bonds, TA.BOND_ITERATIONS); tw.set_colliders(TA.RING_COLLIDERS)
+        twins.append(tw)
+    old, new = twins
+    for s in range(TA.STEPS):
+        old.step(E.DT); new.step(E.DT)
+        for a, b in zip(old.arrays(), new.arrays()):
+            assert same_bits(a, b), s
+        assert same_bits(old.area_value, new.area_value) and not np.isnan(new.area_value).any(), s
+    assert old.pushed == new.pushed > 0 and new.bend_changed > 0 and new.area_changed > 0
+    assert old.bends_info() == new.bends_info() and old.areas_info() == new.areas_info() and old.bonds_info() == new.bonds_info()
+    assert new.bends_info()["passes"] == new.areas_info()["passes"] == TA.STEPS
+    assert new.armed() == ("bends", "areas", "bonds", "colliders")
+    old.close(); new.close()
+
+
 def test_the_scene_acts(full):
     frames, counters, first_break, field_changed = full
     sc = E.scene()
     assert len(sc.rad) == E.N == 1025 and (sc.collider_surfaces["flags"] == 1).any()
-    assert len(E.ARMS) == 9 and len(sc.movers) == 4 and (sc.movers["radius"] == 0).sum() == 2
+    assert len(E.ARMS) == 11 and len(sc.movers) == 4 and (sc.movers["radius"] == 0).sum() == 2
+    # four loops, either sense among the rings; a particle that is a bend node, a loop's member, a bond's end and a
+    # member of a body at once, and its body live at the end
+    loops = E.scene_loops(sc.bodies)
+    assert len(sc.areas) == len(loops) == 4 and (sc.areas["rest_area"][:3] > 0).tolist() == [True, False, True]
+    multi = set(sc.bends["uid_b"]) & set(sc.area_member_uid) & set(sc.bonds["uid_a"]) & set(sc.member_uid)
+    first = int(sc.bodies["first"][E.BLOB])
+    assert multi == set(sc.member_uid[first + 1:first + 1 + E.RING]) and multi == set(loops[3])
+    assert not frames[-1].bodies_broken[E.BLOB] and not np.isnan(frames[-1].body_poses[E.BLOB]).any()
+    assert counters["bends"]["passes"] == counters["areas"]["passes"] == E.STEPS
+    assert all(np.isfinite(f.area_value).all() for f in frames) and frames[-1].area_value.shape == (4, 2)
     assert all(np.isfinite(f.pos).all() and np.isfinite(f.prev).all() for f in frames)
     print(counters, "first break after step", first_break)
     assert counters["colliders"]["pushed"] > 0 and counters["movers"]["pushed"] > 0
@@ -136,15 +172,13 @@ def test_every_arm_matters(oracle, full, out):
     assert not (same_bits(last.pos, full[0][-1].pos) and same_bits(last.prev, full[0][-1].prev))
 
 
-PASSES = ("bonds", "bodies", "movers", "colliders", "fields")
+PASSES = ("bends", "areas", "bonds", "bodies", "movers", "colliders", "fields")
 
 
-@pytest.mark.parametrize("first", range(len(PASSES) - 1))
-def test_the_order_of_the_passes_matters(oracle, full, first):
-    """two neighbouring passes swapped behind every step change the bits after 40 steps: the all-arms case on the GPU
-    pins the order of gpe_step, not only the presence of every pass"""
+def _swapped(oracle, full, a, b):
+    """passes a and b of PASSES swapped behind every step: other bits after 40 steps"""
     order = list(PASSES)
-    order[first], order[first + 1] = order[first + 1], order[first]
+    order[a], order[b] = order[b], order[a]
 
     class Swapped(E.Everything):
         def step(self, dt, resort=False):
@@ -160,10 +194,23 @@ def test_the_order_of_the_passes_matters(oracle, full, first):
     assert not (same_bits(last.pos, full[0][-1].pos) and same_bits(last.prev, full[0][-1].prev)), order
 
 
+@pytest.mark.parametrize("first", range(len(PASSES) - 1))
+def test_the_order_of_the_passes_matters(oracle, full, first):
+    """two neighbouring passes swapped behind every step change the bits after 40 steps: the all-arms case on the GPU
+    pins the order of gpe_step, not only the presence of every pass"""
+    _swapped(oracle, full, first, first + 1)
+
+
+def test_the_areas_behind_the_bodies_give_other_bits(oracle, full):
+    """the areas' pass swapped with the bodies' (two sets of the uid sets' table, two apart in it): the blob's loop and
+    the blob's shape matching touch the same particles, so the all-arms case tells the two orders apart"""
+    _swapped(oracle, full, PASSES.index("areas"), PASSES.index("bodies"))
+
+
 @pytest.mark.parametrize("seed", E.SEEDS)
 def test_the_plans_reach_what_they_are_for(oracle, seed):
     plan = E.plan(seed)
-    assert 60 <= len(plan.ops) <= 83 and plan.ops == E.plan(seed).ops
+    assert 60 <= len(plan.ops) == 97 and plan.ops == E.plan(seed).ops
     seq = E.Sequence(plan, oracle)
     try:
         seq.run()

@@ -1,7 +1,7 @@
-"""GPU (-m gpu): every pass behind a step armed at once -- bonds -> bodies -> movers (surfaces, swept) -> static
-colliders (surfaces, swept) -> fields -> observers, the order of gpe_step / gpe_run -- against the one composed twin of
-tests/_everything_model.py, which is made of nothing but the model functions each feature's own tests pin against the
-device (tests/test_everything_cpu.py ties it to the three existing twins).
+"""GPU (-m gpu): every pass behind a step armed at once -- bends -> areas -> bonds -> bodies -> movers (surfaces,
+swept) -> static colliders (surfaces, swept) -> fields -> observers, the order of gpe_step / gpe_run -- against the one
+composed twin of tests/_everything_model.py, which is made of nothing but the model functions each feature's own tests
+pin against the device (tests/test_everything_cpu.py ties it to the four existing twins).
 
 Every comparison is bit for bit on uint32 views, a NaN for a NaN.  Every context runs under GPE_FLAG_GUARD_ALLOCS and
 ends with no damaged red zone.  A mismatch that goes away when one arm is left out (test_every_step_equals_the_twin's
@@ -10,6 +10,8 @@ growth, the order of restoration in State.load -- not at a model."""
 import numpy as np
 import pytest
 
+from tests import _areas_model as AM
+from tests import _bends_model as NM
 from tests import _bonds_model as BM
 from tests import _colliders_model as CM
 from tests import _everything_model as E
@@ -21,7 +23,8 @@ U32 = np.uint32
 DT = E.DT
 STEPS = E.STEPS
 CASES = ["all"] + ["no_" + a for a in E.ARMS] + ["none"]
-TRACKED = np.array([0, 4, 9, 30, 33, 60, 100, 500, 1017, 1024], U32)    # pendulum, bricks (the brittle one), loose, shots
+# pendulum, bricks (the brittle one), the blob's loop, loose, a ring in each sense, shots
+TRACKED = np.array([0, 4, 9, 30, 33, 60, 100, 500, E.RING_FIRST + 3, E.RING_FIRST + E.RING + 5, 1017, 1024], U32)
 
 
 def bits(a):
@@ -85,25 +88,31 @@ def _same_particles(st, tw, what):
     assert same_bits(got[2], rad) and np.array_equal(st.uids(), tw.uids), what
 
 
-def _same_flags_and_poses(st, body_poses, bodies_broken, bonds_broken, mover_poses, what):
-    assert same_bits(st.body_poses(), body_poses), (what, "body poses")
-    assert np.array_equal(st.bodies()[1], bodies_broken) and np.array_equal(st.bonds()[1], bonds_broken), (what, "broken flags")
-    assert same_rows(st.mover_poses(), mover_poses), (what, "mover poses", st.mover_poses(), mover_poses)
+def _same_flags_and_poses(st, f, what):
+    """f: a Frame of the twin -- the bodies' poses, the broken flags, the movers' poses and the loops' (area, lambda)
+    rows as of the last relaxation (NaNs for a loop that was inert in it, and before the first pass)"""
+    assert same_bits(st.body_poses(), f.body_poses), (what, "body poses")
+    assert np.array_equal(st.bodies()[1], f.bodies_broken) and np.array_equal(st.bonds()[1], f.bonds_broken), (what, "broken flags")
+    assert same_rows(st.mover_poses(), f.mover_poses), (what, "mover poses", st.mover_poses(), f.mover_poses)
+    assert same_bits(st.area_values(), f.area_value), (what, "area values", st.area_values(), f.area_value)
 
 
 def _same_as_twin(st, tw, what):
-    """the particles, every stored set read back, the poses, the flags and the counters"""
+    """the particles, every stored set read back, the poses, the flags, the loops' values and the counters"""
     _same_particles(st, tw, what)
     assert same_bits(st.colliders(), tw.colliders) and same_rows(st.movers(), tw.m.movers), (what, "colliders / movers")
     for target in ("colliders", "movers"):
         assert same_rows(st.surfaces(target), tw.surfaces(target)), (what, target, "surfaces")
     assert same_rows(st.fields(), tw.fields) and st.collider_sweep() is tw.sweep, (what, "fields / sweep")
     assert st.mover_sweep() is tw.m.sweep, (what, "the movers' sweep")
+    assert same_rows(st.bends(), tw.bends), (what, "bends")
+    rec, uid = st.areas()                                              # (a pump that did not land shows in rest_area)
+    assert same_rows(rec, tw.areas) and np.array_equal(uid, tw.area_member_uid), (what, "areas")
     rec, _ = st.bonds()
     assert same_rows(rec, tw.bonds), (what, "bonds")
     rec, _, uid, rest = st.bodies()
     assert same_rows(rec, tw.bodies) and np.array_equal(uid, tw.member_uid) and same_bits(rest, tw.member_rest), (what, "bodies")
-    _same_flags_and_poses(st, tw.poses, tw.bodies_broken, tw.broken, tw.m.poses(), what)
+    _same_flags_and_poses(st, E.frame(tw), what)
     got, want = E.state_counters(st), tw.counters()
     assert got == want, (what, {k: (got[k], want[k]) for k in got if got[k] != want[k]})
 
@@ -139,15 +148,16 @@ def resorted(oracle):
 @pytest.mark.parametrize("mode", ["native", "compat"])
 @pytest.mark.parametrize("case", CASES)
 def test_every_step_equals_the_twin(gpe, reference, case, mode):
-    """40 gpe_step calls over scene(): pos and prev after each, the poses and the broken flags after every tenth, every
-    counter at the end.  `all` pins the order of the five passes in the forms the nine arms give them (the movers' and
-    the static colliders' with surfaces and swept) and of the observers behind them; the other cases are bit-identical to
-    the twin configured the same way and bisect a failure of `all`.  `no_movers` keeps the movers' sweep on with no movers
-    held; under `no_mover_sweep` the thin movers run the plain pass."""
+    """40 gpe_step calls over scene(): pos and prev after each, the poses, the broken flags and the loops' values after
+    every tenth, every counter at the end.  `all` pins the order of the seven passes in the forms the eleven arms give
+    them (the movers' and the static colliders' with surfaces and swept) and of the observers behind them; the other
+    cases are bit-identical to the twin configured the same way and bisect a failure of `all`.  `no_movers` keeps the
+    movers' sweep on with no movers held; under `no_mover_sweep` the thin movers run the plain pass."""
     frames, counters = reference(case)
     if case == "all":
         assert counters["sweep"]["stopped"] > 0 and counters["bodies"]["broken"] > 0 and counters["movers"]["pushed"] > 0
         assert counters["mover_sweep"]["stopped"] > 0
+        assert counters["bends"]["passes"] == counters["areas"]["passes"] == STEPS
     st = _state(gpe, mode, _arms(case))
     for s in range(STEPS):
         st.update(DT)
@@ -156,7 +166,7 @@ def test_every_step_equals_the_twin(gpe, reference, case, mode):
         assert same_bits(pos, f.pos), (case, s, "pos", _differ(pos, f.pos))
         assert same_bits(prev, f.prev), (case, s, "prev", _differ(prev, f.prev))
         if s % 10 == 9:
-            _same_flags_and_poses(st, f.body_poses, f.bodies_broken, f.bonds_broken, f.mover_poses, (case, s))
+            _same_flags_and_poses(st, f, (case, s))
     got = E.state_counters(st)
     assert got == counters, {k: (got[k], counters[k]) for k in got if got[k] != counters[k]}
     _ran_native(gpe, st, mode, STEPS)
@@ -176,10 +186,11 @@ def test_one_run_equals_the_loop_and_the_observers_see_the_end_of_the_chain(gpe,
     assert same_bits(pos, last.pos), _differ(pos, last.pos)
     assert same_bits(prev, last.prev), _differ(prev, last.prev)
     assert np.array_equal(st.uids(), last.uids) and not np.array_equal(last.uids, np.arange(E.N))
-    _same_flags_and_poses(st, last.body_poses, last.bodies_broken, last.bonds_broken, last.mover_poses, "run")
+    _same_flags_and_poses(st, last, "run")
     got = E.state_counters(st)
     assert got == counters, {k: (got[k], counters[k]) for k in got if got[k] != counters[k]}
     assert st.bonds_info()["resolves"] == st.bodies_info()["resolves"] == 3          # before steps 0, 16, 32
+    assert st.bends_info()["resolves"] == st.areas_info()["resolves"] == 3
     tr = st.tracers_read()
     rec, recorded = st.monitor_read()
     assert len(tr.step) == STEPS and recorded == STEPS
@@ -197,8 +208,9 @@ def test_one_run_equals_the_loop_and_the_observers_see_the_end_of_the_chain(gpe,
 @pytest.mark.parametrize("mode", ["native", "compat"])
 def test_one_event_invalidates_every_structure(gpe, oracle, mode):
     """Fully armed and stepping: a radius edit to three times the largest and back, gpe_set_world to twice the size and
-    back, an add past the capacity, the removal of a body member and of a bonded uid, a re-sort, a spell in the other
-    mode; three steps and a full comparison (the movers' sweep and its counters in it) behind each.  A grid of the
+    back, an add past the capacity, the removal of a body member, of a bonded uid, of a loop's member and of a bend's
+    hinge, a re-sort (all four uid-named sets look their slots up again), a spell in the other mode; three steps and a
+    full comparison (the movers' sweep and its counters in it) behind each.  A grid of the
     movers that is cut anew must not drop the swept form: its pass counter goes on behind the radius edit and the new
     world."""
     from tests.test_gpu_fields import grid_dims
@@ -258,16 +270,23 @@ def test_one_event_invalidates_every_structure(gpe, oracle, mode):
     grow = np.stack([rng.uniform(2, 58, k), rng.uniform(2, 28, k)], axis=1).astype(F32)
     st.add_particles(grow, np.full(k, 0.25, F32)); tw.add(grow, np.full(k, 0.25, F32))
     steps("growth")
-    # a member of a live body and a bonded particle leave
-    assert not tw.bodies_broken[1] and not tw.broken.any()
-    gone = np.array([10, 17, 1], U32)                                  # of the first brick; the pair bond's end; the anchored one
-    assert st.remove_particles_by_uid(gone) == tw.remove_uids(gone) == 3
+    # a member of a live body, a bonded particle, a member of a ring's loop and the middle node of a bend leave
+    assert not tw.bodies_broken[1] and not tw.broken.any() and not np.isnan(tw.area_value).any()
+    ring = E.RING_FIRST                                                # (the first ring: loop 0, bends 0 .. 15)
+    assert tw.area_member_uid[3] == ring + 3 and tw.bends["uid_b"][4] == ring + 4
+    # of the first brick; the pair bond's end; the anchored one; the loop's member; the bend's hinge
+    gone = np.array([10, 17, 1, ring + 3, ring + 4], U32)
+    assert st.remove_particles_by_uid(gone) == tw.remove_uids(gone) == 5
     steps("removal")
     assert not np.isnan(tw.poses[1]).any()                             # the brick goes on with seven members
-    resolves = st.bonds_info()["resolves"], st.bodies_info()["resolves"]
+    # the loop without its members is inert (tests/_areas_model.loop_phase: NaNs in its row), the other three act
+    assert np.isnan(tw.area_value[0]).all() and not np.isnan(tw.area_value[1:]).any()
+    names = ("bonds", "bodies", "bends", "areas")
+    resolves = {name: getattr(st, name + "_info")()["resolves"] for name in names}
     st.particles.sort_by_cell_id(); tw.morton_resort()
     steps("sort_by_cell_id")
-    assert st.bonds_info()["resolves"] > resolves[0] and st.bodies_info()["resolves"] > resolves[1]
+    for name in names:
+        assert getattr(st, name + "_info")()["resolves"] > resolves[name], name
     other = L.MODE_NATIVE if mode == "compat" else L.MODE_COMPAT
     st.ctx.call("gpe_set_mode", other)
     steps("the other mode")
@@ -284,28 +303,56 @@ def test_one_event_invalidates_every_structure(gpe, oracle, mode):
 
 
 # ---- 5. save and load with everything ---------------------------------------------------------------------------------
+PUMPED = 2                                                             # the loop the save / load test pumps before it saves
+
+
+@pytest.fixture(scope="module")
+def pumped(oracle):
+    """all arms, 15 steps, loop PUMPED pumped to 1.25 times its rest area, 15 more steps without interruption ->
+    (frames, the areas' rows from the pump on)"""
+    tw = E.twin(oracle)
+    frames = E.frames(tw, 15)
+    tw.set_area_targets(PUMPED, F32(1.25) * tw.areas["rest_area"][PUMPED:PUMPED + 1])
+    rows = tw.areas.copy()
+    frames += E.frames(tw, 15)
+    tw.close()
+    return frames, rows
+
+
 @pytest.mark.parametrize("mode", ["native", "compat"])
-def test_save_and_load_with_all_ten_groups(gpe, reference, tmp_path, mode):
-    """saved after 15 steps, loaded into a fresh context of each mode, 15 more steps: the bits of the uninterrupted twin"""
+def test_save_and_load_with_all_twelve_groups(gpe, pumped, tmp_path, mode):
+    """one loop pumped and the context saved after 15 steps, loaded into a fresh context of each mode, 15 more steps:
+    the bits of the uninterrupted twin"""
     L = gpe._lib
-    frames, _ = reference("all")
-    st = _state(gpe, mode)
+    frames, rows = pumped
+    sc = E.scene()
+    st = _state(gpe, mode, sc=sc)
     for s in range(15):
         st.update(DT)
     assert frames[14].bodies_broken.any() and not frames[14].bodies_broken.all()
+    st.set_area_targets(PUMPED, F32(1.25) * sc.areas["rest_area"][PUMPED:PUMPED + 1])
+    assert same_rows(st.areas()[0], rows) and not same_rows(rows, AM.stored(sc.areas))
     path = str(tmp_path / "snap.npz")
     st.save(path)
     with np.load(path) as d:
         assert set(E.GROUPS) <= set(d.files), sorted(d.files)
         assert np.array_equal(d["bodies_broken"], frames[14].bodies_broken) and d["collider_sweep"].tolist() == [1]
         assert same_rows(d["mover_poses"], frames[14].mover_poses) and d["mover_sweep"].tolist() == [1]
+        assert same_rows(d["areas"], rows) and np.array_equal(d["area_member_uid"], sc.area_member_uid)
+        assert same_rows(d["bends"], NM.stored(sc.bends))
+        assert (d["bend_iterations"].tolist(), d["area_iterations"].tolist()) == ([sc.bend_iterations], [sc.area_iterations])
     backs = [gpe.State.load(path, mode=m, flags=L.FLAG_GUARD_ALLOCS) for m in (_mode(gpe, mode), _mode(gpe, "compat" if mode == "native" else "native"))]
+    assert same_bits(st.area_values(), frames[14].area_value) and not np.isnan(st.area_values()).any()
     for h in backs:
         assert h.collider_sweep() is True and np.array_equal(h.bodies()[1], frames[14].bodies_broken)
         assert h.mover_sweep() is True and h.mover_sweep_info()["passes"] == 0     # (its counters start anew)
         assert same_rows(h.mover_poses(), frames[14].mover_poses)
         for target in ("colliders", "movers"):
             assert same_rows(h.surfaces(target), st.surfaces(target)) and len(h.surfaces(target)) > 0
+        got, member = h.areas()
+        assert same_rows(got, rows) and np.array_equal(member, sc.area_member_uid) and same_rows(h.bends(), NM.stored(sc.bends))
+        assert h.area_values().shape == (len(rows), 2) and np.isnan(h.area_values()).all()     # no pass yet
+        assert h.bends_info()["passes"] == h.areas_info()["passes"] == 0
     for s in range(15, 30):
         for h in [st] + backs:
             h.update(DT)
@@ -314,8 +361,10 @@ def test_save_and_load_with_all_ten_groups(gpe, reference, tmp_path, mode):
             assert same_bits(prev, frames[s].prev), (s, h is st, "prev", _differ(prev, frames[s].prev))
     f = frames[29]
     for h in [st] + backs:
-        _same_flags_and_poses(h, f.body_poses, f.bodies_broken, f.bonds_broken, f.mover_poses, "after load")
+        _same_flags_and_poses(h, f, "after load")
         assert h.mover_sweep_info()["passes"] == (30 if h is st else 15)
+        assert h.bends_info()["passes"] == h.areas_info()["passes"] == (30 if h is st else 15)
+        assert same_rows(h.areas()[0], rows)
     _ran_native(gpe, st, mode, 30)
     _ran_native(gpe, backs[0], mode, 15)
     _ran_native(gpe, backs[1], "compat" if mode == "native" else "native", 15)
