@@ -4,6 +4,7 @@
 // in its table (after_step, gpe_destroy, the refusals).
 #include <string.h>
 
+#include "bond_colours.h"
 #include "bond_graph.h"
 #include "k_bond.h"
 #include "uid_sets.h"
@@ -16,6 +17,7 @@ void gpe::bonds_release(gpe_ctx *c)
     dev_free(c, S.rec); dev_free(c, S.max_length); dev_free(c, S.anchors);
     node_table_free(c, S.nt); dev_free(c, S.inc);
     dev_free(c, S.corr); dev_free(c, S.state); dev_free(c, S.broken);
+    dev_free(c, S.order); dev_free(c, S.colour_start);
     S = BondState();
 }
 
@@ -24,10 +26,37 @@ gpe_status gpe::bonds_pass(gpe_ctx *c)
     BondState &S = c->bonds;
     return uid_set_pass(c, S.set.empty(), S.nt.stale, "Bonds", &S.passes,
                         [&] { return uid_slots_resolve(c, "bonds/resolve", S.nt); },
-                        [&] {
+                        [&]() -> gpe_status {
+                            if (c->bond_solver.mode == GPE_BOND_SOLVER_COLOURED) {
+                                GPE_TRY(launch_bonds_coloured(c, c->pos, c->radius, c->n, S, (uint32_t)S.set.size(),
+                                                              (uint32_t)S.nt.nodes, S.iterations, &c->bond_solver.form));
+                                c->bond_solver.passes += 1;
+                                return GPE_OK;
+                            }
                             return launch_bonds_pass(c, c->pos, c->radius, c->n, S, (uint32_t)S.set.size(),
                                                      (uint32_t)S.nt.nodes, S.iterations);
                         });
+}
+
+// The colours of g's bonds (bond_colours.h).  NULL, or why the coloured solver cannot take the set (text kept in *why)
+static const char *bond_colours_of(const BondGraph &g, BondColours *col, std::string *why)
+{
+    if (bond_colours_build(g.rec.data(), g.rec.size(), g.nodes.size(), col)) return nullptr;
+    *why = "the coloured solver needs " + std::to_string(col->colours) +
+           " colours for this set, more than GPE_BOND_COLOURS_MAX (gpe_set_bond_solver)";
+    return why->c_str();
+}
+
+// The colour tables inside an upload transaction, into N.  Read by index below the count they are allocated with.  no slack
+static void bond_colours_upload(HipSetUpload &up, BondState *N, const BondColours &col)
+{
+    up.reserve(&N->order, col.order.size(), "uid.bond_order");
+    up.reserve(&N->colour_start, col.colour_start.size(), "uid.bond_colour_start");
+    up.copy(N->order, col.order.data(), col.order.size());
+    up.copy(N->colour_start, col.colour_start.data(), col.colour_start.size());
+    N->colour_begin = col.colour_start;
+    N->colours = col.colours;
+    N->largest_colour = col.largest;
 }
 
 gpe_status gpe_set_bonds(gpe_ctx *c, const gpe_bond *bonds, uint64_t k, uint32_t iterations)
@@ -36,8 +65,12 @@ gpe_status gpe_set_bonds(gpe_ctx *c, const gpe_bond *bonds, uint64_t k, uint32_t
     if (const char *why = bond_set_problem(bonds, k, iterations))
         return fail(c, GPE_ERR_INVALID_ARG, std::string("gpe_set_bonds: ") + why);
     BondGraph g;
-    GPE_TRY(uid_set_open(c, "gpe_set_bonds", k, bonds_release, [&] {
-        return bond_graph_build(bonds, k, &g) ? nullptr : "a uid has more than GPE_BOND_MAX_DEGREE bonds";
+    BondColours col;
+    std::string why;
+    const bool coloured = c->bond_solver.mode == GPE_BOND_SOLVER_COLOURED;
+    GPE_TRY(uid_set_open(c, "gpe_set_bonds", k, bonds_release, [&]() -> const char * {
+        if (!bond_graph_build(bonds, k, &g)) return "a uid has more than GPE_BOND_MAX_DEGREE bonds";
+        return coloured ? bond_colours_of(g, &col, &why) : nullptr;
     }));
     if (k == 0) return GPE_OK;
     // the new tables beside the old ones (set_upload.h).  Every array is read and written by index below the count it
@@ -54,6 +87,7 @@ gpe_status gpe_set_bonds(gpe_ctx *c, const gpe_bond *bonds, uint64_t k, uint32_t
     up.reserve(&N.corr, k, "uid.bond_corr");
     up.reserve(&N.state, k, "uid.bond_state");
     up.reserve(&N.broken, 1, "uid.bond_broken");
+    if (coloured) bond_colours_upload(up, &N, col);
     up.copy(N.rec, g.rec.data(), g.rec.size());
     up.copy(N.max_length, g.max_length.data(), g.max_length.size());
     up.copy(N.anchors, g.anchors.data(), g.anchors.size());
@@ -104,6 +138,65 @@ gpe_status gpe_get_bonds_info(gpe_ctx *c, gpe_bonds_info *info)
         out.resolves = S.nt.resolves;
         GPE_TRY(info_broken(c, S.broken, &out));
     }
+    *info = out;
+    return GPE_OK;
+}
+
+// ---- the solver (gpe_set_bond_solver): a mode of the pass above, kept in c->bond_solver; the colour tables are the set's
+gpe_status gpe_set_bond_solver(gpe_ctx *c, uint32_t mode)
+{
+    if (!c) return GPE_ERR_INVALID_ARG;
+    if (mode != GPE_BOND_SOLVER_JACOBI && mode != GPE_BOND_SOLVER_COLOURED)
+        return fail(c, GPE_ERR_INVALID_ARG, "gpe_set_bond_solver: mode must be GPE_BOND_SOLVER_JACOBI or GPE_BOND_SOLVER_COLOURED");
+    if (is_sharded(c)) return refuse_sharded(c, "gpe_set_bond_solver");
+    BondState &S = c->bonds;
+    BondColours col;
+    const bool build = mode == GPE_BOND_SOLVER_COLOURED && !S.set.empty() && !S.order;
+    if (build) {                                                       // from the kept set, before anything changes
+        BondGraph g;
+        std::string why;
+        if (!bond_graph_build(S.set.data(), S.set.size(), &g))
+            return fail(c, GPE_ERR_STATE, "gpe_set_bond_solver: the set held no longer builds");
+        if (const char *no = bond_colours_of(g, &col, &why)) return fail(c, GPE_ERR_INVALID_ARG, std::string("gpe_set_bond_solver: ") + no);
+    }
+    GPE_HIP(c, hipSetDevice(c->device));
+    GPE_HIP(c, hipStreamSynchronize(c->stream));                       // (a pass in flight reads the old tables)
+    if (build) {
+        BondState N;                                                   // (only the colour fields are used)
+        HipSetUpload up({c}, "gpe_set_bond_solver");
+        bond_colours_upload(up, &N, col);
+        GPE_TRY(up.finish());
+        S.order = N.order; S.colour_start = N.colour_start;
+        S.colour_begin = std::move(N.colour_begin);
+        S.colours = N.colours; S.largest_colour = N.largest_colour;
+    }
+    if (mode == GPE_BOND_SOLVER_JACOBI) {
+        dev_free(c, S.order); dev_free(c, S.colour_start);
+        S.colour_begin.clear();
+        S.colours = S.largest_colour = 0;
+    }
+    c->bond_solver = BondSolverState();
+    c->bond_solver.mode = mode;
+    return GPE_OK;
+}
+
+gpe_status gpe_get_bond_solver(gpe_ctx *c, uint32_t *mode)
+{
+    if (!c || !mode) return GPE_ERR_INVALID_ARG;
+    *mode = c->bond_solver.mode;
+    return GPE_OK;
+}
+
+gpe_status gpe_get_bond_solver_info(gpe_ctx *c, gpe_bond_solver_info *info)
+{
+    gpe_bond_solver_info out;
+    GPE_TRY(info_open(c, "gpe_get_bond_solver_info", info, &out));
+    out.mode = c->bond_solver.mode;
+    out.colours = c->bonds.colours;
+    out.largest_colour = c->bonds.largest_colour;
+    out.form = c->bond_solver.form;
+    out.lds_nodes_max = kBondLdsNodesMax;
+    out.passes = c->bond_solver.passes;
     *info = out;
     return GPE_OK;
 }

@@ -478,6 +478,19 @@ struct BondState {
     float2 *corr = nullptr;                      // k: this relaxation's corrections
     uint8_t *state = nullptr;                    // k: 0 acted, 1 broken (sticky), 2 inert in this relaxation
     unsigned long long *broken = nullptr;        // one word: bonds broken
+    // the colour tables (bond_colours.h): held only while the solver is coloured (BondSolverState), null otherwise
+    uint32_t *order = nullptr;                   // k: the bond indices by (colour, index)
+    uint32_t *colour_start = nullptr;            // colours + 1, the device's copy (the one-workgroup form reads it)
+    std::vector<uint32_t> colour_begin;          // colours + 1, the host's copy (the per-colour launches' ranges)
+    uint32_t colours = 0, largest_colour = 0;
+};
+
+// the bonds' solver (gpe_set_bond_solver; gpe_bonds.hip, k_bonds.hip, bond_colours.h).  A mode of their pass, like the
+// colliders' sweep: it outlives gpe_set_bonds
+struct BondSolverState {
+    uint32_t mode = 0;                           // GPE_BOND_SOLVER_JACOBI / GPE_BOND_SOLVER_COLOURED
+    uint32_t form = 0;                           // the last coloured pass's: 0 none yet, 1 per colour, 2 one workgroup
+    uint64_t passes = 0;                         // coloured passes enqueued since the mode was last set
 };
 
 // the bend constraints (gpe_set_bends; gpe_bends.hip, k_bends.hip, bend_graph.h).  Step state: gpe_step / gpe_run relax
@@ -957,6 +970,7 @@ struct gpe_ctx {
     gpe::ColliderState colliders;
     gpe::SweepState sweep;
     gpe::BondState bonds;
+    gpe::BondSolverState bond_solver;
     gpe::BendState bends;
     gpe::AreaState areas;
     gpe::BodyState bodies;
@@ -1456,6 +1470,18 @@ gpe_status launch_colliders_pass(gpe_ctx *c, float2 *pos, const float *radius, u
 // distance bonds (k_bonds.hip): `iterations` relaxations of the k bonds of B over pos[0, n) in place, two launches each
 gpe_status launch_bonds_pass(gpe_ctx *c, float2 *pos, const float *radius, uint64_t n, const BondState &B, uint32_t k,
                              uint32_t m, uint32_t iterations);
+// ... under the coloured solver: `iterations` coloured relaxations, B.order and B.colour_start as bond_colours.h built
+// them for B.colours colours.  *form: 2 when the pass was one launch of one workgroup (m <= kBondLdsNodesMax), 1 when
+// it was one launch per colour and relaxation
+#ifndef GPE_BOND_LDS_NODES_MAX
+#define GPE_BOND_LDS_NODES_MAX 1024              // (timing builds set 0 and 8192: every pass in one form, profiles/bond_solver/)
+#endif
+constexpr uint32_t kBondLdsNodesMax = GPE_BOND_LDS_NODES_MAX;       // policy: profiles/bond_solver/README.md
+// the nodes the one-workgroup form declares LDS for, 12 B each: the policy's (12 KiB; a timing build of 8192: 96 KiB)
+constexpr uint32_t kBondLdsNodesCap = kBondLdsNodesMax > 0 ? kBondLdsNodesMax : 1;
+static_assert(kBondLdsNodesCap <= 8192, "12 B a node: 8192 nodes are 96 KiB of the 160 KiB a gfx950 workgroup may declare");
+gpe_status launch_bonds_coloured(gpe_ctx *c, float2 *pos, const float *radius, uint64_t n, const BondState &B, uint32_t k,
+                                 uint32_t m, uint32_t iterations, uint32_t *form);
 // bend constraints (k_bends.hip): `iterations` relaxations of the k bends of B over pos[0, n) in place, two launches each
 gpe_status launch_bends_pass(gpe_ctx *c, float2 *pos, const float *radius, uint64_t n, const BendState &B, uint32_t k,
                              uint32_t m, uint32_t iterations);

@@ -794,6 +794,28 @@ class ParticleSystem:
         self.ctx.call("gpe_get_bonds_info", C.byref(info))
         return {name: getattr(info, name) for name, _ in L.GpeBondsInfo._fields_ if name != "struct_size"}
 
+    def set_bond_solver(self, solver):
+        """gpe_set_bond_solver: "jacobi" (the default: every bond judged from the positions a relaxation starts with) or
+        "coloured" (graph-coloured Gauss-Seidel: the bonds relaxed colour after colour, every bond seeing the corrections
+        of the colours before it -- stiffness 1 is stable, a rope stretches about a quarter as much).  Step state: it
+        outlives set_bonds; save() keeps it with the bonds it belongs to (not for a context without bonds).  Synchronises."""
+        modes = {"jacobi": L.BOND_SOLVER_JACOBI, "coloured": L.BOND_SOLVER_COLOURED}
+        if solver not in modes:
+            raise ValueError('the bond solver is "jacobi" or "coloured"')
+        self.ctx.call("gpe_set_bond_solver", modes[solver])
+
+    def bond_solver(self):
+        """gpe_get_bond_solver -> "jacobi" | "coloured"."""
+        mode = C.c_uint32(0)
+        self.ctx.call("gpe_get_bond_solver", C.byref(mode))
+        return "coloured" if mode.value == L.BOND_SOLVER_COLOURED else "jacobi"
+
+    def bond_solver_info(self):
+        """gpe_get_bond_solver_info -> dict(mode, colours, largest_colour, form, lds_nodes_max, passes)."""
+        info = L.GpeBondSolverInfo(struct_size=C.sizeof(L.GpeBondSolverInfo))
+        self.ctx.call("gpe_get_bond_solver_info", C.byref(info))
+        return {name: getattr(info, name) for name, _ in L.GpeBondSolverInfo._fields_ if name != "struct_size"}
+
     # Bend constraints (not in the reference; include/gpe.h): the angle at a hinge particle between two others, by uid,
     # relaxed on the device after every update() / step of run(), in front of the bonds.  Step state: save() keeps them.
     def set_bends(self, bends, iterations=1):
@@ -1602,6 +1624,18 @@ class State:
         """ParticleSystem.bonds_info -> dict(iterations, k, nodes, passes, live, broken, resolves)."""
         return self.particles.bonds_info()
 
+    def set_bond_solver(self, solver):
+        """ParticleSystem.set_bond_solver: "jacobi" | "coloured"."""
+        self.particles.set_bond_solver(solver)
+
+    def bond_solver(self):
+        """ParticleSystem.bond_solver -> "jacobi" | "coloured"."""
+        return self.particles.bond_solver()
+
+    def bond_solver_info(self):
+        """ParticleSystem.bond_solver_info -> dict(mode, colours, largest_colour, form, lds_nodes_max, passes)."""
+        return self.particles.bond_solver_info()
+
     def set_bends(self, bends, iterations=1):
         """ParticleSystem.set_bends: bend constraints (rows of BEND_DTYPE) relaxed after every step, in front of the bonds."""
         self.particles.set_bends(bends, iterations)
@@ -1854,7 +1888,10 @@ class State:
         bodies with their members and broken flags (`bodies`, `bodies_broken`, `body_member_uid`, `body_member_rest`) and
         force fields (`fields`) and moving colliders with their poses (`movers`, `mover_poses`), and the surfaces of
         the two sets where present (`collider_surfaces`, `mover_surfaces`), and the static colliders' sweep where it is
-        on (`collider_sweep`), and the movers' sweep where it is on (`mover_sweep`)."""
+        on (`collider_sweep`), and the movers' sweep where it is on (`mover_sweep`), and the bonds' solver where bonds are held
+        and it is the coloured one (`bond_solver`).  A coloured mode set on a context that holds no bonds is NOT
+        written -- it has moved nothing -- and such a snapshot loads as Jacobi: a host that sets its bonds after load()
+        sets the solver again with them."""
         extra = {}
         if self.mover_sweep():
             extra.update(mover_sweep=np.array([L.SWEEP_ON], np.uint32))
@@ -1878,6 +1915,8 @@ class State:
         if len(bonds):
             extra.update(bonds=bonds, bond_iterations=np.array([self.bonds_info()["iterations"]], np.uint32),
                          bonds_broken=broken)
+            if self.bond_solver() == "coloured":                       # (asked where bonds are held: the mode alone moves nothing)
+                extra.update(bond_solver=np.array([L.BOND_SOLVER_COLOURED], np.uint32))
         caps = self.colliders()
         if len(caps):
             extra.update(colliders=caps)
@@ -1927,6 +1966,8 @@ class State:
                 st.set_surfaces("colliders", d["collider_surfaces"].astype(SURFACE_DTYPE))
             if "collider_sweep" in d.files:                        # (a file without it: off)
                 st.set_collider_sweep(bool(d["collider_sweep"][0]))
+            if "bond_solver" in d.files and int(d["bond_solver"][0]) == L.BOND_SOLVER_COLOURED:
+                st.set_bond_solver("coloured")                     # (before the bonds: their tables are built once; no key: Jacobi)
             if "bonds" in d.files:                                 # (after the uids they name; a broken bond starts broken)
                 rows = d["bonds"].astype(BOND_DTYPE)
                 rows["flags"] |= np.where(d["bonds_broken"], L.BOND_BROKEN, 0).astype(np.uint32)

@@ -401,6 +401,25 @@ class ParticleSystem {
         ctx_->call(gpe_get_bonds_info(ctx_->raw(), &info));
         return info;
     }
+    // the bonds' solver: Jacobi (the default) or graph-coloured Gauss-Seidel, which holds stiff ropes and cloth at
+    // stiffness 1.  Step state, independent of set_bonds: it outlives it.
+    void set_bond_solver(bool coloured)
+    {
+        ctx_->call(gpe_set_bond_solver(ctx_->raw(), coloured ? GPE_BOND_SOLVER_COLOURED : GPE_BOND_SOLVER_JACOBI));
+    }
+    bool bond_solver_coloured() const
+    {
+        uint32_t mode = GPE_BOND_SOLVER_JACOBI;
+        ctx_->call(gpe_get_bond_solver(ctx_->raw(), &mode));
+        return mode == GPE_BOND_SOLVER_COLOURED;
+    }
+    gpe_bond_solver_info bond_solver_info() const
+    {
+        gpe_bond_solver_info info{};
+        info.struct_size = sizeof(info);
+        ctx_->call(gpe_get_bond_solver_info(ctx_->raw(), &info));
+        return info;
+    }
     // not in the reference: bend constraints (include/gpe.h): the angle at a hinge particle between two others, all named
     // by uid, held at a rest angle given as (rest_cos, rest_sin); relaxed on the device after every step of gpe_step /
     // gpe_run, in front of the bonds.  Step state: a snapshot keeps the set and its relaxation count.

@@ -678,6 +678,55 @@ gpe_status gpe_get_bonds(gpe_ctx *ctx, gpe_bond *out, uint8_t *broken_out, uint6
 gpe_status gpe_apply_bonds(gpe_ctx *ctx);                          /* one pass now, stream-ordered, no sync */
 gpe_status gpe_get_bonds_info(gpe_ctx *ctx, gpe_bonds_info *info); /* synchronises (reads the device counter) */
 
+/* ---- the bonds' solver: Jacobi or coloured Gauss-Seidel (not in the reference) ------------------------------------
+ * A mode of the bonds' pass, off (GPE_BOND_SOLVER_JACOBI) by default; step state like gpe_set_collider_sweep: allowed
+ * with no set present, it outlives gpe_set_bonds, every add, removal, edit and re-sort, and gpe_set_world.  Jacobi
+ * judges every bond from the positions a relaxation starts with: stable only up to a stiffness of 1 / (bonds per
+ * particle), and slow along chains.  GPE_BOND_SOLVER_COLOURED relaxes the bonds one colour after the other, every
+ * bond seeing the corrections of the colours before it: stiffness 1 is stable whatever the degree, and a hanging rope
+ * keeps about a quarter of the excess stretch Jacobi leaves it at the same number of relaxations.  The place of the
+ * pass, gpe_get_bonds, gpe_get_bonds_info, gpe_apply_bonds and the broken flags are the same in both modes.
+ *  - The colouring (csrc/bond_colours.h is the one definition) is a function of the set alone.  In ascending bond
+ *    index j, colour[j] = the least c >= 0 that no bond of lower index has taken at particle uid_a, nor at uid_b for a
+ *    pair (an anchor occupies uid_a only).  Broken bonds, bonds whose uid no particle has and both twins of a bond
+ *    listed twice are coloured too.  No two bonds of one colour share a particle.
+ *  - One coloured relaxation: for c = 0 .. colours - 1, every bond of colour c is judged as above (the same d, break,
+ *    e, f, g, cx, cy, the same w) from the positions as they are NOW; where it acts, a moves to
+ *    clamp(a + (cx, cy)) and, for a pair, b to clamp(b + (-cx, -cy)), K12's clamp with the particle's own radius; where
+ *    it breaks, it is broken from then on; inert otherwise.  Within a colour no position has two writers, so the
+ *    result equals a sequential sweep of the bonds in (colour, index) order: a binary32 function of the set and the
+ *    particles alone, never of launch order, storage order or pipeline mode -- but the order of the colours, and so
+ *    the order of the bonds in the set, is part of the result.  A pass runs `iterations` such relaxations and writes
+ *    pos only.
+ *  - What it is not: the bends and the areas stay Jacobi; a set that needs more than GPE_BOND_COLOURS_MAX colours is
+ *    refused (greedy needs at most 2 * degree - 1, so every set of at most 32 bonds per particle fits; a hub of 200
+ *    bonds stays with Jacobi); there is no coloured solver in sharded runs.
+ *  - gpe_set_bond_solver synchronises; over a set it builds (COLOURED) or frees (JACOBI) the colour tables, keeps the
+ *    set, its broken flags and its counters, and zeroes `passes` and `form` of the info below.  Under COLOURED,
+ *    gpe_set_bonds builds the tables with the set.  With the mode JACOBI the kernels launched, the buffers held and
+ *    every bit are those of a context that never heard of the mode.
+ *  - gpe_get_bond_solver_info: the mode; colours and largest_colour of the set held (0 without one, or under JACOBI);
+ *    form: how the last coloured pass ran -- 0 none yet, 1 one launch per colour and relaxation, 2 one launch of one
+ *    workgroup that keeps the set's particles in LDS, taken when the set names at most lds_nodes_max particles; both
+ *    forms give the same bits.
+ *  - Errors (the previous set, mode and tables stay untouched): a NULL ctx, an unknown mode, a struct_size below the
+ *    struct's, and -- from gpe_set_bond_solver(COLOURED) over a set as from gpe_set_bonds under COLOURED -- a set
+ *    that needs more than GPE_BOND_COLOURS_MAX colours (the message names the count): GPE_ERR_INVALID_ARG.  A sharded
+ *    context: GPE_ERR_UNSUPPORTED -- for either mode, JACOBI included, though it is what such a context runs anyway:
+ *    the call is refused as a whole there, like gpe_set_collider_sweep, and gpe_get_bond_solver reads JACOBI. */
+#define GPE_BOND_COLOURS_MAX      64u
+#define GPE_BOND_SOLVER_JACOBI    0u
+#define GPE_BOND_SOLVER_COLOURED  1u
+typedef struct gpe_bond_solver_info {
+    uint32_t struct_size, mode;        /* in / GPE_BOND_SOLVER_*                                               */
+    uint32_t colours, largest_colour;  /* of the set held under COLOURED: colours / bonds in the fullest one  */
+    uint32_t form, lds_nodes_max;      /* the last coloured pass's launch form (0, 1, 2) / form 2's node limit */
+    uint64_t passes;                   /* coloured passes enqueued since the last gpe_set_bond_solver          */
+} gpe_bond_solver_info;                /* 32 bytes */
+gpe_status gpe_set_bond_solver(gpe_ctx *ctx, uint32_t mode);          /* synchronises */
+gpe_status gpe_get_bond_solver(gpe_ctx *ctx, uint32_t *mode);
+gpe_status gpe_get_bond_solver_info(gpe_ctx *ctx, gpe_bond_solver_info *info);
+
 /* ---- bend constraints (not in the reference) ----------------------------------------------------------------------
  * Angles between bonded particles: a rope with stiffness, grass and hair that spring back, a cloth that resists
  * folding, an articulated shape that holds a rest angle.  A bend names three distinct particles by uid (gpe_enable_uids
