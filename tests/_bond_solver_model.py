@@ -5,7 +5,7 @@ uids up afresh.  TEST INFRASTRUCTURE ONLY.
 
 colours() colours a set, relax() is one coloured relaxation, apply() a pass of `iterations` of them.  Mixin gives a twin
 that holds bonds (tests/_bonds_model.Twin and everything above it) the solver's mode; Twin is the bonds' twin with it,
-Everything the composed twin with it.  hostile_scene() is tests/test_gpu_bonds._pass_scene with the hub cut to degree 30
+and tests/_everything_model.Everything, the composed twin, has it in front of its bases.  hostile_scene() is tests/test_gpu_bonds._pass_scene with the hub cut to degree 30
 (a hub of 200 needs more than 64 colours) and the late break moved to where a coloured sweep puts it; table_text() the
 table tests/cpp/bond_colours_tests.cpp replays."""
 import numpy as np
@@ -131,12 +131,11 @@ class Twin(Mixin, BM.Twin):
 
 
 def everything_class():
-    """tests/_everything_model.Everything with the solver's mode (imported late: that module imports GPU test files)"""
+    """tests/_everything_model.Everything, which has this file's Mixin in front of its bases (imported late: that module
+    imports this one, and GPU test files)"""
     from tests import _everything_model as EV
-
-    class Everything(Mixin, EV.Everything):
-        pass
-    return Everything
+    assert EV.Everything.__mro__[1] is Mixin
+    return EV.Everything
 
 
 # ---- the hostile scene ----------------------------------------------------------------------------------------------

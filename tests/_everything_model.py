@@ -1,12 +1,14 @@
-"""Every pass behind a step armed at once: bends -> areas -> bonds -> bodies -> movers (plain / surfaces / swept) ->
-static colliders (plain / surfaces / swept) -> fields, the order of gpe_step and gpe_run (csrc/gpe_api.hip).  TEST
-INFRASTRUCTURE ONLY.
+"""Every pass behind a step armed at once: bends -> areas -> bonds (Jacobi / coloured) -> bodies -> movers (plain /
+surfaces / swept) -> static colliders (plain / surfaces / swept) -> fields, the order of gpe_step and gpe_run
+(csrc/gpe_api.hip).  TEST INFRASTRUCTURE ONLY.
 
 Everything is one twin over the three chains of twins the features' own tests use (tests/_bodies_model.Twin: bonds,
 bodies, plain colliders; tests/_areas_model.Twin: bends, areas, bonds, plain colliders; tests/_sweep_model.Twin: movers,
-surfaces, sweep, fields) with the movers' sweep of tests/_mover_sweep_model.Mixin in front.  It writes no physics: every
-pass is the model function its feature's tests pin against the device, and tests/test_everything_cpu.py ties it bit for
-bit to the four existing twins.  THE NEXT PASS BEHIND A STEP IS ADDED HERE: its twin into the bases, its call into step().
+surfaces, sweep, fields) with the movers' sweep of tests/_mover_sweep_model.Mixin and the bonds' solver of
+tests/_bond_solver_model.Mixin in front.  It writes no physics: every pass is the model function its feature's tests
+pin against the device, and tests/test_everything_cpu.py ties it bit for bit to the five existing twins.  THE NEXT PASS
+BEHIND A STEP IS ADDED HERE: its twin into the bases, its call into step(), its arm into ARMS, arm(), armed(),
+counters(), state_counters() and reloaded(), its blocks into BLOCKS and what they must reach into Coverage.check().
 
 scene() is the staged scene of the CPU and GPU tests, arm() sets its features on a twin or on a State (their methods
 share names), plan(seed) a list of operations and Sequence the thing that applies them to a twin and, when it has one, to
@@ -22,6 +24,7 @@ import numpy as np
 from tests import _areas_model as AM
 from tests import _bends_model as NM
 from tests import _bodies_model as BD
+from tests import _bond_solver_model as BS
 from tests import _bonds_model as BM
 from tests import _fields_model as FM
 from tests import _mover_sweep_model as MS
@@ -36,23 +39,25 @@ DT = 1.0 / 60.0
 DTS = (1.0 / 60.0, 1.0 / 120.0)
 STEPS = 40
 SEEDS = (1, 2, 3)
-ARMS = ("bends", "areas", "bonds", "bodies", "movers", "mover_surfaces", "mover_sweep", "colliders", "collider_surfaces",
-        "sweep", "fields")
-# the arrays of a snapshot that holds all twelve optional groups (State.save; the movers' poses belong to the movers'
-# group, the relaxation counts and the loops' members to the bends' and the areas')
-GROUPS = ("colliders", "collider_surfaces", "collider_sweep", "bonds", "bends", "bend_iterations", "areas",
+ARMS = ("bends", "areas", "bonds", "bond_solver", "bodies", "movers", "mover_surfaces", "mover_sweep", "colliders",
+        "collider_surfaces", "sweep", "fields")
+# the arrays of a snapshot that holds all thirteen optional groups (State.save; the movers' poses belong to the movers'
+# group, the relaxation counts and the loops' members to the bends' and the areas'; the bonds' solver is written where
+# bonds are held and it is the coloured one)
+GROUPS = ("colliders", "collider_surfaces", "collider_sweep", "bonds", "bond_solver", "bends", "bend_iterations", "areas",
           "area_member_uid", "area_iterations", "bodies", "fields", "movers", "mover_poses", "mover_surfaces", "mover_sweep",
           "uids")
 
 
-class Everything(MS.Mixin, BD.Twin, AM.Twin, SW.Twin):
-    """One context with all ten features: the MRO runs through the three chains once, every constructor is cooperative;
-    the mixin in front makes self.m a set that holds the movers' sweep (a mode of the context, not of the set)."""
+class Everything(BS.Mixin, MS.Mixin, BD.Twin, AM.Twin, SW.Twin):
+    """One context with all eleven features: the MRO runs through the three chains once, every constructor is
+    cooperative; the movers' mixin makes self.m a set that holds the movers' sweep, the solver's mixin in front keeps
+    the bonds' solver and the colours of the set held (both modes of the context, not of a set)."""
 
     def __init__(self, *a, **kw):
         super().__init__(*a, **kw)
         self.field_passes = self.field_touched = self.field_changed = 0
-        self.bend_changed = self.area_changed = 0
+        self.bend_changed = self.area_changed = self.coloured_changed = 0
 
     def _changed_by(self, apply):
         """run a pass of a twin below -> the rows whose pos bits it changed"""
@@ -67,6 +72,14 @@ class Everything(MS.Mixin, BD.Twin, AM.Twin, SW.Twin):
     def apply_areas(self):
         """gpe_apply_areas: the areas' twin's pass (tests/_areas_model.apply); area_changed counts the rows it changed"""
         self.area_changed += self._changed_by(super().apply_areas)
+
+    def apply_bonds(self):
+        """gpe_apply_bonds: the bonds' twin's pass, or the solver's coloured one; coloured_changed counts the rows a
+        coloured pass changed"""
+        coloured = self.bond_solver == BS.COLOURED
+        changed = self._changed_by(super().apply_bonds)
+        if coloured:
+            self.coloured_changed += changed
 
     def set_fields(self, fields):
         super().set_fields(fields)
@@ -97,7 +110,8 @@ class Everything(MS.Mixin, BD.Twin, AM.Twin, SW.Twin):
     def armed(self):
         """-> the arms that are set"""
         on = dict(bends=len(self.bends) > 0, areas=len(self.areas) > 0,
-                  bonds=len(self.bonds) > 0, bodies=len(self.bodies) > 0, movers=len(self.m) > 0,
+                  bonds=len(self.bonds) > 0, bond_solver=self.bond_solver == BS.COLOURED,
+                  bodies=len(self.bodies) > 0, movers=len(self.m) > 0,
                   mover_surfaces=self.m.surfaces is not None, mover_sweep=self.m.sweep, colliders=len(self.colliders) > 0,
                   collider_surfaces=self.collider_surfaces is not None, sweep=self.sweep, fields=len(self.fields) > 0)
         return tuple(a for a in ARMS if on[a])
@@ -107,8 +121,12 @@ class Everything(MS.Mixin, BD.Twin, AM.Twin, SW.Twin):
 
     def reloaded(self):
         """State.save() / State.load(): every set is set anew (its counters start again, the body poses are unknown
-        until a pass), the broken flags, the movers' states and the two sweeps' modes are kept"""
+        until a pass), the broken flags, the movers' states, the two sweeps' modes and the bonds' solver with the
+        colours of its set are kept.  (A coloured mode over no bonds is not written: it comes back as Jacobi.)"""
         self.passes = self.pushed = 0
+        self.solver_passes = 0
+        if len(self.bonds) == 0:
+            self.bond_solver, self.bond_colour = BS.JACOBI, np.zeros(0, np.int64)
         self.bend_passes = self.area_passes = 0
         self.area_value = np.full((len(self.areas), 2), np.nan, F32)   # (as set_areas leaves it: no pass yet)
         self.bond_passes = self.body_passes = 0
@@ -125,12 +143,14 @@ class Everything(MS.Mixin, BD.Twin, AM.Twin, SW.Twin):
                     sweep=dict(mode=int(self.sweep), passes=self.sweep_passes, swept=self.swept, stopped=self.stopped),
                     mover_sweep=self.mover_sweep_info(),
                     bends=self.bends_info(), areas=self.areas_info(), bonds=self.bonds_info(), bodies=self.bodies_info(),
+                    bond_solver=self.bond_solver_info(),
                     fields=dict(k=len(self.fields), passes=self.field_passes if len(self.fields) else 0,
                                 touched=self.field_touched if len(self.fields) else 0))
 
 
 def state_counters(st):
-    """the same dict from a State (the grids' sizes and the uid lookups, which the model does not have, left out)"""
+    """the same dict from a State (the grids' sizes, the uid lookups and the solver's launch form and LDS limit, which
+    the model does not have, left out)"""
     pick = lambda info, names: {k: info[k] for k in names}
     bends, areas, bonds, bodies = st.bends_info(), st.areas_info(), st.bonds_info(), st.bodies_info()
     for info in (bends, areas, bonds, bodies):
@@ -138,6 +158,7 @@ def state_counters(st):
     return dict(colliders=pick(st.colliders_info(), ("k", "passes", "pushed")),
                 movers=pick(st.movers_info(), ("k", "passes", "pushed")), sweep=st.sweep_info(),
                 mover_sweep=st.mover_sweep_info(), bends=bends, areas=areas, bonds=bonds, bodies=bodies,
+                bond_solver=pick(st.bond_solver_info(), ("mode", "colours", "largest_colour", "passes")),
                 fields=pick(st.fields_info(), ("k", "passes", "touched")))
 
 
@@ -158,6 +179,7 @@ RING = 16
 RINGS = (((11.5, 29.0), False), ((42.0, 13.0), True), ((22.5, 13.0), False))
 RING_PRESSURE = (1.0, 1.1, 0.9)
 RING_FIRST = N - SHOTS - RING * len(RINGS)                             # the rings' uids: behind the fill, before the shots
+FALLER, TIE_LENGTH = RING_FIRST + RING + 2, 1.5                        # a member of the second ring and the tie that lets it go
 BLOB = 7                                                               # the yard's soft body: its 16 outer members carry a loop
 BEND_STIFFNESS, AREA_STIFFNESS, EDGE_STIFFNESS = 0.1, 0.8, 0.25
 Scene = collections.namedtuple("Scene", "pos prev rad bonds iterations bodies member_uid member_rest colliders "
@@ -179,8 +201,8 @@ def scene():
     the floor, three RINGS, and eight shots: particles below the corner that leave for its apex at 6 units per step.
     Every ring, and the ring of the blob's 16 outer members, carries bonds along its edge, a bend at every member (one
     relaxation) and one area constraint (two): a member of the blob's ring is a bend node, an area member, a bond end
-    and a body member at once.  The movers are tests/_movers_model.run_movers' thick piston and paddle, then
-    THIN_MOVERS."""
+    and a body member at once.  The last bond is a tie that breaks when FALLER has fallen TIE_LENGTH.  The movers are
+    tests/_movers_model.run_movers' thick piston and paddle, then THIN_MOVERS."""
     from tests.test_gpu_areas import ring
     from tests.test_gpu_bodies import YARD_COLLIDERS, yard_scene
     pos, rad, bodies, member_uid, member_rest, bonds = yard_scene()
@@ -211,7 +233,10 @@ def scene():
     uid = np.stack(loops)
     nxt, prv = np.roll(uid, -1, axis=1), np.roll(uid, 1, axis=1)
     rest = np.repeat([1.1] * len(RINGS) + [1.05], RING)                # a little over the spacing the loops start with
-    bonds = np.concatenate([bonds, BM.pairs(uid.ravel(), nxt.ravel(), rest, EDGE_STIFFNESS)])
+    # ... and a tie of stiffness 0 from a member of the ring that falls over the paddle to where it starts: it moves
+    # nothing and breaks once the member is TIE_LENGTH away, under either solver
+    bonds = np.concatenate([bonds, BM.pairs(uid.ravel(), nxt.ravel(), rest, EDGE_STIFFNESS),
+                            BM.anchors([FALLER], [pos[FALLER]], 0.0, 0.0, TIE_LENGTH)])
     start = np.arange(N, dtype=U32)
     bends = NM.captured(pos, start, np.stack([prv.ravel(), uid.ravel(), nxt.ravel()], axis=1), BEND_STIFFNESS)
     areas, area_member_uid = AM.captured(pos, start, loops, AREA_STIFFNESS, RING_PRESSURE + (1.0,))
@@ -224,13 +249,40 @@ def scene():
                  bends, 1, areas, area_member_uid, 2)
 
 
+def wide_scene(lds_nodes_max):
+    """scene() with ties of stiffness 0 along the fill until the bonds name more than lds_nodes_max uids
+    (gpe_get_bond_solver_info): a coloured pass over it takes the per-colour launch form.  Neighbouring uids no bond of
+    the scene names are tied in disjoint pairs, every third tie with a max_length a shove breaks; a uid left over gets
+    an anchor where it starts; past the scene's particles the ties name uids nobody has (nodes all the same)."""
+    sc = scene()
+    named = np.zeros(N, bool)
+    named[np.concatenate([sc.bonds["uid_a"], sc.bonds["uid_b"][(sc.bonds["flags"] & BM.BOND_ANCHOR) == 0]])] = True
+    loose = np.nonzero(~named)[0].astype(U32)
+    a, b = loose[0:len(loose) - 1:2], loose[1::2]
+    ties = [BM.pairs(a, b, 1.0, 0.0, np.where(np.arange(len(a)) % 3 == 0, 1.6, 0.0).astype(F32))]
+    if len(loose) % 2:
+        ties.append(BM.anchors(loose[-1:], sc.pos[loose[-1:]], 0.0, 0.0))
+    short = lds_nodes_max + 1 - N
+    if short > 0:
+        absent = N + 7 + np.arange(short + short % 2, dtype=U32)
+        ties.append(BM.pairs(absent[0::2], absent[1::2], 1.0, 0.0))
+    bonds = np.concatenate([sc.bonds] + ties)
+    assert BM.node_count(bonds) > lds_nodes_max and BS.colour_info(bonds)[0] <= BS.COLOURS_MAX
+    ends = np.concatenate([bonds["uid_a"], bonds["uid_b"][(bonds["flags"] & BM.BOND_ANCHOR) == 0]])
+    assert np.unique(ends, return_counts=True)[1].max() <= BM.BOND_MAX_DEGREE
+    return sc._replace(bonds=bonds)
+
+
 def arm(h, sc, arms=ARMS):
     """set the features of `arms` on a twin or a State (uids on already); a set left out leaves its surfaces out, but
-    not the movers' sweep: the mode is the context's, on with no movers held as well"""
+    not the movers' sweep nor the bonds' solver: the modes are the context's, on with no movers and no bonds held as
+    well.  The solver is set in front of its set (the plans cover the other order)."""
     if "bends" in arms:
         h.set_bends(sc.bends, sc.bend_iterations)
     if "areas" in arms:
         h.set_areas(sc.areas, sc.area_member_uid, sc.area_iterations)
+    if "bond_solver" in arms:
+        h.set_bond_solver("coloured")
     if "bonds" in arms:
         h.set_bonds(sc.bonds, sc.iterations)
     if "bodies" in arms:
@@ -289,9 +341,12 @@ BLOCKS = ([["set_" + s, "step", "clear_" + s, "step", "set_" + s] for s in SETS]
     ["remove_circle", "step"], ["remove_members", "step"], ["remove_uid"], ["edit_pos", "step"],
     ["radius_up", "step", "radius_down", "step"], ["kick", "step"], ["world_grow", "step", "world_back", "step"], ["gravity"],
     ["other_mode"], ["save_load", "step"], ["pump", "step"], ["apply_bends"], ["apply_areas"], ["apply_bonds"],
-    ["apply_bodies"], ["apply_movers"], ["apply_colliders"], ["apply_fields"]])
+    ["apply_bodies"], ["apply_movers"], ["apply_colliders"], ["apply_fields"],
+    # the bonds' solver: switched with the set held, set while already on, and a set it cannot take
+    ["solver_jacobi", "step", "solver_coloured", "step"], ["solver_coloured_again", "step"], ["refuse_65_colours", "step"]])
 REPLACING = (["set_" + s for s in SETS + ("colliders", "movers", "mover_poses")] + ["clear_" + s for s in SETS + ("colliders", "movers")]
-             + ["sweep_off", "sweep_on", "mover_sweep_off", "mover_sweep_on"])
+             + ["sweep_off", "sweep_on", "mover_sweep_off", "mover_sweep_on"]
+             + ["solver_jacobi", "solver_coloured", "solver_coloured_again", "refuse_65_colours"])
 
 
 def plan(seed):
@@ -302,8 +357,8 @@ def plan(seed):
     order = rng.permutation(len(BLOCKS))
     ops = ["run_start"] + [op for i in order for op in BLOCKS[i]]
     # the opening run and every block once: seven sets of 5, two of 7, 2 x 3 + 2 for the modes and the poses, 3 runs,
-    # 9 blocks of 2 (the pump's among them), 2 of 4, 3 single operations and the 7 passes
-    assert len(ops) == 1 + 7 * 5 + 2 * 7 + 8 + 3 + 9 * 2 + 2 * 4 + 3 + 7 == 97
+    # 9 blocks of 2 (the pump's among them), 2 of 4, 3 single operations, the 7 passes and the solver's 4 + 2 + 2
+    assert len(ops) == 1 + 7 * 5 + 2 * 7 + 8 + 3 + 9 * 2 + 2 * 4 + 3 + 7 + 8 == 105
     return Plan(seed, ops)
 
 
@@ -313,11 +368,14 @@ class Coverage(collections.Counter):
     def check(self):
         need = (["armed_" + k for k in ("colliders_pushed", "movers_pushed", "swept", "stopped", "mover_swept", "mover_stopped",
                                         "body_broke", "field_changed", "bend_changed", "area_changed", "resort", "growth",
-                                        "removal_of_member_and_bonded", "loop_lost_a_member", "pump", "radius_up")]
-                + ["set_world_with_grids", "save_load_every_group", "run_resorts_in_its_middle"] + ["op_" + op for op in REPLACING])
+                                        "removal_of_member_and_bonded", "loop_lost_a_member", "pump", "radius_up",
+                                        "bond_broke_under_coloured", "coloured_changed")]
+                + ["set_world_with_grids", "save_load_every_group", "run_resorts_in_its_middle"] + ["op_" + op for op in REPLACING]
+                + ["solver_switched_with_a_broken_bond_held", "save_load_with_the_mode_and_a_broken_bond",
+                   "growth_under_coloured", "removal_of_bonded_under_coloured"])
         missing = [k for k in need if self[k] == 0]
         assert not missing, "the sequence never reached: %s\n%s" % (", ".join(missing), dict(self))
-        assert self["armed_steps"] >= 30, "only %d steps with all eleven arms set" % self["armed_steps"]
+        assert self["armed_steps"] >= 30, "only %d steps with all twelve arms set" % self["armed_steps"]
 
 
 class Sequence:
@@ -389,7 +447,9 @@ class Sequence:
         return dict(colliders_pushed=tw.pushed, movers_pushed=tw.m.pushed, swept=tw.swept, stopped=tw.stopped,
                     mover_swept=tw.m.swept, mover_stopped=tw.m.stopped,
                     body_broke=int(tw.bodies_broken.sum()), field_changed=tw.field_changed,
-                    bend_changed=tw.bend_changed, area_changed=tw.area_changed)
+                    bend_changed=tw.bend_changed, area_changed=tw.area_changed,
+                    # (counted over fully armed steps, where the solver is the coloured one)
+                    bond_broke_under_coloured=int(tw.broken.sum()), coloured_changed=tw.coloured_changed)
 
     def _twin_step(self, dt, resort):
         armed = self.tw.fully_armed()
@@ -466,6 +526,7 @@ class Sequence:
             self.cap = max(n + len(r), 2 * self.cap)
             if self.tw.fully_armed():
                 self.cov["armed_growth"] += 1
+                self.cov["growth_under_coloured"] += 1
         self.log.append("%s %d%s" % (what, len(r), " (grew to %d)" % self.cap if grew else ""))
 
     def op_add_few(self):
@@ -507,6 +568,8 @@ class Sequence:
         q += [rng.choice(node)] if len(node) else []
         if armed and len(member) and len(bonded):
             self.cov["armed_removal_of_member_and_bonded"] += 1
+        if armed and len(bonded):
+            self.cov["removal_of_bonded_under_coloured"] += 1
         if armed and len(looped) and len(node):
             self.cov["armed_loop_lost_a_member"] += 1
         q = np.unique(np.concatenate([q, rng.choice(tw.uids, 2, replace=False), [tw.next_uid + 3]]).astype(U32))
@@ -590,6 +653,8 @@ class Sequence:
         every = tw.fully_armed()
         if every:
             self.cov["save_load_every_group"] += 1
+        if every and tw.broken.any():
+            self.cov["save_load_with_the_mode_and_a_broken_bond"] += 1
         if self.st is not None:
             path = os.path.join(self.tmp.name, "snap_%d.npz" % len(self.log))
             self.st.save(path)
@@ -694,11 +759,12 @@ class Sequence:
         self._set("set_areas", np.zeros(0, AM.AREA_DTYPE), np.zeros(0, U32), 1, what="clear areas")
 
     def op_set_bonds(self):
-        """anchors that hold particles where they are, pairs of neighbours (some that snap), one uid nobody has"""
+        """anchors that hold particles where they are, a tie of stiffness 0 between two of them that breaks in its first
+        relaxation unless they touch, pairs of neighbours (some that snap), one uid nobody has"""
         rng, tw = self.rng, self.tw
         p = tw.arrays()[0]
         pins = rng.choice(len(tw), 4, replace=False)
-        rows = [BM.anchors(tw.uids[pins], p[pins], 0.0, 0.5)]
+        rows = [BM.anchors(tw.uids[pins], p[pins], 0.0, 0.5), BM.pairs([tw.uids[pins[1]]], [tw.uids[pins[2]]], 1.0, 0.0, 1.0)]
         for _ in range(5):
             a = int(rng.integers(0, len(tw)))
             near = self._near(a, 3, np.ones(len(tw), bool))
@@ -823,3 +889,47 @@ class Sequence:
             self.st.particles.set_mover_sweep(True)
         self.tw.set_mover_sweep(True)
         self.log.append("mover sweep on (ParticleSystem)")
+
+    # ---- the bonds' solver --------------------------------------------------------------------------------------------
+    def _solver(self, solver, what):
+        tw = self.tw
+        held = len(tw.bonds) > 0
+        if solver == "coloured" and tw.bond_solver == BS.JACOBI and held and tw.broken.any():
+            self.cov["solver_switched_with_a_broken_bond_held"] += 1   # (the tables are built from the kept set)
+        self._set("set_bond_solver", solver, what="%s (%d bonds held, %d broken)" % (what, len(tw.bonds), int(tw.broken.sum())))
+
+    def op_solver_jacobi(self):
+        assert self.tw.bond_solver == BS.COLOURED and len(self.tw.bonds) > 0
+        self._solver("jacobi", "solver: jacobi")
+
+    def op_solver_coloured(self):
+        assert self.tw.bond_solver == BS.JACOBI and len(self.tw.bonds) > 0
+        self._solver("coloured", "solver: coloured")
+
+    def op_solver_coloured_again(self):
+        """the mode set while it is on: the tables are kept, the solver's counters start again"""
+        colour = self.tw.bond_colour.copy()
+        assert self.tw.bond_solver == BS.COLOURED and len(colour) > 0
+        self._solver("coloured", "solver: coloured again")
+        assert np.array_equal(self.tw.bond_colour, colour) and self.tw.solver_passes == 0
+
+    def op_refuse_65_colours(self):
+        """a star of 65 bonds on one live uid needs 65 colours: refused, the set held stays"""
+        tw, rng = self.tw, self.rng
+        assert tw.bond_solver == BS.COLOURED
+        hub = int(rng.choice(tw.uids))
+        star = BM.pairs(np.full(65, hub), rng.choice(tw.uids[tw.uids != hub], 65, replace=False), 3.0, 0.01)
+        held = tw.bonds.copy()
+        try:
+            tw.set_bonds(star, 1)
+            raise AssertionError("the twin took a set of 65 colours")
+        except BS.Refused:
+            pass
+        assert tw.bonds.tobytes() == held.tobytes()
+        if self.st is not None:
+            try:
+                self.st.set_bonds(star, 1)
+                raise AssertionError("the context took a set of 65 colours")
+            except self.gpe.GpeError as e:
+                assert e.status == self.L.GPE_ERR_INVALID_ARG, e
+        self.log.append("a star of 65 on uid %d: refused" % hub)

@@ -1,12 +1,15 @@
-"""CPU: the composed twin of tests/_everything_model.py (bends, areas, bonds, bodies, movers with surfaces and their
-sweep, static colliders with surfaces and the sweep, fields, all behind one step) before any GPU time is spent on it: it
-is no new oracle (bit for bit the four existing twins where only their features are set), its scene acts and tells every
-arm apart, and its random plans reach what tests/test_gpu_everything.py needs them to reach."""
+"""CPU: the composed twin of tests/_everything_model.py (bends, areas, bonds under either solver, bodies, movers with
+surfaces and their sweep, static colliders with surfaces and the sweep, fields, all behind one step) before any GPU time
+is spent on it: it is no new oracle (bit for bit the four existing twins where only their features are set, and the
+solver's twin with the coloured solver on), its scene acts and tells every arm apart, and its random plans reach what
+tests/test_gpu_everything.py needs them to reach."""
 import numpy as np
 import pytest
 
 from tests import _areas_model as AM
 from tests import _bodies_model as BD
+from tests import _bond_solver_model as BS
+from tests import _bonds_model as BM
 from tests import _everything_model as E
 from tests import _mover_sweep_model as MS
 from tests import _sweep_model as SW
@@ -52,11 +55,51 @@ def test_with_the_yards_features_alone_it_is_the_bodies_twin(oracle):
     old.close(); new.close()
 
 
+def test_with_the_yards_features_and_the_coloured_solver_it_is_the_solvers_twin(oracle):
+    """bonds under the coloured solver, bodies and the yard's colliders: the frames, the broken flags and the solver's
+    info of tests/_bond_solver_model.Twin chained as the bodies' twin (its pass in the bonds' place of
+    tests/_bodies_model.Twin.step) over the yard's 60 steps; the mode set before the set on one pair, behind it on the
+    other"""
+    from tests.test_gpu_bodies import STEPS, YARD_COLLIDERS, YARD_GRAVITY, YARD_WORLD, yard_scene
+
+    class Chained(BD.Twin, BS.Twin):
+        pass
+    assert Chained.__mro__[1:4] == (BD.Twin, BS.Twin, BS.Mixin) and Chained.apply_bonds is BS.Mixin.apply_bonds
+    pos, rad, bodies, member_uid, member_rest, bonds = yard_scene()
+    bonds = bonds.copy()
+    bonds["max_length"][-1] = F32(1.01) * bonds["rest_length"][-1]     # (a bond that breaks on the way)
+    for first in (True, False):
+        twins = []
+        for cls in (Chained, E.Everything):
+            tw = cls(oracle, pos, rad, world=YARD_WORLD, gravity=YARD_GRAVITY)
+            tw.enable_uids()
+            if first:
+                tw.set_bond_solver("coloured")
+            tw.set_bonds(bonds, 2); tw.set_bodies(bodies, member_uid, member_rest); tw.set_colliders(YARD_COLLIDERS)
+            if not first:
+                tw.set_bond_solver("coloured")
+            twins.append(tw)
+        old, new = twins
+        for s in range(STEPS):
+            old.step(E.DT); new.step(E.DT)
+            for a, b in zip(old.arrays(), new.arrays()):
+                assert same_bits(a, b), s
+            assert same_bits(old.poses, new.poses) and np.array_equal(old.bodies_broken, new.bodies_broken), s
+            assert np.array_equal(old.broken, new.broken), s
+        assert old.bodies_broken.any() and old.pushed == new.pushed > 0 and new.coloured_changed > 0
+        assert old.broken.any() and not old.broken.all()
+        assert old.bonds_info() == new.bonds_info() and old.bodies_info() == new.bodies_info()
+        assert old.bond_solver_info() == new.bond_solver_info() and new.bond_solver_info()["passes"] == STEPS
+        print(new.bonds_info(), new.bond_solver_info())
+        assert new.armed() == ("bonds", "bond_solver", "bodies", "colliders")
+        old.close(); new.close()
+
+
 def test_with_the_sweeps_features_alone_it_is_the_sweep_twin(oracle):
     """movers, colliders, both surfaces, the sweep and fields over scene(): the frames of tests/_sweep_model.Twin (which
     has no movers' sweep: the thin movers run the plain pass)"""
     sc = E.scene()
-    arms = tuple(a for a in E.ARMS if a not in ("bends", "areas", "bonds", "bodies", "mover_sweep"))
+    arms = tuple(a for a in E.ARMS if a not in ("bends", "areas", "bonds", "bond_solver", "bodies", "mover_sweep"))
     twins = []
     for cls in (SW.Twin, E.Everything):
         tw = cls(oracle, sc.pos, sc.rad, world=E.WORLD, gravity=E.GRAVITY, prev=sc.prev)
@@ -78,7 +121,7 @@ def test_with_both_sweeps_and_no_bonds_or_bodies_it_is_the_mover_sweep_twin(orac
     """movers, both surfaces, colliders, both sweeps and fields over scene(): the frames, the mover poses and the swept
     pass's counters of tests/_mover_sweep_model.Twin"""
     sc = E.scene()
-    arms = tuple(a for a in E.ARMS if a not in ("bends", "areas", "bonds", "bodies"))
+    arms = tuple(a for a in E.ARMS if a not in ("bends", "areas", "bonds", "bond_solver", "bodies"))
     twins = []
     for cls in (MS.Twin, E.Everything):
         tw = cls(oracle, sc.pos, sc.rad, world=E.WORLD, gravity=E.GRAVITY, prev=sc.prev)
@@ -128,7 +171,7 @@ def test_the_scene_acts(full):
     frames, counters, first_break, field_changed = full
     sc = E.scene()
     assert len(sc.rad) == E.N == 1025 and (sc.collider_surfaces["flags"] == 1).any()
-    assert len(E.ARMS) == 11 and len(sc.movers) == 4 and (sc.movers["radius"] == 0).sum() == 2
+    assert len(E.ARMS) == 12 and len(sc.movers) == 4 and (sc.movers["radius"] == 0).sum() == 2
     # four loops, either sense among the rings; a particle that is a bend node, a loop's member, a bond's end and a
     # member of a body at once, and its body live at the end
     loops = E.scene_loops(sc.bodies)
@@ -146,8 +189,39 @@ def test_the_scene_acts(full):
     assert counters["mover_sweep"]["swept"] > 0 and counters["mover_sweep"]["stopped"] > 0
     assert counters["bodies"]["broken"] >= 1 and first_break < 15       # (test_gpu_everything saves after 15 steps)
     assert counters["bodies"]["broken"] < counters["bodies"]["k"]      # (... and needs a body that is not broken)
+    # a bond breaks under the coloured pass, before the save as well: the tie, and nothing else
+    first_snap = next(s for s, f in enumerate(frames) if f.bonds_broken.any())
+    assert counters["bond_solver"]["mode"] == BS.COLOURED and counters["bond_solver"]["passes"] == E.STEPS
+    assert 0 < first_snap < 15 and frames[first_snap].bonds_broken[-1] and counters["bonds"]["broken"] >= 1
+    assert counters["bond_solver"]["colours"] >= 3 and counters["bonds"]["nodes"] <= 1024
     assert counters["bonds"]["passes"] == counters["bodies"]["passes"] == counters["sweep"]["passes"] == E.STEPS
     assert counters["movers"]["passes"] == counters["fields"]["passes"] == counters["mover_sweep"]["passes"] == E.STEPS
+
+
+def test_the_wide_scene_names_more_particles_than_one_workgroup_takes(oracle, full):
+    """wide_scene(limit): more nodes than the limit (the library's policy constant here; the GPU test asks the device),
+    within GPE_BOND_MAX_DEGREE and 64 colours.  Its ties have stiffness 0 and follow the scene's bonds, whose colours
+    they leave alone: the particles' bits are the scene's, some ties break on the way."""
+    import os
+    import re
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    internal = open(os.path.join(root, "gpu-physics-engine_amd", "csrc", "gpe_internal.h")).read()
+    policy = int(re.search(r"#define GPE_BOND_LDS_NODES_MAX (\d+)", internal).group(1))
+    base = E.scene()
+    for limit in (policy, E.N - 1, E.N + 41):                          # (past the particles: uids nobody has)
+        sc = E.wide_scene(limit)
+        assert BM.node_count(sc.bonds) > limit and sc.bonds[:len(base.bonds)].tobytes() == base.bonds.tobytes()
+        assert np.array_equal(BS.colours(sc.bonds)[:len(base.bonds)], BS.colours(base.bonds))
+        assert BS.colour_info(sc.bonds)[0] <= BS.COLOURS_MAX
+    tw = E.twin(oracle, sc=E.wide_scene(policy))
+    frames = E.frames(tw)
+    counters = tw.counters()
+    tw.close()
+    for s, (f, g) in enumerate(zip(frames, full[0])):
+        assert same_bits(f.pos, g.pos) and same_bits(f.prev, g.prev), s
+    print(counters["bonds"], counters["bond_solver"])
+    assert counters["bonds"]["broken"] > full[1]["bonds"]["broken"] >= 1
+    assert counters["bond_solver"]["passes"] == E.STEPS
 
 
 def test_the_thin_movers_skip_particles_under_the_plain_pass(oracle, full):
@@ -210,13 +284,18 @@ def test_the_areas_behind_the_bodies_give_other_bits(oracle, full):
 @pytest.mark.parametrize("seed", E.SEEDS)
 def test_the_plans_reach_what_they_are_for(oracle, seed):
     plan = E.plan(seed)
-    assert 60 <= len(plan.ops) == 97 and plan.ops == E.plan(seed).ops
+    assert 60 <= len(plan.ops) == 105 and plan.ops == E.plan(seed).ops
     seq = E.Sequence(plan, oracle)
     try:
         seq.run()
         print("\n".join(seq.log))
         print(dict(seq.cov))
         seq.cov.check()
+        for k in ("op_solver_jacobi", "op_solver_coloured", "op_solver_coloured_again", "op_refuse_65_colours",
+                  "solver_switched_with_a_broken_bond_held", "armed_bond_broke_under_coloured", "armed_coloured_changed",
+                  "save_load_with_the_mode_and_a_broken_bond", "growth_under_coloured", "removal_of_bonded_under_coloured"):
+            assert seq.cov[k] >= 1, k
+        print("fully armed steps: %d of %d" % (seq.cov["armed_steps"], seq.steps))
         assert np.isfinite(seq.tw.arrays()[0]).all()
     finally:
         seq.close()

@@ -1,7 +1,12 @@
-"""GPU (-m gpu): every pass behind a step armed at once -- bends -> areas -> bonds -> bodies -> movers (surfaces,
-swept) -> static colliders (surfaces, swept) -> fields -> observers, the order of gpe_step / gpe_run -- against the one
-composed twin of tests/_everything_model.py, which is made of nothing but the model functions each feature's own tests
-pin against the device (tests/test_everything_cpu.py ties it to the four existing twins).
+"""GPU (-m gpu): every pass behind a step armed at once -- bends -> areas -> bonds (the coloured solver) -> bodies ->
+movers (surfaces, swept) -> static colliders (surfaces, swept) -> fields -> observers, the order of gpe_step / gpe_run
+-- against the one composed twin of tests/_everything_model.py, which is made of nothing but the model functions each
+feature's own tests pin against the device (tests/test_everything_cpu.py ties it to the five existing twins).
+
+The bonds' solver is the twelfth arm: `no_bond_solver` is the eleven arms under Jacobi, `all` runs the coloured pass in
+its one-workgroup form (the scene's bonds name fewer particles than lds_nodes_max), `all_wide` over
+tests/_everything_model.wide_scene in its per-colour form.  The model does not know the form: both must give its bits
+inside a full step.
 
 Every comparison is bit for bit on uint32 views, a NaN for a NaN.  Every context runs under GPE_FLAG_GUARD_ALLOCS and
 ends with no damaged red zone.  A mismatch that goes away when one arm is left out (test_every_step_equals_the_twin's
@@ -12,6 +17,7 @@ import pytest
 
 from tests import _areas_model as AM
 from tests import _bends_model as NM
+from tests import _bond_solver_model as BS
 from tests import _bonds_model as BM
 from tests import _colliders_model as CM
 from tests import _everything_model as E
@@ -22,7 +28,7 @@ F32 = np.float32
 U32 = np.uint32
 DT = E.DT
 STEPS = E.STEPS
-CASES = ["all"] + ["no_" + a for a in E.ARMS] + ["none"]
+CASES = ["all"] + ["no_" + a for a in E.ARMS] + ["none", "all_wide"]
 # pendulum, bricks (the brittle one), the blob's loop, loose, a ring in each sense, shots
 TRACKED = np.array([0, 4, 9, 30, 33, 60, 100, 500, E.RING_FIRST + 3, E.RING_FIRST + E.RING + 5, 1017, 1024], U32)
 
@@ -54,7 +60,17 @@ def _mode(gpe, mode):
 
 
 def _arms(case):
-    return {"all": E.ARMS, "none": ()}.get(case, tuple(a for a in E.ARMS if "no_" + a != case))
+    return {"all": E.ARMS, "all_wide": E.ARMS, "none": ()}.get(case, tuple(a for a in E.ARMS if "no_" + a != case))
+
+
+def _form(st, tw_info, what):
+    """the launch form the last coloured pass took (the device's alone): 0 where none ran since the mode was set, else 2
+    (one workgroup) while the set held names at most lds_nodes_max uids, 1 (a launch per colour) past that"""
+    info = st.bond_solver_info()
+    nodes = st.bonds_info()["nodes"]
+    want = 0 if tw_info["passes"] == 0 else (2 if nodes <= info["lds_nodes_max"] else 1)
+    assert info["form"] == want, (what, info, nodes)
+    return info["form"]
 
 
 def _state(gpe, mode, arms=E.ARMS, sc=None):
@@ -115,21 +131,37 @@ def _same_as_twin(st, tw, what):
     _same_flags_and_poses(st, E.frame(tw), what)
     got, want = E.state_counters(st), tw.counters()
     assert got == want, (what, {k: (got[k], want[k]) for k in got if got[k] != want[k]})
+    assert st.bond_solver() == ("coloured" if tw.bond_solver == BS.COLOURED else "jacobi"), (what, "the bonds' solver")
+    _form(st, want["bond_solver"], what)
 
 
 # ---- the references: the twin alone, once per configuration ---------------------------------------------------------
 @pytest.fixture(scope="module")
-def reference(oracle):
-    """reference(case) -> (frames after each of the 40 steps, counters at the end) of the twin armed as the case says"""
+def lds_nodes_max(gpe):
+    """the most particles a set may name for the coloured pass's one-workgroup form, as the library reports it"""
+    probe = gpe.State(np.full((1, 2), 5.0, F32), np.full(1, 0.5, F32), world=E.WORLD, mode=gpe.MODE_NATIVE,
+                      flags=gpe._lib.FLAG_GUARD_ALLOCS)
+    lds = probe.bond_solver_info()["lds_nodes_max"]
+    _end(probe)
+    return lds
+
+
+@pytest.fixture(scope="module")
+def reference(oracle, lds_nodes_max):
+    """reference(case) -> (the scene, frames after each of the 40 steps, counters at the end) of the twin armed as the
+    case says; `all_wide` over wide_scene(lds_nodes_max), every other case over scene()"""
     done = {}
 
     def get(case):
         if case not in done:
             arms = _arms(case)
-            tw = E.twin(oracle, arms)
-            # (no set, no surfaces; the movers' sweep is the context's mode: on with no movers held, off with thin ones)
-            assert tw.armed() == tuple(a for a in arms if a.split("_")[0] + "s" in arms or "_" not in a or a == "mover_sweep")
-            done[case] = (E.frames(tw), tw.counters())
+            sc = E.wide_scene(lds_nodes_max) if case == "all_wide" else E.scene()
+            tw = E.twin(oracle, arms, sc)
+            # (no set, no surfaces; the movers' sweep and the bonds' solver are the context's modes: on with no movers
+            # and no bonds held, off with thin movers and with bonds)
+            assert tw.armed() == tuple(a for a in arms if a.split("_")[0] + "s" in arms or "_" not in a
+                                       or a in ("mover_sweep", "bond_solver"))
+            done[case] = (sc, E.frames(tw), tw.counters())
             tw.close()
         return done[case]
     return get
@@ -147,28 +179,44 @@ def resorted(oracle):
 # ---- 1, 2. every step equals the twin: all arms, each one left out, none ---------------------------------------------
 @pytest.mark.parametrize("mode", ["native", "compat"])
 @pytest.mark.parametrize("case", CASES)
-def test_every_step_equals_the_twin(gpe, reference, case, mode):
+def test_every_step_equals_the_twin(gpe, reference, lds_nodes_max, case, mode):
     """40 gpe_step calls over scene(): pos and prev after each, the poses, the broken flags and the loops' values after
-    every tenth, every counter at the end.  `all` pins the order of the seven passes in the forms the eleven arms give
-    them (the movers' and the static colliders' with surfaces and swept) and of the observers behind them; the other
-    cases are bit-identical to the twin configured the same way and bisect a failure of `all`.  `no_movers` keeps the
-    movers' sweep on with no movers held; under `no_mover_sweep` the thin movers run the plain pass."""
-    frames, counters = reference(case)
-    if case == "all":
+    every tenth, every counter at the end.  `all` pins the order of the seven passes in the forms the twelve arms give
+    them (the bonds' coloured, the movers' and the static colliders' with surfaces and swept) and of the observers behind
+    them; the other cases are bit-identical to the twin configured the same way and bisect a failure of `all`.
+    `no_movers` keeps the movers' sweep on with no movers held and `no_bonds` the coloured solver with no bonds held;
+    under `no_mover_sweep` the thin movers run the plain pass, and `no_bond_solver` is the eleven arms under Jacobi.
+    The coloured pass of `all` takes the one-workgroup form; `all_wide`, whose bonds name more than lds_nodes_max
+    particles, the per-colour one from its first step on."""
+    sc, frames, counters = reference(case)
+    solver = counters["bond_solver"]
+    if case in ("all", "all_wide"):
         assert counters["sweep"]["stopped"] > 0 and counters["bodies"]["broken"] > 0 and counters["movers"]["pushed"] > 0
         assert counters["mover_sweep"]["stopped"] > 0
         assert counters["bends"]["passes"] == counters["areas"]["passes"] == STEPS
-    st = _state(gpe, mode, _arms(case))
+        assert solver["mode"] == BS.COLOURED and solver["passes"] == STEPS and counters["bonds"]["broken"] > 0
+    if case == "all_wide":
+        assert counters["bonds"]["nodes"] > lds_nodes_max and solver["colours"] <= BS.COLOURS_MAX
+        assert counters["bonds"]["broken"] > 1                         # (the tie, and ties along the fill)
+    if case in ("no_bonds", "no_bond_solver", "none"):
+        assert solver["passes"] == 0 and solver["mode"] == (BS.JACOBI if case != "no_bonds" else BS.COLOURED)
+    st = _state(gpe, mode, _arms(case), sc)
+    assert _form(st, dict(passes=0), (case, "before the first step")) == 0
     for s in range(STEPS):
         st.update(DT)
         f = frames[s]
         pos, prev = st.positions(), st.previous_positions()
         assert same_bits(pos, f.pos), (case, s, "pos", _differ(pos, f.pos))
         assert same_bits(prev, f.prev), (case, s, "prev", _differ(prev, f.prev))
+        if s == 0 and case == "all_wide":
+            assert st.bond_solver_info()["form"] == 1
         if s % 10 == 9:
             _same_flags_and_poses(st, f, (case, s))
     got = E.state_counters(st)
     assert got == counters, {k: (got[k], counters[k]) for k in got if got[k] != counters[k]}
+    form = _form(st, solver, (case, "at the end"))
+    assert form == {"all": 2, "all_wide": 1}.get(case, form) and (form == 0) == (solver["passes"] == 0)
+    print("case %s (%s): form %d, %d colours, %d nodes" % (case, mode, form, solver["colours"], counters["bonds"]["nodes"]))
     _ran_native(gpe, st, mode, STEPS)
     _end(st)
 
@@ -210,15 +258,18 @@ def test_one_event_invalidates_every_structure(gpe, oracle, mode):
     """Fully armed and stepping: a radius edit to three times the largest and back, gpe_set_world to twice the size and
     back, an add past the capacity, the removal of a body member, of a bonded uid, of a loop's member and of a bend's
     hinge, a re-sort (all four uid-named sets look their slots up again), a spell in the other mode; three steps and a
-    full comparison (the movers' sweep and its counters in it) behind each.  A grid of the
+    full comparison (the movers' sweep and the bonds' solver with their counters in it) behind each.  A grid of the
     movers that is cut anew must not drop the swept form: its pass counter goes on behind the radius edit and the new
-    world."""
+    world.  The bonds' coloured pass, in its one-workgroup form, reads node_slot again and writes every present node
+    back behind each event: its pass counter goes on as well, and the colours stay the set's."""
     from tests.test_gpu_fields import grid_dims
     L = gpe._lib
     st = _state(gpe, mode)
     tw = E.twin(oracle)
     rng = np.random.default_rng(5)
     total = [0]
+    colours = BS.colour_info(tw.bonds)
+    assert colours[0] >= 3
 
     def steps(what, k=3):
         for _ in range(k):
@@ -235,6 +286,9 @@ def test_one_event_invalidates_every_structure(gpe, oracle, mode):
         """the mode is on and every step so far ran the movers' pass in its swept form"""
         info = st.mover_sweep_info()
         assert st.mover_sweep() is True and info["mode"] == L.SWEEP_ON and info["passes"] == total[0], (what, info, total[0])
+        info = st.bond_solver_info()
+        assert st.bond_solver() == "coloured" and (info["passes"], info["form"]) == (total[0], 2), (what, info, total[0])
+        assert (info["colours"], info["largest_colour"]) == colours, (what, info, colours)
 
     start = steps("start", 6)
     assert grids(start)[2] == grid_dims(E.WORLD)[1:]
@@ -271,11 +325,13 @@ def test_one_event_invalidates_every_structure(gpe, oracle, mode):
     st.add_particles(grow, np.full(k, 0.25, F32)); tw.add(grow, np.full(k, 0.25, F32))
     steps("growth")
     # a member of a live body, a bonded particle, a member of a ring's loop and the middle node of a bend leave
-    assert not tw.bodies_broken[1] and not tw.broken.any() and not np.isnan(tw.area_value).any()
     ring = E.RING_FIRST                                                # (the first ring: loop 0, bends 0 .. 15)
-    assert tw.area_member_uid[3] == ring + 3 and tw.bends["uid_b"][4] == ring + 4
     # of the first brick; the pair bond's end; the anchored one; the loop's member; the bend's hinge
     gone = np.array([10, 17, 1, ring + 3, ring + 4], U32)
+    # (no bond is broken but the tie of the ring over the paddle, which names none of them)
+    assert tw.broken.tolist() == [False] * (len(tw.bonds) - 1) + [True] and tw.bonds["uid_a"][-1] == E.FALLER not in gone
+    assert not tw.bodies_broken[1] and not np.isnan(tw.area_value).any()
+    assert tw.area_member_uid[3] == ring + 3 and tw.bends["uid_b"][4] == ring + 4
     assert st.remove_particles_by_uid(gone) == tw.remove_uids(gone) == 5
     steps("removal")
     assert not np.isnan(tw.poses[1]).any()                             # the brick goes on with seven members
@@ -320,16 +376,19 @@ def pumped(oracle):
 
 
 @pytest.mark.parametrize("mode", ["native", "compat"])
-def test_save_and_load_with_all_twelve_groups(gpe, pumped, tmp_path, mode):
-    """one loop pumped and the context saved after 15 steps, loaded into a fresh context of each mode, 15 more steps:
-    the bits of the uninterrupted twin"""
+def test_save_and_load_with_all_thirteen_groups(gpe, pumped, tmp_path, mode):
+    """one loop pumped and the context saved after 15 steps, with the coloured solver on and the tie broken, loaded
+    into a fresh context of each mode, 15 more steps: the bits of the uninterrupted twin.  The loaded contexts hold the
+    mode, the colours of the loaded set and its broken flags whichever of the two was restored first."""
     L = gpe._lib
     frames, rows = pumped
     sc = E.scene()
+    colours = BS.colour_info(sc.bonds)
     st = _state(gpe, mode, sc=sc)
     for s in range(15):
         st.update(DT)
     assert frames[14].bodies_broken.any() and not frames[14].bodies_broken.all()
+    assert frames[14].bonds_broken.any() and not frames[14].bonds_broken.all() and colours[0] >= 3
     st.set_area_targets(PUMPED, F32(1.25) * sc.areas["rest_area"][PUMPED:PUMPED + 1])
     assert same_rows(st.areas()[0], rows) and not same_rows(rows, AM.stored(sc.areas))
     path = str(tmp_path / "snap.npz")
@@ -338,6 +397,8 @@ def test_save_and_load_with_all_twelve_groups(gpe, pumped, tmp_path, mode):
         assert set(E.GROUPS) <= set(d.files), sorted(d.files)
         assert np.array_equal(d["bodies_broken"], frames[14].bodies_broken) and d["collider_sweep"].tolist() == [1]
         assert same_rows(d["mover_poses"], frames[14].mover_poses) and d["mover_sweep"].tolist() == [1]
+        assert d["bond_solver"].tolist() == [L.BOND_SOLVER_COLOURED]
+        assert np.array_equal(d["bonds_broken"], frames[14].bonds_broken)
         assert same_rows(d["areas"], rows) and np.array_equal(d["area_member_uid"], sc.area_member_uid)
         assert same_rows(d["bends"], NM.stored(sc.bends))
         assert (d["bend_iterations"].tolist(), d["area_iterations"].tolist()) == ([sc.bend_iterations], [sc.area_iterations])
@@ -346,6 +407,10 @@ def test_save_and_load_with_all_twelve_groups(gpe, pumped, tmp_path, mode):
     for h in backs:
         assert h.collider_sweep() is True and np.array_equal(h.bodies()[1], frames[14].bodies_broken)
         assert h.mover_sweep() is True and h.mover_sweep_info()["passes"] == 0     # (its counters start anew)
+        info = h.bond_solver_info()
+        assert h.bond_solver() == "coloured" and (info["colours"], info["largest_colour"]) == colours, info
+        assert (info["mode"], info["passes"], info["form"]) == (L.BOND_SOLVER_COLOURED, 0, 0), info
+        assert np.array_equal(h.bonds()[1], frames[14].bonds_broken)
         assert same_rows(h.mover_poses(), frames[14].mover_poses)
         for target in ("colliders", "movers"):
             assert same_rows(h.surfaces(target), st.surfaces(target)) and len(h.surfaces(target)) > 0
@@ -364,6 +429,9 @@ def test_save_and_load_with_all_twelve_groups(gpe, pumped, tmp_path, mode):
         _same_flags_and_poses(h, f, "after load")
         assert h.mover_sweep_info()["passes"] == (30 if h is st else 15)
         assert h.bends_info()["passes"] == h.areas_info()["passes"] == (30 if h is st else 15)
+        info = h.bond_solver_info()
+        assert (info["passes"], info["form"]) == (30 if h is st else 15, 2), info
+        assert (info["colours"], info["largest_colour"]) == colours, info
         assert same_rows(h.areas()[0], rows)
     _ran_native(gpe, st, mode, 30)
     _ran_native(gpe, backs[0], mode, 15)
@@ -377,7 +445,9 @@ def test_save_and_load_with_all_twelve_groups(gpe, pumped, tmp_path, mode):
 @pytest.mark.parametrize("seed", E.SEEDS)
 def test_a_random_interleaving_against_the_twin(gpe, oracle, seed, mode):
     """plan(seed) against a State and the twin: after every operation the particles, every stored set read back, the
-    two sweeps' modes, the poses, the broken flags and the counters"""
+    two sweeps' modes, the bonds' solver with its colours and launch form, the poses, the broken flags and the
+    counters.  The solver is switched with a set and a broken bond held, set again while on, and offered a set of 65
+    colours; every other block runs under the coloured mode."""
     seq = E.Sequence(E.plan(seed), oracle, gpe=gpe, mode_name=mode, compare=_same_as_twin, end=_end)
     try:
         seq.run()
