@@ -67,6 +67,8 @@ SURFACE_PLAIN = 1
 SWEEP_OFF, SWEEP_ON = 0, 1
 BOND_SOLVER_JACOBI, BOND_SOLVER_COLOURED = 0, 1
 BOND_COLOURS_MAX = 64
+BEND_SOLVER_JACOBI, BEND_SOLVER_COLOURED = 0, 1
+BEND_COLOURS_MAX = 64
 EDIT_BY_INDEX, EDIT_BY_UID = 0, 1
 CLUSTER_BY_INDEX, CLUSTER_BY_UID = 0, 1
 VEL_ADD, VEL_SET, VEL_SCALE = 0, 1, 2
@@ -275,6 +277,15 @@ class GpeBondSolverInfo(C.Structure):
                 ("passes", C.c_uint64)]
 
 
+class GpeBendSolverInfo(C.Structure):
+    """gpe_bend_solver_info: in struct_size; out the bends' solver mode, the colours of the set held and the bends of the
+    fullest one, the launch form of the last coloured pass (0 none yet, 1 per colour, 2 one workgroup), the node count
+    up to which form 2 is taken, the coloured passes run since the last gpe_set_bend_solver.  32 bytes."""
+    _fields_ = [("struct_size", C.c_uint32), ("mode", C.c_uint32), ("colours", C.c_uint32),
+                ("largest_colour", C.c_uint32), ("form", C.c_uint32), ("lds_nodes_max", C.c_uint32),
+                ("passes", C.c_uint64)]
+
+
 class GpeBend(C.Structure):
     """gpe_bend: the angle at the hinge uid_b from (uid_a - uid_b) to (uid_c - uid_b) held at the rest angle
     (rest_cos, rest_sin).  32 bytes."""
@@ -442,6 +453,9 @@ SYMBOLS = [
     ("gpe_get_bends", _I32, [_VP, C.POINTER(GpeBend), _U64, C.POINTER(_U64)]),
     ("gpe_apply_bends", _I32, [_VP]),
     ("gpe_get_bends_info", _I32, [_VP, C.POINTER(GpeBendsInfo)]),
+    ("gpe_set_bend_solver", _I32, [_VP, _U32]),
+    ("gpe_get_bend_solver", _I32, [_VP, C.POINTER(_U32)]),
+    ("gpe_get_bend_solver_info", _I32, [_VP, C.POINTER(GpeBendSolverInfo)]),
     ("gpe_set_areas", _I32, [_VP, C.POINTER(GpeArea), _U64, C.POINTER(C.c_uint32), _U64, C.c_uint32]),
     ("gpe_get_areas", _I32, [_VP, C.POINTER(GpeArea), _U64, C.POINTER(_U64), C.POINTER(C.c_uint32), _U64, C.POINTER(_U64)]),
     ("gpe_apply_areas", _I32, [_VP]),

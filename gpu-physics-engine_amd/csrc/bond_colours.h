@@ -14,69 +14,25 @@
 
 #include <stdint.h>
 
-#include <unordered_map>
-#include <vector>
-
 #include "bond_graph.h"
+#include "colour_tables.h"
 
 namespace gpe {
 
-struct BondColours {
-    std::vector<uint32_t> colour;        // k
-    std::vector<uint32_t> order;         // k: the bond indices sorted by (colour, index)
-    std::vector<uint32_t> colour_start;  // colours + 1
-    uint32_t colours = 0;                // C: 1 + the largest colour given (0 for no bonds)
-    uint32_t largest = 0;                // the bonds of the fullest colour
-};
+using BondColours = ColourTables;        // colour, order, colour_start, colours, largest: of the bonds
 
 // The colours of k records over m nodes (bond_graph_build's: every node index < m; a record whose index is not is
 // coloured as if it had no such end).  false: the set needs more than GPE_BOND_COLOURS_MAX colours -- out->colours says
-// how many, the tables are complete all the same.
+// how many, the tables are complete all the same.  The greedy core is colour_tables.h's, shared with the bends.
 inline bool bond_colours_build(const BondRecord *rec, uint64_t k, uint64_t m, BondColours *out)
 {
     *out = BondColours();
-    // the colours taken at a node: colours 0 .. 63 in one word per node, the rest (a set that will be refused, but whose
-    // count the refusal names) in words only the crowded nodes have
-    std::vector<uint64_t> low(m, 0);
-    std::unordered_map<uint64_t, std::vector<uint64_t>> high;          // node -> words 1, 2, ...
-    const auto word = [&](uint64_t node, size_t w) -> uint64_t {
-        if (node >= m) return 0;
-        if (w == 0) return low[node];
-        const auto it = high.find(node);
-        return (it == high.end() || it->second.size() < w) ? 0 : it->second[w - 1];
-    };
-    const auto take = [&](uint64_t node, uint32_t c) {
-        if (node >= m) return;
-        if (c < 64) { low[node] |= 1ull << c; return; }
-        std::vector<uint64_t> &v = high[node];
-        if (v.size() < c / 64) v.resize(c / 64, 0);
-        v[c / 64 - 1] |= 1ull << (c % 64);
-    };
-    out->colour.resize(k);
-    std::vector<uint32_t> size;
-    for (uint64_t j = 0; j < k; ++j) {
-        const uint64_t a = rec[j].a;
-        const uint64_t b = (rec[j].b & kBondAnchorBit) ? m : rec[j].b;  // (m: no node)
-        uint32_t c = 0;
-        for (size_t w = 0;; ++w) {
-            const uint64_t taken = word(a, w) | word(b, w);
-            if (taken != ~0ull) { c = (uint32_t)(64 * w) + (uint32_t)__builtin_ctzll(~taken); break; }
-        }
-        take(a, c);
-        take(b, c);
-        out->colour[j] = c;
-        if (c >= size.size()) size.resize(c + 1, 0);
-        size[c] += 1;
-    }
-    out->colours = (uint32_t)size.size();
-    out->colour_start.assign(out->colours + 1, 0);
-    for (uint32_t c = 0; c < out->colours; ++c) {
-        out->colour_start[c + 1] = out->colour_start[c] + size[c];
-        if (size[c] > out->largest) out->largest = size[c];
-    }
-    std::vector<uint32_t> at(out->colour_start.begin(), out->colour_start.end() - 1);
-    out->order.resize(k);
-    for (uint64_t j = 0; j < k; ++j) out->order[at[out->colour[j]]++] = (uint32_t)j;   // ascending j within a colour
+    colour_tables_build(k, m, [&](uint64_t j, uint64_t *v) -> size_t {
+        v[0] = rec[j].a;
+        if (rec[j].b & kBondAnchorBit) return 1;                       // (its point is no node)
+        v[1] = rec[j].b;
+        return 2;
+    }, out);
     return out->colours <= GPE_BOND_COLOURS_MAX;
 }
 

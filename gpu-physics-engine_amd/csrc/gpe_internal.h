@@ -505,6 +505,19 @@ struct BendState {
     uint32_t *inc = nullptr;                     // row_start[m] = 3 k: a node's bends, bend << 2 | role
     float4 *corr = nullptr;                      // k: this relaxation's corrections (da.x, da.y, dc.x, dc.y)
     uint8_t *state = nullptr;                    // k: 0 acted, 2 inert in this relaxation
+    // the colour tables (bend_colours.h): held only while the solver is coloured (BendSolverState), null otherwise
+    uint32_t *order = nullptr;                   // k: the bend indices by (colour, index)
+    uint32_t *colour_start = nullptr;            // colours + 1, the device's copy (the one-workgroup form reads it)
+    std::vector<uint32_t> colour_begin;          // colours + 1, the host's copy (the per-colour launches' ranges)
+    uint32_t colours = 0, largest_colour = 0;
+};
+
+// the bends' solver (gpe_set_bend_solver; gpe_bends.hip, k_bends.hip, bend_colours.h).  A mode of their pass, like the
+// bonds' solver: it outlives gpe_set_bends
+struct BendSolverState {
+    uint32_t mode = 0;                           // GPE_BEND_SOLVER_JACOBI / GPE_BEND_SOLVER_COLOURED
+    uint32_t form = 0;                           // the last coloured pass's: 0 none yet, 1 per colour, 2 one workgroup
+    uint64_t passes = 0;                         // coloured passes enqueued since the mode was last set
 };
 
 // the area constraints (gpe_set_areas; gpe_areas.hip, k_areas.hip, area_table.h).  Step state: gpe_step / gpe_run relax
@@ -972,6 +985,7 @@ struct gpe_ctx {
     gpe::BondState bonds;
     gpe::BondSolverState bond_solver;
     gpe::BendState bends;
+    gpe::BendSolverState bend_solver;
     gpe::AreaState areas;
     gpe::BodyState bodies;
     gpe::FieldState fields;
@@ -1485,6 +1499,18 @@ gpe_status launch_bonds_coloured(gpe_ctx *c, float2 *pos, const float *radius, u
 // bend constraints (k_bends.hip): `iterations` relaxations of the k bends of B over pos[0, n) in place, two launches each
 gpe_status launch_bends_pass(gpe_ctx *c, float2 *pos, const float *radius, uint64_t n, const BendState &B, uint32_t k,
                              uint32_t m, uint32_t iterations);
+// ... under the coloured solver: `iterations` coloured relaxations, B.order and B.colour_start as bend_colours.h built
+// them for B.colours colours.  *form: 2 when the pass was one launch of one workgroup (m <= kBendLdsNodesMax), 1 when
+// it was one launch per colour and relaxation
+#ifndef GPE_BEND_LDS_NODES_MAX
+#define GPE_BEND_LDS_NODES_MAX 1024              // (timing builds set 0 and 8192: every pass in one form, profiles/bend_solver/)
+#endif
+constexpr uint32_t kBendLdsNodesMax = GPE_BEND_LDS_NODES_MAX;       // policy: profiles/bend_solver/README.md
+// the nodes the one-workgroup form declares LDS for, 12 B each: the policy's (12 KiB; a timing build of 8192: 96 KiB)
+constexpr uint32_t kBendLdsNodesCap = kBendLdsNodesMax > 0 ? kBendLdsNodesMax : 1;
+static_assert(kBendLdsNodesCap <= 8192, "12 B a node: 8192 nodes are 96 KiB of the 160 KiB a gfx950 workgroup may declare");
+gpe_status launch_bends_coloured(gpe_ctx *c, float2 *pos, const float *radius, uint64_t n, const BendState &B, uint32_t k,
+                                 uint32_t m, uint32_t iterations, uint32_t *form);
 // area constraints (k_areas.hip): `iterations` relaxations of the k loops of A over pos[0, n) in place: one launch per
 // non-empty width class, then one over the m nodes; launch_areas_expand: member_slot[i] = node_slot[member_node[i]]
 gpe_status launch_areas_pass(gpe_ctx *c, float2 *pos, const float *radius, uint64_t n, const AreaState &A, uint32_t k,

@@ -7,7 +7,9 @@
 // deviation from the rest angle) with equal masses: the three corrections sum to zero.  One relaxation judges every bend
 // from the positions the relaxation starts with (Jacobi): the bend's corrections are a function of those three
 // positions and the bend alone, a particle's new position the sum of its bends' shares in ascending bend index.  No
-// order of addition depends on the launch, on where the particles are stored or on the pipeline.
+// order of addition depends on the launch, on where the particles are stored or on the pipeline.  Under the coloured
+// solver (gpe_set_bend_solver, bend_colours.h) the same bend_correction is judged from the positions as they are, colour
+// after colour, and a bend moves its three particles itself (tests/cpp/bend_colours_tests.cpp replays that).
 #pragma once
 
 #include <math.h>

@@ -15,6 +15,21 @@
 // zero still counts: its particle is clamped), so the mark is the state byte.
 // No LDS, no float atomics.  Slots are checked against n, indices against the count of their array, before they index
 // anything.
+//
+// Under the coloured solver (gpe_set_bend_solver; bend_colours.h colours the set on the host) a relaxation is a sweep of
+// the colours in order, every bend judged from the positions as they are and moving its three particles itself: no
+// corr, no node phase.  No two bends of one colour share a node, so within a colour no position has two writers, and
+// the bits are those of a sequential sweep in (colour, index) order whatever the launch.  Two launch forms, one
+// bend_in_place:
+//   - k_bends_colour, one launch per colour and relaxation on the in-order stream, one lane per entry of
+//     order[colour_start[c] .. colour_start[c + 1]).  Reads order (4 B), state (1 B), the record (32 B), three
+//     node_slot, three positions and three radii; writes three positions, and state when it changes.  No LDS.
+//   - k_bends_coloured, one launch of one 1024-lane workgroup for a set of at most kBendLdsNodesMax nodes (a blade of
+//     grass, a hinge, one fold: launches would cost more than the work).  Stages position and radius of the set's m
+//     nodes in LDS (12 B a node, static, for kBendLdsNodesMax nodes: 12 KiB), runs all iterations * colours sweeps
+//     there with the bends of a colour strided over the lanes and a barrier between colours, writes the present nodes
+//     back once.
+// Neither uses float atomics.
 #include "gpe_internal.h"
 #include "bend_graph.h"
 #include "k_bend.h"
@@ -73,6 +88,123 @@ __global__ __launch_bounds__(kStreamBlock) void k_bends_bend(const float2 *__res
     }
 }
 
+// One bend of a coloured sweep, in place.  Nodes: where the particles of the set's nodes are read and written --
+//   at(node) -> a handle; present(handle); get(handle) -> float2; rad(handle) -> float; put(handle, float2).
+// Every index is checked against the count of its array before it indexes anything.
+template <class Nodes>
+__device__ __forceinline__ void bend_in_place(const BendPassArgs &P, uint32_t j, Nodes &N)
+{
+#pragma clang fp contract(off)
+    if (j >= P.k) return;
+    const uint32_t was = P.state[j];
+    const uint4 r0 = P.rec[2 * (size_t)j];                             // (a, b, c, rc)
+    const uint4 r1 = P.rec[2 * (size_t)j + 1];                         // (rs, stiffness, 0, 0)
+    uint32_t now = kBendInert;
+    if (r0.x < P.m && r0.y < P.m && r0.z < P.m) {
+        const uint32_t ha = N.at(r0.x);
+        const uint32_t hb = N.at(r0.y);
+        const uint32_t hc = N.at(r0.z);
+        if (N.present(ha) && N.present(hb) && N.present(hc)) {
+            const float2 a = N.get(ha);
+            const float2 b = N.get(hb);
+            const float2 c = N.get(hc);
+            float dax = 0.f, day = 0.f, dcx = 0.f, dcy = 0.f;
+            now = bend_correction(a.x, a.y, b.x, b.y, c.x, c.y, __uint_as_float(r0.w), __uint_as_float(r1.x),
+                                  __uint_as_float(r1.y), &dax, &day, &dcx, &dcy);
+            if (now == kBendActs) {
+                float2 o;
+                bond_move(a.x, a.y, N.rad(ha), dax, day, P.world_w, P.world_h, &o.x, &o.y);
+                N.put(ha, o);
+                bond_move(c.x, c.y, N.rad(hc), dcx, dcy, P.world_w, P.world_h, &o.x, &o.y);
+                N.put(hc, o);
+                bond_move(b.x, b.y, N.rad(hb), bend_hinge_share(dax, dcx), bend_hinge_share(day, dcy), P.world_w,
+                          P.world_h, &o.x, &o.y);
+                N.put(hb, o);
+            }
+        }
+    }
+    if (now != was) P.state[j] = (uint8_t)now;
+}
+
+struct BendNodesGlobal {                         // the particles where they are stored: a handle is a storage slot
+    float2 *pos;
+    const float *radius;
+    const uint32_t *node_slot;
+    uint32_t n;
+    __device__ __forceinline__ uint32_t at(uint32_t node) const { return node_slot[node]; }   // (an absent uid: 0xffffffff >= n)
+    __device__ __forceinline__ bool present(uint32_t h) const { return h < n; }
+    __device__ __forceinline__ float2 get(uint32_t h) const { return pos[h]; }
+    __device__ __forceinline__ float rad(uint32_t h) const { return radius[h]; }
+    __device__ __forceinline__ void put(uint32_t h, float2 v) const { pos[h] = v; }
+};
+
+// the bends order[lo .. hi) -- one colour -- over the particles in place.  lo <= hi <= k
+__global__ __launch_bounds__(kStreamBlock) void k_bends_colour(float2 *pos, const float *__restrict__ radius,
+                                                               BendPassArgs P, const uint32_t *__restrict__ order,
+                                                               uint32_t lo, uint32_t hi)
+{
+    BendNodesGlobal N{pos, radius, P.node_slot, P.n};
+    const uint32_t stride = gridDim.x * blockDim.x;
+    for (uint32_t e = lo + blockIdx.x * blockDim.x + threadIdx.x; e < hi && e < P.k; e += stride)
+        bend_in_place(P, order[e], N);
+}
+
+constexpr int kBendLdsBlock = 1024;
+
+struct BendNodesLds {                            // the particles staged by node index: a handle is a node, < m <= the cap
+    float2 *lpos;
+    float *lrad;
+    __device__ __forceinline__ uint32_t at(uint32_t node) const { return node; }
+    __device__ __forceinline__ bool present(uint32_t) const { return true; }     // (an absent node's position is NaN)
+    __device__ __forceinline__ float2 get(uint32_t h) const { return lpos[h]; }
+    __device__ __forceinline__ float rad(uint32_t h) const { return lrad[h]; }
+    __device__ __forceinline__ void put(uint32_t h, float2 v) const { lpos[h] = v; }
+};
+
+// a whole pass of a set of P.m <= kBendLdsNodesCap nodes: one workgroup.  colour_start: colours + 1 words, ascending,
+// the last one <= k.  An absent node's staged position is NaN: bend_correction calls its bends inert, which is what an
+// absent uid means
+__global__ __launch_bounds__(kBendLdsBlock) void k_bends_coloured(float2 *pos, const float *__restrict__ radius,
+                                                                  BendPassArgs P, const uint32_t *__restrict__ order,
+                                                                  const uint32_t *__restrict__ colour_start,
+                                                                  uint32_t colours, uint32_t iterations)
+{
+    __shared__ float2 lpos[kBendLdsNodesCap];
+    __shared__ float lrad[kBendLdsNodesCap];
+    if (P.m > kBendLdsNodesCap) return;          // (uniform; the host never launches it so)
+    for (uint32_t v = threadIdx.x; v < P.m; v += kBendLdsBlock) {
+        const uint32_t slot = P.node_slot[v];
+        const bool present = slot < P.n;
+        lpos[v] = present ? pos[slot] : make_float2(__uint_as_float(0x7fc00000u), __uint_as_float(0x7fc00000u));
+        lrad[v] = present ? radius[slot] : 0.0f;
+    }
+    __syncthreads();
+    BendNodesLds N{lpos, lrad};
+    for (uint32_t it = 0; it < iterations; ++it) {
+        for (uint32_t c = 0; c < colours; ++c) {
+            const uint32_t lo = colour_start[c], hi = colour_start[c + 1];
+            // (at the shipped limit a colour holds at most a third as many bends as there are nodes: one trip)
+            for (uint32_t e = lo + threadIdx.x; e < hi && e < P.k; e += kBendLdsBlock) bend_in_place(P, order[e], N);
+            __syncthreads();                     // (lo, hi, colours, iterations are uniform: every lane arrives)
+        }
+    }
+    for (uint32_t v = threadIdx.x; v < P.m; v += kBendLdsBlock) {
+        const uint32_t slot = P.node_slot[v];
+        if (slot < P.n) pos[slot] = lpos[v];     // (a node no bend moved gets its own bits back)
+    }
+}
+
+static BendPassArgs bend_pass_args(const gpe_ctx *c, uint64_t n, const BendState &B, uint32_t k, uint32_t m)
+{
+    BendPassArgs P;
+    P.rec = B.rec;
+    P.node_slot = B.nt.node_slot; P.row_start = B.nt.row_start; P.inc = B.inc;
+    P.corr = B.corr; P.state = B.state;
+    P.k = k; P.m = m; P.n = (uint32_t)n;
+    P.world_w = c->cfg.world_width; P.world_h = c->cfg.world_height;
+    return P;
+}
+
 // B's tables as gpe_set_bends uploaded them for k bends and m nodes (every node index < m, every inc entry >> 2 < k),
 // node_slot resolved for the particles as they are.
 gpe_status launch_bends_pass(gpe_ctx *c, float2 *pos, const float *radius, uint64_t n, const BendState &B, uint32_t k,
@@ -80,12 +212,7 @@ gpe_status launch_bends_pass(gpe_ctx *c, float2 *pos, const float *radius, uint6
 {
     if (n == 0 || k == 0 || m == 0) return GPE_OK;
     if (n > 0xFFFFFFFFull) return refuse_too_many(c, "bends");
-    BendPassArgs P;
-    P.rec = B.rec;
-    P.node_slot = B.nt.node_slot; P.row_start = B.nt.row_start; P.inc = B.inc;
-    P.corr = B.corr; P.state = B.state;
-    P.k = k; P.m = m; P.n = (uint32_t)n;
-    P.world_w = c->cfg.world_width; P.world_h = c->cfg.world_height;
+    const BendPassArgs P = bend_pass_args(c, n, B, k, m);
     for (uint32_t it = 0; it < iterations; ++it) {
         {
             Scope s(c, "bends/bend");
@@ -94,6 +221,37 @@ gpe_status launch_bends_pass(gpe_ctx *c, float2 *pos, const float *radius, uint6
         }
         GPE_TRY(launch_uid_nodes(c, "bends/node", pos, radius, P));
     }
+    return GPE_OK;
+}
+
+// ... and B.order (k entries, each < k), B.colour_start on the device and B.colour_begin on the host (B.colours + 1
+// words, ascending from 0 to k) as the coloured solver built them
+gpe_status launch_bends_coloured(gpe_ctx *c, float2 *pos, const float *radius, uint64_t n, const BendState &B, uint32_t k,
+                                 uint32_t m, uint32_t iterations, uint32_t *form)
+{
+    if (n == 0 || k == 0 || m == 0) return GPE_OK;
+    if (n > 0xFFFFFFFFull) return refuse_too_many(c, "bends");
+    if (!B.order || !B.colour_start || B.colour_begin.size() != (size_t)B.colours + 1 || B.colour_begin.back() != k)
+        return fail(c, GPE_ERR_STATE, "the coloured bends' pass: no colour tables for this set");
+    const BendPassArgs P = bend_pass_args(c, n, B, k, m);
+    if (m <= kBendLdsNodesMax) {
+        Scope s(c, "bends/coloured");
+        hipLaunchKernelGGL(k_bends_coloured, dim3(1), dim3(kBendLdsBlock), 0, c->stream, pos, radius, P, B.order,
+                           B.colour_start, B.colours, iterations);
+        GPE_HIP(c, hipGetLastError());
+        *form = 2;
+        return GPE_OK;
+    }
+    for (uint32_t it = 0; it < iterations; ++it) {
+        for (uint32_t col = 0; col < B.colours; ++col) {
+            const uint32_t lo = B.colour_begin[col], hi = B.colour_begin[col + 1];
+            Scope s(c, "bends/colour");
+            hipLaunchKernelGGL(k_bends_colour, dim3(stream_grid(hi - lo)), dim3(kStreamBlock), 0, c->stream, pos, radius,
+                               P, B.order, lo, hi);
+            GPE_HIP(c, hipGetLastError());
+        }
+    }
+    *form = 1;
     return GPE_OK;
 }
 

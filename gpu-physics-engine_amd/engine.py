@@ -847,6 +847,29 @@ class ParticleSystem:
         self.ctx.call("gpe_get_bends_info", C.byref(info))
         return {name: getattr(info, name) for name, _ in L.GpeBendsInfo._fields_ if name != "struct_size"}
 
+    def set_bend_solver(self, solver):
+        """gpe_set_bend_solver: "jacobi" (the default: every bend judged from the positions a relaxation starts with) or
+        "coloured" (graph-coloured Gauss-Seidel: the bends relaxed colour after colour, every bend seeing the corrections
+        of the colours before it -- stiffness 1 is stable, a short cantilever droops less than half as far; no gain on
+        long chains).  Step state: it outlives set_bends; save() keeps it with the bends it belongs to (not for a
+        context without bends).  Synchronises."""
+        modes = {"jacobi": L.BEND_SOLVER_JACOBI, "coloured": L.BEND_SOLVER_COLOURED}
+        if solver not in modes:
+            raise ValueError('the bend solver is "jacobi" or "coloured"')
+        self.ctx.call("gpe_set_bend_solver", modes[solver])
+
+    def bend_solver(self):
+        """gpe_get_bend_solver -> "jacobi" | "coloured"."""
+        mode = C.c_uint32(0)
+        self.ctx.call("gpe_get_bend_solver", C.byref(mode))
+        return "coloured" if mode.value == L.BEND_SOLVER_COLOURED else "jacobi"
+
+    def bend_solver_info(self):
+        """gpe_get_bend_solver_info -> dict(mode, colours, largest_colour, form, lds_nodes_max, passes)."""
+        info = L.GpeBendSolverInfo(struct_size=C.sizeof(L.GpeBendSolverInfo))
+        self.ctx.call("gpe_get_bend_solver_info", C.byref(info))
+        return {name: getattr(info, name) for name, _ in L.GpeBendSolverInfo._fields_ if name != "struct_size"}
+
     # Area constraints (not in the reference; include/gpe.h): closed loops of particles, named by uid in order around a
     # polygon, that keep a signed rest area; relaxed on the device after every update() / step of run(), behind the bends
     # and in front of the bonds.  Step state: save() keeps them.
@@ -1656,6 +1679,18 @@ class State:
         """ParticleSystem.bends_info -> dict(iterations, k, nodes, passes, resolves)."""
         return self.particles.bends_info()
 
+    def set_bend_solver(self, solver):
+        """ParticleSystem.set_bend_solver: "jacobi" | "coloured"."""
+        self.particles.set_bend_solver(solver)
+
+    def bend_solver(self):
+        """ParticleSystem.bend_solver -> "jacobi" | "coloured"."""
+        return self.particles.bend_solver()
+
+    def bend_solver_info(self):
+        """ParticleSystem.bend_solver_info -> dict(mode, colours, largest_colour, form, lds_nodes_max, passes)."""
+        return self.particles.bend_solver_info()
+
     def bends_from_positions(self, triples, stiffness=1.0):
         """Rows of BEND_DTYPE for the uid triples (a, hinge b, c) whose rest angles are the angles the particles hold
         now: the cosine and sine of the angle from a - b to c - b in float64 from the downloaded positions, rounded once
@@ -1891,7 +1926,8 @@ class State:
         on (`collider_sweep`), and the movers' sweep where it is on (`mover_sweep`), and the bonds' solver where bonds are held
         and it is the coloured one (`bond_solver`).  A coloured mode set on a context that holds no bonds is NOT
         written -- it has moved nothing -- and such a snapshot loads as Jacobi: a host that sets its bonds after load()
-        sets the solver again with them."""
+        sets the solver again with them.  The bends' solver is kept the same way (`bend_solver`: only where bends are
+        held and it is the coloured one)."""
         extra = {}
         if self.mover_sweep():
             extra.update(mover_sweep=np.array([L.SWEEP_ON], np.uint32))
@@ -1925,6 +1961,8 @@ class State:
             bends = self.bends()                                       # (they name particles by uid: none without uids)
             if len(bends):
                 extra.update(bends=bends, bend_iterations=np.array([self.bends_info()["iterations"]], np.uint32))
+                if self.bend_solver() == "coloured":                   # (asked where bends are held: the mode alone moves nothing)
+                    extra.update(bend_solver=np.array([L.BEND_SOLVER_COLOURED], np.uint32))
             areas, area_member_uid = self.areas()
             if len(areas):
                 extra.update(areas=areas, area_member_uid=area_member_uid,
@@ -1972,6 +2010,8 @@ class State:
                 rows = d["bonds"].astype(BOND_DTYPE)
                 rows["flags"] |= np.where(d["bonds_broken"], L.BOND_BROKEN, 0).astype(np.uint32)
                 st.set_bonds(rows, int(d["bond_iterations"][0]))
+            if "bend_solver" in d.files and int(d["bend_solver"][0]) == L.BEND_SOLVER_COLOURED:
+                st.set_bend_solver("coloured")                     # (before the bends: their tables are built once; no key: Jacobi)
             if "bends" in d.files:                                 # (after the uids they name)
                 st.set_bends(d["bends"].astype(BEND_DTYPE), int(d["bend_iterations"][0]))
             if "areas" in d.files:                                 # (after the uids they name)

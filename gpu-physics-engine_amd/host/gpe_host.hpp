@@ -444,6 +444,25 @@ class ParticleSystem {
         ctx_->call(gpe_get_bends_info(ctx_->raw(), &info));
         return info;
     }
+    // the bends' solver: Jacobi (the default) or graph-coloured Gauss-Seidel, which holds short stiff pieces (grass,
+    // hinges, folds) at stiffness 1; no gain on long chains.  Step state, independent of set_bends: it outlives it.
+    void set_bend_solver(bool coloured)
+    {
+        ctx_->call(gpe_set_bend_solver(ctx_->raw(), coloured ? GPE_BEND_SOLVER_COLOURED : GPE_BEND_SOLVER_JACOBI));
+    }
+    bool bend_solver_coloured() const
+    {
+        uint32_t mode = GPE_BEND_SOLVER_JACOBI;
+        ctx_->call(gpe_get_bend_solver(ctx_->raw(), &mode));
+        return mode == GPE_BEND_SOLVER_COLOURED;
+    }
+    gpe_bend_solver_info bend_solver_info() const
+    {
+        gpe_bend_solver_info info{};
+        info.struct_size = sizeof(info);
+        ctx_->call(gpe_get_bend_solver_info(ctx_->raw(), &info));
+        return info;
+    }
     // not in the reference: area constraints (include/gpe.h): closed loops of particles named by uid, in order around a
     // polygon, that keep a signed rest area; relaxed on the device after every step of gpe_step / gpe_run, behind the
     // bends and in front of the bonds.  Step state: a snapshot keeps the set, its members and its relaxation count.
